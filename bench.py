@@ -8,8 +8,17 @@ utterances (998 000 frames) resident in HBM; one "step" = one pass of the whole 
 independent utterance shards (weak scaling, no data-path collective; torch.distributed is used
 only for the barrier and the max-over-ranks of the timing).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+  A plain run sets up, settles, warms up, times the K steps and prints the line (metric, value, ms_per_step, config).
+  --full                        also measures what the headline does not need: the roofline (per-kernel times from a
+                                profiled pass of K more steps after the timed ones, HBM traffic from two rocprofv3 child
+                                runs at N = 1) and the CPU baseline on rank 0 (--no-cpu-baseline / --no-live-traffic
+                                switch those two off again)
+  --dump-outputs DIR            after the timed steps, writes the features of the last timed step as DIR/features.npy
+                                (float32 [rows][width]) with the row numbers as DIR/features_rows.npy (float64); an output
+                                above the size cap is sampled by a fixed seed (the same rows on every run)
 
   --workload C2|C3|C4|C5|R|T   (R = the reference main()'s own defaults, ASR_OCL.cpp:560: 15 banks, 12 MFCC + c0, CVN)
   --scaling weak|strong         weak (default): every rank runs the workload's utterance count; strong: ONE job of
@@ -34,6 +43,8 @@ import __graft_entry__ as G  # noqa: E402
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s (spec)
 FP32_PEAK_TFLOPS = 157.3
 RCCL_PROBE_TIMEOUT_S = 60   # --collective rccl: a slow bring-up must not eat the driver's time limit
+DUMP_BYTES = 48000000       # --dump-outputs: cap on the bytes written (features + row numbers, all ranks together)
+DUMP_SEED = 0x5EED
 
 # What the counters say limits each front-end kernel, and the committed profile the reading comes from (DESIGN.md
 # section 7).  roofline.bound stays the contract's nominal bound for this path ("hbm"); a kernel without a collected
@@ -328,6 +339,26 @@ def measure_traffic_live(argv_tail, timeout_s=75):
     return res or None
 
 
+def dump_rows(total_rows, width, world, seed=DUMP_SEED):
+    """Which output rows --dump-outputs writes: all of them when they fit this rank's share of DUMP_BYTES (4 B per value,
+    8 B per row number), else a sorted sample drawn with a fixed seed -- the same rows on every run of the same arguments."""
+    k = DUMP_BYTES // world // (4 * width + 8)
+    if total_rows <= k:
+        return np.arange(total_rows, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(total_rows, size=k, replace=False)).astype(np.int64)
+
+
+def dump_outputs(torch, out_dir, out, total_rows, rank, world):
+    """DIR/features.npy: the rows of `out` chosen by dump_rows (float32), DIR/features_rows.npy: their row numbers (float64).
+    With N > 1 every rank writes its own pair, suffixed _rank<r>."""
+    os.makedirs(out_dir, exist_ok=True)
+    idx = dump_rows(total_rows, out.shape[1], world)
+    sel = out.index_select(0, torch.as_tensor(idx, device=out.device)).cpu().numpy().astype(np.float32, copy=False)
+    tag = "" if world == 1 else "_rank%d" % rank
+    np.save(os.path.join(out_dir, "features%s.npy" % tag), sel)
+    np.save(os.path.join(out_dir, "features_rows%s.npy" % tag), idx.astype(np.float64))
+
+
 def wl_frames(wl):
     per = (wl["utt_samples"] - (wl["W"] - wl["S"])) // wl["S"]
     return per * wl["n_utt"]
@@ -383,6 +414,11 @@ def build_parser():
                     help="strong: one job of the workload's n_utt_total utterances sharded round-robin over the ranks")
     ap.add_argument("--collective", default="gloo", choices=["gloo", "rccl"],
                     help="N > 1: what carries the barrier and the max-over-ranks (no collective is on the data path)")
+    ap.add_argument("--full", action="store_true",
+                    help="also report the roofline (profiled pass after the timed steps, live HBM traffic) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's features (a seeded sample of rows above %d MB) as DIR/*.npy"
+                         % (DUMP_BYTES // 1000000))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="take roofline.traffic from the tracked profiles/traffic_latest.json instead of measuring it after the "
@@ -515,8 +551,6 @@ def main():
     torch.cuda.synchronize()
     if dist is not None:
         barrier()
-    m.profile_enable(True)
-    m.profile_read(reset=True)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -529,8 +563,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=device if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group_dev if backend == "nccl" else None)
         elapsed = float(t.item())
-    launches, kernel_ms = m.profile_read(reset=True)
-    m.profile_enable(False)
+    if args.dump_outputs:   # `out` still holds the last timed step's features
+        dump_outputs(torch, args.dump_outputs, out, int(total_rows), rank, world)
 
     frames_rank = int(total_rows)
     if dist is not None:   # strong scaling: the shards differ by one utterance at most, the total is the sum over ranks
@@ -542,85 +576,97 @@ def main():
     ms_per_step = 1e3 * elapsed / args.steps
     value = frames_all / (elapsed / args.steps)
 
-    # ---- roofline of the dominant kernel (HIP events on the handle's stream around that kernel)
-    bytes_in = 2 * S * channels
-    cols = (wl["nc"] + (1 if wl.get("c0") else 0)) if wl["nc"] > 0 else wl["nb"]
-    kname = m.dominant_kernel_name()
-    model = work_model(wl, width, channels)
-    # the front-end kernel reads each PCM sample once and writes the static coefficients once;
-    # the (small) delta kernel adds the remaining 4*2*cols B/frame of output
-    kernel_bytes_per_frame = bytes_in + 4 * cols
-    path_bytes_per_frame = bytes_in + 4 * width
-    avg_kernel_ms = kernel_ms / max(launches, 1)
-    launches_per_step = max(launches, 1) / args.steps
-    achieved = (kernel_bytes_per_frame * frames_rank / launches_per_step) / (avg_kernel_ms * 1e-3) / 1e9 if avg_kernel_ms > 0 else 0.0
-    # HBM bytes per launch from the PMC passes (FETCH_SIZE / WRITE_SIZE, collected in their own rocprofv3 --pmc runs of
-    # this same command and corrected as MI355X_MICROARCH.md prescribes): NOT measured in this run -- read from the
-    # tracked profiles/traffic_latest.json, per workload and kernel, and labelled so
-    traffic, traffic_source, step_traffic = None, None, None
-    live = None
-    if (world == 1 and not args.no_live_traffic and not args.no_cpu_baseline and os.environ.get("MFX_BENCH_LIVE_TRAFFIC", "1") != "0"):
-        # (the full default line only: A/B loops, profiler runs and the multi-rank path keep the tracked file)
-        tail = ["--workload", args.workload, "--engine", str(args.engine), "--tail-split", str(args.tail_split)]
-        live = measure_traffic_live(tail)
-    if live and kname in live:
-        front = max(live[kname]["launches"], 1)
-        traffic = live[kname]["total"]
-        traffic_source = ("measured in this run, after the timed region: two child runs of this command (3 steps) under "
-                          "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (x2 / x1, KiB; MI355X_MICROARCH.md), per launch")
-        step_traffic = {"bytes_per_step": sum(v["total"] * v["launches"] / front for v in live.values()),
-                        "kernels": {k: v["total"] for k, v in live.items()}, "source": traffic_source}
-    tpath = os.path.join(ROOT, "profiles", "traffic_latest.json")
-    if traffic is None and os.path.exists(tpath):
-        try:
-            tj = json.load(open(tpath))
-            ent = tj.get(args.workload) if isinstance(tj.get(args.workload), dict) else tj
-            if ent.get("workload", args.workload) == args.workload and ent.get("kernel") == kname:
-                traffic = ent.get("hbm_bytes_per_launch")
-                traffic_source = "profiles/traffic_latest.json (%s)" % ent.get("source", "rocprofv3 --pmc passes")
-                # every kernel of the step (front end + delta (+ normaliser)): counter bytes per launch x launches per step
-                sk = ent.get("step_kernels")
-                if isinstance(sk, dict) and sk:
-                    step_traffic = {"bytes_per_step": sum(v["hbm_bytes_per_launch"] * v.get("launches_per_step", 1) for v in sk.values()),
-                                    "kernels": {k: v["hbm_bytes_per_launch"] for k, v in sk.items()},
-                                    "source": traffic_source}
-        except Exception:
-            traffic = None
-    frames_per_launch = frames_rank / launches_per_step
-    kernel_tflops = model["flops_front"] * frames_per_launch / (avg_kernel_ms * 1e-3) / 1e12 if avg_kernel_ms > 0 else 0.0
-    path_tflops = model["flops"] * frames_rank / (ms_per_step * 1e-3) / 1e12
-    staged_gbs = model["staged_bytes"] * frames_rank / (ms_per_step * 1e-3) / 1e9
-    roofline = {
-        # `achieved` / `peak` / `frac` price the dominant kernel against HBM (the contract's nominal bound for this path).
-        # What the counters say limits it is vector-instruction issue + dependent LDS round trips:
-        # fully fused, the path has ~32 flop/B against a machine balance of ~20 flop/B, so 60 % of the HBM roofline
-        # would need ~100 % of the FP32 vector peak.  Both fractions are reported.
-        "bound": "hbm",
-        "bound_diagnosed": ({"label": BOUND_DIAGNOSED[kname][0], "source": BOUND_DIAGNOSED[kname][1]}
-                            if kname in BOUND_DIAGNOSED else None),
-        "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-        "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
-        "kernel": kname, "kernel_avg_ms": avg_kernel_ms, "kernel_launches_per_step": launches_per_step,
-        "algorithmic_bytes_per_frame": kernel_bytes_per_frame,
-        "flops_per_frame": model["flops"], "kernel_flops_per_frame": model["flops_front"],
-        "achieved_tflops": kernel_tflops, "peak_fp32_tflops": FP32_PEAK_TFLOPS,
-        "frac_fp32_peak": kernel_tflops / FP32_PEAK_TFLOPS,
-        "arithmetic_intensity_flop_per_byte": model["flops"] / model["fused_bytes"],
-        "machine_balance_flop_per_byte": FP32_PEAK_TFLOPS * 1e12 / (HBM_PEAK_GBS * 1e9),
-        "staged_bytes_per_frame": model["staged_bytes"],
-        "staged_pipeline_equivalent": {"achieved": staged_gbs, "frac": staged_gbs / HBM_PEAK_GBS,
-                                       "what": "HBM bytes a one-kernel-per-reference-stage pipeline would move per "
-                                               "frame x this run's frame rate (diagnostic, not traffic)"},
-        "whole_path": {"bytes_per_frame": path_bytes_per_frame,
-                       "achieved": path_bytes_per_frame * frames_rank / (ms_per_step * 1e-3) / 1e9,
-                       "frac": path_bytes_per_frame * frames_rank / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                       "achieved_tflops": path_tflops, "frac_fp32_peak": path_tflops / FP32_PEAK_TFLOPS,
-                       # counter bytes of ALL kernels of a step against the algorithmic bytes of the step
-                       "traffic": step_traffic["bytes_per_step"] if step_traffic else None,
-                       "traffic_kernels": step_traffic["kernels"] if step_traffic else None,
-                       "traffic_over_algorithmic": (step_traffic["bytes_per_step"] / (path_bytes_per_frame * frames_rank)
-                                                    if step_traffic else None)},
-    }
+    roofline = None
+    if args.full:
+        # ---- per-kernel times: a profiled pass of as many steps again, after the timed ones (HIP events on the handle's
+        # stream around every kernel; kept out of the timed region, whose figure they would otherwise enter)
+        m.profile_enable(True)
+        m.profile_read(reset=True)
+        for _ in range(args.steps):
+            step()
+        m.synchronize()
+        launches, kernel_ms = m.profile_read(reset=True)
+        m.profile_enable(False)
+
+        # ---- roofline of the dominant kernel
+        bytes_in = 2 * S * channels
+        cols = (wl["nc"] + (1 if wl.get("c0") else 0)) if wl["nc"] > 0 else wl["nb"]
+        kname = m.dominant_kernel_name()
+        model = work_model(wl, width, channels)
+        # the front-end kernel reads each PCM sample once and writes the static coefficients once;
+        # the (small) delta kernel adds the remaining 4*2*cols B/frame of output
+        kernel_bytes_per_frame = bytes_in + 4 * cols
+        path_bytes_per_frame = bytes_in + 4 * width
+        avg_kernel_ms = kernel_ms / max(launches, 1)
+        launches_per_step = max(launches, 1) / args.steps
+        achieved = (kernel_bytes_per_frame * frames_rank / launches_per_step) / (avg_kernel_ms * 1e-3) / 1e9 if avg_kernel_ms > 0 else 0.0
+        # HBM bytes per launch from the PMC passes (FETCH_SIZE / WRITE_SIZE, collected in their own rocprofv3 --pmc runs of
+        # this same command, with the gfx950 counter corrections of tools/pmc_run.sh): measured live at N = 1 unless switched
+        # off, else read from the tracked profiles/traffic_latest.json, per workload and kernel, and labelled so
+        traffic, traffic_source, step_traffic = None, None, None
+        live = None
+        if (world == 1 and not args.no_live_traffic and not args.no_cpu_baseline and os.environ.get("MFX_BENCH_LIVE_TRAFFIC", "1") != "0"):
+            # (--full with the CPU baseline only: A/B loops, profiler runs and the multi-rank path keep the tracked file)
+            tail = ["--workload", args.workload, "--engine", str(args.engine), "--tail-split", str(args.tail_split)]
+            live = measure_traffic_live(tail)
+        if live and kname in live:
+            front = max(live[kname]["launches"], 1)
+            traffic = live[kname]["total"]
+            traffic_source = ("measured in this run, after the timed region: two child runs of this command (3 steps) under "
+                              "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (x2 / x1, KiB), per launch")
+            step_traffic = {"bytes_per_step": sum(v["total"] * v["launches"] / front for v in live.values()),
+                            "kernels": {k: v["total"] for k, v in live.items()}, "source": traffic_source}
+        tpath = os.path.join(ROOT, "profiles", "traffic_latest.json")
+        if traffic is None and os.path.exists(tpath):
+            try:
+                tj = json.load(open(tpath))
+                ent = tj.get(args.workload) if isinstance(tj.get(args.workload), dict) else tj
+                if ent.get("workload", args.workload) == args.workload and ent.get("kernel") == kname:
+                    traffic = ent.get("hbm_bytes_per_launch")
+                    traffic_source = "profiles/traffic_latest.json (%s)" % ent.get("source", "rocprofv3 --pmc passes")
+                    # every kernel of the step (front end + delta (+ normaliser)): counter bytes per launch x launches per step
+                    sk = ent.get("step_kernels")
+                    if isinstance(sk, dict) and sk:
+                        step_traffic = {"bytes_per_step": sum(v["hbm_bytes_per_launch"] * v.get("launches_per_step", 1) for v in sk.values()),
+                                        "kernels": {k: v["hbm_bytes_per_launch"] for k, v in sk.items()},
+                                        "source": traffic_source}
+            except Exception:
+                traffic = None
+        frames_per_launch = frames_rank / launches_per_step
+        kernel_tflops = model["flops_front"] * frames_per_launch / (avg_kernel_ms * 1e-3) / 1e12 if avg_kernel_ms > 0 else 0.0
+        path_tflops = model["flops"] * frames_rank / (ms_per_step * 1e-3) / 1e12
+        staged_gbs = model["staged_bytes"] * frames_rank / (ms_per_step * 1e-3) / 1e9
+        roofline = {
+            # `achieved` / `peak` / `frac` price the dominant kernel against HBM (the contract's nominal bound for this path).
+            # What the counters say limits it is vector-instruction issue + dependent LDS round trips:
+            # fully fused, the path has ~32 flop/B against a machine balance of ~20 flop/B, so 60 % of the HBM roofline
+            # would need ~100 % of the FP32 vector peak.  Both fractions are reported.
+            "bound": "hbm",
+            "bound_diagnosed": ({"label": BOUND_DIAGNOSED[kname][0], "source": BOUND_DIAGNOSED[kname][1]}
+                                if kname in BOUND_DIAGNOSED else None),
+            "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
+            "kernel": kname, "kernel_avg_ms": avg_kernel_ms, "kernel_launches_per_step": launches_per_step,
+            "algorithmic_bytes_per_frame": kernel_bytes_per_frame,
+            "flops_per_frame": model["flops"], "kernel_flops_per_frame": model["flops_front"],
+            "achieved_tflops": kernel_tflops, "peak_fp32_tflops": FP32_PEAK_TFLOPS,
+            "frac_fp32_peak": kernel_tflops / FP32_PEAK_TFLOPS,
+            "arithmetic_intensity_flop_per_byte": model["flops"] / model["fused_bytes"],
+            "machine_balance_flop_per_byte": FP32_PEAK_TFLOPS * 1e12 / (HBM_PEAK_GBS * 1e9),
+            "staged_bytes_per_frame": model["staged_bytes"],
+            "staged_pipeline_equivalent": {"achieved": staged_gbs, "frac": staged_gbs / HBM_PEAK_GBS,
+                                           "what": "HBM bytes a one-kernel-per-reference-stage pipeline would move per "
+                                                   "frame x this run's frame rate (diagnostic, not traffic)"},
+            "whole_path": {"bytes_per_frame": path_bytes_per_frame,
+                           "achieved": path_bytes_per_frame * frames_rank / (ms_per_step * 1e-3) / 1e9,
+                           "frac": path_bytes_per_frame * frames_rank / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                           "achieved_tflops": path_tflops, "frac_fp32_peak": path_tflops / FP32_PEAK_TFLOPS,
+                           # counter bytes of ALL kernels of a step against the algorithmic bytes of the step
+                           "traffic": step_traffic["bytes_per_step"] if step_traffic else None,
+                           "traffic_kernels": step_traffic["kernels"] if step_traffic else None,
+                           "traffic_over_algorithmic": (step_traffic["bytes_per_step"] / (path_bytes_per_frame * frames_rank)
+                                                        if step_traffic else None)},
+        }
 
     result = {
         "metric": "audio frames/sec (16 kHz, 25 ms/10 ms, 512-pt FFT, 40 mel, 13 MFCC + delta + delta-delta)"
@@ -638,10 +684,11 @@ def main():
                    "sharding": "round-robin utterance shards (rank r owns r, r + N, ...), no collective" if strong
                                else "independent utterance shards per rank, no collective",
                    "step_pipelining": "delta tail of step i overlaps front end of step i+1" if args.overlap else "off"},
-        "roofline": roofline,
     }
+    if roofline is not None:
+        result["roofline"] = roofline
 
-    if rank == 0 and not args.no_cpu_baseline:   # rank 0 only, the same bounded sample at every N
+    if rank == 0 and args.full and not args.no_cpu_baseline:   # rank 0 only, the same bounded sample at every N
         orc = G.load_oracle()
         n_host = min(n_utt_rank, 512)
         pcm_host = pcm[:n_host].cpu().numpy()

@@ -21,6 +21,9 @@ Files
                            calls pick the FLOAT overloads -- the selection the reference's own toolchain (MSVC) makes.  The
                            checker's DEFAULT binding is bit-identical to these, MINMAX included; the HIP path is compared
                            with them.
+  ref_objects_random.npz   outputs of the same reference objects on the seeded inputs of
+                           tests/test_oracle.py::test_live_reference_objects_random (delta, CMN / CVN, segmenter counts
+                           and frames), so that the test runs where oracle/_ref cannot be built.
   c1_a0001_oracle.npz      features of BASELINE config C1 (a0001.wav, 26 mel, 13 MFCC + d + dd)
                            from this repo's oracle (oracle/mfcc_oracle.c).  NOT reference output:
                            mfcccpu.cpp needs libfftw3f and cannot be built here, and the reference
@@ -129,6 +132,16 @@ def ref_stage_vectors():
     print("wrote ref_stage_vectors.npz with", len(out), "arrays")
 
 
+def ref_objects_random():
+    sys.path.insert(0, os.path.dirname(HERE))
+    import test_oracle
+    got, ref = test_oracle.objects_random(O, O.ref())
+    for k in got:
+        assert np.array_equal(got[k], ref[k]), k
+    np.savez_compressed(os.path.join(HERE, "ref_objects_random.npz"), **ref)
+    print("wrote ref_objects_random.npz with", len(ref), "arrays")
+
+
 def c1_oracle():
     pcm, sr = O.read_wav_pcm16(os.path.join(HERE, "a0001.wav"))
     pcm = pcm[:, 0]
@@ -195,6 +208,7 @@ if __name__ == "__main__":
         print("oracle/_ref/libref_mfcccpu.so missing: ref_mfcccpu_vectors.npz not regenerated")
     if O.ref_available():
         ref_stage_vectors()
+        ref_objects_random()
     else:
-        print("oracle/_ref missing: ref_stage_vectors.npz not regenerated")
+        print("oracle/_ref missing: ref_stage_vectors.npz, ref_objects_random.npz not regenerated")
     c1_oracle()

@@ -470,6 +470,21 @@ def test_bench_work_model_matches_survey_8d():
     assert c2["flops"] / c2["fused_bytes"] > B.FP32_PEAK_TFLOPS * 1e12 / (B.HBM_PEAK_GBS * 1e9)
 
 
+def test_bench_dump_rows_fixed_and_capped():
+    """--dump-outputs: every row when the output fits the cap, else a sorted sample drawn with a fixed seed -- the same rows
+    on every run, within DUMP_BYTES over all ranks, and the options exist with --full off by default."""
+    B = _import_bench()
+    assert np.array_equal(B.dump_rows(1000, 39, 1), np.arange(1000))
+    a, b = B.dump_rows(998000, 39, 1), B.dump_rows(998000, 39, 1)
+    assert np.array_equal(a, b) and np.all(np.diff(a) > 0) and a[-1] < 998000
+    assert a.size * (4 * 39 + 8) <= B.DUMP_BYTES < (a.size + 1) * (4 * 39 + 8)
+    assert 2 * B.dump_rows(998000, 39, 2).size * (4 * 39 + 8) <= B.DUMP_BYTES <= 64 * 10 ** 6
+    ap = B.build_parser()
+    d = ap.parse_args([])
+    assert d.full is False and d.dump_outputs is None
+    assert ap.parse_args(["--full", "--dump-outputs", "x"]).dump_outputs == "x"
+
+
 def test_bench_plan_job_weak_and_strong(pkg):
     B = _import_bench()
     sh = pkg.sharding

@@ -126,54 +126,85 @@ def test_base_arithmetic_matches_reference_vectors(orc, pkg, vec):
             assert pkg.host_frame_count(s, W, S) == e
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(os.path.dirname(GOLDEN), "..", "oracle", "_ref", "libref_stages.so")),
-                    reason="oracle/_ref not built (needs /root/reference)")
-def test_live_reference_objects_random(orc):
-    """Same comparisons on fresh random inputs against the loaded reference objects."""
-    R = orc.ref()
+def objects_random(orc, R=None, rec=None):
+    """Fresh seeded inputs through the checker and, given R (oracle/_ref/libref_stages.so), through the reference objects
+    beside it: (checker outputs, reference outputs or None), dicts keyed alike.  Without R the segmenter's count of new
+    frames comes from `rec`, the recording of the reference side (tests/golden/ref_objects_random.npz, written by
+    tests/golden/make_golden.py)."""
     L = orc.lib()
     rng = np.random.default_rng(99)
+    got, ref = {}, ({} if R is not None else None)
     for trial in range(5):
         dim, wc, Ld = int(rng.integers(1, 50)), int(rng.integers(1, 80)), int(rng.integers(1, 5))
         x = (rng.standard_normal((wc + 2 * Ld, dim)) * 20).astype(np.float32)
-        d = R.ref_delta_new(dim, wc + 2, Ld)
-        R.ref_delta_apply(d, fp(x), wc)
-        want = np.ctypeslib.as_array(R.ref_delta_output(d), shape=(wc * dim,)).reshape(wc, dim).copy()
-        R.ref_delta_free(d)
-        got = np.zeros_like(want)
-        L.orc_delta_apply(fp(x), dim, wc, Ld, fp(got))
-        assert np.array_equal(got, want)
+        if R is not None:
+            d = R.ref_delta_new(dim, wc + 2, Ld)
+            R.ref_delta_apply(d, fp(x), wc)
+            ref["delta_%d" % trial] = np.ctypeslib.as_array(R.ref_delta_output(d), shape=(wc * dim,)).reshape(wc, dim).copy()
+            R.ref_delta_free(d)
+        g = np.zeros((wc, dim), np.float32)
+        L.orc_delta_apply(fp(x), dim, wc, Ld, fp(g))
+        got["delta_%d" % trial] = g
         for nt in (1, 2):
             y = (rng.standard_normal((wc + 5, dim)) * 3 - 1).astype(np.float32)
             a, b = y.copy(), y.copy()
-            nz = R.ref_norm_new(nt, dim)
-            R.ref_norm_normalize(nz, fp(a), wc + 5, 0)
-            R.ref_norm_free(nz)
+            if R is not None:
+                nz = R.ref_norm_new(nt, dim)
+                R.ref_norm_normalize(nz, fp(a), wc + 5, 0)
+                R.ref_norm_free(nz)
+                ref["norm%d_%d" % (nt, trial)] = a
             mean, var, mm = (np.zeros(dim, np.float32) for _ in range(3))
             L.orc_normalize(nt, fp(b), dim, wc + 5, 0, fp(mean), fp(var), fp(mm))
-            assert np.array_equal(a, b)
+            got["norm%d_%d" % (nt, trial)] = b
     # segmenter: random block sizes, both objects side by side
     W, S, D, wl = 400, 160, 6, 60
     window = orc.reference_window(W)
-    seg = R.ref_seg_new(W, S, wl, D)
-    R.ref_seg_set_window(seg, fp(window))
+    if R is not None:
+        seg = R.ref_seg_new(W, S, wl, D)
+        R.ref_seg_set_window(seg, fp(window))
     iwl = wl - 2 - 3 * D
     o = orc.OracleMfcc(orc.make_config(iwl * S + W - S, num_banks=26, ceps_len=13), window)
     data = np.zeros((wl, 512), np.float32)
     for i in range(12):
         b = int(rng.integers(1300 if i == 0 else 1, o.input_buffer_size))
         pcm = rng.integers(-32768, 32767, size=b, dtype=np.int16)
-        wc, wcnd = C.c_int(0), C.c_int(0)
-        rc = R.ref_seg_set_input(seg, sp(pcm), fp(data), b, C.byref(wc), C.byref(wcnd))
-        assert rc == 0
+        if R is not None:
+            wc, wcnd = C.c_int(0), C.c_int(0)
+            rc = R.ref_seg_set_input(seg, sp(pcm), fp(data), b, C.byref(wc), C.byref(wcnd))
+            assert rc == 0
+            ref["seg_wc_%d" % i] = np.array([wc.value], np.int64)
+            ref["seg_wcnd_%d" % i] = np.array([wcnd.value], np.int64)
+            nd = wcnd.value
+        else:
+            nd = int(rec["seg_wcnd_%d" % i][0])
         n = o.set_input(pcm)
-        assert n == wc.value
+        got["seg_wc_%d" % i] = np.array([n], np.int64)
         if n > 0:
-            assert np.array_equal(o.tap("frames", wcnd.value)[:, :W], data[:wcnd.value, :W])
-    wc, wcnd = C.c_int(0), C.c_int(0)
-    R.ref_seg_flush(seg, fp(data), C.byref(wc), C.byref(wcnd))
-    assert o.flush() == max(wc.value, 0)
-    R.ref_seg_free(seg)
+            got["seg_frames_%d" % i] = o.tap("frames", nd)[:, :W]
+            if R is not None:
+                ref["seg_frames_%d" % i] = data[:nd, :W].copy()
+    got["seg_flush"] = np.array([o.flush()], np.int64)
+    if R is not None:
+        wc, wcnd = C.c_int(0), C.c_int(0)
+        R.ref_seg_flush(seg, fp(data), C.byref(wc), C.byref(wcnd))
+        ref["seg_flush"] = np.array([max(wc.value, 0)], np.int64)
+        R.ref_seg_free(seg)
+    return got, ref
+
+
+def test_live_reference_objects_random(orc):
+    """Same comparisons on fresh random inputs: against the recorded outputs of the reference objects on them
+    (tests/golden/ref_objects_random.npz) always, and against the objects themselves when oracle/_ref is built."""
+    rec = np.load(os.path.join(GOLDEN, "ref_objects_random.npz"))
+    R = orc.ref() if orc.ref_available() else None
+    got, ref = objects_random(orc, R, rec)
+    if ref is not None:   # the live objects reproduce the recording
+        assert sorted(ref) == sorted(rec.files)
+        for k in ref:
+            assert np.array_equal(ref[k], rec[k]), k
+    assert sorted(got) == sorted(k for k in rec.files if not k.startswith("seg_wcnd_"))
+    for k in got:
+        assert np.array_equal(got[k], rec[k]), k
 
 
 # ---------------------------------------------------------------------------------------------

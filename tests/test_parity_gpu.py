@@ -880,7 +880,7 @@ def test_bench_two_rank_launch_path(tmp_path):
     env = dict(os.environ, MFX_BENCH_DEVICE="0", MFX_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
                         "--master-addr", "127.0.0.1", "--master-port", "29547", os.path.join(root, "bench.py"),
-                        "--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", "T", "--no-cpu-baseline"],
+                        "--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", "T", "--full", "--no-cpu-baseline"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -1246,7 +1246,7 @@ def test_bench_self_launch_two_ranks_strong_scaling():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(MFX_BENCH_DEVICE="0", MFX_BENCH_BACKEND="gloo")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--settle-ms", "5", "--workload", "T", "--scaling", "strong"],
+                        "--settle-ms", "5", "--workload", "T", "--scaling", "strong", "--full"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
@@ -1259,7 +1259,7 @@ def test_bench_self_launch_two_ranks_strong_scaling():
 
 
 def test_bench_measures_hbm_traffic_in_the_run():
-    """Round 4: the default line's roofline.traffic is MEASURED by bench.py itself -- two child runs of the same command under
+    """Round 4: the --full line's roofline.traffic is MEASURED by bench.py itself -- two child runs of the same command under
     `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` after the timed region -- not copied from a tracked file; the whole step's
     counter bytes stand beside its algorithmic bytes.  (Tiny workload here: the figures are launch overheads, the plumbing is
     what is checked.)"""
@@ -1273,7 +1273,7 @@ def test_bench_measures_hbm_traffic_in_the_run():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MFX_BENCH_LIVE_TRAFFIC")}
     env["MFX_CPU_THREADS"] = "2"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--settle-ms", "5",
-                        "--workload", "T"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+                        "--workload", "T", "--full"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     rf = d["roofline"]
@@ -1342,12 +1342,42 @@ def test_bench_reference_defaults_workload_runs_the_normaliser():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--settle-ms", "5",
-                        "--workload", "R", "--no-cpu-baseline"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                        "--workload", "R", "--full", "--no-cpu-baseline"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                        timeout=600)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert d["config"]["frames_per_step"] == 998000 and "CVN" in d["config"]["workload"]
     assert d["roofline"]["algorithmic_bytes_per_frame"] == 320 + 52
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run prints the headline (metric, value, unit, higher_is_better, dtype, ms_per_step) and nothing that
+    needs runs of its own (no roofline, no CPU baseline: those are --full); --dump-outputs writes the last timed step's
+    features, and two runs with the same arguments write the same arrays."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    got = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "1", "--settle-ms", "5",
+                            "--workload", "T", "--dump-outputs", str(tmp_path / run)], env=env, stdout=subprocess.PIPE,
+                           stderr=subprocess.PIPE, text=True, timeout=300)
+        assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 4 and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert abs(d["value"] - 8 * 98 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+        assert "roofline" not in d and "cpu_baseline" not in d
+        f = np.load(tmp_path / run / "features.npy")
+        rows = np.load(tmp_path / run / "features_rows.npy")
+        assert f.dtype == np.float32 and rows.dtype == np.float64
+        assert f.shape == (8 * 98, 39) and np.array_equal(rows, np.arange(8 * 98)) and np.isfinite(f).all()
+        assert np.abs(f).max() > 0
+        got.append(f)
+    assert np.array_equal(got[0], got[1])
 
 
 # ---------------------------------------------------------------------------------------------

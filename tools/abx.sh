@@ -2,6 +2,7 @@
 # dev aid (GPU box): kernel time of several variant libraries in ONE call, interleaved twice (same box, same thermal state)
 #   tools/abx.sh name1 name2 ...     (names under build/var/lib_<name>.so; "shipped" = the in-tree library)
 mkdir -p gpurun_out/abx
+ABX_ARGS="--full ${ABX_ARGS:-}"   # roofline.kernel_avg_ms below is a --full figure
 for rep in 1 2; do
 for n in "$@"; do
     lib=build/var/lib_$n.so; [ "$n" = shipped ] && lib=""

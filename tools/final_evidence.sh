@@ -31,7 +31,7 @@ if has c2; then
   stats C2 --steps 500 --warmup 50 || exit 1
   tools/pmc_run.sh "$TAG/pmc_C2" > "$O/pmc_C2_stdout.log" 2>&1 || exit 1
   merge_traffic C2 "$O/pmc_C2/traffic.json"
-  timeout -k 10 400 python3 bench.py > "$O/bench_C2_default.json" 2> "$O/bench_C2_default.err" || exit 1
+  timeout -k 10 400 python3 bench.py --full > "$O/bench_C2_default.json" 2> "$O/bench_C2_default.err" || exit 1
   timeout -k 10 200 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$O/bench_C2_steps20_warmup5.json" 2>> "$O/bench_C2_default.err" || exit 1
   tail -c 900 "$O/bench_C2_default.json"; echo; head -3 "$O/C2_kernel_stats.csv" | cut -c1-150
 fi
@@ -41,7 +41,7 @@ for w in C3 C5 R; do
     stats $w --workload $w --steps 100 --warmup 20 || exit 1
     tools/pmc_run.sh "$TAG/pmc_$w" --workload $w > "$O/pmc_${w}_stdout.log" 2>&1 || exit 1
     merge_traffic $w "$O/pmc_$w/traffic.json"
-    timeout -k 10 400 python3 bench.py --workload $w --steps 100 --warmup 20 > "$O/bench_$w.json" 2> "$O/bench_$w.err" || exit 1
+    timeout -k 10 400 python3 bench.py --full --workload $w --steps 100 --warmup 20 > "$O/bench_$w.json" 2> "$O/bench_$w.err" || exit 1
     python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(sys.argv[2], d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline']['traffic'], d.get('cpu_baseline',{}).get('value'))" "$O/bench_$w.json" $w
   fi
 done
