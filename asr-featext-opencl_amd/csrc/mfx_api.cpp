@@ -118,7 +118,6 @@ struct mfx_handle {
     bool flushed = true, last_calc_flushed = false, last_block = false;
     int block_wcnd = 0;      // frames (with context) the last FFT covered
     int block_frames = 0;    // frames apply() delivers
-    bool block_applied = false;
     DevBuf<float> d_spec, d_src, d_blk, d_stats_stream;
     DevBuf<Chunk> d_chunks_stream;
     int stream_chunk_frames = 16;
@@ -131,12 +130,15 @@ struct mfx_handle {
     size_t stage_tail_off = 0;  // samples: where the pending tail (h->remaining samples) starts in h_stage
     float *h_out_stage = nullptr;         // pinned staging of get_output_data (allocated on first use)
     size_t h_out_stage_n = 0;
-    bool rows_in_stage = false;           // the current block's rows were written straight into h_out_stage by the delta kernel
+    bool rows_in_stage = false;           // the current block's PLAIN rows were written straight into h_out_stage by the delta
+                                          // kernel (set by a plain apply only; cleared by set_input and flush)
+    float *h_alpha_stage = nullptr;       // pinned staging of get_output_data_alpha: never h_out_stage, which may hold the
+    size_t h_alpha_stage_n = 0;           // plain rows a later get_output_data returns
     hipEvent_t ev_copy[16] = {};          // chunk events of the pipelined device-to-host copy
     // VTLN sweep (mfx_apply_alphas): one filterbank, one static and one output block per alpha
     std::vector<float> sweep_alphas;      // alphas of the tables currently in d_sweep_w
     int sweep_cap = 0;                    // alphas the sweep buffers hold
-    int sweep_n = 0;                      // alphas of the last sweep (0: last apply was a plain one)
+    int sweep_n = 0;                      // alphas of the current block's last sweep (0: none since set_input / flush)
     DevBuf<float> d_sweep_w, d_sweep_src, d_sweep_blk, d_sweep_stats;
     DevBuf<int32_t> d_sweep_beg;
     DevBuf<Segment> d_sweep_segs;         // [2][sweep_cap]: rows with context, rows delivered
@@ -532,6 +534,7 @@ extern "C" void mfx_destroy(mfx_handle *h)
     }
     if (h->h_stage) (void)hipHostFree(h->h_stage);
     if (h->h_out_stage) (void)hipHostFree(h->h_out_stage);
+    if (h->h_alpha_stage) (void)hipHostFree(h->h_alpha_stage);
     if (h->stream_up) (void)hipStreamDestroy(h->stream_up);
     if (h->stream_dn) (void)hipStreamDestroy(h->stream_dn);
     for (int i = 0; i < 16; ++i) {
@@ -1048,8 +1051,9 @@ int upload_block(mfx_handle *h, int16_t *d_dst, const int16_t *src, size_t sampl
     return MFX_OK;
 }
 
-// device rows -> host, returns when `dst` holds them
-int download_rows(mfx_handle *h, float *dst, const float *d_src, size_t count)
+// device rows -> host, returns when `dst` holds them; `stage_buf` / `stage_n`: the pinned staging buffer of the caller (h_out_stage
+// for the plain rows, h_alpha_stage for a sweep's), grown here when it is too small
+int download_rows(mfx_handle *h, float *dst, const float *d_src, size_t count, float *&stage_buf, size_t &stage_n)
 {
     const size_t bytes = count * sizeof(float);
     if (small_block(h, bytes)) {
@@ -1061,15 +1065,15 @@ int download_rows(mfx_handle *h, float *dst, const float *d_src, size_t count)
             HIP_TRY(h, hipStreamSynchronize(h->stream));
             return MFX_OK;
         }
-        if (h->h_out_stage_n < count + 4) {
-            if (h->h_out_stage) (void)hipHostFree(h->h_out_stage);
-            h->h_out_stage = nullptr;
-            h->h_out_stage_n = 0;
+        if (stage_n < count + 4) {
+            if (stage_buf) (void)hipHostFree(stage_buf);
+            stage_buf = nullptr;
+            stage_n = 0;
             const size_t want = std::max(count, (size_t)h->cap_rows * h->width) + 4;
-            HIP_TRY(h, hipHostMalloc((void **)&h->h_out_stage, want * sizeof(float), hipHostMallocDefault));
-            h->h_out_stage_n = want;
+            HIP_TRY(h, hipHostMalloc((void **)&stage_buf, want * sizeof(float), hipHostMallocDefault));
+            stage_n = want;
         }
-        char *stage = (char *)h->h_out_stage + ((uintptr_t)d_src & 15);
+        char *stage = (char *)stage_buf + ((uintptr_t)d_src & 15);
         HIP_TRY(h, launch_copy_small(stage, d_src, bytes, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         std::memcpy(dst, stage, bytes);
@@ -1080,13 +1084,13 @@ int download_rows(mfx_handle *h, float *dst, const float *d_src, size_t count)
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         return MFX_OK;
     }
-    if (h->h_out_stage_n < count) {
-        if (h->h_out_stage) (void)hipHostFree(h->h_out_stage);
-        h->h_out_stage = nullptr;
-        h->h_out_stage_n = 0;
+    if (stage_n < count) {
+        if (stage_buf) (void)hipHostFree(stage_buf);
+        stage_buf = nullptr;
+        stage_n = 0;
         const size_t want = std::max(count, (size_t)h->cap_rows * h->width);
-        HIP_TRY(h, hipHostMalloc((void **)&h->h_out_stage, want * sizeof(float), hipHostMallocDefault));
-        h->h_out_stage_n = want;
+        HIP_TRY(h, hipHostMalloc((void **)&stage_buf, want * sizeof(float), hipHostMallocDefault));
+        stage_n = want;
     }
     // chunks of the DMA into pinned staging, each followed by an event; the copy out of staging of chunk c runs under
     // the DMA of chunk c+1
@@ -1094,7 +1098,7 @@ int download_rows(mfx_handle *h, float *dst, const float *d_src, size_t count)
     int n = 0;
     for (size_t off = 0; off < bytes; off += chunk, ++n) {
         const size_t len = std::min(chunk, bytes - off);
-        HIP_TRY(h, hipMemcpyAsync((char *)h->h_out_stage + off, (const char *)d_src + off, len, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipMemcpyAsync((char *)stage_buf + off, (const char *)d_src + off, len, hipMemcpyDeviceToHost, h->stream));
         if (!h->ev_copy[n]) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_copy[n], hipEventDisableTiming));
         HIP_TRY(h, hipEventRecord(h->ev_copy[n], h->stream));
     }
@@ -1102,7 +1106,7 @@ int download_rows(mfx_handle *h, float *dst, const float *d_src, size_t count)
     for (size_t off = 0; off < bytes; off += chunk, ++n) {
         const size_t len = std::min(chunk, bytes - off);
         HIP_TRY(h, hipEventSynchronize(h->ev_copy[n]));
-        host_copy((char *)dst + off, (const char *)h->h_out_stage + off, len);
+        host_copy((char *)dst + off, (const char *)stage_buf + off, len);
     }
     return MFX_OK;
 }
@@ -1157,7 +1161,8 @@ extern "C" int mfx_set_input(mfx_handle *h, const int16_t *pcm, int32_t samples,
     if (samples > h->input_buffer_size) return fail(h, MFX_ERR_BUFFER_TOO_SMALL, kMsgBuffer);
     HIP_TRY(h, hipSetDevice(h->device));
     h->last_block = false; // a new stream may follow a flush (reference never resets this: DESIGN.md B7)
-    h->block_applied = false;
+    h->rows_in_stage = false;
+    h->sweep_n = 0;
     h->block_frames = 0;
 
     const int D = h->D, W = h->W, S = h->S;
@@ -1255,7 +1260,8 @@ extern "C" int mfx_flush(mfx_handle *h, int32_t *frames_out)
     HIP_TRY(h, hipSetDevice(h->device));
     h->last_block = true;
     h->flushed = true;
-    h->block_applied = false;
+    h->rows_in_stage = false;
+    h->sweep_n = 0;
     h->block_frames = 0;
     const int wcnd = estimated_window_count_f32(h->remaining, h->W, h->S);
     const int window_count = wcnd - h->D;
@@ -1469,7 +1475,9 @@ int apply_impl(mfx_handle *h, const float *alphas, int n_alpha)
     // deltas -- writes them straight into the page-locked staging buffer (posted writes over the link, consecutive
     // threads on consecutive addresses), and get_output_data has nothing to launch: one kernel and one launch less per
     // call sequence (profiles/r04/stream_small_timeline.txt).  Same kernel, same values: the same bits as through d_blk.
-    h->rows_in_stage = false;
+    // Only a plain apply (and set_input / flush) changes rows_in_stage: a sweep writes d_sweep_blk and leaves the plain
+    // rows -- in h_out_stage or in d_blk -- for get_output_data as they are.
+    if (!sweep) h->rows_in_stage = false;
     float *rows_out = d_blk;
     // (not when the rows are normalised after the deltas: the one-launch normaliser is ONE block per segment, and a
     // single CU writing 155 KB over the link takes what the copy kernel it would save takes -- measured, +- 0.5 us)
@@ -1511,8 +1519,7 @@ int apply_impl(mfx_handle *h, const float *alphas, int n_alpha)
                       (size_t)n_tab * 2 * h->cols);
         if (rc != MFX_OK) return rc;
     }
-    h->block_applied = true;
-    h->sweep_n = sweep ? n_alpha : 0;
+    if (sweep) h->sweep_n = n_alpha; // a plain apply leaves the sweep's rows readable
     return MFX_OK;
 }
 
@@ -1540,11 +1547,14 @@ extern "C" int mfx_get_output_data_alpha(mfx_handle *h, int32_t alpha_index, flo
     if (!h) return MFX_ERR_ARG;
     if (h->planning) return fail(h, MFX_ERR_DEVICE, kMsgPlanning);
     if ((!data_out && frames > 0) || frames < 0) return fail(h, MFX_ERR_ARG, "invalid argument");
+    if (h->sweep_n == 0) return fail(h, MFX_ERR_STATE, "no sweep on the current block");
     if (alpha_index < 0 || alpha_index >= h->sweep_n) return fail(h, MFX_ERR_ARG, "alpha index outside the last sweep");
     if (frames > h->cap_rows) return fail(h, MFX_ERR_WINDOW_HIGH, kMsgHigh);
     if (frames == 0) return MFX_OK;
     HIP_TRY(h, hipSetDevice(h->device));
-    return download_rows(h, data_out, h->d_sweep_blk.p + (size_t)alpha_index * h->cap_rows * h->width, (size_t)frames * h->width);
+    // (own staging buffer: h_out_stage may hold the plain rows that get_output_data returns next)
+    return download_rows(h, data_out, h->d_sweep_blk.p + (size_t)alpha_index * h->cap_rows * h->width, (size_t)frames * h->width,
+                         h->h_alpha_stage, h->h_alpha_stage_n);
 }
 
 extern "C" int mfx_get_output_data(mfx_handle *h, float *data_out, int32_t frames)
@@ -1555,12 +1565,12 @@ extern "C" int mfx_get_output_data(mfx_handle *h, float *data_out, int32_t frame
     if (frames > h->cap_rows) return fail(h, MFX_ERR_WINDOW_HIGH, kMsgHigh);
     if (frames == 0) return MFX_OK;
     HIP_TRY(h, hipSetDevice(h->device));
-    if (h->rows_in_stage && h->block_applied) { // the delta kernel wrote the rows into page-locked memory: wait for it, copy
+    if (h->rows_in_stage) { // the delta kernel wrote the rows into page-locked memory: wait for it, copy
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         std::memcpy(data_out, h->h_out_stage, (size_t)frames * h->width * sizeof(float));
         return MFX_OK;
     }
-    return download_rows(h, data_out, h->d_blk.p, (size_t)frames * h->width);
+    return download_rows(h, data_out, h->d_blk.p, (size_t)frames * h->width, h->h_out_stage, h->h_out_stage_n);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -13,6 +13,8 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <mutex>
+#include <vector>
 #include "mfx_delta_dev.h"
 
 namespace mfx {
@@ -560,30 +562,32 @@ int num_cus()
 hipError_t allow_dynamic_lds(const void *func, size_t lds_bytes)
 {
     if (lds_bytes <= 64 * 1024) return hipSuccess;
+    // The attribute belongs to the function on the device, for the whole process: the grant is cached process-wide and
+    // only ever raised.  (A per-thread cache let a thread with a smaller need set it DOWN under another thread that had
+    // cached its larger grant and went on launching with it: DESIGN.md B14.)
     struct Key {
         int dev;
         const void *func;
         size_t granted;
     };
-    static thread_local Key cache[32];
-    static thread_local int used = 0, next = 0;
+    static std::mutex mu;
+    static std::vector<Key> cache;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+    std::lock_guard<std::mutex> lock(mu);
     Key *slot = nullptr;
-    for (int i = 0; i < used; ++i)
-        if (cache[i].dev == dev && cache[i].func == func) {
-            if (cache[i].granted >= lds_bytes) return hipSuccess;
-            slot = &cache[i];
+    for (Key &k : cache)
+        if (k.dev == dev && k.func == func) {
+            if (k.granted >= lds_bytes) return hipSuccess;
+            slot = &k;
             break;
         }
     const hipError_t e = hipFuncSetAttribute(func, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     if (e != hipSuccess) return e;
-    if (!slot) {
-        slot = &cache[next];
-        next = (next + 1) % 32;
-        if (used < 32) ++used;
-    }
-    *slot = Key{dev, func, lds_bytes};
+    if (slot)
+        slot->granted = lds_bytes;
+    else
+        cache.push_back(Key{dev, func, lds_bytes});
     return hipSuccess;
 }
 

@@ -147,7 +147,11 @@ int mfx_get_output_data(mfx_handle *h, float *data_out, int32_t frames);
  * are applied to the stored spectrum of the current block in one launch per stage; results are the
  * same as n_alpha rounds of mfx_set_alpha + mfx_apply.  Read block a with mfx_get_output_data_alpha.
  * The handle's own alpha (mfx_set_alpha) is not changed.  Normalisation statistics are kept per
- * alpha, so a flush block re-uses the statistics of the same alpha (normalizercpu.cpp use_last_stats). */
+ * alpha, so a flush block re-uses the statistics of the same alpha (normalizercpu.cpp use_last_stats).
+ * The plain rows and the sweep's rows of a block are kept apart, and may be read in any order and more than
+ * once: a sweep does not change what mfx_get_output_data returns for the block's plain apply, and a plain
+ * apply does not change what mfx_get_output_data_alpha returns.  mfx_set_input and mfx_flush end both:
+ * mfx_get_output_data_alpha on a block that has had no sweep returns MFX_ERR_STATE. */
 int mfx_apply_alphas(mfx_handle *h, const float *alphas, int32_t n_alpha);
 int mfx_get_output_data_alpha(mfx_handle *h, int32_t alpha_index, float *data_out, int32_t frames);
 /* ParamBase::get_input_buffer_size / estimated_window_count (parambase.h:23-24, parambase.cpp:12-19) */

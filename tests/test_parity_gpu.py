@@ -413,6 +413,182 @@ def test_vtln_sweep_in_one_call(pkg, orc, norm, nad):
         m.get_output_data_alpha(len(alphas), 1)
 
 
+# Steps within a block: P = plain apply (the handle's alpha), S = sweep (apply_alphas), p = read the plain rows,
+# s = read every alpha's rows.  Paths: the default engine with blocks under 1 MB of rows (the delta kernel writes the plain
+# rows into the pinned staging buffer), engine bit 32 (MFX_ENGINE_DMA_SMALL_BLOCKS: the same blocks through d_blk), blocks
+# over 1 MB.  Norm: 0; CMN before the deltas (nad False: still the staging path); CVN after the deltas (through d_blk).
+_INTERLEAVED = ([(o, "stage", d, nm, nad) for o in ("PSps", "PSsp", "SPps", "PpSsp") for d in ("pageable", "pinned")
+                 for nm, nad in ((0, True), (1, False))] +
+                [("PSps", "stage", "pageable", 2, True), ("PpSsp", "stage", "pinned", 2, True),
+                 ("PSps", "dma", "pageable", 0, True), ("SPps", "dma", "pinned", 1, False), ("PpSsp", "dma", "pageable", 2, True),
+                 ("PSsp", "large", "pinned", 0, True), ("PSps", "large", "pageable", 1, False),
+                 ("PpSsp", "large", "pinned", 2, True)])
+
+
+@pytest.mark.parametrize("order,path,dest,norm,nad", _INTERLEAVED)
+def test_plain_and_sweep_reads_interleaved(pkg, orc, order, path, dest, norm, nad):
+    """one block read both ways -- the plain apply's rows and a sweep's -- in any order, into pageable or
+    pinned memory.  A sweep must not change what get_output_data returns, nor a plain apply what get_output_data_alpha
+    returns: every read is bit-identical to a sweep-free twin handle (plain: apply only; alpha a: set_alpha(a) + apply),
+    and the rows pass the checker.  Block 0 is plain only, so a stale read returns real rows of an earlier block."""
+    import ctypes as C
+    import torch
+    alphas = [0.9, 1.0, 1.12]
+    kw, ibs, blk, n_pcm = {"stage": (dict(), 20000, 16000, 57000), "dma": (dict(engine=32), 20000, 16000, 57000),
+                           "large": (dict(S=40), 300000, 300000, 880000)}[path]
+    pcm = synth_utterance(n_pcm, 23)
+    m, cfg, w = make_pair(pkg, orc, ibs, norm=norm, nad=nad, **kw)
+    p = make_pair(pkg, orc, ibs, norm=norm, nad=nad, **kw)[0]
+    twins = [make_pair(pkg, orc, ibs, norm=norm, nad=nad, **kw)[0] for _ in alphas]
+    m.set_alpha(1.0)
+    p.set_alpha(1.0)
+    width = m.get_output_data_width()
+    pinned = torch.empty(m.max_frames_out() * width, dtype=torch.float32).pin_memory() if dest == "pinned" else None
+
+    def read(idx, k):   # idx None: the plain rows
+        if pinned is None:
+            return m.get_output_data(k) if idx is None else m.get_output_data_alpha(idx, k)
+        pinned.fill_(float("nan"))
+        ptr = C.cast(pinned.data_ptr(), C.POINTER(C.c_float))
+        m._chk(m._L.mfx_get_output_data(m._h, ptr, k) if idx is None else m._L.mfx_get_output_data_alpha(m._h, idx, ptr, k))
+        return pinned[:k * width].numpy().reshape(k, width).copy()
+
+    plain, want_plain = [], []
+    swept, want_swept = [[] for _ in alphas], [[] for _ in alphas]
+    pos, b = 0, 0
+    while True:
+        last = pos >= pcm.size
+        if last:
+            k = m.flush()
+            assert k == p.flush() and all(k == t.flush() for t in twins)
+        else:
+            piece = pcm[pos:pos + blk]
+            pos += blk
+            k = m.set_input(piece)
+            assert k == p.set_input(piece) and all(k == t.set_input(piece) for t in twins)
+            rows_bytes = k * width * 4
+            assert rows_bytes < 1 << 20 if path != "large" else rows_bytes > 1 << 20, (path, b, rows_bytes)
+        if k > 0:
+            p.apply()
+            want_plain.append(p.get_output_data(k))
+            if b > 0:
+                for i, (t, a) in enumerate(zip(twins, alphas)):
+                    t.set_alpha(a)
+                    t.apply()
+                    want_swept[i].append(t.get_output_data(k))
+            got_p = []
+            for step in (order if b > 0 else "Pp"):
+                if step == "P":
+                    m.apply()
+                elif step == "S":
+                    m.apply_alphas(alphas)
+                elif step == "p":
+                    got_p.append(read(None, k))
+                else:
+                    for i in range(len(alphas)):
+                        swept[i].append(read(i, k))
+            what = "%s block %d%s" % (order, b, " (flush)" if last else "")
+            assert np.array_equal(got_p[0], want_plain[-1]), "%s: plain rows differ from the sweep-free twin's" % what
+            for g in got_p[1:]:
+                assert np.array_equal(g, got_p[0]), "%s: plain rows read again after the sweep differ" % what
+            plain.append(got_p[0])
+            for i, a in enumerate(alphas):
+                if b > 0:
+                    assert np.array_equal(swept[i][-1], want_swept[i][-1]), "%s: alpha %.2f rows differ from its twin's" % (what, a)
+        b += 1
+        if last:
+            break
+    assert b >= 4
+    got = np.concatenate(plain)
+    if norm == 0:
+        for a, rows, skip in [(1.0, got, 0)] + [(a, np.concatenate(swept[i]), 1) for i, a in enumerate(alphas)]:
+            o = orc.OracleMfcc(cfg, w)
+            want, pos, j = [], 0, 0
+            while True:
+                last = pos >= pcm.size
+                k = o.flush() if last else o.set_input(pcm[pos:pos + blk])
+                pos += blk
+                if k > 0:
+                    o.set_alpha(a)
+                    o.apply()
+                    if j >= skip:
+                        want.append(o.get_output_data(k))
+                j += 1
+                if last:
+                    break
+            o.close()
+            assert_close(rows, np.concatenate(want), "%s %s alpha %.2f%s" % (order, path, a, "" if skip else " (plain)"), groups=3)
+    else:
+        alone = stream_normalised_check(pkg, orc, pcm, ibs, "%s %s norm %d" % (order, path, norm), norm=norm, dyn=2, nad=nad,
+                                        alpha=1.0, block=blk, **kw)
+        assert np.array_equal(got, alone)
+    for e in [m, p] + twins:
+        e.close()
+
+
+def test_handles_on_two_threads_with_different_dynamic_lds(pkg, orc):
+    """the dynamic-LDS grant of a kernel is an attribute of the process, not of a thread.  k_melcep at a
+    4096-point transform (16 kHz, 64 Hz - 8 kHz) needs 114 464 bytes of LDS with 64 filters and 105 312 bytes with 20
+    (melcep_lds_bytes, 4 waves per block), both above the 64 KB that needs no attribute.  Thread A applies a block (114 464),
+    then thread B applies its first block (105 312), then A applies its next block: with the grant cached per thread, B set
+    the attribute down under A's cached grant.  Every block of both threads must match the checker, with no MfxError."""
+    import threading
+    W, S, ibs, blk = 2400, 960, 60000, 48000
+    cases = {"A": dict(nb=64), "B": dict(nb=20)}
+    pcm = {"A": synth_utterance(4 * blk + 30000, 31), "B": synth_utterance(4 * blk + 30000, 32)}
+    pairs = {k: make_pair(pkg, orc, ibs, W=W, S=S, **kw) for k, kw in cases.items()}
+    assert all(pr[0].fft_size() == 4096 for pr in pairs.values())
+    barrier = threading.Barrier(2, timeout=300)
+    got = {k: [] for k in cases}
+    errors = []
+
+    def run(name):
+        m, x = pairs[name][0], pcm[name]
+        try:
+            if name == "B":
+                barrier.wait()                                  # 1: A has applied its first block
+            for i, pos in enumerate(range(0, x.size, blk)):
+                n = m.set_input(x[pos:pos + blk])
+                if n > 0:
+                    m.apply()
+                    got[name].append(m.get_output_data(n))
+                if i == 0:
+                    if name == "A":
+                        barrier.wait()                          # 1
+                    barrier.wait()                              # 2: B has applied its first block; A goes on
+            n = m.flush()
+            if n > 0:
+                m.apply()
+                got[name].append(m.get_output_data(n))
+        except Exception as e:  # (the thread's failure is the test's: reported below)
+            errors.append("thread %s: %r" % (name, e))
+            barrier.abort()
+
+    threads = [threading.Thread(target=run, args=(k,)) for k in cases]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(600)
+    assert not any(t.is_alive() for t in threads), "a thread did not finish"
+    assert not errors, errors
+    for name in cases:
+        m, cfg, w = pairs[name]
+        o = orc.OracleMfcc(cfg, w)
+        want = []
+        for pos in list(range(0, pcm[name].size, blk)) + [None]:
+            n = o.flush() if pos is None else o.set_input(pcm[name][pos:pos + blk])
+            if n > 0:
+                o.apply()
+                want.append(o.get_output_data(n))
+        assert len(want) == len(got[name])
+        for j, (g, r) in enumerate(zip(got[name], want)):
+            if j + 1 < len(want):
+                assert_close(g, r, "thread %s block %d" % (name, j), groups=3)
+        assert_close(np.concatenate(got[name]), np.concatenate(want), "thread %s stream" % name, groups=3)
+        o.close()
+        m.close()
+
+
 @pytest.mark.parametrize("W,S,off", [(400, 160, 0), (400, 161, 0), (400, 160, 1), (512, 128, 0), (511, 127, 0)])
 def test_c3_shape_1024_override(pkg, orc, W, S, off):
     """BASELINE configs[2] in small: 25 ms window zero padded to a 1024-point FFT, 80 mel, 13 MFCC; also with an odd
