@@ -15,6 +15,8 @@ from .mfcc import (  # noqa: F401
     DYN_ACC,
     DYN_DELTA,
     DYN_NONE,
+    METHOD_MFCC,
+    METHOD_PLP,
     NORM_CMN,
     NORM_CVN,
     NORM_MINMAX,
@@ -27,9 +29,11 @@ from .mfcc import (  # noqa: F401
     host_frame_count,
     host_mel_lane_plan,
     host_mel_table,
+    host_plp_tables,
     KERNEL_TABLE,
     library_path,
     load_library,
+    method_supported,
     plan_kernel,
     reference_window,
 )

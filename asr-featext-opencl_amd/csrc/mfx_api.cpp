@@ -77,6 +77,8 @@ struct mfx_handle {
     bool stuff256 = false; // fast512 serving 256-point transforms in the zero-stuffed form
     bool fast1024 = false; // 1024 points, window <= 512 samples: k_front1024 (two 256-point transforms per frame)
     int nm16 = 16;
+    bool plp = false;  // mfx_config.method == MFX_METHOD_PLP: k_plp where MFCC runs k_melcep, never the fused front ends
+    int lpc = 0;       // PLP model order (lpc_order, 0 -> 8)
     float alpha = 1.f, table_alpha = -1.f;
     bool have_window = false;
 
@@ -89,6 +91,8 @@ struct mfx_handle {
     DevBuf<float> d_sweep64_w;
     DevBuf<int32_t> d_sweep64_start, d_sweep64_fid, d_sweep64_L;
     int sweep64_rs = 0;
+    // PLP: equal-loudness weights of the handle's alpha / of every sweep alpha, autocorrelation basis, lifter, r taps
+    DevBuf<float> d_plp_eql, d_sweep_eql, d_plp_idft, d_plp_lift, d_plp_r;
     // 512-point kernel: per-lane mel plan + transposed DCT matrix
     DevBuf<float> d_mel_lane_w, d_dct_t;
     DevBuf<int32_t> d_mel_lane_start, d_mel_lane_fid;
@@ -276,6 +280,21 @@ int refresh_mel(mfx_handle *h)
         if (melcep_lds_bytes(probe, 1) > 160 * 1024)
             return fail(h, MFX_ERR_CONFIG, "mel filterbank does not fit the kernels' LDS (very wide filters on a long transform)");
     }
+    if (h->plp) {
+        std::vector<float> eql, idft;
+        build_plp_tables(h->nb, h->cfg.sample_rate, h->cfg.low_freq, h->cfg.high_freq, h->alpha, h->lpc, eql, idft);
+        HIP_TRY(h, upload(h->d_plp_eql, eql));
+        PlpParams probe;
+        std::memset(&probe, 0, sizeof(probe));
+        probe.num_banks = h->nb;
+        probe.lpc_order = h->lpc;
+        probe.ceps_len = h->ceps;
+        probe.mel64_rounds = h->wplan.rounds;
+        probe.mel64_row_stride = h->wplan.row_stride;
+        probe.mag_floats = std::max(h->W2, (h->spec_pitch + 3) & ~3);
+        if (plp_lds_bytes(probe, 1) > 160 * 1024)
+            return fail(h, MFX_ERR_CONFIG, "mel filterbank does not fit the PLP kernel's LDS");
+    }
     h->wplan_ok = true;
     h->wplan32_ok = false;
     if (h->fast2048) { // k_front2048 walks the filters on the 32 lanes of each of a wave's two frames
@@ -437,6 +456,7 @@ int run_norm(mfx_handle *h, float *data, int pitch, int col0, const Segment *seg
 // ------------------------------------------------------------------------------------------------
 
 extern "C" int mfx_abi_version(void) { return MFX_ABI_VERSION; }
+extern "C" int mfx_method_supported(int32_t method) { return method == MFX_METHOD_MFCC || method == MFX_METHOD_PLP ? 1 : 0; }
 
 extern "C" const char *mfx_status_string(int status)
 {
@@ -580,6 +600,11 @@ int create_impl(const mfx_config *cfg, int hip_device, mfx_handle **out)
     if (cfg->ceps_len > 0 && cfg->lift_coef == 0.f) return MFX_ERR_CONFIG; // reference divides by lift_coef
     if (cfg->dyn != MFX_DYN_NONE && cfg->delta_l1 <= 0) return MFX_ERR_CONFIG;
     if (cfg->dyn == MFX_DYN_ACC && cfg->delta_l2 <= 0) return MFX_ERR_CONFIG;
+    if (cfg->method != MFX_METHOD_MFCC && cfg->method != MFX_METHOD_PLP) return MFX_ERR_CONFIG;
+    if (cfg->method == MFX_METHOD_PLP) { // PLP has no log-energy form; the recursion runs in registers up to kPlpMaxOrder
+        const int p = cfg->lpc_order == 0 ? 8 : cfg->lpc_order;
+        if (cfg->ceps_len <= 0 || cfg->lpc_order < 0 || p > std::min(kPlpMaxOrder, (int)cfg->num_banks)) return MFX_ERR_CONFIG;
+    }
 
     if (!t_planning) {
         int ndev = 0;
@@ -596,6 +621,8 @@ int create_impl(const mfx_config *cfg, int hip_device, mfx_handle **out)
     h->S = cfg->shift;
     h->nb = cfg->num_banks;
     h->ceps = cfg->ceps_len;
+    h->plp = cfg->method == MFX_METHOD_PLP;
+    h->lpc = h->plp ? (cfg->lpc_order == 0 ? 8 : cfg->lpc_order) : 0;
     h->l1 = cfg->dyn != MFX_DYN_NONE ? cfg->delta_l1 : 0;
     h->l2 = cfg->dyn == MFX_DYN_ACC ? cfg->delta_l2 : 0;
     h->D = h->l1 + h->l2;
@@ -727,6 +754,12 @@ int create_impl(const mfx_config *cfg, int hip_device, mfx_handle **out)
             }
         }
     }
+    if (h->plp) {
+        std::vector<float> eql, idft, lift;
+        build_plp_tables(h->nb, cfg->sample_rate, cfg->low_freq, cfg->high_freq, 1.f, h->lpc, eql, idft);
+        build_plp_lifter(h->ceps, cfg->lift_coef, lift);
+        if (upload(h->d_plp_idft, idft) != hipSuccess || upload(h->d_plp_lift, lift) != hipSuccess) return bail(MFX_ERR_DEVICE);
+    }
     rc = refresh_mel(h);
     if (rc != MFX_OK) return bail(rc);
 
@@ -745,6 +778,7 @@ int create_impl(const mfx_config *cfg, int hip_device, mfx_handle **out)
     if (h->d_src.alloc((size_t)h->cap_rows * h->cols) != hipSuccess) return bail(MFX_ERR_DEVICE);
     if (h->d_blk.alloc((size_t)h->cap_rows * h->width) != hipSuccess) return bail(MFX_ERR_DEVICE);
     if (h->d_stats_stream.alloc((size_t)3 * 2 * h->cols) != hipSuccess) return bail(MFX_ERR_DEVICE);
+    if (h->plp && h->d_plp_r.alloc((size_t)h->cap_rows * (h->lpc + 1)) != hipSuccess) return bail(MFX_ERR_DEVICE);
     if (cfg->norm != MFX_NORM_NONE) { // chunk results of the statistics over a long streaming block
         const size_t need = norm_partial_doubles(1, h->cap_rows, h->cols);
         if (need > 0 && h->d_norm_partial.alloc(need) != hipSuccess) return bail(MFX_ERR_DEVICE);
@@ -860,7 +894,8 @@ namespace {
 enum FrontKind { kFront512, kFront1024, kFront2048, kFrontGenFused, kSpec512, kSpecGen };
 FrontKind choose_front(const mfx_handle *h)
 {
-    const bool allow_fused = !(h->cfg.engine & MFX_ENGINE_STREAM_KERNELS); // (else: the streaming interface's kernels)
+    // (else: the streaming interface's kernels; PLP has no fused front end: spectrum through HBM, then k_plp)
+    const bool allow_fused = !(h->cfg.engine & MFX_ENGINE_STREAM_KERNELS) && !h->plp;
     if (allow_fused && h->fast512 && h->fused_ok) return kFront512;
     // (k_front1024, windows longer than 512 samples: aligned frames only)
     if (allow_fused && h->fast1024 && h->fused_ok && (h->W <= 512 || h->batch_aligned)) return kFront1024;
@@ -1289,6 +1324,7 @@ int prepare_sweep(mfx_handle *h, const float *alphas, int n)
     const bool same = (int)h->sweep_alphas.size() == n && std::equal(alphas, alphas + n, h->sweep_alphas.begin());
     if (n > h->sweep_cap) {
         HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (h->plp) HIP_TRY(h, h->d_sweep_eql.alloc((size_t)h->nb * n));
         HIP_TRY(h, h->d_sweep_w.alloc(wstride * n));
         HIP_TRY(h, h->d_sweep_beg.alloc(bstride * n));
         HIP_TRY(h, h->d_sweep_src.alloc((size_t)n * h->cap_rows * h->cols));
@@ -1302,8 +1338,14 @@ int prepare_sweep(mfx_handle *h, const float *alphas, int n)
     std::vector<float> w(wstride * n);
     std::vector<int32_t> b(bstride * n);
     std::vector<MelWavePlan> plans((size_t)n);
+    std::vector<float> eql_all;
     int rs = 4;
     for (int a = 0; a < n; ++a) {
+        if (h->plp) {
+            std::vector<float> eql, idft;
+            build_plp_tables(h->nb, h->cfg.sample_rate, h->cfg.low_freq, h->cfg.high_freq, alphas[a], 0, eql, idft);
+            eql_all.insert(eql_all.end(), eql.begin(), eql.end());
+        }
         MelTable t;
         build_mel_table(h->nb, h->W2, h->cfg.sample_rate, h->cfg.low_freq, h->cfg.high_freq, alphas[a], t);
         for (int v : t.beg)
@@ -1337,6 +1379,18 @@ int prepare_sweep(mfx_handle *h, const float *alphas, int n)
         probe.mag_floats = std::max(h->W2, (h->spec_pitch + 3) & ~3);
         if (melcep_lds_bytes(probe, 1) > 160 * 1024)
             return fail(h, MFX_ERR_CONFIG, "a warped mel filterbank of the sweep does not fit the kernels' LDS");
+        if (h->plp) {
+            PlpParams pp;
+            std::memset(&pp, 0, sizeof(pp));
+            pp.num_banks = h->nb;
+            pp.lpc_order = h->lpc;
+            pp.ceps_len = h->ceps;
+            pp.mel64_rounds = rounds;
+            pp.mel64_row_stride = rs;
+            pp.mag_floats = probe.mag_floats;
+            if (plp_lds_bytes(pp, 1) > 160 * 1024)
+                return fail(h, MFX_ERR_CONFIG, "a warped mel filterbank of the sweep does not fit the PLP kernel's LDS");
+        }
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     HIP_TRY(h, hipMemcpy(h->d_sweep_w.p, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -1345,6 +1399,7 @@ int prepare_sweep(mfx_handle *h, const float *alphas, int n)
     HIP_TRY(h, upload(h->d_sweep64_start, pst));
     HIP_TRY(h, upload(h->d_sweep64_fid, pfid));
     HIP_TRY(h, upload(h->d_sweep64_L, pL));
+    if (h->plp) HIP_TRY(h, hipMemcpy(h->d_sweep_eql.p, eql_all.data(), eql_all.size() * sizeof(float), hipMemcpyHostToDevice));
     h->sweep64_rs = rs;
     h->sweep_alphas.assign(alphas, alphas + n);
     return MFX_OK;
@@ -1374,6 +1429,32 @@ void fill_melcep(const mfx_handle *h, MelcepParams &mp, bool sweep)
     mp.n_tables = 1;
     mp.mel_w_stride = (int64_t)2 * h->W2;
     mp.mel_beg_stride = h->nb + 2;
+}
+
+// k_plp parameters that do not depend on the caller (the PLP twin of fill_melcep)
+void fill_plp(const mfx_handle *h, PlpParams &pp, bool sweep)
+{
+    MelcepParams mp;
+    fill_melcep(h, mp, sweep);
+    std::memset(&pp, 0, sizeof(pp));
+    pp.spec_pitch = mp.spec_pitch;
+    pp.fft_size = mp.fft_size;
+    pp.num_banks = h->nb;
+    pp.lpc_order = h->lpc;
+    pp.ceps_len = h->ceps;
+    pp.want_c0 = h->cfg.want_c0 ? 1 : 0;
+    pp.cols = h->cols;
+    pp.mel64_w = mp.mel64_w;
+    pp.mel64_start = mp.mel64_start;
+    pp.mel64_fid = mp.mel64_fid;
+    pp.mel64_L = mp.mel64_L;
+    pp.mel64_rounds = mp.mel64_rounds;
+    pp.mel64_row_stride = mp.mel64_row_stride;
+    pp.mag_floats = mp.mag_floats;
+    pp.eql = sweep ? h->d_sweep_eql.p : h->d_plp_eql.p;
+    pp.idft = h->d_plp_idft.p;
+    pp.lift = h->d_plp_lift.p;
+    pp.n_tables = 1;
 }
 
 // apply() for the current block: n_alpha == 0 -> the handle's alpha into d_src/d_blk (ParamBase::apply);
@@ -1412,16 +1493,29 @@ int apply_impl(mfx_handle *h, const float *alphas, int n_alpha)
     float *d_blk = sweep ? h->d_sweep_blk.p : h->d_blk.p;
     float *d_stats = sweep ? h->d_sweep_stats.p : h->d_stats_stream.p;
 
-    // filterbank + log + DCT over all frames with context
-    MelcepParams mp;
-    fill_melcep(h, mp, sweep);
-    mp.spec = h->d_spec.p;
-    mp.n_rows = wcnd;
-    mp.feat = d_src;
-    mp.feat_pitch = h->cols;
-    mp.n_tables = n_tab;
-    mp.feat_table_stride = (int64_t)h->cap_rows * h->cols;
-    HIP_TRY(h, launch_melcep(mp, h->stream));
+    // filterbank + log + DCT (PLP: k_plp) over all frames with context
+    if (h->plp) {
+        PlpParams pp;
+        fill_plp(h, pp, sweep);
+        pp.spec = h->d_spec.p;
+        pp.n_rows = wcnd;
+        pp.feat = d_src;
+        pp.feat_pitch = h->cols;
+        pp.n_tables = n_tab;
+        pp.feat_table_stride = (int64_t)h->cap_rows * h->cols;
+        pp.r_out = sweep ? nullptr : h->d_plp_r.p;
+        HIP_TRY(h, launch_plp(pp, h->stream));
+    } else {
+        MelcepParams mp;
+        fill_melcep(h, mp, sweep);
+        mp.spec = h->d_spec.p;
+        mp.n_rows = wcnd;
+        mp.feat = d_src;
+        mp.feat_pitch = h->cols;
+        mp.n_tables = n_tab;
+        mp.feat_table_stride = (int64_t)h->cap_rows * h->cols;
+        HIP_TRY(h, launch_melcep(mp, h->stream));
+    }
 
     // static row offset as the reference reads it (mfcccpu.cpp:274,439): was_flushed() ? 0 : D.
     // With bug_compat off a flush block always reads at D (fixes B1).
@@ -1963,13 +2057,23 @@ int batch_run_range(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_tot
                 else
                     HIP_TRY(h, launch_front_generic(q, /*fused=*/false, h->stream));
             }
-            MelcepParams mp;
-            fill_melcep(h, mp, false);
-            mp.spec = h->d_spec_slab.p;
-            mp.n_rows = rows;
-            mp.feat = p.feat + row0 * (int64_t)p.feat_pitch;
-            mp.feat_pitch = p.feat_pitch;
-            HIP_TRY(h, launch_melcep(mp, h->stream));
+            if (h->plp) {
+                PlpParams pp;
+                fill_plp(h, pp, false);
+                pp.spec = h->d_spec_slab.p;
+                pp.n_rows = rows;
+                pp.feat = p.feat + row0 * (int64_t)p.feat_pitch;
+                pp.feat_pitch = p.feat_pitch;
+                HIP_TRY(h, launch_plp(pp, h->stream));
+            } else {
+                MelcepParams mp;
+                fill_melcep(h, mp, false);
+                mp.spec = h->d_spec_slab.p;
+                mp.n_rows = rows;
+                mp.feat = p.feat + row0 * (int64_t)p.feat_pitch;
+                mp.feat_pitch = p.feat_pitch;
+                HIP_TRY(h, launch_melcep(mp, h->stream));
+            }
             c0 = c1;
         }
     }
@@ -2182,6 +2286,10 @@ extern "C" int64_t mfx_debug_read(mfx_handle *h, int kind, void *dst, int64_t ds
         count = h->cfg.norm == MFX_NORM_NONE ? 0
                                              : (int64_t)(h->cfg.norm_after_dyn ? h->width / h->cols : 1) * h->n_utt * 2 * h->cols;
         break;
+    case 7: // PLP autocorrelations of the last plain streaming apply(): [frames_with_context][lpc_order + 1]
+        src = h->d_plp_r.p;
+        count = h->plp ? (int64_t)h->block_wcnd * (h->lpc + 1) : 0;
+        break;
     default:
         return MFX_ERR_ARG;
     }
@@ -2195,6 +2303,17 @@ extern "C" int64_t mfx_debug_read(mfx_handle *h, int kind, void *dst, int64_t ds
 // ------------------------------------------------------------------------------------------------
 // host-side table builders (no device)
 // ------------------------------------------------------------------------------------------------
+
+extern "C" int mfx_host_plp_tables(int32_t num_banks, int32_t fft_size, float sample_rate, float low_freq, float high_freq,
+                                   float alpha, int32_t lpc_order, float *eql, float *idft)
+{
+    if (num_banks <= 0 || fft_size <= 0 || sample_rate <= 0 || lpc_order < 0 || !eql || !idft) return MFX_ERR_ARG;
+    std::vector<float> e, b;
+    build_plp_tables(num_banks, sample_rate, low_freq, high_freq, alpha, lpc_order, e, b);
+    std::copy(e.begin(), e.end(), eql);
+    std::copy(b.begin(), b.end(), idft);
+    return MFX_OK;
+}
 
 extern "C" int mfx_host_mel_table(int32_t num_banks, int32_t fft_size, float sample_rate, float low_freq,
                                   float high_freq, float alpha, float *weights, int32_t *beg)

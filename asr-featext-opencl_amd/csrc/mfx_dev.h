@@ -268,6 +268,8 @@ __device__ __forceinline__ void dct_mfma4s(const float *arow, __amdgpu_buffer_rs
 // round, so lanes >= nb never carry one -- they walk the last staged row (same addresses: a broadcast) and park a finite value.
 __host__ __device__ __forceinline__ int mel64_rows(int num_banks) { return num_banks < 64 ? (num_banks > 0 ? num_banks : 1) : 64; }
 
+// LOG = false: the floored energy itself, without the log (k_plp walks power spectra: mfx_plp.hip).
+template <bool LOG = true>
 __device__ __forceinline__ void mel64_walk_log(const float *mag, float *lmf, int park, const float *s_mw, const int *s_mst,
                                                const int *s_mfid, const int *Lr, int rounds, int RS, int lane, int w_rows)
 {
@@ -293,7 +295,7 @@ __device__ __forceinline__ void mel64_walk_log(const float *mag, float *lmf, int
             acc += w1.w * mm[3].y;
         }
         wrow += L;
-        lmf[fid >= 0 ? fid : park] = MFX_LOG(fmaxf(acc, 1e-30f));
+        lmf[fid >= 0 ? fid : park] = LOG ? MFX_LOG(fmaxf(acc, 1e-30f)) : fmaxf(acc, 1e-30f);
     }
 }
 

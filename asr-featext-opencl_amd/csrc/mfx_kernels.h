@@ -1,10 +1,11 @@
-// mfx_kernels.h -- launch interface of the gfx950 kernels (implemented in mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip: one translation unit per kernel family).
+// mfx_kernels.h -- launch interface of the gfx950 kernels (implemented in mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip, mfx_plp.hip: one translation unit per kernel family).
 //
 // Kernel inventory and the reference stage each one replaces:
 //   spectrum512 / fused512   segmenter.cl kernelSegmentWindow + AppleFFT fft0 + mfcc.cl kernelTranspose
 //                            (+ mfcc.cl kernelFilter + the DCT slot when fused)
 //   spectrum_generic         same three stages for any power-of-two FFT length
 //   melcep                   mfcc.cl kernelFilter + DCT slot (mfccopencl.cpp:315-358) from a stored spectrum
+//   plp                      PLP cepstra from a stored spectrum (no reference kernel: the reference names the method only)
 //   delta                    delta.cl kernelDelta x2 + the staging copies of mfccopencl.cpp:360-387
 //   norm_stats / norm_apply  norm.cl kernelSum + kernelFinalizeSum / kernelNormalize
 #pragma once
@@ -148,6 +149,36 @@ struct MelcepParams {
     int64_t feat_table_stride;
 };
 
+// k_plp (mfx_plp.hip): stored magnitudes -> power -> mel filterbank -> equal loudness + cube root -> autocorrelation ->
+// Levinson-Durbin -> LPC cepstrum -> lifter (PLP).  Same spectrum rows, 64-lane mel plan and sweep layout as
+// MelcepParams; statics of width cols = ceps_len (+ 1 with c0 as the last column).
+struct PlpParams {
+    const float *spec;
+    int32_t spec_pitch;
+    int64_t n_rows;
+    float *feat;
+    int32_t feat_pitch;
+    int32_t fft_size;
+    int32_t num_banks;
+    int32_t lpc_order;            // p, 1 .. kPlpMaxOrder
+    int32_t ceps_len;             // C >= 1
+    int32_t want_c0;
+    int32_t cols;                 // ceps_len + (want_c0 ? 1 : 0)
+    const float *mel64_w;         // as MelcepParams
+    const int32_t *mel64_start;
+    const int32_t *mel64_fid;
+    const int32_t *mel64_L;
+    int32_t mel64_rounds, mel64_row_stride;
+    int32_t mag_floats;
+    const float *eql;             // [n_tables][num_banks] equal-loudness weights e_m (centres move with alpha)
+    const float *idft;            // [lpc_order + 1][num_banks + 2] cosine basis of the autocorrelation (mfx_host_plp_tables)
+    const float *lift;            // [ceps_len] lifter weights w_1 .. w_C
+    float *r_out;                 // nullptr, or [n_rows][lpc_order + 1] autocorrelations (table 0 only; mfx_debug_read 7)
+    int32_t n_tables;
+    int64_t feat_table_stride;
+};
+constexpr int kPlpMaxOrder = 32;
+
 struct DeltaParams {
     const float *src;      // static features, [rows][src_pitch]
     int32_t src_pitch;
@@ -191,6 +222,9 @@ hipError_t launch_front_generic(const FrontParams &p, bool fused, hipStream_t st
 size_t front_wave_lds_bytes(const FrontParams &p, bool fused);
 hipError_t launch_melcep(const MelcepParams &p, hipStream_t stream);
 hipError_t launch_delta(const DeltaParams &p, hipStream_t stream);
+hipError_t launch_plp(const PlpParams &p, hipStream_t stream);
+// LDS of k_plp with n_waves waves per block (the launcher takes as many of 4 as fit)
+size_t plp_lds_bytes(const PlpParams &p, int n_waves);
 // LDS of k_melcep with n_waves waves per block (the launcher takes as many of 4 as fit)
 size_t melcep_lds_bytes(const MelcepParams &p, int n_waves);
 hipError_t launch_norm_stats(const NormParams &p, hipStream_t stream);

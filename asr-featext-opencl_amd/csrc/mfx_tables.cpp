@@ -75,6 +75,38 @@ void build_mel_table(int num_banks, int fft_size, float sample_rate, float low_f
     }
 }
 
+void build_plp_tables(int num_banks, float sample_rate, float low_freq, float high_freq, float alpha, int lpc_order,
+                      std::vector<float> &eql, std::vector<float> &idft)
+{
+    // centres in double, as the float64 restatement states them (np_restatement.mel_tables); the filterbank itself keeps
+    // the float32 centres of build_mel_table
+    const double pi = 3.14159265358979323846264338;
+    const double sr = sample_rate, a1 = 1.0 - (double)alpha;
+    const double mlo = 1127.0 * std::log((double)low_freq / 700.0 + 1.0), mhi = 1127.0 * std::log((double)high_freq / 700.0 + 1.0);
+    eql.assign((size_t)num_banks, 0.f);
+    for (int m = 0; m < num_banks; ++m) {
+        const double f = 700.0 * (std::exp(((m + 1) / (double)(num_banks + 1) * (mhi - mlo) + mlo) / 1127.0) - 1.0);
+        double o = 2 * pi * f / sr;
+        o = o + 2 * std::atan((a1 * std::sin(o)) / (1 - a1 * std::cos(o)));
+        const double fc = sr * o / (2 * pi), q = fc * fc;
+        const double t = q / (q + 1.6e5);
+        eql[m] = (float)(t * t * (q + 1.44e6) / (q + 9.61e6));
+    }
+    const int N = num_banks + 2;
+    idft.assign((size_t)(lpc_order + 1) * N, 0.f);
+    for (int i = 0; i <= lpc_order; ++i)
+        for (int m = 0; m < N; ++m) {
+            const double w = (m == 0 || m == N - 1) ? 1.0 : 2.0;
+            idft[(size_t)i * N + m] = (float)(w * std::cos(pi * i * m / (N - 1)) / (2.0 * (N - 1)));
+        }
+}
+
+void build_plp_lifter(int ceps_len, float lift_coef, std::vector<float> &out)
+{
+    out.assign((size_t)ceps_len, 0.f);
+    for (int c = 1; c <= ceps_len; ++c) out[c - 1] = (1 + lift_coef / 2 * sinf(kPiF * (float)c / lift_coef)); // as build_dct_matrix
+}
+
 void build_dct_matrix(int num_banks, int ceps_len, bool want_c0, float lift_coef, std::vector<float> &out)
 {
     const int dct_len = ceps_len + (want_c0 ? 1 : 0);

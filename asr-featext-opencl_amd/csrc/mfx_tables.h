@@ -34,6 +34,16 @@ void build_mel_table(int num_banks, int fft_size, float sample_rate, float low_f
 // (reference: mfcccpu.cpp:118-136).  Row-major [num_banks][dct_len].
 void build_dct_matrix(int num_banks, int ceps_len, bool want_c0, float lift_coef, std::vector<float> &out);
 
+// PLP tables (PLP), evaluated in double and rounded once to float:
+//   eql  [num_banks]: equal-loudness weight e_m = (q / (q + 1.6e5))^2 (q + 1.44e6) / (q + 9.61e6), q = f_m^2, f_m the
+//        (warped) centre of filter m in Hz
+//   idft [lpc_order + 1][num_banks + 2]: r_i = sum_m idft[i][m] A_m, idft[i][m] = w_m cos(pi i m / (N - 1)) / (2 (N - 1)),
+//        N = num_banks + 2, w_m = 1 at both ends, 2 elsewhere
+void build_plp_tables(int num_banks, float sample_rate, float low_freq, float high_freq, float alpha, int lpc_order,
+                      std::vector<float> &eql, std::vector<float> &idft);
+// lifter weights w_1 .. w_C of the PLP cepstra: the float32 expression of build_dct_matrix
+void build_plp_lifter(int ceps_len, float lift_coef, std::vector<float> &out);
+
 // exp(-2*pi*i*k/n) for k in [0, count), evaluated in double and rounded once to float.
 void build_twiddles(int n, int count, std::vector<float> &re_im_interleaved);
 

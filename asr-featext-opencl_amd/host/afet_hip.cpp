@@ -44,6 +44,7 @@ struct Options {
     float alpha_min = 1.f, alpha_max = 1.f, alpha_step = 1.f;
     int sample_limit = 10000000, device = 0;
     bool bug_compat = true;
+    int method = MFX_METHOD_MFCC, model_order = 8; // --method MFCC|PLP, --model-order (ASR_OCL.cpp:54-56: default 8)
     bool htk = false; // binary output in HTK parameter-file format instead of the reference's text rows
     int format_threads = 4; // threads that format the text rows of a block (per worker)
     int batch_mb = 16;      // PCM per batch of files (0: the per-file loop only); small enough that a few thousand files pipeline
@@ -153,7 +154,7 @@ void put_be16(FILE *f, uint16_t v)
 }
 void write_htk_header(FILE *f, uint32_t n_frames, const Options &o, int width)
 {
-    uint16_t kind = o.ceps > 0 ? 6 /* MFCC */ : 7 /* FBANK */;
+    uint16_t kind = o.method == MFX_METHOD_PLP ? 11 /* PLP */ : o.ceps > 0 ? 6 /* MFCC */ : 7 /* FBANK */;
     if (o.ceps > 0 && o.c0) kind |= 0x2000;  // _0
     if (o.dyn >= 1) kind |= 0x0100;          // _D
     if (o.dyn >= 2) kind |= 0x0200;          // _A
@@ -533,10 +534,15 @@ void worker(const Options &o, int device, float sr, const std::vector<std::strin
         // The extractor (HIP start-up, code object load, tables: 0.1-0.3 s of a fresh process) is created on a helper
         // thread while this one claims and reads the first batch of files: reading needs nothing from the device.
         auto make_param = [&] {
-            std::unique_ptr<MfccHip> p(new MfccHip(o.sample_limit, (int)W, (int)S, o.banks, sr, o.low, o.high, o.ceps, o.c0, o.lift,
-                                                  (Normalizer::norm_t)o.norm, (ParamBase::dyn_t)o.dyn, o.l1, o.l2,
-                                                  o.norm_after_dyn, device, o.bug_compat,
-                                                  o.batch_mb > 0 ? MFX_ENGINE_STREAM_KERNELS : 0));
+            const int engine = o.batch_mb > 0 ? MFX_ENGINE_STREAM_KERNELS : 0;
+            std::unique_ptr<MfccHip> p(
+                o.method == MFX_METHOD_PLP
+                    ? new PlpHip(o.sample_limit, (int)W, (int)S, o.banks, sr, o.low, o.high, o.ceps, o.c0, o.lift, o.model_order,
+                                 (Normalizer::norm_t)o.norm, (ParamBase::dyn_t)o.dyn, o.l1, o.l2, o.norm_after_dyn, device,
+                                 o.bug_compat, engine)
+                    : new MfccHip(o.sample_limit, (int)W, (int)S, o.banks, sr, o.low, o.high, o.ceps, o.c0, o.lift,
+                                  (Normalizer::norm_t)o.norm, (ParamBase::dyn_t)o.dyn, o.l1, o.l2, o.norm_after_dyn, device,
+                                  o.bug_compat, engine));
             std::vector<float> window((size_t)W);
             for (long i = 0; i < W; ++i) // ASR_OCL.cpp:149-151
                 window[i] = (float)(0.56f - 0.46f * std::cos((2.0f * M_PI * i) / W)) / 32768.f;
@@ -773,6 +779,13 @@ int main(int argc, char **argv)
         }
         else if (a == "--bug-compat") o.bug_compat = std::atoi(val()) != 0;
         else if (a == "--htk") o.htk = true;
+        else if (a == "--method") { // the reference's names (ASR_OCL.cpp:54-56); TRAPS is not built
+            const std::string m = val();
+            if (m == "MFCC") o.method = MFX_METHOD_MFCC;
+            else if (m == "PLP") o.method = MFX_METHOD_PLP;
+            else { std::fprintf(stderr, "--method: MFCC or PLP (TRAPS is not supported)\n"); return 2; }
+        }
+        else if (a == "--model-order") o.model_order = std::atoi(val());
         else if (a == "--timing") g_time.on = true;
         else if (a == "--format-threads") o.format_threads = std::max(1, std::atoi(val()));
         else if (a == "--batch-mb") o.batch_mb = std::max(0, std::atoi(val()));
@@ -812,6 +825,7 @@ int main(int argc, char **argv)
                         "         [--dyn 0..2] [--l1 n] [--l2 n] [--low-freq hz] [--high-freq hz] [--lift-coef x]\n"
                         "         [--norm-after-dyn 0|1] [--alpha a | --alpha-min a --alpha-max b --alpha-step s]\n"
                         "         [--sample-limit n] [--dev n | --devs a,b,...] [--bug-compat 0|1] [--htk]  in.wav out.txt [...]\n"
+                        "         [--method MFCC|PLP] [--model-order n (PLP model order, default 8)]\n"
                         "         [--batch-mb n (PCM per batch of whole files; 0 = per-file loop)] [--io-threads n]\n"
                         "  --devs: one worker per listed GPU, files dealt from a shared queue\n"
                         "  inputs: RIFF/WAVE or NIST SPHERE, 16-bit PCM; output: the reference's text rows, or HTK binary\n");

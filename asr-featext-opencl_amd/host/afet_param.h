@@ -113,9 +113,25 @@ public:
     int max_frames_out() const;
     mfx_handle *handle() const { return m_handle; }
 
+protected:
+    // method: MFX_METHOD_* of include/mfx.h (PlpHip passes MFX_METHOD_PLP and its model order)
+    MfccHip(int input_buffer_size, int window_size, int shift, int num_banks, float sample_rate, float low_freq,
+            float high_freq, int ceps_len, bool want_c0, float lift_coef, Normalizer::norm_t norm, dyn_t dyn, int delta_l1,
+            int delta_l2, bool norm_after_dyn, int hip_device, bool bug_compat, int engine, int method, int lpc_order);
+
 private:
     void check(int status) const;
     mfx_handle *m_handle;
+};
+
+// PLP cepstra (PLP) behind the same interface: MfccHip's arguments with the LPC model order after lift_coef
+// (0 = 8, the reference CLI's --model-order default).  Same output width and row layout as the MFCC configuration.
+class PlpHip : public MfccHip {
+public:
+    PlpHip(int input_buffer_size, int window_size, int shift, int num_banks, float sample_rate, float low_freq,
+           float high_freq, int ceps_len, bool want_c0, float lift_coef, int lpc_order,
+           Normalizer::norm_t norm = Normalizer::NORM_NONE, dyn_t dyn = DYN_NONE, int delta_l1 = 1, int delta_l2 = 1,
+           bool norm_after_dyn = true, int hip_device = 0, bool bug_compat = true, int engine = 0);
 };
 
 #endif // AFET_PARAM_H

@@ -53,6 +53,23 @@ MfccHip::MfccHip(int input_buffer_size, int window_size, int shift, int num_bank
                  float low_freq, float high_freq, int ceps_len, bool want_c0, float lift_coef,
                  Normalizer::norm_t norm, dyn_t dyn, int delta_l1, int delta_l2, bool norm_after_dyn, int hip_device,
                  bool bug_compat, int engine)
+    : MfccHip(input_buffer_size, window_size, shift, num_banks, sample_rate, low_freq, high_freq, ceps_len, want_c0, lift_coef,
+              norm, dyn, delta_l1, delta_l2, norm_after_dyn, hip_device, bug_compat, engine, MFX_METHOD_MFCC, 0)
+{
+}
+
+PlpHip::PlpHip(int input_buffer_size, int window_size, int shift, int num_banks, float sample_rate, float low_freq,
+               float high_freq, int ceps_len, bool want_c0, float lift_coef, int lpc_order, Normalizer::norm_t norm, dyn_t dyn,
+               int delta_l1, int delta_l2, bool norm_after_dyn, int hip_device, bool bug_compat, int engine)
+    : MfccHip(input_buffer_size, window_size, shift, num_banks, sample_rate, low_freq, high_freq, ceps_len, want_c0, lift_coef,
+              norm, dyn, delta_l1, delta_l2, norm_after_dyn, hip_device, bug_compat, engine, MFX_METHOD_PLP, lpc_order)
+{
+}
+
+MfccHip::MfccHip(int input_buffer_size, int window_size, int shift, int num_banks, float sample_rate, float low_freq,
+                 float high_freq, int ceps_len, bool want_c0, float lift_coef, Normalizer::norm_t norm, dyn_t dyn,
+                 int delta_l1, int delta_l2, bool norm_after_dyn, int hip_device, bool bug_compat, int engine, int method,
+                 int lpc_order)
     : MfccBase(input_buffer_size, window_size, shift, num_banks, sample_rate, low_freq, high_freq, ceps_len, want_c0,
                lift_coef, norm, dyn, delta_l1, delta_l2, norm_after_dyn),
       m_handle(nullptr)
@@ -75,8 +92,13 @@ MfccHip::MfccHip(int input_buffer_size, int window_size, int shift, int num_bank
     cfg.norm_after_dyn = norm_after_dyn ? 1 : 0;
     cfg.bug_compat = bug_compat ? 1 : 0;
     cfg.engine = engine;
+    cfg.method = method;
+    cfg.lpc_order = lpc_order;
+    if (method != MFX_METHOD_MFCC && !mfx_method_supported(method))
+        throw std::runtime_error("MfccHip: feature method not supported by this libmfcchip.so");
     const int rc = mfx_create(&cfg, hip_device, &m_handle);
-    if (rc != MFX_OK) throw std::runtime_error(std::string("MfccHip: ") + mfx_status_string(rc));
+    if (rc != MFX_OK)
+        throw std::runtime_error(std::string(method == MFX_METHOD_PLP ? "PlpHip: " : "MfccHip: ") + mfx_status_string(rc));
 }
 
 MfccHip::~MfccHip() { mfx_destroy(m_handle); }

@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 
 NORM_NONE, NORM_CMN, NORM_CVN, NORM_MINMAX = 0, 1, 2, 3   # normalizer.h:5
 DYN_NONE, DYN_DELTA, DYN_ACC = 0, 1, 2                     # parambase.h:9
+METHOD_MFCC, METHOD_PLP = 0, 1                             # mfx_config.method (include/mfx.h)
 
 
 class MfxError(RuntimeError):
@@ -47,7 +48,8 @@ class MfxConfig(C.Structure):
         ("batch_norm_stats", C.c_int32),
         ("engine", C.c_int32),
         ("tail_split", C.c_int32),
-        ("reserved", C.c_int32 * 2),
+        ("method", C.c_int32),
+        ("lpc_order", C.c_int32),
     ]
 
 
@@ -64,6 +66,7 @@ EXPORTED_SYMBOLS = (
     "mfx_set_stream", "mfx_synchronize", "mfx_profile_enable", "mfx_profile_read",
     "mfx_dominant_kernel_name", "mfx_debug_read", "mfx_plan_create", "mfx_plan_set_aligned",
     "mfx_host_mel_table", "mfx_host_dct_matrix", "mfx_host_frame_count",
+    "mfx_method_supported", "mfx_host_plp_tables",
 )
 
 
@@ -129,6 +132,8 @@ def load_library():
     L.mfx_host_mel_table.argtypes = [i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, fp, C.POINTER(i32)]
     L.mfx_host_dct_matrix.argtypes = [i32, i32, i32, C.c_float, fp]
     L.mfx_host_frame_count.argtypes, L.mfx_host_frame_count.restype = [i64, i32, i32], i64
+    L.mfx_method_supported.argtypes = [i32]
+    L.mfx_host_plp_tables.argtypes = [i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, i32, fp, fp]
     _lib = L
     return L
 
@@ -197,6 +202,31 @@ def host_dct_matrix(num_banks, ceps_len, want_c0, lift_coef):
     return m
 
 
+def method_supported(method):
+    """True when the loaded library computes feature method `method` (METHOD_*)."""
+    return bool(load_library().mfx_method_supported(int(method)))
+
+
+def _check_method(method):
+    # a library older than mfx_config.method ignores the field and would quietly return MFCC
+    if int(method) != METHOD_MFCC and not method_supported(method):
+        raise MfxError(-5, "feature method %d is not supported by %s" % (int(method), library_path()))
+
+
+def host_plp_tables(num_banks, fft_size, sample_rate, low_freq, high_freq, alpha=1.0, lpc_order=8):
+    """PLP tables exactly as uploaded (host code, no GPU needed): equal-loudness weights [num_banks] and the
+    autocorrelation basis [lpc_order + 1][num_banks + 2]."""
+    L = load_library()
+    eql = np.zeros(num_banks, dtype=np.float32)
+    idft = np.zeros((lpc_order + 1, num_banks + 2), dtype=np.float32)
+    fpt = C.POINTER(C.c_float)
+    rc = L.mfx_host_plp_tables(int(num_banks), int(fft_size), float(sample_rate), float(low_freq), float(high_freq),
+                               float(alpha), int(lpc_order), eql.ctypes.data_as(fpt), idft.ctypes.data_as(fpt))
+    if rc != 0:
+        raise MfxError(rc, "mfx_host_plp_tables failed")
+    return eql, idft
+
+
 def host_frame_count(samples, window_size, shift):
     return int(load_library().mfx_host_frame_count(int(samples), int(window_size), int(shift)))
 
@@ -210,7 +240,7 @@ def reference_window(window_size):
 
 
 def plan_kernel(window_size, shift, num_banks, sample_rate, ceps_len, want_c0=False, dyn=DYN_NONE, fft_size=0, channels=1,
-                aligned=True, engine=0, low_freq=64.0, high_freq=None, input_buffer_size=0):
+                aligned=True, engine=0, low_freq=64.0, high_freq=None, input_buffer_size=0, method=METHOD_MFCC, lpc_order=0):
     """Which front-end kernel the batch entries run for a shape -- asked of a PLANNING handle (mfx_plan_create: the
     library's own configuration checks, host-built tables and LDS sums, no device, nothing computed).  Works without a
     GPU; returns the kernel's name as rocprofv3 prints it.  Raises MfxError for a configuration mfx_create refuses."""
@@ -219,6 +249,8 @@ def plan_kernel(window_size, shift, num_banks, sample_rate, ceps_len, want_c0=Fa
                     float(sample_rate), float(low_freq), float(sample_rate / 2 if high_freq is None else high_freq),
                     int(ceps_len), int(bool(want_c0)), 22.0, NORM_NONE, int(dyn), 3, 3, 1, int(fft_size), int(channels), 1, 0,
                     int(engine), 0)
+    _check_method(method)
+    cfg.method, cfg.lpc_order = int(method), int(lpc_order)
     h = C.c_void_p()
     rc = L.mfx_plan_create(C.byref(cfg), C.byref(h))
     if rc != 0:
@@ -277,19 +309,22 @@ class MfccHip:
     """Python mirror of ``class MfccHip : public MfccBase`` (host/afet_param.h).
 
     Constructor arguments are those of MfccBase (mfccbase.h:21-35) in the same order; ``device``
-    replaces MfccOpenCL's trailing ``cl_device_id`` (mfccopencl.h:60).
+    replaces MfccOpenCL's trailing ``cl_device_id`` (mfccopencl.h:60).  ``method=METHOD_PLP`` computes PLP cepstra
+    of model order ``lpc_order`` (0 = 8) instead of MFCC, with the same interface and output layout.
     """
 
     def __init__(self, input_buffer_size, window_size, shift, num_banks, sample_rate, low_freq, high_freq,
                  ceps_len, want_c0, lift_coef, norm=NORM_NONE, dyn=DYN_NONE, delta_l1=1, delta_l2=1,
                  norm_after_dyn=True, device=0, fft_size=0, channels=1, bug_compat=True, batch_norm_stats=0, engine=0,
-                 tail_split=0):
+                 tail_split=0, method=METHOD_MFCC, lpc_order=0):
         self._L = load_library()
+        _check_method(method)
         self.cfg = MfxConfig(int(input_buffer_size), int(window_size), int(shift), int(num_banks),
                              float(sample_rate), float(low_freq), float(high_freq), int(ceps_len),
                              int(bool(want_c0)), float(lift_coef), int(norm), int(dyn), int(delta_l1),
                              int(delta_l2), int(bool(norm_after_dyn)), int(fft_size), int(channels),
-                             int(bool(bug_compat)), int(batch_norm_stats), int(engine), int(tail_split))
+                             int(bool(bug_compat)), int(batch_norm_stats), int(engine), int(tail_split),
+                             int(method), int(lpc_order))
         h = C.c_void_p()
         rc = self._L.mfx_create(C.byref(self.cfg), int(device), C.byref(h))
         if rc != 0:

@@ -84,8 +84,16 @@ typedef struct mfx_config {
                                   agree to float32 rounding either way                                               */
     int32_t tail_split;        /* fused batch front ends: the last `tail_split` chunks of every wave of the grid are cut
                                   into 4-frame pieces so that the launch ends evenly; 0 = default (2), -1 = off        */
-    int32_t reserved[2];
+    int32_t method;            /* MFX_METHOD_*: 0 = MFCC; 1 = PLP cepstra (PLP): the same spectrum and mel
+                                  table on power, equal loudness, cube root, LPC of order lpc_order, its cepstrum with the
+                                  MFCC lifter; ceps_len >= 1 (no log-energy form); same output width and layout.  Check
+                                  mfx_method_supported first: a library older than this field ignores it (returns MFCC) */
+    int32_t lpc_order;         /* PLP: model order p, 1 .. min(32, num_banks); 0 = 8 (the reference CLI's default).
+                                  Ignored for MFCC                                                                   */
 } mfx_config;
+
+/* mfx_config.method */
+enum { MFX_METHOD_MFCC = 0, MFX_METHOD_PLP = 1 };
 
 /* mfx_config.engine bits */
 #define MFX_ENGINE_NO_FRONT1024 1 /* 1024-point short-window configurations stay on the generic long-transform kernel  */
@@ -119,6 +127,8 @@ const char *mfx_last_error(const mfx_handle *h);
 /* message for a status code when no handle exists (mfx_create failure) */
 const char *mfx_status_string(int status);
 int mfx_abi_version(void);
+/* 1 when this library computes mfx_config.method `method` (MFX_METHOD_*), else 0 */
+int mfx_method_supported(int32_t method);
 
 /* ---- streaming parameterizer interface, one function per ParamBase method (parambase.h:23-32) ---- */
 
@@ -241,13 +251,20 @@ int mfx_host_mel_lane_plan(int32_t lanes, int32_t num_banks, int32_t fft_size, c
 /* Operands of the DCT on the matrix pipe, [tile][K step][lane]; returns their count.  Test / inspection aid. */
 int64_t mfx_host_dct_mfma_operands(int32_t num_banks, int32_t dct_len, const float *matrix, float *out, int64_t out_cap,
                                    int32_t *tiles, int32_t *ksteps);
+/* PLP tables as uploaded (PLP): equal-loudness weights eql [num_banks] at the (warped) filter centres, and the
+ * cosine basis of the autocorrelation idft [lpc_order + 1][num_banks + 2] (r_i = sum_m idft[i][m] A_m).  Neither depends on
+ * fft_size; it is taken for symmetry with mfx_host_mel_table */
+int mfx_host_plp_tables(int32_t num_banks, int32_t fft_size, float sample_rate, float low_freq, float high_freq, float alpha,
+                        int32_t lpc_order, float *eql, float *idft);
 /* frame count, integer arithmetic (parambase.cpp:16-19 without the float32 division) */
 int64_t mfx_host_frame_count(int64_t samples, int32_t window_size, int32_t shift);
 
 /* ---- test taps (device -> host copies of intermediate tables; used by the parity tests) ---- */
 /* kind: 0 = mel table [2][fft_size] floats, 1 = filter_beg [num_banks+2] int32,
  *       2 = DCT matrix [num_banks][dct_len] floats, 3 = magnitude spectrum of the current block
- *       [frames_with_context][fft_size/2+1] floats.  Returns element count or <0. */
+ *       [frames_with_context][fft_size/2+1] floats, 5 / 6 = normaliser statistics of the last streaming apply / batch run,
+ *       7 = PLP autocorrelations r_0 .. r_p of the last plain streaming apply [frames_with_context][lpc_order + 1] floats
+ *       (MFCC handles: 0 elements).  Returns element count or <0. */
 int64_t mfx_debug_read(mfx_handle *h, int kind, void *dst, int64_t dst_bytes);
 
 #ifdef __cplusplus
