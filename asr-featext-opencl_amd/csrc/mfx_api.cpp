@@ -13,6 +13,7 @@
 #include <cstring>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "mfx_kernels.h"
@@ -36,16 +37,34 @@ constexpr int kChunkFrames = 16; // frames per work item of the front-end kernel
 // shape -> kernel table of DESIGN.md section 5 is pinned by a test that needs no GPU.  It computes nothing.
 thread_local bool t_planning = false;
 
+// device memory, freed with its owner
 template <class T>
 struct DevBuf {
     T *p = nullptr;
     size_t n = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept { *this = std::move(o); }
+    DevBuf &operator=(DevBuf &&o) noexcept // (o frees what this held)
+    {
+        std::swap(p, o.p), std::swap(n, o.n);
+        return *this;
+    }
+    ~DevBuf() { release(); }
+    // (planning handles: records the size, allocates nothing)
     hipError_t alloc(size_t count)
     {
         release();
+        if (count > 0 && !t_planning) {
+            const hipError_t e = hipMalloc((void **)&p, count * sizeof(T));
+            if (e != hipSuccess) {
+                p = nullptr;
+                return e;
+            }
+        }
         n = count;
-        if (count == 0 || t_planning) return hipSuccess;
-        return hipMalloc((void **)&p, count * sizeof(T));
+        return hipSuccess;
     }
     void release()
     {
@@ -53,6 +72,47 @@ struct DevBuf {
         p = nullptr;
         n = 0;
     }
+};
+
+// page-locked host memory, freed with its owner
+template <class T>
+struct PinnedBuf {
+    T *p = nullptr;
+    size_t n = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+    ~PinnedBuf()
+    {
+        if (p) (void)hipHostFree(p);
+    }
+    // fewer than `need` elements: wait for `stream` (work on it may still use the old block), then replace the block by
+    // one of `want` (>= need) elements
+    hipError_t grow(size_t need, size_t want, hipStream_t stream)
+    {
+        if (n >= need) return hipSuccess;
+        if (hipError_t e = hipStreamSynchronize(stream); e != hipSuccess) return e;
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        n = 0;
+        if (hipError_t e = hipHostMalloc((void **)&p, want * sizeof(T), hipHostMallocDefault); e != hipSuccess) {
+            p = nullptr;
+            return e;
+        }
+        n = want;
+        return hipSuccess;
+    }
+};
+
+// What k_melcep / k_plp read for n warp factors: the mel tables (mel_w [n][2 * W2], mel_beg [n][nb + 2]), one 64-lane
+// plan per table padded to a common row stride (w64 [n][64][row_stride], start64 / fid64 [n][rounds][64], L64 [n][8]) and,
+// for PLP, the equal-loudness weights (eql [n][nb]).
+struct CepTables {
+    DevBuf<float> mel_w, w64, eql;
+    DevBuf<int32_t> mel_beg, start64, fid64, L64;
+    int rounds = 0, row_stride = 0;
+    std::vector<float> alphas; // the warp factors the tables hold (empty: none)
+    bool holds(const float *a, int n) const { return !alphas.empty() && (int)alphas.size() == n && std::equal(a, a + n, alphas.begin()); }
 };
 
 } // namespace
@@ -79,29 +139,25 @@ struct mfx_handle {
     int nm16 = 16;
     bool plp = false;  // mfx_config.method == MFX_METHOD_PLP: k_plp where MFCC runs k_melcep, never the fused front ends
     int lpc = 0;       // PLP model order (lpc_order, 0 -> 8)
-    float alpha = 1.f, table_alpha = -1.f;
+    float alpha = 1.f;
     bool have_window = false;
 
     // tables in HBM
     DevBuf<float> d_win1024o;
-    DevBuf<float> d_window, d_winpair, d_twid_pass, d_twid_half, d_twid_split, d_twid_reg, d_mel_w, d_dct;
-    DevBuf<int32_t> d_mel_beg;
-    DevBuf<int32_t> d_mel64_L;                       // [8] of the handle's own plan (k_melcep reads L from memory)
-    // VTLN sweep: one 64-lane plan per alpha, padded to a common row stride
-    DevBuf<float> d_sweep64_w;
-    DevBuf<int32_t> d_sweep64_start, d_sweep64_fid, d_sweep64_L;
-    int sweep64_rs = 0;
-    // PLP: equal-loudness weights of the handle's alpha / of every sweep alpha, autocorrelation basis, lifter, r taps
-    DevBuf<float> d_plp_eql, d_sweep_eql, d_plp_idft, d_plp_lift, d_plp_r;
+    DevBuf<float> d_window, d_winpair, d_twid_pass, d_twid_half, d_twid_split, d_twid_reg, d_dct;
+    // k_melcep / k_plp tables of the handle's alpha (also the fused front ends' mel table and 64-lane plan) and of the
+    // last VTLN sweep's alphas
+    CepTables own, sweep;
+    // PLP: autocorrelation basis, lifter, r taps
+    DevBuf<float> d_plp_idft, d_plp_lift, d_plp_r;
     // 512-point kernel: per-lane mel plan + transposed DCT matrix
     DevBuf<float> d_mel_lane_w, d_dct_t;
     DevBuf<int32_t> d_mel_lane_start, d_mel_lane_fid;
     MelLanePlan plan;
-    // wave-per-frame kernels (k_front_reg, fused): 64-lane mel plan + DCT operands for the matrix pipe
+    // wave-per-frame kernels (k_front_reg, fused): the 64-lane mel plan of `own` + DCT operands for the matrix pipe
     MelWavePlan wplan;
     bool wplan_ok = false;
-    DevBuf<float> d_mel64_w, d_dct_b;
-    DevBuf<int32_t> d_mel64_start, d_mel64_fid;
+    DevBuf<float> d_dct_b;
     DevBuf<float> d_dct_b4;                          // k_front2048: DCT operands as 16-byte words
     DevBuf<float> d_dct_b4s;                         // k_front2048: the split form for <= 40 columns (or empty)
     int dct_split = 0;
@@ -126,25 +182,21 @@ struct mfx_handle {
     DevBuf<Chunk> d_chunks_stream;
     int stream_chunk_frames = 16;
     int n_chunks_stream_max = 0;
-    int16_t *h_stage = nullptr; // pinned
-    size_t h_stage_n = 0;
+    PinnedBuf<int16_t> h_stage;
     // small-block handles (every block under 1 MB): the carried tail stays on the HOST, inside the pinned staging buffer, and
     // goes up again in front of the next block -- one copy kernel per set_input instead of copy + device-to-device tail copy
     bool host_tail = false;
     size_t stage_tail_off = 0;  // samples: where the pending tail (h->remaining samples) starts in h_stage
-    float *h_out_stage = nullptr;         // pinned staging of get_output_data (allocated on first use)
-    size_t h_out_stage_n = 0;
+    PinnedBuf<float> h_out_stage;         // staging of get_output_data (allocated on first use)
     bool rows_in_stage = false;           // the current block's PLAIN rows were written straight into h_out_stage by the delta
                                           // kernel (set by a plain apply only; cleared by set_input and flush)
-    float *h_alpha_stage = nullptr;       // pinned staging of get_output_data_alpha: never h_out_stage, which may hold the
-    size_t h_alpha_stage_n = 0;           // plain rows a later get_output_data returns
+    PinnedBuf<float> h_alpha_stage;       // staging of get_output_data_alpha: never h_out_stage, which may hold the plain rows
+                                          // a later get_output_data returns
     hipEvent_t ev_copy[16] = {};          // chunk events of the pipelined device-to-host copy
-    // VTLN sweep (mfx_apply_alphas): one filterbank, one static and one output block per alpha
-    std::vector<float> sweep_alphas;      // alphas of the tables currently in d_sweep_w
+    // VTLN sweep (mfx_apply_alphas): one filterbank (`sweep`), one static and one output block per alpha
     int sweep_cap = 0;                    // alphas the sweep buffers hold
     int sweep_n = 0;                      // alphas of the current block's last sweep (0: none since set_input / flush)
-    DevBuf<float> d_sweep_w, d_sweep_src, d_sweep_blk, d_sweep_stats;
-    DevBuf<int32_t> d_sweep_beg;
+    DevBuf<float> d_sweep_src, d_sweep_blk, d_sweep_stats;
     DevBuf<Segment> d_sweep_segs;         // [2][sweep_cap]: rows with context, rows delivered
 
     // batch plan
@@ -187,6 +239,23 @@ struct mfx_handle {
     size_t prof_used = 0;
     int prof_launches = 0;
     double prof_ms = 0;
+
+    // (the buffers free themselves after this; mfx_destroy has waited for the streams)
+    ~mfx_handle()
+    {
+        for (auto &ev : prof_events) {
+            (void)hipEventDestroy(ev.first);
+            (void)hipEventDestroy(ev.second);
+        }
+        auto destroy = [](auto &events) {
+            for (hipEvent_t e : events)
+                if (e) (void)hipEventDestroy(e);
+        };
+        destroy(ev_front), destroy(ev_tail), destroy(ev_up), destroy(ev_run), destroy(ev_copy);
+        for (hipStream_t s : {stream2, stream_up, stream_dn})
+            if (s) (void)hipStreamDestroy(s);
+        if (own_stream && stream) (void)hipStreamDestroy(stream);
+    }
 };
 
 namespace {
@@ -219,84 +288,152 @@ hipError_t upload(DevBuf<T> &b, const std::vector<T> &v)
 
 void fill_front(const mfx_handle *h, FrontParams &p);
 
-// rebuild the alpha-dependent mel table if needed (the reference re-derives it on every apply(),
-// mfcccpu.cpp:194; here only when alpha actually changed)
+// k_melcep parameters that do not depend on the caller, for the tables `t` (the handle's own or the sweep's)
+void fill_melcep(const mfx_handle *h, const CepTables &t, MelcepParams &mp)
+{
+    std::memset(&mp, 0, sizeof(mp));
+    mp.spec_pitch = h->spec_pitch;
+    mp.fft_size = h->W2;
+    mp.mel_w = t.mel_w.p;
+    mp.mel_beg = t.mel_beg.p;
+    mp.mel64_w = t.w64.p;
+    mp.mel64_start = t.start64.p;
+    mp.mel64_fid = t.fid64.p;
+    mp.mel64_L = t.L64.p;
+    mp.mel64_rounds = t.rounds;
+    mp.mel64_row_stride = t.row_stride;
+    mp.mag_floats = std::max(h->W2, (h->spec_pitch + 3) & ~3);
+    mp.dct = h->ceps > 0 ? h->d_dct.p : nullptr;
+    mp.dct_b4 = h->ceps > 0 ? h->d_dct_b4.p : nullptr;
+    mp.dct_ksteps = h->dct_ksteps;
+    mp.num_banks = h->nb;
+    mp.dct_len = h->dl;
+    mp.cols = h->cols;
+    mp.mel_w_stride = (int64_t)2 * h->W2;
+    mp.mel_beg_stride = h->nb + 2;
+}
+
+// k_plp parameters that do not depend on the caller (the PLP twin of fill_melcep)
+void fill_plp(const mfx_handle *h, const CepTables &t, PlpParams &pp)
+{
+    MelcepParams mp;
+    fill_melcep(h, t, mp);
+    std::memset(&pp, 0, sizeof(pp));
+    pp.spec_pitch = mp.spec_pitch;
+    pp.fft_size = mp.fft_size;
+    pp.num_banks = h->nb;
+    pp.lpc_order = h->lpc;
+    pp.ceps_len = h->ceps;
+    pp.want_c0 = h->cfg.want_c0 ? 1 : 0;
+    pp.cols = h->cols;
+    pp.mel64_w = mp.mel64_w;
+    pp.mel64_start = mp.mel64_start;
+    pp.mel64_fid = mp.mel64_fid;
+    pp.mel64_L = mp.mel64_L;
+    pp.mel64_rounds = mp.mel64_rounds;
+    pp.mel64_row_stride = mp.mel64_row_stride;
+    pp.mag_floats = mp.mag_floats;
+    pp.eql = t.eql.p;
+    pp.idft = h->d_plp_idft.p;
+    pp.lift = h->d_plp_lift.p;
+}
+
+// (Re)build `t` for the n warp factors `alphas` (nothing to do when it holds them already): mel tables, 64-lane plans padded
+// to the longest plan's row stride (a row's rounds lie back to back from its start, so padding at the end changes nothing;
+// one table keeps its own stride) and PLP's equal-loudness weights.  first / first_plan (optional) receive table 0's mel
+// table and 64-lane plan.
+int build_cep_tables(mfx_handle *h, const float *alphas, int n, CepTables &t, MelTable *first = nullptr,
+                     MelWavePlan *first_plan = nullptr)
+{
+    if (t.holds(alphas, n)) return MFX_OK;
+    t.alphas.clear(); // (until every table below is in place)
+    const size_t wstride = (size_t)2 * h->W2, bstride = (size_t)h->nb + 2;
+    std::vector<float> w(wstride * n), eql_all;
+    std::vector<int32_t> b(bstride * n);
+    std::vector<MelWavePlan> plans((size_t)n);
+    int rs = 4;
+    for (int a = 0; a < n; ++a) {
+        MelTable mt;
+        build_mel_table(h->nb, h->W2, h->cfg.sample_rate, h->cfg.low_freq, h->cfg.high_freq, alphas[a], mt);
+        // every filter edge must address a computed bin
+        for (int v : mt.beg)
+            if (v < 0 || v > h->W2 / 2) return fail(h, MFX_ERR_CONFIG, "mel filter edge outside [0, fft_size/2]");
+        // (the kernels' magnitude buffers hold W2 floats: bins 0 .. W2/2, finite words beyond)
+        if (!build_mel_wave_plan(mt, h->nb, h->W2, /*max_read_bin=*/h->W2 - 1, plans[a]))
+            return fail(h, MFX_ERR_CONFIG, "mel filterbank does not fit the kernels' lane plan (more than 512 filters?)");
+        rs = std::max(rs, plans[a].row_stride);
+        std::copy(mt.weights.begin(), mt.weights.end(), w.begin() + wstride * a);
+        std::copy(mt.beg.begin(), mt.beg.end(), b.begin() + bstride * a);
+        if (h->plp) {
+            std::vector<float> eql, idft;
+            build_plp_tables(h->nb, h->cfg.sample_rate, h->cfg.low_freq, h->cfg.high_freq, alphas[a], h->lpc, eql, idft);
+            eql_all.insert(eql_all.end(), eql.begin(), eql.end());
+        }
+        if (a == 0 && first) *first = std::move(mt);
+    }
+    t.rounds = plans[0].rounds; // (ceil(nb / 64) for every alpha)
+    t.row_stride = rs;
+    {   // k_melcep / k_plp stage the weight rows (one per filter-carrying lane) + one wave's buffers in LDS.  rows x row
+        // stride is at most ~4 x W2 floats for the reference's triangular banks, so every transform up to 4096 points fits
+        // whatever the filter count (4096 points, 48 kHz, 20 filters: 20 rows of 600 floats = 48 KB); 8192 points and more
+        // with few, wide filters do not: refuse here (a CONFIG error at the call, not a launch failure later)
+        MelcepParams mp;
+        fill_melcep(h, t, mp);
+        if (melcep_lds_bytes(mp, 1) > 160 * 1024)
+            return fail(h, MFX_ERR_CONFIG, "mel filterbank does not fit the kernels' LDS (very wide filters on a long transform)");
+        if (h->plp) {
+            PlpParams pp;
+            fill_plp(h, t, pp);
+            if (plp_lds_bytes(pp, 1) > 160 * 1024) return fail(h, MFX_ERR_CONFIG, "mel filterbank does not fit the PLP kernel's LDS");
+        }
+    }
+    std::vector<float> pw((size_t)n * 64 * rs, 0.f);
+    std::vector<int32_t> pst((size_t)n * 64 * t.rounds), pfid((size_t)n * 64 * t.rounds), pL((size_t)n * 8);
+    for (int a = 0; a < n; ++a) {
+        const MelWavePlan &pl = plans[a];
+        for (int j = 0; j < 64; ++j)
+            std::copy(pl.w.begin() + (size_t)j * pl.row_stride, pl.w.begin() + (size_t)(j + 1) * pl.row_stride,
+                      pw.begin() + ((size_t)a * 64 + j) * rs);
+        std::copy(pl.start.begin(), pl.start.end(), pst.begin() + (size_t)a * 64 * t.rounds);
+        std::copy(pl.fid.begin(), pl.fid.end(), pfid.begin() + (size_t)a * 64 * t.rounds);
+        std::copy(pl.L, pl.L + 8, pL.begin() + (size_t)a * 8);
+    }
+    if (!t_planning) HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, upload(t.mel_w, w));
+    HIP_TRY(h, upload(t.mel_beg, b));
+    HIP_TRY(h, upload(t.w64, pw));
+    HIP_TRY(h, upload(t.start64, pst));
+    HIP_TRY(h, upload(t.fid64, pfid));
+    HIP_TRY(h, upload(t.L64, pL));
+    if (h->plp) HIP_TRY(h, upload(t.eql, eql_all));
+    if (first_plan) *first_plan = std::move(plans[0]);
+    t.alphas.assign(alphas, alphas + n);
+    return MFX_OK;
+}
+
+// rebuild the tables of the handle's alpha if needed (the reference re-derives them on every apply(), mfcccpu.cpp:194; here
+// only when alpha actually changed).  The 64-lane plan serves every configuration (k_melcep / k_plp for the streaming
+// apply(), sweeps and the spectrum path of the batch entry; k_front_reg / k_front_wave fused); the fused front ends'
+// own lane plans are derived here too.
 int refresh_mel(mfx_handle *h)
 {
-    if (h->table_alpha == h->alpha && h->d_mel_w.p) return MFX_OK;
+    if (h->own.holds(&h->alpha, 1)) return MFX_OK;
+    h->fused_ok = h->wplan_ok = h->wplan32_ok = false;
     MelTable t;
-    build_mel_table(h->nb, h->W2, h->cfg.sample_rate, h->cfg.low_freq, h->cfg.high_freq, h->alpha, t);
-    // every filter edge must address a computed bin
-    for (int v : t.beg)
-        if (v < 0 || v > h->W2 / 2) return fail(h, MFX_ERR_CONFIG, "mel filter edge outside [0, fft_size/2]");
-    if (!t_planning) HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, upload(h->d_mel_w, t.weights));
-    HIP_TRY(h, upload(h->d_mel_beg, t.beg));
-    h->fused_ok = false;
-    if (h->fast512 && build_mel_lane_plan(t, h->nb, h->W2, /*max_read_bin=*/511 - 32, h->plan)) {
+    const int rc = build_cep_tables(h, &h->alpha, 1, h->own, &t, &h->wplan);
+    if (rc != MFX_OK) return rc;
+    h->wplan_ok = true;
+    // the 16-lane plan of k_front512, or of k_front1024 (bins up to 527 may be read (times zero weights): the slot keeps 264
+    // words for each of the even / odd arrays)
+    if ((h->fast512 || h->fast1024) &&
+        build_mel_lane_plan(t, h->nb, h->W2, /*max_read_bin=*/h->fast512 ? 511 - 32 : 527, h->plan, /*align=*/h->fast512 ? 2 : 4)) {
         HIP_TRY(h, upload(h->d_mel_lane_w, h->plan.w));
         HIP_TRY(h, upload(h->d_mel_lane_start, h->plan.start));
         HIP_TRY(h, upload(h->d_mel_lane_fid, h->plan.fid));
         FrontParams probe;
         fill_front(h, probe);
-        h->fused_ok = front512_lds_bytes(probe) <= 160 * 1024;
+        h->fused_ok = (h->fast512 ? front512_lds_bytes(probe) : front1024_lds_bytes(probe)) <= 160 * 1024;
     }
-    if (h->fast1024) {
-        // bins up to 527 may be read (times zero weights): the slot keeps 264 words for each of the even / odd arrays
-        h->fused_ok = false;
-        if (build_mel_lane_plan(t, h->nb, h->W2, /*max_read_bin=*/527, h->plan, /*align=*/4)) {
-            HIP_TRY(h, upload(h->d_mel_lane_w, h->plan.w));
-            HIP_TRY(h, upload(h->d_mel_lane_start, h->plan.start));
-            HIP_TRY(h, upload(h->d_mel_lane_fid, h->plan.fid));
-            FrontParams probe;
-            fill_front(h, probe);
-            h->fused_ok = front1024_lds_bytes(probe) <= 160 * 1024;
-        }
-    }
-    // The 64-lane plan (whole filters walked on a wave's lanes): k_front_reg / k_front_wave fused, and k_melcep -- the
-    // streaming apply(), sweeps and the spectrum path of the batch entry, i.e. EVERY configuration needs it.  The kernels'
-    // magnitude buffers hold W2 floats (bins 0 .. W2/2, finite words beyond).
-    h->wplan_ok = false;
-    if (!build_mel_wave_plan(t, h->nb, h->W2, /*max_read_bin=*/h->W2 - 1, h->wplan))
-        return fail(h, MFX_ERR_CONFIG, "mel filterbank does not fit the kernels' lane plan (more than 512 filters?)");
-    HIP_TRY(h, upload(h->d_mel64_w, h->wplan.w));
-    HIP_TRY(h, upload(h->d_mel64_start, h->wplan.start));
-    HIP_TRY(h, upload(h->d_mel64_fid, h->wplan.fid));
-    {
-        std::vector<int32_t> L(h->wplan.L, h->wplan.L + 8);
-        HIP_TRY(h, upload(h->d_mel64_L, L));
-    }
-    {   // apply() runs k_melcep for every configuration: its tables (one weight row per filter-carrying lane, mel64_rows)
-        // + one wave's buffers must fit the CU's LDS.  rows x row stride is at most ~4 x W2 floats for the reference's
-        // triangular banks, so every transform up to 4096 points fits whatever the filter count (4096 points, 48 kHz,
-        // 20 filters: 20 rows of 600 floats = 48 KB; refused until round 4, when all 64 lanes' rows were staged); 8192
-        // points and more with few, wide filters do not: refuse here, not at the first apply()
-        MelcepParams probe;
-        std::memset(&probe, 0, sizeof(probe));
-        probe.num_banks = h->nb;
-        probe.mel64_rounds = h->wplan.rounds;
-        probe.mel64_row_stride = h->wplan.row_stride;
-        probe.mag_floats = std::max(h->W2, (h->spec_pitch + 3) & ~3);
-        if (melcep_lds_bytes(probe, 1) > 160 * 1024)
-            return fail(h, MFX_ERR_CONFIG, "mel filterbank does not fit the kernels' LDS (very wide filters on a long transform)");
-    }
-    if (h->plp) {
-        std::vector<float> eql, idft;
-        build_plp_tables(h->nb, h->cfg.sample_rate, h->cfg.low_freq, h->cfg.high_freq, h->alpha, h->lpc, eql, idft);
-        HIP_TRY(h, upload(h->d_plp_eql, eql));
-        PlpParams probe;
-        std::memset(&probe, 0, sizeof(probe));
-        probe.num_banks = h->nb;
-        probe.lpc_order = h->lpc;
-        probe.ceps_len = h->ceps;
-        probe.mel64_rounds = h->wplan.rounds;
-        probe.mel64_row_stride = h->wplan.row_stride;
-        probe.mag_floats = std::max(h->W2, (h->spec_pitch + 3) & ~3);
-        if (plp_lds_bytes(probe, 1) > 160 * 1024)
-            return fail(h, MFX_ERR_CONFIG, "mel filterbank does not fit the PLP kernel's LDS");
-    }
-    h->wplan_ok = true;
-    h->wplan32_ok = false;
     if (h->fast2048) { // k_front2048 walks the filters on the 32 lanes of each of a wave's two frames
         if (build_mel_wave_plan(t, h->nb, h->W2, /*max_read_bin=*/1039, h->wplan32, /*lanes=*/32)) {
             HIP_TRY(h, upload(h->d_mel32_w, h->wplan32.w));
@@ -312,7 +449,6 @@ int refresh_mel(mfx_handle *h)
             h->wplan32_ok = front2048_lds_bytes(probe) <= 160 * 1024;
         }
     }
-    h->table_alpha = h->alpha;
     return MFX_OK;
 }
 
@@ -331,8 +467,8 @@ void fill_front(const mfx_handle *h, FrontParams &p)
     p.twid_half = h->d_twid_half.p;
     p.twid_reg = h->d_twid_reg.p;
     p.twid_split = h->d_twid_split.p;
-    p.mel_w = h->d_mel_w.p;
-    p.mel_beg = h->d_mel_beg.p;
+    p.mel_w = h->own.mel_w.p;
+    p.mel_beg = h->own.mel_beg.p;
     p.dct = h->ceps > 0 ? h->d_dct.p : nullptr;
     p.num_banks = h->nb;
     p.dct_len = h->dl;
@@ -346,9 +482,9 @@ void fill_front(const mfx_handle *h, FrontParams &p)
     p.mel_row_stride = h->plan.row_stride;
     for (int i = 0; i < 8; ++i) p.mel_L[i] = h->plan.L[i];
     p.dct_mode = (h->ceps > 0 && h->cols <= 16 && h->nb <= 40) ? 1 : 0; // DCT on the matrix pipe
-    p.mel64_w = h->d_mel64_w.p;
-    p.mel64_start = h->d_mel64_start.p;
-    p.mel64_fid = h->d_mel64_fid.p;
+    p.mel64_w = h->own.w64.p;
+    p.mel64_start = h->own.start64.p;
+    p.mel64_fid = h->own.fid64.p;
     p.mel64_rounds = h->wplan_ok ? h->wplan.rounds : 0;
     p.mel64_row_stride = h->wplan_ok ? h->wplan.row_stride : 0;
     for (int i = 0; i < 8; ++i) p.mel64_L[i] = h->wplan.L[i];
@@ -408,7 +544,7 @@ int prof_collect(mfx_handle *h)
 
 // ---- normalisation helper: stats (unless reused) + apply over one column group
 // groups > 1: the column groups col0 + g * cols (g < groups) each with statistics at stats + g * group_stats_stride
-int run_norm(mfx_handle *h, float *data, int pitch, int col0, const Segment *segs, int n_segs, const Segment *seg0,
+int run_norm(mfx_handle *h, hipStream_t stream, float *data, int pitch, int col0, const Segment *segs, int n_segs, const Segment *seg0,
              int row_off, float *stats, bool use_last, int max_rows, int groups = 1, size_t group_stats_stride = 0)
 {
     NormParams np;
@@ -416,7 +552,7 @@ int run_norm(mfx_handle *h, float *data, int pitch, int col0, const Segment *seg
     np.max_rows = max_rows;
     const size_t need = norm_partial_doubles(seg0 ? 1 : n_segs, max_rows, h->cols);
     if (need > h->d_norm_partial.n) { // (sized at create / plan time for the usual shapes: not reached in a timed loop)
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        HIP_TRY(h, hipStreamSynchronize(stream));
         HIP_TRY(h, h->d_norm_partial.alloc(need));
     }
     np.partial = h->d_norm_partial.p;
@@ -437,14 +573,14 @@ int run_norm(mfx_handle *h, float *data, int pitch, int col0, const Segment *seg
     if (!use_last && !(h->cfg.engine & MFX_ENGINE_NORM_TWO_KERNELS) && norm_fused_fits(max_rows, h->cols)) {
         np.groups = groups;
         np.group_stats_stride = (int64_t)group_stats_stride;
-        HIP_TRY(h, launch_norm_fused(np, h->stream)); // short segments: one read of the rows, ONE launch for all groups
+        HIP_TRY(h, launch_norm_fused(np, stream)); // short segments: one read of the rows, ONE launch for all groups
         return MFX_OK;
     }
     for (int g = 0; g < groups; ++g) {
         np.col0 = col0 + g * h->cols;
         np.stats = stats + (size_t)g * group_stats_stride;
-        if (!use_last) HIP_TRY(h, launch_norm_stats(np, h->stream));
-        HIP_TRY(h, launch_norm_apply(np, h->stream));
+        if (!use_last) HIP_TRY(h, launch_norm_stats(np, stream));
+        HIP_TRY(h, launch_norm_apply(np, stream));
     }
     return MFX_OK;
 }
@@ -479,92 +615,12 @@ extern "C" const char *mfx_last_error(const mfx_handle *h) { return h ? h->err.c
 extern "C" void mfx_destroy(mfx_handle *h)
 {
     if (!h) return;
-    if (h->planning) { // nothing was allocated
-        delete h;
-        return;
+    if (!h->planning) { // (a planning handle has no device behind it)
+        (void)hipSetDevice(h->device);
+        for (hipStream_t s : {h->stream, h->stream2, h->stream_up, h->stream_dn})
+            if (s) (void)hipStreamSynchronize(s);
     }
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (auto &ev : h->prof_events) {
-        (void)hipEventDestroy(ev.first);
-        (void)hipEventDestroy(ev.second);
-    }
-    h->d_window.release();
-    h->d_winpair.release();
-    h->d_win1024o.release();
-    h->d_twid_pass.release();
-    h->d_twid_half.release();
-    h->d_twid_reg.release();
-    h->d_twid_split.release();
-    h->d_mel_w.release();
-    h->d_dct.release();
-    h->d_mel_beg.release();
-    h->d_mel64_L.release();
-    h->d_sweep64_w.release();
-    h->d_sweep64_start.release();
-    h->d_sweep64_fid.release();
-    h->d_sweep64_L.release();
-    h->d_mel_lane_w.release();
-    h->d_mel64_w.release();
-    h->d_mel64_start.release();
-    h->d_mel64_fid.release();
-    h->d_dct_b.release();
-    h->d_mel32_w.release();
-    h->d_dct_b4.release();
-    h->d_dct_b4s.release();
-    h->d_mel32_start.release();
-    h->d_mel32_fid.release();
-    h->d_dct_t.release();
-    h->d_mel_lane_start.release();
-    h->d_mel_lane_fid.release();
-    h->d_carry[0].release();
-    h->d_carry[1].release();
-    h->d_spec.release();
-    h->d_src.release();
-    h->d_blk.release();
-    h->d_stats_stream.release();
-    h->d_norm_partial.release();
-    h->d_host_pcm.release();
-    h->d_host_out.release();
-    h->d_fchunks.release();
-    h->d_blk_chunk_off.release();
-    h->d_blk_tile_off.release();
-    h->d_tiles.release();
-    h->d_err.release();
-    h->d_sweep_w.release();
-    h->d_sweep_beg.release();
-    h->d_sweep_src.release();
-    h->d_sweep_blk.release();
-    h->d_sweep_stats.release();
-    h->d_sweep_segs.release();
-    h->d_chunks_stream.release();
-    h->d_chunks.release();
-    h->d_segs.release();
-    h->d_stats_batch.release();
-    h->d_spec_slab.release();
-    h->d_static16[0].release();
-    h->d_static16[1].release();
-    if (h->stream2) {
-        (void)hipStreamSynchronize(h->stream2);
-        (void)hipStreamDestroy(h->stream2);
-    }
-    for (int i = 0; i < 2; ++i) {
-        if (h->ev_front[i]) (void)hipEventDestroy(h->ev_front[i]);
-        if (h->ev_tail[i]) (void)hipEventDestroy(h->ev_tail[i]);
-    }
-    if (h->h_stage) (void)hipHostFree(h->h_stage);
-    if (h->h_out_stage) (void)hipHostFree(h->h_out_stage);
-    if (h->h_alpha_stage) (void)hipHostFree(h->h_alpha_stage);
-    if (h->stream_up) (void)hipStreamDestroy(h->stream_up);
-    if (h->stream_dn) (void)hipStreamDestroy(h->stream_dn);
-    for (int i = 0; i < 16; ++i) {
-        if (h->ev_up[i]) (void)hipEventDestroy(h->ev_up[i]);
-        if (h->ev_run[i]) (void)hipEventDestroy(h->ev_run[i]);
-    }
-    for (auto &e : h->ev_copy)
-        if (e) (void)hipEventDestroy(e);
-    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    delete h; // ~mfx_handle, then the buffers free themselves
 }
 
 namespace {
@@ -668,9 +724,7 @@ int create_impl(const mfx_config *cfg, int hip_device, mfx_handle **out)
 
     int rc = MFX_OK;
     auto bail = [&](int code) {
-        std::string msg = h->err;
         mfx_destroy(h);
-        (void)msg;
         return code;
     };
     if (!t_planning) {
@@ -802,9 +856,8 @@ int create_impl(const mfx_config *cfg, int hip_device, mfx_handle **out)
     }
     h->host_tail = !(h->cfg.engine & MFX_ENGINE_DMA_SMALL_BLOCKS) && (h->carry_capacity + 8) * sizeof(int16_t) < kSmallBlock;
     // (+ 16 bytes: small blocks are staged at the destination's alignment; host_tail: tail + block, up to the carry capacity)
-    h->h_stage_n = (h->host_tail ? h->carry_capacity : (size_t)h->input_buffer_size) + 8;
-    if (!t_planning && hipHostMalloc((void **)&h->h_stage, h->h_stage_n * sizeof(int16_t), hipHostMallocDefault) != hipSuccess)
-        return bail(MFX_ERR_DEVICE);
+    const size_t stage_n = (h->host_tail ? h->carry_capacity : (size_t)h->input_buffer_size) + 8;
+    if (!t_planning && h->h_stage.grow(stage_n, stage_n, h->stream) != hipSuccess) return bail(MFX_ERR_DEVICE);
 
     *out = h;
     return MFX_OK;
@@ -1073,22 +1126,22 @@ int upload_block(mfx_handle *h, int16_t *d_dst, const int16_t *src, size_t sampl
     if (small_block(h, bytes)) {
         // a small block: into the pinned staging buffer at the destination's alignment, then a copy KERNEL reads it over the
         // link (one launch; a DMA command of this size costs more in latency than in transfer)
-        char *stage = (char *)h->h_stage + ((uintptr_t)d_dst & 15);
+        char *stage = (char *)h->h_stage.p + ((uintptr_t)d_dst & 15);
         std::memcpy(stage, src, bytes);
         HIP_TRY(h, launch_copy_small(d_dst, stage, bytes, h->stream));
         return MFX_OK;
     }
     for (size_t off = 0; off < bytes; off += kCopyChunk) { // staging copy of chunk c+1 runs under the DMA of chunk c
         const size_t len = std::min(kCopyChunk, bytes - off);
-        host_copy((char *)h->h_stage + off, (const char *)src + off, len);
-        HIP_TRY(h, hipMemcpyAsync((char *)d_dst + off, (char *)h->h_stage + off, len, hipMemcpyHostToDevice, h->stream));
+        host_copy((char *)h->h_stage.p + off, (const char *)src + off, len);
+        HIP_TRY(h, hipMemcpyAsync((char *)d_dst + off, (char *)h->h_stage.p + off, len, hipMemcpyHostToDevice, h->stream));
     }
     return MFX_OK;
 }
 
-// device rows -> host, returns when `dst` holds them; `stage_buf` / `stage_n`: the pinned staging buffer of the caller (h_out_stage
-// for the plain rows, h_alpha_stage for a sweep's), grown here when it is too small
-int download_rows(mfx_handle *h, float *dst, const float *d_src, size_t count, float *&stage_buf, size_t &stage_n)
+// device rows -> host, returns when `dst` holds them; `stage`: the pinned staging buffer of the caller (h_out_stage for the
+// plain rows, h_alpha_stage for a sweep's), grown here when it is too small
+int download_rows(mfx_handle *h, float *dst, const float *d_src, size_t count, PinnedBuf<float> &stage)
 {
     const size_t bytes = count * sizeof(float);
     if (small_block(h, bytes)) {
@@ -1100,18 +1153,11 @@ int download_rows(mfx_handle *h, float *dst, const float *d_src, size_t count, f
             HIP_TRY(h, hipStreamSynchronize(h->stream));
             return MFX_OK;
         }
-        if (stage_n < count + 4) {
-            if (stage_buf) (void)hipHostFree(stage_buf);
-            stage_buf = nullptr;
-            stage_n = 0;
-            const size_t want = std::max(count, (size_t)h->cap_rows * h->width) + 4;
-            HIP_TRY(h, hipHostMalloc((void **)&stage_buf, want * sizeof(float), hipHostMallocDefault));
-            stage_n = want;
-        }
-        char *stage = (char *)stage_buf + ((uintptr_t)d_src & 15);
-        HIP_TRY(h, launch_copy_small(stage, d_src, bytes, h->stream));
+        HIP_TRY(h, stage.grow(count + 4, std::max(count, (size_t)h->cap_rows * h->width) + 4, h->stream));
+        char *at = (char *)stage.p + ((uintptr_t)d_src & 15);
+        HIP_TRY(h, launch_copy_small(at, d_src, bytes, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
-        std::memcpy(dst, stage, bytes);
+        std::memcpy(dst, at, bytes);
         return MFX_OK;
     }
     if (bytes < kCopyChunk || is_pinned_host(dst)) {
@@ -1119,21 +1165,14 @@ int download_rows(mfx_handle *h, float *dst, const float *d_src, size_t count, f
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         return MFX_OK;
     }
-    if (stage_n < count) {
-        if (stage_buf) (void)hipHostFree(stage_buf);
-        stage_buf = nullptr;
-        stage_n = 0;
-        const size_t want = std::max(count, (size_t)h->cap_rows * h->width);
-        HIP_TRY(h, hipHostMalloc((void **)&stage_buf, want * sizeof(float), hipHostMallocDefault));
-        stage_n = want;
-    }
+    HIP_TRY(h, stage.grow(count, std::max(count, (size_t)h->cap_rows * h->width), h->stream));
     // chunks of the DMA into pinned staging, each followed by an event; the copy out of staging of chunk c runs under
     // the DMA of chunk c+1
     const size_t chunk = std::max(kCopyChunk, (bytes / 16 + 4095) & ~(size_t)4095);
     int n = 0;
     for (size_t off = 0; off < bytes; off += chunk, ++n) {
         const size_t len = std::min(chunk, bytes - off);
-        HIP_TRY(h, hipMemcpyAsync((char *)stage_buf + off, (const char *)d_src + off, len, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipMemcpyAsync((char *)stage.p + off, (const char *)d_src + off, len, hipMemcpyDeviceToHost, h->stream));
         if (!h->ev_copy[n]) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_copy[n], hipEventDisableTiming));
         HIP_TRY(h, hipEventRecord(h->ev_copy[n], h->stream));
     }
@@ -1141,7 +1180,7 @@ int download_rows(mfx_handle *h, float *dst, const float *d_src, size_t count, f
     for (size_t off = 0; off < bytes; off += chunk, ++n) {
         const size_t len = std::min(chunk, bytes - off);
         HIP_TRY(h, hipEventSynchronize(h->ev_copy[n]));
-        host_copy((char *)dst + off, (const char *)stage_buf + off, len);
+        host_copy((char *)dst + off, (const char *)stage.p + off, len);
     }
     return MFX_OK;
 }
@@ -1220,8 +1259,8 @@ extern "C" int mfx_set_input(mfx_handle *h, const int16_t *pcm, int32_t samples,
     int window_count = 0, wcnd = 0;
     if (h->last_calc_flushed) {
         if (h->host_tail) {
-            std::memcpy(h->h_stage, pcm, (size_t)samples * sizeof(int16_t));
-            HIP_TRY(h, launch_copy_small(h->d_carry[h->cur].p, h->h_stage, (size_t)samples * sizeof(int16_t), h->stream));
+            std::memcpy(h->h_stage.p, pcm, (size_t)samples * sizeof(int16_t));
+            HIP_TRY(h, launch_copy_small(h->d_carry[h->cur].p, h->h_stage.p, (size_t)samples * sizeof(int16_t), h->stream));
         } else {
             int rcu = upload_block(h, h->d_carry[h->cur].p, pcm, (size_t)samples, &direct);
             if (rcu != MFX_OK) return rcu;
@@ -1252,10 +1291,10 @@ extern "C" int mfx_set_input(mfx_handle *h, const int16_t *pcm, int32_t samples,
             // the pending tail moves to the front of the staging buffer (the stream is idle: no kernel is reading it), the
             // block goes behind it, and ONE copy kernel takes both to the front of the carry buffer
             if (h->stage_tail_off > 0 && h->remaining > 0)
-                std::memmove(h->h_stage, h->h_stage + h->stage_tail_off, (size_t)h->remaining * sizeof(int16_t));
+                std::memmove(h->h_stage.p, h->h_stage.p + h->stage_tail_off, (size_t)h->remaining * sizeof(int16_t));
             h->stage_tail_off = 0;
-            std::memcpy(h->h_stage + h->remaining, pcm, (size_t)samples * sizeof(int16_t));
-            HIP_TRY(h, launch_copy_small(h->d_carry[h->cur].p, h->h_stage,
+            std::memcpy(h->h_stage.p + h->remaining, pcm, (size_t)samples * sizeof(int16_t));
+            HIP_TRY(h, launch_copy_small(h->d_carry[h->cur].p, h->h_stage.p,
                                          ((size_t)h->remaining + (size_t)samples) * sizeof(int16_t), h->stream));
         } else {
             int rcu = upload_block(h, h->d_carry[h->cur].p + h->remaining, pcm, (size_t)samples, &direct);
@@ -1304,9 +1343,9 @@ extern "C" int mfx_flush(mfx_handle *h, int32_t *frames_out)
     if (h->host_tail && h->remaining > 0) { // the tail is on the host: up it goes, to the front of the carry buffer
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         if (h->stage_tail_off > 0)
-            std::memmove(h->h_stage, h->h_stage + h->stage_tail_off, (size_t)h->remaining * sizeof(int16_t));
+            std::memmove(h->h_stage.p, h->h_stage.p + h->stage_tail_off, (size_t)h->remaining * sizeof(int16_t));
         h->stage_tail_off = 0;
-        HIP_TRY(h, launch_copy_small(h->d_carry[h->cur].p, h->h_stage, (size_t)h->remaining * sizeof(int16_t), h->stream));
+        HIP_TRY(h, launch_copy_small(h->d_carry[h->cur].p, h->h_stage.p, (size_t)h->remaining * sizeof(int16_t), h->stream));
     }
     int rc = stream_front(h, wcnd);
     if (rc != MFX_OK) return rc;
@@ -1317,16 +1356,11 @@ extern "C" int mfx_flush(mfx_handle *h, int32_t *frames_out)
 
 namespace {
 
-// (Re)build the filterbanks of a sweep and size its buffers.
+// Size the buffers of a sweep of n alphas; (re)build its tables.
 int prepare_sweep(mfx_handle *h, const float *alphas, int n)
 {
-    const size_t wstride = (size_t)2 * h->W2, bstride = (size_t)h->nb + 2;
-    const bool same = (int)h->sweep_alphas.size() == n && std::equal(alphas, alphas + n, h->sweep_alphas.begin());
     if (n > h->sweep_cap) {
         HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (h->plp) HIP_TRY(h, h->d_sweep_eql.alloc((size_t)h->nb * n));
-        HIP_TRY(h, h->d_sweep_w.alloc(wstride * n));
-        HIP_TRY(h, h->d_sweep_beg.alloc(bstride * n));
         HIP_TRY(h, h->d_sweep_src.alloc((size_t)n * h->cap_rows * h->cols));
         HIP_TRY(h, h->d_sweep_blk.alloc((size_t)n * h->cap_rows * h->width));
         HIP_TRY(h, h->d_sweep_stats.alloc((size_t)3 * n * 2 * h->cols));
@@ -1334,127 +1368,37 @@ int prepare_sweep(mfx_handle *h, const float *alphas, int n)
         HIP_TRY(h, h->d_sweep_segs.alloc((size_t)2 * n));
         h->sweep_cap = n;
     }
-    if (same && n <= h->sweep_cap && !h->sweep_alphas.empty()) return MFX_OK;
-    std::vector<float> w(wstride * n);
-    std::vector<int32_t> b(bstride * n);
-    std::vector<MelWavePlan> plans((size_t)n);
-    std::vector<float> eql_all;
-    int rs = 4;
-    for (int a = 0; a < n; ++a) {
-        if (h->plp) {
-            std::vector<float> eql, idft;
-            build_plp_tables(h->nb, h->cfg.sample_rate, h->cfg.low_freq, h->cfg.high_freq, alphas[a], 0, eql, idft);
-            eql_all.insert(eql_all.end(), eql.begin(), eql.end());
-        }
-        MelTable t;
-        build_mel_table(h->nb, h->W2, h->cfg.sample_rate, h->cfg.low_freq, h->cfg.high_freq, alphas[a], t);
-        for (int v : t.beg)
-            if (v < 0 || v > h->W2 / 2) return fail(h, MFX_ERR_CONFIG, "mel filter edge outside [0, fft_size/2]");
-        std::copy(t.weights.begin(), t.weights.end(), w.begin() + wstride * a);
-        std::copy(t.beg.begin(), t.beg.end(), b.begin() + bstride * a);
-        if (!build_mel_wave_plan(t, h->nb, h->W2, /*max_read_bin=*/h->W2 - 1, plans[a]))
-            return fail(h, MFX_ERR_CONFIG, "mel filterbank does not fit the kernels' lane plan");
-        rs = std::max(rs, plans[a].row_stride);
+    return build_cep_tables(h, alphas, n, h->sweep);
+}
+
+// filterbank + log + DCT (k_melcep), or PLP (k_plp), of n_rows magnitude rows at `spec` with each of the n_tables tables of
+// `t`; table a writes feat + a * feat_table_stride.  r_out: PLP's autocorrelation tap (table 0), or nullptr.
+int launch_cepstra(mfx_handle *h, const CepTables &t, const float *spec, int64_t n_rows, float *feat, int feat_pitch,
+                   int n_tables, int64_t feat_table_stride, float *r_out, hipStream_t stream)
+{
+    if (h->plp) {
+        PlpParams pp;
+        fill_plp(h, t, pp);
+        pp.spec = spec;
+        pp.n_rows = n_rows;
+        pp.feat = feat;
+        pp.feat_pitch = feat_pitch;
+        pp.n_tables = n_tables;
+        pp.feat_table_stride = feat_table_stride;
+        pp.r_out = r_out;
+        HIP_TRY(h, launch_plp(pp, stream));
+    } else {
+        MelcepParams mp;
+        fill_melcep(h, t, mp);
+        mp.spec = spec;
+        mp.n_rows = n_rows;
+        mp.feat = feat;
+        mp.feat_pitch = feat_pitch;
+        mp.n_tables = n_tables;
+        mp.feat_table_stride = feat_table_stride;
+        HIP_TRY(h, launch_melcep(mp, stream));
     }
-    // one 64-lane plan per alpha, the weight rows padded to the longest plan's stride (a row's rounds lie back to back from
-    // its start, so padding at the end changes nothing)
-    const int rounds = plans[0].rounds;
-    std::vector<float> pw((size_t)n * 64 * rs, 0.f);
-    std::vector<int32_t> pst((size_t)n * 64 * rounds), pfid((size_t)n * 64 * rounds), pL((size_t)n * 8);
-    for (int a = 0; a < n; ++a) {
-        for (int j = 0; j < 64; ++j)
-            std::copy(plans[a].w.begin() + (size_t)j * plans[a].row_stride, plans[a].w.begin() + (size_t)(j + 1) * plans[a].row_stride,
-                      pw.begin() + ((size_t)a * 64 + j) * rs);
-        std::copy(plans[a].start.begin(), plans[a].start.end(), pst.begin() + (size_t)a * 64 * rounds);
-        std::copy(plans[a].fid.begin(), plans[a].fid.end(), pfid.begin() + (size_t)a * 64 * rounds);
-        std::copy(plans[a].L, plans[a].L + 8, pL.begin() + (size_t)a * 8);
-    }
-    {   // the sweep's common row stride may exceed the handle's own plan's: check k_melcep's LDS here (a CONFIG error
-        // at the call, not a launch failure later)
-        MelcepParams probe;
-        std::memset(&probe, 0, sizeof(probe));
-        probe.num_banks = h->nb;
-        probe.mel64_rounds = rounds;
-        probe.mel64_row_stride = rs;
-        probe.mag_floats = std::max(h->W2, (h->spec_pitch + 3) & ~3);
-        if (melcep_lds_bytes(probe, 1) > 160 * 1024)
-            return fail(h, MFX_ERR_CONFIG, "a warped mel filterbank of the sweep does not fit the kernels' LDS");
-        if (h->plp) {
-            PlpParams pp;
-            std::memset(&pp, 0, sizeof(pp));
-            pp.num_banks = h->nb;
-            pp.lpc_order = h->lpc;
-            pp.ceps_len = h->ceps;
-            pp.mel64_rounds = rounds;
-            pp.mel64_row_stride = rs;
-            pp.mag_floats = probe.mag_floats;
-            if (plp_lds_bytes(pp, 1) > 160 * 1024)
-                return fail(h, MFX_ERR_CONFIG, "a warped mel filterbank of the sweep does not fit the PLP kernel's LDS");
-        }
-    }
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, hipMemcpy(h->d_sweep_w.p, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(h->d_sweep_beg.p, b.data(), b.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIP_TRY(h, upload(h->d_sweep64_w, pw));
-    HIP_TRY(h, upload(h->d_sweep64_start, pst));
-    HIP_TRY(h, upload(h->d_sweep64_fid, pfid));
-    HIP_TRY(h, upload(h->d_sweep64_L, pL));
-    if (h->plp) HIP_TRY(h, hipMemcpy(h->d_sweep_eql.p, eql_all.data(), eql_all.size() * sizeof(float), hipMemcpyHostToDevice));
-    h->sweep64_rs = rs;
-    h->sweep_alphas.assign(alphas, alphas + n);
     return MFX_OK;
-}
-
-// k_melcep parameters that do not depend on the caller: the handle's own filterbank (sweep = false) or the sweep's tables
-void fill_melcep(const mfx_handle *h, MelcepParams &mp, bool sweep)
-{
-    std::memset(&mp, 0, sizeof(mp));
-    mp.spec_pitch = h->spec_pitch;
-    mp.fft_size = h->W2;
-    mp.mel_w = sweep ? h->d_sweep_w.p : h->d_mel_w.p;
-    mp.mel_beg = sweep ? h->d_sweep_beg.p : h->d_mel_beg.p;
-    mp.mel64_w = sweep ? h->d_sweep64_w.p : h->d_mel64_w.p;
-    mp.mel64_start = sweep ? h->d_sweep64_start.p : h->d_mel64_start.p;
-    mp.mel64_fid = sweep ? h->d_sweep64_fid.p : h->d_mel64_fid.p;
-    mp.mel64_L = sweep ? h->d_sweep64_L.p : h->d_mel64_L.p;
-    mp.mel64_rounds = h->wplan.rounds;
-    mp.mel64_row_stride = sweep ? h->sweep64_rs : h->wplan.row_stride;
-    mp.mag_floats = std::max(h->W2, (h->spec_pitch + 3) & ~3);
-    mp.dct = h->ceps > 0 ? h->d_dct.p : nullptr;
-    mp.dct_b4 = h->ceps > 0 ? h->d_dct_b4.p : nullptr;
-    mp.dct_ksteps = h->dct_ksteps;
-    mp.num_banks = h->nb;
-    mp.dct_len = h->dl;
-    mp.cols = h->cols;
-    mp.n_tables = 1;
-    mp.mel_w_stride = (int64_t)2 * h->W2;
-    mp.mel_beg_stride = h->nb + 2;
-}
-
-// k_plp parameters that do not depend on the caller (the PLP twin of fill_melcep)
-void fill_plp(const mfx_handle *h, PlpParams &pp, bool sweep)
-{
-    MelcepParams mp;
-    fill_melcep(h, mp, sweep);
-    std::memset(&pp, 0, sizeof(pp));
-    pp.spec_pitch = mp.spec_pitch;
-    pp.fft_size = mp.fft_size;
-    pp.num_banks = h->nb;
-    pp.lpc_order = h->lpc;
-    pp.ceps_len = h->ceps;
-    pp.want_c0 = h->cfg.want_c0 ? 1 : 0;
-    pp.cols = h->cols;
-    pp.mel64_w = mp.mel64_w;
-    pp.mel64_start = mp.mel64_start;
-    pp.mel64_fid = mp.mel64_fid;
-    pp.mel64_L = mp.mel64_L;
-    pp.mel64_rounds = mp.mel64_rounds;
-    pp.mel64_row_stride = mp.mel64_row_stride;
-    pp.mag_floats = mp.mag_floats;
-    pp.eql = sweep ? h->d_sweep_eql.p : h->d_plp_eql.p;
-    pp.idft = h->d_plp_idft.p;
-    pp.lift = h->d_plp_lift.p;
-    pp.n_tables = 1;
 }
 
 // apply() for the current block: n_alpha == 0 -> the handle's alpha into d_src/d_blk (ParamBase::apply);
@@ -1493,29 +1437,10 @@ int apply_impl(mfx_handle *h, const float *alphas, int n_alpha)
     float *d_blk = sweep ? h->d_sweep_blk.p : h->d_blk.p;
     float *d_stats = sweep ? h->d_sweep_stats.p : h->d_stats_stream.p;
 
-    // filterbank + log + DCT (PLP: k_plp) over all frames with context
-    if (h->plp) {
-        PlpParams pp;
-        fill_plp(h, pp, sweep);
-        pp.spec = h->d_spec.p;
-        pp.n_rows = wcnd;
-        pp.feat = d_src;
-        pp.feat_pitch = h->cols;
-        pp.n_tables = n_tab;
-        pp.feat_table_stride = (int64_t)h->cap_rows * h->cols;
-        pp.r_out = sweep ? nullptr : h->d_plp_r.p;
-        HIP_TRY(h, launch_plp(pp, h->stream));
-    } else {
-        MelcepParams mp;
-        fill_melcep(h, mp, sweep);
-        mp.spec = h->d_spec.p;
-        mp.n_rows = wcnd;
-        mp.feat = d_src;
-        mp.feat_pitch = h->cols;
-        mp.n_tables = n_tab;
-        mp.feat_table_stride = (int64_t)h->cap_rows * h->cols;
-        HIP_TRY(h, launch_melcep(mp, h->stream));
-    }
+    // cepstra over all frames with context
+    rc = launch_cepstra(h, sweep ? h->sweep : h->own, h->d_spec.p, wcnd, d_src, h->cols, n_tab, (int64_t)h->cap_rows * h->cols,
+                        sweep ? nullptr : h->d_plp_r.p, h->stream);
+    if (rc != MFX_OK) return rc;
 
     // static row offset as the reference reads it (mfcccpu.cpp:274,439): was_flushed() ? 0 : D.
     // With bug_compat off a flush block always reads at D (fixes B1).
@@ -1561,7 +1486,7 @@ int apply_impl(mfx_handle *h, const float *alphas, int n_alpha)
 
     const bool norm = h->cfg.norm != MFX_NORM_NONE;
     if (norm && !h->cfg.norm_after_dyn) { // normalise statics (with context) before the deltas
-        rc = run_norm(h, d_src, h->cols, 0, segs_ctx, n_tab, sweep ? nullptr : &sg, 0, d_stats, use_last, wcnd);
+        rc = run_norm(h, h->stream, d_src, h->cols, 0, segs_ctx, n_tab, sweep ? nullptr : &sg, 0, d_stats, use_last, wcnd);
         if (rc != MFX_OK) return rc;
     }
 
@@ -1577,16 +1502,9 @@ int apply_impl(mfx_handle *h, const float *alphas, int n_alpha)
     // single CU writing 155 KB over the link takes what the copy kernel it would save takes -- measured, +- 0.5 us)
     if (!sweep && !(norm && h->cfg.norm_after_dyn) && small_block(h, (size_t)wc * h->width * sizeof(float))) {
         const size_t want = (size_t)h->cap_rows * h->width + 4;
-        if (h->h_out_stage_n < want) {
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            if (h->h_out_stage) (void)hipHostFree(h->h_out_stage);
-            h->h_out_stage = nullptr;
-            h->h_out_stage_n = 0;
-            HIP_TRY(h, hipHostMalloc((void **)&h->h_out_stage, want * sizeof(float), hipHostMallocDefault));
-            h->h_out_stage_n = want;
-        }
+        HIP_TRY(h, h->h_out_stage.grow(want, want, h->stream));
         void *dev = nullptr;
-        if (is_pinned_host(h->h_out_stage, &dev) && dev) {
+        if (is_pinned_host(h->h_out_stage.p, &dev) && dev) {
             rows_out = (float *)dev;
             h->rows_in_stage = true;
         }
@@ -1609,7 +1527,7 @@ int apply_impl(mfx_handle *h, const float *alphas, int n_alpha)
 
     if (norm && h->cfg.norm_after_dyn) {
         const int groups = h->width / h->cols;
-        rc = run_norm(h, d_blk, h->width, 0, segs_out, n_tab, sweep ? nullptr : &sd, 0, d_stats, use_last, wc, groups,
+        rc = run_norm(h, h->stream, d_blk, h->width, 0, segs_out, n_tab, sweep ? nullptr : &sd, 0, d_stats, use_last, wc, groups,
                       (size_t)n_tab * 2 * h->cols);
         if (rc != MFX_OK) return rc;
     }
@@ -1648,7 +1566,7 @@ extern "C" int mfx_get_output_data_alpha(mfx_handle *h, int32_t alpha_index, flo
     HIP_TRY(h, hipSetDevice(h->device));
     // (own staging buffer: h_out_stage may hold the plain rows that get_output_data returns next)
     return download_rows(h, data_out, h->d_sweep_blk.p + (size_t)alpha_index * h->cap_rows * h->width, (size_t)frames * h->width,
-                         h->h_alpha_stage, h->h_alpha_stage_n);
+                         h->h_alpha_stage);
 }
 
 extern "C" int mfx_get_output_data(mfx_handle *h, float *data_out, int32_t frames)
@@ -1661,10 +1579,10 @@ extern "C" int mfx_get_output_data(mfx_handle *h, float *data_out, int32_t frame
     HIP_TRY(h, hipSetDevice(h->device));
     if (h->rows_in_stage) { // the delta kernel wrote the rows into page-locked memory: wait for it, copy
         HIP_TRY(h, hipStreamSynchronize(h->stream));
-        std::memcpy(data_out, h->h_out_stage, (size_t)frames * h->width * sizeof(float));
+        std::memcpy(data_out, h->h_out_stage.p, (size_t)frames * h->width * sizeof(float));
         return MFX_OK;
     }
-    return download_rows(h, data_out, h->d_blk.p, (size_t)frames * h->width, h->h_out_stage, h->h_out_stage_n);
+    return download_rows(h, data_out, h->d_blk.p, (size_t)frames * h->width, h->h_out_stage);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2057,23 +1975,9 @@ int batch_run_range(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_tot
                 else
                     HIP_TRY(h, launch_front_generic(q, /*fused=*/false, h->stream));
             }
-            if (h->plp) {
-                PlpParams pp;
-                fill_plp(h, pp, false);
-                pp.spec = h->d_spec_slab.p;
-                pp.n_rows = rows;
-                pp.feat = p.feat + row0 * (int64_t)p.feat_pitch;
-                pp.feat_pitch = p.feat_pitch;
-                HIP_TRY(h, launch_plp(pp, h->stream));
-            } else {
-                MelcepParams mp;
-                fill_melcep(h, mp, false);
-                mp.spec = h->d_spec_slab.p;
-                mp.n_rows = rows;
-                mp.feat = p.feat + row0 * (int64_t)p.feat_pitch;
-                mp.feat_pitch = p.feat_pitch;
-                HIP_TRY(h, launch_melcep(mp, h->stream));
-            }
+            rc = launch_cepstra(h, h->own, h->d_spec_slab.p, rows, p.feat + row0 * (int64_t)p.feat_pitch, p.feat_pitch, 1, 0, nullptr,
+                                h->stream);
+            if (rc != MFX_OK) return rc;
             c0 = c1;
         }
     }
@@ -2082,15 +1986,9 @@ int batch_run_range(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_tot
         HIP_TRY(h, hipEventRecord(h->ev_front[sb], h->stream));
         HIP_TRY(h, hipStreamWaitEvent(h->stream2, h->ev_front[sb], 0));
     }
-    struct StreamSwap { // the tail kernels below launch on h->stream: point it at the tail stream meanwhile
-        mfx_handle *h;
-        hipStream_t keep;
-        StreamSwap(mfx_handle *hh, hipStream_t s) : h(hh), keep(hh->stream) { h->stream = s; }
-        ~StreamSwap() { h->stream = keep; }
-    } swap_guard(h, tail_stream);
     const bool norm = h->cfg.norm != MFX_NORM_NONE;
     if (norm && !h->cfg.norm_after_dyn) {
-        rc = run_norm(h, d_out, h->width, 0, h->d_segs.p + u0, u1 - u0, nullptr, 0, h->d_stats_batch.p + (size_t)u0 * 2 * h->cols,
+        rc = run_norm(h, tail_stream, d_out, h->width, 0, h->d_segs.p + u0, u1 - u0, nullptr, 0, h->d_stats_batch.p + (size_t)u0 * 2 * h->cols,
                       false, h->tiles_max * 64);
         if (rc != MFX_OK) return rc;
     }
@@ -2107,11 +2005,11 @@ int batch_run_range(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_tot
         dp.l1 = h->l1;
         dp.l2 = h->l2;
         dp.tiles_per_seg_max = h->tiles_max;
-        HIP_TRY(h, launch_delta(dp, h->stream));
+        HIP_TRY(h, launch_delta(dp, tail_stream));
     }
     if (norm && h->cfg.norm_after_dyn) {
         const int groups = h->width / h->cols;
-        rc = run_norm(h, d_out, h->width, 0, h->d_segs.p + u0, u1 - u0, nullptr, 0, h->d_stats_batch.p + (size_t)u0 * 2 * h->cols,
+        rc = run_norm(h, tail_stream, d_out, h->width, 0, h->d_segs.p + u0, u1 - u0, nullptr, 0, h->d_stats_batch.p + (size_t)u0 * 2 * h->cols,
                       false, h->tiles_max * 64, groups, (size_t)h->n_utt * 2 * h->cols);
         if (rc != MFX_OK) return rc;
     }
@@ -2256,12 +2154,12 @@ extern "C" int64_t mfx_debug_read(mfx_handle *h, int kind, void *dst, int64_t ds
     switch (kind) {
     case 0:
         if (refresh_mel(h) != MFX_OK) return MFX_ERR_DEVICE;
-        src = h->d_mel_w.p;
+        src = h->own.mel_w.p;
         count = 2 * (int64_t)h->W2;
         break;
     case 1:
         if (refresh_mel(h) != MFX_OK) return MFX_ERR_DEVICE;
-        src = h->d_mel_beg.p;
+        src = h->own.mel_beg.p;
         count = h->nb + 2;
         break;
     case 2:
