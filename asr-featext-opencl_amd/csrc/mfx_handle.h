@@ -1,0 +1,322 @@
+// mfx_handle.h -- internal to the host side of libmfcchip (not installed): the handle behind include/mfx.h, the buffer
+// types it owns, and the few helpers its three translation units share.
+//   mfx_api.cpp    lifetime, tables, kernel choice, profiling, test taps   (writes the shared part of the handle)
+//   mfx_stream.cpp the streaming state machine and its host copies         (owns `st` and `sweep`)
+//   mfx_batch.cpp  the batch planner and runner, the fused-delta plan      (owns `batch` and `fuse`)
+#pragma once
+#include "../../include/mfx.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "mfx_kernels.h"
+#include "mfx_tables.h"
+
+constexpr int kChunkFrames = 16;           // frames per work item of the front-end kernels
+constexpr size_t kLdsCap = 160 * 1024;     // LDS a block may ask for on gfx950 (the kernels keep their own copy)
+constexpr size_t kSmallBlock = (size_t)1 << 20; // below this a copy kernel replaces the DMA command (streaming interface)
+
+inline constexpr const char *kMsgBuffer = "Can't process data, buffer is too small";
+inline constexpr const char *kMsgWindow = "Can't process data, window count is too small";
+inline constexpr const char *kMsgProcessed = "Processed samples <= 0, this should never happen";
+inline constexpr const char *kMsgHigh = "Window count too high";
+
+// device memory, freed with its owner
+template <class T>
+struct DevBuf {
+    T *p = nullptr;
+    size_t n = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept { *this = std::move(o); }
+    DevBuf &operator=(DevBuf &&o) noexcept // (o frees what this held)
+    {
+        std::swap(p, o.p), std::swap(n, o.n);
+        return *this;
+    }
+    ~DevBuf() { release(); }
+    // device == false (planning handles, mfx_handle::alloc): records the size, allocates nothing
+    hipError_t alloc(size_t count, bool device = true)
+    {
+        release();
+        if (count > 0 && device) {
+            const hipError_t e = hipMalloc((void **)&p, count * sizeof(T));
+            if (e != hipSuccess) {
+                p = nullptr;
+                return e;
+            }
+        }
+        n = count;
+        return hipSuccess;
+    }
+    void release()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        n = 0;
+    }
+};
+
+// page-locked host memory, freed with its owner
+template <class T>
+struct PinnedBuf {
+    T *p = nullptr;
+    size_t n = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+    ~PinnedBuf()
+    {
+        if (p) (void)hipHostFree(p);
+    }
+    // fewer than `need` elements: wait for `stream` (work on it may still use the old block), then replace the block by
+    // one of `want` (>= need) elements
+    hipError_t grow(size_t need, size_t want, hipStream_t stream)
+    {
+        if (n >= need) return hipSuccess;
+        if (hipError_t e = hipStreamSynchronize(stream); e != hipSuccess) return e;
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        n = 0;
+        if (hipError_t e = hipHostMalloc((void **)&p, want * sizeof(T), hipHostMallocDefault); e != hipSuccess) {
+            p = nullptr;
+            return e;
+        }
+        n = want;
+        return hipSuccess;
+    }
+};
+
+// What k_melcep / k_plp read for n warp factors: the mel tables (mel_w [n][2 * W2], mel_beg [n][nb + 2]), one 64-lane
+// plan per table padded to a common row stride (w64 [n][64][row_stride], start64 / fid64 [n][rounds][64], L64 [n][8]) and,
+// for PLP, the equal-loudness weights (eql [n][nb]).
+struct CepTables {
+    DevBuf<float> mel_w, w64, eql;
+    DevBuf<int32_t> mel_beg, start64, fid64, L64;
+    int rounds = 0, row_stride = 0;
+    std::vector<float> alphas; // the warp factors the tables hold (empty: none)
+    bool holds(const float *a, int n) const { return !alphas.empty() && (int)alphas.size() == n && std::equal(a, a + n, alphas.begin()); }
+};
+
+// streaming state (segmentercpu.h:7-17, parambase.h:18): mfx_stream.cpp
+struct StreamState {
+    DevBuf<int16_t> d_carry[2];
+    int cur = 0;
+    size_t carry_capacity = 0;
+    int remaining = 0, samples = 0;
+    bool flushed = true, last_calc_flushed = false, last_block = false;
+    int block_wcnd = 0;      // frames (with context) the last FFT covered
+    int block_frames = 0;    // frames apply() delivers
+    DevBuf<float> d_src, d_blk, d_stats, d_plp_r; // (d_plp_r: PLP's r taps)
+    DevBuf<mfx::Chunk> d_chunks;
+    int chunk_frames = 16;
+    int n_chunks_max = 0;
+    PinnedBuf<int16_t> h_stage;
+    // small-block handles (every block under 1 MB): the carried tail stays on the HOST, inside the pinned staging buffer, and
+    // goes up again in front of the next block -- one copy kernel per set_input instead of copy + device-to-device tail copy
+    bool host_tail = false;
+    size_t stage_tail_off = 0;  // samples: where the pending tail (`remaining` samples) starts in h_stage
+    PinnedBuf<float> h_out_stage;         // staging of get_output_data (allocated on first use)
+    bool rows_in_stage = false;           // the current block's PLAIN rows were written straight into h_out_stage by the delta
+                                          // kernel (set by a plain apply only; cleared by set_input and flush)
+    hipEvent_t ev_copy[16] = {};          // chunk events of the pipelined device-to-host copy
+};
+
+// VTLN sweep (mfx_apply_alphas): one filterbank (`tables`), one static and one output block per alpha: mfx_stream.cpp
+struct SweepState {
+    CepTables tables;                     // of the last sweep's alphas
+    int cap = 0;                          // alphas the sweep buffers hold
+    int n = 0;                            // alphas of the current block's last sweep (0: none since set_input / flush)
+    DevBuf<float> d_src, d_blk, d_stats;
+    DevBuf<mfx::Segment> d_segs;          // [2][cap]: rows with context, rows delivered
+    PinnedBuf<float> h_stage;             // staging of get_output_data_alpha: never st.h_out_stage, which may hold the plain
+                                          // rows a later get_output_data returns
+};
+
+// batch plan: mfx_batch.cpp
+struct BatchState {
+    int32_t n_utt = 0;
+    int64_t total_rows = 0;
+    std::vector<int64_t> utt_off, utt_len, utt_row;
+    std::vector<mfx::Chunk> h_chunks;
+    std::vector<int32_t> chunk_utt;      // utterance of every entry of h_chunks
+    std::vector<int32_t> utt_chunk0;     // [n_utt + 1] first chunk of every utterance (chunks are in utterance order)
+    hipStream_t stream_up = nullptr, stream_dn = nullptr; // sliced mfx_batch_run_host: upload / download beside the kernels
+    hipEvent_t ev_up[16] = {}, ev_run[16] = {};
+    DevBuf<mfx::Chunk> d_chunks;
+    DevBuf<mfx::Segment> d_segs;
+    DevBuf<float> d_stats, d_spec_slab, d_host_out;
+    DevBuf<int16_t> d_host_pcm;          // mfx_batch_run_host: device copies of the caller's host buffers
+    DevBuf<float> d_static16[2]; // compact [rows][16] statics between front end and delta (double buffered for overlap)
+    // optional overlap of the delta/normalisation tail of batch i with the front end of batch i+1
+    bool overlap = false;
+    hipStream_t stream2 = nullptr;
+    hipEvent_t ev_front[2] = {nullptr, nullptr}, ev_tail[2] = {nullptr, nullptr};
+    bool tail_pending[2] = {false, false};
+    unsigned seq = 0;
+    int tiles_max = 0;
+    bool aligned = true;                 // frames on aligned sample pairs (fill_front / choose_front read it)
+};
+
+// fused delta stage of the 512-point kernel: per-block chunk lists (own rows + halo) and delta tiles: mfx_batch.cpp
+struct FuseState {
+    bool enabled = false; // mfx_config.engine & MFX_ENGINE_FUSE_DELTA opts in to the fused delta stage (measured 1-2 % slower
+                          // than front end + k_delta on C2; kept tested, off by default)
+    bool planned = false;
+    int blocks = 0, done_words = 0;
+    int32_t nchunks = 0;
+    DevBuf<mfx::Chunk> d_chunks;
+    DevBuf<int32_t> d_blk_chunk_off, d_blk_tile_off, d_err;
+    DevBuf<mfx::DeltaTile> d_tiles;
+};
+
+// profiling of the dominant kernel
+struct ProfState {
+    bool on = false;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
+    size_t used = 0;
+    int launches = 0;
+    double ms = 0;
+};
+
+struct mfx_handle {
+    mfx_config cfg{};
+    int device = 0;
+    // A PLANNING handle (mfx_plan_create) runs mfx_create's own code -- the predicates, the host-built tables, the LDS sums
+    // that decide which kernels a shape lands on -- with every device call left out: it can answer mfx_dominant_kernel_name
+    // and the geometry accessors, and nothing else (no buffer exists; every other entry fails with MFX_ERR_DEVICE).  It is
+    // how the shape -> kernel table of DESIGN.md section 5 is pinned by a test that needs no GPU.  It computes nothing.
+    bool planning = false;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    std::string err;
+
+    // ---- shared: geometry and tables, written at create / refresh_mel / set_window only
+    // derived (mfccbase.cpp:18-30, mfcccpu.cpp:94-105)
+    int W = 0, S = 0, W2 = 0, nb = 0, ceps = 0, dl = 0, cols = 0, width = 0;
+    int l1 = 0, l2 = 0, D = 0;
+    int input_window_limit = 0, input_buffer_size = 0, window_limit = 0, cap_rows = 0;
+    int spec_pitch = 0;
+    int channels = 1;
+    int num_cus = 256;
+    bool fast512 = false;
+    bool stuff256 = false; // fast512 serving 256-point transforms in the zero-stuffed form
+    bool fast1024 = false; // 1024 points, window <= 512 samples: k_front1024 (two 256-point transforms per frame)
+    int nm16 = 16;
+    bool plp = false;  // mfx_config.method == MFX_METHOD_PLP: k_plp where MFCC runs k_melcep, never the fused front ends
+    int lpc = 0;       // PLP model order (lpc_order, 0 -> 8)
+    float alpha = 1.f;
+    bool have_window = false;
+
+    // tables in HBM
+    DevBuf<float> d_win1024o;
+    DevBuf<float> d_window, d_winpair, d_twid_pass, d_twid_half, d_twid_split, d_twid_reg, d_dct;
+    // k_melcep / k_plp tables of the handle's alpha (also the fused front ends' mel table and 64-lane plan)
+    CepTables own;
+    // PLP: autocorrelation basis, lifter
+    DevBuf<float> d_plp_idft, d_plp_lift;
+    // 512-point kernel: per-lane mel plan + transposed DCT matrix
+    DevBuf<float> d_mel_lane_w, d_dct_t;
+    DevBuf<int32_t> d_mel_lane_start, d_mel_lane_fid;
+    mfx::MelLanePlan plan;
+    // wave-per-frame kernels (k_front_reg, fused): the 64-lane mel plan of `own` + DCT operands for the matrix pipe
+    mfx::MelWavePlan wplan;
+    bool wplan_ok = false;
+    DevBuf<float> d_dct_b;
+    DevBuf<float> d_dct_b4;                          // k_front2048: DCT operands as 16-byte words
+    DevBuf<float> d_dct_b4s;                         // k_front2048: the split form for <= 40 columns (or empty)
+    int dct_split = 0;
+    DevBuf<float> d_mel32_w;                         // k_front2048: the 32-lane plan
+    DevBuf<int32_t> d_mel32_start, d_mel32_fid;
+    mfx::MelWavePlan wplan32;
+    bool fast2048 = false, wplan32_ok = false;
+    int dct_tiles = 0, dct_ksteps = 0;
+    int dct_stride = 0, nb_pad = 0;
+    bool fused_ok = false;
+    std::vector<float> h_dct;
+    // scratch both interfaces use
+    DevBuf<float> d_spec;                // streaming spectrum (mfx_debug_read kind 3); the batch runner hands it to dev-build stamps
+    DevBuf<double> d_norm_partial;       // chunk results of the normaliser's statistics (segments longer than 4096 rows)
+
+    StreamState st;
+    SweepState sweep;
+    BatchState batch;
+    FuseState fuse;
+    ProfState prof;
+
+    // buffers of the handle go through these two: a planning handle records sizes and touches no device
+    template <class T>
+    hipError_t alloc(DevBuf<T> &b, size_t count)
+    {
+        return b.alloc(count, !planning);
+    }
+    template <class T>
+    hipError_t upload(DevBuf<T> &b, const std::vector<T> &v)
+    {
+        hipError_t e = alloc(b, v.size());
+        if (e != hipSuccess || v.empty() || planning) return e;
+        return hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+    }
+
+    // (the buffers free themselves after this; mfx_destroy has waited for the streams)
+    ~mfx_handle()
+    {
+        for (auto &ev : prof.events) {
+            (void)hipEventDestroy(ev.first);
+            (void)hipEventDestroy(ev.second);
+        }
+        auto destroy = [](auto &events) {
+            for (hipEvent_t e : events)
+                if (e) (void)hipEventDestroy(e);
+        };
+        destroy(batch.ev_front), destroy(batch.ev_tail), destroy(batch.ev_up), destroy(batch.ev_run), destroy(st.ev_copy);
+        for (hipStream_t s : {batch.stream2, batch.stream_up, batch.stream_dn})
+            if (s) (void)hipStreamDestroy(s);
+        if (own_stream && stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+inline int fail(mfx_handle *h, int code, const std::string &msg)
+{
+    if (h) h->err = msg;
+    return code;
+}
+
+inline int fail_hip(mfx_handle *h, hipError_t e, const char *what)
+{
+    std::string m = std::string(what) + ": " + hipGetErrorString(e);
+    return fail(h, MFX_ERR_DEVICE, m);
+}
+
+#define HIP_TRY(h, expr)                                         \
+    do {                                                         \
+        hipError_t _e = (expr);                                  \
+        if (_e != hipSuccess) return fail_hip((h), _e, #expr);   \
+    } while (0)
+
+// top of every entry that needs the device: a handle, and not a planning one
+#define MFX_DEVICE_ENTRY(h)                                                                                                  \
+    do {                                                                                                                     \
+        if (!(h)) return MFX_ERR_ARG;                                                                                        \
+        if ((h)->planning) return fail((h), MFX_ERR_DEVICE, "planning handle (mfx_plan_create): no device behind it");      \
+    } while (0)
+
+// ---- mfx_api.cpp, for the other two
+// Which front-end kernel the BATCH entries run for this handle (see choose_front's definition)
+enum FrontKind { kFront512, kFront1024, kFront2048, kFrontGenFused, kSpec512, kSpecGen };
+FrontKind choose_front(const mfx_handle *h);
+void fill_front(const mfx_handle *h, mfx::FrontParams &p);
+int refresh_mel(mfx_handle *h);
+int build_cep_tables(mfx_handle *h, const float *alphas, int n, CepTables &t, mfx::MelTable *first = nullptr,
+                     mfx::MelWavePlan *first_plan = nullptr);
+int launch_cepstra(mfx_handle *h, const CepTables &t, const float *spec, int64_t n_rows, float *feat, int feat_pitch,
+                   int n_tables, int64_t feat_table_stride, float *r_out, hipStream_t stream);
+int run_norm(mfx_handle *h, hipStream_t stream, float *data, int pitch, const mfx::Segment *segs, int n_segs, const mfx::Segment *seg0,
+             float *stats, bool use_last, int max_rows, int groups = 1, size_t group_stats_stride = 0);
+// ---- mfx_stream.cpp, for mfx_batch.cpp
+bool is_pinned_host(const void *p, void **dev_ptr = nullptr);

@@ -132,6 +132,109 @@ void build_twiddles(int n, int count, std::vector<float> &t)
     }
 }
 
+void build_split_twiddles(int fft_size, bool stuffed, std::vector<float> &split)
+{
+    const int WS = stuffed ? 512 : fft_size;
+    std::vector<float> ws;
+    build_twiddles(WS, WS / 2 + 1, ws); // W_{WS}^k
+    split.resize(ws.size());
+    for (int k = 0; k <= WS / 2; ++k) { // -i * W = (wi, -wr)
+        split[2 * k] = ws[2 * k + 1];
+        split[2 * k + 1] = -ws[2 * k];
+    }
+}
+
+void build_reg_pass_twiddles(int fft_size, std::vector<float> &reg)
+{
+    const int M = fft_size / 2, R1 = fft_size == 1024 ? 8 : 16, n1 = M / R1, n2 = M / (R1 * R1);
+    std::vector<float> tw;
+    build_twiddles(M, M, tw); // W_M^e
+    reg.resize((size_t)2 * (R1 - 1) * (n1 + n2));
+    size_t o = 0;
+    for (int k = 1; k < R1; ++k)
+        for (int pp = 0; pp < n1; ++pp, ++o) {
+            const int e = (pp * k) & (M - 1);
+            reg[2 * o] = tw[2 * e];
+            reg[2 * o + 1] = tw[2 * e + 1];
+        }
+    for (int k = 1; k < R1; ++k)
+        for (int pp = 0; pp < n2; ++pp, ++o) {
+            const int e = (pp * k * R1) & (M - 1);
+            reg[2 * o] = tw[2 * e];
+            reg[2 * o + 1] = tw[2 * e + 1];
+        }
+}
+
+void build_pass256_twiddles(std::vector<float> &pass)
+{
+    std::vector<float> full;
+    build_twiddles(256, 256, full); // W_256^e
+    pass.resize(16 * 16 * 2);
+    for (int l = 0; l < 16; ++l)
+        for (int k = 0; k < 16; ++k) {
+            int e = (l * k) & 255;
+            pass[2 * (l * 16 + k)] = full[2 * e];
+            pass[2 * (l * 16 + k) + 1] = full[2 * e + 1];
+        }
+}
+
+void build_window_pairs(const std::vector<float> &padded, int fft_size, bool stuffed, std::vector<float> &wp)
+{
+    const float fold = 0.5f / (float)fft_size;
+    wp.assign(16 * 16 * 2, 0.f);
+    for (int l = 0; l < 16; ++l)
+        for (int m = 0; m < 16; ++m) {
+            int n = l + 16 * m;
+            if (stuffed) {
+                const int step = 256 / fft_size;
+                if (n % step == 0 && n / step < fft_size) wp[2 * (l * 16 + m)] = padded[n / step] * fold;
+                continue;
+            }
+            wp[2 * (l * 16 + m)] = padded[2 * n] * fold;
+            wp[2 * (l * 16 + m) + 1] = padded[2 * n + 1] * fold;
+        }
+}
+
+void build_front1024_phase_o(const std::vector<float> &padded, int fft_size, std::vector<float> &wo)
+{
+    const float fold = 0.5f / (float)fft_size;
+    std::vector<float> tw512;
+    build_twiddles(512, 256, tw512);
+    wo.assign(16 * 16 * 4, 0.f);
+    for (int l = 0; l < 16; ++l)
+        for (int m = 0; m < 16; ++m) {
+            const int n = l + 16 * m;
+            const float t0 = padded[2 * n] * fold, t1 = padded[2 * n + 1] * fold;
+            const float c = tw512[2 * n], sn = tw512[2 * n + 1];
+            float *q = &wo[4 * (l * 16 + m)];
+            q[0] = t0 * c;
+            q[1] = -(t1 * sn);
+            q[2] = t0 * sn;
+            q[3] = t1 * c;
+        }
+}
+
+void build_front1024_long_window(const std::vector<float> &padded, int fft_size, std::vector<float> &taps, std::vector<float> &tw)
+{
+    const float fold = 0.5f / (float)fft_size;
+    std::vector<float> tw512;
+    build_twiddles(512, 256, tw512);
+    taps.assign(16 * 32 * 2, 0.f);
+    tw.assign(16 * 16 * 2, 0.f);
+    for (int l = 0; l < 16; ++l) {
+        for (int m = 0; m < 32; ++m) {
+            const int n = l + 16 * m;
+            taps[2 * (l * 32 + m)] = padded[2 * n] * fold;
+            taps[2 * (l * 32 + m) + 1] = padded[2 * n + 1] * fold;
+        }
+        for (int m = 0; m < 16; ++m) {
+            const int n = l + 16 * m;
+            tw[2 * (l * 16 + m)] = tw512[2 * n];
+            tw[2 * (l * 16 + m) + 1] = tw512[2 * n + 1];
+        }
+    }
+}
+
 } // namespace mfx
 
 namespace mfx {

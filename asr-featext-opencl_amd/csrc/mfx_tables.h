@@ -47,6 +47,42 @@ void build_plp_lifter(int ceps_len, float lift_coef, std::vector<float> &out);
 // exp(-2*pi*i*k/n) for k in [0, count), evaluated in double and rounded once to float.
 void build_twiddles(int n, int count, std::vector<float> &re_im_interleaved);
 
+// Split twiddles -i W_WS^k = (wi, -wr), k <= WS / 2, of the real-input split (every front end; k_front512 stages the first
+// 128).  WS = fft_size, or 512 in the zero-stuffed forms (256 / 128 / 64 points on k_front512), which run the 512-POINT
+// transform and its split: the kernel stages W_512^k for k < 128 whatever fft_size is.  (Until round 4 this table had
+// fft_size / 2 + 1 entries: at 128 and 64 points the kernel read 63 / 95 entries past its end.  The split's difference
+// term is rounding noise there, so fresh -- zero -- memory hid it; stale memory with large values did not: found by
+// tools/fuzz_all.py, seed 3 case 17.)
+void build_split_twiddles(int fft_size, bool stuffed, std::vector<float> &out);
+
+// k_front_reg (fft_size >= 1024): per-pass twiddle tables laid out [k][butterfly] so that the lanes of one LDS read touch
+// consecutive words.  M = fft_size / 2, R1 = 8 at 1024 points, else 16.  Pass 1 (radix R1 over M points): W_M^(pp k),
+// pp < M / R1; pass 2 (radix R1 over M / R1 points): W_M^(pp k R1), pp < M / R1^2; k = 1 .. R1 - 1 in both.  Same values as
+// build_twiddles(M, M).
+void build_reg_pass_twiddles(int fft_size, std::vector<float> &out);
+
+// k_front512 / k_front1024: out[l * 16 + k] = W_256^(l k), l, k < 16.
+void build_pass256_twiddles(std::vector<float> &out);
+
+// Window layouts of the register front ends.  `padded`: the window zero-padded to fft_size taps.  Every layout carries the
+// output scale 0.5 / fft_size (1/2 of the real split, 1 / fft_size of mfcccpu.cpp:203): a power of two, so scaling the taps
+// instead of the magnitudes changes no bit of the result and saves a multiply per bin.
+//
+// k_front512, and k_front1024 with a window of at most 512 samples: out[l * 16 + m] = (w[2 n], w[2 n + 1]) * scale,
+// n = l + 16 m.  Zero-stuffed forms (fft_size < 512): packed sample n = (x[n / step], 0) where step = 256 / fft_size
+// divides n, else (0, 0), so out[l * 16 + m] = (w[n / step] * scale, 0) or zero.
+void build_window_pairs(const std::vector<float> &padded, int fft_size, bool stuffed, std::vector<float> &out);
+
+// Phase O of k_front1024 (window <= 512 samples): (taps of pair n) x W_512^n as the real 2 x 2 form
+//   re = A x0 + B x1,  im = C x0 + D x1,   (A, B, C, D) = (t0 c, -t1 s, t0 s, t1 c),  W_512^n = c + i s
+// out[l * 16 + m] = (A, B, C, D) of n = l + 16 m.
+void build_front1024_phase_o(const std::vector<float> &padded, int fft_size, std::vector<float> &out);
+
+// k_front1024, window longer than 512 samples: the taps of all 32 rows of sample pairs, taps[l * 32 + m] = (w[2 n],
+// w[2 n + 1]) * scale, n = l + 16 m, m < 32, and the twiddles of the first 16 rows, tw[l * 16 + m] = W_512^n, m < 16; the
+// kernel folds the frame's halves itself.
+void build_front1024_long_window(const std::vector<float> &padded, int fft_size, std::vector<float> &taps, std::vector<float> &tw);
+
 } // namespace mfx
 
 namespace mfx {

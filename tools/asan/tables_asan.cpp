@@ -1,6 +1,7 @@
 // Sanitizer run of the host table builders (csrc/mfx_tables.cpp) under -fsanitize=address,undefined: mel table, DCT
 // matrix, twiddles, the 16-lane mel plan of the 512-point kernel and the 64- and 32-lane wave plans, over a grid of
-// configurations (bank counts, transform sizes, sample rates, band edges, VTLN warps).  Built by `make -C csrc asan`.
+// configurations (bank counts, transform sizes, sample rates, band edges, VTLN warps), and the front ends' FFT pass / split
+// twiddle tables and window layouts.  Built by `make -C csrc asan`.
 #include <cstdio>
 #include <vector>
 
@@ -41,8 +42,34 @@ int main()
                     }
     std::vector<float> tw;
     for (int fft : ffts) mfx::build_twiddles(fft, fft / 2 + 1, tw);
+    // the FFT and window tables of the front ends, on the shapes the kernels use: every transform size, the zero-stuffed
+    // forms below 512 points, a 400-sample window and a window longer than 512 samples at 1024 points
+    int nt = 0;
+    for (int fft : ffts) {
+        std::vector<float> t, t2;
+        for (bool stuffed : {false, true}) {
+            if (stuffed && fft >= 512) continue; // (k_front512 stuffs 256 / 128 / 64 points only)
+            mfx::build_split_twiddles(fft, stuffed, t);
+            if (t.size() != (size_t)2 * ((stuffed ? 512 : fft) / 2 + 1)) return 1;
+            ++nt;
+        }
+        if (fft >= 1024) mfx::build_reg_pass_twiddles(fft, t), ++nt;
+        for (int W : {fft / 2 + 1, 400, 800, fft}) {
+            if (W > fft) continue;
+            std::vector<float> padded((size_t)fft, 0.f);
+            for (int i = 0; i < W; ++i) padded[i] = 0.5f + 0.001f * (float)i;
+            if (fft <= 512) mfx::build_window_pairs(padded, fft, /*stuffed=*/fft < 512, t), ++nt;
+            if (fft == 1024 && W <= 512) {
+                mfx::build_window_pairs(padded, fft, false, t);
+                mfx::build_front1024_phase_o(padded, fft, t2);
+                nt += 2;
+            }
+            if (fft == 1024 && W > 512) mfx::build_front1024_long_window(padded, fft, t, t2), ++nt;
+        }
+    }
+    mfx::build_pass256_twiddles(tw);
     for (long s : {0L, 1L, 399L, 400L, 160000L, 57600000L, 1L << 31})
         for (int W : {400, 1024}) (void)mfx::frame_count(s, W, 160);
-    std::printf("tables_asan: %d configurations clean\n", n);
+    std::printf("tables_asan: %d configurations, %d front-end tables clean\n", n, nt);
     return 0;
 }
