@@ -17,6 +17,7 @@ from .mfcc import (  # noqa: F401
     DYN_NONE,
     METHOD_MFCC,
     METHOD_PLP,
+    METHOD_TRAPS,
     NORM_CMN,
     NORM_CVN,
     NORM_MINMAX,
@@ -30,6 +31,7 @@ from .mfcc import (  # noqa: F401
     host_mel_lane_plan,
     host_mel_table,
     host_plp_tables,
+    host_traps_basis,
     KERNEL_TABLE,
     library_path,
     load_library,

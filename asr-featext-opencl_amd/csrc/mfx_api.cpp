@@ -33,7 +33,7 @@ void fill_melcep(const mfx_handle *h, const CepTables &t, MelcepParams &mp)
     mp.dct_ksteps = h->dct_ksteps;
     mp.num_banks = h->nb;
     mp.dct_len = h->dl;
-    mp.cols = h->cols;
+    mp.cols = h->fcols;
     mp.mel_w_stride = (int64_t)2 * h->W2;
     mp.mel_beg_stride = h->nb + 2;
 }
@@ -194,7 +194,7 @@ void fill_front(const mfx_handle *h, FrontParams &p)
     p.dct = h->ceps > 0 ? h->d_dct.p : nullptr;
     p.num_banks = h->nb;
     p.dct_len = h->dl;
-    p.cols = h->cols;
+    p.cols = h->fcols;
     p.scale = 0.5f / (float)h->W2;
     p.mel_lane_w = h->d_mel_lane_w.p;
     p.mel_lane_start = h->d_mel_lane_start.p;
@@ -203,7 +203,7 @@ void fill_front(const mfx_handle *h, FrontParams &p)
     p.mel_rounds = h->plan.rounds;
     p.mel_row_stride = h->plan.row_stride;
     for (int i = 0; i < 8; ++i) p.mel_L[i] = h->plan.L[i];
-    p.dct_mode = (h->ceps > 0 && h->cols <= 16 && h->nb <= 40) ? 1 : 0; // DCT on the matrix pipe
+    p.dct_mode = (h->ceps > 0 && h->fcols <= 16 && h->nb <= 40) ? 1 : 0; // DCT on the matrix pipe
     p.mel64_w = h->own.w64.p;
     p.mel64_start = h->own.start64.p;
     p.mel64_fid = h->own.fid64.p;
@@ -225,6 +225,17 @@ void fill_front(const mfx_handle *h, FrontParams &p)
     p.dct_ksteps = h->dct_ksteps;
     p.dct_stride = h->dct_stride;
     p.nb_pad = h->nb_pad > 0 ? h->nb_pad : ((h->nb + 3) & ~3);
+}
+
+// k_traps parameters that do not depend on the caller
+void fill_traps(const mfx_handle *h, TrapsParams &p)
+{
+    std::memset(&p, 0, sizeof(p));
+    p.num_banks = h->nb;
+    p.L = h->traps_L;
+    p.K = h->traps_K;
+    p.valu = (h->cfg.engine & MFX_ENGINE_TRAPS_VALU) ? 1 : 0;
+    p.operands = h->d_traps_b.p;
 }
 
 namespace {
@@ -323,7 +334,10 @@ int launch_cepstra(mfx_handle *h, const CepTables &t, const float *spec, int64_t
 // ------------------------------------------------------------------------------------------------
 
 extern "C" int mfx_abi_version(void) { return MFX_ABI_VERSION; }
-extern "C" int mfx_method_supported(int32_t method) { return method == MFX_METHOD_MFCC || method == MFX_METHOD_PLP ? 1 : 0; }
+extern "C" int mfx_method_supported(int32_t method)
+{
+    return method == MFX_METHOD_MFCC || method == MFX_METHOD_PLP || method == MFX_METHOD_TRAPS ? 1 : 0;
+}
 
 extern "C" const char *mfx_status_string(int status)
 {
@@ -381,10 +395,20 @@ int create_impl(const mfx_config *cfg, int hip_device, bool planning, mfx_handle
     if (cfg->ceps_len > 0 && cfg->lift_coef == 0.f) return MFX_ERR_CONFIG; // reference divides by lift_coef
     if (cfg->dyn != MFX_DYN_NONE && cfg->delta_l1 <= 0) return MFX_ERR_CONFIG;
     if (cfg->dyn == MFX_DYN_ACC && cfg->delta_l2 <= 0) return MFX_ERR_CONFIG;
-    if (cfg->method != MFX_METHOD_MFCC && cfg->method != MFX_METHOD_PLP) return MFX_ERR_CONFIG;
+    if (!mfx_method_supported(cfg->method)) return MFX_ERR_CONFIG;
     if (cfg->method == MFX_METHOD_PLP) { // PLP has no log-energy form; the recursion runs in registers up to kPlpMaxOrder
         const int p = cfg->lpc_order == 0 ? 8 : cfg->lpc_order;
         if (cfg->ceps_len <= 0 || cfg->lpc_order < 0 || p > std::min(kPlpMaxOrder, (int)cfg->num_banks)) return MFX_ERR_CONFIG;
+    }
+    const bool traps = cfg->method == MFX_METHOD_TRAPS;
+    const int traps_L = cfg->traps_len == 0 ? 31 : cfg->traps_len, traps_K = cfg->traps_dct_len == 0 ? 10 : cfg->traps_dct_len;
+    if (traps) {
+        // the log-energy form feeds it; the output row holds num_banks * K statics, and 256 columns is what the normaliser's
+        // statistics kernels take (k_norm_stats / k_norm_seg: one thread per column of a 256-thread block)
+        if (cfg->ceps_len != 0 || cfg->want_c0 != 0) return MFX_ERR_CONFIG;
+        if (cfg->traps_len < 0 || !(traps_L & 1) || traps_L < 3 || traps_L > 101) return MFX_ERR_CONFIG;
+        if (cfg->traps_dct_len < 0 || traps_K > 32 || traps_K > traps_L) return MFX_ERR_CONFIG;
+        if ((int64_t)cfg->num_banks * traps_K > 256) return MFX_ERR_CONFIG;
     }
 
     if (!planning) {
@@ -410,7 +434,11 @@ int create_impl(const mfx_config *cfg, int hip_device, bool planning, mfx_handle
     h->l2 = cfg->dyn == MFX_DYN_ACC ? cfg->delta_l2 : 0;
     h->D = h->l1 + h->l2;
     h->dl = cfg->want_c0 ? cfg->ceps_len + 1 : cfg->ceps_len;
-    h->cols = h->ceps > 0 ? h->dl : h->nb;
+    h->traps = traps;
+    h->traps_L = traps ? traps_L : 0;
+    h->traps_K = traps ? traps_K : 0;
+    h->fcols = h->ceps > 0 ? h->dl : h->nb;
+    h->cols = traps ? h->nb * traps_K : h->fcols;
     h->width = h->cols * (cfg->dyn == MFX_DYN_ACC ? 3 : cfg->dyn == MFX_DYN_DELTA ? 2 : 1);
     h->channels = cfg->channels == 2 ? 2 : 1;
     h->W2 = (int)ceil_pow2((uint32_t)h->W);
@@ -426,11 +454,11 @@ int create_impl(const mfx_config *cfg, int hip_device, bool planning, mfx_handle
     h->window_limit = h->input_window_limit + 2 + (cfg->dyn != MFX_DYN_NONE ? 3 * h->D : 0);
     if (h->input_window_limit <= 0 || h->window_limit <= 0) return MFX_ERR_CONFIG;
     h->spec_pitch = ((h->W2 / 2 + 1) + 3) & ~3;
-    h->fast512 = front512_supported(h->W2, h->W, h->nb, h->cols, h->channels) && !(h->W2 < 512 && (h->cfg.engine & MFX_ENGINE_NO_STUFF256));
+    h->fast512 = front512_supported(h->W2, h->W, h->nb, h->fcols, h->channels) && !(h->W2 < 512 && (h->cfg.engine & MFX_ENGINE_NO_STUFF256));
     h->stuff256 = h->fast512 && h->W2 < 512; // (256, 128 or 64 points: stuff factor 512 / W2)
-    h->fast2048 = !(h->cfg.engine & MFX_ENGINE_NO_FRONT2048) && front2048_supported(h->W2, h->W, h->nb, h->cols, h->channels);
+    h->fast2048 = !(h->cfg.engine & MFX_ENGINE_NO_FRONT2048) && front2048_supported(h->W2, h->W, h->nb, h->fcols, h->channels);
     h->fast1024 = !(h->cfg.engine & MFX_ENGINE_NO_FRONT1024) &&
-                  front1024_supported(h->W2, h->W, h->nb, h->cols, h->channels, h->ceps);
+                  front1024_supported(h->W2, h->W, h->nb, h->fcols, h->channels, h->ceps);
     {
         hipDeviceProp_t prop;
         if (!planning && hipGetDeviceProperties(&prop, hip_device) == hipSuccess && prop.multiProcessorCount > 0)
@@ -491,6 +519,22 @@ int create_impl(const mfx_config *cfg, int hip_device, bool planning, mfx_handle
         DEV_OK(h->upload(h->d_plp_idft, idft));
         DEV_OK(h->upload(h->d_plp_lift, lift));
     }
+    if (h->traps) {
+        std::vector<float> basis, ob;
+        build_traps_basis(h->traps_L, h->traps_K, basis);
+        int a = 0, b = 0;
+        if (h->cfg.engine & MFX_ENGINE_TRAPS_VALU)
+            build_traps_valu_operands(basis, h->traps_L, h->traps_K, a, ob);
+        else
+            build_traps_mfma_operands(basis, h->traps_L, h->traps_K, a, b, ob);
+        DEV_OK(h->upload(h->d_traps_b, ob));
+        // the delta stage's LDS holds (R + 2 D) + (R + 2 l2) + R rows of `cols` floats, R = 32 for wide rows: at 256 columns
+        // that is the binding limit only beyond l1 = l2 = 10 (the normaliser's 256 columns bind first, checked above)
+        if ((size_t)(3 * 32 + 2 * h->D + 2 * h->l2) * h->cols * sizeof(float) > kLdsCap) return MFX_ERR_CONFIG;
+        TrapsParams tp;
+        fill_traps(h, tp);
+        if (traps_tile_rows(tp) == 0) return MFX_ERR_CONFIG;
+    }
     if (const int rc = refresh_mel(h); rc != MFX_OK) return rc;
 
     // ---- streaming buffers (capacity as the reference: segmentercpu.cpp:40-41, mfcccpu.cpp:104-112)
@@ -501,13 +545,16 @@ int create_impl(const mfx_config *cfg, int hip_device, bool planning, mfx_handle
     h->cap_rows = h->window_limit + h->W / h->S + 4;
     st.carry_capacity = (size_t)h->cap_rows * h->S + 2 * (size_t)h->W;
     const size_t carry_alloc = (st.carry_capacity + h->W2 + 8) & ~(size_t)1;
-    for (int i = 0; i < 2; ++i) {
+    // (a TRAPS handle has no streaming entries: no carry, no block buffers)
+    for (int i = 0; i < 2 && !h->traps; ++i) {
         DEV_OK(h->alloc(st.d_carry[i], carry_alloc));
         if (!planning) DEV_OK(hipMemset(st.d_carry[i].p, 0, carry_alloc * sizeof(int16_t)));
     }
     DEV_OK(h->alloc(h->d_spec, (size_t)h->cap_rows * h->spec_pitch));
-    DEV_OK(h->alloc(st.d_src, (size_t)h->cap_rows * h->cols));
-    DEV_OK(h->alloc(st.d_blk, (size_t)h->cap_rows * h->width));
+    if (!h->traps) {
+        DEV_OK(h->alloc(st.d_src, (size_t)h->cap_rows * h->cols));
+        DEV_OK(h->alloc(st.d_blk, (size_t)h->cap_rows * h->width));
+    }
     DEV_OK(h->alloc(st.d_stats, (size_t)3 * 2 * h->cols));
     if (h->plp) DEV_OK(h->alloc(st.d_plp_r, (size_t)h->cap_rows * (h->lpc + 1)));
     if (cfg->norm != MFX_NORM_NONE) { // chunk results of the statistics over a long streaming block
@@ -533,7 +580,7 @@ int create_impl(const mfx_config *cfg, int hip_device, bool planning, mfx_handle
     st.host_tail = !(h->cfg.engine & MFX_ENGINE_DMA_SMALL_BLOCKS) && (st.carry_capacity + 8) * sizeof(int16_t) < kSmallBlock;
     // (+ 16 bytes: small blocks are staged at the destination's alignment; host_tail: tail + block, up to the carry capacity)
     const size_t stage_n = (st.host_tail ? st.carry_capacity : (size_t)h->input_buffer_size) + 8;
-    if (!planning) DEV_OK(st.h_stage.grow(stage_n, stage_n, h->stream));
+    if (!planning && !h->traps) DEV_OK(st.h_stage.grow(stage_n, stage_n, h->stream));
 #undef DEV_OK
 
     *out = owner.release();
@@ -618,7 +665,8 @@ extern "C" int mfx_profile_read(mfx_handle *h, int32_t *launches, double *kernel
 // fits (<= 2048 points), then spectrum through an HBM slab + k_melcep.
 FrontKind choose_front(const mfx_handle *h)
 {
-    // (else: the streaming interface's kernels; PLP has no fused front end: spectrum through HBM, then k_plp)
+    // (else: the streaming interface's kernels; PLP has no fused front end: spectrum through HBM, then k_plp.  TRAPS takes
+    // whatever the fbank handle of its shape takes: its front end IS that handle's, k_traps follows it)
     const bool allow_fused = !(h->cfg.engine & MFX_ENGINE_STREAM_KERNELS) && !h->plp;
     if (allow_fused && h->fast512 && h->fused_ok) return kFront512;
     // (k_front1024, windows longer than 512 samples: aligned frames only)
@@ -748,6 +796,15 @@ extern "C" int64_t mfx_debug_read(mfx_handle *h, int kind, void *dst, int64_t ds
 // ------------------------------------------------------------------------------------------------
 // host-side table builders (no device)
 // ------------------------------------------------------------------------------------------------
+
+extern "C" int mfx_host_traps_basis(int32_t traps_len, int32_t traps_dct_len, float *basis)
+{
+    if (traps_len < 2 || traps_dct_len < 1 || !basis) return MFX_ERR_ARG;
+    std::vector<float> b;
+    build_traps_basis(traps_len, traps_dct_len, b);
+    std::copy(b.begin(), b.end(), basis);
+    return MFX_OK;
+}
 
 extern "C" int mfx_host_plp_tables(int32_t num_banks, int32_t fft_size, float sample_rate, float low_freq, float high_freq,
                                    float alpha, int32_t lpc_order, float *eql, float *idft)

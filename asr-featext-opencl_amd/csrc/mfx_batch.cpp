@@ -181,7 +181,7 @@ int size_static16(mfx_handle *h)
 {
     const size_t need = (size_t)h->batch.total_rows * 16;
     for (int b = 0; b < (h->batch.overlap ? 2 : 1); ++b)
-        if (h->l1 > 0 && h->cols <= 16 && h->batch.d_static16[b].n < need) HIP_TRY(h, h->batch.d_static16[b].alloc(need));
+        if (h->l1 > 0 && h->cols <= 16 && !h->traps && h->batch.d_static16[b].n < need) HIP_TRY(h, h->batch.d_static16[b].alloc(need));
     return MFX_OK;
 }
 
@@ -291,6 +291,11 @@ extern "C" int mfx_batch_plan(mfx_handle *h, int32_t n_utt, const int64_t *offse
         if (rcf != MFX_OK) return rcf;
     }
     // (allocated here so that mfx_batch_run_device itself never allocates)
+    if (h->traps) { // log mel rows between the front end and k_traps (grown, never shrunk)
+        h->batch.mel_pitch = (h->nb + 3) & ~3;
+        const size_t need = (size_t)row * h->batch.mel_pitch;
+        if (h->batch.d_logmel.n < need) HIP_TRY(h, h->batch.d_logmel.alloc(need));
+    }
     return size_static16(h);
 }
 
@@ -329,8 +334,11 @@ int batch_run_range(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_tot
     p.chunks = h->batch.d_chunks.p + rc0;
     p.n_chunks = rc1 - rc0;
     p.row_limit = h->batch.total_rows;
-    p.feat = d_out;
-    p.feat_pitch = h->width;
+    // (TRAPS: the front end's log mel rows go to the scratch; k_traps turns them into the statics of d_out)
+    p.feat = h->traps ? h->batch.d_logmel.p : d_out;
+    p.feat_pitch = h->traps ? h->batch.mel_pitch : h->width;
+    if (h->traps && h->batch.d_logmel.n < (size_t)h->batch.total_rows * h->batch.mel_pitch)
+        return fail(h, MFX_ERR_STATE, "batch not planned");
 
     // Which front end: the 512-point register kernel, else the fused wave-per-frame kernel when its
     // LDS fits, else spectrum through an HBM slab + melcep.
@@ -345,7 +353,7 @@ int batch_run_range(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_tot
     // event, so the memory-bound tail of batch i shares the GPU with the compute-bound front end of
     // batch i+1; the statics scratch is double buffered and the front end of batch i+2 waits for tail i.
     const int sb = (h->batch.overlap && whole) ? (int)(h->batch.seq & 1) : 0;
-    const bool via_scratch = ((fused512 && p.dct_mode == 1) || fused1024 || fused2048 || fusedgen) && h->l1 > 0 && h->cols <= 16 && !norm_before &&
+    const bool via_scratch = ((fused512 && p.dct_mode == 1) || fused1024 || fused2048 || fusedgen) && h->l1 > 0 && h->cols <= 16 && !h->traps && !norm_before &&
                              h->batch.d_static16[sb].n >= (size_t)h->batch.total_rows * 16;
     // Fused delta stage: the 512-point kernel's last wave per block turns the statics into whole output
     // rows while the other 15 produce them; no separate delta launch.
@@ -426,6 +434,18 @@ int batch_run_range(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_tot
         }
     }
 
+    if (h->traps) { // part of the front end: on the handle's stream, before anything of the tail
+        TrapsParams tp;
+        fill_traps(h, tp);
+        tp.src = h->batch.d_logmel.p;
+        tp.src_pitch = h->batch.mel_pitch;
+        tp.out = d_out;
+        tp.out_pitch = h->width;
+        tp.segs = h->batch.d_segs.p + u0;
+        tp.n_segs = u1 - u0;
+        tp.tiles_per_seg_max = h->batch.tiles_max;
+        HIP_TRY(h, launch_traps(tp, h->stream));
+    }
     if (split_tail) {
         HIP_TRY(h, hipEventRecord(h->batch.ev_front[sb], h->stream));
         HIP_TRY(h, hipStreamWaitEvent(h->batch.stream2, h->batch.ev_front[sb], 0));

@@ -152,6 +152,8 @@ struct BatchState {
     DevBuf<mfx::Segment> d_segs;
     DevBuf<float> d_stats, d_spec_slab, d_host_out;
     DevBuf<int16_t> d_host_pcm;          // mfx_batch_run_host: device copies of the caller's host buffers
+    DevBuf<float> d_logmel;      // TRAPS: log mel rows [total_rows][mel_pitch] between the front end and k_traps
+    int mel_pitch = 0;
     DevBuf<float> d_static16[2]; // compact [rows][16] statics between front end and delta (double buffered for overlap)
     // optional overlap of the delta/normalisation tail of batch i with the front end of batch i+1
     bool overlap = false;
@@ -198,7 +200,10 @@ struct mfx_handle {
 
     // ---- shared: geometry and tables, written at create / refresh_mel / set_window only
     // derived (mfccbase.cpp:18-30, mfcccpu.cpp:94-105)
-    int W = 0, S = 0, W2 = 0, nb = 0, ceps = 0, dl = 0, cols = 0, width = 0;
+    // cols: static columns of an output row (delta, normalisation, width, statistics); fcols: columns the front end
+    // delivers -- the same number except for TRAPS, whose front end is the log-energy form (nb columns) and whose rows
+    // hold nb * traps_K statics
+    int W = 0, S = 0, W2 = 0, nb = 0, ceps = 0, dl = 0, cols = 0, fcols = 0, width = 0;
     int l1 = 0, l2 = 0, D = 0;
     int input_window_limit = 0, input_buffer_size = 0, window_limit = 0, cap_rows = 0;
     int spec_pitch = 0;
@@ -210,6 +215,8 @@ struct mfx_handle {
     int nm16 = 16;
     bool plp = false;  // mfx_config.method == MFX_METHOD_PLP: k_plp where MFCC runs k_melcep, never the fused front ends
     int lpc = 0;       // PLP model order (lpc_order, 0 -> 8)
+    bool traps = false; // mfx_config.method == MFX_METHOD_TRAPS: fbank front end -> scratch -> k_traps; batch entries only
+    int traps_L = 0, traps_K = 0; // trajectory length, coefficients kept (defaults applied)
     float alpha = 1.f;
     bool have_window = false;
 
@@ -220,6 +227,8 @@ struct mfx_handle {
     CepTables own;
     // PLP: autocorrelation basis, lifter
     DevBuf<float> d_plp_idft, d_plp_lift;
+    // TRAPS: k_traps' operand table (matrix-pipe or vector form, by MFX_ENGINE_TRAPS_VALU)
+    DevBuf<float> d_traps_b;
     // 512-point kernel: per-lane mel plan + transposed DCT matrix
     DevBuf<float> d_mel_lane_w, d_dct_t;
     DevBuf<int32_t> d_mel_lane_start, d_mel_lane_fid;
@@ -306,11 +315,20 @@ inline int fail_hip(mfx_handle *h, hipError_t e, const char *what)
         if ((h)->planning) return fail((h), MFX_ERR_DEVICE, "planning handle (mfx_plan_create): no device behind it");      \
     } while (0)
 
+// top of every streaming entry: TRAPS handles have none (the streaming state machine's context is D frames, not H)
+#define MFX_STREAM_ENTRY(h)                                                                                                  \
+    do {                                                                                                                     \
+        if ((h)->traps)                                                                                                      \
+            return fail((h), MFX_ERR_STATE,                                                                                  \
+                        "TRAPS handles have no streaming entries: use mfx_batch_plan + mfx_batch_run_device / mfx_batch_run_host"); \
+    } while (0)
+
 // ---- mfx_api.cpp, for the other two
 // Which front-end kernel the BATCH entries run for this handle (see choose_front's definition)
 enum FrontKind { kFront512, kFront1024, kFront2048, kFrontGenFused, kSpec512, kSpecGen };
 FrontKind choose_front(const mfx_handle *h);
 void fill_front(const mfx_handle *h, mfx::FrontParams &p);
+void fill_traps(const mfx_handle *h, mfx::TrapsParams &p);
 int refresh_mel(mfx_handle *h);
 int build_cep_tables(mfx_handle *h, const float *alphas, int n, CepTables &t, mfx::MelTable *first = nullptr,
                      mfx::MelWavePlan *first_plan = nullptr);

@@ -1,4 +1,4 @@
-// mfx_kernels.h -- launch interface of the gfx950 kernels (implemented in mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip, mfx_plp.hip: one translation unit per kernel family).
+// mfx_kernels.h -- launch interface of the gfx950 kernels (implemented in mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip, mfx_plp.hip, mfx_traps.hip: one translation unit per kernel family).
 //
 // Kernel inventory and the reference stage each one replaces:
 //   spectrum512 / fused512   segmenter.cl kernelSegmentWindow + AppleFFT fft0 + mfcc.cl kernelTranspose
@@ -6,6 +6,7 @@
 //   spectrum_generic         same three stages for any power-of-two FFT length
 //   melcep                   mfcc.cl kernelFilter + DCT slot (mfccopencl.cpp:315-358) from a stored spectrum
 //   plp                      PLP cepstra from a stored spectrum (no reference kernel: the reference names the method only)
+//   traps                    TRAPS temporal patterns from stored log mel rows (no reference kernel: the reference names the method only)
 //   delta                    delta.cl kernelDelta x2 + the staging copies of mfccopencl.cpp:360-387
 //   norm_stats / norm_apply  norm.cl kernelSum + kernelFinalizeSum / kernelNormalize
 #pragma once
@@ -179,6 +180,24 @@ struct PlpParams {
 };
 constexpr int kPlpMaxOrder = 32;
 
+// k_traps (mfx_traps.hip): log mel rows -> per band the Hamming-windowed DCT-II of the L frames around every frame
+// (TRAPS).  One Segment per utterance: rows src_row0 + clamp(t - (L - 1) / 2 + j, lo, hi) are read, rows
+// out_row0 + t, t < n_out, written (shift / static_off / pad are not used).  Statics land at columns m * K + k.
+struct TrapsParams {
+    const float *src;      // log mel energies, [rows][src_pitch], columns [0, num_banks)
+    int32_t src_pitch;
+    float *out;            // [rows][out_pitch], columns [0, num_banks * K) written
+    int32_t out_pitch;
+    const Segment *segs;
+    int32_t n_segs;
+    int32_t num_banks;     // M
+    int32_t L, K;          // trajectory length (odd), coefficients kept
+    int32_t valu;          // 0: matrix pipe, operands = build_traps_mfma_operands; 1: vector ALUs, build_traps_valu_operands
+    const float *operands;
+    int32_t tiles_per_seg_max; // in tiles of 64 rows, as DeltaParams
+    int32_t tile_rows;     // set by the launcher: 64, 32 or 16 output rows per block
+};
+
 struct DeltaParams {
     const float *src;      // static features, [rows][src_pitch]
     int32_t src_pitch;
@@ -223,6 +242,10 @@ size_t front_wave_lds_bytes(const FrontParams &p, bool fused);
 hipError_t launch_melcep(const MelcepParams &p, hipStream_t stream);
 hipError_t launch_delta(const DeltaParams &p, hipStream_t stream);
 hipError_t launch_plp(const PlpParams &p, hipStream_t stream);
+hipError_t launch_traps(const TrapsParams &p, hipStream_t stream);
+// LDS of k_traps with tile_rows output rows per block; traps_tile_rows: the tile the launcher takes (0: none fits)
+size_t traps_lds_bytes(const TrapsParams &p, int tile_rows);
+int traps_tile_rows(const TrapsParams &p);
 // LDS of k_plp with n_waves waves per block (the launcher takes as many of 4 as fit)
 size_t plp_lds_bytes(const PlpParams &p, int n_waves);
 // LDS of k_melcep with n_waves waves per block (the launcher takes as many of 4 as fit)

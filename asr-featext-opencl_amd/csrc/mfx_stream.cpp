@@ -189,6 +189,7 @@ int stage_host_tail(mfx_handle *h, int pending, const int16_t *block, int sample
 extern "C" int mfx_set_input(mfx_handle *h, const int16_t *pcm, int32_t samples, int32_t *frames_out)
 {
     MFX_DEVICE_ENTRY(h);
+    MFX_STREAM_ENTRY(h);
     if (!pcm || !frames_out || samples < 0) return fail(h, MFX_ERR_ARG, "invalid argument");
     *frames_out = 0;
     if (!h->have_window) return fail(h, MFX_ERR_STATE, "set_window has not been called");
@@ -262,6 +263,7 @@ extern "C" int mfx_set_input(mfx_handle *h, const int16_t *pcm, int32_t samples,
 extern "C" int mfx_flush(mfx_handle *h, int32_t *frames_out)
 {
     MFX_DEVICE_ENTRY(h);
+    MFX_STREAM_ENTRY(h);
     if (!frames_out) return fail(h, MFX_ERR_ARG, "invalid argument");
     *frames_out = 0;
     if (h->st.last_block) return MFX_OK; // nothing to flush (mfcccpu.cpp:350-351)
@@ -439,12 +441,14 @@ int apply_impl(mfx_handle *h, const float *alphas, int n_alpha)
 extern "C" int mfx_apply(mfx_handle *h)
 {
     MFX_DEVICE_ENTRY(h);
+    MFX_STREAM_ENTRY(h);
     return apply_impl(h, nullptr, 0);
 }
 
 extern "C" int mfx_apply_alphas(mfx_handle *h, const float *alphas, int32_t n_alpha)
 {
     MFX_DEVICE_ENTRY(h);
+    MFX_STREAM_ENTRY(h);
     if (!alphas || n_alpha < 1 || n_alpha > 4096) return fail(h, MFX_ERR_ARG, "invalid argument");
     for (int a = 0; a < n_alpha; ++a)
         if (!(alphas[a] > 0.f)) return fail(h, MFX_ERR_ARG, "alpha must be positive");
@@ -454,6 +458,7 @@ extern "C" int mfx_apply_alphas(mfx_handle *h, const float *alphas, int32_t n_al
 extern "C" int mfx_get_output_data_alpha(mfx_handle *h, int32_t alpha_index, float *data_out, int32_t frames)
 {
     MFX_DEVICE_ENTRY(h);
+    MFX_STREAM_ENTRY(h);
     if ((!data_out && frames > 0) || frames < 0) return fail(h, MFX_ERR_ARG, "invalid argument");
     if (h->sweep.n == 0) return fail(h, MFX_ERR_STATE, "no sweep on the current block");
     if (alpha_index < 0 || alpha_index >= h->sweep.n) return fail(h, MFX_ERR_ARG, "alpha index outside the last sweep");
@@ -468,6 +473,7 @@ extern "C" int mfx_get_output_data_alpha(mfx_handle *h, int32_t alpha_index, flo
 extern "C" int mfx_get_output_data(mfx_handle *h, float *data_out, int32_t frames)
 {
     MFX_DEVICE_ENTRY(h);
+    MFX_STREAM_ENTRY(h);
     if ((!data_out && frames > 0) || frames < 0) return fail(h, MFX_ERR_ARG, "invalid argument");
     if (frames > h->cap_rows) return fail(h, MFX_ERR_WINDOW_HIGH, kMsgHigh);
     if (frames == 0) return MFX_OK;

@@ -101,6 +101,43 @@ void build_plp_tables(int num_banks, float sample_rate, float low_freq, float hi
         }
 }
 
+void build_traps_basis(int traps_len, int traps_dct_len, std::vector<float> &out)
+{
+    const double pi = 3.14159265358979323846264338;
+    const int L = traps_len, K = traps_dct_len;
+    out.assign((size_t)K * L, 0.f);
+    const double norm = std::sqrt(2.0 / L);
+    for (int k = 0; k < K; ++k)
+        for (int j = 0; j < L; ++j) {
+            const double w = 0.54 - 0.46 * std::cos(2 * pi * j / (L - 1));
+            out[(size_t)k * L + j] = (float)(w * norm * std::cos(pi * k * (j + 0.5) / L));
+        }
+}
+
+void build_traps_mfma_operands(const std::vector<float> &basis, int traps_len, int traps_dct_len, int &tiles, int &steps,
+                               std::vector<float> &out)
+{
+    const int L = traps_len, K = traps_dct_len;
+    tiles = (K + 15) / 16;
+    steps = (L + 3) / 4;
+    out.assign((size_t)tiles * steps * 64, 0.f);
+    for (int t = 0; t < tiles; ++t)
+        for (int s = 0; s < steps; ++s)
+            for (int lane = 0; lane < 64; ++lane) {
+                const int k = 16 * t + (lane & 15), j = 4 * s + (lane >> 4);
+                if (k < K && j < L) out[((size_t)t * steps + s) * 64 + lane] = basis[(size_t)k * L + j];
+            }
+}
+
+void build_traps_valu_operands(const std::vector<float> &basis, int traps_len, int traps_dct_len, int &kp, std::vector<float> &out)
+{
+    const int L = traps_len, K = traps_dct_len;
+    kp = K <= 4 ? 4 : K <= 16 ? 16 : 32;
+    out.assign((size_t)L * kp, 0.f);
+    for (int j = 0; j < L; ++j)
+        for (int k = 0; k < K; ++k) out[(size_t)j * kp + k] = basis[(size_t)k * L + j];
+}
+
 void build_plp_lifter(int ceps_len, float lift_coef, std::vector<float> &out)
 {
     out.assign((size_t)ceps_len, 0.f);

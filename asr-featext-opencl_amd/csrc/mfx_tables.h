@@ -44,6 +44,19 @@ void build_plp_tables(int num_banks, float sample_rate, float low_freq, float hi
 // lifter weights w_1 .. w_C of the PLP cepstra: the float32 expression of build_dct_matrix
 void build_plp_lifter(int ceps_len, float lift_coef, std::vector<float> &out);
 
+// TRAPS (TRAPS): basis [K][L] of the trajectory transform, evaluated in double and rounded once to float:
+//   B[k][j] = (0.54 - 0.46 cos(2 pi j / (L - 1))) sqrt(2 / L) cos(pi k (j + 1/2) / L)
+// i.e. a Hamming window over the L frames times the DCT-II in build_dct_matrix's convention (k = 0: the windowed mean,
+// scaled like the c0 column).
+void build_traps_basis(int traps_len, int traps_dct_len, std::vector<float> &out);
+// k_traps on the matrix pipe (v_mfma_f32_16x16x4_f32): B operands for every tile of 16 coefficients and every step of 4
+// taps, out[(tile * steps + s) * 64 + lane] = B[16 tile + (lane & 15)][4 s + (lane >> 4)], zero beyond the basis.
+// tiles = ceil(K / 16), steps = ceil(L / 4).
+void build_traps_mfma_operands(const std::vector<float> &basis, int traps_len, int traps_dct_len, int &tiles, int &steps,
+                               std::vector<float> &out);
+// k_traps on the vector ALUs: the basis transposed, [L][kp], kp = K padded to 4, 16 or 32 accumulators (zero beyond K)
+void build_traps_valu_operands(const std::vector<float> &basis, int traps_len, int traps_dct_len, int &kp, std::vector<float> &out);
+
 // exp(-2*pi*i*k/n) for k in [0, count), evaluated in double and rounded once to float.
 void build_twiddles(int n, int count, std::vector<float> &re_im_interleaved);
 

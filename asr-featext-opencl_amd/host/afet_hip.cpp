@@ -44,7 +44,8 @@ struct Options {
     float alpha_min = 1.f, alpha_max = 1.f, alpha_step = 1.f;
     int sample_limit = 10000000, device = 0;
     bool bug_compat = true;
-    int method = MFX_METHOD_MFCC, model_order = 8; // --method MFCC|PLP, --model-order (ASR_OCL.cpp:54-56: default 8)
+    int method = MFX_METHOD_MFCC, model_order = 8; // --method MFCC|PLP|TRAPS, --model-order (ASR_OCL.cpp:54-56: default 8)
+    int traps_len = 31, traps_dct = 10;            // --traps-length, --traps-dct (ASR_OCL.cpp:604-606: defaults 31 and 10)
     bool htk = false; // binary output in HTK parameter-file format instead of the reference's text rows
     int format_threads = 4; // threads that format the text rows of a block (per worker)
     int batch_mb = 16;      // PCM per batch of files (0: the per-file loop only); small enough that a few thousand files pipeline
@@ -154,8 +155,9 @@ void put_be16(FILE *f, uint16_t v)
 }
 void write_htk_header(FILE *f, uint32_t n_frames, const Options &o, int width)
 {
-    uint16_t kind = o.method == MFX_METHOD_PLP ? 11 /* PLP */ : o.ceps > 0 ? 6 /* MFCC */ : 7 /* FBANK */;
-    if (o.ceps > 0 && o.c0) kind |= 0x2000;  // _0
+    const bool traps = o.method == MFX_METHOD_TRAPS;
+    uint16_t kind = traps ? 9 /* USER */ : o.method == MFX_METHOD_PLP ? 11 /* PLP */ : o.ceps > 0 ? 6 /* MFCC */ : 7 /* FBANK */;
+    if (!traps && o.ceps > 0 && o.c0) kind |= 0x2000;  // _0
     if (o.dyn >= 1) kind |= 0x0100;          // _D
     if (o.dyn >= 2) kind |= 0x0200;          // _A
     if (o.norm == 1) kind |= 0x0800;         // _Z (zero mean)
@@ -484,7 +486,8 @@ bool prepare_batch(Batch &b, const Options &o, const std::vector<std::string> &f
             const long long T = n >= (size_t)W ? (long long)((n - (size_t)(W - S)) / (size_t)S) : 0;
             // the per-file loop keeps: files of more than one block, files too short for the deltas' context (the
             // reference refuses or mangles them: same messages from the same code), alpha sweeps
-            it.stream = sweep || n > (size_t)limit || T < 2 * D + 1;
+            // (TRAPS has no per-file loop: every file is one utterance of a batch, whatever its length)
+            it.stream = o.method != MFX_METHOD_TRAPS && (sweep || n > (size_t)limit || T < 2 * D + 1);
             if (!it.stream) {
                 it.mono.resize(n);
                 const int ch = it.wav.channels;
@@ -533,8 +536,20 @@ void worker(const Options &o, int device, float sr, const std::vector<std::strin
         if (W < 1 || S < 1) throw std::runtime_error("window or shift shorter than one sample at this sample rate");
         // The extractor (HIP start-up, code object load, tables: 0.1-0.3 s of a fresh process) is created on a helper
         // thread while this one claims and reads the first batch of files: reading needs nothing from the device.
-        auto make_param = [&] {
+        auto make_param = [&]() -> std::unique_ptr<MfccHip> {
             const int engine = o.batch_mb > 0 ? MFX_ENGINE_STREAM_KERNELS : 0;
+            if (o.method == MFX_METHOD_TRAPS) { // batch entries only: no engine switch, no reference flush quirk to reproduce
+                std::unique_ptr<TrapsHip> t(new TrapsHip(o.sample_limit, (int)W, (int)S, o.banks, sr, o.low, o.high, o.traps_len,
+                                                         o.traps_dct, (Normalizer::norm_t)o.norm, (ParamBase::dyn_t)o.dyn, o.l1, o.l2,
+                                                         o.norm_after_dyn, device));
+                std::vector<float> window((size_t)W);
+                for (long i = 0; i < W; ++i) // ASR_OCL.cpp:149-151
+                    window[i] = (float)(0.56f - 0.46f * std::cos((2.0f * M_PI * i) / W)) / 32768.f;
+                t->set_window(window.data());
+                t->set_warp(o.alpha_min);
+                if (g_time.on) g_time.t_created = now_ns();
+                return std::unique_ptr<MfccHip>(std::move(t));
+            }
             std::unique_ptr<MfccHip> p(
                 o.method == MFX_METHOD_PLP
                     ? new PlpHip(o.sample_limit, (int)W, (int)S, o.banks, sr, o.low, o.high, o.ceps, o.c0, o.lift, o.model_order,
@@ -678,7 +693,7 @@ void worker(const Options &o, int device, float sr, const std::vector<std::strin
                         // mfcccpu.cpp:439 + segmentercpu.cpp:97-106): rows T - D .. T - 1 repeat the statics of rows
                         // T - 2 D .. T - D - 1 (deltas unaffected).  The batch entries deliver the correct rows; the
                         // per-file loop this replaces reproduces the reference when --bug-compat is on, so do we.
-                        if (o.bug_compat && D > 0)
+                        if (o.bug_compat && D > 0 && o.method != MFX_METHOD_TRAPS)
                             for (int i = 0; i < D; ++i)
                                 std::memcpy(rows + (size_t)(it.row0 + it.frames - D + i) * width,
                                             rows + (size_t)(it.row0 + it.frames - 2 * D + i) * width, (size_t)cols * sizeof(float));
@@ -779,12 +794,15 @@ int main(int argc, char **argv)
         }
         else if (a == "--bug-compat") o.bug_compat = std::atoi(val()) != 0;
         else if (a == "--htk") o.htk = true;
-        else if (a == "--method") { // the reference's names (ASR_OCL.cpp:54-56); TRAPS is not built
+        else if (a == "--method") { // the reference's names (ASR_OCL.cpp:54-56)
             const std::string m = val();
             if (m == "MFCC") o.method = MFX_METHOD_MFCC;
             else if (m == "PLP") o.method = MFX_METHOD_PLP;
-            else { std::fprintf(stderr, "--method: MFCC or PLP (TRAPS is not supported)\n"); return 2; }
+            else if (m == "TRAPS") o.method = MFX_METHOD_TRAPS;
+            else { std::fprintf(stderr, "--method: MFCC, PLP or TRAPS\n"); return 2; }
         }
+        else if (a == "--traps-length") o.traps_len = std::atoi(val());
+        else if (a == "--traps-dct") o.traps_dct = std::atoi(val());
         else if (a == "--model-order") o.model_order = std::atoi(val());
         else if (a == "--timing") g_time.on = true;
         else if (a == "--format-threads") o.format_threads = std::max(1, std::atoi(val()));
@@ -825,7 +843,8 @@ int main(int argc, char **argv)
                         "         [--dyn 0..2] [--l1 n] [--l2 n] [--low-freq hz] [--high-freq hz] [--lift-coef x]\n"
                         "         [--norm-after-dyn 0|1] [--alpha a | --alpha-min a --alpha-max b --alpha-step s]\n"
                         "         [--sample-limit n] [--dev n | --devs a,b,...] [--bug-compat 0|1] [--htk]  in.wav out.txt [...]\n"
-                        "         [--method MFCC|PLP] [--model-order n (PLP model order, default 8)]\n"
+                        "         [--method MFCC|PLP|TRAPS] [--model-order n (PLP model order, default 8)]\n"
+                        "         [--traps-length n (TRAPS frames per trajectory, odd, default 31)] [--traps-dct n (default 10)]\n"
                         "         [--batch-mb n (PCM per batch of whole files; 0 = per-file loop)] [--io-threads n]\n"
                         "  --devs: one worker per listed GPU, files dealt from a shared queue\n"
                         "  inputs: RIFF/WAVE or NIST SPHERE, 16-bit PCM; output: the reference's text rows, or HTK binary\n");
@@ -835,6 +854,16 @@ int main(int argc, char **argv)
     if (files.empty() || files.size() % 2) {
         std::fprintf(stderr, "usage: afet_hip [options] in.wav out.txt [in2.wav out2.txt ...]  (--help)\n");
         return 2;
+    }
+    if (o.method == MFX_METHOD_TRAPS) { // whole files through the batch entries: no per-file loop, no alpha loop, no DCT options
+        if (o.batch_mb <= 0) {
+            std::fprintf(stderr, "--method TRAPS runs whole files through the batch entries: --batch-mb must be positive\n");
+            return 2;
+        }
+        if (o.alpha_max - o.alpha_min >= o.alpha_step) {
+            std::fprintf(stderr, "--method TRAPS takes one warp factor (--alpha), not a sweep\n");
+            return 2;
+        }
     }
     try {
         const Wav first = read_wav(files[0]); // sample rate from the first file (ASR_OCL.cpp:342-358)

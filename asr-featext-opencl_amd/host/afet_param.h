@@ -114,10 +114,12 @@ public:
     mfx_handle *handle() const { return m_handle; }
 
 protected:
-    // method: MFX_METHOD_* of include/mfx.h (PlpHip passes MFX_METHOD_PLP and its model order)
+    // method: MFX_METHOD_* of include/mfx.h (PlpHip passes MFX_METHOD_PLP and its model order, TrapsHip MFX_METHOD_TRAPS
+    // and its two lengths)
     MfccHip(int input_buffer_size, int window_size, int shift, int num_banks, float sample_rate, float low_freq,
             float high_freq, int ceps_len, bool want_c0, float lift_coef, Normalizer::norm_t norm, dyn_t dyn, int delta_l1,
-            int delta_l2, bool norm_after_dyn, int hip_device, bool bug_compat, int engine, int method, int lpc_order);
+            int delta_l2, bool norm_after_dyn, int hip_device, bool bug_compat, int engine, int method, int lpc_order,
+            int traps_len = 0, int traps_dct_len = 0);
 
 private:
     void check(int status) const;
@@ -132,6 +134,20 @@ public:
            float high_freq, int ceps_len, bool want_c0, float lift_coef, int lpc_order,
            Normalizer::norm_t norm = Normalizer::NORM_NONE, dyn_t dyn = DYN_NONE, int delta_l1 = 1, int delta_l2 = 1,
            bool norm_after_dyn = true, int hip_device = 0, bool bug_compat = true, int engine = 0);
+};
+
+// TRAPS temporal patterns (TRAPS) of the log mel energies: traps_dct_len DCT coefficients (0 = 10) of the
+// traps_len frames (0 = 31) around each frame, per band; num_banks * traps_dct_len statics per row.  BATCH ENTRIES ONLY
+// (batch_plan / batch_run_host): set_input, flush, apply and get_output_data throw "TRAPS handles have no streaming
+// entries".  set_alpha takes effect at once (there is no apply() to carry it).
+class TrapsHip : public MfccHip {
+public:
+    TrapsHip(int input_buffer_size, int window_size, int shift, int num_banks, float sample_rate, float low_freq,
+             float high_freq, int traps_len, int traps_dct_len, Normalizer::norm_t norm = Normalizer::NORM_NONE,
+             dyn_t dyn = DYN_NONE, int delta_l1 = 1, int delta_l2 = 1, bool norm_after_dyn = true, int hip_device = 0,
+             int engine = 0);
+    int get_output_data_width() const override; // num_banks * traps_dct_len * (1 + deltas): the library's own answer
+    void set_warp(float alpha);                 // mfx_set_alpha for the next batch run
 };
 
 #endif // AFET_PARAM_H

@@ -66,10 +66,27 @@ PlpHip::PlpHip(int input_buffer_size, int window_size, int shift, int num_banks,
 {
 }
 
+TrapsHip::TrapsHip(int input_buffer_size, int window_size, int shift, int num_banks, float sample_rate, float low_freq,
+                   float high_freq, int traps_len, int traps_dct_len, Normalizer::norm_t norm, dyn_t dyn, int delta_l1,
+                   int delta_l2, bool norm_after_dyn, int hip_device, int engine)
+    : MfccHip(input_buffer_size, window_size, shift, num_banks, sample_rate, low_freq, high_freq, /*ceps_len=*/0, /*want_c0=*/false,
+              /*lift_coef=*/0.f, norm, dyn, delta_l1, delta_l2, norm_after_dyn, hip_device, /*bug_compat=*/false, engine,
+              MFX_METHOD_TRAPS, 0, traps_len, traps_dct_len)
+{
+}
+
+int TrapsHip::get_output_data_width() const { return mfx_get_output_data_width(handle()); }
+
+void TrapsHip::set_warp(float alpha)
+{
+    m_alpha = alpha;
+    if (mfx_set_alpha(handle(), alpha) != MFX_OK) throw std::runtime_error("TrapsHip: set_alpha failed");
+}
+
 MfccHip::MfccHip(int input_buffer_size, int window_size, int shift, int num_banks, float sample_rate, float low_freq,
                  float high_freq, int ceps_len, bool want_c0, float lift_coef, Normalizer::norm_t norm, dyn_t dyn,
                  int delta_l1, int delta_l2, bool norm_after_dyn, int hip_device, bool bug_compat, int engine, int method,
-                 int lpc_order)
+                 int lpc_order, int traps_len, int traps_dct_len)
     : MfccBase(input_buffer_size, window_size, shift, num_banks, sample_rate, low_freq, high_freq, ceps_len, want_c0,
                lift_coef, norm, dyn, delta_l1, delta_l2, norm_after_dyn),
       m_handle(nullptr)
@@ -94,11 +111,13 @@ MfccHip::MfccHip(int input_buffer_size, int window_size, int shift, int num_bank
     cfg.engine = engine;
     cfg.method = method;
     cfg.lpc_order = lpc_order;
+    cfg.traps_len = traps_len;
+    cfg.traps_dct_len = traps_dct_len;
     if (method != MFX_METHOD_MFCC && !mfx_method_supported(method))
         throw std::runtime_error("MfccHip: feature method not supported by this libmfcchip.so");
     const int rc = mfx_create(&cfg, hip_device, &m_handle);
     if (rc != MFX_OK)
-        throw std::runtime_error(std::string(method == MFX_METHOD_PLP ? "PlpHip: " : "MfccHip: ") + mfx_status_string(rc));
+        throw std::runtime_error(std::string(method == MFX_METHOD_PLP ? "PlpHip: " : method == MFX_METHOD_TRAPS ? "TrapsHip: " : "MfccHip: ") + mfx_status_string(rc));
 }
 
 MfccHip::~MfccHip() { mfx_destroy(m_handle); }

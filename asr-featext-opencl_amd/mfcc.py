@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 NORM_NONE, NORM_CMN, NORM_CVN, NORM_MINMAX = 0, 1, 2, 3   # normalizer.h:5
 DYN_NONE, DYN_DELTA, DYN_ACC = 0, 1, 2                     # parambase.h:9
 METHOD_MFCC, METHOD_PLP = 0, 1                             # mfx_config.method (include/mfx.h)
+METHOD_TRAPS = 3                                           # (2 is unassigned and refused)
 
 
 class MfxError(RuntimeError):
@@ -50,6 +51,8 @@ class MfxConfig(C.Structure):
         ("tail_split", C.c_int32),
         ("method", C.c_int32),
         ("lpc_order", C.c_int32),
+        ("traps_len", C.c_int32),
+        ("traps_dct_len", C.c_int32),
     ]
 
 
@@ -66,7 +69,7 @@ EXPORTED_SYMBOLS = (
     "mfx_set_stream", "mfx_synchronize", "mfx_profile_enable", "mfx_profile_read",
     "mfx_dominant_kernel_name", "mfx_debug_read", "mfx_plan_create", "mfx_plan_set_aligned",
     "mfx_host_mel_table", "mfx_host_dct_matrix", "mfx_host_frame_count",
-    "mfx_method_supported", "mfx_host_plp_tables",
+    "mfx_method_supported", "mfx_host_plp_tables", "mfx_host_traps_basis",
 )
 
 
@@ -134,6 +137,7 @@ def load_library():
     L.mfx_host_frame_count.argtypes, L.mfx_host_frame_count.restype = [i64, i32, i32], i64
     L.mfx_method_supported.argtypes = [i32]
     L.mfx_host_plp_tables.argtypes = [i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, i32, fp, fp]
+    L.mfx_host_traps_basis.argtypes = [i32, i32, fp]
     _lib = L
     return L
 
@@ -227,6 +231,16 @@ def host_plp_tables(num_banks, fft_size, sample_rate, low_freq, high_freq, alpha
     return eql, idft
 
 
+def host_traps_basis(traps_len, traps_dct_len):
+    """TRAPS basis exactly as uploaded (host code, no GPU needed): [traps_dct_len][traps_len], Hamming window times DCT-II."""
+    L = load_library()
+    b = np.zeros((int(traps_dct_len), int(traps_len)), dtype=np.float32)
+    rc = L.mfx_host_traps_basis(int(traps_len), int(traps_dct_len), b.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc != 0:
+        raise MfxError(rc, "mfx_host_traps_basis failed")
+    return b
+
+
 def host_frame_count(samples, window_size, shift):
     return int(load_library().mfx_host_frame_count(int(samples), int(window_size), int(shift)))
 
@@ -240,7 +254,8 @@ def reference_window(window_size):
 
 
 def plan_kernel(window_size, shift, num_banks, sample_rate, ceps_len, want_c0=False, dyn=DYN_NONE, fft_size=0, channels=1,
-                aligned=True, engine=0, low_freq=64.0, high_freq=None, input_buffer_size=0, method=METHOD_MFCC, lpc_order=0):
+                aligned=True, engine=0, low_freq=64.0, high_freq=None, input_buffer_size=0, method=METHOD_MFCC, lpc_order=0,
+                traps_len=0, traps_dct_len=0):
     """Which front-end kernel the batch entries run for a shape -- asked of a PLANNING handle (mfx_plan_create: the
     library's own configuration checks, host-built tables and LDS sums, no device, nothing computed).  Works without a
     GPU; returns the kernel's name as rocprofv3 prints it.  Raises MfxError for a configuration mfx_create refuses."""
@@ -251,6 +266,7 @@ def plan_kernel(window_size, shift, num_banks, sample_rate, ceps_len, want_c0=Fa
                     int(engine), 0)
     _check_method(method)
     cfg.method, cfg.lpc_order = int(method), int(lpc_order)
+    cfg.traps_len, cfg.traps_dct_len = int(traps_len), int(traps_dct_len)
     h = C.c_void_p()
     rc = L.mfx_plan_create(C.byref(cfg), C.byref(h))
     if rc != 0:
@@ -311,12 +327,15 @@ class MfccHip:
     Constructor arguments are those of MfccBase (mfccbase.h:21-35) in the same order; ``device``
     replaces MfccOpenCL's trailing ``cl_device_id`` (mfccopencl.h:60).  ``method=METHOD_PLP`` computes PLP cepstra
     of model order ``lpc_order`` (0 = 8) instead of MFCC, with the same interface and output layout.
+    ``method=METHOD_TRAPS`` (``ceps_len=0``, ``want_c0=False``) computes TRAPS temporal patterns: ``traps_dct_len`` (0 = 10)
+    DCT coefficients of the ``traps_len`` (0 = 31) frames around each frame, per mel band -- through the batch entries
+    only; the streaming methods raise ``MfxError`` (-8).
     """
 
     def __init__(self, input_buffer_size, window_size, shift, num_banks, sample_rate, low_freq, high_freq,
                  ceps_len, want_c0, lift_coef, norm=NORM_NONE, dyn=DYN_NONE, delta_l1=1, delta_l2=1,
                  norm_after_dyn=True, device=0, fft_size=0, channels=1, bug_compat=True, batch_norm_stats=0, engine=0,
-                 tail_split=0, method=METHOD_MFCC, lpc_order=0):
+                 tail_split=0, method=METHOD_MFCC, lpc_order=0, traps_len=0, traps_dct_len=0):
         self._L = load_library()
         _check_method(method)
         self.cfg = MfxConfig(int(input_buffer_size), int(window_size), int(shift), int(num_banks),
@@ -324,7 +343,7 @@ class MfccHip:
                              int(bool(want_c0)), float(lift_coef), int(norm), int(dyn), int(delta_l1),
                              int(delta_l2), int(bool(norm_after_dyn)), int(fft_size), int(channels),
                              int(bool(bug_compat)), int(batch_norm_stats), int(engine), int(tail_split),
-                             int(method), int(lpc_order))
+                             int(method), int(lpc_order), int(traps_len), int(traps_dct_len))
         h = C.c_void_p()
         rc = self._L.mfx_create(C.byref(self.cfg), int(device), C.byref(h))
         if rc != 0:

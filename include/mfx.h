@@ -90,10 +90,19 @@ typedef struct mfx_config {
                                   mfx_method_supported first: a library older than this field ignores it (returns MFCC) */
     int32_t lpc_order;         /* PLP: model order p, 1 .. min(32, num_banks); 0 = 8 (the reference CLI's default).
                                   Ignored for MFCC                                                                   */
+    int32_t traps_len;         /* TRAPS: trajectory length L in frames, odd, 3 .. 101; 0 = 31 (the reference CLI's default).
+                                  Ignored unless method is MFX_METHOD_TRAPS                                          */
+    int32_t traps_dct_len;     /* TRAPS: DCT coefficients K kept per band, 1 .. min(32, L); 0 = 10 (the reference CLI's
+                                  default).  Ignored unless method is MFX_METHOD_TRAPS                               */
 } mfx_config;
 
-/* mfx_config.method */
-enum { MFX_METHOD_MFCC = 0, MFX_METHOD_PLP = 1 };
+/* mfx_config.method.  3 = TRAPS temporal patterns (TRAPS): the log mel energies of the MFCC path (ceps_len = 0,
+ * want_c0 = 0 required; lift_coef ignored), per band a Hamming-windowed DCT-II over the traps_len frames around each frame,
+ * traps_dct_len coefficients kept; static row band-major, num_banks * traps_dct_len columns (at most 256).  BATCH ENTRIES
+ * ONLY: on a TRAPS handle mfx_set_input, mfx_flush, mfx_apply, mfx_apply_alphas, mfx_get_output_data and
+ * mfx_get_output_data_alpha return MFX_ERR_STATE.  The value 2 is unassigned and stays refused (mfx_method_supported(2) == 0):
+ * libraries in the field answer for it, so TRAPS did not take it. */
+enum { MFX_METHOD_MFCC = 0, MFX_METHOD_PLP = 1, MFX_METHOD_TRAPS = 3 };
 
 /* mfx_config.engine bits */
 #define MFX_ENGINE_NO_FRONT1024 1 /* 1024-point short-window configurations stay on the generic long-transform kernel  */
@@ -113,6 +122,9 @@ enum { MFX_METHOD_MFCC = 0, MFX_METHOD_PLP = 1 };
                                            are wanted (else: column groups x band parts, summed across the wave)          */
 #define MFX_ENGINE_NO_STUFF256 128      /* 256-point transforms stay on the one-wave-per-frame kernel instead of the zero-stuffed
                                            form of the 512-point kernel                                                   */
+
+#define MFX_ENGINE_TRAPS_VALU 512        /* TRAPS: the trajectory DCT on the vector ALUs instead of the matrix pipe (the same
+                                           ascending float32 FMA chain per output: the same bits)                        */
 
 #define MFX_ENGINE_FRONT1024_12_WAVES 256 /* 1024-point fused kernel: the 12-waves-per-CU build also where the 16-wave build fits
                                             (aligned frames, window <= 512 samples, tables small enough): the same bits      */
@@ -256,6 +268,9 @@ int64_t mfx_host_dct_mfma_operands(int32_t num_banks, int32_t dct_len, const flo
  * fft_size; it is taken for symmetry with mfx_host_mel_table */
 int mfx_host_plp_tables(int32_t num_banks, int32_t fft_size, float sample_rate, float low_freq, float high_freq, float alpha,
                         int32_t lpc_order, float *eql, float *idft);
+/* TRAPS basis as uploaded (TRAPS): basis [traps_dct_len][traps_len], Hamming window times the DCT-II in the
+ * reference's DCT convention, evaluated in double and rounded once.  Lengths as given (no 0 = default here). */
+int mfx_host_traps_basis(int32_t traps_len, int32_t traps_dct_len, float *basis);
 /* frame count, integer arithmetic (parambase.cpp:16-19 without the float32 division) */
 int64_t mfx_host_frame_count(int64_t samples, int32_t window_size, int32_t shift);
 
