@@ -441,6 +441,14 @@ int create_impl(const mfx_config *cfg, int hip_device, bool planning, mfx_handle
     h->cols = traps ? h->nb * traps_K : h->fcols;
     h->width = h->cols * (cfg->dyn == MFX_DYN_ACC ? 3 : cfg->dyn == MFX_DYN_DELTA ? 2 : 1);
     h->channels = cfg->channels == 2 ? 2 : 1;
+    if (h->l1 > 0) {
+        // the delta stage's LDS holds (R + 2 D) + (R + 2 l2) + R rows (launch_delta: R = 64 rows of 16 floats up to 16 columns,
+        // else 32 rows of `cols` floats): an order beyond it is refused here, not by a failed launch.  At 256 columns the
+        // limit is l1 = l2 = 10.
+        const int64_t R = h->cols <= 16 ? 64 : 32, cw = h->cols <= 16 ? 16 : h->cols;
+        const int64_t rows = 3 * R + 2 * ((int64_t)h->l1 + h->l2) + 2 * (int64_t)h->l2;
+        if (rows * cw * (int64_t)sizeof(float) > (int64_t)kLdsCap) return MFX_ERR_CONFIG;
+    }
     h->W2 = (int)ceil_pow2((uint32_t)h->W);
     if (cfg->fft_size != 0) {
         if (cfg->fft_size < h->W || (cfg->fft_size & (cfg->fft_size - 1)) != 0) return MFX_ERR_CONFIG;
@@ -528,9 +536,6 @@ int create_impl(const mfx_config *cfg, int hip_device, bool planning, mfx_handle
         else
             build_traps_mfma_operands(basis, h->traps_L, h->traps_K, a, b, ob);
         DEV_OK(h->upload(h->d_traps_b, ob));
-        // the delta stage's LDS holds (R + 2 D) + (R + 2 l2) + R rows of `cols` floats, R = 32 for wide rows: at 256 columns
-        // that is the binding limit only beyond l1 = l2 = 10 (the normaliser's 256 columns bind first, checked above)
-        if ((size_t)(3 * 32 + 2 * h->D + 2 * h->l2) * h->cols * sizeof(float) > kLdsCap) return MFX_ERR_CONFIG;
         TrapsParams tp;
         fill_traps(h, tp);
         if (traps_tile_rows(tp) == 0) return MFX_ERR_CONFIG;

@@ -63,8 +63,9 @@ typedef struct mfx_config {
     float lift_coef;
     int32_t norm;              /* MFX_NORM_*                                                         */
     int32_t dyn;               /* MFX_DYN_*                                                          */
-    int32_t delta_l1;
-    int32_t delta_l2;
+    int32_t delta_l1;          /* regression orders; (3 R + 2 (l1 + l2) + 2 l2) rows of the delta stage must fit  */
+    int32_t delta_l2;          /* 160 KB of LDS (R = 64 rows of 16 floats up to 16 columns, else 32 rows of the
+                                  column count: l1 = l2 <= 10 at 256 columns), else MFX_ERR_CONFIG      */
     int32_t norm_after_dyn;
     /* ---- extensions ---- */
     int32_t fft_size;          /* 0 = ceil2(window_size) as the reference (mfcccpu.cpp:94); else a

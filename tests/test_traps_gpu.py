@@ -6,6 +6,10 @@ delta-delta groups are checked one group at a time at the same two figures with 
 delta of a TRAPS row is a small difference of large, slowly varying numbers (scale ~0.2 against statics of ~19), the
 regression moves an error of the statics by at most sum(2 l) / (2 sum(l^2)) = 0.43 at l = 3, so the bar on the statics
 implies 1e-4 max|statics| on the deltas, not 1e-4 max|delta|; a wrong clamp or tap still shows at ~1e-2 of that scale.
+
+That bar alone lets a delta column be wrong by 1 % of its own range.  check() therefore also holds every delta and
+delta-delta value against the float64 restatement of the rows' OWN statics within float32 rounding bounds
+(tail_ref.assert_tail_consistent: about 1e-7 relative, no oracle noise in it).
 """
 import ctypes as C
 import os
@@ -16,6 +20,7 @@ import numpy as np
 import pytest
 
 import plp_ref
+import tail_ref
 import traps_ref
 from conftest import GOLDEN, assert_close, assert_normalised_close, synth_utterance  # noqa: F401
 
@@ -45,14 +50,19 @@ def run_batch(m, utts):
     return [out[rows[i]:rows[i] + m.batch_frames(lens[i])] for i in range(len(utts))]
 
 
-def check(got, want, dyn, what, floor=0.0, worst=None):
-    """Statics at the bar; every delta group at the bar with the statics' scale as the floor (module docstring)."""
+def check(got, want, dyn, what, floor=0.0, worst=None, l1=3, l2=3, tail=True):
+    """Statics at the bar; every delta group at the bar with the statics' scale as the floor (module docstring); and the
+    delta groups of `got` against its own statics.  tail=False only for rows that are not [static | d | dd] in float32:
+    rows normalised AFTER the deltas (every group has its own mean and multiplier) and rows read back from decimal text."""
     got, want = np.asarray(got), np.asarray(want)
     assert got.shape == want.shape, "%s: shape %s vs %s" % (what, got.shape, want.shape)
     if want.shape[0] == 0:
         return
     g = 1 + dyn
     c = want.shape[1] // g
+    if dyn > 0 and tail:
+        w = tail_ref.assert_tail_consistent(got, c, dyn, l1, l2 if dyn == 2 else 0, what)
+        print("%s: deltas against their own statics, worst err / bound %s" % (what, w))
     s_scale = float(np.abs(want[:, :c]).max())
     for i in range(g):
         a, b = got[:, i * c:(i + 1) * c], want[:, i * c:(i + 1) * c]
@@ -92,6 +102,27 @@ def test_ragged_batch_against_oracle(pkg, ragged):
         if i < len(RAGGED_FRAMES):
             assert want.shape[0] == RAGGED_FRAMES[i]
         check(g, want, 0, "utt %d (%d frames)" % (i, want.shape[0]))
+
+
+@pytest.fixture(scope="module")
+def ragged_dyn2(pkg, ragged):
+    """The same batch with deltas on: the 1-, 2-, 15- and 16-frame utterances through the delta stage."""
+    m = make(pkg, dyn=2)
+    got = run_batch(m, ragged[0])
+    m.close()
+    return got
+
+
+def test_ragged_batch_with_deltas(pkg, ragged, ragged_dyn2):
+    utts, statics = ragged
+    for i, (u, g, s) in enumerate(zip(utts, ragged_dyn2, statics)):
+        assert g.shape == (s.shape[0], 450)
+        assert np.array_equal(g[:, :150], s), "utt %d: statics differ from the dyn = NONE handle's" % i
+        if i < len(RAGGED_FRAMES):
+            check(g, oracle(pkg, u), 2, "dyn 2, utt %d (%d frames)" % (i, RAGGED_FRAMES[i]))
+        elif g.shape[0]:   # (the long utterance's oracle is computed once, for the dyn = NONE rows)
+            w = tail_ref.assert_tail_consistent(g, 150, 2, 3, 3, "dyn 2, utt %d" % i)
+            print("dyn 2, utt %d (%d frames): worst err / bound %s" % (i, g.shape[0], w))
 
 
 def test_ragged_batch_rows_do_not_depend_on_the_batch(pkg, ragged):
@@ -264,7 +295,7 @@ def test_batch_norm(pkg, norm_utts, norm_twins, kind, nad, bns):
             np.testing.assert_allclose(st[:, u, 0].reshape(-1), mean, rtol=1e-4, atol=1e-4 * np.abs(x).max())
             np.testing.assert_allclose(st[:, u, 1].reshape(-1), mult, rtol=1e-3)
         want = restate_block(x, st[:, u], kind, nad, cols)
-        check(y, want, 2, "norm %d nad %d bns %d utt %d" % (kind, nad, bns, u))
+        check(y, want, 2, "norm %d nad %d bns %d utt %d" % (kind, nad, bns, u), tail=not nad)
     m.close()
 
 
@@ -407,7 +438,7 @@ def test_driver(pkg, orc, tmp_path):
     pcm = pcm[:, 0].copy()
     want = oracle(pkg, pcm, W=int(sr * 25e-3), S=int(sr * 10e-3), sr=float(sr))
     assert rows.shape == (want.shape[0], 1 + 450)
-    check(rows[:, 1:], want, 2, "afet_hip --method TRAPS (text)")
+    check(rows[:, 1:], want, 2, "afet_hip --method TRAPS (text)", tail=False)   # (six decimals, not float32)
     raw = open(h, "rb").read()
     n, period, size, kind = struct.unpack(">iihh", raw[:12])
     assert (n, period, size) == (want.shape[0], 100000, 4 * 450)
