@@ -329,6 +329,30 @@ int launch_cepstra(mfx_handle *h, const CepTables &t, const float *spec, int64_t
     return MFX_OK;
 }
 
+int launch_cepstra_runs(mfx_handle *h, const CepTables &t, const float *spec, float *feat, int feat_pitch, const RowRuns &rr,
+                        const int32_t *h_off, const int64_t *h_runs, hipStream_t stream)
+{
+    const int n_tables = (int)t.alphas.size();
+    if (h->plp) {
+        PlpParams pp;
+        fill_plp(h, t, pp);
+        pp.spec = spec;
+        pp.feat = feat;
+        pp.feat_pitch = feat_pitch;
+        pp.n_tables = n_tables;
+        HIP_TRY(h, launch_plp_runs(pp, rr, h_off, h_runs, stream));
+    } else {
+        MelcepParams mp;
+        fill_melcep(h, t, mp);
+        mp.spec = spec;
+        mp.feat = feat;
+        mp.feat_pitch = feat_pitch;
+        mp.n_tables = n_tables;
+        HIP_TRY(h, launch_melcep_runs(mp, rr, h_off, h_runs, stream));
+    }
+    return MFX_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // lifetime
 // ------------------------------------------------------------------------------------------------
@@ -688,10 +712,18 @@ FrontKind choose_front(const mfx_handle *h)
     return h->fast512 ? kSpec512 : kSpecGen;
 }
 
+// With per-utterance warp factors in force (mfx_batch_set_alphas) the fused front ends, which know one filterbank, are
+// out: the spectrum goes through the slab and k_melcep_runs / k_plp_runs apply each table to its own rows.
+FrontKind batch_front(const mfx_handle *h)
+{
+    if (h->batch.alphas_on) return h->fast512 ? kSpec512 : kSpecGen;
+    return choose_front(h);
+}
+
 extern "C" const char *mfx_dominant_kernel_name(const mfx_handle *h)
 {
     if (!h) return "";
-    switch (choose_front(h)) { // names as rocprofv3 prints them
+    switch (batch_front(h)) { // names as rocprofv3 prints them
     case kFront512:
     case kSpec512: return "k_front512";
     case kFront1024: return "k_front1024";
@@ -897,6 +929,21 @@ extern "C" int mfx_host_dct_matrix(int32_t num_banks, int32_t ceps_len, int32_t 
     build_dct_matrix(num_banks, ceps_len, want_c0 != 0, lift_coef, m);
     std::memcpy(matrix, m.data(), sizeof(float) * m.size());
     return MFX_OK;
+}
+
+extern "C" int64_t mfx_host_alpha_runs(int32_t n_utt, const float *alphas, const int64_t *frames, int64_t win_row0, int64_t win_rows,
+                                       float *tables, int32_t *off, int64_t *runs)
+{
+    if (n_utt < 0 || (n_utt > 0 && (!alphas || !frames))) return MFX_ERR_ARG;
+    std::vector<float> t;
+    std::vector<int32_t> o;
+    std::vector<int64_t> r;
+    build_alpha_runs(alphas, frames, n_utt, t, o, r);
+    if (win_rows >= 0) clip_alpha_runs(win_row0, win_rows, o, r);
+    if (tables) std::copy(t.begin(), t.end(), tables);
+    if (off) std::copy(o.begin(), o.end(), off);
+    if (runs) std::copy(r.begin(), r.end(), runs);
+    return (int64_t)t.size();
 }
 
 extern "C" int64_t mfx_host_frame_count(int64_t samples, int32_t window_size, int32_t shift)

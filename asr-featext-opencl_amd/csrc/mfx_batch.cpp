@@ -194,6 +194,7 @@ extern "C" int mfx_batch_plan(mfx_handle *h, int32_t n_utt, const int64_t *offse
     if (n_utt < 0 || (n_utt > 0 && (!offsets || !lengths))) return fail(h, MFX_ERR_ARG, "invalid argument");
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->batch.alphas_on = false; // (a warp-factor list is tied to the plan's utterance order)
     h->batch.n_utt = n_utt;
     h->batch.utt_off.assign(offsets, offsets + n_utt);
     h->batch.utt_len.assign(lengths, lengths + n_utt);
@@ -299,6 +300,45 @@ extern "C" int mfx_batch_plan(mfx_handle *h, int32_t n_utt, const int64_t *offse
     return size_static16(h);
 }
 
+// rows of the spectrum slab of the batch entries' spectrum path
+static constexpr int64_t kSlabRowsMax = 1 << 17;
+
+extern "C" int mfx_batch_set_alphas(mfx_handle *h, const float *alphas, int32_t n_utt)
+{
+    MFX_DEVICE_ENTRY(h);
+    if (!alphas && n_utt == 0) { // back to mfx_set_alpha's factor and choose_front's kernels
+        h->batch.alphas_on = false;
+        return MFX_OK;
+    }
+    if (!alphas || n_utt != h->batch.n_utt) return fail(h, MFX_ERR_ARG, "one warp factor per planned utterance");
+    for (int u = 0; u < n_utt; ++u)
+        if (!(alphas[u] > 0.f)) return fail(h, MFX_ERR_ARG, "alpha must be positive");
+    std::vector<int64_t> frames((size_t)n_utt);
+    for (int u = 0; u < n_utt; ++u) frames[u] = std::max<int64_t>(frame_count(h->batch.utt_len[u], h->W, h->S), 0);
+    std::vector<float> tables;
+    std::vector<int32_t> off;
+    std::vector<int64_t> runs;
+    build_alpha_runs(alphas, frames.data(), n_utt, tables, off, runs);
+    if (tables.size() > 4096) return fail(h, MFX_ERR_ARG, "more than 4096 distinct warp factors");
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = mfx_synchronize(h); // (a run in flight may read the tables and lists replaced below)
+    if (rc != MFX_OK) return rc;
+    h->batch.alphas_on = false;
+    if (tables.empty()) return MFX_OK; // (a plan without utterances)
+    rc = build_cep_tables(h, tables.data(), (int)tables.size(), h->batch.alpha_tables);
+    if (rc != MFX_OK) return rc;
+    if (runs.empty()) runs.assign(2, 0); // (no utterance has a frame: nothing will run; keep the buffers non-null)
+    HIP_TRY(h, h->upload(h->batch.d_run_off, off));
+    HIP_TRY(h, h->upload(h->batch.d_runs, runs));
+    h->batch.h_run_off.swap(off);
+    h->batch.h_runs.swap(runs);
+    // (everything mfx_batch_run_device needs is allocated here: that entry never allocates)
+    const size_t slab = (size_t)std::min<int64_t>(h->batch.total_rows, kSlabRowsMax) * h->spec_pitch;
+    if (h->batch.d_spec_slab.n < slab) HIP_TRY(h, h->batch.d_spec_slab.alloc(slab));
+    h->batch.alphas_on = true;
+    return MFX_OK;
+}
+
 namespace {
 // utterances [u0, u1) of the planned batch (all of them: the fused-delta and overlap modes apply)
 int batch_run_range(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_total, float *d_out, int u0, int u1);
@@ -342,7 +382,8 @@ int batch_run_range(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_tot
 
     // Which front end: the 512-point register kernel, else the fused wave-per-frame kernel when its
     // LDS fits, else spectrum through an HBM slab + melcep.
-    const FrontKind kind = choose_front(h);
+    // (per-utterance warp factors in force: always the slab)
+    const FrontKind kind = batch_front(h);
     const bool fused512 = kind == kFront512, fused1024 = kind == kFront1024, fused2048 = kind == kFront2048,
                fusedgen = kind == kFrontGenFused;
     // With deltas on, the front end writes its statics as compact 64-byte rows into a scratch buffer
@@ -401,8 +442,7 @@ int batch_run_range(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_tot
         HIP_TRY(h, launch_front_generic(p, /*fused=*/true, h->stream));
     } else {
         // magnitudes go through an HBM slab, then melcep
-        const int64_t slab_rows_max = 1 << 17;
-        const int64_t slab_rows = std::min<int64_t>(h->batch.total_rows, slab_rows_max);
+        const int64_t slab_rows = std::min<int64_t>(h->batch.total_rows, kSlabRowsMax);
         if (h->batch.d_spec_slab.n < (size_t)slab_rows * h->spec_pitch)
             HIP_TRY(h, h->batch.d_spec_slab.alloc((size_t)slab_rows * h->spec_pitch));
         size_t c0 = (size_t)rc0;
@@ -427,8 +467,18 @@ int batch_run_range(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_tot
                 else
                     HIP_TRY(h, launch_front_generic(q, /*fused=*/false, h->stream));
             }
-            rc = launch_cepstra(h, h->own, h->batch.d_spec_slab.p, rows, p.feat + row0 * (int64_t)p.feat_pitch, p.feat_pitch, 1, 0, nullptr,
-                                h->stream);
+            if (h->batch.alphas_on) { // every table on its own rows of the slab, one launch
+                RowRuns rr;
+                rr.runs = h->batch.d_runs.p;
+                rr.off = h->batch.d_run_off.p;
+                rr.row0 = row0;
+                rr.rows = rows;
+                rc = launch_cepstra_runs(h, h->batch.alpha_tables, q.spec, p.feat, p.feat_pitch, rr, h->batch.h_run_off.data(),
+                                         h->batch.h_runs.data(), h->stream);
+            } else {
+                rc = launch_cepstra(h, h->own, h->batch.d_spec_slab.p, rows, p.feat + row0 * (int64_t)p.feat_pitch, p.feat_pitch, 1, 0,
+                                    nullptr, h->stream);
+            }
             if (rc != MFX_OK) return rc;
             c0 = c1;
         }

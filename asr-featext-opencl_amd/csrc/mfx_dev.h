@@ -5,6 +5,8 @@
 
 #include <cstdint>
 
+#include "mfx_kernels.h"
+
 namespace mfx {
 namespace {
 
@@ -323,6 +325,67 @@ __device__ __forceinline__ void dct4_store(const float *lm, int FS, __amdgpu_buf
             for (int cc = lane; cc < cols; cc += 64) (feat + (out_row0 + g) * feat_pitch)[cc] = lm[g * FS + cc];
     }
 }
+
+// ---- row-run forms of k_melcep / k_plp (RowRuns, mfx_kernels.h)
+// The runs [run0, run1) of `table` that reach into the window (a table's runs ascend and are disjoint: those are
+// consecutive); false when there is none.  Uniform over the block.
+__device__ __forceinline__ bool runs_in_window(const RowRuns &rr, int table, int &run0, int &run1)
+{
+    const int64_t w0 = rr.row0, w1 = rr.row0 + rr.rows;
+    int lo = rr.off[table], hi = rr.off[table + 1];
+    run1 = hi;
+    while (lo < hi) { // first run that ends behind w0
+        const int mid = (lo + hi) >> 1;
+        if (rr.runs[2 * mid] + rr.runs[2 * mid + 1] > w0) hi = mid; else lo = mid + 1;
+    }
+    run0 = lo;
+    return run0 < run1 && rr.runs[2 * run0] < w1;
+}
+
+// Groups of G rows of the clipped runs [run0, run1), numbered through in run order: this wave takes the groups `first`,
+// `first + stride`, ...; while valid(), rows row0 .. row0 + count - 1 (count <= G) are its current group.  A group lies
+// inside one run.
+template <int G>
+struct RunGroups {
+    const RowRuns &rr;
+    int r, run1;            // current run (run1: no group left)
+    int64_t idx, stride;    // index of the wave's current group among the table's groups in the window
+    int64_t base = 0;       // groups of the runs before r
+    int64_t lo = 0, hi = 0; // run r, clipped to the window
+    int64_t row0 = 0;
+    int count = 0;
+    __device__ __forceinline__ RunGroups(const RowRuns &runs, int run0, int run1_, int64_t first, int64_t stride_)
+        : rr(runs), r(run0 - 1), run1(run1_), idx(first), stride(stride_)
+    {
+        seek();
+    }
+    __device__ __forceinline__ bool valid() const { return r < run1; }
+    __device__ __forceinline__ void advance()
+    {
+        idx += stride;
+        seek();
+    }
+    // the run that holds group idx, and the group's rows
+    __device__ __forceinline__ void seek()
+    {
+        const int64_t w0 = rr.row0, w1 = rr.row0 + rr.rows;
+        while (idx >= base + (hi - lo + G - 1) / G) {
+            base += (hi - lo + G - 1) / G;
+            lo = hi = 0;
+            if (++r >= run1) return;
+            const int64_t a = rr.runs[2 * r], b = a + rr.runs[2 * r + 1];
+            if (a >= w1) { // (runs ascend: none of the later ones reaches into the window)
+                r = run1;
+                return;
+            }
+            lo = a > w0 ? a : w0;
+            hi = b < w1 ? b : w1;
+            if (hi < lo) hi = lo;
+        }
+        row0 = lo + (idx - base) * G;
+        count = (int)(hi - row0 < G ? hi - row0 : G);
+    }
+};
 
 } // namespace
 } // namespace mfx

@@ -163,6 +163,14 @@ struct BatchState {
     unsigned seq = 0;
     int tiles_max = 0;
     bool aligned = true;                 // frames on aligned sample pairs (fill_front / choose_front read it)
+    // per-utterance warp factors (mfx_batch_set_alphas), tied to the plan: one table per distinct factor and, per table,
+    // the row runs of its utterances (build_alpha_runs); the batch then runs spectrum slab + k_melcep_runs / k_plp_runs
+    bool alphas_on = false;              // (batch_front reads it)
+    CepTables alpha_tables;
+    std::vector<int32_t> h_run_off;      // [tables + 1]
+    std::vector<int64_t> h_runs;         // [runs][2]
+    DevBuf<int32_t> d_run_off;
+    DevBuf<int64_t> d_runs;
 };
 
 // fused delta stage of the 512-point kernel: per-block chunk lists (own rows + halo) and delta tiles: mfx_batch.cpp
@@ -327,6 +335,8 @@ inline int fail_hip(mfx_handle *h, hipError_t e, const char *what)
 // Which front-end kernel the BATCH entries run for this handle (see choose_front's definition)
 enum FrontKind { kFront512, kFront1024, kFront2048, kFrontGenFused, kSpec512, kSpecGen };
 FrontKind choose_front(const mfx_handle *h);
+// what batch_run_range launches: choose_front's kernel, or the spectrum form while per-utterance warp factors are in force
+FrontKind batch_front(const mfx_handle *h);
 void fill_front(const mfx_handle *h, mfx::FrontParams &p);
 void fill_traps(const mfx_handle *h, mfx::TrapsParams &p);
 int refresh_mel(mfx_handle *h);
@@ -334,6 +344,9 @@ int build_cep_tables(mfx_handle *h, const float *alphas, int n, CepTables &t, mf
                      mfx::MelWavePlan *first_plan = nullptr);
 int launch_cepstra(mfx_handle *h, const CepTables &t, const float *spec, int64_t n_rows, float *feat, int feat_pitch,
                    int n_tables, int64_t feat_table_stride, float *r_out, hipStream_t stream);
+// the row-run form: the runs of `rr` (host copies h_off / h_runs) of each of t's tables, absolute rows of spec and feat
+int launch_cepstra_runs(mfx_handle *h, const CepTables &t, const float *spec, float *feat, int feat_pitch, const mfx::RowRuns &rr,
+                        const int32_t *h_off, const int64_t *h_runs, hipStream_t stream);
 int run_norm(mfx_handle *h, hipStream_t stream, float *data, int pitch, const mfx::Segment *segs, int n_segs, const mfx::Segment *seg0,
              float *stats, bool use_last, int max_rows, int groups = 1, size_t group_stats_stride = 0);
 // ---- mfx_stream.cpp, for mfx_batch.cpp

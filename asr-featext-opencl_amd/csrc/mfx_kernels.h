@@ -180,6 +180,17 @@ struct PlpParams {
 };
 constexpr int kPlpMaxOrder = 32;
 
+// Row-run form of k_melcep / k_plp (k_melcep_runs / k_plp_runs: per-utterance warp factors of the batch entries,
+// DESIGN.md, "Per-utterance warp factors").  Table a = blockIdx.y serves the runs [off[a], off[a + 1]) of `runs`; a run is
+// (first row, row count) in absolute rows, ascending and disjoint within a table, and is clipped to the window
+// [row0, row0 + rows) by the kernel.  spec and feat of the accompanying parameters address ABSOLUTE rows (there is one
+// output: n_rows and feat_table_stride are not used, PlpParams::r_out must be null).
+struct RowRuns {
+    const int64_t *runs;  // [n_runs][2]: first row, rows
+    const int32_t *off;   // [n_tables + 1]
+    int64_t row0, rows;   // the window: rows of the spectrum slab
+};
+
 // k_traps (mfx_traps.hip): log mel rows -> per band the Hamming-windowed DCT-II of the L frames around every frame
 // (TRAPS).  One Segment per utterance: rows src_row0 + clamp(t - (L - 1) / 2 + j, lo, hi) are read, rows
 // out_row0 + t, t < n_out, written (shift / static_off / pad are not used).  Statics land at columns m * K + k.
@@ -240,6 +251,9 @@ size_t front512_delta_lds_bytes(const FrontParams &p);
 hipError_t launch_front_generic(const FrontParams &p, bool fused, hipStream_t stream);
 size_t front_wave_lds_bytes(const FrontParams &p, bool fused);
 hipError_t launch_melcep(const MelcepParams &p, hipStream_t stream);
+// the row-run forms: h_off / h_runs are the host's copies of rr.off / rr.runs (they size the grid; nothing is allocated)
+hipError_t launch_melcep_runs(const MelcepParams &p, const RowRuns &rr, const int32_t *h_off, const int64_t *h_runs, hipStream_t stream);
+hipError_t launch_plp_runs(const PlpParams &p, const RowRuns &rr, const int32_t *h_off, const int64_t *h_runs, hipStream_t stream);
 hipError_t launch_delta(const DeltaParams &p, hipStream_t stream);
 hipError_t launch_plp(const PlpParams &p, hipStream_t stream);
 hipError_t launch_traps(const TrapsParams &p, hipStream_t stream);

@@ -4,7 +4,9 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <functional>
+#include <unordered_map>
 #include <vector>
 
 namespace mfx {
@@ -157,6 +159,63 @@ void build_dct_matrix(int num_banks, int ceps_len, bool want_c0, float lift_coef
         }
         if (want_c0) row[ceps_len] = norm;
     }
+}
+
+void build_alpha_runs(const float *alphas, const int64_t *frames, int n_utt, std::vector<float> &tables, std::vector<int32_t> &off,
+                      std::vector<int64_t> &runs)
+{
+    tables.clear();
+    std::unordered_map<uint32_t, int32_t> table_of; // by bit pattern
+    std::vector<int32_t> tab((size_t)std::max(n_utt, 0));
+    for (int u = 0; u < n_utt; ++u) {
+        uint32_t bits;
+        std::memcpy(&bits, &alphas[u], sizeof(bits));
+        const auto it = table_of.emplace(bits, (int32_t)tables.size());
+        if (it.second) tables.push_back(alphas[u]);
+        tab[u] = it.first->second;
+    }
+    // per table its runs in utterance (= row) order; a run grows while the table's next utterance starts where it ends
+    std::vector<std::vector<int64_t>> per(tables.size());
+    int64_t row = 0;
+    for (int u = 0; u < n_utt; ++u) {
+        const int64_t T = frames[u] > 0 ? frames[u] : 0;
+        std::vector<int64_t> &r = per[tab[u]];
+        if (T > 0) {
+            if (!r.empty() && r[r.size() - 2] + r.back() == row) {
+                r.back() += T;
+            } else {
+                r.push_back(row);
+                r.push_back(T);
+            }
+        }
+        row += T;
+    }
+    off.assign(tables.size() + 1, 0);
+    runs.clear();
+    for (size_t a = 0; a < per.size(); ++a) {
+        runs.insert(runs.end(), per[a].begin(), per[a].end());
+        off[a + 1] = (int32_t)(runs.size() / 2);
+    }
+}
+
+void clip_alpha_runs(int64_t row0, int64_t rows, std::vector<int32_t> &off, std::vector<int64_t> &runs)
+{
+    const int64_t w0 = row0, w1 = row0 + rows;
+    std::vector<int64_t> kept;
+    int32_t r = 0;
+    for (size_t a = 0; a + 1 < off.size(); ++a) {
+        const int32_t end = off[a + 1];
+        off[a] = (int32_t)(kept.size() / 2);
+        for (; r < end; ++r) {
+            const int64_t lo = std::max(runs[2 * (size_t)r], w0), hi = std::min(runs[2 * (size_t)r] + runs[2 * (size_t)r + 1], w1);
+            if (hi > lo) {
+                kept.push_back(lo);
+                kept.push_back(hi - lo);
+            }
+        }
+    }
+    if (!off.empty()) off.back() = (int32_t)(kept.size() / 2);
+    runs.swap(kept);
 }
 
 void build_twiddles(int n, int count, std::vector<float> &t)

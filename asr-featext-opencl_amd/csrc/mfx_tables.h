@@ -57,6 +57,17 @@ void build_traps_mfma_operands(const std::vector<float> &basis, int traps_len, i
 // k_traps on the vector ALUs: the basis transposed, [L][kp], kp = K padded to 4, 16 or 32 accumulators (zero beyond K)
 void build_traps_valu_operands(const std::vector<float> &basis, int traps_len, int traps_dct_len, int &kp, std::vector<float> &out);
 
+// Per-utterance warp factors of a planned batch (mfx_batch_set_alphas) -> what the row-run kernels read.  Utterance u holds
+// the rows [sum of frames[0 .. u), + frames[u]).
+//   tables: the distinct factors, compared bit for bit, in order of first appearance
+//   off   : [tables + 1] table a owns runs [off[a], off[a + 1])
+//   runs  : [n][2] (first row, rows); a table's runs ascend; utterances without frames leave none, neighbours (with nothing
+//           but frameless utterances between them) of the same factor are one run
+void build_alpha_runs(const float *alphas, const int64_t *frames, int n_utt, std::vector<float> &tables, std::vector<int32_t> &off,
+                      std::vector<int64_t> &runs);
+// the same lists with every run clipped to the rows [row0, row0 + rows), as the kernels clip them; empty runs dropped
+void clip_alpha_runs(int64_t row0, int64_t rows, std::vector<int32_t> &off, std::vector<int64_t> &runs);
+
 // exp(-2*pi*i*k/n) for k in [0, count), evaluated in double and rounded once to float.
 void build_twiddles(int n, int count, std::vector<float> &re_im_interleaved);
 

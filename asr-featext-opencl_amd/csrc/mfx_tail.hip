@@ -27,57 +27,14 @@ namespace {
 // wave's 64 lanes (MelWavePlan: whole filters in ascending bin order, mfcccpu.cpp:206-217), the log energies wait in
 // lm[4][FS], and the DCT of the four rows runs on the matrix pipe (dct_mfma4) -- the same mel stage as the fused batch
 // kernels (round 3: the round-1 piece plan and its vector-pipe DCT are gone).  blockIdx.y = filterbank of a VTLN sweep.
+// The kernel's text is mfx_melcep_body.h: compiled here as k_melcep and as its row-run form k_melcep_runs.
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_melcep(MelcepParams p)
-{
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, n_waves = blockDim.x >> 6;
-    const int nb = p.num_banks, RS = p.mel64_row_stride, rounds = p.mel64_rounds;
-    const int FS = lm_fs4(nb), MF = p.mag_floats;
-    const int WR = mel64_rows(nb);                   // weight rows in LDS (lanes that carry a filter)
-    float *s_mw = smem;                              // [WR][RS]
-    int *s_mst = (int *)(s_mw + WR * RS);            // [rounds][64]
-    int *s_mfid = s_mst + 64 * rounds;               // [rounds][64]
-    int *s_L = s_mfid + 64 * rounds;                 // [8]
-    float *s_wave = (float *)(s_L + 8) + wave * (MF + 4 * FS);
-    float *mag = s_wave, *lm = s_wave + MF;
-
-    const int table = blockIdx.y;
-    const float *gw = p.mel64_w + (int64_t)table * 64 * RS;
-    const int32_t *gst = p.mel64_start + (int64_t)table * 64 * rounds, *gfid = p.mel64_fid + (int64_t)table * 64 * rounds;
-    float *feat = p.feat + (int64_t)table * p.feat_table_stride;
-    for (int i = tid; i < WR * RS; i += blockDim.x) s_mw[i] = gw[i];
-    for (int i = tid; i < 64 * rounds; i += blockDim.x) {
-        s_mst[i] = gst[i];
-        s_mfid[i] = gfid[i];
-    }
-    if (tid < 8) s_L[tid] = p.mel64_L[table * 8 + tid];
-    for (int i = lane; i < MF + 4 * FS; i += 64) s_wave[i] = 0.f; // words past the last bin stay zero (finite) for good
-    __syncthreads();
-
-    const int dct_ks = p.dct_ksteps, dct_tiles64 = (p.dct_len + 63) >> 6;
-    const int dct_bytes = p.dct_b4 ? dct_tiles64 * dct_ks * 1024 : 0;
-    const __amdgpu_buffer_rsrc_t dct_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)p.dct_b4, 0, dct_bytes, 0x00020000);
-    const int q4 = p.spec_pitch >> 2; // rows are whole 16-byte words (spec_pitch is a multiple of 4, rows 16-byte aligned)
-    const int nbins = (p.fft_size >> 1) + 1;
-    for (int64_t grp = (int64_t)blockIdx.x * n_waves + wave; grp * 4 < p.n_rows; grp += (int64_t)gridDim.x * n_waves) {
-        const int64_t row0 = grp * 4;
-        const int count = (int)(p.n_rows - row0 < 4 ? p.n_rows - row0 : 4);
-        for (int f = 0; f < count; ++f) {
-            const float4 *src = (const float4 *)(p.spec + (row0 + f) * p.spec_pitch);
-            for (int k = lane; k < q4; k += 64) ((float4 *)mag)[k] = src[k];
-            // the row's padding words (bins > W2/2) are never written in memory: they meet zero weights in the walk and
-            // must be finite (0 x NaN is NaN)
-            if (nbins + lane < 4 * q4) mag[nbins + lane] = 0.f;
-            wave_sync();
-            mel64_walk_log(mag, lm + f * FS, FS - 1, s_mw, s_mst, s_mfid, s_L, rounds, RS, lane, WR);
-            wave_sync();
-        }
-        dct4_store<3>(lm, FS, dct_rsrc, dct_bytes, dct_ks, dct_tiles64, p.dct_b4 != nullptr, lane, p.cols, feat, (int64_t)p.feat_pitch,
-                   row0, count);
-        wave_sync();
-    }
-}
+#define MFX_MELCEP_RUNS 0
+#include "mfx_melcep_body.h"
+#undef MFX_MELCEP_RUNS
+#define MFX_MELCEP_RUNS 1
+#include "mfx_melcep_body.h"
+#undef MFX_MELCEP_RUNS
 
 // ------------------------------------------------------------------------------------------------
 // delta: regression coefficients over time (deltacpu.cpp:16-29) with the edge handling of
@@ -641,6 +598,28 @@ hipError_t launch_melcep(const MelcepParams &p, hipStream_t stream)
     const int tables = p.n_tables > 1 ? p.n_tables : 1;
     if (tables > 65535) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_melcep, dim3((unsigned)blocks, (unsigned)tables), dim3(64 * nw), lds, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_melcep_runs(const MelcepParams &p, const RowRuns &rr, const int32_t *h_off, const int64_t *h_runs, hipStream_t stream)
+{
+    const int tables = p.n_tables > 1 ? p.n_tables : 1;
+    int active = 0;
+    const int64_t groups = run_groups_in_window(h_off, h_runs, tables, rr.row0, rr.rows, 4, active); // of the busiest table
+    if (groups <= 0) return hipSuccess;
+    if (p.mag_floats < p.spec_pitch || (p.spec_pitch & 3) || (p.mag_floats & 3)) return hipErrorInvalidValue;
+    int nw = 4; // (as launch_melcep)
+    while (nw > 1 && melcep_lds_bytes(p, nw) > 160 * 1024) nw >>= 1;
+    const size_t lds = melcep_lds_bytes(p, nw);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (hipError_t e = allow_dynamic_lds((const void *)k_melcep_runs, lds); e != hipSuccess) return e;
+    int per_cu = blocks_per_cu((const void *)k_melcep_runs, 64 * nw, lds, (int)std::min<size_t>(4, (160 * 1024) / lds));
+    if (per_cu > 8) per_cu = 8;
+    // the resident blocks are shared among the tables that have rows in this window (the others' blocks leave at once)
+    const int cap = (num_cus() * (per_cu < 1 ? 1 : per_cu) + active - 1) / active;
+    const int64_t blocks = std::min<int64_t>((groups + nw - 1) / nw, cap);
+    if (tables > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_melcep_runs, dim3((unsigned)blocks, (unsigned)tables), dim3(64 * nw), lds, stream, p, rr);
     return hipGetLastError();
 }
 

@@ -15,6 +15,8 @@
 // write the previous batch's rows.  The extractor is created with MFX_ENGINE_STREAM_KERNELS, so the rows are the same
 // bits the per-file loop delivers, and the reference's single-block flush behaviour (B1, --bug-compat) is applied to them:
 // the outputs are byte-identical to the per-file loop's (--batch-mb 0 selects that loop; tests compare the two).
+// --alpha-file gives every input file its own warp factor: the files of a batch then run with mfx_batch_set_alphas (one
+// launch sequence for all factors), files on the per-file loop with set_alpha of their own factor.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -42,6 +44,8 @@ struct Options {
     float low = 64.f, high = 0.f, lift = 22.f;
     bool c0 = true, norm_after_dyn = true;
     float alpha_min = 1.f, alpha_max = 1.f, alpha_step = 1.f;
+    std::string alpha_file;        // --alpha-file: one warp factor per line, in the order of the input list
+    std::vector<float> file_alpha; // its factors: file i of the list is extracted with file_alpha[i]
     int sample_limit = 10000000, device = 0;
     bool bug_compat = true;
     int method = MFX_METHOD_MFCC, model_order = 8; // --method MFCC|PLP|TRAPS, --model-order (ASR_OCL.cpp:54-56: default 8)
@@ -297,8 +301,9 @@ struct Scratch {
     std::vector<char> text;
 };
 
+// own_alpha: the file's factor of --alpha-file (one output, no name suffix) instead of the --alpha options' loop
 void process_file(MfccHip &param, const Options &o, const Wav &w, const std::string &in, const std::string &out_name,
-                  float sample_rate, Scratch &sc)
+                  float sample_rate, Scratch &sc, const float *own_alpha = nullptr)
 {
     if ((float)w.sample_rate != sample_rate)
         throw std::runtime_error("File \"" + in + "\" has incorrect sample rate");
@@ -328,9 +333,10 @@ void process_file(MfccHip &param, const Options &o, const Wav &w, const std::str
 
     std::vector<std::pair<float, FILE *>> outs;
     int idx = 0;
-    for (float a = o.alpha_min; a <= o.alpha_max; a = o.alpha_min + (++idx) * o.alpha_step) {
+    const float a_min = own_alpha ? *own_alpha : o.alpha_min, a_max = own_alpha ? *own_alpha : o.alpha_max;
+    for (float a = a_min; a <= a_max; a = a_min + (++idx) * o.alpha_step) {
         std::string name = out_name;
-        if (o.alpha_max - o.alpha_min >= o.alpha_step) name += "." + std::to_string(a);
+        if (a_max - a_min >= o.alpha_step) name += "." + std::to_string(a);
         FILE *fo = std::fopen(name.c_str(), o.htk ? "wb" : "w");
         if (!fo) throw std::runtime_error("Can't create output file: " + name);
         if (o.htk) write_htk_header(fo, 0, o, width); // frame count patched at the end
@@ -562,6 +568,7 @@ void worker(const Options &o, int device, float sr, const std::vector<std::strin
             for (long i = 0; i < W; ++i) // ASR_OCL.cpp:149-151
                 window[i] = (float)(0.56f - 0.46f * std::cos((2.0f * M_PI * i) / W)) / 32768.f;
             p->set_window(window.data());
+            p->set_warp(o.alpha_min); // (the batch entries have no apply() to carry it; the per-file loop sets its own)
             if (g_time.on) g_time.t_created = now_ns();
             return p;
         };
@@ -683,6 +690,11 @@ void worker(const Options &o, int device, float sr, const std::vector<std::strin
                     const long long td0 = g_time.on ? now_ns() : 0;
                     row0.resize(in_batch.size());
                     b.total_rows = param.batch_plan((int)in_batch.size(), off.data(), len.data(), row0.data());
+                    if (!o.file_alpha.empty()) { // --alpha-file: every file of the batch with its own factor, one run
+                        std::vector<float> al;
+                        for (const BatchItem *it : in_batch) al.push_back(o.file_alpha[it->file]);
+                        param.batch_set_alphas(al.data(), (int)al.size());
+                    }
                     float *rows = (float *)b.rows.get((size_t)std::max<long long>(b.total_rows, 1) * width * sizeof(float));
                     param.batch_run_host((const short *)b.pcm.p, b.samples, rows);
                     for (size_t k = 0; k < in_batch.size(); ++k) {
@@ -704,7 +716,8 @@ void worker(const Options &o, int device, float sr, const std::vector<std::strin
                 for (BatchItem &it : b.items)
                     if (it.error.empty() && it.stream) {
                         try {
-                            process_file(param, o, it.wav, files[2 * it.file], files[2 * it.file + 1], sr, sc);
+                            process_file(param, o, it.wav, files[2 * it.file], files[2 * it.file + 1], sr, sc,
+                                         o.file_alpha.empty() ? nullptr : &o.file_alpha[it.file]);
                         } catch (const std::exception &e) {
                             std::fprintf(stderr, "Exception caught %s\n", e.what());
                             ++failures;
@@ -736,7 +749,8 @@ void worker(const Options &o, int device, float sr, const std::vector<std::strin
                 const long long tw0 = g_time.on ? now_ns() : 0;
                 const Wav w = cur.wav.get();
                 if (g_time.on) g_time.wait_read += now_ns() - tw0;
-                process_file(param, o, w, files[2 * cur.i], files[2 * cur.i + 1], sr, sc);
+                process_file(param, o, w, files[2 * cur.i], files[2 * cur.i + 1], sr, sc,
+                             o.file_alpha.empty() ? nullptr : &o.file_alpha[cur.i]);
             } catch (const std::exception &e) { // a bad file does not stop the queue
                 std::fprintf(stderr, "Exception caught %s\n", e.what());
                 ++failures;
@@ -757,6 +771,7 @@ int main(int argc, char **argv)
     g_time.t_main = now_ns();
     Options o;
     std::vector<std::string> files;
+    bool alpha_options = false; // any of --alpha, --alpha-min, --alpha-max, --alpha-step
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto val = [&]() -> const char * {
@@ -766,6 +781,7 @@ int main(int argc, char **argv)
             }
             return argv[++i];
         };
+        if (a == "--alpha" || a == "--alpha-min" || a == "--alpha-max" || a == "--alpha-step") alpha_options = true;
         if (a == "--window-size") o.window_ms = (float)std::atof(val());
         else if (a == "--shift") o.shift_ms = (float)std::atof(val());
         else if (a == "--banks") o.banks = std::atoi(val());
@@ -783,6 +799,7 @@ int main(int argc, char **argv)
         else if (a == "--alpha-min") o.alpha_min = (float)std::atof(val());
         else if (a == "--alpha-max") o.alpha_max = (float)std::atof(val());
         else if (a == "--alpha-step") o.alpha_step = (float)std::atof(val());
+        else if (a == "--alpha-file") o.alpha_file = val();
         else if (a == "--sample-limit") o.sample_limit = std::atoi(val());
         else if (a == "--dev") o.device = std::atoi(val());
         else if (a == "--devs") { // comma separated device list; an id may repeat (two workers on one GPU)
@@ -841,11 +858,13 @@ int main(int argc, char **argv)
         else if (a == "--help") {
             std::printf("afet_hip [--window-size ms] [--shift ms] [--banks n] [--ceps n] [--c0 0|1] [--norm 0..3]\n"
                         "         [--dyn 0..2] [--l1 n] [--l2 n] [--low-freq hz] [--high-freq hz] [--lift-coef x]\n"
-                        "         [--norm-after-dyn 0|1] [--alpha a | --alpha-min a --alpha-max b --alpha-step s]\n"
+                        "         [--norm-after-dyn 0|1] [--alpha a | --alpha-min a --alpha-max b --alpha-step s | --alpha-file f]\n"
                         "         [--sample-limit n] [--dev n | --devs a,b,...] [--bug-compat 0|1] [--htk]  in.wav out.txt [...]\n"
                         "         [--method MFCC|PLP|TRAPS] [--model-order n (PLP model order, default 8)]\n"
                         "         [--traps-length n (TRAPS frames per trajectory, odd, default 31)] [--traps-dct n (default 10)]\n"
                         "         [--batch-mb n (PCM per batch of whole files; 0 = per-file loop)] [--io-threads n]\n"
+                        "  --alpha-file: one warp factor per line, in the order of the input files; files of a batch run with\n"
+                        "                their own factors in one launch sequence\n"
                         "  --devs: one worker per listed GPU, files dealt from a shared queue\n"
                         "  inputs: RIFF/WAVE or NIST SPHERE, 16-bit PCM; output: the reference's text rows, or HTK binary\n");
             return 0;
@@ -854,6 +873,34 @@ int main(int argc, char **argv)
     if (files.empty() || files.size() % 2) {
         std::fprintf(stderr, "usage: afet_hip [options] in.wav out.txt [in2.wav out2.txt ...]  (--help)\n");
         return 2;
+    }
+    if (!o.alpha_file.empty()) {
+        if (alpha_options) {
+            std::fprintf(stderr, "--alpha-file excludes --alpha and --alpha-min / --alpha-max / --alpha-step\n");
+            return 2;
+        }
+        FILE *fa = std::fopen(o.alpha_file.c_str(), "r");
+        if (!fa) {
+            std::fprintf(stderr, "can't read --alpha-file %s\n", o.alpha_file.c_str());
+            return 2;
+        }
+        char line[256];
+        while (std::fgets(line, sizeof(line), fa)) {
+            char *end = nullptr;
+            const float v = std::strtof(line, &end);
+            if (end == line) continue; // (blank line)
+            if (!(v > 0.f)) {
+                std::fprintf(stderr, "--alpha-file: warp factors must be positive\n");
+                std::fclose(fa);
+                return 2;
+            }
+            o.file_alpha.push_back(v);
+        }
+        std::fclose(fa);
+        if (o.file_alpha.size() != files.size() / 2) {
+            std::fprintf(stderr, "--alpha-file holds %zu warp factors for %zu input files\n", o.file_alpha.size(), files.size() / 2);
+            return 2;
+        }
     }
     if (o.method == MFX_METHOD_TRAPS) { // whole files through the batch entries: no per-file loop, no alpha loop, no DCT options
         if (o.batch_mb <= 0) {

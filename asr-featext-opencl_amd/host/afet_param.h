@@ -106,6 +106,11 @@ public:
     // offsets[u] + lengths[u]) of one PCM array, its rows start at out_rows[u]; returns the total number of rows
     long long batch_plan(int n_utt, const long long *offsets, const long long *lengths, long long *out_rows);
     void batch_run_host(const short *pcm, long long samples_total, float *out);
+    // one warp factor per utterance of the planned batch (mfx_batch_set_alphas); nullptr / 0 clears the list, and so does
+    // the next batch_plan
+    void batch_set_alphas(const float *alphas, int n_utt);
+    // mfx_set_alpha at once, for the batch entries (there is no apply() to carry m_alpha there)
+    void set_warp(float alpha);
     long long batch_frames(long long samples) const;
 
     // upper bound on the rows one set_input()/flush() can deliver (the reference's own bound,
@@ -139,7 +144,7 @@ public:
 // TRAPS temporal patterns (TRAPS) of the log mel energies: traps_dct_len DCT coefficients (0 = 10) of the
 // traps_len frames (0 = 31) around each frame, per band; num_banks * traps_dct_len statics per row.  BATCH ENTRIES ONLY
 // (batch_plan / batch_run_host): set_input, flush, apply and get_output_data throw "TRAPS handles have no streaming
-// entries".  set_alpha takes effect at once (there is no apply() to carry it).
+// entries".  The warp factor is set with MfccHip::set_warp (there is no apply() to carry set_alpha's).
 class TrapsHip : public MfccHip {
 public:
     TrapsHip(int input_buffer_size, int window_size, int shift, int num_banks, float sample_rate, float low_freq,
@@ -147,7 +152,6 @@ public:
              dyn_t dyn = DYN_NONE, int delta_l1 = 1, int delta_l2 = 1, bool norm_after_dyn = true, int hip_device = 0,
              int engine = 0);
     int get_output_data_width() const override; // num_banks * traps_dct_len * (1 + deltas): the library's own answer
-    void set_warp(float alpha);                 // mfx_set_alpha for the next batch run
 };
 
 #endif // AFET_PARAM_H

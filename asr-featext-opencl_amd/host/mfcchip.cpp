@@ -77,11 +77,6 @@ TrapsHip::TrapsHip(int input_buffer_size, int window_size, int shift, int num_ba
 
 int TrapsHip::get_output_data_width() const { return mfx_get_output_data_width(handle()); }
 
-void TrapsHip::set_warp(float alpha)
-{
-    m_alpha = alpha;
-    if (mfx_set_alpha(handle(), alpha) != MFX_OK) throw std::runtime_error("TrapsHip: set_alpha failed");
-}
 
 MfccHip::MfccHip(int input_buffer_size, int window_size, int shift, int num_banks, float sample_rate, float low_freq,
                  float high_freq, int ceps_len, bool want_c0, float lift_coef, Normalizer::norm_t norm, dyn_t dyn,
@@ -182,6 +177,14 @@ long long MfccHip::batch_plan(int n_utt, const long long *offsets, const long lo
 void MfccHip::batch_run_host(const short *pcm, long long samples_total, float *out)
 {
     check(mfx_batch_run_host(m_handle, pcm, (int64_t)samples_total, out));
+}
+
+void MfccHip::batch_set_alphas(const float *alphas, int n_utt) { check(mfx_batch_set_alphas(m_handle, alphas, n_utt)); }
+
+void MfccHip::set_warp(float alpha)
+{
+    m_alpha = alpha;
+    check(mfx_set_alpha(m_handle, alpha));
 }
 
 long long MfccHip::batch_frames(long long samples) const { return (long long)mfx_batch_frames(m_handle, (int64_t)samples); }

@@ -65,6 +65,7 @@ EXPORTED_SYMBOLS = (
     "mfx_host_dct_mfma_operands",
     "mfx_estimated_window_count", "mfx_max_frames_out", "mfx_fft_size",
     "mfx_batch_frames", "mfx_batch_plan", "mfx_batch_run_device", "mfx_batch_run_host", "mfx_batch_overlap",
+    "mfx_batch_set_alphas", "mfx_host_alpha_runs",
     "mfx_alloc_pinned", "mfx_free_pinned",
     "mfx_set_stream", "mfx_synchronize", "mfx_profile_enable", "mfx_profile_read",
     "mfx_dominant_kernel_name", "mfx_debug_read", "mfx_plan_create", "mfx_plan_set_aligned",
@@ -124,6 +125,9 @@ def load_library():
     L.mfx_batch_run_device.argtypes = [vp, vp, i64, vp]
     L.mfx_batch_run_host.argtypes = [vp, sp, i64, fp]
     L.mfx_batch_overlap.argtypes = [vp, C.c_int]
+    L.mfx_batch_set_alphas.argtypes = [vp, fp, i32]
+    L.mfx_host_alpha_runs.argtypes = [i32, fp, C.POINTER(i64), i64, i64, fp, C.POINTER(i32), C.POINTER(i64)]
+    L.mfx_host_alpha_runs.restype = i64
     L.mfx_set_stream.argtypes = [vp, vp]
     L.mfx_synchronize.argtypes = [vp]
     L.mfx_profile_enable.argtypes = [vp, C.c_int]
@@ -239,6 +243,28 @@ def host_traps_basis(traps_len, traps_dct_len):
     if rc != 0:
         raise MfxError(rc, "mfx_host_traps_basis failed")
     return b
+
+
+def host_alpha_runs(alphas, frames, window=None):
+    """Run lists of mfx_batch_set_alphas exactly as uploaded (host code, no GPU needed): (tables, off, runs) for one warp
+    factor and one frame count per utterance; runs is [n][2] = (first row, rows).  window = (row0, rows) clips every run
+    as the kernels clip it to a slab."""
+    L = load_library()
+    a = np.ascontiguousarray(alphas, dtype=np.float32)
+    f = np.ascontiguousarray(frames, dtype=np.int64)
+    assert a.size == f.size
+    n = int(a.size)
+    tables = np.zeros(max(n, 1), np.float32)
+    off = np.zeros(n + 1, np.int32)
+    runs = np.zeros((max(n, 1), 2), np.int64)
+    w0, wn = (0, -1) if window is None else (int(window[0]), int(window[1]))
+    nt = L.mfx_host_alpha_runs(n, a.ctypes.data_as(C.POINTER(C.c_float)), f.ctypes.data_as(C.POINTER(C.c_int64)), w0, wn,
+                               tables.ctypes.data_as(C.POINTER(C.c_float)), off.ctypes.data_as(C.POINTER(C.c_int32)),
+                               runs.ctypes.data_as(C.POINTER(C.c_int64)))
+    if nt < 0:
+        raise MfxError(int(nt), "mfx_host_alpha_runs failed")
+    nt = int(nt)
+    return tables[:nt].copy(), off[:nt + 1].copy(), runs[:int(off[nt])].copy()
 
 
 def host_frame_count(samples, window_size, shift):
@@ -474,6 +500,15 @@ class MfccHip:
         self._chk(self._L.mfx_batch_run_host(self._h, pcm.ctypes.data_as(C.POINTER(C.c_int16)), total,
                                              out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
+
+    def batch_set_alphas(self, alphas):
+        """One VTLN warp factor per utterance of the planned batch (float32 array, plan order); None clears the list.
+        A later batch_plan clears it too."""
+        if alphas is None:
+            self._chk(self._L.mfx_batch_set_alphas(self._h, None, 0))
+            return
+        a = np.ascontiguousarray(alphas, dtype=np.float32)
+        self._chk(self._L.mfx_batch_set_alphas(self._h, a.ctypes.data_as(C.POINTER(C.c_float)), int(a.size)))
 
     def batch_overlap(self, enable=True):
         """Let the delta tail of a batch overlap the next batch's front end (results complete after synchronize())."""

@@ -212,6 +212,23 @@ int mfx_batch_plan(mfx_handle *h, int32_t n_utt, const int64_t *offsets, const i
  * block (mfx_config.batch_norm_stats). */
 int mfx_batch_run_device(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_total, float *d_out);
 
+/* Per-utterance VTLN: one warp factor per utterance of the planned batch, in the plan's utterance order -- the alpha loop
+ * of ASR_OCL.cpp:236-243 applied across files: sweep, pick a factor per speaker, then extract every utterance with its own
+ * factor in ONE run instead of one plan and run per distinct factor.  Valid after mfx_batch_plan; n_utt must be the planned
+ * count and every factor > 0 (MFX_ERR_ARG otherwise).  The list is reduced to its distinct float values, compared bit for
+ * bit (nothing is quantised for the caller); more than 4096 distinct values is MFX_ERR_ARG (the cap of mfx_apply_alphas).
+ * alphas == NULL with n_utt == 0 clears the list, and so does a later mfx_batch_plan (the list is tied to the plan's
+ * utterance order): the handle is back on mfx_set_alpha's factor and the kernels it ran before.
+ * All tables and lists are built, allocated and uploaded HERE (the call waits for the handle's streams);
+ * mfx_batch_run_device still allocates nothing.  mfx_set_alpha and the handle's own tables are untouched: streaming calls
+ * on the same handle are unaffected.  Accepted for MFCC, log mel energies (ceps_len = 0), PLP and TRAPS.
+ * While a list is in force the batch runs spectrum -> HBM slab -> k_melcep_runs / k_plp_runs (every table on its own rows,
+ * one launch per slab and stage) whatever front end the shape would otherwise take: rows of utterance u are bit-identical
+ * to those of an MFX_ENGINE_STREAM_KERNELS handle at mfx_set_alpha(alphas[u]); mfx_dominant_kernel_name names the
+ * spectrum kernel that runs and mfx_profile_read times it.  MFX_ENGINE_FUSE_DELTA and mfx_batch_overlap have NO effect on
+ * such a run: neither the fused delta plan nor the statics scratch (and with it the second stream) is taken. */
+int mfx_batch_set_alphas(mfx_handle *h, const float *alphas, int32_t n_utt);
+
 /* Opt-in pipelining of consecutive batches: with enable=1 the delta / normalisation tail of a batch runs
  * on a second internal stream, so it overlaps the front end of the NEXT mfx_batch_run_device call.
  * Results of a batch are then complete only after mfx_synchronize() (or a device-wide synchronise),
@@ -272,6 +289,14 @@ int mfx_host_plp_tables(int32_t num_banks, int32_t fft_size, float sample_rate, 
 /* TRAPS basis as uploaded (TRAPS): basis [traps_dct_len][traps_len], Hamming window times the DCT-II in the
  * reference's DCT convention, evaluated in double and rounded once.  Lengths as given (no 0 = default here). */
 int mfx_host_traps_basis(int32_t traps_len, int32_t traps_dct_len, float *basis);
+/* Run lists of mfx_batch_set_alphas as uploaded ("Per-utterance warp factors"): utterance u holds frames[u]
+ * consecutive rows.  tables [<= n_utt]: the distinct factors (bit patterns) in order of first appearance; off
+ * [tables + 1]; runs [<= n_utt][2] = (first row, rows): table a owns runs off[a] .. off[a + 1] - 1, ascending, equal
+ * neighbours merged, frameless utterances left out.  win_rows >= 0: every run clipped to rows [win_row0, win_row0 +
+ * win_rows) as the kernels clip it to a slab (empty ones dropped).  Returns the number of tables.  Any output may be NULL.
+ * Test / inspection aid. */
+int64_t mfx_host_alpha_runs(int32_t n_utt, const float *alphas, const int64_t *frames, int64_t win_row0, int64_t win_rows,
+                            float *tables, int32_t *off, int64_t *runs);
 /* frame count, integer arithmetic (parambase.cpp:16-19 without the float32 division) */
 int64_t mfx_host_frame_count(int64_t samples, int32_t window_size, int32_t shift);
 

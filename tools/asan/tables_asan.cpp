@@ -70,6 +70,40 @@ int main()
     mfx::build_pass256_twiddles(tw);
     for (long s : {0L, 1L, 399L, 400L, 160000L, 57600000L, 1L << 31})
         for (int W : {400, 1024}) (void)mfx::frame_count(s, W, 160);
-    std::printf("tables_asan: %d configurations, %d front-end tables clean\n", n, nt);
+    // run lists of mfx_batch_set_alphas: ragged frame counts (frameless utterances included), few and many distinct factors,
+    // clipped to slab windows of every size class; every row of the batch must come out exactly once
+    int nr = 0;
+    for (int n_utt : {0, 1, 9, 257, 5000})
+        for (int distinct : {1, 3, 21, 4096}) {
+            std::vector<float> alphas((size_t)n_utt);
+            std::vector<int64_t> frames((size_t)n_utt);
+            int64_t total = 0;
+            for (int u = 0; u < n_utt; ++u) {
+                alphas[u] = 0.8f + 1e-5f * (float)((u * 7) % distinct);
+                frames[u] = (int64_t)((u * 37) % 11 == 0 ? 0 : (u * 131) % 1003);
+                total += frames[u];
+            }
+            std::vector<float> tables;
+            std::vector<int32_t> off;
+            std::vector<int64_t> runs;
+            mfx::build_alpha_runs(alphas.data(), frames.data(), n_utt, tables, off, runs);
+            if (off.size() != tables.size() + 1 || (size_t)off.back() * 2 != runs.size()) return 1;
+            for (int64_t slab : {(int64_t)1, (int64_t)64, (int64_t)4097, total + 1}) {
+                int64_t seen = 0;
+                for (int64_t w0 = 0; w0 < total; w0 += slab) {
+                    std::vector<int32_t> o2 = off;
+                    std::vector<int64_t> r2 = runs;
+                    mfx::clip_alpha_runs(w0, slab, o2, r2);
+                    for (size_t r = 0; r < r2.size(); r += 2) seen += r2[r + 1];
+                    if (slab == 1 && total > 20000 && w0 > 2000) { // (the one-row slabs of the long batches: a sample)
+                        seen += total - w0 - slab;
+                        break;
+                    }
+                }
+                if (seen != total) return 1;
+                ++nr;
+            }
+        }
+    std::printf("tables_asan: %d configurations, %d front-end tables, %d run lists clean\n", n, nt, nr);
     return 0;
 }
