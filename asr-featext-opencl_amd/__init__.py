@@ -32,6 +32,7 @@ from .mfcc import (  # noqa: F401
     host_mel_table,
     host_plp_tables,
     host_traps_basis,
+    host_xform_operands,
     KERNEL_TABLE,
     library_path,
     load_library,

@@ -946,6 +946,24 @@ extern "C" int64_t mfx_host_alpha_runs(int32_t n_utt, const float *alphas, const
     return (int64_t)t.size();
 }
 
+// Operands of k_splice_affine for one transform: out[(s * tiles + tile) * 64 + lane] (build_xform_operands); returns
+// steps * tiles * 64, or the size needed when out is NULL.
+extern "C" int64_t mfx_host_xform_operands(int32_t out_dim, int32_t in_dim, const float *A, float *out, int64_t out_cap,
+                                           int32_t *tiles, int32_t *steps)
+{
+    if (out_dim < 1 || out_dim > 256 || in_dim < 1 || in_dim > 8192 || !A) return MFX_ERR_ARG;
+    const int tl = (out_dim + 15) / 16, st = (in_dim + 3) / 4;
+    const int64_t n = (int64_t)st * tl * 64;
+    if (tiles) *tiles = tl;
+    if (steps) *steps = st;
+    if (out) {
+        if (n > out_cap) return MFX_ERR_ARG;
+        int a = 0, b = 0;
+        build_xform_operands(A, out_dim, in_dim, a, b, out);
+    }
+    return n;
+}
+
 extern "C" int64_t mfx_host_frame_count(int64_t samples, int32_t window_size, int32_t shift)
 {
     if (window_size <= 0 || shift <= 0) return MFX_ERR_ARG;

@@ -195,6 +195,8 @@ extern "C" int mfx_batch_plan(mfx_handle *h, int32_t n_utt, const int64_t *offse
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->batch.alphas_on = false; // (a warp-factor list is tied to the plan's utterance order)
+    h->batch.xf_on = false;     // (and so are a transform's utterance index and its scratch)
+    h->batch.planned = false;
     h->batch.n_utt = n_utt;
     h->batch.utt_off.assign(offsets, offsets + n_utt);
     h->batch.utt_len.assign(lengths, lengths + n_utt);
@@ -287,17 +289,17 @@ extern "C" int mfx_batch_plan(mfx_handle *h, int32_t n_utt, const int64_t *offse
         const size_t need = norm_partial_doubles(n_utt, tiles_max * 64, h->cols);
         if (need > h->d_norm_partial.n) HIP_TRY(h, h->d_norm_partial.alloc(need));
     }
-    {
-        int rcf = plan_fused_delta(h, T_of);
-        if (rcf != MFX_OK) return rcf;
-    }
+    int rcf = plan_fused_delta(h, T_of);
+    if (rcf != MFX_OK) return rcf;
     // (allocated here so that mfx_batch_run_device itself never allocates)
     if (h->traps) { // log mel rows between the front end and k_traps (grown, never shrunk)
         h->batch.mel_pitch = (h->nb + 3) & ~3;
         const size_t need = (size_t)row * h->batch.mel_pitch;
         if (h->batch.d_logmel.n < need) HIP_TRY(h, h->batch.d_logmel.alloc(need));
     }
-    return size_static16(h);
+    rcf = size_static16(h);
+    h->batch.planned = rcf == MFX_OK;
+    return rcf;
 }
 
 // rows of the spectrum slab of the batch entries' spectrum path
@@ -339,6 +341,75 @@ extern "C" int mfx_batch_set_alphas(mfx_handle *h, const float *alphas, int32_t 
     return MFX_OK;
 }
 
+int batch_out_width(const mfx_handle *h) { return h->batch.xf_on ? h->batch.xf_out : h->width; }
+
+extern "C" int mfx_batch_output_width(const mfx_handle *h) { return h ? batch_out_width(h) : MFX_ERR_ARG; }
+
+static void fill_xform(const mfx_handle *h, XformParams &p)
+{
+    p = XformParams{};
+    p.width = h->width;
+    p.left = h->batch.xf_left;
+    p.right = h->batch.xf_right;
+    p.out_dim = h->batch.xf_out;
+    p.valu = (h->cfg.engine & MFX_ENGINE_XFORM_VALU) ? 1 : 0;
+}
+
+extern "C" int mfx_batch_set_transform(mfx_handle *h, int32_t left, int32_t right, int32_t out_dim, int32_t n_xf, const float *A,
+                                       const float *b, const int32_t *utt_xf, int32_t n_utt)
+{
+    MFX_DEVICE_ENTRY(h);
+    if (!A && n_xf == 0) { // back to the rows the handle delivered before, in the caller's d_out
+        HIP_TRY(h, hipSetDevice(h->device));
+        const int rc = mfx_synchronize(h); // (a run in flight may read what is released below)
+        if (rc != MFX_OK) return rc;
+        h->batch.xf_on = false;
+        h->batch.d_xf_ops.release(), h->batch.d_xf_bias.release(), h->batch.d_xf_idx.release(), h->batch.d_xf_y.release();
+        return MFX_OK;
+    }
+    if (!h->batch.planned) return fail(h, MFX_ERR_STATE, "mfx_batch_set_transform: no batch is planned");
+    if (!A) return fail(h, MFX_ERR_ARG, "no matrix");
+    if (left < 0 || left > 32 || right < 0 || right > 32) return fail(h, MFX_ERR_ARG, "left and right must be 0 .. 32");
+    if (out_dim < 1 || out_dim > 256) return fail(h, MFX_ERR_ARG, "out_dim must be 1 .. 256");
+    if (n_xf < 1 || n_xf > 1024) return fail(h, MFX_ERR_ARG, "n_xf must be 1 .. 1024");
+    const int64_t in_dim = (int64_t)(left + right + 1) * h->width;
+    if (in_dim > 8192) return fail(h, MFX_ERR_ARG, "in_dim = (left + right + 1) * width is larger than 8192");
+    if (utt_xf) {
+        if (n_utt != h->batch.n_utt) return fail(h, MFX_ERR_ARG, "one transform index per planned utterance");
+        for (int u = 0; u < n_utt; ++u)
+            if (utt_xf[u] < 0 || utt_xf[u] >= n_xf) return fail(h, MFX_ERR_ARG, "transform index outside [0, n_xf)");
+    }
+    XformParams probe;
+    fill_xform(h, probe);
+    probe.left = left, probe.right = right, probe.out_dim = out_dim;
+    // (the limits above leave a tile of 16 rows inside 160 KB at every row width a handle can have; checked all the same)
+    if (xform_tile_rows(probe) == 0) return fail(h, MFX_ERR_ARG, "no tile of k_splice_affine fits the LDS for this shape");
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = mfx_synchronize(h); // (a run in flight may read the matrices and the index replaced below)
+    if (rc != MFX_OK) return rc;
+    h->batch.xf_on = false;
+    const int tiles = (out_dim + 15) / 16, steps = (int)((in_dim + 3) / 4);
+    const size_t per = (size_t)steps * tiles * 64;
+    std::vector<float> ops(per * n_xf), bias((size_t)n_xf * tiles * 16, 0.f);
+    for (int x = 0; x < n_xf; ++x) {
+        int tl = 0, st = 0;
+        build_xform_operands(A + (size_t)x * out_dim * in_dim, out_dim, (int)in_dim, tl, st, ops.data() + per * x);
+        if (b) std::copy(b + (size_t)x * out_dim, b + (size_t)(x + 1) * out_dim, bias.begin() + (size_t)x * tiles * 16);
+    }
+    HIP_TRY(h, h->upload(h->batch.d_xf_ops, ops));
+    HIP_TRY(h, h->upload(h->batch.d_xf_bias, bias));
+    if (utt_xf)
+        HIP_TRY(h, h->upload(h->batch.d_xf_idx, std::vector<int32_t>(utt_xf, utt_xf + n_utt)));
+    else
+        h->batch.d_xf_idx.release();
+    // (everything mfx_batch_run_device needs is allocated here: that entry never allocates)
+    const size_t need = (size_t)std::max<int64_t>(h->batch.total_rows, 1) * h->width;
+    if (h->batch.d_xf_y.n < need) HIP_TRY(h, h->batch.d_xf_y.alloc(need));
+    h->batch.xf_left = left, h->batch.xf_right = right, h->batch.xf_out = out_dim;
+    h->batch.xf_on = true;
+    return MFX_OK;
+}
+
 namespace {
 // utterances [u0, u1) of the planned batch (all of them: the fused-delta and overlap modes apply)
 int batch_run_range(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_total, float *d_out, int u0, int u1);
@@ -366,6 +437,13 @@ int batch_run_range(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_tot
     int rc = refresh_mel(h);
     if (rc != MFX_OK) return rc;
     if (rc1 <= rc0) return MFX_OK;
+    // A transform in force: everything below runs as it always does with the handle's scratch in the place of d_out, and
+    // k_splice_affine turns the scratch rows into the caller's array as the last launch.
+    float *const d_final = d_out;
+    if (h->batch.xf_on) {
+        if (h->batch.d_xf_y.n < (size_t)h->batch.total_rows * h->width) return fail(h, MFX_ERR_STATE, "batch not planned");
+        d_out = h->batch.d_xf_y.p;
+    }
 
     FrontParams p;
     fill_front(h, p);
@@ -526,6 +604,21 @@ int batch_run_range(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_tot
                       false, h->batch.tiles_max * 64, groups, (size_t)h->batch.n_utt * 2 * h->cols);
         if (rc != MFX_OK) return rc;
     }
+    if (h->batch.xf_on) { // behind the tail, on its stream: ev_tail covers it
+        XformParams xp;
+        fill_xform(h, xp);
+        xp.src = d_out;
+        xp.src_pitch = h->width;
+        xp.out = d_final;
+        xp.out_pitch = h->batch.xf_out;
+        xp.segs = h->batch.d_segs.p + u0;
+        xp.n_segs = u1 - u0;
+        xp.seg_xf = h->batch.d_xf_idx.p ? h->batch.d_xf_idx.p + u0 : nullptr;
+        xp.operands = h->batch.d_xf_ops.p;
+        xp.bias = h->batch.d_xf_bias.p;
+        xp.tiles_per_seg_max = h->batch.tiles_max;
+        HIP_TRY(h, launch_xform(xp, tail_stream));
+    }
     if (split_tail) {
         HIP_TRY(h, hipEventRecord(h->batch.ev_tail[sb], tail_stream));
         h->batch.tail_pending[sb] = true;
@@ -572,7 +665,8 @@ extern "C" int mfx_batch_run_host(mfx_handle *h, const int16_t *pcm, int64_t pcm
     HIP_TRY(h, hipSetDevice(h->device));
     // device-side staging of the host buffers, kept by the handle and grown on demand
     const size_t n_in = (size_t)pcm_samples_total * h->channels;
-    const size_t n_out = (size_t)std::max<int64_t>(h->batch.total_rows, 1) * h->width;
+    const int64_t ow = batch_out_width(h); // floats of an output row
+    const size_t n_out = (size_t)std::max<int64_t>(h->batch.total_rows, 1) * ow;
     if (h->batch.d_host_pcm.n < n_in + 8) HIP_TRY(h, h->batch.d_host_pcm.alloc(n_in + 8));
     if (h->batch.d_host_out.n < n_out) HIP_TRY(h, h->batch.d_host_out.alloc(n_out));
 
@@ -617,8 +711,8 @@ extern "C" int mfx_batch_run_host(mfx_handle *h, const int16_t *pcm, int64_t pcm
             HIP_TRY(h, hipStreamWaitEvent(h->batch.stream_dn, h->batch.ev_run[k], 0));
             const int64_t r0 = h->batch.utt_row[u0], r1 = u1 < h->batch.n_utt ? h->batch.utt_row[u1] : h->batch.total_rows;
             if (r1 > r0)
-                HIP_TRY(h, hipMemcpyAsync(out + r0 * h->width, h->batch.d_host_out.p + r0 * h->width,
-                                          (size_t)(r1 - r0) * h->width * sizeof(float), hipMemcpyDeviceToHost, h->batch.stream_dn));
+                HIP_TRY(h, hipMemcpyAsync(out + r0 * ow, h->batch.d_host_out.p + r0 * ow, (size_t)(r1 - r0) * ow * sizeof(float),
+                                          hipMemcpyDeviceToHost, h->batch.stream_dn));
             return MFX_OK;
         };
         for (int k = 0; k < K; ++k) {
@@ -642,7 +736,7 @@ extern "C" int mfx_batch_run_host(mfx_handle *h, const int16_t *pcm, int64_t pcm
     }
     if (h->batch.stream2) HIP_TRY(h, hipStreamSynchronize(h->batch.stream2)); // overlapped tail, if any
     if (h->batch.total_rows > 0)
-        HIP_TRY(h, hipMemcpyAsync(out, h->batch.d_host_out.p, (size_t)h->batch.total_rows * h->width * sizeof(float),
-                                  hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(out, h->batch.d_host_out.p, (size_t)h->batch.total_rows * ow * sizeof(float), hipMemcpyDeviceToHost,
+                                  h->stream));
     return mfx_synchronize(h);
 }

@@ -171,6 +171,14 @@ struct BatchState {
     std::vector<int64_t> h_runs;         // [runs][2]
     DevBuf<int32_t> d_run_off;
     DevBuf<int64_t> d_runs;
+    // splice + affine transform (mfx_batch_set_transform), tied to the plan: while xf_on the run writes its rows to d_xf_y
+    // and k_splice_affine turns them into the caller's d_out as the last launch
+    bool planned = false;                // mfx_batch_plan has succeeded
+    bool xf_on = false;
+    int xf_left = 0, xf_right = 0, xf_out = 0;
+    DevBuf<float> d_xf_ops, d_xf_bias;   // [n_xf][steps][tiles][64], [n_xf][tiles * 16]
+    DevBuf<int32_t> d_xf_idx;            // [n_utt] transform of every utterance (empty: all 0)
+    DevBuf<float> d_xf_y;                // [total_rows][width]
 };
 
 // fused delta stage of the 512-point kernel: per-block chunk lists (own rows + halo) and delta tiles: mfx_batch.cpp
@@ -339,6 +347,8 @@ FrontKind choose_front(const mfx_handle *h);
 FrontKind batch_front(const mfx_handle *h);
 void fill_front(const mfx_handle *h, mfx::FrontParams &p);
 void fill_traps(const mfx_handle *h, mfx::TrapsParams &p);
+// (mfx_batch.cpp) row width of the batch entries' output: out_dim while a transform is in force, else `width`
+int batch_out_width(const mfx_handle *h);
 int refresh_mel(mfx_handle *h);
 int build_cep_tables(mfx_handle *h, const float *alphas, int n, CepTables &t, mfx::MelTable *first = nullptr,
                      mfx::MelWavePlan *first_plan = nullptr);

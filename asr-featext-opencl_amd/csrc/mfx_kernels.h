@@ -1,4 +1,4 @@
-// mfx_kernels.h -- launch interface of the gfx950 kernels (implemented in mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip, mfx_plp.hip, mfx_traps.hip: one translation unit per kernel family).
+// mfx_kernels.h -- launch interface of the gfx950 kernels (implemented in mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip, mfx_plp.hip, mfx_traps.hip, mfx_xform.hip: one translation unit per kernel family).
 //
 // Kernel inventory and the reference stage each one replaces:
 //   spectrum512 / fused512   segmenter.cl kernelSegmentWindow + AppleFFT fft0 + mfcc.cl kernelTranspose
@@ -7,6 +7,7 @@
 //   melcep                   mfcc.cl kernelFilter + DCT slot (mfccopencl.cpp:315-358) from a stored spectrum
 //   plp                      PLP cepstra from a stored spectrum (no reference kernel: the reference names the method only)
 //   traps                    TRAPS temporal patterns from stored log mel rows (no reference kernel: the reference names the method only)
+//   splice_affine            frame splicing + affine transform of finished rows (no reference analogue: the last stage of a front end)
 //   delta                    delta.cl kernelDelta x2 + the staging copies of mfccopencl.cpp:360-387
 //   norm_stats / norm_apply  norm.cl kernelSum + kernelFinalizeSum / kernelNormalize
 #pragma once
@@ -209,6 +210,28 @@ struct TrapsParams {
     int32_t tile_rows;     // set by the launcher: 64, 32 or 16 output rows per block
 };
 
+// k_splice_affine (mfx_xform.hip): finished feature rows -> spliced context window -> affine map ("Splice +
+// affine transform").  One Segment per utterance: rows src_row0 + clamp(t - left + c, lo, hi), c <= left + right, are read,
+// rows out_row0 + t, t < n_out, written (shift / static_off / pad are not used).  Segment s maps with transform seg_xf[s].
+struct XformParams {
+    const float *src;      // the rows y, [rows][src_pitch], columns [0, width)
+    int32_t src_pitch;
+    float *out;            // [rows][out_pitch], columns [0, out_dim) written
+    int32_t out_pitch;
+    const Segment *segs;
+    int32_t n_segs;
+    const int32_t *seg_xf; // [n_segs] transform of every segment, or nullptr: all 0
+    int32_t width;         // Wd
+    int32_t left, right;   // context frames, 0 .. 32 each; in_dim = (left + right + 1) * width <= 8192
+    int32_t out_dim;       // 1 .. 256
+    int32_t valu;          // 0: matrix pipe; 1: vector ALUs (the same operands, the same bits)
+    const float *operands; // [n_xf][steps][tiles][64] (build_xform_operands per transform)
+    const float *bias;     // [n_xf][tiles * 16], zero beyond out_dim
+    int32_t tiles_per_seg_max; // in tiles of 64 rows, as DeltaParams
+    int32_t tile_rows;     // set by the launcher: 64, 32 or 16 output rows per block
+    int32_t ksteps;        // set by the launcher: steps of 4 taps per LDS chunk of the matrix
+};
+
 struct DeltaParams {
     const float *src;      // static features, [rows][src_pitch]
     int32_t src_pitch;
@@ -260,6 +283,12 @@ hipError_t launch_traps(const TrapsParams &p, hipStream_t stream);
 // LDS of k_traps with tile_rows output rows per block; traps_tile_rows: the tile the launcher takes (0: none fits)
 size_t traps_lds_bytes(const TrapsParams &p, int tile_rows);
 int traps_tile_rows(const TrapsParams &p);
+hipError_t launch_xform(const XformParams &p, hipStream_t stream);
+// LDS of k_splice_affine with tile_rows output rows per block; xform_tile_rows: the tile the launcher takes (0: the shape is
+// outside the limits, or none fits); xform_shape_ok: width, context, in_dim and out_dim inside the kernel's limits
+size_t xform_lds_bytes(const XformParams &p, int tile_rows);
+int xform_tile_rows(const XformParams &p);
+bool xform_shape_ok(const XformParams &p);
 // LDS of k_plp with n_waves waves per block (the launcher takes as many of 4 as fit)
 size_t plp_lds_bytes(const PlpParams &p, int n_waves);
 // LDS of k_melcep with n_waves waves per block (the launcher takes as many of 4 as fit)

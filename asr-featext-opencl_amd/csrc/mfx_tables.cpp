@@ -140,6 +140,18 @@ void build_traps_valu_operands(const std::vector<float> &basis, int traps_len, i
         for (int k = 0; k < K; ++k) out[(size_t)j * kp + k] = basis[(size_t)k * L + j];
 }
 
+void build_xform_operands(const float *A, int out_dim, int in_dim, int &tiles, int &steps, float *out)
+{
+    tiles = (out_dim + 15) / 16;
+    steps = (in_dim + 3) / 4;
+    for (int s = 0; s < steps; ++s)
+        for (int t = 0; t < tiles; ++t)
+            for (int lane = 0; lane < 64; ++lane) {
+                const int r = 16 * t + (lane & 15), i = 4 * s + (lane >> 4);
+                out[((size_t)s * tiles + t) * 64 + lane] = (r < out_dim && i < in_dim) ? A[(size_t)r * in_dim + i] : 0.f;
+            }
+}
+
 void build_plp_lifter(int ceps_len, float lift_coef, std::vector<float> &out)
 {
     out.assign((size_t)ceps_len, 0.f);

@@ -57,6 +57,12 @@ void build_traps_mfma_operands(const std::vector<float> &basis, int traps_len, i
 // k_traps on the vector ALUs: the basis transposed, [L][kp], kp = K padded to 4, 16 or 32 accumulators (zero beyond K)
 void build_traps_valu_operands(const std::vector<float> &basis, int traps_len, int traps_dct_len, int &kp, std::vector<float> &out);
 
+// k_splice_affine ("Splice + affine transform"): one transform's matrix A, row-major [out_dim][in_dim], as the
+// kernel streams it -- for every step of 4 taps and every tile of 16 outputs the 64 lanes' operands of
+// v_mfma_f32_16x16x4_f32: out[(s * tiles + tile) * 64 + lane] = A[16 tile + (lane & 15)][4 s + (lane >> 4)], zero beyond
+// the matrix.  tiles = ceil(out_dim / 16), steps = ceil(in_dim / 4).  `out` must hold steps * tiles * 64 floats.
+void build_xform_operands(const float *A, int out_dim, int in_dim, int &tiles, int &steps, float *out);
+
 // Per-utterance warp factors of a planned batch (mfx_batch_set_alphas) -> what the row-run kernels read.  Utterance u holds
 // the rows [sum of frames[0 .. u), + frames[u]).
 //   tables: the distinct factors, compared bit for bit, in order of first appearance

@@ -66,6 +66,7 @@ EXPORTED_SYMBOLS = (
     "mfx_estimated_window_count", "mfx_max_frames_out", "mfx_fft_size",
     "mfx_batch_frames", "mfx_batch_plan", "mfx_batch_run_device", "mfx_batch_run_host", "mfx_batch_overlap",
     "mfx_batch_set_alphas", "mfx_host_alpha_runs",
+    "mfx_batch_set_transform", "mfx_batch_output_width", "mfx_host_xform_operands",
     "mfx_alloc_pinned", "mfx_free_pinned",
     "mfx_set_stream", "mfx_synchronize", "mfx_profile_enable", "mfx_profile_read",
     "mfx_dominant_kernel_name", "mfx_debug_read", "mfx_plan_create", "mfx_plan_set_aligned",
@@ -128,6 +129,10 @@ def load_library():
     L.mfx_batch_set_alphas.argtypes = [vp, fp, i32]
     L.mfx_host_alpha_runs.argtypes = [i32, fp, C.POINTER(i64), i64, i64, fp, C.POINTER(i32), C.POINTER(i64)]
     L.mfx_host_alpha_runs.restype = i64
+    L.mfx_batch_set_transform.argtypes = [vp, i32, i32, i32, i32, fp, fp, C.POINTER(i32), i32]
+    L.mfx_batch_output_width.argtypes = [vp]
+    L.mfx_host_xform_operands.argtypes = [i32, i32, fp, fp, i64, C.POINTER(i32), C.POINTER(i32)]
+    L.mfx_host_xform_operands.restype = i64
     L.mfx_set_stream.argtypes = [vp, vp]
     L.mfx_synchronize.argtypes = [vp]
     L.mfx_profile_enable.argtypes = [vp, C.c_int]
@@ -267,6 +272,22 @@ def host_alpha_runs(alphas, frames, window=None):
     return tables[:nt].copy(), off[:nt + 1].copy(), runs[:int(off[nt])].copy()
 
 
+def host_xform_operands(A):
+    """One transform of batch_set_transform exactly as k_splice_affine streams it (host code, no GPU needed):
+    [steps][tiles][64] for a matrix A [out_dim][in_dim]; element [s][t][lane] = A[16 t + (lane & 15)][4 s + (lane >> 4)]."""
+    L = load_library()
+    a = np.ascontiguousarray(A, dtype=np.float32)
+    od, ind = a.shape
+    fpt = C.POINTER(C.c_float)
+    tl, st = C.c_int32(0), C.c_int32(0)
+    n = L.mfx_host_xform_operands(od, ind, a.ctypes.data_as(fpt), None, 0, C.byref(tl), C.byref(st))
+    if n < 0:
+        raise MfxError(int(n), "mfx_host_xform_operands failed")
+    out = np.zeros(n, np.float32)
+    L.mfx_host_xform_operands(od, ind, a.ctypes.data_as(fpt), out.ctypes.data_as(fpt), out.size, C.byref(tl), C.byref(st))
+    return out.reshape(st.value, tl.value, 64)
+
+
 def host_frame_count(samples, window_size, shift):
     return int(load_library().mfx_host_frame_count(int(samples), int(window_size), int(shift)))
 
@@ -345,6 +366,7 @@ KERNEL_TABLE = (
 
 ENGINE_NO_FRONT1024, ENGINE_FUSE_DELTA, ENGINE_NO_FRONT2048, ENGINE_STREAM_KERNELS, ENGINE_NORM_TWO_KERNELS = 1, 2, 4, 8, 16
 ENGINE_DMA_SMALL_BLOCKS, ENGINE_NO_DCT_SPLIT, ENGINE_NO_STUFF256, ENGINE_FRONT1024_12_WAVES = 32, 64, 128, 256     # mfx_config.engine bits (include/mfx.h)
+ENGINE_TRAPS_VALU, ENGINE_XFORM_VALU = 512, 1024
 
 
 class MfccHip:
@@ -496,7 +518,7 @@ class MfccHip:
     def batch_run_host(self, pcm):
         pcm = np.ascontiguousarray(pcm, dtype=np.int16)
         total = pcm.size // max(self.cfg.channels, 1)
-        out = np.zeros((self._plan_total, self.get_output_data_width()), dtype=np.float32)
+        out = np.zeros((self._plan_total, self.batch_output_width()), dtype=np.float32)
         self._chk(self._L.mfx_batch_run_host(self._h, pcm.ctypes.data_as(C.POINTER(C.c_int16)), total,
                                              out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
@@ -509,6 +531,38 @@ class MfccHip:
             return
         a = np.ascontiguousarray(alphas, dtype=np.float32)
         self._chk(self._L.mfx_batch_set_alphas(self._h, a.ctypes.data_as(C.POINTER(C.c_float)), int(a.size)))
+
+    def batch_set_transform(self, A, b=None, left=0, right=0, utt_xf=None):
+        """Splice + affine transform as the last stage of a batch run (mfx_batch_set_transform): every output row becomes
+        b + A . [rows t - left .. t + right of the utterance, edges replicated].  A is [out_dim][in_dim] or
+        [n_xf][out_dim][in_dim] with in_dim = (left + right + 1) * get_output_data_width(); b [out_dim] / [n_xf][out_dim] or
+        None (zeros); utt_xf one transform index per planned utterance or None (all 0).  A = None clears the transform; a
+        later batch_plan clears it too."""
+        if A is None:
+            self._chk(self._L.mfx_batch_set_transform(self._h, 0, 0, 0, 0, None, None, None, 0))
+            return
+        a = np.ascontiguousarray(A, dtype=np.float32)
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3:
+            raise ValueError("A must be [out_dim][in_dim] or [n_xf][out_dim][in_dim]")
+        n_xf, out_dim, in_dim = a.shape
+        if in_dim != (int(left) + int(right) + 1) * self.get_output_data_width():
+            raise ValueError("A must have (left + right + 1) * get_output_data_width() columns")
+        fpt, ipt = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        bb = None
+        if b is not None:
+            bb = np.ascontiguousarray(b, dtype=np.float32).reshape(-1)
+            if bb.size != n_xf * out_dim:
+                raise ValueError("b must have out_dim entries per transform")
+        idx = None if utt_xf is None else np.ascontiguousarray(utt_xf, dtype=np.int32)
+        self._chk(self._L.mfx_batch_set_transform(
+            self._h, int(left), int(right), out_dim, n_xf, a.ctypes.data_as(fpt), None if bb is None else bb.ctypes.data_as(fpt),
+            None if idx is None else idx.ctypes.data_as(ipt), 0 if idx is None else int(idx.size)))
+
+    def batch_output_width(self):
+        """Row width of the batch entries' output: out_dim while a transform is in force, else get_output_data_width()."""
+        return self._L.mfx_batch_output_width(self._h)
 
     def batch_overlap(self, enable=True):
         """Let the delta tail of a batch overlap the next batch's front end (results complete after synchronize())."""

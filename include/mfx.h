@@ -127,6 +127,9 @@ enum { MFX_METHOD_MFCC = 0, MFX_METHOD_PLP = 1, MFX_METHOD_TRAPS = 3 };
 #define MFX_ENGINE_TRAPS_VALU 512        /* TRAPS: the trajectory DCT on the vector ALUs instead of the matrix pipe (the same
                                            ascending float32 FMA chain per output: the same bits)                        */
 
+#define MFX_ENGINE_XFORM_VALU 1024       /* splice + affine transform (mfx_batch_set_transform): the FMA chains on the vector
+                                           ALUs instead of the matrix pipe (the same chain per output: the same bits)     */
+
 #define MFX_ENGINE_FRONT1024_12_WAVES 256 /* 1024-point fused kernel: the 12-waves-per-CU build also where the 16-wave build fits
                                             (aligned frames, window <= 512 samples, tables small enough): the same bits      */
 
@@ -229,6 +232,39 @@ int mfx_batch_run_device(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_sample
  * such a run: neither the fused delta plan nor the statics scratch (and with it the second stream) is taken. */
 int mfx_batch_set_alphas(mfx_handle *h, const float *alphas, int32_t n_utt);
 
+/* Splice + affine transform as the last stage of a batch run ("Splice + affine transform"): LDA / HLDA / MLLT
+ * over spliced frames, PCA or a linear merger over TRAPS columns, a per-speaker fMLLR matrix.  No reference analogue.
+ * For utterance u with T frames, let y[t] (t = 0 .. T-1) be the rows the handle delivers today, of width
+ * Wd = mfx_get_output_data_width(h), layout [static | d | dd], normalised if normalisation is on.  With left, right >= 0,
+ * C = left + right + 1 and in_dim = C * Wd:
+ *   1. Splice.  z[t] = [ y[clamp(t-left, 0, T-1)] | ... | y[clamp(t+right, 0, T-1)] ]: the first and last frame of the
+ *      UTTERANCE are replicated, the rule the delta stage and TRAPS use.
+ *   2. Affine map with transform x = utt_xf[u] (0 when no list is given); A_x row-major [out_dim][in_dim], b_x [out_dim]:
+ *      acc = b_x[r]; for i = 0 .. in_dim-1 ascending: acc = fmaf(A_x[r][i], z[t][i], acc); out[t][r] = acc.
+ *      A float32 chain with one FMA per tap, in this order: a row's bits do not depend on the tiling, on the other
+ *      utterances of the batch, or on whether the matrix-pipe or the vector form (MFX_ENGINE_XFORM_VALU) computed it.
+ *   3. Output.  d_out is then [total_rows][out_dim] in the plan's row order (out_rows[u] unchanged).  The rows y are not
+ *      delivered.
+ * Valid after mfx_batch_plan (MFX_ERR_STATE before one).  A == NULL with n_xf == 0 clears the transform, and so does a
+ * later mfx_batch_plan (the list and the scratch are tied to the plan): the handle is back on its previous kernels and
+ * bits.  MFX_ERR_ARG: left or right outside 0 .. 32, out_dim outside 1 .. 256, n_xf outside 1 .. 1024, in_dim > 8192,
+ * utt_xf given with n_utt != the planned count or with an entry outside [0, n_xf).  The matrix values are not inspected.
+ * The matrices (in the layout the kernel streams, mfx_host_xform_operands), the biases, the per-utterance index and a
+ * handle-owned scratch [total_rows][Wd] for the rows y are allocated and uploaded HERE (the call waits for the handle's
+ * streams); mfx_batch_run_device still allocates nothing.  While a transform is in force a batch run does exactly what it
+ * does today with that scratch in the place of d_out -- whatever the front end, MFX_ENGINE_* bits, per-utterance alpha
+ * list or mfx_batch_overlap mode, so the rows the transform reads are bit-identical to those of a handle without one --
+ * and k_splice_affine then turns scratch rows into d_out as the last launch, on the stream the tail runs on.
+ * mfx_batch_run_host sizes and copies its output by mfx_batch_output_width.  The streaming entries, mfx_set_alpha,
+ * mfx_debug_read, mfx_dominant_kernel_name and mfx_profile_read (which still name and time the front end) do not change. */
+int mfx_batch_set_transform(mfx_handle *h, int32_t left, int32_t right, int32_t out_dim, int32_t n_xf,
+                            const float *A,        /* [n_xf][out_dim][in_dim]            */
+                            const float *b,        /* [n_xf][out_dim], NULL = zeros      */
+                            const int32_t *utt_xf, /* [n_utt] transform of each utterance, NULL = all 0 */
+                            int32_t n_utt);
+/* out_dim while a transform is in force, else mfx_get_output_data_width */
+int mfx_batch_output_width(const mfx_handle *h);
+
 /* Opt-in pipelining of consecutive batches: with enable=1 the delta / normalisation tail of a batch runs
  * on a second internal stream, so it overlaps the front end of the NEXT mfx_batch_run_device call.
  * Results of a batch are then complete only after mfx_synchronize() (or a device-wide synchronise),
@@ -297,6 +333,12 @@ int mfx_host_traps_basis(int32_t traps_len, int32_t traps_dct_len, float *basis)
  * Test / inspection aid. */
 int64_t mfx_host_alpha_runs(int32_t n_utt, const float *alphas, const int64_t *frames, int64_t win_row0, int64_t win_rows,
                             float *tables, int32_t *off, int64_t *runs);
+/* One transform of mfx_batch_set_transform as k_splice_affine streams it: for every step of 4 taps and every tile of 16
+ * outputs the 64 lanes' operands of v_mfma_f32_16x16x4_f32, out[(s * tiles + tile) * 64 + lane] =
+ * A[16 tile + (lane & 15)][4 s + (lane >> 4)], zero beyond the matrix; tiles = ceil(out_dim / 16), steps = ceil(in_dim / 4).
+ * Returns steps * tiles * 64 (out may be NULL to query).  Test / inspection aid. */
+int64_t mfx_host_xform_operands(int32_t out_dim, int32_t in_dim, const float *A, float *out, int64_t out_cap, int32_t *tiles,
+                                int32_t *steps);
 /* frame count, integer arithmetic (parambase.cpp:16-19 without the float32 division) */
 int64_t mfx_host_frame_count(int64_t samples, int32_t window_size, int32_t shift);
 

@@ -104,6 +104,18 @@ int main()
                 ++nr;
             }
         }
-    std::printf("tables_asan: %d configurations, %d front-end tables, %d run lists clean\n", n, nt, nr);
+    // operands of k_splice_affine: exactly-sized input and output buffers at the corners of the limits
+    int nx = 0;
+    for (int od : {1, 15, 16, 17, 40, 256})
+        for (int id : {1, 3, 4, 39, 351, 8192}) {
+            std::vector<float> A((size_t)od * id, 1.f), ops((size_t)((id + 3) / 4) * ((od + 15) / 16) * 64);
+            int tiles = 0, steps = 0;
+            mfx::build_xform_operands(A.data(), od, id, tiles, steps, ops.data());
+            double sum = 0;
+            for (float v : ops) sum += v;
+            if ((size_t)steps * tiles * 64 != ops.size() || sum != (double)od * id) return 1;
+            ++nx;
+        }
+    std::printf("tables_asan: %d configurations, %d front-end tables, %d run lists, %d transform operand sets clean\n", n, nt, nr, nx);
     return 0;
 }
