@@ -31,6 +31,7 @@ from .mfcc import (  # noqa: F401
     host_mel_lane_plan,
     host_mel_table,
     host_plp_tables,
+    host_session_step,
     host_traps_basis,
     host_xform_operands,
     KERNEL_TABLE,

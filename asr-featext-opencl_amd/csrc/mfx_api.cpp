@@ -174,11 +174,14 @@ int refresh_mel(mfx_handle *h)
     return MFX_OK;
 }
 
-void fill_front(const mfx_handle *h, FrontParams &p)
+void fill_front(const mfx_handle *h, FrontParams &p) { fill_front(h, p, h->batch.aligned); }
+
+// (aligned: every chunk of the launch starts on an even sample -- the batch plan's flag, or the session slots' layout)
+void fill_front(const mfx_handle *h, FrontParams &p, bool aligned)
 {
     std::memset(&p, 0, sizeof(p));
     p.channels = h->channels;
-    p.pair_ok = (h->channels == 1 && (h->S % 2) == 0 && (h->W % 2) == 0 && h->batch.aligned) ? 1 : 0;
+    p.pair_ok = (h->channels == 1 && (h->S % 2) == 0 && (h->W % 2) == 0 && aligned) ? 1 : 0;
     p.window_size = h->W;
     p.shift = h->S;
     p.fft_size = h->W2;
@@ -692,21 +695,23 @@ extern "C" int mfx_profile_read(mfx_handle *h, int32_t *launches, double *kernel
 // through planning handles).  Order of preference: the three register kernels (4 frames per wave at 512 points and the
 // short-window 1024-point case, 2 frames per wave at 2048 points), then the fused one-wave-per-frame kernels while their LDS
 // fits (<= 2048 points), then spectrum through an HBM slab + k_melcep.
-FrontKind choose_front(const mfx_handle *h)
+FrontKind choose_front(const mfx_handle *h) { return choose_front(h, h->batch.aligned); }
+
+FrontKind choose_front(const mfx_handle *h, bool aligned)
 {
     // (else: the streaming interface's kernels; PLP has no fused front end: spectrum through HBM, then k_plp.  TRAPS takes
     // whatever the fbank handle of its shape takes: its front end IS that handle's, k_traps follows it)
     const bool allow_fused = !(h->cfg.engine & MFX_ENGINE_STREAM_KERNELS) && !h->plp;
     if (allow_fused && h->fast512 && h->fused_ok) return kFront512;
     // (k_front1024, windows longer than 512 samples: aligned frames only)
-    if (allow_fused && h->fast1024 && h->fused_ok && (h->W <= 512 || h->batch.aligned)) return kFront1024;
+    if (allow_fused && h->fast1024 && h->fused_ok && (h->W <= 512 || aligned)) return kFront1024;
     // (2048 points, any window: stereo, mono on aligned sample pairs, mono at any alignment -- three builds)
     if (allow_fused && h->fast2048 && h->wplan32_ok) return kFront2048;
     // (up to 2048 points the fused form saves the spectrum's round trip through HBM -- 8 KB per frame at 2048 points; at 4096
     // points the tables + per-wave buffers no longer leave enough waves per CU)
     if (allow_fused && h->W2 <= 2048 && h->wplan_ok) {
         FrontParams probe;
-        fill_front(h, probe);
+        fill_front(h, probe, aligned);
         if (front_wave_lds_bytes(probe, true) <= kLdsCap) return kFrontGenFused;
     }
     return h->fast512 ? kSpec512 : kSpecGen;

@@ -3,6 +3,7 @@
 //   mfx_api.cpp    lifetime, tables, kernel choice, profiling, test taps   (writes the shared part of the handle)
 //   mfx_stream.cpp the streaming state machine and its host copies         (owns `st` and `sweep`)
 //   mfx_batch.cpp  the batch planner and runner, the fused-delta plan      (owns `batch` and `fuse`)
+//   mfx_sessions_host.cpp the session entries: many live streams per push       (owns `sess`)
 #pragma once
 #include "../../include/mfx.h"
 
@@ -193,6 +194,49 @@ struct FuseState {
     DevBuf<mfx::DeltaTile> d_tiles;
 };
 
+// session entries (mfx_sessions_*): per-session carry state in two slot arrays, the pending push: mfx_sessions_host.cpp
+struct SessState {
+    int32_t n = 0, max_push = 0;         // sessions; samples per channel one push may bring a session (n == 0: not created)
+    int64_t pcm_stride = 0;              // samples per channel of a slot's PCM part (a multiple of 8)
+    int32_t frames_max = 0;              // frames one push can complete for one session
+    int32_t row_cap = 0, row_floats = 0; // a slot's statics part: rows (2 D carried + frames_max), floats per row
+    DevBuf<int16_t> d_pcm;               // [2][n][pcm_stride * channels] (+ slack for whole-word reads)
+    DevBuf<float> d_stat;                // [2][n][row_cap][row_floats]
+    DevBuf<float> d_slab;                // spectrum rows of the slab path (PLP, long transforms)
+    int64_t slab_rows = 0;
+    DevBuf<char> d_desc;                 // one push: descriptors | segments | chunks | row runs
+    PinnedBuf<char> h_stage[2];          // its staging, double buffered
+    hipEvent_t ev_stage[2] = {};         // recorded behind the upload that reads h_stage[i]
+    bool stage_used[2] = {false, false};
+    int stage_cur = 0;
+    size_t desc_bytes = 0;
+    DevBuf<int16_t> d_host_pcm;          // mfx_sessions_run_host: device copies of the caller's host buffers (grown on demand)
+    DevBuf<float> d_host_out;
+    struct Live {
+        int64_t n = 0, E = 0;            // samples received, rows delivered
+        int64_t f0 = 0;                  // frame whose statics are row 0 of the slot
+        int32_t tail_off = 0;            // samples from the slot's base to the first frame not yet computed
+        int32_t pitch = 0;               // floats per row the slot's statics were written with
+        int32_t parity = 0;              // which of the two slot arrays holds the state
+    };
+    std::vector<Live> live;
+    // the pending push (mfx_sessions_plan; mfx_sessions_run_* consumes it)
+    bool planned = false;
+    std::vector<int32_t> p_ids;
+    std::vector<int64_t> p_end;          // offsets[i] + lengths[i]: checked against the run's pcm_samples_total
+    std::vector<Live> p_next;            // state of p_ids[i] once the run has queued its launches
+    std::vector<uint8_t> p_seen;
+    std::vector<mfx::SessDesc> p_descs;
+    std::vector<mfx::Segment> p_segs;
+    std::vector<mfx::Chunk> p_chunks;    // ascending destination rows
+    std::vector<int64_t> p_runs;         // (first row, rows) of every descriptor's new frames, ascending
+    std::vector<int32_t> p_order;
+    std::vector<mfx::SessionStep> p_steps; // (the planner's work arrays: kept so that a plan allocates nothing once warm)
+    std::vector<int64_t> p_row_of;
+    int64_t p_total_rows = 0;
+    int p_tiles_max = 0;
+};
+
 // profiling of the dominant kernel
 struct ProfState {
     bool on = false;
@@ -272,6 +316,7 @@ struct mfx_handle {
     SweepState sweep;
     BatchState batch;
     FuseState fuse;
+    SessState sess;
     ProfState prof;
 
     // buffers of the handle go through these two: a planning handle records sizes and touches no device
@@ -299,7 +344,8 @@ struct mfx_handle {
             for (hipEvent_t e : events)
                 if (e) (void)hipEventDestroy(e);
         };
-        destroy(batch.ev_front), destroy(batch.ev_tail), destroy(batch.ev_up), destroy(batch.ev_run), destroy(st.ev_copy);
+        destroy(batch.ev_front), destroy(batch.ev_tail), destroy(batch.ev_up), destroy(batch.ev_run), destroy(st.ev_copy),
+            destroy(sess.ev_stage);
         for (hipStream_t s : {batch.stream2, batch.stream_up, batch.stream_dn})
             if (s) (void)hipStreamDestroy(s);
         if (own_stream && stream) (void)hipStreamDestroy(stream);
@@ -343,9 +389,11 @@ inline int fail_hip(mfx_handle *h, hipError_t e, const char *what)
 // Which front-end kernel the BATCH entries run for this handle (see choose_front's definition)
 enum FrontKind { kFront512, kFront1024, kFront2048, kFrontGenFused, kSpec512, kSpecGen };
 FrontKind choose_front(const mfx_handle *h);
+FrontKind choose_front(const mfx_handle *h, bool aligned); // (the session entries: their frames' alignment, not the batch plan's)
 // what batch_run_range launches: choose_front's kernel, or the spectrum form while per-utterance warp factors are in force
 FrontKind batch_front(const mfx_handle *h);
 void fill_front(const mfx_handle *h, mfx::FrontParams &p);
+void fill_front(const mfx_handle *h, mfx::FrontParams &p, bool aligned);
 void fill_traps(const mfx_handle *h, mfx::TrapsParams &p);
 // (mfx_batch.cpp) row width of the batch entries' output: out_dim while a transform is in force, else `width`
 int batch_out_width(const mfx_handle *h);

@@ -1,4 +1,4 @@
-// mfx_kernels.h -- launch interface of the gfx950 kernels (implemented in mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip, mfx_plp.hip, mfx_traps.hip, mfx_xform.hip: one translation unit per kernel family).
+// mfx_kernels.h -- launch interface of the gfx950 kernels (implemented in mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip, mfx_plp.hip, mfx_traps.hip, mfx_xform.hip, mfx_sessions.hip: one translation unit per kernel family).
 //
 // Kernel inventory and the reference stage each one replaces:
 //   spectrum512 / fused512   segmenter.cl kernelSegmentWindow + AppleFFT fft0 + mfcc.cl kernelTranspose
@@ -8,6 +8,8 @@
 //   plp                      PLP cepstra from a stored spectrum (no reference kernel: the reference names the method only)
 //   traps                    TRAPS temporal patterns from stored log mel rows (no reference kernel: the reference names the method only)
 //   splice_affine            frame splicing + affine transform of finished rows (no reference analogue: the last stage of a front end)
+//   sess_gather              carry state of the session entries: PCM tail + new samples + carried static rows into the current slot
+//                            (no reference analogue: the reference re-frames 2 D frames of context per block, segmentercpu.cpp:69-73)
 //   delta                    delta.cl kernelDelta x2 + the staging copies of mfccopencl.cpp:360-387
 //   norm_stats / norm_apply  norm.cl kernelSum + kernelFinalizeSum / kernelNormalize
 #pragma once
@@ -232,6 +234,36 @@ struct XformParams {
     int32_t ksteps;        // set by the launcher: steps of 4 taps per LDS chunk of the matrix
 };
 
+// k_sess_gather (mfx_sessions.hip): one push of one session ("Session entries").  The session's CURRENT slot is
+// written from three sources -- the PCM tail the previous slot carries, the caller's new samples, the static rows the
+// previous slot carries -- and from nowhere else: previous and current slot are different slots of the ping-pong pair.
+// PCM counts are int16 ELEMENTS (samples x channels).
+struct SessDesc {
+    int64_t carry_src;  // slot array: first element of the carried PCM tail (previous slot)
+    int64_t pcm_dst;    // slot array: first element of the current slot's PCM part (a multiple of 8: 16-byte words)
+    int64_t new_src;    // caller's array: first element of the new samples (any 2-byte alignment)
+    int32_t carry_n;    // elements carried
+    int32_t new_n;      // elements new
+    int64_t row_src;    // statics: first carried row in the previous slot (absolute row, times src_pitch)
+    int64_t row_dst;    // statics: first row of the current slot (absolute row, times SessGatherParams::stat_pitch)
+    int32_t n_rows;     // rows carried
+    int32_t src_pitch;  // floats per row the previous slot was written with
+};
+
+struct SessGatherParams {
+    const SessDesc *descs; // [n_descs]: blockIdx.y
+    int32_t n_descs;
+    int32_t narrow;        // nonzero: 2-byte loads throughout (the measurement's comparator; same bits)
+    const int16_t *pcm;    // the caller's array, 4-byte aligned
+    int64_t pcm_elems;     // its int16 elements
+    int16_t *slot_pcm;     // both slot arrays (read: previous slots, written: current slots)
+    int64_t slot_elems;
+    float *slot_stat;      // both statics slot arrays
+    int32_t stat_pitch;    // floats per row of the current slots
+    int32_t cols;          // static columns
+    int32_t items_max;     // set by the planner: the largest item count of any descriptor (sizes the grid)
+};
+
 struct DeltaParams {
     const float *src;      // static features, [rows][src_pitch]
     int32_t src_pitch;
@@ -284,6 +316,9 @@ hipError_t launch_traps(const TrapsParams &p, hipStream_t stream);
 size_t traps_lds_bytes(const TrapsParams &p, int tile_rows);
 int traps_tile_rows(const TrapsParams &p);
 hipError_t launch_xform(const XformParams &p, hipStream_t stream);
+hipError_t launch_sess_gather(const SessGatherParams &p, hipStream_t stream);
+// work items of one descriptor: 16-byte words of PCM, then 16-byte words (or single floats) of static rows
+int sess_gather_items(const SessDesc &d, int stat_pitch, int cols);
 // LDS of k_splice_affine with tile_rows output rows per block; xform_tile_rows: the tile the launcher takes (0: the shape is
 // outside the limits, or none fits); xform_shape_ok: width, context, in_dim and out_dim inside the kernel's limits
 size_t xform_lds_bytes(const XformParams &p, int tile_rows);

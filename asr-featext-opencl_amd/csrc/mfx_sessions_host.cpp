@@ -1,0 +1,413 @@
+// mfx_sessions_host.cpp -- the session entries of include/mfx.h: many open streams, each advanced by one chunk of samples per
+// push, all of them in one launch sequence (k_sess_gather -> front end -> delta).  DESIGN.md section 5, "Session entries".
+// This file owns the handle's `sess` part.  It reads the shared geometry and tables and names no field of `st`, `sweep`,
+// `batch` or `fuse`: a push leaves the streaming state and the batch plan, alpha list and transform as they are.
+#include "mfx_handle.h"
+
+#include <cstdint>
+#include <cstring>
+#include <numeric>
+
+using namespace mfx;
+
+namespace {
+
+constexpr int64_t kSessSlabRowsMax = 1 << 17; // rows of the spectrum slab (as the batch entries')
+
+int not_created(mfx_handle *h) { return fail(h, MFX_ERR_STATE, "mfx_sessions_create has not been called"); }
+
+// the slot arrays' frames lie on even samples exactly when the shift is even: slot bases and pcm_stride are even
+bool sess_aligned(const mfx_handle *h) { return (h->S % 2) == 0; }
+
+bool is_spec_kind(FrontKind k) { return k == kSpec512 || k == kSpecGen; }
+
+} // namespace
+
+extern "C" int mfx_sessions_create(mfx_handle *h, int32_t n_sessions, int32_t max_push_samples)
+{
+    MFX_DEVICE_ENTRY(h);
+    if (h->traps)
+        return fail(h, MFX_ERR_STATE, "the session entries do not serve TRAPS handles (their look-ahead is (L - 1) / 2 frames, not D)");
+    if (h->cfg.norm != MFX_NORM_NONE)
+        return fail(h, MFX_ERR_STATE,
+                    "the session entries do not serve normalisation (norm != MFX_NORM_NONE): statistics over an open stream are not built");
+    if (n_sessions < 0 || max_push_samples < 0 || (n_sessions == 0) != (max_push_samples == 0))
+        return fail(h, MFX_ERR_ARG, "n_sessions and max_push_samples must both be positive (or both 0: release)");
+    if (n_sessions > (1 << 20) || max_push_samples > (1 << 24)) return fail(h, MFX_ERR_ARG, "n_sessions or max_push_samples too large");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    SessState &ss = h->sess;
+    ss.n = 0;
+    ss.planned = false;
+    ss.live.clear();
+    ss.stage_used[0] = ss.stage_used[1] = false;
+    if (n_sessions == 0) {
+        ss.d_pcm.release(), ss.d_stat.release(), ss.d_slab.release(), ss.d_desc.release();
+        ss.d_host_pcm.release(), ss.d_host_out.release();
+        for (auto &b : ss.h_stage) {
+            if (b.p) (void)hipHostFree(b.p);
+            b.p = nullptr, b.n = 0;
+        }
+        ss.max_push = 0;
+        return MFX_OK;
+    }
+    int rc = refresh_mel(h); // (decides which front end the shape takes, and with it whether a spectrum slab is needed)
+    if (rc != MFX_OK) return rc;
+    const int ch = h->channels;
+    ss.max_push = max_push_samples;
+    ss.pcm_stride = ((int64_t)h->W + h->S + max_push_samples + 2 + 7) & ~(int64_t)7;
+    ss.frames_max = max_push_samples / h->S + 1;
+    ss.row_cap = 2 * h->D + ss.frames_max;
+    ss.row_floats = (std::max(16, h->width) + 3) & ~3;
+    const size_t pcm_elems = (size_t)2 * n_sessions * ss.pcm_stride * ch;
+    HIP_TRY(h, ss.d_pcm.alloc(pcm_elems + 8));
+    HIP_TRY(h, hipMemsetAsync(ss.d_pcm.p, 0, (pcm_elems + 8) * sizeof(int16_t), h->stream));
+    HIP_TRY(h, ss.d_stat.alloc((size_t)2 * n_sessions * ss.row_cap * ss.row_floats));
+    ss.slab_rows = 0;
+    ss.d_slab.release();
+    if (is_spec_kind(choose_front(h, sess_aligned(h)))) {
+        ss.slab_rows = std::min<int64_t>((int64_t)2 * n_sessions * ss.row_cap, kSessSlabRowsMax);
+        HIP_TRY(h, ss.d_slab.alloc((size_t)ss.slab_rows * h->spec_pitch));
+    }
+    const size_t chunks_max = (size_t)n_sessions * ((ss.frames_max + kChunkFrames - 1) / kChunkFrames);
+    ss.desc_bytes = (size_t)n_sessions * (sizeof(SessDesc) + sizeof(Segment) + 2 * sizeof(int64_t)) + chunks_max * sizeof(Chunk) + 64;
+    HIP_TRY(h, ss.d_desc.alloc(ss.desc_bytes));
+    for (int b = 0; b < 2; ++b) {
+        HIP_TRY(h, ss.h_stage[b].grow(ss.desc_bytes, ss.desc_bytes, h->stream));
+        if (!ss.ev_stage[b]) HIP_TRY(h, hipEventCreateWithFlags(&ss.ev_stage[b], hipEventDisableTiming));
+    }
+    ss.live.assign((size_t)n_sessions, SessState::Live{});
+    ss.p_seen.assign((size_t)n_sessions, 0);
+    ss.p_ids.reserve(n_sessions), ss.p_end.reserve(n_sessions), ss.p_next.reserve(n_sessions), ss.p_order.reserve(n_sessions);
+    ss.p_descs.reserve(n_sessions), ss.p_segs.reserve(n_sessions), ss.p_runs.reserve((size_t)2 * n_sessions);
+    ss.p_chunks.reserve(chunks_max);
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    ss.n = n_sessions;
+    return MFX_OK;
+}
+
+extern "C" int mfx_sessions_reset(mfx_handle *h, int32_t session)
+{
+    MFX_DEVICE_ENTRY(h);
+    SessState &ss = h->sess;
+    if (ss.n == 0) return not_created(h);
+    if (session < -1 || session >= ss.n) return fail(h, MFX_ERR_ARG, "session id outside [0, n_sessions)");
+    // (the slots themselves need no clearing: a fresh session carries nothing out of them)
+    for (int s = session < 0 ? 0 : session; s < (session < 0 ? ss.n : session + 1); ++s) {
+        const int parity = ss.live[s].parity;
+        ss.live[s] = SessState::Live{};
+        ss.live[s].parity = parity;
+    }
+    ss.planned = false; // (a pending push was planned on the state just dropped)
+    return MFX_OK;
+}
+
+extern "C" int64_t mfx_sessions_delivered(const mfx_handle *h, int32_t session)
+{
+    if (!h) return MFX_ERR_ARG;
+    if (h->sess.n == 0) return MFX_ERR_STATE;
+    if (session < 0 || session >= h->sess.n) return MFX_ERR_ARG;
+    return h->sess.live[session].E;
+}
+
+extern "C" int mfx_sessions_plan(mfx_handle *h, int32_t n, const int32_t *ids, const int64_t *offsets, const int64_t *lengths,
+                                 const int32_t *final_flags, int64_t *out_rows, int32_t *out_counts, int64_t *total_rows)
+{
+    MFX_DEVICE_ENTRY(h);
+    SessState &ss = h->sess;
+    if (ss.n == 0) return not_created(h);
+    if (n < 0 || (n > 0 && (!ids || !offsets || !lengths))) return fail(h, MFX_ERR_ARG, "invalid argument");
+    if (n > ss.n) return fail(h, MFX_ERR_ARG, "more pieces than sessions: an id is given twice or lies outside the range");
+    ss.planned = false;
+    // ---- checks first: nothing below them fails
+    int bad = MFX_OK;
+    const char *why = "";
+    int marked = 0;
+    for (; marked < n && bad == MFX_OK; ++marked) {
+        const int32_t id = ids[marked];
+        if (id < 0 || id >= ss.n) {
+            bad = MFX_ERR_ARG, why = "session id outside [0, n_sessions)";
+            break;
+        }
+        if (ss.p_seen[id]) {
+            bad = MFX_ERR_ARG, why = "session id given twice in one push";
+            break;
+        }
+        ss.p_seen[id] = 1;
+        if (offsets[marked] < 0 || lengths[marked] < 0)
+            bad = MFX_ERR_ARG, why = "negative offset or length";
+        else if (offsets[marked] > INT64_MAX / 4 - lengths[marked]) // (the end, times the channels, stays inside int64)
+            bad = MFX_ERR_ARG, why = "offset + length too large";
+        else if (lengths[marked] > ss.max_push)
+            bad = MFX_ERR_BUFFER_TOO_SMALL, why = "a session's piece is longer than max_push_samples (mfx_sessions_create)";
+        else if (frame_count(ss.live[id].n + lengths[marked], h->W, h->S) > 0x7fffffff)
+            bad = MFX_ERR_ARG, why = "stream too long";
+    }
+    for (int i = 0; i < n && i <= marked; ++i)
+        if (ids[i] >= 0 && ids[i] < ss.n) ss.p_seen[ids[i]] = 0;
+    if (bad != MFX_OK) return fail(h, bad, why);
+
+    // ---- pass 1, the caller's order: every session's step, the output rows
+    const int ch = h->channels, D = h->D;
+    ss.p_ids.assign(ids, ids + n);
+    ss.p_end.resize(n), ss.p_next.resize(n), ss.p_order.resize(n), ss.p_row_of.resize(n);
+    std::vector<SessionStep> &steps = ss.p_steps;
+    steps.resize(n);
+    int64_t row = 0;
+    for (int i = 0; i < n; ++i) {
+        SessState::Live nx = ss.live[ids[i]];
+        const bool fin = final_flags && final_flags[i] != 0;
+        (void)session_step(h->W, h->S, D, nx.n, nx.E, lengths[i], fin, steps[i]);
+        ss.p_end[i] = lengths[i] > 0 ? offsets[i] + lengths[i] : 0;
+        ss.p_next[i] = nx; // (n and E advanced; the slot fields follow in pass 2)
+        ss.p_row_of[i] = row;
+        if (out_rows) out_rows[i] = row;
+        if (out_counts) out_counts[i] = steps[i].n_out;
+        row += steps[i].n_out;
+    }
+    ss.p_total_rows = row;
+    if (total_rows) *total_rows = row;
+
+    // ---- pass 2, ascending slots (the slab path walks the chunk list in windows of rows): descriptors, chunks, segments
+    for (int i = 0; i < n; ++i) ss.p_order[i] = i;
+    auto slot_of = [&](int i) { return (int64_t)(ss.live[ids[i]].parity ^ 1) * ss.n + ids[i]; };
+    std::sort(ss.p_order.begin(), ss.p_order.end(), [&](int a, int b) { return slot_of(a) < slot_of(b); });
+    ss.p_descs.clear(), ss.p_segs.clear(), ss.p_chunks.clear(), ss.p_runs.clear();
+    ss.p_tiles_max = 0;
+    for (int k = 0; k < n; ++k) {
+        const int i = ss.p_order[k];
+        const SessionStep &st = steps[i];
+        const SessState::Live &cur = ss.live[ids[i]];
+        SessState::Live &nx = ss.p_next[i];
+        const bool fin = final_flags && final_flags[i] != 0;
+        // nothing to move, compute or deliver: an empty push of an open stream, the flush of a stream without samples
+        if (lengths[i] == 0 && (!fin || cur.n == 0)) continue;
+        const int64_t f0 = std::max<int64_t>(cur.E - D, 0);
+        const int64_t slot_prev = (int64_t)cur.parity * ss.n + ids[i], slot_cur = slot_of(i);
+        SessDesc d{};
+        d.carry_src = (slot_prev * ss.pcm_stride + cur.tail_off) * ch;
+        d.pcm_dst = slot_cur * ss.pcm_stride * ch;
+        d.new_src = offsets[i] * ch;
+        d.carry_n = (int32_t)(st.carry_samples * ch);
+        d.new_n = (int32_t)(lengths[i] * ch);
+        d.row_src = slot_prev * ss.row_cap + (f0 - cur.f0);
+        d.row_dst = slot_cur * ss.row_cap;
+        d.n_rows = st.carry_rows;
+        d.src_pitch = cur.pitch; // (0: nothing carried yet; the run fills in its own pitch)
+        ss.p_descs.push_back(d);
+        const int64_t new_row0 = d.row_dst + st.carry_rows;
+        for (int t0 = 0; t0 < st.new_frames; t0 += kChunkFrames) {
+            Chunk c;
+            c.pcm_off = slot_cur * ss.pcm_stride + (int64_t)t0 * h->S; // (the carried tail starts at the slot's base)
+            c.out_row = new_row0 + t0;
+            c.n_frames = std::min(kChunkFrames, st.new_frames - t0);
+            c.pad = 0;
+            ss.p_chunks.push_back(c);
+        }
+        if (st.new_frames > 0) ss.p_runs.push_back(new_row0), ss.p_runs.push_back(st.new_frames);
+        if (st.n_out > 0) {
+            Segment s{};
+            s.src_row0 = d.row_dst;
+            s.out_row0 = ss.p_row_of[i];
+            s.n_out = st.n_out;
+            s.shift = st.shift;
+            s.lo = st.lo;
+            s.hi = st.hi;
+            s.static_off = st.static_off;
+            ss.p_segs.push_back(s);
+            ss.p_tiles_max = std::max(ss.p_tiles_max, (st.n_out + 63) / 64);
+        }
+        nx.parity = cur.parity ^ 1;
+        nx.f0 = fin ? 0 : f0;
+        nx.tail_off = fin ? 0 : st.new_frames * h->S;
+        nx.pitch = fin ? 0 : -1; // (-1: the pitch of the run that writes the slot)
+    }
+    ss.planned = true;
+    return MFX_OK;
+}
+
+extern "C" int mfx_sessions_run_device(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_total, float *d_out)
+{
+    MFX_DEVICE_ENTRY(h);
+    SessState &ss = h->sess;
+    if (ss.n == 0) return not_created(h);
+    if (!ss.planned) return fail(h, MFX_ERR_STATE, "mfx_sessions_run: no push is planned (mfx_sessions_plan), or it has run already");
+    if (!h->have_window) return fail(h, MFX_ERR_STATE, "set_window has not been called");
+    const int n = (int)ss.p_ids.size();
+    bool any_new = false;
+    for (const SessDesc &d : ss.p_descs) any_new = any_new || d.new_n > 0;
+    if (pcm_samples_total < 0 || (any_new && !d_pcm) || (ss.p_total_rows > 0 && !d_out)) return fail(h, MFX_ERR_ARG, "invalid argument");
+    if (((uintptr_t)d_pcm & 3) != 0) return fail(h, MFX_ERR_ARG, "d_pcm must be 4-byte aligned");
+    for (int i = 0; i < n; ++i)
+        if (ss.p_end[i] > pcm_samples_total) return fail(h, MFX_ERR_ARG, "a session's piece extends past the end of the PCM array");
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = refresh_mel(h);
+    if (rc != MFX_OK) return rc;
+
+    // the front end of the shape, as the batch entries choose it, and the pitch batch_run_range gives the statics
+    const bool aligned = sess_aligned(h);
+    const FrontKind kind = choose_front(h, aligned);
+    FrontParams p;
+    fill_front(h, p, aligned);
+    const bool fused512 = kind == kFront512, fused1024 = kind == kFront1024, fused2048 = kind == kFront2048, fusedgen = kind == kFrontGenFused;
+    const bool compact = ((fused512 && p.dct_mode == 1) || fused1024 || fused2048 || fusedgen) && h->l1 > 0 && h->cols <= 16;
+    const int pitch = compact ? 16 : h->width;
+    if (is_spec_kind(kind) && ss.slab_rows == 0)
+        return fail(h, MFX_ERR_STATE, "the warp factor moved this shape to the spectrum path: call mfx_sessions_create again");
+
+    const size_t nd = ss.p_descs.size(), ns = ss.p_segs.size(), nc = ss.p_chunks.size(), nr = ss.p_runs.size() / 2;
+    if (nd > 0) {
+        int items_max = 0;
+        for (SessDesc &d : ss.p_descs) {
+            if (d.src_pitch <= 0) d.src_pitch = pitch;
+            items_max = std::max(items_max, sess_gather_items(d, pitch, h->cols));
+        }
+        // ---- one upload: descriptors | segments | chunks | row runs | run offsets
+        const size_t o_seg = nd * sizeof(SessDesc), o_chunk = o_seg + ns * sizeof(Segment), o_run = o_chunk + nc * sizeof(Chunk),
+                     o_off = o_run + nr * 2 * sizeof(int64_t), bytes = o_off + 2 * sizeof(int32_t);
+        if (bytes > ss.desc_bytes) return fail(h, MFX_ERR_STATE, "session descriptors outgrew their buffer");
+        const int b = ss.stage_cur;
+        if (ss.stage_used[b]) HIP_TRY(h, hipEventSynchronize(ss.ev_stage[b])); // (the upload before last read this buffer)
+        char *st = ss.h_stage[b].p;
+        std::memcpy(st, ss.p_descs.data(), o_seg);
+        if (ns) std::memcpy(st + o_seg, ss.p_segs.data(), ns * sizeof(Segment));
+        if (nc) std::memcpy(st + o_chunk, ss.p_chunks.data(), nc * sizeof(Chunk));
+        if (nr) std::memcpy(st + o_run, ss.p_runs.data(), nr * 2 * sizeof(int64_t));
+        const int32_t h_off[2] = {0, (int32_t)nr};
+        std::memcpy(st + o_off, h_off, sizeof(h_off));
+        HIP_TRY(h, hipMemcpyAsync(ss.d_desc.p, st, bytes, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipEventRecord(ss.ev_stage[b], h->stream));
+        ss.stage_used[b] = true;
+        ss.stage_cur = b ^ 1;
+        const SessDesc *d_descs = (const SessDesc *)ss.d_desc.p;
+        const Segment *d_segs = (const Segment *)(ss.d_desc.p + o_seg);
+        const Chunk *d_chunks = (const Chunk *)(ss.d_desc.p + o_chunk);
+
+        // ---- gather: carried PCM tail + new samples + carried static rows -> the current slots
+        SessGatherParams gp{};
+        gp.descs = d_descs;
+        gp.n_descs = (int32_t)nd;
+        gp.narrow = (h->cfg.engine & MFX_ENGINE_SESS_NARROW_LOADS) ? 1 : 0;
+        gp.pcm = d_pcm;
+        gp.pcm_elems = pcm_samples_total * h->channels;
+        gp.slot_pcm = ss.d_pcm.p;
+        gp.slot_elems = (int64_t)2 * ss.n * ss.pcm_stride * h->channels;
+        gp.slot_stat = ss.d_stat.p;
+        gp.stat_pitch = pitch;
+        gp.cols = h->cols;
+        gp.items_max = items_max;
+        HIP_TRY(h, launch_sess_gather(gp, h->stream));
+
+        // ---- front end over the push's chunks: statics straight to their rows of the current slots
+        if (nc > 0) {
+            p.pcm = ss.d_pcm.p;
+            p.pcm_total = gp.slot_elems;
+            p.chunks = d_chunks;
+            p.n_chunks = (int32_t)nc;
+            p.row_limit = (int64_t)2 * ss.n * ss.row_cap;
+            p.feat = ss.d_stat.p;
+            p.feat_pitch = pitch;
+            if (fused512) {
+                HIP_TRY(h, launch_front512(p, /*to_spectrum=*/false, aligned, h->nm16, h->stream));
+            } else if (fused1024) {
+                HIP_TRY(h, launch_front1024(p, aligned, h->nm16, h->stream, (h->cfg.engine & MFX_ENGINE_FRONT1024_12_WAVES) ? 12 : 16));
+            } else if (fused2048) {
+                HIP_TRY(h, launch_front2048(p, h->num_cus, h->stream));
+            } else if (fusedgen) {
+                HIP_TRY(h, launch_front_generic(p, /*fused=*/true, h->stream));
+            } else { // magnitudes through the slab in windows of rows, then k_melcep_runs / k_plp_runs on the new rows only
+                RowRuns rr;
+                rr.runs = (const int64_t *)(ss.d_desc.p + o_run);
+                rr.off = (const int32_t *)(ss.d_desc.p + o_off);
+                size_t c0 = 0;
+                while (c0 < nc) {
+                    const int64_t row0 = ss.p_chunks[c0].out_row;
+                    size_t c1 = c0;
+                    int64_t rows = 0;
+                    while (c1 < nc && ss.p_chunks[c1].out_row + ss.p_chunks[c1].n_frames - row0 <= ss.slab_rows) {
+                        rows = ss.p_chunks[c1].out_row + ss.p_chunks[c1].n_frames - row0;
+                        ++c1;
+                    }
+                    FrontParams q = p;
+                    q.chunks = d_chunks + c0;
+                    q.n_chunks = (int32_t)(c1 - c0);
+                    q.spec = ss.d_slab.p - row0 * (int64_t)h->spec_pitch; // rows are addressed absolutely
+                    q.spec_pitch = h->spec_pitch;
+                    if (h->fast512)
+                        HIP_TRY(h, launch_front512(q, /*to_spectrum=*/true, aligned, h->nm16, h->stream));
+                    else
+                        HIP_TRY(h, launch_front_generic(q, /*fused=*/false, h->stream));
+                    rr.row0 = row0;
+                    rr.rows = rows;
+                    rc = launch_cepstra_runs(h, h->own, q.spec, p.feat, p.feat_pitch, rr, h_off, ss.p_runs.data(), h->stream);
+                    if (rc != MFX_OK) return rc;
+                    c0 = c1;
+                }
+            }
+        }
+
+        // ---- delta: the rows every session's push completes, into the caller's array (l1 == 0: the copy form)
+        if (ns > 0) {
+            DeltaParams dp{};
+            dp.src = ss.d_stat.p;
+            dp.src_pitch = pitch;
+            dp.out = d_out;
+            dp.out_pitch = h->width;
+            dp.segs = d_segs;
+            dp.n_segs = (int32_t)ns;
+            dp.cols = h->cols;
+            dp.l1 = h->l1;
+            dp.l2 = h->l2;
+            dp.tiles_per_seg_max = ss.p_tiles_max;
+            HIP_TRY(h, launch_delta(dp, h->stream));
+        }
+    }
+    // ---- the launches are queued: commit
+    for (int i = 0; i < n; ++i) {
+        SessState::Live &lv = ss.live[ss.p_ids[i]];
+        lv = ss.p_next[i];
+        if (lv.pitch < 0) lv.pitch = pitch;
+    }
+    ss.planned = false;
+    return MFX_OK;
+}
+
+extern "C" int mfx_sessions_run_host(mfx_handle *h, const int16_t *pcm, int64_t pcm_samples_total, float *out)
+{
+    MFX_DEVICE_ENTRY(h);
+    SessState &ss = h->sess;
+    if (ss.n == 0) return not_created(h);
+    if (!ss.planned) return fail(h, MFX_ERR_STATE, "mfx_sessions_run: no push is planned (mfx_sessions_plan), or it has run already");
+    if (pcm_samples_total < 0 || (pcm_samples_total > 0 && !pcm) || (ss.p_total_rows > 0 && !out)) return fail(h, MFX_ERR_ARG, "invalid argument");
+    HIP_TRY(h, hipSetDevice(h->device));
+    // device copies of the caller's buffers, grown on demand (this entry may allocate; mfx_sessions_run_device never does)
+    const size_t n_in = (size_t)pcm_samples_total * h->channels, n_out = (size_t)ss.p_total_rows * h->width;
+    if (ss.d_host_pcm.n < n_in + 8 || ss.d_host_out.n < n_out + 4) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (ss.d_host_pcm.n < n_in + 8) HIP_TRY(h, ss.d_host_pcm.alloc(n_in + 8));
+        if (ss.d_host_out.n < n_out + 4) HIP_TRY(h, ss.d_host_out.alloc(n_out + 4));
+    }
+    if (n_in > 0) HIP_TRY(h, hipMemcpyAsync(ss.d_host_pcm.p, pcm, n_in * sizeof(int16_t), hipMemcpyHostToDevice, h->stream));
+    const int64_t rows = ss.p_total_rows;
+    const int rc = mfx_sessions_run_device(h, ss.d_host_pcm.p, pcm_samples_total, ss.d_host_out.p);
+    if (rc != MFX_OK) {
+        (void)hipStreamSynchronize(h->stream); // (nothing may still read `pcm` once we have returned)
+        return rc;
+    }
+    if (rows > 0) HIP_TRY(h, hipMemcpyAsync(out, ss.d_host_out.p, (size_t)rows * h->width * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return MFX_OK;
+}
+
+extern "C" int32_t mfx_host_session_step(int32_t window, int32_t shift, int32_t D, int64_t state[2], int64_t length, int32_t final_flag,
+                                         int64_t *carry_samples, int32_t *carry_rows, int32_t *new_frames, int32_t seg[5])
+{
+    if (window <= 0 || shift <= 0 || D < 0 || !state || state[0] < 0 || state[1] < 0 || length < 0) return MFX_ERR_ARG;
+    SessionStep st;
+    const int32_t n_out = session_step(window, shift, D, state[0], state[1], length, final_flag != 0, st);
+    if (carry_samples) *carry_samples = st.carry_samples;
+    if (carry_rows) *carry_rows = st.carry_rows;
+    if (new_frames) *new_frames = st.new_frames;
+    if (seg) seg[0] = st.n_out, seg[1] = st.shift, seg[2] = st.lo, seg[3] = st.hi, seg[4] = st.static_off;
+    return n_out;
+}

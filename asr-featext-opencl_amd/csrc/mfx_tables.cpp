@@ -29,6 +29,26 @@ int64_t frame_count(int64_t samples, int window_size, int shift)
     return q;
 }
 
+int32_t session_step(int window_size, int shift, int D, int64_t &n, int64_t &E, int64_t length, bool final_push, SessionStep &st)
+{
+    const int64_t T_old = std::max<int64_t>(frame_count(n, window_size, shift), 0);
+    const int64_t f0 = std::max<int64_t>(E - D, 0);
+    const int64_t n_new = n + length;
+    const int64_t T_new = std::max<int64_t>(frame_count(n_new, window_size, shift), 0);
+    const int64_t E_new = final_push ? T_new : std::max<int64_t>(T_new - D, 0);
+    st.carry_samples = n - T_old * shift;
+    st.carry_rows = (int32_t)(T_old - f0);
+    st.new_frames = (int32_t)(T_new - T_old);
+    st.n_out = (int32_t)(E_new - E);
+    st.static_off = (int32_t)(E - f0);
+    st.shift = st.static_off - D; // (row static_off - shift = D of the padded series is output row 0: k_delta's convention)
+    st.lo = 0;
+    st.hi = (int32_t)(T_new - 1 - f0); // (reached only by a final push: E_new + D <= T_new otherwise)
+    n = final_push ? 0 : n_new;
+    E = final_push ? 0 : E_new;
+    return st.n_out;
+}
+
 int estimated_window_count_f32(int samples, int window_size, int shift)
 {
     return (int)std::floor((float)(samples - (window_size - shift)) / (float)shift);

@@ -17,6 +17,20 @@ uint32_t ceil_pow2(uint32_t v);
 // expression is exact (samples < 2^24).
 int64_t frame_count(int64_t samples, int window_size, int shift);
 
+// One push of one session of the session entries ("Session entries"): a stream that has received n samples per
+// channel and delivered rows [0, E) takes `length` more.  T(n) = max(0, frame_count(n)); E = max(0, T - D) while the
+// stream is open, T once a push is final.  The previous slot carries the samples from the first frame not yet computed,
+// [T * S, n), and the static rows of frames [f0, T), f0 = max(0, E - D); the push computes frames [T_old, T_new) behind
+// them and delivers rows [E_old, E_new) through the delta Segment (n_out, shift, lo, hi, static_off), rows relative to
+// frame f0.  Returns n_out; n and E are advanced (both 0 after a final push: the session is fresh).
+struct SessionStep {
+    int64_t carry_samples; // samples per channel carried in
+    int32_t carry_rows;    // static rows carried in
+    int32_t new_frames;    // frames the push computes
+    int32_t n_out, shift, lo, hi, static_off;
+};
+int32_t session_step(int window_size, int shift, int D, int64_t &n, int64_t &E, int64_t length, bool final_push, SessionStep &st);
+
 // The reference's float32 version, bit-for-bit (used by the streaming state machine).
 int estimated_window_count_f32(int samples, int window_size, int shift);
 

@@ -72,6 +72,8 @@ EXPORTED_SYMBOLS = (
     "mfx_dominant_kernel_name", "mfx_debug_read", "mfx_plan_create", "mfx_plan_set_aligned",
     "mfx_host_mel_table", "mfx_host_dct_matrix", "mfx_host_frame_count",
     "mfx_method_supported", "mfx_host_plp_tables", "mfx_host_traps_basis",
+    "mfx_sessions_create", "mfx_sessions_reset", "mfx_sessions_plan", "mfx_sessions_run_device", "mfx_sessions_run_host",
+    "mfx_sessions_delivered", "mfx_host_session_step",
 )
 
 
@@ -147,6 +149,15 @@ def load_library():
     L.mfx_method_supported.argtypes = [i32]
     L.mfx_host_plp_tables.argtypes = [i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, i32, fp, fp]
     L.mfx_host_traps_basis.argtypes = [i32, i32, fp]
+    p32, p64 = C.POINTER(i32), C.POINTER(i64)
+    L.mfx_sessions_create.argtypes = [vp, i32, i32]
+    L.mfx_sessions_reset.argtypes = [vp, i32]
+    L.mfx_sessions_plan.argtypes = [vp, i32, p32, p64, p64, p32, p64, p32, p64]
+    L.mfx_sessions_run_device.argtypes = [vp, vp, i64, vp]
+    L.mfx_sessions_run_host.argtypes = [vp, sp, i64, fp]
+    L.mfx_sessions_delivered.argtypes, L.mfx_sessions_delivered.restype = [vp, i32], i64
+    L.mfx_host_session_step.argtypes = [i32, i32, i32, p64, i64, i32, p64, p32, p32, p32]
+    L.mfx_host_session_step.restype = i32
     _lib = L
     return L
 
@@ -288,6 +299,22 @@ def host_xform_operands(A):
     return out.reshape(st.value, tl.value, 64)
 
 
+def host_session_step(window_size, shift, D, state, length, final=False):
+    """One push of one session exactly as the planner of the session entries derives it (host code, no GPU needed).
+    state = (n, E): samples received and rows delivered so far.  Returns dict(rows, state, carry_samples, carry_rows,
+    new_frames, n_out, shift, lo, hi, static_off); state is (0, 0) after a final push."""
+    L = load_library()
+    st = (C.c_int64 * 2)(int(state[0]), int(state[1]))
+    cs, cr, nf = C.c_int64(0), C.c_int32(0), C.c_int32(0)
+    seg = (C.c_int32 * 5)()
+    rows = L.mfx_host_session_step(int(window_size), int(shift), int(D), st, int(length), int(bool(final)), C.byref(cs),
+                                   C.byref(cr), C.byref(nf), seg)
+    if rows < 0:
+        raise MfxError(int(rows), "mfx_host_session_step failed")
+    return dict(rows=int(rows), state=(int(st[0]), int(st[1])), carry_samples=cs.value, carry_rows=cr.value,
+                new_frames=nf.value, n_out=seg[0], shift=seg[1], lo=seg[2], hi=seg[3], static_off=seg[4])
+
+
 def host_frame_count(samples, window_size, shift):
     return int(load_library().mfx_host_frame_count(int(samples), int(window_size), int(shift)))
 
@@ -366,7 +393,7 @@ KERNEL_TABLE = (
 
 ENGINE_NO_FRONT1024, ENGINE_FUSE_DELTA, ENGINE_NO_FRONT2048, ENGINE_STREAM_KERNELS, ENGINE_NORM_TWO_KERNELS = 1, 2, 4, 8, 16
 ENGINE_DMA_SMALL_BLOCKS, ENGINE_NO_DCT_SPLIT, ENGINE_NO_STUFF256, ENGINE_FRONT1024_12_WAVES = 32, 64, 128, 256     # mfx_config.engine bits (include/mfx.h)
-ENGINE_TRAPS_VALU, ENGINE_XFORM_VALU = 512, 1024
+ENGINE_TRAPS_VALU, ENGINE_XFORM_VALU, ENGINE_SESS_NARROW_LOADS = 512, 1024, 2048
 
 
 class MfccHip:
@@ -563,6 +590,59 @@ class MfccHip:
     def batch_output_width(self):
         """Row width of the batch entries' output: out_dim while a transform is in force, else get_output_data_width()."""
         return self._L.mfx_batch_output_width(self._h)
+
+    # -- session entries ----------------------------------------------------------------------------
+    def sessions_create(self, n_sessions, max_push_samples):
+        """Size the session entries: n_sessions open streams, at most max_push_samples samples per channel per push and
+        session.  Drops all session state; (0, 0) releases everything."""
+        self._chk(self._L.mfx_sessions_create(self._h, int(n_sessions), int(max_push_samples)))
+        self._sess_total = 0
+
+    def sessions_reset(self, session=-1):
+        """Drop the carried state of one session (-1: of all), and any pending plan."""
+        self._chk(self._L.mfx_sessions_reset(self._h, int(session)))
+
+    def sessions_plan(self, ids, offsets, lengths, final=None):
+        """One push: session ids[i] receives samples [offsets[i], offsets[i] + lengths[i]) of the one PCM array of the run
+        (per channel); final[i] ends its stream.  Returns (out_rows, counts, total)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        ln = np.ascontiguousarray(lengths, dtype=np.int64)
+        assert ids.size == off.size == ln.size
+        fin = None if final is None else np.ascontiguousarray(final, dtype=np.int32)
+        assert fin is None or fin.size == ids.size
+        rows = np.zeros(ids.size, dtype=np.int64)
+        counts = np.zeros(ids.size, dtype=np.int32)
+        total = C.c_int64(0)
+        p32, p64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        self._chk(self._L.mfx_sessions_plan(self._h, ids.size, ids.ctypes.data_as(p32), off.ctypes.data_as(p64),
+                                            ln.ctypes.data_as(p64), None if fin is None else fin.ctypes.data_as(p32),
+                                            rows.ctypes.data_as(p64), counts.ctypes.data_as(p32), C.byref(total)))
+        self._sess_total = total.value
+        return rows, counts, total.value
+
+    def sessions_run_device(self, d_pcm_ptr, pcm_samples_total, d_out_ptr):
+        """Run the planned push on device pointers; asynchronous on the handle's stream."""
+        self._chk(self._L.mfx_sessions_run_device(self._h, C.c_void_p(int(d_pcm_ptr)), int(pcm_samples_total),
+                                                  C.c_void_p(int(d_out_ptr))))
+
+    def sessions_run_host(self, pcm):
+        """Run the planned push from / to host arrays; returns its rows [total][get_output_data_width()]."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.int16)
+        total = pcm.size // max(self.cfg.channels, 1)
+        out = np.zeros((getattr(self, "_sess_total", 0), self.get_output_data_width()), dtype=np.float32)
+        self._chk(self._L.mfx_sessions_run_host(self._h, pcm.ctypes.data_as(C.POINTER(C.c_int16)), total,
+                                                out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def sessions_delivered(self, session):
+        """Rows the session has delivered since it was opened (0 for a fresh one)."""
+        n = int(self._L.mfx_sessions_delivered(self._h, int(session)))
+        if n < 0:
+            raise MfxError(n, self._L.mfx_status_string(n).decode())
+        return n
+
+    host_session_step = staticmethod(host_session_step)
 
     def batch_overlap(self, enable=True):
         """Let the delta tail of a batch overlap the next batch's front end (results complete after synchronize())."""

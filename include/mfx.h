@@ -130,6 +130,10 @@ enum { MFX_METHOD_MFCC = 0, MFX_METHOD_PLP = 1, MFX_METHOD_TRAPS = 3 };
 #define MFX_ENGINE_XFORM_VALU 1024       /* splice + affine transform (mfx_batch_set_transform): the FMA chains on the vector
                                            ALUs instead of the matrix pipe (the same chain per output: the same bits)     */
 
+#define MFX_ENGINE_SESS_NARROW_LOADS 2048 /* session entries: k_sess_gather reads its sources with 2-byte loads throughout instead
+                                            of whole 32-bit words and a byte-align step (the same bits; the comparator of
+                                            the measurement in DESIGN.md, "Session entries")                             */
+
 #define MFX_ENGINE_FRONT1024_12_WAVES 256 /* 1024-point fused kernel: the 12-waves-per-CU build also where the 16-wave build fits
                                             (aligned frames, window <= 512 samples, tables small enough): the same bits      */
 
@@ -274,6 +278,47 @@ int mfx_batch_overlap(mfx_handle *h, int enable);
 /* Convenience: same, from/to HOST buffers (pinned staging + H2D, run, D2H, synchronises). */
 int mfx_batch_run_host(mfx_handle *h, const int16_t *pcm, int64_t pcm_samples_total, float *out);
 
+/* ---- session entries: many OPEN streams, each advanced by one piece of samples per push, all in one launch sequence
+ *      ("Session entries").  No reference analogue: its thread loop is sequential (ASR_OCL.cpp:365-366). ----
+ *
+ * A handle owns up to n_sessions sessions, numbered 0 .. n_sessions-1; a session is one open stream.  Let n be the samples
+ * (per channel) a session has received since it was opened, T(n) = mfx_batch_frames(h, n) and D = delta_l1 + delta_l2 (0
+ * with dyn = NONE).  After every push the session has delivered rows [0, E) of its utterance:
+ *   E = max(0, T(n) - D) while the stream is open;
+ *   E = T(n)             once a push is marked final (it may carry zero new samples: the flush).
+ * The E_new - E_old rows a push delivers are THE SAME BITS that mfx_batch_run_device writes for that utterance as a whole
+ * (planned at an even offset) on a handle of the same configuration and mfx_set_alpha, however the stream was cut into
+ * pushes: shorter than a hop, completing no frame, empty, one sample, at odd offsets of the caller's array.  First- and
+ * last-frame replication happens at the true start and end of the stream only (mfcccpu.cpp:243-254).  After a final push
+ * the session is fresh and its id may be reused at once.  Every frame's static row is computed ONCE: a session carries
+ * static rows (at most 2 D) and fewer than window + shift samples, never PCM context to re-transform.
+ *
+ * mfx_sessions_create sizes everything (two slot arrays, descriptor buffers, pinned descriptor staging) for n_sessions
+ * sessions and pieces of at most max_push_samples samples per channel; called again it re-sizes after a synchronise and
+ * drops all state; (0, 0) releases everything.  mfx_sessions_reset drops the carried state of one session (-1: of all) and
+ * any pending plan.  mfx_sessions_plan describes one push as mfx_batch_plan describes a batch: session ids[i] receives
+ * samples [offsets[i], offsets[i] + lengths[i]) of the caller's ONE PCM array (per channel; interleaved for channels = 2),
+ * final_flags[i] != 0 ends its stream (NULL: none final); out_counts[i] rows will be delivered to rows out_rows[i] ..
+ * (prefix sum) of d_out [total_rows][mfx_get_output_data_width].  A plan changes no session state; a second plan replaces
+ * the first.  mfx_sessions_run_device queues gather -> front end -> delta on the handle's stream, asynchronously, allocates
+ * nothing, and commits the sessions' state once its launches are queued; without a pending plan, or twice for one plan, it
+ * returns MFX_ERR_STATE.  mfx_sessions_run_host is the same from / to host buffers (it synchronises, and may grow its
+ * device copies).  mfx_sessions_delivered: E so far (0 for a fresh session).
+ * Errors: MFX_ERR_ARG an id outside the range or twice in one push, a negative length or offset, a piece past
+ * pcm_samples_total, a misaligned d_pcm (the 4-byte rule of mfx_batch_run_device); MFX_ERR_BUFFER_TOO_SMALL lengths[i] >
+ * max_push_samples; MFX_ERR_STATE no mfx_set_window yet, no mfx_sessions_create yet, a TRAPS handle, a handle with norm !=
+ * MFX_NORM_NONE (the session entries do not serve them); MFX_ERR_DEVICE a planning handle.
+ * The handle's mfx_set_alpha factor applies to all sessions.  NOT applied to session runs: mfx_batch_set_alphas,
+ * mfx_batch_set_transform, mfx_batch_overlap, MFX_ENGINE_FUSE_DELTA.  A push leaves the batch plan (with its alpha list and
+ * transform) and the streaming state of the same handle untouched, and they leave the sessions untouched. */
+int mfx_sessions_create(mfx_handle *h, int32_t n_sessions, int32_t max_push_samples);
+int mfx_sessions_reset(mfx_handle *h, int32_t session);
+int mfx_sessions_plan(mfx_handle *h, int32_t n, const int32_t *ids, const int64_t *offsets, const int64_t *lengths,
+                      const int32_t *final_flags, int64_t *out_rows, int32_t *out_counts, int64_t *total_rows);
+int mfx_sessions_run_device(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_total, float *d_out);
+int mfx_sessions_run_host(mfx_handle *h, const int16_t *pcm, int64_t pcm_samples_total, float *out);
+int64_t mfx_sessions_delivered(const mfx_handle *h, int32_t session);
+
 /* Page-locked host memory for the caller's PCM / feature buffers (mfx_batch_run_host and the streaming entries DMA
  * straight from / to such buffers; pageable ones go through the handle's staging).  NULL on failure. */
 void *mfx_alloc_pinned(size_t bytes);
@@ -339,6 +384,12 @@ int64_t mfx_host_alpha_runs(int32_t n_utt, const float *alphas, const int64_t *f
  * Returns steps * tiles * 64 (out may be NULL to query).  Test / inspection aid. */
 int64_t mfx_host_xform_operands(int32_t out_dim, int32_t in_dim, const float *A, float *out, int64_t out_cap, int32_t *tiles,
                                 int32_t *steps);
+/* One push of one session of the session entries as the planner derives it: state = {n, E} in / out (both 0 after a final
+ * push: the session is fresh); returns the rows delivered.  Also reports the carried PCM samples (per channel) and carried
+ * static rows going in, the frames the push computes, and the delta Segment fields seg = {n_out, shift, lo, hi,
+ * static_off}, rows relative to the first carried frame max(0, E_old - D).  Any output may be NULL.  Test / inspection aid. */
+int32_t mfx_host_session_step(int32_t window, int32_t shift, int32_t D, int64_t state[2], int64_t length, int32_t final_flag,
+                              int64_t *carry_samples, int32_t *carry_rows, int32_t *new_frames, int32_t seg[5]);
 /* frame count, integer arithmetic (parambase.cpp:16-19 without the float32 division) */
 int64_t mfx_host_frame_count(int64_t samples, int32_t window_size, int32_t shift);
 

@@ -116,6 +116,29 @@ int main()
             if ((size_t)steps * tiles * 64 != ops.size() || sum != (double)od * id) return 1;
             ++nx;
         }
-    std::printf("tables_asan: %d configurations, %d front-end tables, %d run lists, %d transform operand sets clean\n", n, nt, nr, nx);
+    // session entries: push sequences through the planner's step (empty, one-sample, sub-hop and long pushes; the flush as
+    // a zero-sample final push): the rows delivered add up to the utterance's frames and the carry stays inside a slot
+    int nq = 0;
+    for (int W : {200, 400, 1102, 2048})
+        for (int S : {80, 160, 441, 512})
+            for (int D : {0, 2, 6, 20}) {
+                if (S > W) continue;
+                const int64_t pushes[] = {0, 1, S - 1, S, W - 1, W, 3000, 0, 7, 2 * W + 3, 1, 0};
+                int64_t n = 0, E = 0, total = 0, rows = 0;
+                const int count = (int)(sizeof(pushes) / sizeof(pushes[0]));
+                for (int k = 0; k < count; ++k) {
+                    mfx::SessionStep st;
+                    total += pushes[k];
+                    rows += mfx::session_step(W, S, D, n, E, pushes[k], k + 1 == count, st);
+                    if (st.carry_samples < 0 || st.carry_samples >= W + S || st.carry_rows < 0 || st.carry_rows > 2 * D ||
+                        st.static_off - st.shift != D || st.n_out < 0)
+                        return 1;
+                }
+                const int64_t T = mfx::frame_count(total, W, S);
+                if (rows != (T > 0 ? T : 0) || n != 0 || E != 0) return 1;
+                ++nq;
+            }
+    std::printf("tables_asan: %d configurations, %d front-end tables, %d run lists, %d transform operand sets, %d session push sequences clean\n",
+                n, nt, nr, nx, nq);
     return 0;
 }
