@@ -825,6 +825,11 @@ extern "C" int64_t mfx_debug_read(mfx_handle *h, int kind, void *dst, int64_t ds
         src = h->st.d_plp_r.p;
         count = h->plp ? (int64_t)h->st.block_wcnd * (h->lpc + 1) : 0;
         break;
+    case 8: // converted PCM of the last batch run under a rates plan: int16, scratch layout (mfx_batch_resample_layout)
+        src = h->batch.d_rs_pcm.p;
+        count = h->batch.rs_on ? h->batch.rs_total * h->channels : 0;
+        esz = 2;
+        break;
     default:
         return MFX_ERR_ARG;
     }
@@ -973,4 +978,49 @@ extern "C" int64_t mfx_host_frame_count(int64_t samples, int32_t window_size, in
 {
     if (window_size <= 0 || shift <= 0) return MFX_ERR_ARG;
     return frame_count(samples, window_size, shift);
+}
+
+// Sample-rate conversion: the table as mfx_batch_plan_rates uploads it, [L][P]; returns L * P (taps may be NULL to query)
+extern "C" int64_t mfx_host_resample_taps(int32_t in_hz, int32_t out_hz, int32_t zeros, float rolloff, float *taps, int64_t cap,
+                                          int32_t *L, int32_t *M, int32_t *P)
+{
+    ResampleShape sh;
+    if (resample_shape(in_hz, out_hz, zeros, rolloff, sh) != 0) return MFX_ERR_ARG;
+    const int64_t n = (int64_t)sh.L * sh.P;
+    if (L) *L = sh.L;
+    if (M) *M = sh.M;
+    if (P) *P = sh.P;
+    if (taps) {
+        if (n > cap) return MFX_ERR_ARG;
+        build_resample_taps(sh, taps);
+    }
+    return n;
+}
+
+extern "C" int64_t mfx_host_resampled_length(int64_t samples, int32_t in_hz, int32_t out_hz)
+{
+    if (samples < 0 || in_hz < 1000 || in_hz > 768000 || out_hz < 1000 || out_hz > 768000) return MFX_ERR_ARG;
+    return resampled_length(samples, in_hz, out_hz);
+}
+
+extern "C" int64_t mfx_host_resample_layout(int32_t n_utt, const int64_t *lengths, const int32_t *rates_hz, int32_t out_hz,
+                                            int64_t *offsets, int64_t *out_lengths)
+{
+    if (n_utt < 0 || (n_utt > 0 && (!lengths || !rates_hz)) || out_hz < 1000 || out_hz > 768000) return MFX_ERR_ARG;
+    const int64_t total = resample_layout(n_utt, lengths, rates_hz, out_hz, offsets, out_lengths);
+    return total < 0 ? MFX_ERR_ARG : total;
+}
+
+// Output samples per tile of k_resample for one rate pair (a multiple of 2; 4096 for in_hz == out_hz, whose samples are
+// copied).  Test / inspection aid: utterance lengths around a tile edge.
+extern "C" int32_t mfx_host_resample_tile(int32_t in_hz, int32_t out_hz, int32_t zeros, float rolloff, int32_t channels)
+{
+    if (channels < 0 || channels > 2) return MFX_ERR_ARG;
+    ResampleShape sh;
+    if (resample_shape(in_hz, out_hz, zeros, rolloff, sh) != 0) return MFX_ERR_ARG;
+    if (in_hz == out_hz) return kResCopyTile;
+    ResRate r{};
+    r.L = sh.L, r.M = sh.M, r.P = sh.P, r.Wh = sh.Wh;
+    resample_geometry(channels, r);
+    return r.tile_out;
 }

@@ -187,10 +187,31 @@ int size_static16(mfx_handle *h)
 
 } // namespace
 
+namespace {
+// mfx_batch_plan's work, on the layout the front ends will read: the caller's, or the converted PCM's (mfx_batch_plan_rates)
+int plan_batch(mfx_handle *h, int32_t n_utt, const int64_t *offsets, const int64_t *lengths, int64_t *out_rows, int64_t *total_rows);
+
+// the converter of a rates plan goes with the plan
+void drop_resampler(mfx_handle *h)
+{
+    h->batch.rs_on = false;
+    h->batch.d_rs_pcm.release(), h->batch.d_rs_taps.release(), h->batch.d_rs_rates.release(), h->batch.d_rs_tiles.release();
+}
+} // namespace
+
 extern "C" int mfx_batch_plan(mfx_handle *h, int32_t n_utt, const int64_t *offsets, const int64_t *lengths,
                               int64_t *out_rows, int64_t *total_rows)
 {
     MFX_DEVICE_ENTRY(h);
+    const int rc = plan_batch(h, n_utt, offsets, lengths, out_rows, total_rows);
+    // (refused arguments leave the previous plan, and its converter, as they were; otherwise plan_batch has waited for the stream)
+    if (rc == MFX_OK || !h->batch.planned) drop_resampler(h);
+    return rc;
+}
+
+namespace {
+int plan_batch(mfx_handle *h, int32_t n_utt, const int64_t *offsets, const int64_t *lengths, int64_t *out_rows, int64_t *total_rows)
+{
     if (n_utt < 0 || (n_utt > 0 && (!offsets || !lengths))) return fail(h, MFX_ERR_ARG, "invalid argument");
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -300,6 +321,115 @@ extern "C" int mfx_batch_plan(mfx_handle *h, int32_t n_utt, const int64_t *offse
     rcf = size_static16(h);
     h->batch.planned = rcf == MFX_OK;
     return rcf;
+}
+} // namespace
+
+// ------------------------------------------------------------------------------------------------
+// sample-rate conversion in front of the batch ("Sample-rate conversion")
+// ------------------------------------------------------------------------------------------------
+
+extern "C" int mfx_batch_plan_rates(mfx_handle *h, int32_t n_utt, const int64_t *offsets, const int64_t *lengths, const int32_t *rates_hz,
+                                    int32_t zeros, float rolloff, int64_t *out_rows, int64_t *total_rows)
+{
+    MFX_DEVICE_ENTRY(h);
+    if (n_utt < 0 || (n_utt > 0 && (!offsets || !lengths || !rates_hz))) return fail(h, MFX_ERR_ARG, "invalid argument");
+    // (the range first: a float outside int32 must not reach the cast)
+    if (!(h->cfg.sample_rate >= 1000.f && h->cfg.sample_rate <= 768000.f))
+        return fail(h, MFX_ERR_ARG, "sample rates must lie in 1000 .. 768000 Hz");
+    const int32_t out_hz = (int32_t)h->cfg.sample_rate;
+    if ((float)out_hz != h->cfg.sample_rate) return fail(h, MFX_ERR_CONFIG, "mfx_batch_plan_rates: sample_rate is not an integral number of Hz");
+    // the distinct input rates, in order of first appearance: one table each (none for the output rate itself)
+    std::vector<int32_t> distinct;
+    std::vector<int32_t> rate_of((size_t)n_utt);
+    for (int u = 0; u < n_utt; ++u) {
+        if (offsets[u] < 0 || lengths[u] < 0) return fail(h, MFX_ERR_ARG, "negative utterance offset/length");
+        if (rates_hz[u] < 1000 || rates_hz[u] > 768000) return fail(h, MFX_ERR_ARG, "sample rates must lie in 1000 .. 768000 Hz");
+        size_t k = 0;
+        while (k < distinct.size() && distinct[k] != rates_hz[u]) ++k;
+        if (k == distinct.size()) {
+            if (distinct.size() == 16) return fail(h, MFX_ERR_ARG, "more than 16 distinct input rates in one plan");
+            distinct.push_back(rates_hz[u]);
+        }
+        rate_of[u] = (int32_t)k;
+    }
+    std::vector<ResRate> rates(distinct.size());
+    std::vector<float> taps;
+    int32_t taps_floats = 0, x_floats = 8, out_elems = 2;
+    for (size_t k = 0; k < distinct.size(); ++k) {
+        ResRate &r = rates[k];
+        r = ResRate{};
+        if (distinct[k] == out_hz) continue; // (tile_out == 0 marks the copy)
+        ResampleShape sh;
+        static const char *const why[] = {"", "sample rates must lie in 1000 .. 768000 Hz", "zeros must be 1 .. 64 (0 = 6)",
+                                          "rolloff must lie in (0, 1] (0 = 0.99)", "L = out_hz / gcd is larger than 4096",
+                                          "the filter has more than 4096 taps per phase", "the tap table L x P is larger than 2^20 floats"};
+        if (const int e = resample_shape(distinct[k], out_hz, zeros, rolloff, sh); e != 0) return fail(h, MFX_ERR_ARG, why[-e]);
+        r.taps_off = (int64_t)taps.size();
+        r.L = sh.L, r.M = sh.M, r.P = sh.P, r.Wh = sh.Wh;
+        taps.resize(taps.size() + (size_t)sh.L * sh.P);
+        build_resample_taps(sh, taps.data() + r.taps_off);
+        resample_geometry(h->channels, r);
+        if (r.in_lds) taps_floats = std::max(taps_floats, (r.L * (r.P + 1) + 3) & ~3);
+        x_floats = std::max(x_floats, resample_span_floats(r));
+        out_elems = std::max(out_elems, r.tile_out * h->channels);
+    }
+    std::vector<int64_t> sc_off((size_t)n_utt), sc_len((size_t)n_utt);
+    const int64_t sc_total = resample_layout(n_utt, lengths, rates_hz, out_hz, sc_off.data(), sc_len.data());
+    if (sc_total < 0) return fail(h, MFX_ERR_ARG, "invalid argument");
+    std::vector<ResTile> tiles;
+    std::vector<int32_t> tile0((size_t)n_utt + 1);
+    for (int u = 0; u < n_utt; ++u) {
+        tile0[u] = (int32_t)tiles.size();
+        const ResRate &r = rates[rate_of[u]];
+        const int64_t step = r.tile_out > 0 ? r.tile_out : kResCopyTile;
+        if ((sc_len[u] + step - 1) / step + (int64_t)tiles.size() > 0x7ffffff0) return fail(h, MFX_ERR_ARG, "batch too long");
+        for (int64_t j0 = 0; j0 < sc_len[u]; j0 += step) {
+            ResTile t{};
+            t.in_off = offsets[u], t.out_off = sc_off[u], t.n_in = lengths[u], t.n_out = sc_len[u], t.j0 = j0;
+            t.rate = r.tile_out > 0 ? rate_of[u] : -1;
+            tiles.push_back(t);
+        }
+    }
+    tile0[n_utt] = (int32_t)tiles.size();
+    ResampleParams probe{};
+    probe.channels = h->channels, probe.taps_floats = taps_floats, probe.x_floats = x_floats, probe.out_elems = out_elems;
+    if (resample_lds_bytes(probe) > kLdsCap) return fail(h, MFX_ERR_ARG, "no tile of k_resample fits the LDS for this shape");
+
+    int rc = plan_batch(h, n_utt, sc_off.data(), sc_len.data(), out_rows, total_rows); // (waits for the stream)
+    h->batch.rs_on = false;
+    if (rc != MFX_OK) return rc;
+    h->batch.planned = false;
+    if (taps.empty()) taps.assign(4, 0.f); // (every utterance at the output rate: keep the buffers non-null)
+    if (tiles.empty()) tiles.push_back(ResTile{});
+    HIP_TRY(h, h->upload(h->batch.d_rs_taps, taps));
+    HIP_TRY(h, h->upload(h->batch.d_rs_rates, rates));
+    HIP_TRY(h, h->upload(h->batch.d_rs_tiles, tiles));
+    // (allocated here so that mfx_batch_run_device itself never allocates; 8 elements of padding: the front ends read the
+    // 32-bit word that holds the last sample)
+    const size_t need = (size_t)sc_total * h->channels + 8;
+    if (h->batch.d_rs_pcm.n < need) {
+        HIP_TRY(h, h->batch.d_rs_pcm.alloc(need));
+        HIP_TRY(h, hipMemset(h->batch.d_rs_pcm.p, 0, need * sizeof(int16_t)));
+    }
+    h->batch.rs_in_off.assign(offsets, offsets + n_utt);
+    h->batch.rs_in_len.assign(lengths, lengths + n_utt);
+    h->batch.rs_utt_tile0.swap(tile0);
+    h->batch.rs_total = sc_total;
+    h->batch.rs_taps_floats = taps_floats, h->batch.rs_x_floats = x_floats, h->batch.rs_out_elems = out_elems;
+    h->batch.rs_on = true;
+    h->batch.planned = true;
+    return MFX_OK;
+}
+
+extern "C" int mfx_batch_resample_layout(const mfx_handle *h, int64_t *offsets, int64_t *lengths, int64_t *total)
+{
+    if (!h) return MFX_ERR_ARG;
+    if (h->planning) return fail(const_cast<mfx_handle *>(h), MFX_ERR_DEVICE, "planning handle (mfx_plan_create): no device behind it");
+    if (!h->batch.rs_on) return fail(const_cast<mfx_handle *>(h), MFX_ERR_STATE, "mfx_batch_resample_layout: no rates plan is in force");
+    if (offsets) std::copy(h->batch.utt_off.begin(), h->batch.utt_off.end(), offsets);
+    if (lengths) std::copy(h->batch.utt_len.begin(), h->batch.utt_len.end(), lengths);
+    if (total) *total = h->batch.rs_total;
+    return MFX_OK;
 }
 
 // rows of the spectrum slab of the batch entries' spectrum path
@@ -428,6 +558,28 @@ int batch_run_range(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_tot
     const bool whole = u0 == 0 && u1 == h->batch.n_utt;
     const int32_t rc0 = h->batch.utt_chunk0[u0], rc1 = h->batch.utt_chunk0[u1]; // chunk range of the utterance range
     if (!h->have_window) return fail(h, MFX_ERR_STATE, "set_window has not been called");
+    if (h->batch.rs_on) {
+        // A rates plan in force: the caller's array is converted into the handle's scratch by one launch over the tiles of
+        // the utterance range, and everything below runs as it always does on the scratch and its layout.
+        if (((uintptr_t)d_pcm & 3) != 0) return fail(h, MFX_ERR_ARG, "d_pcm must be 4-byte aligned");
+        for (int u = u0; u < u1; ++u)
+            if (h->batch.rs_in_off[u] + h->batch.rs_in_len[u] > pcm_samples_total)
+                return fail(h, MFX_ERR_ARG, "utterance extends past the end of the PCM array");
+        HIP_TRY(h, hipSetDevice(h->device));
+        const int32_t t0 = h->batch.rs_utt_tile0[u0], t1 = h->batch.rs_utt_tile0[u1];
+        ResampleParams rp{};
+        rp.pcm = d_pcm;
+        rp.out = h->batch.d_rs_pcm.p;
+        rp.tiles = h->batch.d_rs_tiles.p + t0;
+        rp.n_tiles = t1 - t0;
+        rp.rates = h->batch.d_rs_rates.p;
+        rp.taps = h->batch.d_rs_taps.p;
+        rp.channels = h->channels;
+        rp.taps_floats = h->batch.rs_taps_floats, rp.x_floats = h->batch.rs_x_floats, rp.out_elems = h->batch.rs_out_elems;
+        HIP_TRY(h, launch_resample(rp, h->stream));
+        d_pcm = h->batch.d_rs_pcm.p;
+        pcm_samples_total = h->batch.rs_total;
+    }
     if (h->batch.total_rows == 0) return MFX_OK;
     if (((uintptr_t)d_pcm & 3) != 0) return fail(h, MFX_ERR_ARG, "d_pcm must be 4-byte aligned");
     for (int u = u0; u < u1; ++u)
@@ -674,8 +826,11 @@ extern "C" int mfx_batch_run_host(mfx_handle *h, const int16_t *pcm, int64_t pcm
     // k + 1 and the download of slice k - 1 running beside the kernels of slice k on their own streams (PCIe is full
     // duplex: the 320 MB in and the 156 MB out of a C2 batch overlap instead of queueing up).  Utterance offsets must
     // ascend for a slice to be one contiguous piece of the PCM array; anything else takes the plain path below.
+    // (a rates plan in force: the caller's array is cut by its own layout, in input-rate samples)
+    const std::vector<int64_t> &in_off = h->batch.rs_on ? h->batch.rs_in_off : h->batch.utt_off;
+    const std::vector<int64_t> &in_len = h->batch.rs_on ? h->batch.rs_in_len : h->batch.utt_len;
     bool ascending = true;
-    for (int u = 1; u < h->batch.n_utt && ascending; ++u) ascending = h->batch.utt_off[u] >= h->batch.utt_off[u - 1] + h->batch.utt_len[u - 1];
+    for (int u = 1; u < h->batch.n_utt && ascending; ++u) ascending = in_off[u] >= in_off[u - 1] + in_len[u - 1];
     const int K = (int)std::min<int64_t>(8, h->batch.n_utt / 4);
     if (K >= 2 && ascending && !h->batch.overlap && !h->fuse.planned && n_in * sizeof(int16_t) >= ((size_t)32 << 20) &&
         is_pinned_host(pcm) && is_pinned_host(out)) {
@@ -691,15 +846,15 @@ extern "C" int mfx_batch_run_host(mfx_handle *h, const int16_t *pcm, int64_t pcm
         // every utterance inside the caller's array BEFORE the first copy is queued (batch_run_range only looks at the
         // slice it is given, and only after that slice's upload is in flight)
         for (int u = 0; u < h->batch.n_utt; ++u)
-            if (h->batch.utt_off[u] < 0 || h->batch.utt_off[u] + h->batch.utt_len[u] > pcm_samples_total)
+            if (in_off[u] < 0 || in_off[u] + in_len[u] > pcm_samples_total)
                 return fail(h, MFX_ERR_ARG, "utterance outside the PCM array");
         const int ch = h->channels;
         // one slice; an error leaves copies in flight on three streams, which slices_done drains before returning
         auto run_slice = [&](int k) -> int {
             const int u0 = (int)((int64_t)h->batch.n_utt * k / K), u1 = (int)((int64_t)h->batch.n_utt * (k + 1) / K);
             // samples [s0, s1) of the array hold the slice (s0 rounded down to an even sample: 4-byte aligned pieces)
-            const int64_t s0 = (k == 0 ? 0 : h->batch.utt_off[u0]) & ~(int64_t)1;
-            const int64_t s1 = std::min<int64_t>(k + 1 == K ? pcm_samples_total : h->batch.utt_off[u1], pcm_samples_total);
+            const int64_t s0 = (k == 0 ? 0 : in_off[u0]) & ~(int64_t)1;
+            const int64_t s1 = std::min<int64_t>(k + 1 == K ? pcm_samples_total : in_off[u1], pcm_samples_total);
             if (s1 > s0)
                 HIP_TRY(h, hipMemcpyAsync(h->batch.d_host_pcm.p + s0 * ch, pcm + s0 * ch, (size_t)(s1 - s0) * ch * sizeof(int16_t),
                                           hipMemcpyHostToDevice, h->batch.stream_up));

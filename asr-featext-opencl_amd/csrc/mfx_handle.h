@@ -180,6 +180,18 @@ struct BatchState {
     DevBuf<float> d_xf_ops, d_xf_bias;   // [n_xf][steps][tiles][64], [n_xf][tiles * 16]
     DevBuf<int32_t> d_xf_idx;            // [n_utt] transform of every utterance (empty: all 0)
     DevBuf<float> d_xf_y;                // [total_rows][width]
+    // sample-rate conversion (mfx_batch_plan_rates), tied to the plan: while rs_on the run converts the caller's array into
+    // d_rs_pcm with one launch of k_resample and then does what it always does on d_rs_pcm; utt_off / utt_len above describe
+    // the scratch, rs_in_off / rs_in_len the caller's array
+    bool rs_on = false;
+    std::vector<int64_t> rs_in_off, rs_in_len;
+    std::vector<int32_t> rs_utt_tile0;   // [n_utt + 1] first tile of every utterance (tiles are in utterance order)
+    int64_t rs_total = 0;                // samples per channel of the scratch (even)
+    int32_t rs_taps_floats = 0, rs_x_floats = 0, rs_out_elems = 0; // LDS parts of the launch: maxima over the plan's rates
+    DevBuf<int16_t> d_rs_pcm;            // [rs_total * channels + 8]
+    DevBuf<float> d_rs_taps;
+    DevBuf<mfx::ResRate> d_rs_rates;
+    DevBuf<mfx::ResTile> d_rs_tiles;
 };
 
 // fused delta stage of the 512-point kernel: per-block chunk lists (own rows + halo) and delta tiles: mfx_batch.cpp

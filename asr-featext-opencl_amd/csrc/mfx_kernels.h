@@ -1,4 +1,4 @@
-// mfx_kernels.h -- launch interface of the gfx950 kernels (implemented in mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip, mfx_plp.hip, mfx_traps.hip, mfx_xform.hip, mfx_sessions.hip: one translation unit per kernel family).
+// mfx_kernels.h -- launch interface of the gfx950 kernels (implemented in mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip, mfx_plp.hip, mfx_traps.hip, mfx_xform.hip, mfx_sessions.hip, mfx_resample.hip: one translation unit per kernel family).
 //
 // Kernel inventory and the reference stage each one replaces:
 //   spectrum512 / fused512   segmenter.cl kernelSegmentWindow + AppleFFT fft0 + mfcc.cl kernelTranspose
@@ -10,6 +10,8 @@
 //   splice_affine            frame splicing + affine transform of finished rows (no reference analogue: the last stage of a front end)
 //   sess_gather              carry state of the session entries: PCM tail + new samples + carried static rows into the current slot
 //                            (no reference analogue: the reference re-frames 2 D frames of context per block, segmentercpu.cpp:69-73)
+//   resample                 per-utterance sample-rate conversion of the batch entries' PCM (no reference analogue: the reference takes
+//                            its files at the one rate its model was trained at)
 //   delta                    delta.cl kernelDelta x2 + the staging copies of mfccopencl.cpp:360-387
 //   norm_stats / norm_apply  norm.cl kernelSum + kernelFinalizeSum / kernelNormalize
 #pragma once
@@ -264,6 +266,38 @@ struct SessGatherParams {
     int32_t items_max;     // set by the planner: the largest item count of any descriptor (sizes the grid)
 };
 
+// k_resample (mfx_resample.hip): per-utterance sample-rate conversion, int16 -> int16 ("Sample-rate conversion").
+// One ResRate per distinct input rate of the plan; one ResTile per run of at most tile_out output samples of one utterance.
+struct ResRate {
+    int64_t taps_off;   // first float of the rate's table [L][P] inside ResampleParams::taps
+    int32_t L, M, P, Wh;
+    int32_t R;          // same-phase outputs a work item carries (1, 2 or 4)
+    int32_t items;      // work items of a full tile; a multiple of L when R > 1: outputs w + r items, r < R, share a phase
+    int32_t tile_out;   // R * items, even
+    int32_t in_lds;     // the table is staged in LDS (row stride P + 1), else read through the caches
+};
+struct ResTile {
+    int64_t in_off;     // the utterance in the caller's array: first sample (per channel), any parity
+    int64_t out_off;    // the utterance in the scratch: first sample (per channel), even
+    int64_t n_in, n_out; // its samples per channel before and after
+    int64_t j0;         // first output sample of the tile (a multiple of the rate's tile_out: even)
+    int32_t rate;       // index into ResampleParams::rates; -1: same rate, the samples are copied
+    int32_t pad;
+};
+struct ResampleParams {
+    const int16_t *pcm; // the caller's array, 4-byte aligned
+    int16_t *out;       // the scratch
+    const ResTile *tiles;
+    const ResRate *rates;
+    const float *taps;
+    int32_t n_tiles;
+    int32_t channels;   // 1 or 2 (interleaved; each channel converted on its own)
+    int32_t taps_floats; // LDS floats of the table part (0: no rate of the plan stages its table)
+    int32_t x_floats;   // LDS floats per channel of the staged input span (a multiple of 8)
+    int32_t out_elems;  // LDS int16 elements of the output staging (even)
+};
+constexpr int kResCopyTile = 4096; // samples per channel of a tile of a same-rate utterance
+
 struct DeltaParams {
     const float *src;      // static features, [rows][src_pitch]
     int32_t src_pitch;
@@ -317,6 +351,12 @@ size_t traps_lds_bytes(const TrapsParams &p, int tile_rows);
 int traps_tile_rows(const TrapsParams &p);
 hipError_t launch_xform(const XformParams &p, hipStream_t stream);
 hipError_t launch_sess_gather(const SessGatherParams &p, hipStream_t stream);
+// k_resample: tile geometry of one rate (fills R, items, tile_out, in_lds from L, M, P), the LDS floats per channel its
+// input span needs, and the launch (taps_floats / x_floats / out_elems are the maxima over the plan's rates)
+void resample_geometry(int channels, ResRate &r);
+int resample_span_floats(const ResRate &r);
+size_t resample_lds_bytes(const ResampleParams &p);
+hipError_t launch_resample(const ResampleParams &p, hipStream_t stream);
 // work items of one descriptor: 16-byte words of PCM, then 16-byte words (or single floats) of static rows
 int sess_gather_items(const SessDesc &d, int stat_pitch, int cols);
 // LDS of k_splice_affine with tile_rows output rows per block; xform_tile_rows: the tile the launcher takes (0: the shape is

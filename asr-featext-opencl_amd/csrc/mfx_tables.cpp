@@ -604,4 +604,75 @@ void build_dct_transposed(const std::vector<float> &dct, int num_banks, int dct_
         for (int c = 0; c < dct_len; ++c) out[(size_t)c * stride + m] = dct[(size_t)m * dct_len + c];
 }
 
+// ------------------------------------------------------------------------------------------------
+// sample-rate conversion
+// ------------------------------------------------------------------------------------------------
+
+static int64_t gcd64(int64_t a, int64_t b)
+{
+    while (b) {
+        const int64_t t = a % b;
+        a = b;
+        b = t;
+    }
+    return a;
+}
+
+int resample_shape(int32_t in_hz, int32_t out_hz, int32_t zeros, float rolloff, ResampleShape &s)
+{
+    if (in_hz < 1000 || in_hz > 768000 || out_hz < 1000 || out_hz > 768000) return -1;
+    if (zeros == 0) zeros = 6;
+    if (zeros < 1 || zeros > 64) return -2;
+    const double ro = rolloff == 0.f ? 0.99 : (double)rolloff;
+    if (!(ro > 0.0 && ro <= 1.0)) return -3;
+    const int64_t g = gcd64(in_hz, out_hz);
+    const int64_t L = out_hz / g, M = in_hz / g;
+    if (L > 4096) return -4;
+    const double c = ro * std::min(1.0, (double)L / (double)M);
+    const double wh = std::ceil((double)zeros / c);
+    if (2.0 * wh > 4096.0) return -5;
+    const int64_t P = 2 * (int64_t)wh;
+    if (L * P > ((int64_t)1 << 20)) return -6;
+    s.L = (int32_t)L, s.M = (int32_t)M, s.P = (int32_t)P, s.Wh = (int32_t)wh, s.c = c;
+    return 0;
+}
+
+void build_resample_taps(const ResampleShape &s, float *taps)
+{
+    const double pi = 3.14159265358979323846;
+    for (int phi = 0; phi < s.L; ++phi)
+        for (int k = 0; k < s.P; ++k) {
+            const double t = (double)(k - s.Wh + 1) - (double)phi / (double)s.L;
+            double h = 0.0;
+            if (std::fabs(t) < (double)s.Wh) {
+                const double x = s.c * t;
+                const double sinc = x == 0.0 ? 1.0 : std::sin(pi * x) / (pi * x);
+                h = s.c * sinc * 0.5 * (1.0 + std::cos(pi * t / (double)s.Wh));
+            }
+            taps[(size_t)phi * s.P + k] = (float)h;
+        }
+}
+
+int64_t resampled_length(int64_t samples, int32_t in_hz, int32_t out_hz)
+{
+    if (samples <= 0) return 0;
+    const int64_t g = gcd64(in_hz, out_hz);
+    const int64_t L = out_hz / g, M = in_hz / g;
+    return (samples * L + M - 1) / M;
+}
+
+int64_t resample_layout(int32_t n_utt, const int64_t *lengths, const int32_t *rates_hz, int32_t out_hz, int64_t *offsets,
+                        int64_t *out_lengths)
+{
+    int64_t off = 0;
+    for (int u = 0; u < n_utt; ++u) {
+        if (lengths[u] < 0 || rates_hz[u] < 1000 || rates_hz[u] > 768000) return -1;
+        const int64_t n = resampled_length(lengths[u], rates_hz[u], out_hz);
+        if (offsets) offsets[u] = off;
+        if (out_lengths) out_lengths[u] = n;
+        off += (n + 1) & ~(int64_t)1;
+    }
+    return off;
+}
+
 } // namespace mfx

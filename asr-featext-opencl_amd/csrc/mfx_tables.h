@@ -127,6 +127,27 @@ void build_front1024_phase_o(const std::vector<float> &padded, int fft_size, std
 // kernel folds the frame's halves itself.
 void build_front1024_long_window(const std::vector<float> &padded, int fft_size, std::vector<float> &taps, std::vector<float> &tw);
 
+// Sample-rate conversion ("Sample-rate conversion"): in_hz -> out_hz by the rational factor L / M, L = out_hz / g,
+// M = in_hz / g, g = gcd.  Filter: Hann-windowed sinc, c = rolloff min(1, L / M), Wh = ceil(zeros / c), P = 2 Wh taps per
+// phase.  zeros == 0 means 6, rolloff == 0 means 0.99.  resample_shape returns 0, or a negative number naming the limit that
+// refuses the pair: -1 a rate outside 1000 .. 768000 Hz, -2 zeros outside 1 .. 64, -3 rolloff outside (0, 1], -4 L > 4096,
+// -5 P > 4096, -6 L P > 2^20.
+struct ResampleShape {
+    int32_t L = 1, M = 1, P = 0, Wh = 0;
+    double c = 0; // cutoff as a fraction of the input Nyquist band
+};
+int resample_shape(int32_t in_hz, int32_t out_hz, int32_t zeros, float rolloff, ResampleShape &s);
+// taps [L][P]: h[phi][k] = c sinc(c t) (1 + cos(pi t / Wh)) / 2 for |t| < Wh, else 0, t = (k - Wh + 1) - phi / L;
+// evaluated in double, rounded once to float.  No per-phase renormalisation.
+void build_resample_taps(const ResampleShape &s, float *taps);
+// ceil(samples L / M) in int64 arithmetic (samples >= 0 and samples L < 2^63; in_hz == out_hz: samples)
+int64_t resampled_length(int64_t samples, int32_t in_hz, int32_t out_hz);
+// the converted PCM's layout: utterance u holds resampled_length(lengths[u]) samples per channel from offsets[u]; starts are
+// even and ascend in utterance order with nothing between utterances but the one pad sample behind an odd length.  Returns
+// the total (even), or -1 on a negative length or a rate outside the limits.
+int64_t resample_layout(int32_t n_utt, const int64_t *lengths, const int32_t *rates_hz, int32_t out_hz, int64_t *offsets,
+                        int64_t *out_lengths);
+
 } // namespace mfx
 
 namespace mfx {

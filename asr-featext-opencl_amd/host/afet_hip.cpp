@@ -15,6 +15,10 @@
 // write the previous batch's rows.  The extractor is created with MFX_ENGINE_STREAM_KERNELS, so the rows are the same
 // bits the per-file loop delivers, and the reference's single-block flush behaviour (B1, --bug-compat) is applied to them:
 // the outputs are byte-identical to the per-file loop's (--batch-mb 0 selects that loop; tests compare the two).
+// --resample-to HZ extracts at HZ instead of the first file's rate: window and shift in samples follow HZ, and a file at
+// another rate is converted on the device -- inside its batch through mfx_batch_plan_rates, or as a batch of one where the
+// per-file loop would otherwise run (--batch-mb 0).  The reference has no rows for such a file (it refuses it), so its
+// single-block flush behaviour (B1) is not applied to converted files.  Without the option nothing changes.
 // --alpha-file gives every input file its own warp factor: the files of a batch then run with mfx_batch_set_alphas (one
 // launch sequence for all factors), files on the per-file loop with set_alpha of their own factor.
 #include <cmath>
@@ -55,6 +59,9 @@ struct Options {
     int batch_mb = 16;      // PCM per batch of files (0: the per-file loop only); small enough that a few thousand files pipeline
     int io_threads = 12;    // helper threads of a worker that read files and format / write rows of a batch
     std::vector<int> devices; // --devs a,b,...: one worker (own MfccHip, own thread) per entry
+    int resample_to = 0;    // --resample-to HZ: extract at HZ whatever the first file's rate; files at other rates are converted
+                            // on the device (mfx_batch_plan_rates).  0: the reference's rule -- every file at the first file's rate
+    int resample_zeros = 0; // --resample-zeros N: zero crossings of the conversion filter per side (0 = the library's 6)
 };
 
 struct Wav {
@@ -301,12 +308,53 @@ struct Scratch {
     std::vector<char> text;
 };
 
+// --resample-to, a file at another rate where the per-file loop runs: a batch of one through mfx_batch_plan_rates (the
+// streaming interface takes samples at the extractor's rate only).  One warp factor: the file's own or --alpha.
+void process_file_resampled(MfccHip &param, const Options &o, const Wav &w, const std::string &in, const std::string &out_name,
+                            float sample_rate, Scratch &sc, const float *own_alpha)
+{
+    if (!own_alpha && o.alpha_max - o.alpha_min >= o.alpha_step)
+        throw std::runtime_error("File \"" + in + "\" needs sample-rate conversion, which takes one warp factor, not a sweep");
+    std::vector<int16_t> &mono = sc.mono;
+    mono.assign(w.pcm.size() / w.channels + 2, 0); // (+ 2: the word that holds the last sample is inside the buffer)
+    const long long n = (long long)(w.pcm.size() / w.channels);
+    for (long long i = 0; i < n; ++i)
+        mono[i] = w.channels >= 2 ? (int16_t)(((int)w.pcm[i * w.channels] + (int)w.pcm[i * w.channels + 1]) >> 1)
+                                  : w.pcm[i * w.channels];
+    const int width = param.get_output_data_width();
+    const long long off = 0;
+    long long row0 = 0;
+    const long long total = param.batch_plan_rates(1, &off, &n, &w.sample_rate, o.resample_zeros, &row0);
+    param.set_warp(own_alpha ? *own_alpha : o.alpha_min); // (same-rate files of the loop set their own factor before apply)
+    std::vector<float> &rows = sc.rows;
+    if (rows.size() < (size_t)std::max<long long>(total, 1) * width) rows.resize((size_t)std::max<long long>(total, 1) * width);
+    param.batch_run_host(mono.data(), n + 1, rows.data());
+    const long double dt = o.bug_compat ? (long double)(o.shift_ms / sample_rate) : o.shift_ms / 1000.0L;
+    const long double t0 = o.bug_compat ? (long double)(0.5f * o.window_ms / sample_rate) : 0.5L * o.window_ms / 1000.0L;
+    FILE *fo = std::fopen(out_name.c_str(), o.htk ? "wb" : "w");
+    if (!fo) throw std::runtime_error("Can't create output file: " + out_name);
+    if (o.htk) {
+        write_htk_header(fo, (uint32_t)total, o, width);
+        write_rows_htk(fo, rows.data(), (int)total, width, sc.text);
+    } else {
+        write_rows(fo, rows.data(), (int)total, width, 0, t0, dt, sc.text, o.format_threads);
+    }
+    std::fclose(fo);
+    if (g_time.on) ++g_time.files;
+    static std::mutex print_lock;
+    std::lock_guard<std::mutex> g(print_lock);
+    std::printf("%s: %lld frames x %d\n", in.c_str(), total, width);
+}
+
 // own_alpha: the file's factor of --alpha-file (one output, no name suffix) instead of the --alpha options' loop
 void process_file(MfccHip &param, const Options &o, const Wav &w, const std::string &in, const std::string &out_name,
                   float sample_rate, Scratch &sc, const float *own_alpha = nullptr)
 {
-    if ((float)w.sample_rate != sample_rate)
-        throw std::runtime_error("File \"" + in + "\" has incorrect sample rate");
+    if ((float)w.sample_rate != sample_rate) {
+        if (o.resample_to <= 0) throw std::runtime_error("File \"" + in + "\" has incorrect sample rate");
+        process_file_resampled(param, o, w, in, out_name, sample_rate, sc, own_alpha);
+        return;
+    }
     // Multi-channel input: ONE policy across the product -- the downmix of the batch kernels (channels = 2 in the C
     // ABI: mono = (L + R) >> 1 in integer arithmetic), applied here on the host because the streaming
     // interface is mono like the reference's (which has no downmix at all: it reads `frames` shorts into a mono-sized
@@ -441,6 +489,8 @@ struct BatchItem {
     bool stream = false;        // not batchable: goes through the per-file loop
     Wav wav;                    // kept for the per-file loop
     long long off = 0, len = 0, row0 = 0, frames = 0;
+    int rate = 0;               // the file's own sample rate (--resample-to: may differ from the extractor's)
+    long long conv_len = 0;     // samples after conversion (= len at the extractor's rate)
 };
 
 struct Batch {
@@ -487,13 +537,23 @@ bool prepare_batch(Batch &b, const Options &o, const std::vector<std::string> &f
         BatchItem &it = b.items[k];
         try {
             it.wav = read_wav(files[2 * it.file]);
-            if ((float)it.wav.sample_rate != sr) throw std::runtime_error("File \"" + files[2 * it.file] + "\" has incorrect sample rate");
+            const bool other_rate = (float)it.wav.sample_rate != sr;
+            if (other_rate && o.resample_to <= 0)
+                throw std::runtime_error("File \"" + files[2 * it.file] + "\" has incorrect sample rate");
             const size_t n = it.wav.pcm.size() / it.wav.channels;
-            const long long T = n >= (size_t)W ? (long long)((n - (size_t)(W - S)) / (size_t)S) : 0;
+            it.rate = it.wav.sample_rate;
+            // (--resample-to: frames, block limit and context are counted in samples AFTER conversion)
+            const long long nc = other_rate ? (long long)mfx_host_resampled_length((int64_t)n, it.rate, o.resample_to) : (long long)n;
+            if (nc < 0) throw std::runtime_error("File \"" + files[2 * it.file] + "\": sample rate outside 1000 .. 768000 Hz");
+            it.conv_len = nc;
+            const long long T = nc >= W ? (nc - (W - S)) / S : 0;
             // the per-file loop keeps: files of more than one block, files too short for the deltas' context (the
             // reference refuses or mangles them: same messages from the same code), alpha sweeps
             // (TRAPS has no per-file loop: every file is one utterance of a batch, whatever its length)
-            it.stream = o.method != MFX_METHOD_TRAPS && (sweep || n > (size_t)limit || T < 2 * D + 1);
+            // (a file at another rate has no per-file loop either: it stays in the batch, and a sweep over it is refused)
+            if (other_rate && sweep)
+                throw std::runtime_error("File \"" + files[2 * it.file] + "\" needs sample-rate conversion, which takes one warp factor, not a sweep");
+            it.stream = o.method != MFX_METHOD_TRAPS && !other_rate && (sweep || n > (size_t)limit || T < 2 * D + 1);
             if (!it.stream) {
                 it.mono.resize(n);
                 const int ch = it.wav.channels;
@@ -689,7 +749,14 @@ void worker(const Options &o, int device, float sr, const std::vector<std::strin
                 if (!in_batch.empty()) {
                     const long long td0 = g_time.on ? now_ns() : 0;
                     row0.resize(in_batch.size());
-                    b.total_rows = param.batch_plan((int)in_batch.size(), off.data(), len.data(), row0.data());
+                    if (o.resample_to > 0) { // every file with its own rate: files at the extractor's rate are copied
+                        std::vector<int> rates;
+                        for (const BatchItem *it : in_batch) rates.push_back(it->rate);
+                        b.total_rows = param.batch_plan_rates((int)in_batch.size(), off.data(), len.data(), rates.data(), o.resample_zeros,
+                                                              row0.data());
+                    } else {
+                        b.total_rows = param.batch_plan((int)in_batch.size(), off.data(), len.data(), row0.data());
+                    }
                     if (!o.file_alpha.empty()) { // --alpha-file: every file of the batch with its own factor, one run
                         std::vector<float> al;
                         for (const BatchItem *it : in_batch) al.push_back(o.file_alpha[it->file]);
@@ -700,12 +767,13 @@ void worker(const Options &o, int device, float sr, const std::vector<std::strin
                     for (size_t k = 0; k < in_batch.size(); ++k) {
                         BatchItem &it = *in_batch[k];
                         it.row0 = row0[k];
-                        if (it.frames != param.batch_frames(it.len)) throw std::runtime_error("frame count mismatch");
+                        if (it.frames != param.batch_frames(it.conv_len)) throw std::runtime_error("frame count mismatch");
                         // The reference's flush after exactly one set_input reads its D static rows D rows early (B1,
                         // mfcccpu.cpp:439 + segmentercpu.cpp:97-106): rows T - D .. T - 1 repeat the statics of rows
                         // T - 2 D .. T - D - 1 (deltas unaffected).  The batch entries deliver the correct rows; the
                         // per-file loop this replaces reproduces the reference when --bug-compat is on, so do we.
-                        if (o.bug_compat && D > 0 && o.method != MFX_METHOD_TRAPS)
+                        // (not for a converted file: the reference has no rows for it, and it may be shorter than 2 D frames)
+                        if (o.bug_compat && D > 0 && o.method != MFX_METHOD_TRAPS && (float)it.rate == sr)
                             for (int i = 0; i < D; ++i)
                                 std::memcpy(rows + (size_t)(it.row0 + it.frames - D + i) * width,
                                             rows + (size_t)(it.row0 + it.frames - 2 * D + i) * width, (size_t)cols * sizeof(float));
@@ -825,6 +893,8 @@ int main(int argc, char **argv)
         else if (a == "--format-threads") o.format_threads = std::max(1, std::atoi(val()));
         else if (a == "--batch-mb") o.batch_mb = std::max(0, std::atoi(val()));
         else if (a == "--io-threads") o.io_threads = std::max(1, std::atoi(val()));
+        else if (a == "--resample-to") o.resample_to = std::atoi(val());
+        else if (a == "--resample-zeros") o.resample_zeros = std::atoi(val());
         else if (a == "--selftest-format") { // put_f32 against printf("%f") on n random bit patterns + the known hard cases
             const long n = std::atol(val());
             uint64_t st = 0x9E3779B97F4A7C15ull;
@@ -865,6 +935,9 @@ int main(int argc, char **argv)
                         "         [--batch-mb n (PCM per batch of whole files; 0 = per-file loop)] [--io-threads n]\n"
                         "  --alpha-file: one warp factor per line, in the order of the input files; files of a batch run with\n"
                         "                their own factors in one launch sequence\n"
+                        "         [--resample-to hz [--resample-zeros n]]\n"
+                        "  --resample-to: extract at hz instead of the first file's rate; files at other rates are converted on the\n"
+                        "                device (Hann-windowed sinc, n zero crossings per side, default 6)\n"
                         "  --devs: one worker per listed GPU, files dealt from a shared queue\n"
                         "  inputs: RIFF/WAVE or NIST SPHERE, 16-bit PCM; output: the reference's text rows, or HTK binary\n");
             return 0;
@@ -912,9 +985,17 @@ int main(int argc, char **argv)
             return 2;
         }
     }
+    if (o.resample_to != 0 && (o.resample_to < 1000 || o.resample_to > 768000)) {
+        std::fprintf(stderr, "--resample-to takes a rate of 1000 .. 768000 Hz\n");
+        return 2;
+    }
+    if (o.resample_zeros < 0 || o.resample_zeros > 64) {
+        std::fprintf(stderr, "--resample-zeros takes 1 .. 64\n");
+        return 2;
+    }
     try {
-        const Wav first = read_wav(files[0]); // sample rate from the first file (ASR_OCL.cpp:342-358)
-        const float sr = (float)first.sample_rate;
+        // sample rate from the first file (ASR_OCL.cpp:342-358), unless --resample-to names it
+        const float sr = o.resample_to > 0 ? (float)o.resample_to : (float)read_wav(files[0]).sample_rate;
         if (o.high <= 0) o.high = sr / 2;
         if (o.devices.empty()) o.devices.push_back(o.device);
         std::atomic<size_t> next{0};

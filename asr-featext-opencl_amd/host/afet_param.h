@@ -105,6 +105,11 @@ public:
     // Many files in one launch sequence (mfx_batch_plan / mfx_batch_run_host): utterance u = samples [offsets[u],
     // offsets[u] + lengths[u]) of one PCM array, its rows start at out_rows[u]; returns the total number of rows
     long long batch_plan(int n_utt, const long long *offsets, const long long *lengths, long long *out_rows);
+    // the same for files at their own sample rates (mfx_batch_plan_rates): offsets / lengths in input-rate samples, one rate
+    // per utterance; the run converts them to the extractor's rate on the device first.  conv_lengths (may be null): the
+    // converted lengths
+    long long batch_plan_rates(int n_utt, const long long *offsets, const long long *lengths, const int *rates_hz, int zeros,
+                               long long *out_rows, long long *conv_lengths = nullptr);
     void batch_run_host(const short *pcm, long long samples_total, float *out);
     // one warp factor per utterance of the planned batch (mfx_batch_set_alphas); nullptr / 0 clears the list, and so does
     // the next batch_plan

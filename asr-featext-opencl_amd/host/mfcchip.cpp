@@ -174,6 +174,17 @@ long long MfccHip::batch_plan(int n_utt, const long long *offsets, const long lo
     return (long long)total;
 }
 
+long long MfccHip::batch_plan_rates(int n_utt, const long long *offsets, const long long *lengths, const int *rates_hz, int zeros,
+                                    long long *out_rows, long long *conv_lengths)
+{
+    static_assert(sizeof(int) == sizeof(int32_t), "32-bit int");
+    int64_t total = 0;
+    check(mfx_batch_plan_rates(m_handle, n_utt, (const int64_t *)offsets, (const int64_t *)lengths, (const int32_t *)rates_hz, zeros,
+                               0.f, (int64_t *)out_rows, &total));
+    if (conv_lengths) check(mfx_batch_resample_layout(m_handle, nullptr, (int64_t *)conv_lengths, nullptr));
+    return (long long)total;
+}
+
 void MfccHip::batch_run_host(const short *pcm, long long samples_total, float *out)
 {
     check(mfx_batch_run_host(m_handle, pcm, (int64_t)samples_total, out));

@@ -74,6 +74,8 @@ EXPORTED_SYMBOLS = (
     "mfx_method_supported", "mfx_host_plp_tables", "mfx_host_traps_basis",
     "mfx_sessions_create", "mfx_sessions_reset", "mfx_sessions_plan", "mfx_sessions_run_device", "mfx_sessions_run_host",
     "mfx_sessions_delivered", "mfx_host_session_step",
+    "mfx_batch_plan_rates", "mfx_batch_resample_layout", "mfx_host_resample_taps", "mfx_host_resampled_length",
+    "mfx_host_resample_layout", "mfx_host_resample_tile",
 )
 
 
@@ -158,6 +160,13 @@ def load_library():
     L.mfx_sessions_delivered.argtypes, L.mfx_sessions_delivered.restype = [vp, i32], i64
     L.mfx_host_session_step.argtypes = [i32, i32, i32, p64, i64, i32, p64, p32, p32, p32]
     L.mfx_host_session_step.restype = i32
+    L.mfx_batch_plan_rates.argtypes = [vp, i32, p64, p64, p32, i32, C.c_float, p64, p64]
+    L.mfx_batch_resample_layout.argtypes = [vp, p64, p64, p64]
+    L.mfx_host_resample_taps.argtypes = [i32, i32, i32, C.c_float, fp, i64, p32, p32, p32]
+    L.mfx_host_resample_taps.restype = i64
+    L.mfx_host_resampled_length.argtypes, L.mfx_host_resampled_length.restype = [i64, i32, i32], i64
+    L.mfx_host_resample_layout.argtypes, L.mfx_host_resample_layout.restype = [i32, p64, p32, i32, p64, p64], i64
+    L.mfx_host_resample_tile.argtypes, L.mfx_host_resample_tile.restype = [i32, i32, i32, C.c_float, i32], i32
     _lib = L
     return L
 
@@ -313,6 +322,50 @@ def host_session_step(window_size, shift, D, state, length, final=False):
         raise MfxError(int(rows), "mfx_host_session_step failed")
     return dict(rows=int(rows), state=(int(st[0]), int(st[1])), carry_samples=cs.value, carry_rows=cr.value,
                 new_frames=nf.value, n_out=seg[0], shift=seg[1], lo=seg[2], hi=seg[3], static_off=seg[4])
+
+
+def host_resample_taps(in_hz, out_hz, zeros=0, rolloff=0.0):
+    """Tap table of the sample-rate converter exactly as uploaded (host code, no GPU needed): (taps [L][P], L, M, P)."""
+    lib = load_library()
+    L, M, P = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    n = lib.mfx_host_resample_taps(int(in_hz), int(out_hz), int(zeros), float(rolloff), None, 0, C.byref(L), C.byref(M), C.byref(P))
+    if n < 0:
+        raise MfxError(int(n), "mfx_host_resample_taps: shape outside the limits")
+    taps = np.zeros(int(n), np.float32)
+    lib.mfx_host_resample_taps(int(in_hz), int(out_hz), int(zeros), float(rolloff), taps.ctypes.data_as(C.POINTER(C.c_float)),
+                               taps.size, C.byref(L), C.byref(M), C.byref(P))
+    return taps.reshape(L.value, P.value), L.value, M.value, P.value
+
+
+def host_resampled_length(samples, in_hz, out_hz):
+    """ceil(samples * L / M): samples per channel after conversion."""
+    n = int(load_library().mfx_host_resampled_length(int(samples), int(in_hz), int(out_hz)))
+    if n < 0:
+        raise MfxError(n, "mfx_host_resampled_length failed")
+    return n
+
+
+def host_resample_layout(lengths, rates, out_hz):
+    """Layout of the converted PCM (host code, no GPU needed): (offsets, out_lengths, total) in output-rate samples per
+    channel for utterances of the given input lengths and rates."""
+    ln = np.ascontiguousarray(lengths, dtype=np.int64)
+    rt = np.ascontiguousarray(rates, dtype=np.int32)
+    assert ln.size == rt.size
+    off, out = np.zeros(ln.size, np.int64), np.zeros(ln.size, np.int64)
+    p64 = C.POINTER(C.c_int64)
+    total = load_library().mfx_host_resample_layout(ln.size, ln.ctypes.data_as(p64), rt.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                    int(out_hz), off.ctypes.data_as(p64), out.ctypes.data_as(p64))
+    if total < 0:
+        raise MfxError(int(total), "mfx_host_resample_layout failed")
+    return off, out, int(total)
+
+
+def host_resample_tile(in_hz, out_hz, zeros=0, rolloff=0.0, channels=1):
+    """Output samples per tile of k_resample for a rate pair (test aid: utterance lengths at a tile edge)."""
+    n = int(load_library().mfx_host_resample_tile(int(in_hz), int(out_hz), int(zeros), float(rolloff), int(channels)))
+    if n < 0:
+        raise MfxError(n, "mfx_host_resample_tile failed")
+    return n
 
 
 def host_frame_count(samples, window_size, shift):
@@ -537,6 +590,37 @@ class MfccHip:
         self._plan_rows, self._plan_total = rows, total.value
         return rows, total.value
 
+    def batch_plan_rates(self, offsets, lengths, rates, zeros=0, rolloff=0.0):
+        """batch_plan for utterances at their own sample rates (mfx_batch_plan_rates): offsets / lengths in input-rate
+        samples per channel, rates in Hz; the run converts every utterance to cfg.sample_rate on the device first.
+        Returns (out_rows, total_rows) of the converted lengths."""
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        ln = np.ascontiguousarray(lengths, dtype=np.int64)
+        rt = np.ascontiguousarray(rates, dtype=np.int32)
+        assert off.size == ln.size == rt.size
+        rows = np.zeros(off.size, dtype=np.int64)
+        total = C.c_int64(0)
+        p64 = C.POINTER(C.c_int64)
+        self._chk(self._L.mfx_batch_plan_rates(self._h, off.size, off.ctypes.data_as(p64), ln.ctypes.data_as(p64),
+                                               rt.ctypes.data_as(C.POINTER(C.c_int32)), int(zeros), float(rolloff),
+                                               rows.ctypes.data_as(p64), C.byref(total)))
+        self._plan_rows, self._plan_total = rows, total.value
+        return rows, total.value
+
+    def batch_resample_layout(self):
+        """(offsets, lengths, total) of the converted PCM in output-rate samples per channel, while a rates plan is in
+        force (MfxError with status -8 otherwise)."""
+        n = 0 if self._plan_rows is None else self._plan_rows.size
+        off, ln = np.zeros(n, np.int64), np.zeros(n, np.int64)
+        total = C.c_int64(0)
+        p64 = C.POINTER(C.c_int64)
+        self._chk(self._L.mfx_batch_resample_layout(self._h, off.ctypes.data_as(p64), ln.ctypes.data_as(p64), C.byref(total)))
+        return off, ln, total.value
+
+    host_resample_taps = staticmethod(host_resample_taps)
+    host_resampled_length = staticmethod(host_resampled_length)
+    host_resample_layout = staticmethod(host_resample_layout)
+
     def batch_run_device(self, d_pcm_ptr, pcm_samples_total, d_out_ptr):
         """Device pointers in, device pointer out; asynchronous on the handle's stream."""
         self._chk(self._L.mfx_batch_run_device(self._h, C.c_void_p(int(d_pcm_ptr)), int(pcm_samples_total),
@@ -674,6 +758,12 @@ class MfccHip:
             buf = np.zeros(2 * W2, dtype=np.float32)
         elif kind == 2:
             buf = np.zeros(max(nb * dl, 1), dtype=np.float32)
+        elif kind == 8:   # converted PCM of the last batch run under a rates plan (int16, scratch layout)
+            try:
+                total = self.batch_resample_layout()[2]
+            except MfxError:
+                total = 0
+            buf = np.zeros(max(total * max(self.cfg.channels, 1), 1), dtype=np.int16)
         else:
             buf = np.zeros(64 * 1024 * 1024 // 4, dtype=np.float32)
         n = self._L.mfx_debug_read(self._h, int(kind), buf.ctypes.data_as(C.c_void_p), buf.nbytes)

@@ -269,6 +269,49 @@ int mfx_batch_set_transform(mfx_handle *h, int32_t left, int32_t right, int32_t 
 /* out_dim while a transform is in force, else mfx_get_output_data_width */
 int mfx_batch_output_width(const mfx_handle *h);
 
+/* ---- sample-rate conversion in front of a batch ("Sample-rate conversion").  No reference analogue: the
+ *      reference refuses a file whose rate differs from the first file's (ASR_OCL.cpp:191). ----
+ *
+ * Utterance u arrives at r_in = rates_hz[u] Hz (an integer); the rate the features are extracted at is r_out =
+ * mfx_config.sample_rate, which must be an integral value.  g = gcd(r_in, r_out), L = r_out / g, M = r_in / g.
+ *   Pass-through.  An utterance with r_in == r_out is copied, sample for sample.
+ *   Length.  N_in samples per channel give N_out = ceil(N_in L / M) (int64 arithmetic; 0 gives 0).
+ *   Filter.  A Hann-windowed sinc, evaluated in double on the host and rounded once to float32: rolloff in (0, 1] (0 means
+ *     0.99), zeros in 1 .. 64 (0 means 6); c = rolloff min(1, L / M), Wh = ceil(zeros / c), P = 2 Wh taps per phase.  For
+ *     phase phi in [0, L) and tap k in [0, P): t = (k - Wh + 1) - phi / L,
+ *     h[phi][k] = c sinc(c t) (1 + cos(pi t / Wh)) / 2 for |t| < Wh, else 0; sinc(x) = sin(pi x) / (pi x), sinc(0) = 1.
+ *     No per-phase renormalisation (the phase sums are 1 to within the window's ripple).  Table layout [L][P].
+ *   Output sample j of an utterance, 0 <= j < N_out: n = (j M) div L, phi = (j M) mod L (int64);
+ *     acc = 0; for k = 0 .. P - 1 ascending: acc = fmaf(h[phi][k], (float)x[n - Wh + 1 + k], acc);
+ *     y[j] = clamp(rintf(acc), -32768, 32767) as int16.  x outside [0, N_in) of THAT utterance and channel is 0, never a
+ *     neighbour's samples.  One float32 FMA chain in a fixed order: the bits of y do not depend on the tiling, on the other
+ *     utterances of the batch, or on the alignment of the source.
+ *   Stereo (channels = 2): each channel is converted on its own and the result is stored interleaved; the (L+R)>>1 downmix
+ *     stays in the front ends.
+ *   Limits (MFX_ERR_ARG with a message on the handle): rates in 1000 .. 768000 Hz, L <= 4096, P <= 4096, L P <= 2^20
+ *     floats, at most 16 distinct input rates per plan.
+ *
+ * mfx_batch_plan_rates is mfx_batch_plan with offsets and lengths in INPUT-RATE samples per channel and one input rate per
+ * utterance; out_rows / total_rows follow from the converted lengths, T_u = mfx_batch_frames(h, N_out_u).  It builds and
+ * uploads the tap tables and tile descriptors and allocates a handle-owned int16 scratch for the converted PCM: every
+ * utterance starts at an even sample offset, in ascending utterance order, and the scratch is padded at its end (the front
+ * ends' "32-bit word that holds the last sample" rule holds); mfx_batch_run_device still allocates nothing.  A later
+ * mfx_batch_plan or mfx_batch_plan_rates replaces the plan and drops the converter.  mfx_batch_set_alphas,
+ * mfx_batch_set_transform and mfx_batch_overlap work after it exactly as after mfx_batch_plan.  MFX_ERR_DEVICE on a planning
+ * handle; MFX_ERR_CONFIG when sample_rate is not integral; like mfx_batch_plan it does not need the window yet (the run
+ * returns MFX_ERR_STATE before mfx_set_window).
+ * While a rates plan is in force, mfx_batch_run_device / mfx_batch_run_host take pcm_samples_total and check their bounds
+ * against the INPUT array (4-byte aligned as always; utterances may start at odd input offsets), convert d_pcm -> scratch
+ * with ONE launch of k_resample over the utterance range being run, and then do exactly what they do today with the scratch
+ * and its layout in the place of the caller's array.  The sliced host path cuts the input array by utterance, in input-rate
+ * samples.
+ * mfx_batch_resample_layout: the scratch layout in output-rate samples per channel (what a second handle needs to be planned
+ * on the converted PCM, which mfx_debug_read kind 8 returns); MFX_ERR_STATE without a rates plan.
+ * NOT served: the session entries (mfx_sessions_*) and the streaming interface are untouched and ignore a rates plan. */
+int mfx_batch_plan_rates(mfx_handle *h, int32_t n_utt, const int64_t *offsets, const int64_t *lengths, const int32_t *rates_hz,
+                         int32_t zeros, float rolloff, int64_t *out_rows, int64_t *total_rows);
+int mfx_batch_resample_layout(const mfx_handle *h, int64_t *offsets, int64_t *lengths, int64_t *total);
+
 /* Opt-in pipelining of consecutive batches: with enable=1 the delta / normalisation tail of a batch runs
  * on a second internal stream, so it overlaps the front end of the NEXT mfx_batch_run_device call.
  * Results of a batch are then complete only after mfx_synchronize() (or a device-wide synchronise),
@@ -390,6 +433,19 @@ int64_t mfx_host_xform_operands(int32_t out_dim, int32_t in_dim, const float *A,
  * static_off}, rows relative to the first carried frame max(0, E_old - D).  Any output may be NULL.  Test / inspection aid. */
 int32_t mfx_host_session_step(int32_t window, int32_t shift, int32_t D, int64_t state[2], int64_t length, int32_t final_flag,
                               int64_t *carry_samples, int32_t *carry_rows, int32_t *new_frames, int32_t seg[5]);
+/* Sample-rate conversion (mfx_batch_plan_rates).  mfx_host_resample_taps: the table as uploaded, [L][P]; returns L * P or a
+ * negative status (MFX_ERR_ARG: outside the limits, or cap too small); taps may be NULL to query.
+ * mfx_host_resampled_length: ceil(samples L / M).  mfx_host_resample_layout: the scratch layout (offsets, out_lengths; either
+ * may be NULL) of utterances of the given input lengths and rates; returns the total, in output-rate samples per channel.
+ * mfx_host_resample_tile: output samples per tile of k_resample for the pair.  UNSTABLE, a test / inspection aid only (utterance
+ * lengths at a tile edge): the tiling is the kernel's private matter and may change in any release without an ABI version
+ * change; nothing but tests may depend on its value. */
+int64_t mfx_host_resample_taps(int32_t in_hz, int32_t out_hz, int32_t zeros, float rolloff, float *taps, int64_t cap, int32_t *L,
+                               int32_t *M, int32_t *P);
+int64_t mfx_host_resampled_length(int64_t samples, int32_t in_hz, int32_t out_hz);
+int64_t mfx_host_resample_layout(int32_t n_utt, const int64_t *lengths, const int32_t *rates_hz, int32_t out_hz, int64_t *offsets,
+                                 int64_t *out_lengths);
+int32_t mfx_host_resample_tile(int32_t in_hz, int32_t out_hz, int32_t zeros, float rolloff, int32_t channels);
 /* frame count, integer arithmetic (parambase.cpp:16-19 without the float32 division) */
 int64_t mfx_host_frame_count(int64_t samples, int32_t window_size, int32_t shift);
 
@@ -398,7 +454,8 @@ int64_t mfx_host_frame_count(int64_t samples, int32_t window_size, int32_t shift
  *       2 = DCT matrix [num_banks][dct_len] floats, 3 = magnitude spectrum of the current block
  *       [frames_with_context][fft_size/2+1] floats, 5 / 6 = normaliser statistics of the last streaming apply / batch run,
  *       7 = PLP autocorrelations r_0 .. r_p of the last plain streaming apply [frames_with_context][lpc_order + 1] floats
- *       (MFCC handles: 0 elements).  Returns element count or <0. */
+ *       (MFCC handles: 0 elements), 8 = converted PCM of the last batch run under a rates plan, int16 in the scratch layout
+ *       of mfx_batch_resample_layout (0 elements without one).  Returns element count or <0. */
 int64_t mfx_debug_read(mfx_handle *h, int kind, void *dst, int64_t dst_bytes);
 
 #ifdef __cplusplus

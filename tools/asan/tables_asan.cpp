@@ -1,7 +1,7 @@
 // Sanitizer run of the host table builders (csrc/mfx_tables.cpp) under -fsanitize=address,undefined: mel table, DCT
 // matrix, twiddles, the 16-lane mel plan of the 512-point kernel and the 64- and 32-lane wave plans, over a grid of
 // configurations (bank counts, transform sizes, sample rates, band edges, VTLN warps), and the front ends' FFT pass / split
-// twiddle tables and window layouts.  Built by `make -C csrc asan`.
+// twiddle tables and window layouts, and the sample-rate converter's tap tables, lengths and layouts.  Built by `make -C csrc asan`.
 #include <cstdio>
 #include <vector>
 
@@ -138,6 +138,32 @@ int main()
                 if (rows != (T > 0 ? T : 0) || n != 0 || E != 0) return 1;
                 ++nq;
             }
+    // sample-rate conversion: exactly-sized tap tables at the corners of the limits, lengths and layouts
+    int nv = 0;
+    {
+        const int pairs[][2] = {{48000, 16000}, {8000, 16000}, {44100, 16000}, {11025, 16000}, {17600, 16000}, {16000, 44100},
+                                {768000, 1000}, {1000, 768000}, {4096, 4095}, {16000, 16000}};
+        for (const auto &pr : pairs)
+            for (int zeros : {0, 1, 6, 64})
+                for (float ro : {0.f, 0.25f, 1.f}) {
+                    mfx::ResampleShape sh;
+                    if (mfx::resample_shape(pr[0], pr[1], zeros, ro, sh) != 0) continue; // (outside the limits: refused)
+                    std::vector<float> taps((size_t)sh.L * sh.P);
+                    mfx::build_resample_taps(sh, taps.data());
+                    double sum = 0;
+                    for (float v : taps) sum += v;
+                    if (!(sum > 0.8 * sh.L && sum < 1.1 * sh.L)) return 1; // the phases sum to about 1 (0.82 at one zero crossing)
+                    ++nv;
+                }
+        std::vector<int64_t> lens = {0, 1, 2, 4411, 16000, 7, 48001, 3, 0, 8000, (int64_t)1 << 40}, off(lens.size()), out(lens.size());
+        std::vector<int32_t> rates = {8000, 44100, 16000, 44100, 16000, 16000, 48000, 11025, 16000, 8000, 48000};
+        const int64_t total = mfx::resample_layout((int32_t)lens.size(), lens.data(), rates.data(), 16000, off.data(), out.data());
+        if (total != off.back() + ((out.back() + 1) & ~(int64_t)1) || mfx::resampled_length(((int64_t)1 << 40) + 1, 48000, 16000) != 366503875926)
+            return 1;
+        rates[3] = 500;
+        if (mfx::resample_layout((int32_t)lens.size(), lens.data(), rates.data(), 16000, nullptr, nullptr) != -1) return 1;
+    }
+    std::printf("tables_asan: %d resampler tables; ", nv);
     std::printf("tables_asan: %d configurations, %d front-end tables, %d run lists, %d transform operand sets, %d session push sequences clean\n",
                 n, nt, nr, nx, nq);
     return 0;
