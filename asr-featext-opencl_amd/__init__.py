@@ -32,6 +32,9 @@ from .mfcc import (  # noqa: F401
     host_mel_table,
     host_plp_tables,
     host_session_step,
+    host_speaker_lists,
+    SPK_POOL,
+    SPK_PRIOR_ONLY,
     host_traps_basis,
     host_xform_operands,
     KERNEL_TABLE,

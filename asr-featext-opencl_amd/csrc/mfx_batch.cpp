@@ -217,6 +217,7 @@ int plan_batch(mfx_handle *h, int32_t n_utt, const int64_t *offsets, const int64
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->batch.alphas_on = false; // (a warp-factor list is tied to the plan's utterance order)
     h->batch.xf_on = false;     // (and so are a transform's utterance index and its scratch)
+    h->batch.spk_on = false;    // (and a speaker list)
     h->batch.planned = false;
     h->batch.n_utt = n_utt;
     h->batch.utt_off.assign(offsets, offsets + n_utt);
@@ -471,6 +472,151 @@ extern "C" int mfx_batch_set_alphas(mfx_handle *h, const float *alphas, int32_t 
     return MFX_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// per-speaker normalisation ("Per-speaker normalisation")
+// ------------------------------------------------------------------------------------------------
+
+// normalised columns: the whole row after the deltas, else the statics
+static int spk_wn(const mfx_handle *h) { return h->cfg.norm_after_dyn ? h->width : h->cols; }
+
+extern "C" int mfx_batch_set_speakers(mfx_handle *h, const int32_t *utt_spk, int32_t n_utt, int32_t n_spk, const int64_t *prior_count,
+                                      const double *prior_acc, int32_t mode)
+{
+    MFX_DEVICE_ENTRY(h);
+    if (h->cfg.norm == MFX_NORM_NONE) return fail(h, MFX_ERR_CONFIG, "mfx_batch_set_speakers: the handle does not normalise (norm = NONE)");
+    if (!utt_spk && n_utt == 0) { // back to every utterance's own statistics and run_norm's kernels
+        HIP_TRY(h, hipSetDevice(h->device));
+        const int rc = mfx_synchronize(h); // (a run in flight may read what a later call replaces)
+        if (rc != MFX_OK) return rc;
+        h->batch.spk_on = false;
+        return MFX_OK;
+    }
+    if (!h->batch.planned) return fail(h, MFX_ERR_STATE, "mfx_batch_set_speakers: no batch is planned");
+    if (!utt_spk || n_utt != h->batch.n_utt) return fail(h, MFX_ERR_ARG, "one speaker per planned utterance");
+    if (n_spk < 1 || n_spk > (1 << 20)) return fail(h, MFX_ERR_ARG, "n_spk must be 1 .. 2^20");
+    if ((prior_count == nullptr) != (prior_acc == nullptr)) return fail(h, MFX_ERR_ARG, "a prior is a count AND an accumulator per speaker");
+    if (mode != MFX_SPK_POOL && mode != MFX_SPK_PRIOR_ONLY) return fail(h, MFX_ERR_ARG, "mode must be MFX_SPK_POOL or MFX_SPK_PRIOR_ONLY");
+    if (mode == MFX_SPK_PRIOR_ONLY && !prior_count) return fail(h, MFX_ERR_ARG, "MFX_SPK_PRIOR_ONLY needs a prior");
+    if (prior_count)
+        for (int s = 0; s < n_spk; ++s)
+            if (prior_count[s] < 0) return fail(h, MFX_ERR_ARG, "negative prior count");
+    std::vector<int64_t> frames((size_t)n_utt);
+    for (int u = 0; u < n_utt; ++u) frames[u] = std::max<int64_t>(frame_count(h->batch.utt_len[u], h->W, h->S), 0);
+    std::vector<int32_t> off, list;
+    if (!build_speaker_lists(utt_spk, frames.data(), n_utt, n_spk, off, list)) return fail(h, MFX_ERR_ARG, "speaker id outside [0, n_spk)");
+    if (mode == MFX_SPK_PRIOR_ONLY)
+        for (int s = 0; s < n_spk; ++s)
+            if (prior_count[s] == 0 && off[s + 1] > off[s])
+                return fail(h, MFX_ERR_ARG, "MFX_SPK_PRIOR_ONLY: a speaker with rows in the batch has a prior of count 0");
+    const int Wn = spk_wn(h);
+    const int tile_rows = spk_tile_rows(Wn);
+    std::vector<int32_t> chunk0((size_t)n_utt + 1);
+    std::vector<SpkTile> tiles;
+    int64_t chunks = 0, max_rows = 0;
+    for (int u = 0; u < n_utt; ++u) {
+        chunk0[u] = (int32_t)chunks;
+        chunks += spk_chunks(frames[u]);
+        max_rows = std::max(max_rows, frames[u]);
+        if (chunks > 0x7ffffff0 || (frames[u] + tile_rows - 1) / tile_rows + (int64_t)tiles.size() > 0x7ffffff0)
+            return fail(h, MFX_ERR_ARG, "batch too long");
+        for (int64_t r = 0; r < frames[u]; r += tile_rows) {
+            SpkTile t;
+            t.row0 = h->batch.utt_row[u] + r;
+            t.rows = (int32_t)std::min<int64_t>(tile_rows, frames[u] - r);
+            t.spk = utt_spk[u];
+            tiles.push_back(t);
+        }
+    }
+    chunk0[n_utt] = (int32_t)chunks;
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = mfx_synchronize(h); // (a run in flight may read the lists replaced below)
+    if (rc != MFX_OK) return rc;
+    h->batch.spk_on = false;
+    h->batch.spk_ran = false;
+    // (everything mfx_batch_run_device needs is allocated here: that entry never allocates)
+    HIP_TRY(h, h->upload(h->batch.d_spk_off, off));
+    HIP_TRY(h, h->upload(h->batch.d_spk_list, list));
+    HIP_TRY(h, h->upload(h->batch.d_spk_chunk0, chunk0));
+    HIP_TRY(h, h->upload(h->batch.d_spk_tiles, tiles));
+    const size_t per = (size_t)4 * Wn;
+    if (prior_count) {
+        HIP_TRY(h, h->upload(h->batch.d_spk_prior_n, std::vector<int64_t>(prior_count, prior_count + n_spk)));
+        HIP_TRY(h, h->upload(h->batch.d_spk_prior, std::vector<double>(prior_acc, prior_acc + (size_t)n_spk * per)));
+    } else {
+        h->batch.d_spk_prior_n.release(), h->batch.d_spk_prior.release();
+    }
+    HIP_TRY(h, h->batch.d_spk_partial.alloc((size_t)chunks * per));
+    HIP_TRY(h, h->batch.d_spk_count.alloc((size_t)n_spk));
+    HIP_TRY(h, h->batch.d_spk_acc.alloc((size_t)n_spk * per));
+    HIP_TRY(h, h->batch.d_spk_stats.alloc((size_t)n_spk * 2 * Wn));
+    h->batch.n_spk = n_spk;
+    h->batch.spk_mode = mode;
+    h->batch.spk_tiles = (int32_t)tiles.size();
+    h->batch.spk_max_rows = (int32_t)max_rows;
+    h->batch.spk_on = true;
+    return MFX_OK;
+}
+
+extern "C" int mfx_batch_speaker_stats(mfx_handle *h, int64_t *count, double *acc, float *stats)
+{
+    MFX_DEVICE_ENTRY(h);
+    if (!h->batch.spk_on) return fail(h, MFX_ERR_STATE, "mfx_batch_speaker_stats: no speaker list is in force");
+    if (!h->batch.spk_ran) return fail(h, MFX_ERR_STATE, "mfx_batch_speaker_stats: no batch has run since the list was set");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int rc = mfx_synchronize(h);
+    if (rc != MFX_OK) return rc;
+    const size_t n = (size_t)h->batch.n_spk, Wn = (size_t)spk_wn(h);
+    if (count) HIP_TRY(h, hipMemcpy(count, h->batch.d_spk_count.p, n * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (acc) HIP_TRY(h, hipMemcpy(acc, h->batch.d_spk_acc.p, n * 4 * Wn * sizeof(double), hipMemcpyDeviceToHost));
+    if (stats) HIP_TRY(h, hipMemcpy(stats, h->batch.d_spk_stats.p, n * 2 * Wn * sizeof(float), hipMemcpyDeviceToHost));
+    return MFX_OK;
+}
+
+extern "C" int64_t mfx_host_speaker_lists(int32_t n_utt, const int32_t *utt_spk, const int64_t *frames, int32_t n_spk, int32_t *off,
+                                          int32_t *list)
+{
+    if (n_utt < 0 || n_spk < 0 || (n_utt > 0 && (!utt_spk || !frames))) return MFX_ERR_ARG;
+    std::vector<int32_t> o, l;
+    if (!build_speaker_lists(utt_spk, frames, n_utt, n_spk, o, l)) return MFX_ERR_ARG;
+    if (off) std::copy(o.begin(), o.end(), off);
+    if (list) std::copy(l.begin(), l.end(), list);
+    return (int64_t)l.size();
+}
+
+namespace {
+// the normaliser of a run while a speaker list is in force: in run_norm's place, on its stream, over the whole batch
+int run_speaker_norm(mfx_handle *h, hipStream_t stream, float *data)
+{
+    SpkParams sp{};
+    sp.data = data;
+    sp.pitch = h->width;
+    sp.cols = h->cols;
+    sp.groups = spk_wn(h) / h->cols;
+    sp.norm_type = h->cfg.norm;
+    sp.mode = h->batch.spk_mode;
+    sp.segs = h->batch.d_segs.p;
+    sp.n_utt = h->batch.n_utt;
+    sp.max_rows = h->batch.spk_max_rows;
+    sp.utt_chunk0 = h->batch.d_spk_chunk0.p;
+    sp.partial = h->batch.d_spk_partial.p;
+    sp.spk_off = h->batch.d_spk_off.p;
+    sp.spk_list = h->batch.d_spk_list.p;
+    sp.n_spk = h->batch.n_spk;
+    sp.prior_count = h->batch.d_spk_prior_n.p;
+    sp.prior_acc = h->batch.d_spk_prior.p;
+    sp.count = h->batch.d_spk_count.p;
+    sp.acc = h->batch.d_spk_acc.p;
+    sp.stats = h->batch.d_spk_stats.p;
+    sp.tiles = h->batch.d_spk_tiles.p;
+    sp.n_tiles = h->batch.spk_tiles;
+    if (sp.mode == MFX_SPK_POOL) HIP_TRY(h, launch_spk_sums(sp, stream));
+    HIP_TRY(h, launch_spk_finish(sp, stream));
+    HIP_TRY(h, launch_spk_apply(sp, stream));
+    h->batch.spk_ran = true;
+    return MFX_OK;
+}
+} // namespace
+
 int batch_out_width(const mfx_handle *h) { return h->batch.xf_on ? h->batch.xf_out : h->width; }
 
 extern "C" int mfx_batch_output_width(const mfx_handle *h) { return h ? batch_out_width(h) : MFX_ERR_ARG; }
@@ -556,6 +702,7 @@ int batch_run_range(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_tot
 {
     if (!d_pcm || !d_out || pcm_samples_total <= 0) return fail(h, MFX_ERR_ARG, "invalid argument");
     const bool whole = u0 == 0 && u1 == h->batch.n_utt;
+    if (h->batch.spk_on && !whole) return fail(h, MFX_ERR_STATE, "a speaker list is in force: the batch runs as a whole");
     const int32_t rc0 = h->batch.utt_chunk0[u0], rc1 = h->batch.utt_chunk0[u1]; // chunk range of the utterance range
     if (!h->have_window) return fail(h, MFX_ERR_STATE, "set_window has not been called");
     if (h->batch.rs_on) {
@@ -731,9 +878,11 @@ int batch_run_range(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_tot
         HIP_TRY(h, hipStreamWaitEvent(h->batch.stream2, h->batch.ev_front[sb], 0));
     }
     const bool norm = h->cfg.norm != MFX_NORM_NONE;
+    const bool spk = norm && h->batch.spk_on; // (speakers in force: the run covers the whole batch, mfx_batch_run_host does not slice)
     if (norm && !h->cfg.norm_after_dyn) {
-        rc = run_norm(h, tail_stream, d_out, h->width, h->batch.d_segs.p + u0, u1 - u0, nullptr, h->batch.d_stats.p + (size_t)u0 * 2 * h->cols,
-                      false, h->batch.tiles_max * 64);
+        rc = spk ? run_speaker_norm(h, tail_stream, d_out)
+                 : run_norm(h, tail_stream, d_out, h->width, h->batch.d_segs.p + u0, u1 - u0, nullptr,
+                            h->batch.d_stats.p + (size_t)u0 * 2 * h->cols, false, h->batch.tiles_max * 64);
         if (rc != MFX_OK) return rc;
     }
     if (h->l1 > 0 && !fuse) {
@@ -752,8 +901,10 @@ int batch_run_range(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_tot
     }
     if (norm && h->cfg.norm_after_dyn) {
         const int groups = h->width / h->cols;
-        rc = run_norm(h, tail_stream, d_out, h->width, h->batch.d_segs.p + u0, u1 - u0, nullptr, h->batch.d_stats.p + (size_t)u0 * 2 * h->cols,
-                      false, h->batch.tiles_max * 64, groups, (size_t)h->batch.n_utt * 2 * h->cols);
+        rc = spk ? run_speaker_norm(h, tail_stream, d_out)
+                 : run_norm(h, tail_stream, d_out, h->width, h->batch.d_segs.p + u0, u1 - u0, nullptr,
+                            h->batch.d_stats.p + (size_t)u0 * 2 * h->cols, false, h->batch.tiles_max * 64, groups,
+                            (size_t)h->batch.n_utt * 2 * h->cols);
         if (rc != MFX_OK) return rc;
     }
     if (h->batch.xf_on) { // behind the tail, on its stream: ev_tail covers it
@@ -832,7 +983,8 @@ extern "C" int mfx_batch_run_host(mfx_handle *h, const int16_t *pcm, int64_t pcm
     bool ascending = true;
     for (int u = 1; u < h->batch.n_utt && ascending; ++u) ascending = in_off[u] >= in_off[u - 1] + in_len[u - 1];
     const int K = (int)std::min<int64_t>(8, h->batch.n_utt / 4);
-    if (K >= 2 && ascending && !h->batch.overlap && !h->fuse.planned && n_in * sizeof(int16_t) >= ((size_t)32 << 20) &&
+    // (a speaker list in force: a speaker may span slices, the batch goes through whole)
+    if (K >= 2 && ascending && !h->batch.overlap && !h->fuse.planned && !h->batch.spk_on && n_in * sizeof(int16_t) >= ((size_t)32 << 20) &&
         is_pinned_host(pcm) && is_pinned_host(out)) {
         if (!h->batch.stream_up) {
             HIP_TRY(h, hipStreamCreateWithFlags(&h->batch.stream_up, hipStreamNonBlocking));

@@ -192,6 +192,18 @@ struct BatchState {
     DevBuf<float> d_rs_taps;
     DevBuf<mfx::ResRate> d_rs_rates;
     DevBuf<mfx::ResTile> d_rs_tiles;
+    // per-speaker normalisation (mfx_batch_set_speakers), tied to the plan: while spk_on the run's normaliser is k_spk_sums ->
+    // k_spk_finish -> k_spk_apply over the whole batch instead of run_norm's per-utterance kernels
+    bool spk_on = false;
+    bool spk_ran = false;                // a run has filled the accumulators since the list was set
+    int32_t n_spk = 0, spk_mode = 0, spk_tiles = 0, spk_max_rows = 0;
+    DevBuf<int32_t> d_spk_off, d_spk_list; // [n_spk + 1], [utterances with frames] (build_speaker_lists)
+    DevBuf<int32_t> d_spk_chunk0;        // [n_utt + 1] first 4096-row chunk of every utterance
+    DevBuf<double> d_spk_partial;        // [chunks][4][Wn]
+    DevBuf<int64_t> d_spk_prior_n, d_spk_count; // [n_spk] (the prior's: empty without one)
+    DevBuf<double> d_spk_prior, d_spk_acc;      // [n_spk][4][Wn]
+    DevBuf<float> d_spk_stats;           // [n_spk][2][Wn]
+    DevBuf<mfx::SpkTile> d_spk_tiles;    // k_spk_apply's tiles: whole rows of one utterance
 };
 
 // fused delta stage of the 512-point kernel: per-block chunk lists (own rows + halo) and delta tiles: mfx_batch.cpp

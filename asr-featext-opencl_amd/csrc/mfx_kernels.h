@@ -331,7 +331,46 @@ struct NormParams {
     int64_t group_stats_stride; // floats between the statistics of consecutive groups
 };
 
+// Per-speaker normalisation (mfx_batch_set_speakers; mfx_speakers.hip).  Wn = cols * groups normalised columns.
+struct SpkTile {
+    int64_t row0;          // first row of the tile (rows of ONE utterance)
+    int32_t rows;
+    int32_t spk;           // the utterance's speaker
+};
+
+struct SpkParams {
+    float *data;           // [rows][pitch], normalised in place at columns 0 .. Wn - 1
+    int32_t pitch;
+    int32_t cols;          // columns of one group (<= 256): the statistics' thread mapping is per group
+    int32_t groups;        // 1 (before the deltas), else the groups of the row
+    int32_t norm_type;     // MFX_NORM_*
+    int32_t mode;          // MFX_SPK_*
+    const Segment *segs;   // [n_utt]: uses out_row0 / n_out (ALL rows of the utterance)
+    int32_t n_utt;
+    int32_t u0;            // set by the launcher: first utterance of the launch
+    int32_t max_rows;      // largest row count of any utterance (sizes the grid)
+    const int32_t *utt_chunk0; // [n_utt + 1] first 4096-row chunk of every utterance
+    double *partial;       // [chunks][4][Wn]: S, S2, min, max of every chunk
+    const int32_t *spk_off;  // [n_spk + 1]
+    const int32_t *spk_list; // utterances of every speaker, ascending, frameless ones left out
+    int32_t n_spk;
+    const int64_t *prior_count; // [n_spk] or null
+    const double *prior_acc;    // [n_spk][4][Wn] or null
+    int64_t *count;        // [n_spk]
+    double *acc;           // [n_spk][4][Wn]
+    float *stats;          // [n_spk][2][Wn]: mean, multiplier
+    const SpkTile *tiles;
+    int32_t n_tiles;
+};
+
 // All launchers are asynchronous on `stream` and return the launch status.
+// per-speaker normalisation: chunk totals; accumulators + statistics; apply.  spk_tile_rows: rows of a tile of k_spk_apply at
+// Wn columns; spk_chunks: 4096-row chunks of an utterance of `rows` rows
+hipError_t launch_spk_sums(const SpkParams &p, hipStream_t stream);
+hipError_t launch_spk_finish(const SpkParams &p, hipStream_t stream);
+hipError_t launch_spk_apply(const SpkParams &p, hipStream_t stream);
+int spk_tile_rows(int wn);
+int spk_chunks(int64_t rows);
 hipError_t launch_front512(const FrontParams &p, bool to_spectrum, bool aligned, int nm16, hipStream_t stream);
 // fused front end + delta stage (p.blk_chunk_off etc. filled in); statics only pass through p.feat
 hipError_t launch_front512_delta(const FrontParams &p, bool aligned, int nm16, hipStream_t stream);

@@ -230,6 +230,23 @@ void build_alpha_runs(const float *alphas, const int64_t *frames, int n_utt, std
     }
 }
 
+bool build_speaker_lists(const int32_t *utt_spk, const int64_t *frames, int n_utt, int n_spk, std::vector<int32_t> &off,
+                         std::vector<int32_t> &list)
+{
+    if (n_spk < 0 || n_utt < 0) return false;
+    for (int u = 0; u < n_utt; ++u)
+        if (utt_spk[u] < 0 || utt_spk[u] >= n_spk) return false;
+    off.assign((size_t)n_spk + 1, 0);
+    for (int u = 0; u < n_utt; ++u)
+        if (frames[u] > 0) ++off[(size_t)utt_spk[u] + 1];
+    for (int s = 0; s < n_spk; ++s) off[(size_t)s + 1] += off[s];
+    list.assign((size_t)off[n_spk], 0);
+    std::vector<int32_t> next(off.begin(), off.end() - 1);
+    for (int u = 0; u < n_utt; ++u) // (ascending u: every speaker's part comes out ascending)
+        if (frames[u] > 0) list[(size_t)next[utt_spk[u]]++] = u;
+    return true;
+}
+
 void clip_alpha_runs(int64_t row0, int64_t rows, std::vector<int32_t> &off, std::vector<int64_t> &runs)
 {
     const int64_t w0 = row0, w1 = row0 + rows;

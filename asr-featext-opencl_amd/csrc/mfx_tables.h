@@ -88,6 +88,13 @@ void build_alpha_runs(const float *alphas, const int64_t *frames, int n_utt, std
 // the same lists with every run clipped to the rows [row0, row0 + rows), as the kernels clip them; empty runs dropped
 void clip_alpha_runs(int64_t row0, int64_t rows, std::vector<int32_t> &off, std::vector<int64_t> &runs);
 
+// Speakers of a planned batch (mfx_batch_set_speakers) -> the lists k_spk_finish walks.  utt_spk[u] in [0, n_spk) is the speaker of
+// utterance u (false when one is outside: nothing is written then); frames[u] its row count.
+//   off  : [n_spk + 1] speaker s owns list[off[s] .. off[s + 1])
+//   list : its utterances in ascending utterance index; utterances without frames are left out
+bool build_speaker_lists(const int32_t *utt_spk, const int64_t *frames, int n_utt, int n_spk, std::vector<int32_t> &off,
+                         std::vector<int32_t> &list);
+
 // exp(-2*pi*i*k/n) for k in [0, count), evaluated in double and rounded once to float.
 void build_twiddles(int n, int count, std::vector<float> &re_im_interleaved);
 

@@ -16,6 +16,7 @@
 #include <mutex>
 #include <vector>
 #include "mfx_delta_dev.h"
+#include "mfx_norm_dev.h"
 
 namespace mfx {
 
@@ -266,22 +267,9 @@ __global__ void __launch_bounds__(256, 7) k_delta16(DeltaParams p)
 // Statistics cover the first `stat_rows` rows of the segment (Segment::pad; 0 = all n_out rows): the reference
 // computes them over the block it delivers and re-uses them for the flush rows (mfcccpu.cpp:377-388).
 // ------------------------------------------------------------------------------------------------
-constexpr int kNormChunkRows = 4096;
 constexpr size_t kNormSegLdsBytes = 54 * 1024; // k_norm_seg: dynamic LDS per block (1024 rows of 13 columns: a 10 s utterance; two blocks per CU)
 
-__device__ __forceinline__ void norm_finish_to(float *st, int cols, int norm_type, int c, int n, double S, double S2, float mn,
-                                               float mx)
-{
-    const float mean = (float)(S / n);
-    float mult = 1.f;
-    if (norm_type == 2)
-        mult = (float)sqrt((n - 1) / (S2 - S * (S / n)));
-    else if (norm_type == 3)
-        mult = 1.f / fmaxf(fabsf(mn - mean), fabsf(mx - mean));
-    st[c] = mean;
-    st[cols + c] = mult;
-}
-
+// (kNormChunkRows, norm_finish_to and the summation itself, norm_rows_totals: mfx_norm_dev.h, shared with mfx_speakers.hip)
 __device__ __forceinline__ void norm_finish(const NormParams &p, int seg, int c, int n, double S, double S2, float mn, float mx)
 {
     norm_finish_to(p.stats + (int64_t)seg * 2 * p.cols, p.cols, p.norm_type, c, n, S, S2, mn, mx);
@@ -296,36 +284,11 @@ __global__ void __launch_bounds__(256) k_norm_stats(NormParams p)
     const int r0 = blockIdx.x * kNormChunkRows;
     if (r0 >= n && blockIdx.x > 0) return;
     const int r1 = min(n, r0 + kNormChunkRows);
-    int lg = 0;
-    while ((1 << lg) < p.cols) ++lg;
-    const int Cp = 1 << lg, rpp = 256 >> lg;          // columns per row of threads, rows per pass (cols <= 256)
-    const int tid = threadIdx.x, rr = tid >> lg, c = tid & (Cp - 1);
+    const int lg = norm_lg(p.cols);                   // 2^lg threads per row of threads, 256 >> lg rows per pass (cols <= 256)
+    const int tid = threadIdx.x, rr = tid >> lg, c = tid & ((1 << lg) - 1);
     const float *base = p.data + (sg.out_row0 + p.row_off) * (int64_t)p.pitch + p.col0;
-    double sum = 0, sum2 = 0;
-    float mn = 3.402823466e+38f, mx = -3.402823466e+38f;
-    if (c < p.cols)
-        for (int r = r0 + rr; r < r1; r += rpp) {
-            const float v = base[(int64_t)r * p.pitch + c];
-            sum += v;
-            sum2 += (double)(v * v);
-            mn = fminf(mn, v);
-            mx = fmaxf(mx, v);
-        }
-    s_sum[tid] = sum;
-    s_sum2[tid] = sum2;
-    s_min[tid] = mn;
-    s_max[tid] = mx;
-    __syncthreads();
-    for (int s = rpp >> 1; s > 0; s >>= 1) {
-        if (rr < s) {
-            const int o = tid + (s << lg);
-            s_sum[tid] += s_sum[o];
-            s_sum2[tid] += s_sum2[o];
-            s_min[tid] = fminf(s_min[tid], s_min[o]);
-            s_max[tid] = fmaxf(s_max[tid], s_max[o]);
-        }
-        __syncthreads();
-    }
+    norm_rows_totals<false>([&](int r, int cc) { return base[(int64_t)r * p.pitch + cc]; }, r0, r1, p.cols, lg, tid, s_sum, s_sum2, s_min,
+                            s_max);
     if (rr == 0 && c < p.cols) {
         if (p.chunks <= 1) {
             norm_finish(p, blockIdx.y, c, n, s_sum[tid], s_sum2[tid], s_min[tid], s_max[tid]);
@@ -426,37 +389,10 @@ __global__ void __launch_bounds__(kNormSegThreads) k_norm_seg(NormParams p)
         }
         __syncthreads();
     }
-    int lg = 0;
-    while ((1 << lg) < cols) ++lg;
-    const int Cp = 1 << lg, rpp = 256 >> lg;
-    const int rr = tid >> lg, c = tid & (Cp - 1);
-    double sum = 0, sum2 = 0;
-    float mn = 3.402823466e+38f, mx = -3.402823466e+38f;
-    if (c < cols && tid < 256)
-        for (int r = rr; r < n; r += rpp) {
-            const float v = in_lds ? s_rows[r * cols + c] : base[(int64_t)r * p.pitch + c];
-            sum += v;
-            sum2 += (double)(v * v);
-            mn = fminf(mn, v);
-            mx = fmaxf(mx, v);
-        }
-    if (tid < 256) {
-        s_sum[tid] = sum;
-        s_sum2[tid] = sum2;
-        s_min[tid] = mn;
-        s_max[tid] = mx;
-    }
-    __syncthreads();
-    for (int s = rpp >> 1; s > 0; s >>= 1) {
-        if (rr < s) { // (rr < s <= rpp / 2: threads of the first 256 only)
-            const int o = tid + (s << lg);
-            s_sum[tid] += s_sum[o];
-            s_sum2[tid] += s_sum2[o];
-            s_min[tid] = fminf(s_min[tid], s_min[o]);
-            s_max[tid] = fmaxf(s_max[tid], s_max[o]);
-        }
-        __syncthreads();
-    }
+    const int lg = norm_lg(cols);
+    const int rr = tid >> lg, c = tid & ((1 << lg) - 1);
+    norm_rows_totals<true>([&](int r, int cc) { return in_lds ? s_rows[r * cols + cc] : base[(int64_t)r * p.pitch + cc]; }, 0, n, cols, lg,
+                           tid, s_sum, s_sum2, s_min, s_max);
     if (rr == 0 && c < cols) {
         norm_finish_to(stats, cols, p.norm_type, c, n, s_sum[tid], s_sum2[tid], s_min[tid], s_max[tid]);
         s_st[c] = stats[c]; // (this thread's own writes)

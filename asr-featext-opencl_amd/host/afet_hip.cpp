@@ -21,6 +21,9 @@
 // single-block flush behaviour (B1) is not applied to converted files.  Without the option nothing changes.
 // --alpha-file gives every input file its own warp factor: the files of a batch then run with mfx_batch_set_alphas (one
 // launch sequence for all factors), files on the per-file loop with set_alpha of their own factor.
+// --spk-file gives every input file a speaker label: the normaliser's statistics are pooled over each speaker's files
+// (mfx_batch_set_speakers) in two passes over the list -- pass 1 runs the batches and carries their accumulators from batch
+// to batch, pass 2 runs them again with the final accumulators and writes the files.  Batches only, one device.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -50,6 +53,9 @@ struct Options {
     float alpha_min = 1.f, alpha_max = 1.f, alpha_step = 1.f;
     std::string alpha_file;        // --alpha-file: one warp factor per line, in the order of the input list
     std::vector<float> file_alpha; // its factors: file i of the list is extracted with file_alpha[i]
+    std::string spk_file;          // --spk-file: one speaker label per line, in the order of the input list
+    std::vector<int> file_spk;     // its labels as ids, numbered by first appearance: file i belongs to speaker file_spk[i]
+    int n_spk = 0;
     int sample_limit = 10000000, device = 0;
     bool bug_compat = true;
     int method = MFX_METHOD_MFCC, model_order = 8; // --method MFCC|PLP|TRAPS, --model-order (ASR_OCL.cpp:54-56: default 8)
@@ -285,6 +291,33 @@ void write_rows(FILE *out, const float *rows, int n, int width, int first_frame,
     }
     for (auto &x : th) x.join();
     for (int t = 0; t < T; ++t) std::fwrite(buf.data() + (size_t)((int64_t)n * t / T) * per_row, 1, used[t], out);
+}
+
+// --spk-file: speaker labels (one per line; blank lines skipped, surrounding white space dropped) -> ids by first appearance
+int map_speaker_labels(const std::vector<std::string> &labels, std::vector<int> &ids)
+{
+    std::vector<std::string> seen;
+    ids.clear();
+    for (const std::string &l : labels) {
+        size_t k = 0;
+        while (k < seen.size() && seen[k] != l) ++k;
+        if (k == seen.size()) seen.push_back(l);
+        ids.push_back((int)k);
+    }
+    return (int)seen.size();
+}
+
+bool read_label_lines(FILE *f, std::vector<std::string> &labels)
+{
+    char line[1024];
+    while (std::fgets(line, sizeof(line), f)) {
+        std::string l(line);
+        const size_t a = l.find_first_not_of(" \t\r\n");
+        if (a == std::string::npos) continue; // (blank line)
+        const size_t b = l.find_last_not_of(" \t\r\n");
+        labels.push_back(l.substr(a, b - a + 1));
+    }
+    return true;
 }
 
 // --timing: wall time per phase, summed over the files of all workers (dev aid; printed at exit)
@@ -641,17 +674,21 @@ void worker(const Options &o, int device, float sr, const std::vector<std::strin
             // largest block one set_input takes (parambase.cpp:12-13,16-19; the extractor reports the same number)
             const int limit0 = (int)std::floor(float(o.sample_limit - (W - S)) / S) * (int)S + (int)(W - S);
             std::future<std::unique_ptr<MfccHip>> created = std::async(std::launch::async, make_param);
-            prep = std::async(std::launch::async, [&, limit0] {
-                return prepare_batch(slots[0], o, files, next, sr, cap, limit0, (int)W, (int)S, D);
-            });
+            if (o.file_spk.empty()) // (--spk-file walks the list twice, on its own: below)
+                prep = std::async(std::launch::async, [&, limit0] {
+                    return prepare_batch(slots[0], o, files, next, sr, cap, limit0, (int)W, (int)S, D);
+                });
+            auto prep_wait = [&] {
+                if (prep.valid()) prep.wait();
+            };
             try {
                 param_owner = created.get();
             } catch (...) {
-                prep.wait();
+                prep_wait();
                 throw;
             }
             if (param_owner->get_input_buffer_size() != limit0) {
-                prep.wait();
+                prep_wait();
                 throw std::runtime_error("input block size mismatch");
             }
         } else {
@@ -713,6 +750,63 @@ void worker(const Options &o, int device, float sr, const std::vector<std::strin
                 }
                 if (g_time.on) g_time.write_wall += now_ns() - tww;
             };
+            if (!o.file_spk.empty()) {
+                // ---- --spk-file: two passes over the same batches (prepare_batch cuts the list by file sizes: the same cut
+                // both times).  Pass 1 pools: every batch starts from the accumulators of the batches before it and writes
+                // nothing.  Pass 2 normalises every batch with the final accumulators and writes its files.  A speaker's
+                // files keep their order, so the statistics are those of one batch holding the whole list.  The reference
+                // has no such rows: its single-block flush behaviour (B1) is not applied to them.
+                const int Wn = o.norm_after_dyn ? width : cols;
+                std::vector<long long> count((size_t)o.n_spk, 0);
+                std::vector<double> acc((size_t)o.n_spk * 4 * Wn, 0.0);
+                bool have_prior = false;
+                Batch &b = slots[0];
+                for (int pass = 1; pass <= 2; ++pass) {
+                    std::atomic<size_t> at{0};
+                    while (prepare_batch(b, o, files, at, sr, cap, limit, (int)W, (int)S, D)) {
+                        std::vector<long long> off, len, row0;
+                        std::vector<int> spk, rates;
+                        std::vector<float> al;
+                        std::vector<BatchItem *> in_batch;
+                        for (BatchItem &it : b.items) {
+                            if (!it.error.empty()) throw std::runtime_error(it.error);
+                            if (it.stream)
+                                throw std::runtime_error("--spk-file: \"" + files[2 * it.file] +
+                                                         "\" would take the per-file loop (longer than one block, too short for the "
+                                                         "deltas, or an alpha sweep): speakers are pooled over batches of whole files only");
+                            off.push_back(it.off);
+                            len.push_back(it.len);
+                            spk.push_back(o.file_spk[it.file]);
+                            rates.push_back(it.rate);
+                            if (!o.file_alpha.empty()) al.push_back(o.file_alpha[it.file]);
+                            in_batch.push_back(&it);
+                        }
+                        row0.resize(in_batch.size());
+                        b.width = width;
+                        b.total_rows = o.resample_to > 0 ? param.batch_plan_rates((int)in_batch.size(), off.data(), len.data(), rates.data(),
+                                                                                  o.resample_zeros, row0.data())
+                                                         : param.batch_plan((int)in_batch.size(), off.data(), len.data(), row0.data());
+                        if (!al.empty()) param.batch_set_alphas(al.data(), (int)al.size());
+                        param.batch_set_speakers(spk.data(), (int)spk.size(), o.n_spk, have_prior ? count.data() : nullptr,
+                                                 have_prior ? acc.data() : nullptr, pass == 2);
+                        float *rows = (float *)b.rows.get((size_t)std::max<long long>(b.total_rows, 1) * width * sizeof(float));
+                        param.batch_run_host((const short *)b.pcm.p, b.samples, rows);
+                        if (pass == 1) {
+                            if (b.total_rows > 0) {
+                                param.batch_speaker_stats(count.data(), acc.data(), nullptr);
+                                have_prior = true;
+                            }
+                            continue;
+                        }
+                        for (size_t k = 0; k < in_batch.size(); ++k) {
+                            in_batch[k]->row0 = row0[k];
+                            if (in_batch[k]->frames != param.batch_frames(in_batch[k]->conv_len)) throw std::runtime_error("frame count mismatch");
+                        }
+                        write_batch(&b);
+                    }
+                }
+                return;
+            }
             int cur = 0;
             std::future<void> writer;
             for (;;) {
@@ -868,6 +962,23 @@ int main(int argc, char **argv)
         else if (a == "--alpha-max") o.alpha_max = (float)std::atof(val());
         else if (a == "--alpha-step") o.alpha_step = (float)std::atof(val());
         else if (a == "--alpha-file") o.alpha_file = val();
+        else if (a == "--spk-file") o.spk_file = val();
+        else if (a == "--selftest-spk-labels") { // the label -> id mapping of --spk-file, on a file of labels: prints the ids
+            FILE *fl = std::fopen(val(), "r");
+            if (!fl) {
+                std::fprintf(stderr, "can't read the label file\n");
+                return 2;
+            }
+            std::vector<std::string> labels;
+            read_label_lines(fl, labels);
+            std::fclose(fl);
+            std::vector<int> ids;
+            const int n = map_speaker_labels(labels, ids);
+            std::printf("%d speakers:", n);
+            for (int id : ids) std::printf(" %d", id);
+            std::printf("\n");
+            return 0;
+        }
         else if (a == "--sample-limit") o.sample_limit = std::atoi(val());
         else if (a == "--dev") o.device = std::atoi(val());
         else if (a == "--devs") { // comma separated device list; an id may repeat (two workers on one GPU)
@@ -935,6 +1046,8 @@ int main(int argc, char **argv)
                         "         [--batch-mb n (PCM per batch of whole files; 0 = per-file loop)] [--io-threads n]\n"
                         "  --alpha-file: one warp factor per line, in the order of the input files; files of a batch run with\n"
                         "                their own factors in one launch sequence\n"
+                        "  --spk-file: one speaker label per line, in the order of the input files (needs --norm 1..3, batches, one\n"
+                        "                device): CMN / CVN / MINMAX statistics pooled over each speaker's files, in two passes\n"
                         "         [--resample-to hz [--resample-zeros n]]\n"
                         "  --resample-to: extract at hz instead of the first file's rate; files at other rates are converted on the\n"
                         "                device (Hann-windowed sinc, n zero crossings per side, default 6)\n"
@@ -974,6 +1087,33 @@ int main(int argc, char **argv)
             std::fprintf(stderr, "--alpha-file holds %zu warp factors for %zu input files\n", o.file_alpha.size(), files.size() / 2);
             return 2;
         }
+    }
+    if (!o.spk_file.empty()) {
+        if (o.norm < 1 || o.norm > 3) {
+            std::fprintf(stderr, "--spk-file pools the normaliser's statistics: it needs --norm 1, 2 or 3\n");
+            return 2;
+        }
+        if (o.batch_mb <= 0) {
+            std::fprintf(stderr, "--spk-file pools speakers over batches of whole files: --batch-mb must be positive\n");
+            return 2;
+        }
+        if (o.devices.size() > 1) {
+            std::fprintf(stderr, "--spk-file runs on one device: --devs names more than one\n");
+            return 2;
+        }
+        FILE *fs = std::fopen(o.spk_file.c_str(), "r");
+        if (!fs) {
+            std::fprintf(stderr, "can't read --spk-file %s\n", o.spk_file.c_str());
+            return 2;
+        }
+        std::vector<std::string> labels;
+        read_label_lines(fs, labels);
+        std::fclose(fs);
+        if (labels.size() != files.size() / 2) {
+            std::fprintf(stderr, "--spk-file holds %zu labels for %zu input files\n", labels.size(), files.size() / 2);
+            return 2;
+        }
+        o.n_spk = map_speaker_labels(labels, o.file_spk);
     }
     if (o.method == MFX_METHOD_TRAPS) { // whole files through the batch entries: no per-file loop, no alpha loop, no DCT options
         if (o.batch_mb <= 0) {

@@ -114,6 +114,13 @@ public:
     // one warp factor per utterance of the planned batch (mfx_batch_set_alphas); nullptr / 0 clears the list, and so does
     // the next batch_plan
     void batch_set_alphas(const float *alphas, int n_utt);
+    // per-speaker normalisation of the planned batch (mfx_batch_set_speakers): one speaker id per utterance; the prior (both
+    // arrays or neither) carries the accumulators of earlier batches; prior_only: statistics from the prior alone.
+    // nullptr / 0 clears the list, and so does the next batch_plan
+    void batch_set_speakers(const int *utt_spk, int n_utt, int n_spk, const long long *prior_count = nullptr,
+                            const double *prior_acc = nullptr, bool prior_only = false);
+    // what the last run used: count [n_spk], acc [n_spk][4][Wn] (S, S2, min, max), stats [n_spk][2][Wn]; any may be null
+    void batch_speaker_stats(long long *count, double *acc, float *stats);
     // mfx_set_alpha at once, for the batch entries (there is no apply() to carry m_alpha there)
     void set_warp(float alpha);
     long long batch_frames(long long samples) const;

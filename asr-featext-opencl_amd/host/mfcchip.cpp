@@ -192,6 +192,18 @@ void MfccHip::batch_run_host(const short *pcm, long long samples_total, float *o
 
 void MfccHip::batch_set_alphas(const float *alphas, int n_utt) { check(mfx_batch_set_alphas(m_handle, alphas, n_utt)); }
 
+void MfccHip::batch_set_speakers(const int *utt_spk, int n_utt, int n_spk, const long long *prior_count, const double *prior_acc,
+                                 bool prior_only)
+{
+    check(mfx_batch_set_speakers(m_handle, (const int32_t *)utt_spk, n_utt, n_spk, (const int64_t *)prior_count, prior_acc,
+                                 prior_only ? MFX_SPK_PRIOR_ONLY : MFX_SPK_POOL));
+}
+
+void MfccHip::batch_speaker_stats(long long *count, double *acc, float *stats)
+{
+    check(mfx_batch_speaker_stats(m_handle, (int64_t *)count, acc, stats));
+}
+
 void MfccHip::set_warp(float alpha)
 {
     m_alpha = alpha;

@@ -76,6 +76,7 @@ EXPORTED_SYMBOLS = (
     "mfx_sessions_delivered", "mfx_host_session_step",
     "mfx_batch_plan_rates", "mfx_batch_resample_layout", "mfx_host_resample_taps", "mfx_host_resampled_length",
     "mfx_host_resample_layout", "mfx_host_resample_tile",
+    "mfx_batch_set_speakers", "mfx_batch_speaker_stats", "mfx_host_speaker_lists",
 )
 
 
@@ -167,6 +168,10 @@ def load_library():
     L.mfx_host_resampled_length.argtypes, L.mfx_host_resampled_length.restype = [i64, i32, i32], i64
     L.mfx_host_resample_layout.argtypes, L.mfx_host_resample_layout.restype = [i32, p64, p32, i32, p64, p64], i64
     L.mfx_host_resample_tile.argtypes, L.mfx_host_resample_tile.restype = [i32, i32, i32, C.c_float, i32], i32
+    dp = C.POINTER(C.c_double)
+    L.mfx_batch_set_speakers.argtypes = [vp, p32, i32, i32, p64, dp, i32]
+    L.mfx_batch_speaker_stats.argtypes = [vp, p64, dp, fp]
+    L.mfx_host_speaker_lists.argtypes, L.mfx_host_speaker_lists.restype = [i32, p32, p64, i32, p32, p32], i64
     _lib = L
     return L
 
@@ -290,6 +295,25 @@ def host_alpha_runs(alphas, frames, window=None):
         raise MfxError(int(nt), "mfx_host_alpha_runs failed")
     nt = int(nt)
     return tables[:nt].copy(), off[:nt + 1].copy(), runs[:int(off[nt])].copy()
+
+
+def host_speaker_lists(utt_spk, frames, n_spk=None):
+    """Speaker lists of batch_set_speakers exactly as uploaded (host code, no GPU needed): (off [n_spk + 1], list) -- speaker
+    s owns list[off[s]:off[s + 1]], its utterances in ascending order, frameless utterances left out."""
+    L = load_library()
+    ids = np.ascontiguousarray(utt_spk, dtype=np.int32)
+    f = np.ascontiguousarray(frames, dtype=np.int64)
+    assert ids.size == f.size
+    if n_spk is None:
+        n_spk = int(ids.max()) + 1 if ids.size else 0
+    off = np.zeros(int(n_spk) + 1, np.int32)
+    lst = np.zeros(max(ids.size, 1), np.int32)
+    p32 = C.POINTER(C.c_int32)
+    n = L.mfx_host_speaker_lists(int(ids.size), ids.ctypes.data_as(p32), f.ctypes.data_as(C.POINTER(C.c_int64)), int(n_spk),
+                                 off.ctypes.data_as(p32), lst.ctypes.data_as(p32))
+    if n < 0:
+        raise MfxError(int(n), "mfx_host_speaker_lists failed")
+    return off, lst[:int(n)].copy()
 
 
 def host_xform_operands(A):
@@ -444,6 +468,7 @@ KERNEL_TABLE = (
 )
 
 
+SPK_POOL, SPK_PRIOR_ONLY = 0, 1                            # mfx_batch_set_speakers modes (include/mfx.h)
 ENGINE_NO_FRONT1024, ENGINE_FUSE_DELTA, ENGINE_NO_FRONT2048, ENGINE_STREAM_KERNELS, ENGINE_NORM_TWO_KERNELS = 1, 2, 4, 8, 16
 ENGINE_DMA_SMALL_BLOCKS, ENGINE_NO_DCT_SPLIT, ENGINE_NO_STUFF256, ENGINE_FRONT1024_12_WAVES = 32, 64, 128, 256     # mfx_config.engine bits (include/mfx.h)
 ENGINE_TRAPS_VALU, ENGINE_XFORM_VALU, ENGINE_SESS_NARROW_LOADS = 512, 1024, 2048
@@ -670,6 +695,51 @@ class MfccHip:
         self._chk(self._L.mfx_batch_set_transform(
             self._h, int(left), int(right), out_dim, n_xf, a.ctypes.data_as(fpt), None if bb is None else bb.ctypes.data_as(fpt),
             None if idx is None else idx.ctypes.data_as(ipt), 0 if idx is None else int(idx.size)))
+
+    def norm_width(self):
+        """Wn of the speaker entries: the normalised columns of a row (all of them after the deltas, else the statics)."""
+        w = self.get_output_data_width()
+        return w if self.cfg.norm_after_dyn else w // (1 + self.cfg.dyn)
+
+    def batch_set_speakers(self, utt_spk, n_spk=None, prior=None, mode=SPK_POOL):
+        """Per-speaker CMN / CVN / MINMAX (mfx_batch_set_speakers): utt_spk is one speaker id per planned utterance; the
+        normaliser's statistics are pooled over each speaker's utterances.  n_spk: number of speakers (None: largest id +
+        1); prior: (count [n_spk], acc [n_spk][4][Wn]) of an earlier batch_speaker_stats or sharding.merge_speaker_acc;
+        mode SPK_PRIOR_ONLY takes the statistics from the prior alone.  utt_spk = None clears the list; a later batch_plan
+        clears it too."""
+        if utt_spk is None:
+            self._chk(self._L.mfx_batch_set_speakers(self._h, None, 0, 0, None, None, 0))
+            self._n_spk = 0
+            return
+        ids = np.ascontiguousarray(utt_spk, dtype=np.int32)
+        if n_spk is None:
+            n_spk = int(ids.max()) + 1 if ids.size else 1
+        n_spk = int(n_spk)
+        pc = pa = None
+        if prior is not None:
+            pc = np.ascontiguousarray(prior[0], dtype=np.int64)
+            pa = np.ascontiguousarray(prior[1], dtype=np.float64)
+            if pc.size != n_spk or pa.size != n_spk * 4 * self.norm_width():
+                raise ValueError("prior must be (count [n_spk], acc [n_spk][4][Wn])")
+        self._chk(self._L.mfx_batch_set_speakers(
+            self._h, ids.ctypes.data_as(C.POINTER(C.c_int32)), int(ids.size), n_spk,
+            None if pc is None else pc.ctypes.data_as(C.POINTER(C.c_int64)),
+            None if pa is None else pa.ctypes.data_as(C.POINTER(C.c_double)), int(mode)))
+        self._n_spk = n_spk
+
+    def batch_speaker_stats(self):
+        """(count [n_spk] int64, acc [n_spk][4][Wn] float64 = S, S2, min, max, stats [n_spk][2][Wn] float32 = mean,
+        multiplier) the last batch run used, while a speaker list is in force (MfxError with status -8 otherwise)."""
+        n, wn = int(getattr(self, "_n_spk", 0)), self.norm_width()
+        count = np.zeros(n, np.int64)
+        acc = np.zeros((n, 4, wn), np.float64)
+        stats = np.zeros((n, 2, wn), np.float32)
+        self._chk(self._L.mfx_batch_speaker_stats(self._h, count.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                  acc.ctypes.data_as(C.POINTER(C.c_double)),
+                                                  stats.ctypes.data_as(C.POINTER(C.c_float))))
+        return count, acc, stats
+
+    host_speaker_lists = staticmethod(host_speaker_lists)
 
     def batch_output_width(self):
         """Row width of the batch entries' output: out_dim while a transform is in force, else get_output_data_width()."""

@@ -61,3 +61,30 @@ def max_over_ranks(value, dist=None):
         t = t.cuda()
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     return float(t.item())
+
+
+def merge_speaker_acc(parts):
+    """Sum of the per-speaker accumulators of several ranks (MfccHip.batch_speaker_stats of each rank's pooling pass):
+    parts is a sequence of (count [n_spk] int64, acc [n_spk][4][Wn] float64) in ascending rank order; counts, S and S2
+    are added and min / max taken in that order, starting from rank 0's values as they are.  Returns (count, acc): the
+    prior of every rank's second pass (``batch_set_speakers(..., prior=(count, acc), mode=SPK_PRIOR_ONLY)``).  Utterances
+    of one speaker may lie on different devices (shard_indices deals them round-robin): pass 1 pools per rank, the host
+    merges, pass 2 normalises."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("no accumulators to merge")
+    count = np.array(parts[0][0], dtype=np.int64, copy=True)
+    acc = np.array(parts[0][1], dtype=np.float64, copy=True)
+    if acc.ndim != 3 or acc.shape[0] != count.size or acc.shape[1] != 4:
+        raise ValueError("acc must be [n_spk][4][Wn]")
+    for c, a in parts[1:]:
+        c = np.asarray(c, dtype=np.int64)
+        a = np.asarray(a, dtype=np.float64)
+        if c.shape != count.shape or a.shape != acc.shape:
+            raise ValueError("accumulators of different shapes")
+        count += c
+        acc[:, 0] += a[:, 0]
+        acc[:, 1] += a[:, 1]
+        acc[:, 2] = np.minimum(acc[:, 2], a[:, 2])
+        acc[:, 3] = np.maximum(acc[:, 3], a[:, 3])
+    return count, acc

@@ -269,6 +269,49 @@ int mfx_batch_set_transform(mfx_handle *h, int32_t left, int32_t right, int32_t 
 /* out_dim while a transform is in force, else mfx_get_output_data_width */
 int mfx_batch_output_width(const mfx_handle *h);
 
+/* Per-speaker CMN / CVN / MINMAX ("Per-speaker normalisation"): the statistics of the normaliser pooled over all
+ * utterances of a speaker -- compute-cmvn-stats --spk2utt, then apply-cmvn --utt2spk, of a Kaldi-style recipe -- between the
+ * per-utterance warp factor (mfx_batch_set_alphas) and the per-speaker transform (mfx_batch_set_transform).  No reference
+ * analogue: its NormalizerCPU keeps one block's statistics (normalizercpu.cpp:22-27).
+ * utt_spk[u] in [0, n_spk) is the speaker of utterance u of the planned batch.  Wn is the number of normalised columns:
+ * mfx_get_output_data_width when norm_after_dyn, else the static column count.
+ *   Scope.  Valid after mfx_batch_plan / mfx_batch_plan_rates (MFX_ERR_STATE before one); MFX_ERR_CONFIG on a handle with
+ *     norm == MFX_NORM_NONE, MFX_ERR_DEVICE on a planning handle.  utt_spk == NULL with n_utt == 0 clears the list, and so
+ *     does a later plan: the handle is back on today's kernels and bits.  MFX_ERR_ARG: n_utt is not the planned count, an id
+ *     outside [0, n_spk), n_spk outside 1 .. 2^20, only one of the two prior arrays, a negative prior_count, a mode other
+ *     than the two below, MFX_SPK_PRIOR_ONLY without a prior or with a speaker of count 0 that owns an utterance with frames.
+ *     The lists, the prior, the per-chunk partial totals, the accumulators and the statistics are allocated and uploaded
+ *     HERE (the call waits for the handle's streams); mfx_batch_run_device still allocates nothing.
+ *   Statistics.  Every utterance contributes all T of its rows (mfx_config.batch_norm_stats is ignored).  Per utterance and
+ *     column the totals -- S and S2 in double, S2 from the float32 product v * v, min and max -- are formed exactly as
+ *     k_norm_stats forms them for a segment of those rows: the same thread per (row class, column), the same order of double
+ *     additions, the same tree, chunks of 4096 rows combined in ascending order.  Per speaker the accumulator starts from
+ *     the prior if one is given (a prior of count 0 counts as none), else from the totals of the speaker's first
+ *     contributing utterance as they are; the remaining utterances are added in ascending utterance index, min / max
+ *     likewise.  With n = prior count + pooled rows: mean = (float)(S / n); CVN multiplier (float)sqrt((n - 1) / (S2 - S (S /
+ *     n))); MINMAX 1 / max(|min - mean|, |max - mean|) in float32; CMN 1 -- the per-utterance normaliser's formulas on those
+ *     doubles.  MFX_SPK_PRIOR_ONLY: the statistics come from the prior alone, the batch's rows are not accumulated.  A
+ *     speaker's bits therefore do not depend on the other speakers, on how the ids are numbered, or on unrelated utterances
+ *     of the batch.  A speaker without rows and without a prior has n = 0 and non-finite statistics, which no row reads.
+ *   Apply.  Every row of utterance u becomes (v - mean[spk]) * mult[spk] (v - mean[spk] for CMN), the float32 expression of
+ *     the per-utterance normaliser, in its place in the run: before the deltas or after them as configured, on the stream
+ *     the tail runs on.  Everything else in the run is unchanged -- front end, MFX_ENGINE_* bits, alpha list, rates plan,
+ *     mfx_batch_overlap, the transform (which reads the normalised rows).  While a list is in force mfx_batch_run_host takes
+ *     its unsliced path (a speaker may span slices) and mfx_debug_read kind 6 returns 0 elements.
+ *   Read-back.  mfx_batch_speaker_stats synchronises and returns what the last run used: count [n_spk], acc [n_spk][4][Wn]
+ *     (S, S2, min, max; prior plus batch, in MFX_SPK_PRIOR_ONLY the prior) and stats [n_spk][2][Wn] (mean, multiplier).  Any
+ *     output may be NULL.  MFX_ERR_STATE without a list in force or before a run.  Feeding a run's count and acc as the next
+ *     batch's prior gives the same bits as one batch holding both, provided each speaker's utterances keep their order;
+ *     summing the accumulators of several devices on the host (sharding.merge_speaker_acc) and running MFX_SPK_PRIOR_ONLY
+ *     is the multi-GPU flow.
+ * The session entries and the streaming interface are untouched and ignore the list. */
+enum { MFX_SPK_POOL = 0, MFX_SPK_PRIOR_ONLY = 1 };
+int mfx_batch_set_speakers(mfx_handle *h, const int32_t *utt_spk, int32_t n_utt, int32_t n_spk,
+                           const int64_t *prior_count, /* [n_spk] or NULL */
+                           const double *prior_acc,    /* [n_spk][4][Wn]: S, S2, min, max; or NULL */
+                           int32_t mode);
+int mfx_batch_speaker_stats(mfx_handle *h, int64_t *count, double *acc, float *stats /* [n_spk][2][Wn] mean, multiplier */);
+
 /* ---- sample-rate conversion in front of a batch ("Sample-rate conversion").  No reference analogue: the
  *      reference refuses a file whose rate differs from the first file's (ASR_OCL.cpp:191). ----
  *
@@ -421,6 +464,11 @@ int mfx_host_traps_basis(int32_t traps_len, int32_t traps_dct_len, float *basis)
  * Test / inspection aid. */
 int64_t mfx_host_alpha_runs(int32_t n_utt, const float *alphas, const int64_t *frames, int64_t win_row0, int64_t win_rows,
                             float *tables, int32_t *off, int64_t *runs);
+/* Speaker lists of mfx_batch_set_speakers as uploaded: speaker s owns list[off[s] .. off[s + 1]), its utterances in ascending
+ * utterance index, frameless utterances (frames[u] <= 0) left out.  off [n_spk + 1], list [<= n_utt]; either may be NULL.
+ * Returns the list's length, or MFX_ERR_ARG (an id outside [0, n_spk)).  Test / inspection aid. */
+int64_t mfx_host_speaker_lists(int32_t n_utt, const int32_t *utt_spk, const int64_t *frames, int32_t n_spk,
+                               int32_t *off /* [n_spk+1] */, int32_t *list /* [<= n_utt] */);
 /* One transform of mfx_batch_set_transform as k_splice_affine streams it: for every step of 4 taps and every tile of 16
  * outputs the 64 lanes' operands of v_mfma_f32_16x16x4_f32, out[(s * tiles + tile) * 64 + lane] =
  * A[16 tile + (lane & 15)][4 s + (lane >> 4)], zero beyond the matrix; tiles = ceil(out_dim / 16), steps = ceil(in_dim / 4).
