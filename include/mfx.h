@@ -216,7 +216,10 @@ int mfx_batch_plan(mfx_handle *h, int32_t n_utt, const int64_t *offsets, const i
  * elements is odd the kernels read the 32-bit word that holds the last sample whole (2 bytes past the
  * last element, inside any device allocation; that half-word only meets a zero window tap).
  * With normalisation on, an utterance's statistics are the reference's for a file consumed as one
- * block (mfx_config.batch_norm_stats). */
+ * block (mfx_config.batch_norm_stats).
+ * d_out may have any 4-byte alignment and may lie anywhere in a device allocation (row k of a larger matrix, say): the rows are
+ * the same bits wherever it lies, and nothing outside [d_out, d_out + total_rows * width) is written (width =
+ * mfx_batch_output_width; pinned by tests/test_placement_gpu.py). */
 int mfx_batch_run_device(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_total, float *d_out);
 
 /* Per-utterance VTLN: one warp factor per utterance of the planned batch, in the plan's utterance order -- the alpha loop
@@ -390,6 +393,8 @@ int mfx_batch_run_host(mfx_handle *h, const int16_t *pcm, int64_t pcm_samples_to
  * nothing, and commits the sessions' state once its launches are queued; without a pending plan, or twice for one plan, it
  * returns MFX_ERR_STATE.  mfx_sessions_run_host is the same from / to host buffers (it synchronises, and may grow its
  * device copies).  mfx_sessions_delivered: E so far (0 for a fresh session).
+ * As for mfx_batch_run_device, d_out may have any 4-byte alignment and may lie anywhere in a device allocation: the rows are
+ * the same bits wherever it lies, and nothing outside [d_out, d_out + total_rows * width) is written.
  * Errors: MFX_ERR_ARG an id outside the range or twice in one push, a negative length or offset, a piece past
  * pcm_samples_total, a misaligned d_pcm (the 4-byte rule of mfx_batch_run_device); MFX_ERR_BUFFER_TOO_SMALL lengths[i] >
  * max_push_samples; MFX_ERR_STATE no mfx_set_window yet, no mfx_sessions_create yet, a TRAPS handle, a handle with norm !=
