@@ -1,5 +1,5 @@
 // mfx_api.cpp -- the C ABI of include/mfx.h, entry file: handle lifetime and tables, THE dispatch rule (choose_front),
-// profiling, the test taps.  The streaming interface is mfx_stream.cpp, the batch interface mfx_batch.cpp; the handle they
+// profiling, the test taps.  The streaming interface is mfx_stream.cpp, the batch interface mfx_batch*.cpp; the handle they
 // share is mfx_handle.h.
 //
 // All arithmetic on samples and features happens in the HIP kernels of mfx_front*.hip / mfx_tail.hip / mfx_plp.hip, all
@@ -389,7 +389,7 @@ extern "C" void mfx_destroy(mfx_handle *h)
     if (!h) return;
     if (!h->planning) { // (a planning handle has no device behind it)
         (void)hipSetDevice(h->device);
-        for (hipStream_t s : {h->stream, h->batch.stream2, h->batch.stream_up, h->batch.stream_dn})
+        for (hipStream_t s : {h->stream, h->batch.ov.stream2, h->batch.host.stream_up, h->batch.host.stream_dn})
             if (s) (void)hipStreamSynchronize(s);
     }
     delete h; // ~mfx_handle, then the buffers free themselves
@@ -655,8 +655,8 @@ extern "C" int mfx_synchronize(mfx_handle *h)
 {
     MFX_DEVICE_ENTRY(h);
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (h->batch.stream2) HIP_TRY(h, hipStreamSynchronize(h->batch.stream2));
-    h->batch.tail_pending[0] = h->batch.tail_pending[1] = false;
+    if (h->batch.ov.stream2) HIP_TRY(h, hipStreamSynchronize(h->batch.ov.stream2));
+    h->batch.ov.tail_pending[0] = h->batch.ov.tail_pending[1] = false;
     if (h->fuse.d_err.p) { // the fused delta stage reports a wait that ran out (never expected) instead of hanging
         int32_t flag = 0;
         HIP_TRY(h, hipMemcpy(&flag, h->fuse.d_err.p, sizeof(flag), hipMemcpyDeviceToHost));
@@ -721,8 +721,62 @@ FrontKind choose_front(const mfx_handle *h, bool aligned)
 // out: the spectrum goes through the slab and k_melcep_runs / k_plp_runs apply each table to its own rows.
 FrontKind batch_front(const mfx_handle *h)
 {
-    if (h->batch.alphas_on) return h->fast512 ? kSpec512 : kSpecGen;
+    if (h->batch.va.on) return h->fast512 ? kSpec512 : kSpecGen;
     return choose_front(h);
+}
+
+// The front end `kind` over the chunks of `w`, on h->stream -- the ONE place that launches it for the batch and the session
+// entries.  Fused kinds: one launch.  Spectrum kinds: magnitudes go through the slab in windows of its rows (bounded by row
+// span: chunk rows ascend), then k_melcep / k_plp per window.
+int launch_front(mfx_handle *h, FrontParams &p, FrontKind kind, bool aligned, const FrontWork &w)
+{
+    p.chunks = w.d_chunks;
+    p.n_chunks = (int32_t)w.n_chunks;
+    if (!is_spec_kind(kind)) {
+        if (kind == kFront512 || kind == kFront2048)
+            p.spec = h->d_spec.p; // unused by the fused kernels; a -DMFX_STAMPS dev build drops its cycle sums here
+        ProfScope ps(h, w.profile);
+        switch (kind) {
+        case kFront512: HIP_TRY(h, launch_front512(p, /*to_spectrum=*/false, aligned, h->nm16, h->stream)); break;
+        case kFront1024:
+            HIP_TRY(h, launch_front1024(p, aligned, h->nm16, h->stream, (h->cfg.engine & MFX_ENGINE_FRONT1024_12_WAVES) ? 12 : 16));
+            break;
+        case kFront2048: HIP_TRY(h, launch_front2048(p, h->num_cus, h->stream)); break;
+        default: HIP_TRY(h, launch_front_generic(p, /*fused=*/true, h->stream)); break;
+        }
+        return MFX_OK;
+    }
+    for (size_t c0 = 0, c1; c0 < w.n_chunks; c0 = c1) {
+        const int64_t row0 = w.h_chunks[c0].out_row;
+        int64_t rows = 0;
+        for (c1 = c0; c1 < w.n_chunks && w.h_chunks[c1].out_row + w.h_chunks[c1].n_frames - row0 <= w.slab_rows; ++c1)
+            rows = w.h_chunks[c1].out_row + w.h_chunks[c1].n_frames - row0;
+        FrontParams q = p;
+        q.chunks = w.d_chunks + c0;
+        q.n_chunks = (int32_t)(c1 - c0);
+        q.spec = w.slab - row0 * (int64_t)h->spec_pitch; // rows are addressed absolutely
+        q.spec_pitch = h->spec_pitch;
+        {
+            ProfScope ps(h, w.profile);
+            if (kind == kSpec512)
+                HIP_TRY(h, launch_front512(q, /*to_spectrum=*/true, aligned, h->nm16, h->stream));
+            else
+                HIP_TRY(h, launch_front_generic(q, /*fused=*/false, h->stream));
+        }
+        int rc;
+        if (w.runs) { // every table on its own rows of the window, one launch
+            RowRuns rr;
+            rr.runs = w.runs;
+            rr.off = w.run_off;
+            rr.row0 = row0;
+            rr.rows = rows;
+            rc = launch_cepstra_runs(h, *w.tables, q.spec, p.feat, p.feat_pitch, rr, w.h_run_off, w.h_runs, h->stream);
+        } else {
+            rc = launch_cepstra(h, h->own, w.slab, rows, p.feat + row0 * (int64_t)p.feat_pitch, p.feat_pitch, 1, 0, nullptr, h->stream);
+        }
+        if (rc != MFX_OK) return rc;
+    }
+    return MFX_OK;
 }
 
 extern "C" const char *mfx_dominant_kernel_name(const mfx_handle *h)
@@ -819,7 +873,7 @@ extern "C" int64_t mfx_debug_read(mfx_handle *h, int kind, void *dst, int64_t ds
     case 6: // normaliser statistics of the last batch run: [groups][n_utt][2][cols] (none while a speaker list is in force:
             // mfx_batch_speaker_stats returns those)
         src = h->batch.d_stats.p;
-        count = h->cfg.norm == MFX_NORM_NONE || h->batch.spk_on ? 0
+        count = h->cfg.norm == MFX_NORM_NONE || h->batch.spk.on ? 0
                                              : (int64_t)(h->cfg.norm_after_dyn ? h->width / h->cols : 1) * h->batch.n_utt * 2 * h->cols;
         break;
     case 7: // PLP autocorrelations of the last plain streaming apply(): [frames_with_context][lpc_order + 1]
@@ -827,8 +881,8 @@ extern "C" int64_t mfx_debug_read(mfx_handle *h, int kind, void *dst, int64_t ds
         count = h->plp ? (int64_t)h->st.block_wcnd * (h->lpc + 1) : 0;
         break;
     case 8: // converted PCM of the last batch run under a rates plan: int16, scratch layout (mfx_batch_resample_layout)
-        src = h->batch.d_rs_pcm.p;
-        count = h->batch.rs_on ? h->batch.rs_total * h->channels : 0;
+        src = h->batch.rs.d_pcm.p;
+        count = h->batch.rs.on ? h->batch.rs.total * h->channels : 0;
         esz = 2;
         break;
     default:

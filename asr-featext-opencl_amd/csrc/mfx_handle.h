@@ -1,8 +1,10 @@
 // mfx_handle.h -- internal to the host side of libmfcchip (not installed): the handle behind include/mfx.h, the buffer
-// types it owns, and the few helpers its three translation units share.
-//   mfx_api.cpp    lifetime, tables, kernel choice, profiling, test taps   (writes the shared part of the handle)
+// types it owns, and the few helpers its translation units share.
+//   mfx_api.cpp    lifetime, tables, kernel choice and front-end dispatch, profiling, test taps (writes the shared part)
 //   mfx_stream.cpp the streaming state machine and its host copies         (owns `st` and `sweep`)
-//   mfx_batch.cpp  the batch planner and runner, the fused-delta plan      (owns `batch` and `fuse`)
+//   mfx_batch_plan.cpp   the batch planner, the rates planner, the fused-delta plan (owns `batch`'s plan, `batch.rs`, `fuse`)
+//   mfx_batch_attach.cpp what is attached to a plan: warp factors, transform, speakers (owns `batch.va`, `.xf`, `.spk`)
+//   mfx_batch.cpp        the batch runner, device and host entries, overlap   (owns `batch.ov` and `batch.host`)
 //   mfx_sessions_host.cpp the session entries: many live streams per push       (owns `sess`)
 #pragma once
 #include "../../include/mfx.h"
@@ -139,71 +141,104 @@ struct SweepState {
                                           // rows a later get_output_data returns
 };
 
-// batch plan: mfx_batch.cpp
+// batch plan and what hangs on it: mfx_batch_plan.cpp builds it, mfx_batch_attach.cpp attaches to it, mfx_batch.cpp runs it
 struct BatchState {
+    // ---- the plan proper
+    bool planned = false;                // mfx_batch_plan / mfx_batch_plan_rates has succeeded
     int32_t n_utt = 0;
     int64_t total_rows = 0;
     std::vector<int64_t> utt_off, utt_len, utt_row;
+    std::vector<int64_t> utt_frames;     // [n_utt] rows of every utterance
     std::vector<mfx::Chunk> h_chunks;
     std::vector<int32_t> chunk_utt;      // utterance of every entry of h_chunks
     std::vector<int32_t> utt_chunk0;     // [n_utt + 1] first chunk of every utterance (chunks are in utterance order)
-    hipStream_t stream_up = nullptr, stream_dn = nullptr; // sliced mfx_batch_run_host: upload / download beside the kernels
-    hipEvent_t ev_up[16] = {}, ev_run[16] = {};
     DevBuf<mfx::Chunk> d_chunks;
     DevBuf<mfx::Segment> d_segs;
-    DevBuf<float> d_stats, d_spec_slab, d_host_out;
-    DevBuf<int16_t> d_host_pcm;          // mfx_batch_run_host: device copies of the caller's host buffers
+    DevBuf<float> d_stats, d_spec_slab;
     DevBuf<float> d_logmel;      // TRAPS: log mel rows [total_rows][mel_pitch] between the front end and k_traps
     int mel_pitch = 0;
     DevBuf<float> d_static16[2]; // compact [rows][16] statics between front end and delta (double buffered for overlap)
-    // optional overlap of the delta/normalisation tail of batch i with the front end of batch i+1
-    bool overlap = false;
-    hipStream_t stream2 = nullptr;
-    hipEvent_t ev_front[2] = {nullptr, nullptr}, ev_tail[2] = {nullptr, nullptr};
-    bool tail_pending[2] = {false, false};
-    unsigned seq = 0;
     int tiles_max = 0;
     bool aligned = true;                 // frames on aligned sample pairs (fill_front / choose_front read it)
-    // per-utterance warp factors (mfx_batch_set_alphas), tied to the plan: one table per distinct factor and, per table,
-    // the row runs of its utterances (build_alpha_runs); the batch then runs spectrum slab + k_melcep_runs / k_plp_runs
-    bool alphas_on = false;              // (batch_front reads it)
-    CepTables alpha_tables;
-    std::vector<int32_t> h_run_off;      // [tables + 1]
-    std::vector<int64_t> h_runs;         // [runs][2]
-    DevBuf<int32_t> d_run_off;
-    DevBuf<int64_t> d_runs;
-    // splice + affine transform (mfx_batch_set_transform), tied to the plan: while xf_on the run writes its rows to d_xf_y
-    // and k_splice_affine turns them into the caller's d_out as the last launch
-    bool planned = false;                // mfx_batch_plan has succeeded
-    bool xf_on = false;
-    int xf_left = 0, xf_right = 0, xf_out = 0;
-    DevBuf<float> d_xf_ops, d_xf_bias;   // [n_xf][steps][tiles][64], [n_xf][tiles * 16]
-    DevBuf<int32_t> d_xf_idx;            // [n_utt] transform of every utterance (empty: all 0)
-    DevBuf<float> d_xf_y;                // [total_rows][width]
-    // sample-rate conversion (mfx_batch_plan_rates), tied to the plan: while rs_on the run converts the caller's array into
-    // d_rs_pcm with one launch of k_resample and then does what it always does on d_rs_pcm; utt_off / utt_len above describe
-    // the scratch, rs_in_off / rs_in_len the caller's array
-    bool rs_on = false;
-    std::vector<int64_t> rs_in_off, rs_in_len;
-    std::vector<int32_t> rs_utt_tile0;   // [n_utt + 1] first tile of every utterance (tiles are in utterance order)
-    int64_t rs_total = 0;                // samples per channel of the scratch (even)
-    int32_t rs_taps_floats = 0, rs_x_floats = 0, rs_out_elems = 0; // LDS parts of the launch: maxima over the plan's rates
-    DevBuf<int16_t> d_rs_pcm;            // [rs_total * channels + 8]
-    DevBuf<float> d_rs_taps;
-    DevBuf<mfx::ResRate> d_rs_rates;
-    DevBuf<mfx::ResTile> d_rs_tiles;
-    // per-speaker normalisation (mfx_batch_set_speakers), tied to the plan: while spk_on the run's normaliser is k_spk_sums ->
-    // k_spk_finish -> k_spk_apply over the whole batch instead of run_norm's per-utterance kernels
-    bool spk_on = false;
-    bool spk_ran = false;                // a run has filled the accumulators since the list was set
-    int32_t n_spk = 0, spk_mode = 0, spk_tiles = 0, spk_max_rows = 0;
-    DevBuf<int32_t> d_spk_off, d_spk_list; // [n_spk + 1], [utterances with frames] (build_speaker_lists)
-    DevBuf<int32_t> d_spk_chunk0;        // [n_utt + 1] first 4096-row chunk of every utterance
-    DevBuf<double> d_spk_partial;        // [chunks][4][Wn]
-    DevBuf<int64_t> d_spk_prior_n, d_spk_count; // [n_spk] (the prior's: empty without one)
-    DevBuf<double> d_spk_prior, d_spk_acc;      // [n_spk][4][Wn]
-    DevBuf<float> d_spk_stats;           // [n_spk][2][Wn]
-    DevBuf<mfx::SpkTile> d_spk_tiles;    // k_spk_apply's tiles: whole rows of one utterance
+
+    // Four attachments, each tied to the plan: a new plan drops them.  drop() switches one off and releases what is not kept
+    // for the next one (the grown-never-shrunk scratch stays).
+
+    // sample-rate conversion (mfx_batch_plan_rates): while on, the run converts the caller's array into d_pcm with one
+    // launch of k_resample and then does what it always does on d_pcm; utt_off / utt_len above describe the scratch, in_off /
+    // in_len the caller's array
+    struct Rates {
+        bool on = false;
+        std::vector<int64_t> in_off, in_len;
+        std::vector<int32_t> utt_tile0;  // [n_utt + 1] first tile of every utterance (tiles are in utterance order)
+        int64_t total = 0;               // samples per channel of the scratch (even)
+        int32_t taps_floats = 0, x_floats = 0, out_elems = 0; // LDS parts of the launch: maxima over the plan's rates
+        DevBuf<int16_t> d_pcm;           // [total * channels + 8]
+        DevBuf<float> d_taps;
+        DevBuf<mfx::ResRate> d_rates;
+        DevBuf<mfx::ResTile> d_tiles;
+        void drop() // (the converter of a rates plan goes with the plan)
+        {
+            on = false;
+            d_pcm.release(), d_taps.release(), d_rates.release(), d_tiles.release();
+        }
+    } rs;
+    // per-utterance warp factors (mfx_batch_set_alphas): one table per distinct factor and, per table, the row runs of its
+    // utterances (build_alpha_runs); the batch then runs spectrum slab + k_melcep_runs / k_plp_runs
+    struct Alphas {
+        bool on = false;                 // (batch_front reads it)
+        CepTables tables;
+        std::vector<int32_t> h_run_off;  // [tables + 1]
+        std::vector<int64_t> h_runs;     // [runs][2]
+        DevBuf<int32_t> d_run_off;
+        DevBuf<int64_t> d_runs;
+        void drop() { on = false; }
+    } va;
+    // splice + affine transform (mfx_batch_set_transform): while on, the run writes its rows to d_y and k_splice_affine turns
+    // them into the caller's d_out as the last launch
+    struct Xform {
+        bool on = false;
+        int left = 0, right = 0, out = 0;
+        DevBuf<float> d_ops, d_bias;     // [n_xf][steps][tiles][64], [n_xf][tiles * 16]
+        DevBuf<int32_t> d_idx;           // [n_utt] transform of every utterance (empty: all 0)
+        DevBuf<float> d_y;               // [total_rows][width] (grown, never shrunk: only the (NULL, 0) setter releases it)
+        void drop() { on = false; }
+    } xf;
+    // per-speaker normalisation (mfx_batch_set_speakers): while on, the run's normaliser is k_spk_sums -> k_spk_finish ->
+    // k_spk_apply over the whole batch instead of run_norm's per-utterance kernels
+    struct Speakers {
+        bool on = false;
+        bool ran = false;                // a run has filled the accumulators since the list was set
+        int32_t n_spk = 0, mode = 0, n_tiles = 0, max_rows = 0;
+        DevBuf<int32_t> d_off, d_list;   // [n_spk + 1], [utterances with frames] (build_speaker_lists)
+        DevBuf<int32_t> d_chunk0;        // [n_utt + 1] first 4096-row chunk of every utterance
+        DevBuf<double> d_partial;        // [chunks][4][Wn]
+        DevBuf<int64_t> d_prior_n, d_count; // [n_spk] (the prior's: empty without one)
+        DevBuf<double> d_prior, d_acc;   // [n_spk][4][Wn]
+        DevBuf<float> d_stats;           // [n_spk][2][Wn]
+        DevBuf<mfx::SpkTile> d_tiles;    // k_spk_apply's tiles: whole rows of one utterance
+        void drop() { on = false; }
+    } spk;
+    // what a new utterance list invalidates (the converter is mfx_batch_plan's to drop: mfx_batch_plan_rates plans through
+    // plan_batch too)
+    void detach() { va.drop(), xf.drop(), spk.drop(); }
+
+    // ---- not tied to the plan
+    // optional overlap of the delta/normalisation tail of batch i with the front end of batch i+1 (mfx_batch_overlap)
+    struct Overlap {
+        bool enabled = false;
+        hipStream_t stream2 = nullptr;
+        hipEvent_t ev_front[2] = {nullptr, nullptr}, ev_tail[2] = {nullptr, nullptr};
+        bool tail_pending[2] = {false, false};
+        unsigned seq = 0;
+    } ov;
+    // mfx_batch_run_host: device copies of the caller's host buffers; sliced runs upload / download beside the kernels
+    struct Host {
+        hipStream_t stream_up = nullptr, stream_dn = nullptr;
+        hipEvent_t ev_up[16] = {}, ev_run[16] = {};
+        DevBuf<int16_t> d_pcm;
+        DevBuf<float> d_out;
+    } host;
 };
 
 // fused delta stage of the 512-point kernel: per-block chunk lists (own rows + halo) and delta tiles: mfx_batch.cpp
@@ -368,9 +403,9 @@ struct mfx_handle {
             for (hipEvent_t e : events)
                 if (e) (void)hipEventDestroy(e);
         };
-        destroy(batch.ev_front), destroy(batch.ev_tail), destroy(batch.ev_up), destroy(batch.ev_run), destroy(st.ev_copy),
+        destroy(batch.ov.ev_front), destroy(batch.ov.ev_tail), destroy(batch.host.ev_up), destroy(batch.host.ev_run), destroy(st.ev_copy),
             destroy(sess.ev_stage);
-        for (hipStream_t s : {batch.stream2, batch.stream_up, batch.stream_dn})
+        for (hipStream_t s : {batch.ov.stream2, batch.host.stream_up, batch.host.stream_dn})
             if (s) (void)hipStreamDestroy(s);
         if (own_stream && stream) (void)hipStreamDestroy(stream);
     }
@@ -409,18 +444,58 @@ inline int fail_hip(mfx_handle *h, hipError_t e, const char *what)
                         "TRAPS handles have no streaming entries: use mfx_batch_plan + mfx_batch_run_device / mfx_batch_run_host"); \
     } while (0)
 
-// ---- mfx_api.cpp, for the other two
+// one launch of the dominant kernel between two events, while profiling is on (prof_collect, mfx_api.cpp, sums them up)
+struct ProfScope {
+    mfx_handle *h;
+    hipEvent_t a = nullptr, b = nullptr;
+    explicit ProfScope(mfx_handle *hh, bool wanted = true) : h(hh)
+    {
+        if (!wanted || !h->prof.on) return;
+        if (h->prof.used == h->prof.events.size()) {
+            hipEvent_t x, y;
+            if (hipEventCreate(&x) != hipSuccess || hipEventCreate(&y) != hipSuccess) return;
+            h->prof.events.emplace_back(x, y);
+        }
+        a = h->prof.events[h->prof.used].first;
+        b = h->prof.events[h->prof.used].second;
+        ++h->prof.used;
+        (void)hipEventRecord(a, h->stream);
+    }
+    ~ProfScope()
+    {
+        if (b) (void)hipEventRecord(b, h->stream);
+    }
+};
+
+// ---- mfx_api.cpp, for the others
 // Which front-end kernel the BATCH entries run for this handle (see choose_front's definition)
 enum FrontKind { kFront512, kFront1024, kFront2048, kFrontGenFused, kSpec512, kSpecGen };
+inline bool is_spec_kind(FrontKind k) { return k == kSpec512 || k == kSpecGen; }
+// the fused kinds whose statics can go out as compact 16-float rows (k_front512: only with the DCT on the matrix pipe)
+inline bool compact_statics(FrontKind k, const mfx::FrontParams &p) { return !is_spec_kind(k) && (k != kFront512 || p.dct_mode == 1); }
 FrontKind choose_front(const mfx_handle *h);
 FrontKind choose_front(const mfx_handle *h, bool aligned); // (the session entries: their frames' alignment, not the batch plan's)
 // what batch_run_range launches: choose_front's kernel, or the spectrum form while per-utterance warp factors are in force
 FrontKind batch_front(const mfx_handle *h);
+// What launch_front needs beyond the kernel parameters.  The chunk list in both copies (the spectrum kinds walk the host
+// one); for the spectrum kinds the slab and the cepstra step behind every window of it: the row-run form (`runs` set, its
+// host copies h_off / h_runs; row0 / rows are the window's, filled in per launch) or plain k_melcep / k_plp with the
+// handle's own table over the window's rows, which must then be contiguous.
+struct FrontWork {
+    const mfx::Chunk *h_chunks = nullptr, *d_chunks = nullptr;
+    size_t n_chunks = 0;
+    float *slab = nullptr;
+    int64_t slab_rows = 0;
+    const CepTables *tables = nullptr;
+    const int64_t *runs = nullptr, *h_runs = nullptr;
+    const int32_t *run_off = nullptr, *h_run_off = nullptr;
+    bool profile = false; // every launch of the dominant kernel inside a ProfScope (the batch entries)
+};
+// queues the front end `kind` on h->stream: p filled but for chunks / n_chunks / spec / spec_pitch
+int launch_front(mfx_handle *h, mfx::FrontParams &p, FrontKind kind, bool aligned, const FrontWork &w);
 void fill_front(const mfx_handle *h, mfx::FrontParams &p);
 void fill_front(const mfx_handle *h, mfx::FrontParams &p, bool aligned);
 void fill_traps(const mfx_handle *h, mfx::TrapsParams &p);
-// (mfx_batch.cpp) row width of the batch entries' output: out_dim while a transform is in force, else `width`
-int batch_out_width(const mfx_handle *h);
 int refresh_mel(mfx_handle *h);
 int build_cep_tables(mfx_handle *h, const float *alphas, int n, CepTables &t, mfx::MelTable *first = nullptr,
                      mfx::MelWavePlan *first_plan = nullptr);
@@ -433,3 +508,14 @@ int run_norm(mfx_handle *h, hipStream_t stream, float *data, int pitch, const mf
              float *stats, bool use_last, int max_rows, int groups = 1, size_t group_stats_stride = 0);
 // ---- mfx_stream.cpp, for mfx_batch.cpp
 bool is_pinned_host(const void *p, void **dev_ptr = nullptr);
+// ---- mfx_batch*.cpp, for one another and mfx_api.cpp
+constexpr int64_t kSlabRowsMax = 1 << 17; // rows of the spectrum slab of the batch entries' spectrum path
+// mfx_batch_plan's work, on the layout the front ends will read: the caller's, or the converted PCM's (mfx_batch_plan_rates)
+int plan_batch(mfx_handle *h, int32_t n_utt, const int64_t *offsets, const int64_t *lengths, int64_t *out_rows, int64_t *total_rows);
+// scratch for the compact statics of the planned batch: one buffer, two with overlap on (grown, never shrunk)
+int size_static16(mfx_handle *h);
+// row width of the batch entries' output: out_dim while a transform is in force, else `width`
+int batch_out_width(const mfx_handle *h);
+// normalised columns of a speaker list: the whole row after the deltas, else the statics
+inline int spk_wn(const mfx_handle *h) { return h->cfg.norm_after_dyn ? h->width : h->cols; }
+void fill_xform(const mfx_handle *h, mfx::XformParams &p);

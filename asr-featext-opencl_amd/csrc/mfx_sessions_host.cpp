@@ -12,14 +12,10 @@ using namespace mfx;
 
 namespace {
 
-constexpr int64_t kSessSlabRowsMax = 1 << 17; // rows of the spectrum slab (as the batch entries')
-
 int not_created(mfx_handle *h) { return fail(h, MFX_ERR_STATE, "mfx_sessions_create has not been called"); }
 
 // the slot arrays' frames lie on even samples exactly when the shift is even: slot bases and pcm_stride are even
 bool sess_aligned(const mfx_handle *h) { return (h->S % 2) == 0; }
-
-bool is_spec_kind(FrontKind k) { return k == kSpec512 || k == kSpecGen; }
 
 } // namespace
 
@@ -66,7 +62,7 @@ extern "C" int mfx_sessions_create(mfx_handle *h, int32_t n_sessions, int32_t ma
     ss.slab_rows = 0;
     ss.d_slab.release();
     if (is_spec_kind(choose_front(h, sess_aligned(h)))) {
-        ss.slab_rows = std::min<int64_t>((int64_t)2 * n_sessions * ss.row_cap, kSessSlabRowsMax);
+        ss.slab_rows = std::min<int64_t>((int64_t)2 * n_sessions * ss.row_cap, kSlabRowsMax);
         HIP_TRY(h, ss.d_slab.alloc((size_t)ss.slab_rows * h->spec_pitch));
     }
     const size_t chunks_max = (size_t)n_sessions * ((ss.frames_max + kChunkFrames - 1) / kChunkFrames);
@@ -249,8 +245,7 @@ extern "C" int mfx_sessions_run_device(mfx_handle *h, const int16_t *d_pcm, int6
     const FrontKind kind = choose_front(h, aligned);
     FrontParams p;
     fill_front(h, p, aligned);
-    const bool fused512 = kind == kFront512, fused1024 = kind == kFront1024, fused2048 = kind == kFront2048, fusedgen = kind == kFrontGenFused;
-    const bool compact = ((fused512 && p.dct_mode == 1) || fused1024 || fused2048 || fusedgen) && h->l1 > 0 && h->cols <= 16;
+    const bool compact = compact_statics(kind, p) && h->l1 > 0 && h->cols <= 16;
     const int pitch = compact ? 16 : h->width;
     if (is_spec_kind(kind) && ss.slab_rows == 0)
         return fail(h, MFX_ERR_STATE, "the warp factor moved this shape to the spectrum path: call mfx_sessions_create again");
@@ -302,48 +297,18 @@ extern "C" int mfx_sessions_run_device(mfx_handle *h, const int16_t *d_pcm, int6
         if (nc > 0) {
             p.pcm = ss.d_pcm.p;
             p.pcm_total = gp.slot_elems;
-            p.chunks = d_chunks;
-            p.n_chunks = (int32_t)nc;
             p.row_limit = (int64_t)2 * ss.n * ss.row_cap;
             p.feat = ss.d_stat.p;
             p.feat_pitch = pitch;
-            if (fused512) {
-                HIP_TRY(h, launch_front512(p, /*to_spectrum=*/false, aligned, h->nm16, h->stream));
-            } else if (fused1024) {
-                HIP_TRY(h, launch_front1024(p, aligned, h->nm16, h->stream, (h->cfg.engine & MFX_ENGINE_FRONT1024_12_WAVES) ? 12 : 16));
-            } else if (fused2048) {
-                HIP_TRY(h, launch_front2048(p, h->num_cus, h->stream));
-            } else if (fusedgen) {
-                HIP_TRY(h, launch_front_generic(p, /*fused=*/true, h->stream));
-            } else { // magnitudes through the slab in windows of rows, then k_melcep_runs / k_plp_runs on the new rows only
-                RowRuns rr;
-                rr.runs = (const int64_t *)(ss.d_desc.p + o_run);
-                rr.off = (const int32_t *)(ss.d_desc.p + o_off);
-                size_t c0 = 0;
-                while (c0 < nc) {
-                    const int64_t row0 = ss.p_chunks[c0].out_row;
-                    size_t c1 = c0;
-                    int64_t rows = 0;
-                    while (c1 < nc && ss.p_chunks[c1].out_row + ss.p_chunks[c1].n_frames - row0 <= ss.slab_rows) {
-                        rows = ss.p_chunks[c1].out_row + ss.p_chunks[c1].n_frames - row0;
-                        ++c1;
-                    }
-                    FrontParams q = p;
-                    q.chunks = d_chunks + c0;
-                    q.n_chunks = (int32_t)(c1 - c0);
-                    q.spec = ss.d_slab.p - row0 * (int64_t)h->spec_pitch; // rows are addressed absolutely
-                    q.spec_pitch = h->spec_pitch;
-                    if (h->fast512)
-                        HIP_TRY(h, launch_front512(q, /*to_spectrum=*/true, aligned, h->nm16, h->stream));
-                    else
-                        HIP_TRY(h, launch_front_generic(q, /*fused=*/false, h->stream));
-                    rr.row0 = row0;
-                    rr.rows = rows;
-                    rc = launch_cepstra_runs(h, h->own, q.spec, p.feat, p.feat_pitch, rr, h_off, ss.p_runs.data(), h->stream);
-                    if (rc != MFX_OK) return rc;
-                    c0 = c1;
-                }
-            }
+            // (spectrum kinds: k_melcep_runs / k_plp_runs on the new rows only; a push adds nothing to mfx_profile_read)
+            FrontWork w;
+            w.h_chunks = ss.p_chunks.data(), w.d_chunks = d_chunks, w.n_chunks = nc;
+            w.slab = ss.d_slab.p, w.slab_rows = ss.slab_rows;
+            w.tables = &h->own;
+            w.runs = (const int64_t *)(ss.d_desc.p + o_run), w.run_off = (const int32_t *)(ss.d_desc.p + o_off);
+            w.h_runs = ss.p_runs.data(), w.h_run_off = h_off;
+            rc = launch_front(h, p, kind, aligned, w);
+            if (rc != MFX_OK) return rc;
         }
 
         // ---- delta: the rows every session's push completes, into the caller's array (l1 == 0: the copy form)

@@ -20,7 +20,7 @@ for t in $TUS; do
   /opt/rocm/bin/hipcc -O3 -fPIC -std=c++17 --offload-arch=gfx950 -fno-slp-vectorize $DEFS -I$SRCDIR -I$C -c $SRCDIR/$t.hip -o $T/$t.o & pids="$pids $!"
 done
 for p in $pids; do wait $p; done
-HOST="mfx_api.o mfx_stream.o mfx_batch.o mfx_tables.o"
+HOST=$(make -s -C $C print-host-objs) # (the Makefile's list: HOST_TUS + mfx_tables.o)
 make -s -C $C $HOST
 /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o $R/build/var/lib_$NAME.so $T/*.o $(for o in $HOST; do echo $C/$o; done)
 echo built build/var/lib_$NAME.so
