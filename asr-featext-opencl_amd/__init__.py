@@ -35,6 +35,9 @@ from .mfcc import (  # noqa: F401
     host_speaker_lists,
     SPK_POOL,
     SPK_PRIOR_ONLY,
+    VAD_FLAGS,
+    VAD_SELECT,
+    VAD_PACK,
     host_traps_basis,
     host_xform_operands,
     KERNEL_TABLE,

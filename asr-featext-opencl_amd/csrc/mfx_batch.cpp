@@ -84,7 +84,9 @@ int convert_rates(mfx_handle *h, const int16_t *d_pcm, int u0, int u1)
 struct RunMode {
     FrontKind kind;         // the 512-point register kernel, else the fused wave-per-frame kernel when its LDS fits, else
                             // spectrum through an HBM slab + melcep (per-utterance warp factors in force: always the slab)
-    float *d_out, *d_final; // where the rows are built, where the caller wants them: the same unless a transform is in force
+    float *d_out, *d_last, *d_final; // where the rows y are built, where the run's last stage before the VAD writes, where
+                            // the caller wants the result: all the same unless a transform (d_out is its scratch) or a
+                            // selecting VAD (d_last is its scratch) is in force
     int sb;                 // which of the two statics buffers (overlap)
     bool via_scratch;       // With deltas on, the front end writes its statics as compact 64-byte rows into a scratch buffer
                             // and the delta kernel emits whole [static | d | dd] rows: every HBM write is then a full line
@@ -105,8 +107,11 @@ RunMode decide_mode(const mfx_handle *h, FrontParams &p, float *d_out, bool whol
     m.kind = batch_front(h);
     // A transform in force: everything runs as it always does with the handle's scratch in the place of d_out, and
     // k_splice_affine turns the scratch rows into the caller's array as the last launch.
+    // A selecting VAD in force: the last stage writes to the VAD's scratch, and k_vad_select moves the voiced rows from there
+    // into the caller's array.
     m.d_final = d_out;
-    m.d_out = B.xf.on ? B.xf.d_y.p : d_out;
+    m.d_last = (B.vad.on && B.vad.mode != MFX_VAD_FLAGS) ? B.vad.d_rows.p : d_out;
+    m.d_out = B.xf.on ? B.xf.d_y.p : m.d_last;
     const bool norm_before = h->cfg.norm != MFX_NORM_NONE && !h->cfg.norm_after_dyn;
     m.sb = (B.ov.enabled && whole) ? (int)(B.ov.seq & 1) : 0;
     m.via_scratch = compact_statics(m.kind, p) && h->l1 > 0 && h->cols <= 16 && !h->traps && !norm_before &&
@@ -188,7 +193,42 @@ int run_batch_norm(mfx_handle *h, const RunMode &m, int u0, int u1, int groups, 
                     B.tiles_max * 64, groups, group_stats_stride);
 }
 
-// ---- stage 5, on m.tail_stream: normaliser before the deltas, deltas, normaliser after them, transform
+// the VAD of a run: decision on the rows y (m.d_out, before a transform), selection from m.d_last into the caller's array
+int run_vad(mfx_handle *h, const RunMode &m, int u0, int u1)
+{
+    BatchState &B = h->batch;
+    BatchState::Vad &v = B.vad;
+    VadParams vp{};
+    vp.y = m.d_out;
+    vp.y_pitch = h->width;
+    vp.column = v.column;
+    vp.segs = B.d_segs.p;
+    vp.n_utt = B.n_utt;
+    vp.u0 = u0, vp.u1 = u1;
+    vp.utt_tile0 = v.d_utt_tile0.p, vp.utt_chunk0 = v.d_utt_chunk0.p;
+    vp.tile_utt = v.d_tile_utt.p, vp.chunk_utt = v.d_chunk_utt.p;
+    vp.tile_first = v.utt_tile0[u0], vp.n_tiles = v.utt_tile0[u1] - v.utt_tile0[u0];
+    vp.chunk_first = v.utt_chunk0[u0], vp.n_chunks = v.utt_chunk0[u1] - v.utt_chunk0[u0];
+    vp.energy_threshold = v.et, vp.energy_mean_scale = v.ms, vp.proportion_threshold = v.prop;
+    vp.frames_context = v.ctx;
+    vp.mode = v.mode;
+    vp.partial = v.d_partial.p;
+    vp.thr = v.d_thr.p;
+    vp.voiced = v.d_voiced.p;
+    vp.flags = v.d_flags.p;
+    vp.mask = v.d_mask.p;
+    vp.tile_base = v.d_tile_base.p;
+    vp.packed_row0 = v.d_packed.p;
+    vp.rows = v.mode != MFX_VAD_FLAGS ? m.d_last : nullptr;
+    vp.out = v.mode != MFX_VAD_FLAGS ? m.d_final : nullptr;
+    vp.width = batch_out_width(h);
+    HIP_TRY(h, launch_vad(vp, m.tail_stream));
+    v.last_stream = m.tail_stream;
+    v.ran = true;
+    return MFX_OK;
+}
+
+// ---- stage 5, on m.tail_stream: normaliser before the deltas, deltas, normaliser after them, transform, VAD
 int run_tail(mfx_handle *h, const RunMode &m, int u0, int u1)
 {
     BatchState &B = h->batch;
@@ -224,7 +264,7 @@ int run_tail(mfx_handle *h, const RunMode &m, int u0, int u1)
         fill_xform(h, xp);
         xp.src = m.d_out;
         xp.src_pitch = h->width;
-        xp.out = m.d_final;
+        xp.out = m.d_last;
         xp.out_pitch = B.xf.out;
         xp.segs = B.d_segs.p + u0;
         xp.n_segs = u1 - u0;
@@ -233,6 +273,10 @@ int run_tail(mfx_handle *h, const RunMode &m, int u0, int u1)
         xp.bias = B.xf.d_bias.p;
         xp.tiles_per_seg_max = B.tiles_max;
         HIP_TRY(h, launch_xform(xp, m.tail_stream));
+    }
+    if (B.vad.on) { // last of all, on the tail's stream: ev_tail covers it
+        const int rc = run_vad(h, m, u0, u1);
+        if (rc != MFX_OK) return rc;
     }
     if (m.split_tail) {
         HIP_TRY(h, hipEventRecord(B.ov.ev_tail[m.sb], m.tail_stream));
@@ -249,6 +293,7 @@ int batch_run_range(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_tot
     if (!d_pcm || !d_out || pcm_samples_total <= 0) return fail(h, MFX_ERR_ARG, "invalid argument");
     const bool whole = u0 == 0 && u1 == B.n_utt;
     if (B.spk.on && !whole) return fail(h, MFX_ERR_STATE, "a speaker list is in force: the batch runs as a whole");
+    if (B.vad.on && B.vad.mode == MFX_VAD_PACK && !whole) return fail(h, MFX_ERR_STATE, "a packing VAD is in force: the batch runs as a whole");
     if (!h->have_window) return fail(h, MFX_ERR_STATE, "set_window has not been called");
     int rc;
     if (B.rs.on) {
@@ -257,13 +302,23 @@ int batch_run_range(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_tot
         d_pcm = B.rs.d_pcm.p;
         pcm_samples_total = B.rs.total;
     }
-    if (B.total_rows == 0) return MFX_OK;
+    if (B.total_rows == 0) {
+        B.vad.ran = B.vad.on; // (nothing to decide: the read-back returns what the setter left, no voiced row)
+        return MFX_OK;
+    }
     if ((rc = check_layout(h, d_pcm, pcm_samples_total, B.utt_off, B.utt_len, u0, u1)) != MFX_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     if ((rc = refresh_mel(h)) != MFX_OK) return rc;
     const int32_t c0 = B.utt_chunk0[u0], c1 = B.utt_chunk0[u1]; // chunk range of the utterance range
-    if (c1 <= c0) return MFX_OK;
-    if ((B.xf.on && B.xf.d_y.n < (size_t)B.total_rows * h->width) || (h->traps && B.d_logmel.n < (size_t)B.total_rows * B.mel_pitch))
+    if (c1 <= c0) { // a range without a frame: nothing to compute, but the VAD's counts and prefix are still to be written
+        if (!B.vad.on) return MFX_OK;
+        RunMode none{};
+        none.d_last = B.vad.d_rows.p, none.d_final = d_out;
+        none.tail_stream = h->stream;
+        return run_vad(h, none, u0, u1);
+    }
+    if ((B.xf.on && B.xf.d_y.n < (size_t)B.total_rows * h->width) || (h->traps && B.d_logmel.n < (size_t)B.total_rows * B.mel_pitch) ||
+        (B.vad.on && B.vad.mode != MFX_VAD_FLAGS && B.vad.d_rows.n < (size_t)B.total_rows * batch_out_width(h)))
         return fail(h, MFX_ERR_STATE, "batch not planned");
 
     FrontParams p;
@@ -346,7 +401,9 @@ extern "C" int mfx_batch_run_host(mfx_handle *h, const int16_t *pcm, int64_t pcm
     for (int u = 1; u < h->batch.n_utt && ascending; ++u) ascending = in_off[u] >= in_off[u - 1] + in_len[u - 1];
     const int K = (int)std::min<int64_t>(8, h->batch.n_utt / 4);
     // (a speaker list in force: a speaker may span slices, the batch goes through whole)
-    if (K >= 2 && ascending && !h->batch.ov.enabled && !h->fuse.planned && !h->batch.spk.on && n_in * sizeof(int16_t) >= ((size_t)32 << 20) &&
+    // (a packing VAD in force: an utterance's destination depends on the slices in front of it, the batch goes through whole)
+    const bool packing = h->batch.vad.on && h->batch.vad.mode == MFX_VAD_PACK;
+    if (K >= 2 && ascending && !h->batch.ov.enabled && !h->fuse.planned && !h->batch.spk.on && !packing && n_in * sizeof(int16_t) >= ((size_t)32 << 20) &&
         is_pinned_host(pcm) && is_pinned_host(out)) {
         if (!h->batch.host.stream_up) {
             HIP_TRY(h, hipStreamCreateWithFlags(&h->batch.host.stream_up, hipStreamNonBlocking));

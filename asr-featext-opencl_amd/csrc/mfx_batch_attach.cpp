@@ -1,7 +1,10 @@
 // mfx_batch_attach.cpp -- what a caller attaches to a planned batch (include/mfx.h): per-utterance warp factors, a splice +
-// affine transform, a speaker list.  Each is tied to the plan (mfx_batch_plan_rates' converter is the fourth, and is the
-// planner's); BatchState::detach drops the three of this file.  This file owns `batch.va`, `batch.xf` and `batch.spk`.
+// affine transform, a speaker list, the energy VAD.  Each is tied to the plan (mfx_batch_plan_rates' converter is the fifth,
+// and is the planner's); BatchState::detach drops the four of this file.  This file owns `batch.va`, `batch.xf`, `batch.spk`
+// and `batch.vad`.
 #include "mfx_handle.h"
+
+#include <cmath>
 
 using namespace mfx;
 
@@ -160,7 +163,7 @@ extern "C" int mfx_batch_set_transform(mfx_handle *h, int32_t left, int32_t righ
         if (rc != MFX_OK) return rc;
         h->batch.xf.drop();
         h->batch.xf.d_ops.release(), h->batch.xf.d_bias.release(), h->batch.xf.d_idx.release(), h->batch.xf.d_y.release();
-        return MFX_OK;
+        return size_vad_rows(h); // (the output rows are `width` floats again)
     }
     if (!h->batch.planned) return fail(h, MFX_ERR_STATE, "mfx_batch_set_transform: no batch is planned");
     if (!A) return fail(h, MFX_ERR_ARG, "no matrix");
@@ -202,5 +205,106 @@ extern "C" int mfx_batch_set_transform(mfx_handle *h, int32_t left, int32_t righ
     if (h->batch.xf.d_y.n < need) HIP_TRY(h, h->batch.xf.d_y.alloc(need));
     h->batch.xf.left = left, h->batch.xf.right = right, h->batch.xf.out = out_dim;
     h->batch.xf.on = true;
+    return size_vad_rows(h); // (the output rows are out_dim floats now)
+}
+
+// ------------------------------------------------------------------------------------------------
+// energy VAD + voiced-frame selection ("Voice activity and frame selection")
+// ------------------------------------------------------------------------------------------------
+
+// the scratch the last stage writes to while a selecting VAD is in force: [total_rows][Wo] at the CURRENT output width
+// (called by the VAD's and the transform's setters, with the streams idle; grown, never shrunk)
+int size_vad_rows(mfx_handle *h)
+{
+    BatchState::Vad &v = h->batch.vad;
+    if (!v.on || v.mode == MFX_VAD_FLAGS) return MFX_OK;
+    const size_t need = (size_t)std::max<int64_t>(h->batch.total_rows, 1) * batch_out_width(h);
+    if (v.d_rows.n < need) HIP_TRY(h, v.d_rows.alloc(need));
+    return MFX_OK;
+}
+
+extern "C" int mfx_batch_set_vad(mfx_handle *h, int32_t column, float energy_threshold, float energy_mean_scale, int32_t frames_context,
+                                 float proportion_threshold, int32_t mode)
+{
+    MFX_DEVICE_ENTRY(h);
+    BatchState &B = h->batch;
+    if (!B.planned) return fail(h, MFX_ERR_STATE, "mfx_batch_set_vad: no batch is planned");
+    if (column < -1 || column >= h->width) return fail(h, MFX_ERR_ARG, "column must be -1 (the last static column) or inside the row");
+    if (frames_context < 0 || frames_context > 64) return fail(h, MFX_ERR_ARG, "frames_context must be 0 .. 64");
+    if (!(proportion_threshold > 0.f && proportion_threshold <= 1.f)) return fail(h, MFX_ERR_ARG, "proportion_threshold must lie in (0, 1]");
+    if (!std::isfinite(energy_threshold) || !std::isfinite(energy_mean_scale))
+        return fail(h, MFX_ERR_ARG, "energy_threshold and energy_mean_scale must be finite");
+    if (mode != MFX_VAD_FLAGS && mode != MFX_VAD_SELECT && mode != MFX_VAD_PACK)
+        return fail(h, MFX_ERR_ARG, "mode must be MFX_VAD_FLAGS, MFX_VAD_SELECT or MFX_VAD_PACK");
+    std::vector<int32_t> tile0, tile_utt, chunk0, chunk_utt;
+    if (!build_vad_layout(B.utt_frames.data(), B.n_utt, tile0, tile_utt, chunk0, chunk_utt)) return fail(h, MFX_ERR_ARG, "batch too long");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int rc = mfx_synchronize(h); // (a run in flight may read the lists replaced below)
+    if (rc != MFX_OK) return rc;
+    BatchState::Vad &v = B.vad;
+    v.drop();
+    // (everything mfx_batch_run_device needs is allocated here: that entry never allocates)
+    const size_t n = (size_t)B.n_utt, tiles = tile_utt.size();
+    HIP_TRY(h, h->upload(v.d_utt_tile0, tile0));
+    HIP_TRY(h, h->upload(v.d_tile_utt, tile_utt));
+    HIP_TRY(h, h->upload(v.d_utt_chunk0, chunk0));
+    HIP_TRY(h, h->upload(v.d_chunk_utt, chunk_utt));
+    HIP_TRY(h, v.d_partial.alloc(chunk_utt.size()));
+    HIP_TRY(h, v.d_mask.alloc(tiles));
+    HIP_TRY(h, v.d_tile_base.alloc(tiles));
+    // what a run that launches nothing (a batch without rows) leaves for the read-back: no voiced row, thr = energy_threshold
+    HIP_TRY(h, h->upload(v.d_thr, std::vector<float>(n, energy_threshold)));
+    HIP_TRY(h, h->upload(v.d_voiced, std::vector<int32_t>(n, 0)));
+    HIP_TRY(h, h->upload(v.d_packed, std::vector<int64_t>(n + 1, 0)));
+    HIP_TRY(h, v.d_flags.alloc((size_t)B.total_rows)); // (every row has a frame: a run writes them all before a read-back)
+    v.utt_tile0.swap(tile0), v.utt_chunk0.swap(chunk0);
+    v.column = column >= 0 ? column : h->cols - 1;
+    v.et = energy_threshold, v.ms = energy_mean_scale, v.ctx = frames_context, v.prop = proportion_threshold, v.mode = mode;
+    v.last_stream = h->stream;
+    v.on = true;
+    const int rs = size_vad_rows(h);
+    if (rs != MFX_OK) v.drop();
+    return rs;
+}
+
+extern "C" int mfx_batch_clear_vad(mfx_handle *h)
+{
+    MFX_DEVICE_ENTRY(h);
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int rc = mfx_synchronize(h); // (a run in flight may read what is released below)
+    if (rc != MFX_OK) return rc;
+    BatchState::Vad &v = h->batch.vad;
+    v.drop();
+    v.d_utt_tile0.release(), v.d_tile_utt.release(), v.d_utt_chunk0.release(), v.d_chunk_utt.release(), v.d_partial.release();
+    v.d_thr.release(), v.d_voiced.release(), v.d_tile_base.release(), v.d_flags.release(), v.d_mask.release(), v.d_packed.release();
+    v.d_rows.release();
+    return MFX_OK;
+}
+
+extern "C" int mfx_batch_vad_read(mfx_handle *h, uint8_t *flags, int32_t *voiced, float *threshold, int64_t *total_voiced)
+{
+    MFX_DEVICE_ENTRY(h);
+    const BatchState::Vad &v = h->batch.vad;
+    if (!v.on) return fail(h, MFX_ERR_STATE, "mfx_batch_vad_read: no VAD is in force");
+    if (!v.ran) return fail(h, MFX_ERR_STATE, "mfx_batch_vad_read: no batch has run since the VAD was set");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int rc = mfx_synchronize(h);
+    if (rc != MFX_OK) return rc;
+    const size_t n = (size_t)h->batch.n_utt;
+    if (flags && h->batch.total_rows > 0) HIP_TRY(h, hipMemcpy(flags, v.d_flags.p, (size_t)h->batch.total_rows, hipMemcpyDeviceToHost));
+    if (voiced && n > 0) HIP_TRY(h, hipMemcpy(voiced, v.d_voiced.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (threshold && n > 0) HIP_TRY(h, hipMemcpy(threshold, v.d_thr.p, n * sizeof(float), hipMemcpyDeviceToHost));
+    if (total_voiced) HIP_TRY(h, hipMemcpy(total_voiced, v.d_packed.p + n, sizeof(int64_t), hipMemcpyDeviceToHost));
+    return MFX_OK;
+}
+
+extern "C" int mfx_batch_vad_device(const mfx_handle *h, const uint8_t **d_flags, const int32_t **d_voiced, const int64_t **d_packed_row0)
+{
+    if (!h) return MFX_ERR_ARG;
+    if (h->planning) return MFX_ERR_DEVICE;
+    if (!h->batch.vad.on) return MFX_ERR_STATE;
+    if (d_flags) *d_flags = h->batch.vad.d_flags.p;
+    if (d_voiced) *d_voiced = h->batch.vad.d_voiced.p;
+    if (d_packed_row0) *d_packed_row0 = h->batch.vad.d_packed.p;
     return MFX_OK;
 }

@@ -3,7 +3,7 @@
 //   mfx_api.cpp    lifetime, tables, kernel choice and front-end dispatch, profiling, test taps (writes the shared part)
 //   mfx_stream.cpp the streaming state machine and its host copies         (owns `st` and `sweep`)
 //   mfx_batch_plan.cpp   the batch planner, the rates planner, the fused-delta plan (owns `batch`'s plan, `batch.rs`, `fuse`)
-//   mfx_batch_attach.cpp what is attached to a plan: warp factors, transform, speakers (owns `batch.va`, `.xf`, `.spk`)
+//   mfx_batch_attach.cpp what is attached to a plan: warp factors, transform, speakers, VAD (owns `batch.va`, `.xf`, `.spk`, `.vad`)
 //   mfx_batch.cpp        the batch runner, device and host entries, overlap   (owns `batch.ov` and `batch.host`)
 //   mfx_sessions_host.cpp the session entries: many live streams per push       (owns `sess`)
 #pragma once
@@ -161,7 +161,7 @@ struct BatchState {
     int tiles_max = 0;
     bool aligned = true;                 // frames on aligned sample pairs (fill_front / choose_front read it)
 
-    // Four attachments, each tied to the plan: a new plan drops them.  drop() switches one off and releases what is not kept
+    // Five attachments, each tied to the plan: a new plan drops them.  drop() switches one off and releases what is not kept
     // for the next one (the grown-never-shrunk scratch stays).
 
     // sample-rate conversion (mfx_batch_plan_rates): while on, the run converts the caller's array into d_pcm with one
@@ -219,9 +219,28 @@ struct BatchState {
         DevBuf<mfx::SpkTile> d_tiles;    // k_spk_apply's tiles: whole rows of one utterance
         void drop() { on = false; }
     } spk;
+    // energy VAD + voiced-frame selection (mfx_batch_set_vad): while on, the run's last stage writes to d_rows instead of the
+    // caller's array (modes SELECT / PACK) and the launches of launch_vad follow it on the tail's stream
+    struct Vad {
+        bool on = false;
+        bool ran = false;                // a run has filled the arrays since the setter
+        int32_t column = 0, ctx = 0, mode = 0; // (column resolved: never -1)
+        float et = 0.f, ms = 0.f, prop = 0.f;
+        std::vector<int32_t> utt_tile0, utt_chunk0; // [n_utt + 1] (build_vad_layout)
+        DevBuf<int32_t> d_utt_tile0, d_tile_utt, d_utt_chunk0, d_chunk_utt;
+        DevBuf<double> d_partial;        // [chunks]
+        DevBuf<float> d_thr;             // [n_utt]
+        DevBuf<int32_t> d_voiced, d_tile_base; // [n_utt], [tiles]
+        DevBuf<uint8_t> d_flags;         // [total_rows]
+        DevBuf<uint64_t> d_mask;         // [tiles]
+        DevBuf<int64_t> d_packed;        // [n_utt + 1]
+        DevBuf<float> d_rows;            // [total_rows][Wo] (grown, never shrunk: only mfx_batch_clear_vad releases it)
+        hipStream_t last_stream = nullptr; // the stream the last run's tail ran on
+        void drop() { on = false, ran = false; }
+    } vad;
     // what a new utterance list invalidates (the converter is mfx_batch_plan's to drop: mfx_batch_plan_rates plans through
     // plan_batch too)
-    void detach() { va.drop(), xf.drop(), spk.drop(); }
+    void detach() { va.drop(), xf.drop(), spk.drop(), vad.drop(); }
 
     // ---- not tied to the plan
     // optional overlap of the delta/normalisation tail of batch i with the front end of batch i+1 (mfx_batch_overlap)
@@ -519,3 +538,5 @@ int batch_out_width(const mfx_handle *h);
 // normalised columns of a speaker list: the whole row after the deltas, else the statics
 inline int spk_wn(const mfx_handle *h) { return h->cfg.norm_after_dyn ? h->width : h->cols; }
 void fill_xform(const mfx_handle *h, mfx::XformParams &p);
+// the VAD's row scratch at the current output width (mfx_batch_attach.cpp; a no-op unless a selecting VAD is in force)
+int size_vad_rows(mfx_handle *h);

@@ -1,4 +1,4 @@
-// mfx_kernels.h -- launch interface of the gfx950 kernels (implemented in mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip, mfx_plp.hip, mfx_traps.hip, mfx_xform.hip, mfx_sessions.hip, mfx_resample.hip: one translation unit per kernel family).
+// mfx_kernels.h -- launch interface of the gfx950 kernels (implemented in mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip, mfx_plp.hip, mfx_traps.hip, mfx_xform.hip, mfx_sessions.hip, mfx_resample.hip, mfx_speakers.hip, mfx_vad.hip: one translation unit per kernel family).
 //
 // Kernel inventory and the reference stage each one replaces:
 //   spectrum512 / fused512   segmenter.cl kernelSegmentWindow + AppleFFT fft0 + mfcc.cl kernelTranspose
@@ -12,6 +12,8 @@
 //                            (no reference analogue: the reference re-frames 2 D frames of context per block, segmentercpu.cpp:69-73)
 //   resample                 per-utterance sample-rate conversion of the batch entries' PCM (no reference analogue: the reference takes
 //                            its files at the one rate its model was trained at)
+//   vad_*                    energy voice-activity decision + voiced-frame selection of finished rows (no reference analogue: the
+//                            reference hands every frame to its consumer)
 //   delta                    delta.cl kernelDelta x2 + the staging copies of mfccopencl.cpp:360-387
 //   norm_stats / norm_apply  norm.cl kernelSum + kernelFinalizeSum / kernelNormalize
 #pragma once
@@ -363,7 +365,40 @@ struct SpkParams {
     int32_t n_tiles;
 };
 
+// Energy VAD + voiced-frame selection (mfx_batch_set_vad; mfx_vad.hip; DESIGN.md, "Voice activity and frame selection").
+// Tiles are runs of 64 consecutive rows of one utterance, chunks runs of kNormChunkRows = 4096, both numbered through the
+// batch in utterance order (build_vad_layout); every per-tile, per-chunk and per-utterance array is indexed absolutely, so
+// that a run over an utterance range fills its part and leaves the rest.
+struct VadParams {
+    const float *y;        // the rows the decision reads, [rows][y_pitch]
+    int32_t y_pitch;
+    int32_t column;        // 0 <= column < y_pitch
+    const Segment *segs;   // [n_utt]: uses out_row0 / n_out
+    int32_t n_utt;
+    int32_t u0, u1;        // the utterance range of this run
+    const int32_t *utt_tile0, *utt_chunk0; // [n_utt + 1]
+    const int32_t *tile_utt, *chunk_utt;   // utterance of every tile / chunk
+    int32_t tile_first, n_tiles;           // = utt_tile0[u0], utt_tile0[u1] - utt_tile0[u0]
+    int32_t chunk_first, n_chunks;
+    float energy_threshold, energy_mean_scale, proportion_threshold;
+    int32_t frames_context; // 0 .. 64
+    int32_t mode;          // MFX_VAD_*: 0 flags only, 1 select inside every utterance's rows, 2 pack the batch
+    double *partial;       // [chunks] sum of e over every chunk
+    float *thr;            // [n_utt]
+    int32_t *voiced;       // [n_utt]
+    uint8_t *flags;        // [total_rows]
+    uint64_t *mask;        // [tiles] bit r: row r of the tile is voiced
+    int32_t *tile_base;    // [tiles] voiced rows of the utterance in front of the tile
+    int64_t *packed_row0;  // [n_utt + 1] exclusive prefix of voiced (written by a run that reaches the last utterance)
+    const float *rows;     // modes 1, 2: the finished rows, [total_rows][width], 16-byte aligned
+    float *out;            // modes 1, 2: the caller's array, [total_rows][width]; never `rows`
+    int32_t width;
+};
+
 // All launchers are asynchronous on `stream` and return the launch status.
+// every launch of the VAD stage for utterances [u0, u1), in order
+hipError_t launch_vad(const VadParams &p, hipStream_t stream);
+bool vad_shape_ok(const VadParams &p);
 // per-speaker normalisation: chunk totals; accumulators + statistics; apply.  spk_tile_rows: rows of a tile of k_spk_apply at
 // Wn columns; spk_chunks: 4096-row chunks of an utterance of `rows` rows
 hipError_t launch_spk_sums(const SpkParams &p, hipStream_t stream);

@@ -247,6 +247,31 @@ bool build_speaker_lists(const int32_t *utt_spk, const int64_t *frames, int n_ut
     return true;
 }
 
+bool build_vad_layout(const int64_t *frames, int n_utt, std::vector<int32_t> &utt_tile0, std::vector<int32_t> &tile_utt,
+                      std::vector<int32_t> &utt_chunk0, std::vector<int32_t> &chunk_utt)
+{
+    if (n_utt < 0) return false;
+    int64_t tiles = 0, chunks = 0;
+    for (int u = 0; u < n_utt; ++u) {
+        if (frames[u] < 0) return false;
+        tiles += (frames[u] + 63) / 64;
+        chunks += (frames[u] + 4095) / 4096;
+        if (tiles > 0x7ffffff0) return false;
+    }
+    utt_tile0.assign((size_t)n_utt + 1, 0);
+    utt_chunk0.assign((size_t)n_utt + 1, 0);
+    tile_utt.assign((size_t)tiles, 0);
+    chunk_utt.assign((size_t)chunks, 0);
+    int32_t t = 0, c = 0;
+    for (int u = 0; u < n_utt; ++u) {
+        utt_tile0[u] = t, utt_chunk0[u] = c;
+        for (int64_t r = 0; r < frames[u]; r += 64) tile_utt[(size_t)t++] = u;
+        for (int64_t r = 0; r < frames[u]; r += 4096) chunk_utt[(size_t)c++] = u;
+    }
+    utt_tile0[n_utt] = t, utt_chunk0[n_utt] = c;
+    return true;
+}
+
 void clip_alpha_runs(int64_t row0, int64_t rows, std::vector<int32_t> &off, std::vector<int64_t> &runs)
 {
     const int64_t w0 = row0, w1 = row0 + rows;

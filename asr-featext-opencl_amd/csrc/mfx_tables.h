@@ -95,6 +95,14 @@ void clip_alpha_runs(int64_t row0, int64_t rows, std::vector<int32_t> &off, std:
 bool build_speaker_lists(const int32_t *utt_spk, const int64_t *frames, int n_utt, int n_spk, std::vector<int32_t> &off,
                          std::vector<int32_t> &list);
 
+// Tiles and chunks of the VAD stage (mfx_batch_set_vad): utterance u of frames[u] rows is cut into tiles of 64 rows and into
+// chunks of 4096 rows (kNormChunkRows), numbered through the batch in utterance order.  False -- and nothing written -- on a
+// negative count or a batch whose tiles do not fit an int32.
+//   utt_tile0 / utt_chunk0 : [n_utt + 1] first tile / chunk of every utterance (a frameless utterance owns none)
+//   tile_utt / chunk_utt   : the utterance of every tile / chunk
+bool build_vad_layout(const int64_t *frames, int n_utt, std::vector<int32_t> &utt_tile0, std::vector<int32_t> &tile_utt,
+                      std::vector<int32_t> &utt_chunk0, std::vector<int32_t> &chunk_utt);
+
 // exp(-2*pi*i*k/n) for k in [0, count), evaluated in double and rounded once to float.
 void build_twiddles(int n, int count, std::vector<float> &re_im_interleaved);
 

@@ -68,6 +68,11 @@ struct Options {
     int resample_to = 0;    // --resample-to HZ: extract at HZ whatever the first file's rate; files at other rates are converted
                             // on the device (mfx_batch_plan_rates).  0: the reference's rule -- every file at the first file's rate
     int resample_zeros = 0; // --resample-zeros N: zero crossings of the conversion filter per side (0 = the library's 6)
+    // --vad: energy VAD + select-voiced-frames on the device (mfx_batch_set_vad, SELECT): every output file holds its voiced
+    // rows only.  The defaults are compute-vad-energy's; the column is the last static one (c0 with --c0 1)
+    bool vad = false;
+    float vad_energy_threshold = 5.f, vad_energy_mean_scale = 0.5f, vad_proportion_threshold = 0.6f;
+    int vad_frames_context = 0, vad_column = -1;
 };
 
 struct Wav {
@@ -522,6 +527,7 @@ struct BatchItem {
     bool stream = false;        // not batchable: goes through the per-file loop
     Wav wav;                    // kept for the per-file loop
     long long off = 0, len = 0, row0 = 0, frames = 0;
+    long long out_frames = 0;   // rows written to the file: frames, or the voiced ones with --vad
     int rate = 0;               // the file's own sample rate (--resample-to: may differ from the extractor's)
     long long conv_len = 0;     // samples after conversion (= len at the extractor's rate)
 };
@@ -724,10 +730,10 @@ void worker(const Options &o, int device, float sr, const std::vector<std::strin
                         std::vector<char> &text = text_bufs[(size_t)t]; // (grown once per helper, not per file)
                         const float *r = rows + (size_t)it.row0 * b->width;
                         if (o.htk) {
-                            write_htk_header(fo, (uint32_t)it.frames, o, b->width);
-                            write_rows_htk(fo, r, (int)it.frames, b->width, text);
+                            write_htk_header(fo, (uint32_t)it.out_frames, o, b->width);
+                            write_rows_htk(fo, r, (int)it.out_frames, b->width, text);
                         } else {
-                            write_rows(fo, r, (int)it.frames, b->width, 0, t0, dt, text, 1);
+                            write_rows(fo, r, (int)it.out_frames, b->width, 0, t0, dt, text, 1);
                         }
                         std::fclose(fo);
                         if (g_time.on) {
@@ -789,6 +795,9 @@ void worker(const Options &o, int device, float sr, const std::vector<std::strin
                         if (!al.empty()) param.batch_set_alphas(al.data(), (int)al.size());
                         param.batch_set_speakers(spk.data(), (int)spk.size(), o.n_spk, have_prior ? count.data() : nullptr,
                                                  have_prior ? acc.data() : nullptr, pass == 2);
+                        if (o.vad && pass == 2) // (the rows that are written: selected from the normalised ones)
+                            param.batch_set_vad(o.vad_column, o.vad_energy_threshold, o.vad_energy_mean_scale, o.vad_frames_context,
+                                                o.vad_proportion_threshold, MFX_VAD_SELECT);
                         float *rows = (float *)b.rows.get((size_t)std::max<long long>(b.total_rows, 1) * width * sizeof(float));
                         param.batch_run_host((const short *)b.pcm.p, b.samples, rows);
                         if (pass == 1) {
@@ -798,9 +807,12 @@ void worker(const Options &o, int device, float sr, const std::vector<std::strin
                             }
                             continue;
                         }
+                        std::vector<int> voiced(in_batch.size());
+                        if (o.vad) param.batch_vad_read(nullptr, voiced.data(), nullptr);
                         for (size_t k = 0; k < in_batch.size(); ++k) {
                             in_batch[k]->row0 = row0[k];
                             if (in_batch[k]->frames != param.batch_frames(in_batch[k]->conv_len)) throw std::runtime_error("frame count mismatch");
+                            in_batch[k]->out_frames = o.vad ? voiced[k] : in_batch[k]->frames;
                         }
                         write_batch(&b);
                     }
@@ -856,12 +868,19 @@ void worker(const Options &o, int device, float sr, const std::vector<std::strin
                         for (const BatchItem *it : in_batch) al.push_back(o.file_alpha[it->file]);
                         param.batch_set_alphas(al.data(), (int)al.size());
                     }
+                    if (o.vad)
+                        param.batch_set_vad(o.vad_column, o.vad_energy_threshold, o.vad_energy_mean_scale, o.vad_frames_context,
+                                            o.vad_proportion_threshold, MFX_VAD_SELECT);
                     float *rows = (float *)b.rows.get((size_t)std::max<long long>(b.total_rows, 1) * width * sizeof(float));
                     param.batch_run_host((const short *)b.pcm.p, b.samples, rows);
+                    std::vector<int> voiced(in_batch.size());
+                    if (o.vad) param.batch_vad_read(nullptr, voiced.data(), nullptr);
                     for (size_t k = 0; k < in_batch.size(); ++k) {
                         BatchItem &it = *in_batch[k];
                         it.row0 = row0[k];
                         if (it.frames != param.batch_frames(it.conv_len)) throw std::runtime_error("frame count mismatch");
+                        it.out_frames = o.vad ? voiced[k] : it.frames;
+                        if (o.vad) continue; // (selected rows have no reference analogue: nothing of B1 to reproduce on them)
                         // The reference's flush after exactly one set_input reads its D static rows D rows early (B1,
                         // mfcccpu.cpp:439 + segmentercpu.cpp:97-106): rows T - D .. T - 1 repeat the statics of rows
                         // T - 2 D .. T - D - 1 (deltas unaffected).  The batch entries deliver the correct rows; the
@@ -878,6 +897,10 @@ void worker(const Options &o, int device, float sr, const std::vector<std::strin
                 for (BatchItem &it : b.items)
                     if (it.error.empty() && it.stream) {
                         try {
+                            if (o.vad)
+                                throw std::runtime_error("--vad: \"" + files[2 * it.file] +
+                                                         "\" would take the per-file loop (longer than one block, too short for the "
+                                                         "deltas, or an alpha sweep): frames are selected in batches of whole files only");
                             process_file(param, o, it.wav, files[2 * it.file], files[2 * it.file + 1], sr, sc,
                                          o.file_alpha.empty() ? nullptr : &o.file_alpha[it.file]);
                         } catch (const std::exception &e) {
@@ -1006,6 +1029,12 @@ int main(int argc, char **argv)
         else if (a == "--io-threads") o.io_threads = std::max(1, std::atoi(val()));
         else if (a == "--resample-to") o.resample_to = std::atoi(val());
         else if (a == "--resample-zeros") o.resample_zeros = std::atoi(val());
+        else if (a == "--vad") o.vad = true;
+        else if (a == "--vad-energy-threshold") o.vad_energy_threshold = (float)std::atof(val());
+        else if (a == "--vad-energy-mean-scale") o.vad_energy_mean_scale = (float)std::atof(val());
+        else if (a == "--vad-frames-context") o.vad_frames_context = std::atoi(val());
+        else if (a == "--vad-proportion-threshold") o.vad_proportion_threshold = (float)std::atof(val());
+        else if (a == "--vad-column") o.vad_column = std::atoi(val());
         else if (a == "--selftest-format") { // put_f32 against printf("%f") on n random bit patterns + the known hard cases
             const long n = std::atol(val());
             uint64_t st = 0x9E3779B97F4A7C15ull;
@@ -1051,6 +1080,10 @@ int main(int argc, char **argv)
                         "         [--resample-to hz [--resample-zeros n]]\n"
                         "  --resample-to: extract at hz instead of the first file's rate; files at other rates are converted on the\n"
                         "                device (Hann-windowed sinc, n zero crossings per side, default 6)\n"
+                        "         [--vad [--vad-energy-threshold x] [--vad-energy-mean-scale x] [--vad-frames-context n]\n"
+                        "          [--vad-proportion-threshold x] [--vad-column n]]\n"
+                        "  --vad: energy voice-activity decision on the device (needs batches); every output file holds its voiced\n"
+                        "                rows only.  Defaults 5, 0.5, 0, 0.6 (compute-vad-energy's); column -1 = the last static one\n"
                         "  --devs: one worker per listed GPU, files dealt from a shared queue\n"
                         "  inputs: RIFF/WAVE or NIST SPHERE, 16-bit PCM; output: the reference's text rows, or HTK binary\n");
             return 0;
@@ -1087,6 +1120,10 @@ int main(int argc, char **argv)
             std::fprintf(stderr, "--alpha-file holds %zu warp factors for %zu input files\n", o.file_alpha.size(), files.size() / 2);
             return 2;
         }
+    }
+    if (o.vad && o.batch_mb <= 0) {
+        std::fprintf(stderr, "--vad selects frames in batches of whole files: --batch-mb must be positive\n");
+        return 2;
     }
     if (!o.spk_file.empty()) {
         if (o.norm < 1 || o.norm > 3) {

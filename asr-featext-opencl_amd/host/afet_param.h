@@ -121,6 +121,14 @@ public:
                             const double *prior_acc = nullptr, bool prior_only = false);
     // what the last run used: count [n_spk], acc [n_spk][4][Wn] (S, S2, min, max), stats [n_spk][2][Wn]; any may be null
     void batch_speaker_stats(long long *count, double *acc, float *stats);
+    // energy VAD + voiced-frame selection as the last stage of the planned batch's runs (mfx_batch_set_vad; mode MFX_VAD_*);
+    // the next batch_plan clears it, and so does batch_clear_vad
+    void batch_set_vad(int column, float energy_threshold, float energy_mean_scale, int frames_context, float proportion_threshold,
+                       int mode);
+    void batch_clear_vad();
+    // what the last run decided: flags [total_rows], voiced [n_utt], threshold [n_utt]; any may be null.  Returns the batch's
+    // voiced rows
+    long long batch_vad_read(unsigned char *flags, int *voiced, float *threshold);
     // mfx_set_alpha at once, for the batch entries (there is no apply() to carry m_alpha there)
     void set_warp(float alpha);
     long long batch_frames(long long samples) const;

@@ -204,6 +204,24 @@ void MfccHip::batch_speaker_stats(long long *count, double *acc, float *stats)
     check(mfx_batch_speaker_stats(m_handle, (int64_t *)count, acc, stats));
 }
 
+void MfccHip::batch_set_vad(int column, float energy_threshold, float energy_mean_scale, int frames_context, float proportion_threshold,
+                            int mode)
+{
+    check(mfx_batch_set_vad(m_handle, column, energy_threshold, energy_mean_scale, frames_context, proportion_threshold, mode));
+}
+
+void MfccHip::batch_clear_vad()
+{
+    check(mfx_batch_clear_vad(m_handle));
+}
+
+long long MfccHip::batch_vad_read(unsigned char *flags, int *voiced, float *threshold)
+{
+    int64_t total = 0;
+    check(mfx_batch_vad_read(m_handle, flags, (int32_t *)voiced, threshold, &total));
+    return (long long)total;
+}
+
 void MfccHip::set_warp(float alpha)
 {
     m_alpha = alpha;

@@ -77,6 +77,7 @@ EXPORTED_SYMBOLS = (
     "mfx_batch_plan_rates", "mfx_batch_resample_layout", "mfx_host_resample_taps", "mfx_host_resampled_length",
     "mfx_host_resample_layout", "mfx_host_resample_tile",
     "mfx_batch_set_speakers", "mfx_batch_speaker_stats", "mfx_host_speaker_lists",
+    "mfx_batch_set_vad", "mfx_batch_clear_vad", "mfx_batch_vad_read", "mfx_batch_vad_device",
 )
 
 
@@ -172,6 +173,10 @@ def load_library():
     L.mfx_batch_set_speakers.argtypes = [vp, p32, i32, i32, p64, dp, i32]
     L.mfx_batch_speaker_stats.argtypes = [vp, p64, dp, fp]
     L.mfx_host_speaker_lists.argtypes, L.mfx_host_speaker_lists.restype = [i32, p32, p64, i32, p32, p32], i64
+    L.mfx_batch_set_vad.argtypes = [vp, i32, C.c_float, C.c_float, i32, C.c_float, i32]
+    L.mfx_batch_clear_vad.argtypes = [vp]
+    L.mfx_batch_vad_read.argtypes = [vp, C.POINTER(C.c_uint8), p32, fp, p64]
+    L.mfx_batch_vad_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     _lib = L
     return L
 
@@ -468,6 +473,7 @@ KERNEL_TABLE = (
 )
 
 
+VAD_FLAGS, VAD_SELECT, VAD_PACK = 0, 1, 2                  # mfx_batch_set_vad modes (include/mfx.h)
 SPK_POOL, SPK_PRIOR_ONLY = 0, 1                            # mfx_batch_set_speakers modes (include/mfx.h)
 ENGINE_NO_FRONT1024, ENGINE_FUSE_DELTA, ENGINE_NO_FRONT2048, ENGINE_STREAM_KERNELS, ENGINE_NORM_TWO_KERNELS = 1, 2, 4, 8, 16
 ENGINE_DMA_SMALL_BLOCKS, ENGINE_NO_DCT_SPLIT, ENGINE_NO_STUFF256, ENGINE_FRONT1024_12_WAVES = 32, 64, 128, 256     # mfx_config.engine bits (include/mfx.h)
@@ -740,6 +746,37 @@ class MfccHip:
         return count, acc, stats
 
     host_speaker_lists = staticmethod(host_speaker_lists)
+
+    def batch_set_vad(self, column=-1, energy_threshold=5.0, energy_mean_scale=0.5, frames_context=0,
+                      proportion_threshold=0.6, mode=VAD_FLAGS):
+        """Energy VAD as the last stage of a batch run (mfx_batch_set_vad; the defaults are compute-vad-energy's): frame t
+        is voiced when at least proportion_threshold of the frames within frames_context of it (inside the utterance) have
+        column `column` (-1: the last static column) above energy_threshold + energy_mean_scale * the utterance's mean.
+        VAD_FLAGS leaves the rows alone; VAD_SELECT moves every utterance's voiced rows to the front of its row range;
+        VAD_PACK packs the whole batch's voiced rows; what is left over is zero.  A later batch_plan clears it."""
+        self._chk(self._L.mfx_batch_set_vad(self._h, int(column), float(energy_threshold), float(energy_mean_scale),
+                                            int(frames_context), float(proportion_threshold), int(mode)))
+
+    def batch_clear_vad(self):
+        self._chk(self._L.mfx_batch_clear_vad(self._h))
+
+    def batch_vad_read(self):
+        """(flags [total_rows] uint8, voiced [n_utt] int32, threshold [n_utt] float32, total_voiced) of the last batch run,
+        while a VAD is in force (MfxError with status -8 otherwise)."""
+        n = 0 if self._plan_rows is None else self._plan_rows.size
+        flags = np.zeros(int(self._plan_total or 0), np.uint8)
+        voiced, thr = np.zeros(n, np.int32), np.zeros(n, np.float32)
+        total = C.c_int64(0)
+        self._chk(self._L.mfx_batch_vad_read(self._h, flags.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                             voiced.ctypes.data_as(C.POINTER(C.c_int32)),
+                                             thr.ctypes.data_as(C.POINTER(C.c_float)), C.byref(total)))
+        return flags, voiced, thr, total.value
+
+    def batch_vad_device(self):
+        """Device addresses (d_flags, d_voiced, d_packed_row0) of the handle-owned arrays of the VAD in force."""
+        a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._chk(self._L.mfx_batch_vad_device(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value or 0, b.value or 0, c.value or 0
 
     def batch_output_width(self):
         """Row width of the batch entries' output: out_dim while a transform is in force, else get_output_data_width()."""

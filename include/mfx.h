@@ -315,6 +315,57 @@ int mfx_batch_set_speakers(mfx_handle *h, const int32_t *utt_spk, int32_t n_utt,
                            int32_t mode);
 int mfx_batch_speaker_stats(mfx_handle *h, int64_t *count, double *acc, float *stats /* [n_spk][2][Wn] mean, multiplier */);
 
+/* Energy voice-activity decision and voiced-frame selection as the last stage of a batch run ("Voice activity and
+ * frame selection"): compute-vad-energy followed by select-voiced-frames of a Kaldi-style recipe, on the device, behind
+ * everything else a run does.  No reference analogue: the reference hands every frame to its consumer.
+ *   Input.  For utterance u with T frames, y[t] is the row the handle delivers today WITHOUT a transform: width Wd =
+ *     mfx_get_output_data_width, normalised if normalisation is on (per utterance or per speaker).  e[t] = y[t][column];
+ *     column = -1 means the last static column (c0 when want_c0).  A transform in force does not change what is read.
+ *   Threshold.  thr_u = (float)((double)energy_threshold + (double)energy_mean_scale * (S / T)), S = the sum of e[t] over
+ *     all T rows in double: rows i, i + 256, ... of every 4096-row chunk by one owner in ascending order, a halving tree over
+ *     the 256 owners, the chunks in ascending order.  No atomics: thr_u does not depend on the other utterances of the batch,
+ *     on buffer placement, or on the run.  T = 0 gives thr_u = energy_threshold.
+ *   Decision (Kaldi's rule; the window is CUT at the utterance ends, not replicated).  For frame t, den = the number of t2 in
+ *     [t - frames_context, t + frames_context] with 0 <= t2 < T, num = the number of those with e[t2] > thr_u (a float32
+ *     comparison: a NaN on either side is "not greater"), flag[t] = ((float)num >= (float)den * proportion_threshold) in
+ *     float32.  Given the rows and thr_u the flags are an exact function.
+ *   Modes.  Wo = mfx_batch_output_width, which the VAD does not change; out_rows[u] are the plan's and do not move.
+ *     MFX_VAD_FLAGS   d_out is exactly what it is without the VAD; only flags and counts are produced.
+ *     MFX_VAD_SELECT  the voiced rows of u, in ascending t, go to rows out_rows[u] .. out_rows[u] + voiced[u] - 1 -- the
+ *                     rows the handle would deliver without the VAD (the transform's output if one is in force), bit for
+ *                     bit; rows [out_rows[u] + voiced[u], out_rows[u] + T) are written as +0.0f.
+ *     MFX_VAD_PACK    the voiced rows of the whole batch lie back to back: utterance u starts at row packed_row0[u], the
+ *                     exclusive prefix sum of voiced; packed_row0[n_utt] = total_voiced; rows [total_voiced, total_rows) are
+ *                     written as +0.0f.
+ *     In every mode nothing outside [d_out, d_out + total_rows * Wo) is written, and mfx_batch_run_device's placement rule
+ *     holds: any 4-byte alignment, the same bits.
+ *   Scope.  Valid after mfx_batch_plan / mfx_batch_plan_rates (MFX_ERR_STATE before one); a later plan drops the VAD with
+ *     the other attachments, and mfx_batch_clear_vad puts the handle back on today's kernels and bits.  MFX_ERR_ARG: column
+ *     outside [-1, Wd), frames_context outside 0 .. 64, proportion_threshold not in (0, 1], a non-finite energy_threshold or
+ *     energy_mean_scale, an unknown mode.  MFX_ERR_DEVICE on a planning handle.  The flags [total_rows], the counts,
+ *     thresholds and packed_row0, the per-chunk sums and per-tile masks and, for SELECT / PACK, a handle-owned scratch
+ *     [total_rows][Wo] (grown, never shrunk; re-sized by a later mfx_batch_set_transform) are allocated HERE (the call waits
+ *     for the handle's streams); mfx_batch_run_device still allocates nothing.
+ *   Composition.  Everything else in a run is unchanged -- front end, MFX_ENGINE_* bits, alpha list, rates plan, speaker
+ *     list, mfx_batch_overlap, the transform.  In SELECT / PACK the run's last stage writes to the scratch instead of the
+ *     caller's array; the VAD's launches follow on the stream the tail runs on.  mfx_batch_run_host works in every mode; its
+ *     sliced path stays on in FLAGS and SELECT (utterances are independent), PACK takes the unsliced path as a speaker list
+ *     does.
+ *   Read-back.  mfx_batch_vad_read synchronises and returns what the last run produced: flags [total_rows] (0 / 1),
+ *     voiced [n_utt], threshold [n_utt], *total_voiced.  Any output may be NULL.  MFX_ERR_STATE without a VAD in force or
+ *     before a run.  mfx_batch_vad_device returns the handle-owned device arrays (d_packed_row0 has n_utt + 1 entries): valid
+ *     until the next plan or clear, and ordered after the run on the stream its tail ran on (the handle's stream, or
+ *     mfx_synchronize with mfx_batch_overlap on).
+ * NOT served: the session entries (mfx_sessions_*) and the streaming interface are untouched and ignore the VAD. */
+enum { MFX_VAD_FLAGS = 0, MFX_VAD_SELECT = 1, MFX_VAD_PACK = 2 };
+int mfx_batch_set_vad(mfx_handle *h, int32_t column, float energy_threshold, float energy_mean_scale, int32_t frames_context,
+                      float proportion_threshold, int32_t mode);
+int mfx_batch_clear_vad(mfx_handle *h);
+int mfx_batch_vad_read(mfx_handle *h, uint8_t *flags /* [total_rows] */, int32_t *voiced /* [n_utt] */,
+                       float *threshold /* [n_utt] */, int64_t *total_voiced);
+int mfx_batch_vad_device(const mfx_handle *h, const uint8_t **d_flags, const int32_t **d_voiced,
+                         const int64_t **d_packed_row0 /* [n_utt + 1] */);
+
 /* ---- sample-rate conversion in front of a batch ("Sample-rate conversion").  No reference analogue: the
  *      reference refuses a file whose rate differs from the first file's (ASR_OCL.cpp:191). ----
  *
