@@ -33,6 +33,7 @@ from .mfcc import (  # noqa: F401
     host_plp_tables,
     host_session_step,
     host_speaker_lists,
+    host_online_norm,
     SPK_POOL,
     SPK_PRIOR_ONLY,
     VAD_FLAGS,

@@ -871,9 +871,9 @@ extern "C" int64_t mfx_debug_read(mfx_handle *h, int kind, void *dst, int64_t ds
         count = h->cfg.norm == MFX_NORM_NONE ? 0 : (int64_t)(h->cfg.norm_after_dyn ? h->width / h->cols : 1) * 2 * h->cols;
         break;
     case 6: // normaliser statistics of the last batch run: [groups][n_utt][2][cols] (none while a speaker list is in force:
-            // mfx_batch_speaker_stats returns those)
+            // mfx_batch_speaker_stats returns those; none with the online normaliser: every row has its own)
         src = h->batch.d_stats.p;
-        count = h->cfg.norm == MFX_NORM_NONE || h->batch.spk.on ? 0
+        count = h->cfg.norm == MFX_NORM_NONE || h->batch.spk.on || h->batch.on.on ? 0
                                              : (int64_t)(h->cfg.norm_after_dyn ? h->width / h->cols : 1) * h->batch.n_utt * 2 * h->cols;
         break;
     case 7: // PLP autocorrelations of the last plain streaming apply(): [frames_with_context][lpc_order + 1]

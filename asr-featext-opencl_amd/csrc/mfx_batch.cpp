@@ -50,6 +50,32 @@ int run_speaker_norm(mfx_handle *h, hipStream_t stream, float *data)
     return MFX_OK;
 }
 
+// the normaliser of a run while the online attachment is in force: in run_norm's place, on its stream, from the raw rows of
+// the scratch (d_pre) into the run's rows (d_out), over the chunks of the utterance range
+int run_online_norm(mfx_handle *h, hipStream_t stream, const float *d_pre, float *d_out, int u0, int u1)
+{
+    const BatchState &B = h->batch;
+    OnormParams op{};
+    op.src = d_pre;
+    op.src_pitch = h->width;
+    op.out = d_out;
+    op.out_pitch = h->width;
+    op.Wn = spk_wn(h);
+    op.window = B.on.window;
+    op.cvn = h->cfg.norm == MFX_NORM_CVN ? 1 : 0;
+    op.prior_frames = B.on.prior_frames;
+    op.prior_count = B.on.prior_count;
+    op.prior_acc = B.on.d_prior.p;
+    op.segs = B.d_segs.p;
+    op.utt_chunk0 = B.on.d_utt_chunk0.p;
+    op.chunk_utt = B.on.d_chunk_utt.p;
+    op.tot = B.on.d_tot.p;
+    op.u0 = u0, op.n_utt = u1 - u0;
+    op.chunk_first = B.on.utt_chunk0[u0], op.n_chunks = B.on.utt_chunk0[u1] - B.on.utt_chunk0[u0];
+    HIP_TRY(h, launch_onorm(op, stream));
+    return MFX_OK;
+}
+
 // ---- stage 1: the checks every layout of the PCM array goes through (the caller's, and the scratch of a rates plan)
 int check_layout(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_total, const std::vector<int64_t> &off,
                  const std::vector<int64_t> &len, int u0, int u1)
@@ -87,6 +113,9 @@ struct RunMode {
     float *d_out, *d_last, *d_final; // where the rows y are built, where the run's last stage before the VAD writes, where
                             // the caller wants the result: all the same unless a transform (d_out is its scratch) or a
                             // selecting VAD (d_last is its scratch) is in force
+    float *d_pre;           // where everything AHEAD of the normaliser's place writes: d_out, unless the online normaliser is
+                            // in force (its raw-row scratch: it must not run in place, its trailing edge reads raw rows that
+                            // another block may already have turned into output)
     int sb;                 // which of the two statics buffers (overlap)
     bool via_scratch;       // With deltas on, the front end writes its statics as compact 64-byte rows into a scratch buffer
                             // and the delta kernel emits whole [static | d | dd] rows: every HBM write is then a full line
@@ -112,11 +141,12 @@ RunMode decide_mode(const mfx_handle *h, FrontParams &p, float *d_out, bool whol
     m.d_final = d_out;
     m.d_last = (B.vad.on && B.vad.mode != MFX_VAD_FLAGS) ? B.vad.d_rows.p : d_out;
     m.d_out = B.xf.on ? B.xf.d_y.p : m.d_last;
+    m.d_pre = B.on.on ? B.on.d_raw.p : m.d_out;
     const bool norm_before = h->cfg.norm != MFX_NORM_NONE && !h->cfg.norm_after_dyn;
     m.sb = (B.ov.enabled && whole) ? (int)(B.ov.seq & 1) : 0;
     m.via_scratch = compact_statics(m.kind, p) && h->l1 > 0 && h->cols <= 16 && !h->traps && !norm_before &&
                     B.d_static16[m.sb].n >= (size_t)B.total_rows * 16;
-    m.fuse = whole && h->fuse.planned && m.kind == kFront512 && m.via_scratch && ((uintptr_t)m.d_out & 15) == 0;
+    m.fuse = whole && h->fuse.planned && m.kind == kFront512 && m.via_scratch && ((uintptr_t)m.d_pre & 15) == 0;
     if (m.fuse) {
         p.dl1 = h->l1;
         p.dl2 = h->l2;
@@ -140,7 +170,7 @@ int run_front(mfx_handle *h, FrontParams &p, const RunMode &m, int u0, int u1, i
         p.blk_chunk_off = h->fuse.d_blk_chunk_off.p;
         p.blk_tile_off = h->fuse.d_blk_tile_off.p;
         p.tiles = h->fuse.d_tiles.p;
-        p.out = m.d_out;
+        p.out = m.d_pre; // (fusing means no normaliser before the deltas: the delta wave is ahead of the normaliser's place)
         p.out_pitch = h->width;
         p.n_blocks = h->fuse.blocks;
         p.err_flag = h->fuse.d_err.p;
@@ -173,7 +203,7 @@ int run_front(mfx_handle *h, FrontParams &p, const RunMode &m, int u0, int u1, i
         fill_traps(h, tp);
         tp.src = B.d_logmel.p;
         tp.src_pitch = B.mel_pitch;
-        tp.out = m.d_out;
+        tp.out = m.d_pre;
         tp.out_pitch = h->width;
         tp.segs = B.d_segs.p + u0;
         tp.n_segs = u1 - u0;
@@ -183,11 +213,13 @@ int run_front(mfx_handle *h, FrontParams &p, const RunMode &m, int u0, int u1, i
     return MFX_OK;
 }
 
-// the normaliser of a run over `groups` column groups of m.d_out: the speaker list's kernels while one is in force (the run
-// then covers the whole batch, mfx_batch_run_host does not slice), else every utterance's own statistics
+// the normaliser of a run over `groups` column groups of m.d_out: the online attachment's kernels while it is in force (raw
+// rows from m.d_pre), the speaker list's while one is (the run then covers the whole batch, mfx_batch_run_host does not
+// slice), else every utterance's own statistics
 int run_batch_norm(mfx_handle *h, const RunMode &m, int u0, int u1, int groups, size_t group_stats_stride)
 {
     const BatchState &B = h->batch;
+    if (B.on.on) return run_online_norm(h, m.tail_stream, m.d_pre, m.d_out, u0, u1);
     if (B.spk.on) return run_speaker_norm(h, m.tail_stream, m.d_out);
     return run_norm(h, m.tail_stream, m.d_out, h->width, B.d_segs.p + u0, u1 - u0, nullptr, B.d_stats.p + (size_t)u0 * 2 * h->cols, false,
                     B.tiles_max * 64, groups, group_stats_stride);
@@ -243,9 +275,11 @@ int run_tail(mfx_handle *h, const RunMode &m, int u0, int u1)
     }
     if (h->l1 > 0 && !m.fuse) {
         DeltaParams dp{};
-        dp.src = m.via_scratch ? B.d_static16[m.sb].p : m.d_out;
+        // (the online normaliser in force: behind it the deltas work on d_out as always, ahead of it on its scratch)
+        float *rows = B.on.on && h->cfg.norm_after_dyn ? m.d_pre : m.d_out;
+        dp.src = m.via_scratch ? B.d_static16[m.sb].p : rows;
         dp.src_pitch = m.via_scratch ? 16 : h->width;
-        dp.out = m.d_out;
+        dp.out = rows;
         dp.out_pitch = h->width;
         dp.segs = B.d_segs.p + u0;
         dp.n_segs = u1 - u0;
@@ -318,7 +352,8 @@ int batch_run_range(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_tot
         return run_vad(h, none, u0, u1);
     }
     if ((B.xf.on && B.xf.d_y.n < (size_t)B.total_rows * h->width) || (h->traps && B.d_logmel.n < (size_t)B.total_rows * B.mel_pitch) ||
-        (B.vad.on && B.vad.mode != MFX_VAD_FLAGS && B.vad.d_rows.n < (size_t)B.total_rows * batch_out_width(h)))
+        (B.vad.on && B.vad.mode != MFX_VAD_FLAGS && B.vad.d_rows.n < (size_t)B.total_rows * batch_out_width(h)) ||
+        (B.on.on && B.on.d_raw.n < (size_t)B.total_rows * h->width))
         return fail(h, MFX_ERR_STATE, "batch not planned");
 
     FrontParams p;
@@ -331,7 +366,7 @@ int batch_run_range(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_tot
         p.feat = B.d_static16[m.sb].p;
         p.feat_pitch = 16;
     } else { // (TRAPS: the front end's log mel rows go to the scratch; k_traps turns them into the statics of d_out)
-        p.feat = h->traps ? B.d_logmel.p : m.d_out;
+        p.feat = h->traps ? B.d_logmel.p : m.d_pre;
         p.feat_pitch = h->traps ? B.mel_pitch : h->width;
     }
     if ((rc = run_front(h, p, m, u0, u1, c0, c1)) != MFX_OK) return rc;

@@ -1,7 +1,7 @@
 // mfx_batch_attach.cpp -- what a caller attaches to a planned batch (include/mfx.h): per-utterance warp factors, a splice +
-// affine transform, a speaker list, the energy VAD.  Each is tied to the plan (mfx_batch_plan_rates' converter is the fifth,
-// and is the planner's); BatchState::detach drops the four of this file.  This file owns `batch.va`, `batch.xf`, `batch.spk`
-// and `batch.vad`.
+// affine transform, a speaker list, the energy VAD, the online normaliser.  Each is tied to the plan (mfx_batch_plan_rates'
+// converter is the sixth, and is the planner's); BatchState::detach drops the five of this file.  This file owns `batch.va`,
+// `batch.xf`, `batch.spk`, `batch.vad` and `batch.on`.
 #include "mfx_handle.h"
 
 #include <cmath>
@@ -59,6 +59,8 @@ extern "C" int mfx_batch_set_speakers(mfx_handle *h, const int32_t *utt_spk, int
         return MFX_OK;
     }
     if (!h->batch.planned) return fail(h, MFX_ERR_STATE, "mfx_batch_set_speakers: no batch is planned");
+    if (h->batch.on.on)
+        return fail(h, MFX_ERR_STATE, "mfx_batch_set_speakers: the online normaliser is in force (mfx_batch_clear_online_norm first)");
     if (!utt_spk || n_utt != h->batch.n_utt) return fail(h, MFX_ERR_ARG, "one speaker per planned utterance");
     if (n_spk < 1 || n_spk > (1 << 20)) return fail(h, MFX_ERR_ARG, "n_spk must be 1 .. 2^20");
     if ((prior_count == nullptr) != (prior_acc == nullptr)) return fail(h, MFX_ERR_ARG, "a prior is a count AND an accumulator per speaker");
@@ -147,6 +149,76 @@ extern "C" int64_t mfx_host_speaker_lists(int32_t n_utt, const int32_t *utt_spk,
     if (off) std::copy(o.begin(), o.end(), off);
     if (list) std::copy(l.begin(), l.end(), list);
     return (int64_t)l.size();
+}
+
+// ------------------------------------------------------------------------------------------------
+// online CMN / CVN ("Online normalisation")
+// ------------------------------------------------------------------------------------------------
+
+int check_online_norm(mfx_handle *h, const char *who, int32_t window, int32_t prior_frames, int64_t prior_count, const double *prior_acc)
+{
+    const std::string w(who);
+    if (h->cfg.norm != MFX_NORM_CMN && h->cfg.norm != MFX_NORM_CVN)
+        return fail(h, MFX_ERR_CONFIG, w + ": the online normaliser serves norm = CMN and CVN only");
+    if (spk_wn(h) > 256) return fail(h, MFX_ERR_CONFIG, w + ": more than 256 normalised columns");
+    if (window < 0 || window > 4096 || window % 32 != 0) return fail(h, MFX_ERR_ARG, w + ": window must be 0 or a multiple of 32 in 32 .. 4096");
+    if (prior_frames < 0 || prior_frames > (1 << 20)) return fail(h, MFX_ERR_ARG, w + ": prior_frames must be 0 .. 2^20");
+    if (prior_count < 0) return fail(h, MFX_ERR_ARG, w + ": negative prior_count");
+    if ((prior_acc == nullptr) != (prior_count == 0)) return fail(h, MFX_ERR_ARG, w + ": prior_acc must be NULL exactly when prior_count is 0");
+    return MFX_OK;
+}
+
+extern "C" int mfx_batch_set_online_norm(mfx_handle *h, int32_t window, int32_t prior_frames, int64_t prior_count, const double *prior_acc)
+{
+    MFX_DEVICE_ENTRY(h);
+    BatchState &B = h->batch;
+    int rc = check_online_norm(h, "mfx_batch_set_online_norm", window, prior_frames, prior_count, prior_acc);
+    if (rc == MFX_ERR_CONFIG) return rc;
+    if (!B.planned) return fail(h, MFX_ERR_STATE, "mfx_batch_set_online_norm: no batch is planned");
+    if (rc != MFX_OK) return rc;
+    if (B.spk.on) return fail(h, MFX_ERR_STATE, "mfx_batch_set_online_norm: a speaker list is in force (clear it first)");
+    const int Wn = spk_wn(h);
+    std::vector<int32_t> chunk0((size_t)B.n_utt + 1), chunk_utt;
+    int64_t chunks = 0;
+    for (int u = 0; u < B.n_utt; ++u) {
+        chunk0[u] = (int32_t)chunks;
+        const int64_t n = (B.utt_frames[u] + 31) / 32;
+        chunks += n;
+        if (chunks > 0x7ffffff0) return fail(h, MFX_ERR_ARG, "batch too long");
+        chunk_utt.insert(chunk_utt.end(), (size_t)n, u);
+    }
+    chunk0[B.n_utt] = (int32_t)chunks;
+    HIP_TRY(h, hipSetDevice(h->device));
+    rc = mfx_synchronize(h); // (a run in flight may read the lists replaced below)
+    if (rc != MFX_OK) return rc;
+    BatchState::Onorm &on = B.on;
+    on.drop();
+    // (everything mfx_batch_run_device needs is allocated here: that entry never allocates)
+    HIP_TRY(h, h->upload(on.d_utt_chunk0, chunk0));
+    HIP_TRY(h, h->upload(on.d_chunk_utt, chunk_utt));
+    if (prior_count > 0)
+        HIP_TRY(h, h->upload(on.d_prior, std::vector<double>(prior_acc, prior_acc + (size_t)2 * Wn)));
+    else
+        on.d_prior.release();
+    HIP_TRY(h, on.d_tot.alloc((size_t)chunks * 2 * Wn));
+    const size_t need = (size_t)std::max<int64_t>(B.total_rows, 1) * h->width;
+    if (on.d_raw.n < need) HIP_TRY(h, on.d_raw.alloc(need));
+    on.utt_chunk0.swap(chunk0);
+    on.window = window, on.prior_frames = prior_frames, on.prior_count = prior_count;
+    on.on = true;
+    return MFX_OK;
+}
+
+extern "C" int mfx_batch_clear_online_norm(mfx_handle *h)
+{
+    MFX_DEVICE_ENTRY(h);
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int rc = mfx_synchronize(h); // (a run in flight may read what is released below)
+    if (rc != MFX_OK) return rc;
+    BatchState::Onorm &on = h->batch.on;
+    on.drop();
+    on.d_utt_chunk0.release(), on.d_chunk_utt.release(), on.d_prior.release(), on.d_tot.release(), on.d_raw.release();
+    return MFX_OK;
 }
 
 int batch_out_width(const mfx_handle *h) { return h->batch.xf.on ? h->batch.xf.out : h->width; }

@@ -3,7 +3,8 @@
 //   mfx_api.cpp    lifetime, tables, kernel choice and front-end dispatch, profiling, test taps (writes the shared part)
 //   mfx_stream.cpp the streaming state machine and its host copies         (owns `st` and `sweep`)
 //   mfx_batch_plan.cpp   the batch planner, the rates planner, the fused-delta plan (owns `batch`'s plan, `batch.rs`, `fuse`)
-//   mfx_batch_attach.cpp what is attached to a plan: warp factors, transform, speakers, VAD (owns `batch.va`, `.xf`, `.spk`, `.vad`)
+//   mfx_batch_attach.cpp what is attached to a plan: warp factors, transform, speakers, VAD, online normaliser (owns `batch.va`,
+//                        `.xf`, `.spk`, `.vad`, `.on`)
 //   mfx_batch.cpp        the batch runner, device and host entries, overlap   (owns `batch.ov` and `batch.host`)
 //   mfx_sessions_host.cpp the session entries: many live streams per push       (owns `sess`)
 #pragma once
@@ -161,7 +162,7 @@ struct BatchState {
     int tiles_max = 0;
     bool aligned = true;                 // frames on aligned sample pairs (fill_front / choose_front read it)
 
-    // Five attachments, each tied to the plan: a new plan drops them.  drop() switches one off and releases what is not kept
+    // Six attachments, each tied to the plan: a new plan drops them.  drop() switches one off and releases what is not kept
     // for the next one (the grown-never-shrunk scratch stays).
 
     // sample-rate conversion (mfx_batch_plan_rates): while on, the run converts the caller's array into d_pcm with one
@@ -238,9 +239,23 @@ struct BatchState {
         hipStream_t last_stream = nullptr; // the stream the last run's tail ran on
         void drop() { on = false, ran = false; }
     } vad;
+    // online (causal, sliding-window) CMN / CVN (mfx_batch_set_online_norm): while on, everything ahead of the normaliser's
+    // place writes to d_raw instead of the run's d_out, and k_onorm_totals -> k_onorm_offsets -> k_onorm_apply turn the Wn
+    // columns of d_raw into d_out in run_norm's place
+    struct Onorm {
+        bool on = false;
+        int32_t window = 0, prior_frames = 0;
+        int64_t prior_count = 0;
+        std::vector<int32_t> utt_chunk0; // [n_utt + 1] first 32-row chunk of every utterance
+        DevBuf<int32_t> d_utt_chunk0, d_chunk_utt;
+        DevBuf<double> d_prior;          // [2][Wn] (empty without a prior)
+        DevBuf<double> d_tot;            // [chunks][2][Wn]
+        DevBuf<float> d_raw;             // [total_rows][width] (grown, never shrunk: only mfx_batch_clear_online_norm releases it)
+        void drop() { on = false; }
+    } on;
     // what a new utterance list invalidates (the converter is mfx_batch_plan's to drop: mfx_batch_plan_rates plans through
     // plan_batch too)
-    void detach() { va.drop(), xf.drop(), spk.drop(), vad.drop(); }
+    void detach() { va.drop(), xf.drop(), spk.drop(), vad.drop(), on.drop(); }
 
     // ---- not tied to the plan
     // optional overlap of the delta/normalisation tail of batch i with the front end of batch i+1 (mfx_batch_overlap)
@@ -298,6 +313,16 @@ struct SessState {
         int32_t parity = 0;              // which of the two slot arrays holds the state
     };
     std::vector<Live> live;
+    // online normaliser (mfx_sessions_set_online_norm: parameters only; mfx_sessions_create sizes the state)
+    struct Onorm {
+        bool set = false;
+        int32_t window = 0, prior_frames = 0;
+        int64_t prior_count = 0;
+        std::vector<double> prior;       // [2][Wn] (empty without a prior)
+        DevBuf<double> d_prior, d_state; // [2][Wn]; [n][8][Wn] lead / trail O and I of v and q
+        DevBuf<float> d_ring;            // [n][window][Wn] the last `window` raw rows of every session
+    } on;
+    std::vector<mfx::OnormSessDesc> p_onorm; // the pending push's rows to normalise
     // the pending push (mfx_sessions_plan; mfx_sessions_run_* consumes it)
     bool planned = false;
     std::vector<int32_t> p_ids;
@@ -535,8 +560,11 @@ int plan_batch(mfx_handle *h, int32_t n_utt, const int64_t *offsets, const int64
 int size_static16(mfx_handle *h);
 // row width of the batch entries' output: out_dim while a transform is in force, else `width`
 int batch_out_width(const mfx_handle *h);
-// normalised columns of a speaker list: the whole row after the deltas, else the statics
+// normalised columns of a speaker list and of the online normaliser: the whole row after the deltas, else the statics
 inline int spk_wn(const mfx_handle *h) { return h->cfg.norm_after_dyn ? h->width : h->cols; }
+// mfx_batch_set_online_norm / mfx_sessions_set_online_norm: the checks the two setters share (MFX_OK, or the status with the
+// message on the handle)
+int check_online_norm(mfx_handle *h, const char *who, int32_t window, int32_t prior_frames, int64_t prior_count, const double *prior_acc);
 void fill_xform(const mfx_handle *h, mfx::XformParams &p);
 // the VAD's row scratch at the current output width (mfx_batch_attach.cpp; a no-op unless a selecting VAD is in force)
 int size_vad_rows(mfx_handle *h);

@@ -1,4 +1,4 @@
-// mfx_kernels.h -- launch interface of the gfx950 kernels (implemented in mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip, mfx_plp.hip, mfx_traps.hip, mfx_xform.hip, mfx_sessions.hip, mfx_resample.hip, mfx_speakers.hip, mfx_vad.hip: one translation unit per kernel family).
+// mfx_kernels.h -- launch interface of the gfx950 kernels (implemented in mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip, mfx_plp.hip, mfx_traps.hip, mfx_xform.hip, mfx_sessions.hip, mfx_resample.hip, mfx_speakers.hip, mfx_vad.hip, mfx_onorm.hip: one translation unit per kernel family).
 //
 // Kernel inventory and the reference stage each one replaces:
 //   spectrum512 / fused512   segmenter.cl kernelSegmentWindow + AppleFFT fft0 + mfcc.cl kernelTranspose
@@ -14,6 +14,8 @@
 //                            its files at the one rate its model was trained at)
 //   vad_*                    energy voice-activity decision + voiced-frame selection of finished rows (no reference analogue: the
 //                            reference hands every frame to its consumer)
+//   onorm_*                  online (causal, sliding-window) CMN / CVN of the batch and session entries (no reference analogue: its
+//                            NormalizerCPU keeps one block's statistics)
 //   delta                    delta.cl kernelDelta x2 + the staging copies of mfccopencl.cpp:360-387
 //   norm_stats / norm_apply  norm.cl kernelSum + kernelFinalizeSum / kernelNormalize
 #pragma once
@@ -395,10 +397,55 @@ struct VadParams {
     int32_t width;
 };
 
+// Online CMN / CVN (mfx_batch_set_online_norm, mfx_sessions_set_online_norm; mfx_onorm.hip; DESIGN.md, "Online
+// normalisation").  Chunks are runs of 32 rows of one utterance, numbered through the batch in utterance order; every
+// per-chunk array is indexed absolutely, so that a run over an utterance range fills its part and leaves the rest.
+struct OnormParams {
+    const float *src;      // the raw rows, [rows][src_pitch], columns [0, Wn): never `out`
+    int32_t src_pitch;
+    float *out;            // [rows][out_pitch], columns [0, Wn) written
+    int32_t out_pitch;
+    int32_t Wn;            // 1 .. 256
+    int32_t window;        // N: 0, or a multiple of 32
+    int32_t cvn;           // 0: CMN, else CVN
+    int32_t prior_frames;  // F
+    int64_t prior_count;   // p
+    const double *prior_acc; // [2][Wn] or null (p == 0)
+    const Segment *segs;   // [n_utt]: uses out_row0 / n_out
+    const int32_t *utt_chunk0; // [n_utt + 1] first chunk of every utterance
+    const int32_t *chunk_utt;  // utterance of every chunk
+    double *tot;           // [chunks][2][Wn]: the chunks' totals of v and q, turned into the offsets O in place
+    int32_t u0, n_utt;     // the utterance range of this run: [u0, u0 + n_utt)
+    int32_t chunk_first, n_chunks; // = utt_chunk0[u0], utt_chunk0[u0 + n_utt] - utt_chunk0[u0]
+};
+
+// k_onorm_sess: the rows one push brings one session, rows [t0, t0 + n_rows) of its stream, normalised in place
+struct OnormSessDesc {
+    int64_t row0;          // first row inside OnormSessParams::data
+    int64_t t0;            // rows of the stream in front of it (0: the session is fresh, its state is not read)
+    int32_t n_rows;
+    int32_t session;
+};
+struct OnormSessParams {
+    float *data;           // [rows][pitch], columns [0, Wn) normalised in place
+    int32_t pitch;
+    int32_t Wn;
+    int32_t window, cvn, prior_frames;
+    int64_t prior_count;
+    const double *prior_acc;
+    const OnormSessDesc *descs;
+    int32_t n_descs;
+    double *state;         // [n_sessions][8][Wn]: lead O (v, q), lead I (v, q), trail O (v, q), trail I (v, q)
+    float *ring;           // [n_sessions][window][Wn] the last `window` raw rows (null when window == 0)
+};
+
 // All launchers are asynchronous on `stream` and return the launch status.
 // every launch of the VAD stage for utterances [u0, u1), in order
 hipError_t launch_vad(const VadParams &p, hipStream_t stream);
 bool vad_shape_ok(const VadParams &p);
+// online normaliser: chunk totals -> offsets -> apply over the utterance range (three launches); the session form
+hipError_t launch_onorm(const OnormParams &p, hipStream_t stream);
+hipError_t launch_onorm_sess(const OnormSessParams &p, hipStream_t stream);
 // per-speaker normalisation: chunk totals; accumulators + statistics; apply.  spk_tile_rows: rows of a tile of k_spk_apply at
 // Wn columns; spk_chunks: 4096-row chunks of an utterance of `rows` rows
 hipError_t launch_spk_sums(const SpkParams &p, hipStream_t stream);

@@ -1,5 +1,6 @@
 // mfx_sessions_host.cpp -- the session entries of include/mfx.h: many open streams, each advanced by one chunk of samples per
-// push, all of them in one launch sequence (k_sess_gather -> front end -> delta).  DESIGN.md section 5, "Session entries".
+// push, all of them in one launch sequence (k_sess_gather -> front end -> delta, with k_onorm_sess before or after the delta
+// while the online normaliser is set).  DESIGN.md section 5, "Session entries".
 // This file owns the handle's `sess` part.  It reads the shared geometry and tables and names no field of `st`, `sweep`,
 // `batch` or `fuse`: a push leaves the streaming state and the batch plan, alpha list and transform as they are.
 #include "mfx_handle.h"
@@ -17,6 +18,8 @@ int not_created(mfx_handle *h) { return fail(h, MFX_ERR_STATE, "mfx_sessions_cre
 // the slot arrays' frames lie on even samples exactly when the shift is even: slot bases and pcm_stride are even
 bool sess_aligned(const mfx_handle *h) { return (h->S % 2) == 0; }
 
+bool norm_before(const mfx_handle *h) { return h->cfg.norm != MFX_NORM_NONE && !h->cfg.norm_after_dyn; }
+
 } // namespace
 
 extern "C" int mfx_sessions_create(mfx_handle *h, int32_t n_sessions, int32_t max_push_samples)
@@ -24,7 +27,7 @@ extern "C" int mfx_sessions_create(mfx_handle *h, int32_t n_sessions, int32_t ma
     MFX_DEVICE_ENTRY(h);
     if (h->traps)
         return fail(h, MFX_ERR_STATE, "the session entries do not serve TRAPS handles (their look-ahead is (L - 1) / 2 frames, not D)");
-    if (h->cfg.norm != MFX_NORM_NONE)
+    if (h->cfg.norm != MFX_NORM_NONE && !h->sess.on.set) // (mfx_sessions_set_online_norm: the one normaliser served)
         return fail(h, MFX_ERR_STATE,
                     "the session entries do not serve normalisation (norm != MFX_NORM_NONE): statistics over an open stream are not built");
     if (n_sessions < 0 || max_push_samples < 0 || (n_sessions == 0) != (max_push_samples == 0))
@@ -40,6 +43,7 @@ extern "C" int mfx_sessions_create(mfx_handle *h, int32_t n_sessions, int32_t ma
     if (n_sessions == 0) {
         ss.d_pcm.release(), ss.d_stat.release(), ss.d_slab.release(), ss.d_desc.release();
         ss.d_host_pcm.release(), ss.d_host_out.release();
+        ss.on.d_prior.release(), ss.on.d_state.release(), ss.on.d_ring.release();
         for (auto &b : ss.h_stage) {
             if (b.p) (void)hipHostFree(b.p);
             b.p = nullptr, b.n = 0;
@@ -66,7 +70,15 @@ extern "C" int mfx_sessions_create(mfx_handle *h, int32_t n_sessions, int32_t ma
         HIP_TRY(h, ss.d_slab.alloc((size_t)ss.slab_rows * h->spec_pitch));
     }
     const size_t chunks_max = (size_t)n_sessions * ((ss.frames_max + kChunkFrames - 1) / kChunkFrames);
-    ss.desc_bytes = (size_t)n_sessions * (sizeof(SessDesc) + sizeof(Segment) + 2 * sizeof(int64_t)) + chunks_max * sizeof(Chunk) + 64;
+    ss.desc_bytes = (size_t)n_sessions * (sizeof(SessDesc) + sizeof(Segment) + 2 * sizeof(int64_t) + sizeof(OnormSessDesc)) +
+                    chunks_max * sizeof(Chunk) + 64;
+    if (h->cfg.norm != MFX_NORM_NONE) { // the online normaliser's state: 8 doubles per session and column, the ring of raw rows
+        const size_t Wn = (size_t)spk_wn(h);
+        HIP_TRY(h, ss.on.d_state.alloc((size_t)n_sessions * 8 * Wn));
+        HIP_TRY(h, ss.on.d_ring.alloc((size_t)n_sessions * ss.on.window * Wn));
+        HIP_TRY(h, h->upload(ss.on.d_prior, ss.on.prior));
+        ss.p_onorm.reserve(n_sessions);
+    }
     HIP_TRY(h, ss.d_desc.alloc(ss.desc_bytes));
     for (int b = 0; b < 2; ++b) {
         HIP_TRY(h, ss.h_stage[b].grow(ss.desc_bytes, ss.desc_bytes, h->stream));
@@ -79,6 +91,30 @@ extern "C" int mfx_sessions_create(mfx_handle *h, int32_t n_sessions, int32_t ma
     ss.p_chunks.reserve(chunks_max);
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     ss.n = n_sessions;
+    return MFX_OK;
+}
+
+extern "C" int mfx_sessions_set_online_norm(mfx_handle *h, int32_t window, int32_t prior_frames, int64_t prior_count, const double *prior_acc)
+{
+    MFX_DEVICE_ENTRY(h);
+    int rc = check_online_norm(h, "mfx_sessions_set_online_norm", window, prior_frames, prior_count, prior_acc);
+    if (rc == MFX_ERR_CONFIG) return rc;
+    if (h->sess.n != 0) return fail(h, MFX_ERR_STATE, "mfx_sessions_set_online_norm: sessions exist (mfx_sessions_create(0, 0) first)");
+    if (rc != MFX_OK) return rc;
+    SessState::Onorm &on = h->sess.on;
+    on.window = window, on.prior_frames = prior_frames, on.prior_count = prior_count;
+    on.prior.clear();
+    if (prior_count > 0) on.prior.assign(prior_acc, prior_acc + (size_t)2 * spk_wn(h));
+    on.set = true;
+    return MFX_OK;
+}
+
+extern "C" int mfx_sessions_clear_online_norm(mfx_handle *h)
+{
+    MFX_DEVICE_ENTRY(h);
+    if (h->sess.n != 0) return fail(h, MFX_ERR_STATE, "mfx_sessions_clear_online_norm: sessions exist (mfx_sessions_create(0, 0) first)");
+    h->sess.on.set = false;
+    h->sess.on.prior.clear();
     return MFX_OK;
 }
 
@@ -168,7 +204,8 @@ extern "C" int mfx_sessions_plan(mfx_handle *h, int32_t n, const int32_t *ids, c
     for (int i = 0; i < n; ++i) ss.p_order[i] = i;
     auto slot_of = [&](int i) { return (int64_t)(ss.live[ids[i]].parity ^ 1) * ss.n + ids[i]; };
     std::sort(ss.p_order.begin(), ss.p_order.end(), [&](int a, int b) { return slot_of(a) < slot_of(b); });
-    ss.p_descs.clear(), ss.p_segs.clear(), ss.p_chunks.clear(), ss.p_runs.clear();
+    ss.p_descs.clear(), ss.p_segs.clear(), ss.p_chunks.clear(), ss.p_runs.clear(), ss.p_onorm.clear();
+    const bool onorm = h->cfg.norm != MFX_NORM_NONE, before = norm_before(h);
     ss.p_tiles_max = 0;
     for (int k = 0; k < n; ++k) {
         const int i = ss.p_order[k];
@@ -201,6 +238,11 @@ extern "C" int mfx_sessions_plan(mfx_handle *h, int32_t n, const int32_t *ids, c
             ss.p_chunks.push_back(c);
         }
         if (st.new_frames > 0) ss.p_runs.push_back(new_row0), ss.p_runs.push_back(st.new_frames);
+        // the online normaliser's rows: the new frames' statics in the slot (frames T_old ..) ahead of the deltas, or the
+        // rows the push delivers (rows E_old ..) behind them; a fresh session has 0 rows in front and reads no state
+        if (onorm && before && st.new_frames > 0)
+            ss.p_onorm.push_back(OnormSessDesc{new_row0, std::max<int64_t>(frame_count(cur.n, h->W, h->S), 0), st.new_frames, ids[i]});
+        if (onorm && !before && st.n_out > 0) ss.p_onorm.push_back(OnormSessDesc{ss.p_row_of[i], cur.E, st.n_out, ids[i]});
         if (st.n_out > 0) {
             Segment s{};
             s.src_row0 = d.row_dst;
@@ -245,21 +287,23 @@ extern "C" int mfx_sessions_run_device(mfx_handle *h, const int16_t *d_pcm, int6
     const FrontKind kind = choose_front(h, aligned);
     FrontParams p;
     fill_front(h, p, aligned);
-    const bool compact = compact_statics(kind, p) && h->l1 > 0 && h->cols <= 16;
+    // (a normaliser before the deltas: the statics keep the row's pitch, as decide_mode of the batch runner has it)
+    const bool compact = compact_statics(kind, p) && h->l1 > 0 && h->cols <= 16 && !norm_before(h);
     const int pitch = compact ? 16 : h->width;
     if (is_spec_kind(kind) && ss.slab_rows == 0)
         return fail(h, MFX_ERR_STATE, "the warp factor moved this shape to the spectrum path: call mfx_sessions_create again");
 
-    const size_t nd = ss.p_descs.size(), ns = ss.p_segs.size(), nc = ss.p_chunks.size(), nr = ss.p_runs.size() / 2;
+    const size_t nd = ss.p_descs.size(), ns = ss.p_segs.size(), nc = ss.p_chunks.size(), nr = ss.p_runs.size() / 2, no = ss.p_onorm.size();
     if (nd > 0) {
         int items_max = 0;
         for (SessDesc &d : ss.p_descs) {
             if (d.src_pitch <= 0) d.src_pitch = pitch;
             items_max = std::max(items_max, sess_gather_items(d, pitch, h->cols));
         }
-        // ---- one upload: descriptors | segments | chunks | row runs | run offsets
+        // ---- one upload: descriptors | segments | chunks | row runs | run offsets | the normaliser's descriptors
         const size_t o_seg = nd * sizeof(SessDesc), o_chunk = o_seg + ns * sizeof(Segment), o_run = o_chunk + nc * sizeof(Chunk),
-                     o_off = o_run + nr * 2 * sizeof(int64_t), bytes = o_off + 2 * sizeof(int32_t);
+                     o_off = o_run + nr * 2 * sizeof(int64_t), o_on = o_off + 2 * sizeof(int32_t), bytes = o_on + no * sizeof(OnormSessDesc);
+        static_assert(sizeof(SessDesc) % 8 == 0 && sizeof(Segment) % 8 == 0 && sizeof(Chunk) % 8 == 0, "8-byte parts");
         if (bytes > ss.desc_bytes) return fail(h, MFX_ERR_STATE, "session descriptors outgrew their buffer");
         const int b = ss.stage_cur;
         if (ss.stage_used[b]) HIP_TRY(h, hipEventSynchronize(ss.ev_stage[b])); // (the upload before last read this buffer)
@@ -270,6 +314,7 @@ extern "C" int mfx_sessions_run_device(mfx_handle *h, const int16_t *d_pcm, int6
         if (nr) std::memcpy(st + o_run, ss.p_runs.data(), nr * 2 * sizeof(int64_t));
         const int32_t h_off[2] = {0, (int32_t)nr};
         std::memcpy(st + o_off, h_off, sizeof(h_off));
+        if (no) std::memcpy(st + o_on, ss.p_onorm.data(), no * sizeof(OnormSessDesc));
         HIP_TRY(h, hipMemcpyAsync(ss.d_desc.p, st, bytes, hipMemcpyHostToDevice, h->stream));
         HIP_TRY(h, hipEventRecord(ss.ev_stage[b], h->stream));
         ss.stage_used[b] = true;
@@ -311,6 +356,21 @@ extern "C" int mfx_sessions_run_device(mfx_handle *h, const int16_t *d_pcm, int6
             if (rc != MFX_OK) return rc;
         }
 
+        // ---- online normaliser: ahead of the deltas on the new frames' statics in the slots, behind them on the delivered rows
+        OnormSessParams op{};
+        op.Wn = spk_wn(h);
+        op.window = ss.on.window, op.cvn = h->cfg.norm == MFX_NORM_CVN ? 1 : 0, op.prior_frames = ss.on.prior_frames;
+        op.prior_count = ss.on.prior_count;
+        op.prior_acc = ss.on.d_prior.p;
+        op.descs = (const OnormSessDesc *)(ss.d_desc.p + o_on);
+        op.n_descs = (int32_t)no;
+        op.state = ss.on.d_state.p;
+        op.ring = ss.on.d_ring.p;
+        if (no > 0 && norm_before(h)) {
+            op.data = ss.d_stat.p, op.pitch = pitch;
+            HIP_TRY(h, launch_onorm_sess(op, h->stream));
+        }
+
         // ---- delta: the rows every session's push completes, into the caller's array (l1 == 0: the copy form)
         if (ns > 0) {
             DeltaParams dp{};
@@ -325,6 +385,10 @@ extern "C" int mfx_sessions_run_device(mfx_handle *h, const int16_t *d_pcm, int6
             dp.l2 = h->l2;
             dp.tiles_per_seg_max = ss.p_tiles_max;
             HIP_TRY(h, launch_delta(dp, h->stream));
+        }
+        if (no > 0 && !norm_before(h)) {
+            op.data = d_out, op.pitch = h->width;
+            HIP_TRY(h, launch_onorm_sess(op, h->stream));
         }
     }
     // ---- the launches are queued: commit

@@ -717,4 +717,73 @@ int64_t resample_layout(int32_t n_utt, const int64_t *lengths, const int32_t *ra
     return off;
 }
 
+// The online normaliser's definition (include/mfx.h, mfx_batch_set_online_norm) on host memory: per column the chunked
+// prefix sums P of v and of q, then every row's window, prior, statistics and float32 apply.  Every double operation is
+// a statement of its own and this file is compiled with -ffp-contract=off.
+bool host_online_norm(const float *rows, int64_t T, int pitch, int Wn, int kind, int window, int prior_frames, int64_t prior_count,
+                      const double *prior_acc, float *out)
+{
+    if (T < 0 || Wn < 1 || Wn > 256 || pitch < Wn || (kind != 1 && kind != 2)) return false;
+    if (window < 0 || window > 4096 || window % 32 != 0 || prior_frames < 0 || prior_frames > (1 << 20) || prior_count < 0) return false;
+    if ((prior_acc == nullptr) != (prior_count == 0) || (T > 0 && (!rows || !out))) return false;
+    std::vector<double> Pv((size_t)T), Pq((size_t)T);
+    for (int j = 0; j < Wn; ++j) {
+        double Ov = 0.0, Oq = 0.0, Iv = 0.0, Iq = 0.0;
+        for (int64_t t = 0; t < T; ++t) {
+            const float v = rows[t * pitch + j];
+            const float q = v * v;
+            Iv = Iv + (double)v;
+            Iq = Iq + (double)q;
+            Pv[(size_t)t] = Ov + Iv;
+            Pq[(size_t)t] = Oq + Iq;
+            if (t % 32 == 31) { // the chunk's last row: Tot = I
+                Ov = Ov + Iv;
+                Oq = Oq + Iq;
+                Iv = 0.0, Iq = 0.0;
+            }
+        }
+        for (int64_t t = 0; t < T; ++t) {
+            const float v = rows[t * pitch + j];
+            double Sw = Pv[(size_t)t], Qw = Pq[(size_t)t];
+            int64_t n = t + 1;
+            if (window > 0 && t >= window) {
+                Sw = Sw - Pv[(size_t)(t - window)];
+                Qw = Qw - Pq[(size_t)(t - window)];
+                n = window;
+            }
+            int64_t k = 0;
+            if (prior_count > 0 && (int64_t)prior_frames > n) k = std::min<int64_t>(prior_count, (int64_t)prior_frames - n);
+            if (k > 0) {
+                const double r = (double)k / (double)prior_count;
+                const double a = prior_acc[j] * r, b = prior_acc[Wn + j] * r;
+                Sw = Sw + a;
+                Qw = Qw + b;
+            }
+            const double nn = (double)(n + k);
+            const double m = Sw / nn;
+            const float mean = (float)m;
+            float y = v - mean;
+            if (kind == 2) {
+                const double sm = Sw * m;
+                const double d = Qw - sm;
+                float mult = 1.0f;
+                if (nn >= 2.0 && d > 0.0) {
+                    const double ratio = (nn - 1.0) / d;
+                    mult = (float)std::sqrt(ratio);
+                }
+                y = y * mult;
+            }
+            out[t * Wn + j] = y;
+        }
+    }
+    return true;
+}
+
 } // namespace mfx
+
+// (the C entry of include/mfx.h, here beside its definition so that the stand-alone sanitizer program links it without HIP)
+extern "C" int mfx_host_online_norm(const float *rows, int64_t T, int32_t pitch, int32_t Wn, int32_t kind, int32_t window,
+                                    int32_t prior_frames, int64_t prior_count, const double *prior_acc, float *out)
+{
+    return mfx::host_online_norm(rows, T, pitch, Wn, kind, window, prior_frames, prior_count, prior_acc, out) ? 0 : -7 /* MFX_ERR_ARG */;
+}

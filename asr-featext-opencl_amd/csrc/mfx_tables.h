@@ -95,6 +95,11 @@ void clip_alpha_runs(int64_t row0, int64_t rows, std::vector<int32_t> &off, std:
 bool build_speaker_lists(const int32_t *utt_spk, const int64_t *frames, int n_utt, int n_spk, std::vector<int32_t> &off,
                          std::vector<int32_t> &list);
 
+// The online normaliser (mfx_batch_set_online_norm) on host memory, exactly as include/mfx.h defines it: rows [T][pitch],
+// columns [0, Wn) -> out [T][Wn].  kind: 1 CMN, 2 CVN.  False -- and nothing written -- on an argument outside the limits.
+bool host_online_norm(const float *rows, int64_t T, int pitch, int Wn, int kind, int window, int prior_frames, int64_t prior_count,
+                      const double *prior_acc, float *out);
+
 // Tiles and chunks of the VAD stage (mfx_batch_set_vad): utterance u of frames[u] rows is cut into tiles of 64 rows and into
 // chunks of 4096 rows (kNormChunkRows), numbered through the batch in utterance order.  False -- and nothing written -- on a
 // negative count or a batch whose tiles do not fit an int32.

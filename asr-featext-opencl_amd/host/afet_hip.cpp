@@ -53,6 +53,8 @@ struct Options {
     float alpha_min = 1.f, alpha_max = 1.f, alpha_step = 1.f;
     std::string alpha_file;        // --alpha-file: one warp factor per line, in the order of the input list
     std::vector<float> file_alpha; // its factors: file i of the list is extracted with file_alpha[i]
+    int online_window = -1;        // --online-window: online (causal) CMN / CVN of the batches, window in frames (0: cumulative)
+    int online_prior_frames = 0;   // --online-prior-frames
     std::string spk_file;          // --spk-file: one speaker label per line, in the order of the input list
     std::vector<int> file_spk;     // its labels as ids, numbered by first appearance: file i belongs to speaker file_spk[i]
     int n_spk = 0;
@@ -868,6 +870,8 @@ void worker(const Options &o, int device, float sr, const std::vector<std::strin
                         for (const BatchItem *it : in_batch) al.push_back(o.file_alpha[it->file]);
                         param.batch_set_alphas(al.data(), (int)al.size());
                     }
+                    if (o.online_window >= 0) // --online-window: every file normalised causally, as a live stream would be
+                        param.batch_set_online_norm(o.online_window, o.online_prior_frames);
                     if (o.vad)
                         param.batch_set_vad(o.vad_column, o.vad_energy_threshold, o.vad_energy_mean_scale, o.vad_frames_context,
                                             o.vad_proportion_threshold, MFX_VAD_SELECT);
@@ -881,6 +885,7 @@ void worker(const Options &o, int device, float sr, const std::vector<std::strin
                         if (it.frames != param.batch_frames(it.conv_len)) throw std::runtime_error("frame count mismatch");
                         it.out_frames = o.vad ? voiced[k] : it.frames;
                         if (o.vad) continue; // (selected rows have no reference analogue: nothing of B1 to reproduce on them)
+                        if (o.online_window >= 0) continue; // (nor have causally normalised rows)
                         // The reference's flush after exactly one set_input reads its D static rows D rows early (B1,
                         // mfcccpu.cpp:439 + segmentercpu.cpp:97-106): rows T - D .. T - 1 repeat the statics of rows
                         // T - 2 D .. T - D - 1 (deltas unaffected).  The batch entries deliver the correct rows; the
@@ -897,6 +902,10 @@ void worker(const Options &o, int device, float sr, const std::vector<std::strin
                 for (BatchItem &it : b.items)
                     if (it.error.empty() && it.stream) {
                         try {
+                            if (o.online_window >= 0)
+                                throw std::runtime_error("--online-window: \"" + files[2 * it.file] +
+                                                         "\" would take the per-file loop (longer than one block, too short for the "
+                                                         "deltas, or an alpha sweep): the online normaliser runs in batches of whole files only");
                             if (o.vad)
                                 throw std::runtime_error("--vad: \"" + files[2 * it.file] +
                                                          "\" would take the per-file loop (longer than one block, too short for the "
@@ -986,6 +995,8 @@ int main(int argc, char **argv)
         else if (a == "--alpha-step") o.alpha_step = (float)std::atof(val());
         else if (a == "--alpha-file") o.alpha_file = val();
         else if (a == "--spk-file") o.spk_file = val();
+        else if (a == "--online-window") o.online_window = std::atoi(val());
+        else if (a == "--online-prior-frames") o.online_prior_frames = std::atoi(val());
         else if (a == "--selftest-spk-labels") { // the label -> id mapping of --spk-file, on a file of labels: prints the ids
             FILE *fl = std::fopen(val(), "r");
             if (!fl) {
@@ -1077,6 +1088,11 @@ int main(int argc, char **argv)
                         "                their own factors in one launch sequence\n"
                         "  --spk-file: one speaker label per line, in the order of the input files (needs --norm 1..3, batches, one\n"
                         "                device): CMN / CVN / MINMAX statistics pooled over each speaker's files, in two passes\n"
+                        "         [--online-window n [--online-prior-frames f]]\n"
+                        "  --online-window: online (causal) CMN / CVN (needs --norm 1|2, batches; excludes --spk-file): every row is\n"
+                        "                normalised with the last n rows of its file, itself included (0: all rows so far; else a\n"
+                        "                multiple of 32 up to 4096).  --online-prior-frames is handed on for a prior, of which the\n"
+                        "                driver has none to give: it changes nothing yet\n"
                         "         [--resample-to hz [--resample-zeros n]]\n"
                         "  --resample-to: extract at hz instead of the first file's rate; files at other rates are converted on the\n"
                         "                device (Hann-windowed sinc, n zero crossings per side, default 6)\n"
@@ -1124,6 +1140,28 @@ int main(int argc, char **argv)
     if (o.vad && o.batch_mb <= 0) {
         std::fprintf(stderr, "--vad selects frames in batches of whole files: --batch-mb must be positive\n");
         return 2;
+    }
+    if (o.online_window != -1 || o.online_prior_frames != 0) {
+        if (o.online_window < 0 || o.online_window > 4096 || o.online_window % 32 != 0) {
+            std::fprintf(stderr, "--online-window must be 0 or a multiple of 32 up to 4096 (--online-prior-frames needs it)\n");
+            return 2;
+        }
+        if (o.online_prior_frames < 0 || o.online_prior_frames > (1 << 20)) {
+            std::fprintf(stderr, "--online-prior-frames must be 0 .. 1048576\n");
+            return 2;
+        }
+        if (o.norm != 1 && o.norm != 2) {
+            std::fprintf(stderr, "--online-window is an online CMN / CVN: it needs --norm 1 or 2\n");
+            return 2;
+        }
+        if (o.batch_mb <= 0) {
+            std::fprintf(stderr, "--online-window runs in batches of whole files: --batch-mb must be positive\n");
+            return 2;
+        }
+        if (!o.spk_file.empty()) {
+            std::fprintf(stderr, "--online-window and --spk-file exclude each other: one normaliser per run\n");
+            return 2;
+        }
     }
     if (!o.spk_file.empty()) {
         if (o.norm < 1 || o.norm > 3) {

@@ -121,6 +121,9 @@ public:
                             const double *prior_acc = nullptr, bool prior_only = false);
     // what the last run used: count [n_spk], acc [n_spk][4][Wn] (S, S2, min, max), stats [n_spk][2][Wn]; any may be null
     void batch_speaker_stats(long long *count, double *acc, float *stats);
+    // online (causal, sliding-window) CMN / CVN of the planned batch (mfx_batch_set_online_norm): window in frames (0:
+    // cumulative), the prior's reach and its accumulators [2][Wn] (nullptr with count 0: none); the next batch_plan clears it
+    void batch_set_online_norm(int window, int prior_frames, long long prior_count = 0, const double *prior_acc = nullptr);
     // energy VAD + voiced-frame selection as the last stage of the planned batch's runs (mfx_batch_set_vad; mode MFX_VAD_*);
     // the next batch_plan clears it, and so does batch_clear_vad
     void batch_set_vad(int column, float energy_threshold, float energy_mean_scale, int frames_context, float proportion_threshold,

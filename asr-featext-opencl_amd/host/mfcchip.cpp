@@ -204,6 +204,11 @@ void MfccHip::batch_speaker_stats(long long *count, double *acc, float *stats)
     check(mfx_batch_speaker_stats(m_handle, (int64_t *)count, acc, stats));
 }
 
+void MfccHip::batch_set_online_norm(int window, int prior_frames, long long prior_count, const double *prior_acc)
+{
+    check(mfx_batch_set_online_norm(m_handle, window, prior_frames, (int64_t)prior_count, prior_acc));
+}
+
 void MfccHip::batch_set_vad(int column, float energy_threshold, float energy_mean_scale, int frames_context, float proportion_threshold,
                             int mode)
 {

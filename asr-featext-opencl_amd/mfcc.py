@@ -78,6 +78,8 @@ EXPORTED_SYMBOLS = (
     "mfx_host_resample_layout", "mfx_host_resample_tile",
     "mfx_batch_set_speakers", "mfx_batch_speaker_stats", "mfx_host_speaker_lists",
     "mfx_batch_set_vad", "mfx_batch_clear_vad", "mfx_batch_vad_read", "mfx_batch_vad_device",
+    "mfx_batch_set_online_norm", "mfx_batch_clear_online_norm", "mfx_sessions_set_online_norm",
+    "mfx_sessions_clear_online_norm", "mfx_host_online_norm",
 )
 
 
@@ -177,6 +179,11 @@ def load_library():
     L.mfx_batch_clear_vad.argtypes = [vp]
     L.mfx_batch_vad_read.argtypes = [vp, C.POINTER(C.c_uint8), p32, fp, p64]
     L.mfx_batch_vad_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.mfx_batch_set_online_norm.argtypes = [vp, i32, i32, i64, dp]
+    L.mfx_batch_clear_online_norm.argtypes = [vp]
+    L.mfx_sessions_set_online_norm.argtypes = [vp, i32, i32, i64, dp]
+    L.mfx_sessions_clear_online_norm.argtypes = [vp]
+    L.mfx_host_online_norm.argtypes = [fp, i64, i32, i32, i32, i32, i32, i64, dp, fp]
     _lib = L
     return L
 
@@ -319,6 +326,27 @@ def host_speaker_lists(utt_spk, frames, n_spk=None):
     if n < 0:
         raise MfxError(int(n), "mfx_host_speaker_lists failed")
     return off, lst[:int(n)].copy()
+
+
+def host_online_norm(rows, kind, window=0, prior_frames=0, prior_count=0, prior_acc=None, wn=None):
+    """The online normaliser of batch_set_online_norm on host memory, exactly as include/mfx.h defines it (host code, no GPU
+    needed): rows [T][pitch] float32, the first wn columns (None: all) -> [T][wn].  kind: 1 CMN, 2 CVN; prior_acc [2][wn]."""
+    L = load_library()
+    x = np.ascontiguousarray(rows, dtype=np.float32)
+    if x.ndim != 2:
+        raise ValueError("rows must be [T][pitch]")
+    T, pitch = x.shape
+    wn = pitch if wn is None else int(wn)
+    pa = None if prior_acc is None else np.ascontiguousarray(prior_acc, dtype=np.float64)
+    if pa is not None and pa.size != 2 * wn:
+        raise ValueError("prior_acc must be [2][wn]")
+    out = np.zeros((T, max(wn, 0)), np.float32)
+    fpt = C.POINTER(C.c_float)
+    rc = L.mfx_host_online_norm(x.ctypes.data_as(fpt), T, pitch, wn, int(kind), int(window), int(prior_frames), int(prior_count),
+                                None if pa is None else pa.ctypes.data_as(C.POINTER(C.c_double)), out.ctypes.data_as(fpt))
+    if rc != 0:
+        raise MfxError(int(rc), "mfx_host_online_norm failed")
+    return out
 
 
 def host_xform_operands(A):
@@ -746,6 +774,37 @@ class MfccHip:
         return count, acc, stats
 
     host_speaker_lists = staticmethod(host_speaker_lists)
+
+    def _online_args(self, window, prior_frames, prior):
+        pc, pa = 0, None
+        if prior is not None:
+            pc = int(prior[0])
+            pa = np.ascontiguousarray(prior[1], dtype=np.float64)
+            if pa.size != 2 * self.norm_width():
+                raise ValueError("prior must be (count, acc [2][Wn])")
+        return (int(window), int(prior_frames), pc, None if pa is None else pa.ctypes.data_as(C.POINTER(C.c_double))), pa
+
+    def batch_set_online_norm(self, window=0, prior_frames=0, prior=None):
+        """Online (causal) CMN / CVN of the planned batch (mfx_batch_set_online_norm): every row is normalised with the
+        statistics of the last `window` rows of its utterance, itself included (0: of all rows so far; else a multiple of 32
+        up to 4096), smoothed with up to prior_frames frames of prior = (count, acc [2][Wn] = sum, sum of squares).  A later
+        batch_plan clears it."""
+        args, keep = self._online_args(window, prior_frames, prior)
+        self._chk(self._L.mfx_batch_set_online_norm(self._h, *args))
+
+    def batch_clear_online_norm(self):
+        self._chk(self._L.mfx_batch_clear_online_norm(self._h))
+
+    def sessions_set_online_norm(self, window=0, prior_frames=0, prior=None):
+        """The same normaliser on the session entries (mfx_sessions_set_online_norm): call it before sessions_create; every
+        push then delivers the bits a batch run with batch_set_online_norm of the same parameters gives the whole stream."""
+        args, keep = self._online_args(window, prior_frames, prior)
+        self._chk(self._L.mfx_sessions_set_online_norm(self._h, *args))
+
+    def sessions_clear_online_norm(self):
+        self._chk(self._L.mfx_sessions_clear_online_norm(self._h))
+
+    host_online_norm = staticmethod(host_online_norm)
 
     def batch_set_vad(self, column=-1, energy_threshold=5.0, energy_mean_scale=0.5, frames_context=0,
                       proportion_threshold=0.6, mode=VAD_FLAGS):

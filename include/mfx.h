@@ -307,13 +307,67 @@ int mfx_batch_output_width(const mfx_handle *h);
  *     batch's prior gives the same bits as one batch holding both, provided each speaker's utterances keep their order;
  *     summing the accumulators of several devices on the host (sharding.merge_speaker_acc) and running MFX_SPK_PRIOR_ONLY
  *     is the multi-GPU flow.
- * The session entries and the streaming interface are untouched and ignore the list. */
+ * The session entries and the streaming interface are untouched and ignore the list.  While the online normaliser
+ * (mfx_batch_set_online_norm, below) is in force the setter answers MFX_ERR_STATE. */
 enum { MFX_SPK_POOL = 0, MFX_SPK_PRIOR_ONLY = 1 };
 int mfx_batch_set_speakers(mfx_handle *h, const int32_t *utt_spk, int32_t n_utt, int32_t n_spk,
                            const int64_t *prior_count, /* [n_spk] or NULL */
                            const double *prior_acc,    /* [n_spk][4][Wn]: S, S2, min, max; or NULL */
                            int32_t mode);
 int mfx_batch_speaker_stats(mfx_handle *h, int64_t *count, double *acc, float *stats /* [n_spk][2][Wn] mean, multiplier */);
+
+/* Online CMN / CVN: a causal sliding-window (or cumulative) normaliser, per stream, for the batch entries and the session
+ * entries ("Online normalisation") -- apply-cmvn-online of a Kaldi-style recipe: training features made to match
+ * what a live recogniser's normaliser delivers, and that normaliser itself on the session entries.  No reference analogue:
+ * its NormalizerCPU keeps one block's statistics (normalizercpu.cpp:22-27).  It needs no look-ahead, so the sessions' E does
+ * not change.  A stream is one utterance of a batch or one session.
+ *   Inputs.  Rows v[t][j], t = 0, 1, ..., j < Wn; Wn as for the speaker list (mfx_get_output_data_width when norm_after_dyn,
+ *     else the static column count), Wn <= 256 (MFX_ERR_CONFIG beyond).  The rows are what the handle's norm = NONE twin
+ *     delivers at the normaliser's place in the run: before or after the deltas, as norm_after_dyn says.
+ *     q[t][j] = (double)(v * v), the product rounded to float32 first (k_norm_stats' rule).
+ *   Parameters.  window N: 0 (cumulative: statistics from the start of the stream) or a multiple of 32 in 32 .. 4096 (the
+ *     last N rows, row t included).  prior_frames F in 0 .. 2^20.  prior_count p >= 0.  prior_acc [2][Wn] doubles (sum, sum
+ *     of squares), NULL exactly when p = 0.  The kind is mfx_config.norm: MFX_NORM_CMN or MFX_NORM_CVN; MFX_NORM_MINMAX and
+ *     MFX_NORM_NONE are refused with MFX_ERR_CONFIG.  Anything else outside these limits: MFX_ERR_ARG.
+ *   Prefix sums, per column, in chunks of 32 rows counted from the stream's first row (the same chains run on q):
+ *     inside chunk c, I = 0, then for each row ascending I = I + (double)v[r]; I[t] is the value after row t; Tot[c] is I at
+ *     the chunk's last row; across chunks O[0] = 0, O[c + 1] = O[c] + Tot[c]; P[t] = O[t div 32] + I[t].
+ *   Window.  n = t + 1 and Sw = P[t] when N = 0 or t < N; else n = N and Sw = P[t] - P[t - N] (N is a multiple of 32: the
+ *     trailing row sits at the same place in its chunk as row t).  Qw likewise from the q chains.
+ *   Prior (Kaldi's global-stats smoothing).  k = min(p, F - n) when p > 0 and F > n, else 0.  If k > 0: r = (double)k /
+ *     (double)p, Sw = Sw + PS[j] * r, Qw = Qw + PQ[j] * r (product and sum rounded separately).  nn = (double)(n + k).
+ *   Statistics and apply.  m = Sw / nn, mean = (float)m.  CVN: d = Qw - Sw * m; mult = (float)sqrt((nn - 1) / d) when nn >= 2
+ *     and d > 0, else 1.0f.  y = v - mean (CMN), y = (v - mean) * mult (CVN), in float32.  Every double operation above is
+ *     rounded on its own (no fused multiply-add), so the rows are an exact function of v and the parameters: they do not
+ *     depend on the other streams, on buffer placement, on the run, or -- for a session -- on how the stream is cut.
+ *   Batch.  mfx_batch_set_online_norm is valid after mfx_batch_plan / mfx_batch_plan_rates (MFX_ERR_STATE before one); a
+ *     later plan drops it with the other attachments; mfx_batch_clear_online_norm puts the handle back on the per-utterance
+ *     normaliser's kernels and bits.  MFX_ERR_STATE while a speaker list is in force, and mfx_batch_set_speakers answers
+ *     MFX_ERR_STATE while this attachment is.  MFX_ERR_DEVICE on a planning handle.  mfx_config.batch_norm_stats is ignored
+ *     and mfx_debug_read kind 6 returns 0 elements.  Everything is allocated HERE (the call waits for the handle's streams):
+ *     16 bytes per 32-row chunk and column of totals / offsets, and a handle-owned scratch [total_rows][width] (grown, never
+ *     shrunk) that everything ahead of the normaliser's place writes instead of the run's rows -- the normaliser does not
+ *     run in place, its trailing edge reads raw rows; mfx_batch_run_device still allocates nothing.  Everything else in a
+ *     run is unchanged: front end, MFX_ENGINE_* bits, alpha list, rates plan, mfx_batch_overlap, the transform and the VAD
+ *     (which read the normalised rows).  Utterances are independent: mfx_batch_run_host keeps its sliced path.
+ *   Sessions.  mfx_sessions_set_online_norm stores the parameters and allocates nothing; it and
+ *     mfx_sessions_clear_online_norm are valid only while no sessions exist (before mfx_sessions_create, or after
+ *     mfx_sessions_create(h, 0, 0)), else MFX_ERR_STATE.  mfx_sessions_create on a CMN / CVN handle succeeds only with the
+ *     parameters set, and then sizes the state: 8 doubles per session and column (lead and trail O and I of v and q), and
+ *     when N > 0 a ring of the last N raw rows, n_sessions * N * Wn * 4 bytes (MFX_ERR_DEVICE when that cannot be
+ *     allocated).  Every push then runs ONE more launch, k_onorm_sess: behind the deltas on the rows [E_old, E_new) it
+ *     delivers, or ahead of them on the new frames' static rows in the slot (carried static rows are already normalised).
+ *     A push may deliver more rows than N.  A final push or mfx_sessions_reset leaves the session fresh.  The rows of a
+ *     push are THE SAME BITS that mfx_batch_run_device writes for the whole utterance on a handle of the same
+ *     configuration with mfx_batch_set_online_norm of the same parameters.
+ * One prior serves all streams.  NOT served: MINMAX, TRAPS handles on the session entries, the streaming interface
+ * (mfx_set_input / mfx_apply), which is untouched. */
+int mfx_batch_set_online_norm(mfx_handle *h, int32_t window, int32_t prior_frames, int64_t prior_count,
+                              const double *prior_acc /* [2][Wn] or NULL */);
+int mfx_batch_clear_online_norm(mfx_handle *h);
+int mfx_sessions_set_online_norm(mfx_handle *h, int32_t window, int32_t prior_frames, int64_t prior_count,
+                                 const double *prior_acc /* [2][Wn] or NULL */);
+int mfx_sessions_clear_online_norm(mfx_handle *h);
 
 /* Energy voice-activity decision and voiced-frame selection as the last stage of a batch run ("Voice activity and
  * frame selection"): compute-vad-energy followed by select-voiced-frames of a Kaldi-style recipe, on the device, behind
@@ -449,7 +503,8 @@ int mfx_batch_run_host(mfx_handle *h, const int16_t *pcm, int64_t pcm_samples_to
  * Errors: MFX_ERR_ARG an id outside the range or twice in one push, a negative length or offset, a piece past
  * pcm_samples_total, a misaligned d_pcm (the 4-byte rule of mfx_batch_run_device); MFX_ERR_BUFFER_TOO_SMALL lengths[i] >
  * max_push_samples; MFX_ERR_STATE no mfx_set_window yet, no mfx_sessions_create yet, a TRAPS handle, a handle with norm !=
- * MFX_NORM_NONE (the session entries do not serve them); MFX_ERR_DEVICE a planning handle.
+ * MFX_NORM_NONE without mfx_sessions_set_online_norm (the one normaliser the session entries serve is the online CMN / CVN
+ * above; MINMAX never); MFX_ERR_DEVICE a planning handle.
  * The handle's mfx_set_alpha factor applies to all sessions.  NOT applied to session runs: mfx_batch_set_alphas,
  * mfx_batch_set_transform, mfx_batch_overlap, MFX_ENGINE_FUSE_DELTA.  A push leaves the batch plan (with its alpha list and
  * transform) and the streaming state of the same handle untouched, and they leave the sessions untouched. */
@@ -550,6 +605,11 @@ int64_t mfx_host_resampled_length(int64_t samples, int32_t in_hz, int32_t out_hz
 int64_t mfx_host_resample_layout(int32_t n_utt, const int64_t *lengths, const int32_t *rates_hz, int32_t out_hz, int64_t *offsets,
                                  int64_t *out_lengths);
 int32_t mfx_host_resample_tile(int32_t in_hz, int32_t out_hz, int32_t zeros, float rolloff, int32_t channels);
+/* The online normaliser (mfx_batch_set_online_norm) on host memory, exactly as defined there: rows [T][pitch], columns
+ * [0, Wn) -> out [T][Wn].  kind: MFX_NORM_CMN or MFX_NORM_CVN.  MFX_ERR_ARG on anything outside the limits (nothing is
+ * written then).  Test / inspection aid. */
+int mfx_host_online_norm(const float *rows, int64_t T, int32_t pitch, int32_t Wn, int32_t kind, int32_t window,
+                         int32_t prior_frames, int64_t prior_count, const double *prior_acc, float *out);
 /* frame count, integer arithmetic (parambase.cpp:16-19 without the float32 division) */
 int64_t mfx_host_frame_count(int64_t samples, int32_t window_size, int32_t shift);
 
