@@ -111,6 +111,43 @@ __device__ __forceinline__ void pcm_issue_stuffed(PcmRegs<true, NM> &r, __amdgpu
     for (int m = 0; m < NM; ++m) r.d[m] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b16(rsrc, voff, row_bytes * m, 0);
 }
 
+// One batch of the mel walk: NB bins (8 or 16) of a round, every read issued before the first multiply -- the weights as
+// 16-byte words, the magnitudes as 8-byte words that stay apart (lds_read_b64), all at immediate offsets from the batch's two
+// addresses -- so that a batch is ONE dependent LDS round trip whatever its size.  (The barrier: left alone the scheduler
+// keeps three magnitude reads in flight and issues the rest between the multiplies.)  The products are added to the one
+// accumulator in ascending bin order (mfcccpu.cpp:192-220): the same chain of multiply-adds as 8 bins at a time.
+template <int NB>
+__device__ __forceinline__ float mel_batch(float acc, const float *w, const float *m)
+{
+    float4 wq[NB / 4];
+    float2 mm[NB / 2];
+#pragma unroll
+    for (int q = 0; q < NB / 4; ++q) wq[q] = *(const float4 *)(w + 4 * q);
+#pragma unroll
+    for (int q = 0; q < NB / 2; ++q) mm[q] = lds_read_b64((const float2 *)(m + 2 * q));
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int q = 0; q < NB / 4; ++q) {
+        acc += wq[q].x * mm[2 * q].x;
+        acc += wq[q].y * mm[2 * q].y;
+        acc += wq[q].z * mm[2 * q + 1].x;
+        acc += wq[q].w * mm[2 * q + 1].y;
+    }
+    return acc;
+}
+
+// One round of the walk (L bins, a multiple of 8): 16 bins at a time, then the 8-bin remainder.  The 32 registers of a
+// 16-bin batch are free in the walk (the frame loop needs its 128 in pass A only); 32-bin batches spill
+// (profiles/r05/abx_c2_mel_round_batches.txt).  L is uniform: scalar branches.
+__device__ __forceinline__ float mel_round(const float *w, const float *m, int L)
+{
+    float acc = 0.f;
+    int s = 0;
+    for (; s + 16 <= L; s += 16) acc = mel_batch<16>(acc, w + s, m + s);
+    if (s < L) acc = mel_batch<8>(acc, w + s, m + s);
+    return acc;
+}
+
 // Dev-only in-kernel stamps (-DMFX_STAMPS): per-wave cycle sums per phase, written by lane 0 to
 // p.spec (which is unused by the fused path).  Never part of a timed build.
 #ifdef MFX_STAMPS
@@ -560,22 +597,7 @@ __global__ void __launch_bounds__(kThreads, 4) k_front512(FrontParams p) // (4 w
                         mmeta += 16;
                         const float *mg = mg0 + mt.x;
                         const int fid = mt.y;
-                        float acc = 0.f;
-                        for (int s = 0; s < L; s += 8) {
-                            float4 w[2];
-                            float2 mm[4];
-#pragma unroll
-                            for (int q = 0; q < 2; ++q) w[q] = *(const float4 *)(wrow + s + 4 * q);
-#pragma unroll
-                            for (int q = 0; q < 4; ++q) mm[q] = lds_read_b64((const float2 *)(mg + s + 2 * q));
-#pragma unroll
-                            for (int q = 0; q < 2; ++q) {
-                                acc += w[q].x * mm[2 * q].x;
-                                acc += w[q].y * mm[2 * q].y;
-                                acc += w[q].z * mm[2 * q + 1].x;
-                                acc += w[q].w * mm[2 * q + 1].y;
-                            }
-                        }
+                        const float acc = mel_round(wrow, mg, L);
                         wrow += L;
                         lm[fid] = MFX_LOG(fmaxf(acc, 1e-30f)); // (idle lanes: fid names a word nobody reads)
                     }
@@ -634,16 +656,7 @@ __global__ void __launch_bounds__(kThreads, 4) k_front512(FrontParams p) // (4 w
                         mmeta += 16;
                         const float *mg = mg0 + mt.x;
                         const int fid = mt.y;
-                        float acc = 0.f;
-                        for (int s = 0; s < L; s += 4) {
-                            const float4 w = *(const float4 *)(wrow + s);
-                            const float2 m0 = *(const float2 *)(mg + s);
-                            const float2 m1 = *(const float2 *)(mg + s + 2);
-                            acc += w.x * m0.x;
-                            acc += w.y * m0.y;
-                            acc += w.z * m1.x;
-                            acc += w.w * m1.y;
-                        }
+                        const float acc = mel_round(wrow, mg, L);
                         wrow += L;
                         if (fid >= 0) melbuf[fid] = MFX_LOG(fmaxf(acc, 1e-30f));
                     }

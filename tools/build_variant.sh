@@ -8,7 +8,7 @@ NAME=$1; DEFS=${2:-}; REV=${3:-}
 C=$R/asr-featext-opencl_amd/csrc
 T=/tmp/var_$NAME
 rm -rf $T; mkdir -p $R/build/var $T
-TUS="mfx_front512 mfx_front_generic mfx_front2048 mfx_tail"
+TUS=$(cd $C && ls *.hip | sed 's/\.hip$//')   # every kernel translation unit: the library links them all
 SRCDIR=$C
 if [ -n "$REV" ]; then
   for f in $(git -C $R ls-tree --name-only $REV asr-featext-opencl_amd/csrc/ | grep -E '\.(hip|h)$'); do git -C $R show $REV:$f > $T/$(basename $f); done
