@@ -31,28 +31,12 @@
 
 #include <hip/hip_runtime.h>
 
-#include "mfx_dev.h"
+#include "mfx_front_dev.h"
 #include "mfx_launch.h"
 
 namespace mfx {
 
 namespace {
-
-// Dev-only in-kernel stamps (-DMFX_STAMPS): per-wave cycle sums per phase, written by lane 0 to p.spec (unused by the
-// fused path); tools/stamps2048.py reads them.  Never part of a timed build.
-#ifdef MFX_STAMPS
-#define MFX_STAMP2(i)                                                                  \
-    do {                                                                               \
-        unsigned long long t_;                                                         \
-        __builtin_amdgcn_sched_barrier(0);                                             \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");     \
-        __builtin_amdgcn_sched_barrier(0);                                             \
-        st_acc[i] += t_ - st_last;                                                     \
-        st_last = t_;                                                                  \
-    } while (0)
-#else
-#define MFX_STAMP2(i)
-#endif
 
 #ifndef MFX_W2048
 #define MFX_W2048 12
@@ -201,41 +185,9 @@ __global__ void __launch_bounds__(kW2048 * 64, (kW2048 + 3) / 4) k_front2048(Fro
     const bool lane0 = l == 0;
 
     // ---- chunk walk: block b owns chunks b, b + B, ...; its waves draw from that list through a counter in LDS
-    struct ChunkCtx {
-        int64_t out_row;
-        int n_live;
-        int odd0; // ANY: the chunk starts on an odd sample (its descriptor on the even one before)
-        __amdgpu_buffer_rsrc_t rsrc;
-    };
-    auto make_ctx = [&](int c) -> ChunkCtx {
-        ChunkCtx x;
-        const bool valid = c < p.n_chunks;
-        const Chunk *chp = p.chunks + (valid ? c : 0);
-        const int64_t pcm_off = chp->pcm_off;
-        x.out_row = chp->out_row;
-        const int n_frames = valid ? chp->n_frames : 0;
-        const int64_t rows_left = p.row_limit - x.out_row;
-        x.n_live = (int)(rows_left < n_frames ? (rows_left < 0 ? 0 : rows_left) : n_frames);
-        // buffer descriptor over [chunk start, end of PCM): out-of-range lanes read 0 (whole 32-bit words: see k_front512)
-        x.odd0 = ANY ? (int)(pcm_off & 1) : 0;
-        const int64_t el0 = STEREO ? pcm_off * 2 : ANY ? (pcm_off & ~(int64_t)1) : pcm_off;
-        int64_t bytes_left = valid ? (((p.pcm_total - el0) * 2 + 3) & ~(int64_t)3) : 0;
-        if (bytes_left > 0xfffffff0ll) bytes_left = 0xfffffff0ll;
-        if (bytes_left < 0) bytes_left = 0;
-        const uintptr_t bp = (uintptr_t)(p.pcm + el0);
-        const uint32_t bp_lo = __builtin_amdgcn_readfirstlane((uint32_t)bp);
-        const uint32_t bp_hi = __builtin_amdgcn_readfirstlane((uint32_t)(bp >> 32));
-        const uint32_t nbytes = __builtin_amdgcn_readfirstlane((uint32_t)bytes_left);
-        x.rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)(((uintptr_t)bp_hi << 32) | bp_lo), 0, nbytes, 0x00020000);
-        return x;
-    };
     const int block_id = xcd_block_id(); // (consecutive ids, i.e. consecutive chunks, on one XCD's L2)
     auto draw = [&]() -> int {
-        int k = 0;
-        if (lane == 0) k = __hip_atomic_fetch_add(s_ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        k = __builtin_amdgcn_readfirstlane(k);
-        const long long cc = (long long)block_id + (long long)k * gridDim.x;
-        return cc < p.n_chunks ? (int)cc : p.n_chunks;
+        return chunk_of_draw(block_id, __builtin_amdgcn_readfirstlane(draw_index(s_ctr, lane)), p.n_chunks);
     };
     // raw words of (frame f, this lane): sample pair n = l + 32 j at byte (f S + 2 n) * (STEREO ? 4 : 2)
     uint32_t raw[NWORD];
@@ -282,7 +234,7 @@ __global__ void __launch_bounds__(kW2048 * 64, (kW2048 + 3) / 4) k_front2048(Fro
     const __amdgpu_buffer_rsrc_t dct_rsrc =
         __builtin_amdgcn_make_buffer_rsrc((void *)(SPLIT ? p.dct_b4s : p.dct_b4), 0, dct_bytes, 0x00020000);
     int c_cur = draw(), c_nxt = draw();
-    ChunkCtx ccur = make_ctx(c_cur), cnxt = make_ctx(c_nxt);
+    ChunkCtx ccur = chunk_ctx<STEREO ? 2 : 1, ANY>(p, c_cur), cnxt = chunk_ctx<STEREO ? 2 : 1, ANY>(p, c_nxt);
     issue(ccur, half);
     while (c_cur < p.n_chunks) {
         const int64_t out_row = ccur.out_row;
@@ -290,10 +242,10 @@ __global__ void __launch_bounds__(kW2048 * 64, (kW2048 + 3) / 4) k_front2048(Fro
         for (int f0 = 0; f0 < n_live; f0 += 2) {
             const int f = f0 + half;
             const bool last = f0 + 2 >= n_live;
-            MFX_STAMP2(0);
+            MFX_STAMP(0);
 #ifdef MFX_STAMPS
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // (stamp builds only: the wait for the prefetched samples on its own)
-            MFX_STAMP2(12);
+            MFX_STAMP(12);
 #endif
             // ---- framing + window: z[n2] = (w[2n] x[2n], w[2n+1] x[2n+1]), n = l + 32 n2
             float2 z[32];
@@ -322,7 +274,7 @@ __global__ void __launch_bounds__(kW2048 * 64, (kW2048 + 3) / 4) k_front2048(Fro
                 const float2 w = s_win[l + 32 * j];
                 z[j] = make_float2(w.x * x0, w.y * x1);
             }
-            MFX_STAMP2(1);
+            MFX_STAMP(1);
             // ---- pass 1 + inter-pass twiddle
             fft32(z);
 #pragma unroll
@@ -338,7 +290,7 @@ __global__ void __launch_bounds__(kW2048 * 64, (kW2048 + 3) / 4) k_front2048(Fro
             }
             // ---- 32 x 32 transposition through the frame's plane: real parts, then imaginary parts.  The LDS executes a
             // wave's instructions in order, so the imaginary parts' writes need not wait for the real parts' reads.
-            MFX_STAMP2(2);
+            MFX_STAMP(2);
             float zr[32], zi[32];
 #pragma unroll
             for (int j = 0; j < 8; ++j)
@@ -357,10 +309,10 @@ __global__ void __launch_bounds__(kW2048 * 64, (kW2048 + 3) / 4) k_front2048(Fro
 #pragma unroll
             for (int n1 = 0; n1 < 32; ++n1) z[n1] = make_float2(zr[n1], zi[n1]);
 
-            MFX_STAMP2(3);
+            MFX_STAMP(3);
             // ---- pass 2: lane k2 = l now holds Z[l + 32 k1] in z[k1]
             fft32(z);
-            MFX_STAMP2(4);
+            MFX_STAMP(4);
 
             // ---- real split over the pairs (k, 1024 - k), k = l + 32 k1, k1 < 16.  Z[1024 - k] is register 31 - k1 of
             // lane 32 - l; lane 0 pairs with itself: register 32 - k1 (and Z[0] with itself), so it sends its registers
@@ -393,7 +345,7 @@ __global__ void __launch_bounds__(kW2048 * 64, (kW2048 + 3) / 4) k_front2048(Fro
                     plane[M - l - 32 * k1] = __builtin_amdgcn_sqrtf(br * br + bi * bi); // |X[1024 - k]| / W2
                 }
             }
-            MFX_STAMP2(10);
+            MFX_STAMP(10);
             { // bin 512 pairs with itself: Z[512] is register 16 of lane 0 (S = 2 Re, T = cs[512] * 2i Im)
                 const float2 zk = z[16], w = *s_cs512;
                 const float sr = zk.x + zk.x, di = zk.y + zk.y;
@@ -407,11 +359,11 @@ __global__ void __launch_bounds__(kW2048 * 64, (kW2048 + 3) / 4) k_front2048(Fro
                 issue(cnxt, half);
             else
                 issue(ccur, f + 2);
-            MFX_STAMP2(11);
+            MFX_STAMP(11);
             const int st_first = s_mst[l]; // first bin of this lane's filter in round 0 of the mel walk (requested before the sync)
             wave_sync();
 
-            MFX_STAMP2(5);
+            MFX_STAMP(5);
             // ---- mel filterbank on the frame's 32 lanes: per round every lane walks ONE filter's bins in ascending order,
             // one chain of multiply-adds (mfcccpu.cpp:206-217); weights from the lane's own zero-padded row (16-byte
             // reads), magnitudes as 8-byte reads from even starts spread over the banks by the host
@@ -468,7 +420,7 @@ __global__ void __launch_bounds__(kW2048 * 64, (kW2048 + 3) / 4) k_front2048(Fro
             }
             wave_sync();
 
-            MFX_STAMP2(6);
+            MFX_STAMP(6);
             // ---- every 4th frame (and at the chunk's end): DCT-II + lifter of the waiting frames on the matrix pipe,
             // D[row][c] = sum_m A[row][m] B[m][c] with frame g in rows 4g..4g+3, so register 0 of the result is out[g][c]
             // on lane (g, c); tiles of 16 columns, K steps of 4 bands, two accumulator chains (as k_front_reg)
@@ -531,14 +483,14 @@ __global__ void __launch_bounds__(kW2048 * 64, (kW2048 + 3) / 4) k_front2048(Fro
                 }
                 wave_sync();
             }
-            MFX_STAMP2(7);
+            MFX_STAMP(7);
         }
         if (n_live <= 0) issue(cnxt, half); // empty chunk: its last iteration never ran, nothing was requested
         c_cur = c_nxt;
         ccur = cnxt;
         c_nxt = draw();
-        cnxt = make_ctx(c_nxt);
-        MFX_STAMP2(8);
+        cnxt = chunk_ctx<STEREO ? 2 : 1, ANY>(p, c_nxt);
+        MFX_STAMP(8);
     }
 #ifdef MFX_STAMPS
     if (lane == 0 && p.spec) {

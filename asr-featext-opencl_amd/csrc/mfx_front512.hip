@@ -4,12 +4,15 @@
 // and their launchers.  Replaces segmenter.cl kernelSegmentWindow + AppleFFT + mfcc.cl kernelTranspose / kernelFilter + the DCT
 // slot (mfccopencl.cpp:315-358).  Numerics follow the reference CPU path (mfcccpu.cpp): frames = window * int16 sample (one
 // rounding), unnormalised forward DFT, magnitude / W2, two-row triangular mel table walked in ascending bin order,
-// log(max(., 1e-30)), DCT as a k-ordered dot product.  See DESIGN.md section 5.
+// log(max(., 1e-30)), DCT as a k-ordered dot product.  See DESIGN.md section 5.  What the two kernels (and k_front2048) share
+// as functions is in mfx_front_dev.h.  The transform core (pass A + twiddles, transposition), the work feed's rotation, the DCT's
+// matrix chain, the mel walk and the fused delta wave are written out in the kernel bodies: moved into functions, each of
+// them changes the register allocation of instantiations that sit at 128 registers (profiles/r06/README.md).
 #include "mfx_kernels.h"
 
 #include <hip/hip_runtime.h>
 
-#include "mfx_dev.h"
+#include "mfx_front_dev.h"
 #include "mfx_launch.h"
 
 #include <algorithm>
@@ -48,120 +51,29 @@ constexpr int kSlot = 512;    // dwords per frame slot
 constexpr int kWaves = MFX_WAVES512;    // waves per block of the 512-point kernel (16 waves per CU in all)
 constexpr int kThreads = kWaves * 64;
 constexpr int kMelOff = 304;  // mel scratch offset inside the slot (after 32 + 257 magnitudes)
-constexpr int kTabStride = 36;   // dwords per lane row of the window / pass-twiddle tables in LDS (16 complex + pad)
-constexpr int kSplitStride = 20; // dwords per lane row of the split-twiddle table (8 complex + pad)
 
-// DCT on the matrix pipe (dct_mode 1): K steps of v_mfma_f32_16x16x4_f32 over the mel bands, 4 bands per step
-constexpr int kDctSteps = 10;  // num_banks <= 40
-constexpr int kDctRow = 12;    // dwords per lane row of the B operand table in LDS (16-byte words, disjoint bank quads)
-// MFX_DCT_QUARTERS (default): the same DCT as 10 v_mfma_f32_4x4x1_16b_f32 -- 16 independent 4 x 4 outer products per
-// instruction: block (kb = lane >> 4, cg = (lane >> 2) & 3) accumulates frames i = 0..3 x columns 4 cg + j over the bands
+// DCT on the matrix pipe (dct_mode 1, num_banks <= 40): 10 v_mfma_f32_4x4x1_16b_f32 -- 16 independent 4 x 4 outer products
+// per instruction: block (kb = lane >> 4, cg = (lane >> 2) & 3) accumulates frames i = 0..3 x columns 4 cg + j over the bands
 // 10 kb .. 10 kb + 9, one band per instruction; the four band quarters are then added across the 16-lane rows
-// (v_permlane16_swap / v_permlane32_swap).  On gfx950 f32 matrix instructions run on the vector pipe's FP32 units
+// (dct_quarters_sum).  On gfx950 f32 matrix instructions run on the vector pipe's FP32 units
 // (SQ_VALU_MFMA_COEXEC_CYCLES = 0), so their cycles are the SIMD's cycles: 10 x 8 here against 10 x 32 for the
 // 16 x 16 x 4 form, which used a quarter of its rows (4 frames).
-#ifndef MFX_DCT_QUARTERS
-#define MFX_DCT_QUARTERS 1
-#endif
 constexpr int kDctQ = 10;      // bands per quarter
-constexpr int kDctQPad = 12;   // floats per quarter in the frame's log-energy row (16-byte aligned quarters)
+constexpr int kDctQPad = 12;   // floats per quarter in the frame's log-energy row, and per lane row of the B operand table in
+                               // LDS (16-byte aligned quarters; the table's 16-byte words on disjoint bank quads)
 __device__ __forceinline__ int dct_q_pos(int m) { return kDctQPad * (m / kDctQ) + (m % kDctQ); }
 
-// Partner fetch of the real split: lanes l >= 1 get x[16 - l] (mirror, then shift right by one inside the row);
-// lane 0, which the shift leaves without a source, keeps `own` -- its partner lives in its own registers.
-__device__ __forceinline__ float row_partner_own0(float own, float x)
-{
-    int t = __builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x140, 0xf, 0xf, true);   // row_mirror
-    t = __builtin_amdgcn_update_dpp(__float_as_int(own), t, 0x111, 0xf, 0xf, false);    // row_shr:1, lane 0 keeps old
-    return __int_as_float(t);
-}
-
-// x of lane 15 - l of the same 16-lane row
-__device__ __forceinline__ float row_mirror(float x)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x140, 0xf, 0xf, true));
-}
-
-template <bool ALIGNED, int NM>
-struct PcmRegs {
-    uint32_t d[ALIGNED ? NM : 2 * NM];
-};
-
-// issue the loads of one iteration (4 frames); `voff` = byte offset of this lane's first pair
-template <bool ALIGNED, int NM>
-__device__ __forceinline__ void pcm_issue(PcmRegs<ALIGNED, NM> &r, __amdgpu_buffer_rsrc_t rsrc, int voff)
-{
-#pragma unroll
-    for (int m = 0; m < NM; ++m) {
-        if (ALIGNED) {
-            r.d[m] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, voff + 64 * m, 0, 0);
-        } else {
-            r.d[2 * m] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, voff + 64 * m, 0, 0);
-            r.d[2 * m + 1] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, voff + 64 * m + 4, 0, 0);
-        }
-    }
-}
-
-// The zero-stuffed form (256-point transforms on the 512-point core, k_front512<.., STUFF>): ONE sample per lane and row,
-// 16 samples per row; `voff` = byte offset of this lane's first sample
-template <int NM>
-__device__ __forceinline__ void pcm_issue_stuffed(PcmRegs<true, NM> &r, __amdgpu_buffer_rsrc_t rsrc, int voff, int row_bytes)
-{
-#pragma unroll
-    for (int m = 0; m < NM; ++m) r.d[m] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b16(rsrc, voff, row_bytes * m, 0);
-}
-
-// One batch of the mel walk: NB bins (8 or 16) of a round, every read issued before the first multiply -- the weights as
-// 16-byte words, the magnitudes as 8-byte words that stay apart (lds_read_b64), all at immediate offsets from the batch's two
-// addresses -- so that a batch is ONE dependent LDS round trip whatever its size.  (The barrier: left alone the scheduler
-// keeps three magnitude reads in flight and issues the rest between the multiplies.)  The products are added to the one
-// accumulator in ascending bin order (mfcccpu.cpp:192-220): the same chain of multiply-adds as 8 bins at a time.
-template <int NB>
-__device__ __forceinline__ float mel_batch(float acc, const float *w, const float *m)
-{
-    float4 wq[NB / 4];
-    float2 mm[NB / 2];
-#pragma unroll
-    for (int q = 0; q < NB / 4; ++q) wq[q] = *(const float4 *)(w + 4 * q);
-#pragma unroll
-    for (int q = 0; q < NB / 2; ++q) mm[q] = lds_read_b64((const float2 *)(m + 2 * q));
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int q = 0; q < NB / 4; ++q) {
-        acc += wq[q].x * mm[2 * q].x;
-        acc += wq[q].y * mm[2 * q].y;
-        acc += wq[q].z * mm[2 * q + 1].x;
-        acc += wq[q].w * mm[2 * q + 1].y;
-    }
-    return acc;
-}
-
-// One round of the walk (L bins, a multiple of 8): 16 bins at a time, then the 8-bin remainder.  The 32 registers of a
-// 16-bin batch are free in the walk (the frame loop needs its 128 in pass A only); 32-bin batches spill
-// (profiles/r05/abx_c2_mel_round_batches.txt).  L is uniform: scalar branches.
-__device__ __forceinline__ float mel_round(const float *w, const float *m, int L)
-{
-    float acc = 0.f;
-    int s = 0;
-    for (; s + 16 <= L; s += 16) acc = mel_batch<16>(acc, w + s, m + s);
-    if (s < L) acc = mel_batch<8>(acc, w + s, m + s);
-    return acc;
-}
-
-// Dev-only in-kernel stamps (-DMFX_STAMPS): per-wave cycle sums per phase, written by lane 0 to
-// p.spec (which is unused by the fused path).  Never part of a timed build.
-#ifdef MFX_STAMPS
-#define MFX_STAMP(i)                                                                   \
-    do {                                                                               \
-        unsigned long long t_;                                                         \
-        __builtin_amdgcn_sched_barrier(0);                                             \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");     \
-        __builtin_amdgcn_sched_barrier(0);                                             \
-        st_acc[i] += t_ - st_last;                                                     \
-        st_last = t_;                                                                  \
+// Dev-only stamps of the fused delta wave (-DMFX_DSTAMPS, tools/dstamps.py): 100 MHz ticks waiting / working (ds_acc, ds_last, ds_t
+// of the wave)
+#ifdef MFX_DSTAMPS
+#define DSTAMP(i)                                                                         \
+    do {                                                                                  \
+        asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ds_t)::"memory");  \
+        ds_acc[i] += ds_t - ds_last;                                                      \
+        ds_last = ds_t;                                                                   \
     } while (0)
 #else
-#define MFX_STAMP(i)
+#define DSTAMP(i)
 #endif
 
 // STUFF: a 256-POINT transform on this core.  The 512-point real DFT of the frame with a zero after every sample,
@@ -193,8 +105,8 @@ __global__ void __launch_bounds__(kThreads, 4) k_front512(FrontParams p) // (4 w
     float *s_melw = s_split + 16 * kSplitStride;     // [16][RS]
     int *s_mmeta = (int *)(s_melw + 16 * RS);        // [rounds][16] (first bin, filter id): one 8-byte read per round
     float *s_dct = (float *)(s_mmeta + 32 * rounds); // [cols][DS]
-    // dct_mode 0: transposed matrix [cols][DS]; dct_mode 1: matrix-pipe B operands per lane, [64][kDctRow]
-    const int dct_floats = !p.dct ? 0 : p.dct_mode == 1 ? 64 * kDctRow : cols * DS;
+    // dct_mode 0: transposed matrix [cols][DS]; dct_mode 1: matrix-pipe B operands per lane, [64][kDctQPad]
+    const int dct_floats = !p.dct ? 0 : p.dct_mode == 1 ? 64 * kDctQPad : cols * DS;
     float *s_wave = s_dct + dct_floats + wave * (4 * kSlot);
     float *xb = s_wave + slot * kSlot;
     // FUSE: the last wave runs the delta stage; its region starts at its (unused) frame slots
@@ -208,29 +120,24 @@ __global__ void __launch_bounds__(kThreads, 4) k_front512(FrontParams p) // (4 w
         for (int i = tid; i < p.done_words; i += kThreads) s_done[i] = 0u;
 
     for (int i = tid; i < 256; i += kThreads) { // HBM tables are [lane][m] as well
-        ((float2 *)(s_win + (i >> 4) * kTabStride))[i & 15] = ((const float2 *)p.winpair)[i];
-        ((float2 *)(s_tw + (i >> 4) * kTabStride))[i & 15] = ((const float2 *)p.twid_pass)[i];
+        stage_lane_row(s_win, p.winpair, i);
+        stage_lane_row(s_tw, p.twid_pass, i);
     }
-    for (int i = tid; i < 128; i += kThreads) // bins 0..127, natural order in HBM
-        ((float2 *)(s_split + (i & 15) * kSplitStride))[i >> 4] = ((const float2 *)p.twid_split)[i];
+    for (int i = tid; i < 128; i += kThreads) stage_split(s_split, i, ((const float2 *)p.twid_split)[i]);
     if (!TO_SPEC) {
-        for (int i = tid; i < 16 * RS; i += kThreads) s_melw[i] = p.mel_lane_w[i];
+        stage_mel_weights(s_melw, p, tid, kThreads);
         for (int i = tid; i < 16 * rounds; i += kThreads) {
             s_mmeta[2 * i] = p.mel_lane_start[i];
             const int fid = p.mel_lane_fid[i];
             // (matrix-pipe form: idle lanes park their value in a word nobody reads)
-            if (MFX_DCT_QUARTERS)
-                s_mmeta[2 * i + 1] = p.dct_mode != 1 ? fid : fid < 0 ? 4 * kDctQPad : dct_q_pos(fid);
-            else
-                s_mmeta[2 * i + 1] = (fid < 0 && p.dct_mode == 1) ? 4 * kDctSteps : fid;
+            s_mmeta[2 * i + 1] = p.dct_mode != 1 ? fid : fid < 0 ? 4 * kDctQPad : dct_q_pos(fid);
         }
         if (p.dct_mode == 1) {
-            // B operand of K step j on lane (k = lane >> 4, n = lane & 15) is dct[4 j + k][n]; zeros beyond the matrix
-            for (int i = tid; i < 64 * kDctRow; i += kThreads) {
-                // (MFX_DCT_QUARTERS: B operand of band 10 kb + j on lane (kb = lane >> 4, n = lane & 15))
-                const int ln = i / kDctRow, j = i - ln * kDctRow, n = ln & 15;
-                const int m = MFX_DCT_QUARTERS ? kDctQ * (ln >> 4) + j : 4 * j + (ln >> 4);
-                s_dct[i] = (j < kDctSteps && m < p.num_banks && n < p.dct_len) ? p.dct[m * p.dct_len + n] : 0.f;
+            // B operand of band 10 kb + j on lane (kb = lane >> 4, n = lane & 15) is dct[10 kb + j][n]; zeros beyond the matrix
+            for (int i = tid; i < 64 * kDctQPad; i += kThreads) {
+                const int ln = i / kDctQPad, j = i - ln * kDctQPad, n = ln & 15;
+                const int m = kDctQ * (ln >> 4) + j;
+                s_dct[i] = (j < kDctQ && m < p.num_banks && n < p.dct_len) ? p.dct[m * p.dct_len + n] : 0.f;
             }
         } else {
             for (int i = tid; i < dct_floats; i += kThreads) s_dct[i] = p.dct_t[i];
@@ -240,7 +147,8 @@ __global__ void __launch_bounds__(kThreads, 4) k_front512(FrontParams p) // (4 w
     for (int i = lane; i < 4 * kSlot; i += 64) s_wave[i] = 0.f;
     __syncthreads();
 
-    // ---- FUSE: the delta wave.  It consumes the block's tiles in order; a tile is ready once the
+    // ---- FUSE: the delta wave (kept in the kernel: as a function of its own it changes the FUSE builds' registers).
+    // It consumes the block's tiles in order; a tile is ready once the
     // chunks it reads (its own rows and up to D rows either side) have their bits set in s_done.  The
     // front-end waves only ever produce, so the wait cannot deadlock; it is bounded all the same.
     const int chunk_base = FUSE ? p.blk_chunk_off[blockIdx.x] : 0;
@@ -255,14 +163,6 @@ __global__ void __launch_bounds__(kThreads, 4) k_front512(FrontParams p) // (4 w
         unsigned long long ds_acc[4] = {0, 0, 0, 0}, ds_last, ds_t, ds_ph[4] = {0, 0, 0, 0};
         asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ds_last)::"memory");
         const unsigned long long ds_begin = ds_last;
-#define DSTAMP(i)                                                                         \
-    do {                                                                                  \
-        asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ds_t)::"memory");  \
-        ds_acc[i] += ds_t - ds_last;                                                      \
-        ds_last = ds_t;                                                                   \
-    } while (0)
-#else
-#define DSTAMP(i)
 #endif
         for (; t < t_end; ++t) {
             // the next descriptor is fetched while this tile is worked on (one past the end is a valid
@@ -334,37 +234,7 @@ __global__ void __launch_bounds__(kThreads, 4) k_front512(FrontParams p) // (4 w
     // chunks are small enough to even out the tail.  The chunk walk is software pipelined so that a
     // chunk boundary costs no memory latency: the next chunk's descriptor is already in scalar
     // registers and the last iteration of a chunk prefetches the first frames of the next one.
-    struct ChunkCtx {
-        int64_t out_row;
-        int n_live, odd0;
-        __amdgpu_buffer_rsrc_t rsrc;
-    };
-    auto make_ctx = [&](int c) -> ChunkCtx {
-        ChunkCtx x;
-        const bool valid = c < p.n_chunks;
-        const Chunk *chp = p.chunks + (valid ? c : 0);
-        const int64_t pcm_off = chp->pcm_off;
-        x.out_row = chp->out_row;
-        const int n_frames = valid ? chp->n_frames : 0;
-        const int64_t rows_left = p.row_limit - x.out_row;
-        x.n_live = (int)(rows_left < n_frames ? (rows_left < 0 ? 0 : rows_left) : n_frames);
-        // buffer descriptor over [chunk start, end of PCM): out-of-range lanes read 0
-        // (CH2: p.pcm_total counts int16 elements, two per sample; every sample is a whole, aligned word)
-        const int64_t base_s = CH2 ? pcm_off * 2 : (ALIGNED && !STUFF) ? pcm_off : (pcm_off & ~(int64_t)1);
-        x.odd0 = (CH2 || (ALIGNED && !STUFF)) ? 0 : (int)(pcm_off & 1);
-        // (rounded up to whole 32-bit words: with an odd sample count the array's last sample sits in a word whose
-        // upper half lies past the end, and the range check would drop the whole word -- the base is 4-byte aligned,
-        // so that word is inside the allocation, and the half past the end only ever meets a zero window tap)
-        int64_t bytes_left = valid ? (((p.pcm_total - base_s) * 2 + 3) & ~(int64_t)3) : 0;
-        if (bytes_left > 0xfffffff0ll) bytes_left = 0xfffffff0ll;
-        if (bytes_left < 0) bytes_left = 0;
-        const uintptr_t bp = (uintptr_t)(p.pcm + base_s);
-        const uint32_t bp_lo = __builtin_amdgcn_readfirstlane((uint32_t)bp);
-        const uint32_t bp_hi = __builtin_amdgcn_readfirstlane((uint32_t)(bp >> 32));
-        const uint32_t nbytes = __builtin_amdgcn_readfirstlane((uint32_t)bytes_left);
-        x.rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)(((uintptr_t)bp_hi << 32) | bp_lo), 0, nbytes, 0x00020000);
-        return x;
-    };
+    auto make_ctx = [&](int c) { return chunk_ctx<CH2 ? 2 : 1, !(ALIGNED && !STUFF)>(p, c); };
     // byte offset of (frame f, sample pair l) relative to the chunk's descriptor base
     auto lane_off = [&](const ChunkCtx &x, int f) -> int {
         // (STUFF: p.stuff = 512 / W2 = 2, 4 or 8 -- a zero after every sample once, twice or three times over: every
@@ -374,19 +244,13 @@ __global__ void __launch_bounds__(kThreads, 4) k_front512(FrontParams p) // (4 w
         const int s = x.odd0 + f * p.shift + 2 * l;
         return ALIGNED ? s * 2 : (s & ~1) * 2;
     };
-    // Block b owns chunks b, b + B, b + 2B, ...; its waves draw from that list through a counter in
-    // LDS (a ds_add_rtn costs ~100 cycles and contends with the block's other waves only), so waves that the
-    // SIMD arbiter favours simply take more chunks instead of finishing early and idling the CU.
+    // The block's waves draw its chunks through the counter in LDS (draw_index / chunk_of_draw); the three-deep rotation
+    // stays written out here and in k_front1024: as a struct of its own it changes every build's register allocation.
     const int block_id = xcd_block_id(); // (consecutive ids, i.e. consecutive chunks, on one XCD's L2)
-    auto next_index = [&]() -> int {
-        int k = 0;
-        if (lane == 0) k = __hip_atomic_fetch_add(s_ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        return k;
-    };
+    auto next_index = [&]() { return draw_index(s_ctr, lane); };
     auto chunk_of = [&](int k) -> int {
         if (FUSE) return k < chunk_cnt ? chunk_base + k : p.n_chunks; // the block's own contiguous list, in order
-        const long long c = (long long)block_id + (long long)k * gridDim.x;
-        return c < p.n_chunks ? (int)c : p.n_chunks;
+        return chunk_of_draw(block_id, k, p.n_chunks);
     };
     int v_a = next_index(), v_b = next_index(), v_nn = next_index();
     int c_cur = chunk_of(__builtin_amdgcn_readfirstlane(v_a));
@@ -450,7 +314,7 @@ __global__ void __launch_bounds__(kThreads, 4) k_front512(FrontParams p) // (4 w
                         x0 = (float)(int)(short)(d & 0xffffu);
                         x1 = (float)((int)d >> 16);
                     }
-                    const float2 w = (m & 1) ? make_float2(wq[m >> 1].z, wq[m >> 1].w) : make_float2(wq[m >> 1].x, wq[m >> 1].y);
+                    const float2 w = pair_at(wq, m);
                     a[m] = STUFF ? make_float2(w.x * x0, 0.f) : make_float2(w.x * x0, w.y * x1);
                 } else {
                     a[m] = make_float2(0.f, 0.f);
@@ -463,7 +327,8 @@ __global__ void __launch_bounds__(kThreads, 4) k_front512(FrontParams p) // (4 w
             issue(last ? cnxt.rsrc : ccur.rsrc, last ? lane_off(cnxt, slot) : lane_off(ccur, f + 4));
 
             MFX_STAMP(1);
-            // ---- pass A + inter-pass twiddle
+            // ---- pass A + inter-pass twiddle (the same lines as k_front1024's fft256_head, and the transposition below as
+            // its phase E's: shared functions for the two change the register allocation of all 32 builds)
             fft16(a);
             {
                 float4 tq[8];
@@ -493,9 +358,7 @@ __global__ void __launch_bounds__(kThreads, 4) k_front512(FrontParams p) // (4 w
 
             MFX_STAMP(3);
             // ---- pass B: a[pp] = Z[l + 16 pp]
-#if !defined(MFX_ABLATE) || MFX_ABLATE < 3
             fft16(a);
-#endif
 
             MFX_STAMP(4);
             // ---- real split + magnitude, one partner fetch per bin PAIR (k, 256 - k), k = l + 16 p, p < 8:
@@ -507,14 +370,6 @@ __global__ void __launch_bounds__(kThreads, 4) k_front512(FrontParams p) // (4 w
             // Lane 0, p = 0 pairs bin 0 with the Nyquist bin 256 = Z[0] again: X[256] = Re Z[0] - Im Z[0] falls out
             // of the same formula; its self-paired bin 128 = conj-scaled Z[128] is done on the side.
             float mag_k[8], mag_p[8];
-#if defined(MFX_ABLATE) && MFX_ABLATE >= 2
-#pragma unroll
-            for (int pp = 0; pp < 8; ++pp) {
-                mag_k[pp] = a[pp].x + a[pp].y;
-                mag_p[pp] = a[15 - pp].x + a[15 - pp].y;
-            }
-            const float mag128 = 0.f;
-#else
             const float m128r = a[8].x + a[8].x, m128i = a[8].y + a[8].y;
             const float mag128 = __builtin_amdgcn_sqrtf(m128r * m128r + m128i * m128i);
             float4 csq[4];
@@ -524,17 +379,9 @@ __global__ void __launch_bounds__(kThreads, 4) k_front512(FrontParams p) // (4 w
             for (int pp = 0; pp < 8; ++pp) {
                 const float zr = row_partner_own0(a[(16 - pp) & 15].x, a[15 - pp].x);
                 const float zi = row_partner_own0(a[(16 - pp) & 15].y, a[15 - pp].y);
-                const float2 cs = (pp & 1) ? make_float2(csq[pp >> 1].z, csq[pp >> 1].w) : make_float2(csq[pp >> 1].x, csq[pp >> 1].y);
-                const float sr = a[pp].x + zr, si = a[pp].y - zi;
-                const float dr = a[pp].x - zr, di = a[pp].y + zi;
-                const float tr = cs.x * dr - cs.y * di;
-                const float ti = cs.x * di + cs.y * dr;
-                const float xr = sr + tr, xi = si + ti;
-                const float yr = sr - tr, yi = si - ti;
-                mag_k[pp] = __builtin_amdgcn_sqrtf(xr * xr + xi * xi); // the window taps carry 0.5 / W2
-                mag_p[pp] = __builtin_amdgcn_sqrtf(yr * yr + yi * yi);
+                const float2 cs = pair_at(csq, pp);
+                split_pair(a[pp], zr, zi, cs, mag_k[pp], mag_p[pp]);
             }
-#endif
 
             MFX_STAMP(5);
             if (TO_SPEC) {
@@ -549,16 +396,6 @@ __global__ void __launch_bounds__(kThreads, 4) k_front512(FrontParams p) // (4 w
                     if (l == 0 && (!STUFF || stuff_sh == 0)) dst[128] = mag128;
                 }
             } else {
-#if defined(MFX_ABLATE) && MFX_ABLATE >= 1
-                {   // dev-only: stop after the magnitudes, keep them live
-                    float acc = mag128;
-#pragma unroll
-                    for (int pp = 0; pp < 8; ++pp) acc += mag_k[pp] + mag_p[pp];
-                    float *dstx = p.feat + (out_row + (live ? f : 0)) * (int64_t)p.feat_pitch;
-                    if (live && l < cols) dstx[l] = acc;
-                    continue;
-                }
-#endif
                 // odd slots keep their magnitudes 32 dwords further in: the two slots of a 32-lane
                 // LDS access group then sit on complementary bank pairs for the b64 mel reads
                 float *mg0 = xb + 32 * (slot & 1);
@@ -584,11 +421,8 @@ __global__ void __launch_bounds__(kThreads, 4) k_front512(FrontParams p) // (4 w
                 if (p.dct_mode == 1) {
                     // log mel energies to the frame's LDS row (8 dwords of skew per slot: the operand reads below
                     // then fall on distinct banks), then the DCT-II + lifter (mfcccpu.cpp:222-232) as ONE chain of
-                    // f32 matrix instructions per 4 frames on the otherwise idle matrix pipe:
-                    //   D[row][c] = sum_m A[row][m] B[m][c],  v_mfma_f32_16x16x4_f32, K step j covers m = 4j .. 4j+3,
-                    // bit for bit an fmaf chain in ascending m.  Frame `slot` sits in rows 4 slot .. 4 slot + 3 (four
-                    // copies: all 64 lanes read valid energies), so register 0 of the result is out[slot][c] on
-                    // lane (slot, c) -- exactly the lane that stores it.
+                    // quartered f32 matrix instructions per 4 frames (see kDctQ), per quarter bit for bit an fmaf chain in
+                    // ascending m; the result is out[slot][l] on lane (slot, l) -- exactly the lane that stores it.
                     float *lm = xb + kMelOff + 8 * slot;
                     const int2 *mmeta = (const int2 *)s_mmeta + l;
                     for (int r = 0; r < rounds; ++r) {
@@ -602,12 +436,12 @@ __global__ void __launch_bounds__(kThreads, 4) k_front512(FrontParams p) // (4 w
                         lm[fid] = MFX_LOG(fmaxf(acc, 1e-30f)); // (idle lanes: fid names a word nobody reads)
                     }
                     wave_sync();
-#if MFX_DCT_QUARTERS
+                    // (the chain stays here and in k_front1024: a shared template swaps registers in the FUSE builds)
                     // A operand of lane (kb = lane >> 4, i = lane & 3): frame i's log energies of bands 10 kb + t (the row of
                     // slot i, quarter kb: 12 floats, 16-byte aligned); B operand: this lane's 10 coefficients.  Two accumulator
                     // chains (even / odd bands of the quarter), each ascending in m.
                     const float4 *aq = (const float4 *)(s_wave + (lane & 3) * (kSlot + 8) + kMelOff + kDctQPad * slot);
-                    const float4 *bq = (const float4 *)(s_dct + lane * kDctRow);
+                    const float4 *bq = (const float4 *)(s_dct + lane * kDctQPad);
                     const float4 a0 = aq[0], a1 = aq[1], a2 = aq[2];
                     const float4 dq0 = bq[0], dq1 = bq[1], dq2 = bq[2];
                     f32x4 dacc = {0.f, 0.f, 0.f, 0.f}, dacc2 = {0.f, 0.f, 0.f, 0.f};
@@ -621,30 +455,7 @@ __global__ void __launch_bounds__(kThreads, 4) k_front512(FrontParams p) // (4 w
                     dacc2 = __builtin_amdgcn_mfma_f32_4x4x1f32(a1.w, dq1.w, dacc2, 0, 0, 0);
                     dacc = __builtin_amdgcn_mfma_f32_4x4x1f32(a2.x, dq2.x, dacc, 0, 0, 0);
                     dacc2 = __builtin_amdgcn_mfma_f32_4x4x1f32(a2.y, dq2.y, dacc2, 0, 0, 0);
-                    // register i of lane (kb, c) now holds frame i's partial sum of column c over quarter kb; the lane that
-                    // stores out[slot][l] is (row slot, column l): add the quarters across the four 16-lane rows while moving
-                    // frame i's sums to row i (two butterfly steps: rows 1 <-> 0 / 3 <-> 2, then the two halves of the wave)
-                    const auto r01 = __builtin_amdgcn_permlane16_swap(__float_as_uint(dacc[0] + dacc2[0]), __float_as_uint(dacc[1] + dacc2[1]), false, false);
-                    const auto r23 = __builtin_amdgcn_permlane16_swap(__float_as_uint(dacc[2] + dacc2[2]), __float_as_uint(dacc[3] + dacc2[3]), false, false);
-                    const float s01 = __uint_as_float(r01[0]) + __uint_as_float(r01[1]);
-                    const float s23 = __uint_as_float(r23[0]) + __uint_as_float(r23[1]);
-                    const auto rr = __builtin_amdgcn_permlane32_swap(__float_as_uint(s01), __float_as_uint(s23), false, false);
-                    const float outv = __uint_as_float(rr[0]) + __uint_as_float(rr[1]);
-#else
-                    const float *arow = s_wave + (l >> 2) * (kSlot + 8) + kMelOff + slot; // A[row l][k = slot] of K step 0
-                    const float4 *bq = (const float4 *)(s_dct + lane * kDctRow);
-                    const float4 dq0 = bq[0], dq1 = bq[1], dq2 = bq[2];
-                    const float dctb[12] = {dq0.x, dq0.y, dq0.z, dq0.w, dq1.x, dq1.y, dq1.z, dq1.w, dq2.x, dq2.y, dq2.z, dq2.w};
-                    // two accumulator chains (even and odd K steps): the 40-cycle dependent latency of the instruction is
-                    // covered by the other chain; each chain is an fmaf chain in ascending m, the two are added at the end
-                    f32x4 dacc = {0.f, 0.f, 0.f, 0.f}, dacc2 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int j = 0; j < kDctSteps; j += 2) {
-                        dacc = __builtin_amdgcn_mfma_f32_16x16x4f32(arow[4 * j], dctb[j], dacc, 0, 0, 0);
-                        dacc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(arow[4 * j + 4], dctb[j + 1], dacc2, 0, 0, 0);
-                    }
-                    const float outv = dacc[0] + dacc2[0];
-#endif
+                    const float outv = dct_quarters_sum(dacc, dacc2);
                     // pitch 16 = compact static scratch: write whole 64-byte rows (zeros beyond cols)
                     if (live && (l < cols || p.feat_pitch == 16)) dst[l] = outv;
                 } else {
@@ -742,8 +553,8 @@ constexpr int kOddOffL = 264;     // O magnitudes inside the slot
 constexpr int kTrOffL = 272;      // phase O's transposition (256 dwords)
 constexpr int kMelOffL = 0;       // log energies (frame `slot` staggered by 8 slot words)
 constexpr int kTabStrideO = 68;   // dwords per lane row of the phase-O window table (16 x (A, B, C, D) + pad: 17 16-byte words)
-constexpr int kDctStepsL = 20;    // num_banks <= 80
-constexpr int kDctRowL = 20;      // dwords per lane row of the B operand table (5 16-byte words: odd)
+constexpr int kDctQL = 20;        // bands per quarter (num_banks <= 80): the frame's row holds the quarters back to back, and the
+                                  // B operand table's lane rows are as long (5 16-byte words: odd)
 
 // WAVES per block = per CU: 16 (4 per SIMD, 128 registers: the aligned builds of windows up to 512 samples, when the tables
 // leave room for 16 x 4 slots) or 12 (3 per SIMD, 168 registers: every other build)
@@ -764,76 +575,46 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES / 4) k_front1024(FrontParams
     float *s_splitO = s_splitE + 16 * kSplitStride;    // [16 l][kSplitStride]: -i W_1024^(2 (l + 16 p) + 1)
     float *s_melw = s_splitO + 16 * kSplitStride;      // [16][RS]
     int *s_mmeta = (int *)(s_melw + 16 * RS);          // [rounds][16] (first bin, filter id): one 8-byte read per round
-    float *s_dct = (float *)(s_mmeta + 32 * rounds);   // [64][kDctRowL]: matrix-pipe B operands per lane
-    float *s_wave = s_dct + 64 * kDctRowL + wave * (4 * kSlotL);
+    float *s_dct = (float *)(s_mmeta + 32 * rounds);   // [64][kDctQL]: matrix-pipe B operands per lane
+    float *s_wave = s_dct + 64 * kDctQL + wave * (4 * kSlotL);
     float *xb = s_wave + slot * kSlotL;
-    int *s_ctr = (int *)(s_dct + 64 * kDctRowL + WAVES * (4 * kSlotL));
+    int *s_ctr = (int *)(s_dct + 64 * kDctQL + WAVES * (4 * kSlotL));
     if (tid == 0) *s_ctr = 0;
 
     for (int i = tid; i < 256; i += WAVES * 64) { // HBM tables are [lane][m]
-        ((float2 *)(s_win + (i >> 4) * kTabStride))[i & 15] = ((const float2 *)p.winpair)[i];
+        stage_lane_row(s_win, p.winpair, i);
         ((float4 *)(s_winO + (i >> 4) * kTabStrideO))[i & 15] = ((const float4 *)p.win1024o)[i];
-        ((float2 *)(s_tw + (i >> 4) * kTabStride))[i & 15] = ((const float2 *)p.twid_pass)[i];
+        stage_lane_row(s_tw, p.twid_pass, i);
     }
     for (int i = tid; i < 128; i += WAVES * 64) { // twid_split holds -i W_1024^e, e <= 512, in natural order
-        ((float2 *)(s_splitE + (i & 15) * kSplitStride))[i >> 4] = ((const float2 *)p.twid_split)[2 * i];
-        ((float2 *)(s_splitO + (i & 15) * kSplitStride))[i >> 4] = ((const float2 *)p.twid_split)[2 * i + 1];
+        stage_split(s_splitE, i, ((const float2 *)p.twid_split)[2 * i]);
+        stage_split(s_splitO, i, ((const float2 *)p.twid_split)[2 * i + 1]);
     }
-    for (int i = tid; i < 16 * RS; i += WAVES * 64) s_melw[i] = p.mel_lane_w[i];
+    stage_mel_weights(s_melw, p, tid, WAVES * 64);
     for (int i = tid; i < 16 * rounds; i += WAVES * 64) {
         s_mmeta[2 * i] = p.mel_lane_start[i] >> 1; // (index into the even / odd magnitude arrays)
         const int fid = p.mel_lane_fid[i];
-        s_mmeta[2 * i + 1] = fid < 0 ? 4 * kDctStepsL : fid; // idle lanes park their value in a word nobody reads
+        s_mmeta[2 * i + 1] = fid < 0 ? 4 * kDctQL : fid; // idle lanes park their value in a word nobody reads
     }
-    for (int i = tid; i < 64 * kDctRowL; i += WAVES * 64) {
-        // (MFX_DCT_QUARTERS: B operand of band 20 kb + j on lane (kb = lane >> 4, n = lane & 15); see k_front512)
-        const int ln = i / kDctRowL, j = i - ln * kDctRowL, n = ln & 15;
-        const int m = MFX_DCT_QUARTERS ? kDctStepsL * (ln >> 4) + j : 4 * j + (ln >> 4);
+    for (int i = tid; i < 64 * kDctQL; i += WAVES * 64) {
+        // (B operand of band 20 kb + j on lane (kb = lane >> 4, n = lane & 15); see k_front512)
+        const int ln = i / kDctQL, j = i - ln * kDctQL, n = ln & 15;
+        const int m = kDctQL * (ln >> 4) + j;
         s_dct[i] = (p.dct && m < p.num_banks && n < p.dct_len) ? p.dct[m * p.dct_len + n] : 0.f;
     }
     for (int i = lane; i < 4 * kSlotL; i += 64) s_wave[i] = 0.f; // words read before they are written meet zero weights: finite
     __syncthreads();
 
-    // ---- chunk walk: as k_front512 (descriptor per chunk, software pipelined, block-local work counter)
-    struct ChunkCtx {
-        int64_t out_row;
-        int n_live, odd0;
-        __amdgpu_buffer_rsrc_t rsrc;
-    };
-    auto make_ctx = [&](int c) -> ChunkCtx {
-        ChunkCtx x;
-        const bool valid = c < p.n_chunks;
-        const Chunk *chp = p.chunks + (valid ? c : 0);
-        const int64_t pcm_off = chp->pcm_off;
-        x.out_row = chp->out_row;
-        const int n_frames = valid ? chp->n_frames : 0;
-        const int64_t rows_left = p.row_limit - x.out_row;
-        x.n_live = (int)(rows_left < n_frames ? (rows_left < 0 ? 0 : rows_left) : n_frames);
-        const int64_t base_s = ALIGNED ? pcm_off : (pcm_off & ~(int64_t)1);
-        x.odd0 = ALIGNED ? 0 : (int)(pcm_off & 1);
-        int64_t bytes_left = valid ? (((p.pcm_total - base_s) * 2 + 3) & ~(int64_t)3) : 0; // (whole words: see k_front512)
-        if (bytes_left > 0xfffffff0ll) bytes_left = 0xfffffff0ll;
-        if (bytes_left < 0) bytes_left = 0;
-        const uintptr_t bp = (uintptr_t)(p.pcm + base_s);
-        const uint32_t bp_lo = __builtin_amdgcn_readfirstlane((uint32_t)bp);
-        const uint32_t bp_hi = __builtin_amdgcn_readfirstlane((uint32_t)(bp >> 32));
-        const uint32_t nbytes = __builtin_amdgcn_readfirstlane((uint32_t)bytes_left);
-        x.rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)(((uintptr_t)bp_hi << 32) | bp_lo), 0, nbytes, 0x00020000);
-        return x;
-    };
+    // ---- chunk walk: as k_front512 (descriptor per chunk, software pipelined, block-local work counter; written out: see there)
+    auto make_ctx = [&](int c) { return chunk_ctx<1, !ALIGNED>(p, c); };
     auto lane_off = [&](const ChunkCtx &x, int f) -> int {
         const int s = x.odd0 + f * p.shift + 2 * l;
         return ALIGNED ? s * 2 : (s & ~1) * 2;
     };
     const int block_id = xcd_block_id(); // (consecutive ids, i.e. consecutive chunks, on one XCD's L2)
-    auto next_index = [&]() -> int {
-        int k = 0;
-        if (lane == 0) k = __hip_atomic_fetch_add(s_ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        return k;
-    };
+    auto next_index = [&]() { return draw_index(s_ctr, lane); };
     auto chunk_of = [&](int k) -> int {
-        const long long c = (long long)block_id + (long long)k * gridDim.x;
-        return c < p.n_chunks ? (int)c : p.n_chunks;
+        return chunk_of_draw(block_id, k, p.n_chunks);
     };
     int v_a = next_index(), v_b = next_index(), v_nn = next_index();
     int c_cur = chunk_of(__builtin_amdgcn_readfirstlane(v_a));
@@ -925,7 +706,7 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES / 4) k_front1024(FrontParams
                     } else if (m < NM) {
                         float x0, x1;
                         pair_of(m, x0, x1, false);
-                        const float2 w = (m & 1) ? make_float2(wq[m >> 1].z, wq[m >> 1].w) : make_float2(wq[m >> 1].x, wq[m >> 1].y);
+                        const float2 w = pair_at(wq, m);
                         a[m] = make_float2(w.x * x0, w.y * x1);
                     } else {
                         a[m] = make_float2(0.f, 0.f);
@@ -953,15 +734,8 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES / 4) k_front1024(FrontParams
                 for (int pp = 0; pp < 8; ++pp) {
                     const float zr = row_partner_own0(a[(16 - pp) & 15].x, a[15 - pp].x);
                     const float zi = row_partner_own0(a[(16 - pp) & 15].y, a[15 - pp].y);
-                    const float2 cs = (pp & 1) ? make_float2(csq[pp >> 1].z, csq[pp >> 1].w) : make_float2(csq[pp >> 1].x, csq[pp >> 1].y);
-                    const float sr = a[pp].x + zr, si = a[pp].y - zi;
-                    const float dr = a[pp].x - zr, di = a[pp].y + zi;
-                    const float tr = cs.x * dr - cs.y * di;
-                    const float ti = cs.x * di + cs.y * dr;
-                    const float xr = sr + tr, xi = si + ti;
-                    const float yr = sr - tr, yi = si - ti;
-                    elo[16 * pp] = __builtin_amdgcn_sqrtf(xr * xr + xi * xi); // the window taps carry 0.5 / W2
-                    ehi[16 * (7 - pp)] = __builtin_amdgcn_sqrtf(yr * yr + yi * yi);
+                    const float2 cs = pair_at(csq, pp);
+                    split_pair(a[pp], zr, zi, cs, elo[16 * pp], ehi[16 * (7 - pp)]);
                 }
             }
 
@@ -1022,15 +796,8 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES / 4) k_front1024(FrontParams
                     // partner V[255 - k]: register 15 - pp of lane 15 - l
                     const float zr = row_mirror(a[15 - pp].x);
                     const float zi = row_mirror(a[15 - pp].y);
-                    const float2 cs = (pp & 1) ? make_float2(csq[pp >> 1].z, csq[pp >> 1].w) : make_float2(csq[pp >> 1].x, csq[pp >> 1].y);
-                    const float sr = a[pp].x + zr, si = a[pp].y - zi;
-                    const float dr = a[pp].x - zr, di = a[pp].y + zi;
-                    const float tr = cs.x * dr - cs.y * di;
-                    const float ti = cs.x * di + cs.y * dr;
-                    const float xr = sr + tr, xi = si + ti;
-                    const float yr = sr - tr, yi = si - ti;
-                    olo[16 * pp] = __builtin_amdgcn_sqrtf(xr * xr + xi * xi);
-                    ohi[16 * (7 - pp)] = __builtin_amdgcn_sqrtf(yr * yr + yi * yi);
+                    const float2 cs = pair_at(csq, pp);
+                    split_pair(a[pp], zr, zi, cs, olo[16 * pp], ohi[16 * (7 - pp)]);
                 }
             }
             wave_sync();
@@ -1042,9 +809,9 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES / 4) k_front1024(FrontParams
             float *dst = p.feat + (out_row + f0) * (int64_t)p.feat_pitch + slot * p.feat_pitch;
             float *lm = xb + kMelOffL + 8 * slot;
             const int2 *mmeta = (const int2 *)s_mmeta + l;
-            float le[kDctStepsL / 4];
+            float le[kDctQL / 4];
 #pragma unroll
-            for (int r = 0; r < kDctStepsL / 4; ++r) {
+            for (int r = 0; r < kDctQL / 4; ++r) {
                 le[r] = 0.f;
                 if (r < rounds) {
                     const int L = p.mel_L[r];
@@ -1075,7 +842,7 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES / 4) k_front1024(FrontParams
             }
             wave_sync();
 #pragma unroll
-            for (int r = 0; r < kDctStepsL / 4; ++r)
+            for (int r = 0; r < kDctQL / 4; ++r)
                 if (r < rounds) lm[mmeta[16 * r].y] = le[r]; // (idle lanes: the filter id names a word nobody reads)
             wave_sync();
             if (!p.dct) {
@@ -1085,51 +852,25 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES / 4) k_front1024(FrontParams
             } else
             // ---- DCT-II + lifter on the matrix pipe (see k_front512): frame `slot` in rows 4 slot .. 4 slot + 3
             {
-#if MFX_DCT_QUARTERS
                 // 20 v_mfma_f32_4x4x1_16b_f32 over band quarters (20 bands each: the frame's row holds them back to back,
                 // 80-byte quarters), then the cross-row butterfly -- see k_front512
-                const float4 *aq = (const float4 *)(s_wave + (lane & 3) * (kSlotL + 8) + kMelOffL + kDctStepsL * slot);
-                const float4 *bq = (const float4 *)(s_dct + lane * kDctRowL);
+                const float4 *aq = (const float4 *)(s_wave + (lane & 3) * (kSlotL + 8) + kMelOffL + kDctQL * slot);
+                const float4 *bq = (const float4 *)(s_dct + lane * kDctQL);
                 f32x4 dacc = {0.f, 0.f, 0.f, 0.f}, dacc2 = {0.f, 0.f, 0.f, 0.f};
-                float4 av[kDctStepsL / 4], bv[kDctStepsL / 4];
+                float4 av[kDctQL / 4], bv[kDctQL / 4];
 #pragma unroll
-                for (int j = 0; j < kDctStepsL / 4; ++j) {
+                for (int j = 0; j < kDctQL / 4; ++j) {
                     av[j] = aq[j];
                     bv[j] = bq[j];
                 }
 #pragma unroll
-                for (int j = 0; j < kDctStepsL / 4; ++j) {
+                for (int j = 0; j < kDctQL / 4; ++j) {
                     dacc = __builtin_amdgcn_mfma_f32_4x4x1f32(av[j].x, bv[j].x, dacc, 0, 0, 0);
                     dacc2 = __builtin_amdgcn_mfma_f32_4x4x1f32(av[j].y, bv[j].y, dacc2, 0, 0, 0);
                     dacc = __builtin_amdgcn_mfma_f32_4x4x1f32(av[j].z, bv[j].z, dacc, 0, 0, 0);
                     dacc2 = __builtin_amdgcn_mfma_f32_4x4x1f32(av[j].w, bv[j].w, dacc2, 0, 0, 0);
                 }
-                const auto r01 = __builtin_amdgcn_permlane16_swap(__float_as_uint(dacc[0] + dacc2[0]), __float_as_uint(dacc[1] + dacc2[1]), false, false);
-                const auto r23 = __builtin_amdgcn_permlane16_swap(__float_as_uint(dacc[2] + dacc2[2]), __float_as_uint(dacc[3] + dacc2[3]), false, false);
-                const float s01 = __uint_as_float(r01[0]) + __uint_as_float(r01[1]);
-                const float s23 = __uint_as_float(r23[0]) + __uint_as_float(r23[1]);
-                const auto rr = __builtin_amdgcn_permlane32_swap(__float_as_uint(s01), __float_as_uint(s23), false, false);
-                const float outv = __uint_as_float(rr[0]) + __uint_as_float(rr[1]);
-#else
-                const float *arow = s_wave + (l >> 2) * (kSlotL + 8) + kMelOffL + slot;
-                const float4 *bq = (const float4 *)(s_dct + lane * kDctRowL);
-                float dctb[kDctStepsL];
-#pragma unroll
-                for (int j = 0; j < kDctStepsL / 4; ++j) {
-                    const float4 t = bq[j];
-                    dctb[4 * j] = t.x;
-                    dctb[4 * j + 1] = t.y;
-                    dctb[4 * j + 2] = t.z;
-                    dctb[4 * j + 3] = t.w;
-                }
-                f32x4 dacc = {0.f, 0.f, 0.f, 0.f}, dacc2 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int j = 0; j < kDctStepsL; j += 2) {
-                    dacc = __builtin_amdgcn_mfma_f32_16x16x4f32(arow[4 * j], dctb[j], dacc, 0, 0, 0);
-                    dacc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(arow[4 * j + 4], dctb[j + 1], dacc2, 0, 0, 0);
-                }
-                const float outv = dacc[0] + dacc2[0];
-#endif
+                const float outv = dct_quarters_sum(dacc, dacc2);
                 if (live && (l < cols || p.feat_pitch == 16)) dst[l] = outv;
             }
             wave_sync();
@@ -1151,7 +892,7 @@ size_t front512_lds_bytes(const FrontParams &p)
     size_t f = 2 * 16 * kTabStride + 16 * kSplitStride;  // window pairs, pass twiddles, split twiddles
     f += (size_t)16 * p.mel_row_stride;                  // per-lane mel weights
     f += (size_t)32 * p.mel_rounds;                      // per-lane bin starts + filter ids
-    f += !p.dct ? 0 : p.dct_mode == 1 ? (size_t)64 * kDctRow : (size_t)p.cols * p.dct_stride; // DCT table (either form)
+    f += !p.dct ? 0 : p.dct_mode == 1 ? (size_t)64 * kDctQPad : (size_t)p.cols * p.dct_stride; // DCT table (either form)
     f += kWaves * 4 * kSlot;                             // 4 frame slots per wave
     f += 4;                                              // block-local work counter
     return f * sizeof(float);
@@ -1204,7 +945,7 @@ size_t front1024_lds_bytes(const FrontParams &p, int waves)
 {
     size_t f = 2 * 16 * kTabStride + 16 * kTabStrideO + 2 * 16 * kSplitStride; // window pairs (E, O), pass twiddles, split twiddles (E, O)
     f += (size_t)16 * p.mel_row_stride + (size_t)32 * p.mel_rounds;             // per-lane mel weights, bin starts + filter ids
-    f += (size_t)64 * kDctRowL;                                                 // matrix-pipe operands of the DCT
+    f += (size_t)64 * kDctQL;                                                 // matrix-pipe operands of the DCT
     f += (size_t)waves * 4 * kSlotL + 4;                                        // 4 frame slots per wave, work counter
     return f * sizeof(float);
 }
@@ -1214,7 +955,7 @@ bool front1024_supported(int fft_size, int window_size, int num_banks, int cols,
 {
     // (with a DCT at most 16 columns -- the quartered matrix-pipe form; without one the log energies of up to 80 filters)
     return fft_size == 1024 && window_size > 0 && window_size <= 1024 && channels <= 1 && num_banks >= 1 &&
-           num_banks <= 4 * kDctStepsL && (ceps_len > 0 ? cols <= 16 : cols == num_banks);
+           num_banks <= 4 * kDctQL && (ceps_len > 0 ? cols <= 16 : cols == num_banks);
 }
 
 namespace {
@@ -1254,14 +995,6 @@ bool front512_supported(int fft_size, int window_size, int num_banks, int cols, 
     // (256 / 128 / 64 points: the zero-stuffed forms of the same kernel, FrontParams::stuff = 512 / fft_size)
     return (fft_size == 512 || fft_size == 256 || fft_size == 128 || fft_size == 64) && window_size <= fft_size && window_size > 0 && channels <= 2 && num_banks >= 1 &&
            num_banks <= 128 && cols <= 128;
-}
-
-const char *front512_kernel_name(bool to_spectrum, bool aligned, int nm16)
-{
-    (void)to_spectrum;
-    (void)aligned;
-    (void)nm16;
-    return "k_front512";
 }
 
 hipError_t launch_front512(const FrontParams &p, bool to_spectrum, bool aligned, int nm16, hipStream_t stream)

@@ -517,7 +517,4 @@ bool front2048_supported(int fft_size, int window_size, int num_banks, int cols,
 size_t front2048_lds_bytes(const FrontParams &p);
 hipError_t launch_front2048(const FrontParams &p, int num_cus, hipStream_t stream);
 
-// symbol name of the dominant kernel for rocprofv3 (depends on the instantiation chosen)
-const char *front512_kernel_name(bool to_spectrum, bool aligned, int nm16);
-
 } // namespace mfx
