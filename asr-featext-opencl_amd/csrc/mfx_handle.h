@@ -21,7 +21,7 @@
 #include "mfx_tables.h"
 
 constexpr int kChunkFrames = 16;           // frames per work item of the front-end kernels
-constexpr size_t kLdsCap = 160 * 1024;     // LDS a block may ask for on gfx950 (the kernels keep their own copy)
+constexpr size_t kLdsCap = 160 * 1024;     // LDS a block may ask for on gfx950 (the launchers' name for it: kLdsMax, mfx_launch.h)
 constexpr size_t kSmallBlock = (size_t)1 << 20; // below this a copy kernel replaces the DMA command (streaming interface)
 
 inline constexpr const char *kMsgBuffer = "Can't process data, buffer is too small";

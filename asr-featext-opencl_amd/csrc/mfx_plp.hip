@@ -42,7 +42,8 @@ __host__ __device__ inline int plp_rp(int nb, int ceps)
 // x^(1/3) for a positive normal x: v_log_f32 / v_exp_f32 (relative error ~1e-6 over the range of e_m E_m)
 __device__ __forceinline__ float plp_cbrt(float x) { return __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(x) * (1.0f / 3.0f)); }
 
-// The kernel's text is mfx_plp_body.h: compiled here as k_plp and as its row-run form k_plp_runs.
+// The kernel's text is mfx_plp_body.h: compiled here as k_plp and as its row-run form k_plp_runs.  (As a function template over
+// a row-group iterator, the form k_melcep has, k_plp_runs<16> was 1.1 % slower twice over: profiles/r07/README.md.)
 #define MFX_PLP_RUNS 0
 #include "mfx_plp_body.h"
 #undef MFX_PLP_RUNS
@@ -60,44 +61,20 @@ size_t plp_lds_bytes_t(const PlpParams &p, int n_waves)
     return f * sizeof(float);
 }
 
+// groups of kPlpRows rows for the busiest of `active` tables (launch_plp: all rows, 1); args: the kernel's arguments
 template <int PMAX>
-hipError_t launch_plp_t(const PlpParams &p, hipStream_t stream)
+hipError_t launch_plp_t(const void *fn, const PlpParams &p, int64_t groups, int active, hipStream_t stream, void **args)
 {
-    int nw = 4; // waves per block: as many of 4 as the LDS holds
-    while (nw > 1 && plp_lds_bytes_t<PMAX>(p, nw) > 160 * 1024) nw >>= 1;
-    const size_t lds = plp_lds_bytes_t<PMAX>(p, nw);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    const void *fn = (const void *)k_plp<PMAX>;
-    if (hipError_t e = allow_dynamic_lds(fn, lds); e != hipSuccess) return e;
-    int64_t blocks = ((p.n_rows + kPlpRows - 1) / kPlpRows + nw - 1) / nw;
-    int per_cu = blocks_per_cu(fn, 64 * nw, lds, (int)std::min<size_t>(4, (160 * 1024) / lds));
-    if (per_cu > 8) per_cu = 8;
-    const int cap = num_cus() * (per_cu < 1 ? 1 : per_cu);
-    if (blocks > cap) blocks = cap;
     const int tables = p.n_tables > 1 ? p.n_tables : 1;
-    if (tables > 65535) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_plp<PMAX>, dim3((unsigned)blocks, (unsigned)tables), dim3(64 * nw), lds, stream, p);
-    return hipGetLastError();
+    if (tables > kGridYMax) return hipErrorInvalidValue;
+    ResidentGrid g;
+    if (hipError_t e = resident_grid(fn, [&](int nw) { return plp_lds_bytes_t<PMAX>(p, nw); }, groups, active, g); e != hipSuccess) return e;
+    return hipLaunchKernel(fn, dim3(g.blocks, (unsigned)tables), dim3(64 * g.waves), args, g.lds, stream);
 }
 
-template <int PMAX>
-hipError_t launch_plp_runs_t(const PlpParams &p, const RowRuns &rr, int64_t groups, int active, hipStream_t stream)
+static bool plp_args_ok(const PlpParams &p)
 {
-    int nw = 4; // (as launch_plp_t)
-    while (nw > 1 && plp_lds_bytes_t<PMAX>(p, nw) > 160 * 1024) nw >>= 1;
-    const size_t lds = plp_lds_bytes_t<PMAX>(p, nw);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    const void *fn = (const void *)k_plp_runs<PMAX>;
-    if (hipError_t e = allow_dynamic_lds(fn, lds); e != hipSuccess) return e;
-    int per_cu = blocks_per_cu(fn, 64 * nw, lds, (int)std::min<size_t>(4, (160 * 1024) / lds));
-    if (per_cu > 8) per_cu = 8;
-    // the resident blocks are shared among the tables that have rows in this window (the others' blocks leave at once)
-    const int cap = (num_cus() * (per_cu < 1 ? 1 : per_cu) + active - 1) / active;
-    const int64_t blocks = std::min<int64_t>((groups + nw - 1) / nw, cap);
-    const int tables = p.n_tables > 1 ? p.n_tables : 1;
-    if (tables > 65535) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_plp_runs<PMAX>, dim3((unsigned)blocks, (unsigned)tables), dim3(64 * nw), lds, stream, p, rr);
-    return hipGetLastError();
+    return spec_rows_ok(p.mag_floats, p.spec_pitch) && p.lpc_order >= 1 && p.lpc_order <= kPlpMaxOrder && p.ceps_len >= 1 && p.num_banks >= 1;
 }
 
 } // namespace
@@ -114,12 +91,14 @@ size_t plp_lds_bytes(const PlpParams &p, int n_waves)
 hipError_t launch_plp(const PlpParams &p, hipStream_t stream)
 {
     if (p.n_rows <= 0) return hipSuccess;
-    if (p.mag_floats < p.spec_pitch || (p.spec_pitch & 3) || (p.mag_floats & 3)) return hipErrorInvalidValue;
-    if (p.lpc_order < 1 || p.lpc_order > kPlpMaxOrder || p.ceps_len < 1 || p.num_banks < 1) return hipErrorInvalidValue;
+    if (!plp_args_ok(p)) return hipErrorInvalidValue;
+    const int64_t groups = (p.n_rows + kPlpRows - 1) / kPlpRows;
+    PlpParams q = p;
+    void *args[] = {&q};
     switch (plp_pmax(p.lpc_order)) {
-    case 8: return launch_plp_t<8>(p, stream);
-    case 16: return launch_plp_t<16>(p, stream);
-    default: return launch_plp_t<32>(p, stream);
+    case 8: return launch_plp_t<8>((const void *)k_plp<8>, p, groups, 1, stream, args);
+    case 16: return launch_plp_t<16>((const void *)k_plp<16>, p, groups, 1, stream, args);
+    default: return launch_plp_t<32>((const void *)k_plp<32>, p, groups, 1, stream, args);
     }
 }
 
@@ -128,12 +107,14 @@ hipError_t launch_plp_runs(const PlpParams &p, const RowRuns &rr, const int32_t 
     int active = 0;
     const int64_t groups = run_groups_in_window(h_off, h_runs, p.n_tables > 1 ? p.n_tables : 1, rr.row0, rr.rows, kPlpRows, active);
     if (groups <= 0) return hipSuccess;
-    if (p.mag_floats < p.spec_pitch || (p.spec_pitch & 3) || (p.mag_floats & 3) || p.r_out) return hipErrorInvalidValue;
-    if (p.lpc_order < 1 || p.lpc_order > kPlpMaxOrder || p.ceps_len < 1 || p.num_banks < 1) return hipErrorInvalidValue;
+    if (!plp_args_ok(p) || p.r_out) return hipErrorInvalidValue;
+    PlpParams q = p;
+    RowRuns r = rr;
+    void *args[] = {&q, &r};
     switch (plp_pmax(p.lpc_order)) {
-    case 8: return launch_plp_runs_t<8>(p, rr, groups, active, stream);
-    case 16: return launch_plp_runs_t<16>(p, rr, groups, active, stream);
-    default: return launch_plp_runs_t<32>(p, rr, groups, active, stream);
+    case 8: return launch_plp_t<8>((const void *)k_plp_runs<8>, p, groups, active, stream, args);
+    case 16: return launch_plp_t<16>((const void *)k_plp_runs<16>, p, groups, active, stream, args);
+    default: return launch_plp_t<32>((const void *)k_plp_runs<32>, p, groups, active, stream, args);
     }
 }
 

@@ -1,5 +1,5 @@
 // mfx_plp_body.h -- the text of k_plp, included twice by mfx_plp.hip: MFX_PLP_RUNS 0 is k_plp itself (the same tokens as
-// ever: the same ISA), 1 is its row-run form k_plp_runs -- as k_melcep_runs (mfx_melcep_body.h) with groups of 64 rows: a
+// ever: the same ISA), 1 is its row-run form k_plp_runs -- as k_melcep_runs (mfx_tail.hip) with groups of 64 rows: a
 // wave's 64 rows come from ONE run, phase 2 runs with the table's own eql.  Not a header in its own right.
 template <int PMAX>
 #if MFX_PLP_RUNS

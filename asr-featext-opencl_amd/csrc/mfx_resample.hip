@@ -266,7 +266,7 @@ hipError_t launch_resample(const ResampleParams &p, hipStream_t stream)
         (p.out_elems & 1))
         return hipErrorInvalidValue;
     const size_t lds = resample_lds_bytes(p);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (lds > kLdsMax) return hipErrorInvalidValue;
     const void *fn = p.channels == 2 ? (const void *)k_resample<2> : (const void *)k_resample<1>;
     if (hipError_t e = allow_dynamic_lds(fn, lds); e != hipSuccess) return e;
     ResampleParams q = p;

@@ -105,13 +105,12 @@ hipError_t launch_sess_gather(const SessGatherParams &p, hipStream_t stream)
     if (p.cols <= 0 || p.stat_pitch < p.cols) return hipErrorInvalidValue;
     // a push is a few hundred words per session: up to 8 blocks of 256 words each
     const int pieces = std::min(8, (p.items_max + 255) / 256);
-    for (int s0 = 0; s0 < p.n_descs; s0 += 65535) {
+    return for_seg_slices(p.n_descs, [&](int s0, int n) {
         SessGatherParams q = p;
         q.descs = p.descs + s0;
-        q.n_descs = std::min(65535, p.n_descs - s0);
-        hipLaunchKernelGGL(k_sess_gather, dim3(pieces, q.n_descs), dim3(256), 0, stream, q);
-    }
-    return hipGetLastError();
+        q.n_descs = n;
+        return launch_kernel((const void *)k_sess_gather, dim3(pieces, n), dim3(256), 0, stream, q);
+    });
 }
 
 } // namespace mfx

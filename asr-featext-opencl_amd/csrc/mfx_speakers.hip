@@ -143,13 +143,11 @@ hipError_t launch_spk_sums(const SpkParams &p, hipStream_t stream)
     if (p.n_utt <= 0 || p.max_rows <= 0) return hipSuccess;
     if (!spk_shape_ok(p)) return hipErrorInvalidValue;
     const int chunks = spk_chunks(p.max_rows);
-    for (int u0 = 0; u0 < p.n_utt; u0 += 65535) {
+    return for_seg_slices(p.n_utt, [&](int u0, int n) {
         SpkParams q = p;
         q.u0 = u0;
-        const int ny = (p.n_utt - u0) < 65535 ? (p.n_utt - u0) : 65535;
-        hipLaunchKernelGGL(k_spk_sums, dim3(chunks, ny, p.groups), dim3(256), 0, stream, q);
-    }
-    return hipGetLastError();
+        return launch_kernel((const void *)k_spk_sums, dim3(chunks, n, p.groups), dim3(256), 0, stream, q);
+    });
 }
 
 hipError_t launch_spk_finish(const SpkParams &p, hipStream_t stream)

@@ -17,6 +17,15 @@
 #include <vector>
 #include "mfx_delta_dev.h"
 #include "mfx_norm_dev.h"
+#include "mfx_tile_dev.h"
+
+// build knobs: output rows per tile of the wide-row delta kernels (less LDS per block: more blocks per CU in flight)
+#ifndef MFX_DELTA_WIDE_ROWS
+#define MFX_DELTA_WIDE_ROWS 32   // k_delta<false, .> (C5: k_delta 0.072 -> 0.055 ms; 16 rows: 0.063)
+#endif
+#ifndef MFX_DELTA_WIDE_ROWS_V
+#define MFX_DELTA_WIDE_ROWS_V 32 // k_delta4
+#endif
 
 namespace mfx {
 
@@ -28,118 +37,79 @@ namespace {
 // wave's 64 lanes (MelWavePlan: whole filters in ascending bin order, mfcccpu.cpp:206-217), the log energies wait in
 // lm[4][FS], and the DCT of the four rows runs on the matrix pipe (dct_mfma4) -- the same mel stage as the fused batch
 // kernels (round 3: the round-1 piece plan and its vector-pipe DCT are gone).  blockIdx.y = filterbank of a VTLN sweep.
-// The kernel's text is mfx_melcep_body.h: compiled here as k_melcep and as its row-run form k_melcep_runs.
+// melcep_rows is the kernel's body over the row groups `groups(first, stride)` deals to this wave: all rows [0, n_rows) in
+// k_melcep, the table's row runs in k_melcep_runs.  (n_threads: blockDim.x, read once in the kernel -- read inside the
+// body it became a vector load in front of the staging.)
 // ------------------------------------------------------------------------------------------------
-#define MFX_MELCEP_RUNS 0
-#include "mfx_melcep_body.h"
-#undef MFX_MELCEP_RUNS
-#define MFX_MELCEP_RUNS 1
-#include "mfx_melcep_body.h"
-#undef MFX_MELCEP_RUNS
+template <class MakeGroups>
+__device__ __forceinline__ void melcep_rows(const MelcepParams &p, int table, float *feat, unsigned n_threads, MakeGroups groups)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, n_waves = n_threads >> 6;
+    const int nb = p.num_banks, RS = p.mel64_row_stride, rounds = p.mel64_rounds;
+    const int FS = lm_fs4(nb), MF = p.mag_floats;
+    const int WR = mel64_rows(nb);
+    MelPlanLds plan;
+    float *s_wave = stage_mel_plan(smem, p, table, tid, n_threads, plan) + wave * (MF + 4 * FS);
+    float *mag = s_wave, *lm = s_wave + MF;
+    for (int i = lane; i < MF + 4 * FS; i += 64) s_wave[i] = 0.f; // words past the last bin stay zero (finite) for good
+    __syncthreads();
+
+    const int dct_ks = p.dct_ksteps, dct_tiles64 = (p.dct_len + 63) >> 6;
+    const int dct_bytes = p.dct_b4 ? dct_tiles64 * dct_ks * 1024 : 0;
+    const __amdgpu_buffer_rsrc_t dct_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)p.dct_b4, 0, dct_bytes, 0x00020000);
+    const int q4 = p.spec_pitch >> 2; // rows are whole 16-byte words (spec_pitch is a multiple of 4, rows 16-byte aligned)
+    const int nbins = (p.fft_size >> 1) + 1;
+    for (auto it = groups((int64_t)blockIdx.x * n_waves + wave, (int64_t)gridDim.x * n_waves); it.valid(); it.advance()) {
+        const int64_t row0 = it.row0;
+        const int count = it.count;
+        for (int f = 0; f < count; ++f) {
+            const float4 *src = (const float4 *)(p.spec + (row0 + f) * p.spec_pitch);
+            for (int k = lane; k < q4; k += 64) ((float4 *)mag)[k] = src[k];
+            // the row's padding words (bins > W2/2) are never written in memory: they meet zero weights in the walk and
+            // must be finite (0 x NaN is NaN)
+            if (nbins + lane < 4 * q4) mag[nbins + lane] = 0.f;
+            wave_sync();
+            mel64_walk_log(mag, lm + f * FS, FS - 1, plan.s_mw, plan.s_mst, plan.s_mfid, plan.s_L, rounds, RS, lane, WR);
+            wave_sync();
+        }
+        dct4_store<3>(lm, FS, dct_rsrc, dct_bytes, dct_ks, dct_tiles64, p.dct_b4 != nullptr, lane, p.cols, feat, (int64_t)p.feat_pitch,
+                   row0, count);
+        wave_sync();
+    }
+}
+
+__global__ void __launch_bounds__(256) k_melcep(MelcepParams p)
+{
+    const int table = blockIdx.y;
+    melcep_rows(p, table, p.feat + (int64_t)table * p.feat_table_stride, blockDim.x,
+                [&](int64_t first, int64_t stride) { return PlainGroups<4>(p.n_rows, first, stride); });
+}
+
+// k_melcep_runs (per-utterance warp factors of the batch entries): blockIdx.y is still the table, staged in LDS exactly as
+// in k_melcep, but instead of all rows [0, n_rows) the block walks that table's row runs (RowRuns), each clipped to the
+// slab's window.  The groups of 4 rows of the table's clipped runs are numbered through in run order and dealt to the
+// waves of the grid's blockIdx.y plane (RunGroups, mfx_dev.h): a group starts at a clipped run's first row + 4 k and never
+// spans two runs, only a run's last group is short.  spec and feat address absolute rows (one output).
+__global__ void __launch_bounds__(256) k_melcep_runs(MelcepParams p, RowRuns rr)
+{
+    const int table = blockIdx.y;
+    int run0, run1; // the table's runs that reach into the window (none: nothing to stage; uniform over the block)
+    if (!runs_in_window(rr, table, run0, run1)) return;
+    melcep_rows(p, table, p.feat, blockDim.x, [&](int64_t first, int64_t stride) { return RunGroups<4>(rr, run0, run1, first, stride); });
+}
 
 // ------------------------------------------------------------------------------------------------
 // delta: regression coefficients over time (deltacpu.cpp:16-29) with the edge handling of
 // MfccCpu::do_delta (mfcccpu.cpp:234-263) expressed as a clamped row accessor (Segment).
-// grid = (tiles, segments); one tile = kDeltaRows output rows.
+// grid = (tiles, segments); one tile = ROWS output rows.  The tile itself is delta_tile (mfx_tile_dev.h), typed for
+// float here (FAST16: cols <= 16) and for float4 in k_delta4.
 // ------------------------------------------------------------------------------------------------
-// FAST16: cols <= 16 -> a row is 16 consecutive work items (no integer division by a run-time
-// column count, 13..16 consecutive floats per row piece); otherwise the generic index split.
 template <bool FAST16, int ROWS>
 __global__ void __launch_bounds__(256) k_delta(DeltaParams p)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const Segment sg = p.inline_seg ? p.seg0 : p.segs[blockIdx.y];
-    const int r0 = blockIdx.x * ROWS;
-    if (r0 >= sg.n_out) return;
-    const int rows = min(ROWS, sg.n_out - r0);
-    const int cols = p.cols, l1 = p.l1, l2 = p.l2, D = l1 + l2;
-    const int cw = FAST16 ? 16 : cols; // row width in work items and in LDS
-    const int tid = threadIdx.x;
-    float *s_pad = smem;                             // [rows + 2D][cw]
-    float *s_d = smem + (ROWS + 2 * D) * cw;   // [rows + 2*l2][cw]
-    // (tile indices stay below 2^16: floor(i / cols) as a multiply-high instead of an integer division per element)
-    const uint32_t magic_c = 0xffffffffu / (uint32_t)(cols > 0 ? cols : 1) + 1;
-    auto split = [&](int i, int &rr, int &c) {
-        if (FAST16) {
-            rr = i >> 4;
-            c = i & 15;
-        } else {
-            rr = (int)__umulhi((uint32_t)i, magic_c);
-            c = i - rr * cols;
-        }
-    };
-
-    if (l1 > 0) {
-        const int n_pad = (rows + 2 * D) * cw;
-        for (int i = tid; i < n_pad; i += 256) {
-            int rr, c;
-            split(i, rr, c);
-            int sr = r0 + rr + sg.shift;
-            sr = max(sg.lo, min(sg.hi, sr));
-            s_pad[i] = (c < cols) ? p.src[(sg.src_row0 + sr) * (int64_t)p.src_pitch + c] : 0.f;
-        }
-        __syncthreads();
-        float den = 0.f;
-        for (int l = 1; l <= l1; ++l) den += (float)(l * l);
-        const float d1 = 2 * den, inv1 = 1.0f / d1;
-        const int n_d = (rows + 2 * l2) * cw;
-        for (int i = tid; i < n_d; i += 256) {
-            float num = 0.f;
-            for (int l = 1; l <= l1; ++l)
-                num = __builtin_fmaf((float)l, s_pad[i + (l1 + l) * cw] - s_pad[i + (l1 - l) * cw], num);
-            s_d[i] = delta_quot(num, d1, inv1);
-        }
-        __syncthreads();
-    }
-    float *s_dd = s_d + (ROWS + 2 * l2) * cw;  // [rows][cw]
-    if (l2 > 0) {
-        float den2 = 0.f;
-        for (int l = 1; l <= l2; ++l) den2 += (float)(l * l);
-        const float d2 = 2 * den2, inv2 = 1.0f / d2;
-        const int n_dd = rows * cw;
-        for (int i = tid; i < n_dd; i += 256) {
-            float num = 0.f;
-            for (int l = 1; l <= l2; ++l)
-                num = __builtin_fmaf((float)l, s_d[i + (l2 + l) * cw] - s_d[i + (l2 - l) * cw], num);
-            s_dd[i] = delta_quot(num, d2, inv2);
-        }
-        __syncthreads();
-    }
-    // The tile's output rows are one contiguous block of rows * width floats: write it with
-    // consecutive threads on consecutive addresses (whole cache lines), statics included.
-    const int width = p.out_pitch == cols * (l2 > 0 ? 3 : l1 > 0 ? 2 : 1) ? p.out_pitch : 0;
-    const int stat_row = sg.static_off - sg.shift; // row of s_pad that holds the static part of output row 0
-    if (width > 0 && l1 > 0) {
-        float *obase = p.out + (sg.out_row0 + r0) * (int64_t)p.out_pitch;
-        const uint32_t magic = 0xffffffffu / (uint32_t)width + 1; // floor(i / width) for i < 2^16
-        const int n_o = rows * width;
-        for (int i = tid; i < n_o; i += 256) {
-            const int rr = (int)__umulhi((uint32_t)i, magic);
-            const int cc = i - rr * width;
-            float v;
-            if (cc < cols)
-                v = s_pad[(rr + stat_row) * cw + cc];
-            else if (cc < 2 * cols)
-                v = s_d[(rr + l2) * cw + cc - cols];
-            else
-                v = s_dd[rr * cw + cc - 2 * cols];
-            obase[i] = v;
-        }
-        return;
-    }
-    // generic fallback (row pitch wider than the feature row, or statics only)
-    const int n_o = rows * cw;
-    for (int i = tid; i < n_o; i += 256) {
-        int rr, c;
-        split(i, rr, c);
-        if (c >= cols) continue;
-        float *orow = p.out + (sg.out_row0 + r0 + rr) * (int64_t)p.out_pitch;
-        orow[c] = p.src[(sg.src_row0 + r0 + rr + sg.static_off) * (int64_t)p.src_pitch + c];
-        if (l1 > 0) {
-            orow[cols + c] = s_d[i + l2 * cw];
-            if (l2 > 0) orow[2 * cols + c] = s_dd[i];
-        }
-    }
+    delta_tile<float, FAST16, ROWS>(p, smem);
 }
 
 // The same stage for wide rows whose column count is a multiple of 4 (BASELINE configs[4]: 40 columns, 120-float rows): a
@@ -150,82 +120,7 @@ template <int ROWS>
 __global__ void __launch_bounds__(256) k_delta4(DeltaParams p)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const Segment sg = p.inline_seg ? p.seg0 : p.segs[blockIdx.y];
-    const int r0 = blockIdx.x * ROWS;
-    if (r0 >= sg.n_out) return;
-    const int rows = min(ROWS, sg.n_out - r0);
-    const int l1 = p.l1, l2 = p.l2, D = l1 + l2;
-    const int q = p.cols >> 2;                       // 16-byte words per group of columns
-    const int tid = threadIdx.x;
-    float4 *s_pad = (float4 *)smem;                  // [rows + 2 D][q]
-    float4 *s_d = s_pad + (ROWS + 2 * D) * q;        // [rows + 2 l2][q]
-    float4 *s_dd = s_d + (ROWS + 2 * l2) * q;        // [rows][q]
-    const uint32_t magic_q = 0xffffffffu / (uint32_t)q + 1; // floor(i / q) for i < 2^16
-    {
-        const int n_pad = (rows + 2 * D) * q;
-        for (int i = tid; i < n_pad; i += 256) {
-            const int rr = (int)__umulhi((uint32_t)i, magic_q), c = i - rr * q;
-            int sr = r0 + rr + sg.shift;
-            sr = max(sg.lo, min(sg.hi, sr));
-            s_pad[i] = ((const float4 *)(p.src + (sg.src_row0 + sr) * (int64_t)p.src_pitch))[c];
-        }
-    }
-    __syncthreads();
-    {
-        float den = 0.f;
-        for (int l = 1; l <= l1; ++l) den += (float)(l * l);
-        const float d1 = 2 * den, inv1 = 1.0f / d1;
-        const int n_d = (rows + 2 * l2) * q;
-        for (int i = tid; i < n_d; i += 256) {
-            float4 num = make_float4(0.f, 0.f, 0.f, 0.f);
-            for (int l = 1; l <= l1; ++l) {
-                const float4 a = s_pad[i + (l1 + l) * q], b = s_pad[i + (l1 - l) * q];
-                num.x = __builtin_fmaf((float)l, a.x - b.x, num.x);
-                num.y = __builtin_fmaf((float)l, a.y - b.y, num.y);
-                num.z = __builtin_fmaf((float)l, a.z - b.z, num.z);
-                num.w = __builtin_fmaf((float)l, a.w - b.w, num.w);
-            }
-            s_d[i] = make_float4(delta_quot(num.x, d1, inv1), delta_quot(num.y, d1, inv1), delta_quot(num.z, d1, inv1),
-                                 delta_quot(num.w, d1, inv1));
-        }
-    }
-    __syncthreads();
-    if (l2 > 0) {
-        float den2 = 0.f;
-        for (int l = 1; l <= l2; ++l) den2 += (float)(l * l);
-        const float d2 = 2 * den2, inv2 = 1.0f / d2;
-        const int n_dd = rows * q;
-        for (int i = tid; i < n_dd; i += 256) {
-            float4 num = make_float4(0.f, 0.f, 0.f, 0.f);
-            for (int l = 1; l <= l2; ++l) {
-                const float4 a = s_d[i + (l2 + l) * q], b = s_d[i + (l2 - l) * q];
-                num.x = __builtin_fmaf((float)l, a.x - b.x, num.x);
-                num.y = __builtin_fmaf((float)l, a.y - b.y, num.y);
-                num.z = __builtin_fmaf((float)l, a.z - b.z, num.z);
-                num.w = __builtin_fmaf((float)l, a.w - b.w, num.w);
-            }
-            s_dd[i] = make_float4(delta_quot(num.x, d2, inv2), delta_quot(num.y, d2, inv2), delta_quot(num.z, d2, inv2),
-                                  delta_quot(num.w, d2, inv2));
-        }
-        __syncthreads();
-    }
-    // the tile's output rows are one contiguous block: consecutive threads write consecutive 16-byte words, statics included
-    const int wq = q * (l2 > 0 ? 3 : 2);
-    const int stat_row = sg.static_off - sg.shift;
-    float4 *obase = (float4 *)(p.out + (sg.out_row0 + r0) * (int64_t)p.out_pitch);
-    const uint32_t magic_w = 0xffffffffu / (uint32_t)wq + 1;
-    const int n_o = rows * wq;
-    for (int i = tid; i < n_o; i += 256) {
-        const int rr = (int)__umulhi((uint32_t)i, magic_w), cc = i - rr * wq;
-        float4 v;
-        if (cc < q)
-            v = s_pad[(rr + stat_row) * q + cc];
-        else if (cc < 2 * q)
-            v = s_d[(rr + l2) * q + cc - q];
-        else
-            v = s_dd[rr * q + cc - 2 * q];
-        obase[i] = v;
-    }
+    delta_tile<float4, false, ROWS>(p, (float4 *)smem);
 }
 
 // Delta stage from the compact statics (pitch 16) to whole output rows: the tile function of the fused
@@ -367,10 +262,9 @@ __global__ void __launch_bounds__(kNormSegThreads) k_norm_seg(NormParams p)
     float *stats = p.stats + (int64_t)blockIdx.y * p.group_stats_stride + (int64_t)blockIdx.x * 2 * cols;
     const bool in_lds = n_out <= p.chunks;
     const int total = n_out * cols;
-    // i / cols for i < 2^32 / cols (LDS-sized products).  cols == 1 would wrap the constant to 0: a one-column
-    // configuration (ceps_len 1 without c0, one filter without a DCT) takes the shift form instead
-    const uint32_t magic = cols > 1 ? 0xffffffffu / (uint32_t)cols + 1 : 0;
-    const auto row_of = [&](int i) -> int { return cols > 1 ? (int)__umulhi((uint32_t)i, magic) : i; };
+    // i / cols for the LDS-sized products (at most kNormSegLdsBytes / 4 elements)
+    const uint32_t magic = div_magic(cols);
+    const auto row_of = [&](int i) -> int { return div_small(i, cols, magic); };
     if (in_lds) { // 16 reads in flight per thread (a plain loop waits for every read before the next)
         const bool contig = p.pitch == cols;
         for (int i0 = tid; i0 < total; i0 += kNormSegThreads * 16) {
@@ -519,21 +413,12 @@ size_t melcep_lds_bytes(const MelcepParams &p, int n_waves)
 hipError_t launch_melcep(const MelcepParams &p, hipStream_t stream)
 {
     if (p.n_rows <= 0) return hipSuccess;
-    if (p.mag_floats < p.spec_pitch || (p.spec_pitch & 3) || (p.mag_floats & 3)) return hipErrorInvalidValue;
-    int nw = 4; // waves per block: as many of 4 as the LDS holds
-    while (nw > 1 && melcep_lds_bytes(p, nw) > 160 * 1024) nw >>= 1;
-    const size_t lds = melcep_lds_bytes(p, nw);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    if (hipError_t e = allow_dynamic_lds((const void *)k_melcep, lds); e != hipSuccess) return e;
-    int64_t blocks = ((p.n_rows + 3) / 4 + nw - 1) / nw;
-    // persistent blocks: as many as are resident at once (registers allow 6 blocks of 4 waves; see launch_front_generic)
-    int per_cu = blocks_per_cu((const void *)k_melcep, 64 * nw, lds, (int)std::min<size_t>(4, (160 * 1024) / lds)); // (per device and launch shape)
-    if (per_cu > 8) per_cu = 8;
-    const int cap = num_cus() * (per_cu < 1 ? 1 : per_cu);
-    if (blocks > cap) blocks = cap;
     const int tables = p.n_tables > 1 ? p.n_tables : 1;
-    if (tables > 65535) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_melcep, dim3((unsigned)blocks, (unsigned)tables), dim3(64 * nw), lds, stream, p);
+    if (!spec_rows_ok(p.mag_floats, p.spec_pitch) || tables > kGridYMax) return hipErrorInvalidValue;
+    ResidentGrid g;
+    if (hipError_t e = resident_grid((const void *)k_melcep, [&](int nw) { return melcep_lds_bytes(p, nw); }, (p.n_rows + 3) / 4, 1, g); e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(k_melcep, dim3(g.blocks, (unsigned)tables), dim3(64 * g.waves), g.lds, stream, p);
     return hipGetLastError();
 }
 
@@ -543,88 +428,56 @@ hipError_t launch_melcep_runs(const MelcepParams &p, const RowRuns &rr, const in
     int active = 0;
     const int64_t groups = run_groups_in_window(h_off, h_runs, tables, rr.row0, rr.rows, 4, active); // of the busiest table
     if (groups <= 0) return hipSuccess;
-    if (p.mag_floats < p.spec_pitch || (p.spec_pitch & 3) || (p.mag_floats & 3)) return hipErrorInvalidValue;
-    int nw = 4; // (as launch_melcep)
-    while (nw > 1 && melcep_lds_bytes(p, nw) > 160 * 1024) nw >>= 1;
-    const size_t lds = melcep_lds_bytes(p, nw);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    if (hipError_t e = allow_dynamic_lds((const void *)k_melcep_runs, lds); e != hipSuccess) return e;
-    int per_cu = blocks_per_cu((const void *)k_melcep_runs, 64 * nw, lds, (int)std::min<size_t>(4, (160 * 1024) / lds));
-    if (per_cu > 8) per_cu = 8;
-    // the resident blocks are shared among the tables that have rows in this window (the others' blocks leave at once)
-    const int cap = (num_cus() * (per_cu < 1 ? 1 : per_cu) + active - 1) / active;
-    const int64_t blocks = std::min<int64_t>((groups + nw - 1) / nw, cap);
-    if (tables > 65535) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_melcep_runs, dim3((unsigned)blocks, (unsigned)tables), dim3(64 * nw), lds, stream, p, rr);
+    if (!spec_rows_ok(p.mag_floats, p.spec_pitch) || tables > kGridYMax) return hipErrorInvalidValue;
+    ResidentGrid g;
+    if (hipError_t e = resident_grid((const void *)k_melcep_runs, [&](int nw) { return melcep_lds_bytes(p, nw); }, groups, active, g); e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(k_melcep_runs, dim3(g.blocks, (unsigned)tables), dim3(64 * g.waves), g.lds, stream, p, rr);
     return hipGetLastError();
 }
 
-#ifndef MFX_DELTA_WIDE_ROWS_V
-#define MFX_DELTA_WIDE_ROWS_V 32
-#endif
 hipError_t launch_delta(const DeltaParams &p, hipStream_t stream)
 {
     if (p.n_segs <= 0 || p.tiles_per_seg_max <= 0) return hipSuccess;
     const int D = p.l1 + p.l2;
     const int groups = p.l2 > 0 ? 3 : 2;
-    if (p.cols <= 16 && p.l1 > 0 && D <= 16 && p.src_pitch == 16 && p.out_pitch == p.cols * groups &&
-        ((uintptr_t)p.out & 15) == 0 && ((uintptr_t)p.src & 15) == 0) {
-        const size_t lds16 = (size_t)delta_wave_lds_floats(p.l1, p.l2) * sizeof(float);
-        const bool u33 = p.l1 == 3 && p.l2 == 3;
-        const int tiles_x = (p.tiles_per_seg_max + kDelta16TilesPerBlock - 1) / kDelta16TilesPerBlock;
-        for (int s0 = 0; s0 < p.n_segs; s0 += 65535) {
-            DeltaParams q = p;
-            q.segs = p.segs + s0;
-            q.n_segs = (p.n_segs - s0) < 65535 ? (p.n_segs - s0) : 65535;
-            if (u33)
-                hipLaunchKernelGGL((k_delta16<3, 3>), dim3(tiles_x, q.n_segs), dim3(256), lds16, stream, q);
-            else
-                hipLaunchKernelGGL((k_delta16<0, 0>), dim3(tiles_x, q.n_segs), dim3(256), lds16, stream, q);
-        }
-        return hipGetLastError();
+    const bool whole_rows = p.out_pitch == p.cols * groups && ((uintptr_t)p.out & 15) == 0 && ((uintptr_t)p.src & 15) == 0;
+    const auto tile_lds = [&](int rows, int cw) { return (size_t)((rows + 2 * D) + (rows + 2 * p.l2) + rows) * cw * sizeof(float); };
+    constexpr int R4 = MFX_DELTA_WIDE_ROWS_V, RW = MFX_DELTA_WIDE_ROWS;
+    const void *fn;
+    int rows_t = kDeltaRows; // output rows per block
+    size_t lds;
+    if (p.cols <= 16 && p.l1 > 0 && D <= 16 && p.src_pitch == 16 && whole_rows) {
+        fn = p.l1 == 3 && p.l2 == 3 ? (const void *)k_delta16<3, 3> : (const void *)k_delta16<0, 0>;
+        rows_t = kDelta16TilesPerBlock * kDeltaRows;
+        lds = (size_t)delta_wave_lds_floats(p.l1, p.l2) * sizeof(float);
+    } else if (p.cols > 16 && (p.cols & 3) == 0 && p.l1 > 0 && (p.src_pitch & 3) == 0 && whole_rows && tile_lds(R4, p.cols) <= 64 * 1024) {
+        // wide rows in whole 16-byte words: the vectorised form (C5: k_delta 0.052 ms -> see profiles/r03)
+        fn = (const void *)k_delta4<R4>;
+        rows_t = R4;
+        lds = tile_lds(R4, p.cols);
+    } else if (p.cols <= 16) {
+        fn = (const void *)k_delta<true, kDeltaRows>;
+        lds = tile_lds(kDeltaRows, 16);
+    } else { // wide rows: tiles of MFX_DELTA_WIDE_ROWS output rows (less LDS per block: more blocks per CU in flight)
+        fn = (const void *)k_delta<false, RW>;
+        rows_t = RW;
+        lds = tile_lds(RW, p.cols);
     }
-    // wide rows in whole 16-byte words: the vectorised form (C5: k_delta 0.052 ms -> see profiles/r03)
-    if (p.cols > 16 && (p.cols & 3) == 0 && p.l1 > 0 && (p.src_pitch & 3) == 0 && p.out_pitch == p.cols * groups &&
-        ((uintptr_t)p.out & 15) == 0 && ((uintptr_t)p.src & 15) == 0) {
-        constexpr int R4 = MFX_DELTA_WIDE_ROWS_V;
-        const size_t lds4 = (size_t)((R4 + 2 * D) + (R4 + 2 * p.l2) + R4) * p.cols * sizeof(float);
-        if (lds4 <= 64 * 1024) {
-            const int tiles_x4 = p.tiles_per_seg_max * (kDeltaRows / R4);
-            for (int s0 = 0; s0 < p.n_segs; s0 += 65535) {
-                DeltaParams qd = p;
-                qd.segs = p.segs + s0;
-                qd.n_segs = (p.n_segs - s0) < 65535 ? (p.n_segs - s0) : 65535;
-                hipLaunchKernelGGL((k_delta4<R4>), dim3(tiles_x4, qd.n_segs), dim3(256), lds4, stream, qd);
-            }
-            return hipGetLastError();
-        }
-    }
-    const bool fast16 = p.cols <= 16;
-    const int cw = fast16 ? 16 : p.cols;
-    // wide rows: tiles of MFX_DELTA_WIDE_ROWS output rows (less LDS per block: more blocks per CU in flight)
-#ifndef MFX_DELTA_WIDE_ROWS
-#define MFX_DELTA_WIDE_ROWS 32   // (C5: k_delta 0.072 -> 0.055 ms; 16 rows: 0.063)
-#endif
-    constexpr int RW = MFX_DELTA_WIDE_ROWS;
-    const int rows_t = fast16 ? kDeltaRows : RW;
-    const int tiles_x = p.tiles_per_seg_max * (kDeltaRows / rows_t);
-    const size_t lds = (size_t)((rows_t + 2 * D) + (rows_t + 2 * p.l2) + rows_t) * cw * sizeof(float);
-    if (hipError_t e = allow_dynamic_lds(fast16 ? (const void *)k_delta<true, kDeltaRows> : (const void *)k_delta<false, RW>, lds); e != hipSuccess)
-        return e;
-    // grid.y is limited to 65535: split the segment list
-    for (int s0 = 0; s0 < p.n_segs; s0 += 65535) {
+    if (hipError_t e = allow_dynamic_lds(fn, lds); e != hipSuccess) return e;
+    const int tiles_x = (int)(((int64_t)p.tiles_per_seg_max * kDeltaRows + rows_t - 1) / rows_t);
+    return for_seg_slices(p.n_segs, [&](int s0, int n) {
         DeltaParams q = p;
         q.segs = p.segs + s0;
-        q.n_segs = (p.n_segs - s0) < 65535 ? (p.n_segs - s0) : 65535;
-        if (fast16)
-            hipLaunchKernelGGL((k_delta<true, kDeltaRows>), dim3(tiles_x, q.n_segs), dim3(256), lds, stream, q);
-        else
-            hipLaunchKernelGGL((k_delta<false, RW>), dim3(tiles_x, q.n_segs), dim3(256), lds, stream, q);
-    }
-    return hipGetLastError();
+        q.n_segs = n;
+        return launch_kernel(fn, dim3(tiles_x, n), dim3(256), lds, stream, q);
+    });
 }
 
 static int norm_chunks(int max_rows) { return max_rows <= kNormChunkRows ? 1 : (max_rows + kNormChunkRows - 1) / kNormChunkRows; }
+
+// the statistics of a slice's segments lie s0 segments further on
+static void norm_slice_stats(NormParams &q, int s0) { q.stats += (int64_t)s0 * 2 * q.cols; }
 
 hipError_t launch_norm_stats(const NormParams &p, hipStream_t stream)
 {
@@ -632,17 +485,16 @@ hipError_t launch_norm_stats(const NormParams &p, hipStream_t stream)
     if (p.cols > 256) return hipErrorInvalidValue;
     const int chunks = norm_chunks(p.max_rows);
     if (chunks > 1 && !p.partial) return hipErrorInvalidValue;
-    for (int s0 = 0; s0 < p.n_segs; s0 += 65535) {
+    return for_seg_slices(p.n_segs, [&](int s0, int n) {
         NormParams q = p;
         q.segs = p.segs + s0;
-        q.stats = p.stats + (int64_t)s0 * 2 * p.cols;
-        q.n_segs = (p.n_segs - s0) < 65535 ? (p.n_segs - s0) : 65535;
+        q.n_segs = n;
+        norm_slice_stats(q, s0);
         q.chunks = chunks;
         if (chunks > 1) q.partial = p.partial + (int64_t)s0 * chunks * 4 * p.cols;
-        hipLaunchKernelGGL(k_norm_stats, dim3(chunks, q.n_segs), dim3(256), 0, stream, q);
-        if (chunks > 1) hipLaunchKernelGGL(k_norm_finalize, dim3(q.n_segs), dim3(256), 0, stream, q);
-    }
-    return hipGetLastError();
+        if (hipError_t e = launch_kernel((const void *)k_norm_stats, dim3(chunks, n), dim3(256), 0, stream, q); e != hipSuccess) return e;
+        return chunks > 1 ? launch_kernel((const void *)k_norm_finalize, dim3(n), dim3(256), 0, stream, q) : hipSuccess;
+    });
 }
 
 // stats + apply in one launch when every segment's rows fit one block's LDS (see k_norm_seg)
@@ -656,15 +508,14 @@ hipError_t launch_norm_fused(const NormParams &p, hipStream_t stream)
     if (p.n_segs <= 0) return hipSuccess;
     if (!norm_fused_fits(p.max_rows, p.cols)) return hipErrorInvalidValue;
     const size_t lds = (size_t)p.max_rows * p.cols * sizeof(float);
-    for (int s0 = 0; s0 < p.n_segs; s0 += 65535) {
+    return for_seg_slices(p.n_segs, [&](int s0, int n) { // (segments along grid.x here; the same limit serves)
         NormParams q = p;
         q.segs = p.segs + s0;
-        q.stats = p.stats + (int64_t)s0 * 2 * p.cols;
-        q.n_segs = (p.n_segs - s0) < 65535 ? (p.n_segs - s0) : 65535;
+        q.n_segs = n;
+        norm_slice_stats(q, s0);
         q.chunks = p.max_rows; // rows the block's LDS holds
-        hipLaunchKernelGGL(k_norm_seg, dim3(q.n_segs, p.groups > 1 ? p.groups : 1), dim3(kNormSegThreads), lds, stream, q);
-    }
-    return hipGetLastError();
+        return launch_kernel((const void *)k_norm_seg, dim3(n, p.groups > 1 ? p.groups : 1), dim3(kNormSegThreads), lds, stream, q);
+    });
 }
 
 hipError_t launch_copy_small(void *dst, const void *src, size_t bytes, hipStream_t stream)
@@ -693,14 +544,13 @@ hipError_t launch_norm_apply(const NormParams &p, hipStream_t stream)
     int64_t gx = ((int64_t)(p.max_rows > 0 ? p.max_rows : 1) * p.cols + 2047) / 2048;
     if (gx < 1) gx = 1;
     if (gx > 4096) gx = 4096;
-    for (int s0 = 0; s0 < p.n_segs; s0 += 65535) {
+    return for_seg_slices(p.n_segs, [&](int s0, int n) {
         NormParams q = p;
         q.segs = p.segs + s0;
-        q.stats = p.stats + (int64_t)s0 * 2 * p.cols;
-        q.n_segs = (p.n_segs - s0) < 65535 ? (p.n_segs - s0) : 65535;
-        hipLaunchKernelGGL(k_norm_apply, dim3((unsigned)gx, q.n_segs), dim3(256), 0, stream, q);
-    }
-    return hipGetLastError();
+        q.n_segs = n;
+        norm_slice_stats(q, s0);
+        return launch_kernel((const void *)k_norm_apply, dim3((unsigned)gx, n), dim3(256), 0, stream, q);
+    });
 }
 
 } // namespace mfx

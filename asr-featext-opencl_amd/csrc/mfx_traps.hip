@@ -25,8 +25,7 @@
 
 #include "mfx_dev.h"
 #include "mfx_launch.h"
-
-#include <algorithm>
+#include "mfx_tile_dev.h"
 
 namespace mfx {
 
@@ -41,9 +40,6 @@ __host__ __device__ inline int traps_operand_floats(int L, int K, bool valu)
 {
     return valu ? L * traps_kp(K) : ((K + 15) >> 4) * traps_steps(L) * 64;
 }
-
-// floor(i / d) for i < 2^16 as a multiply-high; magic = 0xffffffff / d + 1 (which wraps to 0 at d = 1)
-__device__ __forceinline__ int div_small(int i, int d, uint32_t magic) { return d == 1 ? i : (int)__umulhi((uint32_t)i, magic); }
 
 // LDS: s_out [R][M K] | operands | s_x [M][RX]
 template <bool VALU, int KP>
@@ -67,7 +63,7 @@ __global__ void __launch_bounds__(256) k_traps(TrapsParams p)
     for (int i = tid; i < nop; i += 256) s_b[i] = p.operands[i];
     {   // rows r0 - H .. r0 + R + H - 1 of the utterance, clamped to it; zeros behind them
         const int n_ctx = R + L - 1;
-        const uint32_t magic = 0xffffffffu / (uint32_t)M + 1; // floor(i / M) for i < 2^16 (RX * M <= 181 * 256)
+        const uint32_t magic = div_magic(M); // floor(i / M) for i < 2^16 (RX * M <= 181 * 256)
         const int n = RX * M;
         for (int i = tid; i < n; i += 256) {
             const int rr = div_small(i, M, magic);
@@ -150,25 +146,7 @@ __global__ void __launch_bounds__(256) k_traps(TrapsParams p)
     }
     __syncthreads();
 
-    float *obase = p.out + (sg.out_row0 + r0) * (int64_t)p.out_pitch;
-    if ((cols & 3) == 0 && (p.out_pitch & 3) == 0 && ((uintptr_t)p.out & 15) == 0) {
-        const int c4 = cols >> 2;
-        const uint32_t magic = 0xffffffffu / (uint32_t)c4 + 1;
-        const int n = rows * c4;
-        for (int i = tid; i < n; i += 256) {
-            const int rr = div_small(i, c4, magic);
-            const int q = i - rr * c4;
-            *(float4 *)(obase + rr * (int64_t)p.out_pitch + 4 * q) = *(const float4 *)(s_out + rr * cols + 4 * q);
-        }
-    } else {
-        const uint32_t magic = 0xffffffffu / (uint32_t)cols + 1;
-        const int n = rows * cols;
-        for (int i = tid; i < n; i += 256) {
-            const int rr = div_small(i, cols, magic);
-            const int c = i - rr * cols;
-            obase[rr * (int64_t)p.out_pitch + c] = s_out[i];
-        }
-    }
+    tile_store_rows(s_out, cols, rows, p.out, sg.out_row0 + r0, p.out_pitch, tid);
 }
 
 } // namespace
@@ -181,15 +159,11 @@ size_t traps_lds_bytes(const TrapsParams &p, int tile_rows)
 }
 
 #ifndef MFX_TRAPS_LDS_TARGET
-#define MFX_TRAPS_LDS_TARGET (40 * 1024) // four blocks (16 waves) per CU where the shape allows
+#define MFX_TRAPS_LDS_TARGET kTileLdsTarget
 #endif
 int traps_tile_rows(const TrapsParams &p)
 {
-    for (int r : {64, 32, 16})
-        if (traps_lds_bytes(p, r) <= (size_t)MFX_TRAPS_LDS_TARGET) return r;
-    for (int r : {64, 32, 16})
-        if (traps_lds_bytes(p, r) <= 160 * 1024) return r;
-    return 0;
+    return tile_rows_for([&](int r) { return traps_lds_bytes(p, r); }, MFX_TRAPS_LDS_TARGET);
 }
 
 hipError_t launch_traps(const TrapsParams &p, hipStream_t stream)
@@ -208,23 +182,13 @@ hipError_t launch_traps(const TrapsParams &p, hipStream_t stream)
                                 : (const void *)k_traps<true, 32>;
     if (hipError_t e = allow_dynamic_lds(fn, lds); e != hipSuccess) return e;
     const int tiles_x = p.tiles_per_seg_max * (64 / R);
-    // grid.y is limited to 65535: split the segment list
-    for (int s0 = 0; s0 < p.n_segs; s0 += 65535) {
+    return for_seg_slices(p.n_segs, [&](int s0, int n) {
         TrapsParams q = p;
         q.tile_rows = R;
         q.segs = p.segs + s0;
-        q.n_segs = (p.n_segs - s0) < 65535 ? (p.n_segs - s0) : 65535;
-        const dim3 grid(tiles_x, q.n_segs);
-        if (!p.valu)
-            hipLaunchKernelGGL((k_traps<false, 0>), grid, dim3(256), lds, stream, q);
-        else if (kp == 4)
-            hipLaunchKernelGGL((k_traps<true, 4>), grid, dim3(256), lds, stream, q);
-        else if (kp == 16)
-            hipLaunchKernelGGL((k_traps<true, 16>), grid, dim3(256), lds, stream, q);
-        else
-            hipLaunchKernelGGL((k_traps<true, 32>), grid, dim3(256), lds, stream, q);
-    }
-    return hipGetLastError();
+        q.n_segs = n;
+        return launch_kernel(fn, dim3(tiles_x, n), dim3(256), lds, stream, q);
+    });
 }
 
 } // namespace mfx

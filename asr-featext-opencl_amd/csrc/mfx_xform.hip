@@ -28,6 +28,7 @@
 
 #include "mfx_dev.h"
 #include "mfx_launch.h"
+#include "mfx_tile_dev.h"
 
 namespace mfx {
 
@@ -44,9 +45,6 @@ __host__ __device__ inline int xform_ksteps(int in_dim, int out_dim)
 }
 // floats of the staged rows: R + left + right rows back to back, then the zeros the last row's padded taps read
 __host__ __device__ inline int xform_stage_floats(int R, int width, int ctx) { return (R + ctx) * width + 4; }
-
-// floor(i / d) for i < 2^16 as a multiply-high; magic = 0xffffffff / d + 1 (which wraps to 0 at d = 1)
-__device__ __forceinline__ int div_small(int i, int d, uint32_t magic) { return d == 1 ? i : (int)__umulhi((uint32_t)i, magic); }
 
 // LDS: s_out [R][out_dim] | operand buffers [2][ksteps][tiles][64] | s_y [(R + left + right) Wd + 4]
 template <bool VALU, int TM>
@@ -80,7 +78,7 @@ __global__ void __launch_bounds__(256) k_splice_affine(XformParams p)
     }
     {   // rows r0 - left .. r0 + R + right - 1 of the utterance, clamped to it; zeros behind them
         const int n = (R + ctx) * Wd;
-        const uint32_t magic = 0xffffffffu / (uint32_t)Wd + 1; // floor(i / Wd) for i < 2^16 (n < 160 KB / 4)
+        const uint32_t magic = div_magic(Wd); // floor(i / Wd) for i < 2^16 (n < 160 KB / 4)
         for (int i = tid; i < n; i += 256) {
             const int rr = div_small(i, Wd, magic);
             const int c = i - rr * Wd;
@@ -172,25 +170,7 @@ __global__ void __launch_bounds__(256) k_splice_affine(XformParams p)
     }
     __syncthreads();
 
-    float *obase = p.out + (sg.out_row0 + r0) * (int64_t)p.out_pitch;
-    if ((od & 3) == 0 && (p.out_pitch & 3) == 0 && ((uintptr_t)p.out & 15) == 0) {
-        const int c4 = od >> 2;
-        const uint32_t magic = 0xffffffffu / (uint32_t)c4 + 1;
-        const int n = rows * c4;
-        for (int i = tid; i < n; i += 256) {
-            const int rr = div_small(i, c4, magic);
-            const int q = i - rr * c4;
-            *(float4 *)(obase + rr * (int64_t)p.out_pitch + 4 * q) = *(const float4 *)(s_out + rr * od + 4 * q);
-        }
-    } else {
-        const uint32_t magic = 0xffffffffu / (uint32_t)od + 1;
-        const int n = rows * od;
-        for (int i = tid; i < n; i += 256) {
-            const int rr = div_small(i, od, magic);
-            const int c = i - rr * od;
-            obase[rr * (int64_t)p.out_pitch + c] = s_out[i];
-        }
-    }
+    tile_store_rows(s_out, od, rows, p.out, sg.out_row0 + r0, p.out_pitch, tid);
 }
 
 // accumulator tiles a wave carries at tile_rows rows per block, rounded up to an instantiated count
@@ -232,16 +212,11 @@ size_t xform_lds_bytes(const XformParams &p, int tile_rows)
 }
 
 #ifndef MFX_XFORM_LDS_TARGET
-#define MFX_XFORM_LDS_TARGET (40 * 1024) // four blocks (16 waves) per CU where the shape allows
+#define MFX_XFORM_LDS_TARGET kTileLdsTarget
 #endif
 int xform_tile_rows(const XformParams &p)
 {
-    if (!xform_shape_ok(p)) return 0;
-    for (int r : {64, 32, 16})
-        if (xform_lds_bytes(p, r) <= (size_t)MFX_XFORM_LDS_TARGET) return r;
-    for (int r : {64, 32, 16})
-        if (xform_lds_bytes(p, r) <= 160 * 1024) return r;
-    return 0;
+    return xform_shape_ok(p) ? tile_rows_for([&](int r) { return xform_lds_bytes(p, r); }, MFX_XFORM_LDS_TARGET) : 0;
 }
 
 hipError_t launch_xform(const XformParams &p, hipStream_t stream)
@@ -255,18 +230,15 @@ hipError_t launch_xform(const XformParams &p, hipStream_t stream)
     const void *fn = p.valu ? xform_fn<true>(tm) : xform_fn<false>(tm);
     if (hipError_t e = allow_dynamic_lds(fn, lds); e != hipSuccess) return e;
     const int tiles_x = p.tiles_per_seg_max * (64 / R);
-    // grid.y is limited to 65535: split the segment list
-    for (int s0 = 0; s0 < p.n_segs; s0 += 65535) {
+    return for_seg_slices(p.n_segs, [&](int s0, int n) {
         XformParams q = p;
         q.tile_rows = R;
         q.ksteps = xform_ksteps((p.left + p.right + 1) * p.width, p.out_dim);
         q.segs = p.segs + s0;
         if (p.seg_xf) q.seg_xf = p.seg_xf + s0;
-        q.n_segs = (p.n_segs - s0) < 65535 ? (p.n_segs - s0) : 65535;
-        void *args[] = {&q};
-        if (hipError_t e = hipLaunchKernel(fn, dim3(tiles_x, q.n_segs), dim3(256), args, lds, stream); e != hipSuccess) return e;
-    }
-    return hipGetLastError();
+        q.n_segs = n;
+        return launch_kernel(fn, dim3(tiles_x, n), dim3(256), lds, stream, q);
+    });
 }
 
 } // namespace mfx
