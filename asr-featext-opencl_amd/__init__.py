@@ -18,6 +18,10 @@ from .mfcc import (  # noqa: F401
     METHOD_MFCC,
     METHOD_PLP,
     METHOD_TRAPS,
+    METHOD_STFT_LOGMEL,
+    LOGMEL_WHISPER,
+    LOGMEL_LOG10,
+    LOGMEL_LN,
     NORM_CMN,
     NORM_CVN,
     NORM_MINMAX,
@@ -40,6 +44,10 @@ from .mfcc import (  # noqa: F401
     VAD_SELECT,
     VAD_PACK,
     host_traps_basis,
+    host_slaney_mel_table,
+    host_stft_basis,
+    stft_frame_count,
+    periodic_hann,
     host_xform_operands,
     KERNEL_TABLE,
     library_path,

@@ -143,6 +143,7 @@ int build_cep_tables(mfx_handle *h, const float *alphas, int n, CepTables &t, Me
 // own lane plans are derived here too.
 int refresh_mel(mfx_handle *h)
 {
+    if (h->stft) return MFX_OK; // (its one table does not depend on alpha)
     if (h->own.holds(&h->alpha, 1)) return MFX_OK;
     h->fused_ok = h->wplan_ok = h->wplan32_ok = false;
     MelTable t;
@@ -363,7 +364,7 @@ int launch_cepstra_runs(mfx_handle *h, const CepTables &t, const float *spec, fl
 extern "C" int mfx_abi_version(void) { return MFX_ABI_VERSION; }
 extern "C" int mfx_method_supported(int32_t method)
 {
-    return method == MFX_METHOD_MFCC || method == MFX_METHOD_PLP || method == MFX_METHOD_TRAPS ? 1 : 0;
+    return method == MFX_METHOD_MFCC || method == MFX_METHOD_PLP || method == MFX_METHOD_TRAPS || method == MFX_METHOD_STFT_LOGMEL ? 1 : 0;
 }
 
 extern "C" const char *mfx_status_string(int status)
@@ -411,6 +412,53 @@ struct HandleDeleter {
     void operator()(mfx_handle *h) const { mfx_destroy(h); }
 };
 
+// the limits of an STFT log-mel handle (include/mfx.h): everything sized from N, S and M fits k_stft_mel's LDS by them
+bool stft_config_ok(const mfx_config *cfg)
+{
+    const int N = cfg->window_size;
+    if (N < 32 || N > 512 || (N & 1) || (cfg->fft_size != 0 && cfg->fft_size != N)) return false;
+    if (cfg->shift < 1 || cfg->shift > N || cfg->num_banks < 1 || cfg->num_banks > 128) return false;
+    if (!(cfg->low_freq >= 0.f) || !(cfg->low_freq < cfg->high_freq) || !(cfg->high_freq <= cfg->sample_rate / 2)) return false;
+    if (cfg->ceps_len != 0 || cfg->want_c0 != 0 || cfg->dyn != MFX_DYN_NONE || cfg->norm != MFX_NORM_NONE || cfg->channels > 1) return false;
+    if (cfg->logmel_post < MFX_LOGMEL_WHISPER || cfg->logmel_post > MFX_LOGMEL_LN) return false;
+    return true;
+}
+
+// the rest of mfx_create for an STFT log-mel handle: geometry, the Slaney table, the LDS check; the basis waits for the window
+int create_stft(mfx_handle *h, bool planning, std::unique_ptr<mfx_handle, HandleDeleter> &owner, mfx_handle **out)
+{
+    const mfx_config &cfg = h->cfg;
+    h->W2 = h->W;
+    h->input_window_limit = estimated_window_count_f32(cfg.input_buffer_size, h->W, h->S);
+    h->input_buffer_size = h->input_window_limit * h->S + h->W - h->S;
+    h->window_limit = h->input_window_limit + 2;
+    if (h->input_window_limit <= 0) return MFX_ERR_CONFIG;
+    h->cap_rows = h->window_limit + h->W / h->S + 4;
+    h->spec_pitch = ((h->W2 / 2 + 1) + 3) & ~3;
+    h->stft_R = stft_tile_rows(h->W, h->S, h->nb); // (16 frames fit for every shape inside the limits: 512 / 512 / 128 takes 74 KB then)
+    if (h->stft_R == 0) return MFX_ERR_CONFIG;
+    if (!planning) {
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.multiProcessorCount > 0) h->num_cus = prop.multiProcessorCount;
+        if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return MFX_ERR_DEVICE;
+        h->own_stream = true;
+    }
+    const int K1 = h->W / 2 + 1;
+    std::vector<float> dense((size_t)h->nb * K1), w;
+    std::vector<int32_t> meta((size_t)3 * h->nb);
+    build_slaney_mel(h->nb, h->W, cfg.sample_rate, cfg.low_freq, cfg.high_freq, dense.data(), meta.data(), meta.data() + h->nb);
+    for (int m = 0; m < h->nb; ++m) {
+        meta[(size_t)2 * h->nb + m] = (int32_t)w.size();
+        w.insert(w.end(), dense.begin() + (size_t)m * K1 + meta[m], dense.begin() + (size_t)m * K1 + meta[m] + meta[(size_t)h->nb + m]);
+    }
+    if (w.empty()) w.push_back(0.f); // (every band narrower than a bin: keep the buffer non-null)
+    if (h->upload(h->d_stft_melw, w) != hipSuccess || h->upload(h->d_stft_mel, meta) != hipSuccess ||
+        h->alloc(h->st.d_stats, (size_t)3 * 2 * h->cols) != hipSuccess)
+        return MFX_ERR_DEVICE;
+    *out = owner.release();
+    return MFX_OK;
+}
+
 int create_impl(const mfx_config *cfg, int hip_device, bool planning, mfx_handle **out)
 {
     if (!cfg || !out) return MFX_ERR_ARG;
@@ -437,6 +485,8 @@ int create_impl(const mfx_config *cfg, int hip_device, bool planning, mfx_handle
         if (cfg->traps_dct_len < 0 || traps_K > 32 || traps_K > traps_L) return MFX_ERR_CONFIG;
         if ((int64_t)cfg->num_banks * traps_K > 256) return MFX_ERR_CONFIG;
     }
+    const bool stft = cfg->method == MFX_METHOD_STFT_LOGMEL;
+    if (stft && !stft_config_ok(cfg)) return MFX_ERR_CONFIG;
 
     if (!planning) {
         int ndev = 0;
@@ -462,6 +512,7 @@ int create_impl(const mfx_config *cfg, int hip_device, bool planning, mfx_handle
     h->D = h->l1 + h->l2;
     h->dl = cfg->want_c0 ? cfg->ceps_len + 1 : cfg->ceps_len;
     h->traps = traps;
+    h->stft = stft;
     h->traps_L = traps ? traps_L : 0;
     h->traps_K = traps ? traps_K : 0;
     h->fcols = h->ceps > 0 ? h->dl : h->nb;
@@ -476,6 +527,7 @@ int create_impl(const mfx_config *cfg, int hip_device, bool planning, mfx_handle
         const int64_t rows = 3 * R + 2 * ((int64_t)h->l1 + h->l2) + 2 * (int64_t)h->l2;
         if (rows * cw * (int64_t)sizeof(float) > (int64_t)kLdsCap) return MFX_ERR_CONFIG;
     }
+    if (stft) return create_stft(h, planning, owner, out);
     h->W2 = (int)ceil_pow2((uint32_t)h->W);
     if (cfg->fft_size != 0) {
         if (cfg->fft_size < h->W || (cfg->fft_size & (cfg->fft_size - 1)) != 0) return MFX_ERR_CONFIG;
@@ -782,6 +834,7 @@ int launch_front(mfx_handle *h, FrontParams &p, FrontKind kind, bool aligned, co
 extern "C" const char *mfx_dominant_kernel_name(const mfx_handle *h)
 {
     if (!h) return "";
+    if (h->stft) return "k_stft_mel";
     switch (batch_front(h)) { // names as rocprofv3 prints them
     case kFront512:
     case kSpec512: return "k_front512";
@@ -809,6 +862,16 @@ extern "C" int mfx_set_window(mfx_handle *h, const float *window)
     MFX_DEVICE_ENTRY(h);
     if (!window) return fail(h, MFX_ERR_ARG, "invalid argument");
     HIP_TRY(h, hipSetDevice(h->device));
+    if (h->stft) { // the windowed basis as k_stft_mel streams it
+        std::vector<float> basis((size_t)2 * (h->W / 2 + 1) * h->W), ops;
+        build_stft_basis(h->W, window, basis.data());
+        build_stft_operands(basis.data(), h->W, kStftTB < (h->W / 2 + 16) / 16 ? kStftTB : (h->W / 2 + 16) / 16, ops);
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (h->batch.ov.stream2) HIP_TRY(h, hipStreamSynchronize(h->batch.ov.stream2));
+        HIP_TRY(h, h->upload(h->d_stft_ops, ops));
+        h->have_window = true;
+        return MFX_OK;
+    }
     std::vector<float> padded((size_t)h->W2, 0.f);
     std::memcpy(padded.data(), window, sizeof(float) * h->W);
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -842,6 +905,7 @@ extern "C" int64_t mfx_debug_read(mfx_handle *h, int kind, void *dst, int64_t ds
     if (hipSetDevice(h->device) != hipSuccess) return MFX_ERR_DEVICE;
     const void *src = nullptr;
     int64_t count = 0, esz = 4;
+    if (h->stft && kind != 8) return kind >= 0 && kind <= 7 ? 0 : MFX_ERR_ARG; // (none of those tables or blocks exists)
     switch (kind) {
     case 0:
         if (refresh_mel(h) != MFX_OK) return MFX_ERR_DEVICE;
@@ -1027,6 +1091,36 @@ extern "C" int64_t mfx_host_xform_operands(int32_t out_dim, int32_t in_dim, cons
         build_xform_operands(A, out_dim, in_dim, a, b, out);
     }
     return n;
+}
+
+extern "C" int64_t mfx_host_stft_lds_bytes(int32_t dft_size, int32_t shift, int32_t num_banks, int32_t *tile_rows)
+{
+    if (dft_size < 32 || dft_size > 512 || (dft_size & 1) || shift < 1 || shift > dft_size || num_banks < 1 || num_banks > 128) return MFX_ERR_ARG;
+    const int R = stft_tile_rows(dft_size, shift, num_banks);
+    if (tile_rows) *tile_rows = R;
+    return R > 0 ? (int64_t)stft_lds_bytes(dft_size, shift, num_banks, R) : MFX_ERR_CONFIG;
+}
+
+extern "C" int64_t mfx_host_stft_frame_count(int64_t samples, int32_t dft_size, int32_t shift)
+{
+    if (samples < 0 || dft_size < 32 || dft_size > 512 || (dft_size & 1) || shift < 1 || shift > dft_size) return MFX_ERR_ARG;
+    return stft_frame_count(samples, dft_size, shift);
+}
+
+extern "C" int mfx_host_stft_basis(int32_t dft_size, const float *window, float *cos_sin)
+{
+    if (dft_size < 32 || dft_size > 512 || (dft_size & 1) || !window || !cos_sin) return MFX_ERR_ARG;
+    build_stft_basis(dft_size, window, cos_sin);
+    return MFX_OK;
+}
+
+extern "C" int mfx_host_slaney_mel_table(int32_t num_banks, int32_t dft_size, float sample_rate, float low_freq, float high_freq,
+                                         float *weights, int32_t *beg, int32_t *len)
+{
+    if (num_banks < 1 || num_banks > 128 || dft_size < 32 || dft_size > 512 || (dft_size & 1) || !weights || !beg || !len) return MFX_ERR_ARG;
+    if (!(sample_rate > 0.f) || !(low_freq >= 0.f) || !(low_freq < high_freq) || !(high_freq <= sample_rate / 2)) return MFX_ERR_ARG;
+    build_slaney_mel(num_banks, dft_size, sample_rate, low_freq, high_freq, weights, beg, len);
+    return MFX_OK;
 }
 
 extern "C" int64_t mfx_host_frame_count(int64_t samples, int32_t window_size, int32_t shift)

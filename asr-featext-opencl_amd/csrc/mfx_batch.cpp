@@ -162,6 +162,28 @@ RunMode decide_mode(const mfx_handle *h, FrontParams &p, float *d_out, bool whol
 int run_front(mfx_handle *h, FrontParams &p, const RunMode &m, int u0, int u1, int32_t c0, int32_t c1)
 {
     BatchState &B = h->batch;
+    if (h->stft) { // k_stft_mel over the range's blocks, then (WHISPER) the clamp by the utterance's maximum, in place
+        StftParams sp{};
+        sp.pcm = p.pcm;
+        sp.chunks = B.d_stft_chunks.p + c0;
+        sp.n_chunks = c1 - c0;
+        sp.chunk_first = c0;
+        sp.N = h->W, sp.S = h->S, sp.M = h->nb;
+        sp.post = h->cfg.logmel_post;
+        sp.tile_rows = h->stft_R;
+        sp.operands = h->d_stft_ops.p;
+        sp.mel_w = h->d_stft_melw.p;
+        sp.mel_beg = h->d_stft_mel.p, sp.mel_len = h->d_stft_mel.p + h->nb, sp.mel_off = h->d_stft_mel.p + 2 * h->nb;
+        sp.out = p.feat;
+        sp.out_pitch = p.feat_pitch;
+        sp.blk_max = B.d_stft_max.p;
+        {
+            ProfScope ps(h);
+            HIP_TRY(h, launch_stft(sp, h->stream));
+        }
+        if (sp.post == MFX_LOGMEL_WHISPER) HIP_TRY(h, launch_stft_post(sp, h->stream));
+        return MFX_OK;
+    }
     if (m.split_tail && B.ov.tail_pending[m.sb]) // tail of batch i-2 still reads this scratch buffer
         HIP_TRY(h, hipStreamWaitEvent(h->stream, B.ov.ev_tail[m.sb], 0));
     if (m.fuse) {

@@ -15,6 +15,7 @@ extern "C" int mfx_batch_set_alphas(mfx_handle *h, const float *alphas, int32_t 
         h->batch.va.drop();
         return MFX_OK;
     }
+    if (h->stft) return fail(h, MFX_ERR_CONFIG, "mfx_batch_set_alphas: an STFT log-mel handle has no warped Slaney table");
     if (!alphas || n_utt != h->batch.n_utt) return fail(h, MFX_ERR_ARG, "one warp factor per planned utterance");
     for (int u = 0; u < n_utt; ++u)
         if (!(alphas[u] > 0.f)) return fail(h, MFX_ERR_ARG, "alpha must be positive");

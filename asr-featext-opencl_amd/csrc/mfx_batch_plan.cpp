@@ -9,7 +9,7 @@ using namespace mfx;
 extern "C" int64_t mfx_batch_frames(const mfx_handle *h, int64_t samples)
 {
     if (!h) return MFX_ERR_ARG;
-    int64_t t = frame_count(samples, h->W, h->S);
+    int64_t t = utt_frame_count(h, samples);
     return t > 0 ? t : 0;
 }
 
@@ -217,7 +217,7 @@ int plan_batch(mfx_handle *h, int32_t n_utt, const int64_t *offsets, const int64
     if (n_utt < 0 || (n_utt > 0 && (!offsets || !lengths))) return fail(h, MFX_ERR_ARG, "invalid argument");
     for (int u = 0; u < n_utt; ++u) { // (the whole list before anything of the previous plan is touched)
         if (offsets[u] < 0 || lengths[u] < 0) return fail(h, MFX_ERR_ARG, "negative utterance offset/length");
-        if (frame_count(lengths[u], h->W, h->S) > 0x7fffffff) return fail(h, MFX_ERR_ARG, "utterance too long");
+        if (utt_frame_count(h, lengths[u]) > 0x7fffffff) return fail(h, MFX_ERR_ARG, "utterance too long");
     }
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -229,6 +229,9 @@ int plan_batch(mfx_handle *h, int32_t n_utt, const int64_t *offsets, const int64
     h->batch.utt_row.resize(n_utt);
     h->batch.h_chunks.clear();
     h->batch.chunk_utt.clear();
+    h->batch.h_stft_chunks.clear();
+    // (STFT log-mel: a chunk is the run of frames one block of k_stft_mel takes)
+    const int chunk_frames = h->stft ? h->stft_R : kChunkFrames;
     std::vector<Segment> segs((size_t)n_utt);
     std::vector<int64_t> &T_of = h->batch.utt_frames;
     T_of.assign((size_t)n_utt, 0);
@@ -236,17 +239,29 @@ int plan_batch(mfx_handle *h, int32_t n_utt, const int64_t *offsets, const int64
     int tiles_max = 0;
     bool aligned = (h->S % 2) == 0;
     for (int u = 0; u < n_utt; ++u) {
-        const int64_t T = std::max<int64_t>(frame_count(lengths[u], h->W, h->S), 0);
+        const int64_t T = std::max<int64_t>(utt_frame_count(h, lengths[u]), 0);
         h->batch.utt_row[u] = row;
         T_of[u] = T;
         if (out_rows) out_rows[u] = row;
         if (offsets[u] & 1) aligned = false;
-        for (int64_t t0 = 0; t0 < T; t0 += kChunkFrames) {
+        if (h->stft && (T + chunk_frames - 1) / chunk_frames + (int64_t)h->batch.h_chunks.size() > 0x7ffffff0) {
+            h->batch.n_utt = 0, h->batch.total_rows = 0;
+            return fail(h, MFX_ERR_ARG, "batch too long");
+        }
+        for (int64_t t0 = 0; t0 < T; t0 += chunk_frames) {
             Chunk c;
             c.pcm_off = offsets[u] + t0 * h->S;
             c.out_row = row + t0;
-            c.n_frames = (int32_t)std::min<int64_t>(kChunkFrames, T - t0);
+            c.n_frames = (int32_t)std::min<int64_t>(chunk_frames, T - t0);
             c.pad = 0;
+            if (h->stft) {
+                StftChunk sc{};
+                sc.utt_off = offsets[u], sc.utt_len = lengths[u], sc.out_row = c.out_row;
+                sc.t0 = (int32_t)t0, sc.n_frames = c.n_frames;
+                sc.utt_chunk0 = (int32_t)(h->batch.h_chunks.size() - (size_t)(t0 / chunk_frames));
+                sc.utt_chunks = (int32_t)((T + chunk_frames - 1) / chunk_frames);
+                h->batch.h_stft_chunks.push_back(sc);
+            }
             h->batch.h_chunks.push_back(c);
             h->batch.chunk_utt.push_back(u);
         }
@@ -291,6 +306,10 @@ int plan_batch(mfx_handle *h, int32_t n_utt, const int64_t *offsets, const int64
         h->batch.mel_pitch = (h->nb + 3) & ~3;
         const size_t need = (size_t)row * h->batch.mel_pitch;
         if (h->batch.d_logmel.n < need) HIP_TRY(h, h->batch.d_logmel.alloc(need));
+    }
+    if (h->stft) { // the blocks' descriptors and their slots for the utterance maximum (grown, never shrunk)
+        HIP_TRY(h, h->upload(h->batch.d_stft_chunks, h->batch.h_stft_chunks));
+        if (h->batch.d_stft_max.n < h->batch.h_stft_chunks.size()) HIP_TRY(h, h->batch.d_stft_max.alloc(h->batch.h_stft_chunks.size()));
     }
     rcf = size_static16(h);
     h->batch.planned = rcf == MFX_OK;

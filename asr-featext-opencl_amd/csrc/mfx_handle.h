@@ -158,6 +158,9 @@ struct BatchState {
     DevBuf<float> d_stats, d_spec_slab;
     DevBuf<float> d_logmel;      // TRAPS: log mel rows [total_rows][mel_pitch] between the front end and k_traps
     int mel_pitch = 0;
+    std::vector<mfx::StftChunk> h_stft_chunks; // STFT log-mel: one per entry of h_chunks (which keep the utterance slicing working)
+    DevBuf<mfx::StftChunk> d_stft_chunks;
+    DevBuf<float> d_stft_max;    // [chunks] the blocks' largest log values (k_stft_post)
     DevBuf<float> d_static16[2]; // compact [rows][16] statics between front end and delta (double buffered for overlap)
     int tiles_max = 0;
     bool aligned = true;                 // frames on aligned sample pairs (fill_front / choose_front read it)
@@ -380,6 +383,12 @@ struct mfx_handle {
     int lpc = 0;       // PLP model order (lpc_order, 0 -> 8)
     bool traps = false; // mfx_config.method == MFX_METHOD_TRAPS: fbank front end -> scratch -> k_traps; batch entries only
     int traps_L = 0, traps_K = 0; // trajectory length, coefficients kept (defaults applied)
+    // mfx_config.method == MFX_METHOD_STFT_LOGMEL: k_stft_mel (+ k_stft_post) IS the front end; batch entries only.  W is the
+    // DFT length N (W2 == W), nb the output width; none of the FFT / mel / DCT tables below exist on such a handle
+    bool stft = false;
+    int stft_R = 0;                      // frames per block of k_stft_mel (stft_tile_rows)
+    DevBuf<float> d_stft_ops, d_stft_melw; // basis operands (mfx_set_window builds them); the mel rows' spans back to back
+    DevBuf<int32_t> d_stft_mel;          // [3][nb]: beg, len, first weight of every row
     float alpha = 1.f;
     bool have_window = false;
 
@@ -483,6 +492,9 @@ inline int fail_hip(mfx_handle *h, hipError_t e, const char *what)
 // top of every streaming entry: TRAPS handles have none (the streaming state machine's context is D frames, not H)
 #define MFX_STREAM_ENTRY(h)                                                                                                  \
     do {                                                                                                                     \
+        if ((h)->stft)                                                                                                       \
+            return fail((h), MFX_ERR_STATE,                                                                                  \
+                        "STFT log-mel handles have batch entries only: use mfx_batch_plan + mfx_batch_run_device / mfx_batch_run_host"); \
         if ((h)->traps)                                                                                                      \
             return fail((h), MFX_ERR_STATE,                                                                                  \
                         "TRAPS handles have no streaming entries: use mfx_batch_plan + mfx_batch_run_device / mfx_batch_run_host"); \
@@ -560,6 +572,11 @@ int plan_batch(mfx_handle *h, int32_t n_utt, const int64_t *offsets, const int64
 int size_static16(mfx_handle *h);
 // row width of the batch entries' output: out_dim while a transform is in force, else `width`
 int batch_out_width(const mfx_handle *h);
+// frames of an utterance of `samples` samples per channel on this handle (may be <= 0 for the framed methods: callers clamp)
+inline int64_t utt_frame_count(const mfx_handle *h, int64_t samples)
+{
+    return h->stft ? mfx::stft_frame_count(samples, h->W, h->S) : mfx::frame_count(samples, h->W, h->S);
+}
 // normalised columns of a speaker list and of the online normaliser: the whole row after the deltas, else the statics
 inline int spk_wn(const mfx_handle *h) { return h->cfg.norm_after_dyn ? h->width : h->cols; }
 // mfx_batch_set_online_norm / mfx_sessions_set_online_norm: the checks the two setters share (MFX_OK, or the status with the

@@ -1,4 +1,4 @@
-// mfx_kernels.h -- launch interface of the gfx950 kernels (implemented in mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip, mfx_plp.hip, mfx_traps.hip, mfx_xform.hip, mfx_sessions.hip, mfx_resample.hip, mfx_speakers.hip, mfx_vad.hip, mfx_onorm.hip: one translation unit per kernel family).
+// mfx_kernels.h -- launch interface of the gfx950 kernels (implemented in mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip, mfx_plp.hip, mfx_traps.hip, mfx_xform.hip, mfx_sessions.hip, mfx_resample.hip, mfx_speakers.hip, mfx_vad.hip, mfx_onorm.hip, mfx_stft.hip: one translation unit per kernel family).
 //
 // Kernel inventory and the reference stage each one replaces:
 //   spectrum512 / fused512   segmenter.cl kernelSegmentWindow + AppleFFT fft0 + mfcc.cl kernelTranspose
@@ -16,6 +16,8 @@
 //                            reference hands every frame to its consumer)
 //   onorm_*                  online (causal, sliding-window) CMN / CVN of the batch and session entries (no reference analogue: its
 //                            NormalizerCPU keeps one block's statistics)
+//   stft_mel / stft_post     the STFT log-mel front end: exact-length DFT of centred frames on the matrix pipe, power, Slaney mel, log;
+//                            the clamp by the utterance's maximum and the map (no reference analogue: a neural recogniser's input)
 //   delta                    delta.cl kernelDelta x2 + the staging copies of mfccopencl.cpp:360-387
 //   norm_stats / norm_apply  norm.cl kernelSum + kernelFinalizeSum / kernelNormalize
 #pragma once
@@ -438,6 +440,42 @@ struct OnormSessParams {
     double *state;         // [n_sessions][8][Wn]: lead O (v, q), lead I (v, q), trail O (v, q), trail I (v, q)
     float *ring;           // [n_sessions][window][Wn] the last `window` raw rows (null when window == 0)
 };
+
+// STFT log-mel front end (mfx_stft.hip; DESIGN.md, "STFT log-mel"): one block of k_stft_mel takes a run of at most tile_rows
+// consecutive centred frames of one utterance
+struct StftChunk {
+    int64_t utt_off;     // first sample of the chunk's UTTERANCE in the PCM array
+    int64_t utt_len;     // its samples (the reflections happen at its ends)
+    int64_t out_row;     // destination row of the chunk's first frame
+    int32_t t0;          // first frame of the chunk inside the utterance
+    int32_t n_frames;
+    int32_t utt_chunk0;  // first chunk of the utterance, and how many it has: the slots k_stft_post takes its maximum over
+    int32_t utt_chunks;  // (both count from the plan's first chunk)
+};
+
+constexpr int kStftTB = 13;    // bin tiles (16 bins: a cos and a sin accumulator tile) a wave carries through one pass over the taps
+constexpr int kStftKSteps = 2; // steps of 4 taps per LDS buffer of basis operands
+
+struct StftParams {
+    const int16_t *pcm;
+    const StftChunk *chunks;    // the launch's chunks (blockIdx.x)
+    int32_t n_chunks;
+    int32_t chunk_first;        // index of chunks[0] in the plan: its slot in blk_max
+    int32_t N, S, M;            // DFT length, hop, mel bands
+    int32_t post;               // MFX_LOGMEL_*
+    int32_t tile_rows;          // frames per block the chunks were cut for (64, 32 or 16)
+    const float *operands;      // [pass][step][tile of the pass][64] (build_stft_operands)
+    const float *mel_w;         // the rows' non-zero spans back to back
+    const int32_t *mel_beg, *mel_len, *mel_off; // [M] first bin, bins, first weight of every row
+    float *out;
+    int32_t out_pitch;
+    float *blk_max;             // [chunks of the plan] the largest log value of every block (WHISPER)
+};
+// ALL the LDS a block of k_stft_mel asks for at tile_rows frames per block: the kernel declares no static LDS beside it
+size_t stft_lds_bytes(int N, int S, int M, int tile_rows);
+int stft_tile_rows(int N, int S, int M); // frames per block: the largest of 64 / 32 / 16 whose LDS fits, 0: none
+hipError_t launch_stft(const StftParams &p, hipStream_t stream);      // k_stft_mel
+hipError_t launch_stft_post(const StftParams &p, hipStream_t stream); // k_stft_post (WHISPER: clamp and map, in place)
 
 // All launchers are asynchronous on `stream` and return the launch status.
 // every launch of the VAD stage for utterances [u0, u1), in order

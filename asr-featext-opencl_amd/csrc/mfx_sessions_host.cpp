@@ -27,6 +27,8 @@ extern "C" int mfx_sessions_create(mfx_handle *h, int32_t n_sessions, int32_t ma
     MFX_DEVICE_ENTRY(h);
     if (h->traps)
         return fail(h, MFX_ERR_STATE, "the session entries do not serve TRAPS handles (their look-ahead is (L - 1) / 2 frames, not D)");
+    if (h->stft)
+        return fail(h, MFX_ERR_STATE, "the session entries do not serve STFT log-mel handles: use the batch entries (mfx_batch_plan + mfx_batch_run_device)");
     if (h->cfg.norm != MFX_NORM_NONE && !h->sess.on.set) // (mfx_sessions_set_online_norm: the one normaliser served)
         return fail(h, MFX_ERR_STATE,
                     "the session entries do not serve normalisation (norm != MFX_NORM_NONE): statistics over an open stream are not built");

@@ -1,0 +1,271 @@
+// mfx_stft.hip -- k_stft_mel and k_stft_post: the exact-length STFT log-mel front end (MFX_METHOD_STFT_LOGMEL) and their
+// launchers.  See DESIGN.md, "STFT log-mel".
+//
+// Per utterance of n samples (N = DFT length, S = hop, M = bands, K1 = N / 2 + 1 bins): T = 0 when n <= N / 2, else n div S
+// centred frames; frame t, tap j reads sample t S + j - N / 2, reflected at the ends of the utterance.
+//   x[j]      = (float)pcm * 2^-15
+//   re[k]     = 0, then for j = 0 .. N - 1 ascending: fmaf(x[j], Ck[k][j], .)        (im[k] likewise with Sk: the UNFOLDED form)
+//   P[k]      = fmaf(im, im, re * re)
+//   mel[m]    = 0, then over the row's non-zero span ascending: fmaf(Wm[m][k], P[k], .)
+//   L         = log10(max(mel, 1e-10f)), -10.0f at the floor itself (LN: the natural log)
+//   WHISPER   : L = max(L, mx - 8.0f), out = (L + 4.0f) * 0.25f, mx the utterance's largest L          (k_stft_post)
+//
+// k_stft_mel: a block of 4 waves takes R = 64, 32 or 16 consecutive frames of one utterance (StftChunk).  Their PCM span,
+// (R - 1) S + N floats, is staged once in LDS, reflected, converted and scaled: frame t is then the contiguous run at t S
+// and no frame is ever copied (k_splice_affine's staging with the row pitch Wd replaced by the hop).  The basis comes as
+// v_mfma_f32_16x16x4_f32 lane operands [pass][step of 4 taps][tile of 16 outputs][64 lanes] and is streamed through two
+// LDS buffers of kStftKSteps steps, chunk c + 1 travelling through registers while chunk c is consumed.  Wave w owns the 16
+// frames 16 w .. 16 w + 15 and ALL output tiles of the pass: the A operand of a step is read once and serves every tile.
+// Tiles come in pairs -- tile 2 q holds the cos rows, tile 2 q + 1 the sin rows of bins 16 q .. 16 q + 15 -- so re[k] and
+// im[k] of a frame meet in the same lane and register of sibling accumulators and the power is formed in place.  A pass
+// carries at most kStftTB bin tiles (26 accumulator tiles, 104 registers); a DFT with more bins (N > 414) takes a second
+// pass over the taps for the rest -- every output still has ONE uncut chain, inside one pass.  Taps past N (N is padded to
+// a multiple of 4) meet zero operands and finite staged words.  P goes to LDS, the mel chains and the log run one (frame,
+// band) per thread, and the rows leave with consecutive lanes on consecutive words (tile_store_rows).  The block's largest
+// log value goes to its slot of blk_max.
+// k_stft_post (WHISPER only): the block of a chunk takes the maximum over the slots of its utterance's chunks -- a float
+// maximum does not depend on the order, no atomics -- and clamps and maps its own rows in place.
+#include "mfx_kernels.h"
+
+#include <hip/hip_runtime.h>
+
+#include "mfx_dev.h"
+#include "mfx_launch.h"
+#include "mfx_tile_dev.h"
+
+namespace mfx {
+
+namespace {
+
+__host__ __device__ inline int stft_bins(int N) { return N / 2 + 1; }
+__host__ __device__ inline int stft_bin_tiles(int N) { return (stft_bins(N) + 15) >> 4; }
+__host__ __device__ inline int stft_steps(int N) { return (N + 3) >> 2; }
+// bin tiles of a pass: as many as the DFT has, at most kStftTB (the operand table is laid out for it)
+__host__ __device__ inline int stft_pass_tiles(int N) { return stft_bin_tiles(N) < kStftTB ? stft_bin_tiles(N) : kStftTB; }
+// floats of one LDS operand buffer
+__host__ __device__ inline int stft_buf_floats(int N) { return kStftKSteps * 2 * stft_pass_tiles(N) * 64; }
+// floats of the staged span (then 4 words of zeros for the padded taps of the last frame) -- the finished rows [R][M] are
+// assembled in the same words once the DFT is done
+__host__ __device__ inline int stft_span_floats(int N, int S, int R) { return (R - 1) * S + N + 4; }
+__host__ __device__ inline int stft_xo_floats(int N, int S, int M, int R)
+{
+    const int a = stft_span_floats(N, S, R), b = R * M;
+    return ((a > b ? a : b) + 3) & ~3;
+}
+__host__ __device__ inline int stft_p_pitch(int N) { return stft_bins(N) | 1; } // odd: a column of P spreads over the banks
+
+__device__ __forceinline__ float wave_max(float v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+constexpr int kStftPf = (kStftKSteps * 2 * kStftTB * 16 + 255) / 256; // 16-byte words a thread carries for the next chunk
+
+// LDS, all of it dynamic (stft_lds_bytes is the whole of what a block asks for):
+//   operand buffers [2][KS][2 TBp][64] | s_x [(R - 1) S + N + 4] (later s_out [R][M]) | s_P [R][KP] | s_red [4]
+__global__ void __launch_bounds__(256) k_stft_mel(StftParams p)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const StftChunk ck = p.chunks[blockIdx.x];
+    const int R = p.tile_rows, N = p.N, S = p.S, M = p.M;
+    const int rows = ck.n_frames;
+    const int K1 = stft_bins(N), KP = stft_p_pitch(N), NBT = stft_bin_tiles(N), TBp = stft_pass_tiles(N), steps = stft_steps(N);
+    const int tid = threadIdx.x;
+    float *s_b = smem;
+    float *s_x = s_b + 2 * stft_buf_floats(N);
+    float *s_P = s_x + stft_xo_floats(N, S, M, R);
+    float *s_out = s_x;
+    float *s_red = s_P + R * KP; // the waves' maxima
+
+    {   // the span of frames t0 .. t0 + rows - 1, reflected at the ends of the utterance; zeros behind it
+        const int16_t *src = p.pcm + ck.utt_off;
+        const int64_t n = ck.utt_len, base = (int64_t)ck.t0 * S - N / 2;
+        const int span = (rows - 1) * S + N, all = stft_span_floats(N, S, R);
+        for (int i = tid; i < all; i += 256) {
+            float v = 0.f;
+            if (i < span) {
+                int64_t j = base + i;
+                if (j < 0) j = -j;
+                if (j >= n) j = 2 * (n - 1) - j;
+                if (j >= 0 && j < n) v = (float)src[j] * (1.0f / 32768.0f);
+            }
+            s_x[i] = v;
+        }
+    }
+
+    const int lane = tid & 63, g = tid >> 6;
+    const int li = lane & 15, lk = lane >> 4;
+    const bool busy = 16 * g < rows && 16 * g < R;
+    const float *za = s_x + (16 * g + li) * S + lk; // lane (li, lk) feeds frame 16 g + li, tap 4 s + lk
+
+    for (int b0 = 0; b0 < NBT; b0 += TBp) {
+        const int cnt = min(TBp, NBT - b0);       // bin tiles of this pass
+        const int pt = 2 * TBp;                   // tiles of a pass as the table holds them (the last pass: zeros beyond cnt)
+        const int chunk4 = kStftKSteps * pt * 16; // 16-byte words of a chunk
+        const int total4 = steps * pt * 16;
+        const int nchunks = (steps + kStftKSteps - 1) / kStftKSteps;
+        const f32x4 *ops4 = (const f32x4 *)p.operands + (int64_t)(b0 / TBp) * total4;
+
+        f32x4 pf[kStftPf] = {};
+#pragma unroll
+        for (int q = 0; q < kStftPf; ++q) {
+            const int i = tid + 256 * q;
+            if (i < min(chunk4, total4)) pf[q] = ops4[i];
+        }
+        __syncthreads(); // (the previous pass has left the buffers; the first pass: nothing reads them yet)
+#pragma unroll
+        for (int q = 0; q < kStftPf; ++q) {
+            const int i = tid + 256 * q;
+            if (i < min(chunk4, total4)) ((f32x4 *)s_b)[i] = pf[q];
+        }
+        __syncthreads(); // (also: s_x is staged)
+
+        f32x4 acc[2 * kStftTB];
+#pragma unroll
+        for (int j = 0; j < 2 * kStftTB; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+        for (int c = 0; c < nchunks; ++c) {
+            const bool more = c + 1 < nchunks;
+            const int n4 = more ? min(chunk4, total4 - (c + 1) * chunk4) : 0;
+#pragma unroll
+            for (int q = 0; q < kStftPf; ++q) {
+                const int i = tid + 256 * q;
+                if (i < n4) pf[q] = ops4[(c + 1) * chunk4 + i];
+            }
+            if (busy) {
+                const float *buf = s_b + (c & 1) * chunk4 * 4;
+                const int s0 = c * kStftKSteps, s1 = min(steps, s0 + kStftKSteps);
+                for (int s = s0; s < s1; ++s) {
+                    const float *b = buf + (s - s0) * pt * 64 + lane;
+                    const float a = za[4 * s];
+#pragma unroll
+                    for (int j = 0; j < kStftTB; ++j) {
+                        if (j < cnt) {
+                            acc[2 * j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b[(2 * j) * 64], acc[2 * j], 0, 0, 0);
+                            acc[2 * j + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b[(2 * j + 1) * 64], acc[2 * j + 1], 0, 0, 0);
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < kStftPf; ++q) {
+                const int i = tid + 256 * q;
+                if (i < n4) ((f32x4 *)(s_b + ((c + 1) & 1) * chunk4 * 4))[i] = pf[q];
+            }
+            __syncthreads();
+        }
+
+        // D[i][n]: the lane holds frames i = 4 (lane >> 4) + r, bin n = lane & 15 of the tile -- re and im side by side
+        if (busy) {
+#pragma unroll
+            for (int j = 0; j < kStftTB; ++j) {
+                const int k = 16 * (b0 + j) + li;
+                if (j >= cnt || k >= K1) continue;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int t = 16 * g + 4 * lk + r;
+                    const float re = acc[2 * j][r], im = acc[2 * j + 1][r];
+                    if (t < rows) s_P[t * KP + k] = __builtin_fmaf(im, im, re * re);
+                }
+            }
+        }
+    }
+    __syncthreads();
+
+    // mel chains and the log: one (frame, band) per thread and trip
+    float mx = -INFINITY;
+    {
+        const int n = rows * M;
+        const uint32_t magic = div_magic(M);
+        for (int i = tid; i < n; i += 256) {
+            const int t = div_small(i, M, magic);
+            const int m = i - t * M;
+            const int beg = p.mel_beg[m], len = p.mel_len[m];
+            const float *w = p.mel_w + p.mel_off[m];
+            const float *P = s_P + t * KP + beg;
+            float acc = 0.f;
+            for (int j = 0; j < len; ++j) acc = __builtin_fmaf(w[j], P[j], acc);
+            const float v = fmaxf(acc, 1e-10f);
+            float L;
+            if (p.post == 2)
+                L = logf(v);
+            else
+                L = v == 1e-10f ? -10.0f : log10f(v);
+            s_out[i] = L;
+            mx = fmaxf(mx, L);
+        }
+    }
+    mx = wave_max(mx);
+    if (lane == 0) s_red[g] = mx;
+    __syncthreads();
+    if (tid == 0) p.blk_max[p.chunk_first + blockIdx.x] = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
+
+    tile_store_rows(s_out, M, rows, p.out, ck.out_row, p.out_pitch, tid);
+}
+
+__global__ void __launch_bounds__(256) k_stft_post(StftParams p)
+{
+    __shared__ float s_red[4];
+    const StftChunk ck = p.chunks[blockIdx.x];
+    const int tid = threadIdx.x;
+    float mx = -INFINITY;
+    for (int c = tid; c < ck.utt_chunks; c += 256) mx = fmaxf(mx, p.blk_max[ck.utt_chunk0 + c]);
+    mx = wave_max(mx);
+    if ((tid & 63) == 0) s_red[tid >> 6] = mx;
+    __syncthreads();
+    const float lo = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3])) - 8.0f;
+    const int M = p.M, n = ck.n_frames * M;
+    const uint32_t magic = div_magic(M);
+    float *obase = p.out + ck.out_row * (int64_t)p.out_pitch;
+    for (int i = tid; i < n; i += 256) {
+        const int t = div_small(i, M, magic);
+        float *o = obase + t * (int64_t)p.out_pitch + (i - t * M);
+        *o = (fmaxf(*o, lo) + 4.0f) * 0.25f;
+    }
+}
+
+bool stft_params_ok(const StftParams &p)
+{
+    return p.N >= 32 && p.N <= 512 && !(p.N & 1) && p.S >= 1 && p.S <= p.N && p.M >= 1 && p.M <= 128 && p.out_pitch >= p.M && p.pcm && p.chunks &&
+           p.operands && p.mel_w && p.mel_beg && p.mel_len && p.mel_off && p.out && p.blk_max &&
+           (p.tile_rows == 64 || p.tile_rows == 32 || p.tile_rows == 16) && stft_lds_bytes(p.N, p.S, p.M, p.tile_rows) <= kLdsMax;
+}
+
+} // namespace
+
+size_t stft_lds_bytes(int N, int S, int M, int tile_rows)
+{
+    const size_t f = (size_t)2 * stft_buf_floats(N) + (size_t)stft_xo_floats(N, S, M, tile_rows) + (size_t)tile_rows * stft_p_pitch(N) +
+                     4 /* s_red */;
+    return f * sizeof(float);
+}
+
+int stft_tile_rows(int N, int S, int M)
+{
+    for (int r : {64, 32, 16})
+        if (stft_lds_bytes(N, S, M, r) <= kLdsMax) return r;
+    return 0;
+}
+
+hipError_t launch_stft(const StftParams &p, hipStream_t stream)
+{
+    if (p.n_chunks <= 0) return hipSuccess;
+    if (!stft_params_ok(p)) return hipErrorInvalidValue;
+    const size_t lds = stft_lds_bytes(p.N, p.S, p.M, p.tile_rows);
+    const void *fn = (const void *)k_stft_mel;
+    if (hipError_t e = allow_dynamic_lds(fn, lds); e != hipSuccess) return e;
+    StftParams q = p;
+    return launch_kernel(fn, dim3(p.n_chunks), dim3(256), lds, stream, q);
+}
+
+hipError_t launch_stft_post(const StftParams &p, hipStream_t stream)
+{
+    if (p.n_chunks <= 0) return hipSuccess;
+    if (!stft_params_ok(p)) return hipErrorInvalidValue;
+    StftParams q = p;
+    return launch_kernel((const void *)k_stft_post, dim3(p.n_chunks), dim3(256), 0, stream, q);
+}
+
+} // namespace mfx

@@ -405,6 +405,65 @@ void build_front1024_long_window(const std::vector<float> &padded, int fft_size,
     }
 }
 
+// ---- STFT log-mel front end
+
+int64_t stft_frame_count(int64_t samples, int N, int S) { return samples <= N / 2 ? 0 : samples / S; }
+
+void build_stft_basis(int N, const float *window, float *cos_sin)
+{
+    const int K1 = N / 2 + 1;
+    const double two_pi = 6.283185307179586476925286766559;
+    for (int k = 0; k < K1; ++k)
+        for (int j = 0; j < N; ++j) {
+            const double a = two_pi * (double)(((int64_t)k * j) % N) / (double)N, w = (double)window[j];
+            cos_sin[(size_t)k * N + j] = (float)(w * std::cos(a));
+            cos_sin[((size_t)K1 + k) * N + j] = (float)(-w * std::sin(a));
+        }
+}
+
+namespace {
+const double kSlaneyStep = 200.0 / 3.0, kSlaneyLogStep = std::log(6.4) / 27.0;
+double slaney_hz_to_mel(double f) { return f < 1000.0 ? f / kSlaneyStep : 15.0 + std::log(f / 1000.0) / kSlaneyLogStep; }
+double slaney_mel_to_hz(double m) { return m < 15.0 ? m * kSlaneyStep : 1000.0 * std::exp(kSlaneyLogStep * (m - 15.0)); }
+} // namespace
+
+void build_slaney_mel(int M, int N, float sample_rate, float low_freq, float high_freq, float *weights, int32_t *beg, int32_t *len)
+{
+    const int K1 = N / 2 + 1;
+    const double sr = sample_rate, m_lo = slaney_hz_to_mel(low_freq), m_hi = slaney_hz_to_mel(high_freq);
+    std::vector<double> p((size_t)M + 2);
+    for (int i = 0; i < M + 2; ++i) p[i] = slaney_mel_to_hz(m_lo + (m_hi - m_lo) * (double)i / (double)(M + 1));
+    for (int m = 0; m < M; ++m) {
+        int first = -1, last = -2;
+        for (int k = 0; k < K1; ++k) {
+            const double f = (double)k * sr / (double)N;
+            const double up = (f - p[m]) / (p[m + 1] - p[m]), down = (p[m + 2] - f) / (p[m + 2] - p[m + 1]);
+            const float w = (float)(std::max(0.0, std::min(up, down)) * 2.0 / (p[m + 2] - p[m]));
+            weights[(size_t)m * K1 + k] = w;
+            if (w != 0.f) {
+                if (first < 0) first = k;
+                last = k;
+            }
+        }
+        beg[m] = first < 0 ? 0 : first;
+        len[m] = first < 0 ? 0 : last - first + 1;
+    }
+}
+
+void build_stft_operands(const float *cos_sin, int N, int tb, std::vector<float> &out)
+{
+    const int K1 = N / 2 + 1, nbt = (K1 + 15) / 16, steps = (N + 3) / 4, passes = (nbt + tb - 1) / tb;
+    out.assign((size_t)passes * steps * 2 * tb * 64, 0.f);
+    for (int ps = 0; ps < passes; ++ps)
+        for (int s = 0; s < steps; ++s)
+            for (int tile = 0; tile < 2 * tb; ++tile)
+                for (int lane = 0; lane < 64; ++lane) {
+                    const int k = 16 * (ps * tb + tile / 2) + (lane & 15), j = 4 * s + (lane >> 4);
+                    if (k < K1 && j < N)
+                        out[(((size_t)ps * steps + s) * 2 * tb + tile) * 64 + lane] = cos_sin[((size_t)(tile & 1) * K1 + k) * N + j];
+                }
+}
+
 } // namespace mfx
 
 namespace mfx {

@@ -168,6 +168,20 @@ int64_t resampled_length(int64_t samples, int32_t in_hz, int32_t out_hz);
 int64_t resample_layout(int32_t n_utt, const int64_t *lengths, const int32_t *rates_hz, int32_t out_hz, int64_t *offsets,
                         int64_t *out_lengths);
 
+// STFT log-mel front end ("STFT log-mel"; N = DFT length, even; K1 = N / 2 + 1 bins).
+// frames of an utterance of `samples` samples: 0 up to N / 2 samples (the reflection needs one more), else samples div S
+int64_t stft_frame_count(int64_t samples, int N, int S);
+// basis [2][K1][N]: Ck[k][j] = w[j] cos(2 pi ((k j) mod N) / N), Sk[k][j] = -w[j] sin(same), in double from the float32
+// window, rounded once
+void build_stft_basis(int N, const float *window, float *cos_sin);
+// Slaney mel table (librosa filters.mel(htk=False, norm="slaney")), in double, rounded once: weights [M][K1]; beg / len: the
+// non-zero span of every row (len 0: a band narrower than a bin that holds none)
+void build_slaney_mel(int M, int N, float sample_rate, float low_freq, float high_freq, float *weights, int32_t *beg, int32_t *len);
+// the basis as k_stft_mel streams it: passes of `tb` bin tiles (16 bins: tile 2 q of a pass the cos rows, tile 2 q + 1 the
+// sin rows); out[((pass * steps + s) * 2 tb + tile) * 64 + lane] = row(16 bin tile + (lane & 15))[4 s + (lane >> 4)], zero
+// beyond the bins and the taps.  steps = ceil(N / 4), passes = ceil(ceil(K1 / 16) / tb).
+void build_stft_operands(const float *cos_sin, int N, int tb, std::vector<float> &out);
+
 } // namespace mfx
 
 namespace mfx {

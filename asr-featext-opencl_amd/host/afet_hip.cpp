@@ -49,6 +49,7 @@ struct Options {
     float window_ms = 25.f, shift_ms = 10.f;
     int banks = 15, ceps = 12, norm = 2, dyn = 0, l1 = 3, l2 = 3;   // reference main() defaults (ASR_OCL.cpp:560)
     float low = 64.f, high = 0.f, lift = 22.f;
+    bool low_given = false;                        // (--method LOGMEL starts at 0 Hz unless --low-freq says otherwise)
     bool c0 = true, norm_after_dyn = true;
     float alpha_min = 1.f, alpha_max = 1.f, alpha_step = 1.f;
     std::string alpha_file;        // --alpha-file: one warp factor per line, in the order of the input list
@@ -62,6 +63,7 @@ struct Options {
     bool bug_compat = true;
     int method = MFX_METHOD_MFCC, model_order = 8; // --method MFCC|PLP|TRAPS, --model-order (ASR_OCL.cpp:54-56: default 8)
     int traps_len = 31, traps_dct = 10;            // --traps-length, --traps-dct (ASR_OCL.cpp:604-606: defaults 31 and 10)
+    int logmel_post = MFX_LOGMEL_WHISPER;          // --logmel-post whisper|log10|ln (--method LOGMEL)
     bool htk = false; // binary output in HTK parameter-file format instead of the reference's text rows
     int format_threads = 4; // threads that format the text rows of a block (per worker)
     int batch_mb = 16;      // PCM per batch of files (0: the per-file loop only); small enough that a few thousand files pipeline
@@ -587,14 +589,15 @@ bool prepare_batch(Batch &b, const Options &o, const std::vector<std::string> &f
             const long long nc = other_rate ? (long long)mfx_host_resampled_length((int64_t)n, it.rate, o.resample_to) : (long long)n;
             if (nc < 0) throw std::runtime_error("File \"" + files[2 * it.file] + "\": sample rate outside 1000 .. 768000 Hz");
             it.conv_len = nc;
-            const long long T = nc >= W ? (nc - (W - S)) / S : 0;
+            const bool logmel = o.method == MFX_METHOD_STFT_LOGMEL; // (centred frames: its own frame rule)
+            const long long T = logmel ? std::max<long long>(0, (long long)mfx_host_stft_frame_count(nc, W, S)) : nc >= W ? (nc - (W - S)) / S : 0;
             // the per-file loop keeps: files of more than one block, files too short for the deltas' context (the
             // reference refuses or mangles them: same messages from the same code), alpha sweeps
             // (TRAPS has no per-file loop: every file is one utterance of a batch, whatever its length)
             // (a file at another rate has no per-file loop either: it stays in the batch, and a sweep over it is refused)
             if (other_rate && sweep)
                 throw std::runtime_error("File \"" + files[2 * it.file] + "\" needs sample-rate conversion, which takes one warp factor, not a sweep");
-            it.stream = o.method != MFX_METHOD_TRAPS && !other_rate && (sweep || n > (size_t)limit || T < 2 * D + 1);
+            it.stream = o.method != MFX_METHOD_TRAPS && !logmel && !other_rate && (sweep || n > (size_t)limit || T < 2 * D + 1);
             if (!it.stream) {
                 it.mono.resize(n);
                 const int ch = it.wav.channels;
@@ -656,6 +659,14 @@ void worker(const Options &o, int device, float sr, const std::vector<std::strin
                 t->set_warp(o.alpha_min);
                 if (g_time.on) g_time.t_created = now_ns();
                 return std::unique_ptr<MfccHip>(std::move(t));
+            }
+            if (o.method == MFX_METHOD_STFT_LOGMEL) { // batch entries only; the window is the periodic Hann, samples are scaled in the kernel
+                std::unique_ptr<MfccHip> t(new LogmelHip(o.sample_limit, (int)W, (int)S, o.banks, sr, o.low, o.high, o.logmel_post, device));
+                std::vector<float> window((size_t)W);
+                for (long i = 0; i < W; ++i) window[i] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * (double)i / (double)W));
+                t->set_window(window.data());
+                if (g_time.on) g_time.t_created = now_ns();
+                return t;
             }
             std::unique_ptr<MfccHip> p(
                 o.method == MFX_METHOD_PLP
@@ -985,7 +996,7 @@ int main(int argc, char **argv)
         else if (a == "--dyn") o.dyn = std::atoi(val());
         else if (a == "--l1") o.l1 = std::atoi(val());
         else if (a == "--l2") o.l2 = std::atoi(val());
-        else if (a == "--low-freq") o.low = (float)std::atof(val());
+        else if (a == "--low-freq") o.low = (float)std::atof(val()), o.low_given = true;
         else if (a == "--high-freq") o.high = (float)std::atof(val());
         else if (a == "--lift-coef") o.lift = (float)std::atof(val());
         else if (a == "--norm-after-dyn") o.norm_after_dyn = std::atoi(val()) != 0;
@@ -1029,10 +1040,18 @@ int main(int argc, char **argv)
             if (m == "MFCC") o.method = MFX_METHOD_MFCC;
             else if (m == "PLP") o.method = MFX_METHOD_PLP;
             else if (m == "TRAPS") o.method = MFX_METHOD_TRAPS;
-            else { std::fprintf(stderr, "--method: MFCC, PLP or TRAPS\n"); return 2; }
+            else if (m == "LOGMEL") o.method = MFX_METHOD_STFT_LOGMEL;
+            else { std::fprintf(stderr, "--method: MFCC, PLP, TRAPS or LOGMEL\n"); return 2; }
         }
         else if (a == "--traps-length") o.traps_len = std::atoi(val());
         else if (a == "--traps-dct") o.traps_dct = std::atoi(val());
+        else if (a == "--logmel-post") {
+            const std::string m = val();
+            if (m == "whisper") o.logmel_post = MFX_LOGMEL_WHISPER;
+            else if (m == "log10") o.logmel_post = MFX_LOGMEL_LOG10;
+            else if (m == "ln") o.logmel_post = MFX_LOGMEL_LN;
+            else { std::fprintf(stderr, "--logmel-post: whisper, log10 or ln\n"); return 2; }
+        }
         else if (a == "--model-order") o.model_order = std::atoi(val());
         else if (a == "--timing") g_time.on = true;
         else if (a == "--format-threads") o.format_threads = std::max(1, std::atoi(val()));
@@ -1081,7 +1100,8 @@ int main(int argc, char **argv)
                         "         [--dyn 0..2] [--l1 n] [--l2 n] [--low-freq hz] [--high-freq hz] [--lift-coef x]\n"
                         "         [--norm-after-dyn 0|1] [--alpha a | --alpha-min a --alpha-max b --alpha-step s | --alpha-file f]\n"
                         "         [--sample-limit n] [--dev n | --devs a,b,...] [--bug-compat 0|1] [--htk]  in.wav out.txt [...]\n"
-                        "         [--method MFCC|PLP|TRAPS] [--model-order n (PLP model order, default 8)]\n"
+                        "         [--method MFCC|PLP|TRAPS|LOGMEL] [--model-order n (PLP model order, default 8)]\n"
+                        "         [--logmel-post whisper|log10|ln (LOGMEL: what follows the log; default whisper)]\n"
                         "         [--traps-length n (TRAPS frames per trajectory, odd, default 31)] [--traps-dct n (default 10)]\n"
                         "         [--batch-mb n (PCM per batch of whole files; 0 = per-file loop)] [--io-threads n]\n"
                         "  --alpha-file: one warp factor per line, in the order of the input files; files of a batch run with\n"
@@ -1199,6 +1219,19 @@ int main(int argc, char **argv)
             std::fprintf(stderr, "--method TRAPS takes one warp factor (--alpha), not a sweep\n");
             return 2;
         }
+    }
+    if (o.method == MFX_METHOD_STFT_LOGMEL) { // whole files through the batch entries; log mel bands, nothing behind them
+        if (o.batch_mb <= 0) {
+            std::fprintf(stderr, "--method LOGMEL runs whole files through the batch entries: --batch-mb must be positive\n");
+            return 2;
+        }
+        if (o.alpha_max - o.alpha_min >= o.alpha_step) {
+            std::fprintf(stderr, "--method LOGMEL has no warp factor to sweep\n");
+            return 2;
+        }
+        // (the reference CLI's defaults -- 64 Hz, cepstra with c0, deltas, CVN -- belong to the cepstral methods)
+        o.ceps = 0, o.c0 = false, o.dyn = 0, o.norm = 0;
+        if (!o.low_given) o.low = 0.f;
     }
     if (o.resample_to != 0 && (o.resample_to < 1000 || o.resample_to > 768000)) {
         std::fprintf(stderr, "--resample-to takes a rate of 1000 .. 768000 Hz\n");

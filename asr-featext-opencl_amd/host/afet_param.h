@@ -143,11 +143,11 @@ public:
 
 protected:
     // method: MFX_METHOD_* of include/mfx.h (PlpHip passes MFX_METHOD_PLP and its model order, TrapsHip MFX_METHOD_TRAPS
-    // and its two lengths)
+    // and its two lengths, LogmelHip MFX_METHOD_STFT_LOGMEL and logmel_post)
     MfccHip(int input_buffer_size, int window_size, int shift, int num_banks, float sample_rate, float low_freq,
             float high_freq, int ceps_len, bool want_c0, float lift_coef, Normalizer::norm_t norm, dyn_t dyn, int delta_l1,
             int delta_l2, bool norm_after_dyn, int hip_device, bool bug_compat, int engine, int method, int lpc_order,
-            int traps_len = 0, int traps_dct_len = 0);
+            int traps_len = 0, int traps_dct_len = 0, int logmel_post = 0);
 
 private:
     void check(int status) const;
@@ -175,6 +175,15 @@ public:
              dyn_t dyn = DYN_NONE, int delta_l1 = 1, int delta_l2 = 1, bool norm_after_dyn = true, int hip_device = 0,
              int engine = 0);
     int get_output_data_width() const override; // num_banks * traps_dct_len * (1 + deltas): the library's own answer
+};
+
+// STFT log-mel spectrogram of the Whisper family ("STFT log-mel"; MFX_METHOD_STFT_LOGMEL): dft_size-point DFT of
+// centred, reflect-padded frames, num_banks Slaney mel bands, log10, and what logmel_post (MFX_LOGMEL_*) names.  Set the
+// periodic Hann window with set_window.  BATCH ENTRIES ONLY, as TrapsHip; no deltas, no normaliser.
+class LogmelHip : public MfccHip {
+public:
+    LogmelHip(int input_buffer_size, int dft_size, int shift, int num_banks, float sample_rate, float low_freq, float high_freq,
+              int logmel_post = 0 /* MFX_LOGMEL_WHISPER */, int hip_device = 0);
 };
 
 #endif // AFET_PARAM_H

@@ -77,11 +77,19 @@ TrapsHip::TrapsHip(int input_buffer_size, int window_size, int shift, int num_ba
 
 int TrapsHip::get_output_data_width() const { return mfx_get_output_data_width(handle()); }
 
+LogmelHip::LogmelHip(int input_buffer_size, int dft_size, int shift, int num_banks, float sample_rate, float low_freq, float high_freq,
+                     int logmel_post, int hip_device)
+    : MfccHip(input_buffer_size, dft_size, shift, num_banks, sample_rate, low_freq, high_freq, /*ceps_len=*/0, /*want_c0=*/false,
+              /*lift_coef=*/0.f, Normalizer::NORM_NONE, DYN_NONE, 1, 1, true, hip_device, /*bug_compat=*/false, /*engine=*/0,
+              MFX_METHOD_STFT_LOGMEL, 0, 0, 0, logmel_post)
+{
+}
+
 
 MfccHip::MfccHip(int input_buffer_size, int window_size, int shift, int num_banks, float sample_rate, float low_freq,
                  float high_freq, int ceps_len, bool want_c0, float lift_coef, Normalizer::norm_t norm, dyn_t dyn,
                  int delta_l1, int delta_l2, bool norm_after_dyn, int hip_device, bool bug_compat, int engine, int method,
-                 int lpc_order, int traps_len, int traps_dct_len)
+                 int lpc_order, int traps_len, int traps_dct_len, int logmel_post)
     : MfccBase(input_buffer_size, window_size, shift, num_banks, sample_rate, low_freq, high_freq, ceps_len, want_c0,
                lift_coef, norm, dyn, delta_l1, delta_l2, norm_after_dyn),
       m_handle(nullptr)
@@ -108,11 +116,12 @@ MfccHip::MfccHip(int input_buffer_size, int window_size, int shift, int num_bank
     cfg.lpc_order = lpc_order;
     cfg.traps_len = traps_len;
     cfg.traps_dct_len = traps_dct_len;
+    cfg.logmel_post = logmel_post;
     if (method != MFX_METHOD_MFCC && !mfx_method_supported(method))
         throw std::runtime_error("MfccHip: feature method not supported by this libmfcchip.so");
     const int rc = mfx_create(&cfg, hip_device, &m_handle);
     if (rc != MFX_OK)
-        throw std::runtime_error(std::string(method == MFX_METHOD_PLP ? "PlpHip: " : method == MFX_METHOD_TRAPS ? "TrapsHip: " : "MfccHip: ") + mfx_status_string(rc));
+        throw std::runtime_error(std::string(method == MFX_METHOD_PLP ? "PlpHip: " : method == MFX_METHOD_TRAPS ? "TrapsHip: " : method == MFX_METHOD_STFT_LOGMEL ? "LogmelHip: " : "MfccHip: ") + mfx_status_string(rc));
 }
 
 MfccHip::~MfccHip() { mfx_destroy(m_handle); }

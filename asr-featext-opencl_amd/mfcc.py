@@ -17,6 +17,8 @@ NORM_NONE, NORM_CMN, NORM_CVN, NORM_MINMAX = 0, 1, 2, 3   # normalizer.h:5
 DYN_NONE, DYN_DELTA, DYN_ACC = 0, 1, 2                     # parambase.h:9
 METHOD_MFCC, METHOD_PLP = 0, 1                             # mfx_config.method (include/mfx.h)
 METHOD_TRAPS = 3                                           # (2 is unassigned and refused)
+METHOD_STFT_LOGMEL = 5                                     # (4 is unassigned and refused)
+LOGMEL_WHISPER, LOGMEL_LOG10, LOGMEL_LN = 0, 1, 2          # mfx_config.logmel_post (include/mfx.h)
 
 
 class MfxError(RuntimeError):
@@ -53,6 +55,7 @@ class MfxConfig(C.Structure):
         ("lpc_order", C.c_int32),
         ("traps_len", C.c_int32),
         ("traps_dct_len", C.c_int32),
+        ("logmel_post", C.c_int32),
     ]
 
 
@@ -80,6 +83,8 @@ EXPORTED_SYMBOLS = (
     "mfx_batch_set_vad", "mfx_batch_clear_vad", "mfx_batch_vad_read", "mfx_batch_vad_device",
     "mfx_batch_set_online_norm", "mfx_batch_clear_online_norm", "mfx_sessions_set_online_norm",
     "mfx_sessions_clear_online_norm", "mfx_host_online_norm",
+    "mfx_host_slaney_mel_table", "mfx_host_stft_basis", "mfx_host_stft_frame_count",
+    "mfx_host_stft_lds_bytes",
 )
 
 
@@ -184,6 +189,10 @@ def load_library():
     L.mfx_sessions_set_online_norm.argtypes = [vp, i32, i32, i64, dp]
     L.mfx_sessions_clear_online_norm.argtypes = [vp]
     L.mfx_host_online_norm.argtypes = [fp, i64, i32, i32, i32, i32, i32, i64, dp, fp]
+    L.mfx_host_slaney_mel_table.argtypes = [i32, i32, C.c_float, C.c_float, C.c_float, fp, p32, p32]
+    L.mfx_host_stft_basis.argtypes = [i32, fp, fp]
+    L.mfx_host_stft_frame_count.argtypes, L.mfx_host_stft_frame_count.restype = [i64, i32, i32], i64
+    L.mfx_host_stft_lds_bytes.argtypes, L.mfx_host_stft_lds_bytes.restype = [i32, i32, i32, p32], i64
     _lib = L
     return L
 
@@ -425,6 +434,48 @@ def host_resample_tile(in_hz, out_hz, zeros=0, rolloff=0.0, channels=1):
     return n
 
 
+def periodic_hann(n):
+    """The periodic Hann window of n taps, float32: 0.5 - 0.5 cos(2 pi j / n) (torch.hann_window(n), Whisper's at n = 400)."""
+    j = np.arange(int(n), dtype=np.float64)
+    return (0.5 - 0.5 * np.cos(2.0 * np.pi * j / int(n))).astype(np.float32)
+
+
+def host_slaney_mel_table(num_banks, dft_size, sample_rate, low_freq, high_freq):
+    """Slaney mel table of the STFT log-mel front end exactly as uploaded (host code, no GPU needed): (weights
+    [num_banks][dft_size / 2 + 1], beg [num_banks], len [num_banks]) -- beg / len the non-zero span of every row."""
+    L = load_library()
+    w = np.zeros((int(num_banks), int(dft_size) // 2 + 1), np.float32)
+    beg, ln = np.zeros(int(num_banks), np.int32), np.zeros(int(num_banks), np.int32)
+    p32 = C.POINTER(C.c_int32)
+    rc = L.mfx_host_slaney_mel_table(int(num_banks), int(dft_size), float(sample_rate), float(low_freq), float(high_freq),
+                                     w.ctypes.data_as(C.POINTER(C.c_float)), beg.ctypes.data_as(p32), ln.ctypes.data_as(p32))
+    if rc != 0:
+        raise MfxError(rc, "mfx_host_slaney_mel_table failed")
+    return w, beg, ln
+
+
+def host_stft_basis(window):
+    """Windowed DFT basis of the STFT log-mel front end exactly as uploaded (host code, no GPU needed): [2][N / 2 + 1][N] for a
+    window of N taps -- the cosine rows, then the negated sine rows."""
+    L = load_library()
+    w = np.ascontiguousarray(window, dtype=np.float32)
+    n = int(w.size)
+    out = np.zeros((2, n // 2 + 1, n), np.float32)
+    fpt = C.POINTER(C.c_float)
+    rc = L.mfx_host_stft_basis(n, w.ctypes.data_as(fpt), out.ctypes.data_as(fpt))
+    if rc != 0:
+        raise MfxError(rc, "mfx_host_stft_basis failed")
+    return out
+
+
+def stft_frame_count(samples, dft_size, shift):
+    """Frames of an utterance of `samples` samples on an STFT log-mel handle: 0 up to dft_size / 2, else samples // shift."""
+    n = int(load_library().mfx_host_stft_frame_count(int(samples), int(dft_size), int(shift)))
+    if n < 0:
+        raise MfxError(n, "mfx_host_stft_frame_count failed")
+    return n
+
+
 def host_frame_count(samples, window_size, shift):
     return int(load_library().mfx_host_frame_count(int(samples), int(window_size), int(shift)))
 
@@ -517,12 +568,16 @@ class MfccHip:
     ``method=METHOD_TRAPS`` (``ceps_len=0``, ``want_c0=False``) computes TRAPS temporal patterns: ``traps_dct_len`` (0 = 10)
     DCT coefficients of the ``traps_len`` (0 = 31) frames around each frame, per mel band -- through the batch entries
     only; the streaming methods raise ``MfxError`` (-8).
+    ``method=METHOD_STFT_LOGMEL`` computes the log-mel spectrogram of the Whisper family (include/mfx.h): ``window_size`` is
+    the DFT length, ``num_banks`` the output width, ``logmel_post`` one of ``LOGMEL_*``; set ``periodic_hann(window_size)``
+    as the window.  Batch entries only as well.
     """
 
     def __init__(self, input_buffer_size, window_size, shift, num_banks, sample_rate, low_freq, high_freq,
                  ceps_len, want_c0, lift_coef, norm=NORM_NONE, dyn=DYN_NONE, delta_l1=1, delta_l2=1,
                  norm_after_dyn=True, device=0, fft_size=0, channels=1, bug_compat=True, batch_norm_stats=0, engine=0,
-                 tail_split=0, method=METHOD_MFCC, lpc_order=0, traps_len=0, traps_dct_len=0):
+                 tail_split=0, method=METHOD_MFCC, lpc_order=0, traps_len=0, traps_dct_len=0,
+                 logmel_post=LOGMEL_WHISPER):
         self._L = load_library()
         _check_method(method)
         self.cfg = MfxConfig(int(input_buffer_size), int(window_size), int(shift), int(num_banks),
@@ -530,7 +585,7 @@ class MfccHip:
                              int(bool(want_c0)), float(lift_coef), int(norm), int(dyn), int(delta_l1),
                              int(delta_l2), int(bool(norm_after_dyn)), int(fft_size), int(channels),
                              int(bool(bug_compat)), int(batch_norm_stats), int(engine), int(tail_split),
-                             int(method), int(lpc_order), int(traps_len), int(traps_dct_len))
+                             int(method), int(lpc_order), int(traps_len), int(traps_dct_len), int(logmel_post))
         h = C.c_void_p()
         rc = self._L.mfx_create(C.byref(self.cfg), int(device), C.byref(h))
         if rc != 0:

@@ -95,6 +95,8 @@ typedef struct mfx_config {
                                   Ignored unless method is MFX_METHOD_TRAPS                                          */
     int32_t traps_dct_len;     /* TRAPS: DCT coefficients K kept per band, 1 .. min(32, L); 0 = 10 (the reference CLI's
                                   default).  Ignored unless method is MFX_METHOD_TRAPS                               */
+    int32_t logmel_post;       /* STFT log-mel: MFX_LOGMEL_* -- what follows the log.  Ignored unless method is
+                                  MFX_METHOD_STFT_LOGMEL                                                              */
 } mfx_config;
 
 /* mfx_config.method.  3 = TRAPS temporal patterns (TRAPS): the log mel energies of the MFCC path (ceps_len = 0,
@@ -103,7 +105,47 @@ typedef struct mfx_config {
  * ONLY: on a TRAPS handle mfx_set_input, mfx_flush, mfx_apply, mfx_apply_alphas, mfx_get_output_data and
  * mfx_get_output_data_alpha return MFX_ERR_STATE.  The value 2 is unassigned and stays refused (mfx_method_supported(2) == 0):
  * libraries in the field answer for it, so TRAPS did not take it. */
-enum { MFX_METHOD_MFCC = 0, MFX_METHOD_PLP = 1, MFX_METHOD_TRAPS = 3 };
+enum { MFX_METHOD_MFCC = 0, MFX_METHOD_PLP = 1, MFX_METHOD_TRAPS = 3, MFX_METHOD_STFT_LOGMEL = 5 };
+
+/* mfx_config.method 5 = the log-mel spectrogram neural recognisers of the Whisper family feed on ("STFT log-mel"):
+ * an exact-length DFT of centred, reflect-padded frames, Slaney mel bands, log10, and Whisper's clamp and map.  The value 4
+ * is unassigned and stays refused, as 2 does.  BATCH ENTRIES ONLY, as TRAPS: the streaming and the session entries return
+ * MFX_ERR_STATE on such a handle.
+ * Configuration (anything else: MFX_ERR_CONFIG).  window_size = N, the DFT length: even, 32 .. 512; fft_size 0 or N
+ * (mfx_fft_size returns N); shift = S in 1 .. N; num_banks = M in 1 .. 128, the output width; 0 <= low_freq < high_freq <=
+ * sample_rate / 2; ceps_len = 0, want_c0 = 0, dyn = NONE, norm = NONE, channels 0 or 1.  lift_coef, the delta orders and
+ * bug_compat are ignored.  The window is the caller's through mfx_set_window: the periodic Hann for Whisper.
+ * Definition, per utterance of n samples (K1 = N / 2 + 1):
+ *   Frames.  T = 0 when n <= N / 2, else T = n div S.  Frame t, tap j in [0, N) reads sample i = t S + j - N / 2; i < 0 reads
+ *     sample -i, i >= n reads sample 2 (n - 1) - i: neither leaves [0, n).  That is torch.stft(center=True,
+ *     pad_mode="reflect") with its last frame dropped, which is what Whisper keeps.  The reflection happens at the ends of the
+ *     UTTERANCE, never into a neighbour's samples.
+ *   Samples.  x[j] = (float)pcm * 2^-15 (exact).
+ *   Basis.   Ck[k][j] = (float)(w[j] cos(2 pi ((k j) mod N) / N)), Sk[k][j] = (float)(-w[j] sin(2 pi ((k j) mod N) / N)), k <
+ *     K1: in double from the float32 window, rounded once; rebuilt by mfx_set_window (which waits for the handle's streams
+ *     and allocates there).
+ *   DFT.     re[k] = 0, then for j = 0 .. N - 1 ascending re = fmaf(x[j], Ck[k][j], re); im[k] likewise with Sk.  The UNFOLDED
+ *     form: N taps per chain, the frame is not folded first.  One float32 FMA chain per value, whose order does not depend on
+ *     the tiling or on the batch.
+ *   Power.   P[k] = fmaf(im, im, re * re) (no |X| / W2 scaling).
+ *   Mel.     The table of librosa filters.mel(htk=False, norm="slaney"), in double, rounded once.  Hz to mel: f / (200 / 3)
+ *     below 1000 Hz, else 15 + ln(f / 1000) / (ln 6.4 / 27).  Edges p[0 .. M + 1]: M + 2 points equally spaced in mel between
+ *     low_freq and high_freq, mapped back to Hz.  f_k = k sample_rate / N.  Wm[m][k] = max(0, min((f_k - p[m]) / (p[m+1] -
+ *     p[m]), (p[m+2] - f_k) / (p[m+2] - p[m+1]))) * 2 / (p[m+2] - p[m]).  mel[m] = 0, then over the row's non-zero span
+ *     ascending mel = fmaf(Wm[m][k], P[k], mel).  A band narrower than a bin may have an empty span: it is 0 and takes the
+ *     floor.  (Whisper ships this table as a file; the pin here is the formula.)
+ *   Log.     v = max(mel, 1e-10f); L = log10(v) for WHISPER and LOG10, -10.0f when v is the floor itself (the correctly rounded
+ *     value there); L = ln(v) for LN.
+ *   Post.    WHISPER: mx = the largest L of all T * M values of the utterance; L = max(L, mx - 8.0f); out = (L + 4.0f) *
+ *     0.25f.  LOG10 and LN deliver L.
+ *   Output.  Rows [T][M], frame-major, at out_rows[u] (Whisper's own layout is the transpose, [M][T]).
+ * Rows are an exact function of the utterance's samples, the window and the configuration: they do not depend on the other
+ * utterances, on the run, on buffer placement, or on whether the utterance starts at an odd sample.
+ * Entries.  mfx_batch_frames, mfx_batch_plan and mfx_batch_plan_rates use the frame rule above; mfx_batch_run_device / _host,
+ * mfx_batch_overlap, mfx_batch_set_transform and mfx_batch_set_vad work as on any handle; mfx_batch_set_alphas is refused with
+ * MFX_ERR_CONFIG (there is no warped Slaney table) and mfx_set_alpha has no effect; the speaker list and the online
+ * normaliser are refused as on any norm = NONE handle. */
+enum { MFX_LOGMEL_WHISPER = 0, MFX_LOGMEL_LOG10 = 1, MFX_LOGMEL_LN = 2 };
 
 /* mfx_config.engine bits */
 #define MFX_ENGINE_NO_FRONT1024 1 /* 1024-point short-window configurations stay on the generic long-transform kernel  */
@@ -612,6 +654,19 @@ int mfx_host_online_norm(const float *rows, int64_t T, int32_t pitch, int32_t Wn
                          int32_t prior_frames, int64_t prior_count, const double *prior_acc, float *out);
 /* frame count, integer arithmetic (parambase.cpp:16-19 without the float32 division) */
 int64_t mfx_host_frame_count(int64_t samples, int32_t window_size, int32_t shift);
+/* STFT log-mel (MFX_METHOD_STFT_LOGMEL) tables as uploaded, and its frame rule.  mfx_host_slaney_mel_table: weights
+ * [num_banks][dft_size / 2 + 1], beg / len [num_banks] the non-zero span of every row (len 0: none).  mfx_host_stft_basis:
+ * cos_sin [2][dft_size / 2 + 1][dft_size], the windowed cosine rows, then the negated windowed sine rows.  MFX_ERR_ARG outside
+ * the limits of the method (dft_size even in 32 .. 512, num_banks 1 .. 128, shift 1 .. dft_size, the frequency rule). */
+int mfx_host_slaney_mel_table(int32_t num_banks, int32_t dft_size, float sample_rate, float low_freq, float high_freq,
+                              float *weights, int32_t *beg, int32_t *len);
+int mfx_host_stft_basis(int32_t dft_size, const float *window, float *cos_sin);
+int64_t mfx_host_stft_frame_count(int64_t samples, int32_t dft_size, int32_t shift);
+/* Frames per block (*tile_rows: 64, 32 or 16) that k_stft_mel takes for a shape, and ALL the LDS bytes such a block asks for (the
+ * kernel has no static LDS beside them): what mfx_create holds against the 160 KB of a gfx950 block.  MFX_ERR_ARG outside the
+ * method's limits, MFX_ERR_CONFIG if no tile fitted.  UNSTABLE, a test / inspection aid only: the tiling is the kernel's private
+ * matter. */
+int64_t mfx_host_stft_lds_bytes(int32_t dft_size, int32_t shift, int32_t num_banks, int32_t *tile_rows);
 
 /* ---- test taps (device -> host copies of intermediate tables; used by the parity tests) ---- */
 /* kind: 0 = mel table [2][fft_size] floats, 1 = filter_beg [num_banks+2] int32,

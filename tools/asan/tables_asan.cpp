@@ -163,6 +163,32 @@ int main()
         rates[3] = 500;
         if (mfx::resample_layout((int32_t)lens.size(), lens.data(), rates.data(), 16000, nullptr, nullptr) != -1) return 1;
     }
+    // STFT log-mel: exactly-sized basis, Slaney table and operand buffers at the corners of the method's limits
+    int ns = 0;
+    for (int N : {32, 34, 64, 400, 414, 416, 510, 512})
+        for (int M : {1, 8, 80, 128}) {
+            const int K1 = N / 2 + 1;
+            std::vector<float> win((size_t)N, 0.5f), basis((size_t)2 * K1 * N), w((size_t)M * K1), ops;
+            std::vector<int32_t> beg((size_t)M), len((size_t)M);
+            mfx::build_stft_basis(N, win.data(), basis.data());
+            for (float sr : {8000.f, 16000.f}) {
+                mfx::build_slaney_mel(M, N, sr, 0.f, sr / 2, w.data(), beg.data(), len.data());
+                for (int m = 0; m < M; ++m)
+                    if (beg[m] < 0 || len[m] < 0 || beg[m] + len[m] > K1) return 1;
+            }
+            const int nbt = (K1 + 15) / 16, tb = nbt < 13 ? nbt : 13;
+            mfx::build_stft_operands(basis.data(), N, tb, ops);
+            if (ops.size() != (size_t)((nbt + tb - 1) / tb) * ((N + 3) / 4) * 2 * tb * 64) return 1;
+            double a = 0, b = 0; // every basis value appears exactly once among the operands (the sums run in another order)
+            size_t na = 0, nb = 0;
+            for (float v : ops) a += (double)v * v, na += v != 0.f;
+            for (float v : basis) b += (double)v * v, nb += v != 0.f;
+            if (na != nb || !(a >= b * (1 - 1e-9) && a <= b * (1 + 1e-9))) return 1;
+            ++ns;
+        }
+    for (long s : {0L, 200L, 201L, 159L, 160L, 1L << 40})
+        if (mfx::stft_frame_count(s, 400, 160) != (s <= 200 ? 0 : s / 160)) return 1;
+    std::printf("tables_asan: %d STFT table sets; ", ns);
     std::printf("tables_asan: %d resampler tables; ", nv);
     std::printf("tables_asan: %d configurations, %d front-end tables, %d run lists, %d transform operand sets, %d session push sequences clean\n",
                 n, nt, nr, nx, nq);
