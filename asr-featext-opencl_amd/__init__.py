@@ -38,6 +38,7 @@ from .mfcc import (  # noqa: F401
     host_session_step,
     host_speaker_lists,
     host_online_norm,
+    host_pitch,
     SPK_POOL,
     SPK_PRIOR_ONLY,
     VAD_FLAGS,

@@ -1,8 +1,8 @@
 // mfx_batch.cpp -- the runner of the batch interface of include/mfx.h: a planned batch (mfx_batch_plan.cpp) with what is
 // attached to it (mfx_batch_attach.cpp) through the device and host entries, the overlap of a batch's tail with the next
 // front end, the pinned allocator.  Which front end runs is choose_front's decision and launch_front's work (mfx_api.cpp).
-// This file owns `batch.ov` and `batch.host`; of the rest of `batch` and of `fuse` it only reads, but for spk.ran and the
-// spectrum slab it grows.  It names no field of `st` or `sweep`.
+// This file owns `batch.ov` and `batch.host`; of the rest of `batch` and of `fuse` it only reads, but for spk.ran, vad.ran, pt.ran
+// and the spectrum slab it grows.  It names no field of `st` or `sweep`.
 #include "mfx_handle.h"
 
 using namespace mfx;
@@ -235,6 +235,33 @@ int run_front(mfx_handle *h, FrontParams &p, const RunMode &m, int u0, int u1, i
     return MFX_OK;
 }
 
+// the pitch track of a run: k_pitch_nccf and k_pitch_track over the utterance range, on the handle's stream behind the front
+// end (never the tail's: once the handle's stream has passed them the PCM may be reused); `pcm` is what the front end read
+int run_pitch(mfx_handle *h, const int16_t *pcm, int u0, int u1)
+{
+    BatchState &B = h->batch;
+    BatchState::Pitch &pt = B.pt;
+    PitchParams pp{};
+    pp.pcm = pcm;
+    pp.channels = h->channels;
+    pp.utt = pt.d_utt.p;
+    pp.segs = B.d_segs.p;
+    pp.utt_tile0 = pt.d_utt_tile0.p, pp.tile_utt = pt.d_tile_utt.p;
+    pp.tile_first = pt.utt_tile0[u0], pp.n_tiles = pt.utt_tile0[u1] - pt.utt_tile0[u0];
+    pp.tile_frames = pt.tile_frames;
+    pp.u0 = u0, pp.u1 = u1;
+    pp.window = pt.window, pp.shift = h->S, pp.lag_min = pt.lag_min, pp.lag_max = pt.lag_max, pp.K = pt.K, pp.J = pt.J;
+    pp.span_pad = pitch_span_pad(h->S);
+    pp.groups = pitch_groups(pt.lag_min, pt.lag_max);
+    pp.ballast = pt.ballast, pp.penalty = pt.penalty;
+    pp.c1 = (float)(1.0 / (32768.0 * (double)(pt.window + pt.lag_max)));
+    pp.wt = pt.d_wt.p, pp.lg = pt.d_lg.p;
+    pp.nccf = pt.d_nccf.p, pp.bp = pt.d_bp.p, pp.pitch = pt.d_pitch.p, pp.index = pt.d_index.p;
+    HIP_TRY(h, launch_pitch(pp, h->stream));
+    pt.ran = true;
+    return MFX_OK;
+}
+
 // the normaliser of a run over `groups` column groups of m.d_out: the online attachment's kernels while it is in force (raw
 // rows from m.d_pre), the speaker list's while one is (the run then covers the whole batch, mfx_batch_run_host does not
 // slice), else every utterance's own statistics
@@ -360,6 +387,7 @@ int batch_run_range(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_tot
     }
     if (B.total_rows == 0) {
         B.vad.ran = B.vad.on; // (nothing to decide: the read-back returns what the setter left, no voiced row)
+        B.pt.ran = B.pt.on;   // (no row to track: the read-back copies nothing)
         return MFX_OK;
     }
     if ((rc = check_layout(h, d_pcm, pcm_samples_total, B.utt_off, B.utt_len, u0, u1)) != MFX_OK) return rc;
@@ -367,6 +395,7 @@ int batch_run_range(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_tot
     if ((rc = refresh_mel(h)) != MFX_OK) return rc;
     const int32_t c0 = B.utt_chunk0[u0], c1 = B.utt_chunk0[u1]; // chunk range of the utterance range
     if (c1 <= c0) { // a range without a frame: nothing to compute, but the VAD's counts and prefix are still to be written
+        B.pt.ran = B.pt.ran || B.pt.on; // (the pitch track has no row to write either)
         if (!B.vad.on) return MFX_OK;
         RunMode none{};
         none.d_last = B.vad.d_rows.p, none.d_final = d_out;
@@ -375,7 +404,7 @@ int batch_run_range(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_tot
     }
     if ((B.xf.on && B.xf.d_y.n < (size_t)B.total_rows * h->width) || (h->traps && B.d_logmel.n < (size_t)B.total_rows * B.mel_pitch) ||
         (B.vad.on && B.vad.mode != MFX_VAD_FLAGS && B.vad.d_rows.n < (size_t)B.total_rows * batch_out_width(h)) ||
-        (B.on.on && B.on.d_raw.n < (size_t)B.total_rows * h->width))
+        (B.on.on && B.on.d_raw.n < (size_t)B.total_rows * h->width) || (B.pt.on && B.pt.d_nccf.n < (size_t)B.total_rows * B.pt.K))
         return fail(h, MFX_ERR_STATE, "batch not planned");
 
     FrontParams p;
@@ -392,6 +421,7 @@ int batch_run_range(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_tot
         p.feat_pitch = h->traps ? B.mel_pitch : h->width;
     }
     if ((rc = run_front(h, p, m, u0, u1, c0, c1)) != MFX_OK) return rc;
+    if (B.pt.on && (rc = run_pitch(h, d_pcm, u0, u1)) != MFX_OK) return rc;
     if ((rc = run_tail(h, m, u0, u1)) != MFX_OK) return rc;
     if (whole) ++B.ov.seq;
     return MFX_OK;

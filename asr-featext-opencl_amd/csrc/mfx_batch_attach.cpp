@@ -1,7 +1,7 @@
 // mfx_batch_attach.cpp -- what a caller attaches to a planned batch (include/mfx.h): per-utterance warp factors, a splice +
-// affine transform, a speaker list, the energy VAD, the online normaliser.  Each is tied to the plan (mfx_batch_plan_rates'
-// converter is the sixth, and is the planner's); BatchState::detach drops the five of this file.  This file owns `batch.va`,
-// `batch.xf`, `batch.spk`, `batch.vad` and `batch.on`.
+// affine transform, a speaker list, the energy VAD, the online normaliser, the pitch track.  Each is tied to the plan
+// (mfx_batch_plan_rates' converter is the seventh, and is the planner's); BatchState::detach drops the six of this file.  This
+// file owns `batch.va`, `batch.xf`, `batch.spk`, `batch.vad`, `batch.on` and `batch.pt`.
 #include "mfx_handle.h"
 
 #include <cmath>
@@ -379,5 +379,102 @@ extern "C" int mfx_batch_vad_device(const mfx_handle *h, const uint8_t **d_flags
     if (d_flags) *d_flags = h->batch.vad.d_flags.p;
     if (d_voiced) *d_voiced = h->batch.vad.d_voiced.p;
     if (d_packed_row0) *d_packed_row0 = h->batch.vad.d_packed.p;
+    return MFX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// pitch track ("Pitch track")
+// ------------------------------------------------------------------------------------------------
+
+extern "C" int mfx_batch_set_pitch(mfx_handle *h, int32_t window, int32_t lag_min, int32_t lag_max, float ballast, float lag_cost,
+                                   float penalty, int32_t max_jump)
+{
+    MFX_DEVICE_ENTRY(h);
+    BatchState &B = h->batch;
+    if (h->stft) return fail(h, MFX_ERR_CONFIG, "mfx_batch_set_pitch: an STFT log-mel handle frames its utterances centred");
+    if (!B.planned) return fail(h, MFX_ERR_STATE, "mfx_batch_set_pitch: no batch is planned");
+    PitchShape s;
+    if (!pitch_shape(window == 0 ? h->cfg.window_size : window, lag_min, lag_max, ballast, lag_cost, penalty, max_jump, s))
+        return fail(h, MFX_ERR_ARG,
+                    "mfx_batch_set_pitch: window 32 .. 1024, lags 2 .. 1024 (at most 512 of them), finite ballast, lag_cost in [0, 1] "
+                    "and penalty >= 0, max_jump 0 .. 511");
+    const int tile_frames = pitch_tile_frames(s.window, s.lag_max, h->S);
+    std::vector<int32_t> tile0, tile_utt;
+    if (!build_pitch_layout(B.utt_frames.data(), B.n_utt, tile_frames, tile0, tile_utt)) return fail(h, MFX_ERR_ARG, "batch too long");
+    PitchParams probe{};
+    probe.channels = h->channels, probe.tile_frames = tile_frames;
+    probe.window = s.window, probe.shift = h->S, probe.lag_min = s.lag_min, probe.lag_max = s.lag_max, probe.K = s.K, probe.J = s.J;
+    probe.span_pad = pitch_span_pad(h->S);
+    probe.groups = pitch_groups(s.lag_min, s.lag_max);
+    if (!pitch_params_ok(probe)) return fail(h, MFX_ERR_ARG, "mfx_batch_set_pitch: no tile of k_pitch_nccf fits the LDS for this shift");
+    std::vector<float> wt, lg;
+    build_pitch_tables(s, lag_cost, wt, lg);
+    std::vector<int64_t> utt((size_t)2 * B.n_utt);
+    for (int u = 0; u < B.n_utt; ++u) utt[2 * (size_t)u] = B.utt_off[u], utt[2 * (size_t)u + 1] = B.utt_len[u];
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int rc = mfx_synchronize(h); // (a run in flight may read the lists replaced below)
+    if (rc != MFX_OK) return rc;
+    BatchState::Pitch &pt = B.pt;
+    pt.drop();
+    // (everything mfx_batch_run_device needs is allocated here: that entry never allocates)
+    const size_t rows = (size_t)B.total_rows;
+    auto all = [&]() -> int {
+        HIP_TRY(h, h->upload(pt.d_utt_tile0, tile0));
+        HIP_TRY(h, h->upload(pt.d_tile_utt, tile_utt));
+        HIP_TRY(h, h->upload(pt.d_utt, utt));
+        HIP_TRY(h, h->upload(pt.d_wt, wt));
+        HIP_TRY(h, h->upload(pt.d_lg, lg));
+        HIP_TRY(h, pt.d_nccf.alloc(rows * s.K));
+        HIP_TRY(h, pt.d_bp.alloc(rows * s.K));
+        HIP_TRY(h, pt.d_pitch.alloc(rows * 2));
+        HIP_TRY(h, pt.d_index.alloc(rows));
+        return MFX_OK;
+    };
+    if (const int ra = all(); ra != MFX_OK) { // (it did not fit: nothing of it stays)
+        pt.release();
+        return ra;
+    }
+    pt.utt_tile0.swap(tile0);
+    pt.window = s.window, pt.lag_min = s.lag_min, pt.lag_max = s.lag_max, pt.K = s.K, pt.J = s.J, pt.tile_frames = tile_frames;
+    pt.ballast = ballast, pt.penalty = penalty;
+    pt.on = true;
+    return MFX_OK;
+}
+
+extern "C" int mfx_batch_clear_pitch(mfx_handle *h)
+{
+    MFX_DEVICE_ENTRY(h);
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int rc = mfx_synchronize(h); // (a run in flight may read what is released below)
+    if (rc != MFX_OK) return rc;
+    h->batch.pt.drop();
+    h->batch.pt.release();
+    return MFX_OK;
+}
+
+extern "C" int mfx_batch_pitch_read(mfx_handle *h, float *pitch, int32_t *index, float *nccf)
+{
+    MFX_DEVICE_ENTRY(h);
+    const BatchState::Pitch &pt = h->batch.pt;
+    if (!pt.on) return fail(h, MFX_ERR_STATE, "mfx_batch_pitch_read: no pitch track is in force");
+    if (!pt.ran) return fail(h, MFX_ERR_STATE, "mfx_batch_pitch_read: no batch has run since the pitch track was set");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int rc = mfx_synchronize(h);
+    if (rc != MFX_OK) return rc;
+    const size_t rows = (size_t)h->batch.total_rows;
+    if (rows == 0) return MFX_OK;
+    if (pitch) HIP_TRY(h, hipMemcpy(pitch, pt.d_pitch.p, rows * 2 * sizeof(float), hipMemcpyDeviceToHost));
+    if (index) HIP_TRY(h, hipMemcpy(index, pt.d_index.p, rows * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (nccf) HIP_TRY(h, hipMemcpy(nccf, pt.d_nccf.p, rows * pt.K * sizeof(float), hipMemcpyDeviceToHost));
+    return MFX_OK;
+}
+
+extern "C" int mfx_batch_pitch_device(const mfx_handle *h, const float **d_pitch, const int32_t **d_index)
+{
+    if (!h) return MFX_ERR_ARG;
+    if (h->planning) return MFX_ERR_DEVICE;
+    if (!h->batch.pt.on) return MFX_ERR_STATE;
+    if (d_pitch) *d_pitch = h->batch.pt.d_pitch.p;
+    if (d_index) *d_index = h->batch.pt.d_index.p;
     return MFX_OK;
 }

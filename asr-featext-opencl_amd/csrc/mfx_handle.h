@@ -3,8 +3,8 @@
 //   mfx_api.cpp    lifetime, tables, kernel choice and front-end dispatch, profiling, test taps (writes the shared part)
 //   mfx_stream.cpp the streaming state machine and its host copies         (owns `st` and `sweep`)
 //   mfx_batch_plan.cpp   the batch planner, the rates planner, the fused-delta plan (owns `batch`'s plan, `batch.rs`, `fuse`)
-//   mfx_batch_attach.cpp what is attached to a plan: warp factors, transform, speakers, VAD, online normaliser (owns `batch.va`,
-//                        `.xf`, `.spk`, `.vad`, `.on`)
+//   mfx_batch_attach.cpp what is attached to a plan: warp factors, transform, speakers, VAD, online normaliser, pitch track (owns
+//                        `batch.va`, `.xf`, `.spk`, `.vad`, `.on`, `.pt`)
 //   mfx_batch.cpp        the batch runner, device and host entries, overlap   (owns `batch.ov` and `batch.host`)
 //   mfx_sessions_host.cpp the session entries: many live streams per push       (owns `sess`)
 #pragma once
@@ -165,7 +165,7 @@ struct BatchState {
     int tiles_max = 0;
     bool aligned = true;                 // frames on aligned sample pairs (fill_front / choose_front read it)
 
-    // Six attachments, each tied to the plan: a new plan drops them.  drop() switches one off and releases what is not kept
+    // Seven attachments, each tied to the plan: a new plan drops them.  drop() switches one off and releases what is not kept
     // for the next one (the grown-never-shrunk scratch stays).
 
     // sample-rate conversion (mfx_batch_plan_rates): while on, the run converts the caller's array into d_pcm with one
@@ -256,9 +256,31 @@ struct BatchState {
         DevBuf<float> d_raw;             // [total_rows][width] (grown, never shrunk: only mfx_batch_clear_online_norm releases it)
         void drop() { on = false; }
     } on;
+    // pitch track (mfx_batch_set_pitch): while on, k_pitch_nccf and k_pitch_track follow the front end on the handle's stream
+    // and fill the handle-owned arrays below, indexed by the plan's rows; d_out is untouched
+    struct Pitch {
+        bool on = false;
+        bool ran = false;                // a run has filled the arrays since the setter
+        int32_t window = 0, lag_min = 0, lag_max = 0, K = 0, J = 0, tile_frames = 0;
+        float ballast = 0.f, penalty = 0.f;
+        std::vector<int32_t> utt_tile0;  // [n_utt + 1] (build_pitch_layout)
+        DevBuf<int32_t> d_utt_tile0, d_tile_utt;
+        DevBuf<int64_t> d_utt;           // [n_utt][2] first sample and samples of every utterance, as the front end reads them
+        DevBuf<float> d_wt, d_lg;        // [K]
+        DevBuf<float> d_nccf;            // [total_rows][K]
+        DevBuf<uint16_t> d_bp;           // [total_rows][K]
+        DevBuf<float> d_pitch;           // [total_rows][2]
+        DevBuf<int32_t> d_index;         // [total_rows]
+        void drop() { on = false, ran = false; }
+        void release()
+        {
+            d_utt_tile0.release(), d_tile_utt.release(), d_utt.release(), d_wt.release(), d_lg.release(), d_nccf.release(), d_bp.release();
+            d_pitch.release(), d_index.release();
+        }
+    } pt;
     // what a new utterance list invalidates (the converter is mfx_batch_plan's to drop: mfx_batch_plan_rates plans through
     // plan_batch too)
-    void detach() { va.drop(), xf.drop(), spk.drop(), vad.drop(), on.drop(); }
+    void detach() { va.drop(), xf.drop(), spk.drop(), vad.drop(), on.drop(), pt.drop(); }
 
     // ---- not tied to the plan
     // optional overlap of the delta/normalisation tail of batch i with the front end of batch i+1 (mfx_batch_overlap)

@@ -1,4 +1,4 @@
-// mfx_kernels.h -- launch interface of the gfx950 kernels (implemented in mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip, mfx_plp.hip, mfx_traps.hip, mfx_xform.hip, mfx_sessions.hip, mfx_resample.hip, mfx_speakers.hip, mfx_vad.hip, mfx_onorm.hip, mfx_stft.hip: one translation unit per kernel family).
+// mfx_kernels.h -- launch interface of the gfx950 kernels (implemented in mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip, mfx_plp.hip, mfx_traps.hip, mfx_xform.hip, mfx_sessions.hip, mfx_resample.hip, mfx_speakers.hip, mfx_vad.hip, mfx_onorm.hip, mfx_stft.hip, mfx_pitch.hip: one translation unit per kernel family).
 //
 // Kernel inventory and the reference stage each one replaces:
 //   spectrum512 / fused512   segmenter.cl kernelSegmentWindow + AppleFFT fft0 + mfcc.cl kernelTranspose
@@ -14,6 +14,7 @@
 //                            its files at the one rate its model was trained at)
 //   vad_*                    energy voice-activity decision + voiced-frame selection of finished rows (no reference analogue: the
 //                            reference hands every frame to its consumer)
+//   pitch_*                  pitch track beside the rows of a batch run: NCCF of the PCM + Viterbi path (no reference analogue)
 //   onorm_*                  online (causal, sliding-window) CMN / CVN of the batch and session entries (no reference analogue: its
 //                            NormalizerCPU keeps one block's statistics)
 //   stft_mel / stft_post     the STFT log-mel front end: exact-length DFT of centred frames on the matrix pipe, power, Slaney mel, log;
@@ -398,6 +399,35 @@ struct VadParams {
     float *out;            // modes 1, 2: the caller's array, [total_rows][width]; never `rows`
     int32_t width;
 };
+
+// Pitch track (mfx_batch_set_pitch; mfx_pitch.hip; DESIGN.md, "Pitch track").  Tiles are runs of tile_frames consecutive
+// frames of one utterance, numbered through the batch in utterance order (build_pitch_layout); every per-row array is indexed
+// by the plan's rows, so that a run over an utterance range fills its part and leaves the rest.
+struct PitchParams {
+    const int16_t *pcm;    // the array the front end reads (the converted scratch under a rates plan)
+    int32_t channels;      // 1, or 2: one 32-bit word per sample, p = (L + R) >> 1
+    const int64_t *utt;    // [n_utt][2]: first sample (per channel) and samples of every utterance
+    const Segment *segs;   // [n_utt]: uses out_row0 / n_out
+    const int32_t *utt_tile0, *tile_utt; // [n_utt + 1], [tiles]
+    int32_t tile_first, n_tiles;         // = utt_tile0[u0], utt_tile0[u1] - utt_tile0[u0]
+    int32_t tile_frames;   // frames per tile (pitch_tile_frames)
+    int32_t u0, u1;        // the utterance range of this run
+    int32_t window, shift, lag_min, lag_max, K, J;
+    int32_t span_pad;      // pitch_span_pad(shift)
+    int32_t groups;        // pitch_groups(lag_min, lag_max): frames a wave of k_pitch_nccf takes at a time, 1 or 2
+    float ballast, penalty;
+    float c1;              // (float)(1 / (32768 (window + lag_max)))
+    const float *wt, *lg;  // [K]
+    float *nccf;           // [total_rows][K]: k_pitch_nccf leaves e(l_k) there on its way, then rho
+    uint16_t *bp;          // [total_rows][K] back-pointers (the state k' itself)
+    float *pitch;          // [total_rows][2] lag, rho
+    int32_t *index;        // [total_rows]
+};
+bool pitch_params_ok(const PitchParams &p);
+int pitch_groups(int lag_min, int lag_max);
+size_t pitch_nccf_lds_bytes(const PitchParams &p);
+// k_pitch_nccf over the tiles, then k_pitch_track over the utterances of the range
+hipError_t launch_pitch(const PitchParams &p, hipStream_t stream);
 
 // Online CMN / CVN (mfx_batch_set_online_norm, mfx_sessions_set_online_norm; mfx_onorm.hip; DESIGN.md, "Online
 // normalisation").  Chunks are runs of 32 rows of one utterance, numbered through the batch in utterance order; every

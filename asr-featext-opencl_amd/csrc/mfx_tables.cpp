@@ -838,9 +838,196 @@ bool host_online_norm(const float *rows, int64_t T, int pitch, int Wn, int kind,
     return true;
 }
 
+// ---- pitch track (include/mfx.h, mfx_batch_set_pitch)
+
+bool pitch_shape(int window, int lag_min, int lag_max, float ballast, float lag_cost, float penalty, int max_jump, PitchShape &s)
+{
+    if (window < 32 || window > 1024 || lag_min < 2 || lag_max > 1024) return false;
+    const int64_t K = (int64_t)lag_max - lag_min + 1;
+    if (K < 1 || K > 512) return false;
+    if (!std::isfinite(ballast) || !std::isfinite(lag_cost) || !std::isfinite(penalty)) return false;
+    if (ballast < 0.f || lag_cost < 0.f || lag_cost > 1.f || penalty < 0.f) return false;
+    if (max_jump < 0 || max_jump > 511) return false;
+    const int top = std::max((int)K - 1, 1);
+    s.window = window, s.lag_min = lag_min, s.lag_max = lag_max, s.K = (int)K;
+    s.J = max_jump == 0 ? top : std::min(max_jump, top);
+    return true;
+}
+
+void build_pitch_tables(const PitchShape &s, float lag_cost, std::vector<float> &wt, std::vector<float> &lg)
+{
+    wt.assign((size_t)s.K, 0.f), lg.assign((size_t)s.K, 0.f);
+    for (int k = 0; k < s.K; ++k) {
+        const double l = (double)(s.lag_min + k);
+        wt[(size_t)k] = (float)(1.0 - (double)lag_cost * l / (double)s.lag_max);
+        lg[(size_t)k] = (float)std::log(l);
+    }
+}
+
+int pitch_span_pad(int shift) { return shift >= 64 ? (2 - shift) & 63 : 0; }
+
+int pitch_span_slots(int window, int lag_max, int shift, int frames)
+{
+    const int64_t last = (int64_t)(frames - 1) * shift + window + lag_max - 1; // the span's last sample
+    const int64_t slots = last + (int64_t)pitch_span_pad(shift) * (last / shift) + 1;
+    return slots > 0x7fffffff ? 0x7fffffff : (int)slots;
+}
+
+int pitch_tile_frames(int window, int lag_max, int shift)
+{
+    int f = 64;
+    while (f > 1 && pitch_span_slots(window, lag_max, shift, f) > kPitchSpanMax) --f;
+    return f;
+}
+
+bool build_pitch_layout(const int64_t *frames, int n_utt, int tile_frames, std::vector<int32_t> &utt_tile0, std::vector<int32_t> &tile_utt)
+{
+    if (n_utt < 0 || tile_frames < 1) return false;
+    int64_t tiles = 0;
+    for (int u = 0; u < n_utt; ++u) {
+        if (frames[u] < 0) return false;
+        tiles += (frames[u] + tile_frames - 1) / tile_frames;
+        if (tiles > 0x7ffffff0) return false;
+    }
+    utt_tile0.assign((size_t)n_utt + 1, 0);
+    tile_utt.assign((size_t)tiles, 0);
+    int32_t t = 0;
+    for (int u = 0; u < n_utt; ++u) {
+        utt_tile0[u] = t;
+        for (int64_t r = 0; r < frames[u]; r += tile_frames) tile_utt[(size_t)t++] = u;
+    }
+    utt_tile0[n_utt] = t;
+    return true;
+}
+
+// Every float32 and double operation below is a statement of its own and this file is compiled with -ffp-contract=off; the
+// correlation is one std::fmaf chain per value.
+bool host_pitch(const int16_t *pcm, int64_t n, int channels, int64_t T, int shift, int window, int lag_min, int lag_max, float ballast,
+                float lag_cost, float penalty, int max_jump, float *pitch, int32_t *index, float *nccf)
+{
+    PitchShape s;
+    if (!pitch_shape(window, lag_min, lag_max, ballast, lag_cost, penalty, max_jump, s)) return false;
+    if (n < 0 || T < 0 || T > 0x7fffffff || shift < 1 || (channels != 1 && channels != 2) || (n > 0 && !pcm)) return false;
+    if (T == 0) return true;
+    const int W = s.window, K = s.K, J = s.J, Ls = W + s.lag_max;
+    std::vector<float> wt, lg;
+    build_pitch_tables(s, lag_cost, wt, lg);
+    std::vector<float> own;
+    if (!nccf) {
+        own.resize((size_t)T * K);
+        nccf = own.data();
+    }
+    // ---- the NCCF rows
+    const float c1 = (float)(1.0 / (32768.0 * (double)Ls));
+    std::vector<int32_t> p((size_t)Ls);
+    std::vector<float> z((size_t)Ls);
+    std::vector<double> P((size_t)Ls + 1);
+    for (int64_t t = 0; t < T; ++t) {
+        const int64_t i0 = t * shift;
+        int64_t sI = 0;
+        for (int j = 0; j < Ls; ++j) {
+            const int64_t i = i0 + j;
+            int32_t v = 0;
+            if (i < n) v = channels == 2 ? ((int32_t)pcm[2 * i] + (int32_t)pcm[2 * i + 1]) >> 1 : (int32_t)pcm[i];
+            p[(size_t)j] = v;
+            sI += v;
+        }
+        const float m = (float)sI * c1;
+        P[0] = 0.0;
+        for (int j = 0; j < Ls; ++j) {
+            const float x = (float)p[(size_t)j] * 0x1p-15f;
+            const float zj = x - m;
+            const float q = zj * zj;
+            z[(size_t)j] = zj;
+            P[(size_t)j + 1] = P[(size_t)j] + (double)q;
+        }
+        const float e0 = (float)(P[(size_t)W] - P[0]);
+        float *rho = nccf + (size_t)t * K;
+        for (int k = 0; k < K; ++k) {
+            const int l = s.lag_min + k;
+            float c = 0.f;
+            for (int j = 0; j < W; ++j) c = std::fmaf(z[(size_t)j], z[(size_t)(j + l)], c);
+            const float el = (float)(P[(size_t)(l + W)] - P[(size_t)l]);
+            const float prod = e0 * el;
+            const float sden = prod + ballast;
+            float r = 0.f;
+            if (sden > 0.f) {
+                const float root = std::sqrt(sden);
+                r = c / root;
+            }
+            rho[k] = r;
+        }
+    }
+    // ---- the track
+    std::vector<uint16_t> bp((size_t)T * K);
+    std::vector<float> fwd((size_t)K), a((size_t)K);
+    for (int64_t t = 0; t < T; ++t) {
+        const float *rho = nccf + (size_t)t * K;
+        for (int k = 0; k < K; ++k) {
+            const float rw = rho[k] * wt[(size_t)k];
+            const float loc = 1.0f - rw;
+            if (t == 0) {
+                a[(size_t)k] = loc;
+                continue;
+            }
+            const int lo = std::max(0, k - J), hi = std::min(K - 1, k + J);
+            float best = 0.f;
+            int bk = -1;
+            for (int kk = lo; kk <= hi; ++kk) {
+                const float d = lg[(size_t)k] - lg[(size_t)kk];
+                const float pd = penalty * d;
+                const float tr = pd * d;
+                const float cand = fwd[(size_t)kk] + tr;
+                if (bk < 0 || cand < best) best = cand, bk = kk;
+            }
+            a[(size_t)k] = loc + best;
+            bp[(size_t)t * K + k] = (uint16_t)bk;
+        }
+        int km = 0;
+        for (int k = 1; k < K; ++k)
+            if (a[(size_t)k] < a[(size_t)km]) km = k;
+        const float mt = a[(size_t)km];
+        for (int k = 0; k < K; ++k) fwd[(size_t)k] = a[(size_t)k] - mt;
+    }
+    int k = 0;
+    for (int kk = 1; kk < K; ++kk)
+        if (fwd[(size_t)kk] < fwd[(size_t)k]) k = kk;
+    for (int64_t t = T - 1; t >= 0; --t) {
+        const float *rho = nccf + (size_t)t * K;
+        float delta = 0.f;
+        if (k > 0 && k < K - 1) {
+            const float ra = rho[k - 1], rb = rho[k], rc = rho[k + 1];
+            const float d1 = ra - rb, d2 = rc - rb;
+            const float den = d1 + d2;
+            if (den < 0.f) {
+                const float num = ra - rc;
+                const float half = 0.5f * num;
+                delta = half / den;
+                delta = delta < -0.5f ? -0.5f : delta > 0.5f ? 0.5f : delta;
+            }
+        }
+        if (index) index[t] = k;
+        if (pitch) {
+            pitch[2 * t] = (float)(s.lag_min + k) + delta;
+            pitch[2 * t + 1] = rho[k];
+        }
+        if (t > 0) k = bp[(size_t)t * K + k];
+    }
+    return true;
+}
+
 } // namespace mfx
 
 // (the C entry of include/mfx.h, here beside its definition so that the stand-alone sanitizer program links it without HIP)
+extern "C" int mfx_host_pitch(const int16_t *pcm, int64_t n, int32_t channels, int64_t T, int32_t shift, int32_t window, int32_t lag_min,
+                              int32_t lag_max, float ballast, float lag_cost, float penalty, int32_t max_jump, float *pitch, int32_t *index,
+                              float *nccf)
+{
+    return mfx::host_pitch(pcm, n, channels, T, shift, window, lag_min, lag_max, ballast, lag_cost, penalty, max_jump, pitch, index, nccf)
+               ? 0
+               : -7 /* MFX_ERR_ARG */;
+}
+
 extern "C" int mfx_host_online_norm(const float *rows, int64_t T, int32_t pitch, int32_t Wn, int32_t kind, int32_t window,
                                     int32_t prior_frames, int64_t prior_count, const double *prior_acc, float *out)
 {

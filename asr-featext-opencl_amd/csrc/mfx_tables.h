@@ -108,6 +108,29 @@ bool host_online_norm(const float *rows, int64_t T, int pitch, int Wn, int kind,
 bool build_vad_layout(const int64_t *frames, int n_utt, std::vector<int32_t> &utt_tile0, std::vector<int32_t> &tile_utt,
                       std::vector<int32_t> &utt_chunk0, std::vector<int32_t> &chunk_utt);
 
+// Pitch track (mfx_batch_set_pitch; DESIGN.md, "Pitch track").  pitch_shape: the limits of include/mfx.h on the seven
+// parameters (window as resolved: never 0); fills K = lag_max - lag_min + 1 states and the resolved jump J.  False outside them.
+struct PitchShape {
+    int window, lag_min, lag_max, K, J;
+};
+bool pitch_shape(int window, int lag_min, int lag_max, float ballast, float lag_cost, float penalty, int max_jump, PitchShape &s);
+// wt[k] = (float)(1 - lag_cost * l / lag_max), lg[k] = (float)ln(l), l = lag_min + k: double, rounded once
+void build_pitch_tables(const PitchShape &s, float lag_cost, std::vector<float> &wt, std::vector<float> &lg);
+// k_pitch_nccf's tiles: runs of pitch_tile_frames consecutive frames of one utterance (at most 64, fewer while the tile's
+// PCM span would pass kPitchSpanMax staged samples), numbered through the batch in utterance order as the VAD's are.
+// pitch_span_pad: int16 slots left empty behind every `shift` staged samples, so that the frames of a tile start on
+// different LDS banks; pitch_span_slots: the slots the span of `frames` frames takes with them.
+constexpr int kPitchSpanMax = 24576;
+int pitch_span_pad(int shift);
+int pitch_span_slots(int window, int lag_max, int shift, int frames);
+int pitch_tile_frames(int window, int lag_max, int shift);
+bool build_pitch_layout(const int64_t *frames, int n_utt, int tile_frames, std::vector<int32_t> &utt_tile0, std::vector<int32_t> &tile_utt);
+// The definition of include/mfx.h on host memory, for ONE utterance of n samples per channel and T frames at `shift`:
+// pitch [T][2] = (lag, rho), index [T], nccf [T][K]; any of them may be null.  False -- and nothing written -- on an argument
+// outside the limits.
+bool host_pitch(const int16_t *pcm, int64_t n, int channels, int64_t T, int shift, int window, int lag_min, int lag_max, float ballast,
+                float lag_cost, float penalty, int max_jump, float *pitch, int32_t *index, float *nccf);
+
 // exp(-2*pi*i*k/n) for k in [0, count), evaluated in double and rounded once to float.
 void build_twiddles(int n, int count, std::vector<float> &re_im_interleaved);
 

@@ -85,6 +85,7 @@ EXPORTED_SYMBOLS = (
     "mfx_sessions_clear_online_norm", "mfx_host_online_norm",
     "mfx_host_slaney_mel_table", "mfx_host_stft_basis", "mfx_host_stft_frame_count",
     "mfx_host_stft_lds_bytes",
+    "mfx_batch_set_pitch", "mfx_batch_clear_pitch", "mfx_batch_pitch_read", "mfx_batch_pitch_device", "mfx_host_pitch",
 )
 
 
@@ -193,6 +194,11 @@ def load_library():
     L.mfx_host_stft_basis.argtypes = [i32, fp, fp]
     L.mfx_host_stft_frame_count.argtypes, L.mfx_host_stft_frame_count.restype = [i64, i32, i32], i64
     L.mfx_host_stft_lds_bytes.argtypes, L.mfx_host_stft_lds_bytes.restype = [i32, i32, i32, p32], i64
+    L.mfx_batch_set_pitch.argtypes = [vp, i32, i32, i32, C.c_float, C.c_float, C.c_float, i32]
+    L.mfx_batch_clear_pitch.argtypes = [vp]
+    L.mfx_batch_pitch_read.argtypes = [vp, fp, p32, fp]
+    L.mfx_batch_pitch_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.mfx_host_pitch.argtypes = [sp, i64, i32, i64, i32, i32, i32, i32, C.c_float, C.c_float, C.c_float, i32, fp, p32, fp]
     _lib = L
     return L
 
@@ -356,6 +362,23 @@ def host_online_norm(rows, kind, window=0, prior_frames=0, prior_count=0, prior_
     if rc != 0:
         raise MfxError(int(rc), "mfx_host_online_norm failed")
     return out
+
+
+def host_pitch(pcm, frames, shift, window, lag_min, lag_max, ballast=0.0, lag_cost=0.0, penalty=0.0, max_jump=0, channels=1):
+    """The pitch track of batch_set_pitch on host memory, exactly as include/mfx.h defines it (host code, no GPU needed), for
+    one utterance: pcm int16 (interleaved for channels = 2), frames = its frame count on the handle in question.  Returns
+    (lag [T], rho [T], index [T], nccf [T][K])."""
+    L = load_library()
+    x = np.ascontiguousarray(pcm, dtype=np.int16).reshape(-1)
+    n, T, K = x.size // max(int(channels), 1), max(int(frames), 0), max(int(lag_max) - int(lag_min) + 1, 0)
+    pitch, index, nccf = np.zeros((T, 2), np.float32), np.zeros(T, np.int32), np.zeros((T, min(K, 512)), np.float32)
+    fpt = C.POINTER(C.c_float)
+    rc = L.mfx_host_pitch(x.ctypes.data_as(C.POINTER(C.c_int16)), n, int(channels), int(frames), int(shift), int(window), int(lag_min),
+                          int(lag_max), float(ballast), float(lag_cost), float(penalty), int(max_jump), pitch.ctypes.data_as(fpt),
+                          index.ctypes.data_as(C.POINTER(C.c_int32)), nccf.ctypes.data_as(fpt))
+    if rc != 0:
+        raise MfxError(int(rc), "mfx_host_pitch failed")
+    return pitch[:, 0].copy(), pitch[:, 1].copy(), index, nccf
 
 
 def host_xform_operands(A):
@@ -891,6 +914,47 @@ class MfccHip:
         a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
         self._chk(self._L.mfx_batch_vad_device(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return a.value or 0, b.value or 0, c.value or 0
+
+    host_pitch = staticmethod(host_pitch)
+
+    def batch_set_pitch(self, lag_min, lag_max, window=0, ballast=0.0, lag_cost=0.0, penalty=0.0, max_jump=0):
+        """Pitch track beside the rows of a batch run (mfx_batch_set_pitch): per frame the normalised cross-correlation of
+        `window` samples (0: the handle's window_size) at lags lag_min .. lag_max samples, and a Viterbi path through it
+        (local cost 1 - rho (1 - lag_cost lag / lag_max), transition cost penalty (ln lag - ln lag')^2 over at most max_jump
+        lags, 0: any).  The rows of the run are unchanged; batch_pitch_read returns the track.  A later batch_plan clears it."""
+        self._chk(self._L.mfx_batch_set_pitch(self._h, int(window), int(lag_min), int(lag_max), float(ballast), float(lag_cost),
+                                              float(penalty), int(max_jump)))
+        self._pitch_K = int(lag_max) - int(lag_min) + 1
+
+    def batch_clear_pitch(self):
+        self._chk(self._L.mfx_batch_clear_pitch(self._h))
+        self._pitch_K = 0
+
+    def batch_pitch_read(self, nccf=False, f0=False):
+        """(lag [total_rows] float32, rho [total_rows] float32, index [total_rows] int32) of the last batch run while a pitch
+        track is in force (MfxError with status -8 otherwise), followed by the NCCF rows [total_rows][K] and by f0 =
+        sample_rate / lag in Hz (float64) when asked for."""
+        rows = int(self._plan_total or 0)
+        pitch, index = np.zeros((rows, 2), np.float32), np.zeros(rows, np.int32)
+        K = int(getattr(self, "_pitch_K", 0))
+        if nccf and K < 1:   # (the row width is this wrapper's knowledge: the track was not set through batch_set_pitch)
+            raise MfxError(-8, "batch_pitch_read: no pitch track was set through batch_set_pitch")
+        rho = np.zeros((rows, K), np.float32) if nccf else None
+        fpt = C.POINTER(C.c_float)
+        self._chk(self._L.mfx_batch_pitch_read(self._h, pitch.ctypes.data_as(fpt), index.ctypes.data_as(C.POINTER(C.c_int32)),
+                                               None if rho is None else rho.ctypes.data_as(fpt)))
+        out = [pitch[:, 0].copy(), pitch[:, 1].copy(), index]
+        if nccf:
+            out.append(rho)
+        if f0:
+            out.append(float(self.cfg.sample_rate) / pitch[:, 0].astype(np.float64))
+        return tuple(out)
+
+    def batch_pitch_device(self):
+        """Device addresses (d_pitch [total_rows][2], d_index [total_rows]) of the handle-owned arrays of the pitch track."""
+        a, b = C.c_void_p(), C.c_void_p()
+        self._chk(self._L.mfx_batch_pitch_device(self._h, C.byref(a), C.byref(b)))
+        return a.value or 0, b.value or 0
 
     def batch_output_width(self):
         """Row width of the batch entries' output: out_dim while a transform is in force, else get_output_data_width()."""

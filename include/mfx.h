@@ -462,6 +462,63 @@ int mfx_batch_vad_read(mfx_handle *h, uint8_t *flags /* [total_rows] */, int32_t
 int mfx_batch_vad_device(const mfx_handle *h, const uint8_t **d_flags, const int32_t **d_voiced,
                          const int64_t **d_packed_row0 /* [n_utt + 1] */);
 
+/* Pitch track beside the feature rows of a batch run ("Pitch track"): what compute-kaldi-pitch-feats gives a
+ * Kaldi-style recipe -- a normalised cross-correlation (NCCF) of the PCM over a range of lags and a Viterbi path through it --
+ * on the device, from the PCM the batch already has there.  No reference analogue.  d_out, mfx_batch_output_width and every
+ * existing row stay bit for bit what they are: the track goes to handle-owned arrays indexed by the plan's rows.
+ *   Scope.  Valid after mfx_batch_plan / mfx_batch_plan_rates (MFX_ERR_STATE before one); a later plan drops the track with the
+ *     other attachments, and mfx_batch_clear_pitch puts the handle back on today's launches.  MFX_ERR_DEVICE on a planning
+ *     handle, before any argument is looked at.  MFX_ERR_CONFIG on an STFT log-mel handle (its frames are centred); MFCC,
+ *     fbank, PLP and TRAPS handles are served, they share one frame rule.  MFX_ERR_ARG: window outside 32 .. 1024 (0 means the
+ *     handle's window_size, which must then lie in that range); lag_min < 2, lag_max > 1024, or K = lag_max - lag_min + 1
+ *     outside 1 .. 512; ballast, lag_cost or penalty not finite or negative, or lag_cost > 1; max_jump outside 0 .. 511 (0
+ *     means J = K - 1, or 1 when K = 1; larger values are clamped to J = max(K - 1, 1)).
+ *   Samples.  Utterance u has n samples per channel and T = mfx_batch_frames(h, n) frames at shift S; its rows are the
+ *     plan's out_rows[u].  p[i] is the int16 sample, for channels = 2 the front ends' (L + R) >> 1; p[i] = 0 for i outside
+ *     [0, n) of THAT utterance: a neighbour's samples are never read.  Under a rates plan the samples are the converted
+ *     scratch's, which is what the front end reads.  x[i] = (float)p[i] * 2^-15.
+ *   Frame t, span Ls = window + lag_max samples from i0 = t S:
+ *     Mean.  sI = the sum of p[i0 .. i0 + Ls) as an exact integer; m = (float)sI * c1, c1 = (float)(1.0 / (32768.0 * Ls));
+ *       z[j] = x[i0 + j] - m for all j < Ls, the zero-filled samples included.
+ *     Energies.  q[j] = (double)(z[j] * z[j]), the product rounded to float32 first; P[0] = 0, P[j + 1] = P[j] + q[j]
+ *       ascending, in double; e(l) = (float)(P[l + window] - P[l]).
+ *     Correlation, for l_k = lag_min + k: c = 0, then for j = 0 .. window - 1 ascending c = fmaf(z[j], z[j + l_k], c): one
+ *       float32 FMA chain per value, in that order, whatever the tiling and the batch.
+ *     NCCF.  s = e(0) * e(l_k) + ballast, the product and the sum rounded separately; rho[k] = c / sqrtf(s) when s > 0, else
+ *       0; the division and the square root correctly rounded.
+ *   Track, per utterance.  Host tables, built in double and rounded once: wt[k] = (float)(1 - lag_cost * l_k / lag_max),
+ *     lg[k] = (float)ln(l_k).  Every float32 operation below is rounded on its own.
+ *     Local cost.  loc_t[k] = 1.0f - rho_t[k] * wt[k].
+ *     Start.  a_0 = loc_0.  For every t: m_t = min_k a_t[k] and fwd_t[k] = a_t[k] - m_t.
+ *     Step, for t >= 1 and each k, over k' from max(0, k - J) to min(K - 1, k + J) ascending: d = lg[k] - lg[k'],
+ *       tr = (penalty * d) * d, cand = fwd_{t-1}[k'] + tr; a strictly smaller cand replaces the best, so ties keep the
+ *       smallest k'.  a_t[k] = loc_t[k] + best, and bp_t[k] is that k'.
+ *     Backtrace.  The end state is the smallest k that minimises fwd_{T-1}; bp is followed backwards from it.
+ *     Outputs per row.  index = k_t; rho = rho_t[k_t]; lag = (float)l_{k_t} + delta, the parabolic refinement: if
+ *       0 < k_t < K - 1, with a, b, c = rho_t[k_t - 1], rho_t[k_t], rho_t[k_t + 1] and den = (a - b) + (c - b): if den < 0,
+ *       delta = clamp((0.5f * (a - c)) / den, -0.5f, 0.5f); in every other case delta = 0.  f0 is sample_rate / lag.
+ *     All values are finite (|x| <= 1), and the outputs are an exact function of the utterance's samples and the parameters.
+ *   Run.  While in force, mfx_batch_run_device / _host queue k_pitch_nccf and k_pitch_track on the handle's OWN stream,
+ *     directly behind the front end's launches -- never on the tail's: with mfx_batch_overlap the caller may reuse the PCM
+ *     once the handle's stream has passed it.  The run still allocates nothing.  The sliced host path stays on (utterances
+ *     are independent: a slice runs its utterance range).
+ *   Memory.  The setter allocates, after waiting for the handle's streams: the NCCF rows [total_rows][K] floats, the
+ *     back-pointers [total_rows][K] uint16, pitch, index, the two tables and the tile descriptors -- about 1.7 GB for
+ *     1000 x 10 s at K = 281.  MFX_ERR_DEVICE when it does not fit (nothing of it stays allocated then).
+ *   Composition.  d_out, mfx_batch_output_width and every other attachment, in any combination, are unchanged.  The pitch
+ *     arrays are indexed by the plan's rows, also under MFX_VAD_SELECT / MFX_VAD_PACK.
+ *   Read-back.  mfx_batch_pitch_read synchronises and copies pitch [total_rows][2] = (lag, rho), index [total_rows] and the
+ *     NCCF rows [total_rows][K]; any output may be NULL.  MFX_ERR_STATE without the attachment or before a run; a batch
+ *     without rows counts as run.  mfx_batch_pitch_device returns the device arrays: valid until the next plan or clear,
+ *     ordered on the handle's stream.
+ * NOT served: the session entries (mfx_sessions_*) and the streaming interface are untouched and ignore the pitch track. */
+int mfx_batch_set_pitch(mfx_handle *h, int32_t window, int32_t lag_min, int32_t lag_max, float ballast, float lag_cost,
+                        float penalty, int32_t max_jump);
+int mfx_batch_clear_pitch(mfx_handle *h);
+int mfx_batch_pitch_read(mfx_handle *h, float *pitch /* [total_rows][2]: lag, rho */, int32_t *index /* [total_rows] */,
+                         float *nccf /* [total_rows][K] */);
+int mfx_batch_pitch_device(const mfx_handle *h, const float **d_pitch, const int32_t **d_index);
+
 /* ---- sample-rate conversion in front of a batch ("Sample-rate conversion").  No reference analogue: the
  *      reference refuses a file whose rate differs from the first file's (ASR_OCL.cpp:191). ----
  *
@@ -652,6 +709,13 @@ int32_t mfx_host_resample_tile(int32_t in_hz, int32_t out_hz, int32_t zeros, flo
  * written then).  Test / inspection aid. */
 int mfx_host_online_norm(const float *rows, int64_t T, int32_t pitch, int32_t Wn, int32_t kind, int32_t window,
                          int32_t prior_frames, int64_t prior_count, const double *prior_acc, float *out);
+/* The pitch track (mfx_batch_set_pitch) on host memory, exactly as defined there, for ONE utterance: pcm holds its n samples
+ * per channel (interleaved for channels = 2), T = its frames (mfx_batch_frames of n on the handle in question) at `shift`;
+ * window as resolved (32 .. 1024, never 0).  Writes pitch [T][2], index [T], nccf [T][K]; any of them may be NULL.
+ * MFX_ERR_ARG on anything outside the limits (nothing is written then).  Test / inspection aid. */
+int mfx_host_pitch(const int16_t *pcm, int64_t n, int32_t channels, int64_t T, int32_t shift, int32_t window, int32_t lag_min,
+                   int32_t lag_max, float ballast, float lag_cost, float penalty, int32_t max_jump, float *pitch, int32_t *index,
+                   float *nccf);
 /* frame count, integer arithmetic (parambase.cpp:16-19 without the float32 division) */
 int64_t mfx_host_frame_count(int64_t samples, int32_t window_size, int32_t shift);
 /* STFT log-mel (MFX_METHOD_STFT_LOGMEL) tables as uploaded, and its frame rule.  mfx_host_slaney_mel_table: weights
