@@ -39,6 +39,11 @@ from .mfcc import (  # noqa: F401
     host_speaker_lists,
     host_online_norm,
     host_pitch,
+    host_pitch_feats,
+    PF_POV,
+    PF_NORM_LOG_PITCH,
+    PF_DELTA,
+    PF_RAW_LOG_PITCH,
     SPK_POOL,
     SPK_PRIOR_ONLY,
     VAD_FLAGS,

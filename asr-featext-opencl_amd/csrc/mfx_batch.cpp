@@ -1,8 +1,8 @@
 // mfx_batch.cpp -- the runner of the batch interface of include/mfx.h: a planned batch (mfx_batch_plan.cpp) with what is
 // attached to it (mfx_batch_attach.cpp) through the device and host entries, the overlap of a batch's tail with the next
 // front end, the pinned allocator.  Which front end runs is choose_front's decision and launch_front's work (mfx_api.cpp).
-// This file owns `batch.ov` and `batch.host`; of the rest of `batch` and of `fuse` it only reads, but for spk.ran, vad.ran, pt.ran
-// and the spectrum slab it grows.  It names no field of `st` or `sweep`.
+// This file owns `batch.ov` and `batch.host`; of the rest of `batch` and of `fuse` it only reads, but for spk.ran, vad.ran, pt.ran,
+// pf.ran and the spectrum slab it grows.  It names no field of `st` or `sweep`.
 #include "mfx_handle.h"
 
 using namespace mfx;
@@ -10,7 +10,7 @@ using namespace mfx;
 void fill_xform(const mfx_handle *h, XformParams &p)
 {
     p = XformParams{};
-    p.width = h->width;
+    p.width = batch_y_width(h);
     p.left = h->batch.xf.left;
     p.right = h->batch.xf.right;
     p.out_dim = h->batch.xf.out;
@@ -113,6 +113,8 @@ struct RunMode {
     float *d_out, *d_last, *d_final; // where the rows y are built, where the run's last stage before the VAD writes, where
                             // the caller wants the result: all the same unless a transform (d_out is its scratch) or a
                             // selecting VAD (d_last is its scratch) is in force
+    float *d_y;             // where the transform and the VAD read the rows y: d_out, unless pitch features are pasted (d_out
+                            // is then the scratch of the `width` columns, and k_pitch_paste writes the wide rows to d_y)
     float *d_pre;           // where everything AHEAD of the normaliser's place writes: d_out, unless the online normaliser is
                             // in force (its raw-row scratch: it must not run in place, its trailing edge reads raw rows that
                             // another block may already have turned into output)
@@ -140,7 +142,8 @@ RunMode decide_mode(const mfx_handle *h, FrontParams &p, float *d_out, bool whol
     // into the caller's array.
     m.d_final = d_out;
     m.d_last = (B.vad.on && B.vad.mode != MFX_VAD_FLAGS) ? B.vad.d_rows.p : d_out;
-    m.d_out = B.xf.on ? B.xf.d_y.p : m.d_last;
+    m.d_y = B.xf.on ? B.xf.d_y.p : m.d_last;
+    m.d_out = B.pf.on && B.pf.paste ? B.pf.d_narrow.p : m.d_y;
     m.d_pre = B.on.on ? B.on.d_raw.p : m.d_out;
     const bool norm_before = h->cfg.norm != MFX_NORM_NONE && !h->cfg.norm_after_dyn;
     m.sb = (B.ov.enabled && whole) ? (int)(B.ov.seq & 1) : 0;
@@ -236,8 +239,9 @@ int run_front(mfx_handle *h, FrontParams &p, const RunMode &m, int u0, int u1, i
 }
 
 // the pitch track of a run: k_pitch_nccf and k_pitch_track over the utterance range, on the handle's stream behind the front
-// end (never the tail's: once the handle's stream has passed them the PCM may be reused); `pcm` is what the front end read
-int run_pitch(mfx_handle *h, const int16_t *pcm, int u0, int u1)
+// end (never the tail's: once the handle's stream has passed them the PCM may be reused); `pcm` is what the front end read.
+// Pitch features in force: k_pitch_feats directly behind them, so that run_tail's ev_front orders the tail's stream behind it.
+int run_pitch(mfx_handle *h, const RunMode &m, const int16_t *pcm, int u0, int u1)
 {
     BatchState &B = h->batch;
     BatchState::Pitch &pt = B.pt;
@@ -259,6 +263,23 @@ int run_pitch(mfx_handle *h, const int16_t *pcm, int u0, int u1)
     pp.nccf = pt.d_nccf.p, pp.bp = pt.d_bp.p, pp.pitch = pt.d_pitch.p, pp.index = pt.d_index.p;
     HIP_TRY(h, launch_pitch(pp, h->stream));
     pt.ran = true;
+    BatchState::PitchFeats &pf = B.pf;
+    if (!pf.on) return MFX_OK;
+    // (overlap: the paste of the batch before this one reads d_feats on the tail's stream)
+    if (pf.paste && m.split_tail && B.ov.tail_pending[m.sb ^ 1]) HIP_TRY(h, hipStreamWaitEvent(h->stream, B.ov.ev_tail[m.sb ^ 1], 0));
+    PitchFeatParams fp{};
+    fp.pitch = pt.d_pitch.p;
+    fp.segs = B.d_segs.p;
+    fp.utt_tile0 = pf.d_utt_tile0.p, fp.tile_utt = pf.d_tile_utt.p;
+    fp.tile_first = pf.utt_tile0[u0], fp.n_tiles = pf.utt_tile0[u1] - pf.utt_tile0[u0];
+    fp.columns = pf.columns, fp.F = pf.F;
+    fp.left = pf.left, fp.right = pf.right, fp.D = pf.D;
+    fp.sample_rate = h->cfg.sample_rate;
+    fp.pov_scale = pf.pov_scale, fp.pov_offset = pf.pov_offset, fp.pitch_scale = pf.pitch_scale, fp.delta_scale = pf.delta_scale;
+    fp.delta_den = pf.den;
+    fp.feats = pf.d_feats.p;
+    HIP_TRY(h, launch_pitch_feats(fp, h->stream));
+    pf.ran = true;
     return MFX_OK;
 }
 
@@ -274,14 +295,14 @@ int run_batch_norm(mfx_handle *h, const RunMode &m, int u0, int u1, int groups, 
                     B.tiles_max * 64, groups, group_stats_stride);
 }
 
-// the VAD of a run: decision on the rows y (m.d_out, before a transform), selection from m.d_last into the caller's array
+// the VAD of a run: decision on the rows y (m.d_y, before a transform), selection from m.d_last into the caller's array
 int run_vad(mfx_handle *h, const RunMode &m, int u0, int u1)
 {
     BatchState &B = h->batch;
     BatchState::Vad &v = B.vad;
     VadParams vp{};
-    vp.y = m.d_out;
-    vp.y_pitch = h->width;
+    vp.y = m.d_y;
+    vp.y_pitch = batch_y_width(h);
     vp.column = v.column;
     vp.segs = B.d_segs.p;
     vp.n_utt = B.n_utt;
@@ -309,7 +330,7 @@ int run_vad(mfx_handle *h, const RunMode &m, int u0, int u1)
     return MFX_OK;
 }
 
-// ---- stage 5, on m.tail_stream: normaliser before the deltas, deltas, normaliser after them, transform, VAD
+// ---- stage 5, on m.tail_stream: normaliser before the deltas, deltas, normaliser after them, paste, transform, VAD
 int run_tail(mfx_handle *h, const RunMode &m, int u0, int u1)
 {
     BatchState &B = h->batch;
@@ -342,11 +363,19 @@ int run_tail(mfx_handle *h, const RunMode &m, int u0, int u1)
         const int rc = run_batch_norm(h, m, u0, u1, h->width / h->cols, (size_t)B.n_utt * 2 * h->cols);
         if (rc != MFX_OK) return rc;
     }
+    if (B.pf.on && B.pf.paste) { // the rows y become [ y | feats ]: the last launch ahead of the transform
+        PitchPasteParams pq{};
+        pq.narrow = m.d_out, pq.feats = B.pf.d_feats.p;
+        pq.out = m.d_y;
+        pq.row0 = B.utt_row[u0], pq.rows = (u1 < B.n_utt ? B.utt_row[u1] : B.total_rows) - B.utt_row[u0];
+        pq.Wd = h->width, pq.F = B.pf.F;
+        HIP_TRY(h, launch_pitch_paste(pq, m.tail_stream));
+    }
     if (B.xf.on) { // behind the tail, on its stream: ev_tail covers it
         XformParams xp;
         fill_xform(h, xp);
-        xp.src = m.d_out;
-        xp.src_pitch = h->width;
+        xp.src = m.d_y;
+        xp.src_pitch = batch_y_width(h);
         xp.out = m.d_last;
         xp.out_pitch = B.xf.out;
         xp.segs = B.d_segs.p + u0;
@@ -388,6 +417,7 @@ int batch_run_range(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_tot
     if (B.total_rows == 0) {
         B.vad.ran = B.vad.on; // (nothing to decide: the read-back returns what the setter left, no voiced row)
         B.pt.ran = B.pt.on;   // (no row to track: the read-back copies nothing)
+        B.pf.ran = B.pf.on;
         return MFX_OK;
     }
     if ((rc = check_layout(h, d_pcm, pcm_samples_total, B.utt_off, B.utt_len, u0, u1)) != MFX_OK) return rc;
@@ -396,15 +426,17 @@ int batch_run_range(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_tot
     const int32_t c0 = B.utt_chunk0[u0], c1 = B.utt_chunk0[u1]; // chunk range of the utterance range
     if (c1 <= c0) { // a range without a frame: nothing to compute, but the VAD's counts and prefix are still to be written
         B.pt.ran = B.pt.ran || B.pt.on; // (the pitch track has no row to write either)
+        B.pf.ran = B.pf.ran || B.pf.on;
         if (!B.vad.on) return MFX_OK;
         RunMode none{};
         none.d_last = B.vad.d_rows.p, none.d_final = d_out;
         none.tail_stream = h->stream;
         return run_vad(h, none, u0, u1);
     }
-    if ((B.xf.on && B.xf.d_y.n < (size_t)B.total_rows * h->width) || (h->traps && B.d_logmel.n < (size_t)B.total_rows * B.mel_pitch) ||
+    if ((B.xf.on && B.xf.d_y.n < (size_t)B.total_rows * batch_y_width(h)) || (h->traps && B.d_logmel.n < (size_t)B.total_rows * B.mel_pitch) ||
         (B.vad.on && B.vad.mode != MFX_VAD_FLAGS && B.vad.d_rows.n < (size_t)B.total_rows * batch_out_width(h)) ||
-        (B.on.on && B.on.d_raw.n < (size_t)B.total_rows * h->width) || (B.pt.on && B.pt.d_nccf.n < (size_t)B.total_rows * B.pt.K))
+        (B.on.on && B.on.d_raw.n < (size_t)B.total_rows * h->width) || (B.pt.on && B.pt.d_nccf.n < (size_t)B.total_rows * B.pt.K) ||
+        (B.pf.on && (!B.pt.on || B.pf.d_feats.n < (size_t)B.total_rows * B.pf.F || (B.pf.paste && B.pf.d_narrow.n < (size_t)B.total_rows * h->width))))
         return fail(h, MFX_ERR_STATE, "batch not planned");
 
     FrontParams p;
@@ -421,7 +453,7 @@ int batch_run_range(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_tot
         p.feat_pitch = h->traps ? B.mel_pitch : h->width;
     }
     if ((rc = run_front(h, p, m, u0, u1, c0, c1)) != MFX_OK) return rc;
-    if (B.pt.on && (rc = run_pitch(h, d_pcm, u0, u1)) != MFX_OK) return rc;
+    if (B.pt.on && (rc = run_pitch(h, m, d_pcm, u0, u1)) != MFX_OK) return rc;
     if ((rc = run_tail(h, m, u0, u1)) != MFX_OK) return rc;
     if (whole) ++B.ov.seq;
     return MFX_OK;

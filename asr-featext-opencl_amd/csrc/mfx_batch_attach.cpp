@@ -1,7 +1,7 @@
 // mfx_batch_attach.cpp -- what a caller attaches to a planned batch (include/mfx.h): per-utterance warp factors, a splice +
-// affine transform, a speaker list, the energy VAD, the online normaliser, the pitch track.  Each is tied to the plan
-// (mfx_batch_plan_rates' converter is the seventh, and is the planner's); BatchState::detach drops the six of this file.  This
-// file owns `batch.va`, `batch.xf`, `batch.spk`, `batch.vad`, `batch.on` and `batch.pt`.
+// affine transform, a speaker list, the energy VAD, the online normaliser, the pitch track, the pitch features.  Each is tied
+// to the plan (mfx_batch_plan_rates' converter is the eighth, and is the planner's); BatchState::detach drops the seven of this
+// file.  This file owns `batch.va`, `batch.xf`, `batch.spk`, `batch.vad`, `batch.on`, `batch.pt` and `batch.pf`.
 #include "mfx_handle.h"
 
 #include <cmath>
@@ -222,7 +222,7 @@ extern "C" int mfx_batch_clear_online_norm(mfx_handle *h)
     return MFX_OK;
 }
 
-int batch_out_width(const mfx_handle *h) { return h->batch.xf.on ? h->batch.xf.out : h->width; }
+int batch_out_width(const mfx_handle *h) { return h->batch.xf.on ? h->batch.xf.out : batch_y_width(h); }
 
 extern "C" int mfx_batch_output_width(const mfx_handle *h) { return h ? batch_out_width(h) : MFX_ERR_ARG; }
 
@@ -236,14 +236,14 @@ extern "C" int mfx_batch_set_transform(mfx_handle *h, int32_t left, int32_t righ
         if (rc != MFX_OK) return rc;
         h->batch.xf.drop();
         h->batch.xf.d_ops.release(), h->batch.xf.d_bias.release(), h->batch.xf.d_idx.release(), h->batch.xf.d_y.release();
-        return size_vad_rows(h); // (the output rows are `width` floats again)
+        return size_vad_rows(h); // (the output rows are Wy floats again)
     }
     if (!h->batch.planned) return fail(h, MFX_ERR_STATE, "mfx_batch_set_transform: no batch is planned");
     if (!A) return fail(h, MFX_ERR_ARG, "no matrix");
     if (left < 0 || left > 32 || right < 0 || right > 32) return fail(h, MFX_ERR_ARG, "left and right must be 0 .. 32");
     if (out_dim < 1 || out_dim > 256) return fail(h, MFX_ERR_ARG, "out_dim must be 1 .. 256");
     if (n_xf < 1 || n_xf > 1024) return fail(h, MFX_ERR_ARG, "n_xf must be 1 .. 1024");
-    const int64_t in_dim = (int64_t)(left + right + 1) * h->width;
+    const int64_t in_dim = (int64_t)(left + right + 1) * batch_y_width(h); // (Wy: `width`, and the pasted pitch features)
     if (in_dim > 8192) return fail(h, MFX_ERR_ARG, "in_dim = (left + right + 1) * width is larger than 8192");
     if (utt_xf) {
         if (n_utt != h->batch.n_utt) return fail(h, MFX_ERR_ARG, "one transform index per planned utterance");
@@ -274,7 +274,7 @@ extern "C" int mfx_batch_set_transform(mfx_handle *h, int32_t left, int32_t righ
     else
         h->batch.xf.d_idx.release();
     // (everything mfx_batch_run_device needs is allocated here: that entry never allocates)
-    const size_t need = (size_t)std::max<int64_t>(h->batch.total_rows, 1) * h->width;
+    const size_t need = (size_t)std::max<int64_t>(h->batch.total_rows, 1) * batch_y_width(h);
     if (h->batch.xf.d_y.n < need) HIP_TRY(h, h->batch.xf.d_y.alloc(need));
     h->batch.xf.left = left, h->batch.xf.right = right, h->batch.xf.out = out_dim;
     h->batch.xf.on = true;
@@ -445,10 +445,16 @@ extern "C" int mfx_batch_clear_pitch(mfx_handle *h)
 {
     MFX_DEVICE_ENTRY(h);
     HIP_TRY(h, hipSetDevice(h->device));
+    // (the pitch features go with the track they are computed from; pasted, they are part of the rows a transform or a VAD
+    // was sized for)
+    if (batch_y_width(h) != h->width && (h->batch.xf.on || h->batch.vad.on))
+        return fail(h, MFX_ERR_STATE, "mfx_batch_clear_pitch: pasted pitch features are in force under a transform or a VAD (clear those first)");
     const int rc = mfx_synchronize(h); // (a run in flight may read what is released below)
     if (rc != MFX_OK) return rc;
     h->batch.pt.drop();
     h->batch.pt.release();
+    h->batch.pf.drop();
+    h->batch.pf.release();
     return MFX_OK;
 }
 
@@ -476,5 +482,94 @@ extern "C" int mfx_batch_pitch_device(const mfx_handle *h, const float **d_pitch
     if (!h->batch.pt.on) return MFX_ERR_STATE;
     if (d_pitch) *d_pitch = h->batch.pt.d_pitch.p;
     if (d_index) *d_index = h->batch.pt.d_index.p;
+    return MFX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// pitch features ("Pitch features")
+// ------------------------------------------------------------------------------------------------
+
+extern "C" int mfx_batch_set_pitch_feats(mfx_handle *h, int32_t columns, int32_t left, int32_t right, int32_t delta_window,
+                                         float pov_scale, float pov_offset, float pitch_scale, float delta_scale, int32_t paste)
+{
+    MFX_DEVICE_ENTRY(h);
+    BatchState &B = h->batch;
+    if (!B.planned) return fail(h, MFX_ERR_STATE, "mfx_batch_set_pitch_feats: no batch is planned");
+    if (!B.pt.on) return fail(h, MFX_ERR_STATE, "mfx_batch_set_pitch_feats: no pitch track is in force (mfx_batch_set_pitch first)");
+    PitchFeatShape s;
+    if ((paste != 0 && paste != 1) || !pitch_feat_shape(columns, left, right, delta_window, pov_scale, pov_offset, pitch_scale, delta_scale, s))
+        return fail(h, MFX_ERR_ARG,
+                    "mfx_batch_set_pitch_feats: columns 0 or MFX_PF_* bits, left and right 0 .. 1024, delta_window 1 .. 16, finite "
+                    "scales, paste 0 or 1");
+    if (h->width + (paste ? s.F : 0) != batch_y_width(h) && (B.xf.on || B.vad.on))
+        return fail(h, MFX_ERR_STATE,
+                    "mfx_batch_set_pitch_feats: the row width would change under a transform or a VAD (clear them, set the paste, set "
+                    "them again)");
+    std::vector<int32_t> tile0, tile_utt;
+    if (!build_pitch_layout(B.utt_frames.data(), B.n_utt, kPitchFeatRows, tile0, tile_utt)) return fail(h, MFX_ERR_ARG, "batch too long");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int rc = mfx_synchronize(h); // (a run in flight may read the arrays replaced below)
+    if (rc != MFX_OK) return rc;
+    BatchState::PitchFeats &pf = B.pf;
+    pf.drop();
+    // (everything mfx_batch_run_device needs is allocated here: that entry never allocates)
+    const size_t rows = (size_t)B.total_rows;
+    auto all = [&]() -> int {
+        HIP_TRY(h, h->upload(pf.d_utt_tile0, tile0));
+        HIP_TRY(h, h->upload(pf.d_tile_utt, tile_utt));
+        HIP_TRY(h, pf.d_feats.alloc(rows * s.F));
+        if (paste)
+            HIP_TRY(h, pf.d_narrow.alloc(rows * h->width));
+        else
+            pf.d_narrow.release();
+        return MFX_OK;
+    };
+    if (const int ra = all(); ra != MFX_OK) { // (it did not fit: nothing of it stays)
+        pf.release();
+        return ra;
+    }
+    pf.utt_tile0.swap(tile0);
+    pf.columns = s.columns, pf.F = s.F, pf.left = s.left, pf.right = s.right, pf.D = s.D, pf.den = s.den;
+    pf.pov_scale = pov_scale, pf.pov_offset = pov_offset, pf.pitch_scale = pitch_scale, pf.delta_scale = delta_scale;
+    pf.paste = paste != 0;
+    pf.on = true;
+    return MFX_OK;
+}
+
+extern "C" int mfx_batch_clear_pitch_feats(mfx_handle *h)
+{
+    MFX_DEVICE_ENTRY(h);
+    if (batch_y_width(h) != h->width && (h->batch.xf.on || h->batch.vad.on))
+        return fail(h, MFX_ERR_STATE, "mfx_batch_clear_pitch_feats: the row width would change under a transform or a VAD (clear them first)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int rc = mfx_synchronize(h); // (a run in flight may read what is released below)
+    if (rc != MFX_OK) return rc;
+    h->batch.pf.drop();
+    h->batch.pf.release();
+    return MFX_OK;
+}
+
+extern "C" int mfx_batch_pitch_feats_read(mfx_handle *h, float *feats)
+{
+    MFX_DEVICE_ENTRY(h);
+    const BatchState::PitchFeats &pf = h->batch.pf;
+    if (!pf.on) return fail(h, MFX_ERR_STATE, "mfx_batch_pitch_feats_read: no pitch features are in force");
+    if (!pf.ran) return fail(h, MFX_ERR_STATE, "mfx_batch_pitch_feats_read: no batch has run since the pitch features were set");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int rc = mfx_synchronize(h);
+    if (rc != MFX_OK) return rc;
+    const size_t rows = (size_t)h->batch.total_rows;
+    if (rows == 0 || !feats) return MFX_OK;
+    HIP_TRY(h, hipMemcpy(feats, pf.d_feats.p, rows * pf.F * sizeof(float), hipMemcpyDeviceToHost));
+    return MFX_OK;
+}
+
+extern "C" int mfx_batch_pitch_feats_device(const mfx_handle *h, const float **d_feats, int32_t *F)
+{
+    if (!h) return MFX_ERR_ARG;
+    if (h->planning) return MFX_ERR_DEVICE;
+    if (!h->batch.pf.on) return MFX_ERR_STATE;
+    if (d_feats) *d_feats = h->batch.pf.d_feats.p;
+    if (F) *F = h->batch.pf.F;
     return MFX_OK;
 }

@@ -3,8 +3,8 @@
 //   mfx_api.cpp    lifetime, tables, kernel choice and front-end dispatch, profiling, test taps (writes the shared part)
 //   mfx_stream.cpp the streaming state machine and its host copies         (owns `st` and `sweep`)
 //   mfx_batch_plan.cpp   the batch planner, the rates planner, the fused-delta plan (owns `batch`'s plan, `batch.rs`, `fuse`)
-//   mfx_batch_attach.cpp what is attached to a plan: warp factors, transform, speakers, VAD, online normaliser, pitch track (owns
-//                        `batch.va`, `.xf`, `.spk`, `.vad`, `.on`, `.pt`)
+//   mfx_batch_attach.cpp what is attached to a plan: warp factors, transform, speakers, VAD, online normaliser, pitch track,
+//                        pitch features (owns `batch.va`, `.xf`, `.spk`, `.vad`, `.on`, `.pt`, `.pf`)
 //   mfx_batch.cpp        the batch runner, device and host entries, overlap   (owns `batch.ov` and `batch.host`)
 //   mfx_sessions_host.cpp the session entries: many live streams per push       (owns `sess`)
 #pragma once
@@ -165,7 +165,7 @@ struct BatchState {
     int tiles_max = 0;
     bool aligned = true;                 // frames on aligned sample pairs (fill_front / choose_front read it)
 
-    // Seven attachments, each tied to the plan: a new plan drops them.  drop() switches one off and releases what is not kept
+    // Eight attachments, each tied to the plan: a new plan drops them.  drop() switches one off and releases what is not kept
     // for the next one (the grown-never-shrunk scratch stays).
 
     // sample-rate conversion (mfx_batch_plan_rates): while on, the run converts the caller's array into d_pcm with one
@@ -205,7 +205,7 @@ struct BatchState {
         int left = 0, right = 0, out = 0;
         DevBuf<float> d_ops, d_bias;     // [n_xf][steps][tiles][64], [n_xf][tiles * 16]
         DevBuf<int32_t> d_idx;           // [n_utt] transform of every utterance (empty: all 0)
-        DevBuf<float> d_y;               // [total_rows][width] (grown, never shrunk: only the (NULL, 0) setter releases it)
+        DevBuf<float> d_y;               // [total_rows][Wy] (grown, never shrunk: only the (NULL, 0) setter releases it)
         void drop() { on = false; }
     } xf;
     // per-speaker normalisation (mfx_batch_set_speakers): while on, the run's normaliser is k_spk_sums -> k_spk_finish ->
@@ -278,9 +278,27 @@ struct BatchState {
             d_pitch.release(), d_index.release();
         }
     } pt;
+    // pitch features (mfx_batch_set_pitch_feats; needs the pitch track): while on, k_pitch_feats follows k_pitch_track on the
+    // handle's stream and fills d_feats, indexed by the plan's rows.  With `paste` the rows y of a run are Wy = width + F wide:
+    // everything ahead of the transform builds its `width` columns in d_narrow, and k_pitch_paste writes [ narrow | feats ]
+    // where the rows y go (RunMode::d_y, mfx_batch.cpp)
+    struct PitchFeats {
+        bool on = false;
+        bool ran = false;                // a run has filled d_feats since the setter
+        bool paste = false;
+        int32_t columns = 0, F = 0, left = 0, right = 0, D = 0;
+        float pov_scale = 0.f, pov_offset = 0.f, pitch_scale = 0.f, delta_scale = 0.f;
+        double den = 0.0;
+        std::vector<int32_t> utt_tile0;  // [n_utt + 1] (build_pitch_layout at kPitchFeatRows)
+        DevBuf<int32_t> d_utt_tile0, d_tile_utt;
+        DevBuf<float> d_feats;           // [total_rows][F]
+        DevBuf<float> d_narrow;          // [total_rows][width] (paste only)
+        void drop() { on = false, ran = false, paste = false; }
+        void release() { d_utt_tile0.release(), d_tile_utt.release(), d_feats.release(), d_narrow.release(); }
+    } pf;
     // what a new utterance list invalidates (the converter is mfx_batch_plan's to drop: mfx_batch_plan_rates plans through
     // plan_batch too)
-    void detach() { va.drop(), xf.drop(), spk.drop(), vad.drop(), on.drop(), pt.drop(); }
+    void detach() { va.drop(), xf.drop(), spk.drop(), vad.drop(), on.drop(), pt.drop(), pf.drop(); }
 
     // ---- not tied to the plan
     // optional overlap of the delta/normalisation tail of batch i with the front end of batch i+1 (mfx_batch_overlap)
@@ -592,7 +610,10 @@ constexpr int64_t kSlabRowsMax = 1 << 17; // rows of the spectrum slab of the ba
 int plan_batch(mfx_handle *h, int32_t n_utt, const int64_t *offsets, const int64_t *lengths, int64_t *out_rows, int64_t *total_rows);
 // scratch for the compact statics of the planned batch: one buffer, two with overlap on (grown, never shrunk)
 int size_static16(mfx_handle *h);
-// row width of the batch entries' output: out_dim while a transform is in force, else `width`
+// width Wy of the rows y of a batch run, which the transform splices and the VAD moves: `width`, and the F pasted columns
+// while mfx_batch_set_pitch_feats pastes
+inline int batch_y_width(const mfx_handle *h) { return h->width + (h->batch.pf.on && h->batch.pf.paste ? h->batch.pf.F : 0); }
+// row width of the batch entries' output: out_dim while a transform is in force, else Wy
 int batch_out_width(const mfx_handle *h);
 // frames of an utterance of `samples` samples per channel on this handle (may be <= 0 for the framed methods: callers clamp)
 inline int64_t utt_frame_count(const mfx_handle *h, int64_t samples)

@@ -1,4 +1,4 @@
-// mfx_kernels.h -- launch interface of the gfx950 kernels (implemented in mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip, mfx_plp.hip, mfx_traps.hip, mfx_xform.hip, mfx_sessions.hip, mfx_resample.hip, mfx_speakers.hip, mfx_vad.hip, mfx_onorm.hip, mfx_stft.hip, mfx_pitch.hip: one translation unit per kernel family).
+// mfx_kernels.h -- launch interface of the gfx950 kernels (implemented in mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip, mfx_plp.hip, mfx_traps.hip, mfx_xform.hip, mfx_sessions.hip, mfx_resample.hip, mfx_speakers.hip, mfx_vad.hip, mfx_onorm.hip, mfx_stft.hip, mfx_pitch.hip, mfx_pitchfeat.hip: one translation unit per kernel family).
 //
 // Kernel inventory and the reference stage each one replaces:
 //   spectrum512 / fused512   segmenter.cl kernelSegmentWindow + AppleFFT fft0 + mfcc.cl kernelTranspose
@@ -15,6 +15,7 @@
 //   vad_*                    energy voice-activity decision + voiced-frame selection of finished rows (no reference analogue: the
 //                            reference hands every frame to its consumer)
 //   pitch_*                  pitch track beside the rows of a batch run: NCCF of the PCM + Viterbi path (no reference analogue)
+//   pitch_feats / pitch_paste  Kaldi's pitch features from that track, and their paste into the rows (no reference analogue)
 //   onorm_*                  online (causal, sliding-window) CMN / CVN of the batch and session entries (no reference analogue: its
 //                            NormalizerCPU keeps one block's statistics)
 //   stft_mel / stft_post     the STFT log-mel front end: exact-length DFT of centred frames on the matrix pipe, power, Slaney mel, log;
@@ -428,6 +429,32 @@ int pitch_groups(int lag_min, int lag_max);
 size_t pitch_nccf_lds_bytes(const PitchParams &p);
 // k_pitch_nccf over the tiles, then k_pitch_track over the utterances of the range
 hipError_t launch_pitch(const PitchParams &p, hipStream_t stream);
+
+// Pitch features (mfx_batch_set_pitch_feats; mfx_pitchfeat.hip; DESIGN.md, "Pitch features").  Tiles are runs of
+// kPitchFeatRows consecutive rows of one utterance (build_pitch_layout at that size); `pitch` and `feats` are indexed by the
+// plan's rows.
+constexpr int kPfPov = 1, kPfNorm = 2, kPfDelta = 4, kPfRaw = 8; // MFX_PF_* of include/mfx.h
+struct PitchFeatParams {
+    const float *pitch;    // [total_rows][2] lag, rho as k_pitch_track wrote them
+    const Segment *segs;   // [n_utt]: uses out_row0 / n_out
+    const int32_t *utt_tile0, *tile_utt; // [n_utt + 1], [tiles]
+    int32_t tile_first, n_tiles;         // = utt_tile0[u0], utt_tile0[u1] - utt_tile0[u0]
+    int32_t columns, F;    // MFX_PF_* bits (resolved: never 0) and their number
+    int32_t left, right, D;
+    float sample_rate, pov_scale, pov_offset, pitch_scale, delta_scale;
+    double delta_den;      // 2 sum of l^2 over l = 1 .. D
+    float *feats;          // [total_rows][F]
+};
+bool pitch_feat_params_ok(const PitchFeatParams &q);
+hipError_t launch_pitch_feats(const PitchFeatParams &q, hipStream_t stream);
+// rows [row0, row0 + rows) of out [.][Wd + F] = [ narrow [.][Wd] | feats [.][F] ]
+struct PitchPasteParams {
+    const float *narrow, *feats;
+    float *out;
+    int64_t row0, rows;
+    int32_t Wd, F;
+};
+hipError_t launch_pitch_paste(const PitchPasteParams &q, hipStream_t stream);
 
 // Online CMN / CVN (mfx_batch_set_online_norm, mfx_sessions_set_online_norm; mfx_onorm.hip; DESIGN.md, "Online
 // normalisation").  Chunks are runs of 32 rows of one utterance, numbered through the batch in utterance order; every

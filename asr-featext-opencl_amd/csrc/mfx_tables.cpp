@@ -1016,7 +1016,98 @@ bool host_pitch(const int16_t *pcm, int64_t n, int channels, int64_t T, int shif
     return true;
 }
 
+// ---- pitch features (include/mfx.h, mfx_batch_set_pitch_feats)
+
+bool pitch_feat_shape(int columns, int left, int right, int delta_window, float pov_scale, float pov_offset, float pitch_scale,
+                      float delta_scale, PitchFeatShape &s)
+{
+    if (columns < 0 || columns > 15) return false;
+    if (left < 0 || left > 1024 || right < 0 || right > 1024 || delta_window < 1 || delta_window > 16) return false;
+    if (!std::isfinite(pov_scale) || !std::isfinite(pov_offset) || !std::isfinite(pitch_scale) || !std::isfinite(delta_scale)) return false;
+    s.columns = columns == 0 ? 7 : columns;
+    s.F = 0;
+    for (int b = 1; b <= 8; b <<= 1) s.F += (s.columns & b) ? 1 : 0;
+    s.left = left, s.right = right, s.D = delta_window;
+    int den = 0;
+    for (int l = 1; l <= delta_window; ++l) den += 2 * l * l;
+    s.den = (double)den;
+    return true;
+}
+
+// Every double operation below is a statement of its own and this file is compiled with -ffp-contract=off: k_pitch_feats
+// (mfx_pitchfeat.hip) spells the same operations in the same order.
+bool host_pitch_feats(const float *pitch, int64_t T, float sample_rate, int columns, int left, int right, int delta_window,
+                      float pov_scale, float pov_offset, float pitch_scale, float delta_scale, float *feats)
+{
+    PitchFeatShape s;
+    if (!pitch_feat_shape(columns, left, right, delta_window, pov_scale, pov_offset, pitch_scale, delta_scale, s)) return false;
+    if (T < 0 || T > 0x7fffffff || !std::isfinite(sample_rate) || !(sample_rate > 0.f) || (T > 0 && (!pitch || !feats))) return false;
+    std::vector<double> w((size_t)T), p((size_t)T);
+    const double rate = (double)sample_rate;
+    for (int64_t t = 0; t < T; ++t) {
+        const double n = std::fmin(1.0, std::fmax(-1.0, (double)pitch[2 * t + 1]));
+        const double a = std::fabs(n);
+        const double a1 = a - 1.0;
+        const double x1 = 7.5 * a1, x2 = -10.0 * a, x3 = 20.0 * a1;
+        const double e1 = 5.4 * std::exp(x1), e2 = 4.8 * a, e3 = 2.0 * std::exp(x2), e4 = 4.2 * std::exp(x3);
+        double r = -5.2 + e1;
+        r = r + e2;
+        r = r - e3;
+        r = r + e4;
+        const double en = std::exp(-r);
+        const double dn = 1.0 + en;
+        w[(size_t)t] = 1.0 / dn;
+        const double ratio = rate / (double)pitch[2 * t];
+        p[(size_t)t] = std::log(ratio);
+    }
+    for (int64_t t = 0; t < T; ++t) {
+        float *out = feats + t * s.F;
+        const double pt = p[(size_t)t];
+        if (s.columns & 1) {
+            const double n = std::fmin(1.0, std::fmax(-1.0, (double)pitch[2 * t + 1]));
+            const double b = 1.0001 - n;
+            const double y = std::pow(b, 0.15) - 1.0;
+            const double v = (double)pov_scale * y;
+            *out++ = (float)(v + (double)pov_offset);
+        }
+        if (s.columns & 2) {
+            const int64_t lo = std::max<int64_t>(0, t - s.left), hi = std::min<int64_t>(T - 1, t + s.right);
+            double sw = 0.0, sp = 0.0;
+            for (int64_t i = lo; i <= hi; ++i) {
+                const double wp = w[(size_t)i] * p[(size_t)i];
+                sw = sw + w[(size_t)i];
+                sp = sp + wp;
+            }
+            const double mean = sp / sw;
+            const double d = pt - mean;
+            *out++ = (float)((double)pitch_scale * d);
+        }
+        if (s.columns & 4) {
+            double num = 0.0;
+            for (int l = 1; l <= s.D; ++l) {
+                const double d = p[(size_t)std::min<int64_t>(T - 1, t + l)] - p[(size_t)std::max<int64_t>(0, t - l)];
+                const double ld = (double)l * d;
+                num = num + ld;
+            }
+            const double v = (double)delta_scale * num;
+            *out++ = (float)(v / s.den);
+        }
+        if (s.columns & 8) *out++ = (float)pt;
+    }
+    return true;
+}
+
 } // namespace mfx
+
+extern "C" int mfx_host_pitch_feats(const float *pitch, int64_t T, float sample_rate, int32_t columns, int32_t left, int32_t right,
+                                    int32_t delta_window, float pov_scale, float pov_offset, float pitch_scale, float delta_scale,
+                                    float *feats)
+{
+    return mfx::host_pitch_feats(pitch, T, sample_rate, columns, left, right, delta_window, pov_scale, pov_offset, pitch_scale,
+                                 delta_scale, feats)
+               ? 0
+               : -7 /* MFX_ERR_ARG */;
+}
 
 // (the C entry of include/mfx.h, here beside its definition so that the stand-alone sanitizer program links it without HIP)
 extern "C" int mfx_host_pitch(const int16_t *pcm, int64_t n, int32_t channels, int64_t T, int32_t shift, int32_t window, int32_t lag_min,

@@ -131,6 +131,21 @@ bool build_pitch_layout(const int64_t *frames, int n_utt, int tile_frames, std::
 bool host_pitch(const int16_t *pcm, int64_t n, int channels, int64_t T, int shift, int window, int lag_min, int lag_max, float ballast,
                 float lag_cost, float penalty, int max_jump, float *pitch, int32_t *index, float *nccf);
 
+// Pitch features (mfx_batch_set_pitch_feats; DESIGN.md, "Pitch features").  pitch_feat_shape: the limits of include/mfx.h on
+// the eight parameters; fills the resolved column bits (0 -> POV | NORM_LOG_PITCH | DELTA), their number F and
+// den = 2 sum of l^2 over l = 1 .. D.  False outside them.  k_pitch_feats' tiles are build_pitch_layout's at kPitchFeatRows.
+struct PitchFeatShape {
+    int columns, F, left, right, D;
+    double den;
+};
+constexpr int kPitchFeatRows = 256;
+bool pitch_feat_shape(int columns, int left, int right, int delta_window, float pov_scale, float pov_offset, float pitch_scale,
+                      float delta_scale, PitchFeatShape &s);
+// The definition of include/mfx.h on host memory, for ONE utterance of T rows: pitch [T][2] = (lag, rho) -> feats [T][F].
+// False -- and nothing written -- on an argument outside the limits.
+bool host_pitch_feats(const float *pitch, int64_t T, float sample_rate, int columns, int left, int right, int delta_window,
+                      float pov_scale, float pov_offset, float pitch_scale, float delta_scale, float *feats);
+
 // exp(-2*pi*i*k/n) for k in [0, count), evaluated in double and rounded once to float.
 void build_twiddles(int n, int count, std::vector<float> &re_im_interleaved);
 

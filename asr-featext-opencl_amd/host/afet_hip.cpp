@@ -77,6 +77,10 @@ struct Options {
     bool vad = false;
     float vad_energy_threshold = 5.f, vad_energy_mean_scale = 0.5f, vad_proportion_threshold = 0.6f;
     int vad_frames_context = 0, vad_column = -1;
+    // --pitch: pitch track + Kaldi's three default pitch features (mfx_batch_set_pitch, mfx_batch_set_pitch_feats) pasted
+    // behind every row; --pitch-range LO:HI in Hz bounds the lags searched
+    bool pitch = false;
+    float pitch_lo = 50.f, pitch_hi = 400.f;
 };
 
 struct Wav {
@@ -724,8 +728,13 @@ void worker(const Options &o, int device, float sr, const std::vector<std::strin
         if (o.batch_mb > 0) {
             // ---- batches of whole files: read batch k + 1 and write batch k - 1 (helper threads) beside the device calls
             // of batch k (this thread)
-            const int limit = param.get_input_buffer_size(), width = param.get_output_data_width();
-            const int cols = width / (1 + o.dyn);
+            // (--pitch: rows of `width` floats, the extractor's `wd` and the three pitch features behind them)
+            const int limit = param.get_input_buffer_size(), wd = param.get_output_data_width(), width = wd + (o.pitch ? 3 : 0);
+            const int cols = wd / (1 + o.dyn);
+            auto set_pitch = [&] { // the track parameters of tools/pitch_bench.py; process-kaldi-pitch-feats' defaults, pasted
+                param.batch_set_pitch(0, (int)std::floor(sr / o.pitch_hi), (int)std::ceil(sr / o.pitch_lo), 0.f, 0.1f, 1.f, 16);
+                param.batch_set_pitch_feats(0, 75, 75, 2, 2.f, 0.f, 2.f, 10.f, true);
+            };
             const long double dt = o.bug_compat ? (long double)(o.shift_ms / sr) : o.shift_ms / 1000.0L;
             const long double t0 = o.bug_compat ? (long double)(0.5f * o.window_ms / sr) : 0.5L * o.window_ms / 1000.0L;
             std::vector<std::vector<char>> text_bufs((size_t)std::max(o.io_threads, 1));
@@ -775,7 +784,7 @@ void worker(const Options &o, int device, float sr, const std::vector<std::strin
                 // nothing.  Pass 2 normalises every batch with the final accumulators and writes its files.  A speaker's
                 // files keep their order, so the statistics are those of one batch holding the whole list.  The reference
                 // has no such rows: its single-block flush behaviour (B1) is not applied to them.
-                const int Wn = o.norm_after_dyn ? width : cols;
+                const int Wn = o.norm_after_dyn ? wd : cols;
                 std::vector<long long> count((size_t)o.n_spk, 0);
                 std::vector<double> acc((size_t)o.n_spk * 4 * Wn, 0.0);
                 bool have_prior = false;
@@ -808,6 +817,7 @@ void worker(const Options &o, int device, float sr, const std::vector<std::strin
                         if (!al.empty()) param.batch_set_alphas(al.data(), (int)al.size());
                         param.batch_set_speakers(spk.data(), (int)spk.size(), o.n_spk, have_prior ? count.data() : nullptr,
                                                  have_prior ? acc.data() : nullptr, pass == 2);
+                        if (o.pitch && pass == 2) set_pitch(); // (ahead of the VAD, which is sized for the wide rows)
                         if (o.vad && pass == 2) // (the rows that are written: selected from the normalised ones)
                             param.batch_set_vad(o.vad_column, o.vad_energy_threshold, o.vad_energy_mean_scale, o.vad_frames_context,
                                                 o.vad_proportion_threshold, MFX_VAD_SELECT);
@@ -883,6 +893,7 @@ void worker(const Options &o, int device, float sr, const std::vector<std::strin
                     }
                     if (o.online_window >= 0) // --online-window: every file normalised causally, as a live stream would be
                         param.batch_set_online_norm(o.online_window, o.online_prior_frames);
+                    if (o.pitch) set_pitch(); // (ahead of the VAD, which is sized for the wide rows)
                     if (o.vad)
                         param.batch_set_vad(o.vad_column, o.vad_energy_threshold, o.vad_energy_mean_scale, o.vad_frames_context,
                                             o.vad_proportion_threshold, MFX_VAD_SELECT);
@@ -917,6 +928,10 @@ void worker(const Options &o, int device, float sr, const std::vector<std::strin
                                 throw std::runtime_error("--online-window: \"" + files[2 * it.file] +
                                                          "\" would take the per-file loop (longer than one block, too short for the "
                                                          "deltas, or an alpha sweep): the online normaliser runs in batches of whole files only");
+                            if (o.pitch)
+                                throw std::runtime_error("--pitch: \"" + files[2 * it.file] +
+                                                         "\" would take the per-file loop (longer than one block, too short for the "
+                                                         "deltas, or an alpha sweep): the pitch features run in batches of whole files only");
                             if (o.vad)
                                 throw std::runtime_error("--vad: \"" + files[2 * it.file] +
                                                          "\" would take the per-file loop (longer than one block, too short for the "
@@ -1060,6 +1075,14 @@ int main(int argc, char **argv)
         else if (a == "--resample-to") o.resample_to = std::atoi(val());
         else if (a == "--resample-zeros") o.resample_zeros = std::atoi(val());
         else if (a == "--vad") o.vad = true;
+        else if (a == "--pitch") o.pitch = true;
+        else if (a == "--pitch-range") {
+            if (std::sscanf(val(), "%f:%f", &o.pitch_lo, &o.pitch_hi) != 2 || !(o.pitch_lo > 0.f) || !(o.pitch_hi > o.pitch_lo) ||
+                !std::isfinite(o.pitch_hi)) {
+                std::fprintf(stderr, "--pitch-range: LO:HI in Hz, 0 < LO < HI\n");
+                return 2;
+            }
+        }
         else if (a == "--vad-energy-threshold") o.vad_energy_threshold = (float)std::atof(val());
         else if (a == "--vad-energy-mean-scale") o.vad_energy_mean_scale = (float)std::atof(val());
         else if (a == "--vad-frames-context") o.vad_frames_context = std::atoi(val());
@@ -1120,6 +1143,11 @@ int main(int argc, char **argv)
                         "          [--vad-proportion-threshold x] [--vad-column n]]\n"
                         "  --vad: energy voice-activity decision on the device (needs batches); every output file holds its voiced\n"
                         "                rows only.  Defaults 5, 0.5, 0, 0.6 (compute-vad-energy's); column -1 = the last static one\n"
+                        "         [--pitch [--pitch-range LO:HI]]\n"
+                        "  --pitch: pitch track on the device and Kaldi's three pitch features from it (probability of voicing,\n"
+                        "                normalised log-pitch, delta log-pitch; process-kaldi-pitch-feats' defaults) as three more\n"
+                        "                columns of every row (needs batches; not with --method LOGMEL).  Lags of LO .. HI Hz are\n"
+                        "                searched, default 50:400\n"
                         "  --devs: one worker per listed GPU, files dealt from a shared queue\n"
                         "  inputs: RIFF/WAVE or NIST SPHERE, 16-bit PCM; output: the reference's text rows, or HTK binary\n");
             return 0;
@@ -1156,6 +1184,14 @@ int main(int argc, char **argv)
             std::fprintf(stderr, "--alpha-file holds %zu warp factors for %zu input files\n", o.file_alpha.size(), files.size() / 2);
             return 2;
         }
+    }
+    if (o.pitch && o.batch_mb <= 0) {
+        std::fprintf(stderr, "--pitch tracks whole files in batches: --batch-mb must be positive\n");
+        return 2;
+    }
+    if (o.pitch && o.method == MFX_METHOD_STFT_LOGMEL) {
+        std::fprintf(stderr, "--pitch is not served with --method LOGMEL: its frames are centred, the pitch track's are not\n");
+        return 2;
     }
     if (o.vad && o.batch_mb <= 0) {
         std::fprintf(stderr, "--vad selects frames in batches of whole files: --batch-mb must be positive\n");

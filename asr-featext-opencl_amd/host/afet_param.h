@@ -129,6 +129,12 @@ public:
     void batch_set_vad(int column, float energy_threshold, float energy_mean_scale, int frames_context, float proportion_threshold,
                        int mode);
     void batch_clear_vad();
+    // pitch track of the planned batch (mfx_batch_set_pitch) and Kaldi's pitch features from it (mfx_batch_set_pitch_feats;
+    // columns MFX_PF_*, 0: POV, normalised log-pitch, delta), pasted behind every row of a run when `paste`; the next
+    // batch_plan clears both
+    void batch_set_pitch(int window, int lag_min, int lag_max, float ballast, float lag_cost, float penalty, int max_jump);
+    void batch_set_pitch_feats(int columns, int left, int right, int delta_window, float pov_scale, float pov_offset, float pitch_scale,
+                               float delta_scale, bool paste);
     // what the last run decided: flags [total_rows], voiced [n_utt], threshold [n_utt]; any may be null.  Returns the batch's
     // voiced rows
     long long batch_vad_read(unsigned char *flags, int *voiced, float *threshold);

@@ -229,6 +229,17 @@ void MfccHip::batch_clear_vad()
     check(mfx_batch_clear_vad(m_handle));
 }
 
+void MfccHip::batch_set_pitch(int window, int lag_min, int lag_max, float ballast, float lag_cost, float penalty, int max_jump)
+{
+    check(mfx_batch_set_pitch(m_handle, window, lag_min, lag_max, ballast, lag_cost, penalty, max_jump));
+}
+
+void MfccHip::batch_set_pitch_feats(int columns, int left, int right, int delta_window, float pov_scale, float pov_offset, float pitch_scale,
+                                    float delta_scale, bool paste)
+{
+    check(mfx_batch_set_pitch_feats(m_handle, columns, left, right, delta_window, pov_scale, pov_offset, pitch_scale, delta_scale, paste ? 1 : 0));
+}
+
 long long MfccHip::batch_vad_read(unsigned char *flags, int *voiced, float *threshold)
 {
     int64_t total = 0;

@@ -86,6 +86,8 @@ EXPORTED_SYMBOLS = (
     "mfx_host_slaney_mel_table", "mfx_host_stft_basis", "mfx_host_stft_frame_count",
     "mfx_host_stft_lds_bytes",
     "mfx_batch_set_pitch", "mfx_batch_clear_pitch", "mfx_batch_pitch_read", "mfx_batch_pitch_device", "mfx_host_pitch",
+    "mfx_batch_set_pitch_feats", "mfx_batch_clear_pitch_feats", "mfx_batch_pitch_feats_read", "mfx_batch_pitch_feats_device",
+    "mfx_host_pitch_feats",
 )
 
 
@@ -199,6 +201,11 @@ def load_library():
     L.mfx_batch_pitch_read.argtypes = [vp, fp, p32, fp]
     L.mfx_batch_pitch_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.mfx_host_pitch.argtypes = [sp, i64, i32, i64, i32, i32, i32, i32, C.c_float, C.c_float, C.c_float, i32, fp, p32, fp]
+    L.mfx_batch_set_pitch_feats.argtypes = [vp, i32, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, i32]
+    L.mfx_batch_clear_pitch_feats.argtypes = [vp]
+    L.mfx_batch_pitch_feats_read.argtypes = [vp, fp]
+    L.mfx_batch_pitch_feats_device.argtypes = [vp, C.POINTER(vp), p32]
+    L.mfx_host_pitch_feats.argtypes = [fp, i64, C.c_float, i32, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, fp]
     _lib = L
     return L
 
@@ -379,6 +386,28 @@ def host_pitch(pcm, frames, shift, window, lag_min, lag_max, ballast=0.0, lag_co
     if rc != 0:
         raise MfxError(int(rc), "mfx_host_pitch failed")
     return pitch[:, 0].copy(), pitch[:, 1].copy(), index, nccf
+
+
+def _pf_count(columns):
+    c = int(columns)
+    return bin(c if c else 7).count("1") if 0 <= c <= 15 else 0
+
+
+def host_pitch_feats(lag, rho, sample_rate, columns=0, left=75, right=75, delta_window=2, pov_scale=2.0, pov_offset=0.0,
+                     pitch_scale=2.0, delta_scale=10.0):
+    """The pitch features of batch_set_pitch_feats on host memory, as include/mfx.h defines them (host code, no GPU needed),
+    for one utterance: lag [T], rho [T] as batch_pitch_read / host_pitch return them.  Returns feats [T][F] float32."""
+    L = load_library()
+    pitch = np.ascontiguousarray(np.stack((np.asarray(lag, np.float32).reshape(-1), np.asarray(rho, np.float32).reshape(-1)), axis=1))
+    T = pitch.shape[0]
+    out = np.zeros((T, _pf_count(columns)), np.float32)
+    fpt = C.POINTER(C.c_float)
+    rc = L.mfx_host_pitch_feats(pitch.ctypes.data_as(fpt), T, float(sample_rate), int(columns), int(left), int(right),
+                                int(delta_window), float(pov_scale), float(pov_offset), float(pitch_scale), float(delta_scale),
+                                out.ctypes.data_as(fpt))
+    if rc != 0:
+        raise MfxError(int(rc), "mfx_host_pitch_feats failed")
+    return out
 
 
 def host_xform_operands(A):
@@ -576,6 +605,7 @@ KERNEL_TABLE = (
 
 
 VAD_FLAGS, VAD_SELECT, VAD_PACK = 0, 1, 2                  # mfx_batch_set_vad modes (include/mfx.h)
+PF_POV, PF_NORM_LOG_PITCH, PF_DELTA, PF_RAW_LOG_PITCH = 1, 2, 4, 8   # MFX_PF_*: columns of mfx_batch_set_pitch_feats
 SPK_POOL, SPK_PRIOR_ONLY = 0, 1                            # mfx_batch_set_speakers modes (include/mfx.h)
 ENGINE_NO_FRONT1024, ENGINE_FUSE_DELTA, ENGINE_NO_FRONT2048, ENGINE_STREAM_KERNELS, ENGINE_NORM_TWO_KERNELS = 1, 2, 4, 8, 16
 ENGINE_DMA_SMALL_BLOCKS, ENGINE_NO_DCT_SPLIT, ENGINE_NO_STUFF256, ENGINE_FRONT1024_12_WAVES = 32, 64, 128, 256     # mfx_config.engine bits (include/mfx.h)
@@ -725,6 +755,7 @@ class MfccHip:
         self._chk(self._L.mfx_batch_plan(self._h, off.size, off.ctypes.data_as(p64), ln.ctypes.data_as(p64),
                                          rows.ctypes.data_as(p64), C.byref(total)))
         self._plan_rows, self._plan_total = rows, total.value
+        self._pf_F = self._paste_F = 0                               # (a plan drops the attachments)
         return rows, total.value
 
     def batch_plan_rates(self, offsets, lengths, rates, zeros=0, rolloff=0.0):
@@ -742,6 +773,7 @@ class MfccHip:
                                                rt.ctypes.data_as(C.POINTER(C.c_int32)), int(zeros), float(rolloff),
                                                rows.ctypes.data_as(p64), C.byref(total)))
         self._plan_rows, self._plan_total = rows, total.value
+        self._pf_F = self._paste_F = 0                               # (a plan drops the attachments)
         return rows, total.value
 
     def batch_resample_layout(self):
@@ -795,8 +827,8 @@ class MfccHip:
         if a.ndim != 3:
             raise ValueError("A must be [out_dim][in_dim] or [n_xf][out_dim][in_dim]")
         n_xf, out_dim, in_dim = a.shape
-        if in_dim != (int(left) + int(right) + 1) * self.get_output_data_width():
-            raise ValueError("A must have (left + right + 1) * get_output_data_width() columns")
+        if in_dim != (int(left) + int(right) + 1) * (self.get_output_data_width() + int(getattr(self, "_paste_F", 0))):
+            raise ValueError("A must have (left + right + 1) * get_output_data_width() columns (and the pasted pitch features')")
         fpt, ipt = C.POINTER(C.c_float), C.POINTER(C.c_int32)
         bb = None
         if b is not None:
@@ -929,6 +961,38 @@ class MfccHip:
     def batch_clear_pitch(self):
         self._chk(self._L.mfx_batch_clear_pitch(self._h))
         self._pitch_K = 0
+        self._pf_F = self._paste_F = 0                               # (the pitch features go with the track)
+
+    host_pitch_feats = staticmethod(host_pitch_feats)
+
+    def batch_set_pitch_feats(self, columns=0, left=75, right=75, delta_window=2, pov_scale=2.0, pov_offset=0.0, pitch_scale=2.0,
+                              delta_scale=10.0, paste=False):
+        """Kaldi's pitch features from the pitch track (mfx_batch_set_pitch_feats; needs batch_set_pitch): columns is a sum of
+        PF_POV, PF_NORM_LOG_PITCH, PF_DELTA, PF_RAW_LOG_PITCH (0: the first three, process-kaldi-pitch-feats' default, as
+        are the other defaults).  batch_pitch_feats_read returns them; with paste they are also the last F columns of every
+        row of a run, ahead of the transform and the VAD.  A later batch_plan clears it."""
+        self._chk(self._L.mfx_batch_set_pitch_feats(self._h, int(columns), int(left), int(right), int(delta_window), float(pov_scale),
+                                                    float(pov_offset), float(pitch_scale), float(delta_scale), 1 if paste else 0))
+        self._pf_F = _pf_count(columns)
+        self._paste_F = self._pf_F if paste else 0
+
+    def batch_clear_pitch_feats(self):
+        self._chk(self._L.mfx_batch_clear_pitch_feats(self._h))
+        self._pf_F = self._paste_F = 0
+
+    def batch_pitch_feats_read(self):
+        """feats [total_rows][F] float32 of the last batch run while pitch features are in force (MfxError with status -8
+        otherwise), indexed by the plan's rows."""
+        d, F = self.batch_pitch_feats_device()
+        out = np.zeros((int(self._plan_total or 0), F), np.float32)
+        self._chk(self._L.mfx_batch_pitch_feats_read(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def batch_pitch_feats_device(self):
+        """(device address of feats [total_rows][F], F) of the handle-owned array of the pitch features."""
+        a, F = C.c_void_p(), C.c_int32(0)
+        self._chk(self._L.mfx_batch_pitch_feats_device(self._h, C.byref(a), C.byref(F)))
+        return a.value or 0, int(F.value)
 
     def batch_pitch_read(self, nccf=False, f0=False):
         """(lag [total_rows] float32, rho [total_rows] float32, index [total_rows] int32) of the last batch run while a pitch

@@ -519,6 +519,61 @@ int mfx_batch_pitch_read(mfx_handle *h, float *pitch /* [total_rows][2]: lag, rh
                          float *nccf /* [total_rows][K] */);
 int mfx_batch_pitch_device(const mfx_handle *h, const float **d_pitch, const int32_t **d_index);
 
+/* Kaldi's pitch features from the pitch track, and their paste into the rows of a batch run ("Pitch features"):
+ * what process-kaldi-pitch-feats and paste-feats give a Kaldi-style recipe -- a probability-of-voicing feature, the log-pitch
+ * with a POV-weighted sliding mean removed, a delta of the log-pitch, optionally the raw log-pitch -- on the device, from the
+ * (lag, rho) rows k_pitch_track leaves there.  No reference analogue.
+ *   Scope.  Valid while a pitch track is in force (mfx_batch_set_pitch): MFX_ERR_STATE otherwise, and before a plan.
+ *     MFX_ERR_DEVICE on a planning handle, before any argument is looked at.  A later plan drops the attachment with the
+ *     others; mfx_batch_clear_pitch drops it with the track; mfx_batch_clear_pitch_feats drops it alone.
+ *   Arguments.  columns: MFX_PF_* bits, 0 means POV | NORM_LOG_PITCH | DELTA (Kaldi's default); F is the number of bits set,
+ *     the columns are delivered in the order of the enum (Kaldi's).  left, right: 0 .. 1024 rows of the normalisation window
+ *     (Kaldi: 75, 75, its normalization-left-context / -right-context).  delta_window D: 1 .. 16 (Kaldi: 2).  The four
+ *     scales must be finite (Kaldi: pov_scale 2, pov_offset 0, pitch_scale 2, delta_scale 10).  paste: 0 or 1.  Anything else
+ *     is MFX_ERR_ARG, and nothing changes.
+ *   Per utterance of T rows (lag_t, rho_t).  Every operation is in double and rounded on its own (no contraction); an
+ *     output is (float) of the double.
+ *       n = min(1, max(-1, (double)rho_t)), a = |n|
+ *       r = -5.2 + 5.4 exp(7.5 (a - 1)) + 4.8 a - 2 exp(-10 a) + 4.2 exp(20 (a - 1)), summed left to right;
+ *       w_t = 1 / (1 + exp(-r))   (Kaldi's NccfToPov; in (0, 1): no window is empty of weight)
+ *       p_t = ln((double)sample_rate / (double)lag_t)
+ *     POV             pov_scale * (pow(1.0001 - n, 0.15) - 1) + pov_offset
+ *     NORM_LOG_PITCH  lo = max(0, t - left), hi = min(T - 1, t + right); over i = lo .. hi ascending sw += w_i and
+ *                     sp += w_i * p_i -- direct sums per row, not running sums: a row does not depend on any tiling --
+ *                     and the value is pitch_scale * (p_t - sp / sw)
+ *     DELTA           the library's own regression: num = sum over l = 1 .. D ascending of
+ *                     l * (p[min(T - 1, t + l)] - p[max(0, t - l)]), edges replicated as in the delta stage; the value is
+ *                     (delta_scale * num) / (2 sum of l^2)
+ *     RAW_LOG_PITCH   p_t
+ *     A row is a function of its own utterance's track and the parameters only.  exp, ln and pow are the platform's: the
+ *     device and mfx_host_pitch_feats agree to within the functions' errors, not bit for bit (tests/pitchfeat_ref.py bounds
+ *     it).
+ *   NOT served: Kaldi's random delta-pitch-noise-stddev (the DELTA column has no noise added), and its online mode, whose
+ *     normalisation window is not symmetric and grows with the stream (normalization-left-context frames behind a lookahead).
+ *   Run.  k_pitch_feats runs on the handle's own stream directly behind k_pitch_track; it fills feats [total_rows][F], a
+ *     handle-owned array indexed by the plan's rows in every mode, as the pitch arrays are.
+ *   Paste.  With paste = 1 the rows y of a run -- behind the deltas and every normaliser, ahead of the transform and the VAD --
+ *     become [ y (Wd columns) | feats (F columns) ], of width Wy = Wd + F; k_pitch_paste writes them on the stream the tail
+ *     runs on, as the last launch ahead of the transform.  mfx_batch_output_width becomes Wy (out_dim under a transform);
+ *     mfx_batch_set_transform takes in_dim = (left + right + 1) * Wy and splices the wide rows; the VAD reads its column among
+ *     the first Wd columns and, in SELECT / PACK, moves the wide rows; mfx_batch_run_host sizes by the new width.  The first
+ *     Wd columns are bit for bit what the handle delivers without the paste, and every placement guarantee of
+ *     mfx_batch_run_device holds for the wide rows.  A call that would change Wy -- setting or clearing with paste, changing F
+ *     under paste, mfx_batch_clear_pitch under paste -- answers MFX_ERR_STATE while a transform or a VAD is in force: clear
+ *     them, set the paste, set them again.  With paste = 0 nothing outside the feats array changes.
+ *   Memory.  The setter allocates, after waiting for the handle's streams: the feats array, its tile descriptors and, under
+ *     paste, a scratch [total_rows][Wd] for the narrow rows.  The run still allocates nothing.
+ *   Read-back.  mfx_batch_pitch_feats_read synchronises and copies feats [total_rows][F].  MFX_ERR_STATE without the
+ *     attachment or before a run; a batch without rows counts as run.  mfx_batch_pitch_feats_device returns the device array
+ *     and F: valid until the next plan, set or clear, ordered on the handle's stream.
+ * NOT served: the session entries (mfx_sessions_*) and the streaming interface ignore the attachment. */
+enum { MFX_PF_POV = 1, MFX_PF_NORM_LOG_PITCH = 2, MFX_PF_DELTA = 4, MFX_PF_RAW_LOG_PITCH = 8 };
+int mfx_batch_set_pitch_feats(mfx_handle *h, int32_t columns, int32_t left, int32_t right, int32_t delta_window,
+                              float pov_scale, float pov_offset, float pitch_scale, float delta_scale, int32_t paste);
+int mfx_batch_clear_pitch_feats(mfx_handle *h);
+int mfx_batch_pitch_feats_read(mfx_handle *h, float *feats /* [total_rows][F] */);
+int mfx_batch_pitch_feats_device(const mfx_handle *h, const float **d_feats, int32_t *F);
+
 /* ---- sample-rate conversion in front of a batch ("Sample-rate conversion").  No reference analogue: the
  *      reference refuses a file whose rate differs from the first file's (ASR_OCL.cpp:191). ----
  *
@@ -716,6 +771,13 @@ int mfx_host_online_norm(const float *rows, int64_t T, int32_t pitch, int32_t Wn
 int mfx_host_pitch(const int16_t *pcm, int64_t n, int32_t channels, int64_t T, int32_t shift, int32_t window, int32_t lag_min,
                    int32_t lag_max, float ballast, float lag_cost, float penalty, int32_t max_jump, float *pitch, int32_t *index,
                    float *nccf);
+/* The pitch features (mfx_batch_set_pitch_feats) on host memory, as defined there, for ONE utterance of T rows:
+ * pitch [T][2] = (lag, rho) as mfx_batch_pitch_read / mfx_host_pitch deliver them; writes feats [T][F].  MFX_ERR_ARG on
+ * anything outside the limits, a sample_rate that is not finite and positive included (nothing is written then).  Test /
+ * inspection aid. */
+int mfx_host_pitch_feats(const float *pitch /* [T][2]: lag, rho */, int64_t T, float sample_rate, int32_t columns, int32_t left,
+                         int32_t right, int32_t delta_window, float pov_scale, float pov_offset, float pitch_scale,
+                         float delta_scale, float *feats /* [T][F] */);
 /* frame count, integer arithmetic (parambase.cpp:16-19 without the float32 division) */
 int64_t mfx_host_frame_count(int64_t samples, int32_t window_size, int32_t shift);
 /* STFT log-mel (MFX_METHOD_STFT_LOGMEL) tables as uploaded, and its frame rule.  mfx_host_slaney_mel_table: weights
