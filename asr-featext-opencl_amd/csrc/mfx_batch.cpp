@@ -67,11 +67,9 @@ int run_online_norm(mfx_handle *h, hipStream_t stream, const float *d_pre, float
     op.prior_count = B.on.prior_count;
     op.prior_acc = B.on.d_prior.p;
     op.segs = B.d_segs.p;
-    op.utt_chunk0 = B.on.d_utt_chunk0.p;
-    op.chunk_utt = B.on.d_chunk_utt.p;
+    op.chunks = B.on.chunks.range(u0, u1);
     op.tot = B.on.d_tot.p;
     op.u0 = u0, op.n_utt = u1 - u0;
-    op.chunk_first = B.on.utt_chunk0[u0], op.n_chunks = B.on.utt_chunk0[u1] - B.on.utt_chunk0[u0];
     HIP_TRY(h, launch_onorm(op, stream));
     return MFX_OK;
 }
@@ -250,9 +248,7 @@ int run_pitch(mfx_handle *h, const RunMode &m, const int16_t *pcm, int u0, int u
     pp.channels = h->channels;
     pp.utt = pt.d_utt.p;
     pp.segs = B.d_segs.p;
-    pp.utt_tile0 = pt.d_utt_tile0.p, pp.tile_utt = pt.d_tile_utt.p;
-    pp.tile_first = pt.utt_tile0[u0], pp.n_tiles = pt.utt_tile0[u1] - pt.utt_tile0[u0];
-    pp.tile_frames = pt.tile_frames;
+    pp.tiles = pt.tiles.range(u0, u1);
     pp.u0 = u0, pp.u1 = u1;
     pp.window = pt.window, pp.shift = h->S, pp.lag_min = pt.lag_min, pp.lag_max = pt.lag_max, pp.K = pt.K, pp.J = pt.J;
     pp.span_pad = pitch_span_pad(h->S);
@@ -270,8 +266,7 @@ int run_pitch(mfx_handle *h, const RunMode &m, const int16_t *pcm, int u0, int u
     PitchFeatParams fp{};
     fp.pitch = pt.d_pitch.p;
     fp.segs = B.d_segs.p;
-    fp.utt_tile0 = pf.d_utt_tile0.p, fp.tile_utt = pf.d_tile_utt.p;
-    fp.tile_first = pf.utt_tile0[u0], fp.n_tiles = pf.utt_tile0[u1] - pf.utt_tile0[u0];
+    fp.tiles = pf.tiles.range(u0, u1);
     fp.columns = pf.columns, fp.F = pf.F;
     fp.left = pf.left, fp.right = pf.right, fp.D = pf.D;
     fp.sample_rate = h->cfg.sample_rate;
@@ -307,10 +302,7 @@ int run_vad(mfx_handle *h, const RunMode &m, int u0, int u1)
     vp.segs = B.d_segs.p;
     vp.n_utt = B.n_utt;
     vp.u0 = u0, vp.u1 = u1;
-    vp.utt_tile0 = v.d_utt_tile0.p, vp.utt_chunk0 = v.d_utt_chunk0.p;
-    vp.tile_utt = v.d_tile_utt.p, vp.chunk_utt = v.d_chunk_utt.p;
-    vp.tile_first = v.utt_tile0[u0], vp.n_tiles = v.utt_tile0[u1] - v.utt_tile0[u0];
-    vp.chunk_first = v.utt_chunk0[u0], vp.n_chunks = v.utt_chunk0[u1] - v.utt_chunk0[u0];
+    vp.tiles = v.tiles.range(u0, u1), vp.chunks = v.chunks.range(u0, u1);
     vp.energy_threshold = v.et, vp.energy_mean_scale = v.ms, vp.proportion_threshold = v.prop;
     vp.frames_context = v.ctx;
     vp.mode = v.mode;
@@ -433,10 +425,9 @@ int batch_run_range(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_tot
         none.tail_stream = h->stream;
         return run_vad(h, none, u0, u1);
     }
-    if ((B.xf.on && B.xf.d_y.n < (size_t)B.total_rows * batch_y_width(h)) || (h->traps && B.d_logmel.n < (size_t)B.total_rows * B.mel_pitch) ||
-        (B.vad.on && B.vad.mode != MFX_VAD_FLAGS && B.vad.d_rows.n < (size_t)B.total_rows * batch_out_width(h)) ||
-        (B.on.on && B.on.d_raw.n < (size_t)B.total_rows * h->width) || (B.pt.on && B.pt.d_nccf.n < (size_t)B.total_rows * B.pt.K) ||
-        (B.pf.on && (!B.pt.on || B.pf.d_feats.n < (size_t)B.total_rows * B.pf.F || (B.pf.paste && B.pf.d_narrow.n < (size_t)B.total_rows * h->width))))
+    const size_t rows = (size_t)B.total_rows; // (every scratch a launch below writes to holds the plan's rows)
+    if ((h->traps && B.d_logmel.n < rows * B.mel_pitch) || !B.xf.sized(rows, batch_y_width(h)) || !B.vad.sized(rows, batch_out_width(h)) ||
+        !B.on.sized(rows, h->width) || !B.pt.sized(rows) || !B.pf.sized(rows, h->width, B.pt.on))
         return fail(h, MFX_ERR_STATE, "batch not planned");
 
     FrontParams p;
@@ -482,9 +473,7 @@ extern "C" void mfx_free_pinned(void *p)
 extern "C" int mfx_batch_overlap(mfx_handle *h, int enable)
 {
     MFX_DEVICE_ENTRY(h);
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc = mfx_synchronize(h);
-    if (rc != MFX_OK) return rc;
+    if (const int rc = sync_device(h); rc != MFX_OK) return rc;
     if (enable && !h->batch.ov.stream2) {
         HIP_TRY(h, hipStreamCreateWithFlags(&h->batch.ov.stream2, hipStreamNonBlocking));
         for (int i = 0; i < 2; ++i) {

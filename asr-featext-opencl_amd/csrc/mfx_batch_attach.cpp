@@ -24,8 +24,7 @@ extern "C" int mfx_batch_set_alphas(mfx_handle *h, const float *alphas, int32_t 
     std::vector<int64_t> runs;
     build_alpha_runs(alphas, h->batch.utt_frames.data(), n_utt, tables, off, runs);
     if (tables.size() > 4096) return fail(h, MFX_ERR_ARG, "more than 4096 distinct warp factors");
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc = mfx_synchronize(h); // (a run in flight may read the tables and lists replaced below)
+    int rc = sync_device(h); // (a run in flight may read the tables and lists replaced below)
     if (rc != MFX_OK) return rc;
     h->batch.va.drop();
     if (tables.empty()) return MFX_OK; // (a plan without utterances)
@@ -53,9 +52,7 @@ extern "C" int mfx_batch_set_speakers(mfx_handle *h, const int32_t *utt_spk, int
     MFX_DEVICE_ENTRY(h);
     if (h->cfg.norm == MFX_NORM_NONE) return fail(h, MFX_ERR_CONFIG, "mfx_batch_set_speakers: the handle does not normalise (norm = NONE)");
     if (!utt_spk && n_utt == 0) { // back to every utterance's own statistics and run_norm's kernels
-        HIP_TRY(h, hipSetDevice(h->device));
-        const int rc = mfx_synchronize(h); // (a run in flight may read what a later call replaces)
-        if (rc != MFX_OK) return rc;
+        if (const int rc = sync_device(h); rc != MFX_OK) return rc; // (a run in flight may read what a later call replaces)
         h->batch.spk.drop();
         return MFX_OK;
     }
@@ -79,15 +76,14 @@ extern "C" int mfx_batch_set_speakers(mfx_handle *h, const int32_t *utt_spk, int
                 return fail(h, MFX_ERR_ARG, "MFX_SPK_PRIOR_ONLY: a speaker with rows in the batch has a prior of count 0");
     const int Wn = spk_wn(h);
     const int tile_rows = spk_tile_rows(Wn);
-    std::vector<int32_t> chunk0((size_t)n_utt + 1);
+    std::vector<int32_t> chunk0; // (k_spk_sums takes the utterance from the grid: no item_utt)
+    if (!build_utt_tiling(frames.data(), n_utt, kNormChunkRows, chunk0, nullptr)) return fail(h, MFX_ERR_ARG, "batch too long");
+    const size_t chunks = (size_t)chunk0[n_utt];
     std::vector<SpkTile> tiles;
-    int64_t chunks = 0, max_rows = 0;
+    int64_t max_rows = 0;
     for (int u = 0; u < n_utt; ++u) {
-        chunk0[u] = (int32_t)chunks;
-        chunks += spk_chunks(frames[u]);
         max_rows = std::max(max_rows, frames[u]);
-        if (chunks > 0x7ffffff0 || (frames[u] + tile_rows - 1) / tile_rows + (int64_t)tiles.size() > 0x7ffffff0)
-            return fail(h, MFX_ERR_ARG, "batch too long");
+        if ((frames[u] + tile_rows - 1) / tile_rows + (int64_t)tiles.size() > 0x7ffffff0) return fail(h, MFX_ERR_ARG, "batch too long");
         for (int64_t r = 0; r < frames[u]; r += tile_rows) {
             SpkTile t;
             t.row0 = h->batch.utt_row[u] + r;
@@ -96,9 +92,7 @@ extern "C" int mfx_batch_set_speakers(mfx_handle *h, const int32_t *utt_spk, int
             tiles.push_back(t);
         }
     }
-    chunk0[n_utt] = (int32_t)chunks;
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc = mfx_synchronize(h); // (a run in flight may read the lists replaced below)
+    int rc = sync_device(h); // (a run in flight may read the lists replaced below)
     if (rc != MFX_OK) return rc;
     h->batch.spk.drop();
     h->batch.spk.ran = false;
@@ -114,7 +108,7 @@ extern "C" int mfx_batch_set_speakers(mfx_handle *h, const int32_t *utt_spk, int
     } else {
         h->batch.spk.d_prior_n.release(), h->batch.spk.d_prior.release();
     }
-    HIP_TRY(h, h->batch.spk.d_partial.alloc((size_t)chunks * per));
+    HIP_TRY(h, h->batch.spk.d_partial.alloc(chunks * per));
     HIP_TRY(h, h->batch.spk.d_count.alloc((size_t)n_spk));
     HIP_TRY(h, h->batch.spk.d_acc.alloc((size_t)n_spk * per));
     HIP_TRY(h, h->batch.spk.d_stats.alloc((size_t)n_spk * 2 * Wn));
@@ -131,9 +125,7 @@ extern "C" int mfx_batch_speaker_stats(mfx_handle *h, int64_t *count, double *ac
     MFX_DEVICE_ENTRY(h);
     if (!h->batch.spk.on) return fail(h, MFX_ERR_STATE, "mfx_batch_speaker_stats: no speaker list is in force");
     if (!h->batch.spk.ran) return fail(h, MFX_ERR_STATE, "mfx_batch_speaker_stats: no batch has run since the list was set");
-    HIP_TRY(h, hipSetDevice(h->device));
-    const int rc = mfx_synchronize(h);
-    if (rc != MFX_OK) return rc;
+    if (const int rc = sync_device(h); rc != MFX_OK) return rc;
     const size_t n = (size_t)h->batch.spk.n_spk, Wn = (size_t)spk_wn(h);
     if (count) HIP_TRY(h, hipMemcpy(count, h->batch.spk.d_count.p, n * sizeof(int64_t), hipMemcpyDeviceToHost));
     if (acc) HIP_TRY(h, hipMemcpy(acc, h->batch.spk.d_acc.p, n * 4 * Wn * sizeof(double), hipMemcpyDeviceToHost));
@@ -162,7 +154,7 @@ int check_online_norm(mfx_handle *h, const char *who, int32_t window, int32_t pr
     if (h->cfg.norm != MFX_NORM_CMN && h->cfg.norm != MFX_NORM_CVN)
         return fail(h, MFX_ERR_CONFIG, w + ": the online normaliser serves norm = CMN and CVN only");
     if (spk_wn(h) > 256) return fail(h, MFX_ERR_CONFIG, w + ": more than 256 normalised columns");
-    if (window < 0 || window > 4096 || window % 32 != 0) return fail(h, MFX_ERR_ARG, w + ": window must be 0 or a multiple of 32 in 32 .. 4096");
+    if (window < 0 || window > 4096 || window % kOnormChunk != 0) return fail(h, MFX_ERR_ARG, w + ": window must be 0 or a multiple of 32 in 32 .. 4096");
     if (prior_frames < 0 || prior_frames > (1 << 20)) return fail(h, MFX_ERR_ARG, w + ": prior_frames must be 0 .. 2^20");
     if (prior_count < 0) return fail(h, MFX_ERR_ARG, w + ": negative prior_count");
     if ((prior_acc == nullptr) != (prior_count == 0)) return fail(h, MFX_ERR_ARG, w + ": prior_acc must be NULL exactly when prior_count is 0");
@@ -179,32 +171,19 @@ extern "C" int mfx_batch_set_online_norm(mfx_handle *h, int32_t window, int32_t 
     if (rc != MFX_OK) return rc;
     if (B.spk.on) return fail(h, MFX_ERR_STATE, "mfx_batch_set_online_norm: a speaker list is in force (clear it first)");
     const int Wn = spk_wn(h);
-    std::vector<int32_t> chunk0((size_t)B.n_utt + 1), chunk_utt;
-    int64_t chunks = 0;
-    for (int u = 0; u < B.n_utt; ++u) {
-        chunk0[u] = (int32_t)chunks;
-        const int64_t n = (B.utt_frames[u] + 31) / 32;
-        chunks += n;
-        if (chunks > 0x7ffffff0) return fail(h, MFX_ERR_ARG, "batch too long");
-        chunk_utt.insert(chunk_utt.end(), (size_t)n, u);
-    }
-    chunk0[B.n_utt] = (int32_t)chunks;
-    HIP_TRY(h, hipSetDevice(h->device));
-    rc = mfx_synchronize(h); // (a run in flight may read the lists replaced below)
+    rc = sync_device(h); // (a run in flight may read the lists replaced below)
     if (rc != MFX_OK) return rc;
     BatchState::Onorm &on = B.on;
     on.drop();
     // (everything mfx_batch_run_device needs is allocated here: that entry never allocates)
-    HIP_TRY(h, h->upload(on.d_utt_chunk0, chunk0));
-    HIP_TRY(h, h->upload(on.d_chunk_utt, chunk_utt));
+    if ((rc = on.chunks.set(h, kOnormChunk)) != MFX_OK) return rc;
     if (prior_count > 0)
         HIP_TRY(h, h->upload(on.d_prior, std::vector<double>(prior_acc, prior_acc + (size_t)2 * Wn)));
     else
         on.d_prior.release();
-    HIP_TRY(h, on.d_tot.alloc((size_t)chunks * 2 * Wn));
+    HIP_TRY(h, on.d_tot.alloc(on.chunks.items() * 2 * Wn));
     const size_t need = (size_t)std::max<int64_t>(B.total_rows, 1) * h->width;
     if (on.d_raw.n < need) HIP_TRY(h, on.d_raw.alloc(need));
-    on.utt_chunk0.swap(chunk0);
     on.window = window, on.prior_frames = prior_frames, on.prior_count = prior_count;
     on.on = true;
     return MFX_OK;
@@ -213,12 +192,10 @@ extern "C" int mfx_batch_set_online_norm(mfx_handle *h, int32_t window, int32_t 
 extern "C" int mfx_batch_clear_online_norm(mfx_handle *h)
 {
     MFX_DEVICE_ENTRY(h);
-    HIP_TRY(h, hipSetDevice(h->device));
-    const int rc = mfx_synchronize(h); // (a run in flight may read what is released below)
-    if (rc != MFX_OK) return rc;
+    if (const int rc = sync_device(h); rc != MFX_OK) return rc; // (a run in flight may read what is released below)
     BatchState::Onorm &on = h->batch.on;
     on.drop();
-    on.d_utt_chunk0.release(), on.d_chunk_utt.release(), on.d_prior.release(), on.d_tot.release(), on.d_raw.release();
+    on.release();
     return MFX_OK;
 }
 
@@ -231,11 +208,9 @@ extern "C" int mfx_batch_set_transform(mfx_handle *h, int32_t left, int32_t righ
 {
     MFX_DEVICE_ENTRY(h);
     if (!A && n_xf == 0) { // back to the rows the handle delivered before, in the caller's d_out
-        HIP_TRY(h, hipSetDevice(h->device));
-        const int rc = mfx_synchronize(h); // (a run in flight may read what is released below)
-        if (rc != MFX_OK) return rc;
+        if (const int rc = sync_device(h); rc != MFX_OK) return rc; // (a run in flight may read what is released below)
         h->batch.xf.drop();
-        h->batch.xf.d_ops.release(), h->batch.xf.d_bias.release(), h->batch.xf.d_idx.release(), h->batch.xf.d_y.release();
+        h->batch.xf.release();
         return size_vad_rows(h); // (the output rows are Wy floats again)
     }
     if (!h->batch.planned) return fail(h, MFX_ERR_STATE, "mfx_batch_set_transform: no batch is planned");
@@ -255,8 +230,7 @@ extern "C" int mfx_batch_set_transform(mfx_handle *h, int32_t left, int32_t righ
     probe.left = left, probe.right = right, probe.out_dim = out_dim;
     // (the limits above leave a tile of 16 rows inside 160 KB at every row width a handle can have; checked all the same)
     if (xform_tile_rows(probe) == 0) return fail(h, MFX_ERR_ARG, "no tile of k_splice_affine fits the LDS for this shape");
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc = mfx_synchronize(h); // (a run in flight may read the matrices and the index replaced below)
+    int rc = sync_device(h); // (a run in flight may read the matrices and the index replaced below)
     if (rc != MFX_OK) return rc;
     h->batch.xf.drop();
     const int tiles = (out_dim + 15) / 16, steps = (int)((in_dim + 3) / 4);
@@ -303,26 +277,20 @@ extern "C" int mfx_batch_set_vad(mfx_handle *h, int32_t column, float energy_thr
     BatchState &B = h->batch;
     if (!B.planned) return fail(h, MFX_ERR_STATE, "mfx_batch_set_vad: no batch is planned");
     if (column < -1 || column >= h->width) return fail(h, MFX_ERR_ARG, "column must be -1 (the last static column) or inside the row");
-    if (frames_context < 0 || frames_context > 64) return fail(h, MFX_ERR_ARG, "frames_context must be 0 .. 64");
+    if (frames_context < 0 || frames_context > kVadTileRows) return fail(h, MFX_ERR_ARG, "frames_context must be 0 .. 64");
     if (!(proportion_threshold > 0.f && proportion_threshold <= 1.f)) return fail(h, MFX_ERR_ARG, "proportion_threshold must lie in (0, 1]");
     if (!std::isfinite(energy_threshold) || !std::isfinite(energy_mean_scale))
         return fail(h, MFX_ERR_ARG, "energy_threshold and energy_mean_scale must be finite");
     if (mode != MFX_VAD_FLAGS && mode != MFX_VAD_SELECT && mode != MFX_VAD_PACK)
         return fail(h, MFX_ERR_ARG, "mode must be MFX_VAD_FLAGS, MFX_VAD_SELECT or MFX_VAD_PACK");
-    std::vector<int32_t> tile0, tile_utt, chunk0, chunk_utt;
-    if (!build_vad_layout(B.utt_frames.data(), B.n_utt, tile0, tile_utt, chunk0, chunk_utt)) return fail(h, MFX_ERR_ARG, "batch too long");
-    HIP_TRY(h, hipSetDevice(h->device));
-    const int rc = mfx_synchronize(h); // (a run in flight may read the lists replaced below)
+    int rc = sync_device(h); // (a run in flight may read the lists replaced below)
     if (rc != MFX_OK) return rc;
     BatchState::Vad &v = B.vad;
     v.drop();
     // (everything mfx_batch_run_device needs is allocated here: that entry never allocates)
-    const size_t n = (size_t)B.n_utt, tiles = tile_utt.size();
-    HIP_TRY(h, h->upload(v.d_utt_tile0, tile0));
-    HIP_TRY(h, h->upload(v.d_tile_utt, tile_utt));
-    HIP_TRY(h, h->upload(v.d_utt_chunk0, chunk0));
-    HIP_TRY(h, h->upload(v.d_chunk_utt, chunk_utt));
-    HIP_TRY(h, v.d_partial.alloc(chunk_utt.size()));
+    if ((rc = v.tiles.set(h, kVadTileRows)) != MFX_OK || (rc = v.chunks.set(h, kNormChunkRows)) != MFX_OK) return rc;
+    const size_t n = (size_t)B.n_utt, tiles = v.tiles.items();
+    HIP_TRY(h, v.d_partial.alloc(v.chunks.items()));
     HIP_TRY(h, v.d_mask.alloc(tiles));
     HIP_TRY(h, v.d_tile_base.alloc(tiles));
     // what a run that launches nothing (a batch without rows) leaves for the read-back: no voiced row, thr = energy_threshold
@@ -330,7 +298,6 @@ extern "C" int mfx_batch_set_vad(mfx_handle *h, int32_t column, float energy_thr
     HIP_TRY(h, h->upload(v.d_voiced, std::vector<int32_t>(n, 0)));
     HIP_TRY(h, h->upload(v.d_packed, std::vector<int64_t>(n + 1, 0)));
     HIP_TRY(h, v.d_flags.alloc((size_t)B.total_rows)); // (every row has a frame: a run writes them all before a read-back)
-    v.utt_tile0.swap(tile0), v.utt_chunk0.swap(chunk0);
     v.column = column >= 0 ? column : h->cols - 1;
     v.et = energy_threshold, v.ms = energy_mean_scale, v.ctx = frames_context, v.prop = proportion_threshold, v.mode = mode;
     v.last_stream = h->stream;
@@ -343,14 +310,10 @@ extern "C" int mfx_batch_set_vad(mfx_handle *h, int32_t column, float energy_thr
 extern "C" int mfx_batch_clear_vad(mfx_handle *h)
 {
     MFX_DEVICE_ENTRY(h);
-    HIP_TRY(h, hipSetDevice(h->device));
-    const int rc = mfx_synchronize(h); // (a run in flight may read what is released below)
-    if (rc != MFX_OK) return rc;
+    if (const int rc = sync_device(h); rc != MFX_OK) return rc; // (a run in flight may read what is released below)
     BatchState::Vad &v = h->batch.vad;
     v.drop();
-    v.d_utt_tile0.release(), v.d_tile_utt.release(), v.d_utt_chunk0.release(), v.d_chunk_utt.release(), v.d_partial.release();
-    v.d_thr.release(), v.d_voiced.release(), v.d_tile_base.release(), v.d_flags.release(), v.d_mask.release(), v.d_packed.release();
-    v.d_rows.release();
+    v.release();
     return MFX_OK;
 }
 
@@ -360,9 +323,7 @@ extern "C" int mfx_batch_vad_read(mfx_handle *h, uint8_t *flags, int32_t *voiced
     const BatchState::Vad &v = h->batch.vad;
     if (!v.on) return fail(h, MFX_ERR_STATE, "mfx_batch_vad_read: no VAD is in force");
     if (!v.ran) return fail(h, MFX_ERR_STATE, "mfx_batch_vad_read: no batch has run since the VAD was set");
-    HIP_TRY(h, hipSetDevice(h->device));
-    const int rc = mfx_synchronize(h);
-    if (rc != MFX_OK) return rc;
+    if (const int rc = sync_device(h); rc != MFX_OK) return rc;
     const size_t n = (size_t)h->batch.n_utt;
     if (flags && h->batch.total_rows > 0) HIP_TRY(h, hipMemcpy(flags, v.d_flags.p, (size_t)h->batch.total_rows, hipMemcpyDeviceToHost));
     if (voiced && n > 0) HIP_TRY(h, hipMemcpy(voiced, v.d_voiced.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -399,10 +360,8 @@ extern "C" int mfx_batch_set_pitch(mfx_handle *h, int32_t window, int32_t lag_mi
                     "mfx_batch_set_pitch: window 32 .. 1024, lags 2 .. 1024 (at most 512 of them), finite ballast, lag_cost in [0, 1] "
                     "and penalty >= 0, max_jump 0 .. 511");
     const int tile_frames = pitch_tile_frames(s.window, s.lag_max, h->S);
-    std::vector<int32_t> tile0, tile_utt;
-    if (!build_pitch_layout(B.utt_frames.data(), B.n_utt, tile_frames, tile0, tile_utt)) return fail(h, MFX_ERR_ARG, "batch too long");
     PitchParams probe{};
-    probe.channels = h->channels, probe.tile_frames = tile_frames;
+    probe.channels = h->channels, probe.tiles.rows = tile_frames;
     probe.window = s.window, probe.shift = h->S, probe.lag_min = s.lag_min, probe.lag_max = s.lag_max, probe.K = s.K, probe.J = s.J;
     probe.span_pad = pitch_span_pad(h->S);
     probe.groups = pitch_groups(s.lag_min, s.lag_max);
@@ -411,16 +370,13 @@ extern "C" int mfx_batch_set_pitch(mfx_handle *h, int32_t window, int32_t lag_mi
     build_pitch_tables(s, lag_cost, wt, lg);
     std::vector<int64_t> utt((size_t)2 * B.n_utt);
     for (int u = 0; u < B.n_utt; ++u) utt[2 * (size_t)u] = B.utt_off[u], utt[2 * (size_t)u + 1] = B.utt_len[u];
-    HIP_TRY(h, hipSetDevice(h->device));
-    const int rc = mfx_synchronize(h); // (a run in flight may read the lists replaced below)
-    if (rc != MFX_OK) return rc;
+    if (const int rc = sync_device(h); rc != MFX_OK) return rc; // (a run in flight may read the lists replaced below)
     BatchState::Pitch &pt = B.pt;
     pt.drop();
     // (everything mfx_batch_run_device needs is allocated here: that entry never allocates)
     const size_t rows = (size_t)B.total_rows;
     auto all = [&]() -> int {
-        HIP_TRY(h, h->upload(pt.d_utt_tile0, tile0));
-        HIP_TRY(h, h->upload(pt.d_tile_utt, tile_utt));
+        if (const int rt = pt.tiles.set(h, tile_frames); rt != MFX_OK) return rt;
         HIP_TRY(h, h->upload(pt.d_utt, utt));
         HIP_TRY(h, h->upload(pt.d_wt, wt));
         HIP_TRY(h, h->upload(pt.d_lg, lg));
@@ -434,8 +390,7 @@ extern "C" int mfx_batch_set_pitch(mfx_handle *h, int32_t window, int32_t lag_mi
         pt.release();
         return ra;
     }
-    pt.utt_tile0.swap(tile0);
-    pt.window = s.window, pt.lag_min = s.lag_min, pt.lag_max = s.lag_max, pt.K = s.K, pt.J = s.J, pt.tile_frames = tile_frames;
+    pt.window = s.window, pt.lag_min = s.lag_min, pt.lag_max = s.lag_max, pt.K = s.K, pt.J = s.J;
     pt.ballast = ballast, pt.penalty = penalty;
     pt.on = true;
     return MFX_OK;
@@ -444,13 +399,11 @@ extern "C" int mfx_batch_set_pitch(mfx_handle *h, int32_t window, int32_t lag_mi
 extern "C" int mfx_batch_clear_pitch(mfx_handle *h)
 {
     MFX_DEVICE_ENTRY(h);
-    HIP_TRY(h, hipSetDevice(h->device));
     // (the pitch features go with the track they are computed from; pasted, they are part of the rows a transform or a VAD
     // was sized for)
     if (batch_y_width(h) != h->width && (h->batch.xf.on || h->batch.vad.on))
         return fail(h, MFX_ERR_STATE, "mfx_batch_clear_pitch: pasted pitch features are in force under a transform or a VAD (clear those first)");
-    const int rc = mfx_synchronize(h); // (a run in flight may read what is released below)
-    if (rc != MFX_OK) return rc;
+    if (const int rc = sync_device(h); rc != MFX_OK) return rc; // (a run in flight may read what is released below)
     h->batch.pt.drop();
     h->batch.pt.release();
     h->batch.pf.drop();
@@ -464,9 +417,7 @@ extern "C" int mfx_batch_pitch_read(mfx_handle *h, float *pitch, int32_t *index,
     const BatchState::Pitch &pt = h->batch.pt;
     if (!pt.on) return fail(h, MFX_ERR_STATE, "mfx_batch_pitch_read: no pitch track is in force");
     if (!pt.ran) return fail(h, MFX_ERR_STATE, "mfx_batch_pitch_read: no batch has run since the pitch track was set");
-    HIP_TRY(h, hipSetDevice(h->device));
-    const int rc = mfx_synchronize(h);
-    if (rc != MFX_OK) return rc;
+    if (const int rc = sync_device(h); rc != MFX_OK) return rc;
     const size_t rows = (size_t)h->batch.total_rows;
     if (rows == 0) return MFX_OK;
     if (pitch) HIP_TRY(h, hipMemcpy(pitch, pt.d_pitch.p, rows * 2 * sizeof(float), hipMemcpyDeviceToHost));
@@ -505,18 +456,13 @@ extern "C" int mfx_batch_set_pitch_feats(mfx_handle *h, int32_t columns, int32_t
         return fail(h, MFX_ERR_STATE,
                     "mfx_batch_set_pitch_feats: the row width would change under a transform or a VAD (clear them, set the paste, set "
                     "them again)");
-    std::vector<int32_t> tile0, tile_utt;
-    if (!build_pitch_layout(B.utt_frames.data(), B.n_utt, kPitchFeatRows, tile0, tile_utt)) return fail(h, MFX_ERR_ARG, "batch too long");
-    HIP_TRY(h, hipSetDevice(h->device));
-    const int rc = mfx_synchronize(h); // (a run in flight may read the arrays replaced below)
-    if (rc != MFX_OK) return rc;
+    if (const int rc = sync_device(h); rc != MFX_OK) return rc; // (a run in flight may read the arrays replaced below)
     BatchState::PitchFeats &pf = B.pf;
     pf.drop();
     // (everything mfx_batch_run_device needs is allocated here: that entry never allocates)
     const size_t rows = (size_t)B.total_rows;
     auto all = [&]() -> int {
-        HIP_TRY(h, h->upload(pf.d_utt_tile0, tile0));
-        HIP_TRY(h, h->upload(pf.d_tile_utt, tile_utt));
+        if (const int rt = pf.tiles.set(h, kPitchFeatRows); rt != MFX_OK) return rt;
         HIP_TRY(h, pf.d_feats.alloc(rows * s.F));
         if (paste)
             HIP_TRY(h, pf.d_narrow.alloc(rows * h->width));
@@ -528,7 +474,6 @@ extern "C" int mfx_batch_set_pitch_feats(mfx_handle *h, int32_t columns, int32_t
         pf.release();
         return ra;
     }
-    pf.utt_tile0.swap(tile0);
     pf.columns = s.columns, pf.F = s.F, pf.left = s.left, pf.right = s.right, pf.D = s.D, pf.den = s.den;
     pf.pov_scale = pov_scale, pf.pov_offset = pov_offset, pf.pitch_scale = pitch_scale, pf.delta_scale = delta_scale;
     pf.paste = paste != 0;
@@ -541,9 +486,7 @@ extern "C" int mfx_batch_clear_pitch_feats(mfx_handle *h)
     MFX_DEVICE_ENTRY(h);
     if (batch_y_width(h) != h->width && (h->batch.xf.on || h->batch.vad.on))
         return fail(h, MFX_ERR_STATE, "mfx_batch_clear_pitch_feats: the row width would change under a transform or a VAD (clear them first)");
-    HIP_TRY(h, hipSetDevice(h->device));
-    const int rc = mfx_synchronize(h); // (a run in flight may read what is released below)
-    if (rc != MFX_OK) return rc;
+    if (const int rc = sync_device(h); rc != MFX_OK) return rc; // (a run in flight may read what is released below)
     h->batch.pf.drop();
     h->batch.pf.release();
     return MFX_OK;
@@ -555,9 +498,7 @@ extern "C" int mfx_batch_pitch_feats_read(mfx_handle *h, float *feats)
     const BatchState::PitchFeats &pf = h->batch.pf;
     if (!pf.on) return fail(h, MFX_ERR_STATE, "mfx_batch_pitch_feats_read: no pitch features are in force");
     if (!pf.ran) return fail(h, MFX_ERR_STATE, "mfx_batch_pitch_feats_read: no batch has run since the pitch features were set");
-    HIP_TRY(h, hipSetDevice(h->device));
-    const int rc = mfx_synchronize(h);
-    if (rc != MFX_OK) return rc;
+    if (const int rc = sync_device(h); rc != MFX_OK) return rc;
     const size_t rows = (size_t)h->batch.total_rows;
     if (rows == 0 || !feats) return MFX_OK;
     HIP_TRY(h, hipMemcpy(feats, pf.d_feats.p, rows * pf.F * sizeof(float), hipMemcpyDeviceToHost));

@@ -1,5 +1,6 @@
 // mfx_dev.h -- device helpers shared by the gfx950 kernel translation units (mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip):
-// wave-level LDS ordering, LDS reads the optimiser must keep whole, the register FFT butterflies, the fast log.
+// wave-level LDS ordering, LDS reads the optimiser must keep whole, the register FFT butterflies, the fast log; and utt_item, the
+// decode of an utterance tiling's item that mfx_vad.hip, mfx_onorm.hip, mfx_pitch.hip and mfx_pitchfeat.hip share.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -43,6 +44,31 @@ __device__ __forceinline__ int xcd_block_id()
     const int n = gridDim.x, b = blockIdx.x, x = b & 7, q = n >> 3, r = n & 7;
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (b >> 3);
 #endif
+}
+
+// One item of an utterance tiling (UttTiling, mfx_kernels.h): its utterance, where it lies in it, and the utterance's rows.
+struct UttItem {
+    int u;        // the utterance
+    int local;    // the item's index inside it
+    int t0, n;    // first row inside the utterance, rows (1 .. ROWS)
+    int64_t row0; // the utterance's first row (Segment::out_row0)
+    int T;        // the utterance's rows (Segment::n_out)
+};
+// item: absolute, tl.first <= item < tl.first + tl.count.  ROWS: the item size as a compile-time constant (the launcher has
+// checked tl.rows against it), so that t0 is a shift; 0: tl.rows (the pitch track's tile_frames)
+template <int ROWS>
+__device__ __forceinline__ UttItem utt_item(const UttTiling &tl, const Segment *segs, int item)
+{
+    const int rows = ROWS > 0 ? ROWS : tl.rows;
+    UttItem it;
+    it.u = tl.item_utt[item];
+    const Segment sg = segs[it.u];
+    it.row0 = sg.out_row0;
+    it.T = sg.n_out;
+    it.local = item - tl.utt_item0[it.u];
+    it.t0 = it.local * rows;
+    it.n = min(rows, it.T - it.t0);
+    return it;
 }
 
 __device__ __forceinline__ void wave_sync()

@@ -1,5 +1,6 @@
 // mfx_handle.h -- internal to the host side of libmfcchip (not installed): the handle behind include/mfx.h, the buffer
-// types it owns, and the few helpers its translation units share.
+// types it owns (UttTilingBuf among them: the one owner of an utterance tiling, host and device), and the few helpers its
+// translation units share.
 //   mfx_api.cpp    lifetime, tables, kernel choice and front-end dispatch, profiling, test taps (writes the shared part)
 //   mfx_stream.cpp the streaming state machine and its host copies         (owns `st` and `sweep`)
 //   mfx_batch_plan.cpp   the batch planner, the rates planner, the fused-delta plan (owns `batch`'s plan, `batch.rs`, `fuse`)
@@ -107,6 +108,21 @@ struct CepTables {
     bool holds(const float *a, int n) const { return !alphas.empty() && (int)alphas.size() == n && std::equal(a, a + n, alphas.begin()); }
 };
 
+// An utterance tiling of the planned batch (mfx::UttTiling, mfx_kernels.h; DESIGN.md, "Utterance tilings"): the host's item0,
+// the kernels' two arrays, the item size
+struct UttTilingBuf {
+    int32_t rows = 0;
+    std::vector<int32_t> item0;          // [n_utt + 1]
+    DevBuf<int32_t> d_item0, d_item_utt; // [n_utt + 1], [items]
+    // builds the tiling of the plan's utterances at `rows_per_item` and uploads it (defined behind mfx_handle): MFX_ERR_ARG,
+    // "batch too long", leaves the tiling as it was
+    int set(mfx_handle *h, int32_t rows_per_item);
+    // the items of utterances [u0, u1), as a kernel takes them
+    mfx::UttTiling range(int u0, int u1) const { return {d_item0.p, d_item_utt.p, item0[u0], item0[u1] - item0[u0], rows}; }
+    size_t items() const { return item0.empty() ? 0 : (size_t)item0.back(); }
+    void release() { d_item0.release(), d_item_utt.release(); }
+};
+
 // streaming state (segmentercpu.h:7-17, parambase.h:18): mfx_stream.cpp
 struct StreamState {
     DevBuf<int16_t> d_carry[2];
@@ -166,7 +182,9 @@ struct BatchState {
     bool aligned = true;                 // frames on aligned sample pairs (fill_front / choose_front read it)
 
     // Eight attachments, each tied to the plan: a new plan drops them.  drop() switches one off and releases what is not kept
-    // for the next one (the grown-never-shrunk scratch stays).
+    // for the next one (the grown-never-shrunk scratch stays); release() names every buffer once, for the clear entry (and a
+    // setter that ran out of memory); sized() says whether the scratch a run writes to holds the plan's rows (batch_run_range
+    // refuses otherwise).
 
     // sample-rate conversion (mfx_batch_plan_rates): while on, the run converts the caller's array into d_pcm with one
     // launch of k_resample and then does what it always does on d_pcm; utt_off / utt_len above describe the scratch, in_off /
@@ -207,6 +225,8 @@ struct BatchState {
         DevBuf<int32_t> d_idx;           // [n_utt] transform of every utterance (empty: all 0)
         DevBuf<float> d_y;               // [total_rows][Wy] (grown, never shrunk: only the (NULL, 0) setter releases it)
         void drop() { on = false; }
+        void release() { d_ops.release(), d_bias.release(), d_idx.release(), d_y.release(); }
+        bool sized(size_t total_rows, int Wy) const { return !on || d_y.n >= total_rows * Wy; }
     } xf;
     // per-speaker normalisation (mfx_batch_set_speakers): while on, the run's normaliser is k_spk_sums -> k_spk_finish ->
     // k_spk_apply over the whole batch instead of run_norm's per-utterance kernels
@@ -215,7 +235,7 @@ struct BatchState {
         bool ran = false;                // a run has filled the accumulators since the list was set
         int32_t n_spk = 0, mode = 0, n_tiles = 0, max_rows = 0;
         DevBuf<int32_t> d_off, d_list;   // [n_spk + 1], [utterances with frames] (build_speaker_lists)
-        DevBuf<int32_t> d_chunk0;        // [n_utt + 1] first 4096-row chunk of every utterance
+        DevBuf<int32_t> d_chunk0;        // [n_utt + 1] first chunk of every utterance: item0 of the tiling at kNormChunkRows
         DevBuf<double> d_partial;        // [chunks][4][Wn]
         DevBuf<int64_t> d_prior_n, d_count; // [n_spk] (the prior's: empty without one)
         DevBuf<double> d_prior, d_acc;   // [n_spk][4][Wn]
@@ -230,8 +250,7 @@ struct BatchState {
         bool ran = false;                // a run has filled the arrays since the setter
         int32_t column = 0, ctx = 0, mode = 0; // (column resolved: never -1)
         float et = 0.f, ms = 0.f, prop = 0.f;
-        std::vector<int32_t> utt_tile0, utt_chunk0; // [n_utt + 1] (build_vad_layout)
-        DevBuf<int32_t> d_utt_tile0, d_tile_utt, d_utt_chunk0, d_chunk_utt;
+        UttTilingBuf tiles, chunks;      // at kVadTileRows, kNormChunkRows
         DevBuf<double> d_partial;        // [chunks]
         DevBuf<float> d_thr;             // [n_utt]
         DevBuf<int32_t> d_voiced, d_tile_base; // [n_utt], [tiles]
@@ -241,6 +260,12 @@ struct BatchState {
         DevBuf<float> d_rows;            // [total_rows][Wo] (grown, never shrunk: only mfx_batch_clear_vad releases it)
         hipStream_t last_stream = nullptr; // the stream the last run's tail ran on
         void drop() { on = false, ran = false; }
+        void release()
+        {
+            tiles.release(), chunks.release(), d_partial.release(), d_thr.release(), d_voiced.release(), d_tile_base.release();
+            d_flags.release(), d_mask.release(), d_packed.release(), d_rows.release();
+        }
+        bool sized(size_t total_rows, int Wo) const { return !on || mode == MFX_VAD_FLAGS || d_rows.n >= total_rows * Wo; }
     } vad;
     // online (causal, sliding-window) CMN / CVN (mfx_batch_set_online_norm): while on, everything ahead of the normaliser's
     // place writes to d_raw instead of the run's d_out, and k_onorm_totals -> k_onorm_offsets -> k_onorm_apply turn the Wn
@@ -249,22 +274,22 @@ struct BatchState {
         bool on = false;
         int32_t window = 0, prior_frames = 0;
         int64_t prior_count = 0;
-        std::vector<int32_t> utt_chunk0; // [n_utt + 1] first 32-row chunk of every utterance
-        DevBuf<int32_t> d_utt_chunk0, d_chunk_utt;
+        UttTilingBuf chunks;             // at kOnormChunk
         DevBuf<double> d_prior;          // [2][Wn] (empty without a prior)
         DevBuf<double> d_tot;            // [chunks][2][Wn]
         DevBuf<float> d_raw;             // [total_rows][width] (grown, never shrunk: only mfx_batch_clear_online_norm releases it)
         void drop() { on = false; }
+        void release() { chunks.release(), d_prior.release(), d_tot.release(), d_raw.release(); }
+        bool sized(size_t total_rows, int width) const { return !on || d_raw.n >= total_rows * width; }
     } on;
     // pitch track (mfx_batch_set_pitch): while on, k_pitch_nccf and k_pitch_track follow the front end on the handle's stream
     // and fill the handle-owned arrays below, indexed by the plan's rows; d_out is untouched
     struct Pitch {
         bool on = false;
         bool ran = false;                // a run has filled the arrays since the setter
-        int32_t window = 0, lag_min = 0, lag_max = 0, K = 0, J = 0, tile_frames = 0;
+        int32_t window = 0, lag_min = 0, lag_max = 0, K = 0, J = 0;
         float ballast = 0.f, penalty = 0.f;
-        std::vector<int32_t> utt_tile0;  // [n_utt + 1] (build_pitch_layout)
-        DevBuf<int32_t> d_utt_tile0, d_tile_utt;
+        UttTilingBuf tiles;              // at pitch_tile_frames
         DevBuf<int64_t> d_utt;           // [n_utt][2] first sample and samples of every utterance, as the front end reads them
         DevBuf<float> d_wt, d_lg;        // [K]
         DevBuf<float> d_nccf;            // [total_rows][K]
@@ -274,9 +299,10 @@ struct BatchState {
         void drop() { on = false, ran = false; }
         void release()
         {
-            d_utt_tile0.release(), d_tile_utt.release(), d_utt.release(), d_wt.release(), d_lg.release(), d_nccf.release(), d_bp.release();
+            tiles.release(), d_utt.release(), d_wt.release(), d_lg.release(), d_nccf.release(), d_bp.release();
             d_pitch.release(), d_index.release();
         }
+        bool sized(size_t total_rows) const { return !on || d_nccf.n >= total_rows * K; }
     } pt;
     // pitch features (mfx_batch_set_pitch_feats; needs the pitch track): while on, k_pitch_feats follows k_pitch_track on the
     // handle's stream and fills d_feats, indexed by the plan's rows.  With `paste` the rows y of a run are Wy = width + F wide:
@@ -289,12 +315,15 @@ struct BatchState {
         int32_t columns = 0, F = 0, left = 0, right = 0, D = 0;
         float pov_scale = 0.f, pov_offset = 0.f, pitch_scale = 0.f, delta_scale = 0.f;
         double den = 0.0;
-        std::vector<int32_t> utt_tile0;  // [n_utt + 1] (build_pitch_layout at kPitchFeatRows)
-        DevBuf<int32_t> d_utt_tile0, d_tile_utt;
+        UttTilingBuf tiles;              // at kPitchFeatRows
         DevBuf<float> d_feats;           // [total_rows][F]
         DevBuf<float> d_narrow;          // [total_rows][width] (paste only)
         void drop() { on = false, ran = false, paste = false; }
-        void release() { d_utt_tile0.release(), d_tile_utt.release(), d_feats.release(), d_narrow.release(); }
+        void release() { tiles.release(), d_feats.release(), d_narrow.release(); }
+        bool sized(size_t total_rows, int width, bool track_on) const
+        {
+            return !on || (track_on && d_feats.n >= total_rows * F && (!paste || d_narrow.n >= total_rows * width));
+        }
     } pf;
     // what a new utterance list invalidates (the converter is mfx_batch_plan's to drop: mfx_batch_plan_rates plans through
     // plan_batch too)
@@ -521,6 +550,25 @@ inline int fail_hip(mfx_handle *h, hipError_t e, const char *what)
         hipError_t _e = (expr);                                  \
         if (_e != hipSuccess) return fail_hip((h), _e, #expr);   \
     } while (0)
+
+// the handle's device current and its streams idle: ahead of everything that replaces, releases or reads back what a run in
+// flight may use
+inline int sync_device(mfx_handle *h)
+{
+    HIP_TRY(h, hipSetDevice(h->device));
+    return mfx_synchronize(h);
+}
+
+inline int UttTilingBuf::set(mfx_handle *h, int32_t rows_per_item)
+{
+    std::vector<int32_t> i0, iu;
+    if (!mfx::build_utt_tiling(h->batch.utt_frames.data(), h->batch.n_utt, rows_per_item, i0, &iu)) return fail(h, MFX_ERR_ARG, "batch too long");
+    HIP_TRY(h, h->upload(d_item0, i0));
+    HIP_TRY(h, h->upload(d_item_utt, iu));
+    item0.swap(i0);
+    rows = rows_per_item;
+    return MFX_OK;
+}
 
 // top of every entry that needs the device: a handle, and not a planning one
 #define MFX_DEVICE_ENTRY(h)                                                                                                  \

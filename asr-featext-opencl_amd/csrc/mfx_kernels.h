@@ -22,10 +22,13 @@
 //                            the clamp by the utterance's maximum and the map (no reference analogue: a neural recogniser's input)
 //   delta                    delta.cl kernelDelta x2 + the staging copies of mfccopencl.cpp:360-387
 //   norm_stats / norm_apply  norm.cl kernelSum + kernelFinalizeSum / kernelNormalize
+// What is attached to a planned batch (vad_*, onorm_*, pitch_*, pitch_feats) walks its rows by one work list, UttTiling below.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "mfx_tables.h" // (the item sizes of the utterance tilings: kVadTileRows, kNormChunkRows, kOnormChunk, kPitchFeatRows)
 
 namespace mfx {
 
@@ -47,6 +50,16 @@ struct Segment {
     int32_t lo, hi;
     int32_t static_off; // static part of output row r is src row r + static_off
     int32_t pad;        // normalisation: rows the statistics cover (0 = all n_out rows)
+};
+
+// An utterance tiling ("Utterance tilings"; build_utt_tiling, mfx_tables.h): items of `rows` consecutive rows of one
+// utterance, numbered through the batch in utterance order.  Every per-item array of a kernel is indexed absolutely, so that a
+// run over an utterance range fills its part and leaves the rest.  utt_item (mfx_dev.h) decodes an item.
+struct UttTiling {
+    const int32_t *utt_item0; // [n_utt + 1] first item of every utterance (a frameless utterance owns none)
+    const int32_t *item_utt;  // [items] the utterance of every item
+    int32_t first, count;     // the items of this run's utterance range
+    int32_t rows;             // rows per item: the constant the kernel was compiled for, or the launcher refuses
 };
 
 // One tile of the delta stage fused into the 512-point kernel: <= 64 consecutive output rows of one
@@ -357,7 +370,7 @@ struct SpkParams {
     int32_t n_utt;
     int32_t u0;            // set by the launcher: first utterance of the launch
     int32_t max_rows;      // largest row count of any utterance (sizes the grid)
-    const int32_t *utt_chunk0; // [n_utt + 1] first 4096-row chunk of every utterance
+    const int32_t *utt_chunk0; // [n_utt + 1] first chunk of every utterance: UttTiling::utt_item0 at kNormChunkRows
     double *partial;       // [chunks][4][Wn]: S, S2, min, max of every chunk
     const int32_t *spk_off;  // [n_spk + 1]
     const int32_t *spk_list; // utterances of every speaker, ascending, frameless ones left out
@@ -372,9 +385,7 @@ struct SpkParams {
 };
 
 // Energy VAD + voiced-frame selection (mfx_batch_set_vad; mfx_vad.hip; DESIGN.md, "Voice activity and frame selection").
-// Tiles are runs of 64 consecutive rows of one utterance, chunks runs of kNormChunkRows = 4096, both numbered through the
-// batch in utterance order (build_vad_layout); every per-tile, per-chunk and per-utterance array is indexed absolutely, so
-// that a run over an utterance range fills its part and leaves the rest.
+// Two utterance tilings: tiles of kVadTileRows rows, chunks of kNormChunkRows.
 struct VadParams {
     const float *y;        // the rows the decision reads, [rows][y_pitch]
     int32_t y_pitch;
@@ -382,10 +393,7 @@ struct VadParams {
     const Segment *segs;   // [n_utt]: uses out_row0 / n_out
     int32_t n_utt;
     int32_t u0, u1;        // the utterance range of this run
-    const int32_t *utt_tile0, *utt_chunk0; // [n_utt + 1]
-    const int32_t *tile_utt, *chunk_utt;   // utterance of every tile / chunk
-    int32_t tile_first, n_tiles;           // = utt_tile0[u0], utt_tile0[u1] - utt_tile0[u0]
-    int32_t chunk_first, n_chunks;
+    UttTiling tiles, chunks;
     float energy_threshold, energy_mean_scale, proportion_threshold;
     int32_t frames_context; // 0 .. 64
     int32_t mode;          // MFX_VAD_*: 0 flags only, 1 select inside every utterance's rows, 2 pack the batch
@@ -401,17 +409,14 @@ struct VadParams {
     int32_t width;
 };
 
-// Pitch track (mfx_batch_set_pitch; mfx_pitch.hip; DESIGN.md, "Pitch track").  Tiles are runs of tile_frames consecutive
-// frames of one utterance, numbered through the batch in utterance order (build_pitch_layout); every per-row array is indexed
-// by the plan's rows, so that a run over an utterance range fills its part and leaves the rest.
+// Pitch track (mfx_batch_set_pitch; mfx_pitch.hip; DESIGN.md, "Pitch track").  One utterance tiling at pitch_tile_frames
+// frames, the one run-time item size; every per-row array is indexed by the plan's rows.
 struct PitchParams {
     const int16_t *pcm;    // the array the front end reads (the converted scratch under a rates plan)
     int32_t channels;      // 1, or 2: one 32-bit word per sample, p = (L + R) >> 1
     const int64_t *utt;    // [n_utt][2]: first sample (per channel) and samples of every utterance
     const Segment *segs;   // [n_utt]: uses out_row0 / n_out
-    const int32_t *utt_tile0, *tile_utt; // [n_utt + 1], [tiles]
-    int32_t tile_first, n_tiles;         // = utt_tile0[u0], utt_tile0[u1] - utt_tile0[u0]
-    int32_t tile_frames;   // frames per tile (pitch_tile_frames)
+    UttTiling tiles;       // (rows: pitch_tile_frames)
     int32_t u0, u1;        // the utterance range of this run
     int32_t window, shift, lag_min, lag_max, K, J;
     int32_t span_pad;      // pitch_span_pad(shift)
@@ -430,15 +435,13 @@ size_t pitch_nccf_lds_bytes(const PitchParams &p);
 // k_pitch_nccf over the tiles, then k_pitch_track over the utterances of the range
 hipError_t launch_pitch(const PitchParams &p, hipStream_t stream);
 
-// Pitch features (mfx_batch_set_pitch_feats; mfx_pitchfeat.hip; DESIGN.md, "Pitch features").  Tiles are runs of
-// kPitchFeatRows consecutive rows of one utterance (build_pitch_layout at that size); `pitch` and `feats` are indexed by the
-// plan's rows.
+// Pitch features (mfx_batch_set_pitch_feats; mfx_pitchfeat.hip; DESIGN.md, "Pitch features").  One utterance tiling at
+// kPitchFeatRows; `pitch` and `feats` are indexed by the plan's rows.
 constexpr int kPfPov = 1, kPfNorm = 2, kPfDelta = 4, kPfRaw = 8; // MFX_PF_* of include/mfx.h
 struct PitchFeatParams {
     const float *pitch;    // [total_rows][2] lag, rho as k_pitch_track wrote them
     const Segment *segs;   // [n_utt]: uses out_row0 / n_out
-    const int32_t *utt_tile0, *tile_utt; // [n_utt + 1], [tiles]
-    int32_t tile_first, n_tiles;         // = utt_tile0[u0], utt_tile0[u1] - utt_tile0[u0]
+    UttTiling tiles;
     int32_t columns, F;    // MFX_PF_* bits (resolved: never 0) and their number
     int32_t left, right, D;
     float sample_rate, pov_scale, pov_offset, pitch_scale, delta_scale;
@@ -457,8 +460,7 @@ struct PitchPasteParams {
 hipError_t launch_pitch_paste(const PitchPasteParams &q, hipStream_t stream);
 
 // Online CMN / CVN (mfx_batch_set_online_norm, mfx_sessions_set_online_norm; mfx_onorm.hip; DESIGN.md, "Online
-// normalisation").  Chunks are runs of 32 rows of one utterance, numbered through the batch in utterance order; every
-// per-chunk array is indexed absolutely, so that a run over an utterance range fills its part and leaves the rest.
+// normalisation").  One utterance tiling at kOnormChunk rows.
 struct OnormParams {
     const float *src;      // the raw rows, [rows][src_pitch], columns [0, Wn): never `out`
     int32_t src_pitch;
@@ -471,11 +473,9 @@ struct OnormParams {
     int64_t prior_count;   // p
     const double *prior_acc; // [2][Wn] or null (p == 0)
     const Segment *segs;   // [n_utt]: uses out_row0 / n_out
-    const int32_t *utt_chunk0; // [n_utt + 1] first chunk of every utterance
-    const int32_t *chunk_utt;  // utterance of every chunk
+    UttTiling chunks;
     double *tot;           // [chunks][2][Wn]: the chunks' totals of v and q, turned into the offsets O in place
     int32_t u0, n_utt;     // the utterance range of this run: [u0, u0 + n_utt)
-    int32_t chunk_first, n_chunks; // = utt_chunk0[u0], utt_chunk0[u0 + n_utt] - utt_chunk0[u0]
 };
 
 // k_onorm_sess: the rows one push brings one session, rows [t0, t0 + n_rows) of its stream, normalised in place
@@ -542,7 +542,7 @@ bool vad_shape_ok(const VadParams &p);
 hipError_t launch_onorm(const OnormParams &p, hipStream_t stream);
 hipError_t launch_onorm_sess(const OnormSessParams &p, hipStream_t stream);
 // per-speaker normalisation: chunk totals; accumulators + statistics; apply.  spk_tile_rows: rows of a tile of k_spk_apply at
-// Wn columns; spk_chunks: 4096-row chunks of an utterance of `rows` rows
+// Wn columns; spk_chunks: chunks of kNormChunkRows rows of an utterance of `rows` rows
 hipError_t launch_spk_sums(const SpkParams &p, hipStream_t stream);
 hipError_t launch_spk_finish(const SpkParams &p, hipStream_t stream);
 hipError_t launch_spk_apply(const SpkParams &p, hipStream_t stream);

@@ -6,9 +6,9 @@
 
 #include <cstdint>
 
-namespace mfx {
+#include "mfx_kernels.h"
 
-constexpr int kNormChunkRows = 4096; // a segment longer than this is summed in chunks, combined in ascending order
+namespace mfx {
 
 // mean and multiplier from the totals of n rows (normalizercpu.cpp:40-58); N: int, or double where n may pass 2^31
 template <class N>

@@ -1,15 +1,17 @@
 // mfx_onorm.hip -- the online (causal, sliding-window) CMN / CVN of the batch entries (mfx_batch_set_online_norm) and of the
 // session entries (mfx_sessions_set_online_norm), and their launchers:
-//   k_onorm_totals   per (32-row chunk, column): the chunk's totals of v and of q = (double)(float)(v * v)
+//   k_onorm_totals   per (chunk of kOnormChunk = 32 rows, column): the chunk's totals of v and of q = (double)(float)(v * v)
 //   k_onorm_offsets  per (utterance, column): the totals turned into the exclusive ascending chain O, in place
 //   k_onorm_apply    per chunk: lead chain, trail chain (chunk c - N / 32), statistics, write
 //   k_onorm_sess     per (session, column): the same chains carried from push to push, with a ring of the last N raw rows
 // Every sum has one owner and a fixed order (include/mfx.h states it); nothing is atomic.  mfx_onorm_dev.h holds the
-// arithmetic all four share.  See DESIGN.md section 5, "Online normalisation".
+// arithmetic all four share.  See DESIGN.md section 5, "Online normalisation"; the batch kernels' chunks are an utterance tiling
+// (UttTiling, mfx_kernels.h; utt_item, mfx_dev.h).
 #include "mfx_kernels.h"
 
 #include <hip/hip_runtime.h>
 
+#include "mfx_dev.h"
 #include "mfx_launch.h"
 #include "mfx_onorm_dev.h"
 
@@ -23,14 +25,13 @@ namespace {
 // so that a 39-column row still fills the block's lanes.
 __device__ __forceinline__ int onorm_tiles(int Wn) { return Wn >= 256 ? 1 : 256 / Wn; }
 
-// first row (absolute) and row count of chunk c
+// first row (absolute), row count and local index of chunk c
 __device__ __forceinline__ void onorm_chunk(const OnormParams &p, int c, int64_t &row0, int &rows, int &lc)
 {
-    const int u = p.chunk_utt[c];
-    const Segment sg = p.segs[u];
-    lc = c - p.utt_chunk0[u];
-    row0 = sg.out_row0 + (int64_t)lc * kOnormChunk;
-    rows = min(kOnormChunk, sg.n_out - lc * kOnormChunk);
+    const UttItem ch = utt_item<kOnormChunk>(p.chunks, p.segs, c);
+    lc = ch.local;
+    row0 = ch.row0 + ch.t0;
+    rows = ch.n;
 }
 
 // grid = ceil(n_chunks / G), 256 threads.  Lanes of consecutive j read consecutive floats of a row.
@@ -39,8 +40,8 @@ __global__ void __launch_bounds__(256) k_onorm_totals(OnormParams p)
     const int Wn = p.Wn, G = onorm_tiles(Wn);
     const int g = threadIdx.x / Wn, j = threadIdx.x - g * Wn;
     const int ci = blockIdx.x * G + g;
-    if (g >= G || ci >= p.n_chunks) return;
-    const int c = p.chunk_first + ci;
+    if (g >= G || ci >= p.chunks.count) return;
+    const int c = p.chunks.first + ci;
     int64_t row0;
     int rows, lc;
     onorm_chunk(p, c, row0, rows, lc);
@@ -70,7 +71,7 @@ __global__ void __launch_bounds__(256) k_onorm_offsets(OnormParams p)
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (int64_t)p.n_utt * per) return;
     const int u = p.u0 + (int)(i / per), k = (int)(i % per);
-    const int c0 = p.utt_chunk0[u], c1 = p.utt_chunk0[u + 1];
+    const int c0 = p.chunks.utt_item0[u], c1 = p.chunks.utt_item0[u + 1];
     double *t = p.tot + (int64_t)c0 * per + k;
     double O = 0.0;
     int c = c0;
@@ -111,7 +112,7 @@ __global__ void __launch_bounds__(256) k_onorm_apply(OnormParams p)
         const int ci = blockIdx.x * G + tid;
         int64_t row0 = 0;
         int rows = 0, lc = 0;
-        if (ci < p.n_chunks) onorm_chunk(p, p.chunk_first + ci, row0, rows, lc);
+        if (ci < p.chunks.count) onorm_chunk(p, p.chunks.first + ci, row0, rows, lc);
         s_row0[tid] = row0, s_rows[tid] = rows, s_lc[tid] = lc;
     }
     __syncthreads();
@@ -152,7 +153,7 @@ __global__ void __launch_bounds__(256) k_onorm_apply(OnormParams p)
     __syncthreads();
     if (mine) {
         const int lc = s_lc[g];
-        const int c = p.chunk_first + blockIdx.x * G + g;
+        const int c = p.chunks.first + blockIdx.x * G + g;
         OnormStat st;
         st.cvn = p.cvn, st.prior_frames = p.prior_frames, st.prior_count = p.prior_count;
         const double ps = p.prior_count > 0 ? p.prior_acc[j] : 0.0, pq = p.prior_count > 0 ? p.prior_acc[Wn + j] : 0.0;
@@ -259,12 +260,12 @@ bool onorm_shape_ok(int Wn, int window, int prior_frames, int64_t prior_count, c
 
 hipError_t launch_onorm(const OnormParams &p, hipStream_t stream)
 {
-    if (p.n_utt <= 0 || p.n_chunks <= 0) return hipSuccess;
+    if (p.n_utt <= 0 || p.chunks.count <= 0) return hipSuccess;
     if (!onorm_shape_ok(p.Wn, p.window, p.prior_frames, p.prior_count, p.prior_acc) || p.src == p.out || p.src_pitch < p.Wn ||
-        p.out_pitch < p.Wn)
+        p.out_pitch < p.Wn || p.chunks.rows != kOnormChunk) // (the chunk size is the kernels' constant)
         return hipErrorInvalidValue;
     const int G = p.Wn >= 256 ? 1 : 256 / p.Wn;
-    const int blocks = (p.n_chunks + G - 1) / G;
+    const int blocks = (p.chunks.count + G - 1) / G;
     hipLaunchKernelGGL(k_onorm_totals, dim3(blocks), dim3(256), 0, stream, p);
     const int64_t chains = (int64_t)p.n_utt * 2 * p.Wn;
     hipLaunchKernelGGL(k_onorm_offsets, dim3((unsigned)((chains + 255) / 256)), dim3(256), 0, stream, p);

@@ -8,9 +8,9 @@
 
 #include <cstdint>
 
-namespace mfx {
+#include "mfx_kernels.h"
 
-constexpr int kOnormChunk = 32; // rows of a chunk of the prefix sums (the window is a multiple of it)
+namespace mfx {
 
 // what the statistics of a row need beside its window sums
 struct OnormStat {

@@ -2,7 +2,8 @@
 // end reads, then a Viterbi path through its lag states, and their launcher.  See DESIGN.md section 5, "Pitch track"; the
 // definition both kernels follow operation for operation is in include/mfx.h.
 //
-//   k_pitch_nccf   one block of 4 waves per tile of at most 64 consecutive frames of one utterance.  The tile's PCM span goes
+//   k_pitch_nccf   one block of 4 waves per tile of at most 64 consecutive frames of one utterance (an utterance tiling,
+//                  UttTiling of mfx_kernels.h, at pitch_tile_frames frames: the one item size that is no constant).  The tile's PCM span goes
 //                  into LDS once as int16, zero behind the utterance's own end (explicit bounds: a neighbour is never read),
 //                  with pitch_span_pad empty slots behind every `shift` samples, so that the frames of the tile start on
 //                  different banks.  Then, one frame per lane (16 lanes of every wave): the integer sum, m, and the double
@@ -64,11 +65,8 @@ __global__ void __launch_bounds__(256) k_pitch_nccf(PitchParams p)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int tile = p.tile_first + blockIdx.x;
-    const int u = p.tile_utt[tile];
-    const Segment sg = p.segs[u];
-    const int t0 = (tile - p.utt_tile0[u]) * p.tile_frames;
-    const int nf = min(p.tile_frames, sg.n_out - t0);
+    const UttItem tl = utt_item<0>(p.tiles, p.segs, p.tiles.first + blockIdx.x);
+    const int u = tl.u, t0 = tl.t0, nf = tl.n;
     const int W = p.window, S = p.shift, pad = p.span_pad, K = p.K, Ls = W + p.lag_max;
     const int zs = pitch_z_floats(W, p.lag_max);
     const int G = p.groups, gl_n = 64 / G; // frames a wave takes at a time, lanes of each
@@ -98,7 +96,7 @@ __global__ void __launch_bounds__(256) k_pitch_nccf(PitchParams p)
     }
     __syncthreads();
 
-    float *rows = p.nccf + (sg.out_row0 + t0) * (int64_t)K;
+    float *rows = p.nccf + (tl.row0 + t0) * (int64_t)K;
     // ---- one frame per lane: sum, mean, the two prefix chains
     if (lane < 16 && wave * 16 + lane < nf) {
         const int f = wave * 16 + lane;
@@ -336,15 +334,15 @@ bool pitch_params_ok(const PitchParams &p)
 {
     if (p.window < 32 || p.window > 1024 || p.lag_min < 2 || p.lag_max > 1024 || p.K != p.lag_max - p.lag_min + 1 || p.K < 1 || p.K > 512)
         return false;
-    if (p.J < 1 || p.J > 511 || p.shift < 1 || p.tile_frames < 1 || p.tile_frames > 64 || (p.channels != 1 && p.channels != 2)) return false;
+    if (p.J < 1 || p.J > 511 || p.shift < 1 || p.tiles.rows < 1 || p.tiles.rows > 64 || (p.channels != 1 && p.channels != 2)) return false;
     if (p.span_pad < 0 || p.span_pad > 63 || (p.groups != 1 && p.groups != 2)) return false;
-    if ((int64_t)(p.tile_frames - 1) * p.shift > (1 << 24)) return false; // (the span arithmetic stays far inside an int)
+    if ((int64_t)(p.tiles.rows - 1) * p.shift > (1 << 24)) return false; // (the span arithmetic stays far inside an int)
     return pitch_nccf_lds_bytes(p) <= kLdsMax;
 }
 
 size_t pitch_nccf_lds_bytes(const PitchParams &p)
 {
-    const size_t slots = (size_t)pitch_slots(p.window, p.lag_max, p.shift, p.span_pad, p.tile_frames);
+    const size_t slots = (size_t)pitch_slots(p.window, p.lag_max, p.shift, p.span_pad, p.tiles.rows);
     return ((size_t)4 * p.groups * pitch_z_floats(p.window, p.lag_max) + 128) * sizeof(float) + ((slots + 7) & ~(size_t)7) * sizeof(int16_t);
 }
 
@@ -359,11 +357,11 @@ int pitch_groups(int lag_min, int lag_max)
 
 hipError_t launch_pitch(const PitchParams &p, hipStream_t stream)
 {
-    if (p.u1 <= p.u0 || p.n_tiles <= 0) return hipSuccess; // (no utterance of the range has a frame)
+    if (p.u1 <= p.u0 || p.tiles.count <= 0) return hipSuccess; // (no utterance of the range has a frame)
     if (!pitch_params_ok(p)) return hipErrorInvalidValue;
     const size_t lds = pitch_nccf_lds_bytes(p);
     if (hipError_t e = allow_dynamic_lds((const void *)k_pitch_nccf, lds); e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_pitch_nccf, dim3(p.n_tiles), dim3(256), lds, stream, p);
+    hipLaunchKernelGGL(k_pitch_nccf, dim3(p.tiles.count), dim3(256), lds, stream, p);
     const int threads = 64 * ((p.K + 63) / 64);
     hipLaunchKernelGGL(k_pitch_track, dim3(p.u1 - p.u0), dim3(threads), pitch_track_lds_bytes(threads), stream, p); // (at most 54 KB)
     return hipGetLastError();

@@ -2,8 +2,8 @@
 // paste into the rows of a run, and the two launchers.  See DESIGN.md section 5, "Pitch features"; the definition
 // k_pitch_feats follows operation for operation is in include/mfx.h.
 //
-//   k_pitch_feats  one block of 256 threads per tile of at most 256 consecutive rows of one utterance (build_pitch_layout at
-//                  kPitchFeatRows).  The block evaluates w (the probability of voicing that weighs the sliding mean) and
+//   k_pitch_feats  one block of 256 threads per tile of at most 256 consecutive rows of one utterance (an utterance tiling,
+//                  UttTiling of mfx_kernels.h, at kPitchFeatRows).  The block evaluates w (the probability of voicing that weighs the sliding mean) and
 //                  p = ln(rate / lag) once for its rows and a halo of max(left, D) rows before and max(right, D) rows behind
 //                  them, cut at the utterance, into LDS as doubles.  Then one row per thread: the window's two sums, ascending,
 //                  from LDS -- consecutive lanes read consecutive 8-byte words, every row sums its own window from its first
@@ -27,27 +27,22 @@ namespace mfx {
 
 namespace {
 
-constexpr int kFeatRows = 256;               // rows per tile = threads per block (kPitchFeatRows of mfx_tables.h)
-constexpr int kFeatSpan = kFeatRows + 2048;  // the tile's rows and the largest halo on both sides
+constexpr int kFeatSpan = kPitchFeatRows + 2048; // the tile's rows (= threads per block) and the largest halo on both sides
 
 // grid = tiles of the utterance range
-__global__ void __launch_bounds__(kFeatRows) k_pitch_feats(PitchFeatParams q)
+__global__ void __launch_bounds__(kPitchFeatRows) k_pitch_feats(PitchFeatParams q)
 {
     __shared__ double s_w[kFeatSpan], s_p[kFeatSpan];
     const int tid = threadIdx.x;
-    const int tile = q.tile_first + blockIdx.x;
-    const int u = q.tile_utt[tile];
-    const Segment sg = q.segs[u];
-    const int T = sg.n_out;
-    const int t0 = (tile - q.utt_tile0[u]) * kFeatRows;
-    const int nr = min(kFeatRows, T - t0);
+    const UttItem tl = utt_item<kPitchFeatRows>(q.tiles, q.segs, q.tiles.first + blockIdx.x);
+    const int T = tl.T, t0 = tl.t0, nr = tl.n;
     const int D = q.D;
     const int lo0 = max(0, t0 - max(q.left, D)), hi0 = min(T - 1, t0 + nr - 1 + max(q.right, D));
-    const float *track = q.pitch + 2 * sg.out_row0;
+    const float *track = q.pitch + 2 * tl.row0;
     const double rate = (double)q.sample_rate;
 
     // ---- w and p of the tile's rows and their halo, once
-    for (int i = tid; i <= hi0 - lo0; i += kFeatRows) {
+    for (int i = tid; i <= hi0 - lo0; i += kPitchFeatRows) {
         const float lag = track[2 * (int64_t)(lo0 + i)], rho = track[2 * (int64_t)(lo0 + i) + 1];
         const double n = fmin(1.0, fmax(-1.0, (double)rho));
         const double a = fabs(n);
@@ -69,7 +64,7 @@ __global__ void __launch_bounds__(kFeatRows) k_pitch_feats(PitchFeatParams q)
 
     const int t = t0 + tid;
     const double pt = s_p[t - lo0];
-    float *out = q.feats + (sg.out_row0 + t) * (int64_t)q.F;
+    float *out = q.feats + (tl.row0 + t) * (int64_t)q.F;
     if (q.columns & kPfPov) {
         const double n = fmin(1.0, fmax(-1.0, (double)track[2 * (int64_t)t + 1]));
         const double b = 1.0001 - n;
@@ -125,9 +120,9 @@ bool pitch_feat_params_ok(const PitchFeatParams &q)
 
 hipError_t launch_pitch_feats(const PitchFeatParams &q, hipStream_t stream)
 {
-    if (q.n_tiles <= 0) return hipSuccess; // (no utterance of the range has a frame)
-    if (!pitch_feat_params_ok(q) || !q.pitch || !q.feats) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_pitch_feats, dim3(q.n_tiles), dim3(kFeatRows), 0, stream, q);
+    if (q.tiles.count <= 0) return hipSuccess; // (no utterance of the range has a frame)
+    if (!pitch_feat_params_ok(q) || !q.pitch || !q.feats || q.tiles.rows != kPitchFeatRows) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_pitch_feats, dim3(q.tiles.count), dim3(kPitchFeatRows), 0, stream, q);
     return hipGetLastError();
 }
 

@@ -247,28 +247,25 @@ bool build_speaker_lists(const int32_t *utt_spk, const int64_t *frames, int n_ut
     return true;
 }
 
-bool build_vad_layout(const int64_t *frames, int n_utt, std::vector<int32_t> &utt_tile0, std::vector<int32_t> &tile_utt,
-                      std::vector<int32_t> &utt_chunk0, std::vector<int32_t> &chunk_utt)
+bool build_utt_tiling(const int64_t *frames, int n_utt, int rows, std::vector<int32_t> &item0, std::vector<int32_t> *item_utt)
 {
-    if (n_utt < 0) return false;
-    int64_t tiles = 0, chunks = 0;
+    if (n_utt < 0 || rows < 1) return false;
+    int64_t items = 0;
     for (int u = 0; u < n_utt; ++u) {
         if (frames[u] < 0) return false;
-        tiles += (frames[u] + 63) / 64;
-        chunks += (frames[u] + 4095) / 4096;
-        if (tiles > 0x7ffffff0) return false;
+        items += (frames[u] + rows - 1) / rows;
+        if (items > 0x7ffffff0) return false;
     }
-    utt_tile0.assign((size_t)n_utt + 1, 0);
-    utt_chunk0.assign((size_t)n_utt + 1, 0);
-    tile_utt.assign((size_t)tiles, 0);
-    chunk_utt.assign((size_t)chunks, 0);
-    int32_t t = 0, c = 0;
+    item0.assign((size_t)n_utt + 1, 0);
+    if (item_utt) item_utt->assign((size_t)items, 0);
+    int32_t i = 0;
     for (int u = 0; u < n_utt; ++u) {
-        utt_tile0[u] = t, utt_chunk0[u] = c;
-        for (int64_t r = 0; r < frames[u]; r += 64) tile_utt[(size_t)t++] = u;
-        for (int64_t r = 0; r < frames[u]; r += 4096) chunk_utt[(size_t)c++] = u;
+        item0[u] = i;
+        const int32_t n = (int32_t)((frames[u] + rows - 1) / rows);
+        if (item_utt) std::fill_n(item_utt->begin() + i, n, u);
+        i += n;
     }
-    utt_tile0[n_utt] = t, utt_chunk0[n_utt] = c;
+    item0[n_utt] = i;
     return true;
 }
 
@@ -878,26 +875,6 @@ int pitch_tile_frames(int window, int lag_max, int shift)
     int f = 64;
     while (f > 1 && pitch_span_slots(window, lag_max, shift, f) > kPitchSpanMax) --f;
     return f;
-}
-
-bool build_pitch_layout(const int64_t *frames, int n_utt, int tile_frames, std::vector<int32_t> &utt_tile0, std::vector<int32_t> &tile_utt)
-{
-    if (n_utt < 0 || tile_frames < 1) return false;
-    int64_t tiles = 0;
-    for (int u = 0; u < n_utt; ++u) {
-        if (frames[u] < 0) return false;
-        tiles += (frames[u] + tile_frames - 1) / tile_frames;
-        if (tiles > 0x7ffffff0) return false;
-    }
-    utt_tile0.assign((size_t)n_utt + 1, 0);
-    tile_utt.assign((size_t)tiles, 0);
-    int32_t t = 0;
-    for (int u = 0; u < n_utt; ++u) {
-        utt_tile0[u] = t;
-        for (int64_t r = 0; r < frames[u]; r += tile_frames) tile_utt[(size_t)t++] = u;
-    }
-    utt_tile0[n_utt] = t;
-    return true;
 }
 
 // Every float32 and double operation below is a statement of its own and this file is compiled with -ffp-contract=off; the

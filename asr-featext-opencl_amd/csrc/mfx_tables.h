@@ -100,13 +100,18 @@ bool build_speaker_lists(const int32_t *utt_spk, const int64_t *frames, int n_ut
 bool host_online_norm(const float *rows, int64_t T, int pitch, int Wn, int kind, int window, int prior_frames, int64_t prior_count,
                       const double *prior_acc, float *out);
 
-// Tiles and chunks of the VAD stage (mfx_batch_set_vad): utterance u of frames[u] rows is cut into tiles of 64 rows and into
-// chunks of 4096 rows (kNormChunkRows), numbered through the batch in utterance order.  False -- and nothing written -- on a
-// negative count or a batch whose tiles do not fit an int32.
-//   utt_tile0 / utt_chunk0 : [n_utt + 1] first tile / chunk of every utterance (a frameless utterance owns none)
-//   tile_utt / chunk_utt   : the utterance of every tile / chunk
-bool build_vad_layout(const int64_t *frames, int n_utt, std::vector<int32_t> &utt_tile0, std::vector<int32_t> &tile_utt,
-                      std::vector<int32_t> &utt_chunk0, std::vector<int32_t> &chunk_utt);
+// Utterance tilings ("Utterance tilings"): the rows of every utterance of a planned batch cut into items of `rows`
+// consecutive rows (the last one of an utterance may be shorter), numbered through the batch in utterance order.
+//   item0    : [n_utt + 1] first item of every utterance (a frameless utterance owns none)
+//   item_utt : [items] the utterance of every item; may be null (the speakers' chunks: their kernels take the utterance from the grid)
+// False -- and nothing written -- on n_utt < 0, rows < 1, a negative frame count or more than 0x7ffffff0 items.
+bool build_utt_tiling(const int64_t *frames, int n_utt, int rows, std::vector<int32_t> &item0, std::vector<int32_t> *item_utt);
+// The item sizes the kernels are compiled for: one definition each, for the host that builds a tiling and the kernel that
+// walks it (the launchers refuse a tiling of another size).  The pitch track's tile_frames is the one run-time size.
+constexpr int kVadTileRows = 64;     // k_vad_flags, k_vad_scan, k_vad_select: a wave's ballot is a tile's mask
+constexpr int kNormChunkRows = 4096; // a run of rows longer than this is summed in chunks, combined in ascending order (normaliser, speakers, VAD)
+constexpr int kOnormChunk = 32;      // rows of a chunk of the online normaliser's prefix sums (the window is a multiple of it)
+constexpr int kPitchFeatRows = 256;  // rows per tile of k_pitch_feats = threads per block
 
 // Pitch track (mfx_batch_set_pitch; DESIGN.md, "Pitch track").  pitch_shape: the limits of include/mfx.h on the seven
 // parameters (window as resolved: never 0); fills K = lag_max - lag_min + 1 states and the resolved jump J.  False outside them.
@@ -116,15 +121,14 @@ struct PitchShape {
 bool pitch_shape(int window, int lag_min, int lag_max, float ballast, float lag_cost, float penalty, int max_jump, PitchShape &s);
 // wt[k] = (float)(1 - lag_cost * l / lag_max), lg[k] = (float)ln(l), l = lag_min + k: double, rounded once
 void build_pitch_tables(const PitchShape &s, float lag_cost, std::vector<float> &wt, std::vector<float> &lg);
-// k_pitch_nccf's tiles: runs of pitch_tile_frames consecutive frames of one utterance (at most 64, fewer while the tile's
-// PCM span would pass kPitchSpanMax staged samples), numbered through the batch in utterance order as the VAD's are.
+// k_pitch_nccf's tiles: the utterance tiling at pitch_tile_frames frames (at most 64, fewer while the tile's PCM span would
+// pass kPitchSpanMax staged samples).
 // pitch_span_pad: int16 slots left empty behind every `shift` staged samples, so that the frames of a tile start on
 // different LDS banks; pitch_span_slots: the slots the span of `frames` frames takes with them.
 constexpr int kPitchSpanMax = 24576;
 int pitch_span_pad(int shift);
 int pitch_span_slots(int window, int lag_max, int shift, int frames);
 int pitch_tile_frames(int window, int lag_max, int shift);
-bool build_pitch_layout(const int64_t *frames, int n_utt, int tile_frames, std::vector<int32_t> &utt_tile0, std::vector<int32_t> &tile_utt);
 // The definition of include/mfx.h on host memory, for ONE utterance of n samples per channel and T frames at `shift`:
 // pitch [T][2] = (lag, rho), index [T], nccf [T][K]; any of them may be null.  False -- and nothing written -- on an argument
 // outside the limits.
@@ -133,12 +137,11 @@ bool host_pitch(const int16_t *pcm, int64_t n, int channels, int64_t T, int shif
 
 // Pitch features (mfx_batch_set_pitch_feats; DESIGN.md, "Pitch features").  pitch_feat_shape: the limits of include/mfx.h on
 // the eight parameters; fills the resolved column bits (0 -> POV | NORM_LOG_PITCH | DELTA), their number F and
-// den = 2 sum of l^2 over l = 1 .. D.  False outside them.  k_pitch_feats' tiles are build_pitch_layout's at kPitchFeatRows.
+// den = 2 sum of l^2 over l = 1 .. D.  False outside them.  k_pitch_feats' tiles are the utterance tiling at kPitchFeatRows.
 struct PitchFeatShape {
     int columns, F, left, right, D;
     double den;
 };
-constexpr int kPitchFeatRows = 256;
 bool pitch_feat_shape(int columns, int left, int right, int delta_window, float pov_scale, float pov_offset, float pitch_scale,
                       float delta_scale, PitchFeatShape &s);
 // The definition of include/mfx.h on host memory, for ONE utterance of T rows: pitch [T][2] = (lag, rho) -> feats [T][F].

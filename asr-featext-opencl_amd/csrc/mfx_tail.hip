@@ -164,7 +164,8 @@ __global__ void __launch_bounds__(256, 7) k_delta16(DeltaParams p)
 // ------------------------------------------------------------------------------------------------
 constexpr size_t kNormSegLdsBytes = 54 * 1024; // k_norm_seg: dynamic LDS per block (1024 rows of 13 columns: a 10 s utterance; two blocks per CU)
 
-// (kNormChunkRows, norm_finish_to and the summation itself, norm_rows_totals: mfx_norm_dev.h, shared with mfx_speakers.hip)
+// (norm_finish_to and the summation itself, norm_rows_totals: mfx_norm_dev.h, shared with mfx_speakers.hip; kNormChunkRows:
+// mfx_tables.h, shared with the host that lays the speakers' and the VAD's chunks out)
 __device__ __forceinline__ void norm_finish(const NormParams &p, int seg, int c, int n, double S, double S2, float mn, float mx)
 {
     norm_finish_to(p.stats + (int64_t)seg * 2 * p.cols, p.cols, p.norm_type, c, n, S, S2, mn, mx);

@@ -1,12 +1,13 @@
 // mfx_vad.hip -- energy voice-activity decision and voiced-frame selection of the batch entries (mfx_batch_set_vad), and
-// their launcher.  See DESIGN.md section 5, "Voice activity and frame selection".
+// their launcher.  See DESIGN.md section 5, "Voice activity and frame selection"; tiles and chunks are utterance tilings
+// (UttTiling, mfx_kernels.h; utt_item, mfx_dev.h).
 //
 // Per utterance of T frames, e[t] = y[t][column] of the finished rows y (before a transform):
 //   thr     = (float)(energy_threshold + energy_mean_scale * (S / T)),  S = sum of e[t] in double
 //   flag[t] = (float)num >= (float)den * proportion_threshold, over the window [t - ctx, t + ctx] cut at the utterance ends:
 //             den frames in it, num of them with e > thr (float32, a NaN is "not greater")
 //
-//   k_vad_sums    S of every 4096-row chunk of every utterance: 256 threads, thread i adds rows i, i + 256, ... of the chunk
+//   k_vad_sums    S of every chunk (kNormChunkRows rows) of every utterance: 256 threads, thread i adds rows i, i + 256, ... of the chunk
 //                 in ascending order, then a halving tree through LDS -- one owner and one order per sum
 //   k_vad_thresh  one thread per utterance: its chunks in ascending order from zero -> thr
 //   k_vad_flags   one wave per tile of 64 consecutive rows of one utterance.  The "loud" bits e > thr of the tile, of the 64
@@ -46,34 +47,14 @@ __device__ __forceinline__ int bits_between(uint64_t m, int a, int b)
     return __popcll(m & sel);
 }
 
-// tile -> its utterance, first frame and frame count
-struct VadTile {
-    int u, t0, n;
-    int64_t row0; // first row of the utterance
-    int T;
-};
-__device__ __forceinline__ VadTile vad_tile(const VadParams &p, int tile)
-{
-    VadTile v;
-    v.u = p.tile_utt[tile];
-    const Segment sg = p.segs[v.u];
-    v.row0 = sg.out_row0;
-    v.T = sg.n_out;
-    v.t0 = (tile - p.utt_tile0[v.u]) * 64;
-    v.n = min(64, v.T - v.t0);
-    return v;
-}
-
 // grid = chunks of the utterance range
 __global__ void __launch_bounds__(256) k_vad_sums(VadParams p)
 {
     __shared__ double s_sum[256];
-    const int c = p.chunk_first + blockIdx.x;
-    const int u = p.chunk_utt[c];
-    const Segment sg = p.segs[u];
-    const int r0 = (c - p.utt_chunk0[u]) * kNormChunkRows;
-    const int r1 = min(sg.n_out, r0 + kNormChunkRows);
-    const float *e = p.y + sg.out_row0 * (int64_t)p.y_pitch + p.column;
+    const int c = p.chunks.first + blockIdx.x;
+    const UttItem ch = utt_item<kNormChunkRows>(p.chunks, p.segs, c);
+    const int r0 = ch.t0, r1 = ch.t0 + ch.n;
+    const float *e = p.y + ch.row0 * (int64_t)p.y_pitch + p.column;
     const int tid = threadIdx.x;
     double sum = 0;
     for (int r = r0 + tid; r < r1; r += 256) sum += (double)e[(int64_t)r * p.y_pitch];
@@ -93,7 +74,7 @@ __global__ void __launch_bounds__(256) k_vad_thresh(VadParams p)
     if (u >= p.u1) return;
     const int T = p.segs[u].n_out;
     double S = 0;
-    for (int c = p.utt_chunk0[u]; c < p.utt_chunk0[u + 1]; ++c) S += p.partial[c];
+    for (int c = p.chunks.utt_item0[u]; c < p.chunks.utt_item0[u + 1]; ++c) S += p.partial[c];
     // (the two roundings spelled out: no fused multiply-add between them)
     p.thr[u] = T > 0 ? (float)__dadd_rn((double)p.energy_threshold, __dmul_rn((double)p.energy_mean_scale, S / (double)T)) : p.energy_threshold;
 }
@@ -102,9 +83,9 @@ __global__ void __launch_bounds__(256) k_vad_thresh(VadParams p)
 __global__ void __launch_bounds__(256) k_vad_flags(VadParams p)
 {
     const int lane = threadIdx.x & 63;
-    const int tile = p.tile_first + blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (tile >= p.tile_first + p.n_tiles) return; // (whole waves leave; nothing below synchronises the block)
-    const VadTile v = vad_tile(p, tile);
+    const int tile = p.tiles.first + blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (tile >= p.tiles.first + p.tiles.count) return; // (whole waves leave; nothing below synchronises the block)
+    const UttItem v = utt_item<kVadTileRows>(p.tiles, p.segs, tile);
     const float thr = p.thr[v.u];
     const float *e = p.y + v.row0 * (int64_t)p.y_pitch + p.column;
     const int ctx = p.frames_context;
@@ -135,7 +116,7 @@ __global__ void __launch_bounds__(256) k_vad_scan(VadParams p)
     const int lane = threadIdx.x & 63;
     const int u = p.u0 + blockIdx.x * 4 + (threadIdx.x >> 6);
     if (u >= p.u1) return;
-    const int i0 = p.utt_tile0[u], i1 = p.utt_tile0[u + 1];
+    const int i0 = p.tiles.utt_item0[u], i1 = p.tiles.utt_item0[u + 1];
     int running = 0;
     for (int b = i0; b < i1; b += 64) {
         const int i = b + lane;
@@ -181,8 +162,8 @@ template <bool VEC>
 __global__ void __launch_bounds__(256) k_vad_select(VadParams p)
 {
     typedef typename std::conditional<VEC, f32x4, float>::type word;
-    const int tile = p.tile_first + blockIdx.x;
-    const VadTile v = vad_tile(p, tile);
+    const int tile = p.tiles.first + blockIdx.x;
+    const UttItem v = utt_item<kVadTileRows>(p.tiles, p.segs, tile);
     const uint64_t mask = p.mask[tile];
     const bool pack = p.mode == 2;
     // first destination row of the tile's voiced rows; destination rows from `zero_from` on (of the utterance, or of the
@@ -210,28 +191,30 @@ __global__ void __launch_bounds__(256) k_vad_select(VadParams p)
 
 bool vad_shape_ok(const VadParams &p)
 {
-    return p.frames_context >= 0 && p.frames_context <= 64 && p.column >= 0 && p.column < p.y_pitch && p.width >= 1 && p.width <= 1023 &&
+    return p.frames_context >= 0 && p.frames_context <= kVadTileRows && p.column >= 0 && p.column < p.y_pitch && p.width >= 1 && p.width <= 1023 &&
            p.mode >= 0 && p.mode <= 2;
 }
 
-// the launches of one run over utterances [u0, u1): tiles [tile_first, + n_tiles), chunks [chunk_first, + n_chunks)
+// the launches of one run over utterances [u0, u1): the tiles and the chunks of that range
 hipError_t launch_vad(const VadParams &p, hipStream_t stream)
 {
     if (p.u1 <= p.u0) return hipSuccess;
     if (!vad_shape_ok(p)) return hipErrorInvalidValue;
     if (p.mode != 0 && (!p.rows || !p.out || p.rows == p.out)) return hipErrorInvalidValue;
+    if (p.tiles.rows != kVadTileRows || p.chunks.rows != kNormChunkRows) return hipErrorInvalidValue; // (the kernels' constants)
+    const int n_tiles = p.tiles.count, n_chunks = p.chunks.count;
     const int n = p.u1 - p.u0;
-    if (p.n_chunks > 0) hipLaunchKernelGGL(k_vad_sums, dim3(p.n_chunks), dim3(256), 0, stream, p);
+    if (n_chunks > 0) hipLaunchKernelGGL(k_vad_sums, dim3(n_chunks), dim3(256), 0, stream, p);
     hipLaunchKernelGGL(k_vad_thresh, dim3((n + 255) / 256), dim3(256), 0, stream, p);
-    if (p.n_tiles > 0) hipLaunchKernelGGL(k_vad_flags, dim3((p.n_tiles + 3) / 4), dim3(256), 0, stream, p);
+    if (n_tiles > 0) hipLaunchKernelGGL(k_vad_flags, dim3((n_tiles + 3) / 4), dim3(256), 0, stream, p);
     hipLaunchKernelGGL(k_vad_scan, dim3((n + 3) / 4), dim3(256), 0, stream, p);
     if (p.u1 == p.n_utt) hipLaunchKernelGGL(k_vad_pack, dim3(1), dim3(1024), 0, stream, p); // (every count is final by now)
-    if (p.mode != 0 && p.n_tiles > 0) {
+    if (p.mode != 0 && n_tiles > 0) {
         const bool vec = (p.width & 3) == 0 && (((uintptr_t)p.rows | (uintptr_t)p.out) & 15) == 0;
         if (vec)
-            hipLaunchKernelGGL(k_vad_select<true>, dim3(p.n_tiles), dim3(256), 0, stream, p);
+            hipLaunchKernelGGL(k_vad_select<true>, dim3(n_tiles), dim3(256), 0, stream, p);
         else
-            hipLaunchKernelGGL(k_vad_select<false>, dim3(p.n_tiles), dim3(256), 0, stream, p);
+            hipLaunchKernelGGL(k_vad_select<false>, dim3(n_tiles), dim3(256), 0, stream, p);
     }
     return hipGetLastError();
 }

@@ -123,7 +123,7 @@ def test_kernels_build_for_gfx950_without_private_memory():
 
 
 def test_layout_driver_runs_clean_under_the_sanitizers(tmp_path):
-    """tools/asan/vad_asan.cpp (build_vad_layout of mfx_tables.cpp) as `make asan` builds and runs it: a stand-alone CPU
+    """tools/asan/vad_asan.cpp (build_utt_tiling of mfx_tables.cpp at the VAD's two sizes) as `make asan` builds and runs it: a stand-alone CPU
     program under AddressSanitizer + UBSan."""
     gxx = shutil.which("g++")
     assert gxx, "g++ was not found"

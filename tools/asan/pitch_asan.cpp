@@ -1,5 +1,5 @@
 // Sanitizer run of the host side of mfx_batch_set_pitch (csrc/mfx_tables.cpp) under -fsanitize=address,undefined: the tile
-// layout (build_pitch_layout: the empty batch, frameless utterances, lengths on, before and after the tile edge, a negative
+// layout (build_utt_tiling: the empty batch, frameless utterances, lengths on, before and after the tile edge, a negative
 // count, more tiles than an int32 holds), the padded span (every sample of a tile's span in a slot of its own below
 // pitch_span_slots, frames of a tile on different banks) and the host restatement (host_pitch: K = 1, the largest span, stereo,
 // shift 1, utterances shorter than a frame's span, null outputs, every refusal with nothing written).  Built by
@@ -21,7 +21,7 @@ static bool layouts(int &n)
             std::vector<int64_t> frames((size_t)n_utt);
             for (int u = 0; u < n_utt; ++u) frames[u] = n_utt <= 14 ? edge[(u * 5 + n_utt) % n_edge] : ((u * 37) % 11 == 0 ? 0 : (u * 131) % 901);
             std::vector<int32_t> t0, tu;
-            if (!mfx::build_pitch_layout(frames.data(), n_utt, tf, t0, tu)) return false;
+            if (!mfx::build_utt_tiling(frames.data(), n_utt, tf, t0, &tu)) return false;
             if (t0.size() != (size_t)n_utt + 1 || t0[0] != 0 || t0[n_utt] != (int32_t)tu.size()) return false;
             for (int u = 0; u < n_utt; ++u) {
                 if (t0[u + 1] - t0[u] != (int32_t)((frames[u] + tf - 1) / tf)) return false;
@@ -33,13 +33,13 @@ static bool layouts(int &n)
                 std::vector<int64_t> bad = frames;
                 bad[(size_t)n_utt / 2] = -1;
                 std::vector<int32_t> a(3, 7), b(2, 9);
-                if (mfx::build_pitch_layout(bad.data(), n_utt, tf, a, b) || a.size() != 3 || a[0] != 7 || b.size() != 2) return false;
+                if (mfx::build_utt_tiling(bad.data(), n_utt, tf, a, &b) || a.size() != 3 || a[0] != 7 || b.size() != 2) return false;
             }
         }
     std::vector<int64_t> huge(80, (int64_t)0x7fffffff);
     std::vector<int32_t> a, b;
-    if (mfx::build_pitch_layout(huge.data(), 80, 1, a, b) || !a.empty() || !b.empty()) return false;
-    if (mfx::build_pitch_layout(huge.data(), 1, 0, a, b)) return false;
+    if (mfx::build_utt_tiling(huge.data(), 80, 1, a, &b) || !a.empty() || !b.empty()) return false;
+    if (mfx::build_utt_tiling(huge.data(), 1, 0, a, &b) || mfx::build_utt_tiling(huge.data(), -1, 1, a, &b) || !a.empty() || !b.empty()) return false;
     return true;
 }
 

@@ -1,5 +1,5 @@
 // Sanitizer run of the host side of mfx_batch_set_pitch_feats (csrc/mfx_tables.cpp) under -fsanitize=address,undefined: the
-// tile layout k_pitch_feats walks (build_pitch_layout at kPitchFeatRows: the empty batch, frameless utterances, lengths on,
+// tile layout k_pitch_feats walks (build_utt_tiling at kPitchFeatRows: the empty batch, frameless utterances, lengths on,
 // before and after the tile edge; and that every tile's rows with the largest halo fit the kernel's LDS arrays), the limits
 // (pitch_feat_shape) and the host restatement (host_pitch_feats: T = 0, 1, 2, windows longer than the utterance, the largest
 // window and delta window, every column set, rho beyond +-1, output arrays of exactly T * F floats, every refusal with nothing
@@ -22,7 +22,7 @@ static bool layouts(int &n)
         std::vector<int64_t> frames((size_t)n_utt);
         for (int u = 0; u < n_utt; ++u) frames[u] = n_utt <= 11 ? edge[(u * 5 + n_utt) % n_edge] : ((u * 37) % 11 == 0 ? 0 : (u * 131) % 1901);
         std::vector<int32_t> t0, tu;
-        if (!mfx::build_pitch_layout(frames.data(), n_utt, R, t0, tu)) return false;
+        if (!mfx::build_utt_tiling(frames.data(), n_utt, R, t0, &tu)) return false;
         if (t0.size() != (size_t)n_utt + 1 || t0[0] != 0 || t0[n_utt] != (int32_t)tu.size()) return false;
         for (int u = 0; u < n_utt; ++u) {
             if (t0[u + 1] - t0[u] != (int32_t)((frames[u] + R - 1) / R)) return false;

@@ -1,6 +1,8 @@
 // Sanitizer run of the host planner of mfx_batch_set_speakers (csrc/mfx_tables.cpp: build_speaker_lists) under
 // -fsanitize=address,undefined: interleaved ids, speakers without utterances, frameless utterances, ids outside the range,
 // the empty batch, many speakers.  Every utterance with frames must come out exactly once, under its own speaker, ascending.
+// And the chunk0 list of k_spk_sums (build_utt_tiling at kNormChunkRows without item_utt): lengths on, before and after the
+// chunk edge.
 // Built by `make -C csrc asan`.
 #include <cstdint>
 #include <cstdio>
@@ -46,6 +48,16 @@ int main()
                 if (o2.size() != 3 || o2[0] != 7 || l2.size() != 2 || l2[1] != 9) return 1;
             }
         }
+    {   // chunk0: utterance u owns chunks [chunk0[u], chunk0[u + 1]) of kNormChunkRows rows; no item_utt is asked for
+        const std::vector<int64_t> frames = {0, 1, 4096, 4097, 8200};
+        const std::vector<int32_t> want = {0, 0, 1, 2, 4, 7};
+        std::vector<int32_t> chunk0;
+        if (!mfx::build_utt_tiling(frames.data(), (int)frames.size(), mfx::kNormChunkRows, chunk0, nullptr) || chunk0 != want) return 1;
+        std::vector<int64_t> bad = frames;
+        bad[2] = -1; // (refused, nothing written)
+        if (mfx::build_utt_tiling(bad.data(), (int)bad.size(), mfx::kNormChunkRows, chunk0, nullptr) || chunk0 != want) return 1;
+        ++n;
+    }
     std::printf("speakers_asan: %d speaker lists clean\n", n);
     return 0;
 }
