@@ -383,6 +383,10 @@ struct SessState {
         int32_t tail_off = 0;            // samples from the slot's base to the first frame not yet computed
         int32_t pitch = 0;               // floats per row the slot's statics were written with
         int32_t parity = 0;              // which of the two slot arrays holds the state
+        // session transform (E above is then Ey, the finished rows y): transformed rows delivered, the stream row that is
+        // row 0 of the y slot, the session's transform (kept across final pushes and mfx_sessions_reset)
+        int64_t Ex = 0, y0 = 0;
+        int32_t xf = 0;
     };
     std::vector<Live> live;
     // online normaliser (mfx_sessions_set_online_norm: parameters only; mfx_sessions_create sizes the state)
@@ -394,6 +398,26 @@ struct SessState {
         DevBuf<double> d_prior, d_state; // [2][Wn]; [n][8][Wn] lead / trail O and I of v and q
         DevBuf<float> d_ring;            // [n][window][Wn] the last `window` raw rows of every session
     } on;
+    // splice + affine transform (mfx_sessions_set_transform: the host-side operands; mfx_sessions_create uploads them and sizes
+    // the y slots): while set, the delta stage writes the rows y of a push into the session's current y slot behind the rows
+    // carried from the previous one, and k_sess_xform (k_splice_affine under MFX_ENGINE_SESS_XFORM_PLAIN) turns them into d_out
+    struct Xform {
+        bool set = false;
+        int32_t left = 0, right = 0, out = 0, n_xf = 0;
+        int32_t G = 0;                   // row groups per block of k_sess_xform at this shape (sess_xform_tile_rows / 16)
+        std::vector<float> ops, bias;    // [n_xf][steps][tiles][64], [n_xf][tiles * 16]
+        DevBuf<float> d_ops, d_bias;
+        DevBuf<float> d_y;               // [2][n][y_cap][width]
+        int32_t y_cap = 0;               // rows of a y slot: left + right + frames_max + D
+    } xf;
+    std::vector<mfx::SessionXformStep> p_xsteps; // the pending push's transform steps, by piece
+    std::vector<int32_t> p_xn, p_xxf, p_xorder, p_gpiece, p_gr0, p_grows, p_bg0, p_bng, p_bxf; // the packer's input and output
+    std::vector<int64_t> p_xsrc;         // [pieces] absolute row of y[Ex_old] in d_y
+    std::vector<mfx::SessXfGroup> p_groups;
+    std::vector<mfx::SessXfBlock> p_blocks;
+    std::vector<mfx::Segment> p_xsegs;   // MFX_ENGINE_SESS_XFORM_PLAIN: one segment per delivering piece, and its transform
+    std::vector<int32_t> p_xseg_xf;
+    int p_xtiles_max = 0;
     std::vector<mfx::OnormSessDesc> p_onorm; // the pending push's rows to normalise
     // the pending push (mfx_sessions_plan; mfx_sessions_run_* consumes it)
     bool planned = false;
@@ -674,5 +698,7 @@ inline int spk_wn(const mfx_handle *h) { return h->cfg.norm_after_dyn ? h->width
 // message on the handle)
 int check_online_norm(mfx_handle *h, const char *who, int32_t window, int32_t prior_frames, int64_t prior_count, const double *prior_acc);
 void fill_xform(const mfx_handle *h, mfx::XformParams &p);
+// row width of the session entries' output: out_dim while a session transform is set, else `width`
+inline int sess_out_width(const mfx_handle *h) { return h->sess.xf.set ? h->sess.xf.out : h->width; }
 // the VAD's row scratch at the current output width (mfx_batch_attach.cpp; a no-op unless a selecting VAD is in force)
 int size_vad_rows(mfx_handle *h);

@@ -1,4 +1,4 @@
-// mfx_kernels.h -- launch interface of the gfx950 kernels (implemented in mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip, mfx_plp.hip, mfx_traps.hip, mfx_xform.hip, mfx_sessions.hip, mfx_resample.hip, mfx_speakers.hip, mfx_vad.hip, mfx_onorm.hip, mfx_stft.hip, mfx_pitch.hip, mfx_pitchfeat.hip: one translation unit per kernel family).
+// mfx_kernels.h -- launch interface of the gfx950 kernels (implemented in mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip, mfx_plp.hip, mfx_traps.hip, mfx_xform.hip, mfx_sess_xform.hip, mfx_sessions.hip, mfx_resample.hip, mfx_speakers.hip, mfx_vad.hip, mfx_onorm.hip, mfx_stft.hip, mfx_pitch.hip, mfx_pitchfeat.hip: one translation unit per kernel family).
 //
 // Kernel inventory and the reference stage each one replaces:
 //   spectrum512 / fused512   segmenter.cl kernelSegmentWindow + AppleFFT fft0 + mfcc.cl kernelTranspose
@@ -257,6 +257,35 @@ struct XformParams {
     int32_t ksteps;        // set by the launcher: steps of 4 taps per LDS chunk of the matrix
 };
 
+// k_sess_xform (mfx_sess_xform.hip): the same map over the rows one push of the session entries delivers ("Session
+// transform").  The work list: row groups of at most 16 output rows of one session, sorted by transform, and blocks of up to
+// tile_rows / 16 consecutive groups of ONE transform (pack_sess_xform_groups, mfx_tables.h).  Group rows r < rows: rows
+// src_row0 + clamp(r0 + r - left + c, lo, hi), c <= left + right, are read, row out_row0 + r written.
+struct SessXfGroup {
+    int64_t src_row0;      // row of `src` that holds row 0 of the session's piece (the first row this push delivers)
+    int64_t out_row0;      // output row of the group's first row
+    int32_t r0, rows;      // first row of the group inside the piece; its rows (<= 16)
+    int32_t lo, hi;        // the piece's clamp window, relative to src_row0
+};
+struct SessXfBlock {
+    int32_t g0, ng;        // the block's groups: [g0, g0 + ng), ng <= tile_rows / 16
+    int32_t xf, pad;       // their transform
+};
+struct SessXformParams {
+    const float *src;      // the rows y, [rows][src_pitch], columns [0, width)
+    int32_t src_pitch;
+    float *out;            // [rows][out_pitch], columns [0, out_dim) written
+    int32_t out_pitch;
+    const SessXfGroup *groups;
+    const SessXfBlock *blocks;
+    int32_t n_blocks;
+    int32_t width, left, right, out_dim, valu; // as XformParams
+    const float *operands; // [n_xf][steps][tiles][64]
+    const float *bias;     // [n_xf][tiles * 16]
+    int32_t tile_rows;     // 16 G the work list was packed for (0: not checked); the launcher takes sess_xform_tile_rows
+    int32_t ksteps;        // set by the launcher
+};
+
 // k_sess_gather (mfx_sessions.hip): one push of one session ("Session entries").  The session's CURRENT slot is
 // written from three sources -- the PCM tail the previous slot carries, the caller's new samples, the static rows the
 // previous slot carries -- and from nowhere else: previous and current slot are different slots of the ping-pong pair.
@@ -271,6 +300,10 @@ struct SessDesc {
     int64_t row_dst;    // statics: first row of the current slot (absolute row, times SessGatherParams::stat_pitch)
     int32_t n_rows;     // rows carried
     int32_t src_pitch;  // floats per row the previous slot was written with
+    int64_t y_src;      // finished rows y (session transform): first carried row in the previous y slot (absolute row)
+    int64_t y_dst;      // first row of the current y slot
+    int32_t y_rows;     // rows carried (0 without a session transform)
+    int32_t pad;
 };
 
 struct SessGatherParams {
@@ -285,6 +318,8 @@ struct SessGatherParams {
     int32_t stat_pitch;    // floats per row of the current slots
     int32_t cols;          // static columns
     int32_t items_max;     // set by the planner: the largest item count of any descriptor (sizes the grid)
+    float *slot_y;         // both y slot arrays, [rows][y_width] (null without a session transform)
+    int32_t y_width;       // Wd: floats per row of y
 };
 
 // k_resample (mfx_resample.hip): per-utterance sample-rate conversion, int16 -> int16 ("Sample-rate conversion").
@@ -567,14 +602,20 @@ size_t traps_lds_bytes(const TrapsParams &p, int tile_rows);
 int traps_tile_rows(const TrapsParams &p);
 hipError_t launch_xform(const XformParams &p, hipStream_t stream);
 hipError_t launch_sess_gather(const SessGatherParams &p, hipStream_t stream);
+// k_sess_xform: LDS at tile_rows = 16 G rows per block; the tile the launcher takes (the largest G of 4, 2, 1 inside
+// kTileLdsTarget, else the largest inside 160 KB; 0: the shape is outside the limits, or none fits); the launch
+size_t sess_xform_lds_bytes(const SessXformParams &p, int tile_rows);
+int sess_xform_tile_rows(const SessXformParams &p);
+hipError_t launch_sess_xform(const SessXformParams &p, hipStream_t stream);
 // k_resample: tile geometry of one rate (fills R, items, tile_out, in_lds from L, M, P), the LDS floats per channel its
 // input span needs, and the launch (taps_floats / x_floats / out_elems are the maxima over the plan's rates)
 void resample_geometry(int channels, ResRate &r);
 int resample_span_floats(const ResRate &r);
 size_t resample_lds_bytes(const ResampleParams &p);
 hipError_t launch_resample(const ResampleParams &p, hipStream_t stream);
-// work items of one descriptor: 16-byte words of PCM, then 16-byte words (or single floats) of static rows
-int sess_gather_items(const SessDesc &d, int stat_pitch, int cols);
+// work items of one descriptor: 16-byte words of PCM, then 16-byte words (or single floats) of static rows, then the floats
+// of the carried rows y
+int sess_gather_items(const SessDesc &d, int stat_pitch, int cols, int y_width = 0);
 // LDS of k_splice_affine with tile_rows output rows per block; xform_tile_rows: the tile the launcher takes (0: the shape is
 // outside the limits, or none fits); xform_shape_ok: width, context, in_dim and out_dim inside the kernel's limits
 size_t xform_lds_bytes(const XformParams &p, int tile_rows);

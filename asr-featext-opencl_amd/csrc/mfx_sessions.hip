@@ -43,7 +43,8 @@ __device__ __forceinline__ uint4 load8(const int16_t *base, int64_t o, int64_t l
 
 // grid = (pieces, descriptors), 256 threads.  A work item is one 16-byte word of the destination: first the words of the
 // slot's PCM part (carried tail, then the new samples, zeros up to the end of the last word), then the carried static
-// rows.  Every store is an aligned 16-byte word, except static rows whose pitch is no multiple of 4 floats.
+// rows, then (session transform) the carried rows y, float by float.  Every store of the first two parts is an aligned 16-byte
+// word, except static rows whose pitch is no multiple of 4 floats.
 __global__ void __launch_bounds__(256) k_sess_gather(SessGatherParams p)
 {
     const SessDesc d = p.descs[blockIdx.y];
@@ -51,7 +52,8 @@ __global__ void __launch_bounds__(256) k_sess_gather(SessGatherParams p)
     const int pcm_words = (n_pcm + 7) >> 3;
     const bool vec_rows = ((p.stat_pitch | d.src_pitch) & 3) == 0;
     const int per_row = vec_rows ? (p.cols + 3) >> 2 : p.cols;
-    const int total = pcm_words + d.n_rows * per_row;
+    const int stat_items = pcm_words + d.n_rows * per_row;
+    const int total = stat_items + d.y_rows * p.y_width; // (the carried rows y are contiguous in both slots: single floats)
     const bool wide = p.narrow == 0;
     // (per_row > 0: floor(j / per_row) as a multiply-high, j < 2^16 rows x columns of one slot)
     const uint32_t magic = per_row > 1 ? 0xffffffffu / (uint32_t)per_row + 1 : 0;
@@ -78,6 +80,9 @@ __global__ void __launch_bounds__(256) k_sess_gather(SessGatherParams p)
                 v = make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
             }
             *(uint4 *)(p.slot_pcm + d.pcm_dst + e0) = v;
+        } else if (i >= stat_items) {
+            const int j = i - stat_items;
+            p.slot_y[d.y_dst * p.y_width + j] = p.slot_y[d.y_src * p.y_width + j];
         } else {
             const int j = i - pcm_words;
             const int r = per_row > 1 ? (int)__umulhi((uint32_t)j, magic) : j, c = j - r * per_row;
@@ -93,10 +98,10 @@ __global__ void __launch_bounds__(256) k_sess_gather(SessGatherParams p)
 
 } // namespace
 
-int sess_gather_items(const SessDesc &d, int stat_pitch, int cols)
+int sess_gather_items(const SessDesc &d, int stat_pitch, int cols, int y_width)
 {
     const bool vec_rows = ((stat_pitch | d.src_pitch) & 3) == 0;
-    return ((d.carry_n + d.new_n + 7) >> 3) + d.n_rows * (vec_rows ? (cols + 3) >> 2 : cols);
+    return ((d.carry_n + d.new_n + 7) >> 3) + d.n_rows * (vec_rows ? (cols + 3) >> 2 : cols) + d.y_rows * y_width;
 }
 
 hipError_t launch_sess_gather(const SessGatherParams &p, hipStream_t stream)

@@ -49,6 +49,41 @@ int32_t session_step(int window_size, int shift, int D, int64_t &n, int64_t &E, 
     return st.n_out;
 }
 
+int32_t session_xform_step(int left, int right, int64_t &Ey, int64_t &Ex, int32_t n_y, bool final_push, SessionXformStep &st)
+{
+    const int64_t c0 = std::max<int64_t>(Ex - left, 0);
+    const int64_t Ey_new = Ey + n_y;
+    const int64_t Ex_new = final_push ? Ey_new : std::max<int64_t>(Ey_new - right, 0);
+    st.n_out = (int32_t)(Ex_new - Ex);
+    st.carry_rows = (int32_t)(Ey - c0);
+    st.src_row0 = (int32_t)(Ex - c0);
+    st.lo = -st.src_row0;
+    st.hi = (int32_t)(Ey_new - 1 - Ex);
+    Ey = final_push ? 0 : Ey_new;
+    Ex = final_push ? 0 : Ex_new;
+    return st.n_out;
+}
+
+void pack_sess_xform_groups(const int32_t *n_out, const int32_t *xf, int n, int G, std::vector<int32_t> &order, std::vector<int32_t> &group_piece,
+                            std::vector<int32_t> &group_r0, std::vector<int32_t> &group_rows, std::vector<int32_t> &block_g0,
+                            std::vector<int32_t> &block_ng, std::vector<int32_t> &block_xf)
+{
+    group_piece.clear(), group_r0.clear(), group_rows.clear(), block_g0.clear(), block_ng.clear(), block_xf.clear();
+    order.clear();
+    for (int i = 0; i < n; ++i)
+        if (n_out[i] > 0) order.push_back(i);
+    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return xf[a] < xf[b]; });
+    for (int32_t i : order)
+        for (int32_t r0 = 0; r0 < n_out[i]; r0 += 16) {
+            const int32_t g = (int32_t)group_piece.size();
+            if (block_g0.empty() || block_xf.back() != xf[i] || block_ng.back() == G) {
+                block_g0.push_back(g), block_ng.push_back(0), block_xf.push_back(xf[i]);
+            }
+            ++block_ng.back();
+            group_piece.push_back(i), group_r0.push_back(r0), group_rows.push_back(std::min(16, n_out[i] - r0));
+        }
+}
+
 int estimated_window_count_f32(int samples, int window_size, int shift)
 {
     return (int)std::floor((float)(samples - (window_size - shift)) / (float)shift);

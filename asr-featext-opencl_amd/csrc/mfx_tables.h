@@ -31,6 +31,30 @@ struct SessionStep {
 };
 int32_t session_step(int window_size, int shift, int D, int64_t &n, int64_t &E, int64_t length, bool final_push, SessionStep &st);
 
+// The session transform's step ("Session transform"): a session whose rows y[0, Ey) are complete (Ey is the E of
+// session_step) and which has delivered transformed rows [0, Ex) completes n_y more rows.  Ex = max(0, Ey - right) while the
+// stream is open, Ey once a push is final.  The previous y slot carries rows [c0, Ey), c0 = max(0, Ex - left) -- at most left +
+// right of them -- and the push writes the n_y new rows behind them: row 0 of the current slot is y[c0].  The push delivers
+// rows [Ex_old, Ex_new) through k_splice_affine's accessor src[src_row0 + clamp(r - left + c, lo, hi)], r relative to Ex_old:
+// src_row0 = Ex_old - c0 is the slot row of y[Ex_old], lo = -src_row0 (y[c0]: reached only when c0 = 0, the true start of the
+// stream) and hi = Ey_new - 1 - Ex_old (reached only by a final push).  Returns n_out; Ey and Ex are advanced (both 0 after a
+// final push).
+struct SessionXformStep {
+    int32_t n_out;      // rows delivered
+    int32_t carry_rows; // rows y carried in
+    int32_t src_row0, lo, hi;
+};
+int32_t session_xform_step(int left, int right, int64_t &Ey, int64_t &Ex, int32_t n_y, bool final_push, SessionXformStep &st);
+
+// The work list of k_sess_xform for one push: piece i delivers n_out[i] rows with transform xf[i].  Every piece is cut into
+// row groups of at most 16 rows; the groups are sorted by transform (stable: pieces keep their order inside a transform) and
+// packed into blocks of at most G groups of one transform.  group_piece / group_r0 / group_rows: the groups; block_g0 /
+// block_ng / block_xf: the blocks; order: work space (the delivering pieces by transform), the caller's so that a warm planner
+// allocates nothing.
+void pack_sess_xform_groups(const int32_t *n_out, const int32_t *xf, int n, int G, std::vector<int32_t> &order, std::vector<int32_t> &group_piece,
+                            std::vector<int32_t> &group_r0, std::vector<int32_t> &group_rows, std::vector<int32_t> &block_g0,
+                            std::vector<int32_t> &block_ng, std::vector<int32_t> &block_xf);
+
 // The reference's float32 version, bit-for-bit (used by the streaming state machine).
 int estimated_window_count_f32(int samples, int window_size, int shift);
 

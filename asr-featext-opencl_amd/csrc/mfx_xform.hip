@@ -29,20 +29,13 @@
 #include "mfx_dev.h"
 #include "mfx_launch.h"
 #include "mfx_tile_dev.h"
+#include "mfx_xform_dev.h"
 
 namespace mfx {
 
 namespace {
 
-__host__ __device__ inline int xform_tiles(int out_dim) { return (out_dim + 15) >> 4; }
-__host__ __device__ inline int xform_steps(int in_dim) { return (in_dim + 3) >> 2; }
-// steps of 4 taps per LDS chunk: at most 2048 floats (8 KB, two 16-byte words per thread in flight) per buffer -- the
-// two buffers leave room for 64 rows of the C2 shape (39 columns, 9 frames, 40 outputs) inside the LDS target below
-__host__ __device__ inline int xform_ksteps(int in_dim, int out_dim)
-{
-    const int k = 32 / xform_tiles(out_dim), s = xform_steps(in_dim);
-    return k < s ? k : s;
-}
+// (xform_tiles / xform_steps / xform_ksteps, the chunk loop and the scatter: mfx_xform_dev.h, shared with k_sess_xform)
 // floats of the staged rows: R + left + right rows back to back, then the zeros the last row's padded taps read
 __host__ __device__ inline int xform_stage_floats(int R, int width, int ctx) { return (R + ctx) * width + 4; }
 
@@ -71,11 +64,7 @@ __global__ void __launch_bounds__(256) k_splice_affine(XformParams p)
 
     // chunk 0 on its way while the rows are staged
     f32x4 pf[2] = {};
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const int i = tid + 256 * q;
-        if (i < min(chunk4, total4)) pf[q] = ops4[i];
-    }
+    xform_prefetch0(ops4, pf, chunk4, total4, tid);
     {   // rows r0 - left .. r0 + R + right - 1 of the utterance, clamped to it; zeros behind them
         const int n = (R + ctx) * Wd;
         const uint32_t magic = div_magic(Wd); // floor(i / Wd) for i < 2^16 (n < 160 KB / 4)
@@ -87,98 +76,21 @@ __global__ void __launch_bounds__(256) k_splice_affine(XformParams p)
         }
         if (tid < 4) s_y[n + tid] = 0.f;
     }
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const int i = tid + 256 * q;
-        if (i < min(chunk4, total4)) ((f32x4 *)s_b)[i] = pf[q];
-    }
+    xform_commit0(s_b, pf, chunk4, total4, tid);
     __syncthreads();
 
     const int lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, lk = lane >> 4;
-    const int G = R >> 4, slots = 4 / G;       // row groups; waves that share a group split the tiles
-    const int g = wave & (G - 1), slot = wave / G;
-    const int cnt = slot < NT ? min(TM, (NT - slot + slots - 1) / slots) : 0; // tiles slot + j slots, j < cnt
-    const bool busy = cnt > 0 && 16 * g < rows;
+    const XformWave w = xform_wave<TM>(wave, R >> 4, NT); // row group w.g, output tiles w.slot + j w.slots, j < w.cnt
+    const int g = w.g;
+    const bool busy = w.cnt > 0 && 16 * g < rows;
 
-    f32x4 acc[TM];
-#pragma unroll
-    for (int j = 0; j < TM; ++j) {
-        const float b = j < cnt ? bias[16 * (slot + j * slots) + li] : 0.f;
-        acc[j] = f32x4{b, b, b, b};
-    }
     // matrix form: lane (li, lk) feeds row 16 g + li, tap 4 s + lk; vector form: rows 16 g + 4 lk + r, taps in turn
     const float *za = VALU ? s_y + (16 * g + 4 * lk) * Wd : s_y + (16 * g + li) * Wd + lk;
-
-    for (int c = 0; c < nchunks; ++c) {
-        const bool more = c + 1 < nchunks;
-        const int n4 = more ? min(chunk4, total4 - (c + 1) * chunk4) : 0;
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int i = tid + 256 * q;
-            if (i < n4) pf[q] = ops4[(c + 1) * chunk4 + i];
-        }
-        if (busy) {
-            const float *buf = s_b + (c & 1) * chunk4 * 4 + slot * 64;
-            const int s0 = c * KS, s1 = min(steps, s0 + KS);
-            for (int s = s0; s < s1; ++s) {
-                const float *b = buf + (s - s0) * NT * 64;
-                if constexpr (VALU) {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const int i = 4 * s + k;
-                        float z[4];
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) z[r] = i < in_dim ? za[r * Wd + i] : 0.f;
-#pragma unroll
-                        for (int j = 0; j < TM; ++j) {
-                            if (j < cnt) {
-                                const float w = b[j * slots * 64 + 16 * k + li];
-#pragma unroll
-                                for (int r = 0; r < 4; ++r) acc[j][r] = __builtin_fmaf(w, z[r], acc[j][r]);
-                            }
-                        }
-                    }
-                } else {
-                    const float a = 4 * s + lk < in_dim ? za[4 * s] : 0.f;
-#pragma unroll
-                    for (int j = 0; j < TM; ++j)
-                        if (j < cnt) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b[j * slots * 64 + lane], acc[j], 0, 0, 0);
-                }
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int i = tid + 256 * q;
-            if (i < n4) ((f32x4 *)(s_b + ((c + 1) & 1) * chunk4 * 4))[i] = pf[q];
-        }
-        __syncthreads();
-    }
-
-    // D[i][n]: lane holds rows i = 4 (lane >> 4) + r, output n = lane & 15
-    if (busy) {
-#pragma unroll
-        for (int j = 0; j < TM; ++j) {
-            const int o = 16 * (slot + j * slots) + li;
-            if (j >= cnt || o >= od) continue;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int t = 16 * g + 4 * lk + r;
-                if (t < rows) s_out[t * od + o] = acc[j][r];
-            }
-        }
-    }
-    __syncthreads();
+    xform_compute<VALU, TM>(ops4, bias, pf, s_b, chunk4, total4, nchunks, steps, KS, NT, in_dim, Wd, za, busy, w, tid, s_out + 16 * g * od, od,
+                            rows - 16 * g);
 
     tile_store_rows(s_out, od, rows, p.out, sg.out_row0 + r0, p.out_pitch, tid);
-}
-
-// accumulator tiles a wave carries at tile_rows rows per block, rounded up to an instantiated count
-int xform_tm(const XformParams &p, int tile_rows)
-{
-    const int slots = 4 / (tile_rows >> 4);
-    const int t = (xform_tiles(p.out_dim) + slots - 1) / slots;
-    return t <= 4 ? t : t <= 8 ? 8 : 16;
 }
 
 template <bool VALU>
@@ -226,7 +138,7 @@ hipError_t launch_xform(const XformParams &p, hipStream_t stream)
     const int R = xform_tile_rows(p);
     if (R == 0) return hipErrorInvalidValue;
     const size_t lds = xform_lds_bytes(p, R);
-    const int tm = xform_tm(p, R);
+    const int tm = xform_tm(p.out_dim, R);
     const void *fn = p.valu ? xform_fn<true>(tm) : xform_fn<false>(tm);
     if (hipError_t e = allow_dynamic_lds(fn, lds); e != hipSuccess) return e;
     const int tiles_x = p.tiles_per_seg_max * (64 / R);

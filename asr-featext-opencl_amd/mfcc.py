@@ -77,6 +77,8 @@ EXPORTED_SYMBOLS = (
     "mfx_method_supported", "mfx_host_plp_tables", "mfx_host_traps_basis",
     "mfx_sessions_create", "mfx_sessions_reset", "mfx_sessions_plan", "mfx_sessions_run_device", "mfx_sessions_run_host",
     "mfx_sessions_delivered", "mfx_host_session_step",
+    "mfx_sessions_set_transform", "mfx_sessions_clear_transform", "mfx_sessions_select_transform",
+    "mfx_sessions_output_width", "mfx_host_session_xform_step", "mfx_host_sess_xform_groups",
     "mfx_batch_plan_rates", "mfx_batch_resample_layout", "mfx_host_resample_taps", "mfx_host_resampled_length",
     "mfx_host_resample_layout", "mfx_host_resample_tile",
     "mfx_batch_set_speakers", "mfx_batch_speaker_stats", "mfx_host_speaker_lists",
@@ -172,6 +174,14 @@ def load_library():
     L.mfx_sessions_delivered.argtypes, L.mfx_sessions_delivered.restype = [vp, i32], i64
     L.mfx_host_session_step.argtypes = [i32, i32, i32, p64, i64, i32, p64, p32, p32, p32]
     L.mfx_host_session_step.restype = i32
+    L.mfx_sessions_set_transform.argtypes = [vp, i32, i32, i32, i32, fp, fp]
+    L.mfx_sessions_clear_transform.argtypes = [vp]
+    L.mfx_sessions_select_transform.argtypes = [vp, i32, i32]
+    L.mfx_sessions_output_width.argtypes = [vp]
+    L.mfx_host_session_xform_step.argtypes = [i32, i32, p64, i32, i32, p32, p32]
+    L.mfx_host_session_xform_step.restype = i32
+    L.mfx_host_sess_xform_groups.argtypes = [i32, p32, p32, i32, p32, i32, p32, i32, p32]
+    L.mfx_host_sess_xform_groups.restype = i32
     L.mfx_batch_plan_rates.argtypes = [vp, i32, p64, p64, p32, i32, C.c_float, p64, p64]
     L.mfx_batch_resample_layout.argtypes = [vp, p64, p64, p64]
     L.mfx_host_resample_taps.argtypes = [i32, i32, i32, C.c_float, fp, i64, p32, p32, p32]
@@ -442,6 +452,38 @@ def host_session_step(window_size, shift, D, state, length, final=False):
                 new_frames=nf.value, n_out=seg[0], shift=seg[1], lo=seg[2], hi=seg[3], static_off=seg[4])
 
 
+def host_session_xform_step(left, right, state, n_y, final=False):
+    """One push of one session under a session transform exactly as the planner derives it (host code, no GPU needed).
+    state = (Ey, Ex): finished rows y and transformed rows delivered so far; n_y: the rows y the push completes.  Returns
+    dict(rows, state, carry_rows, src_row0, lo, hi); state is (0, 0) after a final push."""
+    L = load_library()
+    st = (C.c_int64 * 2)(int(state[0]), int(state[1]))
+    cr = C.c_int32(0)
+    win = (C.c_int32 * 3)()
+    rows = L.mfx_host_session_xform_step(int(left), int(right), st, int(n_y), int(bool(final)), C.byref(cr), win)
+    if rows < 0:
+        raise MfxError(int(rows), "mfx_host_session_xform_step failed")
+    return dict(rows=int(rows), state=(int(st[0]), int(st[1])), carry_rows=cr.value, src_row0=win[0], lo=win[1], hi=win[2])
+
+
+def host_sess_xform_groups(n_out, xf, G=4):
+    """The work list of k_sess_xform (UNSTABLE inspection aid): (groups [.][3] = piece, first row, rows; blocks [.][3] = first
+    group, groups, transform)."""
+    L = load_library()
+    no = np.ascontiguousarray(n_out, dtype=np.int32)
+    x = np.ascontiguousarray(xf, dtype=np.int32)
+    assert no.size == x.size
+    p32 = C.POINTER(C.c_int32)
+    nb = C.c_int32(0)
+    ng = L.mfx_host_sess_xform_groups(no.size, no.ctypes.data_as(p32), x.ctypes.data_as(p32), int(G), None, 0, None, 0, C.byref(nb))
+    if ng < 0:
+        raise MfxError(int(ng), "mfx_host_sess_xform_groups failed")
+    groups, blocks = np.zeros((ng, 3), np.int32), np.zeros((nb.value, 3), np.int32)
+    L.mfx_host_sess_xform_groups(no.size, no.ctypes.data_as(p32), x.ctypes.data_as(p32), int(G), groups.ctypes.data_as(p32), ng,
+                                 blocks.ctypes.data_as(p32), nb.value, C.byref(nb))
+    return groups, blocks
+
+
 def host_resample_taps(in_hz, out_hz, zeros=0, rolloff=0.0):
     """Tap table of the sample-rate converter exactly as uploaded (host code, no GPU needed): (taps [L][P], L, M, P)."""
     lib = load_library()
@@ -610,6 +652,7 @@ SPK_POOL, SPK_PRIOR_ONLY = 0, 1                            # mfx_batch_set_speak
 ENGINE_NO_FRONT1024, ENGINE_FUSE_DELTA, ENGINE_NO_FRONT2048, ENGINE_STREAM_KERNELS, ENGINE_NORM_TWO_KERNELS = 1, 2, 4, 8, 16
 ENGINE_DMA_SMALL_BLOCKS, ENGINE_NO_DCT_SPLIT, ENGINE_NO_STUFF256, ENGINE_FRONT1024_12_WAVES = 32, 64, 128, 256     # mfx_config.engine bits (include/mfx.h)
 ENGINE_TRAPS_VALU, ENGINE_XFORM_VALU, ENGINE_SESS_NARROW_LOADS = 512, 1024, 2048
+ENGINE_SESS_XFORM_PLAIN = 4096
 
 
 class MfccHip:
@@ -1060,10 +1103,10 @@ class MfccHip:
                                                   C.c_void_p(int(d_out_ptr))))
 
     def sessions_run_host(self, pcm):
-        """Run the planned push from / to host arrays; returns its rows [total][get_output_data_width()]."""
+        """Run the planned push from / to host arrays; returns its rows [total][sessions_output_width()]."""
         pcm = np.ascontiguousarray(pcm, dtype=np.int16)
         total = pcm.size // max(self.cfg.channels, 1)
-        out = np.zeros((getattr(self, "_sess_total", 0), self.get_output_data_width()), dtype=np.float32)
+        out = np.zeros((getattr(self, "_sess_total", 0), self.sessions_output_width()), dtype=np.float32)
         self._chk(self._L.mfx_sessions_run_host(self._h, pcm.ctypes.data_as(C.POINTER(C.c_int16)), total,
                                                 out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
@@ -1075,7 +1118,44 @@ class MfccHip:
             raise MfxError(n, self._L.mfx_status_string(n).decode())
         return n
 
+    def sessions_set_transform(self, A, b=None, left=0, right=0):
+        """Splice + affine transform as the last stage of every push (mfx_sessions_set_transform): call it before
+        sessions_create.  A is [out_dim][in_dim] or [n_xf][out_dim][in_dim] with in_dim = (left + right + 1) *
+        get_output_data_width(); b [out_dim] / [n_xf][out_dim] or None (zeros).  A session then delivers rows [0, Ex), Ex =
+        max(0, E - right) while open, and its rows are sessions_output_width() wide."""
+        a = np.ascontiguousarray(A, dtype=np.float32)
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3:
+            raise ValueError("A must be [out_dim][in_dim] or [n_xf][out_dim][in_dim]")
+        n_xf, out_dim, in_dim = a.shape
+        if in_dim != (int(left) + int(right) + 1) * self.get_output_data_width():
+            raise ValueError("A must have (left + right + 1) * get_output_data_width() columns")
+        fpt = C.POINTER(C.c_float)
+        bb = None
+        if b is not None:
+            bb = np.ascontiguousarray(b, dtype=np.float32).reshape(-1)
+            if bb.size != n_xf * out_dim:
+                raise ValueError("b must have out_dim entries per transform")
+        self._chk(self._L.mfx_sessions_set_transform(self._h, int(left), int(right), out_dim, n_xf, a.ctypes.data_as(fpt),
+                                                     None if bb is None else bb.ctypes.data_as(fpt)))
+
+    def sessions_clear_transform(self):
+        self._chk(self._L.mfx_sessions_clear_transform(self._h))
+
+    def sessions_select_transform(self, session, xf):
+        """The transform of one (fresh) session; kept across final pushes and sessions_reset."""
+        self._chk(self._L.mfx_sessions_select_transform(self._h, int(session), int(xf)))
+
+    def sessions_output_width(self):
+        """Row width of the session entries' output: out_dim while a session transform is set, else get_output_data_width()."""
+        w = int(self._L.mfx_sessions_output_width(self._h))
+        if w < 0:
+            raise MfxError(w, self._L.mfx_status_string(w).decode())
+        return w
+
     host_session_step = staticmethod(host_session_step)
+    host_session_xform_step = staticmethod(host_session_xform_step)
 
     def batch_overlap(self, enable=True):
         """Let the delta tail of a batch overlap the next batch's front end (results complete after synchronize())."""

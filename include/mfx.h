@@ -176,6 +176,10 @@ enum { MFX_LOGMEL_WHISPER = 0, MFX_LOGMEL_LOG10 = 1, MFX_LOGMEL_LN = 2 };
                                             of whole 32-bit words and a byte-align step (the same bits; the comparator of
                                             the measurement in DESIGN.md, "Session entries")                             */
 
+#define MFX_ENGINE_SESS_XFORM_PLAIN 4096 /* session entries with mfx_sessions_set_transform: the transform of a push runs
+                                           k_splice_affine itself, one segment per session, instead of k_sess_xform, which packs
+                                           row groups of different sessions into one block (the same bits; the comparator of
+                                           tools/sess_xform_bench.py) */
 #define MFX_ENGINE_FRONT1024_12_WAVES 256 /* 1024-point fused kernel: the 12-waves-per-CU build also where the 16-wave build fits
                                             (aligned frames, window <= 512 samples, tables small enough): the same bits      */
 
@@ -660,8 +664,9 @@ int mfx_batch_run_host(mfx_handle *h, const int16_t *pcm, int64_t pcm_samples_to
  * MFX_NORM_NONE without mfx_sessions_set_online_norm (the one normaliser the session entries serve is the online CMN / CVN
  * above; MINMAX never); MFX_ERR_DEVICE a planning handle.
  * The handle's mfx_set_alpha factor applies to all sessions.  NOT applied to session runs: mfx_batch_set_alphas,
- * mfx_batch_set_transform, mfx_batch_overlap, MFX_ENGINE_FUSE_DELTA.  A push leaves the batch plan (with its alpha list and
- * transform) and the streaming state of the same handle untouched, and they leave the sessions untouched. */
+ * mfx_batch_overlap, MFX_ENGINE_FUSE_DELTA.  The transform of mfx_batch_set_transform belongs to the batch plan and is not
+ * applied either; the same stage is served through mfx_sessions_set_transform below.  A push leaves the batch plan (with its
+ * alpha list and transform) and the streaming state of the same handle untouched, and they leave the sessions untouched. */
 int mfx_sessions_create(mfx_handle *h, int32_t n_sessions, int32_t max_push_samples);
 int mfx_sessions_reset(mfx_handle *h, int32_t session);
 int mfx_sessions_plan(mfx_handle *h, int32_t n, const int32_t *ids, const int64_t *offsets, const int64_t *lengths,
@@ -669,6 +674,50 @@ int mfx_sessions_plan(mfx_handle *h, int32_t n, const int32_t *ids, const int64_
 int mfx_sessions_run_device(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_total, float *d_out);
 int mfx_sessions_run_host(mfx_handle *h, const int16_t *pcm, int64_t pcm_samples_total, float *out);
 int64_t mfx_sessions_delivered(const mfx_handle *h, int32_t session);
+
+/* ---- session transform: splice + affine transform as the last stage of a push ("Session transform") ----
+ *
+ * The semantics are exactly those of mfx_batch_set_transform: with y[t] the rows a session delivers without it (width Wd =
+ * mfx_get_output_data_width, after the deltas and after the online normaliser if one is set), C = left + right + 1 and in_dim
+ * = C * Wd,
+ *   z[t]      = [ y[clamp(t - left, 0, T - 1)] | ... | y[clamp(t + right, 0, T - 1)] ]     (T: the rows of the whole STREAM)
+ *   out[t][r] = b_x[r], then for i = 0 .. in_dim - 1 ascending: fmaf(A_x[r][i], z[t][i], .)      (float32, one FMA per tap)
+ * with x the session's transform (mfx_sessions_select_transform; default 0).  A is [n_xf][out_dim][in_dim] row-major, b
+ * [n_xf][out_dim] or NULL (zeros).
+ * Delivery rule.  right > 0 needs look-ahead.  Let Ey be the E of the session entries above (max(0, T(n) - D) while the
+ * stream is open, T(n) once final).  A session with a transform has delivered rows [0, Ex):
+ *   Ex = max(0, Ey - right) while the stream is open;
+ *   Ex = Ey = T(n)          once a push is final.
+ * mfx_sessions_delivered returns Ex, out_counts[i] = Ex_new - Ex_old, and d_out is [total_rows][out_dim]
+ * (mfx_sessions_output_width).  The right clamp happens only on a final push, the left clamp only at the true start of the
+ * stream.  A push may deliver 0 rows; a flush delivers up to right + D rows with no new samples.
+ * Contract.  The rows a session delivers are THE SAME BITS that mfx_batch_run_device writes for the whole utterance on a
+ * handle of the same configuration with mfx_batch_set_transform(left, right, out_dim, ..., utt_xf[u] = the session's x):
+ * however the stream is cut, in the matrix and the vector form (MFX_ENGINE_XFORM_VALU applies here too), with or without
+ * MFX_ENGINE_SESS_XFORM_PLAIN, wherever d_out lies (any 4-byte alignment); nothing outside [d_out, d_out + total_rows *
+ * out_dim) is written.
+ * State.  mfx_sessions_set_transform / mfx_sessions_clear_transform are valid only while no sessions exist (before
+ * mfx_sessions_create, or after mfx_sessions_create(h, 0, 0)), else MFX_ERR_STATE.  The setter stores the matrices as the
+ * kernels read them and allocates nothing on the device; mfx_sessions_create sizes and uploads everything (two more slot
+ * arrays of left + right + frames_max + D rows of Wd floats per session, n_xf * out_dim * in_dim operand floats rounded up to
+ * the kernels' tiles), mfx_sessions_run_device still allocates nothing and queues ONE launch more, and
+ * mfx_sessions_create(h, 0, 0) releases the device parts.  A session carries at most left + right finished rows y from push
+ * to push; mfx_sessions_reset drops them with the rest.  Without a session transform every session entry does exactly what it
+ * did before.  The batch plan's transform and the streaming state of the same handle are untouched and leave the session
+ * transform untouched.
+ * mfx_sessions_select_transform(h, session, x): the session's transform.  The choice stays with the id across final pushes
+ * and mfx_sessions_reset; mfx_sessions_create puts all back to 0.  It drops a pending plan.  MFX_ERR_STATE without a transform
+ * or without sessions, or when the session is not fresh (it has received samples since its last final push or reset);
+ * MFX_ERR_ARG for an id or x out of range.
+ * Errors of the setter: MFX_ERR_ARG left / right outside 0 .. 32, out_dim outside 1 .. 256, n_xf outside 1 .. 1024, in_dim >
+ * 8192, A == NULL; MFX_ERR_CONFIG no block tiling fits the LDS (the launchers' own rule; cannot happen inside the limits
+ * above); MFX_ERR_DEVICE a planning handle, before any argument is looked at (all four entries). */
+int mfx_sessions_set_transform(mfx_handle *h, int32_t left, int32_t right, int32_t out_dim, int32_t n_xf, const float *A,
+                               const float *b);
+int mfx_sessions_clear_transform(mfx_handle *h);
+int mfx_sessions_select_transform(mfx_handle *h, int32_t session, int32_t xf);
+/* out_dim while a session transform is set, else mfx_get_output_data_width */
+int mfx_sessions_output_width(const mfx_handle *h);
 
 /* Page-locked host memory for the caller's PCM / feature buffers (mfx_batch_run_host and the streaming entries DMA
  * straight from / to such buffers; pageable ones go through the handle's staging).  NULL on failure. */
@@ -713,6 +762,20 @@ int mfx_host_mel_lane_plan(int32_t lanes, int32_t num_banks, int32_t fft_size, c
 /* Operands of the DCT on the matrix pipe, [tile][K step][lane]; returns their count.  Test / inspection aid. */
 int64_t mfx_host_dct_mfma_operands(int32_t num_banks, int32_t dct_len, const float *matrix, float *out, int64_t out_cap,
                                    int32_t *tiles, int32_t *ksteps);
+/* One push of one session under a session transform, exactly as the planner derives it (mfx_host_session_step's companion).
+ * state = {Ey, Ex}: finished rows y, transformed rows delivered; n_y: the rows y this push completes (mfx_host_session_step's
+ * result).  Returns the rows delivered and advances the state ({0, 0} after a final push).  carry_rows: rows y carried in from
+ * the previous slot (<= left + right); the push's slot holds carry_rows + n_y rows.  win = {src_row0, lo, hi}: output row r
+ * reads slot rows src_row0 + clamp(r - left + c, lo, hi), c <= left + right (k_splice_affine's convention: src_row0 is the
+ * slot row of y[Ex_old], lo is negative by the carried rows in front of it).  MFX_ERR_ARG on a bad argument. */
+int32_t mfx_host_session_xform_step(int32_t left, int32_t right, int64_t state[2], int32_t n_y, int32_t final_flag,
+                                    int32_t *carry_rows, int32_t win[3]);
+/* UNSTABLE test / inspection aid: the work list of k_sess_xform for pieces that deliver n_out[i] rows with transform xf[i], at
+ * G = 4, 2 or 1 row groups per block.  groups [.][3] = (piece, first row, rows <= 16), sorted by transform; blocks [.][3] =
+ * (first group, groups <= G, transform).  Returns the number of groups, *n_blocks the number of blocks; either array may be
+ * NULL (count only), MFX_ERR_ARG when one is too small. */
+int32_t mfx_host_sess_xform_groups(int32_t n, const int32_t *n_out, const int32_t *xf, int32_t G, int32_t *groups,
+                                   int32_t groups_cap, int32_t *blocks, int32_t blocks_cap, int32_t *n_blocks);
 /* PLP tables as uploaded (PLP): equal-loudness weights eql [num_banks] at the (warped) filter centres, and the
  * cosine basis of the autocorrelation idft [lpc_order + 1][num_banks + 2] (r_i = sum_m idft[i][m] A_m).  Neither depends on
  * fft_size; it is taken for symmetry with mfx_host_mel_table */
