@@ -9,12 +9,7 @@ using namespace mfx;
 
 void fill_xform(const mfx_handle *h, XformParams &p)
 {
-    p = XformParams{};
-    p.width = batch_y_width(h);
-    p.left = h->batch.xf.left;
-    p.right = h->batch.xf.right;
-    p.out_dim = h->batch.xf.out;
-    p.valu = (h->cfg.engine & MFX_ENGINE_XFORM_VALU) ? 1 : 0;
+    fill_xform_shape(h, p, batch_y_width(h), h->batch.xf.left, h->batch.xf.right, h->batch.xf.out);
 }
 
 namespace {
@@ -336,18 +331,15 @@ int run_tail(mfx_handle *h, const RunMode &m, int u0, int u1)
         if (rc != MFX_OK) return rc;
     }
     if (h->l1 > 0 && !m.fuse) {
-        DeltaParams dp{};
+        DeltaParams dp;
+        fill_delta(h, dp);
         // (the online normaliser in force: behind it the deltas work on d_out as always, ahead of it on its scratch)
         float *rows = B.on.on && h->cfg.norm_after_dyn ? m.d_pre : m.d_out;
         dp.src = m.via_scratch ? B.d_static16[m.sb].p : rows;
         dp.src_pitch = m.via_scratch ? 16 : h->width;
         dp.out = rows;
-        dp.out_pitch = h->width;
         dp.segs = B.d_segs.p + u0;
         dp.n_segs = u1 - u0;
-        dp.cols = h->cols;
-        dp.l1 = h->l1;
-        dp.l2 = h->l2;
         dp.tiles_per_seg_max = B.tiles_max;
         HIP_TRY(h, launch_delta(dp, m.tail_stream));
     }
@@ -367,9 +359,7 @@ int run_tail(mfx_handle *h, const RunMode &m, int u0, int u1)
         XformParams xp;
         fill_xform(h, xp);
         xp.src = m.d_y;
-        xp.src_pitch = batch_y_width(h);
         xp.out = m.d_last;
-        xp.out_pitch = B.xf.out;
         xp.segs = B.d_segs.p + u0;
         xp.n_segs = u1 - u0;
         xp.seg_xf = B.xf.d_idx.p ? B.xf.d_idx.p + u0 : nullptr;

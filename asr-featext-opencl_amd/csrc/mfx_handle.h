@@ -7,7 +7,7 @@
 //   mfx_batch_attach.cpp what is attached to a plan: warp factors, transform, speakers, VAD, online normaliser, pitch track,
 //                        pitch features (owns `batch.va`, `.xf`, `.spk`, `.vad`, `.on`, `.pt`, `.pf`)
 //   mfx_batch.cpp        the batch runner, device and host entries, overlap   (owns `batch.ov` and `batch.host`)
-//   mfx_sessions_host.cpp the session entries: many live streams per push       (owns `sess`)
+//   mfx_sessions_host.cpp the session entries: many live streams per push       (owns `sess`; the pending push is `sess.push`)
 #pragma once
 #include "../../include/mfx.h"
 
@@ -75,9 +75,12 @@ struct PinnedBuf {
     PinnedBuf() = default;
     PinnedBuf(const PinnedBuf &) = delete;
     PinnedBuf &operator=(const PinnedBuf &) = delete;
-    ~PinnedBuf()
+    ~PinnedBuf() { release(); }
+    void release()
     {
         if (p) (void)hipHostFree(p);
+        p = nullptr;
+        n = 0;
     }
     // fewer than `need` elements: wait for `stream` (work on it may still use the old block), then replace the block by
     // one of `want` (>= need) elements
@@ -85,9 +88,7 @@ struct PinnedBuf {
     {
         if (n >= need) return hipSuccess;
         if (hipError_t e = hipStreamSynchronize(stream); e != hipSuccess) return e;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        n = 0;
+        release();
         if (hipError_t e = hipHostMalloc((void **)&p, want * sizeof(T), hipHostMallocDefault); e != hipSuccess) {
             p = nullptr;
             return e;
@@ -359,7 +360,7 @@ struct FuseState {
     DevBuf<mfx::DeltaTile> d_tiles;
 };
 
-// session entries (mfx_sessions_*): per-session carry state in two slot arrays, the pending push: mfx_sessions_host.cpp
+// session entries (mfx_sessions_*): per-session carry state in two slot arrays, the pending push (`push`): mfx_sessions_host.cpp
 struct SessState {
     int32_t n = 0, max_push = 0;         // sessions; samples per channel one push may bring a session (n == 0: not created)
     int64_t pcm_stride = 0;              // samples per channel of a slot's PCM part (a multiple of 8)
@@ -369,7 +370,7 @@ struct SessState {
     DevBuf<float> d_stat;                // [2][n][row_cap][row_floats]
     DevBuf<float> d_slab;                // spectrum rows of the slab path (PLP, long transforms)
     int64_t slab_rows = 0;
-    DevBuf<char> d_desc;                 // one push: descriptors | segments | chunks | row runs
+    DevBuf<char> d_desc;                 // one push's upload, desc_bytes of it: the parts SessUpload lays out (mfx_sessions_host.cpp)
     PinnedBuf<char> h_stage[2];          // its staging, double buffered
     hipEvent_t ev_stage[2] = {};         // recorded behind the upload that reads h_stage[i]
     bool stage_used[2] = {false, false};
@@ -397,6 +398,7 @@ struct SessState {
         std::vector<double> prior;       // [2][Wn] (empty without a prior)
         DevBuf<double> d_prior, d_state; // [2][Wn]; [n][8][Wn] lead / trail O and I of v and q
         DevBuf<float> d_ring;            // [n][window][Wn] the last `window` raw rows of every session
+        void release() { d_prior.release(), d_state.release(), d_ring.release(); }
     } on;
     // splice + affine transform (mfx_sessions_set_transform: the host-side operands; mfx_sessions_create uploads them and sizes
     // the y slots): while set, the delta stage writes the rows y of a push into the session's current y slot behind the rows
@@ -409,31 +411,50 @@ struct SessState {
         DevBuf<float> d_ops, d_bias;
         DevBuf<float> d_y;               // [2][n][y_cap][width]
         int32_t y_cap = 0;               // rows of a y slot: left + right + frames_max + D
+        void release() { d_ops.release(), d_bias.release(), d_y.release(); }
     } xf;
-    std::vector<mfx::SessionXformStep> p_xsteps; // the pending push's transform steps, by piece
-    std::vector<int32_t> p_xn, p_xxf, p_xorder, p_gpiece, p_gr0, p_grows, p_bg0, p_bng, p_bxf; // the packer's input and output
-    std::vector<int64_t> p_xsrc;         // [pieces] absolute row of y[Ex_old] in d_y
-    std::vector<mfx::SessXfGroup> p_groups;
-    std::vector<mfx::SessXfBlock> p_blocks;
-    std::vector<mfx::Segment> p_xsegs;   // MFX_ENGINE_SESS_XFORM_PLAIN: one segment per delivering piece, and its transform
-    std::vector<int32_t> p_xseg_xf;
-    int p_xtiles_max = 0;
-    std::vector<mfx::OnormSessDesc> p_onorm; // the pending push's rows to normalise
-    // the pending push (mfx_sessions_plan; mfx_sessions_run_* consumes it)
-    bool planned = false;
-    std::vector<int32_t> p_ids;
-    std::vector<int64_t> p_end;          // offsets[i] + lengths[i]: checked against the run's pcm_samples_total
-    std::vector<Live> p_next;            // state of p_ids[i] once the run has queued its launches
+    // the pending push: everything mfx_sessions_plan leaves for mfx_sessions_run_* (which consumes it)
+    struct Piece {                       // one entry of the caller's lists
+        int32_t id = 0;
+        bool fin = false;
+        Live next;                       // state of `id` once the run has queued its launches (id and next: all the commit reads)
+        int64_t off = 0, len = 0;
+        int64_t row = 0;                 // first row of d_out the piece delivers to
+        int64_t xsrc = 0;                // session transform: absolute row of y[Ex_old] in d_y (set where the piece delivers rows)
+        mfx::SessionStep step;
+        mfx::SessionXformStep xstep;     // (session transform only)
+    };
+    struct Push {
+        bool planned = false;
+        std::vector<Piece> pieces;       // in the caller's order
+        std::vector<int32_t> xf_rows, xf_idx; // by piece: rows the transform delivers, its transform (pack_sess_xform_groups' input)
+        // launch-ready, in ascending slots: what SessUpload (mfx_sessions_host.cpp) lays out for the single upload
+        std::vector<mfx::SessDesc> descs;
+        std::vector<mfx::Segment> segs;
+        std::vector<mfx::Chunk> chunks;  // ascending destination rows
+        std::vector<int64_t> runs;       // (first row, rows) of every descriptor's new frames, ascending
+        int32_t run_off[2] = {0, 0};     // the one table's runs: [0, runs / 2)
+        std::vector<mfx::OnormSessDesc> onorm; // rows to normalise
+        std::vector<mfx::SessXfGroup> groups;  // the transform's work list: groups and blocks of k_sess_xform, or under
+        std::vector<mfx::SessXfBlock> blocks;  // MFX_ENGINE_SESS_XFORM_PLAIN one segment per delivering piece and its transform
+        std::vector<mfx::Segment> xsegs;
+        std::vector<int32_t> xseg_xf;
+        int64_t total_rows = 0;
+        int64_t max_end = 0;             // the largest offsets[i] + lengths[i]: checked against the run's pcm_samples_total
+        bool any_new = false;            // a piece brings samples: the run needs d_pcm
+        int tiles_max = 0, xtiles_max = 0;
+        void clear_lists() { descs.clear(), segs.clear(), chunks.clear(), runs.clear(), onorm.clear(), groups.clear(), blocks.clear(), xsegs.clear(), xseg_xf.clear(); }
+    } push;
+    // the planner's scratch (kept so that a plan allocates nothing once warm): ids seen, (slot, piece) keys, the packer's output
     std::vector<uint8_t> p_seen;
-    std::vector<mfx::SessDesc> p_descs;
-    std::vector<mfx::Segment> p_segs;
-    std::vector<mfx::Chunk> p_chunks;    // ascending destination rows
-    std::vector<int64_t> p_runs;         // (first row, rows) of every descriptor's new frames, ascending
-    std::vector<int32_t> p_order;
-    std::vector<mfx::SessionStep> p_steps; // (the planner's work arrays: kept so that a plan allocates nothing once warm)
-    std::vector<int64_t> p_row_of;
-    int64_t p_total_rows = 0;
-    int p_tiles_max = 0;
+    std::vector<int64_t> p_order;
+    std::vector<mfx::SessXfCut> p_cuts;
+    std::vector<mfx::SessXfPack> p_packs;
+    void release() // (what mfx_sessions_create(0, 0) gives back)
+    {
+        d_pcm.release(), d_stat.release(), d_slab.release(), d_desc.release(), d_host_pcm.release(), d_host_out.release();
+        on.release(), xf.release(), h_stage[0].release(), h_stage[1].release();
+    }
 };
 
 // profiling of the dominant kernel
@@ -698,6 +719,22 @@ inline int spk_wn(const mfx_handle *h) { return h->cfg.norm_after_dyn ? h->width
 // message on the handle)
 int check_online_norm(mfx_handle *h, const char *who, int32_t window, int32_t prior_frames, int64_t prior_count, const double *prior_acc);
 void fill_xform(const mfx_handle *h, mfx::XformParams &p);
+// the shape fields XformParams and SessXformParams share, for rows y of `width` floats (pointers and work lists left zero)
+template <class P>
+inline void fill_xform_shape(const mfx_handle *h, P &p, int width, int left, int right, int out_dim)
+{
+    p = P{};
+    p.width = width, p.left = left, p.right = right, p.out_dim = out_dim;
+    p.src_pitch = width, p.out_pitch = out_dim;
+    p.valu = (h->cfg.engine & MFX_ENGINE_XFORM_VALU) ? 1 : 0;
+}
+// the delta stage's shape on this handle: rows of `width` floats out (source, segments and tiles left zero)
+inline void fill_delta(const mfx_handle *h, mfx::DeltaParams &dp)
+{
+    dp = mfx::DeltaParams{};
+    dp.out_pitch = h->width;
+    dp.cols = h->cols, dp.l1 = h->l1, dp.l2 = h->l2;
+}
 // row width of the session entries' output: out_dim while a session transform is set, else `width`
 inline int sess_out_width(const mfx_handle *h) { return h->sess.xf.set ? h->sess.xf.out : h->width; }
 // the VAD's row scratch at the current output width (mfx_batch_attach.cpp; a no-op unless a selecting VAD is in force)

@@ -411,16 +411,13 @@ int apply_impl(mfx_handle *h, const float *alphas, int n_alpha)
             h->st.rows_in_stage = true;
         }
     }
-    DeltaParams dp{};
+    DeltaParams dp;
+    fill_delta(h, dp);
     dp.src = d_src;
     dp.src_pitch = h->cols;
     dp.out = rows_out;
-    dp.out_pitch = h->width;
     dp.segs = segs_out;
     dp.n_segs = n_tab;
-    dp.cols = h->cols;
-    dp.l1 = h->l1;
-    dp.l2 = h->l2;
     dp.tiles_per_seg_max = (wc + 63) / 64;
     dp.inline_seg = sweep ? 0 : 1;
     dp.seg0 = sd;

@@ -64,24 +64,17 @@ int32_t session_xform_step(int left, int right, int64_t &Ey, int64_t &Ex, int32_
     return st.n_out;
 }
 
-void pack_sess_xform_groups(const int32_t *n_out, const int32_t *xf, int n, int G, std::vector<int32_t> &order, std::vector<int32_t> &group_piece,
-                            std::vector<int32_t> &group_r0, std::vector<int32_t> &group_rows, std::vector<int32_t> &block_g0,
-                            std::vector<int32_t> &block_ng, std::vector<int32_t> &block_xf)
+void pack_sess_xform_groups(const int32_t *n_out, const int32_t *xf, int n, int G, std::vector<SessXfCut> &groups, std::vector<SessXfPack> &blocks)
 {
-    group_piece.clear(), group_r0.clear(), group_rows.clear(), block_g0.clear(), block_ng.clear(), block_xf.clear();
-    order.clear();
-    for (int i = 0; i < n; ++i)
-        if (n_out[i] > 0) order.push_back(i);
-    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return xf[a] < xf[b]; });
-    for (int32_t i : order)
-        for (int32_t r0 = 0; r0 < n_out[i]; r0 += 16) {
-            const int32_t g = (int32_t)group_piece.size();
-            if (block_g0.empty() || block_xf.back() != xf[i] || block_ng.back() == G) {
-                block_g0.push_back(g), block_ng.push_back(0), block_xf.push_back(xf[i]);
-            }
-            ++block_ng.back();
-            group_piece.push_back(i), group_r0.push_back(r0), group_rows.push_back(std::min(16, n_out[i] - r0));
-        }
+    groups.clear(), blocks.clear();
+    for (int32_t i = 0; i < n; ++i)
+        for (int32_t r0 = 0; r0 < n_out[i]; r0 += 16) groups.push_back(SessXfCut{i, r0, std::min(16, n_out[i] - r0)});
+    std::stable_sort(groups.begin(), groups.end(), [&](const SessXfCut &a, const SessXfCut &b) { return xf[a.piece] < xf[b.piece]; });
+    for (int32_t g = 0; g < (int32_t)groups.size(); ++g) {
+        const int32_t x = xf[groups[g].piece];
+        if (blocks.empty() || blocks.back().xf != x || blocks.back().ng == G) blocks.push_back(SessXfPack{g, 0, x});
+        ++blocks.back().ng;
+    }
 }
 
 int estimated_window_count_f32(int samples, int window_size, int shift)

@@ -48,12 +48,14 @@ int32_t session_xform_step(int left, int right, int64_t &Ey, int64_t &Ex, int32_
 
 // The work list of k_sess_xform for one push: piece i delivers n_out[i] rows with transform xf[i].  Every piece is cut into
 // row groups of at most 16 rows; the groups are sorted by transform (stable: pieces keep their order inside a transform) and
-// packed into blocks of at most G groups of one transform.  group_piece / group_r0 / group_rows: the groups; block_g0 /
-// block_ng / block_xf: the blocks; order: work space (the delivering pieces by transform), the caller's so that a warm planner
-// allocates nothing.
-void pack_sess_xform_groups(const int32_t *n_out, const int32_t *xf, int n, int G, std::vector<int32_t> &order, std::vector<int32_t> &group_piece,
-                            std::vector<int32_t> &group_r0, std::vector<int32_t> &group_rows, std::vector<int32_t> &block_g0,
-                            std::vector<int32_t> &block_ng, std::vector<int32_t> &block_xf);
+// packed into blocks of at most G consecutive groups of one transform.
+struct SessXfCut {
+    int32_t piece, r0, rows; // the group: rows [r0, r0 + rows) of the piece
+};
+struct SessXfPack {
+    int32_t g0, ng, xf;      // the block: groups [g0, g0 + ng), their transform
+};
+void pack_sess_xform_groups(const int32_t *n_out, const int32_t *xf, int n, int G, std::vector<SessXfCut> &groups, std::vector<SessXfPack> &blocks);
 
 // The reference's float32 version, bit-for-bit (used by the streaming state machine).
 int estimated_window_count_f32(int samples, int window_size, int shift);

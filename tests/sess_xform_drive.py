@@ -11,11 +11,14 @@ CONFIGS, PATTERNS, MAX_PUSH = OD.CONFIGS, OD.PATTERNS, OD.MAX_PUSH
 make, utterances, batch_rows, compare, D_of = OD.make, OD.utterances, OD.batch_rows, OD.compare, OD.D_of
 
 
-def drive(m, utts, n_sessions, cut, seed, right, odd_offsets=False, subset=False, host=False, place=None, xf_of=None, on_tick=None):
+def drive(m, utts, n_sessions, cut, seed, right, odd_offsets=False, subset=False, host=False, place=None, xf_of=None, on_tick=None,
+          shuffle=False):
     """Feed the utterances through n_sessions sessions (an id is reused for the next utterance on the push after its final
     one; with xf_of the fresh session is given transform xf_of[u] first); returns the rows every utterance delivered, in
     order, and checks the plan's counts and mfx_sessions_delivered against the transform's delivery rule.
-    place(total_rows, width): an OutPlacement-like object to run into (its check() is called after every push)."""
+    place(total_rows, width): an OutPlacement-like object to run into (its check() is called after every push).
+    shuffle: the pieces of every push in a random order of ids (the planner's caller order then differs from its slot order
+    and from the packer's)."""
     import torch
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(seed)
@@ -33,6 +36,8 @@ def drive(m, utts, n_sessions, cut, seed, right, odd_offsets=False, subset=False
         if subset and len(active) > 1:                         # a changing subset of the open sessions
             keep = [s for s in active if (s + tick) % 3 != 0]
             active = keep or active[:1]
+        if shuffle:
+            active = [active[k] for k in rng.permutation(len(active))]
         ids, offs, lens, fins, parts, pos = [], [], [], [], [], 0
         for sid in active:
             u, fed, _ = cur[sid]

@@ -189,6 +189,24 @@ def test_per_session_transforms_against_utt_xf(pkg):
         m.close()
 
 
+@pytest.mark.parametrize("engine", (0, PLAIN), ids=("packed", "plain"))
+def test_shuffled_pieces_three_transforms_behind_the_online_normaliser(pkg, engine):
+    """The pieces of every push in a random order of ids, over a changing subset of 5 sessions, with empty pushes and flushes:
+    caller order, slot order and the packer's order (sorted by transform) all differ.  Three transforms dealt by utterance,
+    +2 / -3 -> 24, the online normaliser behind the deltas; the rows are still the twin's, bit for bit."""
+    kw, A, b = shape(pkg, "c1", 2, 3, 24, n_xf=3)
+    utts = utts_of("c1")
+    utt_xf = [u % 3 for u in range(len(utts))]
+    want = want_rows(pkg, "c1-2-3-24-x3-onorm-cvn", kw, utts, A, b, 2, 3, utt_xf=utt_xf, norm=2, nad=True, onorm=32)
+    assert [len(w) for w in want] == FRAMES + [40]
+    m = session_handle(pkg, kw, A, b, 2, 3, 5, norm=2, nad=True, onorm=32, engine=engine)
+    try:
+        got = SD.drive(m, utts, 5, SD.OD.cut_random_with_empty, 23, 3, subset=True, shuffle=True, xf_of=utt_xf)
+        SD.compare("c1", got, want, "xform, shuffled pieces, %s" % ("plain" if engine else "packed"))
+    finally:
+        m.close()
+
+
 # ---- 4. behind the online normaliser ------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("nad", (True, False), ids=("after", "before"))

@@ -44,22 +44,24 @@ int main()
     int np = 0;
     for (int G : {1, 2, 4})
         for (int n : {0, 1, 5, 13, 1000}) {
-            std::vector<int32_t> n_out(n), xf(n), order, gp, gr0, gn, bg0, bng, bxf;
+            std::vector<int32_t> n_out(n), xf(n);
+            std::vector<mfx::SessXfCut> gp;
+            std::vector<mfx::SessXfPack> bl;
             for (int i = 0; i < n; ++i) n_out[i] = (i * 7) % 41 == 3 ? 0 : (i * 13) % 50, xf[i] = (i * 5) % 3;
-            mfx::pack_sess_xform_groups(n_out.data(), xf.data(), n, G, order, gp, gr0, gn, bg0, bng, bxf);
+            mfx::pack_sess_xform_groups(n_out.data(), xf.data(), n, G, gp, bl);
             std::vector<int32_t> seen(n, 0);
-            for (size_t g = 0; g < gp.size(); ++g) {
-                if (gn[g] < 1 || gn[g] > 16 || gr0[g] + gn[g] > n_out[gp[g]]) return 1;
-                seen[gp[g]] += gn[g];
+            for (const mfx::SessXfCut &g : gp) {
+                if (g.rows < 1 || g.rows > 16 || g.r0 + g.rows > n_out[g.piece]) return 1;
+                seen[g.piece] += g.rows;
             }
             for (int i = 0; i < n; ++i)
                 if (seen[i] != n_out[i]) return 1;
             size_t next = 0;
-            for (size_t k = 0; k < bg0.size(); ++k) {
-                if ((size_t)bg0[k] != next || bng[k] < 1 || bng[k] > G) return 1;
-                for (int g = bg0[k]; g < bg0[k] + bng[k]; ++g)
-                    if (xf[gp[g]] != bxf[k]) return 1;
-                next += bng[k];
+            for (const mfx::SessXfPack &k : bl) {
+                if ((size_t)k.g0 != next || k.ng < 1 || k.ng > G) return 1;
+                for (int g = k.g0; g < k.g0 + k.ng; ++g)
+                    if (xf[gp[g].piece] != k.xf) return 1;
+                next += k.ng;
             }
             if (next != gp.size()) return 1;
             ++np;

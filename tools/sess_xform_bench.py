@@ -1,5 +1,5 @@
 """Dev aid: what the session transform (mfx_sessions_set_transform) adds to a push, median device time per push between two
-events on the handle's stream, all cases in one process:
+events on the handle's stream (and the host's time per push around the plan + run pair), all cases in one process:
   (a) C2 shape, 1000 sessions, pushes of 100 ms, no transform -- three times; the spread of the three is the noise
   (b) the same with +-4 -> 40 (k_sess_xform, row groups of different sessions packed into one block)
   (c) the same under MFX_ENGINE_SESS_XFORM_PLAIN (k_splice_affine, one segment per session)
@@ -10,6 +10,7 @@ Usage: sess_xform_bench.py [pushes] [sessions of (a)-(d)] [sessions of (e)]"""
 import json
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -53,20 +54,23 @@ def case(n, nb, nc, dyn, xform=None, n_xf=1, engine=0):
     lens = np.full(n, PUSH, np.int64)
     for rep in range(2):                                      # (the first pass warms everything up)
         ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(PUSHES)]
-        rows = 0
+        host, rows = 0.0, 0
         torch.cuda.synchronize()
         for k in range(PUSHES):
             fin = np.full(n, int(k == PUSHES - 1), np.int32)
+            t0 = time.perf_counter()
             _, _, total = m.sessions_plan(ids, base + k * PUSH, lens, fin)
             ev[k][0].record()
             m.sessions_run_device(d_pcm.data_ptr(), n * LEN, d_out.data_ptr())
             ev[k][1].record()
+            host += time.perf_counter() - t0
             rows += total
         torch.cuda.synchronize()
         us = sorted(1e3 * a.elapsed_time(b) for a, b in ev)
     assert rows == n * m.batch_frames(LEN), (rows, n * m.batch_frames(LEN))
     m.close()
-    return dict(device_us_per_push_median=us[len(us) // 2], device_us_per_push_min=us[0], rows=rows, row_width=width)
+    return dict(device_us_per_push_median=us[len(us) // 2], device_us_per_push_min=us[0],
+                host_us_per_push_plan_and_run=1e6 * host / PUSHES, rows=rows, row_width=width)
 
 
 res = dict(pushes=PUSHES, push_samples=PUSH, sessions_c2=N_C2, sessions_big=N_BIG)

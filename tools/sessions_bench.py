@@ -70,7 +70,7 @@ res["sessions"] = dict(device_us_per_push_median=dev_us[len(dev_us) // 2], devic
 m.close()
 
 # ---- comparator 1: one streaming handle, the same utterances one call sequence each (tools/stream_small_bench.py)
-m = handle(LEN)
+m = handle(LEN + S)                                           # (a handle's block limit is rounded down to whole frames)
 L, hnd = m._L, m._h
 out = np.zeros((T + 64) * width, np.float32)
 op = C.cast(out.ctypes.data, C.POINTER(C.c_float))
