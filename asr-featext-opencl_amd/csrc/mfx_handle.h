@@ -388,6 +388,10 @@ struct SessState {
         // row 0 of the y slot, the session's transform (kept across final pushes and mfx_sessions_reset)
         int64_t Ex = 0, y0 = 0;
         int32_t xf = 0;
+        // session rates (n above is then J, the converted samples): input samples received, the session's rate (kept across
+        // final pushes and mfx_sessions_reset), which of the two carry slot arrays holds its input tail
+        int64_t n_in = 0;
+        int32_t rate = 0, rs_parity = 0;
     };
     std::vector<Live> live;
     // online normaliser (mfx_sessions_set_online_norm: parameters only; mfx_sessions_create sizes the state)
@@ -413,12 +417,36 @@ struct SessState {
         int32_t y_cap = 0;               // rows of a y slot: left + right + frames_max + D
         void release() { d_ops.release(), d_bias.release(), d_y.release(); }
     } xf;
+    // sample-rate conversion in front of a push (mfx_sessions_set_rates: the host-side tables; mfx_sessions_create uploads them
+    // and sizes the carry slots and the scratch): while set, lengths and offsets of a push are in input-rate samples, and a
+    // push with a piece to convert runs k_sess_resample first: every piece's converted samples go to d_conv (pieces in the
+    // caller's order, each on an even sample), which k_sess_gather then reads in the place of the caller's array
+    struct Rates {
+        bool set = false;
+        std::vector<int32_t> hz;
+        std::vector<mfx::ResRate> rates; // one per rate; tile_out == 0: pass-through (the rate is sample_rate)
+        std::vector<float> taps;
+        int32_t taps_floats = 0, x_floats = 8, out_elems = 2; // LDS parts of the launch: maxima over the rates
+        int32_t carry_cap = 0;           // samples per channel of a carry slot: max over rates (2 Wh + M div L + 2), a multiple of 8
+        int32_t tile_min = 0;            // the smallest tile_out (kResCopyTile for a pass-through rate)
+        int64_t conv_stride = 0;         // samples per channel one piece has in the scratch (max_conv rounded up to even)
+        DevBuf<float> d_taps;
+        DevBuf<mfx::ResRate> d_rates;
+        DevBuf<int16_t> d_carry;         // [2][n][carry_cap * channels]
+        DevBuf<int16_t> d_conv;          // [n][conv_stride * channels] (+ slack for whole-word reads)
+        std::vector<int64_t> last_off, last_len; // the pieces of the last push that converted, in the scratch
+        bool last_valid = false;
+        void release() { d_taps.release(), d_rates.release(), d_carry.release(), d_conv.release(); }
+    } rs;
+    int32_t max_conv = 0;                // samples per channel the front end can receive from one piece (max_push without rates)
     // the pending push: everything mfx_sessions_plan leaves for mfx_sessions_run_* (which consumes it)
     struct Piece {                       // one entry of the caller's lists
         int32_t id = 0;
         bool fin = false;
         Live next;                       // state of `id` once the run has queued its launches (id and next: all the commit reads)
-        int64_t off = 0, len = 0;
+        int64_t off = 0, len = 0;        // what the front end sees: the caller's piece, or the converted piece in the scratch
+        int64_t n_in_next = 0;           // session rates: input samples once the push has run, and the carry parity
+        int32_t rs_parity_next = 0;
         int64_t row = 0;                 // first row of d_out the piece delivers to
         int64_t xsrc = 0;                // session transform: absolute row of y[Ex_old] in d_y (set where the piece delivers rows)
         mfx::SessionStep step;
@@ -439,11 +467,15 @@ struct SessState {
         std::vector<mfx::SessXfBlock> blocks;  // MFX_ENGINE_SESS_XFORM_PLAIN one segment per delivering piece and its transform
         std::vector<mfx::Segment> xsegs;
         std::vector<int32_t> xseg_xf;
+        std::vector<mfx::SessResTile> rtiles; // session rates: the tiles of k_sess_resample (empty: nothing to convert or carry)
+        std::vector<int64_t> c_off, c_len;    // the pieces after conversion (the caller's own lists when the push converts nothing)
+        bool convert = false;            // the pieces lie in the scratch
+        bool need_pcm = false;           // a piece brings input samples: the run needs d_pcm
         int64_t total_rows = 0;
         int64_t max_end = 0;             // the largest offsets[i] + lengths[i]: checked against the run's pcm_samples_total
         bool any_new = false;            // a piece brings samples: the run needs d_pcm
         int tiles_max = 0, xtiles_max = 0;
-        void clear_lists() { descs.clear(), segs.clear(), chunks.clear(), runs.clear(), onorm.clear(), groups.clear(), blocks.clear(), xsegs.clear(), xseg_xf.clear(); }
+        void clear_lists() { descs.clear(), segs.clear(), chunks.clear(), runs.clear(), onorm.clear(), groups.clear(), blocks.clear(), xsegs.clear(), xseg_xf.clear(), rtiles.clear(); }
     } push;
     // the planner's scratch (kept so that a plan allocates nothing once warm): ids seen, (slot, piece) keys, the packer's output
     std::vector<uint8_t> p_seen;
@@ -453,7 +485,7 @@ struct SessState {
     void release() // (what mfx_sessions_create(0, 0) gives back)
     {
         d_pcm.release(), d_stat.release(), d_slab.release(), d_desc.release(), d_host_pcm.release(), d_host_out.release();
-        on.release(), xf.release(), h_stage[0].release(), h_stage[1].release();
+        on.release(), xf.release(), rs.release(), h_stage[0].release(), h_stage[1].release();
     }
 };
 

@@ -1,4 +1,4 @@
-// mfx_kernels.h -- launch interface of the gfx950 kernels (implemented in mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip, mfx_plp.hip, mfx_traps.hip, mfx_xform.hip, mfx_sess_xform.hip, mfx_sessions.hip, mfx_resample.hip, mfx_speakers.hip, mfx_vad.hip, mfx_onorm.hip, mfx_stft.hip, mfx_pitch.hip, mfx_pitchfeat.hip: one translation unit per kernel family).
+// mfx_kernels.h -- launch interface of the gfx950 kernels (implemented in mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip, mfx_plp.hip, mfx_traps.hip, mfx_xform.hip, mfx_sess_xform.hip, mfx_sess_resample.hip, mfx_sessions.hip, mfx_resample.hip, mfx_speakers.hip, mfx_vad.hip, mfx_onorm.hip, mfx_stft.hip, mfx_pitch.hip, mfx_pitchfeat.hip: one translation unit per kernel family).
 //
 // Kernel inventory and the reference stage each one replaces:
 //   spectrum512 / fused512   segmenter.cl kernelSegmentWindow + AppleFFT fft0 + mfcc.cl kernelTranspose
@@ -12,6 +12,8 @@
 //                            (no reference analogue: the reference re-frames 2 D frames of context per block, segmentercpu.cpp:69-73)
 //   resample                 per-utterance sample-rate conversion of the batch entries' PCM (no reference analogue: the reference takes
 //                            its files at the one rate its model was trained at)
+//   sess_resample            per-session sample-rate conversion in front of a push of the session entries: the chain of resample on
+//                            an input span staged from the session's carried input tail and the caller's array (no reference analogue)
 //   vad_*                    energy voice-activity decision + voiced-frame selection of finished rows (no reference analogue: the
 //                            reference hands every frame to its consumer)
 //   pitch_*                  pitch track beside the rows of a batch run: NCCF of the PCM + Viterbi path (no reference analogue)
@@ -354,6 +356,34 @@ struct ResampleParams {
 };
 constexpr int kResCopyTile = 4096; // samples per channel of a tile of a same-rate utterance
 
+// k_sess_resample (mfx_sess_resample.hip): the converter in front of a push of the session entries ("Session
+// sample-rate conversion").  One SessResTile per run of at most tile_out outputs of ONE piece; positions are samples per
+// channel of the session's STREAM.  The piece's input is stream samples [c0, n_new): [c0, n_old) in the session's previous
+// carry slot, [n_old, n_new) in the caller's array; everything outside is zero (after n_new only a final push reads).  The
+// piece's first tile also writes the new carry, samples [c1, n_new), to the session's current carry slot (move != 0).
+struct SessResTile {
+    int64_t in_off;     // caller's array: the piece's first new sample (per channel), any parity
+    int64_t out_off;    // scratch: the piece's first converted sample (per channel), even
+    int64_t carry_src;  // carry slots: first ELEMENT of the previous slot (a multiple of 8: 16-byte words)
+    int64_t carry_dst;  // first element of the current slot
+    int64_t c0, n_old, n_new, c1;
+    int64_t j_old, j_new; // the piece converts outputs [j_old, j_new)
+    int64_t j0;         // first output of the tile (j_old plus a multiple of the rate's tile_out)
+    int32_t rate;       // index into SessResampleParams::rates; -1: pass-through, the new samples are copied
+    int32_t move;       // nonzero: the tile writes the carry
+};
+struct SessResampleParams {
+    const int16_t *pcm; // the caller's array, 4-byte aligned (may be null when no piece brings samples)
+    int16_t *out;       // the scratch of converted pieces
+    int16_t *carry;     // both carry slot arrays (read: previous slots, written: current slots)
+    const SessResTile *tiles;
+    const ResRate *rates;
+    const float *taps;
+    int32_t n_tiles;
+    int32_t channels;
+    int32_t taps_floats, x_floats, out_elems; // the LDS parts, as in ResampleParams
+};
+
 struct DeltaParams {
     const float *src;      // static features, [rows][src_pitch]
     int32_t src_pitch;
@@ -613,6 +643,8 @@ void resample_geometry(int channels, ResRate &r);
 int resample_span_floats(const ResRate &r);
 size_t resample_lds_bytes(const ResampleParams &p);
 hipError_t launch_resample(const ResampleParams &p, hipStream_t stream);
+// k_sess_resample: the same LDS sum, and the launch
+hipError_t launch_sess_resample(const SessResampleParams &p, hipStream_t stream);
 // work items of one descriptor: 16-byte words of PCM, then 16-byte words (or single floats) of static rows, then the floats
 // of the carried rows y
 int sess_gather_items(const SessDesc &d, int stat_pitch, int cols, int y_width = 0);

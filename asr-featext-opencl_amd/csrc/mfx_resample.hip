@@ -25,28 +25,19 @@
 //      allows); the half word behind an odd utterance length is written as zero (the scratch pads every utterance to an even
 //      length).
 // Tiles of utterances already at the output rate (rate = -1) copy their samples, word by word.
+// The chain itself (convert_tile) is in mfx_resample_dev.h, shared with k_sess_resample.
 #include "mfx_kernels.h"
 
 #include <hip/hip_runtime.h>
 
 #include "mfx_launch.h"
+#include "mfx_resample_dev.h"
 
 #include <algorithm>
-#include <type_traits>
 
 namespace mfx {
 
 namespace {
-
-typedef float rs_f4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float lo16(uint32_t w) { return (float)(int16_t)(w & 0xffffu); }
-__device__ __forceinline__ float hi16(uint32_t w) { return (float)((int32_t)w >> 16); }
-
-__device__ __forceinline__ int16_t to_pcm(float acc)
-{
-    return (int16_t)(int)fminf(fmaxf(rintf(acc), -32768.f), 32767.f);
-}
 
 // a same-rate utterance: samples [j0, j0 + n) of it, word by word (two words and a 2-byte shift when the source is on an
 // odd element)
@@ -72,56 +63,6 @@ __device__ __forceinline__ void copy_tile(const ResampleParams &p, const ResTile
         }
         dst[i] = v;
     }
-}
-
-template <int CH, int R, bool LDS_TAPS>
-__device__ __forceinline__ void convert_items(const ResRate &r, const ResTile &t, const float *taps, int tap_stride, const float *s_x,
-                                              int xf, int16_t *s_out, int nout, int64_t base_n)
-{
-    // (LDS_TAPS: the table pointer keeps its LDS address space through the call, so the tap reads are ds_read, not flat loads)
-    using TapPtr = typename std::conditional<LDS_TAPS, const __attribute__((address_space(3))) float *, const float *>::type;
-    const int NI = r.items, P = r.P;
-    const int step = (int)(((int64_t)NI * r.M) / r.L); // input samples between the same-phase outputs of an item (exact for R > 1)
-    for (int w = threadIdx.x; w < NI && w < nout; w += 256) {
-        const int64_t jm = (t.j0 + w) * (int64_t)r.M;
-        const int64_t n = jm / r.L;
-        const int phi = (int)(jm - n * r.L);
-        const TapPtr h = (TapPtr)taps + phi * tap_stride;
-        const int xb0 = (int)(n - r.Wh + 1 - base_n);
-        const float *xp[R];
-        float acc[CH][R];
-#pragma unroll
-        for (int q = 0; q < R; ++q) {
-            xp[q] = s_x + (w + q * NI < nout ? xb0 + q * step : 0);
-#pragma unroll
-            for (int c = 0; c < CH; ++c) acc[c][q] = 0.f;
-        }
-#pragma unroll 4
-        for (int k = 0; k < P; ++k) {
-            const float hk = h[k];
-#pragma unroll
-            for (int q = 0; q < R; ++q)
-#pragma unroll
-                for (int c = 0; c < CH; ++c) acc[c][q] = __builtin_fmaf(hk, xp[q][c * xf + k], acc[c][q]);
-        }
-#pragma unroll
-        for (int q = 0; q < R; ++q)
-            if (w + q * NI < nout)
-#pragma unroll
-                for (int c = 0; c < CH; ++c) s_out[(w + q * NI) * CH + c] = to_pcm(acc[c][q]);
-    }
-}
-
-template <int CH, bool LDS_TAPS>
-__device__ __forceinline__ void convert_tile(const ResRate &r, const ResTile &t, const float *taps, int tap_stride, const float *s_x,
-                                             int xf, int16_t *s_out, int nout, int64_t base_n)
-{
-    if (r.R == 4)
-        convert_items<CH, 4, LDS_TAPS>(r, t, taps, tap_stride, s_x, xf, s_out, nout, base_n);
-    else if (r.R == 2)
-        convert_items<CH, 2, LDS_TAPS>(r, t, taps, tap_stride, s_x, xf, s_out, nout, base_n);
-    else
-        convert_items<CH, 1, LDS_TAPS>(r, t, taps, tap_stride, s_x, xf, s_out, nout, base_n);
 }
 
 // LDS: table [taps_floats] | input span [CH][x_floats] | output staging, int16 [out_elems]

@@ -1,7 +1,8 @@
 // mfx_sessions_host.cpp -- the session entries of include/mfx.h: many open streams, each advanced by one chunk of samples per
 // push, all of them in one launch sequence (k_sess_gather -> front end -> delta, with k_onorm_sess before or after the delta
-// while the online normaliser is set, and k_sess_xform as the last launch while a session transform is set).  DESIGN.md
-// section 5, "Session entries" and "Session transform".
+// while the online normaliser is set, k_sess_xform as the last launch while a session transform is set, and k_sess_resample as
+// the first while session rates are set and a piece has something to convert).  DESIGN.md section 5, "Session entries",
+// "Session transform" and "Session sample-rate conversion".
 // This file owns the handle's `sess` part.  It reads the shared geometry and tables and names no field of `st`, `sweep`,
 // `batch` or `fuse`: a push leaves the streaming state and the batch plan, alpha list and transform as they are.
 #include "mfx_handle.h"
@@ -28,8 +29,8 @@ bool norm_before(const mfx_handle *h) { return h->cfg.norm != MFX_NORM_NONE && !
 bool xform_plain(const mfx_handle *h) { return (h->cfg.engine & MFX_ENGINE_SESS_XFORM_PLAIN) != 0; }
 
 // The single upload of a push: descriptors | segments | chunks | row runs | run offsets | the normaliser's descriptors | the
-// transform's groups | its blocks (under MFX_ENGINE_SESS_XFORM_PLAIN: | its segments | their transforms), every part on an
-// 8-byte boundary.  The constructor is the one place that lists them.  mfx_sessions_create calls it on a push whose lists have
+// transform's groups | its blocks (under MFX_ENGINE_SESS_XFORM_PLAIN: | its segments | their transforms) | the converter's
+// tiles (session rates), every part on an 8-byte boundary.  The constructor is the one place that lists them.  mfx_sessions_create calls it on a push whose lists have
 // their largest sizes, without a staging buffer, for the bytes d_desc and the staging need; the run calls it on the planned
 // push: the parts are copied into `stage` and their addresses in `dev` are the members.
 struct SessUpload {
@@ -40,6 +41,7 @@ struct SessUpload {
     const int32_t *run_off = nullptr;
     const OnormSessDesc *onorm = nullptr;
     const void *xa = nullptr, *xb = nullptr;
+    const SessResTile *rtiles = nullptr;
     size_t bytes = 0;
     SessUpload() = default;
     SessUpload(const Push &ps, char *stage, char *dev)
@@ -56,6 +58,8 @@ struct SessUpload {
         onorm = put(ps.onorm);
         const bool plain = !ps.xsegs.empty();
         xa = plain ? (const void *)put(ps.xsegs) : put(ps.groups), xb = plain ? (const void *)put(ps.xseg_xf) : put(ps.blocks);
+        static_assert(sizeof(SessResTile) % 8 == 0, "8-byte parts");
+        rtiles = put(ps.rtiles); // (session rates: the converter's tiles)
     }
 };
 
@@ -83,18 +87,27 @@ extern "C" int mfx_sessions_create(mfx_handle *h, int32_t n_sessions, int32_t ma
     ps.clear_lists();
     ss.live.clear();
     ss.stage_used[0] = ss.stage_used[1] = false;
+    ss.rs.last_valid = false;
     if (n_sessions == 0) {
         ss.release();
-        ss.max_push = 0;
+        ss.max_push = ss.max_conv = 0;
         return MFX_OK;
     }
+    // session rates: the largest converted piece, max over rates ceil((max_push + Wh) L / M) + 1 (a final push converts its
+    // piece and the Wh samples' worth of outputs the open stream held back; this is also the bound of a flush)
+    int64_t max_conv = max_push_samples;
+    if (ss.rs.set)
+        for (const ResRate &r : ss.rs.rates)
+            if (r.tile_out > 0) max_conv = std::max(max_conv, (((int64_t)max_push_samples + r.Wh) * r.L + r.M - 1) / r.M + 1);
+    if (max_conv > (1 << 24)) return fail(h, MFX_ERR_ARG, "max_push_samples too large after conversion to sample_rate");
     int rc = refresh_mel(h); // (decides which front end the shape takes, and with it whether a spectrum slab is needed)
     if (rc != MFX_OK) return rc;
     const int ch = h->channels;
     const size_t n = (size_t)n_sessions;
     ss.max_push = max_push_samples;
-    ss.pcm_stride = ((int64_t)h->W + h->S + max_push_samples + 2 + 7) & ~(int64_t)7;
-    ss.frames_max = max_push_samples / h->S + 1;
+    ss.max_conv = (int32_t)max_conv;
+    ss.pcm_stride = ((int64_t)h->W + h->S + max_conv + 2 + 7) & ~(int64_t)7;
+    ss.frames_max = (int32_t)(max_conv / h->S + 1);
     ss.row_cap = 2 * h->D + ss.frames_max;
     ss.row_floats = (std::max(16, h->width) + 3) & ~3;
     const size_t pcm_elems = (size_t)2 * n_sessions * ss.pcm_stride * ch;
@@ -130,6 +143,20 @@ extern "C" int mfx_sessions_create(mfx_handle *h, int32_t n_sessions, int32_t ma
         HIP_TRY(h, ss.on.d_ring.alloc((size_t)n_sessions * ss.on.window * Wn));
         HIP_TRY(h, h->upload(ss.on.d_prior, ss.on.prior));
         ps.onorm.resize(n);
+    }
+    ss.rs.d_carry.release(), ss.rs.d_conv.release();
+    if (ss.rs.set) { // the session rates: tables, the two carry slot arrays, the scratch of converted pieces; the tile list
+        SessState::Rates &rs = ss.rs;
+        rs.conv_stride = (max_conv + 1) & ~(int64_t)1;
+        HIP_TRY(h, h->upload(rs.d_taps, rs.taps));
+        HIP_TRY(h, h->upload(rs.d_rates, rs.rates));
+        const size_t carry_elems = (size_t)2 * n * rs.carry_cap * ch + 8, conv_elems = n * (size_t)rs.conv_stride * ch + 8;
+        HIP_TRY(h, rs.d_carry.alloc(carry_elems));
+        HIP_TRY(h, hipMemsetAsync(rs.d_carry.p, 0, carry_elems * sizeof(int16_t), h->stream));
+        HIP_TRY(h, rs.d_conv.alloc(conv_elems));
+        HIP_TRY(h, hipMemsetAsync(rs.d_conv.p, 0, conv_elems * sizeof(int16_t), h->stream));
+        ps.rtiles.resize(n * (size_t)(max_conv / rs.tile_min + 2));
+        ps.c_off.reserve(n), ps.c_len.reserve(n), rs.last_off.reserve(n), rs.last_len.reserve(n);
     }
     ss.desc_bytes = SessUpload(ps, nullptr, nullptr).bytes;
     ps.clear_lists();
@@ -221,11 +248,108 @@ extern "C" int mfx_sessions_select_transform(mfx_handle *h, int32_t session, int
     if (ss.n == 0) return not_created(h);
     if (session < 0 || session >= ss.n) return fail(h, MFX_ERR_ARG, "session id outside [0, n_sessions)");
     if (xf < 0 || xf >= ss.xf.n_xf) return fail(h, MFX_ERR_ARG, "transform index outside [0, n_xf)");
-    if (ss.live[session].n != 0)
+    if (ss.live[session].n != 0 || ss.live[session].n_in != 0)
         return fail(h, MFX_ERR_STATE, "mfx_sessions_select_transform: the session has received samples since its last final push or reset");
     ss.live[session].xf = xf;
     ss.push.planned = false; // (a pending push was planned with the earlier choice)
     return MFX_OK;
+}
+
+extern "C" int mfx_sessions_set_rates(mfx_handle *h, int32_t n_rates, const int32_t *rates_hz, int32_t zeros, float rolloff)
+{
+    MFX_DEVICE_ENTRY(h);
+    if (h->sess.n != 0) return sessions_exist(h, "mfx_sessions_set_rates");
+    if (n_rates < 1 || n_rates > 16 || !rates_hz) return fail(h, MFX_ERR_ARG, "n_rates must be 1 .. 16");
+    // (the range first: a float outside int32 must not reach the cast)
+    if (!(h->cfg.sample_rate >= 1000.f && h->cfg.sample_rate <= 768000.f))
+        return fail(h, MFX_ERR_ARG, "sample rates must lie in 1000 .. 768000 Hz");
+    const int32_t out_hz = (int32_t)h->cfg.sample_rate;
+    if ((float)out_hz != h->cfg.sample_rate) return fail(h, MFX_ERR_CONFIG, "mfx_sessions_set_rates: sample_rate is not an integral number of Hz");
+    // the tables and tile geometry of every rate, as mfx_batch_plan_rates builds them (a pass-through rate has none)
+    std::vector<ResRate> rates((size_t)n_rates);
+    std::vector<float> taps;
+    int32_t taps_floats = 0, x_floats = 8, out_elems = 2, carry_cap = 8, tile_min = kResCopyTile;
+    for (int k = 0; k < n_rates; ++k) {
+        ResRate &r = rates[k];
+        r = ResRate{};
+        ResampleShape sh;
+        static const char *const why[] = {"", "sample rates must lie in 1000 .. 768000 Hz", "zeros must be 1 .. 64 (0 = 6)",
+                                          "rolloff must lie in (0, 1] (0 = 0.99)", "L = out_hz / gcd is larger than 4096",
+                                          "the filter has more than 4096 taps per phase", "the tap table L x P is larger than 2^20 floats"};
+        if (const int e = resample_shape(rates_hz[k], out_hz, zeros, rolloff, sh); e != 0) return fail(h, MFX_ERR_ARG, why[-e]);
+        if (rates_hz[k] == out_hz) continue; // (tile_out == 0 marks the pass-through)
+        r.taps_off = (int64_t)taps.size();
+        r.L = sh.L, r.M = sh.M, r.P = sh.P, r.Wh = sh.Wh;
+        taps.resize(taps.size() + (size_t)sh.L * sh.P);
+        build_resample_taps(sh, taps.data() + r.taps_off);
+        resample_geometry(h->channels, r);
+        if (r.in_lds) taps_floats = std::max(taps_floats, (r.L * (r.P + 1) + 3) & ~3);
+        x_floats = std::max(x_floats, resample_span_floats(r));
+        out_elems = std::max(out_elems, r.tile_out * h->channels);
+        carry_cap = std::max(carry_cap, (2 * r.Wh + r.M / r.L + 2 + 7) & ~7);
+        tile_min = std::min(tile_min, r.tile_out);
+    }
+    ResampleParams probe{};
+    probe.channels = h->channels, probe.taps_floats = taps_floats, probe.x_floats = x_floats, probe.out_elems = out_elems;
+    if (resample_lds_bytes(probe) > kLdsCap) return fail(h, MFX_ERR_ARG, "no tile of k_sess_resample fits the LDS for this shape");
+    if (taps.empty()) taps.assign(4, 0.f); // (every rate the output rate: keep the buffer non-null)
+    SessState::Rates &rs = h->sess.rs;
+    rs.hz.assign(rates_hz, rates_hz + n_rates);
+    rs.rates.swap(rates), rs.taps.swap(taps);
+    rs.taps_floats = taps_floats, rs.x_floats = x_floats, rs.out_elems = out_elems, rs.carry_cap = carry_cap, rs.tile_min = tile_min;
+    rs.set = true;
+    return MFX_OK;
+}
+
+extern "C" int mfx_sessions_clear_rates(mfx_handle *h)
+{
+    MFX_DEVICE_ENTRY(h);
+    if (h->sess.n != 0) return sessions_exist(h, "mfx_sessions_clear_rates");
+    SessState::Rates &rs = h->sess.rs;
+    rs.set = false;
+    rs.hz.clear(), rs.rates.clear(), rs.taps.clear();
+    return MFX_OK;
+}
+
+extern "C" int mfx_sessions_select_rate(mfx_handle *h, int32_t session, int32_t rate_index)
+{
+    MFX_DEVICE_ENTRY(h);
+    SessState &ss = h->sess;
+    if (!ss.rs.set) return fail(h, MFX_ERR_STATE, "mfx_sessions_select_rate: no session rates are set");
+    if (ss.n == 0) return not_created(h);
+    if (session < 0 || session >= ss.n) return fail(h, MFX_ERR_ARG, "session id outside [0, n_sessions)");
+    if (rate_index < 0 || rate_index >= (int32_t)ss.rs.rates.size()) return fail(h, MFX_ERR_ARG, "rate index outside [0, n_rates)");
+    if (ss.live[session].n != 0 || ss.live[session].n_in != 0)
+        return fail(h, MFX_ERR_STATE, "mfx_sessions_select_rate: the session has received samples since its last final push or reset");
+    ss.live[session].rate = rate_index;
+    ss.push.planned = false; // (a pending push was planned with the earlier choice)
+    return MFX_OK;
+}
+
+extern "C" int64_t mfx_sessions_converted_read(mfx_handle *h, int16_t *dst, int64_t cap_elems, int64_t *offsets, int64_t *lengths)
+{
+    MFX_DEVICE_ENTRY(h);
+    SessState &ss = h->sess;
+    if (!ss.rs.set) return fail(h, MFX_ERR_STATE, "mfx_sessions_converted_read: no session rates are set");
+    if (ss.n == 0) return not_created(h);
+    if (!ss.rs.last_valid)
+        return fail(h, MFX_ERR_STATE, "mfx_sessions_converted_read: the last push converted nothing (its samples are the caller's own)");
+    const int ch = h->channels;
+    int64_t total = 0;
+    for (const int64_t len : ss.rs.last_len) total += len * ch;
+    if (dst && cap_elems < total) return fail(h, MFX_ERR_BUFFER_TOO_SMALL, "mfx_sessions_converted_read: dst is too small");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    int64_t at = 0;
+    for (size_t i = 0; i < ss.rs.last_len.size(); ++i) {
+        const int64_t len = ss.rs.last_len[i];
+        if (offsets) offsets[i] = at;
+        if (lengths) lengths[i] = len;
+        if (dst && len > 0)
+            HIP_TRY(h, hipMemcpy(dst + at * ch, ss.rs.d_conv.p + ss.rs.last_off[i] * ch, (size_t)len * ch * sizeof(int16_t), hipMemcpyDeviceToHost));
+        at += len;
+    }
+    return total;
 }
 
 extern "C" int mfx_sessions_output_width(const mfx_handle *h)
@@ -243,9 +367,9 @@ extern "C" int mfx_sessions_reset(mfx_handle *h, int32_t session)
     if (session < -1 || session >= ss.n) return fail(h, MFX_ERR_ARG, "session id outside [0, n_sessions)");
     // (the slots themselves need no clearing: a fresh session carries nothing out of them)
     for (int s = session < 0 ? 0 : session; s < (session < 0 ? ss.n : session + 1); ++s) {
-        const int parity = ss.live[s].parity, xf = ss.live[s].xf;
-        ss.live[s] = SessState::Live{}; // (the carried samples, static rows and rows y go with it)
-        ss.live[s].parity = parity, ss.live[s].xf = xf;
+        const int parity = ss.live[s].parity, xf = ss.live[s].xf, rate = ss.live[s].rate, rs_parity = ss.live[s].rs_parity;
+        ss.live[s] = SessState::Live{}; // (the carried samples, static rows, rows y and carried input go with it)
+        ss.live[s].parity = parity, ss.live[s].xf = xf, ss.live[s].rate = rate, ss.live[s].rs_parity = rs_parity;
     }
     ss.push.planned = false; // (a pending push was planned on the state just dropped)
     return MFX_OK;
@@ -261,9 +385,20 @@ extern "C" int64_t mfx_sessions_delivered(const mfx_handle *h, int32_t session)
 
 namespace {
 
-// ---- mfx_sessions_plan: check_pieces -> plan_steps -> plan_slots -> plan_xform_work
+// ---- mfx_sessions_plan: check_pieces -> plan_rates (session rates) -> plan_steps -> plan_slots -> plan_xform_work
 
-// ---- stage 1: the checks.  Nothing behind them fails; every refusal leaves p_seen clean (and no push planned)
+// the samples the front end will have seen of session id once `length` more have arrived (session rates: after conversion)
+int64_t stream_samples(const SessState &ss, int32_t id, int64_t length)
+{
+    const SessState::Live &lv = ss.live[id];
+    if (!ss.rs.set) return lv.n + length;
+    const ResRate &r = ss.rs.rates[lv.rate];
+    const int64_t n = lv.n_in + length;
+    if (r.tile_out == 0) return n;
+    return n > INT64_MAX / r.L ? INT64_MAX : (n * r.L + r.M - 1) / r.M;
+}
+
+// ---- stage 1: the checks (lengths against max_push_samples: in input samples while session rates are set).  Nothing behind them fails; every refusal leaves p_seen clean (and no push planned)
 int check_pieces(mfx_handle *h, int32_t n, const int32_t *ids, const int64_t *offsets, const int64_t *lengths)
 {
     SessState &ss = h->sess;
@@ -281,7 +416,7 @@ int check_pieces(mfx_handle *h, int32_t n, const int32_t *ids, const int64_t *of
             bad = MFX_ERR_ARG, why = "offset + length too large";
         else if (lengths[i] > ss.max_push)
             bad = MFX_ERR_BUFFER_TOO_SMALL, why = "a session's piece is longer than max_push_samples (mfx_sessions_create)";
-        else if (frame_count(ss.live[id].n + lengths[i], h->W, h->S) > 0x7fffffff)
+        else if (frame_count(stream_samples(ss, id, lengths[i]), h->W, h->S) > 0x7fffffff)
             bad = MFX_ERR_ARG, why = "stream too long";
         else
             ss.p_seen[id] = 1;
@@ -291,13 +426,65 @@ int check_pieces(mfx_handle *h, int32_t n, const int32_t *ids, const int64_t *of
     return bad == MFX_OK ? MFX_OK : fail(h, bad, why);
 }
 
-// ---- stage 2 (pass 1, the caller's order): every piece's step and its output rows
+// ---- stage 2, session rates (the caller's order): every piece's input length becomes its converted length
+// (session_resample_step), the converted pieces are laid out in the scratch, each on an even sample, and the converter's tiles
+// are listed.  A push without a piece to convert keeps the caller's own offsets and lengths: it reads the caller's array.
+void plan_rates(mfx_handle *h, int32_t n, const int32_t *ids, const int64_t *offsets, const int64_t *lengths, const int32_t *final_flags)
+{
+    SessState &ss = h->sess;
+    Push &ps = ss.push;
+    const SessState::Rates &rs = ss.rs;
+    const int ch = h->channels;
+    ps.pieces.resize(n);
+    ps.c_off.assign(offsets, offsets + n), ps.c_len.assign(lengths, lengths + n);
+    ps.convert = ps.need_pcm = false;
+    ps.max_end = 0;
+    for (int i = 0; i < n; ++i) {
+        const SessState::Live &cur = ss.live[ids[i]];
+        const bool fin = final_flags && final_flags[i] != 0;
+        if (rs.rates[cur.rate].tile_out > 0 && (lengths[i] > 0 || (fin && cur.n_in > 0))) ps.convert = true;
+        if (lengths[i] > 0) ps.need_pcm = true, ps.max_end = std::max(ps.max_end, offsets[i] + lengths[i]);
+    }
+    int64_t at = 0; // the scratch's next free sample (even)
+    for (int i = 0; i < n; ++i) {
+        const int32_t id = ids[i];
+        const SessState::Live &cur = ss.live[id];
+        const ResRate &r = rs.rates[cur.rate];
+        const bool fin = final_flags && final_flags[i] != 0, pass = r.tile_out == 0;
+        Piece &pc = ps.pieces[i];
+        int64_t N = cur.n_in, J = cur.n;
+        SessionResampleStep st;
+        const int64_t n_conv = session_resample_step(pass ? 1 : r.L, pass ? 1 : r.M, pass ? 0 : r.Wh, N, J, lengths[i], fin, st);
+        pc.n_in_next = N, pc.rs_parity_next = cur.rs_parity;
+        if (!ps.convert) continue;
+        ps.c_off[i] = at, ps.c_len[i] = n_conv;
+        at += (n_conv + 1) & ~(int64_t)1;
+        if (n_conv == 0 && st.carry_out == 0) continue; // (nothing to convert, nothing to carry on)
+        SessResTile t{};
+        t.in_off = offsets[i], t.out_off = ps.c_off[i];
+        t.carry_src = ((int64_t)cur.rs_parity * ss.n + id) * rs.carry_cap * ch;
+        t.carry_dst = ((int64_t)(cur.rs_parity ^ 1) * ss.n + id) * rs.carry_cap * ch;
+        t.c0 = st.c0_old, t.n_old = cur.n_in, t.n_new = cur.n_in + lengths[i], t.c1 = st.c0_new;
+        t.j_old = cur.n, t.j_new = cur.n + n_conv;
+        t.rate = pass ? -1 : cur.rate;
+        t.move = st.carry_out > 0;
+        if (!pass) pc.rs_parity_next = cur.rs_parity ^ 1; // (the carry, or nothing after a final push, is in the other slot)
+        const int64_t step = pass ? kResCopyTile : r.tile_out;
+        t.j0 = t.j_old;
+        do {
+            ps.rtiles.push_back(t);
+            t.move = 0, t.j0 += step;
+        } while (t.j0 < t.j_new);
+    }
+}
+
+// ---- stage 3 (pass 1, the caller's order): every piece's step and its output rows
 void plan_steps(mfx_handle *h, int32_t n, const int32_t *ids, const int64_t *offsets, const int64_t *lengths, const int32_t *final_flags,
                 int64_t *out_rows, int32_t *out_counts)
 {
     SessState &ss = h->sess;
     Push &ps = ss.push;
-    ps.pieces.resize(n);
+    ps.pieces.resize(n); // (plan_rates has done so already, and left its fields)
     if (ss.xf.set) ps.xf_rows.assign(n, 0), ps.xf_idx.assign(n, 0);
     ps.total_rows = ps.max_end = 0;
     for (int i = 0; i < n; ++i) {
@@ -305,6 +492,7 @@ void plan_steps(mfx_handle *h, int32_t n, const int32_t *ids, const int64_t *off
         const SessState::Live &cur = ss.live[ids[i]];
         pc.id = ids[i], pc.off = offsets[i], pc.len = lengths[i], pc.fin = final_flags && final_flags[i] != 0;
         pc.next = cur; // (n, E and Ex advance here; the slot fields follow in plan_slots)
+        if (ss.rs.set) pc.next.n_in = pc.n_in_next, pc.next.rs_parity = pc.rs_parity_next; // (plan_rates has advanced them)
         int32_t n_del = session_step(h->W, h->S, h->D, pc.next.n, pc.next.E, pc.len, pc.fin, pc.step);
         if (ss.xf.set) { // the rows y the push completes are the transform's input; it delivers rows [Ex_old, Ex_new)
             int64_t Ey = cur.E;
@@ -318,7 +506,7 @@ void plan_steps(mfx_handle *h, int32_t n, const int32_t *ids, const int64_t *off
     }
 }
 
-// ---- stage 3 (pass 2, ascending slots: the slab path walks the chunk list in windows of rows): descriptors, chunks, segments,
+// ---- stage 4 (pass 2, ascending slots: the slab path walks the chunk list in windows of rows): descriptors, chunks, segments,
 // the normaliser's rows, the slot fields of every piece's next state
 void plan_slots(mfx_handle *h)
 {
@@ -386,7 +574,7 @@ void plan_slots(mfx_handle *h)
     ps.run_off[0] = 0, ps.run_off[1] = (int32_t)(ps.runs.size() / 2);
 }
 
-// ---- stage 4: the transform's work list, pieces in the caller's order: row groups packed into blocks of one transform, or one
+// ---- stage 5: the transform's work list, pieces in the caller's order: row groups packed into blocks of one transform, or one
 // segment per delivering piece
 void plan_xform_work(mfx_handle *h)
 {
@@ -427,17 +615,26 @@ extern "C" int mfx_sessions_plan(mfx_handle *h, int32_t n, const int32_t *ids, c
     const int rc = check_pieces(h, n, ids, offsets, lengths);
     if (rc != MFX_OK) return rc;
     ss.push.clear_lists(); // (a second plan replaces the first)
-    plan_steps(h, n, ids, offsets, lengths, final_flags, out_rows, out_counts);
+    if (ss.rs.set) { // the stages behind see the converted pieces; the run checks the INPUT array
+        plan_rates(h, n, ids, offsets, lengths, final_flags);
+        const int64_t in_end = ss.push.max_end;
+        plan_steps(h, n, ids, ss.push.c_off.data(), ss.push.c_len.data(), final_flags, out_rows, out_counts);
+        ss.push.max_end = in_end;
+    } else {
+        ss.push.convert = false;
+        plan_steps(h, n, ids, offsets, lengths, final_flags, out_rows, out_counts);
+    }
     if (total_rows) *total_rows = ss.push.total_rows;
     plan_slots(h);
     plan_xform_work(h);
+    if (!ss.rs.set) ss.push.need_pcm = ss.push.any_new;
     ss.push.planned = true;
     return MFX_OK;
 }
 
 namespace {
 
-// ---- mfx_sessions_run_device: check_run -> upload -> run_gather -> run_front -> run_onorm (before) -> run_delta -> run_onorm
+// ---- mfx_sessions_run_device: check_run -> upload -> run_resample (session rates) -> run_gather -> run_front -> run_onorm (before) -> run_delta -> run_onorm
 // (after) -> run_xform -> commit.  What the stages share:
 struct PushRun {
     const int16_t *d_pcm;       // the entry's arguments
@@ -460,7 +657,7 @@ int check_run(mfx_handle *h, PushRun &r)
     if (ss.n == 0) return not_created(h);
     if (!ps.planned) return fail(h, MFX_ERR_STATE, "mfx_sessions_run: no push is planned (mfx_sessions_plan), or it has run already");
     if (!h->have_window) return fail(h, MFX_ERR_STATE, "set_window has not been called");
-    if (r.pcm_total < 0 || (ps.any_new && !r.d_pcm) || (ps.total_rows > 0 && !r.d_out)) return fail(h, MFX_ERR_ARG, "invalid argument");
+    if (r.pcm_total < 0 || (ps.need_pcm && !r.d_pcm) || (ps.total_rows > 0 && !r.d_out)) return fail(h, MFX_ERR_ARG, "invalid argument");
     if (((uintptr_t)r.d_pcm & 3) != 0) return fail(h, MFX_ERR_ARG, "d_pcm must be 4-byte aligned");
     if (ps.max_end > r.pcm_total) return fail(h, MFX_ERR_ARG, "a session's piece extends past the end of the PCM array");
     HIP_TRY(h, hipSetDevice(h->device));
@@ -502,14 +699,32 @@ int upload(mfx_handle *h, PushRun &r)
     return MFX_OK;
 }
 
-// ---- stage 3, gather: carried PCM tail + new samples + carried static rows (+ carried rows y) -> the current slots
+// ---- stage 3, session rates: the pieces' input (carried tail + the caller's array) -> converted pieces in the scratch, the
+// new carry -> the current carry slots
+int run_resample(mfx_handle *h, const PushRun &r)
+{
+    const SessState &ss = h->sess;
+    if (ss.push.rtiles.empty()) return MFX_OK;
+    SessResampleParams rp{};
+    rp.pcm = r.d_pcm, rp.out = ss.rs.d_conv.p, rp.carry = ss.rs.d_carry.p;
+    rp.tiles = r.up.rtiles, rp.n_tiles = (int32_t)ss.push.rtiles.size();
+    rp.rates = ss.rs.d_rates.p, rp.taps = ss.rs.d_taps.p;
+    rp.channels = h->channels;
+    rp.taps_floats = ss.rs.taps_floats, rp.x_floats = ss.rs.x_floats, rp.out_elems = ss.rs.out_elems;
+    HIP_TRY(h, launch_sess_resample(rp, h->stream));
+    return MFX_OK;
+}
+
+// ---- stage 4, gather: carried PCM tail + new samples + carried static rows (+ carried rows y) -> the current slots
 int run_gather(mfx_handle *h, const PushRun &r)
 {
     const SessState &ss = h->sess;
     SessGatherParams gp{};
     gp.descs = r.up.descs, gp.n_descs = (int32_t)ss.push.descs.size(), gp.items_max = r.items_max;
     gp.narrow = (h->cfg.engine & MFX_ENGINE_SESS_NARROW_LOADS) ? 1 : 0;
-    gp.pcm = r.d_pcm, gp.pcm_elems = r.pcm_total * h->channels;
+    // (a push that converts: the new samples are the converted pieces in the scratch)
+    gp.pcm = ss.push.convert ? ss.rs.d_conv.p : r.d_pcm;
+    gp.pcm_elems = ss.push.convert ? (int64_t)ss.n * ss.rs.conv_stride * h->channels : r.pcm_total * h->channels;
     gp.slot_pcm = ss.d_pcm.p, gp.slot_elems = (int64_t)2 * ss.n * ss.pcm_stride * h->channels;
     gp.slot_stat = ss.d_stat.p, gp.stat_pitch = r.pitch, gp.cols = h->cols;
     gp.slot_y = ss.xf.d_y.p, gp.y_width = ss.xf.set ? h->width : 0;
@@ -517,7 +732,7 @@ int run_gather(mfx_handle *h, const PushRun &r)
     return MFX_OK;
 }
 
-// ---- stage 4, front end over the push's chunks: statics straight to their rows of the current slots
+// ---- stage 5, front end over the push's chunks: statics straight to their rows of the current slots
 int run_front(mfx_handle *h, PushRun &r)
 {
     const SessState &ss = h->sess;
@@ -536,7 +751,7 @@ int run_front(mfx_handle *h, PushRun &r)
     return launch_front(h, p, r.kind, r.aligned, w);
 }
 
-// ---- stages 5 and 7, online normaliser: ahead of the deltas on the new frames' statics in the slots (data = the statics
+// ---- stages 6 and 8, online normaliser: ahead of the deltas on the new frames' statics in the slots (data = the statics
 // slots at the run's pitch), behind them on the rows the push completes (data = d_rows at `width`)
 int run_onorm(mfx_handle *h, const PushRun &r, float *data, int pitch)
 {
@@ -553,7 +768,7 @@ int run_onorm(mfx_handle *h, const PushRun &r, float *data, int pitch)
     return MFX_OK;
 }
 
-// ---- stage 6, delta: the rows every session's push completes, into d_rows (l1 == 0: the copy form)
+// ---- stage 7, delta: the rows every session's push completes, into d_rows (l1 == 0: the copy form)
 int run_delta(mfx_handle *h, const PushRun &r)
 {
     const SessState &ss = h->sess;
@@ -566,7 +781,7 @@ int run_delta(mfx_handle *h, const PushRun &r)
     return MFX_OK;
 }
 
-// ---- stage 8, session transform: the rows y in the slots -> the caller's array, [total_rows][out_dim]
+// ---- stage 9, session transform: the rows y in the slots -> the caller's array, [total_rows][out_dim]
 int run_xform(mfx_handle *h, const PushRun &r)
 {
     const SessState &ss = h->sess;
@@ -593,7 +808,7 @@ int run_xform(mfx_handle *h, const PushRun &r)
     return MFX_OK;
 }
 
-// ---- stage 9, once the launches are queued: every piece's session takes its next state; the push is consumed
+// ---- stage 10, once the launches are queued: every piece's session takes its next state; the push is consumed
 void commit(mfx_handle *h, const PushRun &r)
 {
     SessState &ss = h->sess;
@@ -601,6 +816,10 @@ void commit(mfx_handle *h, const PushRun &r)
         SessState::Live &lv = ss.live[pc.id];
         lv = pc.next;
         if (lv.pitch < 0) lv.pitch = r.pitch;
+    }
+    if (ss.rs.set) { // (what mfx_sessions_converted_read returns)
+        ss.rs.last_valid = ss.push.convert;
+        if (ss.push.convert) ss.rs.last_off = ss.push.c_off, ss.rs.last_len = ss.push.c_len;
     }
     ss.push.planned = false;
 }
@@ -614,8 +833,8 @@ extern "C" int mfx_sessions_run_device(mfx_handle *h, const int16_t *d_pcm, int6
     const bool before = norm_before(h);
     int rc = check_run(h, r);
     if (rc != MFX_OK) return rc;
-    if (!h->sess.push.descs.empty()) { // (no descriptor: nothing to move, compute or deliver)
-        if ((rc = upload(h, r)) != MFX_OK || (rc = run_gather(h, r)) != MFX_OK || (rc = run_front(h, r)) != MFX_OK) return rc;
+    if (!h->sess.push.descs.empty() || !h->sess.push.rtiles.empty()) { // (neither: nothing to move, compute or deliver)
+        if ((rc = upload(h, r)) != MFX_OK || (rc = run_resample(h, r)) != MFX_OK || (rc = run_gather(h, r)) != MFX_OK || (rc = run_front(h, r)) != MFX_OK) return rc;
         if (before && (rc = run_onorm(h, r, h->sess.d_stat.p, r.pitch)) != MFX_OK) return rc;
         if ((rc = run_delta(h, r)) != MFX_OK) return rc;
         if (!before && (rc = run_onorm(h, r, r.d_rows, h->width)) != MFX_OK) return rc;
@@ -696,4 +915,19 @@ extern "C" int32_t mfx_host_sess_xform_groups(int32_t n, const int32_t *n_out, c
         for (size_t k = 0; k < bl.size(); ++k) blocks[3 * k] = bl[k].g0, blocks[3 * k + 1] = bl[k].ng, blocks[3 * k + 2] = bl[k].xf;
     }
     return (int32_t)gp.size();
+}
+
+extern "C" int64_t mfx_host_session_resample_step(int32_t in_hz, int32_t out_hz, int32_t zeros, float rolloff, int64_t state[2], int64_t length,
+                                                  int32_t final_flag, int32_t *carry_in, int32_t *carry_out)
+{
+    ResampleShape sh;
+    if (resample_shape(in_hz, out_hz, zeros, rolloff, sh) != 0 || !state || state[0] < 0 || state[1] < 0 || length < 0) return MFX_ERR_ARG;
+    if (state[0] > (INT64_MAX / 4096 - length) / 2) return MFX_ERR_ARG; // (N L stays inside int64)
+    const bool pass = in_hz == out_hz;
+    if (state[1] > (pass ? state[0] : (state[0] * sh.L + sh.M - 1) / sh.M)) return MFX_ERR_ARG; // (more outputs than the stream has)
+    SessionResampleStep st;
+    const int64_t n = session_resample_step(pass ? 1 : sh.L, pass ? 1 : sh.M, pass ? 0 : sh.Wh, state[0], state[1], length, final_flag != 0, st);
+    if (carry_in) *carry_in = st.carry_in;
+    if (carry_out) *carry_out = st.carry_out;
+    return n;
 }

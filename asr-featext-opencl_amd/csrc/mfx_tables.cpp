@@ -801,6 +801,27 @@ int64_t resample_layout(int32_t n_utt, const int64_t *lengths, const int32_t *ra
     return off;
 }
 
+int64_t session_resample_step(int32_t L, int32_t M, int32_t Wh, int64_t &N, int64_t &J, int64_t length, bool final_push,
+                              SessionResampleStep &st)
+{
+    const bool pass = L == M;
+    // (the first input sample output j reads; nothing before the stream's start is kept)
+    auto first_needed = [&](int64_t j) { return std::max<int64_t>((j * M) / L - Wh + 1, 0); };
+    const int64_t N_old = N, J_old = J, N_new = N + length;
+    int64_t J_new;
+    if (pass)
+        J_new = N_new;
+    else if (final_push)
+        J_new = (N_new * L + M - 1) / M;
+    else
+        J_new = N_new > Wh ? ((N_new - Wh) * L + M - 1) / M : 0;
+    st.c0_old = pass ? N_old : std::min(first_needed(J_old), N_old);
+    st.c0_new = pass || final_push ? N_new : std::min(first_needed(J_new), N_new);
+    st.carry_in = (int32_t)(N_old - st.c0_old), st.carry_out = (int32_t)(N_new - st.c0_new);
+    N = final_push ? 0 : N_new, J = final_push ? 0 : J_new;
+    return J_new - J_old;
+}
+
 // The online normaliser's definition (include/mfx.h, mfx_batch_set_online_norm) on host memory: per column the chunked
 // prefix sums P of v and of q, then every row's window, prior, statistics and float32 apply.  Every double operation is
 // a statement of its own and this file is compiled with -ffp-contract=off.

@@ -235,6 +235,20 @@ int64_t resampled_length(int64_t samples, int32_t in_hz, int32_t out_hz);
 int64_t resample_layout(int32_t n_utt, const int64_t *lengths, const int32_t *rates_hz, int32_t out_hz, int64_t *offsets,
                         int64_t *out_lengths);
 
+// One push of one session under a session rate ("Session sample-rate conversion"): a stream that has received N
+// input samples per channel and holds converted samples [0, J) takes `length` more.  J = max(0, ceil((N - Wh) L / M)) while the
+// stream is open -- the outputs whose last tap n + Wh has arrived -- and ceil(N L / M) once a push is final; a pass-through
+// rate (L == M) has J = N and carries nothing.  The previous carry slot holds input samples [c0_old, N_old), c0 = max(0, (J M)
+// div L - Wh + 1) (the first sample output J reads); the push converts outputs [J_old, J_new) from them and the new samples
+// and leaves [c0_new, N_new) in the current slot: at most 2 Wh - 1 samples, nothing after a final push.  Returns J_new - J_old;
+// N and J are advanced (both 0 after a final push: the session is fresh).
+struct SessionResampleStep {
+    int64_t c0_old, c0_new; // first input sample the previous / the current carry slot holds
+    int32_t carry_in, carry_out; // samples per channel carried in and out
+};
+int64_t session_resample_step(int32_t L, int32_t M, int32_t Wh, int64_t &N, int64_t &J, int64_t length, bool final_push,
+                              SessionResampleStep &st);
+
 // STFT log-mel front end ("STFT log-mel"; N = DFT length, even; K1 = N / 2 + 1 bins).
 // frames of an utterance of `samples` samples: 0 up to N / 2 samples (the reflection needs one more), else samples div S
 int64_t stft_frame_count(int64_t samples, int N, int S);

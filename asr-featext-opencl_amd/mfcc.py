@@ -79,6 +79,8 @@ EXPORTED_SYMBOLS = (
     "mfx_sessions_delivered", "mfx_host_session_step",
     "mfx_sessions_set_transform", "mfx_sessions_clear_transform", "mfx_sessions_select_transform",
     "mfx_sessions_output_width", "mfx_host_session_xform_step", "mfx_host_sess_xform_groups",
+    "mfx_sessions_set_rates", "mfx_sessions_clear_rates", "mfx_sessions_select_rate", "mfx_sessions_converted_read",
+    "mfx_host_session_resample_step",
     "mfx_batch_plan_rates", "mfx_batch_resample_layout", "mfx_host_resample_taps", "mfx_host_resampled_length",
     "mfx_host_resample_layout", "mfx_host_resample_tile",
     "mfx_batch_set_speakers", "mfx_batch_speaker_stats", "mfx_host_speaker_lists",
@@ -180,6 +182,12 @@ def load_library():
     L.mfx_sessions_output_width.argtypes = [vp]
     L.mfx_host_session_xform_step.argtypes = [i32, i32, p64, i32, i32, p32, p32]
     L.mfx_host_session_xform_step.restype = i32
+    L.mfx_sessions_set_rates.argtypes = [vp, i32, p32, i32, C.c_float]
+    L.mfx_sessions_clear_rates.argtypes = [vp]
+    L.mfx_sessions_select_rate.argtypes = [vp, i32, i32]
+    L.mfx_sessions_converted_read.argtypes, L.mfx_sessions_converted_read.restype = [vp, sp, i64, p64, p64], i64
+    L.mfx_host_session_resample_step.argtypes = [i32, i32, i32, C.c_float, p64, i64, i32, p32, p32]
+    L.mfx_host_session_resample_step.restype = i64
     L.mfx_host_sess_xform_groups.argtypes = [i32, p32, p32, i32, p32, i32, p32, i32, p32]
     L.mfx_host_sess_xform_groups.restype = i32
     L.mfx_batch_plan_rates.argtypes = [vp, i32, p64, p64, p32, i32, C.c_float, p64, p64]
@@ -464,6 +472,20 @@ def host_session_xform_step(left, right, state, n_y, final=False):
     if rows < 0:
         raise MfxError(int(rows), "mfx_host_session_xform_step failed")
     return dict(rows=int(rows), state=(int(st[0]), int(st[1])), carry_rows=cr.value, src_row0=win[0], lo=win[1], hi=win[2])
+
+
+def host_session_resample_step(in_hz, out_hz, state, length, final=False, zeros=0, rolloff=0.0):
+    """One push of one session under a session rate exactly as the planner derives it (host code, no GPU needed).  state =
+    (N_in, J): input samples received and converted samples held so far.  Returns dict(n_out, state, carry_in, carry_out);
+    state is (0, 0) after a final push."""
+    L = load_library()
+    st = (C.c_int64 * 2)(int(state[0]), int(state[1]))
+    ci, co = C.c_int32(0), C.c_int32(0)
+    n = L.mfx_host_session_resample_step(int(in_hz), int(out_hz), int(zeros), float(rolloff), st, int(length), int(bool(final)),
+                                         C.byref(ci), C.byref(co))
+    if n < 0:
+        raise MfxError(int(n), "mfx_host_session_resample_step failed")
+    return dict(n_out=int(n), state=(int(st[0]), int(st[1])), carry_in=ci.value, carry_out=co.value)
 
 
 def host_sess_xform_groups(n_out, xf, G=4):
@@ -1154,7 +1176,41 @@ class MfccHip:
             raise MfxError(w, self._L.mfx_status_string(w).decode())
         return w
 
+    def sessions_set_rates(self, rates, zeros=0, rolloff=0.0):
+        """Per-session sample-rate conversion in front of every push (mfx_sessions_set_rates): call it before
+        sessions_create.  rates: up to 16 input rates in Hz (cfg.sample_rate itself is a pass-through); a session takes
+        rates[0] unless sessions_select_rate says otherwise.  max_push_samples, offsets and lengths are then in input-rate
+        samples per channel."""
+        rt = np.ascontiguousarray(rates, dtype=np.int32).reshape(-1)
+        self._chk(self._L.mfx_sessions_set_rates(self._h, rt.size, rt.ctypes.data_as(C.POINTER(C.c_int32)), int(zeros),
+                                                 float(rolloff)))
+
+    def sessions_clear_rates(self):
+        self._chk(self._L.mfx_sessions_clear_rates(self._h))
+
+    def sessions_select_rate(self, session, rate_index):
+        """The rate of one (fresh) session; kept across final pushes and sessions_reset."""
+        self._chk(self._L.mfx_sessions_select_rate(self._h, int(session), int(rate_index)))
+
+    def sessions_converted_read(self, n_pieces):
+        """The converted samples of the last push that ran, one int16 array [samples][channels] per piece of its plan
+        (test / inspection aid; synchronises).  MfxError(ERR_STATE) when that push queued no conversion launch."""
+        need = int(self._L.mfx_sessions_converted_read(self._h, None, 0, None, None))
+        if need < 0:
+            self._chk(need)
+        ch = max(self.cfg.channels, 1)
+        dst = np.zeros(max(need, 1), dtype=np.int16)
+        off = np.zeros(int(n_pieces), dtype=np.int64)
+        ln = np.zeros(int(n_pieces), dtype=np.int64)
+        p64 = C.POINTER(C.c_int64)
+        got = int(self._L.mfx_sessions_converted_read(self._h, dst.ctypes.data_as(C.POINTER(C.c_int16)), need,
+                                                      off.ctypes.data_as(p64), ln.ctypes.data_as(p64)))
+        if got < 0:
+            self._chk(got)
+        return [dst[int(o) * ch:int(o + n) * ch].reshape(-1, ch).copy() for o, n in zip(off, ln)]
+
     host_session_step = staticmethod(host_session_step)
+    host_session_resample_step = staticmethod(host_session_resample_step)
     host_session_xform_step = staticmethod(host_session_xform_step)
 
     def batch_overlap(self, enable=True):

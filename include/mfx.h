@@ -616,7 +616,8 @@ int mfx_batch_pitch_feats_device(const mfx_handle *h, const float **d_feats, int
  * samples.
  * mfx_batch_resample_layout: the scratch layout in output-rate samples per channel (what a second handle needs to be planned
  * on the converted PCM, which mfx_debug_read kind 8 returns); MFX_ERR_STATE without a rates plan.
- * NOT served: the session entries (mfx_sessions_*) and the streaming interface are untouched and ignore a rates plan. */
+ * NOT served: the session entries (mfx_sessions_*) and the streaming interface are untouched and ignore a rates plan.  The
+ * session entries have rates of their own: mfx_sessions_set_rates / mfx_sessions_select_rate below. */
 int mfx_batch_plan_rates(mfx_handle *h, int32_t n_utt, const int64_t *offsets, const int64_t *lengths, const int32_t *rates_hz,
                          int32_t zeros, float rolloff, int64_t *out_rows, int64_t *total_rows);
 int mfx_batch_resample_layout(const mfx_handle *h, int64_t *offsets, int64_t *lengths, int64_t *total);
@@ -719,6 +720,58 @@ int mfx_sessions_select_transform(mfx_handle *h, int32_t session, int32_t xf);
 /* out_dim while a session transform is set, else mfx_get_output_data_width */
 int mfx_sessions_output_width(const mfx_handle *h);
 
+/* ---- session rates: per-session sample-rate conversion in front of a push ("Session sample-rate conversion") ----
+ *
+ * A session arrives at r_in = rates_hz[its rate index] Hz (mfx_sessions_select_rate; default index 0); r_out =
+ * mfx_config.sample_rate, g, L, M, the filter h[phi][k], Wh, P, zeros and rolloff are those of mfx_batch_plan_rates above.
+ *   Converted sample.  Output sample j of a STREAM is the batch definition, unchanged: n = (j M) div L, phi = (j M) mod L;
+ *     acc = 0; for k = 0 .. P - 1 ascending: acc = fmaf(h[phi][k], (float)x[n - Wh + 1 + k], acc);
+ *     y[j] = clamp(rintf(acc), -32768, 32767).  x outside [0, N_in) of the stream is 0; the right zero fill happens only once
+ *     the stream is final.
+ *   Delivery rule.  After a session has received N input samples (per channel) it has converted samples [0, J):
+ *     J = max(0, ceil((N - Wh) L / M)) while the stream is open: the outputs whose last tap n + Wh has arrived;
+ *     J = ceil(N L / M)                once a push is final.
+ *     A pass-through session (r_in == r_out) has J = N throughout: its samples are taken as they are.
+ *   Everything behind the converter is the session contract above with n = J: T(J) = mfx_batch_frames(h, J), E, Ex, the online
+ *     normaliser and the session transform are unchanged.  A flush (final push, no new samples) also converts the stream's last
+ *     ceil(N L / M) - J samples before it delivers the tail rows.
+ *   Contract.  The converted samples and the rows of a stream are THE SAME BITS that mfx_batch_run_device produces for the whole
+ *     utterance on a handle of the same configuration under mfx_batch_plan_rates(..., rates_hz[u] = r_in, zeros, rolloff): the
+ *     converted samples are that handle's mfx_debug_read kind 8, the rows its rows (with the same online normaliser and
+ *     transform), however the stream is cut: pushes of 0 or 1 samples, pushes shorter than Wh, pieces at odd offsets of the
+ *     caller's array, mono or stereo (each channel converted on its own, interleaved; the (L+R)>>1 downmix stays in the
+ *     front ends).
+ *   Units.  While rates are set, max_push_samples of mfx_sessions_create, offsets and lengths of mfx_sessions_plan and
+ *     pcm_samples_total of the run entries are in INPUT-rate samples per channel of the caller's one array (4-byte aligned as
+ *     always; pieces may sit at odd offsets).  MFX_ERR_BUFFER_TOO_SMALL: lengths[i] > max_push_samples; MFX_ERR_ARG: a piece past
+ *     pcm_samples_total.
+ * State.  mfx_sessions_set_rates / mfx_sessions_clear_rates are valid only while no sessions exist, else MFX_ERR_STATE.  The
+ * setter builds the tap tables on the host (the code of mfx_batch_plan_rates) and allocates nothing on the device;
+ * mfx_sessions_create sizes and uploads everything -- the tables, two carry slot arrays of max over rates (2 Wh + M div L + 2)
+ * samples per channel and session (rounded up to 8), an int16 scratch of one converted piece per session, and every slot of the
+ * session entries for the largest converted piece, max over rates ceil((max_push_samples + Wh) L / M) + 1 (MFX_ERR_ARG when that
+ * exceeds 2^24) -- mfx_sessions_run_device still allocates nothing and queues ONE launch more (k_sess_resample, ahead of the
+ * gather), and mfx_sessions_create(h, 0, 0) releases the device parts.  A session carries at most 2 Wh - 1 input samples per
+ * channel from push to push; a final push and mfx_sessions_reset leave it fresh.  A push whose pieces are all pass-through (or
+ * bring nothing) queues no conversion launch and reads the caller's array directly.  Without mfx_sessions_set_rates every
+ * session entry does exactly what it did before.  The batch rates plan and the session rates are strangers: neither reads or
+ * changes the other.
+ * mfx_sessions_select_rate(h, session, i): the session's rate.  The choice stays with the id across final pushes and
+ * mfx_sessions_reset; mfx_sessions_create puts all back to 0.  It drops a pending plan.  MFX_ERR_STATE without rates or without
+ * sessions, or when the session is not fresh; MFX_ERR_ARG for an id or index out of range.
+ * Errors of the setter: MFX_ERR_ARG n_rates outside 1 .. 16, rates_hz == NULL, and the limits of mfx_batch_plan_rates (rates in
+ * 1000 .. 768000 Hz, L <= 4096, P <= 4096, L P <= 2^20, zeros in 0 .. 64, rolloff in [0, 1]); MFX_ERR_CONFIG a sample_rate that
+ * is not integral; MFX_ERR_DEVICE a planning handle, before any argument is looked at (all entries).
+ * mfx_sessions_converted_read (test / inspection aid; it synchronises): the converted samples of the last push that ran, piece
+ * by piece in the plan's order, back to back in dst (interleaved for channels = 2); offsets[i] / lengths[i] (either may be NULL)
+ * are piece i's place in dst in samples per channel.  Returns the int16 elements written (dst == NULL: needed);
+ * MFX_ERR_BUFFER_TOO_SMALL when cap_elems is less; MFX_ERR_STATE without rates or sessions, or when the last push queued no
+ * conversion launch (its samples are the caller's own). */
+int mfx_sessions_set_rates(mfx_handle *h, int32_t n_rates, const int32_t *rates_hz, int32_t zeros, float rolloff);
+int mfx_sessions_clear_rates(mfx_handle *h);
+int mfx_sessions_select_rate(mfx_handle *h, int32_t session, int32_t rate_index);
+int64_t mfx_sessions_converted_read(mfx_handle *h, int16_t *dst, int64_t cap_elems, int64_t *offsets, int64_t *lengths);
+
 /* Page-locked host memory for the caller's PCM / feature buffers (mfx_batch_run_host and the streaming entries DMA
  * straight from / to such buffers; pageable ones go through the handle's staging).  NULL on failure. */
 void *mfx_alloc_pinned(size_t bytes);
@@ -809,6 +862,14 @@ int64_t mfx_host_xform_operands(int32_t out_dim, int32_t in_dim, const float *A,
  * static_off}, rows relative to the first carried frame max(0, E_old - D).  Any output may be NULL.  Test / inspection aid. */
 int32_t mfx_host_session_step(int32_t window, int32_t shift, int32_t D, int64_t state[2], int64_t length, int32_t final_flag,
                               int64_t *carry_samples, int32_t *carry_rows, int32_t *new_frames, int32_t seg[5]);
+/* One push of one session under a session rate, exactly as the planner derives it (mfx_sessions_set_rates' delivery rule).  state
+ * = {N_in, J} in / out: input samples received, converted samples held (both 0 after a final push); returns J_new - J_old.
+ * carry_in / carry_out: the input samples per channel the previous carry slot hands in and the current one keeps, [max(0, (J M)
+ * div L - Wh + 1), N) on either side (0 out of a final push, 0 for in_hz == out_hz); either may be NULL.  MFX_ERR_ARG on a pair
+ * outside the limits of mfx_batch_plan_rates, a negative length or state, or J beyond ceil(N L / M); nothing is written then.
+ * Test / inspection aid. */
+int64_t mfx_host_session_resample_step(int32_t in_hz, int32_t out_hz, int32_t zeros, float rolloff, int64_t state[2] /* {N_in, J} */,
+                                       int64_t length, int32_t final_flag, int32_t *carry_in, int32_t *carry_out);
 /* Sample-rate conversion (mfx_batch_plan_rates).  mfx_host_resample_taps: the table as uploaded, [L][P]; returns L * P or a
  * negative status (MFX_ERR_ARG: outside the limits, or cap too small); taps may be NULL to query.
  * mfx_host_resampled_length: ceil(samples L / M).  mfx_host_resample_layout: the scratch layout (offsets, out_lengths; either
