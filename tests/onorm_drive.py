@@ -128,10 +128,11 @@ def D_of(m):
     return 0 if m.cfg.dyn == 0 else m.cfg.delta_l1 if m.cfg.dyn == 1 else m.cfg.delta_l1 + m.cfg.delta_l2
 
 
-def drive(m, utts, n_sessions, cut, seed, odd_offsets=False, subset=False, host=False, place=None):
+def drive(m, utts, n_sessions, cut, seed, odd_offsets=False, subset=False, host=False, place=None, record=None):
     """Feed the utterances through n_sessions sessions (an id is reused for the next utterance on the push after its final
     one); returns the rows every utterance delivered, in order, and checks the plan's counts against the contract.
-    place(total_rows, width): an OutPlacement-like object to run into (its check() is called after every push)."""
+    place(total_rows, width): an OutPlacement-like object to run into (its check() is called after every push).
+    record: a list that takes one entry per push (tests/sess_inflight.py replays them without a wait in between)."""
     import torch
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(seed)
@@ -179,6 +180,7 @@ def drive(m, utts, n_sessions, cut, seed, odd_offsets=False, subset=False, host=
             m.sessions_run_device(d_pcm.data_ptr(), len(pcm), d_out.data_ptr())
             m.synchronize()
             out = d_out.cpu().numpy()[:total]
+        delivered = []
         for sid, n, fin, r0, cnt in zip(ids, lens, fins, out_rows, counts):
             st = cur[sid]
             st[1] += n
@@ -188,8 +190,12 @@ def drive(m, utts, n_sessions, cut, seed, odd_offsets=False, subset=False, host=
             st[2] = E
             got[st[0]].append(out[r0:r0 + cnt].copy())
             assert m.sessions_delivered(sid) == (0 if fin else E)
+            delivered.append(0 if fin else E)
             if fin:
                 del cur[sid]
+        if record is not None:
+            record.append(dict(calls=[], ids=ids, offs=offs, lens=lens, fins=fins, pcm=pcm, out_rows=out_rows, counts=counts,
+                               total=total, rows=np.array(out[:total]), delivered=delivered, host=host))
         tick += 1
     return {u: (np.concatenate(v, 0) if v else np.zeros((0, width), np.float32)) for u, v in got.items()}
 

@@ -130,10 +130,13 @@ def cut_lengths(lengths):
 
 class Fleet:
     """Sessions of one handle, each at its rate; push() runs one push and files every piece's converted samples and rows under
-    the stream it belongs to."""
+    the stream it belongs to.
+    record: a list that takes one entry per push, the host calls made through call() in front of it included
+    (tests/sess_inflight.py replays them without a wait in between)."""
 
-    def __init__(self, pkg, m, seed=0):
+    def __init__(self, pkg, m, seed=0, record=None):
         self.pkg, self.m, self.rng = pkg, m, np.random.default_rng(seed)
+        self.record, self.calls = record, []
         self.ch = max(m.cfg.channels, 1)
         self.state = {}                                   # sid -> [key, rate, N_in, J, rows delivered]
         self.conv, self.rows = {}, {}
@@ -146,6 +149,11 @@ class Fleet:
 
     def drop(self, sid):
         del self.state[sid]
+
+    def call(self, name, *args):
+        """A host call on the handle between two pushes (sessions_select_rate, sessions_reset), noted for the record."""
+        getattr(self.m, name)(*args)
+        self.calls.append((name, args))
 
     def push(self, pieces, odd=False, host=False, place=None, right=0, D=6, check_rows=True):
         """pieces: [(sid, samples [n][ch], final)].  odd: every piece on an odd sample of the caller's array."""
@@ -192,6 +200,7 @@ class Fleet:
             assert e.status == ERR_STATE
             conv = None
             self.launches.append(False)
+        delivered = []
         for i, (sid, x, fin) in enumerate(pieces):
             st = self.state[sid]
             key, rate = st[0], st[1]
@@ -212,9 +221,15 @@ class Fleet:
                 assert st[4] + counts[i] == Ex, (sid, st, counts[i], Ex, fin)
                 st[4] = Ex
                 assert m.sessions_delivered(sid) == (0 if fin else Ex)
+                delivered.append(0 if fin else Ex)
             self.rows[key].append(out[out_rows[i]:out_rows[i] + counts[i]].copy())
             if fin:
                 del self.state[sid]
+        if self.record is not None:
+            self.record.append(dict(calls=self.calls, ids=ids, offs=offs, lens=lens, fins=fins, pcm=pcm, out_rows=out_rows,
+                                    counts=counts, total=total, rows=np.array(out[:total]),
+                                    delivered=delivered if check_rows else None, host=host))
+            self.calls = []
         return out
 
     def converted(self, key):

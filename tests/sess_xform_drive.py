@@ -12,13 +12,15 @@ make, utterances, batch_rows, compare, D_of = OD.make, OD.utterances, OD.batch_r
 
 
 def drive(m, utts, n_sessions, cut, seed, right, odd_offsets=False, subset=False, host=False, place=None, xf_of=None, on_tick=None,
-          shuffle=False):
+          shuffle=False, record=None):
     """Feed the utterances through n_sessions sessions (an id is reused for the next utterance on the push after its final
     one; with xf_of the fresh session is given transform xf_of[u] first); returns the rows every utterance delivered, in
     order, and checks the plan's counts and mfx_sessions_delivered against the transform's delivery rule.
     place(total_rows, width): an OutPlacement-like object to run into (its check() is called after every push).
     shuffle: the pieces of every push in a random order of ids (the planner's caller order then differs from its slot order
-    and from the packer's)."""
+    and from the packer's).
+    record: a list that takes one entry per push, the sessions_select_transform calls in front of it included
+    (tests/sess_inflight.py replays them without a wait in between)."""
     import torch
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(seed)
@@ -27,11 +29,13 @@ def drive(m, utts, n_sessions, cut, seed, right, odd_offsets=False, subset=False
     cur, got = {}, {u: [] for u in range(len(utts))}
     tick = 0
     while pending or cur:
+        calls = []
         for sid in range(n_sessions):
             if sid not in cur and pending:
                 cur[sid] = [pending.pop(0), 0, 0]              # utterance, samples fed, rows delivered
                 if xf_of is not None:
                     m.sessions_select_transform(sid, xf_of[cur[sid][0]])
+                    calls.append(("sessions_select_transform", (sid, xf_of[cur[sid][0]])))
         active = sorted(cur)
         if subset and len(active) > 1:                         # a changing subset of the open sessions
             keep = [s for s in active if (s + tick) % 3 != 0]
@@ -71,6 +75,7 @@ def drive(m, utts, n_sessions, cut, seed, right, odd_offsets=False, subset=False
             m.sessions_run_device(d_pcm.data_ptr(), len(pcm), d_out.data_ptr())
             m.synchronize()
             out = d_out.cpu().numpy()[:total]
+        delivered = []
         for sid, n, fin, r0, cnt in zip(ids, lens, fins, out_rows, counts):
             st = cur[sid]
             st[1] += n
@@ -81,8 +86,12 @@ def drive(m, utts, n_sessions, cut, seed, right, odd_offsets=False, subset=False
             st[2] = Ex
             got[st[0]].append(out[r0:r0 + cnt].copy())
             assert m.sessions_delivered(sid) == (0 if fin else Ex)
+            delivered.append(0 if fin else Ex)
             if fin:
                 del cur[sid]
+        if record is not None:
+            record.append(dict(calls=calls, ids=ids, offs=offs, lens=lens, fins=fins, pcm=pcm, out_rows=out_rows, counts=counts,
+                               total=total, rows=np.array(out[:total]), delivered=delivered, host=host))
         if on_tick:
             on_tick(tick)
         tick += 1

@@ -120,9 +120,11 @@ def cut_random_with_empty(left, S, rng):
     return min(int(rng.integers(1, MAX_PUSH + 1)), left), False
 
 
-def _drive(m, utts, n_sessions, cut, seed, odd_offsets=False, subset=False, descending=False, host=False, on_tick=None):
+def _drive(m, utts, n_sessions, cut, seed, odd_offsets=False, subset=False, descending=False, host=False, on_tick=None,
+           record=None):
     """Feed the utterances through n_sessions sessions (an id is reused for the next utterance on the push after its final
-    one); returns the rows every utterance delivered, in order, and checks the plan's counts against the contract."""
+    one); returns the rows every utterance delivered, in order, and checks the plan's counts against the contract.
+    record: a list that takes one entry per push (tests/sess_inflight.py replays them without a wait in between)."""
     import torch
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(seed)
@@ -166,6 +168,7 @@ def _drive(m, utts, n_sessions, cut, seed, odd_offsets=False, subset=False, desc
             m.sessions_run_device(d_pcm.data_ptr(), len(pcm), d_out.data_ptr())
             m.synchronize()
             out = d_out.cpu().numpy()[:total]
+        delivered = []
         for sid, n, fin, r0, cnt in zip(ids, lens, fins, out_rows, counts):
             st = cur[sid]
             st[1] += n
@@ -175,8 +178,12 @@ def _drive(m, utts, n_sessions, cut, seed, odd_offsets=False, subset=False, desc
             st[2] = E
             got[st[0]].append(out[r0:r0 + cnt].copy())
             assert m.sessions_delivered(sid) == (0 if fin else E)
+            delivered.append(0 if fin else E)
             if fin:
                 del cur[sid]
+        if record is not None:
+            record.append(dict(calls=[], ids=ids, offs=offs, lens=lens, fins=fins, pcm=pcm, out_rows=out_rows, counts=counts,
+                               total=total, rows=np.array(out[:total]), delivered=delivered, host=host))
         if on_tick:
             on_tick(tick)
         tick += 1
