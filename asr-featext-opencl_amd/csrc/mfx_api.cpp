@@ -21,12 +21,7 @@ void fill_melcep(const mfx_handle *h, const CepTables &t, MelcepParams &mp)
     mp.fft_size = h->W2;
     mp.mel_w = t.mel_w.p;
     mp.mel_beg = t.mel_beg.p;
-    mp.mel64_w = t.w64.p;
-    mp.mel64_start = t.start64.p;
-    mp.mel64_fid = t.fid64.p;
-    mp.mel64_L = t.L64.p;
-    mp.mel64_rounds = t.rounds;
-    mp.mel64_row_stride = t.row_stride;
+    mp.mel = t.plan64.tables_arg();
     mp.mag_floats = std::max(h->W2, (h->spec_pitch + 3) & ~3);
     mp.dct = h->ceps > 0 ? h->d_dct.p : nullptr;
     mp.dct_b4 = h->ceps > 0 ? h->d_dct_b4.p : nullptr;
@@ -41,23 +36,16 @@ void fill_melcep(const mfx_handle *h, const CepTables &t, MelcepParams &mp)
 // k_plp parameters that do not depend on the caller (the PLP twin of fill_melcep)
 void fill_plp(const mfx_handle *h, const CepTables &t, PlpParams &pp)
 {
-    MelcepParams mp;
-    fill_melcep(h, t, mp);
     std::memset(&pp, 0, sizeof(pp));
-    pp.spec_pitch = mp.spec_pitch;
-    pp.fft_size = mp.fft_size;
+    pp.spec_pitch = h->spec_pitch;
+    pp.fft_size = h->W2;
     pp.num_banks = h->nb;
     pp.lpc_order = h->lpc;
     pp.ceps_len = h->ceps;
     pp.want_c0 = h->cfg.want_c0 ? 1 : 0;
     pp.cols = h->cols;
-    pp.mel64_w = mp.mel64_w;
-    pp.mel64_start = mp.mel64_start;
-    pp.mel64_fid = mp.mel64_fid;
-    pp.mel64_L = mp.mel64_L;
-    pp.mel64_rounds = mp.mel64_rounds;
-    pp.mel64_row_stride = mp.mel64_row_stride;
-    pp.mag_floats = mp.mag_floats;
+    pp.mel = t.plan64.tables_arg();
+    pp.mag_floats = std::max(h->W2, (h->spec_pitch + 3) & ~3);
     pp.eql = t.eql.p;
     pp.idft = h->d_plp_idft.p;
     pp.lift = h->d_plp_lift.p;
@@ -65,19 +53,17 @@ void fill_plp(const mfx_handle *h, const CepTables &t, PlpParams &pp)
 
 } // namespace
 
-// (Re)build `t` for the n warp factors `alphas` (nothing to do when it holds them already): mel tables, 64-lane plans padded
-// to the longest plan's row stride (a row's rounds lie back to back from its start, so padding at the end changes nothing;
-// one table keeps its own stride) and PLP's equal-loudness weights.  first / first_plan (optional) receive table 0's mel
-// table and 64-lane plan.
-int build_cep_tables(mfx_handle *h, const float *alphas, int n, CepTables &t, MelTable *first, MelWavePlan *first_plan)
+// (Re)build `t` for the n warp factors `alphas` (nothing to do when it holds them already): mel tables, 64-lane plans
+// (MelPlanBuf pads them to one row stride) and PLP's equal-loudness weights.  first (optional) receives table 0's mel table.
+int build_cep_tables(mfx_handle *h, const float *alphas, int n, CepTables &t, MelTable *first)
 {
     if (t.holds(alphas, n)) return MFX_OK;
     t.alphas.clear(); // (until every table below is in place)
+    t.plan64.ok = false;
     const size_t wstride = (size_t)2 * h->W2, bstride = (size_t)h->nb + 2;
     std::vector<float> w(wstride * n), eql_all;
     std::vector<int32_t> b(bstride * n);
-    std::vector<MelWavePlan> plans((size_t)n);
-    int rs = 4;
+    std::vector<MelPlan> plans((size_t)n);
     for (int a = 0; a < n; ++a) {
         MelTable mt;
         build_mel_table(h->nb, h->W2, h->cfg.sample_rate, h->cfg.low_freq, h->cfg.high_freq, alphas[a], mt);
@@ -85,9 +71,8 @@ int build_cep_tables(mfx_handle *h, const float *alphas, int n, CepTables &t, Me
         for (int v : mt.beg)
             if (v < 0 || v > h->W2 / 2) return fail(h, MFX_ERR_CONFIG, "mel filter edge outside [0, fft_size/2]");
         // (the kernels' magnitude buffers hold W2 floats: bins 0 .. W2/2, finite words beyond)
-        if (!build_mel_wave_plan(mt, h->nb, h->W2, /*max_read_bin=*/h->W2 - 1, plans[a]))
+        if (!build_mel_plan(mt, h->nb, h->W2, /*max_read_bin=*/h->W2 - 1, /*lanes=*/64, /*align=*/2, plans[a]))
             return fail(h, MFX_ERR_CONFIG, "mel filterbank does not fit the kernels' lane plan (more than 512 filters?)");
-        rs = std::max(rs, plans[a].row_stride);
         std::copy(mt.weights.begin(), mt.weights.end(), w.begin() + wstride * a);
         std::copy(mt.beg.begin(), mt.beg.end(), b.begin() + bstride * a);
         if (h->plp) {
@@ -97,8 +82,7 @@ int build_cep_tables(mfx_handle *h, const float *alphas, int n, CepTables &t, Me
         }
         if (a == 0 && first) *first = std::move(mt);
     }
-    t.rounds = plans[0].rounds; // (ceil(nb / 64) for every alpha)
-    t.row_stride = rs;
+    t.plan64.shape(plans.data(), n);
     {   // k_melcep / k_plp stage the weight rows (one per filter-carrying lane) + one wave's buffers in LDS.  rows x row
         // stride is at most ~4 x W2 floats for the reference's triangular banks, so every transform up to 4096 points fits
         // whatever the filter count (4096 points, 48 kHz, 20 filters: 20 rows of 600 floats = 48 KB); 8192 points and more
@@ -113,26 +97,11 @@ int build_cep_tables(mfx_handle *h, const float *alphas, int n, CepTables &t, Me
             if (plp_lds_bytes(pp, 1) > kLdsCap) return fail(h, MFX_ERR_CONFIG, "mel filterbank does not fit the PLP kernel's LDS");
         }
     }
-    std::vector<float> pw((size_t)n * 64 * rs, 0.f);
-    std::vector<int32_t> pst((size_t)n * 64 * t.rounds), pfid((size_t)n * 64 * t.rounds), pL((size_t)n * 8);
-    for (int a = 0; a < n; ++a) {
-        const MelWavePlan &pl = plans[a];
-        for (int j = 0; j < 64; ++j)
-            std::copy(pl.w.begin() + (size_t)j * pl.row_stride, pl.w.begin() + (size_t)(j + 1) * pl.row_stride,
-                      pw.begin() + ((size_t)a * 64 + j) * rs);
-        std::copy(pl.start.begin(), pl.start.end(), pst.begin() + (size_t)a * 64 * t.rounds);
-        std::copy(pl.fid.begin(), pl.fid.end(), pfid.begin() + (size_t)a * 64 * t.rounds);
-        std::copy(pl.L, pl.L + 8, pL.begin() + (size_t)a * 8);
-    }
     if (!h->planning) HIP_TRY(h, hipStreamSynchronize(h->stream));
     HIP_TRY(h, h->upload(t.mel_w, w));
     HIP_TRY(h, h->upload(t.mel_beg, b));
-    HIP_TRY(h, h->upload(t.w64, pw));
-    HIP_TRY(h, h->upload(t.start64, pst));
-    HIP_TRY(h, h->upload(t.fid64, pfid));
-    HIP_TRY(h, h->upload(t.L64, pL));
     if (h->plp) HIP_TRY(h, h->upload(t.eql, eql_all));
-    if (first_plan) *first_plan = std::move(plans[0]);
+    if (const int rc = t.plan64.set(h, plans.data(), n); rc != MFX_OK) return rc;
     t.alphas.assign(alphas, alphas + n);
     return MFX_OK;
 }
@@ -145,32 +114,27 @@ int refresh_mel(mfx_handle *h)
 {
     if (h->stft) return MFX_OK; // (its one table does not depend on alpha)
     if (h->own.holds(&h->alpha, 1)) return MFX_OK;
-    h->fused_ok = h->wplan_ok = h->wplan32_ok = false;
+    h->plan16.ok = h->plan32.ok = false;
     MelTable t;
-    const int rc = build_cep_tables(h, &h->alpha, 1, h->own, &t, &h->wplan);
+    const int rc = build_cep_tables(h, &h->alpha, 1, h->own, &t);
     if (rc != MFX_OK) return rc;
-    h->wplan_ok = true;
-    // the 16-lane plan of k_front512, or of k_front1024 (bins up to 527 may be read (times zero weights): the slot keeps 264
-    // words for each of the even / odd arrays)
-    if ((h->fast512 || h->fast1024) &&
-        build_mel_lane_plan(t, h->nb, h->W2, /*max_read_bin=*/h->fast512 ? 511 - 32 : 527, h->plan, /*align=*/h->fast512 ? 2 : 4)) {
-        HIP_TRY(h, h->upload(h->d_mel_lane_w, h->plan.w));
-        HIP_TRY(h, h->upload(h->d_mel_lane_start, h->plan.start));
-        HIP_TRY(h, h->upload(h->d_mel_lane_fid, h->plan.fid));
-        FrontParams probe;
+    // the fused front ends' own plans: build -> set -> the kernel's LDS sum on a fill_front()ed probe decides `ok`
+    auto build_set = [&](MelPlanBuf &buf, int lanes, int align, int max_read_bin) {
+        MelPlan plan;
+        return build_mel_plan(t, h->nb, h->W2, max_read_bin, lanes, align, plan) ? buf.set(h, &plan, 1) : (int)MFX_OK;
+    };
+    FrontParams probe;
+    // the 16-lane plan of k_front512, or of k_front1024 (starts at multiples of 4 bins; bins up to 527 may be read (times zero
+    // weights): the slot keeps 264 words for each of the even / odd arrays)
+    if (h->fast512 || h->fast1024) {
+        if (const int e = build_set(h->plan16, 16, h->fast512 ? 2 : 4, h->fast512 ? 511 - 32 : 527); e != MFX_OK) return e;
         fill_front(h, probe);
-        h->fused_ok = (h->fast512 ? front512_lds_bytes(probe) : front1024_lds_bytes(probe)) <= kLdsCap;
+        h->plan16.ok = h->plan16.ok && (h->fast512 ? front512_lds_bytes(probe) : front1024_lds_bytes(probe)) <= kLdsCap;
     }
     if (h->fast2048) { // k_front2048 walks the filters on the 32 lanes of each of a wave's two frames
-        if (build_mel_wave_plan(t, h->nb, h->W2, /*max_read_bin=*/1039, h->wplan32, /*lanes=*/32)) {
-            HIP_TRY(h, h->upload(h->d_mel32_w, h->wplan32.w));
-            HIP_TRY(h, h->upload(h->d_mel32_start, h->wplan32.start));
-            HIP_TRY(h, h->upload(h->d_mel32_fid, h->wplan32.fid));
-            h->wplan32_ok = true; // (fill_front passes the plan's rounds and stride on only then)
-            FrontParams probe;
-            fill_front(h, probe);
-            h->wplan32_ok = front2048_lds_bytes(probe) <= kLdsCap;
-        }
+        if (const int e = build_set(h->plan32, 32, 2, 1039); e != MFX_OK) return e;
+        fill_front(h, probe);
+        h->plan32.ok = h->plan32.ok && front2048_lds_bytes(probe) <= kLdsCap;
     }
     return MFX_OK;
 }
@@ -200,26 +164,11 @@ void fill_front(const mfx_handle *h, FrontParams &p, bool aligned)
     p.dct_len = h->dl;
     p.cols = h->fcols;
     p.scale = 0.5f / (float)h->W2;
-    p.mel_lane_w = h->d_mel_lane_w.p;
-    p.mel_lane_start = h->d_mel_lane_start.p;
-    p.mel_lane_fid = h->d_mel_lane_fid.p;
+    p.mel16 = h->plan16.arg();
     p.dct_t = h->d_dct_t.p;
-    p.mel_rounds = h->plan.rounds;
-    p.mel_row_stride = h->plan.row_stride;
-    for (int i = 0; i < 8; ++i) p.mel_L[i] = h->plan.L[i];
     p.dct_mode = (h->ceps > 0 && h->fcols <= 16 && h->nb <= 40) ? 1 : 0; // DCT on the matrix pipe
-    p.mel64_w = h->own.w64.p;
-    p.mel64_start = h->own.start64.p;
-    p.mel64_fid = h->own.fid64.p;
-    p.mel64_rounds = h->wplan_ok ? h->wplan.rounds : 0;
-    p.mel64_row_stride = h->wplan_ok ? h->wplan.row_stride : 0;
-    for (int i = 0; i < 8; ++i) p.mel64_L[i] = h->wplan.L[i];
-    p.mel32_w = h->d_mel32_w.p;
-    p.mel32_start = h->d_mel32_start.p;
-    p.mel32_fid = h->d_mel32_fid.p;
-    p.mel32_rounds = h->wplan32_ok ? h->wplan32.rounds : 0;
-    p.mel32_row_stride = h->wplan32_ok ? h->wplan32.row_stride : 0;
-    for (int i = 0; i < 8; ++i) p.mel32_L[i] = h->wplan32.L[i];
+    p.mel64 = h->own.plan64.arg();
+    p.mel32 = h->plan32.arg();
     p.dct_b = h->ceps > 0 ? h->d_dct_b.p : nullptr;
     p.stuff = h->stuff256 ? 512 / h->W2 : 0;
     p.dct_b4 = h->ceps > 0 ? h->d_dct_b4.p : nullptr;
@@ -754,14 +703,14 @@ FrontKind choose_front(const mfx_handle *h, bool aligned)
     // (else: the streaming interface's kernels; PLP has no fused front end: spectrum through HBM, then k_plp.  TRAPS takes
     // whatever the fbank handle of its shape takes: its front end IS that handle's, k_traps follows it)
     const bool allow_fused = !(h->cfg.engine & MFX_ENGINE_STREAM_KERNELS) && !h->plp;
-    if (allow_fused && h->fast512 && h->fused_ok) return kFront512;
+    if (allow_fused && h->fast512 && h->plan16.ok) return kFront512;
     // (k_front1024, windows longer than 512 samples: aligned frames only)
-    if (allow_fused && h->fast1024 && h->fused_ok && (h->W <= 512 || aligned)) return kFront1024;
+    if (allow_fused && h->fast1024 && h->plan16.ok && (h->W <= 512 || aligned)) return kFront1024;
     // (2048 points, any window: stereo, mono on aligned sample pairs, mono at any alignment -- three builds)
-    if (allow_fused && h->fast2048 && h->wplan32_ok) return kFront2048;
+    if (allow_fused && h->fast2048 && h->plan32.ok) return kFront2048;
     // (up to 2048 points the fused form saves the spectrum's round trip through HBM -- 8 KB per frame at 2048 points; at 4096
     // points the tables + per-wave buffers no longer leave enough waves per CU)
-    if (allow_fused && h->W2 <= 2048 && h->wplan_ok) {
+    if (allow_fused && h->W2 <= 2048 && h->own.plan64.ok) {
         FrontParams probe;
         fill_front(h, probe, aligned);
         if (front_wave_lds_bytes(probe, true) <= kLdsCap) return kFrontGenFused;
@@ -994,8 +943,8 @@ extern "C" int mfx_host_mel_table(int32_t num_banks, int32_t fft_size, float sam
     return MFX_OK;
 }
 
-// Lane plan of the mel walk (lanes = 16: the 512-point kernel's MelLanePlan, max_read_bin 479; lanes = 64: the
-// long-transform kernel's MelWavePlan).  Returns the number of rounds (<= 8), or an error.  Outputs (any may be NULL to
+// Lane plan of the mel walk (mfx::MelPlan; lanes = 16: the 512-point kernel's, max_read_bin 479; lanes = 64: the
+// long-transform kernels').  Returns the number of rounds (<= 8), or an error.  Outputs (any may be NULL to
 // query): L[8] bins per lane and round, *row_stride, start / fid [rounds][lanes], w [lanes][row_stride].
 extern "C" int mfx_host_mel_lane_plan(int32_t lanes, int32_t num_banks, int32_t fft_size, const float *weights,
                                       const int32_t *beg, int32_t max_read_bin, int32_t *L, int32_t *row_stride,
@@ -1007,29 +956,18 @@ extern "C" int mfx_host_mel_lane_plan(int32_t lanes, int32_t num_banks, int32_t 
     t.beg.assign(beg, beg + num_banks + 2);
     for (int v : t.beg)
         if (v < 0 || v > fft_size / 2) return MFX_ERR_ARG;
-    int rounds = 0, rs = 0;
-    const int *Ls = nullptr;
-    const std::vector<int32_t> *st = nullptr, *fd = nullptr;
-    const std::vector<float> *ww = nullptr;
-    MelLanePlan p16;
-    MelWavePlan p64;
-    if (lanes == 16) {
-        // (a 1024-point table on 16 lanes is k_front1024's plan: starts at multiples of 4 bins)
-        if (!build_mel_lane_plan(t, num_banks, fft_size, max_read_bin, p16, fft_size == 1024 ? 4 : 2)) return MFX_ERR_CONFIG;
-        rounds = p16.rounds, rs = p16.row_stride, Ls = p16.L, st = &p16.start, fd = &p16.fid, ww = &p16.w;
-    } else {
-        if (!build_mel_wave_plan(t, num_banks, fft_size, max_read_bin, p64, lanes)) return MFX_ERR_CONFIG;
-        rounds = p64.rounds, rs = p64.row_stride, Ls = p64.L, st = &p64.start, fd = &p64.fid, ww = &p64.w;
-    }
-    if (L) std::memcpy(L, Ls, sizeof(int32_t) * 8);
-    if (row_stride) *row_stride = rs;
-    if (start) std::memcpy(start, st->data(), sizeof(int32_t) * st->size());
-    if (fid) std::memcpy(fid, fd->data(), sizeof(int32_t) * fd->size());
+    // (a 1024-point table on 16 lanes is k_front1024's plan: starts at multiples of 4 bins)
+    MelPlan pl;
+    if (!build_mel_plan(t, num_banks, fft_size, max_read_bin, lanes, lanes == 16 && fft_size == 1024 ? 4 : 2, pl)) return MFX_ERR_CONFIG;
+    if (L) std::memcpy(L, pl.L, sizeof(int32_t) * 8);
+    if (row_stride) *row_stride = pl.row_stride;
+    if (start) std::memcpy(start, pl.start.data(), sizeof(int32_t) * pl.start.size());
+    if (fid) std::memcpy(fid, pl.fid.data(), sizeof(int32_t) * pl.fid.size());
     if (w) {
-        if ((int64_t)ww->size() > w_cap) return MFX_ERR_ARG;
-        std::memcpy(w, ww->data(), sizeof(float) * ww->size());
+        if ((int64_t)pl.w.size() > w_cap) return MFX_ERR_ARG;
+        std::memcpy(w, pl.w.data(), sizeof(float) * pl.w.size());
     }
-    return rounds;
+    return pl.rounds;
 }
 
 // Operands of the DCT on the matrix pipe: out[(tile * ksteps + j) * 64 + lane] (build_dct_mfma_operands); returns

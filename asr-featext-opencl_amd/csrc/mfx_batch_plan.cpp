@@ -139,7 +139,7 @@ int plan_fused_delta(mfx_handle *h)
     probe.dl1 = h->l1;
     probe.dl2 = h->l2;
     probe.done_words = done_words;
-    if (!h->fused_ok || probe.dct_mode != 1 || front512_delta_lds_bytes(probe) > kLdsCap) return MFX_OK;
+    if (!h->plan16.ok || probe.dct_mode != 1 || front512_delta_lds_bytes(probe) > kLdsCap) return MFX_OK;
     HIP_TRY(h, h->upload(h->fuse.d_chunks, fch));
     HIP_TRY(h, h->upload(h->fuse.d_blk_chunk_off, coff));
     HIP_TRY(h, h->upload(h->fuse.d_blk_tile_off, toff));
@@ -175,8 +175,8 @@ namespace {
 void split_tail_chunks(mfx_handle *h)
 {
     const int ts = h->cfg.tail_split;
-    const bool f2048 = h->fast2048 && h->wplan32_ok; // (stereo, mono on aligned pairs, mono at any alignment: all three builds)
-    if ((h->fast512 || (h->fast1024 && h->fused_ok) || f2048) && ts >= 0) {
+    const bool f2048 = h->fast2048 && h->plan32.ok; // (stereo, mono on aligned pairs, mono at any alignment: all three builds)
+    if ((h->fast512 || (h->fast1024 && h->plan16.ok) || f2048) && ts >= 0) {
         const size_t n = h->batch.h_chunks.size();
         const size_t tail = std::min<size_t>(n, (size_t)(ts > 0 ? std::min(ts, 64) : f2048 ? 1 : 2) * (f2048 ? 12 : 16) * h->num_cus);
         if (n >= (f2048 ? 2 : 4) * tail) { // only when the launch is long enough for the tail to matter

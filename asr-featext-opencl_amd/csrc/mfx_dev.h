@@ -288,13 +288,15 @@ __device__ __forceinline__ void dct_mfma4s(const float *arow, __amdgpu_buffer_rs
         dct_mfma4_impl<0, DEPTH>(arow, rsrc, table_bytes, lane, group0 / ks, ks, res);
 }
 
-// One frame's mel filterbank on the 64 lanes of a wave (MelWavePlan, lanes = 64) + log: per round every lane walks ONE
+// One frame's mel filterbank on the 64 lanes of a wave (MelPlan, lanes = 64) + log: per round every lane walks ONE
 // filter's bins in ascending order, one chain of multiply-adds (mfcccpu.cpp:206-217); weights from the lane's own
 // zero-padded row (16-byte reads, disjoint bank quads), magnitudes as 8-byte reads from even starts the host spread over
 // the banks.  mag must hold finite values up to the plan's last read.  The log energy of filter fid goes to lmf[fid]; idle
 // lanes park theirs in lmf[park].  s_mw holds mel64_rows(nb) weight rows: filters are dealt to lanes 0, 1, ... of each
 // round, so lanes >= nb never carry one -- they walk the last staged row (same addresses: a broadcast) and park a finite value.
 __host__ __device__ __forceinline__ int mel64_rows(int num_banks) { return num_banks < 64 ? (num_banks > 0 ? num_banks : 1) : 64; }
+// LDS floats of a staged 64-lane plan: the weight rows, start bins and filter ids [rounds][64]
+__host__ inline size_t mel64_lds_floats(int num_banks, int rounds, int row_stride) { return (size_t)mel64_rows(num_banks) * row_stride + (size_t)128 * rounds; }
 
 // LOG = false: the floored energy itself, without the log (k_plp walks power spectra: mfx_plp.hip).
 template <bool LOG = true>
@@ -325,6 +327,32 @@ __device__ __forceinline__ void mel64_walk_log(const float *mag, float *lmf, int
         wrow += L;
         lmf[fid >= 0 ? fid : park] = LOG ? MFX_LOG(fmaxf(acc, 1e-30f)) : fmaxf(acc, 1e-30f);
     }
+}
+
+// The 64-lane mel plan of `table` (k_melcep, k_plp and their row-run forms) from the MelTablesArg into LDS at smem: weights
+// s_mw [mel64_rows][row stride], start bins s_mst and filter ids s_mfid [rounds][64], trip counts s_L [8].  Returns the first
+// word behind them; the caller's __syncthreads() makes them visible.
+struct MelPlanLds {
+    float *s_mw;
+    int *s_mst, *s_mfid, *s_L;
+};
+__device__ __forceinline__ float *stage_mel_plan(float *smem, const MelTablesArg &mel, int num_banks, int table, int tid, unsigned n_threads, MelPlanLds &m)
+{
+    const int RS = mel.row_stride, rounds = mel.rounds;
+    const int WR = mel64_rows(num_banks); // weight rows in LDS (lanes that carry a filter)
+    m.s_mw = smem;                          // [WR][RS]
+    m.s_mst = (int *)(m.s_mw + WR * RS);    // [rounds][64]
+    m.s_mfid = m.s_mst + 64 * rounds;       // [rounds][64]
+    m.s_L = m.s_mfid + 64 * rounds;         // [8]
+    const float *gw = mel.w + (int64_t)table * 64 * RS;
+    const int32_t *gst = mel.start + (int64_t)table * 64 * rounds, *gfid = mel.fid + (int64_t)table * 64 * rounds;
+    for (int i = tid; i < WR * RS; i += n_threads) m.s_mw[i] = gw[i];
+    for (int i = tid; i < 64 * rounds; i += n_threads) {
+        m.s_mst[i] = gst[i];
+        m.s_mfid[i] = gfid[i];
+    }
+    if (tid < 8) m.s_L[tid] = mel.L[table * 8 + tid];
+    return (float *)(m.s_L + 8);
 }
 
 // DCT of the (up to) 4 frames whose log energies wait in lm[4][FS] (lm_fs4), rows out_row0 .. out_row0 + count - 1 of

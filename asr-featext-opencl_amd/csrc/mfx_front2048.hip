@@ -128,7 +128,7 @@ __global__ void __launch_bounds__(kW2048 * 64, (kW2048 + 3) / 4) k_front2048(Fro
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, n_waves = blockDim.x >> 6;
     const int l = lane & 31, half = lane >> 5;
     const int nb = p.num_banks;
-    const int RS = p.mel32_row_stride, rounds = p.mel32_rounds;
+    const int RS = p.mel32.row_stride, rounds = p.mel32.rounds;
     const int lmFS = lm_fs4(nb);
     const int lm_wave = 4 * lmFS; // floats of the 4 waiting frames
 
@@ -163,10 +163,10 @@ __global__ void __launch_bounds__(kW2048 * 64, (kW2048 + 3) / 4) k_front2048(Fro
         s_cs[i] = make_float4(a.x, a.y, b.x, b.y);
     }
     if (tid < 2) s_cs512[tid] = tid == 0 ? ((const float2 *)p.twid_split)[512] : make_float2(0.f, 0.f);
-    for (int i = tid; i < 32 * RS; i += blockDim.x) s_mw[i] = p.mel32_w[i];
+    for (int i = tid; i < 32 * RS; i += blockDim.x) s_mw[i] = p.mel32.w[i];
     for (int i = tid; i < 32 * rounds; i += blockDim.x) {
-        s_mst[i] = p.mel32_start[i];
-        s_mfid[i] = p.mel32_fid[i];
+        s_mst[i] = p.mel32.start[i];
+        s_mfid[i] = p.mel32.fid[i];
     }
     for (int i = lane; i < 2 * kPlane + lm_wave; i += 64) s_wave[i] = 0.f; // (words the walk may read but nothing writes)
     __syncthreads();
@@ -379,7 +379,7 @@ __global__ void __launch_bounds__(kW2048 * 64, (kW2048 + 3) / 4) k_front2048(Fro
                     // (the next round's first bin is in flight during this round's trips: a round starts with ONE dependent LDS
                     // round trip -- its first magnitudes -- instead of two; the filter id is only needed at the round's end)
                     const int st_next = s_mst[(r + 1 < rounds ? r + 1 : r) * 32 + l], fid = s_mfid[r * 32 + l];
-                    const int L = p.mel32_L[r];
+                    const int L = p.mel32.L[r];
                     const float *mg = plane + st;
                     float acc = 0.f;
                     int s2 = 0;
@@ -515,7 +515,7 @@ namespace {
 int lm_fs(const FrontParams &p) { return lm_fs4(p.num_banks); }
 size_t lds_bytes_2048(const FrontParams &p, int n_waves)
 {
-    const size_t f = front2048_table_floats(p.mel32_rounds, p.mel32_row_stride, rows2048(p.window_size)) +
+    const size_t f = front2048_table_floats(p.mel32.rounds, p.mel32.row_stride, rows2048(p.window_size)) +
                      (size_t)n_waves * (2 * kPlane + 4 * (size_t)lm_fs(p)) + 4;
     return f * sizeof(float);
 }

@@ -94,7 +94,7 @@ __global__ void __launch_bounds__(kThreads, 4) k_front512(FrontParams p) // (4 w
 
     // ---- LDS carve: shared tables, then one 4-slot region per wave
     const int cols = p.cols;
-    const int rounds = p.mel_rounds, RS = p.mel_row_stride, DS = p.dct_stride, nb_pad = p.nb_pad;
+    const int rounds = p.mel16.rounds, RS = p.mel16.row_stride, DS = p.dct_stride, nb_pad = p.nb_pad;
     // Lane-major tables: lane l reads ITS window pairs / twiddles as 16-byte words (two complex values per
     // ds_read_b128, half the LDS instructions of the 8-byte form and whole batches in flight); the row strides
     // (36 and 20 dwords) put the 16 lanes of a b128 access group on disjoint bank quads.  The 4 frames of a
@@ -127,8 +127,8 @@ __global__ void __launch_bounds__(kThreads, 4) k_front512(FrontParams p) // (4 w
     if (!TO_SPEC) {
         stage_mel_weights(s_melw, p, tid, kThreads);
         for (int i = tid; i < 16 * rounds; i += kThreads) {
-            s_mmeta[2 * i] = p.mel_lane_start[i];
-            const int fid = p.mel_lane_fid[i];
+            s_mmeta[2 * i] = p.mel16.start[i];
+            const int fid = p.mel16.fid[i];
             // (matrix-pipe form: idle lanes park their value in a word nobody reads)
             s_mmeta[2 * i + 1] = p.dct_mode != 1 ? fid : fid < 0 ? 4 * kDctQPad : dct_q_pos(fid);
         }
@@ -426,7 +426,7 @@ __global__ void __launch_bounds__(kThreads, 4) k_front512(FrontParams p) // (4 w
                     float *lm = xb + kMelOff + 8 * slot;
                     const int2 *mmeta = (const int2 *)s_mmeta + l;
                     for (int r = 0; r < rounds; ++r) {
-                        const int L = p.mel_L[r];
+                        const int L = p.mel16.L[r];
                         const int2 mt = *mmeta;
                         mmeta += 16;
                         const float *mg = mg0 + mt.x;
@@ -462,7 +462,7 @@ __global__ void __launch_bounds__(kThreads, 4) k_front512(FrontParams p) // (4 w
                     float *melbuf = xb + kMelOff;
                     const int2 *mmeta = (const int2 *)s_mmeta + l;
                     for (int r = 0; r < rounds; ++r) {
-                        const int L = p.mel_L[r];
+                        const int L = p.mel16.L[r];
                         const int2 mt = *mmeta;
                         mmeta += 16;
                         const float *mg = mg0 + mt.x;
@@ -566,7 +566,7 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES / 4) k_front1024(FrontParams
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lane = tid & 63;
     const int slot = lane >> 4, l = lane & 15;
-    const int cols = p.cols, rounds = p.mel_rounds, RS = p.mel_row_stride;
+    const int cols = p.cols, rounds = p.mel16.rounds, RS = p.mel16.row_stride;
 
     float *s_win = smem;                               // [16 l][kTabStride]: E window pairs (w[2n], w[2n+1]) * 0.5 / W2
     float *s_winO = s_win + 16 * kTabStride;           // [16 l][kTabStrideO]: (A, B, C, D) of pair n = l + 16 m
@@ -592,8 +592,8 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES / 4) k_front1024(FrontParams
     }
     stage_mel_weights(s_melw, p, tid, WAVES * 64);
     for (int i = tid; i < 16 * rounds; i += WAVES * 64) {
-        s_mmeta[2 * i] = p.mel_lane_start[i] >> 1; // (index into the even / odd magnitude arrays)
-        const int fid = p.mel_lane_fid[i];
+        s_mmeta[2 * i] = p.mel16.start[i] >> 1; // (index into the even / odd magnitude arrays)
+        const int fid = p.mel16.fid[i];
         s_mmeta[2 * i + 1] = fid < 0 ? 4 * kDctQL : fid; // idle lanes park their value in a word nobody reads
     }
     for (int i = tid; i < 64 * kDctQL; i += WAVES * 64) {
@@ -814,7 +814,7 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES / 4) k_front1024(FrontParams
             for (int r = 0; r < kDctQL / 4; ++r) {
                 le[r] = 0.f;
                 if (r < rounds) {
-                    const int L = p.mel_L[r];
+                    const int L = p.mel16.L[r];
                     const int first = mmeta[16 * r].x;
                     const float *me = xb + first, *mo = xb + kOddOffL + first;
                     float acc = 0.f;
@@ -890,8 +890,8 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES / 4) k_front1024(FrontParams
 size_t front512_lds_bytes(const FrontParams &p)
 {
     size_t f = 2 * 16 * kTabStride + 16 * kSplitStride;  // window pairs, pass twiddles, split twiddles
-    f += (size_t)16 * p.mel_row_stride;                  // per-lane mel weights
-    f += (size_t)32 * p.mel_rounds;                      // per-lane bin starts + filter ids
+    f += (size_t)16 * p.mel16.row_stride;                // per-lane mel weights
+    f += (size_t)32 * p.mel16.rounds;                    // per-lane bin starts + filter ids
     f += !p.dct ? 0 : p.dct_mode == 1 ? (size_t)64 * kDctQPad : (size_t)p.cols * p.dct_stride; // DCT table (either form)
     f += kWaves * 4 * kSlot;                             // 4 frame slots per wave
     f += 4;                                              // block-local work counter
@@ -923,8 +923,8 @@ hipError_t launch512(const FrontParams &p_in, hipStream_t stream)
 {
     FrontParams p = p_in;
     if (S) { // spectrum only: no mel / DCT tables in LDS
-        p.mel_rounds = 0;
-        p.mel_row_stride = 0;
+        p.mel16.rounds = 0;
+        p.mel16.row_stride = 0;
         p.dct = nullptr;
         p.dct_mode = 0;
     }
@@ -944,7 +944,7 @@ hipError_t launch512(const FrontParams &p_in, hipStream_t stream)
 size_t front1024_lds_bytes(const FrontParams &p, int waves)
 {
     size_t f = 2 * 16 * kTabStride + 16 * kTabStrideO + 2 * 16 * kSplitStride; // window pairs (E, O), pass twiddles, split twiddles (E, O)
-    f += (size_t)16 * p.mel_row_stride + (size_t)32 * p.mel_rounds;             // per-lane mel weights, bin starts + filter ids
+    f += (size_t)16 * p.mel16.row_stride + (size_t)32 * p.mel16.rounds;         // per-lane mel weights, bin starts + filter ids
     f += (size_t)64 * kDctQL;                                                 // matrix-pipe operands of the DCT
     f += (size_t)waves * 4 * kSlotL + 4;                                        // 4 frame slots per wave, work counter
     return f * sizeof(float);

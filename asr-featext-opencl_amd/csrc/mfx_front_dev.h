@@ -215,7 +215,7 @@ __device__ __forceinline__ void stage_split(float *dst, int i, float2 v)
 }
 __device__ __forceinline__ void stage_mel_weights(float *s_melw, const FrontParams &p, int tid, int threads)
 {
-    for (int i = tid; i < 16 * p.mel_row_stride; i += threads) s_melw[i] = p.mel_lane_w[i];
+    for (int i = tid; i < 16 * p.mel16.row_stride; i += threads) s_melw[i] = p.mel16.w[i];
 }
 } // namespace
 } // namespace mfx

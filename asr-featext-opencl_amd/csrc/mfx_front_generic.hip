@@ -45,9 +45,9 @@ __global__ void __launch_bounds__(256, MFX_WAVE_MINW) k_front_wave(FrontParams p
     };
     const int W2 = p.fft_size, M = W2 >> 1;
     const int nb = p.num_banks, dl = p.dct_len;
-    // shared tables (FUSED only: the 64-lane mel plan, MelWavePlan), then per wave: two complex buffers of M points and the
+    // shared tables (FUSED only: the 64-lane mel plan, MelPlan), then per wave: two complex buffers of M points and the
     // log mel energies of 4 frames waiting for the DCT (lm_fs4)
-    const int RS = FUSED ? p.mel64_row_stride : 0, rounds = FUSED ? p.mel64_rounds : 0;
+    const int RS = FUSED ? p.mel64.row_stride : 0, rounds = FUSED ? p.mel64.rounds : 0;
     const int WR = mel64_rows(nb);                            // weight rows in LDS (lanes that carry a filter)
     float *s_mw = smem;                                       // [WR][RS]
     int *s_mst = (int *)(s_mw + WR * RS);                     // [rounds][64]
@@ -59,10 +59,10 @@ __global__ void __launch_bounds__(256, MFX_WAVE_MINW) k_front_wave(FrontParams p
     float *lm = s_wave + 4 * M;                               // [4][FS]
     (void)dl;
     if (FUSED) {
-        for (int i = tid; i < WR * RS; i += 256) s_mw[i] = p.mel64_w[i];
+        for (int i = tid; i < WR * RS; i += 256) s_mw[i] = p.mel64.w[i];
         for (int i = tid; i < 64 * rounds; i += 256) {
-            s_mst[i] = p.mel64_start[i];
-            s_mfid[i] = p.mel64_fid[i];
+            s_mst[i] = p.mel64.start[i];
+            s_mfid[i] = p.mel64.fid[i];
         }
         for (int i = lane; i < 4 * M + 4 * FS; i += G) s_wave[i] = 0.f; // words read before they are written: finite
     }
@@ -164,7 +164,7 @@ __global__ void __launch_bounds__(256, MFX_WAVE_MINW) k_front_wave(FrontParams p
             if (FUSED) {
                 // mel walk on the wave's 64 lanes + log (the magnitudes sit in the 2 M floats of the other buffer: the plan
                 // reads at most up to word W2 - 1, stale but finite beyond bin M); DCT once per 4 frames and at the chunk's end
-                mel64_walk_log(mag, lm + (f & 3) * FS, FS - 1, s_mw, s_mst, s_mfid, p.mel64_L, rounds, RS, lane, WR);
+                mel64_walk_log(mag, lm + (f & 3) * FS, FS - 1, s_mw, s_mst, s_mfid, p.mel64.L, rounds, RS, lane, WR);
                 group_sync();
                 if ((f & 3) == 3 || f == nf - 1) {
                     const int g0 = f & ~3;
@@ -298,9 +298,9 @@ __global__ void __launch_bounds__(LOG2M >= 11 ? 256 : (LOG2M == 10 && FUSED) ? M
     float2 *s_cs = s_tw + M;                       // [M/2 + 1]  -i W_{2M}^k (one per bin pair), padded to even
     float2 *s_win = s_cs + (M / 2 + 2);            // [nwin] (w[2n], w[2n+1]) * 0.5 / W2: whole 64-pair rows that carry taps
     const int nwin = reg_window_pairs(p.window_size, M);
-    // FUSED: the mel walk's per-lane weight rows and plan (MelWavePlan), then per wave the complex buffer and the
+    // FUSED: the mel walk's per-lane weight rows and plan (MelPlan), then per wave the complex buffer and the
     // log mel energies of 4 frames (the DCT runs on the matrix pipe once per 4 frames)
-    const int RS = FUSED ? p.mel64_row_stride : 0, rounds = FUSED ? p.mel64_rounds : 0;
+    const int RS = FUSED ? p.mel64.row_stride : 0, rounds = FUSED ? p.mel64.rounds : 0;
     const int WR = mel64_rows(nb);                             // weight rows in LDS (lanes that carry a filter)
     float *s_mw = (float *)(s_win + nwin);                     // [WR][RS]
     int *s_mst = (int *)(s_mw + WR * RS);                      // [rounds][64]
@@ -324,10 +324,10 @@ __global__ void __launch_bounds__(LOG2M >= 11 ? 256 : (LOG2M == 10 && FUSED) ? M
     }
     for (int i = tid; i <= M / 2; i += blockDim.x) s_cs[i] = ((const float2 *)p.twid_split)[i];
     if (FUSED) {
-        for (int i = tid; i < WR * RS; i += blockDim.x) s_mw[i] = p.mel64_w[i];
+        for (int i = tid; i < WR * RS; i += blockDim.x) s_mw[i] = p.mel64.w[i];
         for (int i = tid; i < 64 * rounds; i += blockDim.x) {
-            s_mst[i] = p.mel64_start[i];
-            s_mfid[i] = p.mel64_fid[i];
+            s_mst[i] = p.mel64.start[i];
+            s_mfid[i] = p.mel64.fid[i];
         }
         for (int i = lane; i < 4 * nbp; i += 64) lm[i] = 0.f; // words the walk never writes meet zero operands: keep them finite
     }
@@ -565,7 +565,7 @@ __global__ void __launch_bounds__(LOG2M >= 11 ? 256 : (LOG2M == 10 && FUSED) ? M
                     float *lmf = lm + (f & 3) * nbp;
                     const float *wrow = s_mw + (lane < WR ? lane : WR - 1) * RS;
                     auto one_round = [&](int r, int st, int fid) {
-                        const int L = p.mel64_L[r];
+                        const int L = p.mel64.L[r];
                         const float *mg = mag + st;
                         float acc = 0.f;
                         int s2 = 0;
@@ -648,7 +648,7 @@ size_t front_reg_lds_floats(const FrontParams &p, bool fused, int n_waves)
 {
     const size_t M = (size_t)p.fft_size >> 1;
     size_t f = 2 * M + 2 * (M / 2 + 2) + 2 * (size_t)reg_window_pairs(p.window_size, (int)M); // pass twiddles, split twiddles, window pairs
-    if (fused) f += (size_t)mel64_rows(p.num_banks) * p.mel64_row_stride + (size_t)128 * p.mel64_rounds; // lane weight rows, starts + filter ids
+    if (fused) f += mel64_lds_floats(p.num_banks, p.mel64.rounds, p.mel64.row_stride); // lane weight rows, starts + filter ids
 #ifdef MFX_REG_PADDED
     const size_t MP = M + (M >> (p.fft_size == 1024 ? 3 : 4)); // padded buffer (pad_idx)
 #else
@@ -724,7 +724,7 @@ size_t front_wave_lds_bytes(const FrontParams &p, bool fused)
     }
     const int M = p.fft_size >> 1;
     size_t f = 0;
-    if (fused) f += (size_t)mel64_rows(p.num_banks) * p.mel64_row_stride + (size_t)128 * p.mel64_rounds; // lane weight rows, starts + filter ids
+    if (fused) f += mel64_lds_floats(p.num_banks, p.mel64.rounds, p.mel64.row_stride); // lane weight rows, starts + filter ids
     f += 4 * ((size_t)4 * M + (fused ? 4 * (size_t)lm_fs4(p.num_banks) : 0));
     return f * sizeof(float);
 }

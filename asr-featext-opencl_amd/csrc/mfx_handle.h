@@ -98,13 +98,40 @@ struct PinnedBuf {
     }
 };
 
+// Mel lane plans in device memory (mfx::MelPlan -> MelPlanArg / MelTablesArg, mfx_kernels.h): the one owner of the arrays a
+// kernel walks.  `n` plans (the 64-lane plans of a sweep's tables) are padded to the longest plan's row stride: a row's rounds
+// lie back to back from its start, so padding at the end changes nothing; one plan keeps its own stride.
+struct MelPlanBuf {
+    DevBuf<float> w;               // [n][lanes][row_stride]
+    DevBuf<int32_t> start, fid, L; // [n][rounds][lanes] twice, [n][8]
+    int n = 0, rounds = 0, row_stride = 0, L0[8] = {}; // (rounds and L0 are plan 0's: every plan of a set has ceil(nb / lanes) rounds)
+    bool ok = false;               // built, in place AND the LDS of the kernel that walks it fits (whoever calls set() decides the latter)
+    // the host fields alone: what the LDS sums need before anything is replaced
+    void shape(const mfx::MelPlan *plans, int count)
+    {
+        n = count, rounds = plans[0].rounds, row_stride = 0;
+        for (int a = 0; a < count; ++a) row_stride = std::max(row_stride, plans[a].row_stride);
+        std::copy(plans[0].L, plans[0].L + 8, L0);
+    }
+    // shape() + upload (defined behind mfx_handle); ok on success.  The caller has waited for whatever reads the old arrays.
+    int set(mfx_handle *h, const mfx::MelPlan *plans, int count);
+    // plan 0 as a front end takes it; rounds = row_stride = 0 unless ok, so that no LDS sum and no launch counts on it
+    mfx::MelPlanArg arg() const
+    {
+        mfx::MelPlanArg a{w.p, start.p, fid.p, {}, ok ? rounds : 0, ok ? row_stride : 0};
+        std::copy(L0, L0 + 8, a.L);
+        return a;
+    }
+    // all n plans as k_melcep / k_plp take them (valid from shape() on: build_cep_tables probes with it)
+    mfx::MelTablesArg tables_arg() const { return {w.p, start.p, fid.p, L.p, rounds, row_stride}; }
+};
+
 // What k_melcep / k_plp read for n warp factors: the mel tables (mel_w [n][2 * W2], mel_beg [n][nb + 2]), one 64-lane
-// plan per table padded to a common row stride (w64 [n][64][row_stride], start64 / fid64 [n][rounds][64], L64 [n][8]) and,
-// for PLP, the equal-loudness weights (eql [n][nb]).
+// plan per table (plan64) and, for PLP, the equal-loudness weights (eql [n][nb]).
 struct CepTables {
-    DevBuf<float> mel_w, w64, eql;
-    DevBuf<int32_t> mel_beg, start64, fid64, L64;
-    int rounds = 0, row_stride = 0;
+    DevBuf<float> mel_w, eql;
+    DevBuf<int32_t> mel_beg;
+    MelPlanBuf plan64;
     std::vector<float> alphas; // the warp factors the tables hold (empty: none)
     bool holds(const float *a, int n) const { return !alphas.empty() && (int)alphas.size() == n && std::equal(a, a + n, alphas.begin()); }
 };
@@ -547,24 +574,18 @@ struct mfx_handle {
     DevBuf<float> d_plp_idft, d_plp_lift;
     // TRAPS: k_traps' operand table (matrix-pipe or vector form, by MFX_ENGINE_TRAPS_VALU)
     DevBuf<float> d_traps_b;
-    // 512-point kernel: per-lane mel plan + transposed DCT matrix
-    DevBuf<float> d_mel_lane_w, d_dct_t;
-    DevBuf<int32_t> d_mel_lane_start, d_mel_lane_fid;
-    mfx::MelLanePlan plan;
-    // wave-per-frame kernels (k_front_reg, fused): the 64-lane mel plan of `own` + DCT operands for the matrix pipe
-    mfx::MelWavePlan wplan;
-    bool wplan_ok = false;
+    // k_front512 / k_front1024: the 16-lane plan + the transposed DCT matrix
+    MelPlanBuf plan16;
+    DevBuf<float> d_dct_t;
+    // wave-per-frame kernels (k_front_reg, fused) walk own.plan64; DCT operands for the matrix pipe
     DevBuf<float> d_dct_b;
     DevBuf<float> d_dct_b4;                          // k_front2048: DCT operands as 16-byte words
     DevBuf<float> d_dct_b4s;                         // k_front2048: the split form for <= 40 columns (or empty)
     int dct_split = 0;
-    DevBuf<float> d_mel32_w;                         // k_front2048: the 32-lane plan
-    DevBuf<int32_t> d_mel32_start, d_mel32_fid;
-    mfx::MelWavePlan wplan32;
-    bool fast2048 = false, wplan32_ok = false;
+    MelPlanBuf plan32;                               // k_front2048: the 32-lane plan
+    bool fast2048 = false;
     int dct_tiles = 0, dct_ksteps = 0;
     int dct_stride = 0, nb_pad = 0;
-    bool fused_ok = false;
     std::vector<float> h_dct;
     // scratch both interfaces use
     DevBuf<float> d_spec;                // streaming spectrum (mfx_debug_read kind 3); the batch runner hands it to dev-build stamps
@@ -647,6 +668,29 @@ inline int UttTilingBuf::set(mfx_handle *h, int32_t rows_per_item)
     return MFX_OK;
 }
 
+inline int MelPlanBuf::set(mfx_handle *h, const mfx::MelPlan *plans, int count)
+{
+    ok = false;
+    shape(plans, count);
+    const size_t lanes = (size_t)plans[0].lanes, meta = lanes * rounds;
+    std::vector<float> pw(count * lanes * row_stride, 0.f);
+    std::vector<int32_t> pst(count * meta), pfid(count * meta), pL((size_t)count * 8);
+    for (int a = 0; a < count; ++a) {
+        const mfx::MelPlan &pl = plans[a];
+        for (size_t j = 0; j < lanes; ++j)
+            std::copy(pl.w.begin() + j * pl.row_stride, pl.w.begin() + (j + 1) * pl.row_stride, pw.begin() + (a * lanes + j) * row_stride);
+        std::copy(pl.start.begin(), pl.start.end(), pst.begin() + a * meta);
+        std::copy(pl.fid.begin(), pl.fid.end(), pfid.begin() + a * meta);
+        std::copy(pl.L, pl.L + 8, pL.begin() + (size_t)a * 8);
+    }
+    HIP_TRY(h, h->upload(w, pw));
+    HIP_TRY(h, h->upload(start, pst));
+    HIP_TRY(h, h->upload(fid, pfid));
+    HIP_TRY(h, h->upload(L, pL));
+    ok = true;
+    return MFX_OK;
+}
+
 // top of every entry that needs the device: a handle, and not a planning one
 #define MFX_DEVICE_ENTRY(h)                                                                                                  \
     do {                                                                                                                     \
@@ -718,8 +762,7 @@ void fill_front(const mfx_handle *h, mfx::FrontParams &p);
 void fill_front(const mfx_handle *h, mfx::FrontParams &p, bool aligned);
 void fill_traps(const mfx_handle *h, mfx::TrapsParams &p);
 int refresh_mel(mfx_handle *h);
-int build_cep_tables(mfx_handle *h, const float *alphas, int n, CepTables &t, mfx::MelTable *first = nullptr,
-                     mfx::MelWavePlan *first_plan = nullptr);
+int build_cep_tables(mfx_handle *h, const float *alphas, int n, CepTables &t, mfx::MelTable *first = nullptr);
 int launch_cepstra(mfx_handle *h, const CepTables &t, const float *spec, int64_t n_rows, float *feat, int feat_pitch,
                    int n_tables, int64_t feat_table_stride, float *r_out, hipStream_t stream);
 // the row-run form: the runs of `rr` (host copies h_off / h_runs) of each of t's tables, absolute rows of spec and feat

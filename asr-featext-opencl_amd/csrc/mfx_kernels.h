@@ -75,6 +75,22 @@ struct DeltaTile {
     int32_t dep_lo, dep_hi; // block-local chunk indices whose statics the tile reads (inclusive)
 };
 
+// A mel lane plan (mfx::MelPlan, mfx_tables.h) as a kernel takes it: the filters dealt to the `lanes` lanes of a frame in
+// `rounds` rounds, round r padded to L[r] bins; lane j's weights for all rounds are one row of w.
+struct MelPlanArg {
+    const float *w;               // [lanes][row_stride]
+    const int32_t *start, *fid;   // [rounds][lanes] first bin read / filter index or -1
+    int32_t L[8];
+    int32_t rounds, row_stride;   // (last: k_front512 reads them and the two DCT sizes behind mel16 in one scalar load)
+};
+// The 64-lane plans of k_melcep / k_plp, one per table of a sweep, all padded to the same row stride
+struct MelTablesArg {
+    const float *w;               // [n_tables][64][row_stride]
+    const int32_t *start, *fid;   // [n_tables][rounds][64]
+    const int32_t *L;             // [n_tables][8] bins per lane and round (device memory)
+    int32_t rounds, row_stride;
+};
+
 struct FrontParams {
     const int16_t *pcm;
     int64_t pcm_total;        // int16 elements readable behind `pcm` (all channels)
@@ -102,28 +118,14 @@ struct FrontParams {
     const float *mel_w;       // [2][W2]
     const int32_t *mel_beg;   // [nb+2]
     const float *dct;         // [nb][dct_len] or nullptr when ceps_len == 0
-    // 512 fast path: mel filters dealt to the 16 lanes of a frame in `mel_rounds` rounds, round r
-    // padded to mel_L[r] bins (multiple of 4); lane j's weights for all rounds are one row of mel_lane_w
-    const float *mel_lane_w;      // [16][mel_row_stride]
-    const int32_t *mel_lane_start;// [mel_rounds][16] first bin of the lane's filter in that round
-    const int32_t *mel_lane_fid;  // [mel_rounds][16] filter index or -1
+    // the lane plans (rounds = row_stride = 0: the handle has none that fits the kernel)
+    MelPlanArg mel16;             // 512 fast path and k_front1024: the 16 lanes of a frame
+    int32_t dct_stride, nb_pad;   // (directly behind mel16: see MelPlanArg)
     const float *dct_t;           // [cols][dct_stride] transposed DCT matrix, rows zero padded to nb_pad
     int32_t dct_mode;             // 0: DCT from the LDS mel scratch; 1: on the matrix pipe, v_mfma_f32_16x16x4_f32 per
                                   //    4 frames (cols <= 16, num_banks <= 40; matrix from `dct`, held in registers)
-    int32_t mel_rounds, mel_row_stride, dct_stride, nb_pad;
-    int32_t mel_L[8];
-    // wave-per-frame lane plan (k_front_reg / k_front_wave fused): filters dealt to the 64 lanes of the frame's wave in rounds
-    const float *mel64_w;         // [64][mel64_row_stride]
-    const int32_t *mel64_start;   // [mel64_rounds][64]
-    const int32_t *mel64_fid;     // [mel64_rounds][64]
-    int32_t mel64_rounds, mel64_row_stride;
-    int32_t mel64_L[8];
-    // two-frames-per-wave lane plan (k_front2048): filters dealt to the 32 lanes of a frame in rounds of 32
-    const float *mel32_w;         // [32][mel32_row_stride]
-    const int32_t *mel32_start;   // [mel32_rounds][32]
-    const int32_t *mel32_fid;     // [mel32_rounds][32]
-    int32_t mel32_rounds, mel32_row_stride;
-    int32_t mel32_L[8];
+    MelPlanArg mel64;             // wave-per-frame kernels (k_front_reg / k_front_wave fused): the 64 lanes of the frame's wave
+    MelPlanArg mel32;             // k_front2048: the 32 lanes of each of a wave's two frames
     // DCT on the matrix pipe: B operands [dct_tiles][dct_ksteps][64] (build_dct_mfma_operands), read from L1 / L2
     const float *dct_b;
     const float *dct_b4;          // 4x4x1 form: [ceil(dct_len / 64)][dct_ksteps][64][4] (k_front2048, build_dct_mfma_operands4)
@@ -161,12 +163,7 @@ struct MelcepParams {
     const int32_t *mel_beg;
     const float *dct;
     int32_t num_banks, dct_len, cols;
-    // 64-lane mel plan (MelWavePlan), one per table of a sweep, all padded to the same row stride
-    const float *mel64_w;         // [n_tables][64][mel64_row_stride]
-    const int32_t *mel64_start;   // [n_tables][mel64_rounds][64]
-    const int32_t *mel64_fid;     // [n_tables][mel64_rounds][64]
-    const int32_t *mel64_L;       // [n_tables][8] bins per lane and round (device memory)
-    int32_t mel64_rounds, mel64_row_stride;
+    MelTablesArg mel;             // the 64-lane plan of every table
     int32_t mag_floats;           // LDS floats of a wave's magnitude buffer: >= spec_pitch and > the plans' last read, x4
     const float *dct_b4;          // DCT operands of the 4x4x1 form (build_dct_mfma_operands4) or nullptr
     int32_t dct_ksteps;
@@ -193,11 +190,7 @@ struct PlpParams {
     int32_t ceps_len;             // C >= 1
     int32_t want_c0;
     int32_t cols;                 // ceps_len + (want_c0 ? 1 : 0)
-    const float *mel64_w;         // as MelcepParams
-    const int32_t *mel64_start;
-    const int32_t *mel64_fid;
-    const int32_t *mel64_L;
-    int32_t mel64_rounds, mel64_row_stride;
+    MelTablesArg mel;
     int32_t mag_floats;
     const float *eql;             // [n_tables][num_banks] equal-loudness weights e_m (centres move with alpha)
     const float *idft;            // [lpc_order + 1][num_banks + 2] cosine basis of the autocorrelation (mfx_host_plp_tables)

@@ -10,7 +10,7 @@
 //   row = [w_1 c_1 .. w_C c_C (, c_0)]
 //
 // Layout: a wave takes 64 consecutive rows.  Phase 1 walks their filterbanks one row at a time on the wave's 64 lanes
-// (MelWavePlan, mel64_walk_log without the log) into LDS rows of RP floats (RP odd: lane l's row is bank-disjoint from its
+// (MelPlan, mel64_walk_log without the log) into LDS rows of RP floats (RP odd: lane l's row is bank-disjoint from its
 // neighbours'), E_m at word m + 1.  Phase 2 gives each lane one row: cube roots, the autocorrelation, the recursion and
 // the cepstrum run in registers (a[], r[] unrolled to PMAX), c_n goes back to the lane's LDS row, and the wave then writes
 // the 64 rows out with consecutive lanes on consecutive words.  blockIdx.y = filterbank of a VTLN sweep.
@@ -55,7 +55,7 @@ template <int PMAX>
 size_t plp_lds_bytes_t(const PlpParams &p, int n_waves)
 {
     const size_t nb = (size_t)p.num_banks;
-    const size_t f = (size_t)mel64_rows(p.num_banks) * p.mel64_row_stride + (size_t)128 * p.mel64_rounds + 8 +
+    const size_t f = mel64_lds_floats(p.num_banks, p.mel.rounds, p.mel.row_stride) + 8 +
                      (nb + 2) * plp_ps(PMAX) + ((nb + 3) & ~(size_t)3) + (((size_t)p.ceps_len + 3) & ~(size_t)3) +
                      (size_t)n_waves * ((size_t)p.mag_floats + (size_t)kPlpRows * plp_rp(p.num_banks, p.ceps_len));
     return f * sizeof(float);

@@ -1,6 +1,6 @@
-// mfx_plp_body.h -- the text of k_plp, included twice by mfx_plp.hip: MFX_PLP_RUNS 0 is k_plp itself (the same tokens as
-// ever: the same ISA), 1 is its row-run form k_plp_runs -- as k_melcep_runs (mfx_tail.hip) with groups of 64 rows: a
-// wave's 64 rows come from ONE run, phase 2 runs with the table's own eql.  Not a header in its own right.
+// mfx_plp_body.h -- the text of k_plp, included twice by mfx_plp.hip: MFX_PLP_RUNS 0 is k_plp itself, 1 is its row-run form
+// k_plp_runs -- as k_melcep_runs (mfx_tail.hip) with groups of 64 rows: a wave's 64 rows come from ONE run, phase 2 runs with
+// the table's own eql.  Not a header in its own right.
 template <int PMAX>
 #if MFX_PLP_RUNS
 __global__ void __launch_bounds__(256) k_plp_runs(PlpParams p, RowRuns runs)
@@ -10,28 +10,23 @@ __global__ void __launch_bounds__(256) k_plp(PlpParams p)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, n_waves = blockDim.x >> 6;
-    const int nb = p.num_banks, RS = p.mel64_row_stride, rounds = p.mel64_rounds, MF = p.mag_floats;
+    const int nb = p.num_banks, RS = p.mel.row_stride, rounds = p.mel.rounds, MF = p.mag_floats;
     const int N = nb + 2, order = p.lpc_order, C = p.ceps_len;
     constexpr int PS = plp_ps(PMAX);
     const int RP = plp_rp(nb, C);
     const int WR = mel64_rows(nb);
-    float *s_mw = smem;                              // [WR][RS]
-    int *s_mst = (int *)(s_mw + WR * RS);            // [rounds][64]
-    int *s_mfid = s_mst + 64 * rounds;               // [rounds][64]
-    int *s_L = s_mfid + 64 * rounds;                 // [8]
-    float *s_idft = (float *)(s_L + 8);              // [N][PS]
-    float *s_eql = s_idft + N * PS;                  // [nb, x4]
-    float *s_lift = s_eql + ((nb + 3) & ~3);         // [C, x4]
-    float *s_wave = s_lift + ((C + 3) & ~3) + wave * (MF + kPlpRows * RP);
-    float *mag = s_wave, *rows = s_wave + MF;
 
     const int table = blockIdx.y;
 #if MFX_PLP_RUNS
     int run0, run1; // the table's runs that reach into the window (none: nothing to stage; uniform over the block)
     if (!runs_in_window(runs, table, run0, run1)) return;
 #endif
-    const float *gw = p.mel64_w + (int64_t)table * 64 * RS;
-    const int32_t *gst = p.mel64_start + (int64_t)table * 64 * rounds, *gfid = p.mel64_fid + (int64_t)table * 64 * rounds;
+    MelPlanLds plan;
+    float *s_idft = stage_mel_plan(smem, p.mel, nb, table, tid, blockDim.x, plan); // [N][PS]
+    float *s_eql = s_idft + N * PS;                  // [nb, x4]
+    float *s_lift = s_eql + ((nb + 3) & ~3);         // [C, x4]
+    float *s_wave = s_lift + ((C + 3) & ~3) + wave * (MF + kPlpRows * RP);
+    float *mag = s_wave, *rows = s_wave + MF;
     const float *geql = p.eql + (int64_t)table * nb;
 #if MFX_PLP_RUNS
     float *feat = p.feat; // one output, absolute rows
@@ -40,12 +35,6 @@ __global__ void __launch_bounds__(256) k_plp(PlpParams p)
     float *feat = p.feat + (int64_t)table * p.feat_table_stride;
     float *r_out = table == 0 ? p.r_out : nullptr;
 #endif
-    for (int i = tid; i < WR * RS; i += blockDim.x) s_mw[i] = gw[i];
-    for (int i = tid; i < 64 * rounds; i += blockDim.x) {
-        s_mst[i] = gst[i];
-        s_mfid[i] = gfid[i];
-    }
-    if (tid < 8) s_L[tid] = p.mel64_L[table * 8 + tid];
     for (int i = tid; i < N * PS; i += blockDim.x) { // transposed: one 16-byte broadcast read per band and 4 orders
         const int m = i / PS, k = i - m * PS;
         s_idft[i] = k <= order ? p.idft[k * N + m] : 0.f;
@@ -77,7 +66,7 @@ __global__ void __launch_bounds__(256) k_plp(PlpParams p)
             }
             if (nbins + lane < 4 * q4) mag[nbins + lane] = 0.f; // padding words are never written in memory
             wave_sync();
-            mel64_walk_log<false>(mag, rows + f * RP + 1, -1, s_mw, s_mst, s_mfid, s_L, rounds, RS, lane, WR);
+            mel64_walk_log<false>(mag, rows + f * RP + 1, -1, plan.s_mw, plan.s_mst, plan.s_mfid, plan.s_L, rounds, RS, lane, WR);
             wave_sync();
         }
         // ---- phase 2: lane = row

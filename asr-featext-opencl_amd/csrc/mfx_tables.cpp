@@ -533,110 +533,49 @@ static int stride_4odd(int n)
     return 4 * q;
 }
 
-bool build_mel_lane_plan(const MelTable &t, int num_banks, int fft_size, int max_read_bin, MelLanePlan &out, int align)
+bool build_mel_plan(const MelTable &t, int num_banks, int fft_size, int max_read_bin, int lanes, int align, MelPlan &out)
 {
+    if (lanes != 16 && lanes != 32 && lanes != 64) return false;
     std::vector<int> order(num_banks);
     for (int m = 0; m < num_banks; ++m) order[m] = m;
     auto span = [&](int m) { return t.beg[m + 2] - t.beg[m]; };
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return span(a) > span(b); });
-    out.rounds = (num_banks + 15) / 16;
-    if (out.rounds > 8) return false;
-    out.start.assign((size_t)16 * out.rounds, 0);
-    out.fid.assign((size_t)16 * out.rounds, -1);
-    int total = 0;
-    for (int r = 0; r < out.rounds; ++r) {
-        // Starts are multiples of `align` bins (an 8- or 16-byte LDS read).  The 16 lanes of a frame read at start + s
-        // simultaneously; they fall on distinct bank groups when (start / align) mod 16 differs from lane to lane, so a
-        // clashing filter may begin a few reads early (zero weights: the sum keeps its bits) -- as long as the round does
-        // not get longer for it (a two-way bank conflict costs one LDS cycle per read, a longer round a whole 8-bin trip
-        // on every lane).  Which filter moves where is a maximum bipartite matching of the round's filters to residues.
-        int natural = 8;
-        for (int j = 0; j < 16; ++j) {
-            const int idx = r * 16 + j;
-            if (idx >= num_banks) continue;
-            const int m = order[idx];
-            natural = std::max(natural, (t.beg[m + 2] - (t.beg[m] & ~(align - 1)) + 7) & ~7);
-        }
-        std::vector<std::vector<int>> cands(16);
-        for (int j = 0; j < 16; ++j) {
-            const int idx = r * 16 + j;
-            if (idx >= num_banks) continue;
-            const int m = order[idx];
-            for (int d = 0; d < 16; ++d) {
-                const int cand = (t.beg[m] & ~(align - 1)) - align * d;
-                if (cand < 0 || t.beg[m + 2] - cand > natural) break;
-                cands[j].push_back(cand);
-            }
-        }
-        const std::vector<int> pick = match_starts(cands, align, 16);
-        int longest = 0;
-        for (int j = 0; j < 16; ++j) {
-            const int idx = r * 16 + j;
-            if (idx >= num_banks) continue;
-            const int m = order[idx];
-            out.start[r * 16 + j] = pick[j];
-            out.fid[r * 16 + j] = m;
-            longest = std::max(longest, t.beg[m + 2] - pick[j]);
-        }
-        out.L[r] = std::max(8, (longest + 7) & ~7);
-        total += out.L[r];
-    }
-    out.row_stride = stride_4odd(total);
-    out.w.assign((size_t)16 * out.row_stride, 0.0f);
-    int base = 0;
-    for (int r = 0; r < out.rounds; ++r) {
-        for (int j = 0; j < 16; ++j) {
-            const int m = out.fid[r * 16 + j];
-            if (m < 0) continue;
-            const int start = out.start[r * 16 + j];
-            if (start + out.L[r] - 1 > max_read_bin) return false;
-            const float *row = t.weights.data() + (size_t)(m & 1) * fft_size;
-            float *dst = out.w.data() + (size_t)j * out.row_stride + base;
-            for (int k = t.beg[m]; k < t.beg[m + 2]; ++k) dst[k - start] = row[k];
-        }
-        base += out.L[r];
-    }
-    return true;
-}
-
-bool build_mel_wave_plan(const MelTable &t, int num_banks, int fft_size, int max_read_bin, MelWavePlan &out, int lanes)
-{
-    if (lanes != 64 && lanes != 32) return false;
-    std::vector<int> order(num_banks);
-    for (int m = 0; m < num_banks; ++m) order[m] = m;
-    auto span = [&](int m) { return t.beg[m + 2] - t.beg[m]; };
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return span(a) > span(b); });
+    out.lanes = lanes;
     out.rounds = (num_banks + lanes - 1) / lanes;
     if (out.rounds > 8) return false;
     out.start.assign((size_t)lanes * out.rounds, 0);
     out.fid.assign((size_t)lanes * out.rounds, -1);
+    const int group = std::min(lanes, 32);
     int total = 0;
     for (int r = 0; r < out.rounds; ++r) {
-        // An 8-byte read is served in groups of 32 lanes over 32 bank pairs: a group is conflict free when
-        // (start / 2) mod 32 differs from lane to lane, so a clashing filter begins a few pairs early (zero weights) where
-        // the round does not get longer for it; the assignment is a maximum matching per group of 32 lanes.
+        // Starts are multiples of `align` bins (an 8- or 16-byte LDS read).  A read is served in groups of `group` lanes
+        // (the 16 lanes of a frame; 32 lanes of a wider plan's 8-byte read over 32 bank pairs): a group is conflict free
+        // when (start / align) mod group differs from lane to lane, so a clashing filter may begin a few reads early (zero
+        // weights: the sum keeps its bits) -- as long as the round does not get longer for it (a two-way bank conflict
+        // costs one LDS cycle per read, a longer round a whole 8-bin trip on every lane).  Which filter moves where is a
+        // maximum bipartite matching of a group's filters to residues.
         int natural = 8;
         for (int j = 0; j < lanes; ++j) {
             const int idx = r * lanes + j;
             if (idx >= num_banks) continue;
             const int m = order[idx];
-            natural = std::max(natural, (t.beg[m + 2] - (t.beg[m] & ~1) + 7) & ~7);
+            natural = std::max(natural, (t.beg[m + 2] - (t.beg[m] & ~(align - 1)) + 7) & ~7);
         }
         int longest = 0;
-        for (int g0 = 0; g0 < lanes; g0 += 32) {
-            std::vector<std::vector<int>> cands(32);
-            for (int j = g0; j < g0 + 32; ++j) {
+        for (int g0 = 0; g0 < lanes; g0 += group) {
+            std::vector<std::vector<int>> cands(group);
+            for (int j = g0; j < g0 + group; ++j) {
                 const int idx = r * lanes + j;
                 if (idx >= num_banks) continue;
                 const int m = order[idx];
-                for (int d = 0; d < 32; ++d) {
-                    const int cand = (t.beg[m] & ~1) - 2 * d;
+                for (int d = 0; d < group; ++d) {
+                    const int cand = (t.beg[m] & ~(align - 1)) - align * d;
                     if (cand < 0 || t.beg[m + 2] - cand > natural) break;
                     cands[j - g0].push_back(cand);
                 }
             }
-            const std::vector<int> pick = match_starts(cands, 2, 32);
-            for (int j = g0; j < g0 + 32; ++j) {
+            const std::vector<int> pick = match_starts(cands, align, group);
+            for (int j = g0; j < g0 + group; ++j) {
                 const int idx = r * lanes + j;
                 if (idx >= num_banks) continue;
                 const int m = order[idx];

@@ -267,41 +267,24 @@ void build_stft_operands(const float *cos_sin, int N, int tb, std::vector<float>
 
 namespace mfx {
 
-// Work plan of the mel stage of the 512-point kernel: the filters are dealt to the 16 lanes that
-// share a frame, `rounds` at a time (longest filters first so that a round's padding is small).
-// Lane j's weights for round r start at w[j * row_stride + sum(L[0..r))], cover bins
-// [start[r][j], start[r][j] + L[r]) and are zero outside the filter's own span.
-struct MelLanePlan {
-    int rounds = 0;
+// Lane plan of the mel stage: the filters are dealt to the `lanes` lanes that share a frame -- 16 (k_front512, k_front1024),
+// 32 (k_front2048: the two halves of a wave walk the same filters of their own frames) or 64 (k_front_reg, k_front_wave,
+// k_melcep, k_plp) -- a round of `lanes` filters at a time, longest first so that a round's padding is small.  Lane j's
+// weights for round r start at w[j * row_stride + sum(L[0..r))], cover bins [start[r][j], start[r][j] + L[r]) in ascending
+// order (the reference's summation order, mfcccpu.cpp:192-220) and are zero outside the filter's own span.
+struct MelPlan {
+    int lanes = 0, rounds = 0;
     int row_stride = 0;            // floats; a multiple of 4 with row_stride / 4 odd (LDS banks)
-    int L[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    std::vector<float> w;          // [16][row_stride]
-    std::vector<int32_t> start;    // [rounds][16]
-    std::vector<int32_t> fid;      // [rounds][16], -1 = idle lane
+    int L[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // bins per lane in round r (x8)
+    std::vector<float> w;          // [lanes][row_stride]
+    std::vector<int32_t> start;    // [rounds][lanes] first bin read
+    std::vector<int32_t> fid;      // [rounds][lanes] filter, -1 = idle lane
 };
-
-// false when the plan does not fit the kernel's limits (more than 8 rounds, or a padded span that
+// false when the plan does not fit the kernels' limits (lanes not 16 / 32 / 64, more than 8 rounds, or a padded span that
 // would read past `max_read_bin`)
 // align: starts are multiples of it (2: two bins per 8-byte read of one magnitude array; 4: the de-interleaved even / odd
 // arrays of k_front1024, two bins of each per 8-byte read)
-bool build_mel_lane_plan(const MelTable &t, int num_banks, int fft_size, int max_read_bin, MelLanePlan &out, int align = 2);
-
-// The same plan for the wave-per-frame kernels (64 lanes share a frame; k_front_reg): rounds of 64 filters, longest
-// first, every lane walks its filter's bins in ascending order (the reference's summation order, mfcccpu.cpp:192-220).
-//   w     : [64][row_stride], row_stride / 4 odd: the 16 lanes of a 16-byte access group read disjoint bank quads
-//   start : [rounds][64] first bin read (even), fid : [rounds][64] filter or -1, L[r] bins per lane in round r (x8)
-struct MelWavePlan {
-    int rounds = 0;
-    int row_stride = 0;
-    int L[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    std::vector<float> w;
-    std::vector<int32_t> start;
-    std::vector<int32_t> fid;
-};
-// false when it does not fit (more than 8 rounds, or a read past max_read_bin)
-// lanes: 64 (one frame per wave, k_front_reg) or 32 (two frames per wave, k_front2048: the two halves of the wave walk
-// the same filters of their own frames); the arrays are [.][lanes]
-bool build_mel_wave_plan(const MelTable &t, int num_banks, int fft_size, int max_read_bin, MelWavePlan &out, int lanes = 64);
+bool build_mel_plan(const MelTable &t, int num_banks, int fft_size, int max_read_bin, int lanes, int align, MelPlan &out);
 
 // B operands of the DCT on the matrix pipe (v_mfma_f32_16x16x4_f32), for every tile of 16 output columns and every
 // K step of 4 mel bands: out[(tile * ksteps + j) * 64 + lane] = dct[4 j + (lane >> 4)][16 tile + (lane & 15)],

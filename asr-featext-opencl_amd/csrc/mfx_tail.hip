@@ -34,7 +34,7 @@ namespace {
 // ------------------------------------------------------------------------------------------------
 // melcep: stored magnitudes -> mel -> log -> DCT (streaming apply(), VTLN sweeps, the 4096-point batch path).  A wave
 // takes 4 consecutive rows at a time: each row's magnitudes go to the wave's LDS buffer, its filters are walked on the
-// wave's 64 lanes (MelWavePlan: whole filters in ascending bin order, mfcccpu.cpp:206-217), the log energies wait in
+// wave's 64 lanes (MelPlan: whole filters in ascending bin order, mfcccpu.cpp:206-217), the log energies wait in
 // lm[4][FS], and the DCT of the four rows runs on the matrix pipe (dct_mfma4) -- the same mel stage as the fused batch
 // kernels (round 3: the round-1 piece plan and its vector-pipe DCT are gone).  blockIdx.y = filterbank of a VTLN sweep.
 // melcep_rows is the kernel's body over the row groups `groups(first, stride)` deals to this wave: all rows [0, n_rows) in
@@ -46,11 +46,11 @@ __device__ __forceinline__ void melcep_rows(const MelcepParams &p, int table, fl
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, n_waves = n_threads >> 6;
-    const int nb = p.num_banks, RS = p.mel64_row_stride, rounds = p.mel64_rounds;
+    const int nb = p.num_banks, RS = p.mel.row_stride, rounds = p.mel.rounds;
     const int FS = lm_fs4(nb), MF = p.mag_floats;
     const int WR = mel64_rows(nb);
     MelPlanLds plan;
-    float *s_wave = stage_mel_plan(smem, p, table, tid, n_threads, plan) + wave * (MF + 4 * FS);
+    float *s_wave = stage_mel_plan(smem, p.mel, nb, table, tid, n_threads, plan) + wave * (MF + 4 * FS);
     float *mag = s_wave, *lm = s_wave + MF;
     for (int i = lane; i < MF + 4 * FS; i += 64) s_wave[i] = 0.f; // words past the last bin stay zero (finite) for good
     __syncthreads();
@@ -406,7 +406,7 @@ int blocks_per_cu(const void *func, int threads, size_t lds_bytes, int fallback)
 
 size_t melcep_lds_bytes(const MelcepParams &p, int n_waves)
 {
-    const size_t f = (size_t)mel64_rows(p.num_banks) * p.mel64_row_stride + (size_t)128 * p.mel64_rounds + 8 +
+    const size_t f = mel64_lds_floats(p.num_banks, p.mel.rounds, p.mel.row_stride) + 8 +
                      (size_t)n_waves * ((size_t)p.mag_floats + 4 * (size_t)lm_fs4(p.num_banks));
     return f * sizeof(float);
 }

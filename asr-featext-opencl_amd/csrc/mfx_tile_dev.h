@@ -3,8 +3,6 @@
 //   tile_store_rows        a finished tile from LDS to its output rows, 16-byte words where the layout allows
 //   delta_tile             the delta stage of one tile, typed for float (k_delta) or float4 (k_delta4) elements
 //   PlainGroups            the row groups of [0, n_rows): the plain counterpart of RunGroups (mfx_dev.h)
-//   stage_mel_plan         the 64-lane mel plan of one table into LDS (k_melcep and its row-run form).  mfx_plp_body.h stages the
-//                          same plan with its own 15 lines: that duplicate stays, with the PLP kernels' text (profiles/r07)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -192,32 +190,6 @@ struct PlainGroups {
         count = (int)(n_rows - row0 < G ? n_rows - row0 : G);
     }
 };
-
-// The 64-lane mel plan (MelWavePlan) of `table` from the parameter struct's mel64_* arrays into LDS at smem: weights
-// s_mw [mel64_rows][row stride], start bins s_mst and filter ids s_mfid [rounds][64], trip counts s_L [8].  Returns the first
-// word behind them; the caller's __syncthreads() makes them visible.
-struct MelPlanLds {
-    float *s_mw;
-    int *s_mst, *s_mfid, *s_L;
-};
-__device__ __forceinline__ float *stage_mel_plan(float *smem, const MelcepParams &p, int table, int tid, unsigned n_threads, MelPlanLds &m)
-{
-    const int RS = p.mel64_row_stride, rounds = p.mel64_rounds;
-    const int WR = mel64_rows(p.num_banks); // weight rows in LDS (lanes that carry a filter)
-    m.s_mw = smem;                          // [WR][RS]
-    m.s_mst = (int *)(m.s_mw + WR * RS);    // [rounds][64]
-    m.s_mfid = m.s_mst + 64 * rounds;       // [rounds][64]
-    m.s_L = m.s_mfid + 64 * rounds;         // [8]
-    const float *gw = p.mel64_w + (int64_t)table * 64 * RS;
-    const int32_t *gst = p.mel64_start + (int64_t)table * 64 * rounds, *gfid = p.mel64_fid + (int64_t)table * 64 * rounds;
-    for (int i = tid; i < WR * RS; i += n_threads) m.s_mw[i] = gw[i];
-    for (int i = tid; i < 64 * rounds; i += n_threads) {
-        m.s_mst[i] = gst[i];
-        m.s_mfid[i] = gfid[i];
-    }
-    if (tid < 8) m.s_L[tid] = p.mel64_L[table * 8 + tid];
-    return (float *)(m.s_L + 8);
-}
 
 } // namespace
 } // namespace mfx

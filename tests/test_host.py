@@ -177,6 +177,24 @@ def test_mel_lane_plan_starts_are_a_maximum_matching(pkg, lanes, nb, W2, sr, max
         assert total == clashes
 
 
+def test_mel_lane_plan_equals_parent(pkg):
+    """build_mel_plan (one builder for 16, 32 and 64 lanes) answers every case of tests/mel_plan_cases.py as the two
+    builders it replaced did: the same return code from mfx_host_mel_lane_plan (rounds, or the refusal) and the same
+    SHA-256 over L, row_stride, start, fid and w as tests/golden/mel_plan_parent.json, recorded from the parent commit's
+    library by tests/golden/make_mel_plan_parent.py."""
+    import json
+    import mel_plan_cases as PC
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mel_plan_parent.json")) as f:
+        want = json.load(f)
+    lib = pkg.load_library()
+    cases = PC.cases()
+    assert sorted(want) == sorted(PC.key(c) for c in cases)
+    differ = [PC.key(c) for c in cases if list(PC.plan_digest(lib, c)) != want[PC.key(c)]]
+    assert not differ, "%d of %d plans differ from the parent's, first: %s" % (len(differ), len(cases), differ[:5])
+    refused = sorted(k for k, (rc, _) in want.items() if rc < 0)
+    assert refused == sorted(PC.key(c) for c in cases if c[1] == 8 * c[0] + 1 or c[5] == 100)  # 9 rounds; the three small buffers
+
+
 @pytest.mark.parametrize("nb,nc,c0", [(40, 13, False), (26, 13, False), (15, 12, True), (80, 13, False), (128, 40, False)])
 def test_dct_mfma_operands_are_the_matrix(pkg, nb, nc, c0):
     """Operand table of the DCT on the matrix pipe: lane (k = lane >> 4, n = lane & 15) of K step j of tile t holds

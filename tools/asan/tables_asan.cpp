@@ -1,5 +1,5 @@
 // Sanitizer run of the host table builders (csrc/mfx_tables.cpp) under -fsanitize=address,undefined: mel table, DCT
-// matrix, twiddles, the 16-lane mel plan of the 512-point kernel and the 64- and 32-lane wave plans, over a grid of
+// matrix, twiddles, the mel lane plans (16 lanes at 512 and 1024 points, 64 lanes, 32 lanes at 2048 points), over a grid of
 // configurations (bank counts, transform sizes, sample rates, band edges, VTLN warps), and the front ends' FFT pass / split
 // twiddle tables and window layouts, and the sample-rate converter's tap tables, lengths and layouts.  Built by `make -C csrc asan`.
 #include <cstdio>
@@ -24,13 +24,11 @@ int main()
                         bool edges_ok = true;
                         for (int v : t.beg) edges_ok = edges_ok && v >= 0 && v <= fft / 2;
                         if (!edges_ok) continue; // the product refuses such a configuration (mfx_create: MFX_ERR_CONFIG)
-                        if (fft == 512) {
-                            mfx::MelLanePlan lp;
-                            (void)mfx::build_mel_lane_plan(t, nb, fft, 511 - 32, lp);
-                        }
-                        mfx::MelWavePlan wp;
-                        (void)mfx::build_mel_wave_plan(t, nb, fft, fft - 1, wp, 64);
-                        if (fft == 2048) (void)mfx::build_mel_wave_plan(t, nb, fft, 1039, wp, 32);
+                        mfx::MelPlan pl;
+                        if (fft == 512) (void)mfx::build_mel_plan(t, nb, fft, 511 - 32, 16, 2, pl);
+                        if (fft == 1024) (void)mfx::build_mel_plan(t, nb, fft, 527, 16, 4, pl);
+                        (void)mfx::build_mel_plan(t, nb, fft, fft - 1, 64, 2, pl);
+                        if (fft == 2048) (void)mfx::build_mel_plan(t, nb, fft, 1039, 32, 2, pl);
                         for (int ceps : {0, 1, 12, 13, 40}) {
                             if (ceps == 0) continue;
                             std::vector<float> m, mt;
