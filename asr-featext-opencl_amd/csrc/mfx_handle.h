@@ -466,6 +466,10 @@ struct SessState {
         void release() { d_taps.release(), d_rates.release(), d_carry.release(), d_conv.release(); }
     } rs;
     int32_t max_conv = 0;                // samples per channel the front end can receive from one piece (max_push without rates)
+    // STFT log-mel handles ("Session log-mel"): the slots carry PCM only; k_sess_stft_mel (k_stft_mel under
+    // MFX_ENGINE_SESS_STFT_PLAIN) reads the current slots and writes the delivered rows where the delta stage would
+    int32_t stft_G = 0;                  // groups per block of k_sess_stft_mel at this shape (sess_stft_groups)
+    DevBuf<float> d_stft_max;            // MFX_ENGINE_SESS_STFT_PLAIN: the slots k_stft_mel leaves its blocks' maxima in (not read)
     // the pending push: everything mfx_sessions_plan leaves for mfx_sessions_run_* (which consumes it)
     struct Piece {                       // one entry of the caller's lists
         int32_t id = 0;
@@ -478,6 +482,11 @@ struct SessState {
         int64_t xsrc = 0;                // session transform: absolute row of y[Ex_old] in d_y (set where the piece delivers rows)
         mfx::SessionStep step;
         mfx::SessionXformStep xstep;     // (session transform only)
+        // STFT log-mel handles only (`step` then holds n_out and the carried samples, nothing else): the step; the row of
+        // d_out, or of the y slots, the piece's first frame goes to; the element of the slot arrays where stream sample 0 lies
+        // or would lie (the last two are set where the piece moves, computes or delivers something)
+        mfx::SessionStftStep sstep;
+        int64_t stft_row = 0, stft_pcm = 0;
     };
     struct Push {
         bool planned = false;
@@ -495,6 +504,8 @@ struct SessState {
         std::vector<mfx::Segment> xsegs;
         std::vector<int32_t> xseg_xf;
         std::vector<mfx::SessResTile> rtiles; // session rates: the tiles of k_sess_resample (empty: nothing to convert or carry)
+        std::vector<mfx::StftChunk> stft;     // STFT log-mel: the groups of k_sess_stft_mel (<= 16 frames of one session), or
+                                              // under MFX_ENGINE_SESS_STFT_PLAIN the chunks of k_stft_mel (<= stft_R frames)
         std::vector<int64_t> c_off, c_len;    // the pieces after conversion (the caller's own lists when the push converts nothing)
         bool convert = false;            // the pieces lie in the scratch
         bool need_pcm = false;           // a piece brings input samples: the run needs d_pcm
@@ -502,17 +513,19 @@ struct SessState {
         int64_t max_end = 0;             // the largest offsets[i] + lengths[i]: checked against the run's pcm_samples_total
         bool any_new = false;            // a piece brings samples: the run needs d_pcm
         int tiles_max = 0, xtiles_max = 0;
-        void clear_lists() { descs.clear(), segs.clear(), chunks.clear(), runs.clear(), onorm.clear(), groups.clear(), blocks.clear(), xsegs.clear(), xseg_xf.clear(), rtiles.clear(); }
+        void clear_lists() { descs.clear(), segs.clear(), chunks.clear(), runs.clear(), onorm.clear(), groups.clear(), blocks.clear(), xsegs.clear(), xseg_xf.clear(), rtiles.clear(), stft.clear(); }
     } push;
     // the planner's scratch (kept so that a plan allocates nothing once warm): ids seen, (slot, piece) keys, the packer's output
     std::vector<uint8_t> p_seen;
     std::vector<int64_t> p_order;
     std::vector<mfx::SessXfCut> p_cuts;
     std::vector<mfx::SessXfPack> p_packs;
+    std::vector<int32_t> p_stft_rows;    // (STFT log-mel: rows every piece computes, the cutter's input and output)
+    std::vector<mfx::SessStftCut> p_stft_cuts;
     void release() // (what mfx_sessions_create(0, 0) gives back)
     {
         d_pcm.release(), d_stat.release(), d_slab.release(), d_desc.release(), d_host_pcm.release(), d_host_out.release();
-        on.release(), xf.release(), rs.release(), h_stage[0].release(), h_stage[1].release();
+        on.release(), xf.release(), rs.release(), h_stage[0].release(), h_stage[1].release(), d_stft_max.release();
     }
 };
 
@@ -556,7 +569,8 @@ struct mfx_handle {
     int lpc = 0;       // PLP model order (lpc_order, 0 -> 8)
     bool traps = false; // mfx_config.method == MFX_METHOD_TRAPS: fbank front end -> scratch -> k_traps; batch entries only
     int traps_L = 0, traps_K = 0; // trajectory length, coefficients kept (defaults applied)
-    // mfx_config.method == MFX_METHOD_STFT_LOGMEL: k_stft_mel (+ k_stft_post) IS the front end; batch entries only.  W is the
+    // mfx_config.method == MFX_METHOD_STFT_LOGMEL: k_stft_mel (+ k_stft_post) IS the front end; batch entries, and (LOG10 /
+    // LN) the session entries through k_sess_stft_mel.  W is the
     // DFT length N (W2 == W), nb the output width; none of the FFT / mel / DCT tables below exist on such a handle
     bool stft = false;
     int stft_R = 0;                      // frames per block of k_stft_mel (stft_tile_rows)

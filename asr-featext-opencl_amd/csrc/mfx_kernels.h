@@ -22,6 +22,8 @@
 //                            NormalizerCPU keeps one block's statistics)
 //   stft_mel / stft_post     the STFT log-mel front end: exact-length DFT of centred frames on the matrix pipe, power, Slaney mel, log;
 //                            the clamp by the utterance's maximum and the map (no reference analogue: a neural recogniser's input)
+//   sess_stft_mel            the same front end over the frames one push of the session entries completes, groups of 16 frames of
+//                            different sessions sharing a block's pass over the basis (no reference analogue)
 //   delta                    delta.cl kernelDelta x2 + the staging copies of mfccopencl.cpp:360-387
 //   norm_stats / norm_apply  norm.cl kernelSum + kernelFinalizeSum / kernelNormalize
 // What is attached to a planned batch (vad_*, onorm_*, pitch_*, pitch_feats) walks its rows by one work list, UttTiling below.
@@ -591,6 +593,31 @@ size_t stft_lds_bytes(int N, int S, int M, int tile_rows);
 int stft_tile_rows(int N, int S, int M); // frames per block: the largest of 64 / 32 / 16 whose LDS fits, 0: none
 hipError_t launch_stft(const StftParams &p, hipStream_t stream);      // k_stft_mel
 hipError_t launch_stft_post(const StftParams &p, hipStream_t stream); // k_stft_post (WHISPER: clamp and map, in place)
+
+// k_sess_stft_mel (mfx_stft.hip; DESIGN.md, "Session log-mel"): the rows one push of the session entries delivers on an STFT
+// log-mel handle.  The work list: groups of at most 16 consecutive frames of ONE session (StftChunk: utt_off is the element of
+// `pcm` where the stream's sample 0 lies or WOULD lie -- the slot holds the stream from a later sample on, so it may be
+// negative --, utt_len the stream's samples, at whose ends the reflections happen; utt_chunk0 / utt_chunks are not used);
+// block b takes groups [G b, G b + G), wave g of it group g.  No element outside [0, pcm_elems) is read.
+struct SessStftParams {
+    const int16_t *pcm;         // both PCM slot arrays of the session entries
+    int64_t pcm_elems;
+    const StftChunk *groups;
+    int32_t n_groups;
+    int32_t G;                  // groups per block the lists were sized for: sess_stft_groups, or the launcher refuses
+    int32_t N, S, M;            // DFT length, hop, mel bands
+    int32_t post;               // MFX_LOGMEL_LOG10 or MFX_LOGMEL_LN
+    const float *operands;      // as StftParams
+    const float *mel_w;
+    const int32_t *mel_beg, *mel_len, *mel_off;
+    float *out;
+    int32_t out_pitch;
+};
+// ALL the LDS a block of k_sess_stft_mel asks for at G groups per block; the G the launcher takes: the largest of 4 / 2 / 1
+// whose LDS fits 160 KB (0: the shape is outside the method's limits)
+size_t sess_stft_lds_bytes(int N, int S, int M, int G);
+int sess_stft_groups(int N, int S, int M);
+hipError_t launch_sess_stft(const SessStftParams &p, hipStream_t stream);
 
 // All launchers are asynchronous on `stream` and return the launch status.
 // every launch of the VAD stage for utterances [u0, u1), in order

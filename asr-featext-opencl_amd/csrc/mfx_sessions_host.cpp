@@ -2,7 +2,8 @@
 // push, all of them in one launch sequence (k_sess_gather -> front end -> delta, with k_onorm_sess before or after the delta
 // while the online normaliser is set, k_sess_xform as the last launch while a session transform is set, and k_sess_resample as
 // the first while session rates are set and a piece has something to convert).  DESIGN.md section 5, "Session entries",
-// "Session transform" and "Session sample-rate conversion".
+// "Session transform", "Session sample-rate conversion" and "Session log-mel" (an STFT log-mel handle: k_sess_gather moves PCM
+// only, and k_sess_stft_mel stands where front end and delta stage do).
 // This file owns the handle's `sess` part.  It reads the shared geometry and tables and names no field of `st`, `sweep`,
 // `batch` or `fuse`: a push leaves the streaming state and the batch plan, alpha list and transform as they are.
 #include "mfx_handle.h"
@@ -27,10 +28,11 @@ int sessions_exist(mfx_handle *h, const char *who) { return fail(h, MFX_ERR_STAT
 bool sess_aligned(const mfx_handle *h) { return (h->S % 2) == 0; }
 bool norm_before(const mfx_handle *h) { return h->cfg.norm != MFX_NORM_NONE && !h->cfg.norm_after_dyn; }
 bool xform_plain(const mfx_handle *h) { return (h->cfg.engine & MFX_ENGINE_SESS_XFORM_PLAIN) != 0; }
+bool stft_plain(const mfx_handle *h) { return (h->cfg.engine & MFX_ENGINE_SESS_STFT_PLAIN) != 0; }
 
 // The single upload of a push: descriptors | segments | chunks | row runs | run offsets | the normaliser's descriptors | the
 // transform's groups | its blocks (under MFX_ENGINE_SESS_XFORM_PLAIN: | its segments | their transforms) | the converter's
-// tiles (session rates), every part on an 8-byte boundary.  The constructor is the one place that lists them.  mfx_sessions_create calls it on a push whose lists have
+// tiles (session rates) | the groups of k_sess_stft_mel (STFT log-mel), every part on an 8-byte boundary.  The constructor is the one place that lists them.  mfx_sessions_create calls it on a push whose lists have
 // their largest sizes, without a staging buffer, for the bytes d_desc and the staging need; the run calls it on the planned
 // push: the parts are copied into `stage` and their addresses in `dev` are the members.
 struct SessUpload {
@@ -42,6 +44,7 @@ struct SessUpload {
     const OnormSessDesc *onorm = nullptr;
     const void *xa = nullptr, *xb = nullptr;
     const SessResTile *rtiles = nullptr;
+    const StftChunk *stft = nullptr;
     size_t bytes = 0;
     SessUpload() = default;
     SessUpload(const Push &ps, char *stage, char *dev)
@@ -60,6 +63,8 @@ struct SessUpload {
         xa = plain ? (const void *)put(ps.xsegs) : put(ps.groups), xb = plain ? (const void *)put(ps.xseg_xf) : put(ps.blocks);
         static_assert(sizeof(SessResTile) % 8 == 0, "8-byte parts");
         rtiles = put(ps.rtiles); // (session rates: the converter's tiles)
+        static_assert(sizeof(StftChunk) % 8 == 0, "8-byte parts");
+        stft = put(ps.stft); // (STFT log-mel: the frame groups)
     }
 };
 
@@ -70,8 +75,10 @@ extern "C" int mfx_sessions_create(mfx_handle *h, int32_t n_sessions, int32_t ma
     MFX_DEVICE_ENTRY(h);
     if (h->traps)
         return fail(h, MFX_ERR_STATE, "the session entries do not serve TRAPS handles (their look-ahead is (L - 1) / 2 frames, not D)");
-    if (h->stft)
-        return fail(h, MFX_ERR_STATE, "the session entries do not serve STFT log-mel handles: use the batch entries (mfx_batch_plan + mfx_batch_run_device)");
+    if (h->stft && h->cfg.logmel_post == MFX_LOGMEL_WHISPER)
+        return fail(h, MFX_ERR_STATE,
+                    "the session entries do not serve MFX_LOGMEL_WHISPER (its clamp needs the largest value of the whole utterance): use "
+                    "the batch entries (mfx_batch_plan + mfx_batch_run_device), or MFX_LOGMEL_LOG10 / MFX_LOGMEL_LN");
     if (h->cfg.norm != MFX_NORM_NONE && !h->sess.on.set) // (mfx_sessions_set_online_norm: the one normaliser served)
         return fail(h, MFX_ERR_STATE,
                     "the session entries do not serve normalisation (norm != MFX_NORM_NONE): statistics over an open stream are not built");
@@ -109,6 +116,14 @@ extern "C" int mfx_sessions_create(mfx_handle *h, int32_t n_sessions, int32_t ma
     ss.pcm_stride = ((int64_t)h->W + h->S + max_conv + 2 + 7) & ~(int64_t)7;
     ss.frames_max = (int32_t)(max_conv / h->S + 1);
     ss.row_cap = 2 * h->D + ss.frames_max;
+    ss.stft_G = 0;
+    ss.d_stft_max.release();
+    if (h->stft) { // rows of a push: its own and a final push's N / (2 S) + 1 more; no statics live in the slots
+        ss.frames_max = (int32_t)session_stft_rows_max(h->W, h->S, max_conv);
+        ss.row_cap = 1;
+        ss.stft_G = sess_stft_groups(h->W, h->S, h->nb);
+        if (ss.stft_G == 0) return fail(h, MFX_ERR_CONFIG, "no block packing of k_sess_stft_mel fits the LDS for this shape");
+    }
     ss.row_floats = (std::max(16, h->width) + 3) & ~3;
     const size_t pcm_elems = (size_t)2 * n_sessions * ss.pcm_stride * ch;
     HIP_TRY(h, ss.d_pcm.alloc(pcm_elems + 8));
@@ -116,14 +131,20 @@ extern "C" int mfx_sessions_create(mfx_handle *h, int32_t n_sessions, int32_t ma
     HIP_TRY(h, ss.d_stat.alloc((size_t)2 * n_sessions * ss.row_cap * ss.row_floats));
     ss.slab_rows = 0;
     ss.d_slab.release();
-    if (is_spec_kind(choose_front(h, sess_aligned(h)))) {
+    if (!h->stft && is_spec_kind(choose_front(h, sess_aligned(h)))) {
         ss.slab_rows = std::min<int64_t>((int64_t)2 * n_sessions * ss.row_cap, kSlabRowsMax);
         HIP_TRY(h, ss.d_slab.alloc((size_t)ss.slab_rows * h->spec_pitch));
     }
     // the push's lists at their largest: resizing reserves them (a warm plan allocates nothing), SessUpload sizes their upload
     ps.pieces.reserve(n), ss.p_order.reserve(n);
     ps.descs.resize(n), ps.segs.resize(n), ps.runs.resize(2 * n);
-    ps.chunks.resize(n * ((ss.frames_max + kChunkFrames - 1) / kChunkFrames));
+    if (h->stft) { // groups of 16 frames, or the chunks of k_stft_mel and the slots of their maxima
+        const size_t per = (size_t)ss.frames_max / (stft_plain(h) ? h->stft_R : 16) + 1;
+        ps.stft.resize(n * per), ss.p_stft_rows.reserve(n), ss.p_stft_cuts.reserve(n * per);
+        if (stft_plain(h)) HIP_TRY(h, ss.d_stft_max.alloc(n * per));
+    } else {
+        ps.chunks.resize(n * ((ss.frames_max + kChunkFrames - 1) / kChunkFrames));
+    }
     ss.xf.d_y.release();
     if (ss.xf.set) { // the session transform: the two y slot arrays, the operands; the work list of the handle's launch form
         ss.xf.y_cap = ss.xf.left + ss.xf.right + ss.frames_max + h->D;
@@ -385,7 +406,7 @@ extern "C" int64_t mfx_sessions_delivered(const mfx_handle *h, int32_t session)
 
 namespace {
 
-// ---- mfx_sessions_plan: check_pieces -> plan_rates (session rates) -> plan_steps -> plan_slots -> plan_xform_work
+// ---- mfx_sessions_plan: check_pieces -> plan_rates (session rates) -> plan_steps -> plan_slots -> plan_xform_work -> plan_stft_work (STFT log-mel)
 
 // the samples the front end will have seen of session id once `length` more have arrived (session rates: after conversion)
 int64_t stream_samples(const SessState &ss, int32_t id, int64_t length)
@@ -416,7 +437,7 @@ int check_pieces(mfx_handle *h, int32_t n, const int32_t *ids, const int64_t *of
             bad = MFX_ERR_ARG, why = "offset + length too large";
         else if (lengths[i] > ss.max_push)
             bad = MFX_ERR_BUFFER_TOO_SMALL, why = "a session's piece is longer than max_push_samples (mfx_sessions_create)";
-        else if (frame_count(stream_samples(ss, id, lengths[i]), h->W, h->S) > 0x7fffffff)
+        else if (utt_frame_count(h, stream_samples(ss, id, lengths[i])) > 0x7fffffff)
             bad = MFX_ERR_ARG, why = "stream too long";
         else
             ss.p_seen[id] = 1;
@@ -493,7 +514,14 @@ void plan_steps(mfx_handle *h, int32_t n, const int32_t *ids, const int64_t *off
         pc.id = ids[i], pc.off = offsets[i], pc.len = lengths[i], pc.fin = final_flags && final_flags[i] != 0;
         pc.next = cur; // (n, E and Ex advance here; the slot fields follow in plan_slots)
         if (ss.rs.set) pc.next.n_in = pc.n_in_next, pc.next.rs_parity = pc.rs_parity_next; // (plan_rates has advanced them)
-        int32_t n_del = session_step(h->W, h->S, h->D, pc.next.n, pc.next.E, pc.len, pc.fin, pc.step);
+        int32_t n_del;
+        if (h->stft) { // (no frame is computed ahead of its delivery and no static row carried: D = 0)
+            n_del = session_stft_step(h->W, h->S, pc.next.n, pc.next.E, pc.len, pc.fin, pc.sstep);
+            pc.step = SessionStep{};
+            pc.step.carry_samples = pc.sstep.carry_in, pc.step.n_out = n_del;
+        } else {
+            n_del = session_step(h->W, h->S, h->D, pc.next.n, pc.next.E, pc.len, pc.fin, pc.step);
+        }
         if (ss.xf.set) { // the rows y the push completes are the transform's input; it delivers rows [Ex_old, Ex_new)
             int64_t Ey = cur.E;
             n_del = session_xform_step(ss.xf.left, ss.xf.right, Ey, pc.next.Ex, pc.step.n_out, pc.fin, pc.xstep);
@@ -531,7 +559,7 @@ void plan_slots(mfx_handle *h)
         const bool fin = pc.fin;
         // nothing to move, compute or deliver: an empty push of an open stream, the flush of a stream without samples
         if (pc.len == 0 && (!fin || cur.n == 0)) continue;
-        const int64_t f0 = std::max<int64_t>(cur.E - D, 0);
+        const int64_t f0 = h->stft ? 0 : std::max<int64_t>(cur.E - D, 0); // (STFT log-mel: no static rows in the slots)
         const int64_t slot_prev = (int64_t)cur.parity * ss.n + pc.id, slot_cur = key >> 20;
         SessDesc d{};
         d.carry_src = (slot_prev * ss.pcm_stride + cur.tail_off) * ch, d.carry_n = (int32_t)(st.carry_samples * ch);
@@ -561,6 +589,12 @@ void plan_slots(mfx_handle *h)
         if (onorm && before && st.new_frames > 0)
             ps.onorm.push_back(OnormSessDesc{new_row0, std::max<int64_t>(frame_count(cur.n, h->W, h->S), 0), st.new_frames, pc.id});
         if (onorm && !before && st.n_out > 0) ps.onorm.push_back(OnormSessDesc{y_row0, cur.E, st.n_out, pc.id});
+        if (h->stft) { // the slot holds stream samples [c0_old, n_new) from its base on: the carried tail, then the new samples
+            pc.stft_row = y_row0, pc.stft_pcm = slot_cur * ss.pcm_stride - pc.sstep.c0_old;
+            nx.parity = cur.parity ^ 1, nx.f0 = 0, nx.tail_off = fin ? 0 : (int32_t)(pc.sstep.c0_new - pc.sstep.c0_old);
+            nx.pitch = 0;
+            continue;
+        }
         if (st.n_out > 0) {
             Segment s{};
             s.src_row0 = d.row_dst, s.out_row0 = y_row0, s.n_out = st.n_out;
@@ -601,6 +635,32 @@ void plan_xform_work(mfx_handle *h)
     for (const SessXfPack &k : ss.p_packs) ps.blocks.push_back(SessXfBlock{k.g0, k.ng, k.xf, 0});
 }
 
+// ---- stage 6, STFT log-mel: the front end's work list, pieces in the caller's order: groups of at most 16 frames for
+// k_sess_stft_mel (block b takes groups [G b, G b + G)), or chunks of at most stft_R frames for k_stft_mel.  A group's
+// "utterance" is the session's stream: utt_off the element where its sample 0 would lie, utt_len the samples received.  The
+// delivery rule keeps every read inside the slot: a negative index occurs only while the slot holds sample 0, an index >= n
+// only on a final push, and its reflection lies behind c0_old.
+void plan_stft_work(mfx_handle *h)
+{
+    SessState &ss = h->sess;
+    Push &ps = ss.push;
+    if (!h->stft) return;
+    const int n = (int)ps.pieces.size();
+    auto chunk = [&](const Piece &pc, int r0, int rows) {
+        const int64_t E_old = ss.live[pc.id].E, n_new = ss.live[pc.id].n + pc.len;
+        ps.stft.push_back(StftChunk{pc.stft_pcm, n_new, pc.stft_row + r0, (int32_t)(E_old + r0), rows, 0, 0});
+    };
+    if (stft_plain(h)) {
+        for (const Piece &pc : ps.pieces)
+            for (int r0 = 0; r0 < pc.step.n_out; r0 += h->stft_R) chunk(pc, r0, std::min(h->stft_R, pc.step.n_out - r0));
+        return;
+    }
+    ss.p_stft_rows.resize(n);
+    for (int i = 0; i < n; ++i) ss.p_stft_rows[i] = ps.pieces[i].step.n_out;
+    cut_sess_stft_groups(ss.p_stft_rows.data(), n, ss.p_stft_cuts);
+    for (const SessStftCut &g : ss.p_stft_cuts) chunk(ps.pieces[g.piece], g.r0, g.rows);
+}
+
 } // namespace
 
 extern "C" int mfx_sessions_plan(mfx_handle *h, int32_t n, const int32_t *ids, const int64_t *offsets, const int64_t *lengths,
@@ -627,6 +687,7 @@ extern "C" int mfx_sessions_plan(mfx_handle *h, int32_t n, const int32_t *ids, c
     if (total_rows) *total_rows = ss.push.total_rows;
     plan_slots(h);
     plan_xform_work(h);
+    plan_stft_work(h);
     if (!ss.rs.set) ss.push.need_pcm = ss.push.any_new;
     ss.push.planned = true;
     return MFX_OK;
@@ -635,7 +696,7 @@ extern "C" int mfx_sessions_plan(mfx_handle *h, int32_t n, const int32_t *ids, c
 namespace {
 
 // ---- mfx_sessions_run_device: check_run -> upload -> run_resample (session rates) -> run_gather -> run_front -> run_onorm (before) -> run_delta -> run_onorm
-// (after) -> run_xform -> commit.  What the stages share:
+// (after) -> run_xform -> commit (an STFT log-mel handle: ... -> run_gather -> run_stft -> run_xform -> commit).  What the stages share:
 struct PushRun {
     const int16_t *d_pcm;       // the entry's arguments
     int64_t pcm_total;
@@ -663,6 +724,11 @@ int check_run(mfx_handle *h, PushRun &r)
     HIP_TRY(h, hipSetDevice(h->device));
     const int rc = refresh_mel(h);
     if (rc != MFX_OK) return rc;
+    r.d_rows = ss.xf.set ? ss.xf.d_y.p : r.d_out;
+    if (h->stft) { // (k_sess_stft_mel is the front end: no statics, rows of `width` floats straight to d_rows)
+        r.pitch = h->width;
+        return MFX_OK;
+    }
     // the front end of the shape, as the batch entries choose it, and the pitch batch_run_range gives the statics
     r.aligned = sess_aligned(h);
     r.kind = choose_front(h, r.aligned);
@@ -672,7 +738,6 @@ int check_run(mfx_handle *h, PushRun &r)
     r.pitch = compact ? 16 : h->width;
     if (is_spec_kind(r.kind) && ss.slab_rows == 0)
         return fail(h, MFX_ERR_STATE, "the warp factor moved this shape to the spectrum path: call mfx_sessions_create again");
-    r.d_rows = ss.xf.set ? ss.xf.d_y.p : r.d_out;
     return MFX_OK;
 }
 
@@ -749,6 +814,39 @@ int run_front(mfx_handle *h, PushRun &r)
     w.runs = r.up.runs, w.run_off = r.up.run_off;
     w.h_runs = ps.runs.data(), w.h_run_off = ps.run_off;
     return launch_front(h, p, r.kind, r.aligned, w);
+}
+
+// ---- stages 5 to 8 of an STFT log-mel handle: the frames the push completes, from the current slots' PCM into d_rows -- groups
+// of different sessions packed into blocks (k_sess_stft_mel), or under MFX_ENGINE_SESS_STFT_PLAIN k_stft_mel itself, one chunk
+// per run of frames of one session (the measurement's comparator; same bits)
+int run_stft(mfx_handle *h, const PushRun &r)
+{
+    const SessState &ss = h->sess;
+    const Push &ps = ss.push;
+    if (ps.stft.empty()) return MFX_OK;
+    const int nb = h->nb;
+    if (stft_plain(h)) {
+        if (ss.d_stft_max.n < ps.stft.size()) return fail(h, MFX_ERR_STATE, "session chunks outgrew their buffer");
+        StftParams sp{};
+        sp.pcm = ss.d_pcm.p;
+        sp.chunks = r.up.stft, sp.n_chunks = (int32_t)ps.stft.size(), sp.chunk_first = 0;
+        sp.N = h->W, sp.S = h->S, sp.M = nb, sp.post = h->cfg.logmel_post, sp.tile_rows = h->stft_R;
+        sp.operands = h->d_stft_ops.p, sp.mel_w = h->d_stft_melw.p;
+        sp.mel_beg = h->d_stft_mel.p, sp.mel_len = h->d_stft_mel.p + nb, sp.mel_off = h->d_stft_mel.p + 2 * nb;
+        sp.out = r.d_rows, sp.out_pitch = h->width;
+        sp.blk_max = ss.d_stft_max.p;
+        HIP_TRY(h, launch_stft(sp, h->stream));
+        return MFX_OK;
+    }
+    SessStftParams sp{};
+    sp.pcm = ss.d_pcm.p, sp.pcm_elems = (int64_t)2 * ss.n * ss.pcm_stride;
+    sp.groups = r.up.stft, sp.n_groups = (int32_t)ps.stft.size(), sp.G = ss.stft_G;
+    sp.N = h->W, sp.S = h->S, sp.M = nb, sp.post = h->cfg.logmel_post;
+    sp.operands = h->d_stft_ops.p, sp.mel_w = h->d_stft_melw.p;
+    sp.mel_beg = h->d_stft_mel.p, sp.mel_len = h->d_stft_mel.p + nb, sp.mel_off = h->d_stft_mel.p + 2 * nb;
+    sp.out = r.d_rows, sp.out_pitch = h->width;
+    HIP_TRY(h, launch_sess_stft(sp, h->stream));
+    return MFX_OK;
 }
 
 // ---- stages 6 and 8, online normaliser: ahead of the deltas on the new frames' statics in the slots (data = the statics
@@ -834,7 +932,13 @@ extern "C" int mfx_sessions_run_device(mfx_handle *h, const int16_t *d_pcm, int6
     int rc = check_run(h, r);
     if (rc != MFX_OK) return rc;
     if (!h->sess.push.descs.empty() || !h->sess.push.rtiles.empty()) { // (neither: nothing to move, compute or deliver)
-        if ((rc = upload(h, r)) != MFX_OK || (rc = run_resample(h, r)) != MFX_OK || (rc = run_gather(h, r)) != MFX_OK || (rc = run_front(h, r)) != MFX_OK) return rc;
+        if ((rc = upload(h, r)) != MFX_OK || (rc = run_resample(h, r)) != MFX_OK || (rc = run_gather(h, r)) != MFX_OK) return rc;
+        if (h->stft) {
+            if ((rc = run_stft(h, r)) != MFX_OK || (rc = run_xform(h, r)) != MFX_OK) return rc;
+            commit(h, r);
+            return MFX_OK;
+        }
+        if ((rc = run_front(h, r)) != MFX_OK) return rc;
         if (before && (rc = run_onorm(h, r, h->sess.d_stat.p, r.pitch)) != MFX_OK) return rc;
         if ((rc = run_delta(h, r)) != MFX_OK) return rc;
         if (!before && (rc = run_onorm(h, r, r.d_rows, h->width)) != MFX_OK) return rc;
@@ -930,4 +1034,28 @@ extern "C" int64_t mfx_host_session_resample_step(int32_t in_hz, int32_t out_hz,
     if (carry_in) *carry_in = st.carry_in;
     if (carry_out) *carry_out = st.carry_out;
     return n;
+}
+
+extern "C" int32_t mfx_host_session_stft_step(int32_t dft_size, int32_t shift, int64_t state[2], int64_t length, int32_t final_flag,
+                                              int32_t *carry_in, int32_t *carry_out)
+{
+    if (dft_size < 32 || dft_size > 512 || (dft_size & 1) || shift < 1 || shift > dft_size) return MFX_ERR_ARG;
+    if (!state || state[0] < 0 || state[1] < 0 || length < 0 || length > (1 << 24) || state[0] > INT64_MAX / 2) return MFX_ERR_ARG;
+    if (state[1] > stft_frame_count(state[0], dft_size, shift)) return MFX_ERR_ARG; // (more rows than the stream has frames)
+    // (fewer rows than an open stream of n samples has delivered: no slot carries N + S samples or more)
+    if (state[0] - std::max<int64_t>(state[1] * shift - dft_size / 2, 0) >= dft_size + shift) return MFX_ERR_ARG;
+    SessionStftStep st;
+    const int32_t n_out = session_stft_step(dft_size, shift, state[0], state[1], length, final_flag != 0, st);
+    if (carry_in) *carry_in = st.carry_in;
+    if (carry_out) *carry_out = st.carry_out;
+    return n_out;
+}
+
+extern "C" int64_t mfx_host_sess_stft_lds_bytes(int32_t dft_size, int32_t shift, int32_t num_banks, int32_t *groups)
+{
+    if (dft_size < 32 || dft_size > 512 || (dft_size & 1) || shift < 1 || shift > dft_size || num_banks < 1 || num_banks > 128) return MFX_ERR_ARG;
+    const int G = groups && *groups > 0 ? *groups : sess_stft_groups(dft_size, shift, num_banks);
+    if (G != 1 && G != 2 && G != 4) return MFX_ERR_ARG;
+    if (groups) *groups = G;
+    return (int64_t)sess_stft_lds_bytes(dft_size, shift, num_banks, G);
 }

@@ -25,6 +25,8 @@
 // log value goes to its slot of blk_max.
 // k_stft_post (WHISPER only): the block of a chunk takes the maximum over the slots of its utterance's chunks -- a float
 // maximum does not depend on the order, no atomics -- and clamps and maps its own rows in place.
+// k_sess_stft_mel (the session entries, LOG10 / LN): the same DFT loop and mel stage (stft_dft_power, stft_mel_log below: one
+// chain per value, tap for tap) over groups of at most 16 frames of DIFFERENT sessions per block; see its own comment.
 #include "mfx_kernels.h"
 
 #include <hip/hip_runtime.h>
@@ -63,50 +65,23 @@ __device__ __forceinline__ float wave_max(float v)
 
 constexpr int kStftPf = (kStftKSteps * 2 * kStftTB * 16 + 255) / 256; // 16-byte words a thread carries for the next chunk
 
-// LDS, all of it dynamic (stft_lds_bytes is the whole of what a block asks for):
-//   operand buffers [2][KS][2 TBp][64] | s_x [(R - 1) S + N + 4] (later s_out [R][M]) | s_P [R][KP] | s_red [4]
-__global__ void __launch_bounds__(256) k_stft_mel(StftParams p)
+// The DFT and the power of a wave's 16 frames, shared by k_stft_mel and k_sess_stft_mel: every pass over the taps, the basis
+// operands streamed through the two LDS buffers s_b for all waves of the block (every thread calls this: it synchronises the
+// block, the first time once the callers' spans are staged).  Lane (li, lk) of a busy wave feeds frame li, tap 4 s + lk from
+// za[4 s]; the power of the wave's frames r < wave_rows goes to s_Pw [16][KP].
+__device__ __forceinline__ void stft_dft_power(const float *operands, int N, float *s_b, const float *za, bool busy, int wave_rows, float *s_Pw,
+                                               int tid)
 {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const StftChunk ck = p.chunks[blockIdx.x];
-    const int R = p.tile_rows, N = p.N, S = p.S, M = p.M;
-    const int rows = ck.n_frames;
     const int K1 = stft_bins(N), KP = stft_p_pitch(N), NBT = stft_bin_tiles(N), TBp = stft_pass_tiles(N), steps = stft_steps(N);
-    const int tid = threadIdx.x;
-    float *s_b = smem;
-    float *s_x = s_b + 2 * stft_buf_floats(N);
-    float *s_P = s_x + stft_xo_floats(N, S, M, R);
-    float *s_out = s_x;
-    float *s_red = s_P + R * KP; // the waves' maxima
-
-    {   // the span of frames t0 .. t0 + rows - 1, reflected at the ends of the utterance; zeros behind it
-        const int16_t *src = p.pcm + ck.utt_off;
-        const int64_t n = ck.utt_len, base = (int64_t)ck.t0 * S - N / 2;
-        const int span = (rows - 1) * S + N, all = stft_span_floats(N, S, R);
-        for (int i = tid; i < all; i += 256) {
-            float v = 0.f;
-            if (i < span) {
-                int64_t j = base + i;
-                if (j < 0) j = -j;
-                if (j >= n) j = 2 * (n - 1) - j;
-                if (j >= 0 && j < n) v = (float)src[j] * (1.0f / 32768.0f);
-            }
-            s_x[i] = v;
-        }
-    }
-
-    const int lane = tid & 63, g = tid >> 6;
+    const int lane = tid & 63;
     const int li = lane & 15, lk = lane >> 4;
-    const bool busy = 16 * g < rows && 16 * g < R;
-    const float *za = s_x + (16 * g + li) * S + lk; // lane (li, lk) feeds frame 16 g + li, tap 4 s + lk
-
     for (int b0 = 0; b0 < NBT; b0 += TBp) {
         const int cnt = min(TBp, NBT - b0);       // bin tiles of this pass
         const int pt = 2 * TBp;                   // tiles of a pass as the table holds them (the last pass: zeros beyond cnt)
         const int chunk4 = kStftKSteps * pt * 16; // 16-byte words of a chunk
         const int total4 = steps * pt * 16;
         const int nchunks = (steps + kStftKSteps - 1) / kStftKSteps;
-        const f32x4 *ops4 = (const f32x4 *)p.operands + (int64_t)(b0 / TBp) * total4;
+        const f32x4 *ops4 = (const f32x4 *)operands + (int64_t)(b0 / TBp) * total4;
 
         f32x4 pf[kStftPf] = {};
 #pragma unroll
@@ -120,7 +95,7 @@ __global__ void __launch_bounds__(256) k_stft_mel(StftParams p)
             const int i = tid + 256 * q;
             if (i < min(chunk4, total4)) ((f32x4 *)s_b)[i] = pf[q];
         }
-        __syncthreads(); // (also: s_x is staged)
+        __syncthreads(); // (also: the spans are staged)
 
         f32x4 acc[2 * kStftTB];
 #pragma unroll
@@ -165,38 +140,83 @@ __global__ void __launch_bounds__(256) k_stft_mel(StftParams p)
                 if (j >= cnt || k >= K1) continue;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const int t = 16 * g + 4 * lk + r;
+                    const int t = 4 * lk + r;
                     const float re = acc[2 * j][r], im = acc[2 * j + 1][r];
-                    if (t < rows) s_P[t * KP + k] = __builtin_fmaf(im, im, re * re);
+                    if (t < wave_rows) s_Pw[t * KP + k] = __builtin_fmaf(im, im, re * re);
                 }
             }
         }
     }
-    __syncthreads();
+}
 
-    // mel chains and the log: one (frame, band) per thread and trip
+// The mel chains and the log of `rows` frames whose power lies in s_P [rows][KP], one (frame, band) per thread and trip, to
+// s_out [rows][M]; returns the thread's largest log value.  T: the parameters of either kernel.
+template <class T>
+__device__ __forceinline__ float stft_mel_log(const T &p, const float *s_P, int KP, int rows, float *s_out, int tid)
+{
     float mx = -INFINITY;
-    {
-        const int n = rows * M;
-        const uint32_t magic = div_magic(M);
-        for (int i = tid; i < n; i += 256) {
-            const int t = div_small(i, M, magic);
-            const int m = i - t * M;
-            const int beg = p.mel_beg[m], len = p.mel_len[m];
-            const float *w = p.mel_w + p.mel_off[m];
-            const float *P = s_P + t * KP + beg;
-            float acc = 0.f;
-            for (int j = 0; j < len; ++j) acc = __builtin_fmaf(w[j], P[j], acc);
-            const float v = fmaxf(acc, 1e-10f);
-            float L;
-            if (p.post == 2)
-                L = logf(v);
-            else
-                L = v == 1e-10f ? -10.0f : log10f(v);
-            s_out[i] = L;
-            mx = fmaxf(mx, L);
+    const int M = p.M, n = rows * M;
+    const uint32_t magic = div_magic(M);
+    for (int i = tid; i < n; i += 256) {
+        const int t = div_small(i, M, magic);
+        const int m = i - t * M;
+        const int beg = p.mel_beg[m], len = p.mel_len[m];
+        const float *w = p.mel_w + p.mel_off[m];
+        const float *P = s_P + t * KP + beg;
+        float acc = 0.f;
+        for (int j = 0; j < len; ++j) acc = __builtin_fmaf(w[j], P[j], acc);
+        const float v = fmaxf(acc, 1e-10f);
+        float L;
+        if (p.post == 2)
+            L = logf(v);
+        else
+            L = v == 1e-10f ? -10.0f : log10f(v);
+        s_out[i] = L;
+        mx = fmaxf(mx, L);
+    }
+    return mx;
+}
+
+// LDS, all of it dynamic (stft_lds_bytes is the whole of what a block asks for):
+//   operand buffers [2][KS][2 TBp][64] | s_x [(R - 1) S + N + 4] (later s_out [R][M]) | s_P [R][KP] | s_red [4]
+__global__ void __launch_bounds__(256) k_stft_mel(StftParams p)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const StftChunk ck = p.chunks[blockIdx.x];
+    const int R = p.tile_rows, N = p.N, S = p.S, M = p.M;
+    const int rows = ck.n_frames;
+    const int KP = stft_p_pitch(N);
+    const int tid = threadIdx.x;
+    float *s_b = smem;
+    float *s_x = s_b + 2 * stft_buf_floats(N);
+    float *s_P = s_x + stft_xo_floats(N, S, M, R);
+    float *s_out = s_x;
+    float *s_red = s_P + R * KP; // the waves' maxima
+
+    {   // the span of frames t0 .. t0 + rows - 1, reflected at the ends of the utterance; zeros behind it
+        const int16_t *src = p.pcm + ck.utt_off;
+        const int64_t n = ck.utt_len, base = (int64_t)ck.t0 * S - N / 2;
+        const int span = (rows - 1) * S + N, all = stft_span_floats(N, S, R);
+        for (int i = tid; i < all; i += 256) {
+            float v = 0.f;
+            if (i < span) {
+                int64_t j = base + i;
+                if (j < 0) j = -j;
+                if (j >= n) j = 2 * (n - 1) - j;
+                if (j >= 0 && j < n) v = (float)src[j] * (1.0f / 32768.0f);
+            }
+            s_x[i] = v;
         }
     }
+
+    const int lane = tid & 63, g = tid >> 6;
+    const int li = lane & 15, lk = lane >> 4;
+    const bool busy = 16 * g < rows && 16 * g < R;
+    const float *za = s_x + (16 * g + li) * S + lk; // lane (li, lk) feeds frame 16 g + li, tap 4 s + lk
+    stft_dft_power(p.operands, N, s_b, za, busy, rows - 16 * g, s_P + 16 * g * KP, tid);
+    __syncthreads();
+
+    float mx = stft_mel_log(p, s_P, KP, rows, s_out, tid);
     mx = wave_max(mx);
     if (lane == 0) s_red[g] = mx;
     __syncthreads();
@@ -225,6 +245,60 @@ __global__ void __launch_bounds__(256) k_stft_post(StftParams p)
         *o = (fmaxf(*o, lo) + 4.0f) * 0.25f;
     }
 }
+
+// k_sess_stft_mel: the same chains over the rows one push of the session entries delivers, for many sessions at once
+// ("Session log-mel").  A push is many sessions with about ten frames each, so a block does not take R consecutive
+// frames of one utterance: it takes up to G = 4, 2 or 1 GROUPS (StftChunk: at most 16 consecutive frames of one session),
+// wave g owning group g, stages each group's own span, 15 S + N (+ 4) floats, from the session's current slot with the
+// reflections of the STREAM, and streams the basis through the two operand buffers once for all of them.
+// LDS: operand buffers [2][KS][2 TBp][64] | s_x [G][15 S + N + 4] (later s_out [G][16][M]) | s_P [16 G][KP]
+__global__ void __launch_bounds__(256) k_sess_stft_mel(SessStftParams p)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int G = p.G, N = p.N, S = p.S, M = p.M;
+    const int g0 = blockIdx.x * G, ng = min(G, p.n_groups - g0);
+    const int KP = stft_p_pitch(N), xo = stft_xo_floats(N, S, M, 16);
+    const int tid = threadIdx.x;
+    float *s_b = smem;
+    float *s_x = s_b + 2 * stft_buf_floats(N);
+    float *s_P = s_x + G * xo;
+
+    for (int q = 0; q < ng; ++q) { // the span of the group's frames, reflected at the ends of the stream; zeros behind it
+        const StftChunk ck = p.groups[g0 + q];
+        float *sx = s_x + q * xo;
+        const int rows = min(ck.n_frames, 16);
+        const int64_t n = ck.utt_len, base = (int64_t)ck.t0 * S - N / 2;
+        const int span = (rows - 1) * S + N, all = stft_span_floats(N, S, 16);
+        for (int i = tid; i < all; i += 256) {
+            float v = 0.f;
+            if (i < span) {
+                int64_t j = base + i;
+                if (j < 0) j = -j;
+                if (j >= n) j = 2 * (n - 1) - j;
+                const int64_t e = ck.utt_off + j; // (utt_off: where stream sample 0 would lie in the slot array)
+                if (j >= 0 && j < n && e >= 0 && e < p.pcm_elems) v = (float)p.pcm[e] * (1.0f / 32768.0f);
+            }
+            sx[i] = v;
+        }
+    }
+
+    const int lane = tid & 63, wave = tid >> 6;
+    const int li = lane & 15, lk = lane >> 4;
+    const bool busy = wave < ng;
+    const int g = busy ? wave : 0;
+    const float *za = s_x + g * xo + li * S + lk; // lane (li, lk) feeds frame li of the wave's group, tap 4 s + lk
+    stft_dft_power(p.operands, N, s_b, za, busy, busy ? min(p.groups[g0 + g].n_frames, 16) : 0, s_P + 16 * g * KP, tid);
+    __syncthreads();
+
+    for (int q = 0; q < ng; ++q) stft_mel_log(p, s_P + 16 * q * KP, KP, min(p.groups[g0 + q].n_frames, 16), s_x + q * xo, tid);
+    __syncthreads();
+    for (int q = 0; q < ng; ++q) {
+        const StftChunk ck = p.groups[g0 + q];
+        tile_store_rows(s_x + q * xo, M, min(ck.n_frames, 16), p.out, ck.out_row, p.out_pitch, tid);
+    }
+}
+
+bool stft_shape_ok(int N, int S, int M) { return N >= 32 && N <= 512 && !(N & 1) && S >= 1 && S <= N && M >= 1 && M <= 128; }
 
 bool stft_params_ok(const StftParams &p)
 {
@@ -258,6 +332,35 @@ hipError_t launch_stft(const StftParams &p, hipStream_t stream)
     if (hipError_t e = allow_dynamic_lds(fn, lds); e != hipSuccess) return e;
     StftParams q = p;
     return launch_kernel(fn, dim3(p.n_chunks), dim3(256), lds, stream, q);
+}
+
+size_t sess_stft_lds_bytes(int N, int S, int M, int G)
+{
+    const size_t f = (size_t)2 * stft_buf_floats(N) + (size_t)G * stft_xo_floats(N, S, M, 16) + (size_t)16 * G * stft_p_pitch(N);
+    return f * sizeof(float);
+}
+
+int sess_stft_groups(int N, int S, int M)
+{
+    if (!stft_shape_ok(N, S, M)) return 0;
+    for (int g : {4, 2, 1})
+        if (sess_stft_lds_bytes(N, S, M, g) <= kLdsMax) return g;
+    return 0;
+}
+
+hipError_t launch_sess_stft(const SessStftParams &p, hipStream_t stream)
+{
+    if (p.n_groups <= 0) return hipSuccess;
+    if (!stft_shape_ok(p.N, p.S, p.M) || p.out_pitch < p.M || !p.pcm || p.pcm_elems <= 0 || !p.groups || !p.operands || !p.mel_w || !p.mel_beg ||
+        !p.mel_len || !p.mel_off || !p.out)
+        return hipErrorInvalidValue;
+    const int G = sess_stft_groups(p.N, p.S, p.M);
+    if (G == 0 || p.G != G) return hipErrorInvalidValue; // (the caller sized its lists for another packing)
+    const size_t lds = sess_stft_lds_bytes(p.N, p.S, p.M, G);
+    const void *fn = (const void *)k_sess_stft_mel;
+    if (hipError_t e = allow_dynamic_lds(fn, lds); e != hipSuccess) return e;
+    SessStftParams q = p;
+    return launch_kernel(fn, dim3((p.n_groups + G - 1) / G), dim3(256), lds, stream, q);
 }
 
 hipError_t launch_stft_post(const StftParams &p, hipStream_t stream)

@@ -434,6 +434,29 @@ void build_front1024_long_window(const std::vector<float> &padded, int fft_size,
 
 int64_t stft_frame_count(int64_t samples, int N, int S) { return samples <= N / 2 ? 0 : samples / S; }
 
+int32_t session_stft_step(int N, int S, int64_t &n, int64_t &E, int64_t length, bool final_push, SessionStftStep &st)
+{
+    const int64_t half = N / 2, n_new = n + length;
+    int64_t E_new = stft_frame_count(n_new, N, S);
+    if (!final_push && n_new > half) E_new = std::min(E_new, (n_new - half) / S + 1);
+    E_new = std::max(E_new, E); // (the rule is non-decreasing in n: a state outside it delivers nothing)
+    st.c0_old = std::max<int64_t>(E * S - half, 0);
+    st.c0_new = final_push ? n_new : std::max<int64_t>(E_new * S - half, 0);
+    st.carry_in = (int32_t)(n - st.c0_old);
+    st.carry_out = (int32_t)(n_new - st.c0_new);
+    const int32_t n_out = (int32_t)(E_new - E);
+    n = final_push ? 0 : n_new;
+    E = final_push ? 0 : E_new;
+    return n_out;
+}
+
+void cut_sess_stft_groups(const int32_t *n_out, int n, std::vector<SessStftCut> &groups)
+{
+    groups.clear();
+    for (int32_t i = 0; i < n; ++i)
+        for (int32_t r0 = 0; r0 < n_out[i]; r0 += 16) groups.push_back(SessStftCut{i, r0, std::min(16, n_out[i] - r0)});
+}
+
 void build_stft_basis(int N, const float *window, float *cos_sin)
 {
     const int K1 = N / 2 + 1;

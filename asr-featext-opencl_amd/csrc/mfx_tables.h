@@ -263,6 +263,28 @@ void build_slaney_mel(int M, int N, float sample_rate, float low_freq, float hig
 // beyond the bins and the taps.  steps = ceil(N / 4), passes = ceil(ceil(K1 / 16) / tb).
 void build_stft_operands(const float *cos_sin, int N, int tb, std::vector<float> &out);
 
+// One push of one session of an STFT log-mel handle ("Session log-mel"): a stream that has received n samples and
+// delivered rows [0, E) takes `length` more.  While the stream is open E = 0 up to n = N / 2, else min(n div S, (n - N / 2)
+// div S + 1): the frames whose taps have all arrived without a right reflection, and that no later sample can take out of
+// T(n) = stft_frame_count; E = T(n) once a push is final.  The previous slot holds samples [c0_old, n_old), c0 = max(0, E S -
+// N / 2) (the first tap of frame E); the push computes frames [E_old, E_new) from them and the new samples and leaves
+// [c0_new, n_new) for the next slot: fewer than N + S samples, nothing after a final push.  Returns E_new - E_old; n and E are
+// advanced (both 0 after a final push: the session is fresh).
+struct SessionStftStep {
+    int64_t c0_old, c0_new;      // first stream sample the previous / the current slot hands on
+    int32_t carry_in, carry_out; // samples carried in and out
+};
+int32_t session_stft_step(int N, int S, int64_t &n, int64_t &E, int64_t length, bool final_push, SessionStftStep &st);
+// the most rows one push of `max_samples` samples can deliver: its own, and what a final push adds, N / (2 S) + 1
+inline int64_t session_stft_rows_max(int N, int S, int64_t max_samples) { return max_samples / S + N / (2 * S) + 2; }
+
+// The work list of k_sess_stft_mel for one push: piece i delivers n_out[i] rows and is cut into groups of at most 16
+// consecutive frames, pieces in their order; block b of the launch takes groups [G b, G b + G).
+struct SessStftCut {
+    int32_t piece, r0, rows; // the group: rows [r0, r0 + rows) of the piece
+};
+void cut_sess_stft_groups(const int32_t *n_out, int n, std::vector<SessStftCut> &groups);
+
 } // namespace mfx
 
 namespace mfx {

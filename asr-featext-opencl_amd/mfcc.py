@@ -88,7 +88,7 @@ EXPORTED_SYMBOLS = (
     "mfx_batch_set_online_norm", "mfx_batch_clear_online_norm", "mfx_sessions_set_online_norm",
     "mfx_sessions_clear_online_norm", "mfx_host_online_norm",
     "mfx_host_slaney_mel_table", "mfx_host_stft_basis", "mfx_host_stft_frame_count",
-    "mfx_host_stft_lds_bytes",
+    "mfx_host_stft_lds_bytes", "mfx_host_session_stft_step", "mfx_host_sess_stft_lds_bytes",
     "mfx_batch_set_pitch", "mfx_batch_clear_pitch", "mfx_batch_pitch_read", "mfx_batch_pitch_device", "mfx_host_pitch",
     "mfx_batch_set_pitch_feats", "mfx_batch_clear_pitch_feats", "mfx_batch_pitch_feats_read", "mfx_batch_pitch_feats_device",
     "mfx_host_pitch_feats",
@@ -214,6 +214,8 @@ def load_library():
     L.mfx_host_stft_basis.argtypes = [i32, fp, fp]
     L.mfx_host_stft_frame_count.argtypes, L.mfx_host_stft_frame_count.restype = [i64, i32, i32], i64
     L.mfx_host_stft_lds_bytes.argtypes, L.mfx_host_stft_lds_bytes.restype = [i32, i32, i32, p32], i64
+    L.mfx_host_session_stft_step.argtypes, L.mfx_host_session_stft_step.restype = [i32, i32, p64, i64, i32, p32, p32], i32
+    L.mfx_host_sess_stft_lds_bytes.argtypes, L.mfx_host_sess_stft_lds_bytes.restype = [i32, i32, i32, p32], i64
     L.mfx_batch_set_pitch.argtypes = [vp, i32, i32, i32, C.c_float, C.c_float, C.c_float, i32]
     L.mfx_batch_clear_pitch.argtypes = [vp]
     L.mfx_batch_pitch_read.argtypes = [vp, fp, p32, fp]
@@ -488,6 +490,30 @@ def host_session_resample_step(in_hz, out_hz, state, length, final=False, zeros=
     return dict(n_out=int(n), state=(int(st[0]), int(st[1])), carry_in=ci.value, carry_out=co.value)
 
 
+def host_session_stft_step(dft_size, shift, state, length, final=False):
+    """One push of one session of an STFT log-mel handle exactly as the planner derives it (host code, no GPU needed).  state
+    = (n, E): samples received and rows delivered so far.  Returns dict(rows, state, carry_in, carry_out); state is (0, 0)
+    after a final push."""
+    L = load_library()
+    st = (C.c_int64 * 2)(int(state[0]), int(state[1]))
+    ci, co = C.c_int32(0), C.c_int32(0)
+    rows = L.mfx_host_session_stft_step(int(dft_size), int(shift), st, int(length), int(bool(final)), C.byref(ci), C.byref(co))
+    if rows < 0:
+        raise MfxError(int(rows), "mfx_host_session_stft_step failed")
+    return dict(rows=int(rows), state=(int(st[0]), int(st[1])), carry_in=ci.value, carry_out=co.value)
+
+
+def host_sess_stft_lds_bytes(dft_size, shift, num_banks, groups=0):
+    """(LDS bytes of a block of k_sess_stft_mel, groups per block): at the packing mfx_sessions_create takes (groups=0), or at
+    1, 2 or 4 groups per block.  UNSTABLE inspection aid."""
+    L = load_library()
+    g = C.c_int32(int(groups))
+    n = L.mfx_host_sess_stft_lds_bytes(int(dft_size), int(shift), int(num_banks), C.byref(g))
+    if n < 0:
+        raise MfxError(int(n), "mfx_host_sess_stft_lds_bytes failed")
+    return int(n), g.value
+
+
 def host_sess_xform_groups(n_out, xf, G=4):
     """The work list of k_sess_xform (UNSTABLE inspection aid): (groups [.][3] = piece, first row, rows; blocks [.][3] = first
     group, groups, transform)."""
@@ -674,7 +700,7 @@ SPK_POOL, SPK_PRIOR_ONLY = 0, 1                            # mfx_batch_set_speak
 ENGINE_NO_FRONT1024, ENGINE_FUSE_DELTA, ENGINE_NO_FRONT2048, ENGINE_STREAM_KERNELS, ENGINE_NORM_TWO_KERNELS = 1, 2, 4, 8, 16
 ENGINE_DMA_SMALL_BLOCKS, ENGINE_NO_DCT_SPLIT, ENGINE_NO_STUFF256, ENGINE_FRONT1024_12_WAVES = 32, 64, 128, 256     # mfx_config.engine bits (include/mfx.h)
 ENGINE_TRAPS_VALU, ENGINE_XFORM_VALU, ENGINE_SESS_NARROW_LOADS = 512, 1024, 2048
-ENGINE_SESS_XFORM_PLAIN = 4096
+ENGINE_SESS_XFORM_PLAIN, ENGINE_SESS_STFT_PLAIN = 4096, 8192
 
 
 class MfccHip:
@@ -688,7 +714,7 @@ class MfccHip:
     only; the streaming methods raise ``MfxError`` (-8).
     ``method=METHOD_STFT_LOGMEL`` computes the log-mel spectrogram of the Whisper family (include/mfx.h): ``window_size`` is
     the DFT length, ``num_banks`` the output width, ``logmel_post`` one of ``LOGMEL_*``; set ``periodic_hann(window_size)``
-    as the window.  Batch entries only as well.
+    as the window.  Batch entries, and for ``LOGMEL_LOG10`` / ``LOGMEL_LN`` the session entries; no streaming methods.
     """
 
     def __init__(self, input_buffer_size, window_size, shift, num_banks, sample_rate, low_freq, high_freq,
@@ -1212,6 +1238,7 @@ class MfccHip:
     host_session_step = staticmethod(host_session_step)
     host_session_resample_step = staticmethod(host_session_resample_step)
     host_session_xform_step = staticmethod(host_session_xform_step)
+    host_session_stft_step = staticmethod(host_session_stft_step)
 
     def batch_overlap(self, enable=True):
         """Let the delta tail of a batch overlap the next batch's front end (results complete after synchronize())."""

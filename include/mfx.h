@@ -109,8 +109,8 @@ enum { MFX_METHOD_MFCC = 0, MFX_METHOD_PLP = 1, MFX_METHOD_TRAPS = 3, MFX_METHOD
 
 /* mfx_config.method 5 = the log-mel spectrogram neural recognisers of the Whisper family feed on ("STFT log-mel"):
  * an exact-length DFT of centred, reflect-padded frames, Slaney mel bands, log10, and Whisper's clamp and map.  The value 4
- * is unassigned and stays refused, as 2 does.  BATCH ENTRIES ONLY, as TRAPS: the streaming and the session entries return
- * MFX_ERR_STATE on such a handle.
+ * is unassigned and stays refused, as 2 does.  The streaming entries (mfx_set_input ...) return MFX_ERR_STATE on such a handle;
+ * the batch entries serve it, and the session entries do for logmel_post = MFX_LOGMEL_LOG10 or MFX_LOGMEL_LN (below, "Sessions").
  * Configuration (anything else: MFX_ERR_CONFIG).  window_size = N, the DFT length: even, 32 .. 512; fft_size 0 or N
  * (mfx_fft_size returns N); shift = S in 1 .. N; num_banks = M in 1 .. 128, the output width; 0 <= low_freq < high_freq <=
  * sample_rate / 2; ceps_len = 0, want_c0 = 0, dyn = NONE, norm = NONE, channels 0 or 1.  lift_coef, the delta orders and
@@ -144,7 +144,24 @@ enum { MFX_METHOD_MFCC = 0, MFX_METHOD_PLP = 1, MFX_METHOD_TRAPS = 3, MFX_METHOD
  * Entries.  mfx_batch_frames, mfx_batch_plan and mfx_batch_plan_rates use the frame rule above; mfx_batch_run_device / _host,
  * mfx_batch_overlap, mfx_batch_set_transform and mfx_batch_set_vad work as on any handle; mfx_batch_set_alphas is refused with
  * MFX_ERR_CONFIG (there is no warped Slaney table) and mfx_set_alpha has no effect; the speaker list and the online
- * normaliser are refused as on any norm = NONE handle. */
+ * normaliser are refused as on any norm = NONE handle.
+ * Sessions.  mfx_sessions_create serves LOG10 and LN handles; MFX_LOGMEL_WHISPER stays refused with MFX_ERR_STATE (its clamp
+ * needs the largest value of the whole utterance, which an open stream does not have: use the batch entries).
+ *   Delivery rule.  n = samples the session has received since it was opened (with mfx_sessions_set_rates: converted samples,
+ *     n = J), T(n) = mfx_batch_frames(n).  A session has delivered rows [0, E): while open E = 0 when n <= N / 2, else E =
+ *     min(n div S, (n - N / 2) div S + 1) -- the frames whose samples have all arrived without a right reflection (frame 0
+ *     reads sample N / 2 through its left reflection) and that no later sample can take out of the utterance; once a push is
+ *     final E = T(n), the flush (a final push without samples) included.  E never decreases, E <= T(n), and a final push
+ *     delivers at most N / (2 S) + 1 rows beyond its own samples'.  A stream that ends with n <= N / 2 delivers nothing.
+ *   Bits.  The rows of a push are the bits mfx_batch_run_device writes for the whole stream as one utterance on a handle of
+ *     the same configuration: however the stream is cut (pushes of 0 or 1 samples, pushes across n = N / 2, pushes shorter
+ *     than a hop, pieces at odd offsets of the caller's array), wherever d_out lies (any 4-byte alignment; nothing outside
+ *     [d_out, d_out + total_rows * width) is written), with or without MFX_ENGINE_SESS_STFT_PLAIN.  The reflections happen
+ *     at the true start and end of the stream only.  After a final push the id is fresh and may be reused at once.
+ *   Composition.  No static rows are carried (D = 0).  mfx_sessions_set_transform reads the delivered rows: its Ex rule and
+ *     bits are those of mfx_batch_set_transform on the batch twin.  mfx_sessions_set_rates converts in front: bits of the
+ *     mfx_batch_plan_rates twin.  The online normaliser stays refused (norm = NONE is required); mfx_set_alpha has no
+ *     effect.  mfx_sessions_run_device allocates nothing; a push leaves the batch plan and the streaming state alone. */
 enum { MFX_LOGMEL_WHISPER = 0, MFX_LOGMEL_LOG10 = 1, MFX_LOGMEL_LN = 2 };
 
 /* mfx_config.engine bits */
@@ -180,6 +197,10 @@ enum { MFX_LOGMEL_WHISPER = 0, MFX_LOGMEL_LOG10 = 1, MFX_LOGMEL_LN = 2 };
                                            k_splice_affine itself, one segment per session, instead of k_sess_xform, which packs
                                            row groups of different sessions into one block (the same bits; the comparator of
                                            tools/sess_xform_bench.py) */
+#define MFX_ENGINE_SESS_STFT_PLAIN 8192 /* session entries on an STFT log-mel handle: a push runs k_stft_mel itself, one chunk per
+                                           run of frames of one session, instead of k_sess_stft_mel, which packs 16-frame groups
+                                           of different sessions into one block (the same bits; the comparator of
+                                           tools/sess_stft_bench.py) */
 #define MFX_ENGINE_FRONT1024_12_WAVES 256 /* 1024-point fused kernel: the 12-waves-per-CU build also where the 16-wave build fits
                                             (aligned frames, window <= 512 samples, tables small enough): the same bits      */
 
@@ -917,6 +938,19 @@ int64_t mfx_host_stft_frame_count(int64_t samples, int32_t dft_size, int32_t shi
  * method's limits, MFX_ERR_CONFIG if no tile fitted.  UNSTABLE, a test / inspection aid only: the tiling is the kernel's private
  * matter. */
 int64_t mfx_host_stft_lds_bytes(int32_t dft_size, int32_t shift, int32_t num_banks, int32_t *tile_rows);
+/* One push of one session of an STFT log-mel handle, exactly as the planner derives it (the delivery rule of the method's
+ * comment).  state = {n, E} in / out: samples received, rows delivered (both 0 after a final push); returns E_new - E_old.
+ * carry_in / carry_out: the samples the previous slot hands in and the current one keeps, [max(0, E S - N / 2), n) on either
+ * side (0 out of a final push); either may be NULL.  MFX_ERR_ARG outside the method's limits, on a negative length or state, a
+ * length above 2^24, or an E that no open stream of n samples has (beyond mfx_host_stft_frame_count(n), or so far below it
+ * that N + S samples or more would be carried); nothing is written then.  Test / inspection aid. */
+int32_t mfx_host_session_stft_step(int32_t dft_size, int32_t shift, int64_t state[2], int64_t length, int32_t final_flag,
+                                   int32_t *carry_in, int32_t *carry_out);
+/* ALL the LDS bytes a block of k_sess_stft_mel asks for with *groups 16-frame groups per block.  *groups = 0 (or groups NULL)
+ * on entry: the packing mfx_sessions_create takes -- the largest of 4, 2, 1 that fits the 160 KB of a gfx950 block -- written
+ * back; 1, 2 or 4: that packing.  MFX_ERR_ARG outside the method's limits or for another *groups.  UNSTABLE, a test /
+ * inspection aid only, as mfx_host_stft_lds_bytes. */
+int64_t mfx_host_sess_stft_lds_bytes(int32_t dft_size, int32_t shift, int32_t num_banks, int32_t *groups);
 
 /* ---- test taps (device -> host copies of intermediate tables; used by the parity tests) ---- */
 /* kind: 0 = mel table [2][fft_size] floats, 1 = filter_beg [num_banks+2] int32,
