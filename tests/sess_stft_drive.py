@@ -8,10 +8,10 @@ LOG10, LN = 1, 2
 ERR_STATE, ERR_BUFFER = -8, -1
 
 
-def make(pkg, N=400, S=160, M=80, sr=16000.0, post=LOG10, engine=0):
+def make(pkg, N=400, S=160, M=80, sr=16000.0, post=LOG10, engine=0, window=None):
     m = pkg.MfccHip(200000, N, S, M, sr, 0.0, sr / 2, 0, False, 22.0, device=0, bug_compat=False,
                     method=pkg.METHOD_STFT_LOGMEL, logmel_post=post, engine=engine)
-    m.set_window(pkg.periodic_hann(N))
+    m.set_window(pkg.periodic_hann(N) if window is None else window)
     return m
 
 

@@ -3,12 +3,15 @@
 The contract (include/mfx.h, MFX_METHOD_STFT_LOGMEL, "Sessions"): the rows of a push are the bits mfx_batch_run_device writes
 for the whole stream as one utterance of a handle of the same configuration, however the stream is cut, wherever the pieces
 and d_out lie, packed or plain, with the session transform and the session rates; the counts follow the delivery rule.  The
-twin's rows themselves are held against the float64 oracle of tests/stft_ref.py at the project bar (conftest.assert_close)."""
+twin's rows themselves are held against the float64 oracle of tests/stft_ref.py at the project bar (conftest.assert_close);
+under the windows of tests/stft_edge.py, which weigh every tap -- tap 0 of a frame is the oldest carried sample --, at that
+module's bars."""
 import numpy as np
 import pytest
 
 import sess_inflight as SI
 import sess_stft_drive as SD
+import stft_edge as SE
 import stft_ref
 from conftest import assert_close, synth_utterance
 
@@ -236,3 +239,96 @@ def test_refusals(pkg):
         t.sessions_create(2, 1600)
     assert e.value.status == SD.ERR_STATE
     t.close()
+
+
+# ---- windows beyond Hann (tests/stft_edge.py): every tap weighs, so a carry one sample short shows -------------------------
+
+EDGE_SHAPES = {"400_160_80": (400, 160, 80), "34_5_6": (34, 5, 6), "416_104_40": (416, 104, 40), "512_512_80": (512, 512, 80)}
+
+
+def edge_streams(N, S):
+    """Streams of N / 2 (no frame), N / 2 + 1, N / 2 + S, 17 S + 3 and 40 S samples: full-range noise and the synthetic
+    utterance in turn."""
+    rng = np.random.default_rng(N + S)
+    lens = [N // 2, N // 2 + 1, N // 2 + S, 17 * S + 3, 40 * S]
+    return [rng.integers(-32768, 32768, n).astype(np.int16) if i % 2 == 0 else synth_utterance(n, 900 + i) for i, n in enumerate(lens)]
+
+
+@pytest.mark.parametrize("window", ["rect", "ramp", "ends"])
+@pytest.mark.parametrize("name", list(EDGE_SHAPES))
+def test_windows_beyond_hann(pkg, name, window):
+    N, S, M = EDGE_SHAPES[name]
+    w = SE.windows(N)[window]
+    utts = edge_streams(N, S)
+    cuts = {"whole": SD.cut_whole, "hop": SD.cut_step(S), "half_hop": SD.cut_step(max(S // 2, 1)), "random_empty": SD.cut_random_empty,
+            "singles_across_half": SD.cut_singles_across(N // 2)}
+    m = SD.make(pkg, N, S, M, window=w)
+    want = SD.twins(m, utts)
+    assert [len(t) for t in want] == [SD.frames(len(u), N, S) for u in utts]
+    worst, held = 0.0, []
+    for u, t in zip(utts, want):
+        if len(t):
+            ref = stft_ref.logmel(u, w, S, M, 16000.0, 0.0, 8000.0, stft_ref.LOG10)
+            ok = SE.sensitivity(u, w, S, M, 16000.0, 0.0, 8000.0) <= SE.COND_TOL10
+            held.append(ok.reshape(-1))
+            worst = max(worst, SE.assert_rows(t, ref, SE.BARS[window], "%s %s, twin of %d samples" % (name, window, len(u)), ok=ok))
+    assert np.concatenate(held).mean() >= 0.99                  # (noise: all but a stray entry is held)
+    print("\n%s %s: the twin's worst |d L| %.3g / bar %.3g = %.3f" % (name, window, worst, SE.BARS[window], worst / SE.BARS[window]))
+    for engine in (0, PLAIN):
+        if engine:
+            m = SD.make(pkg, N, S, M, engine=PLAIN, window=w)
+        m.sessions_create(3, max(len(u) for u in utts))         # three ids for five streams
+        for k, (cname, cut) in enumerate(cuts.items()):
+            SD.compare(SD.drive(m, utts, 3, cut, N, S, seed=70 + k), want, "%s %s engine %d, %s" % (name, window, engine, cname))
+        m.close()
+
+
+def cut_singles_at_every_boundary(N, S):
+    """Pushes that end one sample in front of, on and one sample behind every n = N / 2 + k S, the counts at which frame k
+    becomes deliverable and the carry moves on by a hop."""
+    def cut(n, rng):
+        ends = sorted({e for k in range(max(n - N // 2, 0) // S + 2) for e in (N // 2 + k * S - 1, N // 2 + k * S, N // 2 + k * S + 1)
+                       if 0 < e < n} | {n})
+        out, pos = [], 0
+        for e in ends:
+            out.append((e - pos, False))
+            pos = e
+        out[-1] = (out[-1][0], True)
+        return out
+    return cut
+
+
+@pytest.mark.parametrize("name", ["400_160_80", "34_5_6"])
+def test_tap_probes_through_sessions(pkg, name):
+    """One-hot windows on taps 0, 1, N / 2 and N - 1 over the probe signal: every row names the sample it was read from.  Tap 0
+    of the first frame of a push is the oldest carried sample, c0 = max(0, E S - N / 2): under Hann it meets an exact zero."""
+    N, S, M = EDGE_SHAPES[name]
+    utts = [SE.probe_signal(n, start=31 * k) for k, n in enumerate(SE.probe_lengths(N, S, 16))]
+    table = stft_ref.mel_table(M, N, 16000.0, 0.0, 8000.0)[0].astype(np.float64)
+    worst = 0.0
+    for j in (0, 1, N // 2, N - 1):
+        w = SE.onehot(N, j)
+        b = stft_ref.basis(w).astype(np.float64)[:, :, j]
+        with np.errstate(divide="ignore"):
+            rowsum = np.log10(table @ (b[0] ** 2 + b[1] ** 2))
+        band = int(np.argmax(np.isfinite(rowsum)))
+        m = SD.make(pkg, N, S, M, window=w)
+        want = SD.twins(m, utts)
+        m.sessions_create(3, max(len(u) for u in utts))         # three ids for six streams: every slot is reused
+        for k, cut in enumerate((SD.cut_step(S), cut_singles_at_every_boundary(N, S))):
+            got = SD.drive(m, utts, 3, cut, N, S, seed=80 + k)
+            for s, (u, g, t) in enumerate(zip(utts, got, want)):
+                ref = stft_ref.logmel(u, w, S, M, 16000.0, 0.0, 8000.0, stft_ref.LOG10)
+                idx = stft_ref.frame_index(len(u), N, S)[:, j] if len(ref) else []
+                assert g.shape == ref.shape
+                floor = ref == SE.FLOOR_WANT
+                d = np.where(floor, 0.0, np.abs(g.astype(np.float64) - ref))
+                bad = np.nonzero((d.max(axis=1) > SE.ONEHOT_BAR) | ((g != SE.FLOOR_L10) & floor).any(axis=1))[0]
+                assert bad.size == 0, ("%s tap %d cut %d stream %d: %d rows miss the one-hot bar; frame %d reads sample = %d (mod 193), "
+                                       "the frame rule sample %d = %d (mod 193)") % (
+                    name, j, k, s, bad.size, bad[0], SE.probe_decode(float(g[bad[0], band]), rowsum[band]), idx[bad[0]],
+                    (idx[bad[0]] + 31 * s) % SE.PROBE_PERIOD)
+                worst = max(worst, d.max(initial=0.0))
+            SD.compare(got, want, "%s tap %d cut %d" % (name, j, k))
+        m.close()
+    print("\n%s one-hot probes through sessions: worst |d L| %.3g / bar %.3g = %.3f" % (name, worst, SE.ONEHOT_BAR, worst / SE.ONEHOT_BAR))
