@@ -52,6 +52,8 @@ from .mfcc import (  # noqa: F401
     host_traps_basis,
     host_slaney_mel_table,
     host_stft_basis,
+    host_stft_fft_tables,
+    host_stft_fft_lds_bytes,
     stft_frame_count,
     periodic_hann,
     host_xform_operands,

@@ -361,11 +361,15 @@ struct HandleDeleter {
     void operator()(mfx_handle *h) const { mfx_destroy(h); }
 };
 
-// the limits of an STFT log-mel handle (include/mfx.h): everything sized from N, S and M fits k_stft_mel's LDS by them
+// DFT lengths of an STFT log-mel handle: even, 32 .. 512 (the matrix form), and 1024 / 2048 (the FFT form)
+bool stft_matrix_size(int N) { return N >= 32 && N <= 512 && !(N & 1); }
+bool stft_fft_size(int N) { return N == 1024 || N == 2048; }
+
+// the limits of an STFT log-mel handle (include/mfx.h): everything sized from N, S and M fits the kernel's LDS by them
 bool stft_config_ok(const mfx_config *cfg)
 {
     const int N = cfg->window_size;
-    if (N < 32 || N > 512 || (N & 1) || (cfg->fft_size != 0 && cfg->fft_size != N)) return false;
+    if ((!stft_matrix_size(N) && !stft_fft_size(N)) || (cfg->fft_size != 0 && cfg->fft_size != N)) return false;
     if (cfg->shift < 1 || cfg->shift > N || cfg->num_banks < 1 || cfg->num_banks > 128) return false;
     if (!(cfg->low_freq >= 0.f) || !(cfg->low_freq < cfg->high_freq) || !(cfg->high_freq <= cfg->sample_rate / 2)) return false;
     if (cfg->ceps_len != 0 || cfg->want_c0 != 0 || cfg->dyn != MFX_DYN_NONE || cfg->norm != MFX_NORM_NONE || cfg->channels > 1) return false;
@@ -384,7 +388,10 @@ int create_stft(mfx_handle *h, bool planning, std::unique_ptr<mfx_handle, Handle
     if (h->input_window_limit <= 0) return MFX_ERR_CONFIG;
     h->cap_rows = h->window_limit + h->W / h->S + 4;
     h->spec_pitch = ((h->W2 / 2 + 1) + 3) & ~3;
-    h->stft_R = stft_tile_rows(h->W, h->S, h->nb); // (16 frames fit for every shape inside the limits: 512 / 512 / 128 takes 74 KB then)
+    h->stft_fft = stft_fft_size(h->W);
+    // (the matrix form: 16 frames fit for every shape inside the limits, 512 / 512 / 128 takes 74 KB then; the FFT form: 4 do,
+    // 2048 / 2048 / 128 takes 104 KB then)
+    h->stft_R = h->stft_fft ? stft_fft_tile_rows(h->W, h->S, h->nb) : stft_tile_rows(h->W, h->S, h->nb);
     if (h->stft_R == 0) return MFX_ERR_CONFIG;
     if (!planning) {
         hipDeviceProp_t prop;
@@ -783,7 +790,7 @@ int launch_front(mfx_handle *h, FrontParams &p, FrontKind kind, bool aligned, co
 extern "C" const char *mfx_dominant_kernel_name(const mfx_handle *h)
 {
     if (!h) return "";
-    if (h->stft) return "k_stft_mel";
+    if (h->stft) return h->stft_fft ? "k_stft_fft_mel" : "k_stft_mel";
     switch (batch_front(h)) { // names as rocprofv3 prints them
     case kFront512:
     case kSpec512: return "k_front512";
@@ -811,10 +818,15 @@ extern "C" int mfx_set_window(mfx_handle *h, const float *window)
     MFX_DEVICE_ENTRY(h);
     if (!window) return fail(h, MFX_ERR_ARG, "invalid argument");
     HIP_TRY(h, hipSetDevice(h->device));
-    if (h->stft) { // the windowed basis as k_stft_mel streams it
-        std::vector<float> basis((size_t)2 * (h->W / 2 + 1) * h->W), ops;
-        build_stft_basis(h->W, window, basis.data());
-        build_stft_operands(basis.data(), h->W, kStftTB < (h->W / 2 + 16) / 16 ? kStftTB : (h->W / 2 + 16) / 16, ops);
+    if (h->stft) { // the windowed basis as k_stft_mel streams it; the FFT form: the window and the FFT tables, no basis
+        std::vector<float> basis, ops;
+        if (h->stft_fft) {
+            build_stft_fft_operands(h->W, window, ops);
+        } else {
+            basis.resize((size_t)2 * (h->W / 2 + 1) * h->W);
+            build_stft_basis(h->W, window, basis.data());
+            build_stft_operands(basis.data(), h->W, kStftTB < (h->W / 2 + 16) / 16 ? kStftTB : (h->W / 2 + 16) / 16, ops);
+        }
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         if (h->batch.ov.stream2) HIP_TRY(h, hipStreamSynchronize(h->batch.ov.stream2));
         HIP_TRY(h, h->upload(h->d_stft_ops, ops));
@@ -1033,7 +1045,7 @@ extern "C" int64_t mfx_host_xform_operands(int32_t out_dim, int32_t in_dim, cons
 
 extern "C" int64_t mfx_host_stft_lds_bytes(int32_t dft_size, int32_t shift, int32_t num_banks, int32_t *tile_rows)
 {
-    if (dft_size < 32 || dft_size > 512 || (dft_size & 1) || shift < 1 || shift > dft_size || num_banks < 1 || num_banks > 128) return MFX_ERR_ARG;
+    if (!stft_matrix_size(dft_size) || shift < 1 || shift > dft_size || num_banks < 1 || num_banks > 128) return MFX_ERR_ARG;
     const int R = stft_tile_rows(dft_size, shift, num_banks);
     if (tile_rows) *tile_rows = R;
     return R > 0 ? (int64_t)stft_lds_bytes(dft_size, shift, num_banks, R) : MFX_ERR_CONFIG;
@@ -1041,13 +1053,31 @@ extern "C" int64_t mfx_host_stft_lds_bytes(int32_t dft_size, int32_t shift, int3
 
 extern "C" int64_t mfx_host_stft_frame_count(int64_t samples, int32_t dft_size, int32_t shift)
 {
-    if (samples < 0 || dft_size < 32 || dft_size > 512 || (dft_size & 1) || shift < 1 || shift > dft_size) return MFX_ERR_ARG;
+    if (samples < 0 || (!stft_matrix_size(dft_size) && !stft_fft_size(dft_size)) || shift < 1 || shift > dft_size) return MFX_ERR_ARG;
     return stft_frame_count(samples, dft_size, shift);
+}
+
+// FFT form (dft_size 1024 / 2048): ALL the LDS bytes of a block of k_stft_fft_mel at the tile mfx_create takes
+extern "C" int64_t mfx_host_stft_fft_lds_bytes(int32_t dft_size, int32_t shift, int32_t num_banks, int32_t *tile_rows)
+{
+    if (!stft_fft_shape_ok(dft_size, shift, num_banks)) return MFX_ERR_ARG;
+    const int R = stft_fft_tile_rows(dft_size, shift, num_banks);
+    if (tile_rows) *tile_rows = R;
+    return R > 0 ? (int64_t)stft_fft_lds_bytes(dft_size, shift, num_banks, R) : MFX_ERR_CONFIG;
+}
+
+// FFT form: the tables as mfx_set_window uploads them behind the window: twid [dft_size / 2] complex, split [dft_size / 2 + 1]
+// complex
+extern "C" int mfx_host_stft_fft_tables(int32_t dft_size, float *twid, float *split)
+{
+    if (!stft_fft_size(dft_size) || !twid || !split) return MFX_ERR_ARG;
+    build_stft_fft_tables(dft_size, twid, split);
+    return MFX_OK;
 }
 
 extern "C" int mfx_host_stft_basis(int32_t dft_size, const float *window, float *cos_sin)
 {
-    if (dft_size < 32 || dft_size > 512 || (dft_size & 1) || !window || !cos_sin) return MFX_ERR_ARG;
+    if (!stft_matrix_size(dft_size) || !window || !cos_sin) return MFX_ERR_ARG;
     build_stft_basis(dft_size, window, cos_sin);
     return MFX_OK;
 }
@@ -1055,7 +1085,7 @@ extern "C" int mfx_host_stft_basis(int32_t dft_size, const float *window, float 
 extern "C" int mfx_host_slaney_mel_table(int32_t num_banks, int32_t dft_size, float sample_rate, float low_freq, float high_freq,
                                          float *weights, int32_t *beg, int32_t *len)
 {
-    if (num_banks < 1 || num_banks > 128 || dft_size < 32 || dft_size > 512 || (dft_size & 1) || !weights || !beg || !len) return MFX_ERR_ARG;
+    if (num_banks < 1 || num_banks > 128 || (!stft_matrix_size(dft_size) && !stft_fft_size(dft_size)) || !weights || !beg || !len) return MFX_ERR_ARG;
     if (!(sample_rate > 0.f) || !(low_freq >= 0.f) || !(low_freq < high_freq) || !(high_freq <= sample_rate / 2)) return MFX_ERR_ARG;
     build_slaney_mel(num_banks, dft_size, sample_rate, low_freq, high_freq, weights, beg, len);
     return MFX_OK;

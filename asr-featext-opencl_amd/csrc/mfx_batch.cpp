@@ -158,7 +158,7 @@ RunMode decide_mode(const mfx_handle *h, FrontParams &p, float *d_out, bool whol
 int run_front(mfx_handle *h, FrontParams &p, const RunMode &m, int u0, int u1, int32_t c0, int32_t c1)
 {
     BatchState &B = h->batch;
-    if (h->stft) { // k_stft_mel over the range's blocks, then (WHISPER) the clamp by the utterance's maximum, in place
+    if (h->stft) { // k_stft_mel (k_stft_fft_mel) over the range's blocks, then (WHISPER) the clamp by the utterance's maximum, in place
         StftParams sp{};
         sp.pcm = p.pcm;
         sp.chunks = B.d_stft_chunks.p + c0;
@@ -175,7 +175,7 @@ int run_front(mfx_handle *h, FrontParams &p, const RunMode &m, int u0, int u1, i
         sp.blk_max = B.d_stft_max.p;
         {
             ProfScope ps(h);
-            HIP_TRY(h, launch_stft(sp, h->stream));
+            HIP_TRY(h, h->stft_fft ? launch_stft_fft(sp, h->stream) : launch_stft(sp, h->stream));
         }
         if (sp.post == MFX_LOGMEL_WHISPER) HIP_TRY(h, launch_stft_post(sp, h->stream));
         return MFX_OK;

@@ -573,8 +573,10 @@ struct mfx_handle {
     // LN) the session entries through k_sess_stft_mel.  W is the
     // DFT length N (W2 == W), nb the output width; none of the FFT / mel / DCT tables below exist on such a handle
     bool stft = false;
-    int stft_R = 0;                      // frames per block of k_stft_mel (stft_tile_rows)
-    DevBuf<float> d_stft_ops, d_stft_melw; // basis operands (mfx_set_window builds them); the mel rows' spans back to back
+    bool stft_fft = false;               // N = 1024 / 2048: k_stft_fft_mel stands where k_stft_mel does; batch entries only
+    int stft_R = 0;                      // frames per block of k_stft_mel (stft_tile_rows) or k_stft_fft_mel (stft_fft_tile_rows)
+    DevBuf<float> d_stft_ops, d_stft_melw; // basis operands -- FFT form: window and FFT tables -- (mfx_set_window builds them); the mel
+                                         // rows' spans back to back
     DevBuf<int32_t> d_stft_mel;          // [3][nb]: beg, len, first weight of every row
     float alpha = 1.f;
     bool have_window = false;

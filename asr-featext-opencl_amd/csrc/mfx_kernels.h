@@ -1,4 +1,4 @@
-// mfx_kernels.h -- launch interface of the gfx950 kernels (implemented in mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip, mfx_plp.hip, mfx_traps.hip, mfx_xform.hip, mfx_sess_xform.hip, mfx_sess_resample.hip, mfx_sessions.hip, mfx_resample.hip, mfx_speakers.hip, mfx_vad.hip, mfx_onorm.hip, mfx_stft.hip, mfx_pitch.hip, mfx_pitchfeat.hip: one translation unit per kernel family).
+// mfx_kernels.h -- launch interface of the gfx950 kernels (implemented in mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip, mfx_plp.hip, mfx_traps.hip, mfx_xform.hip, mfx_sess_xform.hip, mfx_sess_resample.hip, mfx_sessions.hip, mfx_resample.hip, mfx_speakers.hip, mfx_vad.hip, mfx_onorm.hip, mfx_stft.hip, mfx_stft_fft.hip, mfx_pitch.hip, mfx_pitchfeat.hip: one translation unit per kernel family).
 //
 // Kernel inventory and the reference stage each one replaces:
 //   spectrum512 / fused512   segmenter.cl kernelSegmentWindow + AppleFFT fft0 + mfcc.cl kernelTranspose
@@ -22,6 +22,8 @@
 //                            NormalizerCPU keeps one block's statistics)
 //   stft_mel / stft_post     the STFT log-mel front end: exact-length DFT of centred frames on the matrix pipe, power, Slaney mel, log;
 //                            the clamp by the utterance's maximum and the map (no reference analogue: a neural recogniser's input)
+//   stft_fft_mel             the same front end at DFT lengths 1024 / 2048: window product, a float32 FFT per wave and frame (half-length
+//                            complex Stockham FFT in LDS + real split), then stft_mel's power, mel and log; stft_post follows unchanged
 //   sess_stft_mel            the same front end over the frames one push of the session entries completes, groups of 16 frames of
 //                            different sessions sharing a block's pass over the basis (no reference analogue)
 //   delta                    delta.cl kernelDelta x2 + the staging copies of mfccopencl.cpp:360-387
@@ -593,6 +595,17 @@ size_t stft_lds_bytes(int N, int S, int M, int tile_rows);
 int stft_tile_rows(int N, int S, int M); // frames per block: the largest of 64 / 32 / 16 whose LDS fits, 0: none
 hipError_t launch_stft(const StftParams &p, hipStream_t stream);      // k_stft_mel
 hipError_t launch_stft_post(const StftParams &p, hipStream_t stream); // k_stft_post (WHISPER: clamp and map, in place)
+
+// k_stft_fft_mel (mfx_stft_fft.hip; DESIGN.md, "STFT log-mel, FFT form"): the same front end at N = 1024 / 2048, the DFT as a
+// float32 FFT.  It takes the chunks, the mel table and the slots of k_stft_mel through StftParams; `operands` is then the
+// window, the twiddles and the split table back to back (build_stft_fft_operands: 3 N + 2 floats), tile_rows 16, 8 or 4, and
+// k_stft_post follows unchanged.
+bool stft_fft_shape_ok(int N, int S, int M);
+bool stft_fft_params_ok(const StftParams &p); // what launch_stft_fft takes (launch_stft_post: either form's parameters)
+// ALL the LDS a block of k_stft_fft_mel asks for at tile_rows frames per block: the kernel declares no static LDS beside it
+size_t stft_fft_lds_bytes(int N, int S, int M, int tile_rows);
+int stft_fft_tile_rows(int N, int S, int M); // frames per block: the largest of 16 / 8 / 4 whose LDS fits, 0: none
+hipError_t launch_stft_fft(const StftParams &p, hipStream_t stream);
 
 // k_sess_stft_mel (mfx_stft.hip; DESIGN.md, "Session log-mel"): the rows one push of the session entries delivers on an STFT
 // log-mel handle.  The work list: groups of at most 16 consecutive frames of ONE session (StftChunk: utt_off is the element of

@@ -75,6 +75,10 @@ extern "C" int mfx_sessions_create(mfx_handle *h, int32_t n_sessions, int32_t ma
     MFX_DEVICE_ENTRY(h);
     if (h->traps)
         return fail(h, MFX_ERR_STATE, "the session entries do not serve TRAPS handles (their look-ahead is (L - 1) / 2 frames, not D)");
+    if (h->stft_fft)
+        return fail(h, MFX_ERR_STATE,
+                    "the session entries do not serve STFT log-mel handles of DFT length 1024 / 2048 (the carried-tail rule stops at 512): "
+                    "use the batch entries (mfx_batch_plan + mfx_batch_run_device / mfx_batch_run_host)");
     if (h->stft && h->cfg.logmel_post == MFX_LOGMEL_WHISPER)
         return fail(h, MFX_ERR_STATE,
                     "the session entries do not serve MFX_LOGMEL_WHISPER (its clamp needs the largest value of the whole utterance): use "

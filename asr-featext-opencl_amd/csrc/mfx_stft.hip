@@ -25,7 +25,8 @@
 // log value goes to its slot of blk_max.
 // k_stft_post (WHISPER only): the block of a chunk takes the maximum over the slots of its utterance's chunks -- a float
 // maximum does not depend on the order, no atomics -- and clamps and maps its own rows in place.
-// k_sess_stft_mel (the session entries, LOG10 / LN): the same DFT loop and mel stage (stft_dft_power, stft_mel_log below: one
+// k_sess_stft_mel (the session entries, LOG10 / LN): the same DFT loop and mel stage (stft_dft_power below, stft_mel_log of
+// mfx_stft_dev.h -- which k_stft_fft_mel, the FFT form of mfx_stft_fft.hip, shares with the span staging: one
 // chain per value, tap for tap) over groups of at most 16 frames of DIFFERENT sessions per block; see its own comment.
 #include "mfx_kernels.h"
 
@@ -33,13 +34,13 @@
 
 #include "mfx_dev.h"
 #include "mfx_launch.h"
+#include "mfx_stft_dev.h"
 #include "mfx_tile_dev.h"
 
 namespace mfx {
 
 namespace {
 
-__host__ __device__ inline int stft_bins(int N) { return N / 2 + 1; }
 __host__ __device__ inline int stft_bin_tiles(int N) { return (stft_bins(N) + 15) >> 4; }
 __host__ __device__ inline int stft_steps(int N) { return (N + 3) >> 2; }
 // bin tiles of a pass: as many as the DFT has, at most kStftTB (the operand table is laid out for it)
@@ -54,15 +55,6 @@ __host__ __device__ inline int stft_xo_floats(int N, int S, int M, int R)
     const int a = stft_span_floats(N, S, R), b = R * M;
     return ((a > b ? a : b) + 3) & ~3;
 }
-__host__ __device__ inline int stft_p_pitch(int N) { return stft_bins(N) | 1; } // odd: a column of P spreads over the banks
-
-__device__ __forceinline__ float wave_max(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 constexpr int kStftPf = (kStftKSteps * 2 * kStftTB * 16 + 255) / 256; // 16-byte words a thread carries for the next chunk
 
 // The DFT and the power of a wave's 16 frames, shared by k_stft_mel and k_sess_stft_mel: every pass over the taps, the basis
@@ -149,34 +141,6 @@ __device__ __forceinline__ void stft_dft_power(const float *operands, int N, flo
     }
 }
 
-// The mel chains and the log of `rows` frames whose power lies in s_P [rows][KP], one (frame, band) per thread and trip, to
-// s_out [rows][M]; returns the thread's largest log value.  T: the parameters of either kernel.
-template <class T>
-__device__ __forceinline__ float stft_mel_log(const T &p, const float *s_P, int KP, int rows, float *s_out, int tid)
-{
-    float mx = -INFINITY;
-    const int M = p.M, n = rows * M;
-    const uint32_t magic = div_magic(M);
-    for (int i = tid; i < n; i += 256) {
-        const int t = div_small(i, M, magic);
-        const int m = i - t * M;
-        const int beg = p.mel_beg[m], len = p.mel_len[m];
-        const float *w = p.mel_w + p.mel_off[m];
-        const float *P = s_P + t * KP + beg;
-        float acc = 0.f;
-        for (int j = 0; j < len; ++j) acc = __builtin_fmaf(w[j], P[j], acc);
-        const float v = fmaxf(acc, 1e-10f);
-        float L;
-        if (p.post == 2)
-            L = logf(v);
-        else
-            L = v == 1e-10f ? -10.0f : log10f(v);
-        s_out[i] = L;
-        mx = fmaxf(mx, L);
-    }
-    return mx;
-}
-
 // LDS, all of it dynamic (stft_lds_bytes is the whole of what a block asks for):
 //   operand buffers [2][KS][2 TBp][64] | s_x [(R - 1) S + N + 4] (later s_out [R][M]) | s_P [R][KP] | s_red [4]
 __global__ void __launch_bounds__(256) k_stft_mel(StftParams p)
@@ -194,19 +158,8 @@ __global__ void __launch_bounds__(256) k_stft_mel(StftParams p)
     float *s_red = s_P + R * KP; // the waves' maxima
 
     {   // the span of frames t0 .. t0 + rows - 1, reflected at the ends of the utterance; zeros behind it
-        const int16_t *src = p.pcm + ck.utt_off;
-        const int64_t n = ck.utt_len, base = (int64_t)ck.t0 * S - N / 2;
         const int span = (rows - 1) * S + N, all = stft_span_floats(N, S, R);
-        for (int i = tid; i < all; i += 256) {
-            float v = 0.f;
-            if (i < span) {
-                int64_t j = base + i;
-                if (j < 0) j = -j;
-                if (j >= n) j = 2 * (n - 1) - j;
-                if (j >= 0 && j < n) v = (float)src[j] * (1.0f / 32768.0f);
-            }
-            s_x[i] = v;
-        }
+        stft_stage_span(p.pcm, ck.utt_off, INT64_MAX, ck.utt_len, (int64_t)ck.t0 * S - N / 2, span, all, s_x, tid);
     }
 
     const int lane = tid & 63, g = tid >> 6;
@@ -264,22 +217,10 @@ __global__ void __launch_bounds__(256) k_sess_stft_mel(SessStftParams p)
     float *s_P = s_x + G * xo;
 
     for (int q = 0; q < ng; ++q) { // the span of the group's frames, reflected at the ends of the stream; zeros behind it
-        const StftChunk ck = p.groups[g0 + q];
-        float *sx = s_x + q * xo;
+        const StftChunk ck = p.groups[g0 + q]; // (utt_off: where stream sample 0 would lie in the slot array)
         const int rows = min(ck.n_frames, 16);
-        const int64_t n = ck.utt_len, base = (int64_t)ck.t0 * S - N / 2;
         const int span = (rows - 1) * S + N, all = stft_span_floats(N, S, 16);
-        for (int i = tid; i < all; i += 256) {
-            float v = 0.f;
-            if (i < span) {
-                int64_t j = base + i;
-                if (j < 0) j = -j;
-                if (j >= n) j = 2 * (n - 1) - j;
-                const int64_t e = ck.utt_off + j; // (utt_off: where stream sample 0 would lie in the slot array)
-                if (j >= 0 && j < n && e >= 0 && e < p.pcm_elems) v = (float)p.pcm[e] * (1.0f / 32768.0f);
-            }
-            sx[i] = v;
-        }
+        stft_stage_span(p.pcm, ck.utt_off, p.pcm_elems, ck.utt_len, (int64_t)ck.t0 * S - N / 2, span, all, s_x + q * xo, tid);
     }
 
     const int lane = tid & 63, wave = tid >> 6;
@@ -366,7 +307,7 @@ hipError_t launch_sess_stft(const SessStftParams &p, hipStream_t stream)
 hipError_t launch_stft_post(const StftParams &p, hipStream_t stream)
 {
     if (p.n_chunks <= 0) return hipSuccess;
-    if (!stft_params_ok(p)) return hipErrorInvalidValue;
+    if (!stft_params_ok(p) && !stft_fft_params_ok(p)) return hipErrorInvalidValue; // (the chunks of either front end)
     StftParams q = p;
     return launch_kernel((const void *)k_stft_post, dim3(p.n_chunks), dim3(256), 0, stream, q);
 }

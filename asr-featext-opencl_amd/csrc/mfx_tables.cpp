@@ -512,6 +512,22 @@ void build_stft_operands(const float *cos_sin, int N, int tb, std::vector<float>
                 }
 }
 
+void build_stft_fft_tables(int N, float *twid, float *split)
+{
+    std::vector<float> t;
+    build_twiddles(N / 2, N / 2, t); // W_M^k, k < M
+    std::copy(t.begin(), t.end(), twid);
+    build_split_twiddles(N, false, t); // -i W_N^k, k <= M
+    std::copy(t.begin(), t.end(), split);
+}
+
+void build_stft_fft_operands(int N, const float *window, std::vector<float> &out)
+{
+    out.assign((size_t)3 * N + 2, 0.f);
+    std::copy(window, window + N, out.begin());
+    build_stft_fft_tables(N, out.data() + N, out.data() + 2 * N);
+}
+
 } // namespace mfx
 
 namespace mfx {

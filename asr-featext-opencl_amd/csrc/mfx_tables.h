@@ -262,6 +262,12 @@ void build_slaney_mel(int M, int N, float sample_rate, float low_freq, float hig
 // sin rows); out[((pass * steps + s) * 2 tb + tile) * 64 + lane] = row(16 bin tile + (lane & 15))[4 s + (lane >> 4)], zero
 // beyond the bins and the taps.  steps = ceil(N / 4), passes = ceil(ceil(K1 / 16) / tb).
 void build_stft_operands(const float *cos_sin, int N, int tb, std::vector<float> &out);
+// FFT form (N = 1024 / 2048, M = N / 2; DESIGN.md, "STFT log-mel, FFT form"), in double, rounded once:
+// twid [M] complex: W_M^k = e^(-2 pi i k / M), the twiddles of the half-length complex FFT; split [M + 1] complex: -i W_N^k, the
+// real split's factors (2 X[k] = (Z[k] + conj Z[M - k]) + split[k] (Z[k] - conj Z[M - k]))
+void build_stft_fft_tables(int N, float *twid, float *split);
+// what k_stft_fft_mel takes as its operands: window [N] | twid [2 M] | split [2 (M + 1)], 3 N + 2 floats
+void build_stft_fft_operands(int N, const float *window, std::vector<float> &out);
 
 // One push of one session of an STFT log-mel handle ("Session log-mel"): a stream that has received n samples and
 // delivered rows [0, E) takes `length` more.  While the stream is open E = 0 up to n = N / 2, else min(n div S, (n - N / 2)

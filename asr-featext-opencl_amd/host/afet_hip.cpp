@@ -64,6 +64,8 @@ struct Options {
     int method = MFX_METHOD_MFCC, model_order = 8; // --method MFCC|PLP|TRAPS, --model-order (ASR_OCL.cpp:54-56: default 8)
     int traps_len = 31, traps_dct = 10;            // --traps-length, --traps-dct (ASR_OCL.cpp:604-606: defaults 31 and 10)
     int logmel_post = MFX_LOGMEL_WHISPER;          // --logmel-post whisper|log10|ln (--method LOGMEL)
+    int logmel_nfft = 0;                           // --logmel-nfft 1024|2048 (--method LOGMEL): the DFT length; the Hann window of
+                                                   // the --window-size length is centred in it.  0: the window's own length
     bool htk = false; // binary output in HTK parameter-file format instead of the reference's text rows
     int format_threads = 4; // threads that format the text rows of a block (per worker)
     int batch_mb = 16;      // PCM per batch of files (0: the per-file loop only); small enough that a few thousand files pipeline
@@ -644,10 +646,12 @@ void worker(const Options &o, int device, float sr, const std::vector<std::strin
             std::atomic<size_t> &next, std::atomic<int> &failures)
 {
     try {
-        const long W = (long)(sr * o.window_ms * 1e-3), S = (long)(sr * o.shift_ms * 1e-3);
+        // (--logmel-nfft: the frames are nfft samples long, the window of WL samples lies centred in them)
+        const long WL = (long)(sr * o.window_ms * 1e-3), S = (long)(sr * o.shift_ms * 1e-3);
+        const long W = o.logmel_nfft > 0 ? (long)o.logmel_nfft : WL;
         // (a header that announces a sample rate of a few Hz -- found by mutating the reference's own sample1.wav, round 4 --
         // makes the window or the shift shorter than one sample: refused here, before anything divides by the shift)
-        if (W < 1 || S < 1) throw std::runtime_error("window or shift shorter than one sample at this sample rate");
+        if (WL < 1 || S < 1) throw std::runtime_error("window or shift shorter than one sample at this sample rate");
         // The extractor (HIP start-up, code object load, tables: 0.1-0.3 s of a fresh process) is created on a helper
         // thread while this one claims and reads the first batch of files: reading needs nothing from the device.
         auto make_param = [&]() -> std::unique_ptr<MfccHip> {
@@ -666,8 +670,8 @@ void worker(const Options &o, int device, float sr, const std::vector<std::strin
             }
             if (o.method == MFX_METHOD_STFT_LOGMEL) { // batch entries only; the window is the periodic Hann, samples are scaled in the kernel
                 std::unique_ptr<MfccHip> t(new LogmelHip(o.sample_limit, (int)W, (int)S, o.banks, sr, o.low, o.high, o.logmel_post, device));
-                std::vector<float> window((size_t)W);
-                for (long i = 0; i < W; ++i) window[i] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * (double)i / (double)W));
+                std::vector<float> window((size_t)W, 0.f); // (torch.stft's placement: left pad (W - WL) / 2)
+                for (long i = 0; i < WL; ++i) window[(W - WL) / 2 + i] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * (double)i / (double)WL));
                 t->set_window(window.data());
                 if (g_time.on) g_time.t_created = now_ns();
                 return t;
@@ -1060,6 +1064,10 @@ int main(int argc, char **argv)
         }
         else if (a == "--traps-length") o.traps_len = std::atoi(val());
         else if (a == "--traps-dct") o.traps_dct = std::atoi(val());
+        else if (a == "--logmel-nfft") {
+            o.logmel_nfft = std::atoi(val());
+            if (o.logmel_nfft != 1024 && o.logmel_nfft != 2048) { std::fprintf(stderr, "--logmel-nfft: 1024 or 2048\n"); return 2; }
+        }
         else if (a == "--logmel-post") {
             const std::string m = val();
             if (m == "whisper") o.logmel_post = MFX_LOGMEL_WHISPER;
@@ -1125,6 +1133,7 @@ int main(int argc, char **argv)
                         "         [--sample-limit n] [--dev n | --devs a,b,...] [--bug-compat 0|1] [--htk]  in.wav out.txt [...]\n"
                         "         [--method MFCC|PLP|TRAPS|LOGMEL] [--model-order n (PLP model order, default 8)]\n"
                         "         [--logmel-post whisper|log10|ln (LOGMEL: what follows the log; default whisper)]\n"
+                        "         [--logmel-nfft 1024|2048 (LOGMEL: the DFT length; the Hann window of --window-size lies centred in it)]\n"
                         "         [--traps-length n (TRAPS frames per trajectory, odd, default 31)] [--traps-dct n (default 10)]\n"
                         "         [--batch-mb n (PCM per batch of whole files; 0 = per-file loop)] [--io-threads n]\n"
                         "  --alpha-file: one warp factor per line, in the order of the input files; files of a batch run with\n"
@@ -1268,6 +1277,9 @@ int main(int argc, char **argv)
         // (the reference CLI's defaults -- 64 Hz, cepstra with c0, deltas, CVN -- belong to the cepstral methods)
         o.ceps = 0, o.c0 = false, o.dyn = 0, o.norm = 0;
         if (!o.low_given) o.low = 0.f;
+    } else if (o.logmel_nfft > 0) {
+        std::fprintf(stderr, "--logmel-nfft goes with --method LOGMEL\n");
+        return 2;
     }
     if (o.resample_to != 0 && (o.resample_to < 1000 || o.resample_to > 768000)) {
         std::fprintf(stderr, "--resample-to takes a rate of 1000 .. 768000 Hz\n");
@@ -1281,6 +1293,11 @@ int main(int argc, char **argv)
         // sample rate from the first file (ASR_OCL.cpp:342-358), unless --resample-to names it
         const float sr = o.resample_to > 0 ? (float)o.resample_to : (float)read_wav(files[0]).sample_rate;
         if (o.high <= 0) o.high = sr / 2;
+        if (o.logmel_nfft > 0 && (long)(sr * o.window_ms * 1e-3) > (long)o.logmel_nfft) {
+            std::fprintf(stderr, "--window-size is %ld samples at %g Hz: longer than --logmel-nfft %d\n", (long)(sr * o.window_ms * 1e-3), (double)sr,
+                         o.logmel_nfft);
+            return 2;
+        }
         if (o.devices.empty()) o.devices.push_back(o.device);
         std::atomic<size_t> next{0};
         std::atomic<int> failures{0};

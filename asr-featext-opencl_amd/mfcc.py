@@ -89,6 +89,7 @@ EXPORTED_SYMBOLS = (
     "mfx_sessions_clear_online_norm", "mfx_host_online_norm",
     "mfx_host_slaney_mel_table", "mfx_host_stft_basis", "mfx_host_stft_frame_count",
     "mfx_host_stft_lds_bytes", "mfx_host_session_stft_step", "mfx_host_sess_stft_lds_bytes",
+    "mfx_host_stft_fft_tables", "mfx_host_stft_fft_lds_bytes",
     "mfx_batch_set_pitch", "mfx_batch_clear_pitch", "mfx_batch_pitch_read", "mfx_batch_pitch_device", "mfx_host_pitch",
     "mfx_batch_set_pitch_feats", "mfx_batch_clear_pitch_feats", "mfx_batch_pitch_feats_read", "mfx_batch_pitch_feats_device",
     "mfx_host_pitch_feats",
@@ -214,6 +215,8 @@ def load_library():
     L.mfx_host_stft_basis.argtypes = [i32, fp, fp]
     L.mfx_host_stft_frame_count.argtypes, L.mfx_host_stft_frame_count.restype = [i64, i32, i32], i64
     L.mfx_host_stft_lds_bytes.argtypes, L.mfx_host_stft_lds_bytes.restype = [i32, i32, i32, p32], i64
+    L.mfx_host_stft_fft_tables.argtypes = [i32, fp, fp]
+    L.mfx_host_stft_fft_lds_bytes.argtypes, L.mfx_host_stft_fft_lds_bytes.restype = [i32, i32, i32, p32], i64
     L.mfx_host_session_stft_step.argtypes, L.mfx_host_session_stft_step.restype = [i32, i32, p64, i64, i32, p32, p32], i32
     L.mfx_host_sess_stft_lds_bytes.argtypes, L.mfx_host_sess_stft_lds_bytes.restype = [i32, i32, i32, p32], i64
     L.mfx_batch_set_pitch.argtypes = [vp, i32, i32, i32, C.c_float, C.c_float, C.c_float, i32]
@@ -610,6 +613,30 @@ def host_stft_basis(window):
     return out
 
 
+def host_stft_fft_tables(dft_size):
+    """Tables of the FFT form of the STFT log-mel front end (dft_size 1024 or 2048) exactly as uploaded (host code, no GPU
+    needed): (twid [dft_size / 2] complex64, W_M^k of the half-length FFT; split [dft_size / 2 + 1] complex64, -i W_N^k of the
+    real split)."""
+    L = load_library()
+    n = int(dft_size)
+    twid, split = np.zeros(max(n, 0), np.float32), np.zeros(max(n, 0) + 2, np.float32)
+    fpt = C.POINTER(C.c_float)
+    rc = L.mfx_host_stft_fft_tables(n, twid.ctypes.data_as(fpt), split.ctypes.data_as(fpt))
+    if rc != 0:
+        raise MfxError(rc, "mfx_host_stft_fft_tables failed")
+    return twid.view(np.complex64), split.view(np.complex64)
+
+
+def host_stft_fft_lds_bytes(dft_size, shift, num_banks):
+    """(LDS bytes of a block of k_stft_fft_mel, frames per block) at the tile mfx_create takes for the shape.  An inspection
+    aid: the tiling is the kernel's private matter."""
+    r = C.c_int32(0)
+    n = int(load_library().mfx_host_stft_fft_lds_bytes(int(dft_size), int(shift), int(num_banks), C.byref(r)))
+    if n < 0:
+        raise MfxError(n, "mfx_host_stft_fft_lds_bytes failed")
+    return n, int(r.value)
+
+
 def stft_frame_count(samples, dft_size, shift):
     """Frames of an utterance of `samples` samples on an STFT log-mel handle: 0 up to dft_size / 2, else samples // shift."""
     n = int(load_library().mfx_host_stft_frame_count(int(samples), int(dft_size), int(shift)))
@@ -715,6 +742,9 @@ class MfccHip:
     ``method=METHOD_STFT_LOGMEL`` computes the log-mel spectrogram of the Whisper family (include/mfx.h): ``window_size`` is
     the DFT length, ``num_banks`` the output width, ``logmel_post`` one of ``LOGMEL_*``; set ``periodic_hann(window_size)``
     as the window.  Batch entries, and for ``LOGMEL_LOG10`` / ``LOGMEL_LN`` the session entries; no streaming methods.
+    DFT lengths: even, 32 .. 512 (an exact matrix DFT), and 1024 / 2048 (a float32 FFT; batch entries only, the session
+    entries raise ``MfxError`` (-8)).  A window shorter than the DFT (``win_length < n_fft``) is passed centred in
+    ``window_size`` taps with zeros around it, left pad ``(n_fft - win_length) // 2``, as ``torch.stft`` places it.
     """
 
     def __init__(self, input_buffer_size, window_size, shift, num_banks, sample_rate, low_freq, high_freq,

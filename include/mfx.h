@@ -111,7 +111,8 @@ enum { MFX_METHOD_MFCC = 0, MFX_METHOD_PLP = 1, MFX_METHOD_TRAPS = 3, MFX_METHOD
  * an exact-length DFT of centred, reflect-padded frames, Slaney mel bands, log10, and Whisper's clamp and map.  The value 4
  * is unassigned and stays refused, as 2 does.  The streaming entries (mfx_set_input ...) return MFX_ERR_STATE on such a handle;
  * the batch entries serve it, and the session entries do for logmel_post = MFX_LOGMEL_LOG10 or MFX_LOGMEL_LN (below, "Sessions").
- * Configuration (anything else: MFX_ERR_CONFIG).  window_size = N, the DFT length: even, 32 .. 512; fft_size 0 or N
+ * Configuration (anything else: MFX_ERR_CONFIG).  window_size = N, the DFT length: even, 32 .. 512, or 1024 / 2048 (the FFT
+ * form, below: every other length, odd or even, 514 included, stays refused); fft_size 0 or N
  * (mfx_fft_size returns N); shift = S in 1 .. N; num_banks = M in 1 .. 128, the output width; 0 <= low_freq < high_freq <=
  * sample_rate / 2; ceps_len = 0, want_c0 = 0, dyn = NONE, norm = NONE, channels 0 or 1.  lift_coef, the delta orders and
  * bug_compat are ignored.  The window is the caller's through mfx_set_window: the periodic Hann for Whisper.
@@ -141,6 +142,21 @@ enum { MFX_METHOD_MFCC = 0, MFX_METHOD_PLP = 1, MFX_METHOD_TRAPS = 3, MFX_METHOD
  *   Output.  Rows [T][M], frame-major, at out_rows[u] (Whisper's own layout is the transpose, [M][T]).
  * Rows are an exact function of the utterance's samples, the window and the configuration: they do not depend on the other
  * utterances, on the run, on buffer placement, or on whether the utterance starts at an odd sample.
+ * FFT form, N = 1024 or 2048 ("STFT log-mel, FFT form").  Frames, Samples, Power, Mel, Log, Post and Output are as
+ * above, S in 1 .. N, M in 1 .. 128; the reflection never leaves [0, n) for these N either.  In place of Basis and DFT:
+ *   Window.  z[j] = x[j] * w[j], one float32 product, w the caller's N floats from mfx_set_window -- which uploads the window
+ *     and the FFT tables and builds no basis.  A window shorter than the DFT (win_length L < n_fft = N) is passed centred in N
+ *     taps with zeros around it, left pad (N - L) div 2: torch.stft's rule.
+ *   DFT.     X[k] = sum_j z[j] e^(-2 pi i j k / N), k < K1, by a float32 FFT (half-length complex FFT and real split).  It is
+ *     NOT pinned to a summation order.  Its twiddle and split tables are built on the host in double and rounded once
+ *     (mfx_host_stft_fft_tables); the sequence of float32 operations applied to a frame depends on N alone -- not on the tile,
+ *     the wave, the frame's place in its block, or the batch; the factor 2 of the real split is removed by an exact 0.5.
+ *   Contract.  Rows are a deterministic function of the utterance's samples, the window and the configuration: the same bits
+ *     alone or in a batch, at an even or odd sample offset, on a second run, through the device or the host entry, at any
+ *     4-byte placement of d_out, and nothing is written outside [d_out, d_out + total_rows M).  Accuracy against float64 is the
+ *     project's bar (1e-4 of scale, 1e-5 relative L2), not a bit pin.
+ *   Entries.  The batch entries as listed below.  The streaming entries AND mfx_sessions_create answer MFX_ERR_STATE with a
+ *     message that names the batch entries: the carried-tail rule of the session entries stays limited to N <= 512.
  * Entries.  mfx_batch_frames, mfx_batch_plan and mfx_batch_plan_rates use the frame rule above; mfx_batch_run_device / _host,
  * mfx_batch_overlap, mfx_batch_set_transform and mfx_batch_set_vad work as on any handle; mfx_batch_set_alphas is refused with
  * MFX_ERR_CONFIG (there is no warped Slaney table) and mfx_set_alpha has no effect; the speaker list and the online
@@ -928,7 +944,9 @@ int64_t mfx_host_frame_count(int64_t samples, int32_t window_size, int32_t shift
 /* STFT log-mel (MFX_METHOD_STFT_LOGMEL) tables as uploaded, and its frame rule.  mfx_host_slaney_mel_table: weights
  * [num_banks][dft_size / 2 + 1], beg / len [num_banks] the non-zero span of every row (len 0: none).  mfx_host_stft_basis:
  * cos_sin [2][dft_size / 2 + 1][dft_size], the windowed cosine rows, then the negated windowed sine rows.  MFX_ERR_ARG outside
- * the limits of the method (dft_size even in 32 .. 512, num_banks 1 .. 128, shift 1 .. dft_size, the frequency rule). */
+ * the limits of the method (dft_size even in 32 .. 512, or 1024 / 2048; num_banks 1 .. 128, shift 1 .. dft_size, the frequency
+ * rule).  mfx_host_stft_basis describes the matrix form and refuses 1024 / 2048, as mfx_host_stft_lds_bytes,
+ * mfx_host_session_stft_step and mfx_host_sess_stft_lds_bytes do. */
 int mfx_host_slaney_mel_table(int32_t num_banks, int32_t dft_size, float sample_rate, float low_freq, float high_freq,
                               float *weights, int32_t *beg, int32_t *len);
 int mfx_host_stft_basis(int32_t dft_size, const float *window, float *cos_sin);
@@ -938,6 +956,12 @@ int64_t mfx_host_stft_frame_count(int64_t samples, int32_t dft_size, int32_t shi
  * method's limits, MFX_ERR_CONFIG if no tile fitted.  UNSTABLE, a test / inspection aid only: the tiling is the kernel's private
  * matter. */
 int64_t mfx_host_stft_lds_bytes(int32_t dft_size, int32_t shift, int32_t num_banks, int32_t *tile_rows);
+/* FFT form (dft_size 1024 or 2048, M = dft_size / 2).  mfx_host_stft_fft_tables: the tables as uploaded, twid [M] complex
+ * (re, im): W_M^k = e^(-2 pi i k / M); split [M + 1] complex: -i W_N^k.  mfx_host_stft_fft_lds_bytes: frames per block
+ * (*tile_rows: 16, 8 or 4) that k_stft_fft_mel takes for a shape, and ALL the LDS bytes such a block asks for; UNSTABLE, a test /
+ * inspection aid only, as mfx_host_stft_lds_bytes.  MFX_ERR_ARG outside the FFT form's limits. */
+int mfx_host_stft_fft_tables(int32_t dft_size, float *twid, float *split);
+int64_t mfx_host_stft_fft_lds_bytes(int32_t dft_size, int32_t shift, int32_t num_banks, int32_t *tile_rows);
 /* One push of one session of an STFT log-mel handle, exactly as the planner derives it (the delivery rule of the method's
  * comment).  state = {n, E} in / out: samples received, rows delivered (both 0 after a final push); returns E_new - E_old.
  * carry_in / carry_out: the samples the previous slot hands in and the current one keeps, [max(0, E S - N / 2), n) on either
