@@ -361,16 +361,11 @@ struct HandleDeleter {
     void operator()(mfx_handle *h) const { mfx_destroy(h); }
 };
 
-// DFT lengths of an STFT log-mel handle: even, 32 .. 512 (the matrix form), and 1024 / 2048 (the FFT form)
-bool stft_matrix_size(int N) { return N >= 32 && N <= 512 && !(N & 1); }
-bool stft_fft_size(int N) { return N == 1024 || N == 2048; }
-
 // the limits of an STFT log-mel handle (include/mfx.h): everything sized from N, S and M fits the kernel's LDS by them
 bool stft_config_ok(const mfx_config *cfg)
 {
     const int N = cfg->window_size;
-    if ((!stft_matrix_size(N) && !stft_fft_size(N)) || (cfg->fft_size != 0 && cfg->fft_size != N)) return false;
-    if (cfg->shift < 1 || cfg->shift > N || cfg->num_banks < 1 || cfg->num_banks > 128) return false;
+    if (!stft_shape_ok(N, cfg->shift, cfg->num_banks) || (cfg->fft_size != 0 && cfg->fft_size != N)) return false;
     if (!(cfg->low_freq >= 0.f) || !(cfg->low_freq < cfg->high_freq) || !(cfg->high_freq <= cfg->sample_rate / 2)) return false;
     if (cfg->ceps_len != 0 || cfg->want_c0 != 0 || cfg->dyn != MFX_DYN_NONE || cfg->norm != MFX_NORM_NONE || cfg->channels > 1) return false;
     if (cfg->logmel_post < MFX_LOGMEL_WHISPER || cfg->logmel_post > MFX_LOGMEL_LN) return false;
@@ -388,10 +383,10 @@ int create_stft(mfx_handle *h, bool planning, std::unique_ptr<mfx_handle, Handle
     if (h->input_window_limit <= 0) return MFX_ERR_CONFIG;
     h->cap_rows = h->window_limit + h->W / h->S + 4;
     h->spec_pitch = ((h->W2 / 2 + 1) + 3) & ~3;
-    h->stft_fft = stft_fft_size(h->W);
+    h->stft_form = stft_form(h->W);
     // (the matrix form: 16 frames fit for every shape inside the limits, 512 / 512 / 128 takes 74 KB then; the FFT form: 4 do,
     // 2048 / 2048 / 128 takes 104 KB then)
-    h->stft_R = h->stft_fft ? stft_fft_tile_rows(h->W, h->S, h->nb) : stft_tile_rows(h->W, h->S, h->nb);
+    h->stft_R = stft_tile_rows(h->W, h->S, h->nb);
     if (h->stft_R == 0) return MFX_ERR_CONFIG;
     if (!planning) {
         hipDeviceProp_t prop;
@@ -399,15 +394,9 @@ int create_stft(mfx_handle *h, bool planning, std::unique_ptr<mfx_handle, Handle
         if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return MFX_ERR_DEVICE;
         h->own_stream = true;
     }
-    const int K1 = h->W / 2 + 1;
-    std::vector<float> dense((size_t)h->nb * K1), w;
-    std::vector<int32_t> meta((size_t)3 * h->nb);
-    build_slaney_mel(h->nb, h->W, cfg.sample_rate, cfg.low_freq, cfg.high_freq, dense.data(), meta.data(), meta.data() + h->nb);
-    for (int m = 0; m < h->nb; ++m) {
-        meta[(size_t)2 * h->nb + m] = (int32_t)w.size();
-        w.insert(w.end(), dense.begin() + (size_t)m * K1 + meta[m], dense.begin() + (size_t)m * K1 + meta[m] + meta[(size_t)h->nb + m]);
-    }
-    if (w.empty()) w.push_back(0.f); // (every band narrower than a bin: keep the buffer non-null)
+    std::vector<float> w;
+    std::vector<int32_t> meta;
+    build_slaney_spans(h->nb, h->W, cfg.sample_rate, cfg.low_freq, cfg.high_freq, w, meta);
     if (h->upload(h->d_stft_melw, w) != hipSuccess || h->upload(h->d_stft_mel, meta) != hipSuccess ||
         h->alloc(h->st.d_stats, (size_t)3 * 2 * h->cols) != hipSuccess)
         return MFX_ERR_DEVICE;
@@ -790,7 +779,7 @@ int launch_front(mfx_handle *h, FrontParams &p, FrontKind kind, bool aligned, co
 extern "C" const char *mfx_dominant_kernel_name(const mfx_handle *h)
 {
     if (!h) return "";
-    if (h->stft) return h->stft_fft ? "k_stft_fft_mel" : "k_stft_mel";
+    if (h->stft) return h->stft_form == StftForm::Fft ? "k_stft_fft_mel" : "k_stft_mel";
     switch (batch_front(h)) { // names as rocprofv3 prints them
     case kFront512:
     case kSpec512: return "k_front512";
@@ -819,14 +808,8 @@ extern "C" int mfx_set_window(mfx_handle *h, const float *window)
     if (!window) return fail(h, MFX_ERR_ARG, "invalid argument");
     HIP_TRY(h, hipSetDevice(h->device));
     if (h->stft) { // the windowed basis as k_stft_mel streams it; the FFT form: the window and the FFT tables, no basis
-        std::vector<float> basis, ops;
-        if (h->stft_fft) {
-            build_stft_fft_operands(h->W, window, ops);
-        } else {
-            basis.resize((size_t)2 * (h->W / 2 + 1) * h->W);
-            build_stft_basis(h->W, window, basis.data());
-            build_stft_operands(basis.data(), h->W, kStftTB < (h->W / 2 + 16) / 16 ? kStftTB : (h->W / 2 + 16) / 16, ops);
-        }
+        std::vector<float> ops;
+        build_stft_form_operands(h->stft_form, h->W, window, ops);
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         if (h->batch.ov.stream2) HIP_TRY(h, hipStreamSynchronize(h->batch.ov.stream2));
         HIP_TRY(h, h->upload(h->d_stft_ops, ops));
@@ -1043,41 +1026,43 @@ extern "C" int64_t mfx_host_xform_operands(int32_t out_dim, int32_t in_dim, cons
     return n;
 }
 
+// ALL the LDS bytes of a block of the form's batch kernel at the tile mfx_create takes; a shape of another form is no argument
+static int64_t host_stft_lds_bytes(StftForm form, int32_t N, int32_t S, int32_t M, int32_t *tile_rows)
+{
+    if (stft_form(N) != form || !stft_shape_ok(N, S, M)) return MFX_ERR_ARG;
+    const int R = stft_tile_rows(N, S, M);
+    if (tile_rows) *tile_rows = R;
+    return R > 0 ? (int64_t)stft_lds_bytes(N, S, M, R) : MFX_ERR_CONFIG;
+}
+
 extern "C" int64_t mfx_host_stft_lds_bytes(int32_t dft_size, int32_t shift, int32_t num_banks, int32_t *tile_rows)
 {
-    if (!stft_matrix_size(dft_size) || shift < 1 || shift > dft_size || num_banks < 1 || num_banks > 128) return MFX_ERR_ARG;
-    const int R = stft_tile_rows(dft_size, shift, num_banks);
-    if (tile_rows) *tile_rows = R;
-    return R > 0 ? (int64_t)stft_lds_bytes(dft_size, shift, num_banks, R) : MFX_ERR_CONFIG;
+    return host_stft_lds_bytes(StftForm::Matrix, dft_size, shift, num_banks, tile_rows);
+}
+
+extern "C" int64_t mfx_host_stft_fft_lds_bytes(int32_t dft_size, int32_t shift, int32_t num_banks, int32_t *tile_rows)
+{
+    return host_stft_lds_bytes(StftForm::Fft, dft_size, shift, num_banks, tile_rows);
 }
 
 extern "C" int64_t mfx_host_stft_frame_count(int64_t samples, int32_t dft_size, int32_t shift)
 {
-    if (samples < 0 || (!stft_matrix_size(dft_size) && !stft_fft_size(dft_size)) || shift < 1 || shift > dft_size) return MFX_ERR_ARG;
+    if (samples < 0 || stft_form(dft_size) == StftForm::None || shift < 1 || shift > dft_size) return MFX_ERR_ARG;
     return stft_frame_count(samples, dft_size, shift);
-}
-
-// FFT form (dft_size 1024 / 2048): ALL the LDS bytes of a block of k_stft_fft_mel at the tile mfx_create takes
-extern "C" int64_t mfx_host_stft_fft_lds_bytes(int32_t dft_size, int32_t shift, int32_t num_banks, int32_t *tile_rows)
-{
-    if (!stft_fft_shape_ok(dft_size, shift, num_banks)) return MFX_ERR_ARG;
-    const int R = stft_fft_tile_rows(dft_size, shift, num_banks);
-    if (tile_rows) *tile_rows = R;
-    return R > 0 ? (int64_t)stft_fft_lds_bytes(dft_size, shift, num_banks, R) : MFX_ERR_CONFIG;
 }
 
 // FFT form: the tables as mfx_set_window uploads them behind the window: twid [dft_size / 2] complex, split [dft_size / 2 + 1]
 // complex
 extern "C" int mfx_host_stft_fft_tables(int32_t dft_size, float *twid, float *split)
 {
-    if (!stft_fft_size(dft_size) || !twid || !split) return MFX_ERR_ARG;
+    if (stft_form(dft_size) != StftForm::Fft || !twid || !split) return MFX_ERR_ARG;
     build_stft_fft_tables(dft_size, twid, split);
     return MFX_OK;
 }
 
 extern "C" int mfx_host_stft_basis(int32_t dft_size, const float *window, float *cos_sin)
 {
-    if (!stft_matrix_size(dft_size) || !window || !cos_sin) return MFX_ERR_ARG;
+    if (stft_form(dft_size) != StftForm::Matrix || !window || !cos_sin) return MFX_ERR_ARG;
     build_stft_basis(dft_size, window, cos_sin);
     return MFX_OK;
 }
@@ -1085,7 +1070,7 @@ extern "C" int mfx_host_stft_basis(int32_t dft_size, const float *window, float 
 extern "C" int mfx_host_slaney_mel_table(int32_t num_banks, int32_t dft_size, float sample_rate, float low_freq, float high_freq,
                                          float *weights, int32_t *beg, int32_t *len)
 {
-    if (num_banks < 1 || num_banks > 128 || (!stft_matrix_size(dft_size) && !stft_fft_size(dft_size)) || !weights || !beg || !len) return MFX_ERR_ARG;
+    if (num_banks < 1 || num_banks > 128 || stft_form(dft_size) == StftForm::None || !weights || !beg || !len) return MFX_ERR_ARG;
     if (!(sample_rate > 0.f) || !(low_freq >= 0.f) || !(low_freq < high_freq) || !(high_freq <= sample_rate / 2)) return MFX_ERR_ARG;
     build_slaney_mel(num_banks, dft_size, sample_rate, low_freq, high_freq, weights, beg, len);
     return MFX_OK;

@@ -164,20 +164,14 @@ int run_front(mfx_handle *h, FrontParams &p, const RunMode &m, int u0, int u1, i
         sp.chunks = B.d_stft_chunks.p + c0;
         sp.n_chunks = c1 - c0;
         sp.chunk_first = c0;
-        sp.N = h->W, sp.S = h->S, sp.M = h->nb;
-        sp.post = h->cfg.logmel_post;
         sp.tile_rows = h->stft_R;
-        sp.operands = h->d_stft_ops.p;
-        sp.mel_w = h->d_stft_melw.p;
-        sp.mel_beg = h->d_stft_mel.p, sp.mel_len = h->d_stft_mel.p + h->nb, sp.mel_off = h->d_stft_mel.p + 2 * h->nb;
-        sp.out = p.feat;
-        sp.out_pitch = p.feat_pitch;
+        sp.core = stft_core(h, p.feat, p.feat_pitch);
         sp.blk_max = B.d_stft_max.p;
         {
             ProfScope ps(h);
-            HIP_TRY(h, h->stft_fft ? launch_stft_fft(sp, h->stream) : launch_stft(sp, h->stream));
+            HIP_TRY(h, launch_stft(sp, h->stream));
         }
-        if (sp.post == MFX_LOGMEL_WHISPER) HIP_TRY(h, launch_stft_post(sp, h->stream));
+        if (sp.core.post == MFX_LOGMEL_WHISPER) HIP_TRY(h, launch_stft_post(sp, h->stream));
         return MFX_OK;
     }
     if (m.split_tail && B.ov.tail_pending[m.sb]) // tail of batch i-2 still reads this scratch buffer

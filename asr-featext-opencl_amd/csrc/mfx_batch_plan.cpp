@@ -255,12 +255,8 @@ int plan_batch(mfx_handle *h, int32_t n_utt, const int64_t *offsets, const int64
             c.n_frames = (int32_t)std::min<int64_t>(chunk_frames, T - t0);
             c.pad = 0;
             if (h->stft) {
-                StftChunk sc{};
-                sc.utt_off = offsets[u], sc.utt_len = lengths[u], sc.out_row = c.out_row;
-                sc.t0 = (int32_t)t0, sc.n_frames = c.n_frames;
-                sc.utt_chunk0 = (int32_t)(h->batch.h_chunks.size() - (size_t)(t0 / chunk_frames));
-                sc.utt_chunks = (int32_t)((T + chunk_frames - 1) / chunk_frames);
-                h->batch.h_stft_chunks.push_back(sc);
+                const int32_t first = (int32_t)(h->batch.h_chunks.size() - (size_t)(t0 / chunk_frames)), count = (int32_t)((T + chunk_frames - 1) / chunk_frames);
+                h->batch.h_stft_chunks.push_back(make_stft_chunk(offsets[u], lengths[u], c.out_row, (int32_t)t0, c.n_frames, first, count));
             }
             h->batch.h_chunks.push_back(c);
             h->batch.chunk_utt.push_back(u);

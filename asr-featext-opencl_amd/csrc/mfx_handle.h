@@ -573,8 +573,8 @@ struct mfx_handle {
     // LN) the session entries through k_sess_stft_mel.  W is the
     // DFT length N (W2 == W), nb the output width; none of the FFT / mel / DCT tables below exist on such a handle
     bool stft = false;
-    bool stft_fft = false;               // N = 1024 / 2048: k_stft_fft_mel stands where k_stft_mel does; batch entries only
-    int stft_R = 0;                      // frames per block of k_stft_mel (stft_tile_rows) or k_stft_fft_mel (stft_fft_tile_rows)
+    mfx::StftForm stft_form = mfx::StftForm::None; // Fft (N = 1024 / 2048): k_stft_fft_mel stands where k_stft_mel does; batch entries only
+    int stft_R = 0;                      // frames per block of the form's batch kernel (stft_tile_rows)
     DevBuf<float> d_stft_ops, d_stft_melw; // basis operands -- FFT form: window and FFT tables -- (mfx_set_window builds them); the mel
                                          // rows' spans back to back
     DevBuf<int32_t> d_stft_mel;          // [3][nb]: beg, len, first weight of every row
@@ -803,6 +803,12 @@ int batch_out_width(const mfx_handle *h);
 inline int64_t utt_frame_count(const mfx_handle *h, int64_t samples)
 {
     return h->stft ? mfx::stft_frame_count(samples, h->W, h->S) : mfx::frame_count(samples, h->W, h->S);
+}
+// what every STFT log-mel kernel takes from the handle: shape, post mode, operands and the mel spans, for rows to `out`
+inline mfx::StftCore stft_core(const mfx_handle *h, float *out, int pitch)
+{
+    const int32_t *meta = h->d_stft_mel.p; // [3][nb]
+    return mfx::StftCore{h->W, h->S, h->nb, h->cfg.logmel_post, h->d_stft_ops.p, h->d_stft_melw.p, meta, meta + h->nb, meta + 2 * h->nb, out, pitch};
 }
 // normalised columns of a speaker list and of the online normaliser: the whole row after the deltas, else the statics
 inline int spk_wn(const mfx_handle *h) { return h->cfg.norm_after_dyn ? h->width : h->cols; }

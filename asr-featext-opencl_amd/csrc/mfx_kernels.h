@@ -24,6 +24,7 @@
 //                            the clamp by the utterance's maximum and the map (no reference analogue: a neural recogniser's input)
 //   stft_fft_mel             the same front end at DFT lengths 1024 / 2048: window product, a float32 FFT per wave and frame (half-length
 //                            complex Stockham FFT in LDS + real split), then stft_mel's power, mel and log; stft_post follows unchanged
+//                            (one launcher surface and one block tail for both; stft_form(N) of mfx_tables.h says which a length gets)
 //   sess_stft_mel            the same front end over the frames one push of the session entries completes, groups of 16 frames of
 //                            different sessions sharing a block's pass over the basis (no reference analogue)
 //   delta                    delta.cl kernelDelta x2 + the staging copies of mfccopencl.cpp:360-387
@@ -572,40 +573,42 @@ struct StftChunk {
     int32_t utt_chunks;  // (both count from the plan's first chunk)
 };
 
-constexpr int kStftTB = 13;    // bin tiles (16 bins: a cos and a sin accumulator tile) a wave carries through one pass over the taps
+// (utt_chunk0 / utt_chunks 0 where no k_stft_post follows: the session entries)
+inline StftChunk make_stft_chunk(int64_t utt_off, int64_t utt_len, int64_t out_row, int32_t t0, int32_t n_frames, int32_t chunk0 = 0, int32_t chunks = 0)
+{
+    return StftChunk{utt_off, utt_len, out_row, t0, n_frames, chunk0, chunks};
+}
+
 constexpr int kStftKSteps = 2; // steps of 4 taps per LDS buffer of basis operands
 
+// what every kernel of the method takes: the shape, the post mode, the DFT operands of the handle's form, the mel spans, the rows
+struct StftCore {
+    int32_t N, S, M;            // DFT length, hop, mel bands
+    int32_t post;               // MFX_LOGMEL_*
+    const float *operands;      // matrix form: [pass][step][tile of the pass][64] (build_stft_operands); FFT form: the window, the
+                                // twiddles and the split table back to back (build_stft_fft_operands: 3 N + 2 floats)
+    const float *mel_w;         // the rows' non-zero spans back to back
+    const int32_t *mel_beg, *mel_len, *mel_off; // [M] first bin, bins, first weight of every row
+    float *out;
+    int32_t out_pitch;
+};
+
+// The batch front end of either form (stft_form(N)): k_stft_mel at tile_rows 64, 32 or 16, or k_stft_fft_mel (mfx_stft_fft.hip;
+// DESIGN.md, "STFT log-mel, FFT form") at 16, 8 or 4; k_stft_post follows either unchanged.
 struct StftParams {
     const int16_t *pcm;
     const StftChunk *chunks;    // the launch's chunks (blockIdx.x)
     int32_t n_chunks;
     int32_t chunk_first;        // index of chunks[0] in the plan: its slot in blk_max
-    int32_t N, S, M;            // DFT length, hop, mel bands
-    int32_t post;               // MFX_LOGMEL_*
-    int32_t tile_rows;          // frames per block the chunks were cut for (64, 32 or 16)
-    const float *operands;      // [pass][step][tile of the pass][64] (build_stft_operands)
-    const float *mel_w;         // the rows' non-zero spans back to back
-    const int32_t *mel_beg, *mel_len, *mel_off; // [M] first bin, bins, first weight of every row
-    float *out;
-    int32_t out_pitch;
+    int32_t tile_rows;          // frames per block the chunks were cut for
+    StftCore core;
     float *blk_max;             // [chunks of the plan] the largest log value of every block (WHISPER)
 };
-// ALL the LDS a block of k_stft_mel asks for at tile_rows frames per block: the kernel declares no static LDS beside it
+// ALL the LDS a block of the form's kernel asks for at tile_rows frames per block: the kernels declare no static LDS beside it
 size_t stft_lds_bytes(int N, int S, int M, int tile_rows);
-int stft_tile_rows(int N, int S, int M); // frames per block: the largest of 64 / 32 / 16 whose LDS fits, 0: none
-hipError_t launch_stft(const StftParams &p, hipStream_t stream);      // k_stft_mel
+int stft_tile_rows(int N, int S, int M); // frames per block: the largest of the form's three tiles whose LDS fits, 0: none
+hipError_t launch_stft(const StftParams &p, hipStream_t stream);      // k_stft_mel or k_stft_fft_mel, by the form of p.core.N
 hipError_t launch_stft_post(const StftParams &p, hipStream_t stream); // k_stft_post (WHISPER: clamp and map, in place)
-
-// k_stft_fft_mel (mfx_stft_fft.hip; DESIGN.md, "STFT log-mel, FFT form"): the same front end at N = 1024 / 2048, the DFT as a
-// float32 FFT.  It takes the chunks, the mel table and the slots of k_stft_mel through StftParams; `operands` is then the
-// window, the twiddles and the split table back to back (build_stft_fft_operands: 3 N + 2 floats), tile_rows 16, 8 or 4, and
-// k_stft_post follows unchanged.
-bool stft_fft_shape_ok(int N, int S, int M);
-bool stft_fft_params_ok(const StftParams &p); // what launch_stft_fft takes (launch_stft_post: either form's parameters)
-// ALL the LDS a block of k_stft_fft_mel asks for at tile_rows frames per block: the kernel declares no static LDS beside it
-size_t stft_fft_lds_bytes(int N, int S, int M, int tile_rows);
-int stft_fft_tile_rows(int N, int S, int M); // frames per block: the largest of 16 / 8 / 4 whose LDS fits, 0: none
-hipError_t launch_stft_fft(const StftParams &p, hipStream_t stream);
 
 // k_sess_stft_mel (mfx_stft.hip; DESIGN.md, "Session log-mel"): the rows one push of the session entries delivers on an STFT
 // log-mel handle.  The work list: groups of at most 16 consecutive frames of ONE session (StftChunk: utt_off is the element of
@@ -618,16 +621,10 @@ struct SessStftParams {
     const StftChunk *groups;
     int32_t n_groups;
     int32_t G;                  // groups per block the lists were sized for: sess_stft_groups, or the launcher refuses
-    int32_t N, S, M;            // DFT length, hop, mel bands
-    int32_t post;               // MFX_LOGMEL_LOG10 or MFX_LOGMEL_LN
-    const float *operands;      // as StftParams
-    const float *mel_w;
-    const int32_t *mel_beg, *mel_len, *mel_off;
-    float *out;
-    int32_t out_pitch;
+    StftCore core;
 };
 // ALL the LDS a block of k_sess_stft_mel asks for at G groups per block; the G the launcher takes: the largest of 4 / 2 / 1
-// whose LDS fits 160 KB (0: the shape is outside the method's limits)
+// whose LDS fits 160 KB (0: the shape is outside the limits of the matrix form)
 size_t sess_stft_lds_bytes(int N, int S, int M, int G);
 int sess_stft_groups(int N, int S, int M);
 hipError_t launch_sess_stft(const SessStftParams &p, hipStream_t stream);

@@ -75,7 +75,7 @@ extern "C" int mfx_sessions_create(mfx_handle *h, int32_t n_sessions, int32_t ma
     MFX_DEVICE_ENTRY(h);
     if (h->traps)
         return fail(h, MFX_ERR_STATE, "the session entries do not serve TRAPS handles (their look-ahead is (L - 1) / 2 frames, not D)");
-    if (h->stft_fft)
+    if (h->stft_form == StftForm::Fft)
         return fail(h, MFX_ERR_STATE,
                     "the session entries do not serve STFT log-mel handles of DFT length 1024 / 2048 (the carried-tail rule stops at 512): "
                     "use the batch entries (mfx_batch_plan + mfx_batch_run_device / mfx_batch_run_host)");
@@ -652,7 +652,7 @@ void plan_stft_work(mfx_handle *h)
     const int n = (int)ps.pieces.size();
     auto chunk = [&](const Piece &pc, int r0, int rows) {
         const int64_t E_old = ss.live[pc.id].E, n_new = ss.live[pc.id].n + pc.len;
-        ps.stft.push_back(StftChunk{pc.stft_pcm, n_new, pc.stft_row + r0, (int32_t)(E_old + r0), rows, 0, 0});
+        ps.stft.push_back(make_stft_chunk(pc.stft_pcm, n_new, pc.stft_row + r0, (int32_t)(E_old + r0), rows));
     };
     if (stft_plain(h)) {
         for (const Piece &pc : ps.pieces)
@@ -828,16 +828,13 @@ int run_stft(mfx_handle *h, const PushRun &r)
     const SessState &ss = h->sess;
     const Push &ps = ss.push;
     if (ps.stft.empty()) return MFX_OK;
-    const int nb = h->nb;
     if (stft_plain(h)) {
         if (ss.d_stft_max.n < ps.stft.size()) return fail(h, MFX_ERR_STATE, "session chunks outgrew their buffer");
         StftParams sp{};
         sp.pcm = ss.d_pcm.p;
         sp.chunks = r.up.stft, sp.n_chunks = (int32_t)ps.stft.size(), sp.chunk_first = 0;
-        sp.N = h->W, sp.S = h->S, sp.M = nb, sp.post = h->cfg.logmel_post, sp.tile_rows = h->stft_R;
-        sp.operands = h->d_stft_ops.p, sp.mel_w = h->d_stft_melw.p;
-        sp.mel_beg = h->d_stft_mel.p, sp.mel_len = h->d_stft_mel.p + nb, sp.mel_off = h->d_stft_mel.p + 2 * nb;
-        sp.out = r.d_rows, sp.out_pitch = h->width;
+        sp.tile_rows = h->stft_R;
+        sp.core = stft_core(h, r.d_rows, h->width);
         sp.blk_max = ss.d_stft_max.p;
         HIP_TRY(h, launch_stft(sp, h->stream));
         return MFX_OK;
@@ -845,10 +842,7 @@ int run_stft(mfx_handle *h, const PushRun &r)
     SessStftParams sp{};
     sp.pcm = ss.d_pcm.p, sp.pcm_elems = (int64_t)2 * ss.n * ss.pcm_stride;
     sp.groups = r.up.stft, sp.n_groups = (int32_t)ps.stft.size(), sp.G = ss.stft_G;
-    sp.N = h->W, sp.S = h->S, sp.M = nb, sp.post = h->cfg.logmel_post;
-    sp.operands = h->d_stft_ops.p, sp.mel_w = h->d_stft_melw.p;
-    sp.mel_beg = h->d_stft_mel.p, sp.mel_len = h->d_stft_mel.p + nb, sp.mel_off = h->d_stft_mel.p + 2 * nb;
-    sp.out = r.d_rows, sp.out_pitch = h->width;
+    sp.core = stft_core(h, r.d_rows, h->width);
     HIP_TRY(h, launch_sess_stft(sp, h->stream));
     return MFX_OK;
 }
@@ -1057,7 +1051,7 @@ extern "C" int32_t mfx_host_session_stft_step(int32_t dft_size, int32_t shift, i
 
 extern "C" int64_t mfx_host_sess_stft_lds_bytes(int32_t dft_size, int32_t shift, int32_t num_banks, int32_t *groups)
 {
-    if (dft_size < 32 || dft_size > 512 || (dft_size & 1) || shift < 1 || shift > dft_size || num_banks < 1 || num_banks > 128) return MFX_ERR_ARG;
+    if (stft_form(dft_size) != StftForm::Matrix || !stft_shape_ok(dft_size, shift, num_banks)) return MFX_ERR_ARG;
     const int G = groups && *groups > 0 ? *groups : sess_stft_groups(dft_size, shift, num_banks);
     if (G != 1 && G != 2 && G != 4) return MFX_ERR_ARG;
     if (groups) *groups = G;

@@ -41,20 +41,11 @@ namespace mfx {
 
 namespace {
 
-__host__ __device__ inline int stft_bin_tiles(int N) { return (stft_bins(N) + 15) >> 4; }
 __host__ __device__ inline int stft_steps(int N) { return (N + 3) >> 2; }
-// bin tiles of a pass: as many as the DFT has, at most kStftTB (the operand table is laid out for it)
-__host__ __device__ inline int stft_pass_tiles(int N) { return stft_bin_tiles(N) < kStftTB ? stft_bin_tiles(N) : kStftTB; }
 // floats of one LDS operand buffer
 __host__ __device__ inline int stft_buf_floats(int N) { return kStftKSteps * 2 * stft_pass_tiles(N) * 64; }
-// floats of the staged span (then 4 words of zeros for the padded taps of the last frame) -- the finished rows [R][M] are
-// assembled in the same words once the DFT is done
-__host__ __device__ inline int stft_span_floats(int N, int S, int R) { return (R - 1) * S + N + 4; }
-__host__ __device__ inline int stft_xo_floats(int N, int S, int M, int R)
-{
-    const int a = stft_span_floats(N, S, R), b = R * M;
-    return ((a > b ? a : b) + 3) & ~3;
-}
+constexpr int kStftPad = 4; // words of zeros behind a staged span: the padded taps of its last frame
+__host__ __device__ inline int stft_span_floats(int N, int S, int R) { return (R - 1) * S + N + kStftPad; } // the span and its pad
 constexpr int kStftPf = (kStftKSteps * 2 * kStftTB * 16 + 255) / 256; // 16-byte words a thread carries for the next chunk
 
 // The DFT and the power of a wave's 16 frames, shared by k_stft_mel and k_sess_stft_mel: every pass over the taps, the basis
@@ -147,14 +138,13 @@ __global__ void __launch_bounds__(256) k_stft_mel(StftParams p)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const StftChunk ck = p.chunks[blockIdx.x];
-    const int R = p.tile_rows, N = p.N, S = p.S, M = p.M;
+    const int R = p.tile_rows, N = p.core.N, S = p.core.S, M = p.core.M;
     const int rows = ck.n_frames;
     const int KP = stft_p_pitch(N);
     const int tid = threadIdx.x;
     float *s_b = smem;
     float *s_x = s_b + 2 * stft_buf_floats(N);
-    float *s_P = s_x + stft_xo_floats(N, S, M, R);
-    float *s_out = s_x;
+    float *s_P = s_x + stft_xo_floats(N, S, M, R, kStftPad);
     float *s_red = s_P + R * KP; // the waves' maxima
 
     {   // the span of frames t0 .. t0 + rows - 1, reflected at the ends of the utterance; zeros behind it
@@ -166,16 +156,10 @@ __global__ void __launch_bounds__(256) k_stft_mel(StftParams p)
     const int li = lane & 15, lk = lane >> 4;
     const bool busy = 16 * g < rows && 16 * g < R;
     const float *za = s_x + (16 * g + li) * S + lk; // lane (li, lk) feeds frame 16 g + li, tap 4 s + lk
-    stft_dft_power(p.operands, N, s_b, za, busy, rows - 16 * g, s_P + 16 * g * KP, tid);
+    stft_dft_power(p.core.operands, N, s_b, za, busy, rows - 16 * g, s_P + 16 * g * KP, tid);
     __syncthreads();
 
-    float mx = stft_mel_log(p, s_P, KP, rows, s_out, tid);
-    mx = wave_max(mx);
-    if (lane == 0) s_red[g] = mx;
-    __syncthreads();
-    if (tid == 0) p.blk_max[p.chunk_first + blockIdx.x] = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
-
-    tile_store_rows(s_out, M, rows, p.out, ck.out_row, p.out_pitch, tid);
+    stft_finish_block(p.core, s_P, KP, rows, s_x, s_red, p.blk_max + (p.chunk_first + blockIdx.x), ck, tid);
 }
 
 __global__ void __launch_bounds__(256) k_stft_post(StftParams p)
@@ -189,12 +173,12 @@ __global__ void __launch_bounds__(256) k_stft_post(StftParams p)
     if ((tid & 63) == 0) s_red[tid >> 6] = mx;
     __syncthreads();
     const float lo = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3])) - 8.0f;
-    const int M = p.M, n = ck.n_frames * M;
+    const int M = p.core.M, n = ck.n_frames * M;
     const uint32_t magic = div_magic(M);
-    float *obase = p.out + ck.out_row * (int64_t)p.out_pitch;
+    float *obase = p.core.out + ck.out_row * (int64_t)p.core.out_pitch;
     for (int i = tid; i < n; i += 256) {
         const int t = div_small(i, M, magic);
-        float *o = obase + t * (int64_t)p.out_pitch + (i - t * M);
+        float *o = obase + t * (int64_t)p.core.out_pitch + (i - t * M);
         *o = (fmaxf(*o, lo) + 4.0f) * 0.25f;
     }
 }
@@ -208,9 +192,9 @@ __global__ void __launch_bounds__(256) k_stft_post(StftParams p)
 __global__ void __launch_bounds__(256) k_sess_stft_mel(SessStftParams p)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int G = p.G, N = p.N, S = p.S, M = p.M;
+    const int G = p.G, N = p.core.N, S = p.core.S, M = p.core.M;
     const int g0 = blockIdx.x * G, ng = min(G, p.n_groups - g0);
-    const int KP = stft_p_pitch(N), xo = stft_xo_floats(N, S, M, 16);
+    const int KP = stft_p_pitch(N), xo = stft_xo_floats(N, S, M, 16, kStftPad);
     const int tid = threadIdx.x;
     float *s_b = smem;
     float *s_x = s_b + 2 * stft_buf_floats(N);
@@ -228,48 +212,60 @@ __global__ void __launch_bounds__(256) k_sess_stft_mel(SessStftParams p)
     const bool busy = wave < ng;
     const int g = busy ? wave : 0;
     const float *za = s_x + g * xo + li * S + lk; // lane (li, lk) feeds frame li of the wave's group, tap 4 s + lk
-    stft_dft_power(p.operands, N, s_b, za, busy, busy ? min(p.groups[g0 + g].n_frames, 16) : 0, s_P + 16 * g * KP, tid);
+    stft_dft_power(p.core.operands, N, s_b, za, busy, busy ? min(p.groups[g0 + g].n_frames, 16) : 0, s_P + 16 * g * KP, tid);
     __syncthreads();
 
-    for (int q = 0; q < ng; ++q) stft_mel_log(p, s_P + 16 * q * KP, KP, min(p.groups[g0 + q].n_frames, 16), s_x + q * xo, tid);
+    for (int q = 0; q < ng; ++q) stft_mel_log(p.core, s_P + 16 * q * KP, KP, min(p.groups[g0 + q].n_frames, 16), s_x + q * xo, tid);
     __syncthreads();
     for (int q = 0; q < ng; ++q) {
         const StftChunk ck = p.groups[g0 + q];
-        tile_store_rows(s_x + q * xo, M, min(ck.n_frames, 16), p.out, ck.out_row, p.out_pitch, tid);
+        tile_store_rows(s_x + q * xo, M, min(ck.n_frames, 16), p.core.out, ck.out_row, p.core.out_pitch, tid);
     }
 }
 
-bool stft_shape_ok(int N, int S, int M) { return N >= 32 && N <= 512 && !(N & 1) && S >= 1 && S <= N && M >= 1 && M <= 128; }
-
-bool stft_params_ok(const StftParams &p)
+// a core any kernel of the method can run on: a shape inside the limits, every table and the rows in place
+bool stft_core_ok(const StftCore &c)
 {
-    return p.N >= 32 && p.N <= 512 && !(p.N & 1) && p.S >= 1 && p.S <= p.N && p.M >= 1 && p.M <= 128 && p.out_pitch >= p.M && p.pcm && p.chunks &&
-           p.operands && p.mel_w && p.mel_beg && p.mel_len && p.mel_off && p.out && p.blk_max &&
-           (p.tile_rows == 64 || p.tile_rows == 32 || p.tile_rows == 16) && stft_lds_bytes(p.N, p.S, p.M, p.tile_rows) <= kLdsMax;
+    return stft_shape_ok(c.N, c.S, c.M) && c.out_pitch >= c.M && c.operands && c.mel_w && c.mel_beg && c.mel_len && c.mel_off && c.out;
+}
+
+size_t stft_matrix_lds_bytes(int N, int S, int M, int tile_rows)
+{
+    const size_t f = (size_t)2 * stft_buf_floats(N) + (size_t)stft_xo_floats(N, S, M, tile_rows, kStftPad) +
+                     (size_t)tile_rows * stft_p_pitch(N) + 4 /* s_red */;
+    return f * sizeof(float);
 }
 
 } // namespace
 
 size_t stft_lds_bytes(int N, int S, int M, int tile_rows)
 {
-    const size_t f = (size_t)2 * stft_buf_floats(N) + (size_t)stft_xo_floats(N, S, M, tile_rows) + (size_t)tile_rows * stft_p_pitch(N) +
-                     4 /* s_red */;
-    return f * sizeof(float);
+    return stft_form(N) == StftForm::Fft ? stft_fft_lds_bytes(N, S, M, tile_rows) : stft_matrix_lds_bytes(N, S, M, tile_rows);
 }
+
+static int stft_top_tile(int N) { return stft_form(N) == StftForm::Fft ? 16 : 64; } // the largest of the form's three tiles: 64 / 32 / 16, 16 / 8 / 4
 
 int stft_tile_rows(int N, int S, int M)
 {
-    for (int r : {64, 32, 16})
+    if (!stft_shape_ok(N, S, M)) return 0;
+    for (int r = stft_top_tile(N); r >= stft_top_tile(N) / 4; r /= 2)
         if (stft_lds_bytes(N, S, M, r) <= kLdsMax) return r;
     return 0;
+}
+
+static bool stft_params_ok(const StftParams &p) // what launch_stft and launch_stft_post take
+{
+    const int top = stft_top_tile(p.core.N), R = p.tile_rows;
+    return stft_core_ok(p.core) && p.pcm && p.chunks && p.blk_max && (R == top || R == top / 2 || R == top / 4) &&
+           stft_lds_bytes(p.core.N, p.core.S, p.core.M, R) <= kLdsMax;
 }
 
 hipError_t launch_stft(const StftParams &p, hipStream_t stream)
 {
     if (p.n_chunks <= 0) return hipSuccess;
     if (!stft_params_ok(p)) return hipErrorInvalidValue;
-    const size_t lds = stft_lds_bytes(p.N, p.S, p.M, p.tile_rows);
-    const void *fn = (const void *)k_stft_mel;
+    const size_t lds = stft_lds_bytes(p.core.N, p.core.S, p.core.M, p.tile_rows);
+    const void *fn = stft_form(p.core.N) == StftForm::Fft ? stft_fft_kernel() : (const void *)k_stft_mel;
     if (hipError_t e = allow_dynamic_lds(fn, lds); e != hipSuccess) return e;
     StftParams q = p;
     return launch_kernel(fn, dim3(p.n_chunks), dim3(256), lds, stream, q);
@@ -277,13 +273,13 @@ hipError_t launch_stft(const StftParams &p, hipStream_t stream)
 
 size_t sess_stft_lds_bytes(int N, int S, int M, int G)
 {
-    const size_t f = (size_t)2 * stft_buf_floats(N) + (size_t)G * stft_xo_floats(N, S, M, 16) + (size_t)16 * G * stft_p_pitch(N);
+    const size_t f = (size_t)2 * stft_buf_floats(N) + (size_t)G * stft_xo_floats(N, S, M, 16, kStftPad) + (size_t)16 * G * stft_p_pitch(N);
     return f * sizeof(float);
 }
 
 int sess_stft_groups(int N, int S, int M)
 {
-    if (!stft_shape_ok(N, S, M)) return 0;
+    if (stft_form(N) != StftForm::Matrix || !stft_shape_ok(N, S, M)) return 0;
     for (int g : {4, 2, 1})
         if (sess_stft_lds_bytes(N, S, M, g) <= kLdsMax) return g;
     return 0;
@@ -292,12 +288,10 @@ int sess_stft_groups(int N, int S, int M)
 hipError_t launch_sess_stft(const SessStftParams &p, hipStream_t stream)
 {
     if (p.n_groups <= 0) return hipSuccess;
-    if (!stft_shape_ok(p.N, p.S, p.M) || p.out_pitch < p.M || !p.pcm || p.pcm_elems <= 0 || !p.groups || !p.operands || !p.mel_w || !p.mel_beg ||
-        !p.mel_len || !p.mel_off || !p.out)
-        return hipErrorInvalidValue;
-    const int G = sess_stft_groups(p.N, p.S, p.M);
-    if (G == 0 || p.G != G) return hipErrorInvalidValue; // (the caller sized its lists for another packing)
-    const size_t lds = sess_stft_lds_bytes(p.N, p.S, p.M, G);
+    if (!stft_core_ok(p.core) || !p.pcm || p.pcm_elems <= 0 || !p.groups) return hipErrorInvalidValue;
+    const int G = sess_stft_groups(p.core.N, p.core.S, p.core.M);
+    if (G == 0 || p.G != G) return hipErrorInvalidValue; // (another form, or the caller sized its lists for another packing)
+    const size_t lds = sess_stft_lds_bytes(p.core.N, p.core.S, p.core.M, G);
     const void *fn = (const void *)k_sess_stft_mel;
     if (hipError_t e = allow_dynamic_lds(fn, lds); e != hipSuccess) return e;
     SessStftParams q = p;
@@ -307,7 +301,7 @@ hipError_t launch_sess_stft(const SessStftParams &p, hipStream_t stream)
 hipError_t launch_stft_post(const StftParams &p, hipStream_t stream)
 {
     if (p.n_chunks <= 0) return hipSuccess;
-    if (!stft_params_ok(p) && !stft_fft_params_ok(p)) return hipErrorInvalidValue; // (the chunks of either front end)
+    if (!stft_params_ok(p)) return hipErrorInvalidValue;
     StftParams q = p;
     return launch_kernel((const void *)k_stft_post, dim3(p.n_chunks), dim3(256), 0, stream, q);
 }

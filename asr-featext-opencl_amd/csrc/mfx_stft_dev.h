@@ -2,8 +2,10 @@
 // mfx_stft_fft.hip: k_stft_fft_mel, the FFT form):
 //   stft_bins, stft_p_pitch   bins of a DFT of N points; the row pitch of the power rows in LDS
 //   stft_stage_span           the PCM span of a run of centred frames into LDS: reflected, converted, scaled
+//   stft_xo_floats            the overlay both block kernels stage their span in and assemble their rows in
 //   stft_mel_log              the Slaney mel chains and the log over power rows in LDS, one (frame, band) per thread
 //   wave_max                  the largest value of a wave's lanes
+//   stft_finish_block         the tail of a block of the batch kernels: mel and log, the block's maximum, the rows out
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,10 +16,23 @@
 #include "mfx_tile_dev.h"
 
 namespace mfx {
+
+// the FFT form's side of launch_stft / stft_lds_bytes (mfx_stft_fft.hip): its block's LDS, and k_stft_fft_mel
+size_t stft_fft_lds_bytes(int N, int S, int M, int tile_rows);
+const void *stft_fft_kernel();
+
 namespace {
 
 __host__ __device__ inline int stft_bins(int N) { return N / 2 + 1; }
 __host__ __device__ inline int stft_p_pitch(int N) { return stft_bins(N) | 1; } // odd: a column of P spreads over the banks
+
+// floats of the staged span of R frames and `pad` words behind it (the matrix form: 4 words of zeros for the padded taps of
+// the last frame; the FFT form: none) -- the finished rows [R][M] are assembled in the same words once the DFT is done
+__host__ __device__ inline int stft_xo_floats(int N, int S, int M, int R, int pad)
+{
+    const int a = (R - 1) * S + N + pad, b = R * M;
+    return ((a > b ? a : b) + 3) & ~3;
+}
 
 __device__ __forceinline__ float wave_max(float v)
 {
@@ -46,9 +61,8 @@ __device__ __forceinline__ void stft_stage_span(const int16_t *pcm, int64_t off,
 }
 
 // The mel chains and the log of `rows` frames whose power lies in s_P [rows][KP], one (frame, band) per thread and trip, to
-// s_out [rows][M]; returns the thread's largest log value.  T: the parameters of any of the kernels.
-template <class T>
-__device__ __forceinline__ float stft_mel_log(const T &p, const float *s_P, int KP, int rows, float *s_out, int tid)
+// s_out [rows][M]; returns the thread's largest log value.
+__device__ __forceinline__ float stft_mel_log(const StftCore &p, const float *s_P, int KP, int rows, float *s_out, int tid)
 {
     float mx = -INFINITY;
     const int M = p.M, n = rows * M;
@@ -71,6 +85,21 @@ __device__ __forceinline__ float stft_mel_log(const T &p, const float *s_P, int 
         mx = fmaxf(mx, L);
     }
     return mx;
+}
+
+// The tail of a block of k_stft_mel / k_stft_fft_mel once the power of its `rows` frames lies in s_P (every thread calls this,
+// behind a block barrier): mel and log into s_out, the block's largest log value into *blk_max_slot through s_red [4], the rows
+// to the chunk's place in core.out.
+__device__ __forceinline__ void stft_finish_block(const StftCore &core, const float *s_P, int KP, int rows, float *s_out, float *s_red,
+                                                  float *blk_max_slot, const StftChunk &ck, int tid)
+{
+    float mx = stft_mel_log(core, s_P, KP, rows, s_out, tid);
+    mx = wave_max(mx);
+    if ((tid & 63) == 0) s_red[tid >> 6] = mx;
+    __syncthreads();
+    if (tid == 0) *blk_max_slot = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
+
+    tile_store_rows(s_out, core.M, rows, core.out, ck.out_row, core.out_pitch, tid);
 }
 
 } // namespace

@@ -24,20 +24,12 @@
 #include <hip/hip_runtime.h>
 
 #include "mfx_dev.h"
-#include "mfx_launch.h"
 #include "mfx_stft_dev.h"
 #include "mfx_tile_dev.h"
 
 namespace mfx {
 
 namespace {
-
-// floats of the staged span; the finished rows [R][M] are assembled in the same words once the DFT is done
-__host__ __device__ inline int stft_fft_xo_floats(int N, int S, int M, int R)
-{
-    const int a = (R - 1) * S + N, b = R * M;
-    return ((a > b ? a : b) + 3) & ~3;
-}
 
 // One radix-4 Stockham stage over the M points of the wave's buffer, in place: sub-transform length LEN before the stage,
 // stride ST = M / LEN; every lane reads the inputs of its M / 256 butterflies, the wave synchronises, then it writes.
@@ -115,25 +107,24 @@ __device__ __forceinline__ void stft_fft_block(const StftParams &p, float *smem)
 {
     constexpr int N = 2 * M, KP = (M + 1) | 1;
     const StftChunk ck = p.chunks[blockIdx.x];
-    const int R = p.tile_rows, S = p.S, nb = p.M;
+    const int R = p.tile_rows, S = p.core.S, nb = p.core.M;
     const int rows = ck.n_frames;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     float *s_x = smem;
-    float *s_w = s_x + stft_fft_xo_floats(N, S, nb, R);
+    float *s_w = s_x + stft_xo_floats(N, S, nb, R, 0);
     const float2 *s_tw = (const float2 *)(s_w + N);
     float2 *s_f = (float2 *)(s_w + 2 * N) + wave * M;
     float *s_P = s_w + 6 * N;
     float *s_red = s_P + R * KP; // the waves' maxima
-    float *s_out = s_x;
 
     {   // the span of frames t0 .. t0 + rows - 1, reflected at the ends of the utterance; the window and the twiddles
         const int span = (rows - 1) * S + N;
         stft_stage_span(p.pcm, ck.utt_off, INT64_MAX, ck.utt_len, (int64_t)ck.t0 * S - N / 2, span, span, s_x, tid);
-        for (int i = tid; i < 2 * N; i += 256) s_w[i] = p.operands[i];
+        for (int i = tid; i < 2 * N; i += 256) s_w[i] = p.core.operands[i];
     }
     __syncthreads();
 
-    const float2 *cs = (const float2 *)(p.operands + 2 * N); // -i W_N^k, k <= M
+    const float2 *cs = (const float2 *)(p.core.operands + 2 * N); // -i W_N^k, k <= M
     for (int f = wave; f < rows; f += 4) {
         const float *xs = s_x + f * S;
 #pragma unroll
@@ -161,19 +152,13 @@ __device__ __forceinline__ void stft_fft_block(const StftParams &p, float *smem)
     }
     __syncthreads(); // every wave has left the span: the rows may take its words
 
-    float mx = stft_mel_log(p, s_P, KP, rows, s_out, tid);
-    mx = wave_max(mx);
-    if (lane == 0) s_red[wave] = mx;
-    __syncthreads();
-    if (tid == 0) p.blk_max[p.chunk_first + blockIdx.x] = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
-
-    tile_store_rows(s_out, nb, rows, p.out, ck.out_row, p.out_pitch, tid);
+    stft_finish_block(p.core, s_P, KP, rows, s_x, s_red, p.blk_max + (p.chunk_first + blockIdx.x), ck, tid);
 }
 
 __global__ void __launch_bounds__(256) k_stft_fft_mel(StftParams p)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    if (p.N == 1024)
+    if (p.core.N == 1024)
         stft_fft_block<512>(p, smem);
     else
         stft_fft_block<1024>(p, smem);
@@ -181,39 +166,13 @@ __global__ void __launch_bounds__(256) k_stft_fft_mel(StftParams p)
 
 } // namespace
 
-bool stft_fft_shape_ok(int N, int S, int M) { return (N == 1024 || N == 2048) && S >= 1 && S <= N && M >= 1 && M <= 128; }
-
-bool stft_fft_params_ok(const StftParams &p)
-{
-    return stft_fft_shape_ok(p.N, p.S, p.M) && p.out_pitch >= p.M && p.pcm && p.chunks && p.operands && p.mel_w && p.mel_beg && p.mel_len &&
-           p.mel_off && p.out && p.blk_max && (p.tile_rows == 16 || p.tile_rows == 8 || p.tile_rows == 4) &&
-           stft_fft_lds_bytes(p.N, p.S, p.M, p.tile_rows) <= kLdsMax;
-}
-
 size_t stft_fft_lds_bytes(int N, int S, int M, int tile_rows)
 {
-    const size_t f = (size_t)stft_fft_xo_floats(N, S, M, tile_rows) + (size_t)2 * N /* window, twiddles */ + (size_t)4 * N /* FFT buffers */ +
+    const size_t f = (size_t)stft_xo_floats(N, S, M, tile_rows, 0) + (size_t)2 * N /* window, twiddles */ + (size_t)4 * N /* FFT buffers */ +
                      (size_t)tile_rows * stft_p_pitch(N) + 4 /* s_red */;
     return f * sizeof(float);
 }
 
-int stft_fft_tile_rows(int N, int S, int M)
-{
-    if (!stft_fft_shape_ok(N, S, M)) return 0;
-    for (int r : {16, 8, 4})
-        if (stft_fft_lds_bytes(N, S, M, r) <= kLdsMax) return r;
-    return 0;
-}
-
-hipError_t launch_stft_fft(const StftParams &p, hipStream_t stream)
-{
-    if (p.n_chunks <= 0) return hipSuccess;
-    if (!stft_fft_params_ok(p)) return hipErrorInvalidValue;
-    const size_t lds = stft_fft_lds_bytes(p.N, p.S, p.M, p.tile_rows);
-    const void *fn = (const void *)k_stft_fft_mel;
-    if (hipError_t e = allow_dynamic_lds(fn, lds); e != hipSuccess) return e;
-    StftParams q = p;
-    return launch_kernel(fn, dim3(p.n_chunks), dim3(256), lds, stream, q);
-}
+const void *stft_fft_kernel() { return (const void *)k_stft_fft_mel; }
 
 } // namespace mfx

@@ -528,6 +528,28 @@ void build_stft_fft_operands(int N, const float *window, std::vector<float> &out
     build_stft_fft_tables(N, out.data() + N, out.data() + 2 * N);
 }
 
+void build_stft_form_operands(StftForm form, int N, const float *window, std::vector<float> &out)
+{
+    if (form == StftForm::Fft) return build_stft_fft_operands(N, window, out);
+    std::vector<float> basis((size_t)2 * (N / 2 + 1) * N);
+    build_stft_basis(N, window, basis.data());
+    build_stft_operands(basis.data(), N, stft_pass_tiles(N), out);
+}
+
+void build_slaney_spans(int M, int N, float sample_rate, float low_freq, float high_freq, std::vector<float> &w, std::vector<int32_t> &meta)
+{
+    const int K1 = N / 2 + 1;
+    std::vector<float> dense((size_t)M * K1);
+    w.clear();
+    meta.assign((size_t)3 * M, 0);
+    build_slaney_mel(M, N, sample_rate, low_freq, high_freq, dense.data(), meta.data(), meta.data() + M);
+    for (int m = 0; m < M; ++m) {
+        meta[(size_t)2 * M + m] = (int32_t)w.size();
+        w.insert(w.end(), dense.begin() + (size_t)m * K1 + meta[m], dense.begin() + (size_t)m * K1 + meta[m] + meta[(size_t)M + m]);
+    }
+    if (w.empty()) w.push_back(0.f); // (every band narrower than a bin: keep the buffer non-null)
+}
+
 } // namespace mfx
 
 namespace mfx {

@@ -250,6 +250,16 @@ int64_t session_resample_step(int32_t L, int32_t M, int32_t Wh, int64_t &N, int6
                               SessionResampleStep &st);
 
 // STFT log-mel front end ("STFT log-mel"; N = DFT length, even; K1 = N / 2 + 1 bins).
+// The DFT lengths the method takes and the kernel form each one gets -- THE rule, host and device: even lengths 32 .. 512 run on
+// the matrix pipe (k_stft_mel, k_sess_stft_mel), 1024 and 2048 as a float32 FFT (k_stft_fft_mel, batch entries only)
+enum class StftForm { None, Matrix, Fft };
+constexpr StftForm stft_form(int N) { return N >= 32 && N <= 512 && !(N & 1) ? StftForm::Matrix : N == 1024 || N == 2048 ? StftForm::Fft : StftForm::None; }
+// the limits of a shape: a DFT length of either form, hop 1 .. N, 1 .. 128 bands
+constexpr bool stft_shape_ok(int N, int S, int M) { return stft_form(N) != StftForm::None && S >= 1 && S <= N && M >= 1 && M <= 128; }
+constexpr int kStftTB = 13; // bin tiles (16 bins: a cos and a sin accumulator tile) a wave carries through one pass over the taps
+constexpr int stft_bin_tiles(int N) { return (N / 2 + 1 + 15) >> 4; }
+// bin tiles of a pass of the matrix form: as many as the DFT has, at most kStftTB (the operand table is laid out for it)
+constexpr int stft_pass_tiles(int N) { return stft_bin_tiles(N) < kStftTB ? stft_bin_tiles(N) : kStftTB; }
 // frames of an utterance of `samples` samples: 0 up to N / 2 samples (the reflection needs one more), else samples div S
 int64_t stft_frame_count(int64_t samples, int N, int S);
 // basis [2][K1][N]: Ck[k][j] = w[j] cos(2 pi ((k j) mod N) / N), Sk[k][j] = -w[j] sin(same), in double from the float32
@@ -268,6 +278,12 @@ void build_stft_operands(const float *cos_sin, int N, int tb, std::vector<float>
 void build_stft_fft_tables(int N, float *twid, float *split);
 // what k_stft_fft_mel takes as its operands: window [N] | twid [2 M] | split [2 (M + 1)], 3 N + 2 floats
 void build_stft_fft_operands(int N, const float *window, std::vector<float> &out);
+// what mfx_set_window uploads for a handle of `form`: the basis of `window` in stft_pass_tiles(N)-tile passes
+// (build_stft_basis, build_stft_operands), or the FFT form's operands
+void build_stft_form_operands(StftForm form, int N, const float *window, std::vector<float> &out);
+// the Slaney table as the kernels read it: the rows' non-zero spans back to back in `w` (one zero when every band is narrower
+// than a bin: the buffer is never empty), meta [3][M]: first bin, bins, first weight of every row
+void build_slaney_spans(int M, int N, float sample_rate, float low_freq, float high_freq, std::vector<float> &w, std::vector<int32_t> &meta);
 
 // One push of one session of an STFT log-mel handle ("Session log-mel"): a stream that has received n samples and
 // delivered rows [0, E) takes `length` more.  While the stream is open E = 0 up to n = N / 2, else min(n div S, (n - N / 2)

@@ -1,0 +1,37 @@
+"""Records tests/golden/stft_bits_parent.npz: what commit 51f5b97 (the STFT log-mel kernels before their form rule, argument
+core, block tail and overlay became single pieces) gives for the cases of tests/stft_bits_cases.py, on an MI355X.  The kernels'
+argument structs changed with that work, so the library comes from the WHOLE tree of that commit, not from a variant linked
+against this tree's host objects:
+
+    git worktree add --detach ../stft_parent 51f5b97 && make -C ../stft_parent/asr-featext-opencl_amd/csrc
+    MFX_LIB=../stft_parent/asr-featext-opencl_amd/libmfcchip.so python3 tests/golden/make_stft_bits_parent.py [out.npz]
+
+Per case: the float32 bit patterns (int32 views) of the rows of the three shortest non-empty utterances in full, and an 8-byte
+BLAKE2b digest of every row (uint64), utterance after utterance."""
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import __graft_entry__ as G   # noqa: E402
+import stft_bits_cases as BC  # noqa: E402
+
+pkg = G.load_package()
+out, failed = {}, []
+for name, c in BC.CASES.items():
+    assert BC.tile(pkg, c) == c["want"], (name, BC.tile(pkg, c))
+    try:
+        got = BC.run_case(pkg, name)
+    except (AssertionError, pkg.MfxError) as e:     # (the other cases are still worth seeing)
+        failed.append(name)
+        print("%-36s FAILED: %r" % (name, e), flush=True)
+        continue
+    out[name + "__rows"] = BC.shortest_bits(got)
+    out[name + "__digests"] = BC.digests(got)
+    print("%-36s tile %2d  rows %4d x %d" % (name, c["want"], sum(len(g) for g in got), got[0].shape[1]), flush=True)
+path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "tests", "golden", "stft_bits_parent.npz")
+np.savez_compressed(path, **out)
+assert not failed, failed
+print("wrote %s (%d bytes), library %s" % (path, os.path.getsize(path), os.environ.get("MFX_LIB") or "in-tree"))

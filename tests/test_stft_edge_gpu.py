@@ -2,14 +2,13 @@
 tests/edge_signals.py against the float64 oracle of tests/stft_ref.py at one absolute bar per window, one-hot windows that
 name the sample every probed tap reads, and the maximum of k_stft_post over more than 256 blocks.  Every test prints its
 worst error over its bar; tests/test_stft_edge_host.py derives the bars and the conditions on the CPU."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import edge_signals as ES
 import stft_edge as SE
 import stft_ref
+from stft_drive import MATRIX, bits, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -17,25 +16,11 @@ IDS = [SE.shape_id(s) for s in SE.SHAPES]
 
 
 def make(pkg, shape, window, post=SE.LOG10):
-    N, S, M, sr, low, high = shape
-    m = pkg.MfccHip(200000, N, S, M, sr, low, high, 0, False, 22.0, device=0, bug_compat=False, method=pkg.METHOD_STFT_LOGMEL,
-                    logmel_post=post)
-    m.set_window(window)
-    return m
+    return MATRIX.make(pkg, *shape, window=window, post=post)
 
 
 def block_rows(pkg, shape):
-    r = C.c_int32(0)
-    assert pkg.load_library().mfx_host_stft_lds_bytes(shape[0], shape[1], shape[2], C.byref(r)) > 0
-    return r.value
-
-
-def bits(x):
-    return np.ascontiguousarray(x, np.float32).view(np.uint32)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(bits(a), bits(b))
+    return MATRIX.block_rows(pkg, *shape[:3])
 
 
 def run(m, utts, first=0, order=None):

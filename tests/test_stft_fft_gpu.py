@@ -17,61 +17,13 @@ import stft_edge as SE
 import stft_fft_ref as FR
 import stft_ref
 import xform_ref
-from conftest import GOLDEN, assert_close, synth_utterance
-from test_stft_gpu import hard_inputs
+from conftest import GOLDEN, synth_utterance
+from stft_drive import FFT, check, hard_inputs, layout, run_batch, same_bits
 
 pytestmark = pytest.mark.gpu
 
-N0, S0, M0, SR0 = FR.SHAPES[0]          # (1024, 256, 80, 22050 Hz): the shape most tests run at
-
-
-def make(pkg, N=N0, S=S0, M=M0, sr=SR0, window=None, post=0, ibs=400000):
-    m = pkg.MfccHip(ibs, N, S, M, sr, 0.0, sr / 2, 0, False, 22.0, device=0, bug_compat=False, method=pkg.METHOD_STFT_LOGMEL,
-                    logmel_post=post)
-    m.set_window(pkg.periodic_hann(N) if window is None else window)
-    return m
-
-
-def oracle(pkg, pcm, N=N0, S=S0, M=M0, sr=SR0, window=None, post=0):
-    return FR.logmel(pcm, pkg.periodic_hann(N) if window is None else window, S, M, sr, 0.0, sr / 2, post)
-
-
-def block_rows(pkg, N, S, M):
-    r = pkg.host_stft_fft_lds_bytes(N, S, M)[1]
-    assert r in FR.TILES
-    return r
-
-
-def layout(utts, first=0):
-    lens = np.array([u.size for u in utts], np.int64)
-    offs = first + np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
-    pcm = np.concatenate([np.zeros(first, np.int16)] + list(utts) + [np.zeros(2, np.int16)])
-    return offs, lens, pcm
-
-
-def run_batch(m, utts, first=0):
-    offs, lens, pcm = layout(utts, first)
-    rows, total = m.batch_plan(offs, lens)
-    out = m.batch_run_host(pcm)
-    return [out[rows[i]:rows[i] + m.batch_frames(int(lens[i]))] for i in range(len(utts))]
-
-
-def check(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape, "%s: shape %s vs %s" % (what, got.shape, want.shape)
-    if want.size == 0:
-        return 0.0
-    scale = max(np.abs(want).max(), 1e-30)
-    emax = np.abs(got.astype(np.float64) - want).max() / scale
-    el2 = np.linalg.norm(got - want) / max(np.linalg.norm(want), 1e-30)
-    print("%s: max err / scale = %.3g, rel L2 = %.3g (scale %.3g)" % (what, emax, el2, scale))
-    assert_close(got, want, what)
-    return emax
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+N0, S0, M0, SR0 = FFT.shape             # (1024, 256, 80, 22050 Hz): the shape most tests run at
+make, oracle, block_rows = FFT.make, FFT.oracle, FFT.block_rows
 
 
 # ---- 1. ragged batch ------------------------------------------------------------------------------------------------

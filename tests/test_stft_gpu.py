@@ -4,7 +4,6 @@ tests/stft_ref.py at the project bar (conftest.assert_close: 1e-4 of scale, 1e-5
 A float32 restatement of the pipeline on the CPU stays below 2e-6 of scale in WHISPER mode on the inputs used here, so the bar
 leaves about 50x room for the chain order and the device's log; every test prints its worst figure.
 """
-import ctypes as C
 import os
 import struct
 import subprocess
@@ -14,54 +13,13 @@ import pytest
 
 import stft_ref
 import xform_ref
-from conftest import GOLDEN, assert_close, synth_utterance
+from conftest import GOLDEN, synth_utterance
+from stft_drive import MATRIX, check, hard_inputs, layout, run_batch, same_bits
 
 pytestmark = pytest.mark.gpu
 
 R = 64   # frames per block of k_stft_mel at N = 400, S = 160 (mfx_stft.hip: the largest tile whose LDS fits)
-
-
-def make(pkg, N=400, S=160, M=80, sr=16000.0, low=0.0, high=None, post=0, ibs=200000):
-    m = pkg.MfccHip(ibs, N, S, M, sr, low, sr / 2 if high is None else high, 0, False, 22.0, device=0, bug_compat=False,
-                    method=pkg.METHOD_STFT_LOGMEL, logmel_post=post)
-    m.set_window(pkg.periodic_hann(N))
-    return m
-
-
-def oracle(pkg, pcm, N=400, S=160, M=80, sr=16000.0, low=0.0, high=None, post=0):
-    return stft_ref.logmel(pcm, pkg.periodic_hann(N), S, M, sr, low, sr / 2 if high is None else high, post)
-
-
-def layout(utts, first=0):
-    lens = np.array([u.size for u in utts], np.int64)
-    offs = first + np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
-    pcm = np.concatenate([np.zeros(first, np.int16)] + list(utts) + [np.zeros(2, np.int16)])
-    return offs, lens, pcm
-
-
-def run_batch(m, utts, first=0):
-    offs, lens, pcm = layout(utts, first)
-    rows, total = m.batch_plan(offs, lens)
-    out = m.batch_run_host(pcm)
-    return [out[rows[i]:rows[i] + m.batch_frames(int(lens[i]))] for i in range(len(utts))]
-
-
-def check(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape, "%s: shape %s vs %s" % (what, got.shape, want.shape)
-    if want.size == 0:
-        return 0.0
-    scale = max(np.abs(want).max(), 1e-30)
-    emax = np.abs(got.astype(np.float64) - want).max() / scale
-    el2 = np.linalg.norm(got - want) / max(np.linalg.norm(want), 1e-30)
-    print("%s: max err / scale = %.3g, rel L2 = %.3g (scale %.3g)" % (what, emax, el2, scale))
-    assert_close(got, want, what)
-    return emax
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+make, oracle = MATRIX.make, MATRIX.oracle       # (N, S, M, sr default to (400, 160, 80, 16 kHz))
 
 
 # ---- 1. ragged batch ------------------------------------------------------------------------------------------------
@@ -173,24 +131,6 @@ def test_post_modes(pkg):
 
 
 # ---- 4. hard inputs -------------------------------------------------------------------------------------------------
-
-def hard_inputs():
-    n = 20800
-    t = np.arange(n)
-    rng = np.random.default_rng(5)
-    imp_mid = np.zeros(n, np.int16)
-    imp_mid[n // 2] = 32767
-    imp_ends = np.zeros(n, np.int16)
-    imp_ends[0], imp_ends[-1] = 32767, -32768
-    return {
-        "silence": np.zeros(n, np.int16),
-        "full-scale tone": np.round(32767.0 * np.sin(2 * np.pi * 1000.0 * t / 16000.0)).astype(np.int16),
-        "clipped noise": np.clip(np.round(40000.0 * rng.standard_normal(n)), -32768, 32767).astype(np.int16),
-        "quiet": (synth_utterance(n, 31).astype(np.int32) // 512).astype(np.int16),
-        "impulse at the centre": imp_mid,
-        "impulses at both ends": imp_ends,
-    }
-
 
 def test_hard_inputs(pkg):
     sig = hard_inputs()

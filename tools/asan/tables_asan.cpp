@@ -182,6 +182,13 @@ int main()
             for (float v : ops) a += (double)v * v, na += v != 0.f;
             for (float v : basis) b += (double)v * v, nb += v != 0.f;
             if (na != nb || !(a >= b * (1 - 1e-9) && a <= b * (1 + 1e-9))) return 1;
+            std::vector<float> form_ops, spans; // the two builders the handle goes through: the same operands, the spans packed
+            std::vector<int32_t> meta;
+            mfx::build_stft_form_operands(mfx::stft_form(N), N, win.data(), form_ops);
+            mfx::build_slaney_spans(M, N, 16000.f, 0.f, 8000.f, spans, meta);
+            if (form_ops != ops || meta.size() != (size_t)3 * M || spans.empty()) return 1;
+            for (int m = 0; m < M; ++m)
+                if (meta[m] != beg[m] || meta[M + m] != len[m] || (len[m] > 0 && spans[meta[2 * M + m]] != w[(size_t)m * K1 + beg[m]])) return 1;
             ++ns;
         }
     for (long s : {0L, 200L, 201L, 159L, 160L, 1L << 40})
