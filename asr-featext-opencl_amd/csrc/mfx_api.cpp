@@ -1118,11 +1118,7 @@ extern "C" int64_t mfx_host_resample_layout(int32_t n_utt, const int64_t *length
 extern "C" int32_t mfx_host_resample_tile(int32_t in_hz, int32_t out_hz, int32_t zeros, float rolloff, int32_t channels)
 {
     if (channels < 0 || channels > 2) return MFX_ERR_ARG;
-    ResampleShape sh;
-    if (resample_shape(in_hz, out_hz, zeros, rolloff, sh) != 0) return MFX_ERR_ARG;
-    if (in_hz == out_hz) return kResCopyTile;
-    ResRate r{};
-    r.L = sh.L, r.M = sh.M, r.P = sh.P, r.Wh = sh.Wh;
-    resample_geometry(channels, r);
-    return r.tile_out;
+    ResRateSet set;
+    if (build_resample_rates(channels, out_hz, &in_hz, 1, zeros, rolloff, true, set) != 0) return MFX_ERR_ARG;
+    return set.tile_min; // (the one rate's tile_out, or kResCopyTile)
 }

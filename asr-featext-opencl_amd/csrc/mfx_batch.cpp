@@ -94,7 +94,7 @@ int convert_rates(mfx_handle *h, const int16_t *d_pcm, int u0, int u1)
     rp.rates = rs.d_rates.p;
     rp.taps = rs.d_taps.p;
     rp.channels = h->channels;
-    rp.taps_floats = rs.taps_floats, rp.x_floats = rs.x_floats, rp.out_elems = rs.out_elems;
+    rp.lds = rs.lds;
     HIP_TRY(h, launch_resample(rp, h->stream));
     return MFX_OK;
 }

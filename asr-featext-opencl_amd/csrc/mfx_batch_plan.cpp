@@ -340,27 +340,11 @@ extern "C" int mfx_batch_plan_rates(mfx_handle *h, int32_t n_utt, const int64_t 
         }
         rate_of[u] = (int32_t)k;
     }
-    std::vector<ResRate> rates(distinct.size());
-    std::vector<float> taps;
-    int32_t taps_floats = 0, x_floats = 8, out_elems = 2;
-    for (size_t k = 0; k < distinct.size(); ++k) {
-        ResRate &r = rates[k];
-        r = ResRate{};
-        if (distinct[k] == out_hz) continue; // (tile_out == 0 marks the copy)
-        ResampleShape sh;
-        static const char *const why[] = {"", "sample rates must lie in 1000 .. 768000 Hz", "zeros must be 1 .. 64 (0 = 6)",
-                                          "rolloff must lie in (0, 1] (0 = 0.99)", "L = out_hz / gcd is larger than 4096",
-                                          "the filter has more than 4096 taps per phase", "the tap table L x P is larger than 2^20 floats"};
-        if (const int e = resample_shape(distinct[k], out_hz, zeros, rolloff, sh); e != 0) return fail(h, MFX_ERR_ARG, why[-e]);
-        r.taps_off = (int64_t)taps.size();
-        r.L = sh.L, r.M = sh.M, r.P = sh.P, r.Wh = sh.Wh;
-        taps.resize(taps.size() + (size_t)sh.L * sh.P);
-        build_resample_taps(sh, taps.data() + r.taps_off);
-        resample_geometry(h->channels, r);
-        if (r.in_lds) taps_floats = std::max(taps_floats, (r.L * (r.P + 1) + 3) & ~3);
-        x_floats = std::max(x_floats, resample_span_floats(r));
-        out_elems = std::max(out_elems, r.tile_out * h->channels);
-    }
+    // (zeros and rolloff are not judged for the output rate itself: a plan whose utterances all have it takes any)
+    ResRateSet set;
+    if (const int e = build_resample_rates(h->channels, out_hz, distinct.data(), (int)distinct.size(), zeros, rolloff, false, set); e != 0)
+        return fail(h, MFX_ERR_ARG, kResampleWhy[e]);
+    const std::vector<ResRate> &rates = set.rates;
     std::vector<int64_t> sc_off((size_t)n_utt), sc_len((size_t)n_utt);
     const int64_t sc_total = resample_layout(n_utt, lengths, rates_hz, out_hz, sc_off.data(), sc_len.data());
     if (sc_total < 0) return fail(h, MFX_ERR_ARG, "invalid argument");
@@ -379,17 +363,14 @@ extern "C" int mfx_batch_plan_rates(mfx_handle *h, int32_t n_utt, const int64_t 
         }
     }
     tile0[n_utt] = (int32_t)tiles.size();
-    ResampleParams probe{};
-    probe.channels = h->channels, probe.taps_floats = taps_floats, probe.x_floats = x_floats, probe.out_elems = out_elems;
-    if (resample_lds_bytes(probe) > kLdsCap) return fail(h, MFX_ERR_ARG, "no tile of k_resample fits the LDS for this shape");
+    if (resample_lds_bytes(h->channels, set.lds) > kLdsCap) return fail(h, MFX_ERR_ARG, "no tile of k_resample fits the LDS for this shape");
 
     int rc = plan_batch(h, n_utt, sc_off.data(), sc_len.data(), out_rows, total_rows); // (waits for the stream)
     h->batch.rs.on = false; // (not drop(): the scratch is grown, never shrunk, and the tables are replaced below)
     if (rc != MFX_OK) return rc;
     h->batch.planned = false;
-    if (taps.empty()) taps.assign(4, 0.f); // (every utterance at the output rate: keep the buffers non-null)
     if (tiles.empty()) tiles.push_back(ResTile{});
-    HIP_TRY(h, h->upload(h->batch.rs.d_taps, taps));
+    HIP_TRY(h, h->upload(h->batch.rs.d_taps, set.taps));
     HIP_TRY(h, h->upload(h->batch.rs.d_rates, rates));
     HIP_TRY(h, h->upload(h->batch.rs.d_tiles, tiles));
     // (allocated here so that mfx_batch_run_device itself never allocates; 8 elements of padding: the front ends read the
@@ -403,7 +384,7 @@ extern "C" int mfx_batch_plan_rates(mfx_handle *h, int32_t n_utt, const int64_t 
     h->batch.rs.in_len.assign(lengths, lengths + n_utt);
     h->batch.rs.utt_tile0.swap(tile0);
     h->batch.rs.total = sc_total;
-    h->batch.rs.taps_floats = taps_floats, h->batch.rs.x_floats = x_floats, h->batch.rs.out_elems = out_elems;
+    h->batch.rs.lds = set.lds;
     h->batch.rs.on = true;
     h->batch.planned = true;
     return MFX_OK;

@@ -222,7 +222,7 @@ struct BatchState {
         std::vector<int64_t> in_off, in_len;
         std::vector<int32_t> utt_tile0;  // [n_utt + 1] first tile of every utterance (tiles are in utterance order)
         int64_t total = 0;               // samples per channel of the scratch (even)
-        int32_t taps_floats = 0, x_floats = 0, out_elems = 0; // LDS parts of the launch: maxima over the plan's rates
+        mfx::ResLds lds{};               // LDS parts of the launch: maxima over the plan's rates
         DevBuf<int16_t> d_pcm;           // [total * channels + 8]
         DevBuf<float> d_taps;
         DevBuf<mfx::ResRate> d_rates;
@@ -453,7 +453,7 @@ struct SessState {
         std::vector<int32_t> hz;
         std::vector<mfx::ResRate> rates; // one per rate; tile_out == 0: pass-through (the rate is sample_rate)
         std::vector<float> taps;
-        int32_t taps_floats = 0, x_floats = 8, out_elems = 2; // LDS parts of the launch: maxima over the rates
+        mfx::ResLds lds{0, 8, 2};        // LDS parts of the launch: maxima over the rates
         int32_t carry_cap = 0;           // samples per channel of a carry slot: max over rates (2 Wh + M div L + 2), a multiple of 8
         int32_t tile_min = 0;            // the smallest tile_out (kResCopyTile for a pass-through rate)
         int64_t conv_stride = 0;         // samples per channel one piece has in the scratch (max_conv rounded up to even)

@@ -323,15 +323,8 @@ struct SessGatherParams {
 };
 
 // k_resample (mfx_resample.hip): per-utterance sample-rate conversion, int16 -> int16 ("Sample-rate conversion").
-// One ResRate per distinct input rate of the plan; one ResTile per run of at most tile_out output samples of one utterance.
-struct ResRate {
-    int64_t taps_off;   // first float of the rate's table [L][P] inside ResampleParams::taps
-    int32_t L, M, P, Wh;
-    int32_t R;          // same-phase outputs a work item carries (1, 2 or 4)
-    int32_t items;      // work items of a full tile; a multiple of L when R > 1: outputs w + r items, r < R, share a phase
-    int32_t tile_out;   // R * items, even
-    int32_t in_lds;     // the table is staged in LDS (row stride P + 1), else read through the caches
-};
+// One ResRate (mfx_tables.h) per distinct input rate of the plan; one ResTile per run of at most tile_out output samples of one
+// utterance.
 struct ResTile {
     int64_t in_off;     // the utterance in the caller's array: first sample (per channel), any parity
     int64_t out_off;    // the utterance in the scratch: first sample (per channel), even
@@ -348,11 +341,8 @@ struct ResampleParams {
     const float *taps;
     int32_t n_tiles;
     int32_t channels;   // 1 or 2 (interleaved; each channel converted on its own)
-    int32_t taps_floats; // LDS floats of the table part (0: no rate of the plan stages its table)
-    int32_t x_floats;   // LDS floats per channel of the staged input span (a multiple of 8)
-    int32_t out_elems;  // LDS int16 elements of the output staging (even)
+    ResLds lds;         // the LDS parts: maxima over the plan's rates
 };
-constexpr int kResCopyTile = 4096; // samples per channel of a tile of a same-rate utterance
 
 // k_sess_resample (mfx_sess_resample.hip): the converter in front of a push of the session entries ("Session
 // sample-rate conversion").  One SessResTile per run of at most tile_out outputs of ONE piece; positions are samples per
@@ -379,7 +369,7 @@ struct SessResampleParams {
     const float *taps;
     int32_t n_tiles;
     int32_t channels;
-    int32_t taps_floats, x_floats, out_elems; // the LDS parts, as in ResampleParams
+    ResLds lds;         // as in ResampleParams
 };
 
 struct DeltaParams {
@@ -667,13 +657,8 @@ hipError_t launch_sess_gather(const SessGatherParams &p, hipStream_t stream);
 size_t sess_xform_lds_bytes(const SessXformParams &p, int tile_rows);
 int sess_xform_tile_rows(const SessXformParams &p);
 hipError_t launch_sess_xform(const SessXformParams &p, hipStream_t stream);
-// k_resample: tile geometry of one rate (fills R, items, tile_out, in_lds from L, M, P), the LDS floats per channel its
-// input span needs, and the launch (taps_floats / x_floats / out_elems are the maxima over the plan's rates)
-void resample_geometry(int channels, ResRate &r);
-int resample_span_floats(const ResRate &r);
-size_t resample_lds_bytes(const ResampleParams &p);
+// k_resample and k_sess_resample (geometry and the LDS sum: mfx_tables.h)
 hipError_t launch_resample(const ResampleParams &p, hipStream_t stream);
-// k_sess_resample: the same LDS sum, and the launch
 hipError_t launch_sess_resample(const SessResampleParams &p, hipStream_t stream);
 // work items of one descriptor: 16-byte words of PCM, then 16-byte words (or single floats) of static rows, then the floats
 // of the carried rows y

@@ -290,38 +290,16 @@ extern "C" int mfx_sessions_set_rates(mfx_handle *h, int32_t n_rates, const int3
         return fail(h, MFX_ERR_ARG, "sample rates must lie in 1000 .. 768000 Hz");
     const int32_t out_hz = (int32_t)h->cfg.sample_rate;
     if ((float)out_hz != h->cfg.sample_rate) return fail(h, MFX_ERR_CONFIG, "mfx_sessions_set_rates: sample_rate is not an integral number of Hz");
-    // the tables and tile geometry of every rate, as mfx_batch_plan_rates builds them (a pass-through rate has none)
-    std::vector<ResRate> rates((size_t)n_rates);
-    std::vector<float> taps;
-    int32_t taps_floats = 0, x_floats = 8, out_elems = 2, carry_cap = 8, tile_min = kResCopyTile;
-    for (int k = 0; k < n_rates; ++k) {
-        ResRate &r = rates[k];
-        r = ResRate{};
-        ResampleShape sh;
-        static const char *const why[] = {"", "sample rates must lie in 1000 .. 768000 Hz", "zeros must be 1 .. 64 (0 = 6)",
-                                          "rolloff must lie in (0, 1] (0 = 0.99)", "L = out_hz / gcd is larger than 4096",
-                                          "the filter has more than 4096 taps per phase", "the tap table L x P is larger than 2^20 floats"};
-        if (const int e = resample_shape(rates_hz[k], out_hz, zeros, rolloff, sh); e != 0) return fail(h, MFX_ERR_ARG, why[-e]);
-        if (rates_hz[k] == out_hz) continue; // (tile_out == 0 marks the pass-through)
-        r.taps_off = (int64_t)taps.size();
-        r.L = sh.L, r.M = sh.M, r.P = sh.P, r.Wh = sh.Wh;
-        taps.resize(taps.size() + (size_t)sh.L * sh.P);
-        build_resample_taps(sh, taps.data() + r.taps_off);
-        resample_geometry(h->channels, r);
-        if (r.in_lds) taps_floats = std::max(taps_floats, (r.L * (r.P + 1) + 3) & ~3);
-        x_floats = std::max(x_floats, resample_span_floats(r));
-        out_elems = std::max(out_elems, r.tile_out * h->channels);
-        carry_cap = std::max(carry_cap, (2 * r.Wh + r.M / r.L + 2 + 7) & ~7);
-        tile_min = std::min(tile_min, r.tile_out);
-    }
-    ResampleParams probe{};
-    probe.channels = h->channels, probe.taps_floats = taps_floats, probe.x_floats = x_floats, probe.out_elems = out_elems;
-    if (resample_lds_bytes(probe) > kLdsCap) return fail(h, MFX_ERR_ARG, "no tile of k_sess_resample fits the LDS for this shape");
-    if (taps.empty()) taps.assign(4, 0.f); // (every rate the output rate: keep the buffer non-null)
+    // the tables and tile geometry of every rate, as mfx_batch_plan_rates builds them (a pass-through rate has none, but
+    // zeros and rolloff are judged for it too)
+    ResRateSet set;
+    if (const int e = build_resample_rates(h->channels, out_hz, rates_hz, n_rates, zeros, rolloff, true, set); e != 0)
+        return fail(h, MFX_ERR_ARG, kResampleWhy[e]);
+    if (resample_lds_bytes(h->channels, set.lds) > kLdsCap) return fail(h, MFX_ERR_ARG, "no tile of k_sess_resample fits the LDS for this shape");
     SessState::Rates &rs = h->sess.rs;
     rs.hz.assign(rates_hz, rates_hz + n_rates);
-    rs.rates.swap(rates), rs.taps.swap(taps);
-    rs.taps_floats = taps_floats, rs.x_floats = x_floats, rs.out_elems = out_elems, rs.carry_cap = carry_cap, rs.tile_min = tile_min;
+    rs.rates.swap(set.rates), rs.taps.swap(set.taps);
+    rs.lds = set.lds, rs.carry_cap = set.carry_cap, rs.tile_min = set.tile_min;
     rs.set = true;
     return MFX_OK;
 }
@@ -779,7 +757,7 @@ int run_resample(mfx_handle *h, const PushRun &r)
     rp.tiles = r.up.rtiles, rp.n_tiles = (int32_t)ss.push.rtiles.size();
     rp.rates = ss.rs.d_rates.p, rp.taps = ss.rs.d_taps.p;
     rp.channels = h->channels;
-    rp.taps_floats = ss.rs.taps_floats, rp.x_floats = ss.rs.x_floats, rp.out_elems = ss.rs.out_elems;
+    rp.lds = ss.rs.lds;
     HIP_TRY(h, launch_sess_resample(rp, h->stream));
     return MFX_OK;
 }

@@ -801,6 +801,75 @@ int64_t resample_layout(int32_t n_utt, const int64_t *lengths, const int32_t *ra
     return off;
 }
 
+// outputs whose input span fits `budget` floats per channel
+static int64_t fit_outputs(const ResRate &r, int64_t budget)
+{
+    const int64_t s = budget - r.P - 32;
+    return s <= 0 ? 0 : s * r.L / r.M;
+}
+
+// Target: 2048 outputs per tile with the input span inside 32 KB of LDS (all channels); a ratio or a filter too long for that
+// takes up to 64 KB, and fewer outputs (the limits of resample_shape leave at least 4).  R same-phase outputs per work item: 4
+// where four periods of L fit the tile, else 2, else 1 (every phase then occurs at most once in a tile: nothing to share).  The
+// table goes to LDS when its padded form is at most 64 KB.
+void resample_geometry(int channels, ResRate &r)
+{
+    const int ch = channels == 2 ? 2 : 1;
+    int64_t to = std::min<int64_t>(2048, fit_outputs(r, 8192 / ch));
+    if (to < 64) to = std::min<int64_t>(2048, fit_outputs(r, 16384 / ch));
+    to = std::max<int64_t>(to & ~(int64_t)1, 2);
+    if (2 * (int64_t)r.L > to) {
+        r.R = 1;
+        r.items = (int32_t)to;
+    } else {
+        r.R = 4 * (int64_t)r.L <= to ? 4 : 2;
+        r.items = r.L * (int32_t)(to / ((int64_t)r.R * r.L));
+    }
+    r.tile_out = r.R * r.items;
+    r.in_lds = (int64_t)r.L * (r.P + 1) <= 16384 ? 1 : 0;
+}
+
+// (tile_out - 1) M / L + 1 input positions + P - 1 of halo + 1 for the parity step of a mono source, rounded up to whole groups
+// of 8
+int resample_span_floats(const ResRate &r)
+{
+    const int64_t span = ((int64_t)(r.tile_out - 1) * r.M) / r.L + r.P + 3;
+    return (int)(((span + 7) & ~(int64_t)7) + 8);
+}
+
+const char *const kResampleWhy[7] = {"", "sample rates must lie in 1000 .. 768000 Hz", "zeros must be 1 .. 64 (0 = 6)",
+                                     "rolloff must lie in (0, 1] (0 = 0.99)", "L = out_hz / gcd is larger than 4096",
+                                     "the filter has more than 4096 taps per phase", "the tap table L x P is larger than 2^20 floats"};
+
+int build_resample_rates(int channels, int32_t out_hz, const int32_t *in_hz, int n_rates, int32_t zeros, float rolloff, bool check_same_rate,
+                         ResRateSet &set)
+{
+    set.rates.assign((size_t)n_rates, ResRate{});
+    set.taps.clear();
+    set.lds = ResLds{0, 8, 2};
+    set.carry_cap = 8, set.tile_min = kResCopyTile;
+    for (int k = 0; k < n_rates; ++k) {
+        ResRate &r = set.rates[k];
+        const bool same = in_hz[k] == out_hz;
+        if (same && !check_same_rate) continue;
+        ResampleShape sh;
+        if (const int e = resample_shape(in_hz[k], out_hz, zeros, rolloff, sh); e != 0) return -e;
+        if (same) continue;
+        r.taps_off = (int64_t)set.taps.size();
+        r.L = sh.L, r.M = sh.M, r.P = sh.P, r.Wh = sh.Wh;
+        set.taps.resize(set.taps.size() + (size_t)sh.L * sh.P);
+        build_resample_taps(sh, set.taps.data() + r.taps_off);
+        resample_geometry(channels, r);
+        if (r.in_lds) set.lds.taps_floats = std::max(set.lds.taps_floats, (r.L * (r.P + 1) + 3) & ~3);
+        set.lds.x_floats = std::max(set.lds.x_floats, resample_span_floats(r));
+        set.lds.out_elems = std::max(set.lds.out_elems, r.tile_out * channels);
+        set.carry_cap = std::max(set.carry_cap, (2 * r.Wh + r.M / r.L + 2 + 7) & ~7);
+        set.tile_min = std::min(set.tile_min, r.tile_out);
+    }
+    if (set.taps.empty()) set.taps.assign(4, 0.f);
+    return 0;
+}
+
 int64_t session_resample_step(int32_t L, int32_t M, int32_t Wh, int64_t &N, int64_t &J, int64_t length, bool final_push,
                               SessionResampleStep &st)
 {

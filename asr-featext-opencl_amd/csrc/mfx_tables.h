@@ -4,6 +4,7 @@
 // are built once per handle (the mel table again on every set_alpha change) in the reference's
 // float32 expression order and uploaded to HBM.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 #include <vector>
 
@@ -234,6 +235,44 @@ int64_t resampled_length(int64_t samples, int32_t in_hz, int32_t out_hz);
 // the total (even), or -1 on a negative length or a rate outside the limits.
 int64_t resample_layout(int32_t n_utt, const int64_t *lengths, const int32_t *rates_hz, int32_t out_hz, int64_t *offsets,
                         int64_t *out_lengths);
+
+// What the two converters (k_resample, k_sess_resample) are told about one input rate: its table and its tile geometry.
+struct ResRate {
+    int64_t taps_off;   // first float of the rate's table [L][P] inside the launch's taps
+    int32_t L, M, P, Wh;
+    int32_t R;          // same-phase outputs a work item carries (1, 2 or 4)
+    int32_t items;      // work items of a full tile; a multiple of L when R > 1: outputs w + r items, r < R, share a phase
+    int32_t tile_out;   // R * items, even
+    int32_t in_lds;     // the table is staged in LDS (row stride P + 1), else read through the caches
+};
+// The three parts of a converter launch's LDS, each the maximum over the rates it serves
+struct ResLds {
+    int32_t taps_floats; // floats of the table part (0: no rate stages its table)
+    int32_t x_floats;    // floats per channel of the staged input span (a multiple of 8)
+    int32_t out_elems;   // int16 elements of the output staging (even)
+};
+constexpr int kResCopyTile = 4096; // samples per channel of a tile of a same-rate utterance / pass-through piece
+inline size_t resample_lds_bytes(int channels, const ResLds &l)
+{
+    return ((size_t)l.taps_floats + (size_t)(channels == 2 ? 2 : 1) * l.x_floats) * sizeof(float) + (size_t)l.out_elems * sizeof(int16_t);
+}
+// Tile geometry of one rate (fills R, items, tile_out, in_lds from L, M, P), and the LDS floats per channel its span needs
+void resample_geometry(int channels, ResRate &r);
+int resample_span_floats(const ResRate &r);
+// Everything a plan or a session set derives from its input rates, in the order given: tables (concatenated; four zeros when no
+// rate converts, so that the buffer is never empty), geometry, the LDS maxima, and for the sessions the carry slot's samples
+// per channel (max over rates of 2 Wh + M div L + 2, a multiple of 8) and the smallest tile.  A rate equal to out_hz has no
+// table: tile_out == 0 marks the copy; check_same_rate says whether resample_shape judges zeros and rolloff for it too
+// (mfx_sessions_set_rates does, mfx_batch_plan_rates does not).  Returns 0, or the index into kResampleWhy of the refusal.
+struct ResRateSet {
+    std::vector<ResRate> rates;
+    std::vector<float> taps;
+    ResLds lds;
+    int32_t carry_cap, tile_min;
+};
+extern const char *const kResampleWhy[7];
+int build_resample_rates(int channels, int32_t out_hz, const int32_t *in_hz, int n_rates, int32_t zeros, float rolloff, bool check_same_rate,
+                         ResRateSet &set);
 
 // One push of one session under a session rate ("Session sample-rate conversion"): a stream that has received N
 // input samples per channel and holds converted samples [0, J) takes `length` more.  J = max(0, ceil((N - Wh) L / M)) while the

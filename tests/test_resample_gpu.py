@@ -82,21 +82,21 @@ def signal(kind, n, rate, seed):
     return np.where((t // 23) % 2 == 0, 32767, -32768).astype(np.int16)   # full-scale square wave: the overshoot saturates
 
 
-def batch(pkg):
-    """The ragged batch (computed once, never modified): per-rate lengths 0, 1, 2, Wh - 1, Wh, 2 Wh + 1, around one tile of
-    the kernel, two tiles + 3; three pass-through utterances; every other utterance on an odd input offset; gaps between
-    utterances filled with +-32767."""
-    if _BATCH:
-        return _BATCH
+def ragged(pkg, in_rates, out_hz, channels=1, kinds=3):
+    """A ragged batch to convert to out_hz (host arithmetic only): per input rate lengths 0, 1, 2, Wh - 1, Wh, 2 Wh + 1, around
+    one tile of the kernel, two tiles + 3; three pass-through utterances; every other utterance on an odd input offset; gaps
+    between utterances filled with +-32767.  Utterance i carries signal kind i % kinds (kinds = 1: full-scale noise throughout);
+    a second channel carries the same kind at another seed.  Returns dict(lens, rates, offs, utts [n][channels] (mono: [n]),
+    pcm (flat, interleaved))."""
     lens, rates = [], []
-    for r in RATES3:
-        h, L, M, P = pkg.mfcc.host_resample_taps(r, SR)
-        Wh, tile = P // 2, pkg.mfcc.host_resample_tile(r, SR)
+    for r in in_rates:
+        h, L, M, P = pkg.mfcc.host_resample_taps(r, out_hz)
+        Wh, tile = P // 2, pkg.mfcc.host_resample_tile(r, out_hz, channels=channels)
         edge = -(-tile * M // L)                            # the shortest input that fills one tile
         for n in (0, 1, 2, Wh - 1, Wh, 2 * Wh + 1, edge - 1, edge, edge + 1, 2 * edge + 3):
             lens.append(n), rates.append(r)
     for n in (0, 401, 4096 + 5):                            # pass-through: empty, short, more than one copy tile
-        lens.append(n), rates.append(SR)
+        lens.append(n), rates.append(out_hz)
     order = np.random.default_rng(5).permutation(len(lens))
     lens, rates = [lens[i] for i in order], [rates[i] for i in order]
     offs, pos = [], 2
@@ -106,11 +106,22 @@ def batch(pkg):
             pos += 1                                        # odd utterances on odd offsets
         offs.append(pos)
         pos += n
-    pcm = np.where(np.arange(pos + 8) % 2 == 0, 32767, -32767).astype(np.int16)
+    pcm = np.repeat(np.where(np.arange(pos + 8) % 2 == 0, 32767, -32767).astype(np.int16)[:, None], channels, 1)
     utts = []
     for i, (o, n, r) in enumerate(zip(offs, lens, rates)):
-        utts.append(signal(i % 3, n, r, i))
-        pcm[o:o + n] = utts[-1]
+        x = np.stack([signal(i % kinds, n, r, i + 1000 * c) for c in range(channels)], 1)
+        pcm[o:o + n] = x
+        utts.append(x[:, 0].copy() if channels == 1 else x)
+    return dict(lens=lens, rates=rates, offs=offs, utts=utts, pcm=pcm.reshape(-1))
+
+
+def batch(pkg):
+    """ragged() of RATES3 -> SR, mono, the three signal kinds, and what the library gives for it (computed once, never
+    modified)."""
+    if _BATCH:
+        return _BATCH
+    d = ragged(pkg, RATES3, SR)
+    lens, rates, offs, pcm, utts = d["lens"], d["rates"], d["offs"], d["pcm"], d["utts"]
     m = make(pkg)
     rows, total = m.batch_plan_rates(offs, lens, rates)
     feats = m.batch_run_host(pcm)
@@ -318,6 +329,12 @@ def test_limits_and_config_errors_on_the_handle(pkg):
     with pytest.raises(pkg.MfxError) as e:
         m.batch_plan_rates([0], [100], [44100], zeros=65)
     assert e.value.status == -7
+    # utterances at the output rate have no filter: zeros and rolloff are not judged for them (the sessions do judge them:
+    # tests/test_sess_resample_gpu.py)
+    x = signal(0, 500, SR, 1)
+    m.batch_plan_rates([0], [500], [SR], zeros=65)
+    m.batch_run_host(np.concatenate([x, np.zeros(8, np.int16)]))
+    assert np.array_equal(m.debug_read(8), x)
     m.close()
     f = make(pkg, sr=16000.5)
     with pytest.raises(pkg.MfxError) as e:

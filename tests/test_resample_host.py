@@ -109,6 +109,30 @@ def test_tile_rule_stays_inside_the_lds(pkg):
     assert pkg.mfcc.host_resample_tile(16000, 16000) == 4096
 
 
+def test_the_tile_of_the_output_rate_itself_judges_zeros_and_rolloff(pkg):
+    """mfx_host_resample_tile goes through the planners' rate builder with the check the sessions ask for: a pair of equal
+    rates is a copy tile, and its zeros and rolloff are still judged (mfx_batch_plan_rates alone does not judge them:
+    tests/test_resample_gpu.py, tools/asan/tables_asan.cpp)."""
+    L = pkg.load_library()
+    assert L.mfx_host_resample_tile(16000, 16000, 0, 0.0, 1) == 4096 and L.mfx_host_resample_tile(16000, 16000, 64, 1.0, 2) == 4096
+    assert L.mfx_host_resample_tile(16000, 16000, 65, 0.0, 1) == ERR_ARG and L.mfx_host_resample_tile(16000, 16000, 0, 1.5, 1) == ERR_ARG
+    assert L.mfx_host_resample_tile(44100, 16000, 65, 0.0, 1) == ERR_ARG and L.mfx_host_resample_tile(16000, 16001, 0, 0.0, 1) == ERR_ARG
+    assert L.mfx_host_resample_tile(44100, 16000, 0, 0.0, 3) == ERR_ARG
+
+
+def test_the_recorded_cases_name_their_geometry_and_their_paths(pkg):
+    """tests/resample_bits_cases.py on the CPU: every case's geometry is the library's, every session cut takes the paths of the
+    group loader it is there for, and the one case over 64 KB of LDS is over it."""
+    import resample_bits_cases as BC
+    for name, c in BC.CASES.items():
+        assert BC.geometry(pkg, c) == c["want"], name
+        if c["kind"] == "session":
+            assert BC.needed(c) <= BC.paths(pkg, c), (name, BC.paths(pkg, c))
+    assert BC.lds_bytes(BC.CASES["batch_44142_44100_ch1"]) == 75424
+    assert [n for n, c in BC.CASES.items() if c["kind"] == "batch" and BC.lds_bytes(c) > 65536] == ["batch_44142_44100_ch1"]
+    assert any("carry5" in BC.needed(c) for c in BC.CASES.values() if c["kind"] == "session")
+
+
 def test_a_planning_handle_answers_err_device(pkg):
     L = pkg.load_library()
     cfg = pkg.MfxConfig()

@@ -272,6 +272,8 @@ def test_state_rules_and_errors(pkg):
     assert status_of(pkg, m.sessions_set_rates, [48000] * 17) == ERR_ARG
     assert status_of(pkg, m.sessions_set_rates, [999]) == ERR_ARG
     assert status_of(pkg, m.sessions_set_rates, [48000], 65) == ERR_ARG
+    assert status_of(pkg, m.sessions_set_rates, [SR], 65) == ERR_ARG            # judged for a pass-through rate too
+    assert status_of(pkg, m.sessions_set_rates, [SR, 48000], 0, 1.5) == ERR_ARG
     assert status_of(pkg, m.sessions_set_rates, [48000], 0, 1.5) == ERR_ARG
     assert status_of(pkg, m.sessions_set_rates, [16001]) == ERR_ARG             # L = 16000 > 4096
     m.sessions_set_rates([48000, SR])

@@ -160,6 +160,33 @@ int main()
             return 1;
         rates[3] = 500;
         if (mfx::resample_layout((int32_t)lens.size(), lens.data(), rates.data(), 16000, nullptr, nullptr) != -1) return 1;
+        // the rate-set builder of both planners: the rates the recorded cases use (tests/resample_bits_cases.py), the output rate
+        // among them, mono and stereo; then what it refuses, and the one difference between its callers
+        for (int ch : {1, 2}) {
+            mfx::ResRateSet s;
+            const int32_t to16[] = {48000, 8000, 16000, 44100, 11025, 12345}, to44[] = {44142, 200000, 44100};
+            if (mfx::build_resample_rates(ch, 16000, to16, 6, 0, 0.f, true, s) != 0 || s.rates.size() != 6) return 1;
+            size_t floats = 0;
+            for (const mfx::ResRate &r : s.rates) {
+                if ((r.tile_out == 0) != (&r == &s.rates[2]) || r.tile_out != r.R * r.items || (r.tile_out & 1)) return 1;
+                if (r.tile_out && (r.taps_off != (int64_t)floats || mfx::resample_span_floats(r) > s.lds.x_floats)) return 1;
+                floats += (size_t)r.L * r.P;
+            }
+            if (s.taps.size() != floats || s.lds.taps_floats != 9600 /* 11025 Hz: 640 x 15 */ || (s.lds.x_floats & 7) || (s.lds.out_elems & 1)) return 1;
+            if (s.carry_cap != 48 /* 48000 Hz: 2 x 19 + 3 + 2, up to 8 */ || s.tile_min != 1280 /* 11025 Hz */) return 1;
+            if (mfx::build_resample_rates(ch, 44100, to44, 3, 0, 0.f, false, s) != 0) return 1;
+            if (ch == 1 && mfx::resample_lds_bytes(1, mfx::ResLds{s.rates[0].in_lds ? 15752 : 0, mfx::resample_span_floats(s.rates[0]), 2048}) != 75424) return 1;
+            if (s.rates[1].in_lds || s.rates[1].R != (ch == 2 ? 2 : 4) || s.rates[2].tile_out != 0) return 1;
+        }
+        mfx::ResRateSet s;
+        const int32_t far[] = {8000, 16001}, same[] = {16000};
+        if (mfx::build_resample_rates(1, 16000, far, 2, 0, 0.f, true, s) != 4) return 1;       // L = 16000 > 4096
+        if (mfx::build_resample_rates(1, 16000, far, 1, 65, 0.f, false, s) != 2) return 1;     // zeros
+        if (mfx::build_resample_rates(1, 16000, same, 1, 65, 0.f, true, s) != 2) return 1;     // the sessions judge zeros at the output rate
+        if (mfx::build_resample_rates(1, 16000, same, 1, 65, 0.f, false, s) != 0 || s.taps.size() != 4 || s.tile_min != mfx::kResCopyTile)
+            return 1;                                                                         // a plan does not
+        if (mfx::kResampleWhy[4][0] != 'L' || mfx::kResampleWhy[0][0] != 0) return 1;
+        ++nv;
     }
     // STFT log-mel: exactly-sized basis, Slaney table and operand buffers at the corners of the method's limits
     int ns = 0;
