@@ -49,6 +49,14 @@ from .mfcc import (  # noqa: F401
     VAD_FLAGS,
     VAD_SELECT,
     VAD_PACK,
+    TENSOR_TIME_MAJOR,
+    TENSOR_CHANNEL_MAJOR,
+    DTYPE_F32,
+    DTYPE_F16,
+    DTYPE_BF16,
+    host_tensor_pack,
+    host_tensor_bytes,
+    host_tensor_tile,
     host_traps_basis,
     host_slaney_mel_table,
     host_stft_basis,

@@ -2,7 +2,7 @@
 // attached to it (mfx_batch_attach.cpp) through the device and host entries, the overlap of a batch's tail with the next
 // front end, the pinned allocator.  Which front end runs is choose_front's decision and launch_front's work (mfx_api.cpp).
 // This file owns `batch.ov` and `batch.host`; of the rest of `batch` and of `fuse` it only reads, but for spk.ran, vad.ran, pt.ran,
-// pf.ran and the spectrum slab it grows.  It names no field of `st` or `sweep`.
+// pf.ran (tn.ran is run_tensor's, mfx_batch_attach.cpp) and the spectrum slab it grows.  It names no field of `st` or `sweep`.
 #include "mfx_handle.h"
 
 using namespace mfx;
@@ -104,8 +104,10 @@ struct RunMode {
     FrontKind kind;         // the 512-point register kernel, else the fused wave-per-frame kernel when its LDS fits, else
                             // spectrum through an HBM slab + melcep (per-utterance warp factors in force: always the slab)
     float *d_out, *d_last, *d_final; // where the rows y are built, where the run's last stage before the VAD writes, where
-                            // the caller wants the result: all the same unless a transform (d_out is its scratch) or a
-                            // selecting VAD (d_last is its scratch) is in force
+                            // the finished rows go: all the same unless a transform (d_out is its scratch) or a
+                            // selecting VAD (d_last is its scratch) is in force.  d_final is the caller's array, unless a
+                            // tensor output is in force: then its row scratch, and k_tensor_pack writes the caller's tensor
+    void *d_tensor;         // the caller's array while a tensor output is in force, else null
     float *d_y;             // where the transform and the VAD read the rows y: d_out, unless pitch features are pasted (d_out
                             // is then the scratch of the `width` columns, and k_pitch_paste writes the wide rows to d_y)
     float *d_pre;           // where everything AHEAD of the normaliser's place writes: d_out, unless the online normaliser is
@@ -133,8 +135,11 @@ RunMode decide_mode(const mfx_handle *h, FrontParams &p, float *d_out, bool whol
     // k_splice_affine turns the scratch rows into the caller's array as the last launch.
     // A selecting VAD in force: the last stage writes to the VAD's scratch, and k_vad_select moves the voiced rows from there
     // into the caller's array.
-    m.d_final = d_out;
-    m.d_last = (B.vad.on && B.vad.mode != MFX_VAD_FLAGS) ? B.vad.d_rows.p : d_out;
+    // A tensor output in force: the last link.  The finished rows go to its scratch, and k_tensor_pack turns them into the
+    // caller's tensor.
+    m.d_tensor = B.tn.on ? d_out : nullptr;
+    m.d_final = B.tn.on ? B.tn.d_rows.p : d_out;
+    m.d_last = (B.vad.on && B.vad.mode != MFX_VAD_FLAGS) ? B.vad.d_rows.p : m.d_final;
     m.d_y = B.xf.on ? B.xf.d_y.p : m.d_last;
     m.d_out = B.pf.on && B.pf.paste ? B.pf.d_narrow.p : m.d_y;
     m.d_pre = B.on.on ? B.on.d_raw.p : m.d_out;
@@ -308,6 +313,8 @@ int run_vad(mfx_handle *h, const RunMode &m, int u0, int u1)
     HIP_TRY(h, launch_vad(vp, m.tail_stream));
     v.last_stream = m.tail_stream;
     v.ran = true;
+    if (m.d_tensor) // behind the selection, on its stream: the lengths are this run's counts under MFX_VAD_SELECT
+        return run_tensor(h, m.tail_stream, m.d_final, m.d_tensor, u0, u1, v.mode == MFX_VAD_SELECT);
     return MFX_OK;
 }
 
@@ -362,8 +369,11 @@ int run_tail(mfx_handle *h, const RunMode &m, int u0, int u1)
         xp.tiles_per_seg_max = B.tiles_max;
         HIP_TRY(h, launch_xform(xp, m.tail_stream));
     }
-    if (B.vad.on) { // last of all, on the tail's stream: ev_tail covers it
+    if (B.vad.on) { // last of all (but for the tensor launch at its end), on the tail's stream: ev_tail covers it
         const int rc = run_vad(h, m, u0, u1);
+        if (rc != MFX_OK) return rc;
+    } else if (m.d_tensor) { // the finished rows become the caller's tensor: the last launch, on the tail's stream
+        const int rc = run_tensor(h, m.tail_stream, m.d_final, m.d_tensor, u0, u1, false);
         if (rc != MFX_OK) return rc;
     }
     if (m.split_tail) {
@@ -394,7 +404,9 @@ int batch_run_range(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_tot
         B.vad.ran = B.vad.on; // (nothing to decide: the read-back returns what the setter left, no voiced row)
         B.pt.ran = B.pt.on;   // (no row to track: the read-back copies nothing)
         B.pf.ran = B.pf.on;
-        return MFX_OK;
+        if (!B.tn.on) return MFX_OK;
+        HIP_TRY(h, hipSetDevice(h->device)); // (a tensor of pad values: every element is written on every run)
+        return run_tensor(h, h->stream, B.tn.d_rows.p, d_out, u0, u1, B.vad.on && B.vad.mode == MFX_VAD_SELECT);
     }
     if ((rc = check_layout(h, d_pcm, pcm_samples_total, B.utt_off, B.utt_len, u0, u1)) != MFX_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
@@ -403,15 +415,16 @@ int batch_run_range(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_tot
     if (c1 <= c0) { // a range without a frame: nothing to compute, but the VAD's counts and prefix are still to be written
         B.pt.ran = B.pt.ran || B.pt.on; // (the pitch track has no row to write either)
         B.pf.ran = B.pf.ran || B.pf.on;
-        if (!B.vad.on) return MFX_OK;
         RunMode none{};
-        none.d_last = B.vad.d_rows.p, none.d_final = d_out;
+        none.d_tensor = B.tn.on ? d_out : nullptr;
+        none.d_last = B.vad.d_rows.p, none.d_final = B.tn.on ? B.tn.d_rows.p : d_out;
         none.tail_stream = h->stream;
-        return run_vad(h, none, u0, u1);
+        if (B.vad.on) return run_vad(h, none, u0, u1);
+        return B.tn.on ? run_tensor(h, h->stream, none.d_final, d_out, u0, u1, false) : MFX_OK; // (pad values: every element is written)
     }
     const size_t rows = (size_t)B.total_rows; // (every scratch a launch below writes to holds the plan's rows)
     if ((h->traps && B.d_logmel.n < rows * B.mel_pitch) || !B.xf.sized(rows, batch_y_width(h)) || !B.vad.sized(rows, batch_out_width(h)) ||
-        !B.on.sized(rows, h->width) || !B.pt.sized(rows) || !B.pf.sized(rows, h->width, B.pt.on))
+        !B.on.sized(rows, h->width) || !B.pt.sized(rows) || !B.pf.sized(rows, h->width, B.pt.on) || !B.tn.sized(rows, batch_out_width(h)))
         return fail(h, MFX_ERR_STATE, "batch not planned");
 
     FrontParams p;
@@ -478,7 +491,10 @@ extern "C" int mfx_batch_run_host(mfx_handle *h, const int16_t *pcm, int64_t pcm
     // device-side staging of the host buffers, kept by the handle and grown on demand
     const size_t n_in = (size_t)pcm_samples_total * h->channels;
     const int64_t ow = batch_out_width(h); // floats of an output row
-    const size_t n_out = (size_t)std::max<int64_t>(h->batch.total_rows, 1) * ow;
+    // (a tensor output in force: `out` is the tensor, mfx_batch_output_bytes of it; staged in whole floats)
+    const BatchState::Tensor &tn = h->batch.tn;
+    const int64_t out_bytes = batch_output_bytes(h);
+    const size_t n_out = tn.on ? (size_t)(out_bytes + 3) / 4 + 1 : (size_t)std::max<int64_t>(h->batch.total_rows, 1) * ow;
     if (h->batch.host.d_pcm.n < n_in + 8) HIP_TRY(h, h->batch.host.d_pcm.alloc(n_in + 8));
     if (h->batch.host.d_out.n < n_out) HIP_TRY(h, h->batch.host.d_out.alloc(n_out));
 
@@ -527,6 +543,13 @@ extern "C" int mfx_batch_run_host(mfx_handle *h, const int16_t *pcm, int64_t pcm
             if (rc != MFX_OK) return rc;
             HIP_TRY(h, hipEventRecord(h->batch.host.ev_run[k], h->stream));
             HIP_TRY(h, hipStreamWaitEvent(h->batch.host.stream_dn, h->batch.host.ev_run[k], 0));
+            if (tn.on) { // an utterance's block of the tensor is contiguous in both layouts: the slice's blocks are one piece
+                const int64_t per = (int64_t)tn.Tp * tn.Wo * tensor_elem_bytes(tn.dtype);
+                if (per > 0)
+                    HIP_TRY(h, hipMemcpyAsync((char *)out + u0 * per, (const char *)h->batch.host.d_out.p + u0 * per, (size_t)((u1 - u0) * per),
+                                              hipMemcpyDeviceToHost, h->batch.host.stream_dn));
+                return MFX_OK;
+            }
             const int64_t r0 = h->batch.utt_row[u0], r1 = u1 < h->batch.n_utt ? h->batch.utt_row[u1] : h->batch.total_rows;
             if (r1 > r0)
                 HIP_TRY(h, hipMemcpyAsync(out + r0 * ow, h->batch.host.d_out.p + r0 * ow, (size_t)(r1 - r0) * ow * sizeof(float),
@@ -553,8 +576,7 @@ extern "C" int mfx_batch_run_host(mfx_handle *h, const int16_t *pcm, int64_t pcm
         return rc;
     }
     if (h->batch.ov.stream2) HIP_TRY(h, hipStreamSynchronize(h->batch.ov.stream2)); // overlapped tail, if any
-    if (h->batch.total_rows > 0)
-        HIP_TRY(h, hipMemcpyAsync(out, h->batch.host.d_out.p, (size_t)h->batch.total_rows * ow * sizeof(float), hipMemcpyDeviceToHost,
-                                  h->stream));
+    if (out_bytes > 0) // (total_rows * ow floats, or the tensor)
+        HIP_TRY(h, hipMemcpyAsync(out, h->batch.host.d_out.p, (size_t)out_bytes, hipMemcpyDeviceToHost, h->stream));
     return mfx_synchronize(h);
 }

@@ -1,7 +1,8 @@
 // mfx_batch_attach.cpp -- what a caller attaches to a planned batch (include/mfx.h): per-utterance warp factors, a splice +
 // affine transform, a speaker list, the energy VAD, the online normaliser, the pitch track, the pitch features.  Each is tied
-// to the plan (mfx_batch_plan_rates' converter is the eighth, and is the planner's); BatchState::detach drops the seven of this
-// file.  This file owns `batch.va`, `batch.xf`, `batch.spk`, `batch.vad`, `batch.on`, `batch.pt` and `batch.pf`.
+// to the plan (mfx_batch_plan_rates' converter is the ninth, and is the planner's); BatchState::detach drops the eight of this
+// file: the seven above and the dense tensor output, which is set last.  This file owns `batch.va`, `batch.xf`, `batch.spk`,
+// `batch.vad`, `batch.on`, `batch.pt`, `batch.pf` and `batch.tn`.
 #include "mfx_handle.h"
 
 #include <cmath>
@@ -207,6 +208,7 @@ extern "C" int mfx_batch_set_transform(mfx_handle *h, int32_t left, int32_t righ
                                        const float *b, const int32_t *utt_xf, int32_t n_utt)
 {
     MFX_DEVICE_ENTRY(h);
+    if (h->batch.tn.on) return fail(h, MFX_ERR_STATE, "mfx_batch_set_transform: a tensor output is in force (clear the tensor first)");
     if (!A && n_xf == 0) { // back to the rows the handle delivered before, in the caller's d_out
         if (const int rc = sync_device(h); rc != MFX_OK) return rc; // (a run in flight may read what is released below)
         h->batch.xf.drop();
@@ -275,6 +277,7 @@ extern "C" int mfx_batch_set_vad(mfx_handle *h, int32_t column, float energy_thr
 {
     MFX_DEVICE_ENTRY(h);
     BatchState &B = h->batch;
+    if (B.tn.on) return fail(h, MFX_ERR_STATE, "mfx_batch_set_vad: a tensor output is in force (clear the tensor first)");
     if (!B.planned) return fail(h, MFX_ERR_STATE, "mfx_batch_set_vad: no batch is planned");
     if (column < -1 || column >= h->width) return fail(h, MFX_ERR_ARG, "column must be -1 (the last static column) or inside the row");
     if (frames_context < 0 || frames_context > kVadTileRows) return fail(h, MFX_ERR_ARG, "frames_context must be 0 .. 64");
@@ -310,6 +313,7 @@ extern "C" int mfx_batch_set_vad(mfx_handle *h, int32_t column, float energy_thr
 extern "C" int mfx_batch_clear_vad(mfx_handle *h)
 {
     MFX_DEVICE_ENTRY(h);
+    if (h->batch.tn.on) return fail(h, MFX_ERR_STATE, "mfx_batch_clear_vad: a tensor output is in force (clear the tensor first)");
     if (const int rc = sync_device(h); rc != MFX_OK) return rc; // (a run in flight may read what is released below)
     BatchState::Vad &v = h->batch.vad;
     v.drop();
@@ -403,6 +407,8 @@ extern "C" int mfx_batch_clear_pitch(mfx_handle *h)
     // was sized for)
     if (batch_y_width(h) != h->width && (h->batch.xf.on || h->batch.vad.on))
         return fail(h, MFX_ERR_STATE, "mfx_batch_clear_pitch: pasted pitch features are in force under a transform or a VAD (clear those first)");
+    if (batch_y_width(h) != h->width && h->batch.tn.on)
+        return fail(h, MFX_ERR_STATE, "mfx_batch_clear_pitch: the row width would change under a tensor output (clear the tensor first)");
     if (const int rc = sync_device(h); rc != MFX_OK) return rc; // (a run in flight may read what is released below)
     h->batch.pt.drop();
     h->batch.pt.release();
@@ -456,6 +462,8 @@ extern "C" int mfx_batch_set_pitch_feats(mfx_handle *h, int32_t columns, int32_t
         return fail(h, MFX_ERR_STATE,
                     "mfx_batch_set_pitch_feats: the row width would change under a transform or a VAD (clear them, set the paste, set "
                     "them again)");
+    if (h->width + (paste ? s.F : 0) != batch_y_width(h) && B.tn.on)
+        return fail(h, MFX_ERR_STATE, "mfx_batch_set_pitch_feats: the row width would change under a tensor output (clear the tensor first)");
     if (const int rc = sync_device(h); rc != MFX_OK) return rc; // (a run in flight may read the arrays replaced below)
     BatchState::PitchFeats &pf = B.pf;
     pf.drop();
@@ -486,6 +494,8 @@ extern "C" int mfx_batch_clear_pitch_feats(mfx_handle *h)
     MFX_DEVICE_ENTRY(h);
     if (batch_y_width(h) != h->width && (h->batch.xf.on || h->batch.vad.on))
         return fail(h, MFX_ERR_STATE, "mfx_batch_clear_pitch_feats: the row width would change under a transform or a VAD (clear them first)");
+    if (batch_y_width(h) != h->width && h->batch.tn.on)
+        return fail(h, MFX_ERR_STATE, "mfx_batch_clear_pitch_feats: the row width would change under a tensor output (clear the tensor first)");
     if (const int rc = sync_device(h); rc != MFX_OK) return rc; // (a run in flight may read what is released below)
     h->batch.pf.drop();
     h->batch.pf.release();
@@ -513,4 +523,139 @@ extern "C" int mfx_batch_pitch_feats_device(const mfx_handle *h, const float **d
     if (d_feats) *d_feats = h->batch.pf.d_feats.p;
     if (F) *F = h->batch.pf.F;
     return MFX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// dense padded tensor output ("Tensor output")
+// ------------------------------------------------------------------------------------------------
+
+int64_t batch_output_bytes(const mfx_handle *h)
+{
+    const BatchState &B = h->batch;
+    if (B.tn.on) return tensor_bytes(B.n_utt, B.tn.Wo, B.tn.Tp, B.tn.dtype);
+    return B.total_rows * (int64_t)batch_out_width(h) * (int64_t)sizeof(float);
+}
+
+int run_tensor(mfx_handle *h, hipStream_t stream, const float *rows, void *out, int u0, int u1, bool voiced)
+{
+    BatchState::Tensor &tn = h->batch.tn;
+    TensorParams tp{};
+    tp.rows = rows;
+    tp.out = out;
+    tp.utt = tn.d_utt.p;
+    tp.voiced = voiced ? h->batch.vad.d_voiced.p : nullptr;
+    tp.len = tn.d_len.p;
+    tp.u0 = u0, tp.u1 = u1;
+    tp.Tp = tn.Tp, tp.Wo = tn.Wo;
+    tp.layout = tn.layout, tp.dtype = tn.dtype;
+    tp.pad_value = tn.pad;
+    HIP_TRY(h, launch_tensor_pack(tp, stream));
+    tn.ran = true;
+    return MFX_OK;
+}
+
+extern "C" int mfx_batch_set_tensor(mfx_handle *h, int32_t layout, int32_t dtype, int32_t t_pad, float pad_value)
+{
+    MFX_DEVICE_ENTRY(h);
+    BatchState &B = h->batch;
+    if (!B.planned) return fail(h, MFX_ERR_STATE, "mfx_batch_set_tensor: no batch is planned");
+    if (layout != MFX_TENSOR_TIME_MAJOR && layout != MFX_TENSOR_CHANNEL_MAJOR)
+        return fail(h, MFX_ERR_ARG, "mfx_batch_set_tensor: layout must be MFX_TENSOR_TIME_MAJOR or MFX_TENSOR_CHANNEL_MAJOR");
+    if (dtype != MFX_DTYPE_F32 && dtype != MFX_DTYPE_F16 && dtype != MFX_DTYPE_BF16)
+        return fail(h, MFX_ERR_ARG, "mfx_batch_set_tensor: dtype must be MFX_DTYPE_F32, MFX_DTYPE_F16 or MFX_DTYPE_BF16");
+    if (t_pad < 0 || t_pad > kTensorPadMax) return fail(h, MFX_ERR_ARG, "mfx_batch_set_tensor: t_pad must be 0 .. 2^24");
+    if (B.vad.on && B.vad.mode == MFX_VAD_PACK)
+        return fail(h, MFX_ERR_STATE, "mfx_batch_set_tensor: a packing VAD is in force (packed rows have no per-utterance place)");
+    const int Wo = batch_out_width(h);
+    int64_t Tp = t_pad;
+    if (t_pad == 0)
+        for (int u = 0; u < B.n_utt; ++u) Tp = std::max(Tp, B.utt_frames[u]);
+    TensorParams probe{};
+    probe.u1 = B.n_utt, probe.Tp = (int32_t)std::min<int64_t>(Tp, kTensorPadMax), probe.Wo = Wo, probe.layout = layout, probe.dtype = dtype;
+    if (Tp > kTensorPadMax || tensor_bytes(B.n_utt, Wo, Tp, dtype) < 0) return fail(h, MFX_ERR_ARG, "mfx_batch_set_tensor: the tensor is too large");
+    if (layout == MFX_TENSOR_CHANNEL_MAJOR && tensor_lds_bytes(Wo) > kLdsCap)
+        return fail(h, MFX_ERR_CONFIG, "mfx_batch_set_tensor: no tile of k_tensor_pack fits the LDS at this output width");
+    if (!tensor_params_ok(probe)) return fail(h, MFX_ERR_ARG, "mfx_batch_set_tensor: batch too long");
+    std::vector<TensorUtt> utt((size_t)B.n_utt);
+    std::vector<int32_t> len((size_t)B.n_utt);
+    for (int u = 0; u < B.n_utt; ++u) {
+        utt[u] = TensorUtt{B.utt_row[u], (int32_t)B.utt_frames[u], 0};
+        len[u] = (int32_t)std::min<int64_t>(B.utt_frames[u], Tp);
+    }
+    if (const int rc = sync_device(h); rc != MFX_OK) return rc; // (a run in flight may read the arrays replaced below)
+    BatchState::Tensor &tn = B.tn;
+    tn.drop();
+    // (everything mfx_batch_run_device needs is allocated here: that entry never allocates)
+    auto all = [&]() -> int {
+        HIP_TRY(h, h->upload(tn.d_utt, utt));
+        HIP_TRY(h, h->upload(tn.d_len, len));
+        const size_t need = (size_t)std::max<int64_t>(B.total_rows, 1) * Wo;
+        if (tn.d_rows.n < need) HIP_TRY(h, tn.d_rows.alloc(need));
+        return MFX_OK;
+    };
+    if (const int ra = all(); ra != MFX_OK) { // (it did not fit: nothing of it stays)
+        tn.release();
+        return ra;
+    }
+    tn.layout = layout, tn.dtype = dtype, tn.Tp = (int32_t)Tp, tn.Wo = Wo, tn.pad = pad_value;
+    tn.on = true;
+    return MFX_OK;
+}
+
+extern "C" int mfx_batch_clear_tensor(mfx_handle *h)
+{
+    MFX_DEVICE_ENTRY(h);
+    if (const int rc = sync_device(h); rc != MFX_OK) return rc; // (a run in flight may read what is released below)
+    h->batch.tn.drop();
+    h->batch.tn.release();
+    return MFX_OK;
+}
+
+extern "C" int64_t mfx_batch_output_bytes(const mfx_handle *h)
+{
+    if (!h) return MFX_ERR_ARG;
+    if (h->planning) return MFX_ERR_DEVICE;
+    return batch_output_bytes(h);
+}
+
+extern "C" int mfx_batch_tensor_shape(const mfx_handle *h, int64_t dims[3], int32_t *elem_bytes)
+{
+    if (!h) return MFX_ERR_ARG;
+    if (h->planning) return MFX_ERR_DEVICE;
+    const BatchState::Tensor &tn = h->batch.tn;
+    if (!tn.on) return MFX_ERR_STATE;
+    if (dims) {
+        dims[0] = h->batch.n_utt;
+        dims[1] = tn.layout == MFX_TENSOR_TIME_MAJOR ? tn.Tp : tn.Wo;
+        dims[2] = tn.layout == MFX_TENSOR_TIME_MAJOR ? tn.Wo : tn.Tp;
+    }
+    if (elem_bytes) *elem_bytes = tensor_elem_bytes(tn.dtype);
+    return MFX_OK;
+}
+
+extern "C" int mfx_batch_tensor_lengths(mfx_handle *h, int32_t *len, const int32_t **d_len)
+{
+    MFX_DEVICE_ENTRY(h);
+    const BatchState &B = h->batch;
+    if (!B.tn.on) return fail(h, MFX_ERR_STATE, "mfx_batch_tensor_lengths: no tensor output is in force");
+    if (B.vad.on && B.vad.mode == MFX_VAD_SELECT && !B.tn.ran)
+        return fail(h, MFX_ERR_STATE, "mfx_batch_tensor_lengths: a selecting VAD decides the lengths and no batch has run since the tensor was set");
+    if (const int rc = sync_device(h); rc != MFX_OK) return rc;
+    if (len && B.n_utt > 0) HIP_TRY(h, hipMemcpy(len, B.tn.d_len.p, (size_t)B.n_utt * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (d_len) *d_len = B.tn.d_len.p;
+    return MFX_OK;
+}
+
+extern "C" int mfx_batch_tensor_from_rows(mfx_handle *h, const float *d_rows, void *d_out)
+{
+    MFX_DEVICE_ENTRY(h);
+    const BatchState &B = h->batch;
+    if (!B.tn.on) return fail(h, MFX_ERR_STATE, "mfx_batch_tensor_from_rows: no tensor output is in force");
+    if (B.vad.on) return fail(h, MFX_ERR_STATE, "mfx_batch_tensor_from_rows: a VAD is in force");
+    if (batch_output_bytes(h) == 0) return MFX_OK; // (no element to write)
+    if (!d_rows || !d_out) return fail(h, MFX_ERR_ARG, "invalid argument");
+    if (((uintptr_t)d_rows & 3) != 0 || ((uintptr_t)d_out & (uintptr_t)(tensor_elem_bytes(B.tn.dtype) - 1)) != 0)
+        return fail(h, MFX_ERR_ARG, "mfx_batch_tensor_from_rows: d_rows must be 4-byte aligned and d_out aligned to its element");
+    HIP_TRY(h, hipSetDevice(h->device));
+    return run_tensor(h, h->stream, d_rows, d_out, 0, B.n_utt, false);
 }

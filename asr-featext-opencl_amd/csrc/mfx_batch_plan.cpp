@@ -221,7 +221,7 @@ int plan_batch(mfx_handle *h, int32_t n_utt, const int64_t *offsets, const int64
     }
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->batch.detach(); // (a warp-factor list, a transform's utterance index and scratch, a speaker list, the VAD: tied to the plan)
+    h->batch.detach(); // (a warp-factor list, a transform's utterance index and scratch, a speaker list, the VAD, the tensor output: tied to the plan)
     h->batch.planned = false;
     h->batch.n_utt = n_utt;
     h->batch.utt_off.assign(offsets, offsets + n_utt);

@@ -5,7 +5,7 @@
 //   mfx_stream.cpp the streaming state machine and its host copies         (owns `st` and `sweep`)
 //   mfx_batch_plan.cpp   the batch planner, the rates planner, the fused-delta plan (owns `batch`'s plan, `batch.rs`, `fuse`)
 //   mfx_batch_attach.cpp what is attached to a plan: warp factors, transform, speakers, VAD, online normaliser, pitch track,
-//                        pitch features (owns `batch.va`, `.xf`, `.spk`, `.vad`, `.on`, `.pt`, `.pf`)
+//                        pitch features, tensor output (owns `batch.va`, `.xf`, `.spk`, `.vad`, `.on`, `.pt`, `.pf`, `.tn`)
 //   mfx_batch.cpp        the batch runner, device and host entries, overlap   (owns `batch.ov` and `batch.host`)
 //   mfx_sessions_host.cpp the session entries: many live streams per push       (owns `sess`; the pending push is `sess.push`)
 #pragma once
@@ -209,7 +209,7 @@ struct BatchState {
     int tiles_max = 0;
     bool aligned = true;                 // frames on aligned sample pairs (fill_front / choose_front read it)
 
-    // Eight attachments, each tied to the plan: a new plan drops them.  drop() switches one off and releases what is not kept
+    // Nine attachments, each tied to the plan: a new plan drops them.  drop() switches one off and releases what is not kept
     // for the next one (the grown-never-shrunk scratch stays); release() names every buffer once, for the clear entry (and a
     // setter that ran out of memory); sized() says whether the scratch a run writes to holds the plan's rows (batch_run_range
     // refuses otherwise).
@@ -353,9 +353,24 @@ struct BatchState {
             return !on || (track_on && d_feats.n >= total_rows * F && (!paste || d_narrow.n >= total_rows * width));
         }
     } pf;
+    // dense padded tensor output (mfx_batch_set_tensor; set LAST): while on, the run's last stage -- the VAD's selection
+    // included -- writes its rows to d_rows instead of the caller's array, and k_tensor_pack turns them into the caller's
+    // tensor as the last launch on the tail's stream
+    struct Tensor {
+        bool on = false;
+        bool ran = false;                // a run has written d_len since the setter
+        int32_t layout = 0, dtype = 0, Tp = 0, Wo = 0; // (Wo: the output width the scratch was sized for)
+        float pad = 0.f;
+        DevBuf<float> d_rows;            // [total_rows][Wo] (grown, never shrunk: only mfx_batch_clear_tensor releases it)
+        DevBuf<int32_t> d_len;           // [n_utt] min(L_u, Tp); the setter leaves the plan's values
+        DevBuf<mfx::TensorUtt> d_utt;    // [n_utt] first row and rows of every utterance
+        void drop() { on = false, ran = false; }
+        void release() { d_rows.release(), d_len.release(), d_utt.release(); }
+        bool sized(size_t total_rows, int width) const { return !on || (Wo == width && d_rows.n >= total_rows * width); }
+    } tn;
     // what a new utterance list invalidates (the converter is mfx_batch_plan's to drop: mfx_batch_plan_rates plans through
     // plan_batch too)
-    void detach() { va.drop(), xf.drop(), spk.drop(), vad.drop(), on.drop(), pt.drop(), pf.drop(); }
+    void detach() { va.drop(), xf.drop(), spk.drop(), vad.drop(), on.drop(), pt.drop(), pf.drop(), tn.drop(); }
 
     // ---- not tied to the plan
     // optional overlap of the delta/normalisation tail of batch i with the front end of batch i+1 (mfx_batch_overlap)
@@ -836,3 +851,8 @@ inline void fill_delta(const mfx_handle *h, mfx::DeltaParams &dp)
 inline int sess_out_width(const mfx_handle *h) { return h->sess.xf.set ? h->sess.xf.out : h->width; }
 // the VAD's row scratch at the current output width (mfx_batch_attach.cpp; a no-op unless a selecting VAD is in force)
 int size_vad_rows(mfx_handle *h);
+// bytes a run writes at d_out: the tensor's while one is in force, else total_rows * Wo * 4 (mfx_batch_attach.cpp)
+int64_t batch_output_bytes(const mfx_handle *h);
+// the one launch of k_tensor_pack over utterances [u0, u1): `rows` [total_rows][Wo] -> the tensor at `out`; lengths from the
+// VAD's counts while `voiced` (mfx_batch_attach.cpp)
+int run_tensor(mfx_handle *h, hipStream_t stream, const float *rows, void *out, int u0, int u1, bool voiced);

@@ -1,4 +1,4 @@
-// mfx_kernels.h -- launch interface of the gfx950 kernels (implemented in mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip, mfx_plp.hip, mfx_traps.hip, mfx_xform.hip, mfx_sess_xform.hip, mfx_sess_resample.hip, mfx_sessions.hip, mfx_resample.hip, mfx_speakers.hip, mfx_vad.hip, mfx_onorm.hip, mfx_stft.hip, mfx_stft_fft.hip, mfx_pitch.hip, mfx_pitchfeat.hip: one translation unit per kernel family).
+// mfx_kernels.h -- launch interface of the gfx950 kernels (implemented in mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip, mfx_plp.hip, mfx_traps.hip, mfx_xform.hip, mfx_sess_xform.hip, mfx_sess_resample.hip, mfx_sessions.hip, mfx_resample.hip, mfx_speakers.hip, mfx_vad.hip, mfx_onorm.hip, mfx_stft.hip, mfx_stft_fft.hip, mfx_pitch.hip, mfx_pitchfeat.hip, mfx_tensor.hip: one translation unit per kernel family).
 //
 // Kernel inventory and the reference stage each one replaces:
 //   spectrum512 / fused512   segmenter.cl kernelSegmentWindow + AppleFFT fft0 + mfcc.cl kernelTranspose
@@ -27,6 +27,8 @@
 //                            (one launcher surface and one block tail for both; stft_form(N) of mfx_tables.h says which a length gets)
 //   sess_stft_mel            the same front end over the frames one push of the session entries completes, groups of 16 frames of
 //                            different sessions sharing a block's pass over the basis (no reference analogue)
+//   tensor_pack              the finished rows of a batch run as a dense padded tensor, time- or channel-major, float32 / half / bfloat16
+//                            (no reference analogue: a neural model's input)
 //   delta                    delta.cl kernelDelta x2 + the staging copies of mfccopencl.cpp:360-387
 //   norm_stats / norm_apply  norm.cl kernelSum + kernelFinalizeSum / kernelNormalize
 // What is attached to a planned batch (vad_*, onorm_*, pitch_*, pitch_feats) walks its rows by one work list, UttTiling below.
@@ -511,6 +513,27 @@ struct PitchPasteParams {
     int32_t Wd, F;
 };
 hipError_t launch_pitch_paste(const PitchPasteParams &q, hipStream_t stream);
+
+// Dense padded tensor output (mfx_batch_set_tensor; mfx_tensor.hip; DESIGN.md, "Tensor output").  No work list: a regular grid of
+// (u1 - u0) x ceil(Tp / kTensorTileRows) blocks, block (u, i) owning rows t in [i R, min((i + 1) R, Tp)) of utterance u.
+struct TensorUtt {
+    int64_t row0;          // first row of the utterance in `rows`
+    int32_t T;             // its rows in the plan
+    int32_t pad;
+};
+struct TensorParams {
+    const float *rows;     // the finished rows, [total_rows][Wo]
+    void *out;             // the tensor: [B][Tp][Wo] or [B][Wo][Tp] elements of `dtype`, element-aligned
+    const TensorUtt *utt;  // [B]
+    const int32_t *voiced; // [B] rows that count of every utterance (MFX_VAD_SELECT), or null: TensorUtt::T
+    int32_t *len;          // [B] min(L_u, Tp), written by block (u, 0)
+    int32_t u0, u1;        // the utterance range of this run
+    int32_t Tp, Wo;        // Tp >= 0, 1 <= Wo
+    int32_t layout, dtype; // kTensor*, kDtype* (mfx_tables.h)
+    float pad_value;
+};
+bool tensor_params_ok(const TensorParams &p);
+hipError_t launch_tensor_pack(const TensorParams &p, hipStream_t stream);
 
 // Online CMN / CVN (mfx_batch_set_online_norm, mfx_sessions_set_online_norm; mfx_onorm.hip; DESIGN.md, "Online
 // normalisation").  One utterance tiling at kOnormChunk rows.

@@ -1219,3 +1219,92 @@ extern "C" int mfx_host_online_norm(const float *rows, int64_t T, int32_t pitch,
 {
     return mfx::host_online_norm(rows, T, pitch, Wn, kind, window, prior_frames, prior_count, prior_acc, out) ? 0 : -7 /* MFX_ERR_ARG */;
 }
+
+// ------------------------------------------------------------------------------------------------
+// dense padded tensor output (mfx_batch_set_tensor; DESIGN.md, "Tensor output")
+// ------------------------------------------------------------------------------------------------
+namespace mfx {
+
+int64_t tensor_bytes(int64_t B, int64_t Wo, int64_t Tp, int dtype)
+{
+    if (B < 0 || Wo < 0 || Tp < 0 || Tp > kTensorPadMax || dtype < kDtypeF32 || dtype > kDtypeBf16) return -1;
+    int64_t n = 0;
+    if (__builtin_mul_overflow(B, Tp, &n) || __builtin_mul_overflow(n, Wo, &n) ||
+        __builtin_mul_overflow(n, (int64_t)tensor_elem_bytes(dtype), &n))
+        return -1;
+    return n;
+}
+
+uint16_t f32_to_f16_bits(uint32_t u)
+{
+    const uint32_t sign = (u >> 16) & 0x8000u, a = u & 0x7fffffffu;
+    if (a > 0x7f800000u) return (uint16_t)(sign | 0x7e00u | ((a >> 13) & 0x3ffu)); // NaN, made quiet
+    if (a >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u); // 65520 and above (inf included) round to inf
+    if (a >= 0x38800000u) { // normal result: 2^-14 and above
+        const uint32_t v = a - 0x38000000u; // exponent rebiased; a carry out of the mantissa moves into it
+        return (uint16_t)(sign | ((v + 0xfffu + ((v >> 13) & 1u)) >> 13));
+    }
+    if (a < 0x33000000u) return (uint16_t)sign; // below 2^-25: zero (2^-25 itself is a tie to even: zero, handled below)
+    // subnormal result: the 24-bit significand shifted down to units of 2^-24
+    const uint32_t e = a >> 23, m = (a & 0x7fffffu) | 0x800000u;
+    const uint32_t sh = 126u - e; // 14 .. 24
+    const uint32_t q = m >> sh, rem = m & ((1u << sh) - 1u), half = 1u << (sh - 1);
+    return (uint16_t)(sign | (q + ((rem > half || (rem == half && (q & 1u))) ? 1u : 0u)));
+}
+
+uint16_t f32_to_bf16_bits(uint32_t u)
+{
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u); // NaN, made quiet
+    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16); // (a carry runs through the exponent: overflow gives inf)
+}
+
+bool tensor_pack_host(const float *rows, const int64_t *out_rows, const int32_t *lengths, int64_t B, int Wo, int64_t Tp, int layout,
+                      int dtype, float pad, void *out)
+{
+    const int64_t bytes = tensor_bytes(B, Wo, Tp, dtype);
+    if (bytes < 0 || Wo < 1 || (layout != kTensorTimeMajor && layout != kTensorChannelMajor)) return false;
+    if (bytes == 0) return true;
+    if (!out || !out_rows || !lengths) return false;
+    for (int64_t u = 0; u < B; ++u)
+        if (lengths[u] < 0 || out_rows[u] < 0 || (!rows && lengths[u] > 0 && Tp > 0)) return false;
+    auto put = [&](int64_t idx, float v) {
+        uint32_t bits;
+        std::memcpy(&bits, &v, 4);
+        if (dtype == kDtypeF32)
+            std::memcpy((char *)out + idx * 4, &bits, 4);
+        else {
+            const uint16_t s = dtype == kDtypeF16 ? f32_to_f16_bits(bits) : f32_to_bf16_bits(bits);
+            std::memcpy((char *)out + idx * 2, &s, 2);
+        }
+    };
+    for (int64_t u = 0; u < B; ++u) {
+        const int64_t len = std::min<int64_t>(lengths[u], Tp);
+        for (int64_t t = 0; t < Tp; ++t)
+            for (int64_t c = 0; c < Wo; ++c) {
+                const float v = t < len ? rows[(out_rows[u] + t) * Wo + c] : pad;
+                put(layout == kTensorTimeMajor ? (u * Tp + t) * Wo + c : (u * Wo + c) * Tp + t, v);
+            }
+    }
+    return true;
+}
+
+} // namespace mfx
+
+extern "C" int64_t mfx_host_tensor_bytes(int64_t B, int32_t Wo, int64_t Tp, int32_t dtype)
+{
+    const int64_t n = mfx::tensor_bytes(B, Wo, Tp, dtype);
+    return n < 0 ? -7 /* MFX_ERR_ARG */ : n;
+}
+
+extern "C" int mfx_host_tensor_pack(const float *rows, const int64_t *out_rows, const int32_t *lengths, int64_t B, int32_t Wo, int64_t Tp,
+                                    int32_t layout, int32_t dtype, float pad, void *out)
+{
+    return mfx::tensor_pack_host(rows, out_rows, lengths, B, Wo, Tp, layout, dtype, pad, out) ? 0 : -7 /* MFX_ERR_ARG */;
+}
+
+extern "C" int64_t mfx_host_tensor_lds_bytes(int32_t Wo, int32_t *tile_rows)
+{
+    if (Wo < 1) return -7 /* MFX_ERR_ARG */;
+    if (tile_rows) *tile_rows = mfx::kTensorTileRows;
+    return (int64_t)mfx::tensor_lds_bytes(Wo);
+}

@@ -176,6 +176,31 @@ bool pitch_feat_shape(int columns, int left, int right, int delta_window, float 
 bool host_pitch_feats(const float *pitch, int64_t T, float sample_rate, int columns, int left, int right, int delta_window,
                       float pov_scale, float pov_offset, float pitch_scale, float delta_scale, float *feats);
 
+// Dense padded tensor output (mfx_batch_set_tensor; DESIGN.md, "Tensor output").  Layouts and element types are the MFX_TENSOR_*
+// and MFX_DTYPE_* values of include/mfx.h.
+#ifndef MFX_TENSOR_TILE_ROWS // (a dev build may pass -DMFX_TENSOR_TILE_ROWS=128 to measure the other size)
+#define MFX_TENSOR_TILE_ROWS 64
+#endif
+constexpr int kTensorTileRows = MFX_TENSOR_TILE_ROWS; // rows t of one utterance per block of k_tensor_pack: 64 or 128
+constexpr int kTensorTimeMajor = 0, kTensorChannelMajor = 1;
+constexpr int kDtypeF32 = 0, kDtypeF16 = 1, kDtypeBf16 = 2;
+constexpr int kTensorPadMax = 1 << 24; // largest t_pad
+inline int tensor_elem_bytes(int dtype) { return dtype == kDtypeF32 ? 4 : 2; }
+// LDS bytes of a block of k_tensor_pack: the CHANNEL_MAJOR image of kTensorTileRows rows at the odd pitch Wo | 1 dwords
+// (TIME_MAJOR uses none)
+inline size_t tensor_lds_bytes(int Wo) { return (size_t)kTensorTileRows * (size_t)(Wo | 1) * sizeof(float); }
+// bytes of the tensor [B][Tp][Wo]; -1 on a negative size, an unknown dtype, Tp > kTensorPadMax or a product beyond int64
+int64_t tensor_bytes(int64_t B, int64_t Wo, int64_t Tp, int dtype);
+// float32 -> IEEE binary16 / bfloat16 bits, roundTiesToEven in integer arithmetic: overflow to inf, subnormals produced, the sign
+// of zero kept, a NaN stays a NaN (quiet, the payload's top bits)
+uint16_t f32_to_f16_bits(uint32_t u);
+uint16_t f32_to_bf16_bits(uint32_t u);
+// The definition of include/mfx.h on host memory: rows [.][Wo] with utterance u's rows from out_rows[u] on, lengths[u] = L_u
+// (any value >= 0: cut at Tp) -> the tensor at `out`, tensor_bytes of it, every element written.  False -- and nothing written
+// -- on an argument outside the limits.
+bool tensor_pack_host(const float *rows, const int64_t *out_rows, const int32_t *lengths, int64_t B, int Wo, int64_t Tp, int layout,
+                      int dtype, float pad, void *out);
+
 // exp(-2*pi*i*k/n) for k in [0, count), evaluated in double and rounded once to float.
 void build_twiddles(int n, int count, std::vector<float> &re_im_interleaved);
 

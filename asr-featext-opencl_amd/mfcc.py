@@ -93,6 +93,9 @@ EXPORTED_SYMBOLS = (
     "mfx_batch_set_pitch", "mfx_batch_clear_pitch", "mfx_batch_pitch_read", "mfx_batch_pitch_device", "mfx_host_pitch",
     "mfx_batch_set_pitch_feats", "mfx_batch_clear_pitch_feats", "mfx_batch_pitch_feats_read", "mfx_batch_pitch_feats_device",
     "mfx_host_pitch_feats",
+    "mfx_batch_set_tensor", "mfx_batch_clear_tensor", "mfx_batch_output_bytes", "mfx_batch_tensor_shape",
+    "mfx_batch_tensor_lengths", "mfx_batch_tensor_from_rows",
+    "mfx_host_tensor_pack", "mfx_host_tensor_bytes", "mfx_host_tensor_lds_bytes",
 )
 
 
@@ -229,6 +232,15 @@ def load_library():
     L.mfx_batch_pitch_feats_read.argtypes = [vp, fp]
     L.mfx_batch_pitch_feats_device.argtypes = [vp, C.POINTER(vp), p32]
     L.mfx_host_pitch_feats.argtypes = [fp, i64, C.c_float, i32, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, fp]
+    L.mfx_batch_set_tensor.argtypes = [vp, i32, i32, i32, C.c_float]
+    L.mfx_batch_clear_tensor.argtypes = [vp]
+    L.mfx_batch_output_bytes.argtypes, L.mfx_batch_output_bytes.restype = [vp], i64
+    L.mfx_batch_tensor_shape.argtypes = [vp, C.POINTER(i64), C.POINTER(i32)]
+    L.mfx_batch_tensor_lengths.argtypes = [vp, C.POINTER(i32), C.POINTER(vp)]
+    L.mfx_batch_tensor_from_rows.argtypes = [vp, vp, vp]
+    L.mfx_host_tensor_pack.argtypes = [fp, C.POINTER(i64), C.POINTER(i32), i64, i32, i64, i32, i32, C.c_float, vp]
+    L.mfx_host_tensor_bytes.argtypes, L.mfx_host_tensor_bytes.restype = [i64, i32, i64, i32], i64
+    L.mfx_host_tensor_lds_bytes.argtypes, L.mfx_host_tensor_lds_bytes.restype = [i32, C.POINTER(i32)], i64
     _lib = L
     return L
 
@@ -391,6 +403,50 @@ def host_online_norm(rows, kind, window=0, prior_frames=0, prior_count=0, prior_
                                 None if pa is None else pa.ctypes.data_as(C.POINTER(C.c_double)), out.ctypes.data_as(fpt))
     if rc != 0:
         raise MfxError(int(rc), "mfx_host_online_norm failed")
+    return out
+
+
+TENSOR_TIME_MAJOR, TENSOR_CHANNEL_MAJOR = 0, 1            # mfx_batch_set_tensor layouts (include/mfx.h)
+DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2                 # ... and element types
+_TENSOR_NP = {DTYPE_F32: np.float32, DTYPE_F16: np.float16, DTYPE_BF16: np.uint16}   # (numpy has no bfloat16: its bits)
+
+
+def host_tensor_bytes(B, Wo, Tp, dtype):
+    """Bytes of the tensor of batch_set_tensor: B * Tp * Wo elements of dtype (host code, no GPU needed)."""
+    n = int(load_library().mfx_host_tensor_bytes(int(B), int(Wo), int(Tp), int(dtype)))
+    if n < 0:
+        raise MfxError(n, "mfx_host_tensor_bytes failed")
+    return n
+
+
+def host_tensor_tile():
+    """(rows t per block of k_tensor_pack, a function Wo -> the LDS bytes of a CHANNEL_MAJOR block).  UNSTABLE: tests only."""
+    L = load_library()
+    r = C.c_int32(0)
+    L.mfx_host_tensor_lds_bytes(1, C.byref(r))
+    return int(r.value), (lambda Wo: int(L.mfx_host_tensor_lds_bytes(int(Wo), None)))
+
+
+def host_tensor_pack(rows, out_rows, lengths, Tp, layout, dtype, pad=0.0):
+    """The tensor of batch_set_tensor on host memory, exactly as include/mfx.h defines it, conversions in integer arithmetic
+    (host code, no GPU needed): rows [.][Wo] float32, utterance u's from row out_rows[u] on, lengths[u] of them counting (cut
+    at Tp).  Returns [B][Tp][Wo] (TENSOR_TIME_MAJOR) or [B][Wo][Tp] as float32 / float16 / uint16 (the bits of bfloat16)."""
+    L = load_library()
+    x = np.ascontiguousarray(rows, dtype=np.float32)
+    if x.ndim != 2:
+        raise ValueError("rows must be [.][Wo]")
+    Wo = x.shape[1]
+    r0 = np.ascontiguousarray(out_rows, dtype=np.int64)
+    ln = np.ascontiguousarray(lengths, dtype=np.int32)
+    B, Tp = int(r0.size), int(Tp)
+    if ln.size != B or int(dtype) not in _TENSOR_NP:
+        raise ValueError("one length per utterance, dtype one of DTYPE_*")
+    out = np.zeros((B, Tp, Wo) if int(layout) == TENSOR_TIME_MAJOR else (B, Wo, Tp), _TENSOR_NP[int(dtype)])
+    rc = L.mfx_host_tensor_pack(x.ctypes.data_as(C.POINTER(C.c_float)), r0.ctypes.data_as(C.POINTER(C.c_int64)),
+                                ln.ctypes.data_as(C.POINTER(C.c_int32)), B, Wo, Tp, int(layout), int(dtype), float(pad),
+                                C.c_void_p(out.ctypes.data))
+    if rc != 0:
+        raise MfxError(int(rc), "mfx_host_tensor_pack failed")
     return out
 
 
@@ -917,12 +973,68 @@ class MfccHip:
                                                C.c_void_p(int(d_out_ptr))))
 
     def batch_run_host(self, pcm):
+        """The planned batch from host PCM: the ragged rows [total_rows][batch_output_width()] float32, or, while a tensor
+        output is in force (batch_set_tensor), an array of the tensor's shape and type (bfloat16 as uint16 bits)."""
         pcm = np.ascontiguousarray(pcm, dtype=np.int16)
         total = pcm.size // max(self.cfg.channels, 1)
-        out = np.zeros((self._plan_total, self.batch_output_width()), dtype=np.float32)
+        shape = self.batch_tensor_shape()
+        if shape is None:
+            out = np.zeros((self._plan_total, self.batch_output_width()), dtype=np.float32)
+        else:
+            out = np.zeros(shape[0], dtype=shape[1])
         self._chk(self._L.mfx_batch_run_host(self._h, pcm.ctypes.data_as(C.POINTER(C.c_int16)), total,
-                                             out.ctypes.data_as(C.POINTER(C.c_float))))
+                                             C.cast(C.c_void_p(out.ctypes.data), C.POINTER(C.c_float))))
         return out
+
+    host_tensor_pack = staticmethod(host_tensor_pack)
+    host_tensor_bytes = staticmethod(host_tensor_bytes)
+
+    def batch_set_tensor(self, layout=TENSOR_TIME_MAJOR, dtype=DTYPE_F32, t_pad=0, pad_value=0.0):
+        """Dense padded tensor output of a batch run (mfx_batch_set_tensor; set it LAST, behind the transform, the pitch
+        features and the VAD): d_out becomes [B][Tp][Wo] (TENSOR_TIME_MAJOR) or [B][Wo][Tp] (TENSOR_CHANNEL_MAJOR) of
+        DTYPE_F32 / DTYPE_F16 / DTYPE_BF16, Tp = t_pad or the plan's longest utterance, longer utterances cut, shorter ones
+        padded with pad_value; every element is written on every run.  A later batch_plan clears it."""
+        self._chk(self._L.mfx_batch_set_tensor(self._h, int(layout), int(dtype), int(t_pad), float(pad_value)))
+        self._tensor_dtype = int(dtype)
+
+    def batch_clear_tensor(self):
+        self._chk(self._L.mfx_batch_clear_tensor(self._h))
+
+    def batch_output_bytes(self):
+        """Bytes a batch run writes at d_out: the tensor's while one is in force, else total_rows * batch_output_width() * 4."""
+        n = int(self._L.mfx_batch_output_bytes(self._h))
+        if n < 0:
+            self._chk(n)
+        return n
+
+    def batch_tensor_shape(self):
+        """((B, Tp, Wo) or (B, Wo, Tp), numpy dtype) of the tensor output in force (bfloat16: uint16), else None."""
+        dims, eb = (C.c_int64 * 3)(), C.c_int32(0)
+        rc = self._L.mfx_batch_tensor_shape(self._h, dims, C.byref(eb))
+        if rc == -8:
+            return None
+        self._chk(rc)
+        dt = np.float32 if eb.value == 4 else _TENSOR_NP[getattr(self, "_tensor_dtype", DTYPE_F16)]
+        return (int(dims[0]), int(dims[1]), int(dims[2])), dt
+
+    def batch_tensor_lengths(self):
+        """len [B] int32 = min(L_u, Tp) of the tensor output in force (synchronises; MfxError with status -8 without one, or
+        before a run when a selecting VAD decides the lengths)."""
+        n = 0 if self._plan_rows is None else self._plan_rows.size
+        ln = np.zeros(n, np.int32)
+        self._chk(self._L.mfx_batch_tensor_lengths(self._h, ln.ctypes.data_as(C.POINTER(C.c_int32)), None))
+        return ln
+
+    def batch_tensor_lengths_device(self):
+        """Device address of the handle-owned len [B] int32 (synchronises, as batch_tensor_lengths)."""
+        a = C.c_void_p()
+        self._chk(self._L.mfx_batch_tensor_lengths(self._h, None, C.byref(a)))
+        return a.value or 0
+
+    def batch_tensor_from_rows(self, d_rows_ptr, d_out_ptr):
+        """The tensor launch alone (mfx_batch_tensor_from_rows): device rows [total_rows][Wo] float32 in the plan's row order
+        -> the tensor at d_out_ptr; asynchronous on the handle's stream."""
+        self._chk(self._L.mfx_batch_tensor_from_rows(self._h, C.c_void_p(int(d_rows_ptr)), C.c_void_p(int(d_out_ptr))))
 
     def batch_set_alphas(self, alphas):
         """One VTLN warp factor per utterance of the planned batch (float32 array, plan order); None clears the list.

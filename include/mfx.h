@@ -615,6 +615,60 @@ int mfx_batch_clear_pitch_feats(mfx_handle *h);
 int mfx_batch_pitch_feats_read(mfx_handle *h, float *feats /* [total_rows][F] */);
 int mfx_batch_pitch_feats_device(const mfx_handle *h, const float **d_feats, int32_t *F);
 
+/* Dense padded tensor output of a batch run ("Tensor output"): what pad_sequence, a transpose and a cast to half
+ * or bfloat16 make of the ragged rows, written by one launch as the last stage of the run.  No reference analogue: a neural
+ * model's input.
+ *   Definition.  B = the planned utterance count; Wo = mfx_batch_output_width (out_dim under a transform, the wide rows under
+ *     a pitch paste); y_u[t][c] = what the run delivers today at row out_rows[u] + t, behind everything, the transform and the
+ *     VAD included.  L_u = T_u, the plan's frame count; under MFX_VAD_SELECT, voiced[u] of this run.  Tp = t_pad when t_pad > 0,
+ *     else the largest T_u of the whole plan: fixed when the setter is called; it may be 0.  len_u = min(L_u, Tp): a longer
+ *     utterance is cut to its first Tp rows.  Element (u, t, c) = cvt(y_u[t][c]) for t < len_u, else cvt(pad_value), at index
+ *       MFX_TENSOR_TIME_MAJOR     (u * Tp + t) * Wo + c      the tensor is [B][Tp][Wo]
+ *       MFX_TENSOR_CHANNEL_MAJOR  (u * Wo + c) * Tp + t      the tensor is [B][Wo][Tp]
+ *     in 64-bit arithmetic.
+ *   Conversion.  MFX_DTYPE_F32 delivers the bits as they are.  MFX_DTYPE_F16 (IEEE binary16) and MFX_DTYPE_BF16 round to
+ *     nearest, ties to even (IEEE 754 roundTiesToEven): overflow gives +-inf, results in the subnormal range are produced, not
+ *     flushed, the sign of zero is kept, a NaN becomes a NaN (its payload is not pinned).
+ *   Write guarantee.  Every element of the tensor is written on every run: the caller never has to clear it.  Nothing outside
+ *     [d_out, d_out + mfx_batch_output_bytes) is written.  d_out needs only the alignment of the element (4, 2 or 2 bytes); the
+ *     bits are the same wherever it lies and on a second run.
+ *   Whisper.  A Whisper encoder wants [80][3000] from audio zero-padded to 30 s.  A constant pad value does not reproduce that
+ *     (MFX_LOGMEL_WHISPER's clamp follows the utterance's maximum, and the last frames reflect the audio's right end): callers
+ *     who need exactly that pad the AUDIO.  Everyone else -- conformer / wav2vec-style front ends, vocoders, taggers -- pads the
+ *     features.
+ *   Scope.  Valid after mfx_batch_plan / mfx_batch_plan_rates (MFX_ERR_STATE before one); a later plan drops the tensor with the
+ *     other attachments, and mfx_batch_clear_tensor puts the handle back on today's launches and bits.  MFX_ERR_DEVICE on a
+ *     planning handle, before any argument is looked at (all entries below).  MFX_ERR_ARG: an unknown layout or dtype, t_pad
+ *     outside 0 .. 2^24 (or, with t_pad = 0, a T_u beyond it).  pad_value is not inspected.  MFX_ERR_CONFIG: CHANNEL_MAJOR at an
+ *     output width whose tile does not fit the LDS (never at Wo <= 256): there is never a failed launch.
+ *     The tensor is set LAST: while it is in force mfx_batch_set_transform, mfx_batch_set_vad, mfx_batch_clear_vad and the
+ *     pitch-feats calls that would change the row width answer MFX_ERR_STATE ("clear the tensor first").  The setter itself
+ *     answers MFX_ERR_STATE under MFX_VAD_PACK: packed rows have no per-utterance place.  A float32 scratch [total_rows][Wo]
+ *     that the run's last stage writes in the place of d_out (grown, never shrunk), len [B] and the utterance table k_tensor_pack
+ *     reads are allocated HERE (the call waits for the handle's streams); mfx_batch_run_device still allocates nothing.
+ *   Composition.  Everything else in a run is unchanged -- front end, MFX_ENGINE_* bits, alpha list, rates plan, speakers,
+ *     online normaliser, pitch, mfx_batch_overlap.  The one launch of k_tensor_pack goes on the stream the tail runs on, as the
+ *     transform and the VAD do.  mfx_batch_run_device's d_out is then the tensor (the float pointer is a formality), and so is
+ *     mfx_batch_run_host's out: mfx_batch_output_bytes of it.  The host entry keeps its sliced path: an utterance's block of the
+ *     tensor is contiguous in both layouts.
+ *   Read-back.  mfx_batch_output_bytes: what a run writes at d_out -- the tensor's bytes, else total_rows * Wo * 4.
+ *     mfx_batch_tensor_shape: dims = {B, Tp, Wo} or {B, Wo, Tp} and the element's bytes (MFX_ERR_STATE without a tensor).
+ *     mfx_batch_tensor_lengths synchronises and returns len [B] and / or the handle-owned device array (valid until the next plan,
+ *     set or clear; written by the run, ordered as mfx_batch_vad_device's arrays are): MFX_ERR_STATE without a tensor, or before
+ *     a run when a selecting VAD decides the lengths.
+ *   A second format.  mfx_batch_tensor_from_rows queues the one launch alone, on the handle's stream, over the caller's device
+ *     rows [total_rows][Wo] in the plan's row order (4-byte aligned), with L_u = T_u: a second layout or type from rows the
+ *     caller already has.  MFX_ERR_STATE without a tensor or while a VAD is in force.
+ * NOT served: the session entries (mfx_sessions_*) and the streaming interface ignore the attachment. */
+enum { MFX_TENSOR_TIME_MAJOR = 0 /* [B][Tp][Wo] */, MFX_TENSOR_CHANNEL_MAJOR = 1 /* [B][Wo][Tp] */ };
+enum { MFX_DTYPE_F32 = 0, MFX_DTYPE_F16 = 1, MFX_DTYPE_BF16 = 2 };
+int mfx_batch_set_tensor(mfx_handle *h, int32_t layout, int32_t dtype, int32_t t_pad, float pad_value);
+int mfx_batch_clear_tensor(mfx_handle *h);
+int64_t mfx_batch_output_bytes(const mfx_handle *h);      /* what a run writes at d_out: tensor bytes, else total_rows * Wo * 4 */
+int mfx_batch_tensor_shape(const mfx_handle *h, int64_t dims[3], int32_t *elem_bytes);
+int mfx_batch_tensor_lengths(mfx_handle *h, int32_t *len /* [B] or NULL */, const int32_t **d_len /* or NULL */);
+int mfx_batch_tensor_from_rows(mfx_handle *h, const float *d_rows, void *d_out);
+
 /* ---- sample-rate conversion in front of a batch ("Sample-rate conversion").  No reference analogue: the
  *      reference refuses a file whose rate differs from the first file's (ASR_OCL.cpp:191). ----
  *
@@ -939,6 +993,16 @@ int mfx_host_pitch(const int16_t *pcm, int64_t n, int32_t channels, int64_t T, i
 int mfx_host_pitch_feats(const float *pitch /* [T][2]: lag, rho */, int64_t T, float sample_rate, int32_t columns, int32_t left,
                          int32_t right, int32_t delta_window, float pov_scale, float pov_offset, float pitch_scale,
                          float delta_scale, float *feats /* [T][F] */);
+/* The tensor output (mfx_batch_set_tensor) on host memory, exactly as defined there, with both conversions in integer
+ * arithmetic: rows [.][Wo], utterance u's from row out_rows[u] on, lengths[u] = L_u (cut at Tp) -> out, mfx_host_tensor_bytes
+ * of it, every element written.  mfx_host_tensor_bytes: B * Tp * Wo elements of dtype in bytes.  Both: MFX_ERR_ARG on a
+ * negative size, Wo < 1 (pack), Tp > 2^24, an unknown layout or dtype, a product beyond int64 (nothing is written then).
+ * mfx_host_tensor_lds_bytes: the LDS bytes a block of k_tensor_pack asks for in CHANNEL_MAJOR at this width and the rows t a
+ * block owns (*tile_rows); UNSTABLE, a test / inspection aid only, as mfx_host_stft_lds_bytes. */
+int mfx_host_tensor_pack(const float *rows, const int64_t *out_rows /* [B] */, const int32_t *lengths /* [B] */, int64_t B,
+                         int32_t Wo, int64_t Tp, int32_t layout, int32_t dtype, float pad, void *out);
+int64_t mfx_host_tensor_bytes(int64_t B, int32_t Wo, int64_t Tp, int32_t dtype);
+int64_t mfx_host_tensor_lds_bytes(int32_t Wo, int32_t *tile_rows);
 /* frame count, integer arithmetic (parambase.cpp:16-19 without the float32 division) */
 int64_t mfx_host_frame_count(int64_t samples, int32_t window_size, int32_t shift);
 /* STFT log-mel (MFX_METHOD_STFT_LOGMEL) tables as uploaded, and its frame rule.  mfx_host_slaney_mel_table: weights
