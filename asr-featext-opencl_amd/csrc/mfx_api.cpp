@@ -6,6 +6,7 @@
 // arithmetic on tables in mfx_tables.cpp.  There is deliberately no CPU compute path in these three files.
 #include "mfx_handle.h"
 
+#include <cmath>
 #include <cstring>
 #include <memory>
 
@@ -112,7 +113,7 @@ int build_cep_tables(mfx_handle *h, const float *alphas, int n, CepTables &t, Me
 // own lane plans are derived here too.
 int refresh_mel(mfx_handle *h)
 {
-    if (h->stft) return MFX_OK; // (its one table does not depend on alpha)
+    if (h->stft || h->kaldi) return MFX_OK; // (its one table does not depend on alpha)
     if (h->own.holds(&h->alpha, 1)) return MFX_OK;
     h->plan16.ok = h->plan32.ok = false;
     MelTable t;
@@ -313,7 +314,10 @@ int launch_cepstra_runs(mfx_handle *h, const CepTables &t, const float *spec, fl
 extern "C" int mfx_abi_version(void) { return MFX_ABI_VERSION; }
 extern "C" int mfx_method_supported(int32_t method)
 {
-    return method == MFX_METHOD_MFCC || method == MFX_METHOD_PLP || method == MFX_METHOD_TRAPS || method == MFX_METHOD_STFT_LOGMEL ? 1 : 0;
+    return method == MFX_METHOD_MFCC || method == MFX_METHOD_PLP || method == MFX_METHOD_TRAPS || method == MFX_METHOD_STFT_LOGMEL ||
+                   method == MFX_METHOD_KALDI
+               ? 1
+               : 0;
 }
 
 extern "C" const char *mfx_status_string(int status)
@@ -404,6 +408,54 @@ int create_stft(mfx_handle *h, bool planning, std::unique_ptr<mfx_handle, Handle
     return MFX_OK;
 }
 
+// the limits of a Kaldi handle (include/mfx.h): everything sized from W, S, M and C fits the kernel's LDS by them
+bool kaldi_config_ok(const mfx_config *cfg)
+{
+    const int W = cfg->window_size;
+    if (!kaldi_shape_ok(W, cfg->shift, cfg->num_banks, cfg->ceps_len) || (cfg->fft_size != 0 && cfg->fft_size != kaldi_fft_size(W))) return false;
+    if (!kaldi_freqs_ok(cfg->sample_rate, cfg->low_freq, cfg->high_freq)) return false;
+    if (cfg->want_c0 != 0 || cfg->channels > 1 || !(cfg->lift_coef >= 0.f) || !std::isfinite(cfg->lift_coef)) return false;
+    return kaldi_lds_bytes(W, cfg->shift, cfg->num_banks, cfg->ceps_len) <= kLdsCap;
+}
+
+// the rest of mfx_create for a Kaldi handle: geometry, the mel table and G, what the normalisers of both interfaces share; the
+// window and the FFT tables wait for mfx_set_window
+int create_kaldi(mfx_handle *h, bool planning, std::unique_ptr<mfx_handle, HandleDeleter> &owner, mfx_handle **out)
+{
+    const mfx_config &cfg = h->cfg;
+    h->W2 = kaldi_fft_size(h->W);
+    h->input_window_limit = estimated_window_count_f32(cfg.input_buffer_size, h->W, h->S);
+    h->input_buffer_size = h->input_window_limit * h->S + h->W - h->S;
+    h->window_limit = h->input_window_limit + 2 + (cfg.dyn != MFX_DYN_NONE ? 3 * h->D : 0);
+    if (h->input_window_limit <= 0) return MFX_ERR_CONFIG;
+    h->cap_rows = h->window_limit + h->W / h->S + 4;
+    h->spec_pitch = ((h->W2 / 2 + 1) + 3) & ~3;
+    if (!planning) {
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.multiProcessorCount > 0) h->num_cus = prop.multiProcessorCount;
+        if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return MFX_ERR_DEVICE;
+        h->own_stream = true;
+    }
+    double high = 0.0;
+    (void)kaldi_freqs_ok(cfg.sample_rate, cfg.low_freq, cfg.high_freq, &high);
+    std::vector<float> w, gt;
+    std::vector<int32_t> meta;
+    build_kaldi_spans(h->nb, h->W2, cfg.sample_rate, cfg.low_freq, high, w, meta);
+    if (w.size() > (size_t)h->W2) return MFX_ERR_CONFIG; // (a bin lies in two bands at most: the kernel keeps N weights in LDS)
+    if (h->ceps > 0) { // G [C][M] -> [M][C]: the cepstra's threads read one band's row together
+        std::vector<float> g((size_t)h->ceps * h->nb);
+        build_kaldi_dct(h->nb, h->ceps, cfg.lift_coef, g.data());
+        gt.resize(g.size());
+        for (int i = 0; i < h->ceps; ++i)
+            for (int m = 0; m < h->nb; ++m) gt[(size_t)m * h->ceps + i] = g[(size_t)i * h->nb + m];
+    }
+    if (h->upload(h->d_kaldi_melw, w) != hipSuccess || h->upload(h->d_kaldi_mel, meta) != hipSuccess || h->upload(h->d_kaldi_dct_t, gt) != hipSuccess ||
+        h->alloc(h->st.d_stats, (size_t)3 * 2 * h->cols) != hipSuccess)
+        return MFX_ERR_DEVICE;
+    *out = owner.release();
+    return MFX_OK;
+}
+
 int create_impl(const mfx_config *cfg, int hip_device, bool planning, mfx_handle **out)
 {
     if (!cfg || !out) return MFX_ERR_ARG;
@@ -412,7 +464,8 @@ int create_impl(const mfx_config *cfg, int hip_device, bool planning, mfx_handle
         cfg->sample_rate <= 0 || cfg->norm < 0 || cfg->norm > 3 || cfg->dyn < 0 || cfg->dyn > 2 ||
         cfg->channels < 0 || cfg->channels > 2)
         return MFX_ERR_CONFIG;
-    if (cfg->ceps_len > 0 && cfg->lift_coef == 0.f) return MFX_ERR_CONFIG; // reference divides by lift_coef
+    const bool kaldi = cfg->method == MFX_METHOD_KALDI; // (its lifter Q = 0 means none)
+    if (cfg->ceps_len > 0 && cfg->lift_coef == 0.f && !kaldi) return MFX_ERR_CONFIG; // reference divides by lift_coef
     if (cfg->dyn != MFX_DYN_NONE && cfg->delta_l1 <= 0) return MFX_ERR_CONFIG;
     if (cfg->dyn == MFX_DYN_ACC && cfg->delta_l2 <= 0) return MFX_ERR_CONFIG;
     if (!mfx_method_supported(cfg->method)) return MFX_ERR_CONFIG;
@@ -432,6 +485,7 @@ int create_impl(const mfx_config *cfg, int hip_device, bool planning, mfx_handle
     }
     const bool stft = cfg->method == MFX_METHOD_STFT_LOGMEL;
     if (stft && !stft_config_ok(cfg)) return MFX_ERR_CONFIG;
+    if (kaldi && !kaldi_config_ok(cfg)) return MFX_ERR_CONFIG;
 
     if (!planning) {
         int ndev = 0;
@@ -458,6 +512,7 @@ int create_impl(const mfx_config *cfg, int hip_device, bool planning, mfx_handle
     h->dl = cfg->want_c0 ? cfg->ceps_len + 1 : cfg->ceps_len;
     h->traps = traps;
     h->stft = stft;
+    h->kaldi = kaldi;
     h->traps_L = traps ? traps_L : 0;
     h->traps_K = traps ? traps_K : 0;
     h->fcols = h->ceps > 0 ? h->dl : h->nb;
@@ -473,6 +528,7 @@ int create_impl(const mfx_config *cfg, int hip_device, bool planning, mfx_handle
         if (rows * cw * (int64_t)sizeof(float) > (int64_t)kLdsCap) return MFX_ERR_CONFIG;
     }
     if (stft) return create_stft(h, planning, owner, out);
+    if (kaldi) return create_kaldi(h, planning, owner, out);
     h->W2 = (int)ceil_pow2((uint32_t)h->W);
     if (cfg->fft_size != 0) {
         if (cfg->fft_size < h->W || (cfg->fft_size & (cfg->fft_size - 1)) != 0) return MFX_ERR_CONFIG;
@@ -696,6 +752,7 @@ FrontKind choose_front(const mfx_handle *h) { return choose_front(h, h->batch.al
 
 FrontKind choose_front(const mfx_handle *h, bool aligned)
 {
+    if (h->kaldi) return kKaldi; // (one kernel, whatever the alignment and the engine bits)
     // (else: the streaming interface's kernels; PLP has no fused front end: spectrum through HBM, then k_plp.  TRAPS takes
     // whatever the fbank handle of its shape takes: its front end IS that handle's, k_traps follows it)
     const bool allow_fused = !(h->cfg.engine & MFX_ENGINE_STREAM_KERNELS) && !h->plp;
@@ -718,6 +775,7 @@ FrontKind choose_front(const mfx_handle *h, bool aligned)
 // out: the spectrum goes through the slab and k_melcep_runs / k_plp_runs apply each table to its own rows.
 FrontKind batch_front(const mfx_handle *h)
 {
+    if (h->kaldi) return kKaldi; // (mfx_batch_set_alphas is refused on such a handle)
     if (h->batch.va.on) return h->fast512 ? kSpec512 : kSpecGen;
     return choose_front(h);
 }
@@ -739,6 +797,14 @@ int launch_front(mfx_handle *h, FrontParams &p, FrontKind kind, bool aligned, co
             HIP_TRY(h, launch_front1024(p, aligned, h->nm16, h->stream, (h->cfg.engine & MFX_ENGINE_FRONT1024_12_WAVES) ? 12 : 16));
             break;
         case kFront2048: HIP_TRY(h, launch_front2048(p, h->num_cus, h->stream)); break;
+        case kKaldi: {
+            const int32_t *meta = h->d_kaldi_mel.p; // [3][nb]
+            KaldiParams kp{p.pcm, p.pcm_total, p.chunks, p.n_chunks, p.row_limit, h->W, h->S, h->W2, h->nb, h->ceps, h->kaldi_preemph,
+                           h->kaldi_remove_dc ? 1 : 0, h->kaldi_use_power ? 1 : 0, h->d_kaldi_ops.p, h->d_kaldi_melw.p, (int32_t)h->d_kaldi_melw.n, meta, meta + h->nb,
+                           meta + 2 * h->nb, h->d_kaldi_dct_t.p, p.feat, p.feat_pitch};
+            HIP_TRY(h, launch_kaldi(kp, h->stream));
+            break;
+        }
         default: HIP_TRY(h, launch_front_generic(p, /*fused=*/true, h->stream)); break;
         }
         return MFX_OK;
@@ -780,6 +846,7 @@ extern "C" const char *mfx_dominant_kernel_name(const mfx_handle *h)
 {
     if (!h) return "";
     if (h->stft) return h->stft_form == StftForm::Fft ? "k_stft_fft_mel" : "k_stft_mel";
+    if (h->kaldi) return "k_kaldi_front";
     switch (batch_front(h)) { // names as rocprofv3 prints them
     case kFront512:
     case kSpec512: return "k_front512";
@@ -816,6 +883,15 @@ extern "C" int mfx_set_window(mfx_handle *h, const float *window)
         h->have_window = true;
         return MFX_OK;
     }
+    if (h->kaldi) { // the window's W taps zero padded to N, and the FFT tables
+        std::vector<float> ops;
+        build_kaldi_operands(h->W, h->W2, window, ops);
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (h->batch.ov.stream2) HIP_TRY(h, hipStreamSynchronize(h->batch.ov.stream2));
+        HIP_TRY(h, h->upload(h->d_kaldi_ops, ops));
+        h->have_window = true;
+        return MFX_OK;
+    }
     std::vector<float> padded((size_t)h->W2, 0.f);
     std::memcpy(padded.data(), window, sizeof(float) * h->W);
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -849,7 +925,8 @@ extern "C" int64_t mfx_debug_read(mfx_handle *h, int kind, void *dst, int64_t ds
     if (hipSetDevice(h->device) != hipSuccess) return MFX_ERR_DEVICE;
     const void *src = nullptr;
     int64_t count = 0, esz = 4;
-    if (h->stft && kind != 8) return kind >= 0 && kind <= 7 ? 0 : MFX_ERR_ARG; // (none of those tables or blocks exists)
+    if ((h->stft || h->kaldi) && kind != 8 && kind != 6) return kind >= 0 && kind <= 7 ? 0 : MFX_ERR_ARG; // (none of those tables or blocks exists)
+    if (h->stft && kind == 6) return 0;
     switch (kind) {
     case 0:
         if (refresh_mel(h) != MFX_OK) return MFX_ERR_DEVICE;
@@ -1074,6 +1151,52 @@ extern "C" int mfx_host_slaney_mel_table(int32_t num_banks, int32_t dft_size, fl
     if (!(sample_rate > 0.f) || !(low_freq >= 0.f) || !(low_freq < high_freq) || !(high_freq <= sample_rate / 2)) return MFX_ERR_ARG;
     build_slaney_mel(num_banks, dft_size, sample_rate, low_freq, high_freq, weights, beg, len);
     return MFX_OK;
+}
+
+// ---- Kaldi front end: the three frame options; the tables as uploaded and the kernel's LDS, for tests (no device needed)
+extern "C" int mfx_kaldi_set_options(mfx_handle *h, float preemph_coeff, int32_t remove_dc_offset, int32_t use_power)
+{
+    if (!h) return MFX_ERR_ARG;
+    if (!h->kaldi) return fail(h, MFX_ERR_CONFIG, "mfx_kaldi_set_options: not a Kaldi handle (method != MFX_METHOD_KALDI)");
+    if (!std::isfinite(preemph_coeff) || preemph_coeff < 0.f || preemph_coeff > 1.f)
+        return fail(h, MFX_ERR_ARG, "mfx_kaldi_set_options: preemph_coeff must lie in [0, 1]");
+    if ((remove_dc_offset != 0 && remove_dc_offset != 1) || (use_power != 0 && use_power != 1))
+        return fail(h, MFX_ERR_ARG, "mfx_kaldi_set_options: remove_dc_offset and use_power are 0 or 1");
+    if (h->sess.n > 0)
+        return fail(h, MFX_ERR_STATE, "mfx_kaldi_set_options: sessions exist (an open stream's rows must not change under it): mfx_sessions_create(h, 0, 0) first");
+    if (!h->planning) { // (runs in flight were queued with the options they were called under: they are kernel arguments)
+        const int rc = sync_device(h);
+        if (rc != MFX_OK) return rc;
+    }
+    h->kaldi_preemph = preemph_coeff;
+    h->kaldi_remove_dc = remove_dc_offset != 0;
+    h->kaldi_use_power = use_power != 0;
+    return MFX_OK;
+}
+
+extern "C" int mfx_host_kaldi_mel_table(int32_t num_banks, int32_t fft_size, float sample_rate, float low_freq, float high_freq,
+                                        float *weights, int32_t *beg, int32_t *len)
+{
+    double high = 0.0;
+    if (num_banks < 1 || num_banks > 128 || (fft_size != 128 && fft_size != 256 && fft_size != 512) || !(sample_rate > 0.f) ||
+        !kaldi_freqs_ok(sample_rate, low_freq, high_freq, &high) || !weights || !beg || !len)
+        return MFX_ERR_ARG;
+    build_kaldi_mel(num_banks, fft_size, sample_rate, low_freq, high, weights, beg, len);
+    return MFX_OK;
+}
+
+extern "C" int mfx_host_kaldi_dct(int32_t num_banks, int32_t ceps_len, float lifter, float *matrix)
+{
+    if (num_banks < 1 || num_banks > 128 || ceps_len < 1 || ceps_len > num_banks || !(lifter >= 0.f) || !std::isfinite(lifter) || !matrix)
+        return MFX_ERR_ARG;
+    build_kaldi_dct(num_banks, ceps_len, lifter, matrix);
+    return MFX_OK;
+}
+
+extern "C" int64_t mfx_host_kaldi_lds_bytes(int32_t window_size, int32_t shift, int32_t num_banks, int32_t ceps_len)
+{
+    if (!kaldi_shape_ok(window_size, shift, num_banks, ceps_len)) return MFX_ERR_ARG;
+    return (int64_t)kaldi_lds_bytes(window_size, shift, num_banks, ceps_len);
 }
 
 extern "C" int64_t mfx_host_frame_count(int64_t samples, int32_t window_size, int32_t shift)

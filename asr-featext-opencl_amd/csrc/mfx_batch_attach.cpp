@@ -17,6 +17,7 @@ extern "C" int mfx_batch_set_alphas(mfx_handle *h, const float *alphas, int32_t 
         return MFX_OK;
     }
     if (h->stft) return fail(h, MFX_ERR_CONFIG, "mfx_batch_set_alphas: an STFT log-mel handle has no warped Slaney table");
+    if (h->kaldi) return fail(h, MFX_ERR_CONFIG, "mfx_batch_set_alphas: a Kaldi handle has no VTLN warp (vtln_warp is not served)");
     if (!alphas || n_utt != h->batch.n_utt) return fail(h, MFX_ERR_ARG, "one warp factor per planned utterance");
     for (int u = 0; u < n_utt; ++u)
         if (!(alphas[u] > 0.f)) return fail(h, MFX_ERR_ARG, "alpha must be positive");

@@ -593,6 +593,15 @@ struct mfx_handle {
     DevBuf<float> d_stft_ops, d_stft_melw; // basis operands -- FFT form: window and FFT tables -- (mfx_set_window builds them); the mel
                                          // rows' spans back to back
     DevBuf<int32_t> d_stft_mel;          // [3][nb]: beg, len, first weight of every row
+    // mfx_config.method == MFX_METHOD_KALDI: k_kaldi_front IS the front end (FrontKind kKaldi), for the batch and the session
+    // entries; everything behind it is an MFCC handle's.  W2 is the DFT length kaldi_fft_size(W); none of the FFT / mel / DCT
+    // tables below exist on such a handle
+    bool kaldi = false;
+    float kaldi_preemph = 0.97f;         // the three options (mfx_kaldi_set_options), Kaldi's defaults
+    bool kaldi_remove_dc = true, kaldi_use_power = true;
+    DevBuf<float> d_kaldi_ops, d_kaldi_melw, d_kaldi_dct_t; // window and FFT tables (mfx_set_window builds them); the bands' spans
+                                         // back to back; G transposed [nb][ceps] (empty at ceps == 0)
+    DevBuf<int32_t> d_kaldi_mel;         // [3][nb]: beg, len, first weight of every band
     float alpha = 1.f;
     bool have_window = false;
 
@@ -738,6 +747,9 @@ inline int MelPlanBuf::set(mfx_handle *h, const mfx::MelPlan *plans, int count)
         if ((h)->traps)                                                                                                      \
             return fail((h), MFX_ERR_STATE,                                                                                  \
                         "TRAPS handles have no streaming entries: use mfx_batch_plan + mfx_batch_run_device / mfx_batch_run_host"); \
+        if ((h)->kaldi)                                                                                                      \
+            return fail((h), MFX_ERR_STATE,                                                                                  \
+                        "Kaldi handles have no streaming entries: use mfx_batch_plan + mfx_batch_run_device / mfx_batch_run_host, or the session entries"); \
     } while (0)
 
 // one launch of the dominant kernel between two events, while profiling is on (prof_collect, mfx_api.cpp, sums them up)
@@ -765,7 +777,9 @@ struct ProfScope {
 
 // ---- mfx_api.cpp, for the others
 // Which front-end kernel the BATCH entries run for this handle (see choose_front's definition)
-enum FrontKind { kFront512, kFront1024, kFront2048, kFrontGenFused, kSpec512, kSpecGen };
+// (kKaldi: k_kaldi_front of a Kaldi handle -- no spectrum kind, no slab, no k_melcep: wherever the kind matters it behaves as
+// kFrontGenFused)
+enum FrontKind { kFront512, kFront1024, kFront2048, kFrontGenFused, kSpec512, kSpecGen, kKaldi };
 inline bool is_spec_kind(FrontKind k) { return k == kSpec512 || k == kSpecGen; }
 // the fused kinds whose statics can go out as compact 16-float rows (k_front512: only with the DCT on the matrix pipe)
 inline bool compact_statics(FrontKind k, const mfx::FrontParams &p) { return !is_spec_kind(k) && (k != kFront512 || p.dct_mode == 1); }

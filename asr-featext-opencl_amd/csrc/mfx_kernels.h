@@ -1,4 +1,4 @@
-// mfx_kernels.h -- launch interface of the gfx950 kernels (implemented in mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip, mfx_plp.hip, mfx_traps.hip, mfx_xform.hip, mfx_sess_xform.hip, mfx_sess_resample.hip, mfx_sessions.hip, mfx_resample.hip, mfx_speakers.hip, mfx_vad.hip, mfx_onorm.hip, mfx_stft.hip, mfx_stft_fft.hip, mfx_pitch.hip, mfx_pitchfeat.hip, mfx_tensor.hip: one translation unit per kernel family).
+// mfx_kernels.h -- launch interface of the gfx950 kernels (implemented in mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip, mfx_plp.hip, mfx_traps.hip, mfx_xform.hip, mfx_sess_xform.hip, mfx_sess_resample.hip, mfx_sessions.hip, mfx_resample.hip, mfx_speakers.hip, mfx_vad.hip, mfx_onorm.hip, mfx_stft.hip, mfx_stft_fft.hip, mfx_kaldi.hip, mfx_pitch.hip, mfx_pitchfeat.hip, mfx_tensor.hip: one translation unit per kernel family).
 //
 // Kernel inventory and the reference stage each one replaces:
 //   spectrum512 / fused512   segmenter.cl kernelSegmentWindow + AppleFFT fft0 + mfcc.cl kernelTranspose
@@ -27,6 +27,8 @@
 //                            (one launcher surface and one block tail for both; stft_form(N) of mfx_tables.h says which a length gets)
 //   sess_stft_mel            the same front end over the frames one push of the session entries completes, groups of 16 frames of
 //                            different sessions sharing a block's pass over the basis (no reference analogue)
+//   kaldi_front              the Kaldi-compatible fbank / MFCC front end: per-frame DC removal, pre-emphasis, window, a float32 FFT per
+//                            wave and frame, power, Kaldi's mel table, log, DCT + lifter with c0 first (no reference analogue)
 //   tensor_pack              the finished rows of a batch run as a dense padded tensor, time- or channel-major, float32 / half / bfloat16
 //                            (no reference analogue: a neural model's input)
 //   delta                    delta.cl kernelDelta x2 + the staging copies of mfccopencl.cpp:360-387
@@ -641,6 +643,30 @@ struct SessStftParams {
 size_t sess_stft_lds_bytes(int N, int S, int M, int G);
 int sess_stft_groups(int N, int S, int M);
 hipError_t launch_sess_stft(const SessStftParams &p, hipStream_t stream);
+
+// k_kaldi_front (mfx_kaldi.hip; DESIGN.md section 5, "Kaldi front end"): the front end of MFX_METHOD_KALDI over the chunks of a
+// batch plan or of a push -- one block per Chunk of at most 16 frames, statics to `feat` as the fused kinds deliver them.
+struct KaldiParams {
+    const int16_t *pcm;
+    int64_t pcm_total;          // int16 elements readable behind `pcm` (mono)
+    const Chunk *chunks;        // the launch's chunks (blockIdx.x)
+    int32_t n_chunks;
+    int64_t row_limit;          // frames whose destination row is >= row_limit are skipped
+    int32_t W, S, N;            // window, shift, DFT length kaldi_fft_size(W)
+    int32_t M, C;               // mel bands; cepstra (0: the log mel energies are the statics)
+    float preemph;              // c in [0, 1]
+    int32_t remove_dc, use_power;
+    const float *operands;      // window [N] zero padded | W_{N/2}^k, k < N / 2, complex | -i W_N^k, k < N / 2, complex (build_kaldi_operands)
+    const float *mel_w;         // the bands' non-zero spans back to back
+    int32_t mel_w_floats;       // their floats: 1 .. N (a bin lies in two bands at most)
+    const int32_t *mel_beg, *mel_len, *mel_off; // [M] first bin, bins, first weight of every band
+    const float *dct_t;         // [M][C]: G transposed (null at C = 0)
+    float *feat;                // [rows][feat_pitch], statics at columns [0, C or M)
+    int32_t feat_pitch;
+};
+// ALL the LDS a block of k_kaldi_front asks for: the kernel declares no static LDS beside it
+size_t kaldi_lds_bytes(int W, int S, int M, int C);
+hipError_t launch_kaldi(const KaldiParams &p, hipStream_t stream);
 
 // All launchers are asynchronous on `stream` and return the launch status.
 // every launch of the VAD stage for utterances [u0, u1), in order

@@ -550,6 +550,73 @@ void build_slaney_spans(int M, int N, float sample_rate, float low_freq, float h
     if (w.empty()) w.push_back(0.f); // (every band narrower than a bin: keep the buffer non-null)
 }
 
+bool kaldi_freqs_ok(float sample_rate, float low_freq, float high_freq, double *high_abs)
+{
+    const double nyq = (double)sample_rate / 2.0, hi = high_freq > 0.f ? (double)high_freq : nyq + (double)high_freq;
+    if (high_abs) *high_abs = hi;
+    return low_freq >= 0.f && (double)low_freq < hi && hi <= nyq; // (false for NaN)
+}
+
+void build_kaldi_mel(int M, int N, float sample_rate, float low_freq, double high_abs, float *weights, int32_t *beg, int32_t *len)
+{
+    const int K = N / 2;
+    auto mel = [](double f) { return 1127.0 * std::log(1.0 + f / 700.0); };
+    const double ml = mel((double)low_freq), mh = mel(high_abs), delta = (mh - ml) / (double)(M + 1);
+    for (int m = 0; m < M; ++m) {
+        const double l = ml + (double)m * delta, c = l + delta, r = l + 2.0 * delta;
+        int first = -1, last = -2;
+        for (int k = 0; k < K; ++k) {
+            const double mk = mel((double)k * (double)sample_rate / (double)N);
+            float w = 0.f;
+            if (mk > l && mk < r) w = (float)(mk <= c ? (mk - l) / (c - l) : (r - mk) / (r - c));
+            weights[(size_t)m * K + k] = w;
+            if (w != 0.f) {
+                if (first < 0) first = k;
+                last = k;
+            }
+        }
+        beg[m] = first < 0 ? 0 : first;
+        len[m] = first < 0 ? 0 : last - first + 1;
+    }
+}
+
+void build_kaldi_spans(int M, int N, float sample_rate, float low_freq, double high_abs, std::vector<float> &w, std::vector<int32_t> &meta)
+{
+    const int K = N / 2;
+    std::vector<float> dense((size_t)M * K);
+    w.clear();
+    meta.assign((size_t)3 * M, 0);
+    build_kaldi_mel(M, N, sample_rate, low_freq, high_abs, dense.data(), meta.data(), meta.data() + M);
+    for (int m = 0; m < M; ++m) {
+        meta[(size_t)2 * M + m] = (int32_t)w.size();
+        w.insert(w.end(), dense.begin() + (size_t)m * K + meta[m], dense.begin() + (size_t)m * K + meta[m] + meta[(size_t)M + m]);
+    }
+    if (w.empty()) w.push_back(0.f); // (every band empty: keep the buffer non-null)
+}
+
+void build_kaldi_dct(int M, int C, float lifter, float *G)
+{
+    const double pi = 3.14159265358979323846264338, Q = (double)lifter;
+    for (int i = 0; i < C; ++i) {
+        const double l = Q > 0.0 ? 1.0 + Q / 2.0 * std::sin(pi * (double)i / Q) : 1.0;
+        for (int m = 0; m < M; ++m) {
+            const double D = i == 0 ? std::sqrt(1.0 / (double)M) : std::sqrt(2.0 / (double)M) * std::cos(pi / (double)M * ((double)m + 0.5) * (double)i);
+            G[(size_t)i * M + m] = (float)(l * D);
+        }
+    }
+}
+
+void build_kaldi_operands(int W, int N, const float *window, std::vector<float> &out)
+{
+    out.assign((size_t)3 * N, 0.f);
+    std::copy(window, window + W, out.begin());
+    std::vector<float> t;
+    build_twiddles(N / 2, N / 2, t); // W_M^k, k < M
+    std::copy(t.begin(), t.end(), out.begin() + N);
+    build_split_twiddles(N, false, t); // -i W_N^k, k <= M: the kernel splits bins k < M
+    std::copy(t.begin(), t.begin() + N, out.begin() + 2 * N);
+}
+
 } // namespace mfx
 
 namespace mfx {

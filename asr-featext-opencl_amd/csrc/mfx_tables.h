@@ -349,6 +349,25 @@ void build_stft_form_operands(StftForm form, int N, const float *window, std::ve
 // than a bin: the buffer is never empty), meta [3][M]: first bin, bins, first weight of every row
 void build_slaney_spans(int M, int N, float sample_rate, float low_freq, float high_freq, std::vector<float> &w, std::vector<int32_t> &meta);
 
+// Kaldi front end (MFX_METHOD_KALDI; include/mfx.h states the definition; DESIGN.md section 5, "Kaldi front end").
+// The DFT length of a window of W samples: the next power of two, 128 at least
+constexpr int kaldi_fft_size(int W) { return W <= 128 ? 128 : W <= 256 ? 256 : 512; }
+// the limits of a shape: window 65 .. 512, shift 1 .. W, 1 .. 128 bands, 0 .. M cepstra (0: the log mel energies)
+constexpr bool kaldi_shape_ok(int W, int S, int M, int C) { return W >= 65 && W <= 512 && S >= 1 && S <= W && M >= 1 && M <= 128 && C >= 0 && C <= M; }
+// high_freq as the table takes it: absolute when > 0, else Kaldi's offset from Nyquist; false unless 0 <= low < high <= Nyquist
+bool kaldi_freqs_ok(float sample_rate, float low_freq, float high_freq, double *high_abs = nullptr);
+// Kaldi's mel table, in double, rounded once: mel(f) = 1127 ln(1 + f / 700), M + 2 points equally spaced in mel between low and
+// high (absolute), f_k = k sample_rate / N for the bins k < N / 2 (the Nyquist bin has no weight).  weights [M][N / 2]; beg /
+// len: the non-zero span of every band (len 0: none)
+void build_kaldi_mel(int M, int N, float sample_rate, float low_freq, double high_abs, float *weights, int32_t *beg, int32_t *len);
+// the table as k_kaldi_front reads it: spans back to back and meta [3][M], as build_slaney_spans lays them out
+void build_kaldi_spans(int M, int N, float sample_rate, float low_freq, double high_abs, std::vector<float> &w, std::vector<int32_t> &meta);
+// G [C][M] = (float)(l[i] D[i][m]): Kaldi's DCT (row 0 sqrt(1 / M), row i sqrt(2 / M) cos(pi / M (m + 1/2) i)) times its lifter
+// l[i] = 1 + Q / 2 sin(pi i / Q) (1 at Q = 0), in double, rounded once
+void build_kaldi_dct(int M, int C, float lifter, float *G);
+// what k_kaldi_front takes as its operands: the window's W taps zero padded to N | W_{N/2}^k, k < N / 2 | -i W_N^k, k < N / 2: 3 N floats
+void build_kaldi_operands(int W, int N, const float *window, std::vector<float> &out);
+
 // One push of one session of an STFT log-mel handle ("Session log-mel"): a stream that has received n samples and
 // delivered rows [0, E) takes `length` more.  While the stream is open E = 0 up to n = N / 2, else min(n div S, (n - N / 2)
 // div S + 1): the frames whose taps have all arrived without a right reflection, and that no later sample can take out of

@@ -66,6 +66,10 @@ struct Options {
     int logmel_post = MFX_LOGMEL_WHISPER;          // --logmel-post whisper|log10|ln (--method LOGMEL)
     int logmel_nfft = 0;                           // --logmel-nfft 1024|2048 (--method LOGMEL): the DFT length; the Hann window of
                                                    // the --window-size length is centred in it.  0: the window's own length
+    // --method KALDI: the three frame options (Kaldi's defaults); the window is the Povey window, --ceps 0 is fbank
+    float kaldi_preemph = 0.97f;   // --preemph X
+    bool kaldi_dc = true;          // --no-dc-removal
+    bool kaldi_power = true;       // --magnitude
     bool htk = false; // binary output in HTK parameter-file format instead of the reference's text rows
     int format_threads = 4; // threads that format the text rows of a block (per worker)
     int batch_mb = 16;      // PCM per batch of files (0: the per-file loop only); small enough that a few thousand files pipeline
@@ -189,7 +193,7 @@ void write_htk_header(FILE *f, uint32_t n_frames, const Options &o, int width)
 {
     const bool traps = o.method == MFX_METHOD_TRAPS;
     uint16_t kind = traps ? 9 /* USER */ : o.method == MFX_METHOD_PLP ? 11 /* PLP */ : o.ceps > 0 ? 6 /* MFCC */ : 7 /* FBANK */;
-    if (!traps && o.ceps > 0 && o.c0) kind |= 0x2000;  // _0
+    if (!traps && o.ceps > 0 && o.c0) kind |= 0x2000;  // _0 (a Kaldi handle's c0 is column 0, not the last: no qualifier)
     if (o.dyn >= 1) kind |= 0x0100;          // _D
     if (o.dyn >= 2) kind |= 0x0200;          // _A
     if (o.norm == 1) kind |= 0x0800;         // _Z (zero mean)
@@ -603,7 +607,7 @@ bool prepare_batch(Batch &b, const Options &o, const std::vector<std::string> &f
             // (a file at another rate has no per-file loop either: it stays in the batch, and a sweep over it is refused)
             if (other_rate && sweep)
                 throw std::runtime_error("File \"" + files[2 * it.file] + "\" needs sample-rate conversion, which takes one warp factor, not a sweep");
-            it.stream = o.method != MFX_METHOD_TRAPS && !logmel && !other_rate && (sweep || n > (size_t)limit || T < 2 * D + 1);
+            it.stream = o.method != MFX_METHOD_TRAPS && o.method != MFX_METHOD_KALDI && !logmel && !other_rate && (sweep || n > (size_t)limit || T < 2 * D + 1);
             if (!it.stream) {
                 it.mono.resize(n);
                 const int ch = it.wav.channels;
@@ -665,6 +669,17 @@ void worker(const Options &o, int device, float sr, const std::vector<std::strin
                     window[i] = (float)(0.56f - 0.46f * std::cos((2.0f * M_PI * i) / W)) / 32768.f;
                 t->set_window(window.data());
                 t->set_warp(o.alpha_min);
+                if (g_time.on) g_time.t_created = now_ns();
+                return std::unique_ptr<MfccHip>(std::move(t));
+            }
+            if (o.method == MFX_METHOD_KALDI) { // batch entries only; the Povey window, samples in the int16 range
+                std::unique_ptr<KaldiHip> t(new KaldiHip(o.sample_limit, (int)W, (int)S, o.banks, sr, o.low, o.high, o.ceps, o.lift,
+                                                         (Normalizer::norm_t)o.norm, (ParamBase::dyn_t)o.dyn, o.l1, o.l2, o.norm_after_dyn,
+                                                         device));
+                std::vector<float> window((size_t)W);
+                KaldiHip::povey_window((int)W, window.data());
+                t->set_window(window.data());
+                t->set_options(o.kaldi_preemph, o.kaldi_dc, o.kaldi_power);
                 if (g_time.on) g_time.t_created = now_ns();
                 return std::unique_ptr<MfccHip>(std::move(t));
             }
@@ -917,7 +932,7 @@ void worker(const Options &o, int device, float sr, const std::vector<std::strin
                         // T - 2 D .. T - D - 1 (deltas unaffected).  The batch entries deliver the correct rows; the
                         // per-file loop this replaces reproduces the reference when --bug-compat is on, so do we.
                         // (not for a converted file: the reference has no rows for it, and it may be shorter than 2 D frames)
-                        if (o.bug_compat && D > 0 && o.method != MFX_METHOD_TRAPS && (float)it.rate == sr)
+                        if (o.bug_compat && D > 0 && o.method != MFX_METHOD_TRAPS && o.method != MFX_METHOD_KALDI && (float)it.rate == sr)
                             for (int i = 0; i < D; ++i)
                                 std::memcpy(rows + (size_t)(it.row0 + it.frames - D + i) * width,
                                             rows + (size_t)(it.row0 + it.frames - 2 * D + i) * width, (size_t)cols * sizeof(float));
@@ -996,6 +1011,7 @@ int main(int argc, char **argv)
     Options o;
     std::vector<std::string> files;
     bool alpha_options = false; // any of --alpha, --alpha-min, --alpha-max, --alpha-step
+    bool kaldi_opts = false;    // any of --preemph, --no-dc-removal, --magnitude
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto val = [&]() -> const char * {
@@ -1060,8 +1076,16 @@ int main(int argc, char **argv)
             else if (m == "PLP") o.method = MFX_METHOD_PLP;
             else if (m == "TRAPS") o.method = MFX_METHOD_TRAPS;
             else if (m == "LOGMEL") o.method = MFX_METHOD_STFT_LOGMEL;
-            else { std::fprintf(stderr, "--method: MFCC, PLP, TRAPS or LOGMEL\n"); return 2; }
+            else if (m == "KALDI") o.method = MFX_METHOD_KALDI;
+            else { std::fprintf(stderr, "--method: MFCC, PLP, TRAPS, LOGMEL or KALDI\n"); return 2; }
         }
+        else if (a == "--preemph") {
+            o.kaldi_preemph = (float)std::atof(val());
+            if (!(o.kaldi_preemph >= 0.f && o.kaldi_preemph <= 1.f)) { std::fprintf(stderr, "--preemph: 0 .. 1\n"); return 2; }
+            kaldi_opts = true;
+        }
+        else if (a == "--no-dc-removal") o.kaldi_dc = false, kaldi_opts = true;
+        else if (a == "--magnitude") o.kaldi_power = false, kaldi_opts = true;
         else if (a == "--traps-length") o.traps_len = std::atoi(val());
         else if (a == "--traps-dct") o.traps_dct = std::atoi(val());
         else if (a == "--logmel-nfft") {
@@ -1131,7 +1155,9 @@ int main(int argc, char **argv)
                         "         [--dyn 0..2] [--l1 n] [--l2 n] [--low-freq hz] [--high-freq hz] [--lift-coef x]\n"
                         "         [--norm-after-dyn 0|1] [--alpha a | --alpha-min a --alpha-max b --alpha-step s | --alpha-file f]\n"
                         "         [--sample-limit n] [--dev n | --devs a,b,...] [--bug-compat 0|1] [--htk]  in.wav out.txt [...]\n"
-                        "         [--method MFCC|PLP|TRAPS|LOGMEL] [--model-order n (PLP model order, default 8)]\n"
+                        "         [--method MFCC|PLP|TRAPS|LOGMEL|KALDI] [--model-order n (PLP model order, default 8)]\n"
+                        "         [--preemph x] [--no-dc-removal] [--magnitude] (KALDI: Kaldi-compatible fbank (--ceps 0) / MFCC with c0 first,\n"
+                        "          Povey window, --high-freq <= 0 an offset from Nyquist, --lift-coef the cepstral lifter; defaults 0.97, DC removal, power)\n"
                         "         [--logmel-post whisper|log10|ln (LOGMEL: what follows the log; default whisper)]\n"
                         "         [--logmel-nfft 1024|2048 (LOGMEL: the DFT length; the Hann window of --window-size lies centred in it)]\n"
                         "         [--traps-length n (TRAPS frames per trajectory, odd, default 31)] [--traps-dct n (default 10)]\n"
@@ -1281,6 +1307,21 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "--logmel-nfft goes with --method LOGMEL\n");
         return 2;
     }
+    if (o.method == MFX_METHOD_KALDI) { // whole files through the batch entries; c0 is column 0 of the cepstra, there is no warp
+        if (o.batch_mb <= 0) {
+            std::fprintf(stderr, "--method KALDI runs whole files through the batch entries: --batch-mb must be positive\n");
+            return 2;
+        }
+        if (o.alpha_max - o.alpha_min >= o.alpha_step || !o.alpha_file.empty()) {
+            std::fprintf(stderr, "--method KALDI has no warp factor\n");
+            return 2;
+        }
+        o.c0 = false, o.bug_compat = false;
+        if (!o.low_given) o.low = 20.f; // (Kaldi's default)
+    } else if (kaldi_opts) {
+        std::fprintf(stderr, "--preemph, --no-dc-removal and --magnitude go with --method KALDI\n");
+        return 2;
+    }
     if (o.resample_to != 0 && (o.resample_to < 1000 || o.resample_to > 768000)) {
         std::fprintf(stderr, "--resample-to takes a rate of 1000 .. 768000 Hz\n");
         return 2;
@@ -1292,7 +1333,7 @@ int main(int argc, char **argv)
     try {
         // sample rate from the first file (ASR_OCL.cpp:342-358), unless --resample-to names it
         const float sr = o.resample_to > 0 ? (float)o.resample_to : (float)read_wav(files[0]).sample_rate;
-        if (o.high <= 0) o.high = sr / 2;
+        if (o.high <= 0 && o.method != MFX_METHOD_KALDI) o.high = sr / 2; // (KALDI: <= 0 is the library's offset from Nyquist)
         if (o.logmel_nfft > 0 && (long)(sr * o.window_ms * 1e-3) > (long)o.logmel_nfft) {
             std::fprintf(stderr, "--window-size is %ld samples at %g Hz: longer than --logmel-nfft %d\n", (long)(sr * o.window_ms * 1e-3), (double)sr,
                          o.logmel_nfft);

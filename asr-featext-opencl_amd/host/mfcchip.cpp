@@ -85,6 +85,29 @@ LogmelHip::LogmelHip(int input_buffer_size, int dft_size, int shift, int num_ban
 {
 }
 
+KaldiHip::KaldiHip(int input_buffer_size, int window_size, int shift, int num_banks, float sample_rate, float low_freq, float high_freq,
+                   int ceps_len, float lift_coef, Normalizer::norm_t norm, dyn_t dyn, int delta_l1, int delta_l2, bool norm_after_dyn,
+                   int hip_device)
+    : MfccHip(input_buffer_size, window_size, shift, num_banks, sample_rate, low_freq, high_freq, ceps_len, /*want_c0=*/false, lift_coef,
+              norm, dyn, delta_l1, delta_l2, norm_after_dyn, hip_device, /*bug_compat=*/false, /*engine=*/0, MFX_METHOD_KALDI, 0)
+{
+}
+
+void KaldiHip::set_options(float preemph_coeff, bool remove_dc_offset, bool use_power)
+{
+    const int rc = mfx_kaldi_set_options(handle(), preemph_coeff, remove_dc_offset ? 1 : 0, use_power ? 1 : 0);
+    if (rc != MFX_OK) {
+        const char *m = mfx_last_error(handle());
+        throw std::runtime_error((m && *m) ? m : mfx_status_string(rc));
+    }
+}
+
+int KaldiHip::get_output_data_width() const { return mfx_get_output_data_width(handle()); }
+
+void KaldiHip::povey_window(int n, float *window)
+{
+    for (int i = 0; i < n; ++i) window[i] = (float)std::pow(0.5 - 0.5 * std::cos(2.0 * M_PI * (double)i / (double)(n - 1)), 0.85);
+}
 
 MfccHip::MfccHip(int input_buffer_size, int window_size, int shift, int num_banks, float sample_rate, float low_freq,
                  float high_freq, int ceps_len, bool want_c0, float lift_coef, Normalizer::norm_t norm, dyn_t dyn,
@@ -121,7 +144,7 @@ MfccHip::MfccHip(int input_buffer_size, int window_size, int shift, int num_bank
         throw std::runtime_error("MfccHip: feature method not supported by this libmfcchip.so");
     const int rc = mfx_create(&cfg, hip_device, &m_handle);
     if (rc != MFX_OK)
-        throw std::runtime_error(std::string(method == MFX_METHOD_PLP ? "PlpHip: " : method == MFX_METHOD_TRAPS ? "TrapsHip: " : method == MFX_METHOD_STFT_LOGMEL ? "LogmelHip: " : "MfccHip: ") + mfx_status_string(rc));
+        throw std::runtime_error(std::string(method == MFX_METHOD_PLP ? "PlpHip: " : method == MFX_METHOD_TRAPS ? "TrapsHip: " : method == MFX_METHOD_STFT_LOGMEL ? "LogmelHip: " : method == MFX_METHOD_KALDI ? "KaldiHip: " : "MfccHip: ") + mfx_status_string(rc));
 }
 
 MfccHip::~MfccHip() { mfx_destroy(m_handle); }

@@ -18,6 +18,7 @@ DYN_NONE, DYN_DELTA, DYN_ACC = 0, 1, 2                     # parambase.h:9
 METHOD_MFCC, METHOD_PLP = 0, 1                             # mfx_config.method (include/mfx.h)
 METHOD_TRAPS = 3                                           # (2 is unassigned and refused)
 METHOD_STFT_LOGMEL = 5                                     # (4 is unassigned and refused)
+METHOD_KALDI = 7                                           # (6 is unassigned and refused)
 LOGMEL_WHISPER, LOGMEL_LOG10, LOGMEL_LN = 0, 1, 2          # mfx_config.logmel_post (include/mfx.h)
 
 
@@ -90,6 +91,7 @@ EXPORTED_SYMBOLS = (
     "mfx_host_slaney_mel_table", "mfx_host_stft_basis", "mfx_host_stft_frame_count",
     "mfx_host_stft_lds_bytes", "mfx_host_session_stft_step", "mfx_host_sess_stft_lds_bytes",
     "mfx_host_stft_fft_tables", "mfx_host_stft_fft_lds_bytes",
+    "mfx_kaldi_set_options", "mfx_host_kaldi_mel_table", "mfx_host_kaldi_dct", "mfx_host_kaldi_lds_bytes",
     "mfx_batch_set_pitch", "mfx_batch_clear_pitch", "mfx_batch_pitch_read", "mfx_batch_pitch_device", "mfx_host_pitch",
     "mfx_batch_set_pitch_feats", "mfx_batch_clear_pitch_feats", "mfx_batch_pitch_feats_read", "mfx_batch_pitch_feats_device",
     "mfx_host_pitch_feats",
@@ -222,6 +224,10 @@ def load_library():
     L.mfx_host_stft_fft_lds_bytes.argtypes, L.mfx_host_stft_fft_lds_bytes.restype = [i32, i32, i32, p32], i64
     L.mfx_host_session_stft_step.argtypes, L.mfx_host_session_stft_step.restype = [i32, i32, p64, i64, i32, p32, p32], i32
     L.mfx_host_sess_stft_lds_bytes.argtypes, L.mfx_host_sess_stft_lds_bytes.restype = [i32, i32, i32, p32], i64
+    L.mfx_kaldi_set_options.argtypes = [vp, C.c_float, i32, i32]
+    L.mfx_host_kaldi_mel_table.argtypes = [i32, i32, C.c_float, C.c_float, C.c_float, fp, p32, p32]
+    L.mfx_host_kaldi_dct.argtypes = [i32, i32, C.c_float, fp]
+    L.mfx_host_kaldi_lds_bytes.argtypes, L.mfx_host_kaldi_lds_bytes.restype = [i32, i32, i32, i32], i64
     L.mfx_batch_set_pitch.argtypes = [vp, i32, i32, i32, C.c_float, C.c_float, C.c_float, i32]
     L.mfx_batch_clear_pitch.argtypes = [vp]
     L.mfx_batch_pitch_read.argtypes = [vp, fp, p32, fp]
@@ -701,6 +707,50 @@ def stft_frame_count(samples, dft_size, shift):
     return n
 
 
+def povey_window(n):
+    """Kaldi's default ("povey") window of n taps, float32: pow(0.5 - 0.5 cos(2 pi i / (n - 1)), 0.85), in double, rounded
+    once."""
+    i = np.arange(int(n), dtype=np.float64)
+    return np.power(0.5 - 0.5 * np.cos(2.0 * np.pi * i / (int(n) - 1)), 0.85).astype(np.float32)
+
+
+def kaldi_fft_size(window_size):
+    """DFT length of a Kaldi handle: the next power of two >= window_size (128 at least)."""
+    return 128 if window_size <= 128 else 256 if window_size <= 256 else 512
+
+
+def host_kaldi_mel_table(num_banks, fft_size, sample_rate, low_freq, high_freq):
+    """Kaldi's mel table exactly as uploaded (host code, no GPU needed): (weights [num_banks][fft_size / 2], beg [num_banks],
+    len [num_banks]) -- beg / len the non-zero span of every band.  high_freq <= 0 is the offset from Nyquist."""
+    L = load_library()
+    w = np.zeros((max(int(num_banks), 0), max(int(fft_size), 0) // 2), np.float32)
+    beg, ln = np.zeros(max(int(num_banks), 0), np.int32), np.zeros(max(int(num_banks), 0), np.int32)
+    p32 = C.POINTER(C.c_int32)
+    rc = L.mfx_host_kaldi_mel_table(int(num_banks), int(fft_size), float(sample_rate), float(low_freq), float(high_freq),
+                                    w.ctypes.data_as(C.POINTER(C.c_float)), beg.ctypes.data_as(p32), ln.ctypes.data_as(p32))
+    if rc != 0:
+        raise MfxError(rc, "mfx_host_kaldi_mel_table failed")
+    return w, beg, ln
+
+
+def host_kaldi_dct(num_banks, ceps_len, lifter):
+    """Kaldi's DCT times its lifter exactly as uploaded (host code, no GPU needed): G [ceps_len][num_banks], row 0 is c0's."""
+    L = load_library()
+    g = np.zeros((max(int(ceps_len), 0), max(int(num_banks), 0)), np.float32)
+    rc = L.mfx_host_kaldi_dct(int(num_banks), int(ceps_len), float(lifter), g.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc != 0:
+        raise MfxError(rc, "mfx_host_kaldi_dct failed")
+    return g
+
+
+def host_kaldi_lds_bytes(window_size, shift, num_banks, ceps_len):
+    """ALL the LDS bytes a block of k_kaldi_front asks for at a shape.  An inspection aid."""
+    n = int(load_library().mfx_host_kaldi_lds_bytes(int(window_size), int(shift), int(num_banks), int(ceps_len)))
+    if n < 0:
+        raise MfxError(n, "mfx_host_kaldi_lds_bytes failed")
+    return n
+
+
 def host_frame_count(samples, window_size, shift):
     return int(load_library().mfx_host_frame_count(int(samples), int(window_size), int(shift)))
 
@@ -801,6 +851,10 @@ class MfccHip:
     DFT lengths: even, 32 .. 512 (an exact matrix DFT), and 1024 / 2048 (a float32 FFT; batch entries only, the session
     entries raise ``MfxError`` (-8)).  A window shorter than the DFT (``win_length < n_fft``) is passed centred in
     ``window_size`` taps with zeros around it, left pad ``(n_fft - win_length) // 2``, as ``torch.stft`` places it.
+    ``method=METHOD_KALDI`` computes Kaldi-compatible fbank (``ceps_len=0``) or MFCC (``ceps_len`` = num_ceps, c0 in column
+    0; ``want_c0=False``; ``lift_coef`` = cepstral_lifter, 0 = none) features (include/mfx.h): ``window_size`` 65 .. 512,
+    ``high_freq <= 0`` is Kaldi's offset from Nyquist; set ``povey_window(window_size)`` as the window and the three frame
+    options with ``kaldi_set_options``.  Batch and session entries; no streaming methods, no warp factors.
     """
 
     def __init__(self, input_buffer_size, window_size, shift, num_banks, sample_rate, low_freq, high_freq,
@@ -849,6 +903,11 @@ class MfccHip:
 
     def set_alpha(self, alpha):
         self._chk(self._L.mfx_set_alpha(self._h, float(alpha)))
+
+    def kaldi_set_options(self, preemph_coeff=0.97, remove_dc_offset=True, use_power=True):
+        """The three frame options of a METHOD_KALDI handle (Kaldi's defaults).  Flags may be given as 0 / 1; any other
+        integer is refused by the library."""
+        self._chk(self._L.mfx_kaldi_set_options(self._h, float(preemph_coeff), int(remove_dc_offset), int(use_power)))
 
     def set_window(self, window):
         w = np.ascontiguousarray(window, dtype=np.float32)

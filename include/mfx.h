@@ -105,7 +105,7 @@ typedef struct mfx_config {
  * ONLY: on a TRAPS handle mfx_set_input, mfx_flush, mfx_apply, mfx_apply_alphas, mfx_get_output_data and
  * mfx_get_output_data_alpha return MFX_ERR_STATE.  The value 2 is unassigned and stays refused (mfx_method_supported(2) == 0):
  * libraries in the field answer for it, so TRAPS did not take it. */
-enum { MFX_METHOD_MFCC = 0, MFX_METHOD_PLP = 1, MFX_METHOD_TRAPS = 3, MFX_METHOD_STFT_LOGMEL = 5 };
+enum { MFX_METHOD_MFCC = 0, MFX_METHOD_PLP = 1, MFX_METHOD_TRAPS = 3, MFX_METHOD_STFT_LOGMEL = 5, MFX_METHOD_KALDI = 7 };
 
 /* mfx_config.method 5 = the log-mel spectrogram neural recognisers of the Whisper family feed on ("STFT log-mel"):
  * an exact-length DFT of centred, reflect-padded frames, Slaney mel bands, log10, and Whisper's clamp and map.  The value 4
@@ -180,6 +180,54 @@ enum { MFX_METHOD_MFCC = 0, MFX_METHOD_PLP = 1, MFX_METHOD_TRAPS = 3, MFX_METHOD
  *     effect.  mfx_sessions_run_device allocates nothing; a push leaves the batch plan and the streaming state alone. */
 enum { MFX_LOGMEL_WHISPER = 0, MFX_LOGMEL_LOG10 = 1, MFX_LOGMEL_LN = 2 };
 
+/* mfx_config.method 7 = the Kaldi-compatible front end ("Kaldi front end"): what compute-fbank-feats /
+ * compute-mfcc-feats and torchaudio.compliance.kaldi.fbank define -- per-frame DC removal, pre-emphasis, the Povey window, power
+ * spectrum, Kaldi's mel table, log, and for MFCC Kaldi's DCT and lifter with c0 in column 0.  The value 6 is unassigned and stays
+ * refused, as 2 and 4 do.  The definition below is restated from Kaldi's feature-window.cc, mel-computations.cc, feature-fbank.cc
+ * and feature-mfcc.cc; agreement with a Kaldi or torchaudio binary has NOT been measured (neither is available to the build).
+ * Configuration (anything else: MFX_ERR_CONFIG, from mfx_create and mfx_plan_create).  window_size = W in 65 .. 512; N = the next
+ * power of two >= W (128, 256 or 512); fft_size 0 or N (mfx_fft_size returns N); shift = S in 1 .. W; num_banks = M in 1 .. 128;
+ * channels 0 or 1; low_freq >= 0; high_freq > 0 is absolute, high_freq <= 0 is Kaldi's offset from Nyquist (sample_rate / 2 +
+ * high_freq); then low < high <= sample_rate / 2.  ceps_len = C: 0 delivers the M log mel energies (fbank), 1 .. M Kaldi's
+ * num_ceps cepstra WITH c0 IN COLUMN 0; want_c0 must be 0 (c0 is already in).  lift_coef = Kaldi's cepstral_lifter Q >= 0, 0
+ * meaning none (ignored at C = 0; the rule that refuses lift_coef == 0 does not apply to this method).  norm, dyn, delta_l1 / l2,
+ * norm_after_dyn and batch_norm_stats are as on an MFCC handle; bug_compat, engine, lpc_order, traps_* and logmel_post are
+ * ignored.  Width = (C or M) * (1 + dyn).  The three frame options come through mfx_kaldi_set_options (below).
+ * Definition, per utterance of n samples: T = mfx_batch_frames = floor((n - W) / S) + 1 for n >= W, else 0 (Kaldi's snip_edges =
+ * true).  For frame t and taps i in [0, W):
+ *   Samples.  x[i] = (float)pcm[t S + i], not scaled: Kaldi works in the int16 range.
+ *   DC.       s = the exact integer sum of the frame's W samples (it fits int32); mean = (float)s / (float)W, one conversion and
+ *     one float32 division; d[i] = x[i] - mean.  With DC removal off d = x.
+ *   Pre-emphasis, c = preemph_coeff.  e[i] = fmaf(-c, d[i - 1], d[i]) for i >= 1, e[0] = fmaf(-c, d[0], d[0]): the frame's first
+ *     sample stands for its predecessor, so no sample outside the frame is read.  With c = 0, e = d.
+ *   Window.   z[i] = e[i] * w[i], w the caller's W floats from mfx_set_window; z[i] = 0 for W <= i < N.  The Povey window is
+ *     pow(0.5 - 0.5 cos(2 pi i / (W - 1)), 0.85), in double, rounded once.
+ *   DFT.      X[k] = sum_i z[i] e^(-2 pi i i k / N), k in [0, N / 2), by a float32 FFT (half-length complex FFT and real split).
+ *     It is NOT pinned to a summation order.  Its tables are built on the host in double and rounded once; the float32
+ *     operations a frame sees depend on N alone -- not on the chunk, the wave, the frame's place in its block, the batch or the
+ *     entry.
+ *   Power.    P[k] = fmaf(im, im, re * re); with use_power = 0, P[k] = sqrtf(P[k]).
+ *   Mel.      Kaldi's table, in double, rounded once (mfx_host_kaldi_mel_table).  mel(f) = 1127 ln(1 + f / 700), f_k = k
+ *     sample_rate / N; only bins k < N / 2 enter (the Nyquist bin has no weight).  ml = mel(low), mh = mel(high), delta = (mh -
+ *     ml) / (M + 1); band m has l = ml + m delta, c = l + delta, r = l + 2 delta; Wm[m][k] = 0 unless l < mel(f_k) < r, else
+ *     (mel - l) / (c - l) when mel <= c, else (r - mel) / (r - c).  mel[m] = 0, then over the band's non-zero span in ascending
+ *     k mel = fmaf(Wm[m][k], P[k], mel).  An empty band is 0 and takes the floor.
+ *   Log.      L[m] = logf(max(mel[m], 0x1p-23f)): the floor is Kaldi's FLT_EPSILON; silence gives -15.9424.
+ *   Cepstra (C > 0).  D[0][m] = sqrt(1 / M), D[i][m] = sqrt(2 / M) cos(pi / M (m + 1/2) i); l[i] = 1 + (Q / 2) sin(pi i / Q), or 1
+ *     at Q = 0; G[i][m] = (float)(l[i] D[i][m]), in double, rounded once (mfx_host_kaldi_dct); c[i] = 0, then in ascending m
+ *     c = fmaf(G[i][m], L[m], c).
+ *   Contract.  Rows are a deterministic function of the utterance's samples, the window, the configuration and the three
+ *     options: the same bits alone or in a batch, at an even or odd sample offset, on a second run, through the device or the
+ *     host entry, at any 4-byte placement of d_out with nothing written outside the rows, and through the session entries however
+ *     the stream is cut.  Accuracy against float64 is the project's bar (1e-4 of scale, 1e-5 relative L2), not a bit pin.
+ * Entries.  The batch entries and the session entries serve the method exactly as they serve an MFCC handle of the same W, S,
+ * width, dyn and norm: D, the carried rows, mfx_sessions_set_online_norm, _set_transform and _set_rates are unchanged, and all
+ * batch attachments work (mfx_batch_set_vad's default column -1 is the last static column: callers who want c0 pass column =
+ * 0).  Refused: mfx_batch_set_alphas with MFX_ERR_CONFIG (there is no Kaldi VTLN warp; mfx_set_alpha has no effect), and the
+ * streaming entries (mfx_set_input, mfx_flush, mfx_apply, mfx_apply_alphas, mfx_get_output_data[_alpha]) with MFX_ERR_STATE
+ * and a message that names the batch entries.
+ * Not served: dither, use_energy / raw_energy / energy_floor, htk_compat, snip_edges = false, vtln_warp, W > 512, stereo. */
+
 /* mfx_config.engine bits */
 #define MFX_ENGINE_NO_FRONT1024 1 /* 1024-point short-window configurations stay on the generic long-transform kernel  */
 #define MFX_ENGINE_NO_FRONT2048 4 /* 2048-point short-window configurations stay on the generic long-transform kernel  */
@@ -232,6 +280,11 @@ const char *mfx_status_string(int status);
 int mfx_abi_version(void);
 /* 1 when this library computes mfx_config.method `method` (MFX_METHOD_*), else 0 */
 int mfx_method_supported(int32_t method);
+/* The three frame options of a Kaldi handle (MFX_METHOD_KALDI); after mfx_create Kaldi's defaults are in force: 0.97f, 1, 1.
+ * MFX_ERR_CONFIG on a handle of another method; MFX_ERR_ARG for a preemph_coeff outside [0, 1] or not finite, or a flag other
+ * than 0 / 1; MFX_ERR_STATE while sessions exist (an open stream's bits must not change under it: mfx_sessions_create(h, 0, 0)
+ * first).  It works on a planning handle, waits for the handle's streams, and allocates nothing. */
+int mfx_kaldi_set_options(mfx_handle *h, float preemph_coeff, int32_t remove_dc_offset, int32_t use_power);
 
 /* ---- streaming parameterizer interface, one function per ParamBase method (parambase.h:23-32) ---- */
 
@@ -1039,6 +1092,15 @@ int32_t mfx_host_session_stft_step(int32_t dft_size, int32_t shift, int64_t stat
  * back; 1, 2 or 4: that packing.  MFX_ERR_ARG outside the method's limits or for another *groups.  UNSTABLE, a test /
  * inspection aid only, as mfx_host_stft_lds_bytes. */
 int64_t mfx_host_sess_stft_lds_bytes(int32_t dft_size, int32_t shift, int32_t num_banks, int32_t *groups);
+/* Kaldi front end (MFX_METHOD_KALDI) tables as uploaded.  mfx_host_kaldi_mel_table: weights [num_banks][fft_size / 2] (the Nyquist
+ * bin has none), beg / len [num_banks] the non-zero span of every band (len 0: none); fft_size 128, 256 or 512, high_freq by the
+ * method's rule.  mfx_host_kaldi_dct: matrix [ceps_len][num_banks] = G, row 0 is c0's.  MFX_ERR_ARG outside the method's limits.
+ * mfx_host_kaldi_lds_bytes: ALL the LDS bytes a block of k_kaldi_front asks for (the kernel has no static LDS beside them): what
+ * mfx_create holds against the 160 KB of a gfx950 block; UNSTABLE, a test / inspection aid only. */
+int mfx_host_kaldi_mel_table(int32_t num_banks, int32_t fft_size, float sample_rate, float low_freq, float high_freq,
+                             float *weights, int32_t *beg, int32_t *len);
+int mfx_host_kaldi_dct(int32_t num_banks, int32_t ceps_len, float lifter, float *matrix);
+int64_t mfx_host_kaldi_lds_bytes(int32_t window_size, int32_t shift, int32_t num_banks, int32_t ceps_len);
 
 /* ---- test taps (device -> host copies of intermediate tables; used by the parity tests) ---- */
 /* kind: 0 = mel table [2][fft_size] floats, 1 = filter_beg [num_banks+2] int32,
