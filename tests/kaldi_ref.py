@@ -26,6 +26,28 @@ def povey_window(W):
     return np.power(0.5 - 0.5 * np.cos(2.0 * np.pi * i / (W - 1)), 0.85).astype(np.float32)
 
 
+def hamming_window(W):
+    """Kaldi's window_type=hamming."""
+    i = np.arange(W, dtype=np.float64)
+    return (0.54 - 0.46 * np.cos(2.0 * np.pi * i / (W - 1))).astype(np.float32)
+
+
+def rect_window(W):
+    return np.ones(W, np.float32)
+
+
+def ramp_window(W):
+    """Asymmetric, every tap distinct, both ends non-zero: 0.2 + 0.8 / W at tap 0, 1 at tap W - 1."""
+    i = np.arange(W, dtype=np.float64)
+    return (0.2 + 0.8 * (i + 1.0) / W).astype(np.float32)
+
+
+WINDOWS = {"povey": povey_window, "hamming": hamming_window, "rect": rect_window, "ramp": ramp_window}
+
+# the frame-start predecessor: the definition's d[0]; the two seeded faults of tests/test_kaldi_windows_host.py
+PRED_FIRST, PRED_ZERO, PRED_BEFORE = "d0", "zero", "before"
+
+
 def high_abs(sample_rate, high):
     """high > 0 is absolute, else Kaldi's offset from Nyquist -- from the float32 values the configuration holds."""
     sr, hi = float(np.float32(sample_rate)), float(np.float32(high))
@@ -72,8 +94,11 @@ def dct(M, C, Q):
     return g.astype(np.float32)
 
 
-def features(pcm, window, S, M, sample_rate, low, high, C=0, Q=22.0, preemph=0.97, remove_dc=True, use_power=True, energies=False):
-    """Rows [T][C or M] in float64.  energies: the mel energies before the floor and the log, [T][M]."""
+def features(pcm, window, S, M, sample_rate, low, high, C=0, Q=22.0, preemph=0.97, remove_dc=True, use_power=True, energies=False,
+             predecessor=PRED_FIRST):
+    """Rows [T][C or M] in float64.  energies: the mel energies before the floor and the log, [T][M].
+    predecessor (tests only; the default is the definition): what e[0] takes for d[-1] -- PRED_FIRST d[0], PRED_ZERO 0,
+    PRED_BEFORE the sample in front of the frame less the frame's mean (d[0] at sample 0 of the utterance)."""
     pcm = np.asarray(pcm, np.int16)
     w = np.asarray(window, np.float32).astype(np.float64)
     W = w.size
@@ -93,7 +118,16 @@ def features(pcm, window, S, M, sample_rate, low, high, C=0, Q=22.0, preemph=0.9
     else:
         d = x
     c = float(np.float32(preemph))
-    prev = np.concatenate([d[:, :1], d[:, :-1]], axis=1)
+    if predecessor == PRED_FIRST:
+        first = d[:, :1]
+    elif predecessor == PRED_ZERO:
+        first = np.zeros((T, 1))
+    else:
+        assert predecessor == PRED_BEFORE
+        at = np.arange(T) * S - 1
+        before = pcm[np.maximum(at, 0)].astype(np.float64) - (mean if remove_dc else 0.0)
+        first = np.where(at >= 0, before, d[:, 0])[:, None]
+    prev = np.concatenate([first, d[:, :-1]], axis=1)
     e = d - c * prev
     z = np.zeros((T, N))
     z[:, :W] = e * w[None, :]

@@ -51,17 +51,19 @@ def converted_count(pkg, rate, N, final):
     return -(-N * L // M) if final else max(0, -(-(N - Wh) * L // M))
 
 
-def twins(pkg, xs, rates, setup=None, norm=0):
+def twins(pkg, xs, rates, setup=None, norm=0, make_handle=None):
     """The batch twins: every stream as one utterance of one batch under mfx_batch_plan_rates (an utterance's samples and
     rows do not depend on its neighbours: tests/test_resample_gpu.py).  Returns per stream (converted [J][ch], rows); a
-    stream without samples has neither, by the definition (N_out = 0, T = 0)."""
+    stream without samples has neither, by the definition (N_out = 0, T = 0).  make_handle(pkg, channels=, norm=): the handle
+    of another configuration at SR (default: this module's make)."""
+    mk = make_handle or make
     ch = xs[0].shape[1]
     if not any(len(x) for x in xs):
-        m = make(pkg, channels=ch, norm=norm)
+        m = mk(pkg, channels=ch, norm=norm)
         width = m.get_output_data_width()
         m.close()
         return [(np.zeros((0, ch), np.int16), np.zeros((0, width), np.float32)) for x in xs]
-    m = make(pkg, channels=ch, norm=norm)
+    m = mk(pkg, channels=ch, norm=norm)
     offs, pos, parts = [], 0, []
     for x in xs:
         offs.append(pos)
@@ -86,8 +88,8 @@ def twins(pkg, xs, rates, setup=None, norm=0):
     return out
 
 
-def twin(pkg, x, rate, setup=None, norm=0):
-    return twins(pkg, [x], [rate], setup, norm)[0]
+def twin(pkg, x, rate, setup=None, norm=0, make_handle=None):
+    return twins(pkg, [x], [rate], setup=setup, norm=norm, make_handle=make_handle)[0]
 
 
 # ---- cut patterns: lists of (length, final) -------------------------------------------------------------------------------

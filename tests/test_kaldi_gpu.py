@@ -1,7 +1,13 @@
-"""The Kaldi front end (MFX_METHOD_KALDI: k_kaldi_front) on the MI355X against the float64 oracle of tests/kaldi_ref.py at the
-project bar (conftest.assert_close: 1e-4 of scale, 1e-5 rel-L2), the bit contract of the method -- rows do not depend on the
-batch, the offset, the run, the entry or the placement --, and its composition with the stages behind it, each against the
-restatement the project already has for that stage.  Shapes are W / S / M / C.
+"""The Kaldi front end (MFX_METHOD_KALDI: k_kaldi_front) on the MI355X, under the Povey window, against the float64 oracle of
+tests/kaldi_ref.py at the project bar (conftest.assert_close: 1e-4 of scale, 1e-5 rel-L2), the bit contract of the method at W =
+400 -- rows do not depend on the batch, the offset, the run, the entry or the placement --, and its composition with the stages
+behind it, each against the restatement the project already has for that stage.  Shapes are W / S / M / C.
+
+Every test here runs under the Povey window, whose taps 0 and W - 1 are exactly zero: the frame-start rule, the end taps and the
+i1 < W guard of an odd W cannot move a row of this module.  Windows other than Povey, the shapes where the kernel's layout or
+its guards change, and the bit contract and the sessions away from W = 400 are held in tests/test_kaldi_windows_gpu.py (its
+inputs' power is shown on the CPU in tests/test_kaldi_windows_host.py); the other batch attachments and the session transform
+and rates on a Kaldi handle in tests/test_kaldi_compose_gpu.py.
 
 Room under the bar.  A float32 restatement of the pipeline on the CPU (float32 mean, pre-emphasis and window product, torch's
 float32 rfft, float32 tables, mel product and log) against the float64 oracle, on the utterances used here:
