@@ -551,7 +551,9 @@ int create_impl(const mfx_config *cfg, int hip_device, bool planning, mfx_handle
         hipDeviceProp_t prop;
         if (!planning && hipGetDeviceProperties(&prop, hip_device) == hipSuccess && prop.multiProcessorCount > 0)
             h->num_cus = prop.multiProcessorCount;
-        h->fuse.enabled = (h->cfg.engine & MFX_ENGINE_FUSE_DELTA) != 0;
+        h->fuse.off = (h->cfg.engine & MFX_ENGINE_NO_FUSE_DELTA) != 0;
+        h->fuse.enabled = !h->fuse.off && (h->cfg.engine & MFX_ENGINE_FUSE_DELTA) != 0;
+        h->fuse.share = (h->cfg.engine & MFX_ENGINE_FUSE_NO_SHARE) ? 0 : (h->cfg.engine & MFX_ENGINE_FUSE_SHARE_ALL) ? 2 : 1;
     }
     // rows of the frame that carry window taps: 32 samples per row, or 16 / 8 / 4 in the zero-stuffed forms
     h->nm16 = h->stuff256 ? (h->W + h->W2 / 16 - 1) / (h->W2 / 16) : (h->W + 31) / 32;

@@ -118,7 +118,8 @@ struct RunMode {
                             // and the delta kernel emits whole [static | d | dd] rows: every HBM write is then a full line
                             // (13-float row pieces at a 156-byte pitch cost 1.5x their size in 32-byte sectors).
     bool fuse;              // Fused delta stage: the 512-point kernel's last wave per block turns the statics into whole
-                            // output rows while the other 15 produce them; no separate delta launch.
+                            // output rows while the other 15 produce them, and help it with the block's last tiles once their
+                            // frames are over; no separate delta launch.
     bool split_tail;        // Overlap (opt-in, mfx_batch_overlap): the delta/normalisation tail runs on a second stream behind
                             // an event, so the memory-bound tail of batch i shares the GPU with the compute-bound front end of
                             // batch i+1; the statics scratch is double buffered and the front end of batch i+2 waits for tail i.
@@ -148,10 +149,15 @@ RunMode decide_mode(const mfx_handle *h, FrontParams &p, float *d_out, bool whol
     m.via_scratch = compact_statics(m.kind, p) && h->l1 > 0 && h->cols <= 16 && !h->traps && !norm_before &&
                     B.d_static16[m.sb].n >= (size_t)B.total_rows * 16;
     m.fuse = whole && h->fuse.planned && m.kind == kFront512 && m.via_scratch && ((uintptr_t)m.d_pre & 15) == 0;
+    // Not asked for (MFX_ENGINE_FUSE_DELTA): the plain run only -- the planner has looked at the batch's size; nothing
+    // attached, no overlap in force (the fused form has no tail to put on the second stream)
+    if (m.fuse && !h->fuse.enabled)
+        m.fuse = !B.ov.enabled && !B.rs.on && !B.va.on && !B.xf.on && !B.spk.on && !B.vad.on && !B.on.on && !B.pt.on && !B.pf.on && !B.tn.on;
     if (m.fuse) {
         p.dl1 = h->l1;
         p.dl2 = h->l2;
         p.done_words = h->fuse.done_words;
+        p.dshare = delta_share_fits(h->l1, h->l2) ? h->fuse.share : 0; // (orders whose sub-tile does not fit: the delta wave alone)
         m.fuse = p.dct_mode == 1 && front512_delta_lds_bytes(p) <= kLdsCap;
     }
     m.split_tail = whole && B.ov.enabled && m.via_scratch && !m.fuse;
@@ -194,6 +200,7 @@ int run_front(mfx_handle *h, FrontParams &p, const RunMode &m, int u0, int u1, i
         p.spec = h->d_spec.p; // unused by this kernel; a -DMFX_DSTAMPS dev build drops the delta wave's tick counts here
         ProfScope ps(h);
         HIP_TRY(h, launch_front512_delta(p, B.aligned, h->nm16, h->stream));
+        ++h->fuse.runs;
     } else {
         FrontWork w;
         w.h_chunks = B.h_chunks.data() + c0, w.d_chunks = B.d_chunks.p + c0, w.n_chunks = (size_t)(c1 - c0);
@@ -509,9 +516,10 @@ extern "C" int mfx_batch_run_host(mfx_handle *h, const int16_t *pcm, int64_t pcm
     for (int u = 1; u < h->batch.n_utt && ascending; ++u) ascending = in_off[u] >= in_off[u - 1] + in_len[u - 1];
     const int K = (int)std::min<int64_t>(8, h->batch.n_utt / 4);
     // (a speaker list in force: a speaker may span slices, the batch goes through whole)
+    // (the fused delta stage asked for: it runs on whole batches only; not asked for, it yields to the slices)
     // (a packing VAD in force: an utterance's destination depends on the slices in front of it, the batch goes through whole)
     const bool packing = h->batch.vad.on && h->batch.vad.mode == MFX_VAD_PACK;
-    if (K >= 2 && ascending && !h->batch.ov.enabled && !h->fuse.planned && !h->batch.spk.on && !packing && n_in * sizeof(int16_t) >= ((size_t)32 << 20) &&
+    if (K >= 2 && ascending && !h->batch.ov.enabled && !(h->fuse.planned && h->fuse.enabled) && !h->batch.spk.on && !packing && n_in * sizeof(int16_t) >= ((size_t)32 << 20) &&
         is_pinned_host(pcm) && is_pinned_host(out)) {
         if (!h->batch.host.stream_up) {
             HIP_TRY(h, hipStreamCreateWithFlags(&h->batch.host.stream_up, hipStreamNonBlocking));

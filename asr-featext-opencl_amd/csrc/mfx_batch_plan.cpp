@@ -1,5 +1,5 @@
 // mfx_batch_plan.cpp -- the planners of the batch interface of include/mfx.h: chunks and segments of an utterance list
-// (mfx_batch_plan), the same behind a sample-rate converter (mfx_batch_plan_rates), the opt-in fused-delta plan.  Running
+// (mfx_batch_plan), the same behind a sample-rate converter (mfx_batch_plan_rates), the fused-delta plan.  Running
 // a plan is mfx_batch.cpp, what is attached to one mfx_batch_attach.cpp.  This file owns the plan proper of the handle's
 // `batch`, its `rs` and `fuse`.
 #include "mfx_handle.h"
@@ -94,7 +94,12 @@ int plan_fused_delta(mfx_handle *h)
     const std::vector<int64_t> &T_of = h->batch.utt_frames;
     h->fuse.planned = false;
     const size_t n = h->batch.h_chunks.size();
-    if (!h->fuse.enabled || !h->fast512 || h->stuff256 || h->channels != 1 || h->l1 <= 0 || h->cols > 16 || h->ceps <= 0 || h->D > 16 || n == 0 ||
+    // (asked for: any batch; not asked for: batches of kFuseMinFrames .. kFuseMaxFrames frames -- decide_mode has the rest of
+    // that gate)
+    int64_t frames = 0;
+    for (const int64_t T : T_of) frames += T;
+    if (h->fuse.off || (!h->fuse.enabled && (frames < kFuseMinFrames || frames > kFuseMaxFrames))) return MFX_OK;
+    if (!h->fast512 || h->stuff256 || h->channels != 1 || h->l1 <= 0 || h->cols > 16 || h->ceps <= 0 || h->D > 16 || n == 0 ||
         n > 0x3fffffff || (h->cfg.norm != MFX_NORM_NONE && !h->cfg.norm_after_dyn))
         return MFX_OK;
     const int D = h->D;
@@ -126,6 +131,9 @@ int plan_fused_delta(mfx_handle *h)
         const size_t cnt = fch.size() - base;
         max_list = std::max(max_list, cnt);
         fuse_block_tiles(h, fch.data() + base, cnt, own0, own0 + (c1 - c0), c0, tiles);
+        // the block's claim word counts its tiles in 16 bits (claim_init): a list beyond that -- tens of thousands of
+        // utterances of a frame or two per block -- takes the separate delta kernel
+        if (tiles.size() - (size_t)toff[b] > (size_t)kClaimMaxTiles) return MFX_OK;
     }
     coff[B] = (int32_t)fch.size();
     toff[B] = (int32_t)tiles.size();
@@ -399,4 +407,36 @@ extern "C" int mfx_batch_resample_layout(const mfx_handle *h, int64_t *offsets, 
     if (lengths) std::copy(h->batch.utt_len.begin(), h->batch.utt_len.end(), lengths);
     if (total) *total = h->batch.rs.total;
     return MFX_OK;
+}
+
+// the fused delta stage: what the plan and the runs so far say (unstable, like the engine bits that steer it)
+extern "C" int mfx_batch_fuse_info(const mfx_handle *h, int32_t *planned, int32_t *share, int64_t *runs, int64_t *min_frames,
+                                   int64_t *max_frames)
+{
+    if (!h) return MFX_ERR_ARG;
+    if (planned) *planned = h->fuse.planned ? 1 : 0;
+    if (share) *share = delta_share_fits(h->l1, h->l2) ? h->fuse.share : 0;
+    if (runs) *runs = h->fuse.runs;
+    if (min_frames) *min_frames = kFuseMinFrames;
+    if (max_frames) *max_frames = kFuseMaxFrames;
+    return MFX_OK;
+}
+
+extern "C" int32_t mfx_host_delta_tile_lds_floats(int32_t rows, int32_t l1, int32_t l2, int32_t *shares)
+{
+    if (shares) *shares = delta_share_fits(l1, l2) ? 1 : 0;
+    return delta_tile_lds_floats(rows, l1, l2);
+}
+
+extern "C" int64_t mfx_host_fuse_claim(int64_t word, int32_t from_head, int32_t *tile)
+{
+    if (!tile) return -1;
+    if (word < 0) return *tile >= 0 && *tile <= kClaimMaxTiles ? (int64_t)claim_init(*tile) : -1;
+    const uint32_t w = (uint32_t)word;
+    if (claim_empty(w)) {
+        *tile = -1;
+        return word;
+    }
+    *tile = from_head ? claim_head_tile(w) : claim_tail_tile(w);
+    return (int64_t)(from_head ? claim_take_head(w) : claim_take_tail(w));
 }

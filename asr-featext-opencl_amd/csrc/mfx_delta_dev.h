@@ -1,4 +1,4 @@
-// mfx_delta_dev.h -- the delta stage's device code shared by k_delta16 (mfx_tail.hip) and the opt-in fused delta wave of
+// mfx_delta_dev.h -- the delta stage's device code shared by k_delta16 (mfx_tail.hip) and the fused delta stage of
 // k_front512 (mfx_front512.hip): one arithmetic, the same bits (deltacpu.cpp:16-29, mfcccpu.cpp:234-263).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -80,7 +80,7 @@ __device__ __forceinline__ void lds_put4(float *dst, float4 v, int nvalid)
 // LDS floats the delta wave needs: staged statics + deltas (16-float rows) and the output tile
 __host__ __device__ inline int delta_wave_lds_floats(int l1, int l2)
 {
-    return ((kDeltaRows + 2 * (l1 + l2)) + (kDeltaRows + 2 * l2)) * 16 + kDeltaRows * 48 + 8;
+    return delta_tile_lds_floats(kDeltaRows, l1, l2);
 }
 
 // One tile of the delta stage, rows of <= 16 columns, executed by NT threads (`lane` = thread index): rows
@@ -90,10 +90,12 @@ __host__ __device__ inline int delta_wave_lds_floats(int l1, int l2)
 // staged in LDS as 16-float rows; the finished rows are assembled in LDS exactly as they lie in memory
 // (same position modulo 16 bytes) and leave as aligned 16-byte stores of consecutive lanes.
 // `out` must be 16-byte aligned and out_pitch == cols * (l2 > 0 ? 3 : 2).
-// The statics of one tile on their way from memory: (64 + 32) staged rows x 4 quads over NT threads.
-template <int NT>
+// The statics of one tile on their way from memory: (TR + 32) staged rows x 4 quads over NT threads.
+// TR = rows the tile's LDS layout is sized for (rows <= TR): kDeltaRows for k_delta16 and the fused delta wave, kDeltaShareRows
+// for the sub-tiles of a helper wave of the fused kernel.
+template <int NT, int TR = kDeltaRows>
 struct DeltaFill {
-    static constexpr int kFill = (96 * 4 + NT - 1) / NT;
+    static constexpr int kFill = ((TR + 32) * 4 + NT - 1) / NT;
     float4 v[kFill];
     // issue the loads of rows [r0 - D, r0 + rows + D) of the segment (clamped, mfcccpu.cpp:243-256)
     __device__ __forceinline__ void issue(const Segment &sg, int r0, int rows, int D, const float *__restrict__ src, int lane)
@@ -111,10 +113,10 @@ struct DeltaFill {
     }
 };
 
-template <int L1, int L2, int NT>
+template <int L1, int L2, int NT, int TR = kDeltaRows>
 __device__ __forceinline__ void delta_tile16(const Segment &sg, int r0, int rows, const float *__restrict__ src,
                                              float *__restrict__ out, int out_pitch, int cols, int l1, int l2,
-                                             float *smem, int lane, DeltaFill<NT> &fill, int next_r0, int next_rows,
+                                             float *smem, int lane, DeltaFill<NT, TR> &fill, int next_r0, int next_rows,
                                              unsigned long long *ph = nullptr)
 {
     // `fill` holds this tile's loads (DeltaFill::issue); once they are staged in LDS the loads of the
@@ -126,7 +128,7 @@ __device__ __forceinline__ void delta_tile16(const Segment &sg, int r0, int rows
         else
             __syncthreads();
     };
-    constexpr int kFill = DeltaFill<NT>::kFill;
+    constexpr int kFill = DeltaFill<NT, TR>::kFill;
     float4(&v)[kFill] = fill.v;
 #ifdef MFX_DSTAMPS
     unsigned long long ph_last, ph_t;
@@ -143,14 +145,14 @@ __device__ __forceinline__ void delta_tile16(const Segment &sg, int r0, int rows
 #endif
     const int D = l1 + l2;
     float4 *s_pad4 = (float4 *)smem;                      // [rows + 2D][4]
-    float4 *s_d4 = s_pad4 + (kDeltaRows + 2 * D) * 4;     // [rows + 2*l2][4]
-    float *s_out = (float *)(s_d4 + (kDeltaRows + 2 * l2) * 4); // the output tile, phase-shifted (below)
+    float4 *s_d4 = s_pad4 + (TR + 2 * D) * 4;             // [rows + 2*l2][4]
+    float *s_out = (float *)(s_d4 + (TR + 2 * l2) * 4);   // the output tile, phase-shifted (below)
     const int stat_row = sg.static_off - sg.shift;        // s_pad row that holds the static part of output row 0
     // first output dword of the tile, and its position inside a 16-byte group
     const int64_t g0 = (sg.out_row0 + r0) * (int64_t)out_pitch;
     const int phase = (int)(g0 & 3);
     float *so = s_out + phase;                            // so[rr * out_pitch + cc]
-    const int n_pad4 = (rows + 2 * D) * 4;   // <= (64 + 32) * 4 quads
+    const int n_pad4 = (rows + 2 * D) * 4;   // <= (TR + 32) * 4 quads
     PSTAMP(0);
 #pragma unroll
     for (int j = 0; j < kFill; ++j) {

@@ -76,6 +76,46 @@ __device__ __forceinline__ int dct_q_pos(int m) { return kDctQPad * (m / kDctQ) 
 #define DSTAMP(i)
 #endif
 
+// ---- the fused delta stage's two pieces of synchronisation, as functions: lambdas in the kernel body, though never called in the
+// builds without FUSE, moved two pointers of their mel walk to other registers.
+// One claim on the block's tile list (claim word at s_claim: claim_init, mfx_kernels.h): the claimed tile's index in the list,
+// the same on every lane; -1: the list is exhausted.  Wave-uniform control: the word travels in a scalar register, lane 0 makes
+// the exchange; a failed exchange returns the word as it stands, so every retry follows another wave's claim.
+__device__ __forceinline__ int fuse_claim_tile(unsigned *s_claim, int lane, bool from_head)
+{
+    unsigned w = __builtin_amdgcn_readfirstlane(__hip_atomic_load(s_claim, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+    while (!claim_empty(w)) {
+        unsigned seen = w;
+        if (lane == 0)
+            __hip_atomic_compare_exchange_strong(s_claim, &seen, from_head ? claim_take_head(w) : claim_take_tail(w),
+                                                 __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        seen = __builtin_amdgcn_readfirstlane(seen);
+        if (seen == w) return from_head ? claim_head_tile(w) : claim_tail_tile(w);
+        w = seen;
+    }
+    return -1;
+}
+// Wait for chunks lo .. hi of the block's list (their bits in s_done), then acquire their statics; false: the bounded wait ran
+// out (never expected: reported through err_flag, not hung on)
+__device__ __forceinline__ bool fuse_tile_ready(const unsigned *s_done, int lo, int hi, int lane, int32_t *err_flag)
+{
+    bool ok = false;
+    for (int spins = 0; spins < (1 << 22); ++spins) {
+        ok = true;
+        for (int w = lo >> 5; w <= (hi >> 5); ++w) {
+            const int b0 = max(lo - 32 * w, 0), b1 = min(hi - 32 * w, 31);
+            const unsigned mask = (b1 == 31 ? 0xffffffffu : ((1u << (b1 + 1)) - 1u)) & ~((1u << b0) - 1u);
+            const unsigned v = __hip_atomic_load(&s_done[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if ((v & mask) != mask) ok = false;
+        }
+        if (ok) break;
+        __builtin_amdgcn_s_sleep(8);
+    }
+    if (!ok && lane == 0 && err_flag) atomicExch(err_flag, 1);
+    if (ok) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    return ok;
+}
+
 // STUFF: a 256-POINT transform on this core.  The 512-point real DFT of the frame with a zero after every sample,
 // y[2n] = x[n], y[2n+1] = 0, is X_256[k mod 256]: the packed sequence is z[n] = x[n] + 0i, one sample per lane and row (16-bit
 // loads, 16 samples per row, any alignment), and bins 0 .. 128 of the result are the 256-point spectrum -- the same arithmetic
@@ -115,9 +155,17 @@ __global__ void __launch_bounds__(kThreads, 4) k_front512(FrontParams p) // (4 w
     const int tail_floats = delta_floats > 4 * kSlot ? delta_floats : 4 * kSlot;
     int *s_ctr = (int *)(s_dct + dct_floats + (kWaves - 1) * (4 * kSlot) + tail_floats); // block-local work counter
     unsigned *s_done = (unsigned *)(s_ctr + 4);   // FUSE: bit k = chunk k of this block's list has its statics in memory
+    // (FUSE: the claim word of the block's tile list sits beside the work counter, at s_ctr + 1: claim_init, mfx_kernels.h)
     if (tid == 0) *s_ctr = 0;
-    if (FUSE)
+    if (FUSE) {
+        if (tid == 0) {
+            *(unsigned *)(s_ctr + 1) = claim_init(p.blk_tile_off[blockIdx.x + 1] - p.blk_tile_off[blockIdx.x]);
+#ifdef MFX_DSTAMPS
+            s_ctr[2] = s_ctr[3] = 0; // tiles taken by helpers, helpers that are through
+#endif
+        }
         for (int i = tid; i < p.done_words; i += kThreads) s_done[i] = 0u;
+    }
 
     for (int i = tid; i < 256; i += kThreads) { // HBM tables are [lane][m] as well
         stage_lane_row(s_win, p.winpair, i);
@@ -148,44 +196,33 @@ __global__ void __launch_bounds__(kThreads, 4) k_front512(FrontParams p) // (4 w
     __syncthreads();
 
     // ---- FUSE: the delta wave (kept in the kernel: as a function of its own it changes the FUSE builds' registers).
-    // It consumes the block's tiles in order; a tile is ready once the
+    // The block's tiles are claimed through one word in LDS (claim_init, mfx_kernels.h): the delta wave takes them in ascending
+    // order from the head of the list; a front-end wave whose chunk draw has run past the block's list takes them in
+    // descending order from the tail (p.dshare; below the frame loop).  The compare-exchange of the claim alone decides who
+    // works a tile: none is worked twice, none is skipped.  A tile is ready once the
     // chunks it reads (its own rows and up to D rows either side) have their bits set in s_done.  The
-    // front-end waves only ever produce, so the wait cannot deadlock; it is bounded all the same.
+    // front-end waves only ever produce -- a helper has produced everything it ever will before its first claim, and the
+    // waves it waits for wait for nobody -- so the wait cannot deadlock; it is bounded all the same.
     const int chunk_base = FUSE ? p.blk_chunk_off[blockIdx.x] : 0;
     const int chunk_cnt = FUSE ? p.blk_chunk_off[blockIdx.x + 1] - chunk_base : 0;
     if (FUSE && wave == kWaves - 1) {
         __builtin_amdgcn_s_setprio(3); // little work, but everything it does is on the block's critical path
-        const int t_end = p.blk_tile_off[blockIdx.x + 1];
-        int t = p.blk_tile_off[blockIdx.x];
-        if (t >= t_end) return;
-        DeltaTile T = p.tiles[t];
+        if (p.dshare == 2 && delta_share_fits(p.dl1, p.dl2)) return; // (helpers take every tile)
+        const int tile_base = p.blk_tile_off[blockIdx.x];
+        int t = fuse_claim_tile((unsigned *)(s_ctr + 1), lane, true);
+        if (t < 0) return;
+        DeltaTile T = p.tiles[tile_base + t];
 #ifdef MFX_DSTAMPS
-        unsigned long long ds_acc[4] = {0, 0, 0, 0}, ds_last, ds_t, ds_ph[4] = {0, 0, 0, 0};
+        unsigned long long ds_acc[4] = {0, 0, 0, 0}, ds_last, ds_t, ds_ph[4] = {0, 0, 0, 0}, ds_tiles = 0;
         asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ds_last)::"memory");
         const unsigned long long ds_begin = ds_last;
 #endif
-        for (; t < t_end; ++t) {
-            // the next descriptor is fetched while this tile is worked on (one past the end is a valid
-            // address: the host pads the tile array by one entry)
-            const DeltaTile nxt = p.tiles[t + 1];
+        for (; t >= 0; t = fuse_claim_tile((unsigned *)(s_ctr + 1), lane, true)) {
+            // the next descriptor is fetched while this tile is worked on: only this wave claims from the head, so its next
+            // tile, if it gets one, is t + 1 (one past the end is a valid address: the host pads the tile array by one entry)
+            const DeltaTile nxt = p.tiles[tile_base + t + 1];
             const int lo = __builtin_amdgcn_readfirstlane(T.dep_lo), hi = __builtin_amdgcn_readfirstlane(T.dep_hi);
-            bool ok = false;
-            for (int spins = 0; spins < (1 << 22); ++spins) {
-                ok = true;
-                for (int w = lo >> 5; w <= (hi >> 5); ++w) {
-                    const int b0 = max(lo - 32 * w, 0), b1 = min(hi - 32 * w, 31);
-                    const unsigned mask = (b1 == 31 ? 0xffffffffu : ((1u << (b1 + 1)) - 1u)) & ~((1u << b0) - 1u);
-                    const unsigned v = __hip_atomic_load(&s_done[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    if ((v & mask) != mask) ok = false;
-                }
-                if (ok) break;
-                __builtin_amdgcn_s_sleep(8);
-            }
-            if (!ok) { // never expected: report instead of hanging
-                if (lane == 0 && p.err_flag) atomicExch(p.err_flag, 1);
-                return;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            if (!fuse_tile_ready(s_done, lo, hi, lane, p.err_flag)) return;
             DSTAMP(0);
             Segment sg;
             sg.src_row0 = sg.out_row0 = T.seg_row0;
@@ -209,14 +246,17 @@ __global__ void __launch_bounds__(kThreads, 4) k_front512(FrontParams p) // (4 w
                                        0, 0, php);
             DSTAMP(1);
             T = nxt;
+#ifdef MFX_DSTAMPS
+            ++ds_tiles;
+#endif
         }
 #ifdef MFX_DSTAMPS
-        if (lane == 0 && p.spec) { // 100 MHz ticks: waiting, working, whole life, tiles
+        if (lane == 0 && p.spec) { // 100 MHz ticks: waiting, working, whole life; tiles this wave took
             unsigned long long *o = (unsigned long long *)p.spec + (size_t)blockIdx.x * 8;
             o[0] = ds_acc[0];
             o[1] = ds_acc[1];
             o[2] = ds_last - ds_begin;
-            o[3] = (unsigned long long)(t_end - p.blk_tile_off[blockIdx.x]);
+            o[3] = ds_tiles;
             for (int i = 0; i < 4; ++i) o[4 + i] = ds_ph[i];
         }
 #endif
@@ -512,6 +552,55 @@ __global__ void __launch_bounds__(kThreads, 4) k_front512(FrontParams p) // (4 w
         c_nxt = chunk_of(__builtin_amdgcn_readfirstlane(v_nn));
         cnxt = make_ctx(c_nxt);
         v_nn = next_index();
+    }
+    // ---- FUSE, tile sharing: this wave's frames are over (its chunk draw ran past the block's list), its four frame slots are
+    // free.  It works off tiles from the tail of the block's list, each as sub-tiles of kDeltaShareRows rows staged in those
+    // slots, until the list is exhausted.  Same readiness test, same bounded wait and same arithmetic as the delta wave.
+    // (the host sets dshare by the same formula.  The branch hint only moves this block in the layout, and with it the frame
+    // loop's register allocation: hinted, the aligned FUSE builds keep the scratch they had with the delta wave alone
+    // (0 and 20 bytes), the unaligned ones keep theirs (48 and 48 -> 44) without it; the other way round each gains 4 - 8 bytes)
+    if constexpr (FUSE) if (const bool helps = p.dshare && delta_share_fits(p.dl1, p.dl2); ALIGNED ? __builtin_expect(helps, 0) : helps) {
+#ifdef MFX_DSTAMPS
+        int hs_tiles = 0;
+#endif
+        const int tile_base = p.blk_tile_off[blockIdx.x]; // (read here: nothing more in registers across the frame loop)
+        for (int t = fuse_claim_tile((unsigned *)(s_ctr + 1), lane, false); t >= 0; t = fuse_claim_tile((unsigned *)(s_ctr + 1), lane, false)) {
+            const DeltaTile T = p.tiles[tile_base + t];
+            const int lo = __builtin_amdgcn_readfirstlane(T.dep_lo), hi = __builtin_amdgcn_readfirstlane(T.dep_hi);
+            if (!fuse_tile_ready(s_done, lo, hi, lane, p.err_flag)) return;
+            Segment sg;
+            sg.src_row0 = sg.out_row0 = T.seg_row0;
+            sg.n_out = 0;
+            sg.shift = T.shift;
+            sg.lo = T.lo;
+            sg.hi = T.hi;
+            sg.static_off = T.static_off;
+            sg.pad = 0;
+            const int n_rows = __builtin_amdgcn_readfirstlane(T.n_rows);
+            DeltaFill<64, kDeltaShareRows> fill;
+            fill.issue(sg, T.r0, min(n_rows, kDeltaShareRows), p.dl1 + p.dl2, p.feat, lane);
+            for (int r = 0; r < n_rows; r += kDeltaShareRows) {
+                const int rows = min(n_rows - r, kDeltaShareRows);
+                const int nrows = max(min(n_rows - r - kDeltaShareRows, kDeltaShareRows), 0); // the next sub-tile's loads fly meanwhile
+                if (p.dl1 == 3 && p.dl2 == 3)
+                    delta_tile16<3, 3, 64, kDeltaShareRows>(sg, T.r0 + r, rows, p.feat, p.out, p.out_pitch, cols, 3, 3, s_wave, lane,
+                                                            fill, T.r0 + r + kDeltaShareRows, nrows);
+                else
+                    delta_tile16<0, 0, 64, kDeltaShareRows>(sg, T.r0 + r, rows, p.feat, p.out, p.out_pitch, cols, p.dl1, p.dl2, s_wave,
+                                                            lane, fill, T.r0 + r + kDeltaShareRows, nrows);
+            }
+#ifdef MFX_DSTAMPS
+            ++hs_tiles;
+#endif
+        }
+#ifdef MFX_DSTAMPS
+        if (lane == 0 && p.spec) { // the block's last helper through reports the tiles that helpers took
+            atomicAdd(&s_ctr[2], hs_tiles);
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+            if (atomicAdd(&s_ctr[3], 1) == kWaves - 2)
+                ((unsigned long long *)p.spec)[(size_t)gridDim.x * 8 + blockIdx.x] = (unsigned long long)atomicAdd(&s_ctr[2], 0);
+        }
+#endif
     }
 #ifdef MFX_STAMPS
     if (lane == 0 && p.spec) {

@@ -23,6 +23,9 @@
 
 constexpr int kChunkFrames = 16;           // frames per work item of the front-end kernels
 constexpr size_t kLdsCap = 160 * 1024;     // LDS a block may ask for on gfx950 (the launchers' name for it: kLdsMax, mfx_launch.h)
+constexpr int64_t kFuseMinFrames = 500000; // frames of a batch from which the fused delta stage runs without being asked for
+                                           // (profiles/r13/README.md; above every batch of the suites that pin the two-kernel path)
+constexpr int64_t kFuseMaxFrames = 2000000; // ... and up to which: on a 12.5 M-frame batch it loses 5 % to the two kernels
 constexpr size_t kSmallBlock = (size_t)1 << 20; // below this a copy kernel replaces the DMA command (streaming interface)
 
 inline constexpr const char *kMsgBuffer = "Can't process data, buffer is too small";
@@ -392,9 +395,12 @@ struct BatchState {
 
 // fused delta stage of the 512-point kernel: per-block chunk lists (own rows + halo) and delta tiles: mfx_batch.cpp
 struct FuseState {
-    bool enabled = false; // mfx_config.engine & MFX_ENGINE_FUSE_DELTA opts in to the fused delta stage (measured 1-2 % slower
-                          // than front end + k_delta on C2; kept tested, off by default)
+    bool enabled = false; // mfx_config.engine & MFX_ENGINE_FUSE_DELTA: the fused delta stage on every batch that qualifies
+    bool off = false;     // MFX_ENGINE_NO_FUSE_DELTA: never.  Neither bit: batches of kFuseMinFrames .. kFuseMaxFrames frames, with no
+                          // attachment and no overlap in force (decide_mode), and never at the price of the host entry's slices
+    int share = 1;        // FrontParams::dshare of a run whose orders fit (MFX_ENGINE_FUSE_NO_SHARE 0, MFX_ENGINE_FUSE_SHARE_ALL 2)
     bool planned = false;
+    int64_t runs = 0;     // fused launches since the handle was created (mfx_batch_fuse_info)
     int blocks = 0, done_words = 0;
     int32_t nchunks = 0;
     DevBuf<mfx::Chunk> d_chunks;

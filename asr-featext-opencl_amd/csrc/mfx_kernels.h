@@ -84,6 +84,33 @@ struct DeltaTile {
     int32_t dep_lo, dep_hi; // block-local chunk indices whose statics the tile reads (inclusive)
 };
 
+// LDS floats of one delta tile staged `tr` output rows at a time (delta_tile16<.., TR>): the statics with their 2 (l1 + l2)
+// context rows and the deltas with their 2 l2, as 16-float rows; the output rows at up to 48 floats; 8 floats for the
+// tile's position inside a 16-byte group.  One formula for the kernels and the host.
+__host__ __device__ inline int delta_tile_lds_floats(int tr, int l1, int l2)
+{
+    return ((tr + 2 * (l1 + l2)) + (tr + 2 * l2)) * 16 + tr * 48 + 8;
+}
+// Tile sharing in the fused k_front512: a front-end wave that has run out of frames works a tile off as sub-tiles of
+// kDeltaShareRows rows in its own frame slots (kDeltaShareFloats of LDS).  Orders whose sub-tile does not fit there do not
+// share: the delta wave alone walks the tiles.
+constexpr int kDeltaShareRows = 16;
+constexpr int kDeltaShareFloats = 4 * 512;
+__host__ __device__ inline bool delta_share_fits(int l1, int l2)
+{
+    return delta_tile_lds_floats(kDeltaShareRows, l1, l2) <= kDeltaShareFloats;
+}
+// The claim word of a block's tile list, in LDS: head | tail << 16, both biased by one -- tiles [head - 1, tail - 1] of the list
+// are unclaimed, and the list is exhausted when head > tail.  The delta wave claims ascending from head, helpers descending
+// from tail, each by one compare-exchange: no tile twice, none skipped.  (Host restatement for the planner's bound and tests.)
+constexpr int kClaimMaxTiles = 0xfffe;
+__host__ __device__ inline uint32_t claim_init(int n_tiles) { return 1u | ((uint32_t)n_tiles << 16); }
+__host__ __device__ inline bool claim_empty(uint32_t w) { return (w & 0xffffu) > (w >> 16); }
+__host__ __device__ inline int claim_head_tile(uint32_t w) { return (int)(w & 0xffffu) - 1; }
+__host__ __device__ inline int claim_tail_tile(uint32_t w) { return (int)(w >> 16) - 1; }
+__host__ __device__ inline uint32_t claim_take_head(uint32_t w) { return w + 1u; }
+__host__ __device__ inline uint32_t claim_take_tail(uint32_t w) { return w - 0x10000u; }
+
 // A mel lane plan (mfx::MelPlan, mfx_tables.h) as a kernel takes it: the filters dealt to the `lanes` lanes of a frame in
 // `rounds` rounds, round r padded to L[r] bins; lane j's weights for all rounds are one row of w.
 struct MelPlanArg {
@@ -158,7 +185,10 @@ struct FrontParams {
     int32_t dl1, dl2;
     int32_t n_blocks;
     int32_t done_words;       // LDS words of the per-block "chunk finished" bitmap
-    int32_t *err_flag;        // set nonzero if the delta wave gave up waiting (never expected)
+    int32_t dshare;           // tile sharing: 0 the delta wave alone, 1 idle front-end waves help from the list's tail,
+                              // 2 helpers take every tile (the delta wave claims none).  (In what was padding in front of
+                              // err_flag: the argument block of every front-end kernel keeps its size and offsets.)
+    int32_t *err_flag;        // set nonzero if a delta or helper wave gave up waiting (never expected)
 };
 
 struct MelcepParams {

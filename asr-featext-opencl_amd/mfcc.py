@@ -98,6 +98,7 @@ EXPORTED_SYMBOLS = (
     "mfx_batch_set_tensor", "mfx_batch_clear_tensor", "mfx_batch_output_bytes", "mfx_batch_tensor_shape",
     "mfx_batch_tensor_lengths", "mfx_batch_tensor_from_rows",
     "mfx_host_tensor_pack", "mfx_host_tensor_bytes", "mfx_host_tensor_lds_bytes",
+    "mfx_batch_fuse_info", "mfx_host_delta_tile_lds_floats", "mfx_host_fuse_claim",
 )
 
 
@@ -165,6 +166,9 @@ def load_library():
     L.mfx_profile_read.argtypes = [vp, C.POINTER(i32), C.POINTER(C.c_double), C.c_int]
     L.mfx_dominant_kernel_name.argtypes, L.mfx_dominant_kernel_name.restype = [vp], C.c_char_p
     L.mfx_plan_create.argtypes = [C.POINTER(MfxConfig), C.POINTER(vp)]
+    L.mfx_batch_fuse_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+    L.mfx_host_delta_tile_lds_floats.argtypes, L.mfx_host_delta_tile_lds_floats.restype = [i32, i32, i32, C.POINTER(i32)], i32
+    L.mfx_host_fuse_claim.argtypes, L.mfx_host_fuse_claim.restype = [i64, i32, C.POINTER(i32)], i64
     L.mfx_plan_set_aligned.argtypes = [vp, C.c_int]
     L.mfx_debug_read.argtypes, L.mfx_debug_read.restype = [vp, C.c_int, vp, i64], i64
     L.mfx_host_mel_table.argtypes = [i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, fp, C.POINTER(i32)]
@@ -834,6 +838,7 @@ ENGINE_NO_FRONT1024, ENGINE_FUSE_DELTA, ENGINE_NO_FRONT2048, ENGINE_STREAM_KERNE
 ENGINE_DMA_SMALL_BLOCKS, ENGINE_NO_DCT_SPLIT, ENGINE_NO_STUFF256, ENGINE_FRONT1024_12_WAVES = 32, 64, 128, 256     # mfx_config.engine bits (include/mfx.h)
 ENGINE_TRAPS_VALU, ENGINE_XFORM_VALU, ENGINE_SESS_NARROW_LOADS = 512, 1024, 2048
 ENGINE_SESS_XFORM_PLAIN, ENGINE_SESS_STFT_PLAIN = 4096, 8192
+ENGINE_FUSE_NO_SHARE, ENGINE_FUSE_SHARE_ALL, ENGINE_NO_FUSE_DELTA = 16384, 32768, 65536
 
 
 class MfccHip:
@@ -1461,6 +1466,12 @@ class MfccHip:
 
     def dominant_kernel_name(self):
         return self._L.mfx_dominant_kernel_name(self._h).decode()
+
+    def batch_fuse_info(self):
+        """(planned, share, fused launches so far, frames from / up to which a batch fuses unasked): mfx_batch_fuse_info"""
+        planned, share, runs, lo, hi = C.c_int32(0), C.c_int32(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._chk(self._L.mfx_batch_fuse_info(self._h, C.byref(planned), C.byref(share), C.byref(runs), C.byref(lo), C.byref(hi)))
+        return bool(planned.value), share.value, runs.value, lo.value, hi.value
 
     def debug_read(self, kind):
         W2, nb = self.fft_size(), self.cfg.num_banks

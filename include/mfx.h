@@ -235,8 +235,14 @@ enum { MFX_LOGMEL_WHISPER = 0, MFX_LOGMEL_LOG10 = 1, MFX_LOGMEL_LN = 2 };
                                       mel / DCT kernel) instead of the fused front ends: the rows are then the SAME BITS
                                       that set_input / apply / get_output_data deliver for a file consumed as one block
                                       (the fused kernels agree with them to float32 rounding, ~1e-6 of scale)           */
-#define MFX_ENGINE_FUSE_DELTA 2   /* 512-point batch path: delta / delta-delta computed by a wave of the front-end kernel
-                                     instead of the separate delta kernel (slower on MI355X)        */
+#define MFX_ENGINE_FUSE_DELTA 2   /* 512-point batch path: delta / delta-delta computed inside the front-end kernel (a delta
+                                     wave per block, idle front-end waves sharing its tiles) instead of the separate delta
+                                     kernel, on a batch of any size that qualifies (the same bits)  */
+#define MFX_ENGINE_FUSE_NO_SHARE 16384  /* fused delta stage: the delta wave alone works the block's tiles off              */
+#define MFX_ENGINE_FUSE_SHARE_ALL 32768 /* fused delta stage: the delta wave claims nothing, front-end waves that have run out
+                                           of frames take every tile (orders whose 16-row sub-tile does not fit a wave's frame
+                                           slots: as MFX_ENGINE_FUSE_NO_SHARE)                                             */
+#define MFX_ENGINE_NO_FUSE_DELTA 65536  /* the separate delta kernel always (wins over MFX_ENGINE_FUSE_DELTA)               */
 
 #define MFX_ENGINE_NORM_TWO_KERNELS 16 /* normaliser: statistics and apply as two launches also where one block's LDS holds a
                                           segment's rows (the one-launch form computes the same bits)                    */
@@ -933,6 +939,21 @@ int mfx_profile_read(mfx_handle *h, int32_t *launches, double *kernel_ms, int re
 /* name of the dominant (front-end) kernel of the batch entries as it appears in rocprofv3's kernel trace: what the ONE
  * dispatch rule of the library (choose_front, mfx_api.cpp) picks for this handle */
 const char *mfx_dominant_kernel_name(const mfx_handle *h);
+/* The fused delta stage of the 512-point batch path (k_front512's FUSE builds; unstable, like the MFX_ENGINE_* bits that steer
+ * it).  Without MFX_ENGINE_FUSE_DELTA it runs on planned batches of *min_frames .. *max_frames frames with nothing attached and no
+ * overlap in force (measured: it wins on a batch of a million frames and loses on one of twelve); with it, on every batch that qualifies; with MFX_ENGINE_NO_FUSE_DELTA never.  *planned: 1 when the current
+ * plan carries the fused form's block lists; *runs: fused launches since the handle was created (a run that took the separate
+ * delta kernel does not count); *share: what such a launch does with the block's tiles -- 0 the delta wave alone, 1 shared
+ * with front-end waves that have run out of frames, 2 those waves take every tile.  Any pointer may be null. */
+int mfx_batch_fuse_info(const mfx_handle *h, int32_t *planned, int32_t *share, int64_t *runs, int64_t *min_frames,
+                        int64_t *max_frames);
+/* Host restatements of what the kernel and the planner share (mfx_kernels.h).  LDS floats of a delta tile staged `rows` rows
+ * at a time; *shares: 1 when a 16-row sub-tile at these orders fits a wave's frame slots (else tiles are not shared). */
+int32_t mfx_host_delta_tile_lds_floats(int32_t rows, int32_t l1, int32_t l2, int32_t *shares);
+/* The claim word of a block's tile list.  word < 0: the initial word of a list of *tile tiles.  Else one claim from the head
+ * (from_head != 0) or the tail: the word after it, *tile = the tile claimed, or -1 with the word unchanged once the list is
+ * exhausted. */
+int64_t mfx_host_fuse_claim(int64_t word, int32_t from_head, int32_t *tile);
 /* A PLANNING handle: mfx_create's own configuration checks, host-built tables and LDS sums with every device call left
  * out -- it answers mfx_dominant_kernel_name and the geometry accessors (mfx_get_output_data_width,
  * mfx_get_input_buffer_size, mfx_estimated_window_count, mfx_max_frames_out, mfx_fft_size) without a GPU and computes
