@@ -350,7 +350,7 @@ extern "C" void mfx_destroy(mfx_handle *h)
 }
 
 namespace {
-int create_impl(const mfx_config *cfg, int hip_device, bool planning, mfx_handle **out);
+int create_impl(const mfx_config *cfg, int hip_device, bool planning, mfx_handle **out, int kaldi_flags = 0, float kaldi_energy_floor = 0.f);
 }
 
 extern "C" int mfx_create(const mfx_config *cfg, int hip_device, mfx_handle **out) { return create_impl(cfg, hip_device, false, out); }
@@ -359,6 +359,18 @@ extern "C" int mfx_create(const mfx_config *cfg, int hip_device, mfx_handle **ou
  * (mfx_get_output_data_width, mfx_get_input_buffer_size, mfx_estimated_window_count, mfx_max_frames_out, mfx_fft_size),
  * mfx_last_error and mfx_destroy are meaningful on it. */
 extern "C" int mfx_plan_create(const mfx_config *cfg, mfx_handle **out) { return create_impl(cfg, -1, true, out); }
+
+/* the two with the options of a Kaldi handle (include/mfx.h, method 7, "Options") */
+extern "C" int mfx_create_kaldi(const mfx_config *cfg, int32_t kaldi_flags, float kaldi_energy_floor, int hip_device, mfx_handle **out)
+{
+    if (cfg && out && cfg->method != MFX_METHOD_KALDI) return *out = nullptr, MFX_ERR_CONFIG;
+    return create_impl(cfg, hip_device, false, out, kaldi_flags, kaldi_energy_floor);
+}
+extern "C" int mfx_plan_create_kaldi(const mfx_config *cfg, int32_t kaldi_flags, float kaldi_energy_floor, mfx_handle **out)
+{
+    if (cfg && out && cfg->method != MFX_METHOD_KALDI) return *out = nullptr, MFX_ERR_CONFIG;
+    return create_impl(cfg, -1, true, out, kaldi_flags, kaldi_energy_floor);
+}
 
 namespace {
 struct HandleDeleter {
@@ -409,13 +421,15 @@ int create_stft(mfx_handle *h, bool planning, std::unique_ptr<mfx_handle, Handle
 }
 
 // the limits of a Kaldi handle (include/mfx.h): everything sized from W, S, M and C fits the kernel's LDS by them
-bool kaldi_config_ok(const mfx_config *cfg)
+bool kaldi_config_ok(const mfx_config *cfg, int kaldi_flags, float kaldi_energy_floor)
 {
     const int W = cfg->window_size;
     if (!kaldi_shape_ok(W, cfg->shift, cfg->num_banks, cfg->ceps_len) || (cfg->fft_size != 0 && cfg->fft_size != kaldi_fft_size(W))) return false;
     if (!kaldi_freqs_ok(cfg->sample_rate, cfg->low_freq, cfg->high_freq)) return false;
     if (cfg->want_c0 != 0 || cfg->channels > 1 || !(cfg->lift_coef >= 0.f) || !std::isfinite(cfg->lift_coef)) return false;
-    return kaldi_lds_bytes(W, cfg->shift, cfg->num_banks, cfg->ceps_len) <= kLdsCap;
+    // the options: known bits, the windowed energy only with the energy column, a floor Kaldi's log can take
+    if (!kaldi_flags_ok(kaldi_flags) || !(kaldi_energy_floor >= 0.f) || !std::isfinite(kaldi_energy_floor)) return false;
+    return kaldi_lds_bytes(W, cfg->shift, cfg->num_banks, cfg->ceps_len, kaldi_flags) <= kLdsCap;
 }
 
 // the rest of mfx_create for a Kaldi handle: geometry, the mel table and G, what the normalisers of both interfaces share; the
@@ -456,7 +470,7 @@ int create_kaldi(mfx_handle *h, bool planning, std::unique_ptr<mfx_handle, Handl
     return MFX_OK;
 }
 
-int create_impl(const mfx_config *cfg, int hip_device, bool planning, mfx_handle **out)
+int create_impl(const mfx_config *cfg, int hip_device, bool planning, mfx_handle **out, int kaldi_flags, float kaldi_energy_floor)
 {
     if (!cfg || !out) return MFX_ERR_ARG;
     *out = nullptr;
@@ -485,7 +499,7 @@ int create_impl(const mfx_config *cfg, int hip_device, bool planning, mfx_handle
     }
     const bool stft = cfg->method == MFX_METHOD_STFT_LOGMEL;
     if (stft && !stft_config_ok(cfg)) return MFX_ERR_CONFIG;
-    if (kaldi && !kaldi_config_ok(cfg)) return MFX_ERR_CONFIG;
+    if (kaldi && !kaldi_config_ok(cfg, kaldi_flags, kaldi_energy_floor)) return MFX_ERR_CONFIG;
 
     if (!planning) {
         int ndev = 0;
@@ -513,9 +527,13 @@ int create_impl(const mfx_config *cfg, int hip_device, bool planning, mfx_handle
     h->traps = traps;
     h->stft = stft;
     h->kaldi = kaldi;
+    if (kaldi) {
+        h->kaldi_flags = kaldi_flags;
+        if (kaldi_energy_floor > 0.f) h->kaldi_log_floor = (float)std::log((double)kaldi_energy_floor);
+    }
     h->traps_L = traps ? traps_L : 0;
     h->traps_K = traps ? traps_K : 0;
-    h->fcols = h->ceps > 0 ? h->dl : h->nb;
+    h->fcols = kaldi ? kaldi_static_cols(h->nb, h->ceps, h->kaldi_flags) : h->ceps > 0 ? h->dl : h->nb; // (the energy column of a Kaldi fbank)
     h->cols = traps ? h->nb * traps_K : h->fcols;
     h->width = h->cols * (cfg->dyn == MFX_DYN_ACC ? 3 : cfg->dyn == MFX_DYN_DELTA ? 2 : 1);
     h->channels = cfg->channels == 2 ? 2 : 1;
@@ -801,9 +819,14 @@ int launch_front(mfx_handle *h, FrontParams &p, FrontKind kind, bool aligned, co
         case kFront2048: HIP_TRY(h, launch_front2048(p, h->num_cus, h->stream)); break;
         case kKaldi: {
             const int32_t *meta = h->d_kaldi_mel.p; // [3][nb]
+            // (centred frames: the plan's own utterance count, and only while the bounds uploaded with that plan hold exactly
+            // its utterances -- upload() sizes the buffer to the list; anything else is 0, which launch_kaldi refuses)
+            const int32_t centred_utts =
+                (h->kaldi_flags & kKaldiNoSnipEdges) && h->d_kaldi_bounds.n == 2 * (size_t)h->batch.n_utt ? h->batch.n_utt : 0;
             KaldiParams kp{p.pcm, p.pcm_total, p.chunks, p.n_chunks, p.row_limit, h->W, h->S, h->W2, h->nb, h->ceps, h->kaldi_preemph,
                            h->kaldi_remove_dc ? 1 : 0, h->kaldi_use_power ? 1 : 0, h->d_kaldi_ops.p, h->d_kaldi_melw.p, (int32_t)h->d_kaldi_melw.n, meta, meta + h->nb,
-                           meta + 2 * h->nb, h->d_kaldi_dct_t.p, p.feat, p.feat_pitch};
+                           meta + 2 * h->nb, h->d_kaldi_dct_t.p, p.feat, p.feat_pitch, h->kaldi_flags, h->kaldi_log_floor,
+                           h->d_kaldi_bounds.p, centred_utts};
             HIP_TRY(h, launch_kaldi(kp, h->stream));
             break;
         }
@@ -848,7 +871,7 @@ extern "C" const char *mfx_dominant_kernel_name(const mfx_handle *h)
 {
     if (!h) return "";
     if (h->stft) return h->stft_form == StftForm::Fft ? "k_stft_fft_mel" : "k_stft_mel";
-    if (h->kaldi) return "k_kaldi_front";
+    if (h->kaldi) return h->kaldi_flags != 0 ? "k_kaldi_front_opts" : "k_kaldi_front";
     switch (batch_front(h)) { // names as rocprofv3 prints them
     case kFront512:
     case kSpec512: return "k_front512";
@@ -1199,6 +1222,28 @@ extern "C" int64_t mfx_host_kaldi_lds_bytes(int32_t window_size, int32_t shift, 
 {
     if (!kaldi_shape_ok(window_size, shift, num_banks, ceps_len)) return MFX_ERR_ARG;
     return (int64_t)kaldi_lds_bytes(window_size, shift, num_banks, ceps_len);
+}
+
+extern "C" int32_t mfx_kaldi_flags_supported(void) { return kKaldiFlagsAll; }
+
+extern "C" int64_t mfx_host_kaldi_lds_bytes_flags(int32_t window_size, int32_t shift, int32_t num_banks, int32_t ceps_len, int32_t flags)
+{
+    if (!kaldi_shape_ok(window_size, shift, num_banks, ceps_len) || !kaldi_flags_ok(flags)) return MFX_ERR_ARG;
+    return (int64_t)kaldi_lds_bytes(window_size, shift, num_banks, ceps_len, flags);
+}
+
+extern "C" int64_t mfx_host_kaldi_frame_count(int64_t samples, int32_t window_size, int32_t shift, int32_t flags)
+{
+    if (samples < 0 || !kaldi_shape_ok(window_size, shift, 1, 0) || !kaldi_flags_ok(flags)) return MFX_ERR_ARG;
+    return std::max<int64_t>(kaldi_frame_count(samples, window_size, shift, flags), 0);
+}
+
+extern "C" int mfx_host_kaldi_frame_samples(int64_t samples, int32_t window_size, int32_t shift, int32_t flags, int64_t t, int64_t *idx)
+{
+    if (samples < 0 || !kaldi_shape_ok(window_size, shift, 1, 0) || !kaldi_flags_ok(flags) || !idx) return MFX_ERR_ARG;
+    if (t < 0 || t >= kaldi_frame_count(samples, window_size, shift, flags)) return MFX_ERR_ARG;
+    kaldi_frame_samples(samples, window_size, shift, flags, t, idx);
+    return MFX_OK;
 }
 
 extern "C" int64_t mfx_host_frame_count(int64_t samples, int32_t window_size, int32_t shift)

@@ -358,6 +358,10 @@ extern "C" int mfx_batch_set_pitch(mfx_handle *h, int32_t window, int32_t lag_mi
     MFX_DEVICE_ENTRY(h);
     BatchState &B = h->batch;
     if (h->stft) return fail(h, MFX_ERR_CONFIG, "mfx_batch_set_pitch: an STFT log-mel handle frames its utterances centred");
+    if (h->kaldi && (h->kaldi_flags & kKaldiNoSnipEdges))
+        return fail(h, MFX_ERR_CONFIG,
+                    "mfx_batch_set_pitch: a Kaldi handle with MFX_KALDI_NO_SNIP_EDGES frames its utterances centred (the track's frames "
+                    "follow the snip-edged rule and would not line up with the rows)");
     if (!B.planned) return fail(h, MFX_ERR_STATE, "mfx_batch_set_pitch: no batch is planned");
     PitchShape s;
     if (!pitch_shape(window == 0 ? h->cfg.window_size : window, lag_min, lag_max, ballast, lag_cost, penalty, max_jump, s))

@@ -240,6 +240,9 @@ int plan_batch(mfx_handle *h, int32_t n_utt, const int64_t *offsets, const int64
     h->batch.h_stft_chunks.clear();
     // (STFT log-mel: a chunk is the run of frames one block of k_stft_mel takes)
     const int chunk_frames = h->stft ? h->stft_R : kChunkFrames;
+    // (a Kaldi handle with snip_edges = false: a chunk starts at the UNREFLECTED first tap of its first frame, which may lie in
+    // front of the utterance, and names its utterance in `pad`; k_kaldi_front mirrors the span into the utterance's bounds)
+    const bool centred = h->kaldi && (h->kaldi_flags & kKaldiNoSnipEdges);
     std::vector<Segment> segs((size_t)n_utt);
     std::vector<int64_t> &T_of = h->batch.utt_frames;
     T_of.assign((size_t)n_utt, 0);
@@ -258,10 +261,10 @@ int plan_batch(mfx_handle *h, int32_t n_utt, const int64_t *offsets, const int64
         }
         for (int64_t t0 = 0; t0 < T; t0 += chunk_frames) {
             Chunk c;
-            c.pcm_off = offsets[u] + t0 * h->S;
+            c.pcm_off = offsets[u] + (centred ? kaldi_centred_start(t0, h->W, h->S) : t0 * h->S);
             c.out_row = row + t0;
             c.n_frames = (int32_t)std::min<int64_t>(chunk_frames, T - t0);
-            c.pad = 0;
+            c.pad = centred ? u : 0;
             if (h->stft) {
                 const int32_t first = (int32_t)(h->batch.h_chunks.size() - (size_t)(t0 / chunk_frames)), count = (int32_t)((T + chunk_frames - 1) / chunk_frames);
                 h->batch.h_stft_chunks.push_back(make_stft_chunk(offsets[u], lengths[u], c.out_row, (int32_t)t0, c.n_frames, first, count));
@@ -298,6 +301,11 @@ int plan_batch(mfx_handle *h, int32_t n_utt, const int64_t *offsets, const int64
     if (total_rows) *total_rows = row;
     HIP_TRY(h, h->upload(h->batch.d_chunks, h->batch.h_chunks));
     HIP_TRY(h, h->upload(h->batch.d_segs, segs));
+    if (centred) {
+        std::vector<int64_t> bounds((size_t)n_utt * 2);
+        for (int u = 0; u < n_utt; ++u) bounds[2 * (size_t)u] = offsets[u], bounds[2 * (size_t)u + 1] = lengths[u];
+        HIP_TRY(h, h->upload(h->d_kaldi_bounds, bounds));
+    }
     if (h->cfg.norm != MFX_NORM_NONE) {
         HIP_TRY(h, h->batch.d_stats.alloc((size_t)n_utt * 3 * 2 * h->cols));
         const size_t need = norm_partial_doubles(n_utt, tiles_max * 64, h->cols);

@@ -608,6 +608,10 @@ struct mfx_handle {
     DevBuf<float> d_kaldi_ops, d_kaldi_melw, d_kaldi_dct_t; // window and FFT tables (mfx_set_window builds them); the bands' spans
                                          // back to back; G transposed [nb][ceps] (empty at ceps == 0)
     DevBuf<int32_t> d_kaldi_mel;         // [3][nb]: beg, len, first weight of every band
+    int kaldi_flags = 0;                 // kaldi_flags of mfx_create_kaldi (kKaldi* of mfx_tables.h), checked at creation
+    float kaldi_log_floor = -INFINITY;   // (float)log(kaldi_energy_floor), -inf for none
+    DevBuf<int64_t> d_kaldi_bounds;      // kKaldiNoSnipEdges: [n_utt][2] first sample and samples of the plan's utterances (a
+                                         // chunk's `pad` is its utterance; plan_batch writes both)
     float alpha = 1.f;
     bool have_window = false;
 
@@ -837,6 +841,7 @@ int batch_out_width(const mfx_handle *h);
 // frames of an utterance of `samples` samples per channel on this handle (may be <= 0 for the framed methods: callers clamp)
 inline int64_t utt_frame_count(const mfx_handle *h, int64_t samples)
 {
+    if (h->kaldi) return mfx::kaldi_frame_count(samples, h->W, h->S, h->kaldi_flags); // (flags 0: frame_count's rule)
     return h->stft ? mfx::stft_frame_count(samples, h->W, h->S) : mfx::frame_count(samples, h->W, h->S);
 }
 // what every STFT log-mel kernel takes from the handle: shape, post mode, operands and the mel spans, for rows to `out`

@@ -1,4 +1,4 @@
-// mfx_kernels.h -- launch interface of the gfx950 kernels (implemented in mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip, mfx_plp.hip, mfx_traps.hip, mfx_xform.hip, mfx_sess_xform.hip, mfx_sess_resample.hip, mfx_sessions.hip, mfx_resample.hip, mfx_speakers.hip, mfx_vad.hip, mfx_onorm.hip, mfx_stft.hip, mfx_stft_fft.hip, mfx_kaldi.hip, mfx_pitch.hip, mfx_pitchfeat.hip, mfx_tensor.hip: one translation unit per kernel family).
+// mfx_kernels.h -- launch interface of the gfx950 kernels (implemented in mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip, mfx_plp.hip, mfx_traps.hip, mfx_xform.hip, mfx_sess_xform.hip, mfx_sess_resample.hip, mfx_sessions.hip, mfx_resample.hip, mfx_speakers.hip, mfx_vad.hip, mfx_onorm.hip, mfx_stft.hip, mfx_stft_fft.hip, mfx_kaldi.hip, mfx_kaldi_opts.hip, mfx_pitch.hip, mfx_pitchfeat.hip, mfx_tensor.hip: one translation unit per kernel family).
 //
 // Kernel inventory and the reference stage each one replaces:
 //   spectrum512 / fused512   segmenter.cl kernelSegmentWindow + AppleFFT fft0 + mfcc.cl kernelTranspose
@@ -48,7 +48,8 @@ struct Chunk {
     int64_t pcm_off;  // sample index (per channel) of the first sample of the chunk's first frame
     int64_t out_row;  // destination row of the chunk's first frame
     int32_t n_frames;
-    int32_t pad;
+    int32_t pad;      // 0, except on a Kaldi handle with snip_edges = false: the chunk's utterance (KaldiParams::utt_bounds), and
+                      // pcm_off is then the unreflected start, which may lie in front of the utterance
 };
 
 // One independent series of feature rows (an utterance, or the current streaming block) for the
@@ -691,11 +692,19 @@ struct KaldiParams {
     int32_t mel_w_floats;       // their floats: 1 .. N (a bin lies in two bands at most)
     const int32_t *mel_beg, *mel_len, *mel_off; // [M] first bin, bins, first weight of every band
     const float *dct_t;         // [M][C]: G transposed (null at C = 0)
-    float *feat;                // [rows][feat_pitch], statics at columns [0, C or M)
+    float *feat;                // [rows][feat_pitch], statics at columns [0, kaldi_static_cols(M, C, flags))
     int32_t feat_pitch;
+    // kaldi_flags of mfx_create_kaldi (kKaldi* of mfx_tables.h); 0: everything below is unused and the rows are those of a handle without
+    int32_t flags;
+    float energy_log_floor;     // (float)log(energy_floor), -inf for none: the energy column is max(logE, this)
+    // kKaldiNoSnipEdges: [n_utt][2] = (first sample, samples) of every utterance; a chunk's `pad` is its utterance and its
+    // pcm_off the UNREFLECTED start of its first frame (it may lie in front of the utterance): the span is gathered through
+    // kaldi_reflect from the utterance's own samples
+    const int64_t *utt_bounds;
+    int32_t n_utt;
 };
 // ALL the LDS a block of k_kaldi_front asks for: the kernel declares no static LDS beside it
-size_t kaldi_lds_bytes(int W, int S, int M, int C);
+size_t kaldi_lds_bytes(int W, int S, int M, int C, int flags = 0);
 hipError_t launch_kaldi(const KaldiParams &p, hipStream_t stream);
 
 // All launchers are asynchronous on `stream` and return the launch status.

@@ -83,6 +83,11 @@ extern "C" int mfx_sessions_create(mfx_handle *h, int32_t n_sessions, int32_t ma
         return fail(h, MFX_ERR_STATE,
                     "the session entries do not serve MFX_LOGMEL_WHISPER (its clamp needs the largest value of the whole utterance): use "
                     "the batch entries (mfx_batch_plan + mfx_batch_run_device), or MFX_LOGMEL_LOG10 / MFX_LOGMEL_LN");
+    if (h->kaldi && (h->kaldi_flags & kKaldiNoSnipEdges))
+        return fail(h, MFX_ERR_STATE,
+                    "the session entries do not serve a Kaldi handle with MFX_KALDI_NO_SNIP_EDGES (its frames are mirrored at the true "
+                    "ends of the stream: another carry and delivery rule): use the batch entries (mfx_batch_plan + mfx_batch_run_device / "
+                    "mfx_batch_run_host)");
     if (h->cfg.norm != MFX_NORM_NONE && !h->sess.on.set) // (mfx_sessions_set_online_norm: the one normaliser served)
         return fail(h, MFX_ERR_STATE,
                     "the session entries do not serve normalisation (norm != MFX_NORM_NONE): statistics over an open stream are not built");

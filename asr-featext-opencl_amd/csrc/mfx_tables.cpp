@@ -557,6 +557,19 @@ bool kaldi_freqs_ok(float sample_rate, float low_freq, float high_freq, double *
     return low_freq >= 0.f && (double)low_freq < hi && hi <= nyq; // (false for NaN)
 }
 
+int64_t kaldi_frame_count(int64_t samples, int W, int S, int flags)
+{
+    if (!(flags & kKaldiNoSnipEdges)) return frame_count(samples, W, S);
+    return samples <= 0 ? 0 : (samples + S / 2) / S;
+}
+
+void kaldi_frame_samples(int64_t samples, int W, int S, int flags, int64_t t, int64_t *idx)
+{
+    const bool centred = (flags & kKaldiNoSnipEdges) != 0;
+    const int64_t s0 = centred ? kaldi_centred_start(t, W, S) : t * S;
+    for (int i = 0; i < W; ++i) idx[i] = centred ? kaldi_reflect(s0 + i, samples) : s0 + i;
+}
+
 void build_kaldi_mel(int M, int N, float sample_rate, float low_freq, double high_abs, float *weights, int32_t *beg, int32_t *len)
 {
     const int K = N / 2;

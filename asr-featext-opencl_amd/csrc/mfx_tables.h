@@ -367,6 +367,26 @@ void build_kaldi_spans(int M, int N, float sample_rate, float low_freq, double h
 void build_kaldi_dct(int M, int C, float lifter, float *G);
 // what k_kaldi_front takes as its operands: the window's W taps zero padded to N | W_{N/2}^k, k < N / 2 | -i W_N^k, k < N / 2: 3 N floats
 void build_kaldi_operands(int W, int N, const float *window, std::vector<float> &out);
+// kaldi_flags of mfx_create_kaldi as the code reads them (MFX_KALDI_* of include/mfx.h)
+constexpr int kKaldiNoSnipEdges = 1, kKaldiUseEnergy = 2, kKaldiEnergyWindowed = 4, kKaldiHtkCompat = 8, kKaldiFlagsAll = 15;
+// a flag word the method serves: known bits only, the windowed energy only with the energy column
+constexpr bool kaldi_flags_ok(int flags) { return (flags & ~kKaldiFlagsAll) == 0 && (!(flags & kKaldiEnergyWindowed) || (flags & kKaldiUseEnergy)); }
+// static columns of a row: M + 1 for fbank with the energy column, else C or M
+constexpr int kaldi_static_cols(int M, int C, int flags) { return C > 0 ? C : M + ((flags & kKaldiUseEnergy) ? 1 : 0); }
+// frames of an utterance of n samples: snip_edges = true is frame_count's rule; false (n + S div 2) div S, centred on the hops
+int64_t kaldi_frame_count(int64_t samples, int W, int S, int flags);
+// Kaldi's mirror of sample index s into an utterance of n >= 1 samples (feature-window.cc: while s < 0 or s >= n: s = -s - 1 or
+// 2 n - 1 - s) in closed form: the symmetric reflection of period 2 n.  The kernel and the host restatement share it
+constexpr int64_t kaldi_reflect(int64_t s, int64_t n)
+{
+    int64_t m = s % (2 * n);
+    if (m < 0) m += 2 * n;
+    return m < n ? m : 2 * n - 1 - m;
+}
+// idx [W]: the utterance sample of every tap of frame t < kaldi_frame_count(samples) (samples >= 1 then)
+void kaldi_frame_samples(int64_t samples, int W, int S, int flags, int64_t t, int64_t *idx);
+// sample index relative to the utterance of tap 0 of frame t under snip_edges = false (may be negative: kaldi_reflect maps it)
+constexpr int64_t kaldi_centred_start(int64_t t, int W, int S) { return t * S + S / 2 - W / 2; }
 
 // One push of one session of an STFT log-mel handle ("Session log-mel"): a stream that has received n samples and
 // delivered rows [0, E) takes `length` more.  While the stream is open E = 0 up to n = N / 2, else min(n div S, (n - N / 2)

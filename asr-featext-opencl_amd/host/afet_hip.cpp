@@ -70,6 +70,9 @@ struct Options {
     float kaldi_preemph = 0.97f;   // --preemph X
     bool kaldi_dc = true;          // --no-dc-removal
     bool kaldi_power = true;       // --magnitude
+    int kaldi_flags = 0;           // --snip-edges 0, --use-energy, --raw-energy 0, --htk-compat: MFX_KALDI_* (creation-time)
+    bool kaldi_raw_energy = true;  // --raw-energy 0|1 (needs --use-energy when 0)
+    float kaldi_energy_floor = 0.f; // --energy-floor X
     bool htk = false; // binary output in HTK parameter-file format instead of the reference's text rows
     int format_threads = 4; // threads that format the text rows of a block (per worker)
     int batch_mb = 16;      // PCM per batch of files (0: the per-file loop only); small enough that a few thousand files pipeline
@@ -675,7 +678,7 @@ void worker(const Options &o, int device, float sr, const std::vector<std::strin
             if (o.method == MFX_METHOD_KALDI) { // batch entries only; the Povey window, samples in the int16 range
                 std::unique_ptr<KaldiHip> t(new KaldiHip(o.sample_limit, (int)W, (int)S, o.banks, sr, o.low, o.high, o.ceps, o.lift,
                                                          (Normalizer::norm_t)o.norm, (ParamBase::dyn_t)o.dyn, o.l1, o.l2, o.norm_after_dyn,
-                                                         device));
+                                                         device, o.kaldi_flags, o.kaldi_energy_floor));
                 std::vector<float> window((size_t)W);
                 KaldiHip::povey_window((int)W, window.data());
                 t->set_window(window.data());
@@ -1086,6 +1089,24 @@ int main(int argc, char **argv)
         }
         else if (a == "--no-dc-removal") o.kaldi_dc = false, kaldi_opts = true;
         else if (a == "--magnitude") o.kaldi_power = false, kaldi_opts = true;
+        else if (a == "--snip-edges") {
+            const int v = std::atoi(val());
+            if (v != 0 && v != 1) { std::fprintf(stderr, "--snip-edges: 0 or 1\n"); return 2; }
+            o.kaldi_flags = v ? (o.kaldi_flags & ~MFX_KALDI_NO_SNIP_EDGES) : (o.kaldi_flags | MFX_KALDI_NO_SNIP_EDGES);
+            kaldi_opts = true;
+        }
+        else if (a == "--use-energy") o.kaldi_flags |= MFX_KALDI_USE_ENERGY, kaldi_opts = true;
+        else if (a == "--raw-energy") {
+            const int v = std::atoi(val());
+            if (v != 0 && v != 1) { std::fprintf(stderr, "--raw-energy: 0 or 1\n"); return 2; }
+            o.kaldi_raw_energy = v != 0, kaldi_opts = true;
+        }
+        else if (a == "--energy-floor") {
+            o.kaldi_energy_floor = (float)std::atof(val());
+            if (!(o.kaldi_energy_floor >= 0.f) || !std::isfinite(o.kaldi_energy_floor)) { std::fprintf(stderr, "--energy-floor: >= 0\n"); return 2; }
+            kaldi_opts = true;
+        }
+        else if (a == "--htk-compat") o.kaldi_flags |= MFX_KALDI_HTK_COMPAT, kaldi_opts = true;
         else if (a == "--traps-length") o.traps_len = std::atoi(val());
         else if (a == "--traps-dct") o.traps_dct = std::atoi(val());
         else if (a == "--logmel-nfft") {
@@ -1158,6 +1179,9 @@ int main(int argc, char **argv)
                         "         [--method MFCC|PLP|TRAPS|LOGMEL|KALDI] [--model-order n (PLP model order, default 8)]\n"
                         "         [--preemph x] [--no-dc-removal] [--magnitude] (KALDI: Kaldi-compatible fbank (--ceps 0) / MFCC with c0 first,\n"
                         "          Povey window, --high-freq <= 0 an offset from Nyquist, --lift-coef the cepstral lifter; defaults 0.97, DC removal, power)\n"
+                        "         [--snip-edges 0|1] [--use-energy] [--raw-energy 0|1] [--energy-floor x] [--htk-compat] (KALDI: Kaldi's options of\n"
+                        "          those names; --use-energy puts the frame's log-energy in column 0 -- fbank rows are one column wider --,\n"
+                        "          --htk-compat moves it, or c0 times sqrt 2, behind the others; defaults 1, off, 1, 0, off)\n"
                         "         [--logmel-post whisper|log10|ln (LOGMEL: what follows the log; default whisper)]\n"
                         "         [--logmel-nfft 1024|2048 (LOGMEL: the DFT length; the Hann window of --window-size lies centred in it)]\n"
                         "         [--traps-length n (TRAPS frames per trajectory, odd, default 31)] [--traps-dct n (default 10)]\n"
@@ -1318,8 +1342,19 @@ int main(int argc, char **argv)
         }
         o.c0 = false, o.bug_compat = false;
         if (!o.low_given) o.low = 20.f; // (Kaldi's default)
+        if (!o.kaldi_raw_energy) {
+            if (!(o.kaldi_flags & MFX_KALDI_USE_ENERGY)) {
+                std::fprintf(stderr, "--raw-energy 0 goes with --use-energy\n");
+                return 2;
+            }
+            o.kaldi_flags |= MFX_KALDI_ENERGY_WINDOWED;
+        }
+        if (o.kaldi_flags != 0 && (o.kaldi_flags & ~mfx_kaldi_flags_supported()) != 0) {
+            std::fprintf(stderr, "this libmfcchip.so does not serve these Kaldi options\n");
+            return 2;
+        }
     } else if (kaldi_opts) {
-        std::fprintf(stderr, "--preemph, --no-dc-removal and --magnitude go with --method KALDI\n");
+        std::fprintf(stderr, "--preemph, --no-dc-removal, --magnitude, --snip-edges, --use-energy, --raw-energy, --energy-floor and --htk-compat go with --method KALDI\n");
         return 2;
     }
     if (o.resample_to != 0 && (o.resample_to < 1000 || o.resample_to > 768000)) {

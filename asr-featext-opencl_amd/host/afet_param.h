@@ -149,11 +149,11 @@ public:
 
 protected:
     // method: MFX_METHOD_* of include/mfx.h (PlpHip passes MFX_METHOD_PLP and its model order, TrapsHip MFX_METHOD_TRAPS
-    // and its two lengths, LogmelHip MFX_METHOD_STFT_LOGMEL and logmel_post)
+    // and its two lengths, LogmelHip MFX_METHOD_STFT_LOGMEL and logmel_post, KaldiHip MFX_METHOD_KALDI and its two option fields)
     MfccHip(int input_buffer_size, int window_size, int shift, int num_banks, float sample_rate, float low_freq,
             float high_freq, int ceps_len, bool want_c0, float lift_coef, Normalizer::norm_t norm, dyn_t dyn, int delta_l1,
             int delta_l2, bool norm_after_dyn, int hip_device, bool bug_compat, int engine, int method, int lpc_order,
-            int traps_len = 0, int traps_dct_len = 0, int logmel_post = 0);
+            int traps_len = 0, int traps_dct_len = 0, int logmel_post = 0, int kaldi_flags = 0, float kaldi_energy_floor = 0.f);
 
 private:
     void check(int status) const;
@@ -195,14 +195,16 @@ public:
 // Kaldi-compatible fbank / MFCC ("Kaldi front end"; MFX_METHOD_KALDI): ceps_len 0 delivers num_banks log mel
 // energies, 1 .. num_banks Kaldi's cepstra with c0 first; lift_coef is cepstral_lifter (0: none); high_freq <= 0 is the offset
 // from Nyquist.  Set the Povey window with set_window, the three frame options with set_options (Kaldi's defaults until then).
+// kaldi_flags (MFX_KALDI_* of include/mfx.h: snip_edges = false, use_energy, raw_energy = false, htk_compat) and
+// kaldi_energy_floor are creation-time: fbank with the energy column is num_banks + 1 wide.
 // Batch entries (and the session entries of include/mfx.h); set_input, flush, apply and get_output_data throw.
 class KaldiHip : public MfccHip {
 public:
     KaldiHip(int input_buffer_size, int window_size, int shift, int num_banks, float sample_rate, float low_freq, float high_freq,
              int ceps_len, float lift_coef, Normalizer::norm_t norm = Normalizer::NORM_NONE, dyn_t dyn = DYN_NONE, int delta_l1 = 1,
-             int delta_l2 = 1, bool norm_after_dyn = true, int hip_device = 0);
+             int delta_l2 = 1, bool norm_after_dyn = true, int hip_device = 0, int kaldi_flags = 0, float kaldi_energy_floor = 0.f);
     void set_options(float preemph_coeff, bool remove_dc_offset, bool use_power);
-    int get_output_data_width() const override; // (ceps_len or num_banks) * (1 + deltas): the library's own answer
+    int get_output_data_width() const override; // the static columns * (1 + deltas): the library's own answer
     // pow(0.5 - 0.5 cos(2 pi i / (n - 1)), 0.85), in double, rounded once
     static void povey_window(int n, float *window);
 };

@@ -87,9 +87,10 @@ LogmelHip::LogmelHip(int input_buffer_size, int dft_size, int shift, int num_ban
 
 KaldiHip::KaldiHip(int input_buffer_size, int window_size, int shift, int num_banks, float sample_rate, float low_freq, float high_freq,
                    int ceps_len, float lift_coef, Normalizer::norm_t norm, dyn_t dyn, int delta_l1, int delta_l2, bool norm_after_dyn,
-                   int hip_device)
+                   int hip_device, int kaldi_flags, float kaldi_energy_floor)
     : MfccHip(input_buffer_size, window_size, shift, num_banks, sample_rate, low_freq, high_freq, ceps_len, /*want_c0=*/false, lift_coef,
-              norm, dyn, delta_l1, delta_l2, norm_after_dyn, hip_device, /*bug_compat=*/false, /*engine=*/0, MFX_METHOD_KALDI, 0)
+              norm, dyn, delta_l1, delta_l2, norm_after_dyn, hip_device, /*bug_compat=*/false, /*engine=*/0, MFX_METHOD_KALDI, 0, 0, 0, 0,
+              kaldi_flags, kaldi_energy_floor)
 {
 }
 
@@ -112,7 +113,7 @@ void KaldiHip::povey_window(int n, float *window)
 MfccHip::MfccHip(int input_buffer_size, int window_size, int shift, int num_banks, float sample_rate, float low_freq,
                  float high_freq, int ceps_len, bool want_c0, float lift_coef, Normalizer::norm_t norm, dyn_t dyn,
                  int delta_l1, int delta_l2, bool norm_after_dyn, int hip_device, bool bug_compat, int engine, int method,
-                 int lpc_order, int traps_len, int traps_dct_len, int logmel_post)
+                 int lpc_order, int traps_len, int traps_dct_len, int logmel_post, int kaldi_flags, float kaldi_energy_floor)
     : MfccBase(input_buffer_size, window_size, shift, num_banks, sample_rate, low_freq, high_freq, ceps_len, want_c0,
                lift_coef, norm, dyn, delta_l1, delta_l2, norm_after_dyn),
       m_handle(nullptr)
@@ -140,9 +141,12 @@ MfccHip::MfccHip(int input_buffer_size, int window_size, int shift, int num_bank
     cfg.traps_len = traps_len;
     cfg.traps_dct_len = traps_dct_len;
     cfg.logmel_post = logmel_post;
+    if (kaldi_flags != 0 && (kaldi_flags & ~mfx_kaldi_flags_supported()) != 0)
+        throw std::runtime_error("KaldiHip: kaldi_flags not supported by this libmfcchip.so");
     if (method != MFX_METHOD_MFCC && !mfx_method_supported(method))
         throw std::runtime_error("MfccHip: feature method not supported by this libmfcchip.so");
-    const int rc = mfx_create(&cfg, hip_device, &m_handle);
+    const int rc = method == MFX_METHOD_KALDI ? mfx_create_kaldi(&cfg, kaldi_flags, kaldi_energy_floor, hip_device, &m_handle)
+                                               : mfx_create(&cfg, hip_device, &m_handle);
     if (rc != MFX_OK)
         throw std::runtime_error(std::string(method == MFX_METHOD_PLP ? "PlpHip: " : method == MFX_METHOD_TRAPS ? "TrapsHip: " : method == MFX_METHOD_STFT_LOGMEL ? "LogmelHip: " : method == MFX_METHOD_KALDI ? "KaldiHip: " : "MfccHip: ") + mfx_status_string(rc));
 }

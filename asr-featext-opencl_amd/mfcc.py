@@ -20,6 +20,7 @@ METHOD_TRAPS = 3                                           # (2 is unassigned an
 METHOD_STFT_LOGMEL = 5                                     # (4 is unassigned and refused)
 METHOD_KALDI = 7                                           # (6 is unassigned and refused)
 LOGMEL_WHISPER, LOGMEL_LOG10, LOGMEL_LN = 0, 1, 2          # mfx_config.logmel_post (include/mfx.h)
+KALDI_NO_SNIP_EDGES, KALDI_USE_ENERGY, KALDI_ENERGY_WINDOWED, KALDI_HTK_COMPAT = 1, 2, 4, 8   # kaldi_flags of mfx_create_kaldi
 
 
 class MfxError(RuntimeError):
@@ -92,6 +93,7 @@ EXPORTED_SYMBOLS = (
     "mfx_host_stft_lds_bytes", "mfx_host_session_stft_step", "mfx_host_sess_stft_lds_bytes",
     "mfx_host_stft_fft_tables", "mfx_host_stft_fft_lds_bytes",
     "mfx_kaldi_set_options", "mfx_host_kaldi_mel_table", "mfx_host_kaldi_dct", "mfx_host_kaldi_lds_bytes",
+    "mfx_create_kaldi", "mfx_plan_create_kaldi", "mfx_kaldi_flags_supported", "mfx_host_kaldi_lds_bytes_flags", "mfx_host_kaldi_frame_count", "mfx_host_kaldi_frame_samples",
     "mfx_batch_set_pitch", "mfx_batch_clear_pitch", "mfx_batch_pitch_read", "mfx_batch_pitch_device", "mfx_host_pitch",
     "mfx_batch_set_pitch_feats", "mfx_batch_clear_pitch_feats", "mfx_batch_pitch_feats_read", "mfx_batch_pitch_feats_device",
     "mfx_host_pitch_feats",
@@ -232,6 +234,12 @@ def load_library():
     L.mfx_host_kaldi_mel_table.argtypes = [i32, i32, C.c_float, C.c_float, C.c_float, fp, p32, p32]
     L.mfx_host_kaldi_dct.argtypes = [i32, i32, C.c_float, fp]
     L.mfx_host_kaldi_lds_bytes.argtypes, L.mfx_host_kaldi_lds_bytes.restype = [i32, i32, i32, i32], i64
+    L.mfx_kaldi_flags_supported.argtypes, L.mfx_kaldi_flags_supported.restype = [], i32
+    L.mfx_create_kaldi.argtypes = [C.POINTER(MfxConfig), i32, C.c_float, C.c_int, C.POINTER(vp)]
+    L.mfx_plan_create_kaldi.argtypes = [C.POINTER(MfxConfig), i32, C.c_float, C.POINTER(vp)]
+    L.mfx_host_kaldi_lds_bytes_flags.argtypes, L.mfx_host_kaldi_lds_bytes_flags.restype = [i32, i32, i32, i32, i32], i64
+    L.mfx_host_kaldi_frame_count.argtypes, L.mfx_host_kaldi_frame_count.restype = [i64, i32, i32, i32], i64
+    L.mfx_host_kaldi_frame_samples.argtypes = [i64, i32, i32, i32, i64, C.POINTER(C.c_int64)]
     L.mfx_batch_set_pitch.argtypes = [vp, i32, i32, i32, C.c_float, C.c_float, C.c_float, i32]
     L.mfx_batch_clear_pitch.argtypes = [vp]
     L.mfx_batch_pitch_read.argtypes = [vp, fp, p32, fp]
@@ -747,12 +755,39 @@ def host_kaldi_dct(num_banks, ceps_len, lifter):
     return g
 
 
-def host_kaldi_lds_bytes(window_size, shift, num_banks, ceps_len):
-    """ALL the LDS bytes a block of k_kaldi_front asks for at a shape.  An inspection aid."""
-    n = int(load_library().mfx_host_kaldi_lds_bytes(int(window_size), int(shift), int(num_banks), int(ceps_len)))
+def host_kaldi_lds_bytes(window_size, shift, num_banks, ceps_len, flags=0):
+    """ALL the LDS bytes a block of k_kaldi_front asks for at a shape (under ``flags``, a sum of KALDI_*).  An inspection aid."""
+    L = load_library()
+    if flags:
+        n = int(L.mfx_host_kaldi_lds_bytes_flags(int(window_size), int(shift), int(num_banks), int(ceps_len), int(flags)))
+    else:
+        n = int(L.mfx_host_kaldi_lds_bytes(int(window_size), int(shift), int(num_banks), int(ceps_len)))
     if n < 0:
         raise MfxError(n, "mfx_host_kaldi_lds_bytes failed")
     return n
+
+
+def kaldi_flags_supported():
+    """The KALDI_* bits of ``kaldi_flags`` this library serves."""
+    return int(load_library().mfx_kaldi_flags_supported())
+
+
+def host_kaldi_frame_count(samples, window_size, shift, flags=0):
+    """Frames of an utterance on a Kaldi handle under ``flags`` (KALDI_NO_SNIP_EDGES: (n + S // 2) // S).  No GPU needed."""
+    n = int(load_library().mfx_host_kaldi_frame_count(int(samples), int(window_size), int(shift), int(flags)))
+    if n < 0:
+        raise MfxError(n, "mfx_host_kaldi_frame_count failed")
+    return n
+
+
+def host_kaldi_frame_samples(samples, window_size, shift, flags, t):
+    """The utterance sample index of every tap of frame ``t`` (int64 [window_size]), by the closed form the kernel uses."""
+    idx = np.zeros(max(int(window_size), 0), np.int64)
+    rc = load_library().mfx_host_kaldi_frame_samples(int(samples), int(window_size), int(shift), int(flags), int(t),
+                                                     idx.ctypes.data_as(C.POINTER(C.c_int64)))
+    if rc != 0:
+        raise MfxError(rc, "mfx_host_kaldi_frame_samples failed")
+    return idx
 
 
 def host_frame_count(samples, window_size, shift):
@@ -860,13 +895,16 @@ class MfccHip:
     0; ``want_c0=False``; ``lift_coef`` = cepstral_lifter, 0 = none) features (include/mfx.h): ``window_size`` 65 .. 512,
     ``high_freq <= 0`` is Kaldi's offset from Nyquist; set ``povey_window(window_size)`` as the window and the three frame
     options with ``kaldi_set_options``.  Batch and session entries; no streaming methods, no warp factors.
+    ``kaldi_flags`` (a sum of ``KALDI_NO_SNIP_EDGES``, ``KALDI_USE_ENERGY``, ``KALDI_ENERGY_WINDOWED``, ``KALDI_HTK_COMPAT``) and
+    ``kaldi_energy_floor`` are Kaldi's snip_edges = false, use_energy, raw_energy = false, htk_compat and energy_floor; fbank
+    with the energy column is ``num_banks + 1`` wide.  ``KALDI_NO_SNIP_EDGES``: batch entries only, no pitch track.
     """
 
     def __init__(self, input_buffer_size, window_size, shift, num_banks, sample_rate, low_freq, high_freq,
                  ceps_len, want_c0, lift_coef, norm=NORM_NONE, dyn=DYN_NONE, delta_l1=1, delta_l2=1,
                  norm_after_dyn=True, device=0, fft_size=0, channels=1, bug_compat=True, batch_norm_stats=0, engine=0,
                  tail_split=0, method=METHOD_MFCC, lpc_order=0, traps_len=0, traps_dct_len=0,
-                 logmel_post=LOGMEL_WHISPER):
+                 logmel_post=LOGMEL_WHISPER, kaldi_flags=0, kaldi_energy_floor=0.0):
         self._L = load_library()
         _check_method(method)
         self.cfg = MfxConfig(int(input_buffer_size), int(window_size), int(shift), int(num_banks),
@@ -875,8 +913,12 @@ class MfccHip:
                              int(delta_l2), int(bool(norm_after_dyn)), int(fft_size), int(channels),
                              int(bool(bug_compat)), int(batch_norm_stats), int(engine), int(tail_split),
                              int(method), int(lpc_order), int(traps_len), int(traps_dct_len), int(logmel_post))
+        self.kaldi_flags, self.kaldi_energy_floor = int(kaldi_flags), float(kaldi_energy_floor)
         h = C.c_void_p()
-        rc = self._L.mfx_create(C.byref(self.cfg), int(device), C.byref(h))
+        if int(method) == METHOD_KALDI:   # (the creation entry that carries the two options; both zero: mfx_create itself)
+            rc = self._L.mfx_create_kaldi(C.byref(self.cfg), self.kaldi_flags, self.kaldi_energy_floor, int(device), C.byref(h))
+        else:
+            rc = self._L.mfx_create(C.byref(self.cfg), int(device), C.byref(h))
         if rc != 0:
             raise MfxError(rc, "mfx_create: " + self._L.mfx_status_string(rc).decode())
         self._h = h

@@ -99,6 +99,12 @@ typedef struct mfx_config {
                                   MFX_METHOD_STFT_LOGMEL                                                              */
 } mfx_config;
 
+/* kaldi_flags of mfx_create_kaldi / mfx_plan_create_kaldi (below); any other bit is MFX_ERR_CONFIG */
+#define MFX_KALDI_NO_SNIP_EDGES 1   /* snip_edges = false: frames centred on the hops, the utterance mirrored at its ends */
+#define MFX_KALDI_USE_ENERGY 2      /* use_energy = true: the frame's log-energy is a column of the row                   */
+#define MFX_KALDI_ENERGY_WINDOWED 4 /* raw_energy = false (needs MFX_KALDI_USE_ENERGY, else MFX_ERR_CONFIG)               */
+#define MFX_KALDI_HTK_COMPAT 8      /* htk_compat = true: HTK's column order                                              */
+
 /* mfx_config.method.  3 = TRAPS temporal patterns (TRAPS): the log mel energies of the MFCC path (ceps_len = 0,
  * want_c0 = 0 required; lift_coef ignored), per band a Hamming-windowed DCT-II over the traps_len frames around each frame,
  * traps_dct_len coefficients kept; static row band-major, num_banks * traps_dct_len columns (at most 256).  BATCH ENTRIES
@@ -226,7 +232,43 @@ enum { MFX_LOGMEL_WHISPER = 0, MFX_LOGMEL_LOG10 = 1, MFX_LOGMEL_LN = 2 };
  * 0).  Refused: mfx_batch_set_alphas with MFX_ERR_CONFIG (there is no Kaldi VTLN warp; mfx_set_alpha has no effect), and the
  * streaming entries (mfx_set_input, mfx_flush, mfx_apply, mfx_apply_alphas, mfx_get_output_data[_alpha]) with MFX_ERR_STATE
  * and a message that names the batch entries.
- * Not served: dither, use_energy / raw_energy / energy_floor, htk_compat, snip_edges = false, vtln_warp, W > 512, stereo. */
+ * Options (kaldi_flags and kaldi_energy_floor of mfx_create_kaldi / mfx_plan_create_kaldi; restated from Kaldi's
+ * feature-window.cc, feature-fbank.cc and feature-mfcc.cc).  They are creation-time arguments, not arguments of
+ * mfx_kaldi_set_options, because they change the output width and the frame count, which size buffers at creation; and they
+ * are arguments of a creation entry of their own, not fields of mfx_config, whose size and last field stay what libraries and
+ * callers in the field agree on.  mfx_create is mfx_create_kaldi with both zero: the definition above and its bits.  Unknown bits,
+ * ENERGY_WINDOWED without USE_ENERGY, a negative or non-finite floor, or a shape whose rows no longer fit the kernel's LDS
+ * (mfx_host_kaldi_lds_bytes_flags): MFX_ERR_CONFIG.
+ *   Width.    fbank (C = 0): M + 1 static columns with USE_ENERGY, else M.  MFCC: C columns.  mfx_get_output_data_width and
+ *     every buffer follow.
+ *   Frames, NO_SNIP_EDGES.  T = mfx_batch_frames = (n + S div 2) div S, 0 for n = 0.  Frame t, tap i reads utterance sample
+ *     r(t S + S div 2 - W div 2 + i), r being Kaldi's loop `while s < 0 or s >= n: s = -s - 1 if s < 0 else 2 n - 1 - s`, that
+ *     is the symmetric reflection of period 2 n: m = s mod 2 n (non-negative), r = m if m < n else 2 n - 1 - m.  The kernel
+ *     uses the closed form (mfx_host_kaldi_frame_samples restates it).  The reflection happens at the ends of the UTTERANCE,
+ *     never into a neighbour's samples: nothing outside [offset, offset + n) is read.  DC removal, pre-emphasis (the frame's
+ *     first tap still stands for its predecessor), window, DFT and everything after see the W gathered samples exactly as they
+ *     see a frame above.
+ *   Energy, USE_ENERGY.  E = sum over i < W of d[i]^2, d after DC removal and before pre-emphasis and window (Kaldi's
+ *     raw_energy = true); with ENERGY_WINDOWED E = sum of z[i]^2, z after the window.  The sum is float32: per-lane ascending
+ *     FMA chains, then a wave reduction; it is NOT pinned to a summation order, but its operation sequence depends on W alone.
+ *     logE = logf(max(E, 0x1p-23f)); if kaldi_energy_floor > 0, logE = max(logE, lf), lf = (float)log((double)floor), built
+ *     once on the host.
+ *   Columns.  fbank + USE_ENERGY: logE in column 0, the log mel energies in 1 .. M; with HTK_COMPAT the bands in 0 .. M - 1 and
+ *     logE in column M.  HTK_COMPAT without USE_ENERGY changes nothing on fbank.  MFCC + USE_ENERGY: column 0 is logE instead
+ *     of c0.  MFCC + HTK_COMPAT: columns 1 .. C - 1 move to 0 .. C - 2 and column C - 1 takes logE with USE_ENERGY, else
+ *     (float)((double)c0 * 1.4142135623730951) (Kaldi's M_SQRT2 on c0).  The lifter is applied before the move, as in Kaldi.
+ *     mfx_batch_set_vad's default column -1 (the last static column) therefore lands on the energy under HTK_COMPAT +
+ *     USE_ENERGY, which is the column Kaldi's VAD reads.
+ *   Contract. As above: the same bits alone or in a batch, at any sample offset, on a second run, through the device or the host
+ *     entry, at any 4-byte placement of d_out, nothing written outside the rows.
+ *   Entries.  The batch entries and all their attachments see rows and T and work unchanged, mfx_batch_plan_rates included (its
+ *     frame rule acts on the converted lengths).  mfx_batch_set_pitch (and so _set_pitch_feats) on a NO_SNIP_EDGES handle is
+ *     refused with MFX_ERR_CONFIG: the track's frames follow the snip-edged rule and would not line up with the rows.  The session
+ *     entries serve USE_ENERGY, ENERGY_WINDOWED and HTK_COMPAT with no change of the step rule, as the batch twin's bits;
+ *     mfx_sessions_create on a NO_SNIP_EDGES handle answers MFX_ERR_STATE with a message that names the batch entries (the
+ *     carry and delivery rule differs: left reflection at the stream start, W / 2 + S / 2 more samples held back, final-push
+ *     frames; it is not served yet).
+ * Not served: dither, vtln_warp, W > 512, stereo; sessions with snip_edges = false. */
 
 /* mfx_config.engine bits */
 #define MFX_ENGINE_NO_FRONT1024 1 /* 1024-point short-window configurations stay on the generic long-transform kernel  */
@@ -291,6 +333,15 @@ int mfx_method_supported(int32_t method);
  * than 0 / 1; MFX_ERR_STATE while sessions exist (an open stream's bits must not change under it: mfx_sessions_create(h, 0, 0)
  * first).  It works on a planning handle, waits for the handle's streams, and allocates nothing. */
 int mfx_kaldi_set_options(mfx_handle *h, float preemph_coeff, int32_t remove_dc_offset, int32_t use_power);
+/* mfx_create / mfx_plan_create for a Kaldi handle (cfg->method == MFX_METHOD_KALDI, else MFX_ERR_CONFIG) with the options of
+ * method 7, "Options": kaldi_flags = MFX_KALDI_* bits, kaldi_energy_floor = Kaldi's energy_floor (0 = none; must be >= 0 and
+ * finite).  Unknown bits, MFX_KALDI_ENERGY_WINDOWED without MFX_KALDI_USE_ENERGY or a bad floor: MFX_ERR_CONFIG.  (0, 0.f) is
+ * mfx_create / mfx_plan_create itself. */
+int mfx_create_kaldi(const mfx_config *cfg, int32_t kaldi_flags, float kaldi_energy_floor, int hip_device, mfx_handle **out);
+int mfx_plan_create_kaldi(const mfx_config *cfg, int32_t kaldi_flags, float kaldi_energy_floor, mfx_handle **out);
+/* the MFX_KALDI_* bits this library serves (15); a library older than the options has neither this symbol nor
+ * mfx_create_kaldi */
+int32_t mfx_kaldi_flags_supported(void);
 
 /* ---- streaming parameterizer interface, one function per ParamBase method (parambase.h:23-32) ---- */
 
@@ -1122,6 +1173,16 @@ int mfx_host_kaldi_mel_table(int32_t num_banks, int32_t fft_size, float sample_r
                              float *weights, int32_t *beg, int32_t *len);
 int mfx_host_kaldi_dct(int32_t num_banks, int32_t ceps_len, float lifter, float *matrix);
 int64_t mfx_host_kaldi_lds_bytes(int32_t window_size, int32_t shift, int32_t num_banks, int32_t ceps_len);
+/* The same under kaldi_flags (fbank with the energy column assembles rows of num_banks + 1 floats): what mfx_create
+ * holds against the cap on a handle with flags; at flags 0 it is mfx_host_kaldi_lds_bytes.  MFX_ERR_ARG for flags the method
+ * refuses.  UNSTABLE likewise. */
+int64_t mfx_host_kaldi_lds_bytes_flags(int32_t window_size, int32_t shift, int32_t num_banks, int32_t ceps_len, int32_t flags);
+/* Host restatements of the Kaldi frame rule (no device needed).  mfx_host_kaldi_frame_count: T of an utterance of `samples`
+ * samples under `flags` (only MFX_KALDI_NO_SNIP_EDGES matters); MFX_ERR_ARG for samples < 0 or a window / shift outside the
+ * method's limits.  mfx_host_kaldi_frame_samples: idx [window_size] = the utterance sample index of every tap of frame t, by
+ * the closed form the kernel uses (every index lies in [0, samples)); MFX_ERR_ARG also for t outside [0, T). */
+int64_t mfx_host_kaldi_frame_count(int64_t samples, int32_t window_size, int32_t shift, int32_t flags);
+int mfx_host_kaldi_frame_samples(int64_t samples, int32_t window_size, int32_t shift, int32_t flags, int64_t t, int64_t *idx);
 
 /* ---- test taps (device -> host copies of intermediate tables; used by the parity tests) ---- */
 /* kind: 0 = mel table [2][fft_size] floats, 1 = filter_beg [num_banks+2] int32,

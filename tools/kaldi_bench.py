@@ -5,7 +5,9 @@ reference's definition: no DC removal, no pre-emphasis), timed the same way -- t
 frame; there is no pass threshold.
 Prints one JSON line.  The kernel's share comes from a separate
 `rocprofv3 --kernel-trace --stats -- python tools/kaldi_bench.py --reps 3 --no-yardstick`.
-usage: python tools/kaldi_bench.py [--utts 1000] [--seconds 10] [--reps 10] [--warmup 3] [--banks 80] [--ceps 0] [--no-yardstick]"""
+--flags: kaldi_flags of mfx_create_kaldi (1 snip_edges = false, 2 the energy column, 4 windowed energy, 8 HTK order): k_kaldi_front_opts.
+usage: python tools/kaldi_bench.py [--utts 1000] [--seconds 10] [--reps 10] [--warmup 3] [--banks 80] [--ceps 0] [--flags 0]
+       [--no-yardstick]"""
 import argparse
 import json
 import os
@@ -23,6 +25,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--banks", type=int, default=80)
     ap.add_argument("--ceps", type=int, default=0)
+    ap.add_argument("--flags", type=int, default=0)
     ap.add_argument("--no-yardstick", action="store_true")
     a = ap.parse_args()
 
@@ -67,10 +70,11 @@ def main():
         m.close()
         return r
 
-    res = {"workload": "%d x %g s, 16 kHz, W %d, S %d, %d banks, %d cepstra" % (a.utts, a.seconds, W, S, M, C), "runs": []}
-    m = pkg.MfccHip(n + 1000, W, S, M, float(sr), 20.0, 0.0, C, False, 22.0, device=0, method=pkg.METHOD_KALDI)
+    res = {"workload": "%d x %g s, 16 kHz, W %d, S %d, %d banks, %d cepstra, kaldi_flags %d" % (a.utts, a.seconds, W, S, M, C, a.flags),
+           "runs": []}
+    m = pkg.MfccHip(n + 1000, W, S, M, float(sr), 20.0, 0.0, C, False, 22.0, device=0, method=pkg.METHOD_KALDI, kaldi_flags=a.flags)
     m.set_window(pkg.povey_window(W))
-    res["runs"].append(run("kaldi", m, C or M))
+    res["runs"].append(run("kaldi", m, m.get_output_data_width()))
     if not a.no_yardstick:
         m = pkg.MfccHip(n + 1000, W, S, M, float(sr), 64.0, sr / 2.0, C, False, 22.0, device=0, method=pkg.METHOD_MFCC)
         m.set_window(pkg.reference_window(W))
