@@ -413,7 +413,7 @@ int create_stft(mfx_handle *h, bool planning, std::unique_ptr<mfx_handle, Handle
     std::vector<float> w;
     std::vector<int32_t> meta;
     build_slaney_spans(h->nb, h->W, cfg.sample_rate, cfg.low_freq, cfg.high_freq, w, meta);
-    if (h->upload(h->d_stft_melw, w) != hipSuccess || h->upload(h->d_stft_mel, meta) != hipSuccess ||
+    if (h->upload(h->d_span_melw, w) != hipSuccess || h->upload(h->d_span_mel, meta) != hipSuccess ||
         h->alloc(h->st.d_stats, (size_t)3 * 2 * h->cols) != hipSuccess)
         return MFX_ERR_DEVICE;
     *out = owner.release();
@@ -463,7 +463,7 @@ int create_kaldi(mfx_handle *h, bool planning, std::unique_ptr<mfx_handle, Handl
         for (int i = 0; i < h->ceps; ++i)
             for (int m = 0; m < h->nb; ++m) gt[(size_t)m * h->ceps + i] = g[(size_t)i * h->nb + m];
     }
-    if (h->upload(h->d_kaldi_melw, w) != hipSuccess || h->upload(h->d_kaldi_mel, meta) != hipSuccess || h->upload(h->d_kaldi_dct_t, gt) != hipSuccess ||
+    if (h->upload(h->d_span_melw, w) != hipSuccess || h->upload(h->d_span_mel, meta) != hipSuccess || h->upload(h->d_kaldi_dct_t, gt) != hipSuccess ||
         h->alloc(h->st.d_stats, (size_t)3 * 2 * h->cols) != hipSuccess)
         return MFX_ERR_DEVICE;
     *out = owner.release();
@@ -818,14 +818,13 @@ int launch_front(mfx_handle *h, FrontParams &p, FrontKind kind, bool aligned, co
             break;
         case kFront2048: HIP_TRY(h, launch_front2048(p, h->num_cus, h->stream)); break;
         case kKaldi: {
-            const int32_t *meta = h->d_kaldi_mel.p; // [3][nb]
             // (centred frames: the plan's own utterance count, and only while the bounds uploaded with that plan hold exactly
             // its utterances -- upload() sizes the buffer to the list; anything else is 0, which launch_kaldi refuses)
             const int32_t centred_utts =
                 (h->kaldi_flags & kKaldiNoSnipEdges) && h->d_kaldi_bounds.n == 2 * (size_t)h->batch.n_utt ? h->batch.n_utt : 0;
             KaldiParams kp{p.pcm, p.pcm_total, p.chunks, p.n_chunks, p.row_limit, h->W, h->S, h->W2, h->nb, h->ceps, h->kaldi_preemph,
-                           h->kaldi_remove_dc ? 1 : 0, h->kaldi_use_power ? 1 : 0, h->d_kaldi_ops.p, h->d_kaldi_melw.p, (int32_t)h->d_kaldi_melw.n, meta, meta + h->nb,
-                           meta + 2 * h->nb, h->d_kaldi_dct_t.p, p.feat, p.feat_pitch, h->kaldi_flags, h->kaldi_log_floor,
+                           h->kaldi_remove_dc ? 1 : 0, h->kaldi_use_power ? 1 : 0, h->d_kaldi_ops.p, mel_spans(h), (int32_t)h->d_span_melw.n,
+                           h->d_kaldi_dct_t.p, p.feat, p.feat_pitch, h->kaldi_flags, h->kaldi_log_floor,
                            h->d_kaldi_bounds.p, centred_utts};
             HIP_TRY(h, launch_kaldi(kp, h->stream));
             break;

@@ -1,5 +1,5 @@
 // mfx_dev.h -- device helpers shared by the gfx950 kernel translation units (mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip):
-// wave-level LDS ordering, LDS reads the optimiser must keep whole, the register FFT butterflies, the fast log; and utt_item, the
+// wave-level LDS ordering and the wave reductions, LDS reads the optimiser must keep whole, the register FFT butterflies, the fast log; and utt_item, the
 // decode of an utterance tiling's item that mfx_vad.hip, mfx_onorm.hip, mfx_pitch.hip and mfx_pitchfeat.hip share.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -76,6 +76,28 @@ __device__ __forceinline__ void wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Reductions over a wave's 64 lanes (butterflies: every lane ends with the same value, whatever its place)
+__device__ __forceinline__ int wave_sum_i32(int v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__device__ __forceinline__ float wave_sum_f32(float v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__device__ __forceinline__ float wave_max(float v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
 }
 
 // 8-byte LDS read that the load/store optimiser must not fuse with a neighbour: ds_read2_b64 costs

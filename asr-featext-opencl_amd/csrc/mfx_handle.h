@@ -596,18 +596,19 @@ struct mfx_handle {
     bool stft = false;
     mfx::StftForm stft_form = mfx::StftForm::None; // Fft (N = 1024 / 2048): k_stft_fft_mel stands where k_stft_mel does; batch entries only
     int stft_R = 0;                      // frames per block of the form's batch kernel (stft_tile_rows)
-    DevBuf<float> d_stft_ops, d_stft_melw; // basis operands -- FFT form: window and FFT tables -- (mfx_set_window builds them); the mel
-                                         // rows' spans back to back
-    DevBuf<int32_t> d_stft_mel;          // [3][nb]: beg, len, first weight of every row
+    DevBuf<float> d_stft_ops;            // basis operands -- FFT form: window and FFT tables -- (mfx_set_window builds them)
+    // the mel table of an STFT log-mel or a Kaldi handle (a handle is one or the other; mel_spans below): the rows' spans back to
+    // back, and [3][nb]: beg, len, first weight of every row
+    DevBuf<float> d_span_melw;
+    DevBuf<int32_t> d_span_mel;
     // mfx_config.method == MFX_METHOD_KALDI: k_kaldi_front IS the front end (FrontKind kKaldi), for the batch and the session
     // entries; everything behind it is an MFCC handle's.  W2 is the DFT length kaldi_fft_size(W); none of the FFT / mel / DCT
     // tables below exist on such a handle
     bool kaldi = false;
     float kaldi_preemph = 0.97f;         // the three options (mfx_kaldi_set_options), Kaldi's defaults
     bool kaldi_remove_dc = true, kaldi_use_power = true;
-    DevBuf<float> d_kaldi_ops, d_kaldi_melw, d_kaldi_dct_t; // window and FFT tables (mfx_set_window builds them); the bands' spans
-                                         // back to back; G transposed [nb][ceps] (empty at ceps == 0)
-    DevBuf<int32_t> d_kaldi_mel;         // [3][nb]: beg, len, first weight of every band
+    DevBuf<float> d_kaldi_ops, d_kaldi_dct_t; // window and FFT tables (mfx_set_window builds them); G transposed [nb][ceps] (empty at
+                                         // ceps == 0)
     int kaldi_flags = 0;                 // kaldi_flags of mfx_create_kaldi (kKaldi* of mfx_tables.h), checked at creation
     float kaldi_log_floor = -INFINITY;   // (float)log(kaldi_energy_floor), -inf for none
     DevBuf<int64_t> d_kaldi_bounds;      // kKaldiNoSnipEdges: [n_utt][2] first sample and samples of the plan's utterances (a
@@ -844,11 +845,16 @@ inline int64_t utt_frame_count(const mfx_handle *h, int64_t samples)
     if (h->kaldi) return mfx::kaldi_frame_count(samples, h->W, h->S, h->kaldi_flags); // (flags 0: frame_count's rule)
     return h->stft ? mfx::stft_frame_count(samples, h->W, h->S) : mfx::frame_count(samples, h->W, h->S);
 }
+// the mel table of an STFT log-mel or a Kaldi handle as its kernels take it
+inline mfx::MelSpans mel_spans(const mfx_handle *h)
+{
+    const int32_t *meta = h->d_span_mel.p; // [3][nb]
+    return mfx::MelSpans{h->d_span_melw.p, meta, meta + h->nb, meta + 2 * h->nb};
+}
 // what every STFT log-mel kernel takes from the handle: shape, post mode, operands and the mel spans, for rows to `out`
 inline mfx::StftCore stft_core(const mfx_handle *h, float *out, int pitch)
 {
-    const int32_t *meta = h->d_stft_mel.p; // [3][nb]
-    return mfx::StftCore{h->W, h->S, h->nb, h->cfg.logmel_post, h->d_stft_ops.p, h->d_stft_melw.p, meta, meta + h->nb, meta + 2 * h->nb, out, pitch};
+    return mfx::StftCore{h->W, h->S, h->nb, h->cfg.logmel_post, h->d_stft_ops.p, mel_spans(h), out, pitch};
 }
 // normalised columns of a speaker list and of the online normaliser: the whole row after the deltas, else the statics
 inline int spk_wn(const mfx_handle *h) { return h->cfg.norm_after_dyn ? h->width : h->cols; }

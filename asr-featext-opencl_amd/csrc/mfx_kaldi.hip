@@ -9,10 +9,12 @@
 // other, in its own buffer of M complex points:
 //   - the exact integer sum of the frame's W samples by a wave reduction (shuffles), mean = (float)s / (float)W;
 //   - d = x - mean, e[i] = fmaf(-c, d[i - 1], d[i]), z = e * w as M complex points (z[2 n], z[2 n + 1]), zero from tap W on;
-//   - a complex FFT of M = 64, 128 or 256 points, Stockham autosort, radix 4 (M = 128: three stages, then one of radix 2): the
-//     stages of mfx_stft_fft.hip with one butterfly per lane, lanes beyond M / 4 idle.  A stage reads all of its inputs into
-//     registers before it writes any output, so one buffer serves, and only the wave synchronises;
-//   - the real split for bins k < M (the Nyquist bin has no mel weight) and the power, or its root, into s_P [frame][KP].
+//   - a complex FFT of M = 64, 128 or 256 points, Stockham autosort, radix 4 (M = 128: three stages, then one of radix 2):
+//     wave_fft_half of mfx_wavefft_dev.h, the stages k_stft_fft_mel runs, here with one butterfly per lane, lanes beyond M / 4
+//     idle.  A stage reads all of its inputs into registers before it writes any output, so one buffer serves, and only the
+//     wave synchronises;
+//   - the real split (real_split_power of the same header) for bins k < M (the Nyquist bin has no mel weight) and the power, or
+//     its root, into s_P [frame][KP].
 // The float32 operations a frame sees are those of this one instruction stream: they depend on N alone, not on the chunk, the
 // wave, the frame's place in its block, the batch or the entry.  After a block barrier the mel chains and the log run one
 // (frame, band) per thread into the span's words -- every wave has left the span by then --, the cepstra one (frame, i) per
@@ -52,8 +54,8 @@ size_t kaldi_lds_bytes(int W, int S, int M, int C, int flags)
 hipError_t launch_kaldi(const KaldiParams &p, hipStream_t stream)
 {
     if (p.n_chunks <= 0) return hipSuccess;
-    if (!kaldi_shape_ok(p.W, p.S, p.M, p.C) || p.N != kaldi_fft_size(p.W) || !p.pcm || !p.chunks || !p.operands || !p.mel_w || !p.mel_beg ||
-        !p.mel_len || !p.mel_off || p.mel_w_floats < 1 || p.mel_w_floats > p.N || (p.C > 0 && !p.dct_t) || !p.feat || !kaldi_flags_ok(p.flags) ||
+    if (!kaldi_shape_ok(p.W, p.S, p.M, p.C) || p.N != kaldi_fft_size(p.W) || !p.pcm || !p.chunks || !p.operands || !p.mel.w || !p.mel.beg ||
+        !p.mel.len || !p.mel.off || p.mel_w_floats < 1 || p.mel_w_floats > p.N || (p.C > 0 && !p.dct_t) || !p.feat || !kaldi_flags_ok(p.flags) ||
         p.feat_pitch < kaldi_static_cols(p.M, p.C, p.flags) || ((p.flags & kKaldiNoSnipEdges) && (!p.utt_bounds || p.n_utt <= 0)))
         return hipErrorInvalidValue;
     const size_t lds = kaldi_lds_bytes(p.W, p.S, p.M, p.C, p.flags);

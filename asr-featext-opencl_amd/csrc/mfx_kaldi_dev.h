@@ -1,11 +1,13 @@
 // mfx_kaldi_dev.h -- the block body of the Kaldi front end, shared by k_kaldi_front (mfx_kaldi.hip) and k_kaldi_front_opts
-// (mfx_kaldi_opts.hip: the build for kaldi_flags of mfx_create_kaldi != 0).  mfx_kaldi.hip describes the structure.
+// (mfx_kaldi_opts.hip: the build for kaldi_flags of mfx_create_kaldi != 0).  mfx_kaldi.hip describes the structure; the wave FFT,
+// the real split and the mel chain are those of mfx_wavefft_dev.h, which the STFT FFT form shares.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "mfx_dev.h"
 #include "mfx_kernels.h"
 #include "mfx_tile_dev.h"
+#include "mfx_wavefft_dev.h"
 
 namespace mfx {
 
@@ -22,82 +24,6 @@ __host__ __device__ inline int kaldi_xo_floats(int W, int S, int M)
 }
 __host__ __device__ inline int kaldi_c_floats(int C) { return (kKaldiRows * C + 3) & ~3; }
 __host__ __device__ inline int kaldi_meta_words(int M) { return (3 * M + 3) & ~3; }
-
-// One radix-4 Stockham stage over the MH points of the wave's buffer, in place: sub-transform length LEN before the stage,
-// stride ST = MH / LEN; lane l < MH / 4 reads the inputs of butterfly l, the wave synchronises, then it writes.  tw: W_MH^k.
-template <int MH, int LEN>
-__device__ __forceinline__ void kaldi_fft_stage4(float2 *buf, const float2 *tw, int lane)
-{
-    constexpr int ST = MH / LEN, N1 = LEN / 4, NBF = MH / 4;
-    const bool on = lane < NBF;
-    const int pp = lane / ST, q = lane % ST;
-    float2 v0 = {}, v1 = {}, v2 = {}, v3 = {};
-    if (on) {
-        v0 = buf[q + ST * pp];
-        v1 = buf[q + ST * (pp + N1)];
-        v2 = buf[q + ST * (pp + 2 * N1)];
-        v3 = buf[q + ST * (pp + 3 * N1)];
-    }
-    wave_sync();
-    if (on) {
-        float2 o0, o1, o2, o3;
-        dft4(v0, v1, v2, v3, o0, o1, o2, o3);
-        float2 *y = buf + q + ST * (4 * pp);
-        y[0] = o0;
-        if (LEN == 4) { // (pp = 0: no twiddles)
-            y[ST] = o1, y[2 * ST] = o2, y[3 * ST] = o3;
-        } else {
-            y[ST] = cmul(o1, tw[pp * ST]);
-            y[2 * ST] = cmul(o2, tw[2 * pp * ST]);
-            y[3 * ST] = cmul(o3, tw[3 * pp * ST]);
-        }
-    }
-    wave_sync();
-}
-
-// the last stage of MH = 128: radix 2 at sub-transform length 2 (no twiddles), one butterfly per lane
-template <int MH>
-__device__ __forceinline__ void kaldi_fft_stage2_last(float2 *buf, int lane)
-{
-    constexpr int ST = MH / 2;
-    const bool on = lane < ST;
-    float2 a = {}, b = {};
-    if (on) a = buf[lane], b = buf[lane + ST];
-    wave_sync();
-    if (on) {
-        buf[lane] = make_float2(a.x + b.x, a.y + b.y);
-        buf[lane + ST] = make_float2(a.x - b.x, a.y - b.y);
-    }
-    wave_sync();
-}
-
-template <int MH>
-__device__ __forceinline__ void kaldi_fft_half(float2 *buf, const float2 *tw, int lane)
-{
-    static_assert(MH == 64 || MH == 128 || MH == 256, "the three lengths of the method");
-    kaldi_fft_stage4<MH, MH>(buf, tw, lane);
-    kaldi_fft_stage4<MH, MH / 4>(buf, tw, lane);
-    kaldi_fft_stage4<MH, MH / 16>(buf, tw, lane);
-    if constexpr (MH == 256)
-        kaldi_fft_stage4<MH, 4>(buf, tw, lane);
-    else if constexpr (MH == 128)
-        kaldi_fft_stage2_last<MH>(buf, lane);
-}
-
-__device__ __forceinline__ int wave_sum_i32(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// (a butterfly: every lane ends with the same float, whatever its place)
-__device__ __forceinline__ float wave_sum_f32(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // LDS, all of it dynamic (kaldi_lds_bytes is the whole of what a block asks for):
 //   s_x [max(15 S + W, 16 M)] (later the log mel rows [16][M]) | s_c [16][C] | window [N] | W_MH^k [MH] complex | -i W_N^k [MH]
@@ -155,8 +81,8 @@ __device__ __forceinline__ void kaldi_block(const KaldiParams &p, float *smem)
 #pragma unroll
         for (int i = tid; i < 3 * N; i += 256) s_w[i] = p.operands[i];
         const int nw = p.mel_w_floats < N ? p.mel_w_floats : N;
-        for (int i = tid; i < nw; i += 256) s_mw[i] = p.mel_w[i];
-        for (int i = tid; i < nb; i += 256) s_meta[i] = p.mel_beg[i], s_meta[nb + i] = p.mel_len[i], s_meta[2 * nb + i] = p.mel_off[i];
+        for (int i = tid; i < nw; i += 256) s_mw[i] = p.mel.w[i];
+        for (int i = tid; i < nb; i += 256) s_meta[i] = p.mel.beg[i], s_meta[nb + i] = p.mel.len[i], s_meta[2 * nb + i] = p.mel.off[i];
     }
     __syncthreads();
 
@@ -199,18 +125,12 @@ __device__ __forceinline__ void kaldi_block(const KaldiParams &p, float *smem)
             if (lane == 0) s_P[f * KP + MH] = le;
         }
         wave_sync();
-        kaldi_fft_half<MH>(s_f, s_tw, lane);
+        wave_fft_half<MH>(s_f, s_tw, lane);
         float *P = s_P + f * KP;
 #pragma unroll
         for (int b = 0; b < MH / 64; ++b) {
             const int k = lane + 64 * b;
-            const float2 zk = s_f[k], zm = s_f[(MH - k) & (MH - 1)];
-            const float sr = zk.x + zm.x, si = zk.y - zm.y;
-            const float dr = zk.x - zm.x, di = zk.y + zm.y;
-            const float2 w = s_sp[k];
-            const float re = 0.5f * (sr + (w.x * dr - w.y * di));
-            const float im = 0.5f * (si + (w.x * di + w.y * dr));
-            const float pw = __builtin_fmaf(im, im, re * re);
+            const float pw = real_split_power(s_f[k], s_f[(MH - k) & (MH - 1)], s_sp[k]);
             P[k] = p.use_power ? pw : sqrtf(pw);
         }
         wave_sync(); // (the next frame takes the buffer)
@@ -223,11 +143,7 @@ __device__ __forceinline__ void kaldi_block(const KaldiParams &p, float *smem)
         for (int i = tid; i < n; i += 256) {
             const int t = div_small(i, nb, magic);
             const int m = i - t * nb;
-            const int len = s_meta[nb + m];
-            const float *w = s_mw + s_meta[2 * nb + m];
-            const float *P = s_P + t * KP + s_meta[m];
-            float acc = 0.f;
-            for (int j = 0; j < len; ++j) acc = __builtin_fmaf(w[j], P[j], acc);
+            const float acc = mel_span_chain(s_mw + s_meta[2 * nb + m], s_P + t * KP + s_meta[m], s_meta[nb + m]);
             if (OPTS) // (fbank with the energy column: it leads the bands, or under HTK follows them)
                 s_x[t * xp + m + (xp > nb && !htk ? 1 : 0)] = logf(fmaxf(acc, 0x1p-23f));
             else

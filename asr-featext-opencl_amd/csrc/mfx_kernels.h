@@ -627,14 +627,20 @@ inline StftChunk make_stft_chunk(int64_t utt_off, int64_t utt_len, int64_t out_r
 
 constexpr int kStftKSteps = 2; // steps of 4 taps per LDS buffer of basis operands
 
+// A mel table as the STFT log-mel and the Kaldi kernels read it (pack_mel_spans of mfx_tables.h): the rows' non-zero spans back to
+// back, and per row its first bin, its bins and its first weight
+struct MelSpans {
+    const float *w;
+    const int32_t *beg, *len, *off; // [M]
+};
+
 // what every kernel of the method takes: the shape, the post mode, the DFT operands of the handle's form, the mel spans, the rows
 struct StftCore {
     int32_t N, S, M;            // DFT length, hop, mel bands
     int32_t post;               // MFX_LOGMEL_*
     const float *operands;      // matrix form: [pass][step][tile of the pass][64] (build_stft_operands); FFT form: the window, the
                                 // twiddles and the split table back to back (build_stft_fft_operands: 3 N + 2 floats)
-    const float *mel_w;         // the rows' non-zero spans back to back
-    const int32_t *mel_beg, *mel_len, *mel_off; // [M] first bin, bins, first weight of every row
+    MelSpans mel;               // the rows of the Slaney table
     float *out;
     int32_t out_pitch;
 };
@@ -688,9 +694,8 @@ struct KaldiParams {
     float preemph;              // c in [0, 1]
     int32_t remove_dc, use_power;
     const float *operands;      // window [N] zero padded | W_{N/2}^k, k < N / 2, complex | -i W_N^k, k < N / 2, complex (build_kaldi_operands)
-    const float *mel_w;         // the bands' non-zero spans back to back
-    int32_t mel_w_floats;       // their floats: 1 .. N (a bin lies in two bands at most)
-    const int32_t *mel_beg, *mel_len, *mel_off; // [M] first bin, bins, first weight of every band
+    MelSpans mel;               // the bands of Kaldi's table
+    int32_t mel_w_floats;       // floats of mel.w: 1 .. N (a bin lies in two bands at most)
     const float *dct_t;         // [M][C]: G transposed (null at C = 0)
     float *feat;                // [rows][feat_pitch], statics at columns [0, kaldi_static_cols(M, C, flags))
     int32_t feat_pitch;

@@ -226,7 +226,7 @@ __global__ void __launch_bounds__(256) k_sess_stft_mel(SessStftParams p)
 // a core any kernel of the method can run on: a shape inside the limits, every table and the rows in place
 bool stft_core_ok(const StftCore &c)
 {
-    return stft_shape_ok(c.N, c.S, c.M) && c.out_pitch >= c.M && c.operands && c.mel_w && c.mel_beg && c.mel_len && c.mel_off && c.out;
+    return stft_shape_ok(c.N, c.S, c.M) && c.out_pitch >= c.M && c.operands && c.mel.w && c.mel.beg && c.mel.len && c.mel.off && c.out;
 }
 
 size_t stft_matrix_lds_bytes(int N, int S, int M, int tile_rows)

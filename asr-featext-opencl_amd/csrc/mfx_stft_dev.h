@@ -3,8 +3,8 @@
 //   stft_bins, stft_p_pitch   bins of a DFT of N points; the row pitch of the power rows in LDS
 //   stft_stage_span           the PCM span of a run of centred frames into LDS: reflected, converted, scaled
 //   stft_xo_floats            the overlay both block kernels stage their span in and assemble their rows in
-//   stft_mel_log              the Slaney mel chains and the log over power rows in LDS, one (frame, band) per thread
-//   wave_max                  the largest value of a wave's lanes
+//   stft_mel_log              the Slaney mel chains (mel_span_chain of mfx_wavefft_dev.h) and the log over power rows in LDS, one
+//                             (frame, band) per thread
 //   stft_finish_block         the tail of a block of the batch kernels: mel and log, the block's maximum, the rows out
 #pragma once
 #include <hip/hip_runtime.h>
@@ -14,6 +14,7 @@
 #include "mfx_dev.h"
 #include "mfx_kernels.h"
 #include "mfx_tile_dev.h"
+#include "mfx_wavefft_dev.h"
 
 namespace mfx {
 
@@ -32,13 +33,6 @@ __host__ __device__ inline int stft_xo_floats(int N, int S, int M, int R, int pa
 {
     const int a = (R - 1) * S + N + pad, b = R * M;
     return ((a > b ? a : b) + 3) & ~3;
-}
-
-__device__ __forceinline__ float wave_max(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
 }
 
 // Words [0, span) of s_x: samples base .. base + span - 1 of the utterance (or stream) of n samples whose sample 0 lies -- or
@@ -70,11 +64,8 @@ __device__ __forceinline__ float stft_mel_log(const StftCore &p, const float *s_
     for (int i = tid; i < n; i += 256) {
         const int t = div_small(i, M, magic);
         const int m = i - t * M;
-        const int beg = p.mel_beg[m], len = p.mel_len[m];
-        const float *w = p.mel_w + p.mel_off[m];
-        const float *P = s_P + t * KP + beg;
-        float acc = 0.f;
-        for (int j = 0; j < len; ++j) acc = __builtin_fmaf(w[j], P[j], acc);
+        const int beg = p.mel.beg[m], len = p.mel.len[m];
+        const float acc = mel_span_chain(p.mel.w + p.mel.off[m], s_P + t * KP + beg, len);
         const float v = fmaxf(acc, 1e-10f);
         float L;
         if (p.post == 2)

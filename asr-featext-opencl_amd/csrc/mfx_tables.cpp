@@ -521,12 +521,16 @@ void build_stft_fft_tables(int N, float *twid, float *split)
     std::copy(t.begin(), t.end(), split);
 }
 
-void build_stft_fft_operands(int N, const float *window, std::vector<float> &out)
+void build_fft_operands(int W, int N, int n_split, const float *window, std::vector<float> &out)
 {
-    out.assign((size_t)3 * N + 2, 0.f);
-    std::copy(window, window + N, out.begin());
-    build_stft_fft_tables(N, out.data() + N, out.data() + 2 * N);
+    out.assign((size_t)2 * N + 2 * (size_t)n_split, 0.f);
+    std::copy(window, window + W, out.begin());
+    std::vector<float> split((size_t)N + 2);
+    build_stft_fft_tables(N, out.data() + N, split.data());
+    std::copy(split.begin(), split.begin() + 2 * (size_t)n_split, out.begin() + 2 * N);
 }
+
+void build_stft_fft_operands(int N, const float *window, std::vector<float> &out) { build_fft_operands(N, N, N / 2 + 1, window, out); }
 
 void build_stft_form_operands(StftForm form, int N, const float *window, std::vector<float> &out)
 {
@@ -536,18 +540,24 @@ void build_stft_form_operands(StftForm form, int N, const float *window, std::ve
     build_stft_operands(basis.data(), N, stft_pass_tiles(N), out);
 }
 
+void pack_mel_spans(const float *dense, int M, int row_width, std::vector<float> &w, std::vector<int32_t> &meta)
+{
+    w.clear();
+    for (int m = 0; m < M; ++m) {
+        const float *span = dense + (size_t)m * row_width + meta[m];
+        meta[(size_t)2 * M + m] = (int32_t)w.size();
+        w.insert(w.end(), span, span + meta[(size_t)M + m]);
+    }
+    if (w.empty()) w.push_back(0.f); // (every band empty or narrower than a bin: keep the buffer non-null)
+}
+
 void build_slaney_spans(int M, int N, float sample_rate, float low_freq, float high_freq, std::vector<float> &w, std::vector<int32_t> &meta)
 {
     const int K1 = N / 2 + 1;
     std::vector<float> dense((size_t)M * K1);
-    w.clear();
     meta.assign((size_t)3 * M, 0);
     build_slaney_mel(M, N, sample_rate, low_freq, high_freq, dense.data(), meta.data(), meta.data() + M);
-    for (int m = 0; m < M; ++m) {
-        meta[(size_t)2 * M + m] = (int32_t)w.size();
-        w.insert(w.end(), dense.begin() + (size_t)m * K1 + meta[m], dense.begin() + (size_t)m * K1 + meta[m] + meta[(size_t)M + m]);
-    }
-    if (w.empty()) w.push_back(0.f); // (every band narrower than a bin: keep the buffer non-null)
+    pack_mel_spans(dense.data(), M, K1, w, meta);
 }
 
 bool kaldi_freqs_ok(float sample_rate, float low_freq, float high_freq, double *high_abs)
@@ -597,14 +607,9 @@ void build_kaldi_spans(int M, int N, float sample_rate, float low_freq, double h
 {
     const int K = N / 2;
     std::vector<float> dense((size_t)M * K);
-    w.clear();
     meta.assign((size_t)3 * M, 0);
     build_kaldi_mel(M, N, sample_rate, low_freq, high_abs, dense.data(), meta.data(), meta.data() + M);
-    for (int m = 0; m < M; ++m) {
-        meta[(size_t)2 * M + m] = (int32_t)w.size();
-        w.insert(w.end(), dense.begin() + (size_t)m * K + meta[m], dense.begin() + (size_t)m * K + meta[m] + meta[(size_t)M + m]);
-    }
-    if (w.empty()) w.push_back(0.f); // (every band empty: keep the buffer non-null)
+    pack_mel_spans(dense.data(), M, K, w, meta);
 }
 
 void build_kaldi_dct(int M, int C, float lifter, float *G)
@@ -619,16 +624,8 @@ void build_kaldi_dct(int M, int C, float lifter, float *G)
     }
 }
 
-void build_kaldi_operands(int W, int N, const float *window, std::vector<float> &out)
-{
-    out.assign((size_t)3 * N, 0.f);
-    std::copy(window, window + W, out.begin());
-    std::vector<float> t;
-    build_twiddles(N / 2, N / 2, t); // W_M^k, k < M
-    std::copy(t.begin(), t.end(), out.begin() + N);
-    build_split_twiddles(N, false, t); // -i W_N^k, k <= M: the kernel splits bins k < M
-    std::copy(t.begin(), t.begin() + N, out.begin() + 2 * N);
-}
+// (the kernel splits bins k < M)
+void build_kaldi_operands(int W, int N, const float *window, std::vector<float> &out) { build_fft_operands(W, N, N / 2, window, out); }
 
 } // namespace mfx
 

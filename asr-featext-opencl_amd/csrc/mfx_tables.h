@@ -340,13 +340,19 @@ void build_stft_operands(const float *cos_sin, int N, int tb, std::vector<float>
 // twid [M] complex: W_M^k = e^(-2 pi i k / M), the twiddles of the half-length complex FFT; split [M + 1] complex: -i W_N^k, the
 // real split's factors (2 X[k] = (Z[k] + conj Z[M - k]) + split[k] (Z[k] - conj Z[M - k]))
 void build_stft_fft_tables(int N, float *twid, float *split);
-// what k_stft_fft_mel takes as its operands: window [N] | twid [2 M] | split [2 (M + 1)], 3 N + 2 floats
+// What the FFT kernels of two methods take as their operands, in double, rounded once: the window's W taps zero padded to N | W_M^k, k
+// < M = N / 2, complex | the first n_split factors -i W_N^k, complex: 2 N + 2 n_split floats
+void build_fft_operands(int W, int N, int n_split, const float *window, std::vector<float> &out);
+// k_stft_fft_mel's (W = N, every bin k <= M): window [N] | twid [2 M] | split [2 (M + 1)], 3 N + 2 floats
 void build_stft_fft_operands(int N, const float *window, std::vector<float> &out);
 // what mfx_set_window uploads for a handle of `form`: the basis of `window` in stft_pass_tiles(N)-tile passes
 // (build_stft_basis, build_stft_operands), or the FFT form's operands
 void build_stft_form_operands(StftForm form, int N, const float *window, std::vector<float> &out);
-// the Slaney table as the kernels read it: the rows' non-zero spans back to back in `w` (one zero when every band is narrower
-// than a bin: the buffer is never empty), meta [3][M]: first bin, bins, first weight of every row
+// A dense mel table [M][row_width] whose rows' non-zero spans stand in meta [0, M) (first bin) and [M, 2 M) (bins), as the kernels
+// read it (MelSpans): the spans back to back in `w` (one zero when every row is empty: the buffer is never empty) and every row's
+// first weight in meta [2 M, 3 M)
+void pack_mel_spans(const float *dense, int M, int row_width, std::vector<float> &w, std::vector<int32_t> &meta);
+// the Slaney table packed so; meta [3][M]: first bin, bins, first weight of every row
 void build_slaney_spans(int M, int N, float sample_rate, float low_freq, float high_freq, std::vector<float> &w, std::vector<int32_t> &meta);
 
 // Kaldi front end (MFX_METHOD_KALDI; include/mfx.h states the definition; DESIGN.md section 5, "Kaldi front end").
@@ -365,7 +371,7 @@ void build_kaldi_spans(int M, int N, float sample_rate, float low_freq, double h
 // G [C][M] = (float)(l[i] D[i][m]): Kaldi's DCT (row 0 sqrt(1 / M), row i sqrt(2 / M) cos(pi / M (m + 1/2) i)) times its lifter
 // l[i] = 1 + Q / 2 sin(pi i / Q) (1 at Q = 0), in double, rounded once
 void build_kaldi_dct(int M, int C, float lifter, float *G);
-// what k_kaldi_front takes as its operands: the window's W taps zero padded to N | W_{N/2}^k, k < N / 2 | -i W_N^k, k < N / 2: 3 N floats
+// k_kaldi_front's operands (build_fft_operands, the bins k < N / 2): 3 N floats
 void build_kaldi_operands(int W, int N, const float *window, std::vector<float> &out);
 // kaldi_flags of mfx_create_kaldi as the code reads them (MFX_KALDI_* of include/mfx.h)
 constexpr int kKaldiNoSnipEdges = 1, kKaldiUseEnergy = 2, kKaldiEnergyWindowed = 4, kKaldiHtkCompat = 8, kKaldiFlagsAll = 15;

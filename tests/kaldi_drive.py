@@ -46,10 +46,10 @@ FBANK80 = Shape(400, 160, 80, 0)
 MFCC13 = Shape(400, 160, 23, 13)
 
 
-def make(pkg, sh, norm=0, dyn=0, l1=2, l2=2, nad=True, ibs=200000):
-    """A Kaldi handle of the shape under the shape's window and options."""
+def make(pkg, sh, norm=0, dyn=0, l1=2, l2=2, nad=True, ibs=200000, flags=0, floor=0.0):
+    """A Kaldi handle of the shape under the shape's window and options (flags, floor: kaldi_flags and kaldi_energy_floor)."""
     m = pkg.MfccHip(ibs, sh.W, sh.S, sh.M, sh.sr, sh.low, sh.high, sh.C, False, sh.Q, norm, dyn, l1, l2, nad, device=0, bug_compat=False,
-                    method=pkg.METHOD_KALDI)
+                    method=pkg.METHOD_KALDI, kaldi_flags=flags, kaldi_energy_floor=floor)
     m.set_window(pkg.povey_window(sh.W) if sh.window == "povey" else sh.taps())
     m.kaldi_set_options(sh.preemph, sh.remove_dc, sh.use_power)
     return m
