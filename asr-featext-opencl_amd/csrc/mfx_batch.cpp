@@ -69,6 +69,26 @@ int run_online_norm(mfx_handle *h, hipStream_t stream, const float *d_pre, float
     return MFX_OK;
 }
 
+// the sliding-window normaliser of a run: behind the paste, on the tail's stream, from the raw rows y of its scratch (d_raw)
+// into where the rows y go (d_y), all Wy columns, over the chunks of the utterance range
+int run_sliding_norm(mfx_handle *h, hipStream_t stream, const float *d_raw, float *d_y, int u0, int u1)
+{
+    const BatchState &B = h->batch;
+    SlideParams sp{};
+    sp.pre.src = d_raw;
+    sp.pre.src_pitch = B.sl.Wy;
+    sp.pre.out = d_y;
+    sp.pre.out_pitch = B.sl.Wy;
+    sp.pre.Wn = B.sl.Wy;
+    sp.pre.segs = B.d_segs.p;
+    sp.pre.chunks = B.sl.chunks.range(u0, u1);
+    sp.pre.tot = B.sl.d_tot.p;
+    sp.pre.u0 = u0, sp.pre.n_utt = u1 - u0;
+    sp.window = B.sl.window, sp.min_window = B.sl.min_window, sp.center = B.sl.center, sp.norm_vars = B.sl.norm_vars;
+    HIP_TRY(h, launch_slide(sp, stream));
+    return MFX_OK;
+}
+
 // ---- stage 1: the checks every layout of the PCM array goes through (the caller's, and the scratch of a rates plan)
 int check_layout(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_total, const std::vector<int64_t> &off,
                  const std::vector<int64_t> &len, int u0, int u1)
@@ -108,8 +128,11 @@ struct RunMode {
                             // selecting VAD (d_last is its scratch) is in force.  d_final is the caller's array, unless a
                             // tensor output is in force: then its row scratch, and k_tensor_pack writes the caller's tensor
     void *d_tensor;         // the caller's array while a tensor output is in force, else null
-    float *d_y;             // where the transform and the VAD read the rows y: d_out, unless pitch features are pasted (d_out
-                            // is then the scratch of the `width` columns, and k_pitch_paste writes the wide rows to d_y)
+    float *d_y;             // where the transform reads the rows y
+    float *d_raw;           // where the rows y are finished and the VAD's decision reads them: d_y, unless the sliding-window
+                            // normaliser is in force (its raw-row scratch; k_slide_apply writes the normalised rows to d_y).
+                            // It is d_out, unless pitch features are pasted (d_out is then the scratch of the `width`
+                            // columns, and k_pitch_paste writes the wide rows to d_raw)
     float *d_pre;           // where everything AHEAD of the normaliser's place writes: d_out, unless the online normaliser is
                             // in force (its raw-row scratch: it must not run in place, its trailing edge reads raw rows that
                             // another block may already have turned into output)
@@ -142,7 +165,8 @@ RunMode decide_mode(const mfx_handle *h, FrontParams &p, float *d_out, bool whol
     m.d_final = B.tn.on ? B.tn.d_rows.p : d_out;
     m.d_last = (B.vad.on && B.vad.mode != MFX_VAD_FLAGS) ? B.vad.d_rows.p : m.d_final;
     m.d_y = B.xf.on ? B.xf.d_y.p : m.d_last;
-    m.d_out = B.pf.on && B.pf.paste ? B.pf.d_narrow.p : m.d_y;
+    m.d_raw = B.sl.on ? B.sl.d_raw.p : m.d_y;
+    m.d_out = B.pf.on && B.pf.paste ? B.pf.d_narrow.p : m.d_raw;
     m.d_pre = B.on.on ? B.on.d_raw.p : m.d_out;
     const bool norm_before = h->cfg.norm != MFX_NORM_NONE && !h->cfg.norm_after_dyn;
     m.sb = (B.ov.enabled && whole) ? (int)(B.ov.seq & 1) : 0;
@@ -152,7 +176,7 @@ RunMode decide_mode(const mfx_handle *h, FrontParams &p, float *d_out, bool whol
     // Not asked for (MFX_ENGINE_FUSE_DELTA): the plain run only -- the planner has looked at the batch's size; nothing
     // attached, no overlap in force (the fused form has no tail to put on the second stream)
     if (m.fuse && !h->fuse.enabled)
-        m.fuse = !B.ov.enabled && !B.rs.on && !B.va.on && !B.xf.on && !B.spk.on && !B.vad.on && !B.on.on && !B.pt.on && !B.pf.on && !B.tn.on;
+        m.fuse = !B.ov.enabled && !B.rs.on && !B.va.on && !B.xf.on && !B.spk.on && !B.vad.on && !B.on.on && !B.sl.on && !B.pt.on && !B.pf.on && !B.tn.on;
     if (m.fuse) {
         p.dl1 = h->l1;
         p.dl2 = h->l2;
@@ -291,13 +315,14 @@ int run_batch_norm(mfx_handle *h, const RunMode &m, int u0, int u1, int groups, 
                     B.tiles_max * 64, groups, group_stats_stride);
 }
 
-// the VAD of a run: decision on the rows y (m.d_y, before a transform), selection from m.d_last into the caller's array
+// the VAD of a run: decision on the rows y (m.d_raw: before a transform, and before the sliding-window normaliser), selection
+// from m.d_last into the caller's array
 int run_vad(mfx_handle *h, const RunMode &m, int u0, int u1)
 {
     BatchState &B = h->batch;
     BatchState::Vad &v = B.vad;
     VadParams vp{};
-    vp.y = m.d_y;
+    vp.y = m.d_raw;
     vp.y_pitch = batch_y_width(h);
     vp.column = v.column;
     vp.segs = B.d_segs.p;
@@ -325,7 +350,8 @@ int run_vad(mfx_handle *h, const RunMode &m, int u0, int u1)
     return MFX_OK;
 }
 
-// ---- stage 5, on m.tail_stream: normaliser before the deltas, deltas, normaliser after them, paste, transform, VAD
+// ---- stage 5, on m.tail_stream: normaliser before the deltas, deltas, normaliser after them, paste, sliding-window
+// normaliser, transform, VAD
 int run_tail(mfx_handle *h, const RunMode &m, int u0, int u1)
 {
     BatchState &B = h->batch;
@@ -358,10 +384,14 @@ int run_tail(mfx_handle *h, const RunMode &m, int u0, int u1)
     if (B.pf.on && B.pf.paste) { // the rows y become [ y | feats ]: the last launch ahead of the transform
         PitchPasteParams pq{};
         pq.narrow = m.d_out, pq.feats = B.pf.d_feats.p;
-        pq.out = m.d_y;
+        pq.out = m.d_raw;
         pq.row0 = B.utt_row[u0], pq.rows = (u1 < B.n_utt ? B.utt_row[u1] : B.total_rows) - B.utt_row[u0];
         pq.Wd = h->width, pq.F = B.pf.F;
         HIP_TRY(h, launch_pitch_paste(pq, m.tail_stream));
+    }
+    if (B.sl.on) { // the rows y, pasted columns included, become their normalised twins: the last link ahead of the transform
+        const int rc = run_sliding_norm(h, m.tail_stream, m.d_raw, m.d_y, u0, u1);
+        if (rc != MFX_OK) return rc;
     }
     if (B.xf.on) { // behind the tail, on its stream: ev_tail covers it
         XformParams xp;
@@ -431,7 +461,7 @@ int batch_run_range(mfx_handle *h, const int16_t *d_pcm, int64_t pcm_samples_tot
     }
     const size_t rows = (size_t)B.total_rows; // (every scratch a launch below writes to holds the plan's rows)
     if ((h->traps && B.d_logmel.n < rows * B.mel_pitch) || !B.xf.sized(rows, batch_y_width(h)) || !B.vad.sized(rows, batch_out_width(h)) ||
-        !B.on.sized(rows, h->width) || !B.pt.sized(rows) || !B.pf.sized(rows, h->width, B.pt.on) || !B.tn.sized(rows, batch_out_width(h)))
+        !B.on.sized(rows, h->width) || !B.sl.sized(rows, batch_y_width(h)) || !B.pt.sized(rows) || !B.pf.sized(rows, h->width, B.pt.on) || !B.tn.sized(rows, batch_out_width(h)))
         return fail(h, MFX_ERR_STATE, "batch not planned");
 
     FrontParams p;

@@ -1,8 +1,8 @@
 // mfx_batch_attach.cpp -- what a caller attaches to a planned batch (include/mfx.h): per-utterance warp factors, a splice +
-// affine transform, a speaker list, the energy VAD, the online normaliser, the pitch track, the pitch features.  Each is tied
-// to the plan (mfx_batch_plan_rates' converter is the ninth, and is the planner's); BatchState::detach drops the eight of this
-// file: the seven above and the dense tensor output, which is set last.  This file owns `batch.va`, `batch.xf`, `batch.spk`,
-// `batch.vad`, `batch.on`, `batch.pt`, `batch.pf` and `batch.tn`.
+// affine transform, a speaker list, the energy VAD, the online normaliser, the sliding-window normaliser, the pitch track, the
+// pitch features.  Each is tied to the plan (mfx_batch_plan_rates' converter is the tenth, and is the planner's);
+// BatchState::detach drops the nine of this file: the eight above and the dense tensor output, which is set last.  This file
+// owns `batch.va`, `batch.xf`, `batch.spk`, `batch.vad`, `batch.on`, `batch.sl`, `batch.pt`, `batch.pf` and `batch.tn`.
 #include "mfx_handle.h"
 
 #include <cmath>
@@ -198,6 +198,49 @@ extern "C" int mfx_batch_clear_online_norm(mfx_handle *h)
     BatchState::Onorm &on = h->batch.on;
     on.drop();
     on.release();
+    return MFX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// sliding-window CMN / CVN ("Sliding-window normalisation")
+// ------------------------------------------------------------------------------------------------
+
+extern "C" int mfx_batch_set_sliding_norm(mfx_handle *h, int32_t window, int32_t min_window, int32_t center, int32_t norm_vars)
+{
+    MFX_DEVICE_ENTRY(h);
+    BatchState &B = h->batch;
+    if (h->cfg.norm != MFX_NORM_NONE)
+        return fail(h, MFX_ERR_CONFIG, "mfx_batch_set_sliding_norm: the handle normalises already (the sliding window replaces norm, it does not stack on it)");
+    if (h->stft) return fail(h, MFX_ERR_CONFIG, "mfx_batch_set_sliding_norm: an STFT log-mel handle is not served");
+    const int Wy = batch_y_width(h);
+    if (Wy > 256) return fail(h, MFX_ERR_CONFIG, "mfx_batch_set_sliding_norm: more than 256 columns");
+    if (!B.planned) return fail(h, MFX_ERR_STATE, "mfx_batch_set_sliding_norm: no batch is planned");
+    if (window < 1 || window > 4096) return fail(h, MFX_ERR_ARG, "mfx_batch_set_sliding_norm: window must be 1 .. 4096");
+    if (min_window < 0 || min_window > window) return fail(h, MFX_ERR_ARG, "mfx_batch_set_sliding_norm: min_window must be 0 .. window");
+    if ((center != 0 && center != 1) || (norm_vars != 0 && norm_vars != 1))
+        return fail(h, MFX_ERR_ARG, "mfx_batch_set_sliding_norm: center and norm_vars must be 0 or 1");
+    for (const int64_t T : B.utt_frames) // (k_slide_apply forms t + window in 32 bits)
+        if (T > 0x7fffffff - 4096) return fail(h, MFX_ERR_ARG, "mfx_batch_set_sliding_norm: utterance too long");
+    int rc = sync_device(h); // (a run in flight may read the lists replaced below)
+    if (rc != MFX_OK) return rc;
+    BatchState::Slide &sl = B.sl;
+    sl.drop();
+    // (everything mfx_batch_run_device needs is allocated here: that entry never allocates)
+    if ((rc = sl.chunks.set(h, kOnormChunk)) != MFX_OK) return rc;
+    HIP_TRY(h, sl.d_tot.alloc(sl.chunks.items() * 2 * Wy));
+    const size_t need = (size_t)std::max<int64_t>(B.total_rows, 1) * Wy;
+    if (sl.d_raw.n < need) HIP_TRY(h, sl.d_raw.alloc(need));
+    sl.window = window, sl.min_window = min_window, sl.center = center, sl.norm_vars = norm_vars, sl.Wy = Wy;
+    sl.on = true;
+    return MFX_OK;
+}
+
+extern "C" int mfx_batch_clear_sliding_norm(mfx_handle *h)
+{
+    MFX_DEVICE_ENTRY(h);
+    if (const int rc = sync_device(h); rc != MFX_OK) return rc; // (a run in flight may read what is released below)
+    h->batch.sl.drop();
+    h->batch.sl.release();
     return MFX_OK;
 }
 
@@ -410,8 +453,8 @@ extern "C" int mfx_batch_clear_pitch(mfx_handle *h)
     MFX_DEVICE_ENTRY(h);
     // (the pitch features go with the track they are computed from; pasted, they are part of the rows a transform or a VAD
     // was sized for)
-    if (batch_y_width(h) != h->width && (h->batch.xf.on || h->batch.vad.on))
-        return fail(h, MFX_ERR_STATE, "mfx_batch_clear_pitch: pasted pitch features are in force under a transform or a VAD (clear those first)");
+    if (batch_y_width(h) != h->width && (h->batch.xf.on || h->batch.vad.on || h->batch.sl.on))
+        return fail(h, MFX_ERR_STATE, "mfx_batch_clear_pitch: pasted pitch features are in force under a transform, a VAD or the sliding-window normaliser (clear those first)");
     if (batch_y_width(h) != h->width && h->batch.tn.on)
         return fail(h, MFX_ERR_STATE, "mfx_batch_clear_pitch: the row width would change under a tensor output (clear the tensor first)");
     if (const int rc = sync_device(h); rc != MFX_OK) return rc; // (a run in flight may read what is released below)
@@ -463,10 +506,10 @@ extern "C" int mfx_batch_set_pitch_feats(mfx_handle *h, int32_t columns, int32_t
         return fail(h, MFX_ERR_ARG,
                     "mfx_batch_set_pitch_feats: columns 0 or MFX_PF_* bits, left and right 0 .. 1024, delta_window 1 .. 16, finite "
                     "scales, paste 0 or 1");
-    if (h->width + (paste ? s.F : 0) != batch_y_width(h) && (B.xf.on || B.vad.on))
+    if (h->width + (paste ? s.F : 0) != batch_y_width(h) && (B.xf.on || B.vad.on || B.sl.on))
         return fail(h, MFX_ERR_STATE,
-                    "mfx_batch_set_pitch_feats: the row width would change under a transform or a VAD (clear them, set the paste, set "
-                    "them again)");
+                    "mfx_batch_set_pitch_feats: the row width would change under a transform, a VAD or the sliding-window normaliser (clear "
+                    "them, set the paste, set them again)");
     if (h->width + (paste ? s.F : 0) != batch_y_width(h) && B.tn.on)
         return fail(h, MFX_ERR_STATE, "mfx_batch_set_pitch_feats: the row width would change under a tensor output (clear the tensor first)");
     if (const int rc = sync_device(h); rc != MFX_OK) return rc; // (a run in flight may read the arrays replaced below)
@@ -497,8 +540,8 @@ extern "C" int mfx_batch_set_pitch_feats(mfx_handle *h, int32_t columns, int32_t
 extern "C" int mfx_batch_clear_pitch_feats(mfx_handle *h)
 {
     MFX_DEVICE_ENTRY(h);
-    if (batch_y_width(h) != h->width && (h->batch.xf.on || h->batch.vad.on))
-        return fail(h, MFX_ERR_STATE, "mfx_batch_clear_pitch_feats: the row width would change under a transform or a VAD (clear them first)");
+    if (batch_y_width(h) != h->width && (h->batch.xf.on || h->batch.vad.on || h->batch.sl.on))
+        return fail(h, MFX_ERR_STATE, "mfx_batch_clear_pitch_feats: the row width would change under a transform, a VAD or the sliding-window normaliser (clear them first)");
     if (batch_y_width(h) != h->width && h->batch.tn.on)
         return fail(h, MFX_ERR_STATE, "mfx_batch_clear_pitch_feats: the row width would change under a tensor output (clear the tensor first)");
     if (const int rc = sync_device(h); rc != MFX_OK) return rc; // (a run in flight may read what is released below)

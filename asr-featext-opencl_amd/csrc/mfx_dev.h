@@ -1,6 +1,6 @@
 // mfx_dev.h -- device helpers shared by the gfx950 kernel translation units (mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip):
 // wave-level LDS ordering and the wave reductions, LDS reads the optimiser must keep whole, the register FFT butterflies, the fast log; and utt_item, the
-// decode of an utterance tiling's item that mfx_vad.hip, mfx_onorm.hip, mfx_pitch.hip and mfx_pitchfeat.hip share.
+// decode of an utterance tiling's item that mfx_vad.hip, mfx_onorm.hip, mfx_slide.hip, mfx_pitch.hip and mfx_pitchfeat.hip share.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -212,7 +212,7 @@ struct BatchState {
     int tiles_max = 0;
     bool aligned = true;                 // frames on aligned sample pairs (fill_front / choose_front read it)
 
-    // Nine attachments, each tied to the plan: a new plan drops them.  drop() switches one off and releases what is not kept
+    // Ten attachments, each tied to the plan: a new plan drops them.  drop() switches one off and releases what is not kept
     // for the next one (the grown-never-shrunk scratch stays); release() names every buffer once, for the clear entry (and a
     // setter that ran out of memory); sized() says whether the scratch a run writes to holds the plan's rows (batch_run_range
     // refuses otherwise).
@@ -313,6 +313,21 @@ struct BatchState {
         void release() { chunks.release(), d_prior.release(), d_tot.release(), d_raw.release(); }
         bool sized(size_t total_rows, int width) const { return !on || d_raw.n >= total_rows * width; }
     } on;
+    // sliding-window CMN / CVN (mfx_batch_set_sliding_norm; norm = NONE handles): while on, everything up to and including
+    // the pitch paste writes the rows y to d_raw instead of where they go today (RunMode::d_raw, mfx_batch.cpp), and
+    // k_onorm_totals -> k_onorm_offsets -> k_slide_apply turn all Wy columns of d_raw into the rows the transform and the
+    // tensor output read.  The VAD's decision keeps reading d_raw.
+    struct Slide {
+        bool on = false;
+        int32_t window = 0, min_window = 0, center = 0, norm_vars = 0;
+        int32_t Wy = 0;                  // the row width the scratch was sized for
+        UttTilingBuf chunks;             // at kOnormChunk
+        DevBuf<double> d_tot;            // [chunks][2][Wy]
+        DevBuf<float> d_raw;             // [total_rows][Wy] (grown, never shrunk: only mfx_batch_clear_sliding_norm releases it)
+        void drop() { on = false; }
+        void release() { chunks.release(), d_tot.release(), d_raw.release(); }
+        bool sized(size_t total_rows, int width) const { return !on || (Wy == width && d_raw.n >= total_rows * width); }
+    } sl;
     // pitch track (mfx_batch_set_pitch): while on, k_pitch_nccf and k_pitch_track follow the front end on the handle's stream
     // and fill the handle-owned arrays below, indexed by the plan's rows; d_out is untouched
     struct Pitch {
@@ -373,7 +388,7 @@ struct BatchState {
     } tn;
     // what a new utterance list invalidates (the converter is mfx_batch_plan's to drop: mfx_batch_plan_rates plans through
     // plan_batch too)
-    void detach() { va.drop(), xf.drop(), spk.drop(), vad.drop(), on.drop(), pt.drop(), pf.drop(), tn.drop(); }
+    void detach() { va.drop(), xf.drop(), spk.drop(), vad.drop(), on.drop(), sl.drop(), pt.drop(), pf.drop(), tn.drop(); }
 
     // ---- not tied to the plan
     // optional overlap of the delta/normalisation tail of batch i with the front end of batch i+1 (mfx_batch_overlap)

@@ -1,4 +1,4 @@
-// mfx_kernels.h -- launch interface of the gfx950 kernels (implemented in mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip, mfx_plp.hip, mfx_traps.hip, mfx_xform.hip, mfx_sess_xform.hip, mfx_sess_resample.hip, mfx_sessions.hip, mfx_resample.hip, mfx_speakers.hip, mfx_vad.hip, mfx_onorm.hip, mfx_stft.hip, mfx_stft_fft.hip, mfx_kaldi.hip, mfx_kaldi_opts.hip, mfx_pitch.hip, mfx_pitchfeat.hip, mfx_tensor.hip: one translation unit per kernel family).
+// mfx_kernels.h -- launch interface of the gfx950 kernels (implemented in mfx_front512.hip, mfx_front_generic.hip, mfx_front2048.hip, mfx_tail.hip, mfx_plp.hip, mfx_traps.hip, mfx_xform.hip, mfx_sess_xform.hip, mfx_sess_resample.hip, mfx_sessions.hip, mfx_resample.hip, mfx_speakers.hip, mfx_vad.hip, mfx_onorm.hip, mfx_slide.hip, mfx_stft.hip, mfx_stft_fft.hip, mfx_kaldi.hip, mfx_kaldi_opts.hip, mfx_pitch.hip, mfx_pitchfeat.hip, mfx_tensor.hip: one translation unit per kernel family).
 //
 // Kernel inventory and the reference stage each one replaces:
 //   spectrum512 / fused512   segmenter.cl kernelSegmentWindow + AppleFFT fft0 + mfcc.cl kernelTranspose
@@ -20,6 +20,8 @@
 //   pitch_feats / pitch_paste  Kaldi's pitch features from that track, and their paste into the rows (no reference analogue)
 //   onorm_*                  online (causal, sliding-window) CMN / CVN of the batch and session entries (no reference analogue: its
 //                            NormalizerCPU keeps one block's statistics)
+//   slide_apply              sliding-window CMN / CVN of the batch entries (apply-cmvn-sliding) on onorm's prefix chains (no
+//                            reference analogue)
 //   stft_mel / stft_post     the STFT log-mel front end: exact-length DFT of centred frames on the matrix pipe, power, Slaney mel, log;
 //                            the clamp by the utterance's maximum and the map (no reference analogue: a neural recogniser's input)
 //   stft_fft_mel             the same front end at DFT lengths 1024 / 2048: window product, a float32 FFT per wave and frame (half-length
@@ -33,7 +35,7 @@
 //                            (no reference analogue: a neural model's input)
 //   delta                    delta.cl kernelDelta x2 + the staging copies of mfccopencl.cpp:360-387
 //   norm_stats / norm_apply  norm.cl kernelSum + kernelFinalizeSum / kernelNormalize
-// What is attached to a planned batch (vad_*, onorm_*, pitch_*, pitch_feats) walks its rows by one work list, UttTiling below.
+// What is attached to a planned batch (vad_*, onorm_*, slide_apply, pitch_*, pitch_feats) walks its rows by one work list, UttTiling below.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -587,6 +589,17 @@ struct OnormParams {
     int32_t u0, n_utt;     // the utterance range of this run: [u0, u0 + n_utt)
 };
 
+// Sliding-window CMN / CVN (mfx_batch_set_sliding_norm; mfx_slide.hip; DESIGN.md, "Sliding-window normalisation"): the
+// online normaliser's prefix chains (launch_onorm_prefix fills pre.tot from pre.src) and k_slide_apply over the same tiling.
+// `pre` carries src, src_pitch, out, out_pitch, Wn, segs, chunks, tot, u0, n_utt; its window, cvn and prior fields are not read.
+struct SlideParams {
+    OnormParams pre;
+    int32_t window;        // N: 1 .. 4096
+    int32_t min_window;    // 0 .. N (read without `center` only)
+    int32_t center;        // 0 / 1
+    int32_t norm_vars;     // 0: CMN, 1: CVN
+};
+
 // k_onorm_sess: the rows one push brings one session, rows [t0, t0 + n_rows) of its stream, normalised in place
 struct OnormSessDesc {
     int64_t row0;          // first row inside OnormSessParams::data
@@ -719,6 +732,8 @@ bool vad_shape_ok(const VadParams &p);
 // online normaliser: chunk totals -> offsets -> apply over the utterance range (three launches); the session form
 hipError_t launch_onorm(const OnormParams &p, hipStream_t stream);
 hipError_t launch_onorm_sess(const OnormSessParams &p, hipStream_t stream);
+hipError_t launch_onorm_prefix(const OnormParams &p, hipStream_t stream); // k_onorm_totals + k_onorm_offsets alone
+hipError_t launch_slide(const SlideParams &p, hipStream_t stream);        // launch_onorm_prefix, then k_slide_apply
 // per-speaker normalisation: chunk totals; accumulators + statistics; apply.  spk_tile_rows: rows of a tile of k_spk_apply at
 // Wn columns; spk_chunks: chunks of kNormChunkRows rows of an utterance of `rows` rows
 hipError_t launch_spk_sums(const SpkParams &p, hipStream_t stream);

@@ -21,9 +21,7 @@ namespace mfx {
 
 namespace {
 
-// A block of the batch kernels serves G = max(1, 256 / Wn) chunks: thread tid is (tile g = tid / Wn, column j = tid % Wn),
-// so that a 39-column row still fills the block's lanes.
-__device__ __forceinline__ int onorm_tiles(int Wn) { return Wn >= 256 ? 1 : 256 / Wn; }
+// (the block's tiles, G = onorm_tiles(Wn) of them, and their LDS image: mfx_onorm_dev.h)
 
 // first row (absolute), row count and local index of chunk c
 __device__ __forceinline__ void onorm_chunk(const OnormParams &p, int c, int64_t &row0, int &rows, int &lc)
@@ -130,26 +128,8 @@ __global__ void __launch_bounds__(256) k_onorm_apply(OnormParams p)
 #pragma unroll
         for (int r = 0; r < kOnormChunk; ++r) w[r] = 0.f;
     }
-    // Word i of the tile area is (row r = i / GW, tile, column c): i / GW and rem / Wn for i < 2^16 as multiply-highs (Wn == 1
-    // would wrap the constant to 0: the shift form).  Four loads are in flight before the first LDS write waits for them.
-    const uint32_t magic_gw = 0xffffffffu / (uint32_t)GW + 1, magic = Wn > 1 ? 0xffffffffu / (uint32_t)Wn + 1 : 0;
-    const int words = kOnormChunk * GW;
-    for (int i0 = tid; i0 < words; i0 += 4 * 256) {
-        float a[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int i = i0 + k * 256;
-            a[k] = 0.f;
-            if (i < words) {
-                const int r = (int)__umulhi((uint32_t)i, magic_gw), rem = i - r * GW;
-                const int gg = Wn > 1 ? (int)__umulhi((uint32_t)rem, magic) : rem, c = rem - gg * Wn;
-                if (r < s_rows[gg]) a[k] = p.src[(s_row0[gg] + r) * (int64_t)p.src_pitch + c];
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (i0 + k * 256 < words) lead[i0 + k * 256] = a[k];
-    }
+    const OnormTileIndex ix(Wn, G);
+    onorm_tiles_load(ix, p.src, p.src_pitch, s_row0, s_rows, lead, tid);
     __syncthreads();
     if (mine) {
         const int lc = s_lc[g];
@@ -186,11 +166,7 @@ __global__ void __launch_bounds__(256) k_onorm_apply(OnormParams p)
         }
     }
     __syncthreads();
-    for (int i = tid; i < words; i += 256) {
-        const int r = (int)__umulhi((uint32_t)i, magic_gw), rem = i - r * GW;
-        const int gg = Wn > 1 ? (int)__umulhi((uint32_t)rem, magic) : rem, c = rem - gg * Wn;
-        if (r < s_rows[gg]) p.out[(s_row0[gg] + r) * (int64_t)p.out_pitch + c] = lead[i];
-    }
+    onorm_tiles_store(ix, p.out, p.out_pitch, s_row0, s_rows, lead, tid);
 }
 
 // one thread per (descriptor, column): the push's rows in ascending order, in place.  Slot t mod N of the ring holds raw row
@@ -258,6 +234,20 @@ bool onorm_shape_ok(int Wn, int window, int prior_frames, int64_t prior_count, c
 
 } // namespace
 
+// k_onorm_totals, then k_onorm_offsets: p.tot holds the offsets O of v and q of every chunk of the range.  Reads src, src_pitch,
+// Wn, segs, chunks, tot, u0, n_utt of `p` (the sliding-window normaliser, mfx_slide.hip, builds its sums on the same chains).
+hipError_t launch_onorm_prefix(const OnormParams &p, hipStream_t stream)
+{
+    if (p.n_utt <= 0 || p.chunks.count <= 0) return hipSuccess;
+    if (p.Wn < 1 || p.Wn > 256 || p.src_pitch < p.Wn || p.chunks.rows != kOnormChunk) return hipErrorInvalidValue;
+    const int G = p.Wn >= 256 ? 1 : 256 / p.Wn;
+    const int blocks = (p.chunks.count + G - 1) / G;
+    hipLaunchKernelGGL(k_onorm_totals, dim3(blocks), dim3(256), 0, stream, p);
+    const int64_t chains = (int64_t)p.n_utt * 2 * p.Wn;
+    hipLaunchKernelGGL(k_onorm_offsets, dim3((unsigned)((chains + 255) / 256)), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
 hipError_t launch_onorm(const OnormParams &p, hipStream_t stream)
 {
     if (p.n_utt <= 0 || p.chunks.count <= 0) return hipSuccess;
@@ -266,9 +256,7 @@ hipError_t launch_onorm(const OnormParams &p, hipStream_t stream)
         return hipErrorInvalidValue;
     const int G = p.Wn >= 256 ? 1 : 256 / p.Wn;
     const int blocks = (p.chunks.count + G - 1) / G;
-    hipLaunchKernelGGL(k_onorm_totals, dim3(blocks), dim3(256), 0, stream, p);
-    const int64_t chains = (int64_t)p.n_utt * 2 * p.Wn;
-    hipLaunchKernelGGL(k_onorm_offsets, dim3((unsigned)((chains + 255) / 256)), dim3(256), 0, stream, p);
+    if (hipError_t e = launch_onorm_prefix(p, stream); e != hipSuccess) return e;
     const size_t lds = (size_t)G * 16 + (size_t)kOnormChunk * G * p.Wn * sizeof(float); // descriptors + lead tiles: <= 36 KB
     hipLaunchKernelGGL(k_onorm_apply, dim3(blocks), dim3(256), lds, stream, p);
     return hipGetLastError();

@@ -1030,6 +1030,61 @@ bool host_online_norm(const float *rows, int64_t T, int pitch, int Wn, int kind,
     return true;
 }
 
+// The sliding-window normaliser's definition (include/mfx.h, mfx_batch_set_sliding_norm) on host memory: per column the
+// online normaliser's chunked prefix sums P of v and of q, then every row's window (slide_window), statistics and float32
+// apply.  Every double operation is a statement of its own and this file is compiled with -ffp-contract=off.
+bool host_sliding_norm(const float *rows, int64_t T, int W, int pitch, int window, int min_window, int center, int norm_vars, float *out,
+                       int out_pitch)
+{
+    if (T < 0 || W < 1 || W > 256 || pitch < W || out_pitch < W) return false;
+    if (window < 1 || window > 4096 || min_window < 0 || min_window > window) return false;
+    if ((center != 0 && center != 1) || (norm_vars != 0 && norm_vars != 1) || (T > 0 && (!rows || !out))) return false;
+    std::vector<double> Pv((size_t)T), Pq((size_t)T);
+    for (int j = 0; j < W; ++j) {
+        double Ov = 0.0, Oq = 0.0, Iv = 0.0, Iq = 0.0;
+        for (int64_t t = 0; t < T; ++t) {
+            const float v = rows[t * pitch + j];
+            const float q = v * v;
+            Iv = Iv + (double)v;
+            Iq = Iq + (double)q;
+            Pv[(size_t)t] = Ov + Iv;
+            Pq[(size_t)t] = Oq + Iq;
+            if (t % 32 == 31) { // the chunk's last row: Tot = I
+                Ov = Ov + Iv;
+                Oq = Oq + Iq;
+                Iv = 0.0, Iq = 0.0;
+            }
+        }
+        for (int64_t t = 0; t < T; ++t) {
+            int64_t ws, we;
+            slide_window(T, window, min_window, center != 0, t, ws, we);
+            const double Sw = Pv[(size_t)(we - 1)] - (ws > 0 ? Pv[(size_t)(ws - 1)] : 0.0);
+            const double Qw = Pq[(size_t)(we - 1)] - (ws > 0 ? Pq[(size_t)(ws - 1)] : 0.0);
+            const int64_t n = we - ws;
+            const float v = rows[t * pitch + j];
+            const double nn = (double)n;
+            const double m = Sw / nn;
+            const float mean = (float)m;
+            float y = v - mean;
+            if (norm_vars) {
+                if (n == 1) {
+                    y = 0.0f;
+                } else {
+                    const double e2 = Qw / nn;
+                    const double mm = m * m;
+                    double var = e2 - mm;
+                    if (var < 1e-10) var = 1e-10;
+                    const double sd = std::sqrt(var);
+                    const double inv = 1.0 / sd;
+                    y = y * (float)inv;
+                }
+            }
+            out[t * out_pitch + j] = y;
+        }
+    }
+    return true;
+}
+
 // ---- pitch track (include/mfx.h, mfx_batch_set_pitch)
 
 bool pitch_shape(int window, int lag_min, int lag_max, float ballast, float lag_cost, float penalty, int max_jump, PitchShape &s)
@@ -1295,6 +1350,20 @@ extern "C" int mfx_host_online_norm(const float *rows, int64_t T, int32_t pitch,
                                     int32_t prior_frames, int64_t prior_count, const double *prior_acc, float *out)
 {
     return mfx::host_online_norm(rows, T, pitch, Wn, kind, window, prior_frames, prior_count, prior_acc, out) ? 0 : -7 /* MFX_ERR_ARG */;
+}
+
+extern "C" int mfx_host_sliding_window(int64_t T, int32_t window, int32_t min_window, int32_t center, int64_t t, int64_t *ws, int64_t *we)
+{
+    if (window < 1 || window > 4096 || min_window < 0 || min_window > window || (center != 0 && center != 1) || t < 0 || t >= T || !ws || !we)
+        return -7 /* MFX_ERR_ARG */;
+    mfx::slide_window<int64_t>(T, window, min_window, center != 0, t, *ws, *we);
+    return 0;
+}
+
+extern "C" int mfx_host_sliding_norm(const float *rows, int64_t T, int32_t W, int32_t pitch, int32_t window, int32_t min_window,
+                                     int32_t center, int32_t norm_vars, float *out, int32_t out_pitch)
+{
+    return mfx::host_sliding_norm(rows, T, W, pitch, window, min_window, center, norm_vars, out, out_pitch) ? 0 : -7 /* MFX_ERR_ARG */;
 }
 
 // ------------------------------------------------------------------------------------------------

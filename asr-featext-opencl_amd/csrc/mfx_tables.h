@@ -127,6 +127,42 @@ bool build_speaker_lists(const int32_t *utt_spk, const int64_t *frames, int n_ut
 bool host_online_norm(const float *rows, int64_t T, int pitch, int Wn, int kind, int window, int prior_frames, int64_t prior_count,
                       const double *prior_acc, float *out);
 
+// The sliding-window normaliser (mfx_batch_set_sliding_norm): the window [ws, we) of row t of an utterance of T rows, Kaldi's
+// SlidingWindowCmn rule as include/mfx.h restates it.  One definition for the host restatement and k_slide_apply.
+// 0 <= t < T, window >= 1, 0 <= min_window: then 0 <= ws <= t < we <= T.
+#if defined(__HIP__)
+#define MFX_HOST_DEVICE __host__ __device__
+#else
+#define MFX_HOST_DEVICE
+#endif
+// (I: int64_t on the host; int in the kernel: T + window must fit, and its utterances hold fewer than 2^31 - 4096 rows)
+template <class I>
+MFX_HOST_DEVICE inline void slide_window(I T, int window, int min_window, bool center, I t, I &ws, I &we)
+{
+    if (center) {
+        ws = t - window / 2;
+        we = ws + window;
+    } else {
+        ws = t - window;
+        we = t + 1;
+    }
+    if (ws < 0) {
+        we -= ws;
+        ws = 0;
+    }
+    if (!center) we = t + 1 > (I)min_window ? t + 1 : (I)min_window;
+    if (we > T) {
+        ws -= we - T;
+        we = T;
+        if (ws < 0) ws = 0;
+    }
+}
+#undef MFX_HOST_DEVICE
+// The definition on host memory: rows [T][pitch], columns [0, W) -> out [T][out_pitch].  False -- and nothing written -- on an
+// argument outside the limits of include/mfx.h.
+bool host_sliding_norm(const float *rows, int64_t T, int W, int pitch, int window, int min_window, int center, int norm_vars, float *out,
+                       int out_pitch);
+
 // Utterance tilings ("Utterance tilings"): the rows of every utterance of a planned batch cut into items of `rows`
 // consecutive rows (the last one of an utterance may be shorter), numbered through the batch in utterance order.
 //   item0    : [n_utt + 1] first item of every utterance (a frameless utterance owns none)

@@ -56,6 +56,11 @@ struct Options {
     std::vector<float> file_alpha; // its factors: file i of the list is extracted with file_alpha[i]
     int online_window = -1;        // --online-window: online (causal) CMN / CVN of the batches, window in frames (0: cumulative)
     int online_prior_frames = 0;   // --online-prior-frames
+    int cmn_window = 0;            // --cmn-window: sliding-window CMN / CVN of the batches (apply-cmvn-sliding), window in frames (0: off)
+    int cmn_center = 0;            // --cmn-center 0|1
+    int cmn_min_window = -1;       // --cmn-min-window (-1: apply-cmvn-sliding's 100, or the window if that is shorter)
+    bool cmn_norm_vars = false;    // --cmn-norm-vars
+    bool cmn_options = false;      // one of the three was given
     std::string spk_file;          // --spk-file: one speaker label per line, in the order of the input list
     std::vector<int> file_spk;     // its labels as ids, numbered by first appearance: file i belongs to speaker file_spk[i]
     int n_spk = 0;
@@ -916,6 +921,8 @@ void worker(const Options &o, int device, float sr, const std::vector<std::strin
                     if (o.online_window >= 0) // --online-window: every file normalised causally, as a live stream would be
                         param.batch_set_online_norm(o.online_window, o.online_prior_frames);
                     if (o.pitch) set_pitch(); // (ahead of the VAD, which is sized for the wide rows)
+                    if (o.cmn_window > 0) // --cmn-window: behind the paste (all columns are normalised); the VAD decides on the raw rows
+                        param.batch_set_sliding_norm(o.cmn_window, o.cmn_min_window, o.cmn_center, o.cmn_norm_vars ? 1 : 0);
                     if (o.vad)
                         param.batch_set_vad(o.vad_column, o.vad_energy_threshold, o.vad_energy_mean_scale, o.vad_frames_context,
                                             o.vad_proportion_threshold, MFX_VAD_SELECT);
@@ -930,6 +937,7 @@ void worker(const Options &o, int device, float sr, const std::vector<std::strin
                         it.out_frames = o.vad ? voiced[k] : it.frames;
                         if (o.vad) continue; // (selected rows have no reference analogue: nothing of B1 to reproduce on them)
                         if (o.online_window >= 0) continue; // (nor have causally normalised rows)
+                        if (o.cmn_window > 0) continue;     // (nor rows normalised over a sliding window)
                         // The reference's flush after exactly one set_input reads its D static rows D rows early (B1,
                         // mfcccpu.cpp:439 + segmentercpu.cpp:97-106): rows T - D .. T - 1 repeat the statics of rows
                         // T - 2 D .. T - D - 1 (deltas unaffected).  The batch entries deliver the correct rows; the
@@ -950,6 +958,10 @@ void worker(const Options &o, int device, float sr, const std::vector<std::strin
                                 throw std::runtime_error("--online-window: \"" + files[2 * it.file] +
                                                          "\" would take the per-file loop (longer than one block, too short for the "
                                                          "deltas, or an alpha sweep): the online normaliser runs in batches of whole files only");
+                            if (o.cmn_window > 0)
+                                throw std::runtime_error("--cmn-window: \"" + files[2 * it.file] +
+                                                         "\" would take the per-file loop (longer than one block, too short for the "
+                                                         "deltas, or an alpha sweep): the sliding-window normaliser runs in batches of whole files only");
                             if (o.pitch)
                                 throw std::runtime_error("--pitch: \"" + files[2 * it.file] +
                                                          "\" would take the per-file loop (longer than one block, too short for the "
@@ -1046,6 +1058,14 @@ int main(int argc, char **argv)
         else if (a == "--spk-file") o.spk_file = val();
         else if (a == "--online-window") o.online_window = std::atoi(val());
         else if (a == "--online-prior-frames") o.online_prior_frames = std::atoi(val());
+        else if (a == "--cmn-window") o.cmn_window = std::atoi(val()), o.cmn_options = true;
+        else if (a == "--cmn-center") o.cmn_center = std::atoi(val()), o.cmn_options = true;
+        else if (a == "--cmn-min-window") {
+            const int m = std::atoi(val());
+            o.cmn_min_window = m < 0 ? -2 : m; // (-1 is "not given": a negative value is refused below)
+            o.cmn_options = true;
+        }
+        else if (a == "--cmn-norm-vars") o.cmn_norm_vars = o.cmn_options = true;
         else if (a == "--selftest-spk-labels") { // the label -> id mapping of --spk-file, on a file of labels: prints the ids
             FILE *fl = std::fopen(val(), "r");
             if (!fl) {
@@ -1195,6 +1215,13 @@ int main(int argc, char **argv)
                         "                normalised with the last n rows of its file, itself included (0: all rows so far; else a\n"
                         "                multiple of 32 up to 4096).  --online-prior-frames is handed on for a prior, of which the\n"
                         "                driver has none to give: it changes nothing yet\n"
+                        "         [--cmn-window n [--cmn-center 0|1] [--cmn-min-window m] [--cmn-norm-vars]]\n"
+                        "  --cmn-window: sliding-window CMN, with --cmn-norm-vars CVN (apply-cmvn-sliding; needs --norm 0, batches;\n"
+                        "                excludes --spk-file and --online-window): every row is normalised with the statistics of n\n"
+                        "                rows of its file (1 .. 4096) around it (--cmn-center 1) or behind it (default; at least\n"
+                        "                --cmn-min-window of them at a file's start, default 100).  All columns, pasted pitch features\n"
+                        "                included; --vad decides on the rows as they were before.  Restated from Kaldi's\n"
+                        "                SlidingWindowCmn; agreement with a Kaldi binary has not been measured\n"
                         "         [--resample-to hz [--resample-zeros n]]\n"
                         "  --resample-to: extract at hz instead of the first file's rate; files at other rates are converted on the\n"
                         "                device (Hann-windowed sinc, n zero crossings per side, default 6)\n"
@@ -1275,6 +1302,37 @@ int main(int argc, char **argv)
         }
         if (!o.spk_file.empty()) {
             std::fprintf(stderr, "--online-window and --spk-file exclude each other: one normaliser per run\n");
+            return 2;
+        }
+    }
+    if (o.cmn_options) {
+        if (o.cmn_window < 1 || o.cmn_window > 4096) {
+            std::fprintf(stderr, "--cmn-window must be 1 .. 4096 (--cmn-center, --cmn-min-window and --cmn-norm-vars need it)\n");
+            return 2;
+        }
+        if (o.cmn_center != 0 && o.cmn_center != 1) {
+            std::fprintf(stderr, "--cmn-center must be 0 or 1\n");
+            return 2;
+        }
+        if (o.cmn_min_window == -1) o.cmn_min_window = std::min(100, o.cmn_window);
+        if (o.cmn_min_window < 0 || o.cmn_min_window > o.cmn_window) {
+            std::fprintf(stderr, "--cmn-min-window must be 0 .. --cmn-window\n");
+            return 2;
+        }
+        if (o.norm != 0) {
+            std::fprintf(stderr, "--cmn-window replaces the other normalisers, it does not stack on them: it needs --norm 0\n");
+            return 2;
+        }
+        if (o.method == MFX_METHOD_STFT_LOGMEL) {
+            std::fprintf(stderr, "--cmn-window is not served with --method LOGMEL\n");
+            return 2;
+        }
+        if (o.batch_mb <= 0) {
+            std::fprintf(stderr, "--cmn-window runs in batches of whole files: --batch-mb must be positive\n");
+            return 2;
+        }
+        if (!o.spk_file.empty() || o.online_window != -1) {
+            std::fprintf(stderr, "--cmn-window excludes --spk-file and --online-window: one normaliser per run\n");
             return 2;
         }
     }

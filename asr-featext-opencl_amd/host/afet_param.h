@@ -124,6 +124,9 @@ public:
     // online (causal, sliding-window) CMN / CVN of the planned batch (mfx_batch_set_online_norm): window in frames (0:
     // cumulative), the prior's reach and its accumulators [2][Wn] (nullptr with count 0: none); the next batch_plan clears it
     void batch_set_online_norm(int window, int prior_frames, long long prior_count = 0, const double *prior_acc = nullptr);
+    // sliding-window CMN / CVN of the planned batch (mfx_batch_set_sliding_norm; norm = NONE handles): window and min_window in
+    // frames, center and norm_vars 0 / 1; the next batch_plan clears it
+    void batch_set_sliding_norm(int window, int min_window, int center, int norm_vars);
     // energy VAD + voiced-frame selection as the last stage of the planned batch's runs (mfx_batch_set_vad; mode MFX_VAD_*);
     // the next batch_plan clears it, and so does batch_clear_vad
     void batch_set_vad(int column, float energy_threshold, float energy_mean_scale, int frames_context, float proportion_threshold,

@@ -245,6 +245,11 @@ void MfccHip::batch_set_online_norm(int window, int prior_frames, long long prio
     check(mfx_batch_set_online_norm(m_handle, window, prior_frames, (int64_t)prior_count, prior_acc));
 }
 
+void MfccHip::batch_set_sliding_norm(int window, int min_window, int center, int norm_vars)
+{
+    check(mfx_batch_set_sliding_norm(m_handle, window, min_window, center, norm_vars));
+}
+
 void MfccHip::batch_set_vad(int column, float energy_threshold, float energy_mean_scale, int frames_context, float proportion_threshold,
                             int mode)
 {

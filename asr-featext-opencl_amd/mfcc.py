@@ -89,6 +89,7 @@ EXPORTED_SYMBOLS = (
     "mfx_batch_set_vad", "mfx_batch_clear_vad", "mfx_batch_vad_read", "mfx_batch_vad_device",
     "mfx_batch_set_online_norm", "mfx_batch_clear_online_norm", "mfx_sessions_set_online_norm",
     "mfx_sessions_clear_online_norm", "mfx_host_online_norm",
+    "mfx_batch_set_sliding_norm", "mfx_batch_clear_sliding_norm", "mfx_host_sliding_window", "mfx_host_sliding_norm",
     "mfx_host_slaney_mel_table", "mfx_host_stft_basis", "mfx_host_stft_frame_count",
     "mfx_host_stft_lds_bytes", "mfx_host_session_stft_step", "mfx_host_sess_stft_lds_bytes",
     "mfx_host_stft_fft_tables", "mfx_host_stft_fft_lds_bytes",
@@ -222,6 +223,10 @@ def load_library():
     L.mfx_sessions_set_online_norm.argtypes = [vp, i32, i32, i64, dp]
     L.mfx_sessions_clear_online_norm.argtypes = [vp]
     L.mfx_host_online_norm.argtypes = [fp, i64, i32, i32, i32, i32, i32, i64, dp, fp]
+    L.mfx_batch_set_sliding_norm.argtypes = [vp, i32, i32, i32, i32]
+    L.mfx_batch_clear_sliding_norm.argtypes = [vp]
+    L.mfx_host_sliding_window.argtypes = [i64, i32, i32, i32, i64, C.POINTER(i64), C.POINTER(i64)]
+    L.mfx_host_sliding_norm.argtypes = [fp, i64, i32, i32, i32, i32, i32, i32, fp, i32]
     L.mfx_host_slaney_mel_table.argtypes = [i32, i32, C.c_float, C.c_float, C.c_float, fp, p32, p32]
     L.mfx_host_stft_basis.argtypes = [i32, fp, fp]
     L.mfx_host_stft_frame_count.argtypes, L.mfx_host_stft_frame_count.restype = [i64, i32, i32], i64
@@ -421,6 +426,31 @@ def host_online_norm(rows, kind, window=0, prior_frames=0, prior_count=0, prior_
                                 None if pa is None else pa.ctypes.data_as(C.POINTER(C.c_double)), out.ctypes.data_as(fpt))
     if rc != 0:
         raise MfxError(int(rc), "mfx_host_online_norm failed")
+    return out
+
+
+def host_sliding_window(T, window, min_window, center, t):
+    """The window [ws, we) of row t of an utterance of T rows under batch_set_sliding_norm (host code, no GPU needed)."""
+    ws, we = C.c_int64(0), C.c_int64(0)
+    rc = load_library().mfx_host_sliding_window(int(T), int(window), int(min_window), int(center), int(t), C.byref(ws), C.byref(we))
+    if rc != 0:
+        raise MfxError(int(rc), "mfx_host_sliding_window failed")
+    return ws.value, we.value
+
+
+def host_sliding_norm(rows, window=600, min_window=100, center=False, norm_vars=False):
+    """The sliding-window normaliser of batch_set_sliding_norm on host memory, exactly as include/mfx.h defines it (host code,
+    no GPU needed): rows [T][W] float32 -> [T][W]."""
+    x = np.ascontiguousarray(rows, dtype=np.float32)
+    if x.ndim != 2:
+        raise ValueError("rows must be [T][W]")
+    T, W = x.shape
+    out = np.zeros((T, W), np.float32)
+    fpt = C.POINTER(C.c_float)
+    rc = load_library().mfx_host_sliding_norm(x.ctypes.data_as(fpt), T, W, W, int(window), int(min_window), int(center), int(norm_vars),
+                                              out.ctypes.data_as(fpt), W)
+    if rc != 0:
+        raise MfxError(int(rc), "mfx_host_sliding_norm failed")
     return out
 
 
@@ -1254,6 +1284,19 @@ class MfccHip:
         self._chk(self._L.mfx_sessions_clear_online_norm(self._h))
 
     host_online_norm = staticmethod(host_online_norm)
+
+    def batch_set_sliding_norm(self, window=600, min_window=100, center=False, norm_vars=False):
+        """Sliding-window CMN / CVN of the planned batch (mfx_batch_set_sliding_norm; the defaults are apply-cmvn-sliding's):
+        every row of a norm = NONE handle is normalised with the statistics of `window` rows of its utterance around it
+        (center) or behind it, between the rows y and the transform; the VAD keeps deciding on the raw rows.  A later
+        batch_plan clears it."""
+        self._chk(self._L.mfx_batch_set_sliding_norm(self._h, int(window), int(min_window), int(bool(center)), int(bool(norm_vars))))
+
+    def batch_clear_sliding_norm(self):
+        self._chk(self._L.mfx_batch_clear_sliding_norm(self._h))
+
+    host_sliding_window = staticmethod(host_sliding_window)
+    host_sliding_norm = staticmethod(host_sliding_norm)
 
     def batch_set_vad(self, column=-1, energy_threshold=5.0, energy_mean_scale=0.5, frames_context=0,
                       proportion_threshold=0.6, mode=VAD_FLAGS):

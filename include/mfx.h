@@ -562,12 +562,60 @@ int mfx_sessions_set_online_norm(mfx_handle *h, int32_t window, int32_t prior_fr
                                  const double *prior_acc /* [2][Wn] or NULL */);
 int mfx_sessions_clear_online_norm(mfx_handle *h);
 
+/* Sliding-window CMN / CVN of the batch entries ("Sliding-window normalisation"): apply-cmvn-sliding of a
+ * Kaldi-style recipe -- a mean (optionally a variance) over a window of a few hundred frames around every row, centred or
+ * trailing -- the normaliser of the speaker-recognition recipes (compute-mfcc-feats, compute-vad-energy, apply-cmvn-sliding
+ * --center=true --cmn-window=300, select-voiced-frames).  The definition below is restated from Kaldi's SlidingWindowCmn
+ * (feature-functions.cc); AGREEMENT WITH A KALDI BINARY HAS NOT BEEN MEASURED (none is available to the build).  No
+ * reference analogue.  The online normaliser above cannot stand in for it: it is causal, its window is a multiple of 32 and
+ * it divides the variance by n - 1.
+ *   Rows.  For utterance u with T frames, y[t] is the row the transform and the VAD read today: width Wy =
+ *     mfx_batch_output_width WITHOUT a transform, pasted pitch columns included when a paste is in force.  Wy <= 256
+ *     (MFX_ERR_CONFIG beyond).  All Wy columns are normalised.  v = y[t][j]; q = (double)(float)(v * v), the product rounded
+ *     to float32 first (k_norm_stats' rule).
+ *   Window of row t (Kaldi's rule), N = window.  With center: ws = t - N div 2, we = ws + N.  Without it: ws = t - N,
+ *     we = t + 1 -- THE STEADY WINDOW THEN HOLDS N + 1 ROWS, as in Kaldi.  If ws < 0: we -= ws, ws = 0.  Without center:
+ *     we = max(t + 1, min_window); min_window is ignored with center, as in Kaldi.  If we > T: ws -= we - T, we = T,
+ *     ws = max(ws, 0).  n = we - ws; always 0 <= ws <= t < we <= T.
+ *   Sums.  P is the prefix chain the online normaliser defines above -- chunks of 32 rows from the utterance's first row, I,
+ *     Tot, O -- built on v and on q.  Sw = P[we - 1] - P[ws - 1] with P[-1] = 0 (the subtraction is done then too); Qw
+ *     likewise.  Every double operation is rounded on its own (no fused multiply-add).
+ *   Statistics and apply.  m = Sw / n, mean = (float)m, c = v - mean in float32.  CMN (norm_vars = 0): y = c.  With
+ *     norm_vars: if n == 1, y = +0.0f; else var = Qw / n - m * m (quotient, product and difference rounded separately), var
+ *     = 1e-10 when var < 1e-10, mult = (float)(1.0 / sqrt(var)) (square root and quotient rounded separately), y = c * mult
+ *     in float32.  This is Kaldi's population variance and its floor, not the online normaliser's n - 1.
+ *     The rows are an exact function of the utterance's rows and the four parameters: they do not depend on the other
+ *     utterances, the tiling, buffer placement, the run, or the device or host entry.
+ *   Scope.  Valid after mfx_batch_plan / mfx_batch_plan_rates (MFX_ERR_STATE before one); a later plan drops it with the other
+ *     attachments; mfx_batch_clear_sliding_norm puts the handle back on its previous kernels and bits.  MFX_ERR_CONFIG:
+ *     mfx_config.norm != MFX_NORM_NONE (this normaliser replaces the others, it does not stack on them), an STFT log-mel
+ *     handle, Wy > 256.  MFX_ERR_ARG: window outside 1 .. 4096, min_window outside 0 .. window, center or norm_vars other than
+ *     0 / 1.  MFX_ERR_DEVICE on a planning handle.  Everything is allocated HERE (the call waits for the handle's streams):
+ *     a handle-owned raw-row scratch [total_rows][Wy] (grown, never shrunk) and 16 bytes per 32-row chunk and column of
+ *     totals / offsets; mfx_batch_run_device still allocates nothing.  While it is in force a call that would change Wy
+ *     (mfx_batch_set_pitch_feats, mfx_batch_clear_pitch, mfx_batch_clear_pitch_feats) answers MFX_ERR_STATE, as under a
+ *     transform or a VAD.
+ *   Place in a run.  One more link, between the rows y and the transform: everything up to and including the pitch paste
+ *     writes the raw rows into the scratch; k_onorm_totals, k_onorm_offsets and k_slide_apply read them and write the
+ *     normalised rows where the rows y went before; the transform and the tensor output read the normalised rows.  The VAD's
+ *     decision reads the raw rows (see there).  The front end, MFX_ENGINE_* bits, alpha list, rates plan and
+ *     mfx_batch_overlap are unchanged; the launches go on the stream the tail runs on.  Utterances are independent:
+ *     mfx_batch_run_host keeps its sliced path.
+ * NOT served: the session entries and the streaming interface, which ignore it (a centred window needs N / 2 rows of
+ * look-ahead); stacking on another normaliser; windows beyond 4096. */
+int mfx_batch_set_sliding_norm(mfx_handle *h, int32_t window, int32_t min_window, int32_t center, int32_t norm_vars);
+int mfx_batch_clear_sliding_norm(mfx_handle *h);
+
 /* Energy voice-activity decision and voiced-frame selection as the last stage of a batch run ("Voice activity and
  * frame selection"): compute-vad-energy followed by select-voiced-frames of a Kaldi-style recipe, on the device, behind
  * everything else a run does.  No reference analogue: the reference hands every frame to its consumer.
  *   Input.  For utterance u with T frames, y[t] is the row the handle delivers today WITHOUT a transform: width Wd =
  *     mfx_get_output_data_width, normalised if normalisation is on (per utterance or per speaker).  e[t] = y[t][column];
  *     column = -1 means the last static column (c0 when want_c0).  A transform in force does not change what is read.
+ *     Nor does the sliding-window normaliser (mfx_batch_set_sliding_norm; norm = NONE handles only): it sits between the
+ *     rows y and the transform, so the decision reads the raw c0 or energy -- threshold and flags are what they are
+ *     without that attachment -- and SELECT / PACK move the finished, normalised rows.  That is the recipe's order
+ *     (compute-vad-energy on the raw features, apply-cmvn-sliding, select-voiced-frames).
  *   Threshold.  thr_u = (float)((double)energy_threshold + (double)energy_mean_scale * (S / T)), S = the sum of e[t] over
  *     all T rows in double: rows i, i + 256, ... of every 4096-row chunk by one owner in ascending order, a halving tree over
  *     the 256 owners, the chunks in ascending order.  No atomics: thr_u does not depend on the other utterances of the batch,
@@ -1104,6 +1152,13 @@ int32_t mfx_host_resample_tile(int32_t in_hz, int32_t out_hz, int32_t zeros, flo
  * written then).  Test / inspection aid. */
 int mfx_host_online_norm(const float *rows, int64_t T, int32_t pitch, int32_t Wn, int32_t kind, int32_t window,
                          int32_t prior_frames, int64_t prior_count, const double *prior_acc, float *out);
+/* The sliding-window normaliser (mfx_batch_set_sliding_norm) on host memory, exactly as defined there (no device needed).
+ * mfx_host_sliding_window: the window [*ws, *we) of row t of an utterance of T rows.  mfx_host_sliding_norm: rows [T][pitch],
+ * columns [0, W) -> out [T][out_pitch], 1 <= W <= 256.  MFX_ERR_ARG on anything outside the limits stated there, t outside
+ * [0, T) or a pitch below W (nothing is written then).  Test / inspection aid. */
+int mfx_host_sliding_window(int64_t T, int32_t window, int32_t min_window, int32_t center, int64_t t, int64_t *ws, int64_t *we);
+int mfx_host_sliding_norm(const float *rows, int64_t T, int32_t W, int32_t pitch, int32_t window, int32_t min_window,
+                          int32_t center, int32_t norm_vars, float *out, int32_t out_pitch);
 /* The pitch track (mfx_batch_set_pitch) on host memory, exactly as defined there, for ONE utterance: pcm holds its n samples
  * per channel (interleaved for channels = 2), T = its frames (mfx_batch_frames of n on the handle in question) at `shift`;
  * window as resolved (32 .. 1024, never 0).  Writes pitch [T][2], index [T], nccf [T][K]; any of them may be NULL.
